@@ -378,10 +378,40 @@ def run_other_config(n, device, rank, pk_threads, streams, subbatch=None):
         h.close()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_FIELDS = ("cand", "f0_idx", "h0_idx", "snr", "ttweak", "ftweak", "ipass", "ap", "method", "fine")
+
+
+def dump_outputs(out_dir, msgs, counts, suffix=""):
+    """--dump-outputs: the message lists of the last timed step (what a caller of the path receives: package_batch's messages and
+    per-frame counts) as .npy files, so that two builds can be compared output for output.  Only the `counts[f]` valid messages of
+    each frame are written, concatenated in frame order: msg_<field>.npy (float64, one value per message) for every numeric field
+    of the message record, msg_text.npy (float32 [n, 48]: the byte codes of the three 16-byte text fields), message_counts.npy and
+    frame_index.npy (float64, per dumped frame).  Beyond DUMP_LIMIT_BYTES in all a fixed seeded sample of frames is written, in
+    frame order."""
+    counts = np.asarray(counts, np.int64)
+    per_msg = 8 * len(DUMP_FIELDS) + 4 * 48
+    cost = 16 + per_msg * counts
+    if int(cost.sum()) <= DUMP_LIMIT_BYTES:
+        frames = np.arange(len(counts))
+    else:
+        order = np.random.default_rng(0).permutation(len(counts))
+        frames = np.sort(order[np.cumsum(cost[order]) <= DUMP_LIMIT_BYTES])
+    sel = np.concatenate([msgs[f, :counts[f]] for f in frames]) if len(frames) else msgs[:0, 0]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"frame_index": frames.astype(np.float64), "message_counts": counts[frames].astype(np.float64),
+              "msg_text": np.ascontiguousarray(sel["f"]).view(np.uint8).reshape(len(sel), 48).astype(np.float32)}
+    for k in DUMP_FIELDS:
+        arrays["msg_" + k] = sel[k].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return len(frames), len(sel)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="timed steps (default 100 = 0.5 s of config 1: the un-overlapped fetch + host layer of the LAST step, 1.3 ms, then weighs 0.3 % instead of 1.3 % at 20)")
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (default 100 = 0.5 s of config 1: the un-overlapped fetch + host layer of the LAST step, 1.3 ms, then weighs 0.3 %% instead of 1.3 %% at 20)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames", type=int, default=256, help="frames per GPU per step (BASELINE config 1: 256)")
     ap.add_argument("--total-frames", type=int, default=None, help="N > 1: shard THIS many frames per step over the ranks (contiguous blocks, "
@@ -426,7 +456,12 @@ def main():
                     "of up to a step); 1 = the round-4 loop (views of the result slot, one batch queued)")
     ap.add_argument("--min-seconds", type=float, default=3.0, help="after the K timed steps keep stepping (untimed for `value`, reported as "
                     "extra_steps) until the GPU has been busy this long, so that coarse GPU-activity samplers see the run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the message lists of the last one "
+                    "as DIR/<name>.npy (float32/float64, at most 64 MB: a fixed seeded sample of frames beyond that; dump_outputs); "
+                    "rank r > 0 of a multi-rank run writes its shard as <name>.rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     explicit = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
     if args.config is not None:
         preset = {1: dict(frames=256), 2: dict(frames=4096, bp_iters=30, osd=(30, 2)), 3: dict(frames=8192),
@@ -650,6 +685,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, msgs_, mc_, suffix=f".rank{rank}" if rank else "")
     step_gaps = np.diff(np.array([t0] + step_marks)) * 1e3 if step_marks else np.zeros(1)
     # keep the GPU busy for --min-seconds in total (identical steps, not part of `value`): a 0.16-s timed region is invisible to
     # a GPU-activity sampler with a period of seconds

@@ -268,25 +268,31 @@ def test_packed_results_edge_cases():
             h.close()
 
 
-def test_eight_ranks_one_gpu_gloo_uneven_total():
-    """What the 8-GPU node will run cold, at world size 8 on the one GPU of a test box (gloo; RCCL refuses several ranks per device):
-    bench.py's whole N > 1 flow with an UNEVEN total (8 x 16 + 3 frames: shard() gives the first three ranks one more), per-rank
+# Ranks of the multi-rank flow tests that share the one GPU of a test box: together with this pytest process (which holds the GPU
+# through the in-process tests) at most five processes have the device open -- a shared box allows six.
+WORLD_ONE_GPU = 4
+
+
+def test_four_ranks_one_gpu_gloo_uneven_total():
+    """What the 8-GPU node will run cold, at world size 4 on the one GPU of a test box (gloo; RCCL refuses several ranks per device):
+    bench.py's whole N > 1 flow with an UNEVEN total (4 x 16 + 3 frames: shard() gives the first three ranks one more), per-rank
     placement on pairwise-disjoint whole-core CPU sets, the packed gather inside every timed step with the frames arriving in shard
     order, value = all frames x steps / max-over-ranks time."""
-    total, steps = 8 * 16 + 3, 2
-    out = _launch(8, ["--backend", "gloo", "--total-frames", str(total), "--steps", str(steps), "--warmup", "1", "--no-host-entry", "--min-seconds", "0"],
+    W = WORLD_ONE_GPU
+    total, steps = W * 16 + 3, 2
+    out = _launch(W, ["--backend", "gloo", "--total-frames", str(total), "--steps", str(steps), "--warmup", "1", "--no-host-entry", "--min-seconds", "0"],
                   timeout=2400)
     assert out.returncode == 0, (out.stderr + out.stdout)[-4000:]
     d = _one_line(out)
-    assert d["n_gpus"] == 8 and d["steps"] == steps and d["scaling"] == "weak" and d["cpu_baseline"] is None and d["other_configs"] is None
+    assert d["n_gpus"] == W and d["steps"] == steps and d["scaling"] == "weak" and d["cpu_baseline"] is None and d["other_configs"] is None
     pr = d["per_rank"]
-    assert pr["frames"] == [17, 17, 17, 16, 16, 16, 16, 16]
-    assert all(len(pr[k]) == 8 for k in ("ms_per_step", "frames_per_s", "kernel_only_frames_per_s", "placement"))
-    # per-rank clocks stop BEFORE the closing barrier (a gloo barrier of 8 processes: milliseconds, against two short steps), `value` after it
+    assert pr["frames"] == [17, 17, 17] + [16] * (W - 3)
+    assert all(len(pr[k]) == W for k in ("ms_per_step", "frames_per_s", "kernel_only_frames_per_s", "placement"))
+    # per-rank clocks stop BEFORE the closing barrier (a gloo barrier of W processes: milliseconds, against two short steps), `value` after it
     assert d["value"] <= 1.001 * total / (max(pr["ms_per_step"]) * 1e-3) and d["ms_per_step"] >= max(pr["ms_per_step"]) - 1e-3
     assert abs(d["value"] - total / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
     g = pr["gather"]
-    assert g["ok"] and "packed results of 8 ranks gathered to rank 0 over gloo inside every timed step" in d["config"]["gather"], d["config"]["gather"]
+    assert g["ok"] and f"packed results of {W} ranks gathered to rank 0 over gloo inside every timed step" in d["config"]["gather"], d["config"]["gather"]
     assert "every rank's frames arrived in shard order" in d["config"]["gather"]
     # placement: every rank pinned to its own CPUs; hardware threads of one core never split between two ranks
     sets = []
@@ -297,9 +303,9 @@ def test_eight_ranks_one_gpu_gloo_uneven_total():
             a, _, b = part.partition("-")
             cpus |= set(range(int(a), int(b or a) + 1))
         sets.append(cpus)
-    if len(set().union(*sets)) >= 16:                  # (a box with fewer cores than ranks cannot give disjoint slices)
-        for i in range(8):
-            for j in range(i + 1, 8):
+    if len(set().union(*sets)) >= 2 * W:               # (a box with fewer cores than ranks cannot give disjoint slices)
+        for i in range(W):
+            for j in range(i + 1, W):
                 assert not (sets[i] & sets[j]), (i, j, pr["placement"][i], pr["placement"][j])
         for i, cs in enumerate(sets):
             for c in cs:
@@ -311,28 +317,29 @@ def test_eight_ranks_one_gpu_gloo_uneven_total():
                 for part in sib.split(","):
                     a, _, b = part.partition("-")
                     sibs |= set(range(int(a), int(b or a) + 1))
-                assert not any(sibs & sets[j] for j in range(8) if j != i), (i, c, sib)
+                assert not any(sibs & sets[j] for j in range(W) if j != i), (i, c, sib)
 
 
 def test_a_straggler_does_not_slow_the_other_ranks():
-    """No cross-rank rendezvous inside the steps: eight ranks over gloo on one GPU, rank 5 sleeps 20 ms on the host
+    """No cross-rank rendezvous inside the steps: four ranks over gloo on one GPU, rank 2 sleeps 20 ms on the host
     in every step.  Its own steps take >= 20 ms; every other sending rank keeps its own pace -- each rank only waits for its OWN sends,
     and rank 0's ring (depth >= the number of batches) never fills.  With round 4's per-step all_gather of the byte counts all eight
     clocks were the straggler's.  (Rank 0 is left out: its clock includes draining the last batch of every rank.)"""
+    W, slow = WORLD_ONE_GPU, 2
     steps, delay = 16, 20.0
     common = ["--backend", "gloo", "--frames", "8", "--steps", str(steps), "--warmup", "2", "--no-host-entry", "--min-seconds", "0",
               "--gather-depth", "32"]
-    out = _launch(8, common + ["--delay-rank", "5", "--delay-ms", str(delay)], timeout=2400)
+    out = _launch(W, common + ["--delay-rank", str(slow), "--delay-ms", str(delay)], timeout=2400)
     assert out.returncode == 0, (out.stderr + out.stdout)[-4000:]
     d = _one_line(out)
     ms = d["per_rank"]["ms_per_step"]
     assert d["per_rank"]["gather"]["ok"] and "every rank's frames arrived in shard order" in d["config"]["gather"], d["config"]["gather"]
-    others = [ms[r] for r in range(1, 8) if r != 5]
-    assert ms[5] >= delay, ms
-    assert max(others) < ms[5] - 0.5 * delay, ms                           # they did not inherit the straggler's 20 ms
+    others = [ms[r] for r in range(1, W) if r != slow]
+    assert ms[slow] >= delay, ms
+    assert max(others) < ms[slow] - 0.5 * delay, ms                           # they did not inherit the straggler's 20 ms
     ph = d["per_rank"]["gather"]["submit_phases_ms_by_rank"]
-    assert all(ph[r]["sizes"] < 1.0 and ph[r]["wait_slot"] < 0.25 * delay for r in range(1, 8)), ph      # no rank waited for another's batch
-    assert abs(d["value"] - 8 * 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and d["ms_per_step"] >= ms[5] - 1e-3
+    assert all(ph[r]["sizes"] < 1.0 and ph[r]["wait_slot"] < 0.25 * delay for r in range(1, W)), ph      # no rank waited for another's batch
+    assert abs(d["value"] - W * 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and d["ms_per_step"] >= ms[slow] - 1e-3
 
 
 def test_bench_gpus_flag_starts_the_launcher_itself():

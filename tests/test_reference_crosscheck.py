@@ -7,8 +7,8 @@ lists in emit order, SNR/dt/frequency strings, decode notes and the complete unp
 
 It needs /root/reference (~3 s per frame).  A fixed subset of eight frames -- four recipes at Receiver defaults / non-default kwargs
 and four with time windows far beyond the default, where symbols are read clamped -- runs whenever the reference is present
-(test_default_subset: part of the plain CPU suite in the build container, skipped on a box without /root/reference); the large runs
-are on request:
+(test_default_subset: part of the plain CPU suite everywhere -- it compares the oracle with the reference's traces of these frames,
+stored in tests/golden/crosscheck/ by oracle/gen_golden_crosscheck.py, so it needs no reference tree); the large runs are on request:
     PYFT8_REF_CROSSCHECK=1000 PYFT8_REF_LOG=lines.txt python -m pytest tests/test_reference_crosscheck.py -q -m ref -n 7
 """
 import os
@@ -65,12 +65,46 @@ def test_oracle_equals_reference_on_fresh_frame(k):
     crosscheck_frame(k, RECIPES[k % len(RECIPES)], KWARGS[k % len(KWARGS)], BASE)
 
 
-@needs_ref
-@pytest.mark.parametrize("which,k", [("std", 0), ("std", 1), ("std", 3), ("std", 9), ("time", 0), ("time", 1), ("time", 2), ("time", 3), ("far", 0), ("far", 1)])
+DEFAULT_SUBSET = [("std", 0), ("std", 1), ("std", 3), ("std", 9), ("time", 0), ("time", 1), ("time", 2), ("time", 3), ("far", 0), ("far", 1)]
+GOLDEN_TRACES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crosscheck")
+
+
+def stored_trace(which, k):
+    """The reference's trace of one DEFAULT_SUBSET frame as oracle/gen_golden_crosscheck.py stored it, with the attributes of
+    ref_harness.Trace that crosscheck_frame reads."""
+    import json
+    from types import SimpleNamespace
+    z = np.load(os.path.join(GOLDEN_TRACES, f"{which}_{k}.npz"))
+    meta = json.loads(str(z["meta"]))
+    fine, rows = {}, iter(range(len(z["fine_llr"])))
+    for e in meta["fine"]:
+        r = next(rows) if fine_arrays_read(e["stopped"], meta["final"][e["idx"]]["h0_idx"]) else None
+        fine[e["idx"]] = dict(tweaks=e["tweaks"], stopped=e["stopped"], llr=None if r is None else z["fine_llr"][r],
+                              signal_grid=None if r is None else z["fine_sgrid"][r])
+    # osd_012 inputs: a row whose osd_base is a fine row r is that row with osd_ndiff entries replaced (the a-priori bits of an AP
+    # pattern), the positions and values taken in order from osd_pos / osd_val; osd_base -1 = the next full row of osd_llr
+    osd, full, at = [], iter(z["osd_llr"]), 0
+    for e, base, n in zip(meta["osd"], z["osd_base"], z["osd_ndiff"]):
+        if base < 0:
+            llr = next(full)
+        else:
+            llr = z["fine_llr"][base].copy()
+            llr[z["osd_pos"][at:at + n]] = z["osd_val"][at:at + n]
+            at += n
+        osd.append(dict(e, llr_in=llr))
+    return SimpleNamespace(
+        final=meta["final"], fine=fine,
+        bp_calls=[dict(cand=c, ipass=0, ap="NoAP", llr_in=llr) for c, llr in zip(meta["bp_cand"], z["bp_llr"])],
+        osd_calls=osd,
+        unpack_calls=[(int(bits, 16), True if valid else None, cand, ipass) for bits, valid, cand, ipass in meta["unpack"]],
+        messages=meta["messages"])
+
+
+@pytest.mark.parametrize("which,k", DEFAULT_SUBSET)
 def test_default_subset(which, k):
     """Not env-gated: a future edit of the arithmetic contract cannot drift from receiver.py:140-206 / decoders.py:223-272
-    unnoticed -- every run of the CPU suite in the build container decodes these eight frames with the real reference."""
-    crosscheck_frame(*frame_of_set(which, k))
+    unnoticed -- every run of the CPU suite checks the oracle on these ten frames against the real reference's stored traces."""
+    crosscheck_frame(*frame_of_set(which, k), tr=stored_trace(which, k))
 
 
 def _summary_worker(item):
@@ -103,6 +137,18 @@ def test_residual_classes_are_pinned():
     assert tot["osd_calls"] > 5000, tot
 
 
+def far_out(h0):
+    """A candidate whose every read of the middle Costas block is clamped to one position (a search_time_range beyond -7.3 .. +9.6 s):
+    crosscheck_frame compares only its fine-sync tweaks."""
+    return h0 <= -169 or h0 >= 253
+
+
+def fine_arrays_read(stopped, h0):
+    """Whether crosscheck_frame reads a fine-sync candidate's LLRs and signal grid (fine_inputs_alike): not for a candidate the
+    reference stopped at the fine sync, nor for a far-out one -- the stored traces keep these arrays for the others only."""
+    return not stopped and not far_out(h0)
+
+
 def row_structure(sgrid):
     """The groups of bit-identical rows of a 79 x 8 fine-sync grid as a canonical labelling (first occurrence order).  Symbols whose
     first sample clip() moves to the same position read the same 32 samples (receiver.py:189-195): identical rows, hence exact |LLR|
@@ -114,13 +160,15 @@ def row_structure(sgrid):
     return out
 
 
-def crosscheck_frame(k, recipe, kw, BASE):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    from ref_harness import run_frame
+def crosscheck_frame(k, recipe, kw, BASE, tr=None):
+    """The oracle against the reference's trace `tr` of this frame (ref_harness.Trace); None = decode it with the live reference."""
     from pyft8_amd import synth
     from pyft8_amd.receiver import config_from_kwargs
     audio = synth.make_frame(BASE + k, **recipe)
-    cands, tr, rx = run_frame(audio, **kw)
+    if tr is None:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+        from ref_harness import run_frame
+        _, tr, _ = run_frame(audio, **kw)
     cfg = config_from_kwargs(**kw)
     ocfg = O.default_config(sync_score_min=cfg.sync_score_min, max_cands=cfg.max_cands, f0_lo=cfg.f0_lo, f0_hi=cfg.f0_hi,
                             h0_lo=cfg.h0_lo, h0_hi=cfg.h0_hi)
@@ -150,7 +198,7 @@ def crosscheck_frame(k, recipe, kw, BASE):
         if ridx not in tr.fine:
             return False
         fo = O.fine(spec_o, kk[0], kk[1], ocfg)
-        if kk[1] <= -169 or kk[1] >= 253:
+        if far_out(kk[1]):
             # Far-out candidates (a search_time_range beyond -7.3 .. +9.6 s): every read of the middle Costas block is clamped to ONE
             # position for every tweak, the seven symbols are identical, and the score S1 + w6 S2 is 0 up to rounding (each tone is the
             # Costas tone of exactly one symbol: S2 = 6 S1, w6 = float32(-1/6)) -- the reference's choice of tweaks is the rounding noise
