@@ -9,8 +9,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FT8RX_LIB", os.path.join(HERE, "libft8rx.so"))   # FT8RX_LIB: A/B builds of the same ABI
-# the same source with the wide layouts (-DFT8RX_WIDE, include/ft8rx.h): search_freq_range up to 5900 Hz and up to 2048 candidates per
-# frame (max_cands > 256); loaded only when a config asks for either
+# the same source with the wide layouts (-DFT8RX_WIDE, include/ft8rx.h): search_freq_range up to 5900 Hz (and up to 2048 candidates per
+# frame, more than 1024 = every f0 bin of a range up to 3000 Hz); loaded only when a config asks for it
 LIB_PATH_WIDE = os.environ.get("FT8RX_LIB_WIDE", os.path.join(HERE, "libft8rx_wide.so"))
 SRC = os.path.join(HERE, "csrc", "ft8rx.hip")
 # second translation unit: the FFT kernels (k_fine, k_spectrogram), compiled with the ILP scheduling strategy -- 3.9 % / 3 % faster for
@@ -22,7 +22,7 @@ ILP_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-Wno-unused-result",
                "-Wno-unused-value", "-fPIC", "-shared"]
 
-NSAMP, GRID_ROWS, GRID_COLS, SPEC_BINS, MAX_CANDS, EVENT_CAP = 180000, 376, 976, 49152, 256, 512
+NSAMP, GRID_ROWS, GRID_COLS, SPEC_BINS, MAX_CANDS, EVENT_CAP = 180000, 376, 976, 49152, 1024, 512
 MIN_H0, MAX_H0 = -898, 578                          # FT8RX_MIN_H0 / FT8RX_MAX_H0: bounds of config.h0_lo / h0_hi = where the reference's own search stops
                                                     # indexing its 750-row grid (search_time_range -36.4 .. +22.6 s, receiver.py:346-347)
 MIN_H0_FD, MAX_H0_FD = -140, 220                    # FT8RX_MIN_H0_FD / _MAX_H0_FD: candidates inside take the frequency-domain fine sync
@@ -145,9 +145,9 @@ def build_variant(path, extra=(), ilp_flags=None):
 
 
 def lib(wide=False):
-    """The loaded library; wide=True -> the build with the wide layouts (Handle picks it when cfg.f0_hi > 960 or cfg.max_cands > 256).
-    The host-only entry points (tone encoder, hash tables, defaults) are the same code in both and are taken from the default one; the
-    message layer's capacity follows FT8RX_MAX_CANDS, so record arrays wider than 256 candidates are packaged by the wide build's copy."""
+    """The loaded library; wide=True -> the build with the wide layouts (Handle picks it when cfg.f0_hi > 960, or cfg.max_cands > 1024,
+    which only a range beyond 3000 Hz has bins for).  The host-only entry points (message layer, tone encoder, hash tables, defaults)
+    are the same code in both and are taken from the default one."""
     wide = bool(wide)
     if wide not in _libs:
         path = LIB_PATH_WIDE if wide else LIB_PATH
@@ -219,7 +219,7 @@ class Handle:
 
     def __init__(self, cfg=None, device=0, max_frames=1):
         self.cfg = cfg or default_config()
-        self.wide = self.cfg.f0_hi > MAX_F0 or self.cfg.max_cands > MAX_CANDS      # beyond 3000 Hz / 256 candidates: the wide build (include/ft8rx.h)
+        self.wide = self.cfg.f0_hi > MAX_F0 or self.cfg.max_cands > MAX_CANDS      # beyond 3000 Hz / 1024 candidates: the wide build (include/ft8rx.h)
         L = self._L = lib(self.wide)
         self.grid_cols, self.spec_bins = (GRID_COLS_WIDE, SPEC_BINS_WIDE) if self.wide else (GRID_COLS, SPEC_BINS)
         self.max_frames = int(max_frames)
@@ -718,7 +718,7 @@ def package_batch(rec, cnt, ev, evc, max_msgs=None, n_threads=None, table=None, 
         flags = np.zeros(B, np.int32)
     if n_threads is None:
         n_threads = min(32, os.cpu_count() or 1)
-    L = lib(mc > MAX_CANDS)
+    L = lib()
     L.ft8rx_package_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_int, C.c_void_p, C.c_void_p]
     rc = L.ft8rx_package_batch(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, int(B), int(mc), out.ctypes.data,
@@ -827,7 +827,7 @@ def package_packed(buf, frame_lo=0, n_frames=None, max_msgs=None, n_threads=None
     oc = np.zeros(max(n, 0), np.int32)
     flags = np.zeros(max(n, 0), np.int32)
     if n > 0:
-        L = lib(pk.max_cands > MAX_CANDS)
+        L = lib()
         L.ft8rx_package_packed.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         rc = L.ft8rx_package_packed(pk.buf.ctypes.data, C.c_uint64(pk.nbytes), int(frame_lo), n, out.ctypes.data, int(max_msgs), oc.ctypes.data,
                                     int(n_threads or min(32, os.cpu_count() or 1)), table._t if table is not None else None, flags.ctypes.data)

@@ -32,7 +32,6 @@
 #include "../../include/ft8rx.h"
 #include "ft8_dev.h"
 
-#define MAXC FT8RX_MAX_CANDS
 #define WL_MULT(i) ((i) == WL_BP0 ? 5 : (i) == WL_OSDNAN ? 10 : 1)      /* entries per candidate slot of work list i */
 #define NF0MAX (FT8RX_MAX_F0 > 1024 ? 2048 : 1024)     /* per-frame stride of the per-f0 sync results; k_topk sorts this many keys */
 
@@ -108,7 +107,7 @@ struct ft8rx_handle {
     cpx *d_A, *d_spec;
     ft8rx_event* d_ev; int32_t* d_evcount;
     const uint32_t* d_trials; int n_trials;      // OSD trial list of this configuration
-    int32_t* d_work[WL_N];                       // ladder work lists (kernels/common.hpp: WorkList), [B][MAXC] candidate ids each
+    int32_t* d_work[WL_N];                       // ladder work lists (kernels/common.hpp: WorkList), [B][stride] candidate ids each
     int32_t* d_wcount;                           // [16 chunks][WL_N] list lengths, zeroed at the head of every chunk's chain
     uint8_t* d_colmask; bool use_mask;           // [B][NF0MAX] search mask of the local re-search (ft8rx_set_search_mask), allocated on first use
     // Result slots.  A batch writes its records/events into slot k % 2 (slot 0 = d_rec/d_ncand/d_ev/d_evcount above) and, when its
@@ -274,7 +273,8 @@ int ft8rx_build_info(int32_t* grid_cols, int32_t* spec_bins, int32_t* max_f0) {
     return 0;
 }
 int ft8rx_build_limits(int32_t* max_cands, int32_t* event_cap) {
-    static_assert(MAXC % 256 == 0 && MAXC <= NF0MAX, "candidate stride: whole 256-thread blocks, never more than k_topk has keys");
+    static_assert(FT8RX_MAX_CANDS <= NF0MAX && (1 << cand_shift(FT8RX_MAX_CANDS)) == FT8RX_MAX_CANDS,
+                  "max_cands: never more than k_topk has keys, and the largest candidate stride is the limit itself");
     if (max_cands) *max_cands = FT8RX_MAX_CANDS;
     if (event_cap) *event_cap = FT8RX_EVENT_CAP;
     return 0;
@@ -321,7 +321,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
 
 int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_handle** out) {
     if (!cfg || !out || max_frames < 1) { set_err(nullptr, "ft8rx_create: bad arguments"); return -1; }
-    if (cfg->max_cands < 1 || cfg->max_cands > MAXC || cfg->f0_lo < 4 || cfg->f0_hi > FT8RX_MAX_F0 || cfg->f0_lo >= cfg->f0_hi ||
+    if (cfg->max_cands < 1 || cfg->max_cands > FT8RX_MAX_CANDS || cfg->f0_lo < 4 || cfg->f0_hi > FT8RX_MAX_F0 || cfg->f0_lo >= cfg->f0_hi ||
         cfg->h0_hi <= cfg->h0_lo || cfg->h0_lo < FT8RX_MIN_H0 || cfg->h0_hi > FT8RX_MAX_H0 || cfg->bp_nc0_a > cfg->bp_nc0_b || cfg->bp_iters_a > cfg->bp_iters_b ||
         cfg->osd_single < 0 || cfg->osd_single > OSD_MAXFLIP || cfg->osd_double < 0 || cfg->osd_double > OSD_MAXFLIP ||
         cfg->osd_triple < 0 || cfg->osd_triple > 40 || cfg->osd_max_hd < 0 || cfg->osd_max_hd > 174 ||
@@ -346,31 +346,31 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     for (int k = 0; k < 2; k++) { h->h_pkhdr[k] = nullptr; h->d_pkhdr[k] = nullptr; h->slot_packed[k] = false; h->pk_fence[k] = nullptr; }
     h->d_zdec = nullptr; h->d_model = nullptr; h->d_adec = nullptr; h->d_subctx = nullptr; h->d_ones = nullptr;
     if (hipSetDevice(device) != hipSuccess || !(h->stream = pool_stream(device, &StreamPool::main, true))) { set_err(nullptr, "ft8rx_create: cannot open device %d", device); delete h; return -2; }
-    const size_t B = (size_t)max_frames;
+    const size_t B = (size_t)max_frames, S = (size_t)1 << cand_shift(*cfg);      // S: per-frame stride of the per-candidate workspaces
     int rc = 0;
     rc |= dalloc(h, &h->d_grid, B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS);
     rc |= dalloc(h, &h->d_best_score, B * NF0MAX);
     rc |= dalloc(h, &h->d_best_h0, B * NF0MAX);
-    rc |= dalloc(h, &h->d_rec, B * MAXC);
+    rc |= dalloc(h, &h->d_rec, B * S);
     rc |= dalloc(h, &h->d_ncand, B);
-    rc |= dalloc(h, &h->d_llr0, B * MAXC * 174);
-    rc |= dalloc(h, &h->d_saved, B * MAXC * 5 * 174);
-    rc |= dalloc(h, &h->d_att0, B * MAXC * 5);
-    rc |= dalloc(h, &h->d_attG, B * MAXC * 2);
-    rc |= dalloc(h, &h->d_attB, B * MAXC * 5);
-    rc |= dalloc(h, &h->d_attO, B * MAXC * 10);
+    rc |= dalloc(h, &h->d_llr0, B * S * 174);
+    rc |= dalloc(h, &h->d_saved, B * S * 5 * 174);
+    rc |= dalloc(h, &h->d_att0, B * S * 5);
+    rc |= dalloc(h, &h->d_attG, B * S * 2);
+    rc |= dalloc(h, &h->d_attB, B * S * 5);
+    rc |= dalloc(h, &h->d_attO, B * S * 10);
     // The four-step scratch (768 KB per frame) and the cycle spectrum (393 KB; 768 KB in the wide build) live INSIDE the grid buffer: the
     // dB grid is dead once k_grid_llr has gathered the payloads, and the cycle FFT only starts after that (enqueue_chain places a chunk's
     // A and spectrum at the start of the chunk's own grid region; k_spectrogram rewrites the constant row 0 with every batch).  The
     // stage entry points use one of the three at a time.  -1.16 MB of HBM per frame.
     static_assert((size_t)(96000 + FT8RX_SPEC_BINS) * sizeof(cpx) <= (size_t)FT8RX_GRID_ROWS * FT8RX_GRID_COLS * sizeof(float), "scratch A + cycle spectrum fit a frame's grid");
     if (!rc) { h->d_A = reinterpret_cast<cpx*>(h->d_grid); h->d_spec = h->d_A + B * 96000; }
-    for (int i = 0; i < WL_N; i++) rc |= dalloc(h, &h->d_work[i], B * MAXC * WL_MULT(i));      // WL_BP0 / WL_OSDNAN list attempts
+    for (int i = 0; i < WL_N; i++) rc |= dalloc(h, &h->d_work[i], B * S * WL_MULT(i));      // WL_BP0 / WL_OSDNAN list attempts
     rc |= dalloc(h, &h->d_wcount, (size_t)16 * WL_N);
     rc |= dalloc(h, &h->d_ev, B * FT8RX_EVENT_CAP);
     rc |= dalloc(h, &h->d_evcount, B);
     h->s_rec[0] = h->d_rec; h->s_ncand[0] = h->d_ncand; h->s_ev[0] = h->d_ev; h->s_evcount[0] = h->d_evcount;
-    rc |= dalloc(h, &h->s_rec[1], B * MAXC);
+    rc |= dalloc(h, &h->s_rec[1], B * S);
     rc |= dalloc(h, &h->s_ncand[1], B);
     rc |= dalloc(h, &h->s_ev[1], B * FT8RX_EVENT_CAP);
     rc |= dalloc(h, &h->s_evcount[1], B);
@@ -545,18 +545,19 @@ static void launch_sync(const float* grid, float* bs, int32_t* bh, const ft8rx_c
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
     const ft8rx_config& c = h->cfg;
     const size_t F = (size_t)f0;
+    const int sh = cand_shift(c); const size_t S = (size_t)1 << sh, FS = F * S;        // candidate stride (ft8rx_create)
     const int16_t* audio = d_audio + F * FT8RX_NSAMP;
     float* grid = h->d_grid + F * FT8RX_GRID_ROWS * FT8RX_GRID_COLS;
     float* bs = h->d_best_score + F * NF0MAX; int32_t* bh = h->d_best_h0 + F * NF0MAX;
-    ft8rx_record* rec = h->s_rec[slot] + F * MAXC; int32_t* ncand = h->s_ncand[slot] + F;
-    float* llr0 = h->d_llr0 + F * MAXC * 174; float* saved = h->d_saved + F * MAXC * 5 * 174;
-    Att* att0 = h->d_att0 + F * MAXC * 5; Att* attG = h->d_attG + F * MAXC * 2; Att* attB = h->d_attB + F * MAXC * 5; Att* attO = h->d_attO + F * MAXC * 10;
+    ft8rx_record* rec = h->s_rec[slot] + FS; int32_t* ncand = h->s_ncand[slot] + F;
+    float* llr0 = h->d_llr0 + FS * 174; float* saved = h->d_saved + FS * 5 * 174;
+    Att* att0 = h->d_att0 + FS * 5; Att* attG = h->d_attG + FS * 2; Att* attB = h->d_attB + FS * 5; Att* attO = h->d_attO + FS * 10;
     cpx* A = reinterpret_cast<cpx*>(grid); cpx* spec = A + (size_t)B * 96000;      // inside this chunk's (by then dead) grid region, see ft8rx_create
     ft8rx_event* ev = h->s_ev[slot] + F * FT8RX_EVENT_CAP; int32_t* evc = h->s_evcount[slot] + F;
 #define STAGE(name) do { if (prof) { hipEventRecord(h->pev[h->pnames.size()], s); h->pnames.push_back(name); } } while (0)
     int32_t* wc = h->d_wcount + WL_N * chunk;                      // (evc and wc are zeroed by k_topk)
     WorkList wl[WL_N];
-    for (int i = 0; i < WL_N; i++) { wl[i].items = h->d_work[i] + F * MAXC * WL_MULT(i); wl[i].count = wc + i; }
+    for (int i = 0; i < WL_N; i++) { wl[i].items = h->d_work[i] + FS * WL_MULT(i); wl[i].count = wc + i; }
     STAGE("spectrogram");
     ft8rx_ilp_spectrogram(B, s, audio, grid, h->T);
     STAGE("sync");
@@ -565,11 +566,11 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     k_topk<<<B, 1024, 0, s>>>(bs, bh, rec, ncand, c, evc, wc, h->use_mask ? h->d_colmask + F * NF0MAX : nullptr);
     STAGE("grid_llr");
     k_grid_llr<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
-    k_worklist_att<<<(B * MAXC * 5 + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, wl[WL_BP0]);
+    k_worklist_att<<<(B * S * 5 + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_BP0]);
     STAGE("bp_grid");
     k_bp<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
     STAGE("select0");
-    k_select0<<<(B * MAXC + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, wl[WL_FINE]);
+    k_select0<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_FINE]);
     STAGE("cycle_fft");
     k_cyc_a<<<dim3(40, B), 256, 0, s>>>(audio, A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, s>>>(A, spec, h->T);
@@ -577,33 +578,33 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     ft8rx_ilp_fine(ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
     if (c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1)      // a search_time_range beyond -6.1 .. +8.3 s: the candidates k_fine leaves out
         k_fine_td<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
-    k_worklist<<<(B * MAXC + 255) / 256, 256, 0, s>>>(rec, ncand, B, wl[WL_BP1]);
+    k_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl[WL_BP1]);
     STAGE("bp_fine");
     // fine-stage BP: in ladder order (three launches; decided candidates drop out), or -- ft8rx_set_ladder_mode(h, 1), for small
     // batches where latency matters more than work -- all five variants in one launch: one dependent BP instead of three, same
     // records and messages (the event log then also holds entries of attempts the ladder would not have reached)
     if (h->ladder_mode == 0) {
         k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1);
-        k_select1<<<(B * MAXC + 255) / 256, 256, 0, s>>>(0, rec, ncand, attG, attB, B, c, wl[WL_BP1B]);
+        k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(0, rec, ncand, attG, attB, B, c, wl[WL_BP1B]);
         k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1);
-        k_select1<<<(B * MAXC + 255) / 256, 256, 0, s>>>(1, rec, ncand, attG, attB, B, c, wl[WL_BP1C]);
+        k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(1, rec, ncand, attG, attB, B, c, wl[WL_BP1C]);
         k_bp<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3);
         STAGE("select1");
-        k_select1<<<(B * MAXC + 255) / 256, 256, 0, s>>>(2, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
+        k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(2, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     } else {
         k_bp<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5);
         STAGE("select1");
-        k_select1<<<(B * MAXC + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
+        k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     }
     STAGE("osd");
     const bool osd_wide = osd_nflip(c.osd_single, c.osd_triple) > OSD_FLIPS_A;
     (osd_wide ? k_osd_wide : k_osd)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
-        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, wl[WL_OSD], wl[WL_OSDNAN]);
+        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
     // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
     (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, s>>>(
-        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, wl[WL_OSDNAN]);
+        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSDNAN]);
     STAGE("select2");
-    k_select2<<<(B * MAXC + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B);
+    k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
 }
@@ -756,14 +757,14 @@ static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* 
     h->slot_packed[slot] = h->pk_buf[slot] != nullptr;
     if (h->slot_packed[slot]) {                              // packed results for a gather: header | frame table | kept records | used events
         if (h->pk_fence[slot]) { HIPCHK(h, hipStreamWaitEvent(fin, h->pk_fence[slot], 0)); h->pk_fence[slot] = nullptr; }      // the consumer's asynchronous read of this buffer
-        k_pack_count<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ncand[slot], h->s_ev[slot], h->s_evcount[slot], h->d_pkneed, h->d_pknrec);
+        k_pack_count<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ncand[slot], h->s_ev[slot], h->s_evcount[slot], h->d_pkneed, h->d_pknrec, cand_shift(h->cfg));
         k_pack_scan<<<1, 1024, 0, fin>>>(h->d_pknrec, h->s_ncand[slot], h->s_evcount[slot], B, mc, (unsigned long long)h->pk_cap, h->pk_buf[slot], h->d_pkhdr[slot]);
-        k_pack_write<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ev[slot], h->d_pkneed, B, h->pk_buf[slot]);
+        k_pack_write<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ev[slot], h->d_pkneed, B, h->pk_buf[slot], cand_shift(h->cfg));
     }
     HIPCHK(h, hipEventRecord(h->ev_comp[slot], fin));
     if (!free_run) HIPCHK(h, hipStreamWaitEvent(h->copy_s, h->ev_comp[slot], 0));
     HIPCHK(h, hipMemcpyAsync(h->h_cnt[slot], h->s_ncand[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
-    HIPCHK(h, hipMemcpy2DAsync(h->h_rec[slot], sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) * MAXC,
+    HIPCHK(h, hipMemcpy2DAsync(h->h_rec[slot], sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) << cand_shift(h->cfg),
                                sizeof(ft8rx_record) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
     HIPCHK(h, hipMemcpyAsync(h->h_evc[slot], h->s_evcount[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
     // The event log is [B][FT8RX_EVENT_CAP] x 24 B = 12 KB per frame of which a frame typically uses a tenth (config 1: ~40 events).
@@ -895,7 +896,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
         if (!dev[k] || ((uintptr_t)dev[k] & 15)) { set_err(h, "ft8rx_set_packed_output: buffer %d is not device-accessible / 16-byte aligned", k); return -1; }
     }
     if (!h->d_pkneed) {
-        int rc = dalloc(h, &h->d_pkneed, (size_t)h->max_frames * PK_NW);
+        int rc = dalloc(h, &h->d_pkneed, (size_t)h->max_frames * ((1 << cand_shift(h->cfg)) / 64));      // k_pack_count's mask words
         rc |= dalloc(h, &h->d_pknrec, (size_t)h->max_frames);
         if (rc) return -2;
         for (int k = 0; k < 2; k++) {
@@ -932,7 +933,7 @@ int ft8rx_results_to_device(ft8rx_handle* h, int B, ft8rx_record* d_records, int
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int mc = h->cfg.max_cands;
     if (d_counts) HIPCHK(h, hipMemcpyAsync(d_counts, h->s_ncand[slot], sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
-    if (d_records) HIPCHK(h, hipMemcpy2DAsync(d_records, sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) * MAXC,
+    if (d_records) HIPCHK(h, hipMemcpy2DAsync(d_records, sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) << cand_shift(h->cfg),
                                               sizeof(ft8rx_record) * mc, B, hipMemcpyDeviceToDevice, h->stream));
     if (d_event_counts) HIPCHK(h, hipMemcpyAsync(d_event_counts, h->s_evcount[slot], sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
     if (d_events) HIPCHK(h, hipMemcpyAsync(d_events, h->s_ev[slot], sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToDevice, h->stream));
@@ -1002,11 +1003,12 @@ int ft8rx_sync_search(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx
     launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
     k_topk<<<B, 1024, 0, h->stream>>>(h->d_best_score, h->d_best_h0, h->d_rec, h->d_ncand, c, nullptr, nullptr, nullptr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::vector<ft8rx_record> rec((size_t)B * MAXC);
+    const size_t S = (size_t)1 << cand_shift(c);
+    std::vector<ft8rx_record> rec((size_t)B * S);
     HIPCHK(h, hipMemcpy(rec.data(), h->d_rec, sizeof(ft8rx_record) * rec.size(), hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(counts, h->d_ncand, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
     for (int f = 0; f < B; f++) for (int i = 0; i < c.max_cands; i++) {
-        const ft8rx_record& r = rec[(size_t)f * MAXC + i];
+        const ft8rx_record& r = rec[(size_t)f * S + i];
         size_t o = (size_t)f * c.max_cands + i;
         f0_idx[o] = r.f0_idx; h0_idx[o] = r.h0_idx; score[o] = r.score;
     }
@@ -1125,9 +1127,9 @@ int ft8rx_osd_ext(ft8rx_handle* h, const float* llr, int n, int singleflips, int
     const bool osd_wide = osd_nflip(singleflips, tripleflips) > OSD_FLIPS_A;
     (osd_wide ? k_osd_wide : k_osd)<<<n, 64, 0, h->stream>>>(
         2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd,
-        WorkList{nullptr, nullptr}, nanl);
+        cand_shift(h->cfg), WorkList{nullptr, nullptr}, nanl);
     (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, h->stream>>>(
-        2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd, nanl);
+        2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd, cand_shift(h->cfg), nanl);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<Att> a(n);
     HIPCHK(h, hipMemcpy(a.data(), d_att, sizeof(Att) * n, hipMemcpyDeviceToHost));

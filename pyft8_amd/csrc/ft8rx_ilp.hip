@@ -16,7 +16,6 @@
 #include "../../include/ft8rx.h"
 #include "ft8_dev.h"
 
-#define MAXC FT8RX_MAX_CANDS
 #define NF0MAX (FT8RX_MAX_F0 > 1024 ? 2048 : 1024)
 
 #include "kernels/common.hpp"

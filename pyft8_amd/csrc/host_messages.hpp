@@ -228,6 +228,10 @@ static bool ev_before(const Ev& a, const Ev& b) {          // the reference's ca
     if (a.slot != b.slot) return a.slot < b.slot;
     return a.seq < b.seq;
 }
+// Capacity of this layer: the largest max_cands of either build (libft8rx_wide.so), so both copies package any record width the
+// ABI allows.
+enum { PKG_MAX_CANDS = 2048 };
+static_assert(FT8RX_MAX_CANDS <= PKG_MAX_CANDS, "message layer capacity");
 // -> number of messages written (<= cap).  *flags: FT8RX_PKG_MSG_TRUNCATED if more than cap messages were emitted.
 // sparse = the records of a packed result buffer (include/ft8rx.h): only the candidates that decoded or logged an event, in candidate
 // order, each carrying its candidate index in pad2.  The replay never looks at any other candidate, and a stable sort orders a
@@ -235,14 +239,14 @@ static bool ev_before(const Ev& a, const Ev& b) {          // the reference's ca
 static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, int nev, ft8rx_message* out, int cap, Hashes& H, int* flags,
                          bool sparse = false) {
     std::vector<Ev> E; E.reserve((size_t)nev);
-    int16_t pos[FT8RX_MAX_CANDS];
+    int16_t pos[PKG_MAX_CANDS];
     if (sparse) {
-        for (int i = 0; i < FT8RX_MAX_CANDS; i++) pos[i] = -1;
-        for (int i = 0; i < n; i++) if (rec[i].pad2 < (uint32_t)FT8RX_MAX_CANDS) pos[rec[i].pad2] = (int16_t)i;
+        for (int i = 0; i < PKG_MAX_CANDS; i++) pos[i] = -1;
+        for (int i = 0; i < n; i++) if (rec[i].pad2 < (uint32_t)PKG_MAX_CANDS) pos[rec[i].pad2] = (int16_t)i;
     }
     for (int i = 0; i < nev; i++) {
         int c = ev[i].cand;
-        if (sparse) { c = c < FT8RX_MAX_CANDS ? pos[c] : -1; if (c < 0) continue; }
+        if (sparse) { c = c < PKG_MAX_CANDS ? pos[c] : -1; if (c < 0) continue; }
         E.push_back({c, ev[i].ipass, ev[i].slot, ev[i].seq, ev[i].msg_lo, ev[i].msg_hi});
     }
     std::sort(E.begin(), E.end(), ev_before);
@@ -372,7 +376,7 @@ static int package_packed(const void* packed, uint64_t bytes, int frame_lo, int 
         const ft8rx_packed_frame& t = tab[f];
         const int ne = t.n_ev > FT8RX_EVENT_CAP ? FT8RX_EVENT_CAP : (t.n_ev < 0 ? 0 : t.n_ev);
         if (t.rec_off < 0 || t.ev_off < 0 || (int64_t)t.rec_off + t.n_rec > hd.n_records || (int64_t)t.ev_off + ne > hd.n_events ||
-            t.n_rec > FT8RX_MAX_CANDS) return -1;
+            t.n_rec > PKG_MAX_CANDS) return -1;
     }
     if (n_threads < 1 || table) n_threads = 1;
     if (n_threads > n_frames) n_threads = n_frames;

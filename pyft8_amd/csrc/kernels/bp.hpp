@@ -39,13 +39,14 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
     // lanes' tanh values) -- 2.3 KB of LDS less per wave: bp_fine 0.719 -> 0.694 ms, bp_grid 0.171 -> 0.167 (profiles/archive/r03_notes.md)
     float* dl = tl;
     __shared__ float P[84];
-    int frame = 0, ci = 0, ap = 0; size_t vec;
+    int ap = 0; size_t vec;                   // modes 0 / 1: vec = the candidate (frame << cand_shift + ci)
     BT_DECL
     if (mode == 2) vec = bid;
     else {
-        ap = bid % 5; int c = bid / 5; frame = c / MAXC; ci = c % MAXC;
-        if (ci >= ncand[frame]) return;
-        if (rec[(size_t)frame * MAXC + ci].status != FT8RX_ST_ACTIVE) return;
+        const int sh = cand_shift(cfg);
+        ap = bid % 5; const int c = bid / 5;
+        if ((c & ((1 << sh) - 1)) >= ncand[c >> sh]) return;
+        if (rec[c].status != FT8RX_ST_ACTIVE) return;
         vec = (size_t)c;
     }
     {   // three loads in flight, then the AP override (ap_value around the load would branch over it: one round trip per basic block)
@@ -69,7 +70,7 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
             const uint64_t b1 = __ballot(lane < 27 && ap_value(g, 64 + lane, llr[64 + (lane < 27 ? lane : 0)]) > 0.0f);
             uint64_t lo, hi;
             const int r = ft8_crc_check_wave(b0, b1, lane, &lo, &hi);
-            if (r) { if (lane == 0) log_event(ev, evcount, frame, ci, 2, g, 0, lo, hi, r == 2); }
+            if (r) { if (lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), 2, g, 0, lo, hi, r == 2); }
             if (r == 2) { resG.ok = 1; resG.lo = lo; resG.hi = hi; resG.n_its = 0; resG.method = FT8RX_M_GOOD91; any = true; }
             if (lane == 0) attG[vec * 2 + g] = resG;
         }
@@ -105,7 +106,7 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
             int r = ft8_crc_check_wave(b0, b1, lane, &lo, &hi);
             if (r) {
                 int ipass = (mode == 0) ? 0 : ((ap < 2 && res.nc0 <= cfg.bp_nc0_a && it < cfg.bp_iters_a) ? 3 : 4);
-                if (lane == 0) log_event(ev, evcount, frame, ci, ipass, ap, it + 1, lo, hi, r == 2);
+                if (lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), ipass, ap, it + 1, lo, hi, r == 2);
             }
             if (r == 2) { res.ok = 1; res.lo = lo; res.hi = hi; res.n_its = (int16_t)it; res.has_out = 0; }
             break;      // success, or frozen state: the reference changes nothing from here on (decoders.py:161-164)
@@ -218,10 +219,10 @@ __global__ __launch_bounds__(64, BP_WV) void k_bp(int mode, const float* __restr
 }
 
 // first success in ladder order after ipass 0 (receiver.py:72-78)
-__global__ void k_select0(ft8rx_record* rec, const int32_t* ncand, const Att* att0, int B, WorkList next) {
+__global__ void k_select0(ft8rx_record* rec, const int32_t* ncand, const Att* att0, int B, int sh, WorkList next) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     bool go_on = false;
-    if (c < B * MAXC && (c % MAXC) < ncand[c / MAXC]) {
+    if (cand_live(c, B, sh, ncand)) {
         ft8rx_record& r = rec[c];
         if (r.status == FT8RX_ST_ACTIVE) {
             go_on = true;
@@ -235,16 +236,16 @@ __global__ void k_select0(ft8rx_record* rec, const int32_t* ncand, const Att* at
 }
 
 // work list of a ladder step = every candidate that is ACTIVE now (thread per candidate, one atomic per block)
-__global__ void k_worklist(const ft8rx_record* rec, const int32_t* ncand, int B, WorkList next) {
+__global__ void k_worklist(const ft8rx_record* rec, const int32_t* ncand, int B, int sh, WorkList next) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool on = c < B * MAXC && (c % MAXC) < ncand[c / MAXC] && rec[c].status == FT8RX_ST_ACTIVE;
+    const bool on = cand_live(c, B, sh, ncand) && rec[c].status == FT8RX_ST_ACTIVE;
     work_push_block(next, on, c);
 }
 
 // attempt list of the first BP: thread per (candidate, ap); pending = left open by bp0_precheck
-__global__ void k_worklist_att(const ft8rx_record* rec, const int32_t* ncand, const Att* att0, int B, WorkList next) {
+__global__ void k_worklist_att(const ft8rx_record* rec, const int32_t* ncand, const Att* att0, int B, int sh, WorkList next) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, c = i / 5;
-    const bool on = c < B * MAXC && (c % MAXC) < ncand[c / MAXC] && rec[c].status == FT8RX_ST_ACTIVE && att0[i].pad[1] != 0;
+    const bool on = cand_live(c, B, sh, ncand) && rec[c].status == FT8RX_ST_ACTIVE && att0[i].pad[1] != 0;
     work_push_block(next, on, i);
 }
 
@@ -260,7 +261,7 @@ FT8_DEV bool sel_take(ft8rx_record& r, const Att& a, int ipass, int ap, int meth
 __global__ void k_select1(int step, ft8rx_record* rec, const int32_t* ncand, const Att* attG, const Att* attB, int B, ft8rx_config cfg, WorkList next) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     bool go_on = false;
-    if (c < B * MAXC && (c % MAXC) < ncand[c / MAXC] && rec[c].status == FT8RX_ST_ACTIVE) {
+    if (cand_live(c, B, cand_shift(cfg), ncand) && rec[c].status == FT8RX_ST_ACTIVE) {
         ft8rx_record& r = rec[c];
         go_on = true;
         const Att* b = attB + (size_t)c * 5;
@@ -290,11 +291,9 @@ __global__ void k_select1(int step, ft8rx_record* rec, const int32_t* ncand, con
 }
 
 // ipass 5 (OSD on llr0+AP, slots 0..4) then ipass 6 (OSD on the saved BP outputs, slots 5..9)
-__global__ void k_select2(ft8rx_record* rec, const int32_t* ncand, const Att* attO, int B) {
+__global__ void k_select2(ft8rx_record* rec, const int32_t* ncand, const Att* attO, int B, int sh) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= B * MAXC) return;
-    int frame = c / MAXC, ci = c % MAXC;
-    if (ci >= ncand[frame]) return;
+    if (!cand_live(c, B, sh, ncand)) return;
     ft8rx_record& r = rec[c];
     if (r.status != FT8RX_ST_ACTIVE) return;
     for (int s = 0; s < 10; s++) {

@@ -30,10 +30,18 @@ __device__ __constant__ uint8_t d_PAYSYM[58] = {7,8,9,10,11,12,13,14,15,16,17,18
 // per frame for the second BP, 27 % for OSD, a few per cent in sparse low-SNR frames), so instead of one mostly-empty block per slot
 // a thread-per-candidate kernel (k_worklist, k_select0, k_select1) appends the candidates that go on to a compact list and the
 // consumer indexes list x attempts: k_fine and k_osd with a bounded grid whose blocks stride over the items, k_bp with one
-// attempt per block (its attempts are short and very uneven).  Entries are chunk-relative candidate ids (frame * MAXC + ci); the
+// attempt per block (its attempts are short and very uneven).  Entries are chunk-relative candidate ids (frame * stride + ci); the
 // order is whatever the atomics give -- every attempt writes its own result slot and the host sorts the event log, so results do
 // not depend on it.
 struct WorkList { int32_t* items; int32_t* count; };
+
+// Per-frame stride of the per-candidate workspaces (records, LLRs, attempt slots, work lists), as a shift: the smallest power of two
+// >= max_cands, at least 256 (whole 256-thread blocks) -- 256 at the default max_cands = 200.  Set by config.max_cands at create
+// time, so every frame / candidate split stays a shift and a mask.
+constexpr __host__ __device__ int cand_shift(int max_cands) { return max_cands <= 256 ? 8 : max_cands <= 512 ? 9 : max_cands <= 1024 ? 10 : 11; }
+constexpr __host__ __device__ int cand_shift(const ft8rx_config& c) { return cand_shift(c.max_cands); }
+// thread-per-candidate kernels: chunk-relative id c is a candidate slot of the batch that k_topk filled
+FT8_DEV bool cand_live(int c, int B, int sh, const int32_t* ncand) { return c < (B << sh) && (c & ((1 << sh) - 1)) < ncand[c >> sh]; }
 
 // XCD-aware block map for kernels whose blocks of one FRAME read the same memory (the frame's dB grid): consecutive workgroup ids go
 // round-robin over the 8 XCDs, each with an L2 of its own, so with the plain map (frame = id / per) the `per` blocks of a frame land on
@@ -161,39 +169,39 @@ __global__ __launch_bounds__(64) void k_ev_compact(const ft8rx_event* __restrict
 // block) turns the per-frame counts into offsets and the header, k_pack_write (a block per frame) moves the entries.
 // A frame in which any candidate has a NaN llr_sd keeps ALL its candidates: the replay orders candidates by a stable sort on llr_sd
 // (receiver.py:389), and with unordered keys the order of a subset need not be the order inside the full list.
-static_assert(MAXC % 256 == 0 && sizeof(ft8rx_record) == 48 && sizeof(ft8rx_event) == 24 && sizeof(ft8rx_packed_frame) == 16 &&
+static_assert(sizeof(ft8rx_record) == 48 && sizeof(ft8rx_event) == 24 && sizeof(ft8rx_packed_frame) == 16 &&
               sizeof(ft8rx_packed_header) == 32, "packed result layout");
-#define PK_NW (MAXC / 64)                       /* 64-candidate mask words per frame: 4 (libft8rx.so), 32 (wide build) */
+// need[] holds stride / 64 mask words per frame (64 candidates each); sh = cand_shift(cfg)
 __global__ __launch_bounds__(256) void k_pack_count(const ft8rx_record* __restrict__ rec, const int32_t* __restrict__ ncand,
                                                     const ft8rx_event* __restrict__ ev, const int32_t* __restrict__ evcount,
-                                                    uint64_t* __restrict__ need /*[B][PK_NW]*/, int32_t* __restrict__ nrec /*[B]*/) {
-    __shared__ uint32_t s_has[MAXC / 32];
-    __shared__ int s_cnt[PK_NW], s_nan;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    for (int i = tid; i < MAXC / 32; i += 256) s_has[i] = 0;
+                                                    uint64_t* __restrict__ need /*[B][stride / 64]*/, int32_t* __restrict__ nrec /*[B]*/, int sh) {
+    __shared__ uint32_t s_has[FT8RX_MAX_CANDS / 32];
+    __shared__ int s_cnt[FT8RX_MAX_CANDS / 64], s_nan;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, S = 1 << sh, nw = S >> 6;
+    for (int i = tid; i < S / 32; i += 256) s_has[i] = 0;
     if (tid == 0) s_nan = 0;
     __syncthreads();
     int c = evcount[f]; c = c > FT8RX_EVENT_CAP ? FT8RX_EVENT_CAP : (c < 0 ? 0 : c);
     for (int i = tid; i < c; i += 256) {
         const unsigned cand = ev[(size_t)f * FT8RX_EVENT_CAP + i].cand;
-        if (cand < (unsigned)MAXC) atomicOr(&s_has[cand >> 5], 1u << (cand & 31));
+        if (cand < (unsigned)S) atomicOr(&s_has[cand >> 5], 1u << (cand & 31));
     }
-    int n = ncand[f]; n = n > MAXC ? MAXC : (n < 0 ? 0 : n);
+    int n = ncand[f]; n = n > S ? S : (n < 0 ? 0 : n);
     for (int i = tid; i < n; i += 256) {
-        const ft8rx_record& r = rec[(size_t)f * MAXC + i];
+        const ft8rx_record& r = rec[((size_t)f << sh) + i];
         if (r.grid_sd != r.grid_sd || r.fine_sd != r.fine_sd) s_nan = 1;
     }
     __syncthreads();
 #pragma unroll 1
-    for (int q = 0; q < MAXC / 256; q++) {
+    for (int q = 0; q < S / 256; q++) {
         const int i = tid + 256 * q;
-        const bool decoded = i < n && rec[(size_t)f * MAXC + (i < n ? i : 0)].status == FT8RX_ST_DECODED;
+        const bool decoded = i < n && rec[((size_t)f << sh) + (i < n ? i : 0)].status == FT8RX_ST_DECODED;
         const bool want = i < n && (decoded || ((s_has[i >> 5] >> (i & 31)) & 1u) || s_nan);
         const uint64_t m = __ballot(want);
-        if (lane == 0) { need[(size_t)f * PK_NW + (i >> 6)] = m; s_cnt[i >> 6] = __popcll(m); }
+        if (lane == 0) { need[(size_t)f * nw + (i >> 6)] = m; s_cnt[i >> 6] = __popcll(m); }
     }
     __syncthreads();
-    if (tid == 0) { int t = 0; for (int w = 0; w < PK_NW; w++) t += s_cnt[w]; nrec[f] = t; }
+    if (tid == 0) { int t = 0; for (int w = 0; w < nw; w++) t += s_cnt[w]; nrec[f] = t; }
 }
 // offsets of every frame's records / events in the packed runs, the frame table and the header (also mirrored into page-locked
 // host memory, `hdr_host`, so that the host knows the size without a copy)
@@ -222,7 +230,7 @@ __global__ __launch_bounds__(1024) void k_pack_scan(const int32_t* __restrict__ 
         if (f < B && table_fits) {
             ft8rx_packed_frame t;
             t.rec_off = br + ir - r; t.ev_off = be + ie - e;
-            int n = ncand[f]; n = n > MAXC ? MAXC : (n < 0 ? 0 : n);
+            int n = ncand[f]; n = n > max_cands ? max_cands : (n < 0 ? 0 : n);
             t.n_cand = (uint16_t)n; t.n_rec = (uint16_t)r; t.n_ev = eraw < 0 ? 0 : eraw;
             table[f] = t;
         }
@@ -241,23 +249,23 @@ __global__ __launch_bounds__(1024) void k_pack_scan(const int32_t* __restrict__ 
     }
 }
 __global__ __launch_bounds__(256) void k_pack_write(const ft8rx_record* __restrict__ rec, const ft8rx_event* __restrict__ ev,
-                                                    const uint64_t* __restrict__ need, int B, unsigned char* __restrict__ buf) {
+                                                    const uint64_t* __restrict__ need, int B, unsigned char* __restrict__ buf, int sh) {
     const ft8rx_packed_header hd = *reinterpret_cast<const ft8rx_packed_header*>(buf);
     if (hd.overflow) return;
-    __shared__ int s_pre[PK_NW];                                       // kept records in the mask words before word w
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    __shared__ int s_pre[FT8RX_MAX_CANDS / 64];                        // kept records in the mask words before word w
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, S = 1 << sh, nw = S >> 6;
     const ft8rx_packed_frame t = reinterpret_cast<const ft8rx_packed_frame*>(buf + sizeof(ft8rx_packed_header))[f];
     unsigned char* recs = buf + sizeof(ft8rx_packed_header) + (size_t)B * sizeof(ft8rx_packed_frame);
     unsigned char* evs = recs + (size_t)hd.n_records * sizeof(ft8rx_record);
-    if (tid == 0) { int a = 0; for (int w = 0; w < PK_NW; w++) { s_pre[w] = a; a += __popcll(need[(size_t)f * PK_NW + w]); } }
+    if (tid == 0) { int a = 0; for (int w = 0; w < nw; w++) { s_pre[w] = a; a += __popcll(need[(size_t)f * nw + w]); } }
     __syncthreads();
 #pragma unroll 1
-    for (int q = 0; q < MAXC / 256; q++) {
+    for (int q = 0; q < S / 256; q++) {
         const int i = tid + 256 * q;
-        const uint64_t mine = need[(size_t)f * PK_NW + (i >> 6)];
+        const uint64_t mine = need[(size_t)f * nw + (i >> 6)];
         if ((mine >> lane) & 1ull) {
             const int p = s_pre[i >> 6] + __popcll(mine & ((1ull << lane) - 1));
-            const uint4* src = reinterpret_cast<const uint4*>(rec + (size_t)f * MAXC + i);
+            const uint4* src = reinterpret_cast<const uint4*>(rec + ((size_t)f << sh) + i);
             uint4* dst = reinterpret_cast<uint4*>(recs + ((size_t)t.rec_off + p) * sizeof(ft8rx_record));
             uint4 a = src[0], b = src[1], c = src[2];
             c.w = (uint32_t)i;                                         // pad2 = the candidate's index inside its frame

@@ -429,9 +429,9 @@ FT8_DEV void fine_candidate(int tid, int bid, const cpx* __restrict__ spec, ft8r
     int frame, ci = 0, f0, h0;
     if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; }
     else {
-        frame = bid / MAXC; ci = bid % MAXC;
+        frame = bid >> cand_shift(cfg); ci = bid & ((1 << cand_shift(cfg)) - 1);
         if (ci >= ncand[frame]) return;
-        const ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+        const ft8rx_record& r = rec[bid];
         if (r.status != FT8RX_ST_ACTIVE) return;
         f0 = r.f0_idx; h0 = r.h0_idx;
     }
@@ -648,7 +648,7 @@ FT8_DEV void fine_candidate(int tid, int bid, const cpx* __restrict__ spec, ft8r
     if (tid == 0) {
         if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
         else {
-            ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+            ft8rx_record& r = rec[bid];
             r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
             if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
             else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }
@@ -707,9 +707,9 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
     int frame, ci = 0, f0, h0;
     if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; }
     else {
-        frame = bid / MAXC; ci = bid % MAXC;
+        frame = bid >> cand_shift(cfg); ci = bid & ((1 << cand_shift(cfg)) - 1);
         if (ci >= ncand[frame]) return;
-        const ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+        const ft8rx_record& r = rec[bid];
         if (r.status != FT8RX_ST_ACTIVE) return;
         f0 = r.f0_idx; h0 = r.h0_idx;
         if (h0 >= FT8RX_MIN_H0_FD && h0 <= FT8RX_MAX_H0_FD) return;  // k_fine's candidate
@@ -820,7 +820,7 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
     if (tid == 0) {
         if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
         else {
-            ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+            ft8rx_record& r = rec[bid];
             r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
             if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
             else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }

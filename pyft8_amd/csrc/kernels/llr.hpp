@@ -145,9 +145,9 @@ __global__ __launch_bounds__(64) void k_grid_llr(const float* __restrict__ grid,
     if (trip) { frame = trip[3 * blockIdx.x]; f0 = trip[3 * blockIdx.x + 1]; h0 = trip[3 * blockIdx.x + 2]; ci = 0; }
     else {
         if (!xcd_frame_map(blockIdx.x, cfg.max_cands, B, frame, ci)) return;      // a frame's candidates gather from one XCD's L2 (launch: XCD_GRID(B, max_cands))
-        slot = (size_t)frame * MAXC + ci;
+        slot = ((size_t)frame << cand_shift(cfg)) + ci;
         if (ci >= ncand[frame]) return;
-        const ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+        const ft8rx_record& r = rec[slot];
         f0 = r.f0_idx; h0 = r.h0_idx;
     }
     ChkMasks cm;
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(64) void k_grid_llr(const float* __restrict__ grid,
     if (lane == 0) {
         if (trip) { t_sd[blockIdx.x] = sd; t_snr[blockIdx.x] = snr; }
         else {
-            ft8rx_record& r = rec[(size_t)frame * MAXC + ci];
+            ft8rx_record& r = rec[slot];
             r.grid_sd = sd; r.snr_grid = (int8_t)snr;
             if (sd <= cfg.llr_sd_min) r.status = FT8RX_ST_STOP_GRID_SD;
         }

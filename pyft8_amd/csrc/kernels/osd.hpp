@@ -203,7 +203,7 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
                          const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,
                          const int32_t* __restrict__ ncand, Att* __restrict__ attO,
                          ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,
-                         int nflip, int max_hd, const WorkList& nanlist) {
+                         int nflip, int max_hd, int sh, const WorkList& nanlist) {
     __shared__ float llr[176];
     __shared__ uint64_t skey[256];
     __shared__ uint64_t ftab[192];                         // per column (natural order): bit i = flip i covers it (i < 62), bit 63 = order-0 codeword bit
@@ -215,12 +215,12 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
     const int nflipA = wide ? OSD_FLIPS_A : nflip;
     __shared__ uint32_t hmw[3];
     __shared__ uint16_t fsyn[OSD_MAXFLIP + 2];             // [i] flip i, [OSD_MAXFLIP] = 0 ("no flip"), [OSD_MAXFLIP + 1] order-0 codeword
-    int frame = 0, ci = 0, slot = 0; size_t vec = bid;
+    int slot = 0; size_t vec = bid;
     OT_DECL
     if (mode == 0) {
-        slot = bid % 10; int c = bid / 10; frame = c / MAXC; ci = c % MAXC;
-        if (ci >= ncand[frame]) return;
-        if (rec[(size_t)frame * MAXC + ci].status != FT8RX_ST_ACTIVE) return;
+        slot = bid % 10; const int c = bid / 10;
+        if ((c & ((1 << sh) - 1)) >= ncand[c >> sh]) return;
+        if (rec[c].status != FT8RX_ST_ACTIVE) return;
         if (slot >= 5 && !attB[(size_t)c * 5 + (slot - 5)].has_out) { if (lane == 0) { Att a; memset(&a, 0, sizeof(a)); a.n_its = -1; attO[(size_t)c * 10 + slot] = a; } return; }
         // slots 0..4: the fine LLRs with the AP override, slots 5..9: the saved BP outputs; three loads in flight either way
         const float* src = slot < 5 ? llr_in + (size_t)c * 174 : saved + ((size_t)c * 5 + (slot - 5)) * 174;
@@ -589,7 +589,7 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
             uint64_t lo = 0, hi = 0;
             const int r = ft8_crc_check(w0, w1 & M1, &lo, &hi);
             const int t = base + hl;
-            if (r && lane == 0) log_event(ev, evcount, frame, ci, ipass, slot, t, lo, hi, r == 2);   // a call the reference made
+            if (r && lane == 0) log_event(ev, evcount, (int)(vec / 10) >> sh, (int)(vec / 10) & ((1 << sh) - 1), ipass, slot, t, lo, hi, r == 2);   // a call the reference made (mode 0: vec = candidate * 10 + slot)
             if (r == 2) {
                 res.ok = 1; res.lo = lo; res.hi = hi; res.n_its = (int16_t)t;
                 res.method = (slot < 5) ? FT8RX_M_OSD : FT8RX_M_LDPC_B_OSD;
@@ -618,14 +618,14 @@ __global__ __launch_bounds__(64) OSD_ATTR void NAME(int mode, const float* __res
                                            const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,                            \
                                            const int32_t* __restrict__ ncand, Att* __restrict__ attO,                               \
                                            ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,        \
-                                           int nflip, int max_hd, WorkList work, WorkList nanlist) {                                \
-    if (mode == 2) { osd_attempt<WIDE, false>(threadIdx.x, 2, blockIdx.x, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, nanlist); return; } \
+                                           int nflip, int max_hd, int sh, WorkList work, WorkList nanlist) {                        \
+    if (mode == 2) { osd_attempt<WIDE, false>(threadIdx.x, 2, blockIdx.x, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); return; } \
     const int n = *work.count * 10;                                                                                                 \
     _Pragma("unroll 1")                                                                                                             \
     for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                      \
         int lane = threadIdx.x;                                                                                                     \
         asm volatile("" : "+v"(lane));       /* opaque per item: nothing lane-specific is hoisted across attempts (register pressure) */ \
-        osd_attempt<WIDE, false>(lane, 0, work.items[item / 10] * 10 + item % 10, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, nanlist); \
+        osd_attempt<WIDE, false>(lane, 0, work.items[item / 10] * 10 + item % 10, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); \
         __syncthreads();                     /* the LDS arrays are reused by the next attempt */                                   \
     }                                                                                                                               \
 }
@@ -638,11 +638,11 @@ __global__ __launch_bounds__(64) void NAME(int mode, const float* __restrict__ l
                                            const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,                            \
                                            const int32_t* __restrict__ ncand, Att* __restrict__ attO,                               \
                                            ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,        \
-                                           int nflip, int max_hd, WorkList nanlist) {                                               \
+                                           int nflip, int max_hd, int sh, WorkList nanlist) {                                       \
     const int n = *nanlist.count;                                                                                                   \
     _Pragma("unroll 1")                                                                                                             \
     for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                      \
-        osd_attempt<WIDE, true>(threadIdx.x, mode, nanlist.items[item], llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, nanlist); \
+        osd_attempt<WIDE, true>(threadIdx.x, mode, nanlist.items[item], llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); \
         __syncthreads();                                                                                                            \
     }                                                                                                                               \
 }

@@ -43,8 +43,8 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
     if cfg.max_cands < 1:
         raise _lib.Ft8rxError(f"max_cands={max_cands}: at least one candidate per frame")
     # max_cands: no limit.  Receiver.search makes at most one candidate per f0 bin (receiver.py:341-365), so any value beyond the
-    # number of bins of the search range keeps exactly the same list; more than 256 select the build with the deep candidate
-    # layouts (libft8rx_wide.so: FT8RX_MAX_CANDS = 2048 > 1884 bins of the widest range).
+    # number of bins of the search range keeps exactly the same list, and both builds take that many (FT8RX_MAX_CANDS = 1024 > 956
+    # bins up to 3000 Hz; libft8rx_wide.so: 2048 > 1884 bins of the widest range).
     cfg.max_cands = min(cfg.max_cands, max(1, cfg.f0_hi - cfg.f0_lo))
     # search_time_range: any window the reference itself can search.  Its search reads grid rows h0 + 148 .. h0 + 172 of a 750-row grid
     # (receiver.py:322, 346-347; negative rows wrap, rows >= 750 are an IndexError), i.e. h0 in [-898, 577]; candidates whose middle

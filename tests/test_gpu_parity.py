@@ -1092,7 +1092,7 @@ def test_search_time_range_beyond_the_fine_sync_series():
 
 def test_candidate_cap_and_kwarg_limits():
     """The build's boundary limits against the reference's open-ended kwargs (receiver.py:311-313, 319, 366-367):
-    max_cands = 256, the most the default layouts hold -- with sync_score_min = 40 the threshold admits far more than 256 maxima, the
+    max_cands = 256, the largest handle at the default candidate stride -- with sync_score_min = 40 the threshold admits far more than 256 maxima, the
     stable top-K cut really happens, and every record and message still equals the oracle's; beyond the limits that remain Receiver
     names the kwarg instead of failing with the library's generic bad-config error.  (max_cands itself has no limit any more:
     test_max_cands_beyond_256_uses_the_deep_layouts.)"""
@@ -1116,22 +1116,25 @@ def test_candidate_cap_and_kwarg_limits():
             Receiver("x", None, **kw)
 
 
-def test_max_cands_beyond_256_uses_the_deep_layouts():
+@pytest.mark.parametrize("f_hi", [3000, 4000])
+def test_max_cands_beyond_256_uses_the_deep_layouts(f_hi):
     """max_cands is open-ended in the reference (receiver.py:311-313, 366-367): every f0 bin of the search range whose best sync score
-    passes sync_score_min is a candidate -- up to 928 at the default range.  More than 256 select libft8rx_wide.so (FT8RX_MAX_CANDS =
-    2048 there, include/ft8rx.h).  Receiver(max_cands=600, sync_score_min=30): more than 256 candidates in EVERY frame, each record,
-    event and message equal to the oracle's; the packed form (k_pack_*: 32 mask words per frame in this build) renders the same
-    messages; a max_cands beyond the number of f0 bins keeps exactly the list of max_cands = number of bins."""
+    passes sync_score_min is a candidate -- up to 928 at the default range.  Both builds take every bin of their ranges (FT8RX_MAX_CANDS
+    = 1024 / 2048, include/ft8rx.h); the per-candidate workspaces follow max_cands (stride 1024 here, 2048 for the uncapped run), and only
+    a range beyond 3000 Hz selects libft8rx_wide.so.  Receiver(max_cands=600, sync_score_min=30): more than 256 candidates in EVERY
+    frame, each record, event and message equal to the oracle's; the packed form (k_pack_*: 16 mask words per frame at stride 1024)
+    renders the same messages; a max_cands beyond the number of f0 bins keeps exactly the list of max_cands = number of bins."""
     from pyft8_amd import _lib, synth
     from pyft8_amd.receiver import Receiver, config_from_kwargs, decode_frames
+    rng = dict(search_freq_range=[100, f_hi])
     audio = synth.make_batch(64100, 3, n_signals=60, snr_range=(-14.0, 6.0))
-    cfg = config_from_kwargs(sync_score_min=30, max_cands=600)
+    cfg = config_from_kwargs(sync_score_min=30, max_cands=600, **rng)
     assert cfg.max_cands == 600
     h = _lib.Handle(cfg, max_frames=3)
-    assert h.wide
+    assert h.wide == (f_hi > 3000)
     rec, cnt, ev, evc = h.decode_batch(audio)
     assert rec.shape[1] == 600 and (cnt > 256).all(), cnt
-    ocfg = O.default_config(**_lib.fft_plans(), sync_score_min=30.0, max_cands=600)
+    ocfg = O.default_config(**_lib.fft_plans(), sync_score_min=30.0, max_cands=600, f0_lo=cfg.f0_lo, f0_hi=cfg.f0_hi)
     for i in range(3):
         _check_frame(rec[i], cnt[i], ev[i], evc[i], audio[i], None, ocfg)
     # packed results of the same batch (page-locked host buffers): byte for byte the numpy twin's, and the same messages as the dense arrays
@@ -1146,19 +1149,46 @@ def test_max_cands_beyond_256_uses_the_deep_layouts():
     m1, m2 = _lib.package_batch(*res), _lib.package_packed(pin[which][:hdr["bytes"]])
     assert m1[0].tobytes() == m2[0].tobytes() and np.array_equal(m1[1], m2[1]) and (m1[1] > 0).all()
     h.close()
-    # no limit: beyond the 928 f0 bins of the default range nothing changes (and the count is whatever passes the threshold)
-    big = config_from_kwargs(sync_score_min=30, max_cands=10**9)
-    assert big.max_cands == 928
+    # no limit: beyond the f0 bins of the range (928 at the default one) nothing changes (and the count is whatever passes the threshold)
+    nbins = cfg.f0_hi - cfg.f0_lo
+    big = config_from_kwargs(sync_score_min=30, max_cands=10**9, **rng)
+    assert big.max_cands == nbins == {3000: 928, 4000: 1248}[f_hi]
     h = _lib.Handle(big, max_frames=1)
     rec2, cnt2, ev2, evc2 = h.decode_batch(audio[:1])
     h.close()
-    assert 600 < int(cnt2[0]) <= 928
-    _check_frame(rec2[0], cnt2[0], ev2[0], evc2[0], audio[0], None, O.default_config(**_lib.fft_plans(), sync_score_min=30.0, max_cands=928))
+    assert 600 < int(cnt2[0]) <= nbins
+    _check_frame(rec2[0], cnt2[0], ev2[0], evc2[0], audio[0], None,
+                 O.default_config(**_lib.fft_plans(), sync_score_min=30.0, max_cands=nbins, f0_lo=cfg.f0_lo, f0_hi=cfg.f0_hi))
     assert np.array_equal(rec2[0, :600][["f0_idx", "h0_idx", "score"]], rec[0, :600][["f0_idx", "h0_idx", "score"]])
-    msgs = decode_frames(audio[:1], sync_score_min=30, max_cands=600)
+    msgs = decode_frames(audio[:1], sync_score_min=30, max_cands=600, **rng)
     assert len(msgs) == 1 and len(msgs[0]) > 0
-    rx = Receiver("x", None, max_cands=600, sync_score_min=30)
+    rx = Receiver("x", None, max_cands=600, sync_score_min=30, **rng)
     assert rx.cfg.max_cands == 600
+
+
+@pytest.mark.parametrize("max_cands", [256, 257, 1024])
+def test_candidate_stride_boundaries(max_cands):
+    """The per-frame stride of the per-candidate workspaces is the smallest power of two >= max(max_cands, 256), set at create time
+    (include/ft8rx.h): 256 is the last handle at stride 256, 257 the first at 512, 1024 the largest libft8rx.so takes.  At
+    sync_score_min = 30 every frame fills its candidates beyond the next smaller stride; records, counts and messages equal the
+    oracle's, and every unpack() call of the oracle's ladder is in the event log (which also holds the calls of attempts that ran
+    beside the ladder and that the replay passes over)."""
+    from collections import Counter
+    from pyft8_amd import _lib, synth
+    from helpers import records_from_oracle
+    audio = synth.make_batch(64200, 2, n_signals=60, snr_range=(-14.0, 6.0))
+    h = _lib.Handle(_lib.default_config(sync_score_min=30.0, max_cands=max_cands), max_frames=2)
+    assert not h.wide
+    rec, cnt, ev, evc = h.decode_batch(audio)
+    h.close()
+    assert rec.shape[1] == max_cands and (cnt > {256: 255, 257: 256, 1024: 512}[max_cands]).all(), cnt
+    ocfg = O.default_config(**_lib.fft_plans(), sync_score_min=30.0, max_cands=max_cands)
+    for i in range(2):
+        _check_frame(rec[i], cnt[i], ev[i], evc[i], audio[i], None, ocfg)
+        r = O.decode_frame(audio[i], ocfg)
+        assert r["n_events"] <= int(evc[i]) <= _lib.EVENT_CAP
+        want = Counter(e.tobytes() for e in records_from_oracle(r, max_cands)[2][:r["n_events"]])
+        assert not want - Counter(e.tobytes() for e in ev[i, :int(evc[i])])
 
 
 def test_device_synth_generator(H, ocfg):
@@ -1418,7 +1448,7 @@ def test_error_paths_and_lifecycle():
     """C ABI error convention: negative return + ft8rx_last_error text, surfaced as Ft8rxError; never a crash."""
     from pyft8_amd import _lib
     with pytest.raises(_lib.Ft8rxError, match="configuration"):
-        _lib.Handle(_lib.default_config(max_cands=5000))                    # > FT8RX_MAX_CANDS of the deep layouts (2048)
+        _lib.Handle(_lib.default_config(max_cands=5000))                    # > FT8RX_MAX_CANDS of either build (1024 / 2048)
     with pytest.raises(_lib.Ft8rxError, match="configuration"):
         _lib.Handle(_lib.default_config(f0_lo=0))
     with pytest.raises(_lib.Ft8rxError, match="configuration"):
