@@ -36,6 +36,7 @@
  *     ft8rx_synth_frames  ft8rx_synth_frames_ex                                        (f-1: workload generator)
  *     ft8rx_subtract  ft8rx_subtraction_list  ft8rx_encode_tones  ft8rx_merge_messages  ft8rx_set_search_mask   (f-4: subtraction passes)
  *     ft8rx_osd_ext                                                                    (order-3 / distance-gate knobs)
+ *     ft8rx_set_msg_types  ft8rx_package_batch_ext  ft8rx_valid77_ext                  (opt-in message types)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
@@ -101,6 +102,16 @@ typedef struct {
                                       *     whatever its distance (decoders.py:248-272), which is where its false decodes come from. */
 } ft8rx_config;
 
+/* Opt-in message types (extension; ft8rx_set_msg_types): FT8RX_MT_* bits, i3.n3 of the 77-bit word (Franke, Somerville, Taylor,
+ * QEX 2020).  The reference leaves them unimplemented (decoders.py:16-49 returns None); 0 = its rule, bit for bit. */
+#define FT8RX_MT_FREE_TEXT   1        /* 0.0  13 characters of a 42-character alphabet */
+#define FT8RX_MT_DXPEDITION  2        /* 0.1  c28 c28 h10 r5 */
+#define FT8RX_MT_FIELD_DAY   4        /* 0.3 / 0.4  c28 c28 R1 n4 k3 s7 */
+#define FT8RX_MT_TELEMETRY   8        /* 0.5  71 bits, 18 hex digits */
+#define FT8RX_MT_RTTY_RU     16       /* 3    t1 c28 c28 R1 r3 s13 */
+#define FT8RX_MT_EU_VHF      32       /* 5    h12 h22 R1 r3 s11 g25 */
+#define FT8RX_MT_ALL         63
+
 enum { FT8RX_ST_ACTIVE = 0, FT8RX_ST_DECODED = 1, FT8RX_ST_STOP_GRID_SD = 2, FT8RX_ST_STOP_COSTAS = 3,
        FT8RX_ST_STOP_FINE_SD = 4, FT8RX_ST_EXHAUSTED = 5 };
 enum { FT8RX_M_GOOD91 = 0, FT8RX_M_LDPC_A = 1, FT8RX_M_LDPC_B = 2, FT8RX_M_OSD = 3, FT8RX_M_LDPC_B_OSD = 4 };
@@ -139,6 +150,18 @@ typedef struct {
     uint8_t  ipass, ap, method, fine;
     uint8_t  pad[3];
 } ft8rx_message;
+
+/* The same for a handle with msg_types != 0 (ft8rx_package_batch_ext): fields wide enough for every message type, and the
+ * type.  f[0..2] = msg_tuple: (first call -- or "TU; call", or "call RR73;" for DXpedition --, second call, the rest); free text and
+ * telemetry are (text, "", "").  112 bytes. */
+typedef struct {
+    char     f[3][32];               /* msg_tuple, NUL-terminated */
+    int16_t  cand, f0_idx, h0_idx;
+    int8_t   snr, ttweak, ftweak;
+    uint8_t  ipass, ap, method, fine;
+    uint8_t  i3, n3;                 /* message type: i3, and n3 when i3 == 0 (0 otherwise) */
+    uint8_t  pad[1];
+} ft8rx_message_ext;
 
 typedef struct ft8rx_handle ft8rx_handle;
 typedef struct ft8rx_hashes ft8rx_hashes;                           /* persistent call-hash table, ft8rx_hashes_* below */
@@ -257,6 +280,12 @@ int  ft8rx_set_subbatch(ft8rx_handle* h, int frames);
  *     (one frame: 0.38 vs 0.49 ms host to host).  The event log then also holds CRC-passing words of attempts the ladder would not
  *     have reached; ft8rx_package_batch skips them. */
 int  ft8rx_set_ladder_mode(ft8rx_handle* h, int mode);
+/* Opt-in message types (FT8RX_MT_* bits; 0 = the default = the reference's rule): with a bit set, a CRC-valid word of that type that
+ * passes its plausibility gate (csrc/ft8_dev.h: ft8_valid77_ext) stops a candidate's ladder like any other message; free text and
+ * telemetry are never accepted from an OSD trial.  Records / events are then packaged with
+ * ft8rx_package_batch_ext; ft8rx_decode_messages and the packed output (ft8rx_set_packed_output) refuse a non-zero mask.  Applies to
+ * batches enqueued afterwards.  A handle setting rather than a field of ft8rx_config, whose layout callers' bindings hard-code. */
+int  ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the
@@ -305,6 +334,9 @@ int  ft8rx_osd_ext(ft8rx_handle* h, const float* llr, int n, int singleflips, in
 int  ft8rx_crc_valid(ft8rx_handle* h, const float* cw91, int n, int32_t* res, uint64_t* msg_lo, uint64_t* msg_hi);
 /* unpack() validity predicate (decoders.py:16-115) on n 77-bit words */
 int  ft8rx_valid77(ft8rx_handle* h, const uint64_t* msg_lo, const uint64_t* msg_hi, int n, int32_t* valid);
+/* the same predicate with opt-in message types (FT8RX_MT_* bits; mask = 0 is ft8rx_valid77), as the GOOD91 and BP steps
+ * apply it -- an OSD trial additionally never accepts free text or telemetry */
+int  ft8rx_valid77_ext(ft8rx_handle* h, const uint64_t* msg_lo, const uint64_t* msg_hi, int n, int32_t mask, int32_t* valid);
 /* Workload generator (modelled on transmitter.py:41-70): n_frames synthetic 15-s frames of
  * n_signals GFSK signals + Philox white noise, written to the device buffer d_audio[n_frames][180000] int16.
  * signal_table: n_frames*n_signals records laid out as pyft8_amd/synth.py:SIGNAL_DTYPE; pulse_cumsum: 5761 doubles. */
@@ -330,6 +362,12 @@ int  ft8rx_synth_frames_ex(ft8rx_handle* h, uint64_t seed, int first_index, int 
 int  ft8rx_package_batch(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
                          int n_frames, int max_cands, ft8rx_message* out, int max_msgs, int32_t* out_counts, int n_threads,
                          ft8rx_hashes* table, int32_t* flags);
+/* ft8rx_package_batch for records of a handle with msg_types = mask: the words of the opt-in types are rendered too (their
+ * standard calls enter the call-hash table, hash fields are looked up in it), into the wider ft8rx_message_ext.  mask = 0 renders
+ * exactly what ft8rx_package_batch does.  The packed path (ft8rx_package_packed) has no _ext form. */
+int  ft8rx_package_batch_ext(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
+                             int n_frames, int max_cands, ft8rx_message_ext* out, int max_msgs, int32_t* out_counts, int n_threads,
+                             ft8rx_hashes* table, int32_t* flags, int32_t mask);
 /* Multi-pass decoding (extension; no GPU needed): append to each frame's message list out[f][0..out_counts[f])
  * those messages of a later pass, add[f][0..add_counts[f]), whose text the frame does not have yet (pad[0] = pass_tag marks them);
  * the same messages, untagged, go to fresh[f] (optional; [n_frames][max_add]) -- the input of the next subtraction sweep.

@@ -36,6 +36,9 @@ class Config(C.Structure):
                 ("bp_nc0_a", C.c_int32), ("bp_iters_a", C.c_int32), ("bp_nc0_b", C.c_int32), ("bp_iters_b", C.c_int32),
                 ("osd_single", C.c_int32), ("osd_double", C.c_int32), ("llr_sd_min", C.c_float),
                 ("osd_triple", C.c_int32), ("osd_max_hd", C.c_int32)]
+    # opt-in message types (FT8RX_MT_* bits): not a field of ft8rx_config but a handle setting (ft8rx_set_msg_types) that Handle applies
+    # at create time; kept here so that a config carries every knob of a receiver.  0 = the reference's rule.
+    msg_types = 0
 
 
 RECORD_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("score", "<f4"), ("grid_sd", "<f4"), ("fine_sd", "<f4"),
@@ -46,6 +49,14 @@ EVENT_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("cand", "<u2"), (
                         ("seq", "<u2"), ("valid", "<u2")])
 MESSAGE_DTYPE = np.dtype([("f", "S16", (3,)), ("cand", "<i2"), ("f0_idx", "<i2"), ("h0_idx", "<i2"), ("snr", "i1"), ("ttweak", "i1"),
                           ("ftweak", "i1"), ("ipass", "u1"), ("ap", "u1"), ("method", "u1"), ("fine", "u1"), ("pad", "u1", (3,))])
+# ft8rx_message_ext (ft8rx_package_batch_ext): wider text fields and the message type (i3, n3)
+MESSAGE_EXT_DTYPE = np.dtype([("f", "S32", (3,)), ("cand", "<i2"), ("f0_idx", "<i2"), ("h0_idx", "<i2"), ("snr", "i1"), ("ttweak", "i1"),
+                              ("ftweak", "i1"), ("ipass", "u1"), ("ap", "u1"), ("method", "u1"), ("fine", "u1"), ("i3", "u1"), ("n3", "u1"),
+                              ("pad", "u1", (1,))])
+assert MESSAGE_EXT_DTYPE.itemsize == 112
+# Config.msg_types bits (include/ft8rx.h FT8RX_MT_*, ft8rx_set_msg_types)
+MSG_TYPE_BITS = {"free_text": 1, "dxpedition": 2, "field_day": 4, "telemetry": 8, "rtty_ru": 16, "eu_vhf": 32}
+MT_ALL = 63
 SUBSIG_DTYPE = np.dtype([("fHz", "<f8"), ("tsec", "<f8"), ("tones", "u1", (79,)), ("pad", "u1")])
 assert SUBSIG_DTYPE.itemsize == 96
 # packed results (include/ft8rx.h: ft8rx_packed_header / ft8rx_packed_frame): header | frame table | kept records | used events
@@ -228,6 +239,9 @@ class Handle:
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
+        if self.cfg.msg_types:
+            L.ft8rx_set_msg_types.argtypes = [C.c_void_p, C.c_int32]
+            self._chk(L.ft8rx_set_msg_types(self._h, int(self.cfg.msg_types)), "ft8rx_set_msg_types")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -347,6 +361,9 @@ class Handle:
         keep: the objects that own the two buffers (torch tensors, page-locked arrays).  The handle holds on to them -- and to the events
         given to packed_fence -- until the packed output is reset or the handle is closed, so the pack kernels can never write into
         memory whose Python owner has already been collected."""
+        if buf0 is not None and self.cfg.msg_types:
+            raise Ft8rxError("set_packed_output: msg_types != 0 is not supported on the packed path (ft8rx_package_packed renders only the "
+                             "reference's message types)")
         L = self._L
         L.ft8rx_set_packed_output.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         self._chk(L.ft8rx_set_packed_output(self._h, C.c_void_p(buf0 or None), C.c_void_p(buf1 or None), C.c_uint64(int(cap_bytes))),
@@ -555,6 +572,16 @@ class Handle:
         self._chk(self._L.ft8rx_valid77(self._h, _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), len(lo), _ptr(out, C.c_int32)), "ft8rx_valid77")
         return out
 
+    def valid77_ext(self, bits, mask):
+        """ft8rx_valid77_ext: the validity predicate with the opt-in message types `mask` (MSG_TYPE_BITS) on the GPU."""
+        lo = np.array([b & (2 ** 64 - 1) for b in bits], np.uint64)
+        hi = np.array([b >> 64 for b in bits], np.uint64)
+        out = np.zeros(len(lo), np.int32)
+        L = self._L
+        L.ft8rx_valid77_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_void_p]
+        self._chk(L.ft8rx_valid77_ext(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), int(mask), out.ctypes.data), "ft8rx_valid77_ext")
+        return out
+
     def subtract(self, d_audio_ptr, n_frames, signals, return_float=False, refine=False, return_origins=False):
         """Subtract decoded signals from device-resident int16 audio in place (ft8rx_subtract).
         signals: per frame a list of (tones79, fHz, tsec), subtracted in list order.  -> float32 residual if return_float.
@@ -726,6 +753,35 @@ def package_batch(rec, cnt, ev, evc, max_msgs=None, n_threads=None, table=None, 
     if rc != 0:
         raise Ft8rxError(f"ft8rx_package_batch failed ({rc})")
     _warn_truncation(flags, "package_batch")
+    return (out, oc, flags) if return_flags else (out, oc)
+
+
+def package_batch_ext(rec, cnt, ev, evc, mask, max_msgs=None, n_threads=None, table=None, return_flags=False):
+    """ft8rx_package_batch_ext: package_batch for records decoded with msg_types = mask -> (messages[B, max_msgs] of
+    MESSAGE_EXT_DTYPE, counts[B]).  mask = 0 renders what package_batch renders."""
+    rec = np.ascontiguousarray(rec)
+    ev = np.ascontiguousarray(ev)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    evc = np.ascontiguousarray(evc, np.int32)
+    B, mc = rec.shape
+    if ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE:
+        raise Ft8rxError("package_batch_ext: records/events are not the arrays returned by decode_batch/fetch")
+    if max_msgs is None:
+        max_msgs = max(mc, 1)
+    out = np.zeros((B, max_msgs), MESSAGE_EXT_DTYPE)
+    oc = np.zeros(B, np.int32)
+    flags = np.zeros(B, np.int32)
+    if n_threads is None:
+        n_threads = min(32, os.cpu_count() or 1)
+    L = lib()
+    L.ft8rx_package_batch_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32]
+    rc = L.ft8rx_package_batch_ext(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, int(B), int(mc), out.ctypes.data,
+                                   int(max_msgs), oc.ctypes.data, int(n_threads), table._t if table is not None else None,
+                                   flags.ctypes.data, int(mask))
+    if rc != 0:
+        raise Ft8rxError(f"ft8rx_package_batch_ext failed ({rc})")
+    _warn_truncation(flags, "package_batch_ext")
     return (out, oc, flags) if return_flags else (out, oc)
 
 

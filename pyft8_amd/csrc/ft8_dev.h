@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ft8_tables.h"
+#include "ft8_msg_tables.h"
 
 typedef float2 cpx;
 
@@ -366,6 +367,47 @@ FT8_DEV bool ft8_valid77(uint64_t lo, uint64_t hi) {
     return false;
 }
 
+// The same predicate with the opt-in message types of ft8rx_set_msg_types (FT8RX_MT_* bits, include/ft8rx.h).  mask == 0 is
+// ft8_valid77 itself; i3 = 1, 2, 4 always take the reference's rule.  Per type (bit layouts: Franke, Somerville, Taylor, QEX 2020;
+// bit 0 = least significant of the 77-bit integer, fields listed from the top):
+//   0.0 free text  f71 < 42^13 (13 base-42 characters)                                         -- never from an OSD trial
+//   0.1 DXpedition c28 c28 h10 r5: both c28 pass the i3 = 1 field rule (ft8_call29_ok, no suffix flag)
+//   0.3/0.4 Field Day  c28 c28 R1 n4 k3 s7: both c28 as above, s7 = 1 .. FT8_N_SECTIONS
+//   0.5 telemetry  71 bits, not all zero (an empty line)                                       -- never from an OSD trial
+//   3   RTTY RU    t1 c28 c28 R1 r3 s13: both c28 as above, s13 = serial 1 .. 7999 or 8000 + 1 .. FT8_N_MULT
+//   5   EU VHF     h12 h22 R1 r3 s11 g25: g25 < 18 x 18 x 10 x 10 x 24 x 24 (a 6-character locator)
+// 0.2, 0.6, 0.7 and i3 = 6, 7 stay rejected.  osd: the word comes from an OSD trial.  Free text and telemetry carry no redundancy
+// beyond the CRC-14, so any OSD trial that meets the CRC would be accepted as one; those trials are treated as rejected words.
+FT8_DEV bool ft8_c28_ok(uint32_t c28) { return ft8_call29_ok(c28 << 1, 1); }
+FT8_DEV bool ft8_valid77_ext(uint64_t lo, uint64_t hi, unsigned mask, bool osd = false) {
+    if (mask == 0) return ft8_valid77(lo, hi);
+    if (lo == 0 && hi == 0) return false;
+    const unsigned i3 = (unsigned)(lo & 7u), n3 = (unsigned)((lo >> 3) & 7u);
+    if (i3 == 1 || i3 == 2 || i3 == 4) return ft8_valid77(lo, hi);
+    const uint32_t ca28 = (uint32_t)(((lo >> 49) | (hi << 15)) & 0xFFFFFFFu), cb28 = (uint32_t)((lo >> 21) & 0xFFFFFFFu);   // i3 = 0 layout
+    if (i3 == 0) {
+        const uint64_t vlo = (lo >> 6) | (hi << 58), vhi = (hi >> 6) & 0x7Fu;      // the 71-bit payload
+        switch (n3) {
+        case 0: return (mask & FT8RX_MT_FREE_TEXT) && !osd && (vhi < 0x44u || (vhi == 0x44u && vlo < 0x9979e458016ca000ull));   // 42^13
+        case 1: return (mask & FT8RX_MT_DXPEDITION) && ft8_c28_ok(ca28) && ft8_c28_ok(cb28);
+        case 3: case 4: {
+            const unsigned s7 = (unsigned)((lo >> 6) & 0x7Fu);
+            return (mask & FT8RX_MT_FIELD_DAY) && s7 >= 1 && s7 <= FT8_N_SECTIONS && ft8_c28_ok(ca28) && ft8_c28_ok(cb28);
+        }
+        case 5: return (mask & FT8RX_MT_TELEMETRY) && !osd && (vlo | vhi) != 0;
+        default: return false;
+        }
+    }
+    if (i3 == 3) {
+        const unsigned s13 = (unsigned)((lo >> 3) & 0x1FFFu);
+        const uint32_t a28 = (uint32_t)(((lo >> 48) | (hi << 16)) & 0xFFFFFFFu), b28 = (uint32_t)((lo >> 20) & 0xFFFFFFFu);
+        return (mask & FT8RX_MT_RTTY_RU) && ((s13 >= 1 && s13 <= 7999) || (s13 >= 8001 && s13 <= 8000 + FT8_N_MULT)) &&
+               ft8_c28_ok(a28) && ft8_c28_ok(b28);
+    }
+    if (i3 == 5) return (mask & FT8RX_MT_EU_VHF) && (unsigned)((lo >> 3) & 0x1FFFFFFu) < 18662400u;
+    return false;
+}
+
 // 91 hard bits given as two ballots (b0: codeword bits 0..63, b1: bits 64..90, LSB = lowest index)
 // -> 77-bit message (bit 76 = codeword bit 0) and the received CRC field
 FT8_DEV void ft8_cw_to_msg(uint64_t b0, uint64_t b1, uint64_t* lo, uint64_t* hi, unsigned* crc) {
@@ -411,20 +453,24 @@ FT8_DEV unsigned ft8_crc_syndrome_wave(uint64_t b0, uint64_t b1, int lane) {
     return (unsigned)__builtin_amdgcn_readfirstlane((int)ft8_xor_row16(ft8_crc_entry(b0, b1 & ((1ull << 27) - 1), lane)));
 }
 
-// 0 = no CRC match (or all-zero message), 1 = CRC ok but unpack() -> None, 2 = accepted
-FT8_DEV int ft8_crc_check(uint64_t b0, uint64_t b1, uint64_t* lo, uint64_t* hi) {
+// 0 = no CRC match (or all-zero message), 1 = CRC ok but unpack() -> None, 2 = accepted.
+// EXT = false is the reference's predicate (the kernels of a handle with msg_types = 0 are instantiated with it: the same code as
+// before the extension); EXT = true applies ft8_valid77_ext(mask, osd).
+template <bool EXT = false>
+FT8_DEV int ft8_crc_check(uint64_t b0, uint64_t b1, uint64_t* lo, uint64_t* hi, unsigned mask = 0, bool osd = false) {
     if (ft8_crc_syndrome(b0, b1 & ((1ull << 27) - 1)) != 0) return 0;        // 12 table lookups instead of a 77-step bit loop
     unsigned crc;
     ft8_cw_to_msg(b0, b1, lo, hi, &crc);
     if (*lo == 0 && *hi == 0) return 0;
-    return ft8_valid77(*lo, *hi) ? 2 : 1;
+    return (EXT ? ft8_valid77_ext(*lo, *hi, mask, osd) : ft8_valid77(*lo, *hi)) ? 2 : 1;
 }
 // the same for a wave-uniform word, all 64 lanes active
-FT8_DEV int ft8_crc_check_wave(uint64_t b0, uint64_t b1, int lane, uint64_t* lo, uint64_t* hi) {
+template <bool EXT = false>
+FT8_DEV int ft8_crc_check_wave(uint64_t b0, uint64_t b1, int lane, uint64_t* lo, uint64_t* hi, unsigned mask = 0) {
     if (ft8_crc_syndrome_wave(b0, b1, lane) != 0) return 0;
     unsigned crc;
     ft8_cw_to_msg(b0, b1, lo, hi, &crc);
     if (*lo == 0 && *hi == 0) return 0;
-    return ft8_valid77(*lo, *hi) ? 2 : 1;
+    return (EXT ? ft8_valid77_ext(*lo, *hi, mask) : ft8_valid77(*lo, *hi)) ? 2 : 1;
 }
 #endif  // FT8RX_ILP_UNIT

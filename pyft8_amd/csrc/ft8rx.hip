@@ -87,6 +87,7 @@ struct ft8rx_handle {
     hipStream_t stream;
     int n_streams;                       // chunks of a batch run their kernel chains on separate streams
     int ladder_mode;                     // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
+    int msg_types;                       // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
     int sub_frames;                      // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
     hipStream_t sub[8];
     hipEvent_t ev_fork, ev_join[8];
@@ -332,7 +333,7 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     if (device < 0 || device >= ndev) { set_err(nullptr, "ft8rx_create: device %d out of range (%d devices)", device, ndev); return -1; }
     ft8rx_handle* h = new ft8rx_handle();
     h->cfg = *cfg; h->device = device; h->max_frames = max_frames; h->stream = nullptr; h->profiling = false; h->n_stage = 0;
-    h->n_streams = 2; h->ladder_mode = 0; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
+    h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
     h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
     for (int k = 0; k < 2; k++) { h->ev_comp[k] = h->ev_done[k] = nullptr; h->h_rec[k] = nullptr; h->h_cnt[k] = nullptr; h->h_ev[k] = nullptr; h->h_evc[k] = nullptr; h->h_evpacked[k] = nullptr; h->d_evpacked[k] = nullptr; h->d_evoffs[k] = nullptr; h->slot_B[k] = 0; }
     h->slot_enq = h->slot_fetch = h->inflight = 0; h->last_slot = -1;
@@ -565,10 +566,14 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     STAGE("topk");
     k_topk<<<B, 1024, 0, s>>>(bs, bh, rec, ncand, c, evc, wc, h->use_mask ? h->d_colmask + F * NF0MAX : nullptr);
     STAGE("grid_llr");
-    k_grid_llr<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
+    // msg_types != 0: the same kernels instantiated with the extended validity predicate (ft8_valid77_ext); at 0 the code is unchanged
+    const unsigned mt = (unsigned)h->msg_types;
+    if (!mt) k_grid_llr<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
+    else k_grid_llr_ext<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B, mt);
     k_worklist_att<<<(B * S * 5 + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_BP0]);
     STAGE("bp_grid");
-    k_bp<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
+    if (!mt) k_bp<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
+    else k_bp_ext<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5, mt);
     STAGE("select0");
     k_select0<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_FINE]);
     STAGE("cycle_fft");
@@ -584,25 +589,37 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     // batches where latency matters more than work -- all five variants in one launch: one dependent BP instead of three, same
     // records and messages (the event log then also holds entries of attempts the ladder would not have reached)
     if (h->ladder_mode == 0) {
-        k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1);
+        if (!mt) k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1);
+        else k_bp_ext<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1, mt);
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(0, rec, ncand, attG, attB, B, c, wl[WL_BP1B]);
-        k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1);
+        if (!mt) k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1);
+        else k_bp_ext<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1, mt);
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(1, rec, ncand, attG, attB, B, c, wl[WL_BP1C]);
-        k_bp<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3);
+        if (!mt) k_bp<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3);
+        else k_bp_ext<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3, mt);
         STAGE("select1");
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(2, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     } else {
-        k_bp<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5);
+        if (!mt) k_bp<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5);
+        else k_bp_ext<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5, mt);
         STAGE("select1");
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     }
     STAGE("osd");
     const bool osd_wide = osd_nflip(c.osd_single, c.osd_triple) > OSD_FLIPS_A;
-    (osd_wide ? k_osd_wide : k_osd)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
-        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
-    // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
-    (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, s>>>(
-        0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSDNAN]);
+    const int nflip = osd_nflip(c.osd_single, c.osd_triple);
+    if (!mt) {
+        (osd_wide ? k_osd_wide : k_osd)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
+            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
+        // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
+        (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, s>>>(
+            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN]);
+    } else {
+        (osd_wide ? k_osd_wide_ext : k_osd_ext)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
+            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN], mt);
+        (osd_wide ? k_osd_nan_wide_ext : k_osd_nan_ext)<<<OSD_NAN_GRID, 64, 0, s>>>(
+            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN], mt);
+    }
     STAGE("select2");
     k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
@@ -812,6 +829,14 @@ int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > 8) return
 int ft8rx_set_subbatch(ft8rx_handle* h, int frames) { if (!h || frames < 0) return -1; h->sub_frames = frames; return 0; }
 int ft8rx_set_ladder_mode(ft8rx_handle* h, int mode) { if (!h || mode < 0 || mode > 1) return -1; h->ladder_mode = mode; return 0; }
 
+int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
+    if (!h) return -1;
+    if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
+    if (mask && h->pk_buf[0]) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
+    h->msg_types = mask;                        // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
+    return 0;
+}
+
 int ft8rx_set_search_mask(ft8rx_handle* h, const uint8_t* mask, int n_frames) {
     if (!h) return -1;
     ENTER(h);                                   // batches in flight were enqueued under the previous setting
@@ -883,6 +908,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     HIPCHK(h, hipStreamSynchronize(h->copy_s));
     h->pk_fence[0] = h->pk_fence[1] = nullptr;
     if (!d_buf0 && !d_buf1) { h->pk_buf[0] = h->pk_buf[1] = nullptr; h->pk_cap = 0; return 0; }
+    if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -958,6 +984,7 @@ int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_me
                           int n_threads, ft8rx_hashes* table, int32_t* flags) {
     if (!h || !audio || !out || !out_counts) return -1;
     if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "ft8rx_decode_messages: bad n_frames / max_msgs"); return -1; }
+    if (h->msg_types) { set_err(h, "ft8rx_decode_messages: msg_types != 0 -- ft8rx_message holds only the reference's message types"); return -1; }
     h->inflight = 0; h->slot_fetch = h->slot_enq;                     // synchronous entry: nothing older is kept
     if (need_staging(h)) return -2;
     int rc = launch_batch(h, h->d_audio, audio, B);
@@ -1174,6 +1201,19 @@ int ft8rx_valid77(ft8rx_handle* h, const uint64_t* msg_lo, const uint64_t* msg_h
     return 0;
 }
 
+int ft8rx_valid77_ext(ft8rx_handle* h, const uint64_t* msg_lo, const uint64_t* msg_hi, int n, int32_t mask, int32_t* valid) {
+    if (!h || !msg_lo || !msg_hi || n < 1 || mask < 0 || mask > FT8RX_MT_ALL) return -1;
+    ENTER(h);
+    Scratch S{h};
+    uint64_t* d_lo = S.put(msg_lo, n); NEED(d_lo);
+    uint64_t* d_hi = S.put(msg_hi, n); NEED(d_hi);
+    int32_t* d_v = S.get<int32_t>(n); NEED(d_v);
+    k_valid_ext_probe<<<(n + 255) / 256, 256, 0, h->stream>>>(d_lo, d_hi, n, (unsigned)mask, d_v);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(valid, d_v, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int16_t* ft8rx_staging_audio(ft8rx_handle* h) {
     if (!h || hipSetDevice(h->device) != hipSuccess || need_staging(h)) return nullptr;
     return h->d_audio;
@@ -1381,6 +1421,14 @@ int ft8rx_package_batch(const ft8rx_record* records, const int32_t* counts, cons
                         ft8rx_hashes* table, int32_t* flags) {
     return hostmsg::package_batch(records, counts, events, event_counts, n_frames, max_cands, out, max_msgs, out_counts, n_threads,
                                   table ? &table->H : nullptr, flags);
+}
+
+int ft8rx_package_batch_ext(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
+                            int n_frames, int max_cands, ft8rx_message_ext* out, int max_msgs, int32_t* out_counts, int n_threads,
+                            ft8rx_hashes* table, int32_t* flags, int32_t mask) {
+    if (mask < 0 || mask > FT8RX_MT_ALL) return -1;
+    return hostmsg::package_batch(records, counts, events, event_counts, n_frames, max_cands, out, max_msgs, out_counts, n_threads,
+                                  table ? &table->H : nullptr, flags, (unsigned)mask);
 }
 
 int ft8rx_package_packed(const void* packed, uint64_t bytes, int frame_lo, int n_frames, ft8rx_message* out, int max_msgs,

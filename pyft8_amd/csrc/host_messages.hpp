@@ -22,6 +22,7 @@
 #include <condition_variable>
 #include <functional>
 #include <unistd.h>
+#include "ft8_msg_tables.h"
 namespace hostmsg {
 // Persistent worker threads of the packaging entry points.  Creating and joining n std::threads per call was ~1 ms of the 1.2 ms a
 // 256-frame batch took at 32 threads (and, with one process per GPU, tens of thousands of thread creations per second on the host).
@@ -221,6 +222,95 @@ static bool unpack(uint64_t lo, uint64_t hi, Hashes& H, std::string f[3]) {
     }
     return false;
 }
+// unpack() with the opt-in message types of `mask` (FT8RX_MT_* bits, include/ft8rx.h): the C++ twin of messages.unpack_ext.  mask = 0
+// and i3 = 1, 2, 4 are unpack() itself.  true iff the device gate ft8_valid77_ext (csrc/ft8_dev.h) accepts the word outside OSD; the
+// c28 fields go through field29 (a standard call enters H, as the reference's call_29 does for i3 = 1 / 2), both before any range check,
+// so H evolves the same way whatever the outcome; hash fields are looked up in H ("<...>" on a miss).
+static bool unpack_ext(uint64_t lo, uint64_t hi, unsigned mask, Hashes& H, std::string f[3]) {
+    const unsigned i3 = (unsigned)(lo & 7u), n3 = (unsigned)((lo >> 3) & 7u);
+    if (mask == 0 || (!lo && !hi) || i3 == 1 || i3 == 2 || i3 == 4) return unpack(lo, hi, H, f);
+    typedef unsigned __int128 u128;
+    const u128 w = ((u128)(hi & 0x1FFFull) << 64) | lo;
+    auto bits = [&](int pos, int n) { return (uint64_t)((w >> pos) & (((u128)1 << n) - 1)); };
+    char buf[48];
+    auto hashed = [&](uint32_t h, int nb) { return "<" + H.get(h, nb) + ">"; };
+    if (i3 == 0) {
+        const u128 v71 = w >> 6;
+        if (n3 == 0) {                                                  // free text: 13 characters, base 42, first character most significant
+            static const char A42[] = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ+-./?";
+            if (!(mask & FT8RX_MT_FREE_TEXT)) return false;
+            u128 v = v71;
+            const u128 lim = ((u128)0x44 << 64) | 0x9979e458016ca000ull;  // 42^13
+            if (v >= lim) return false;
+            std::string t(13, ' ');
+            for (int i = 12; i >= 0; i--) { t[i] = A42[(int)(v % 42)]; v /= 42; }
+            f[0] = strip(t); f[1] = ""; f[2] = "";
+            return true;
+        }
+        if (n3 == 5) {                                                  // telemetry: 18 hex digits, leading zeros dropped
+            if (!(mask & FT8RX_MT_TELEMETRY) || v71 == 0) return false;
+            snprintf(buf, sizeof buf, "%X%016llX", (unsigned)(uint64_t)(v71 >> 64), (unsigned long long)(uint64_t)v71);
+            const char* q = buf; while (*q == '0') q++;
+            f[0] = q; f[1] = ""; f[2] = "";
+            return true;
+        }
+        if (n3 == 1) {                                                  // DXpedition: c28 c28 h10 r5
+            if (!(mask & FT8RX_MT_DXPEDITION)) return false;
+            std::string a, b;
+            const bool oka = field29((uint32_t)bits(49, 28) << 1, 1, H, a), okb = field29((uint32_t)bits(21, 28) << 1, 1, H, b);
+            snprintf(buf, sizeof buf, " %+03d", 2 * (int)bits(6, 5) - 30);
+            f[0] = a + " RR73;"; f[1] = b; f[2] = hashed((uint32_t)bits(11, 10), 10) + buf;
+            return oka && okb;
+        }
+        if (n3 == 3 || n3 == 4) {                                       // ARRL Field Day: c28 c28 R1 n4 k3 s7
+            if (!(mask & FT8RX_MT_FIELD_DAY)) return false;
+            std::string a, b;
+            const bool oka = field29((uint32_t)bits(49, 28) << 1, 1, H, a), okb = field29((uint32_t)bits(21, 28) << 1, 1, H, b);
+            const unsigned s7 = (unsigned)bits(6, 7);
+            if (!oka || !okb || s7 < 1 || s7 > FT8_N_SECTIONS) return false;
+            snprintf(buf, sizeof buf, "%s%d%c %s", bits(20, 1) ? "R " : "", (int)bits(16, 4) + 1 + (n3 == 4 ? 16 : 0), (char)('A' + bits(13, 3)),
+                     FT8_SECTIONS[s7 - 1]);
+            f[0] = a; f[1] = b; f[2] = buf;
+            return true;
+        }
+        return false;
+    }
+    if (i3 == 3) {                                                      // ARRL RTTY Roundup: t1 c28 c28 R1 r3 s13
+        if (!(mask & FT8RX_MT_RTTY_RU)) return false;
+        std::string a, b;
+        const bool oka = field29((uint32_t)bits(48, 28) << 1, 1, H, a), okb = field29((uint32_t)bits(20, 28) << 1, 1, H, b);
+        const unsigned s13 = (unsigned)bits(3, 13);
+        const bool serial = s13 >= 1 && s13 <= 7999, mult = s13 >= 8001 && s13 <= 8000 + FT8_N_MULT;
+        if (!oka || !okb || !(serial || mult)) return false;
+        char ex[8];
+        if (serial) snprintf(ex, sizeof ex, "%04u", s13); else snprintf(ex, sizeof ex, "%s", FT8_MULT[s13 - 8001]);
+        snprintf(buf, sizeof buf, "%s5%d9 %s", bits(19, 1) ? "R " : "", (int)bits(16, 3) + 2, ex);
+        f[0] = (bits(76, 1) ? "TU; " : "") + a; f[1] = b; f[2] = buf;
+        return true;
+    }
+    if (i3 == 5) {                                                      // EU VHF contest: h12 h22 R1 r3 s11 g25
+        if (!(mask & FT8RX_MT_EU_VHF)) return false;
+        uint32_t g = (uint32_t)bits(3, 25);
+        if (g >= 18662400u) return false;
+        char loc[7]; loc[6] = 0;
+        loc[5] = (char)('A' + g % 24); g /= 24; loc[4] = (char)('A' + g % 24); g /= 24; loc[3] = (char)('0' + g % 10); g /= 10;
+        loc[2] = (char)('0' + g % 10); g /= 10; loc[1] = (char)('A' + g % 18); g /= 18; loc[0] = (char)('A' + g);
+        snprintf(buf, sizeof buf, "%s%02d%04u %s", bits(42, 1) ? "R " : "", 52 + (int)bits(39, 3), (unsigned)bits(28, 11), loc);
+        f[0] = hashed((uint32_t)bits(65, 12), 12); f[1] = hashed((uint32_t)bits(43, 22), 22); f[2] = buf;
+        return true;
+    }
+    return false;
+}
+// the message's text (duplicate filter, ALL.TXT line): the reference's " ".join(msg_tuple) for i3 = 1, 2, 4; the empty fields of free
+// text and telemetry are left out for the opt-in types
+static std::string msg_line(uint64_t lo, const std::string f[3]) {
+    const unsigned i3 = (unsigned)(lo & 7u);
+    if (i3 == 0 || i3 == 3 || i3 == 5) return f[1].empty() ? f[0] : f[0] + " " + f[1] + " " + f[2];
+    return f[0] + " " + f[1] + " " + f[2];
+}
+// the output row types of the packager: ft8rx_message (ft8rx_package_batch / _packed) and ft8rx_message_ext (ft8rx_package_batch_ext)
+static void set_type(ft8rx_message&, uint64_t) {}
+static void set_type(ft8rx_message_ext& o, uint64_t lo) { o.i3 = (uint8_t)(lo & 7u); o.n3 = o.i3 == 0 ? (uint8_t)((lo >> 3) & 7u) : 0; }
 struct Ev { int cand, ipass, slot, seq; uint64_t lo, hi; };
 static bool ev_before(const Ev& a, const Ev& b) {          // the reference's call order: candidate, ladder step, attempt, order inside it
     if (a.cand != b.cand) return a.cand < b.cand;
@@ -236,8 +326,10 @@ static_assert(FT8RX_MAX_CANDS <= PKG_MAX_CANDS, "message layer capacity");
 // sparse = the records of a packed result buffer (include/ft8rx.h): only the candidates that decoded or logged an event, in candidate
 // order, each carrying its candidate index in pad2.  The replay never looks at any other candidate, and a stable sort orders a
 // subset exactly as it orders it inside the full list, so the messages are the ones the dense arrays give.
-static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, int nev, ft8rx_message* out, int cap, Hashes& H, int* flags,
-                         bool sparse = false) {
+// mask: the opt-in message types (unpack_ext); 0 for ft8rx_message rows
+template <typename Msg>
+static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, int nev, Msg* out, int cap, Hashes& H, int* flags,
+                         bool sparse = false, unsigned mask = 0) {
     std::vector<Ev> E; E.reserve((size_t)nev);
     int16_t pos[PKG_MAX_CANDS];
     if (sparse) {
@@ -278,17 +370,19 @@ static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, 
                 if (here && (it->slot > sslot || (it->slot == sslot && it->seq > sseq))) break;
                 if (it->slot == pslot && it->seq == pseq) continue;          // the same call logged twice
                 pslot = it->slot; pseq = it->seq;
-                const bool ok = unpack(it->lo, it->hi, H, f);
+                const bool ok = unpack_ext(it->lo, it->hi, mask, H, f);
                 if (here && it->slot == sslot && it->seq == sseq) { have = ok; if (ok) { got[0] = f[0]; got[1] = f[1]; got[2] = f[2]; } }
             }
             if (!here) continue;
-            if (!have) { have = unpack(r.msg_lo, r.msg_hi, H, got); if (!have) continue; }    // event log truncated
-            std::string text = got[0] + " " + got[1] + " " + got[2];
+            if (!have) { have = unpack_ext(r.msg_lo, r.msg_hi, mask, H, got); if (!have) continue; }    // event log truncated
+            std::string text = msg_line(r.msg_lo, got);
             if (std::find(seen.begin(), seen.end(), text) != seen.end()) continue;
             seen.push_back(text);
             if (nm < cap) {
-                ft8rx_message& o = out[nm]; memset(&o, 0, sizeof(o));
-                for (int k = 0; k < 3; k++) { const size_t L = got[k].size() < 15 ? got[k].size() : 15; memcpy(o.f[k], got[k].data(), L); }      // (o is zeroed: NUL-terminated)
+                Msg& o = out[nm]; memset(&o, 0, sizeof(o));
+                const size_t W = sizeof(o.f[0]) - 1;
+                for (int k = 0; k < 3; k++) { const size_t L = got[k].size() < W ? got[k].size() : W; memcpy(o.f[k], got[k].data(), L); }      // (o is zeroed: NUL-terminated)
+                set_type(o, r.msg_lo);
                 o.cand = (int16_t)(sparse ? (int)r.pad2 : i); o.f0_idx = r.f0_idx; o.h0_idx = r.h0_idx; o.ipass = r.ipass; o.ap = r.ap; o.method = r.method;
                 const bool fine = rnd >= 2;
                 o.fine = fine; o.snr = fine ? r.snr_fine : r.snr_grid; o.ttweak = fine ? r.ttweak : 0; o.ftweak = fine ? r.ftweak : 0;
@@ -334,9 +428,11 @@ static void encode_tones(uint64_t lo, uint64_t hi, uint8_t* t) {
 
 // records/events of n_frames frames -> messages; table == nullptr: a fresh hash table per frame (frames spread over n_threads
 // threads); table != nullptr: frames in order on the caller's thread, all sharing (and updating) that table.
+// mask: the opt-in message types (ft8rx_package_batch_ext; Msg = ft8rx_message_ext)
+template <typename Msg>
 static int package_batch(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
-                         int n_frames, int max_cands, ft8rx_message* out, int max_msgs, int32_t* out_counts, int n_threads,
-                         Hashes* table, int32_t* flags) {
+                         int n_frames, int max_cands, Msg* out, int max_msgs, int32_t* out_counts, int n_threads,
+                         Hashes* table, int32_t* flags, unsigned mask = 0) {
     if (!records || !counts || !events || !event_counts || !out || !out_counts || n_frames < 1 || max_cands < 1 || max_msgs < 1) return -1;
     if (n_threads < 1 || table) n_threads = 1;
     if (n_threads > n_frames) n_threads = n_frames;
@@ -351,7 +447,7 @@ static int package_batch(const ft8rx_record* records, const int32_t* counts, con
             int n = counts[f] < 0 ? 0 : (counts[f] > max_cands ? max_cands : counts[f]);
             if (!table) local.clear();
             out_counts[f] = package_frame(records + (size_t)f * max_cands, n, events + (size_t)f * FT8RX_EVENT_CAP, nev,
-                                          out + (size_t)f * max_msgs, max_msgs, table ? *table : local, &fl);
+                                          out + (size_t)f * max_msgs, max_msgs, table ? *table : local, &fl, false, mask);
             if (flags) flags[f] = fl;
         }
     };

@@ -28,10 +28,11 @@ __device__ unsigned long long g_bp_t[65536][8];
 #define BT_DECL
 #define BT(i) do { } while (0)
 #endif
+template <bool EXT>                   // EXT: the opt-in message types mt (ft8rx_set_msg_types, ft8_valid77_ext); the k_bp / k_bp_ext pair below
 FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ llr_in, ft8rx_record* __restrict__ rec,
                         const int32_t* __restrict__ ncand, Att* __restrict__ attG, Att* __restrict__ attB,
                         float* __restrict__ saved, ft8rx_event* ev, int32_t* evcount, const ft8rx_config& cfg,
-                        int max_nc0, int max_iters) {
+                        int max_nc0, int max_iters, unsigned mt) {
     __shared__ float llr[176];
     __shared__ float tl[576];        // 9 x 64 edge slots: slots >= 522 are dummy edges (variable 174, check 83) so that the
     // per-edge code below is straight-line for all nine slots of a lane.  The message deltas overwrite the tanh values in place: a
@@ -69,7 +70,7 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
             const uint64_t b0 = __ballot(ap_value(g, lane, llr[lane]) > 0.0f);
             const uint64_t b1 = __ballot(lane < 27 && ap_value(g, 64 + lane, llr[64 + (lane < 27 ? lane : 0)]) > 0.0f);
             uint64_t lo, hi;
-            const int r = ft8_crc_check_wave(b0, b1, lane, &lo, &hi);
+            const int r = ft8_crc_check_wave<EXT>(b0, b1, lane, &lo, &hi, mt);
             if (r) { if (lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), 2, g, 0, lo, hi, r == 2); }
             if (r == 2) { resG.ok = 1; resG.lo = lo; resG.hi = hi; resG.n_its = 0; resG.method = FT8RX_M_GOOD91; any = true; }
             if (lane == 0) attG[vec * 2 + g] = resG;
@@ -103,7 +104,7 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
             uint64_t b0 = h0;
             uint64_t b1 = h1 & ((1ull << 27) - 1);
             uint64_t lo, hi;
-            int r = ft8_crc_check_wave(b0, b1, lane, &lo, &hi);
+            int r = ft8_crc_check_wave<EXT>(b0, b1, lane, &lo, &hi, mt);
             if (r) {
                 int ipass = (mode == 0) ? 0 : ((ap < 2 && res.nc0 <= cfg.bp_nc0_a && it < cfg.bp_iters_a) ? 3 : 4);
                 if (lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), ipass, ap, it + 1, lo, hi, r == 2);
@@ -192,31 +193,40 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
 // very uneven: the hardware's block dispatcher balances them better than a strided loop, and the straight-line kernel allocates
 // registers better); blocks beyond the list exit after one load.
 // mode 0: the list holds attempts (candidate * 5 + ap) that survived bp0_precheck; mode 1: candidates, AP variants ap_lo .. ap_lo + ap_n - 1
-__global__ __launch_bounds__(64, BP_WV) void k_bp(int mode, const float* __restrict__ llr_in, ft8rx_record* __restrict__ rec,
-                                           const int32_t* __restrict__ ncand, Att* __restrict__ attG, Att* __restrict__ attB,
-                                           float* __restrict__ saved, ft8rx_event* ev, int32_t* evcount, ft8rx_config cfg,
-                                           int max_nc0, int max_iters, WorkList work, int ap_lo, int ap_n) {
-    if (mode == 2) { bp_attempt(threadIdx.x, 2, blockIdx.x, llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters); return; }
-    // ipass 0: bounded grid (ladder_grid).  The host does not know the list's length, and the grid sized for the worst case (every
-    // candidate x 5 variants: 327 k blocks per 256 frames for ~25 k pending attempts) spent a quarter of the launch dispatching
-    // blocks that load the count and exit: 0.158 -> 0.12 ms.  With the cap nearly every block still runs at most one attempt.
-    if (mode == 0) {
-        const int n = *work.count;
-#pragma unroll 1
-        for (int item = blockIdx.x; item < n; item += gridDim.x) {
-            int tid = threadIdx.x;
-            asm volatile("" : "+v"(tid));                           // opaque per attempt: nothing thread-specific is carried across attempts (else 100 B of scratch)
-            bp_attempt(tid, 0, work.items[item], llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters);
-            __syncthreads();                                        // the LDS arrays are reused by the next attempt
-        }
-        return;
-    }
-    // fine stage: one attempt per block, blocks beyond the list exit after one load (the looped form measured 4 % slower here: the
-    // lists are a sixth to a half of the worst case, and the loop costs the attempt's code more than the empty blocks cost the launch)
-    const int item = blockIdx.x;
-    if (item >= *work.count * ap_n) return;
-    bp_attempt(threadIdx.x, mode, work.items[item / ap_n] * 5 + ap_lo + item % ap_n, llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters);
+// k_bp: a handle with msg_types = 0 (the reference's predicate; the code it always was); k_bp_ext: msg_types != 0, passed as the last
+// argument.  The body is stamped into both kernels (a shared __device__ body that takes the kernel's by-value config by reference cost
+// k_bp a 12-byte spill).
+#define BP_KERNEL(NAME, EXT, MT_PARAM, MT)                                                                                                                       \
+__global__ __launch_bounds__(64, BP_WV) void NAME(int mode, const float* __restrict__ llr_in, ft8rx_record* __restrict__ rec,                         \
+                                           const int32_t* __restrict__ ncand, Att* __restrict__ attG, Att* __restrict__ attB,                         \
+                                           float* __restrict__ saved, ft8rx_event* ev, int32_t* evcount, ft8rx_config cfg,                            \
+                                           int max_nc0, int max_iters, WorkList work, int ap_lo, int ap_n MT_PARAM) {                                      \
+    if (mode == 2) { bp_attempt<EXT>(threadIdx.x, 2, blockIdx.x, llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters, MT); return; }\
+    /* ipass 0: bounded grid (ladder_grid).  The host does not know the list's length, and the grid sized for the worst case (every */                \
+    /* candidate x 5 variants: 327 k blocks per 256 frames for ~25 k pending attempts) spent a quarter of the launch dispatching */                   \
+    /* blocks that load the count and exit: 0.158 -> 0.12 ms.  With the cap nearly every block still runs at most one attempt. */                     \
+    if (mode == 0) {                                                                                                                                  \
+        const int n = *work.count;                                                                                                                    \
+_Pragma("unroll 1")                                                                                                                                   \
+        for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                                    \
+            int tid = threadIdx.x;                                                                                                                    \
+            asm volatile("" : "+v"(tid));                           /* opaque per attempt: nothing thread-specific is carried across attempts (else 100 B of scratch) */\
+            bp_attempt<EXT>(tid, 0, work.items[item], llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters, MT);                   \
+            __syncthreads();                                        /* the LDS arrays are reused by the next attempt */                               \
+        }                                                                                                                                             \
+        return;                                                                                                                                       \
+    }                                                                                                                                                 \
+    /* fine stage: one attempt per block, blocks beyond the list exit after one load (the looped form measured 4 % slower here: the */                \
+    /* lists are a sixth to a half of the worst case, and the loop costs the attempt's code more than the empty blocks cost the launch) */            \
+    const int item = blockIdx.x;                                                                                                                      \
+    if (item >= *work.count * ap_n) return;                                                                                                           \
+    bp_attempt<EXT>(threadIdx.x, mode, work.items[item / ap_n] * 5 + ap_lo + item % ap_n, llr_in, rec, ncand, attG, attB, saved, ev, evcount, cfg, max_nc0, max_iters, MT);\
 }
+#define BP_MT_PARAM , unsigned mt
+BP_KERNEL(k_bp, false, , 0u)
+BP_KERNEL(k_bp_ext, true, BP_MT_PARAM, mt)
+#undef BP_MT_PARAM
+#undef BP_KERNEL
 
 // first success in ladder order after ipass 0 (receiver.py:72-78)
 __global__ void k_select0(ft8rx_record* rec, const int32_t* ncand, const Att* att0, int B, int sh, WorkList next) {

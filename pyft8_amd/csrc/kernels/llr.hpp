@@ -81,8 +81,10 @@ FT8_DEV ChkMasks chk_masks(int lane) {
     c.m[3] = d_CHK_MASK[lane + 64][0]; c.m[4] = d_CHK_MASK[lane + 64][1]; c.m[5] = d_CHK_MASK[lane + 64][2];
     return c;
 }
+template <bool EXT>
 FT8_DEV void bp0_precheck(int lane, const float* llr /*LDS [174]*/, const ChkMasks& cm, int frame, int ci,
-                          Att* __restrict__ att /*this candidate's [5]*/, ft8rx_event* ev, int32_t* evcount, int max_nc0, int max_iters) {
+                          Att* __restrict__ att /*this candidate's [5]*/, ft8rx_event* ev, int32_t* evcount, int max_nc0, int max_iters,
+                          unsigned msg_types) {
     const float v0 = llr[lane], v1 = llr[64 + lane], v2 = llr[128 + (lane < 46 ? lane : 0)];
     const uint64_t m27 = (1ull << 27) - 1;
     uint64_t h0[5], h1[5];
@@ -114,7 +116,7 @@ FT8_DEV void bp0_precheck(int lane, const float* llr /*LDS [174]*/, const ChkMas
         const uint64_t my0 = lane == 0 ? h0[0] : lane == 1 ? h0[1] : lane == 2 ? h0[2] : lane == 3 ? h0[3] : h0[4];
         const uint64_t my1 = lane == 0 ? h1[0] : lane == 1 ? h1[1] : lane == 2 ? h1[2] : lane == 3 ? h1[3] : h1[4];
         myn = lane == 0 ? nchk[0] : lane == 1 ? nchk[1] : lane == 2 ? nchk[2] : lane == 3 ? nchk[3] : nchk[4];
-        if (syn == 0) r = ft8_crc_check(my0, my1 & m27, &lo, &hi);
+        if (syn == 0) r = ft8_crc_check<EXT>(my0, my1 & m27, &lo, &hi, msg_types);
     }
     const uint64_t okm = __ballot(r == 2);
     const int first = okm ? __builtin_ctzll(okm) : 5;
@@ -131,11 +133,12 @@ FT8_DEV void bp0_precheck(int lane, const float* llr /*LDS [174]*/, const ChkMas
 }
 
 // block of 64 = one candidate (or one test triple when `trip` is given)
-__global__ __launch_bounds__(64) void k_grid_llr(const float* __restrict__ grid, ft8rx_record* __restrict__ rec,
-                                                 const int32_t* __restrict__ ncand, float* __restrict__ llr0,
-                                                 ft8rx_config cfg, const int32_t* __restrict__ trip, float* __restrict__ t_sd,
-                                                 int32_t* __restrict__ t_snr, Att* __restrict__ att0, ft8rx_event* ev,
-                                                 int32_t* evcount, int B) {
+template <bool EXT>
+FT8_DEV void k_grid_llr_body(const float* __restrict__ grid, ft8rx_record* __restrict__ rec,
+                             const int32_t* __restrict__ ncand, float* __restrict__ llr0,
+                             const ft8rx_config& cfg, const int32_t* __restrict__ trip, float* __restrict__ t_sd,
+                             int32_t* __restrict__ t_snr, Att* __restrict__ att0, ft8rx_event* ev,
+                             int32_t* evcount, int B, unsigned mt) {
     __shared__ float p[464];
     __shared__ float llr[174];
     __shared__ float sq[174];
@@ -177,8 +180,22 @@ __global__ __launch_bounds__(64) void k_grid_llr(const float* __restrict__ grid,
         }
     }
     if (att0 && !(sd <= cfg.llr_sd_min))        // pipeline: the candidate stays ACTIVE -> pre-check its five ipass-0 attempts
-        bp0_precheck(lane, llr, cm, frame, ci, att0 + slot * 5, ev, evcount, cfg.bp_nc0_a, cfg.bp_iters_a);
+        bp0_precheck<EXT>(lane, llr, cm, frame, ci, att0 + slot * 5, ev, evcount, cfg.bp_nc0_a, cfg.bp_iters_a, mt);
 }
+// k_grid_llr: msg_types = 0 (the reference's predicate at GOOD91); k_grid_llr_ext: msg_types != 0, passed as the last argument
+#define GRID_LLR_KERNEL(NAME, EXT, MT_PARAM, MT)                                                                                               \
+__global__ __launch_bounds__(64) void NAME(const float* __restrict__ grid, ft8rx_record* __restrict__ rec,                          \
+                                           const int32_t* __restrict__ ncand, float* __restrict__ llr0,                            \
+                                           ft8rx_config cfg, const int32_t* __restrict__ trip, float* __restrict__ t_sd,           \
+                                           int32_t* __restrict__ t_snr, Att* __restrict__ att0, ft8rx_event* ev,                   \
+                                           int32_t* evcount, int B MT_PARAM) {                                                    \
+    k_grid_llr_body<EXT>(grid, rec, ncand, llr0, cfg, trip, t_sd, t_snr, att0, ev, evcount, B, MT);                                 \
+}
+#define GRID_LLR_MT_PARAM , unsigned mt
+GRID_LLR_KERNEL(k_grid_llr, false, , 0u)
+GRID_LLR_KERNEL(k_grid_llr_ext, true, GRID_LLR_MT_PARAM, mt)
+#undef GRID_LLR_MT_PARAM
+#undef GRID_LLR_KERNEL
 #endif  // FT8RX_ILP_UNIT
 
 #endif

@@ -198,12 +198,13 @@ FT8_DEV unsigned osd_syndrome(uint64_t w0, uint64_t w1) { return ft8_crc_syndrom
 // NANV: the kernel of the attempts whose vector holds a NaN (k_osd_nan / k_osd_nan_wide).  The library sorts such a vector with std::sort
 // -- a serial algorithm, run by one lane, whose code costs the main kernel 8 VGPRs and a scratch frame if it lives there: the main kernels
 // (NANV = false) only append such an attempt to `nanlist` and leave; the NaN kernels stride over that list (almost always empty).
-template <bool WIDE, bool NANV>
+// EXT: the opt-in message types mt (ft8rx_set_msg_types, ft8_valid77_ext with osd = true: free text and telemetry are never accepted here)
+template <bool WIDE, bool NANV, bool EXT = false>
 FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ llr_in, const float* __restrict__ saved,
                          const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,
                          const int32_t* __restrict__ ncand, Att* __restrict__ attO,
                          ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,
-                         int nflip, int max_hd, int sh, const WorkList& nanlist) {
+                         int nflip, int max_hd, int sh, const WorkList& nanlist, unsigned mt = 0) {
     __shared__ float llr[176];
     __shared__ uint64_t skey[256];
     __shared__ uint64_t ftab[192];                         // per column (natural order): bit i = flip i covers it (i < 62), bit 63 = order-0 codeword bit
@@ -587,7 +588,7 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
             const int hd = __popcll(w0 ^ hard0) + __popcll(w1 ^ hard1) + __popcll((w2 ^ hard2) & M2);
             if (max_hd > 0 && hd > max_hd) continue;          // gate (extension): no unpack() call beyond max_hd
             uint64_t lo = 0, hi = 0;
-            const int r = ft8_crc_check(w0, w1 & M1, &lo, &hi);
+            const int r = ft8_crc_check<EXT>(w0, w1 & M1, &lo, &hi, mt, true);
             const int t = base + hl;
             if (r && lane == 0) log_event(ev, evcount, (int)(vec / 10) >> sh, (int)(vec / 10) & ((1 << sh) - 1), ipass, slot, t, lo, hi, r == 2);   // a call the reference made (mode 0: vec = candidate * 10 + slot)
             if (r == 2) {
@@ -613,42 +614,49 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
 #ifndef OSD_ATTR
 #define OSD_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))
 #endif
-#define OSD_KERNEL(NAME, WIDE)                                                                                                       \
+// k_osd* : a handle with msg_types = 0 (the reference's predicate); k_osd*_ext: msg_types != 0, passed as the last argument
+#define OSD_KERNEL(NAME, WIDE, EXT, MT_PARAM, MT)                                                                                    \
 __global__ __launch_bounds__(64) OSD_ATTR void NAME(int mode, const float* __restrict__ llr_in, const float* __restrict__ saved,             \
                                            const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,                            \
                                            const int32_t* __restrict__ ncand, Att* __restrict__ attO,                               \
                                            ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,        \
-                                           int nflip, int max_hd, int sh, WorkList work, WorkList nanlist) {                        \
-    if (mode == 2) { osd_attempt<WIDE, false>(threadIdx.x, 2, blockIdx.x, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); return; } \
+                                           int nflip, int max_hd, int sh, WorkList work, WorkList nanlist MT_PARAM) {               \
+    if (mode == 2) { osd_attempt<WIDE, false, EXT>(threadIdx.x, 2, blockIdx.x, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist, MT); return; } \
     const int n = *work.count * 10;                                                                                                 \
     _Pragma("unroll 1")                                                                                                             \
     for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                      \
         int lane = threadIdx.x;                                                                                                     \
         asm volatile("" : "+v"(lane));       /* opaque per item: nothing lane-specific is hoisted across attempts (register pressure) */ \
-        osd_attempt<WIDE, false>(lane, 0, work.items[item / 10] * 10 + item % 10, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); \
+        osd_attempt<WIDE, false, EXT>(lane, 0, work.items[item / 10] * 10 + item % 10, llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist, MT); \
         __syncthreads();                     /* the LDS arrays are reused by the next attempt */                                   \
     }                                                                                                                               \
 }
-OSD_KERNEL(k_osd, false)
-OSD_KERNEL(k_osd_wide, true)        /* more than OSD_FLIPS_A flip rows */
+#define OSD_MT_PARAM , unsigned mt
+OSD_KERNEL(k_osd, false, false, , 0u)
+OSD_KERNEL(k_osd_wide, true, false, , 0u)        /* more than OSD_FLIPS_A flip rows */
+OSD_KERNEL(k_osd_ext, false, true, OSD_MT_PARAM, mt)
+OSD_KERNEL(k_osd_wide_ext, true, true, OSD_MT_PARAM, mt)
 #undef OSD_KERNEL
 // the attempts the main kernels left on `nanlist` (attempt ids as they got them: candidate * 10 + slot, or the vector index in mode 2)
-#define OSD_NAN_KERNEL(NAME, WIDE)                                                                                                   \
+#define OSD_NAN_KERNEL(NAME, WIDE, EXT, MT_PARAM, MT)                                                                                \
 __global__ __launch_bounds__(64) void NAME(int mode, const float* __restrict__ llr_in, const float* __restrict__ saved,             \
                                            const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,                            \
                                            const int32_t* __restrict__ ncand, Att* __restrict__ attO,                               \
                                            ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,        \
-                                           int nflip, int max_hd, int sh, WorkList nanlist) {                                       \
+                                           int nflip, int max_hd, int sh, WorkList nanlist MT_PARAM) {                              \
     const int n = *nanlist.count;                                                                                                   \
     _Pragma("unroll 1")                                                                                                             \
     for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                      \
-        osd_attempt<WIDE, true>(threadIdx.x, mode, nanlist.items[item], llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist); \
+        osd_attempt<WIDE, true, EXT>(threadIdx.x, mode, nanlist.items[item], llr_in, saved, attB, rec, ncand, attO, ev, evcount, trials, ntr, nflip, max_hd, sh, nanlist, MT); \
         __syncthreads();                                                                                                            \
     }                                                                                                                               \
 }
-OSD_NAN_KERNEL(k_osd_nan, false)
-OSD_NAN_KERNEL(k_osd_nan_wide, true)
+OSD_NAN_KERNEL(k_osd_nan, false, false, , 0u)
+OSD_NAN_KERNEL(k_osd_nan_wide, true, false, , 0u)
+OSD_NAN_KERNEL(k_osd_nan_ext, false, true, OSD_MT_PARAM, mt)
+OSD_NAN_KERNEL(k_osd_nan_wide_ext, true, true, OSD_MT_PARAM, mt)
 #undef OSD_NAN_KERNEL
+#undef OSD_MT_PARAM
 #define OSD_NAN_GRID 512             /* blocks of the NaN kernels: they stride over a list that is almost always empty */
 
 #endif

@@ -29,5 +29,9 @@ __global__ void k_valid_probe(const uint64_t* lo, const uint64_t* hi, int n, int
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = ft8_valid77(lo[i], hi[i]) ? 1 : 0;
 }
+__global__ void k_valid_ext_probe(const uint64_t* lo, const uint64_t* hi, int n, unsigned mask, int32_t* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = ft8_valid77_ext(lo[i], hi[i], mask) ? 1 : 0;
+}
 
 #endif

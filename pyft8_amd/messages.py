@@ -8,6 +8,7 @@ effects in the reference's call order.  Written table-driven from the FT8 messag
 import time
 
 from .ft8_tables import PFX1_MASK, PFX1_TRAP, PFX2_BITMAP
+from .ft8_msg_tables import MULT, SECTIONS
 
 A37 = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"
 A38 = A37 + "/"
@@ -134,6 +135,114 @@ def unpack(bits77, table):
     return None
 
 
+# ---- opt-in message types (config msg_types; include/ft8rx.h FT8RX_MT_*).  Bit layouts: Franke, Somerville, Taylor, "The FT4 and FT8
+# Communication Protocols", QEX 2020.  The reference renders none of these (decoders.py:16-49 returns None).
+MT_FREE_TEXT, MT_DXPEDITION, MT_FIELD_DAY, MT_TELEMETRY, MT_RTTY_RU, MT_EU_VHF = 1, 2, 4, 8, 16, 32
+MT_ALL = 63
+A42 = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ+-./?"
+LOC6 = 18 * 18 * 10 * 10 * 24 * 24
+
+
+def _c28(n28, table):
+    """A c28 field of the opt-in types: the i3 = 1 field rule without the suffix flag (standard calls enter the table)."""
+    return _field29(n28 << 1, 1, table)
+
+
+def _bits(v, pos, n):
+    return (v >> pos) & ((1 << n) - 1)
+
+
+def unpack_ext(bits77, table, mask):
+    """unpack() with the opt-in message types of `mask`: -> (first, second, rest) or None.  mask = 0 and i3 = 1, 2, 4 are unpack().
+    None exactly where the device gate (csrc/ft8_dev.h: ft8_valid77_ext) rejects the word outside OSD.  Both c28 fields are rendered
+    (and enter the table) before any range check, as in host_messages.hpp."""
+    i3, n3 = bits77 & 7, (bits77 >> 3) & 7
+    if not mask or not bits77 or i3 in (1, 2, 4):
+        return unpack(bits77, table)
+    if i3 == 0:
+        v71 = bits77 >> 6
+        if n3 == 0:                                       # free text: 13 characters of A42, first character most significant
+            if not mask & MT_FREE_TEXT or v71 >= 42 ** 13:
+                return None
+            s = ""
+            for _ in range(13):
+                v71, r = divmod(v71, 42)
+                s = A42[r] + s
+            return (s.strip(), "", "")
+        if n3 == 5:                                       # telemetry: 18 hex digits, leading zeros dropped
+            if not mask & MT_TELEMETRY or v71 == 0:
+                return None
+            return ("%X" % v71, "", "")
+        if n3 == 1:                                       # DXpedition: c28 c28 h10 r5
+            if not mask & MT_DXPEDITION:
+                return None
+            a, b = _c28(_bits(bits77, 49, 28), table), _c28(_bits(bits77, 21, 28), table)
+            if a is None or b is None:
+                return None
+            return (a + " RR73;", b, "<%s> %+03d" % (table.lookup(_bits(bits77, 11, 10), 10), 2 * _bits(bits77, 6, 5) - 30))
+        if n3 in (3, 4):                                  # ARRL Field Day: c28 c28 R1 n4 k3 s7
+            if not mask & MT_FIELD_DAY:
+                return None
+            a, b = _c28(_bits(bits77, 49, 28), table), _c28(_bits(bits77, 21, 28), table)
+            s7 = _bits(bits77, 6, 7)
+            if a is None or b is None or not 1 <= s7 <= len(SECTIONS):
+                return None
+            ntx = _bits(bits77, 16, 4) + 1 + (16 if n3 == 4 else 0)
+            return (a, b, "%s%d%s %s" % ("R " if _bits(bits77, 20, 1) else "", ntx, chr(65 + _bits(bits77, 13, 3)), SECTIONS[s7 - 1]))
+        return None
+    if i3 == 3:                                           # ARRL RTTY Roundup: t1 c28 c28 R1 r3 s13
+        if not mask & MT_RTTY_RU:
+            return None
+        a, b = _c28(_bits(bits77, 48, 28), table), _c28(_bits(bits77, 20, 28), table)
+        s13 = _bits(bits77, 3, 13)
+        if a is None or b is None:
+            return None
+        if 1 <= s13 <= 7999:
+            ex = "%04d" % s13
+        elif 8001 <= s13 <= 8000 + len(MULT):
+            ex = MULT[s13 - 8001]
+        else:
+            return None
+        return (("TU; " if _bits(bits77, 76, 1) else "") + a, b,
+                "%s5%d9 %s" % ("R " if _bits(bits77, 19, 1) else "", _bits(bits77, 16, 3) + 2, ex))
+    if i3 == 5:                                           # EU VHF contest: h12 h22 R1 r3 s11 g25
+        if not mask & MT_EU_VHF:
+            return None
+        g = _bits(bits77, 3, 25)
+        if g >= LOC6:
+            return None
+        loc = ""
+        for size, base in ((24, "A"), (24, "A"), (10, "0"), (10, "0"), (18, "A")):
+            g, r = divmod(g, size)
+            loc = chr(ord(base) + r) + loc
+        loc = chr(65 + g) + loc
+        return ("<%s>" % table.lookup(_bits(bits77, 65, 12), 12), "<%s>" % table.lookup(_bits(bits77, 43, 22), 22),
+                "%s%02d%04d %s" % ("R " if _bits(bits77, 42, 1) else "", 52 + _bits(bits77, 39, 3), _bits(bits77, 28, 11), loc))
+    return None
+
+
+def valid77_ext(bits77, mask, osd=False):
+    """The device predicate ft8_valid77_ext (csrc/ft8_dev.h) in Python: does unpack_ext render the word?  osd: the word comes from an
+    OSD trial, where free text and telemetry are never accepted."""
+    if osd and mask and (bits77 & 0x3F) in (0, 0x28):   # i3.n3 = 0.0 / 0.5
+        return False
+    return unpack_ext(bits77, CallHashes(), mask) is not None
+
+
+def msg_type(bits77):
+    """The type code of a 77-bit word as the message dict's "msg_type": "i3.n3" for i3 = 0, "i3" otherwise."""
+    i3 = bits77 & 7
+    return "0.%d" % ((bits77 >> 3) & 7) if i3 == 0 else str(i3)
+
+
+def _msg_text(bits77, text):
+    """A message's line (duplicate filter, ALL.TXT): " ".join(msg_tuple) for i3 = 1, 2, 4 (the reference's), the empty fields of free
+    text and telemetry left out for the opt-in types."""
+    if bits77 & 7 in (0, 3, 5):
+        return " ".join(x for x in text if x) if not text[1] else " ".join(text)
+    return " ".join(text)
+
+
 def decode_notes(rec):
     """'{source}_{AP}_{method}' + tweaks, formatted as the reference does (receiver.py:42,57,121,126,133,162)."""
     fine = rec["ipass"] >= 2
@@ -150,11 +259,12 @@ def tweaks_str(rec):
 _LAST_IPASS = {2: 0, 3: 1, 4: 1}     # status -> last ladder step taken (STOP_GRID_SD, STOP_COSTAS, STOP_FINE_SD)
 
 
-def package_frame(rec, count, events, n_events, cyclestart_string="", band=None, odd_even=0, table=None, on_message=None):
+def package_frame(rec, count, events, n_events, cyclestart_string="", band=None, odd_even=0, table=None, on_message=None, mask=0):
     """Replay one frame's candidate records in the reference's order (receiver.py:389-398):
     per round all live candidates advance one ipass in llr_sd-descending (stable) order; CRC-passing
     unpack() calls update the hash table as they happen; first sighting of a message text is emitted.
-    Returns the list of message dicts (reference receiver.py:61-64 keys)."""
+    Returns the list of message dicts (reference receiver.py:61-64 keys).  mask != 0: the opt-in message types are rendered too
+    (unpack_ext) and every dict gains "msg_type"."""
     table = table if table is not None else CallHashes()
     rec = rec[:count]
     n_ev = min(int(n_events), len(events))
@@ -189,15 +299,16 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
                 if (slot, seq) in done:
                     continue
                 done.add((slot, seq))
-                res = unpack(bits, table)
+                res = unpack_ext(bits, table, mask)
                 if stop_key == (slot, seq):
                     text = res
             if decoded_here:
+                word = (int(r["msg_hi"]) << 64) | int(r["msg_lo"])
                 if text is None:        # event log truncated: render at emit time
-                    text = unpack((int(r["msg_hi"]) << 64) | int(r["msg_lo"]), table)
+                    text = unpack_ext(word, table, mask)
                 if text is None:
                     continue
-                msg_text = " ".join(text)
+                msg_text = _msg_text(word, text)
                 if msg_text in seen:
                     continue
                 seen.add(msg_text)
@@ -214,6 +325,8 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
                      "all_txt_format": f"{cyclestart_string} {snr} {(tsec - 0.6):4.1f} {fHz:4.0f} ~ {msg_text}",
                      "cyclestart_string": cyclestart_string, "decode_completed": time.time(), "tweaks": tw,
                      "decode_notes": notes + tw}
+                if mask:
+                    m["msg_type"] = msg_type(word)
                 out.append(m)
                 if on_message is not None:
                     on_message(m)
@@ -230,7 +343,9 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
         return out
     # whole columns to Python lists first: field access on numpy structured scalars costs more than everything else here
     cols = [rows[k].tolist() for k in ("f", "h0_idx", "f0_idx", "ttweak", "ftweak", "snr", "ipass", "method", "ap", "fine")]
-    for f3, h0, f0, tt, ft, sn, ipass, method, ap, fn in zip(*cols):
+    ext = "i3" in rows.dtype.names                   # rows of ft8rx_package_batch_ext (_lib.MESSAGE_EXT_DTYPE): the opt-in types
+    types = list(zip(rows["i3"].tolist(), rows["n3"].tolist())) if ext else [None] * len(rows)
+    for f3, h0, f0, tt, ft, sn, ipass, method, ap, fn, ty in zip(*cols, types):
         text = tuple(x.decode() for x in f3)
         tsec = h0 / 25.0
         fHz = 3.125 * f0
@@ -240,9 +355,12 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
         snr = "%+03d" % sn
         rec = {"ipass": ipass, "method": method, "ap": ap, "ttweak": tt, "ftweak": ft}
         notes, tw = decode_notes(rec)
+        line = _msg_text(ty[0] | (ty[1] << 3), text) if ext else " ".join(text)
         d = {"band": band, "tsec": tsec, "fHz": fHz, "msg_tuple": text, "their_snr": snr, "their_tx_cycle": odd_even,
-             "all_txt_format": f"{cyclestart_string} {snr} {(tsec - 0.6):4.1f} {fHz:4.0f} ~ {' '.join(text)}",
+             "all_txt_format": f"{cyclestart_string} {snr} {(tsec - 0.6):4.1f} {fHz:4.0f} ~ {line}",
              "cyclestart_string": cyclestart_string, "decode_completed": now, "tweaks": tw, "decode_notes": notes + tw}
+        if ext:
+            d["msg_type"] = msg_type(ty[0] | (ty[1] << 3))
         out.append(d)
         if on_message is not None:
             on_message(d)

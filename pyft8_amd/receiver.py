@@ -57,12 +57,36 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
     if cfg.f0_lo < 4 or cfg.f0_hi > _lib.MAX_F0_WIDE or cfg.f0_lo >= cfg.f0_hi:
         raise _lib.Ft8rxError(f"search_freq_range={list(search_freq_range)}: supported are 12.5 .. {_lib.MAX_F0_WIDE * df:.0f} Hz, low < high "
                               "(above 3000 Hz the wide build libft8rx_wide.so is used; the reference fails beyond ~5940 Hz, receiver.py:181-182)")
+    mask = msg_types_mask(ext.pop("msg_types", 0))       # a handle setting, not a field of ft8rx_config (_lib.Config.msg_types)
     known = {f[0] for f in _lib.Config._fields_}
     for k, v in ext.items():          # extension knobs: bp_iters_b, osd_single, osd_double, osd_triple, osd_max_hd, ...
         if k not in known:            # like the reference's fixed signature (e.g. the CLI's misspelt `search_timerange`, pyft8.py:137)
             raise TypeError(f"Receiver() got an unexpected keyword argument '{k}'")
         setattr(cfg, k, v)
+    if mask:
+        cfg.msg_types = mask
     return cfg
+
+
+def msg_types_mask(msg_types):
+    """The msg_types kwarg (opt-in message types the reference leaves unimplemented; include/ft8rx.h FT8RX_MT_*) -> its bit mask:
+    an int, "all", or a collection of names from {"free_text", "dxpedition", "field_day", "telemetry", "rtty_ru", "eu_vhf"}."""
+    if isinstance(msg_types, str):
+        if msg_types != "all":
+            raise _lib.Ft8rxError(f'msg_types={msg_types!r}: "all", a set of {sorted(_lib.MSG_TYPE_BITS)} or an int bit mask')
+        return _lib.MT_ALL
+    if isinstance(msg_types, (int, np.integer)) and not isinstance(msg_types, bool):
+        if not 0 <= int(msg_types) <= _lib.MT_ALL:
+            raise _lib.Ft8rxError(f"msg_types={msg_types}: a bit mask in 0 .. {_lib.MT_ALL}")
+        return int(msg_types)
+    names = set(msg_types)
+    bad = names - set(_lib.MSG_TYPE_BITS)
+    if bad:
+        raise _lib.Ft8rxError(f"msg_types: unknown message type(s) {sorted(bad)}; known are {sorted(_lib.MSG_TYPE_BITS)}")
+    mask = 0
+    for n in names:
+        mask |= _lib.MSG_TYPE_BITS[n]
+    return mask
 
 
 def frames_from_ragged(frames):
@@ -654,14 +678,23 @@ class Receiver:
         finally:
             h.set_search_mask(None)
 
+    def _package(self, rec, cnt, ev, evc, **kw):
+        """The native host message layer for this receiver's config: ft8rx_package_batch, or ft8rx_package_batch_ext when the config
+        opts into more message types (msg_types != 0; rows of _lib.MESSAGE_EXT_DTYPE)."""
+        if self.cfg.msg_types:
+            return _lib.package_batch_ext(rec, cnt, ev, evc, self.cfg.msg_types, **kw)
+        return _lib.package_batch(rec, cnt, ev, evc, **kw)
+
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full"):
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
+        if self.cfg.msg_types and int(passes) > 1:
+            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with msg_types != 0")
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
-        msgs, mcnt = _lib.package_batch(rec, cnt, ev, evc)
+        msgs, mcnt = self._package(rec, cnt, ev, evc)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
         out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message)
                for f in range(B)]
@@ -734,6 +767,9 @@ class Receiver:
     def _decode_frames_arrays_locked(self, audio, B, n_threads, passes, subtract_min_snr, sub_pass_osd, research="full"):
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
+        if self.cfg.msg_types:
+            raise _lib.Ft8rxError("decode_frames_arrays returns _lib.MESSAGE_DTYPE rows, which cannot hold the message types of msg_types != 0: "
+                                  "use decode_frames")
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)
@@ -779,7 +815,7 @@ class Receiver:
             cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
             with self._live_lock:
                 rec, cnt, ev, evc = self._live_handle().decode_batch(frame[None])
-            msgs, mcnt = _lib.package_batch(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
+            msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
             dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC))
             seen = self._cycle_seen.setdefault(t0, set())
             for k in [k for k in self._cycle_seen if k < t0 - 4 * T_CYC]:

@@ -12,6 +12,8 @@ callsigns, f0 ~ U[200,2800] Hz, start = 0.5 s + U[-0.5,+1.0] s, SNR ~ U[lo,hi] d
 2500 Hz (WSJT-X convention), unit-variance white noise scaled to sigma = 1000 counts,
 clipped to int16.  RNG = numpy Philox keyed on (seed_base + frame index).
 """
+import re
+
 import numpy as np
 
 from .ft8_tables import GEN_HEX
@@ -92,6 +94,82 @@ def pack77(call_a, call_b, extra):
     v = (v << 15) | g15
     v = (v << 3) | i3
     return v
+
+
+# ----------------------------------------------------------------------------- opt-in message types (messages.unpack_ext is the inverse)
+_A42 = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ+-./?"
+_HEX = set("0123456789ABCDEF")
+
+
+def _c28_ext(call):
+    """A c28 field of the opt-in types: a standard call or one of the tokens DE / QRZ / CQ."""
+    return {"DE": 0, "QRZ": 1, "CQ": 2}[call] if call in ("DE", "QRZ", "CQ") else pack_c28(call)
+
+
+def _call_hash(text, nb):
+    """'<CALL>' -> its nb-bit call hash (databases.py:8-26 arithmetic); '<...>' has no hash to pack."""
+    from .messages import CallHashes
+    if not (text.startswith("<") and text.endswith(">")) or text == "<...>":
+        raise ValueError(f"not a hashed call: {text!r}")
+    t = CallHashes()
+    t.add(text[1:-1])
+    return dict((n, h) for h, n in t.by_call[text[1:-1]])[nb]
+
+
+def pack77_ext(text, msg_type=None):
+    """Text of one of the opt-in message types (messages.unpack_ext renders it back) -> 77-bit int.  The type is recognised from the
+    text (the forms of the table in DESIGN.md section 10: "TU; K1ABC W9XYZ 579 WI", "K1ABC RR73; W9XYZ <KH1/KH7Z> -08",
+    "K1ABC W9XYZ R 17B EMA", "<PA3XYZ> <G4ABC/P> R 590003 IO91NP"); anything else is free text, or telemetry when it is more than 13
+    hex digits.  msg_type = "free_text" / "telemetry" forces one of the two (a short hex string is free text otherwise)."""
+    from .ft8_msg_tables import MULT, SECTIONS
+    t = " ".join(text.split())
+    w = t.split(" ")
+    if msg_type == "free_text" or msg_type is None and not (len(t) > 13 and all(c in _HEX for c in t)):
+        m = re.fullmatch(r"(\S+) RR73; (\S+) (<\S+>) ([+-]\d\d)", t) if msg_type is None else None
+        if m:                                                                          # 0.1 DXpedition: c28 c28 h10 r5
+            r5 = (int(m.group(4)) + 30) // 2
+            if not 0 <= r5 <= 31 or 2 * r5 - 30 != int(m.group(4)):
+                raise ValueError(f"DXpedition report {m.group(4)}: even, -30 .. +32")
+            v = (_c28_ext(m.group(1)) << 28) | _c28_ext(m.group(2))
+            return (((((v << 10) | _call_hash(m.group(3), 10)) << 5) | r5) << 6) | (1 << 3)
+        m = re.fullmatch(r"(TU; )?(\S+) (\S+) (R )?5([2-9])9 (\d{4}|[A-Z]+)", t) if msg_type is None else None
+        if m:                                                                          # 3 RTTY Roundup: t1 c28 c28 R1 r3 s13
+            ex = m.group(6)
+            s13 = int(ex) if ex.isdigit() else 8001 + MULT.index(ex)
+            if not 1 <= s13 <= 8000 + len(MULT) or s13 == 8000:
+                raise ValueError(f"RTTY Roundup exchange {ex!r}")
+            v = (((1 if m.group(1) else 0) << 28) | _c28_ext(m.group(2))) << 28 | _c28_ext(m.group(3))
+            v = (((v << 1) | (1 if m.group(4) else 0)) << 3) | (int(m.group(5)) - 2)
+            return (((v << 13) | s13) << 3) | 3
+        m = re.fullmatch(r"(<\S+>) (<\S+>) (R )?5([2-9])(\d{4}) ([A-R][A-R]\d\d[A-X][A-X])", t) if msg_type is None else None
+        if m:                                                                          # 5 EU VHF: h12 h22 R1 r3 s11 g25
+            s11, loc = int(m.group(5)), m.group(6)
+            if s11 > 2047:
+                raise ValueError(f"EU VHF serial {s11} > 2047")
+            g = ord(loc[0]) - 65
+            for ch, size, base in zip(loc[1:], (18, 10, 10, 24, 24), "A00AA"):
+                g = g * size + ord(ch) - ord(base)
+            v = (_call_hash(m.group(1), 12) << 22) | _call_hash(m.group(2), 22)
+            v = (((v << 1) | (1 if m.group(3) else 0)) << 3) | (int(m.group(4)) - 2)
+            return (((((v << 11) | s11) << 25) | g) << 3) | 5
+        m = re.fullmatch(r"(\S+) (\S+) (R )?(\d{1,2})([A-H]) ([A-Z]+)", t) if msg_type is None else None
+        if m and m.group(6) in SECTIONS:                                               # 0.3 / 0.4 Field Day: c28 c28 R1 n4 k3 s7
+            ntx = int(m.group(4))
+            if not 1 <= ntx <= 32:
+                raise ValueError(f"Field Day transmitters {ntx}: 1 .. 32")
+            n3 = 3 if ntx <= 16 else 4
+            v = (_c28_ext(m.group(1)) << 28) | _c28_ext(m.group(2))
+            v = (((((v << 1) | (1 if m.group(3) else 0)) << 4) | (ntx - 1 - (16 if n3 == 4 else 0))) << 3) | (ord(m.group(5)) - 65)
+            return (((v << 7) | (1 + SECTIONS.index(m.group(6)))) << 6) | (n3 << 3)
+        if len(t) > 13 or any(c not in _A42 for c in t):                               # 0.0 free text: 13 characters, right-aligned
+            raise ValueError(f"free text {text!r}: at most 13 characters of {_A42!r}")
+        v = 0
+        for c in t.rjust(13):
+            v = v * 42 + _A42.index(c)
+        return v << 6
+    if msg_type not in (None, "telemetry") or len(t) > 18 or not t or (len(t) == 18 and t[0] > "7"):   # 0.5 telemetry: 71 bits
+        raise ValueError(f"telemetry {text!r}: at most 18 hex digits, below 2^71")
+    return (int(t, 16) << 6) | (5 << 3)
 
 
 def crc14(bits77):
