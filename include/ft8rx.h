@@ -37,6 +37,7 @@
  *     ft8rx_subtract  ft8rx_subtraction_list  ft8rx_encode_tones  ft8rx_merge_messages  ft8rx_set_search_mask   (f-4: subtraction passes)
  *     ft8rx_osd_ext                                                                    (order-3 / distance-gate knobs)
  *     ft8rx_set_msg_types  ft8rx_package_batch_ext  ft8rx_valid77_ext                  (opt-in message types)
+ *     ft8rx_set_ap_calls  ft8rx_set_ap_max_hd  ft8rx_ap_patterns  ft8rx_ap_calls_probe (opt-in a-priori calls, ipass 7)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
@@ -114,7 +115,8 @@ typedef struct {
 
 enum { FT8RX_ST_ACTIVE = 0, FT8RX_ST_DECODED = 1, FT8RX_ST_STOP_GRID_SD = 2, FT8RX_ST_STOP_COSTAS = 3,
        FT8RX_ST_STOP_FINE_SD = 4, FT8RX_ST_EXHAUSTED = 5 };
-enum { FT8RX_M_GOOD91 = 0, FT8RX_M_LDPC_A = 1, FT8RX_M_LDPC_B = 2, FT8RX_M_OSD = 3, FT8RX_M_LDPC_B_OSD = 4 };
+enum { FT8RX_M_GOOD91 = 0, FT8RX_M_LDPC_A = 1, FT8RX_M_LDPC_B = 2, FT8RX_M_OSD = 3, FT8RX_M_LDPC_B_OSD = 4,
+       FT8RX_M_AP_CODEWORD = 5 /* ipass 7, full pattern: codeword test (ft8rx_set_ap_calls) */ };
 
 /* One candidate's outcome (replaces the state of a reference `Candidate`, receiver.py:29-66). 48 bytes. */
 typedef struct {
@@ -122,10 +124,11 @@ typedef struct {
     float    score, grid_sd, fine_sd;
     int16_t  f0_idx, h0_idx;
     int8_t   ttweak, ftweak, snr_grid, snr_fine;
-    uint8_t  status, ipass, ap, method;
+    uint8_t  status, ipass, ap, method;  /* ipass 7 / ap 5..10: the opt-in a-priori step of ft8rx_set_ap_calls */
     int16_t  n_its;                  /* BP iteration index or OSD trial index of the success */
     uint8_t  nsync;
-    uint8_t  osd_hd;                 /* OSD decodes: Hamming distance of the accepted codeword to the 174 hard decisions */
+    uint8_t  osd_hd;                 /* OSD decodes: Hamming distance of the accepted codeword to the 174 hard decisions;
+                                      * ipass 7: the same distance to the hard decisions of the un-overridden fine LLRs */
     uint32_t pad2;
 } ft8rx_record;
 
@@ -135,8 +138,9 @@ typedef struct {
 typedef struct {
     uint64_t msg_lo, msg_hi;
     uint16_t cand;                   /* candidate index within the frame */
-    uint8_t  ipass;                  /* ladder step the call belongs to (0..6) */
-    uint8_t  slot;                   /* attempt index inside the ipass step (AP index / saved-llr index) */
+    uint8_t  ipass;                  /* ladder step the call belongs to (0..6; 7 = ft8rx_set_ap_calls) */
+    uint8_t  slot;                   /* attempt index inside the ipass step (AP index / saved-llr index; ipass 7: 2 * ap for BP and
+                                      * the codeword test, 2 * ap + 1 for OSD) */
     uint16_t seq;                    /* order inside the attempt: GOOD91=0, BP iteration+1, OSD trial */
     uint16_t valid;                  /* unpack() would have returned a tuple */
 } ft8rx_event;
@@ -286,6 +290,28 @@ int  ft8rx_set_ladder_mode(ft8rx_handle* h, int mode);
  * ft8rx_package_batch_ext; ft8rx_decode_messages and the packed output (ft8rx_set_packed_output) refuse a non-zero mask.  Applies to
  * batches enqueued afterwards.  A handle setting rather than a field of ft8rx_config, whose layout callers' bindings hard-code. */
 int  ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask);
+/* Opt-in a-priori decoding with the operator's own call and the DX station's call (extension).  NULL or ""
+ * = unset; both unset (the default) = the reference's ladder, same kernels and launches.  With a call set, a candidate the whole
+ * reference ladder left undecoded after the fine stage (status EXHAUSTED) gets ipass 7: the patterns whose calls are set --
+ * ap 5 "MY ???", 6 "MY DX ???", 7 "CQ DX ???" (known bits forced to +-5, BP_B then OSD) and 8 "MY DX RRR", 9 "MY DX 73",
+ * 10 "MY DX RR73" (a codeword test) -- accepted only if the codeword lies within ap_max_hd of the hard decisions of the
+ * un-overridden fine LLRs; the smallest distance wins (ties: pattern order).  Every record ipass 0..6 decodes is unchanged.  Only
+ * standard callsigns (3..6 letters / digits, the c28 form of i3 = 1 messages); anything else returns -1 naming the argument.
+ * Applies to batches enqueued afterwards and allocates nothing (cheap to call every cycle).  Refused with msg_types != 0 and with
+ * the packed output (ft8rx_set_packed_output). */
+#define FT8RX_AP_MAX_HD_DEFAULT 36
+int  ft8rx_set_ap_calls(ft8rx_handle* h, const char* my_call, const char* dx_call);
+/* the ipass-7 acceptance gate (1..174; default FT8RX_AP_MAX_HD_DEFAULT) */
+int  ft8rx_set_ap_max_hd(ft8rx_handle* h, int32_t max_hd);
+/* Host only (tests): the six patterns ap 5..10 of (my_call, dx_call) as [6][174] bytes in LLR order -- bits_out the known values
+ * (full patterns: the 174-bit codeword), mask_out which positions are known (0 for a pattern whose calls are unset).  -1 for
+ * a call that is not a standard callsign (ft8rx_last_error(NULL)). */
+int  ft8rx_ap_patterns(const char* my_call, const char* dx_call, uint8_t* bits_out, uint8_t* mask_out);
+/* Test entry: ipass 7 alone, with the handle's setting, on n <= cfg.max_cands fine-LLR vectors [n][174] taken as the candidates
+ * 0 .. n - 1 of one frame that the reference's ladder left undecoded -- the batch's own launch sequence.  -> their records (ipass 7
+ * and ap / method / osd_hd where a pattern was accepted, status EXHAUSTED otherwise) and the frame's event log (events: FT8RX_EVENT_CAP
+ * entries; *event_count may exceed that).  -1 while no call is set. */
+int  ft8rx_ap_calls_probe(ft8rx_handle* h, const float* llr, int n, ft8rx_record* records, ft8rx_event* events, int32_t* event_count);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -39,6 +39,11 @@ class Config(C.Structure):
     # opt-in message types (FT8RX_MT_* bits): not a field of ft8rx_config but a handle setting (ft8rx_set_msg_types) that Handle applies
     # at create time; kept here so that a config carries every knob of a receiver.  0 = the reference's rule.
     msg_types = 0
+    # opt-in a-priori calls (ft8rx_set_ap_calls / ft8rx_set_ap_max_hd): handle settings too, applied by Handle at create time.
+    # None = unset; both unset = the reference's ladder.
+    ap_my_call = None
+    ap_dx_call = None
+    ap_max_hd = None                 # None = the library's default (FT8RX_AP_MAX_HD_DEFAULT)
 
 
 RECORD_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("score", "<f4"), ("grid_sd", "<f4"), ("fine_sd", "<f4"),
@@ -68,6 +73,11 @@ assert PACKED_HEADER_DTYPE.itemsize == 32 and PACKED_FRAME_DTYPE.itemsize == 16
 assert RECORD_DTYPE.itemsize == 48 and EVENT_DTYPE.itemsize == 24 and MESSAGE_DTYPE.itemsize == 64
 
 ST_ACTIVE, ST_DECODED, ST_STOP_GRID_SD, ST_STOP_COSTAS, ST_STOP_FINE_SD, ST_EXHAUSTED = range(6)
+M_AP_CODEWORD = 5                    # ipass 7, full pattern (include/ft8rx.h FT8RX_M_AP_CODEWORD)
+AP_MAX_HD_DEFAULT = 36               # FT8RX_AP_MAX_HD_DEFAULT
+# ipass-7 patterns (record field ap = 5 .. 10, ft8rx_set_ap_calls): name, calls it needs
+AP_CALL_PATTERNS = {5: ("MY ???", "my"), 6: ("MY DX ???", "both"), 7: ("CQ DX ???", "dx"),
+                    8: ("MY DX RRR", "both"), 9: ("MY DX 73", "both"), 10: ("MY DX RR73", "both")}
 M_GOOD91, M_LDPC_A, M_LDPC_B, M_OSD, M_LDPC_B_OSD = range(5)
 
 _libs = {}
@@ -236,12 +246,43 @@ class Handle:
         self.max_frames = int(max_frames)
         self.device = int(device)
         self._h = C.c_void_p()
+        self.ap_calls = (None, None)
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
         if self.cfg.msg_types:
             L.ft8rx_set_msg_types.argtypes = [C.c_void_p, C.c_int32]
             self._chk(L.ft8rx_set_msg_types(self._h, int(self.cfg.msg_types)), "ft8rx_set_msg_types")
+        if getattr(self.cfg, "ap_max_hd", None) is not None:
+            self.set_ap_max_hd(self.cfg.ap_max_hd)
+        if getattr(self.cfg, "ap_my_call", None) or getattr(self.cfg, "ap_dx_call", None):
+            self.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
+
+    def set_ap_calls(self, my_call=None, dx_call=None):
+        """ft8rx_set_ap_calls: the operator's own call and the DX station's call as ipass-7 a-priori bits (None / "" = unset); applies
+        to batches enqueued afterwards."""
+        L = self._L
+        L.ft8rx_set_ap_calls.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        self._chk(L.ft8rx_set_ap_calls(self._h, (my_call or "").encode(), (dx_call or "").encode()), "ft8rx_set_ap_calls")
+        self.ap_calls = (my_call or None, dx_call or None)
+
+    def ap_calls_probe(self, llr):
+        """ft8rx_ap_calls_probe: ipass 7 alone on fine-LLR vectors [n][174] (candidates 0 .. n - 1 of one frame) -> (records[n],
+        events, event count)."""
+        llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)
+        n = len(llr)
+        rec = np.zeros(n, RECORD_DTYPE)
+        ev = np.zeros(EVENT_CAP, EVENT_DTYPE)
+        ne = C.c_int32(0)
+        L = self._L
+        L.ft8rx_ap_calls_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        self._chk(L.ft8rx_ap_calls_probe(self._h, llr.ctypes.data, n, rec.ctypes.data, ev.ctypes.data, C.byref(ne)), "ft8rx_ap_calls_probe")
+        return rec, ev, int(ne.value)
+
+    def set_ap_max_hd(self, max_hd):
+        L = self._L
+        L.ft8rx_set_ap_max_hd.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(L.ft8rx_set_ap_max_hd(self._h, int(max_hd)), "ft8rx_set_ap_max_hd")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -949,6 +990,17 @@ def encode_tones(msg_lo, msg_hi):
     if L.ft8rx_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
         raise Ft8rxError("ft8rx_encode_tones failed")
     return out
+
+
+def ap_patterns(my_call=None, dx_call=None):
+    """ft8rx_ap_patterns (host only): the ipass-7 patterns ap 5..10 -> (bits[6, 174], mask[6, 174]) uint8 in LLR order; raises
+    Ft8rxError naming the argument for a call that is not a standard callsign."""
+    L = lib()
+    L.ft8rx_ap_patterns.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
+    bits, mask = np.zeros((6, 174), np.uint8), np.zeros((6, 174), np.uint8)
+    if L.ft8rx_ap_patterns((my_call or "").encode(), (dx_call or "").encode(), bits.ctypes.data, mask.ctypes.data) != 0:
+        raise Ft8rxError(L.ft8rx_last_error(None).decode())
+    return bits, mask
 
 
 def default_handle(max_frames=1):

@@ -13,6 +13,8 @@
 //   k_bp           (candidate, AP)      GOOD91 + BP(90,20) with saved outputs
 //   k_select1, k_osd (candidate, slot) one wavefront: rank sort, register-resident GF(2) Gauss-Jordan
 //                                       with ballot pivoting, lane-per-trial CRC-14 + validity, k_select2
+//   k_bp_ap, k_osd_ap (cand, pattern)   opt-in ipass 7 (ft8rx_set_ap_calls): the operator's and the DX station's calls as known bits,
+//                                       only while a call is set (kernels/ap_calls.hpp)
 // A batch is cut into chunks whose chains run on separate HIP streams -- free-running: chunk i of batch k+1 follows chunk i of batch k
 // on stream i, no per-batch fork / join; results land in one of two result slots and are copied to page-locked host buffers by a copy
 // stream while the next batch computes; the used part of the event log is packed by k_ev_scan / k_ev_compact straight into
@@ -40,10 +42,12 @@
 #include "kernels/spectrogram.hpp"
 #include "kernels/sync_search.hpp"
 #include "kernels/llr.hpp"
+#include "kernels/ap_patterns.hpp"
 #include "kernels/bp.hpp"
 #include "kernels/cycle_spectrum.hpp"
 #include "kernels/fine_sync.hpp"
 #include "kernels/osd.hpp"
+#include "kernels/ap_calls.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -88,6 +92,10 @@ struct ft8rx_handle {
     int n_streams;                       // chunks of a batch run their kernel chains on separate streams
     int ladder_mode;                     // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
     int msg_types;                       // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
+    ApCalls ap;                          // ipass-7 patterns (ft8rx_set_ap_calls; ap.np = 0: off), as the host last set them
+    uint32_t ap_version, ap_chunk_version[16];   // the setting's version, and the version each chunk's device copy holds
+    ApCalls* d_apc;                      // [16] per-chunk device copies of `ap`, written on the chunk's stream (enqueue_chain)
+    int32_t* d_apcount;                  // [16][2] ipass-7 list lengths per chunk: candidates, OSD attempts
     int sub_frames;                      // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
     hipStream_t sub[8];
     hipEvent_t ev_fork, ev_join[8];
@@ -333,6 +341,8 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     if (device < 0 || device >= ndev) { set_err(nullptr, "ft8rx_create: device %d out of range (%d devices)", device, ndev); return -1; }
     ft8rx_handle* h = new ft8rx_handle();
     h->cfg = *cfg; h->device = device; h->max_frames = max_frames; h->stream = nullptr; h->profiling = false; h->n_stage = 0;
+    memset(&h->ap, 0, sizeof(h->ap)); h->ap.max_hd = FT8RX_AP_MAX_HD_DEFAULT; h->ap_version = 0; for (int i = 0; i < 16; i++) h->ap_chunk_version[i] = 0;
+    h->d_apc = nullptr; h->d_apcount = nullptr;
     h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
     h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
     for (int k = 0; k < 2; k++) { h->ev_comp[k] = h->ev_done[k] = nullptr; h->h_rec[k] = nullptr; h->h_cnt[k] = nullptr; h->h_ev[k] = nullptr; h->h_evc[k] = nullptr; h->h_evpacked[k] = nullptr; h->d_evpacked[k] = nullptr; h->d_evoffs[k] = nullptr; h->slot_B[k] = 0; }
@@ -368,6 +378,8 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     if (!rc) { h->d_A = reinterpret_cast<cpx*>(h->d_grid); h->d_spec = h->d_A + B * 96000; }
     for (int i = 0; i < WL_N; i++) rc |= dalloc(h, &h->d_work[i], B * S * WL_MULT(i));      // WL_BP0 / WL_OSDNAN list attempts
     rc |= dalloc(h, &h->d_wcount, (size_t)16 * WL_N);
+    rc |= dalloc(h, &h->d_apc, 16);                  // ft8rx_set_ap_calls allocates nothing: it is called every cycle
+    rc |= dalloc(h, &h->d_apcount, (size_t)16 * 2);
     rc |= dalloc(h, &h->d_ev, B * FT8RX_EVENT_CAP);
     rc |= dalloc(h, &h->d_evcount, B);
     h->s_rec[0] = h->d_rec; h->s_ncand[0] = h->d_ncand; h->s_ev[0] = h->d_ev; h->s_evcount[0] = h->d_evcount;
@@ -543,6 +555,22 @@ static void launch_sync(const float* grid, float* bs, int32_t* bh, const ft8rx_c
     }
 }
 
+// ipass 7 of B frames (kernels/ap_calls.hpp): candidate list in cand_items (B * stride entries), OSD list in osd_items (B * stride * 3),
+// attempt results in attO (B * stride * 10), the two list counters at ac; the batch chain and ft8rx_ap_calls_probe launch the same
+static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_record* rec, const int32_t* ncand, Att* attO, ft8rx_event* ev,
+                            int32_t* evc, int32_t* cand_items, int32_t* osd_items, int32_t* ac, const ApCalls* apc, hipStream_t s) {
+    const ft8rx_config& c = h->cfg;
+    const int sh = cand_shift(c); const size_t S = (size_t)1 << sh;
+    const int nflip = osd_nflip(c.osd_single, c.osd_triple);
+    hipMemsetAsync(ac, 0, 2 * sizeof(int32_t), s);
+    const WorkList cl = {cand_items, ac}, ol = {osd_items, ac + 1};
+    k_ap_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, cl);
+    k_bp_ap<<<ladder_grid(B * c.max_cands * h->ap.np), 64, 0, s>>>(llr0, rec, ncand, attO, ev, evc, c, apc, cl, ol);
+    (nflip > OSD_FLIPS_A ? k_osd_ap_wide : k_osd_ap)<<<ladder_grid(B * c.max_cands * 3), 64, 0, s>>>(
+        llr0, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, sh, apc, ol);
+    k_select_ap<<<(B * S + 255) / 256, 256, 0, s>>>(rec, attO, apc, cl);
+}
+
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
     const ft8rx_config& c = h->cfg;
     const size_t F = (size_t)f0;
@@ -622,6 +650,17 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     }
     STAGE("select2");
     k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
+    if (h->ap.np) {
+        // ipass 7 (ft8rx_set_ap_calls, kernels/ap_calls.hpp), after the whole reference ladder.  Scratch that is dead by now: the
+        // candidate list in WL_BP0's items, the OSD list in WL_OSDNAN's, the attempt results in attO's slots.
+        STAGE("ap_calls");
+        ApCalls* apc = h->d_apc + chunk;
+        if (h->ap_chunk_version[chunk] != h->ap_version) {       // this chunk's copy is stale: rewrite it behind the chunk's earlier work
+            k_ap_stage<<<1, 64, 0, s>>>(apc, h->ap);
+            h->ap_chunk_version[chunk] = h->ap_version;
+        }
+        launch_ap_calls(h, B, llr0, rec, ncand, attO, ev, evc, wl[WL_BP0].items, wl[WL_OSDNAN].items, h->d_apcount + 2 * chunk, apc, s);
+    }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
 }
@@ -833,7 +872,74 @@ int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
     if (!h) return -1;
     if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
     if (mask && h->pk_buf[0]) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
+    if (mask && h->ap.np) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_ap_calls"); return -1; }
     h->msg_types = mask;                        // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
+    return 0;
+}
+
+// ipass-7 patterns of (my, dx) (kernels/ap_patterns.hpp); NULL / "" = unset.  -> 0, or -1 with the reason in err
+static int build_ap_patterns(const char* my, const char* dx, ApCalls* a, std::string* err) {
+    const bool hm = my && *my, hd = dx && *dx;
+    const long cm = hm ? hostmsg::pack_c28_std(my) : 0, cd = hd ? hostmsg::pack_c28_std(dx) : 0;
+    if (cm < 0) { *err = std::string("my_call '") + my + "' is not a standard callsign"; return -1; }
+    if (cd < 0) { *err = std::string("dx_call '") + dx + "' is not a standard callsign"; return -1; }
+    const int32_t max_hd = a->max_hd;
+    memset(a, 0, sizeof(*a)); a->max_hd = max_hd;
+    // 77-bit i3 = 1 word: c28 r1 c28 r1 R1 g15 i3; position i (LLR order) = word bit 76 - i
+    auto word = [](long c1, long c2, unsigned g15) { return ((unsigned __int128)c1 << 49) | ((unsigned __int128)c2 << 20) | ((unsigned __int128)g15 << 3) | 1u; };
+    const unsigned G_RRR = 32402, G_73 = 32404, G_RR73 = 32403;
+    for (int p = 5; p <= 10; p++) {
+        const bool on = p == 5 ? hm : p == 7 ? hd : (hm && hd);
+        if (!on) continue;
+        const int k = p - FT8RX_AP_FIRST;
+        const unsigned __int128 w = word(p == 7 ? 2 : cm, p == 5 ? 0 : cd, p == 8 ? G_RRR : p == 9 ? G_73 : G_RR73);
+        const uint64_t lo = (uint64_t)w, hi = (uint64_t)(w >> 64);
+        if (p >= 8) {
+            hostmsg::encode_cw174(lo, hi, a->val[k]);
+            a->msk[k][0] = a->msk[k][1] = ~0ull; a->msk[k][2] = (1ull << 46) - 1;
+            a->lo[k] = lo; a->hi[k] = hi;
+            hostmsg::Hashes H; std::string f[3];
+            if (!hostmsg::unpack_ext(lo, hi, 0, H, f)) { *err = "the words of my_call / dx_call do not unpack as a standard message"; return -1; }
+        } else {
+            const int nk = p == 5 ? 29 : 58;                                // known call fields: positions 0 .. nk - 1, and i3 (74 .. 76)
+            for (int i = 0; i < 77; i++) {
+                if (!(i < nk || i >= 74)) continue;
+                const unsigned b = (unsigned)((w >> (76 - i)) & 1u);
+                a->msk[k][i >> 6] |= 1ull << (i & 63);
+                if (b) a->val[k][i >> 6] |= 1ull << (i & 63);
+            }
+        }
+        a->pat[a->np++] = p;
+    }
+    return 0;
+}
+
+int ft8rx_set_ap_calls(ft8rx_handle* h, const char* my_call, const char* dx_call) {
+    if (!h) return -1;
+    ApCalls a = h->ap;
+    std::string err;
+    if (build_ap_patterns(my_call, dx_call, &a, &err)) { set_err(h, "ft8rx_set_ap_calls: %s", err.c_str()); return -1; }
+    if (a.np && h->msg_types) { set_err(h, "ft8rx_set_ap_calls: not supported together with msg_types != 0"); return -1; }
+    if (a.np && h->pk_buf[0]) { set_err(h, "ft8rx_set_ap_calls: not supported on the packed output"); return -1; }
+    h->ap = a; h->ap_version++;                 // batches in flight keep the setting they were enqueued with (enqueue_chain)
+    return 0;
+}
+
+int ft8rx_set_ap_max_hd(ft8rx_handle* h, int32_t max_hd) {
+    if (!h) return -1;
+    if (max_hd < 1 || max_hd > 174) { set_err(h, "ft8rx_set_ap_max_hd: %d outside [1, 174]", max_hd); return -1; }
+    h->ap.max_hd = max_hd; h->ap_version++;
+    return 0;
+}
+
+int ft8rx_ap_patterns(const char* my_call, const char* dx_call, uint8_t* bits_out, uint8_t* mask_out) {
+    ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = FT8RX_AP_MAX_HD_DEFAULT;
+    std::string err;
+    if (build_ap_patterns(my_call, dx_call, &a, &err)) { g_create_err = "ft8rx_ap_patterns: " + err; return -1; }
+    for (int k = 0; k < FT8RX_AP_N; k++) for (int i = 0; i < 174; i++) {
+        if (bits_out) bits_out[k * 174 + i] = (uint8_t)((a.val[k][i >> 6] >> (i & 63)) & 1ull);
+        if (mask_out) mask_out[k * 174 + i] = (uint8_t)((a.msk[k][i >> 6] >> (i & 63)) & 1ull);
+    }
     return 0;
 }
 
@@ -909,6 +1015,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     h->pk_fence[0] = h->pk_fence[1] = nullptr;
     if (!d_buf0 && !d_buf1) { h->pk_buf[0] = h->pk_buf[1] = nullptr; h->pk_cap = 0; return 0; }
     if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
+    if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -1133,6 +1240,41 @@ int ft8rx_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int ma
     HIPCHK(h, hipMemcpy(a.data(), d_att, sizeof(Att) * n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) { ok[i] = a[i].ok; msg_lo[i] = a[i].lo; msg_hi[i] = a[i].hi; n_its[i] = a[i].ok ? a[i].n_its : -1; has_out[i] = a[i].has_out; }
     if (llr_out) HIPCHK(h, hipMemcpy(llr_out, d_out, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ipass 7 alone, on n <= max_cands fine-LLR vectors of one frame (candidates 0 .. n - 1, each as the ladder leaves an undecoded one):
+// the batch's launch sequence (launch_ap_calls) with the handle's setting -> their records and the frame's event log
+int ft8rx_ap_calls_probe(ft8rx_handle* h, const float* llr, int n, ft8rx_record* records, ft8rx_event* events, int32_t* event_count) {
+    if (!h || !llr || !records || n < 1 || n > h->cfg.max_cands) { if (h) set_err(h, "ft8rx_ap_calls_probe: 1 <= n <= max_cands"); return -1; }
+    if (!h->ap.np) { set_err(h, "ft8rx_ap_calls_probe: no call set (ft8rx_set_ap_calls)"); return -1; }
+    ENTER(h);
+    Scratch S{h};
+    const size_t st = (size_t)1 << cand_shift(h->cfg);
+    std::vector<ft8rx_record> r0(st);
+    memset(r0.data(), 0, sizeof(ft8rx_record) * st);
+    for (int i = 0; i < n; i++) r0[i].status = FT8RX_ST_EXHAUSTED;
+    std::vector<float> l0(st * 174, 0.0f);
+    memcpy(l0.data(), llr, sizeof(float) * (size_t)n * 174);
+    const int32_t nc = n, zero = 0;
+    float* d_llr = S.put(l0.data(), l0.size()); NEED(d_llr);
+    ft8rx_record* d_rec = S.put(r0.data(), st); NEED(d_rec);
+    int32_t* d_nc = S.put(&nc, 1); NEED(d_nc);
+    int32_t* d_evc = S.put(&zero, 1); NEED(d_evc);
+    Att* d_att = S.get<Att>(st * 10); NEED(d_att);
+    ft8rx_event* d_ev = S.get<ft8rx_event>(FT8RX_EVENT_CAP); NEED(d_ev);
+    int32_t* d_cl = S.get<int32_t>(st); NEED(d_cl);
+    int32_t* d_ol = S.get<int32_t>(st * 3); NEED(d_ol);
+    int32_t* d_ac = S.get<int32_t>(2); NEED(d_ac);
+    ApCalls* d_apc = S.get<ApCalls>(1); NEED(d_apc);
+    k_ap_stage<<<1, 64, 0, h->stream>>>(d_apc, h->ap);
+    launch_ap_calls(h, 1, d_llr, d_rec, d_nc, d_att, d_ev, d_evc, d_cl, d_ol, d_ac, d_apc, h->stream);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(records, d_rec, sizeof(ft8rx_record) * (size_t)n, hipMemcpyDeviceToHost));
+    int32_t ne = 0;
+    HIPCHK(h, hipMemcpy(&ne, d_evc, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (event_count) *event_count = ne;
+    if (events) HIPCHK(h, hipMemcpy(events, d_ev, sizeof(ft8rx_event) * (size_t)(ne < FT8RX_EVENT_CAP ? ne : FT8RX_EVENT_CAP), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -359,7 +359,7 @@ static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, 
             int sslot = -1, sseq = -1;
             if (here) {
                 const int m = r.method;
-                sslot = r.ap + (m == FT8RX_M_LDPC_B_OSD ? 5 : 0);
+                sslot = rnd == 7 ? 2 * r.ap + (m == FT8RX_M_OSD ? 1 : 0) : r.ap + (m == FT8RX_M_LDPC_B_OSD ? 5 : 0);    // ipass 7: kernels/ap_calls.hpp
                 sseq = m == FT8RX_M_GOOD91 ? 0 : (m == FT8RX_M_LDPC_A || m == FT8RX_M_LDPC_B) ? r.n_its + 1 : r.n_its;
             }
             std::string f[3], got[3]; bool have = false;
@@ -407,17 +407,49 @@ static inline unsigned crc14_serial(uint64_t lo, uint64_t hi) {
     return r;
 }
 // 77-bit word -> 79 tones (transmitter.py:181-223 encode_bits77): CRC-14, LDPC(174,91) systematic encode, Gray map, Costas framing
-static void encode_tones(uint64_t lo, uint64_t hi, uint8_t* t) {
-    static const uint8_t costas[7] = {3, 1, 4, 0, 6, 5, 2}, gray[8] = {0, 1, 3, 2, 5, 6, 4, 7};
+// 77-bit word -> 174-bit codeword: CRC-14, LDPC(174,91) systematic encode; codeword bit v at cw[v >> 6] bit v & 63
+static void encode_cw174(uint64_t lo, uint64_t hi, uint64_t cw[3]) {
     hi &= 0x1FFFull;
     const unsigned crc = crc14_serial(lo, hi);
-    uint64_t cw[3] = {0, 0, 0};                                    // codeword bit v at word v >> 6, bit v & 63
+    cw[0] = cw[1] = cw[2] = 0;
     for (int r = 0; r < 91; r++) {                                 // message bit r: 77 message bits (bit 76 first), then the CRC
         unsigned b;
         if (r < 77) { const int pos = 76 - r; b = (unsigned)((pos >= 64 ? (hi >> (pos - 64)) : (lo >> pos)) & 1u); }
         else b = (crc >> (13 - (r - 77))) & 1u;
         if (b) { cw[0] ^= FT8_G0[r][0]; cw[1] ^= FT8_G0[r][1]; cw[2] ^= FT8_G0[r][2]; }
     }
+}
+// standard callsign -> c28 (FT8 protocol, i3 = 1: the form pyft8_amd/synth.py pack_c28 packs), -1 for anything else: the tokens
+// DE / QRZ / CQ, hashed or compound calls, lower case, blanks.  3..6 characters, letters and digits; the digit is the second or
+// third character; after it up to three letters.
+static long pack_c28_std(const char* call) {
+    if (!call) return -1;
+    const size_t n = strlen(call);
+    if (n < 3 || n > 6) return -1;
+    for (size_t i = 0; i < n; i++) { const char ch = call[i]; if (!((ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9'))) return -1; }
+    char c[7] = "      ";
+    if (call[2] >= '0' && call[2] <= '9') memcpy(c, call, n);
+    else { if (n > 5) return -1; c[0] = ' '; memcpy(c + 1, call, n); }
+    static const char* A0 = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ", *A1 = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ", *A3 = " ABCDEFGHIJKLMNOPQRSTUVWXYZ";
+    if (!(c[2] >= '0' && c[2] <= '9')) return -1;
+    const char* p0 = strchr(A0, c[0]), *p1 = strchr(A1, c[1]);
+    if (!p0 || !p1 || !c[1] || c[1] == ' ') return -1;
+    long v = (long)(p0 - A0);
+    v = v * 36 + (long)(p1 - A1);
+    v = v * 10 + (c[2] - '0');
+    bool blank = false;
+    for (int i = 3; i < 6; i++) {
+        const char* q = strchr(A3, c[i]);
+        if (!q || !c[i]) return -1;
+        if (c[i] == ' ') blank = true; else if (blank) return -1;          // letters after a blank: not a call
+        v = v * 27 + (long)(q - A3);
+    }
+    return v + 2063592L + 4194304L;                                  // NTOKENS + MAX22
+}
+static void encode_tones(uint64_t lo, uint64_t hi, uint8_t* t) {
+    static const uint8_t costas[7] = {3, 1, 4, 0, 6, 5, 2}, gray[8] = {0, 1, 3, 2, 5, 6, 4, 7};
+    uint64_t cw[3];
+    encode_cw174(lo, hi, cw);
     for (int k = 0; k < 7; k++) { t[k] = costas[k]; t[36 + k] = costas[k]; t[72 + k] = costas[k]; }
     for (int sidx = 0; sidx < 58; sidx++) {
         unsigned v = 0;

@@ -28,11 +28,15 @@ __device__ unsigned long long g_bp_t[65536][8];
 #define BT_DECL
 #define BT(i) do { } while (0)
 #endif
-template <bool EXT>                   // EXT: the opt-in message types mt (ft8rx_set_msg_types, ft8_valid77_ext); the k_bp / k_bp_ext pair below
+// EXT: the opt-in message types mt (ft8rx_set_msg_types, ft8_valid77_ext); the k_bp / k_bp_ext pair below.
+// AP7: the ipass-7 step of ft8rx_set_ap_calls (kernels/ap_calls.hpp: k_bp_ap): bid = candidate << 4 | pattern (5..7), the fine LLRs
+// with the pattern's known bits, BP(nc0_b, iters_b); the result goes to attB[candidate * 10 + pattern - 5], and an attempt whose BP
+// found no valid word goes onto *osdl (OSD of the same input).  The default kernels instantiate AP7 = false: the code they always were.
+template <bool EXT, bool AP7 = false>
 FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ llr_in, ft8rx_record* __restrict__ rec,
                         const int32_t* __restrict__ ncand, Att* __restrict__ attG, Att* __restrict__ attB,
                         float* __restrict__ saved, ft8rx_event* ev, int32_t* evcount, const ft8rx_config& cfg,
-                        int max_nc0, int max_iters, unsigned mt) {
+                        int max_nc0, int max_iters, unsigned mt, const ApCalls* __restrict__ apc = nullptr, const WorkList* osdl = nullptr) {
     __shared__ float llr[176];
     __shared__ float tl[576];        // 9 x 64 edge slots: slots >= 522 are dummy edges (variable 174, check 83) so that the
     // per-edge code below is straight-line for all nine slots of a lane.  The message deltas overwrite the tanh values in place: a
@@ -42,7 +46,9 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
     __shared__ float P[84];
     int ap = 0; size_t vec;                   // modes 0 / 1: vec = the candidate (frame << cand_shift + ci)
     BT_DECL
-    if (mode == 2) vec = bid;
+    uint64_t ho0 = 0, ho1 = 0, ho2 = 0;       // AP7: hard decisions of the un-overridden LLRs (the acceptance gate)
+    if (AP7) { ap = bid & 15; vec = (size_t)(bid >> 4); }
+    else if (mode == 2) vec = bid;
     else {
         const int sh = cand_shift(cfg);
         ap = bid % 5; const int c = bid / 5;
@@ -53,8 +59,14 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
     {   // three loads in flight, then the AP override (ap_value around the load would branch over it: one round trip per basic block)
         const float* src = llr_in + vec * 174;
         const float v0 = src[lane], v1 = src[64 + lane], v2 = src[128 + (lane < 46 ? lane : 0)];
-        llr[lane] = ap_value(ap, lane, v0); llr[64 + lane] = ap_value(ap, 64 + lane, v1);
-        if (lane < 46) llr[128 + lane] = ap_value(ap, 128 + lane, v2);
+        if constexpr (AP7) {
+            llr[lane] = ap7_value(apc, ap, lane, v0); llr[64 + lane] = ap7_value(apc, ap, 64 + lane, v1);
+            if (lane < 46) llr[128 + lane] = ap7_value(apc, ap, 128 + lane, v2);
+            ho0 = __ballot(v0 > 0.0f); ho1 = __ballot(v1 > 0.0f); ho2 = __ballot(lane < 46 && v2 > 0.0f);
+        } else {
+            llr[lane] = ap_value(ap, lane, v0); llr[64 + lane] = ap_value(ap, 64 + lane, v1);
+            if (lane < 46) llr[128 + lane] = ap_value(ap, 128 + lane, v2);
+        }
     }
     if (lane < 2) llr[174 + lane] = 0.0f;
     if (lane == 0) P[83] = 1.0f;
@@ -62,7 +74,7 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
     Att res; memset(&res, 0, sizeof(res)); res.n_its = -1;
     // ---- GOOD91 of the fine stage (ipass 2, ap 0 then ap 1): CRC on the hard decisions of llr[:91] (receiver.py:119-122)
     // (ipass 0's GOOD91 is done by bp0_precheck in k_grid_llr)
-    if (mode == 1 && ap == 0) {
+    if (!AP7 && mode == 1 && ap == 0) {
         bool any = false;
 #pragma unroll
         for (int g = 0; g < 2; g++) {
@@ -105,6 +117,14 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
             uint64_t b1 = h1 & ((1ull << 27) - 1);
             uint64_t lo, hi;
             int r = ft8_crc_check_wave<EXT>(b0, b1, lane, &lo, &hi, mt);
+            if constexpr (AP7) {          // ipass 7: event slot 2 * pattern (kernels/ap_calls.hpp), then the distance gate on the un-overridden LLRs
+                if (r && lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), 7, 2 * ap, it + 1, lo, hi, r == 2);
+                const int hd = __popcll(h0 ^ ho0) + __popcll(h1 ^ ho1) + __popcll(h2 ^ ho2);
+                res.pad[1] = (uint8_t)(r == 2);      // BP reached a valid word (accepted or not: either way OSD does not follow)
+                if (r == 2 && hd <= apc->max_hd) { res.ok = 1; res.lo = lo; res.hi = hi; res.n_its = (int16_t)it; res.pad[0] = (uint8_t)hd; }
+                res.has_out = 0;
+                break;
+            }
             if (r) {
                 int ipass = (mode == 0) ? 0 : ((ap < 2 && res.nc0 <= cfg.bp_nc0_a && it < cfg.bp_iters_a) ? 3 : 4);
                 if (lane == 0) log_event(ev, evcount, (int)vec >> cand_shift(cfg), (int)vec & ((1 << cand_shift(cfg)) - 1), ipass, ap, it + 1, lo, hi, r == 2);
@@ -176,6 +196,13 @@ FT8_DEV void bp_attempt(int lane, int mode, int bid, const float* __restrict__ l
         BT(5);
     }
     BT(6);
+    if constexpr (AP7) {
+        if (res.ok) res.method = FT8RX_M_LDPC_B;
+        // "BP_B, then OSD if that fails": only an attempt whose BP found no valid word goes on to OSD -- a valid word beyond the
+        // gate ends the pattern (receiver.ap_calls_attempts is the same rule through the single-vector entry points)
+        if (lane == 0) { attB[vec * 10 + (ap - 5)] = res; if (!res.pad[1]) work_push(*osdl, bid); }
+        return;
+    }
     if (res.ok) res.method = (mode == 0) ? FT8RX_M_LDPC_A : FT8RX_M_LDPC_B;
     if (mode == 2) {
         if (lane == 0) attB[vec] = res;

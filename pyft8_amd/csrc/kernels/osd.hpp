@@ -199,12 +199,17 @@ FT8_DEV unsigned osd_syndrome(uint64_t w0, uint64_t w1) { return ft8_crc_syndrom
 // -- a serial algorithm, run by one lane, whose code costs the main kernel 8 VGPRs and a scratch frame if it lives there: the main kernels
 // (NANV = false) only append such an attempt to `nanlist` and leave; the NaN kernels stride over that list (almost always empty).
 // EXT: the opt-in message types mt (ft8rx_set_msg_types, ft8_valid77_ext with osd = true: free text and telemetry are never accepted here)
-template <bool WIDE, bool NANV, bool EXT = false>
+// AP7: the ipass-7 step of ft8rx_set_ap_calls (kernels/ap_calls.hpp: k_osd_ap): bid = candidate << 4 | pattern (5..7), the fine LLRs
+// with the pattern's known bits; the first valid trial (as osd_012 returns it, max_hd = 0) is then gated: its distance to the hard
+// decisions of the un-overridden LLRs must be <= the setting's ap_max_hd; the result goes to attO[candidate * 10 + pattern - 5].
+// A vector with a NaN is skipped on purpose (k_osd_ap passes no NaN list): the attempt keeps the undecoded result k_bp_ap wrote.  Fine
+// LLRs can hold NaNs (a NaN sd passes the sd gate), and a word forced onto such a candidate has nothing to be measured against.
+template <bool WIDE, bool NANV, bool EXT = false, bool AP7 = false>
 FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ llr_in, const float* __restrict__ saved,
                          const Att* __restrict__ attB, ft8rx_record* __restrict__ rec,
                          const int32_t* __restrict__ ncand, Att* __restrict__ attO,
                          ft8rx_event* ev, int32_t* evcount, const uint32_t* __restrict__ trials, int ntr,
-                         int nflip, int max_hd, int sh, const WorkList& nanlist, unsigned mt = 0) {
+                         int nflip, int max_hd, int sh, const WorkList& nanlist, unsigned mt = 0, const ApCalls* __restrict__ apc = nullptr) {
     __shared__ float llr[176];
     __shared__ uint64_t skey[256];
     __shared__ uint64_t ftab[192];                         // per column (natural order): bit i = flip i covers it (i < 62), bit 63 = order-0 codeword bit
@@ -217,8 +222,16 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
     __shared__ uint32_t hmw[3];
     __shared__ uint16_t fsyn[OSD_MAXFLIP + 2];             // [i] flip i, [OSD_MAXFLIP] = 0 ("no flip"), [OSD_MAXFLIP + 1] order-0 codeword
     int slot = 0; size_t vec = bid;
+    const float* src7 = nullptr;                           // AP7: the un-overridden fine LLRs
     OT_DECL
-    if (mode == 0) {
+    if constexpr (AP7) {
+        slot = bid & 15; const size_t c = (size_t)(bid >> 4);
+        src7 = llr_in + c * 174;
+        const float v0 = src7[lane], v1 = src7[64 + lane], v2 = src7[128 + (lane < 46 ? lane : 0)];
+        llr[lane] = ap7_value(apc, slot, lane, v0); llr[64 + lane] = ap7_value(apc, slot, 64 + lane, v1);
+        if (lane < 46) llr[128 + lane] = ap7_value(apc, slot, 128 + lane, v2);
+        vec = c * 10 + (slot - 5);
+    } else if (mode == 0) {
         slot = bid % 10; const int c = bid / 10;
         if ((c & ((1 << sh) - 1)) >= ncand[c >> sh]) return;
         if (rec[c].status != FT8RX_ST_ACTIVE) return;
@@ -297,8 +310,9 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
     uint32_t x10 = d_G0T[ord1][0], x11 = d_G0T[ord1][1], x12 = d_G0T[ord1][2];
     uint32_t x20 = has2 ? d_G0T[ord2][0] : 0u, x21 = has2 ? d_G0T[ord2][1] : 0u, x22 = has2 ? d_G0T[ord2][2] : 0u;
     // hard decisions: in natural order (distance test of the slow path) and per sorted position
-    const uint64_t hard0 = __ballot(llr[lane] > 0.0f), hard1 = __ballot(llr[64 + lane] > 0.0f),
-                   hard2 = __ballot(has2 && llr[128 + (has2 ? lane : 0)] > 0.0f);
+    const float* hsrc = AP7 ? src7 : llr;                 // AP7: the gate's distance is to the un-overridden LLRs
+    const uint64_t hard0 = __ballot(hsrc[lane] > 0.0f), hard1 = __ballot(hsrc[64 + lane] > 0.0f),
+                   hard2 = __ballot(has2 && hsrc[128 + (has2 ? lane : 0)] > 0.0f);
     const bool hs0 = llr[ord0] > 0.0f, hs1 = llr[ord1] > 0.0f, hs2 = has2 && llr[ord2] > 0.0f;
     uint64_t lock01 = 0; uint32_t lock2 = ~((1u << 27) - 1u);
     uint64_t acc0 = 0, acc1 = 0, acc2 = 0;             // accepted positions per register set
@@ -551,7 +565,7 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
     const unsigned syn_c = fsyn[OSD_MAXFLIP + 1];
     const uint64_t M1 = (1ull << 27) - 1, M2 = (1ull << 46) - 1;
     Att res; memset(&res, 0, sizeof(res)); res.n_its = -1;
-    const int ipass = (slot < 5) ? 5 : 6;
+    const int ipass = AP7 ? 7 : (slot < 5) ? 5 : 6;
 #ifdef OSD_TIMING_SKIP_TRIALS
     ntr = 0;
 #endif
@@ -590,10 +604,11 @@ FT8_DEV void osd_attempt(int lane, int mode, int bid, const float* __restrict__ 
             uint64_t lo = 0, hi = 0;
             const int r = ft8_crc_check<EXT>(w0, w1 & M1, &lo, &hi, mt, true);
             const int t = base + hl;
-            if (r && lane == 0) log_event(ev, evcount, (int)(vec / 10) >> sh, (int)(vec / 10) & ((1 << sh) - 1), ipass, slot, t, lo, hi, r == 2);   // a call the reference made (mode 0: vec = candidate * 10 + slot)
+            if (r && lane == 0) log_event(ev, evcount, (int)(vec / 10) >> sh, (int)(vec / 10) & ((1 << sh) - 1), ipass, AP7 ? 2 * slot + 1 : slot, t, lo, hi, r == 2);   // a call the reference made (mode 0: vec = candidate * 10 + slot)
             if (r == 2) {
                 res.ok = 1; res.lo = lo; res.hi = hi; res.n_its = (int16_t)t;
-                res.method = (slot < 5) ? FT8RX_M_OSD : FT8RX_M_LDPC_B_OSD;
+                if constexpr (AP7) res.ok = hd <= apc->max_hd;   // AP7: the first valid trial, as osd_012 returns it, then the gate
+                res.method = (AP7 || slot < 5) ? FT8RX_M_OSD : FT8RX_M_LDPC_B_OSD;
                 res.pad[0] = (uint8_t)hd;                     // Hamming distance of the accepted codeword to the hard decisions
                 done = true;
             }

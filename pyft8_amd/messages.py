@@ -15,6 +15,15 @@ A38 = A37 + "/"
 A27 = " ABCDEFGHIJKLMNOPQRSTUVWXYZ"
 NTOKENS, MAX22 = 2063592, 4194304
 AP_NAMES = ("NoAP", "CQ", "RR73", "73", "RRR")
+# ipass 7 (ft8rx_set_ap_calls): the patterns ap 5..10 with the operator's call MY and the DX station's call DX
+AP_CALL_NAMES = ("MY ???", "MY DX ???", "CQ DX ???", "MY DX RRR", "MY DX 73", "MY DX RR73")
+
+
+def ap_name(ap):
+    """The record's ap field -> the pattern's name (the reference's five, then the ipass-7 ones)."""
+    return AP_NAMES[ap] if ap < 5 else AP_CALL_NAMES[ap - 5]
+
+
 M64 = (1 << 64) - 1
 
 
@@ -246,8 +255,9 @@ def _msg_text(bits77, text):
 def decode_notes(rec):
     """'{source}_{AP}_{method}' + tweaks, formatted as the reference does (receiver.py:42,57,121,126,133,162)."""
     fine = rec["ipass"] >= 2
-    meth = ("GOOD91 ", "LDPC5", "LDPC20", "OSD", "LDPC20_OSD")[rec["method"]]
-    return ("fine" if fine else "grid") + "_" + AP_NAMES[rec["ap"]] + "_" + meth, tweaks_str(rec)
+    meth = ("GOOD91 ", "LDPC5", "LDPC20", "OSD", "LDPC20_OSD", "CODEWORD")[rec["method"]]
+    ap = AP_NAMES[rec["ap"]] if rec["ap"] < 5 else AP_CALL_NAMES[rec["ap"] - 5].replace(" ", "_")
+    return ("fine" if fine else "grid") + "_" + ap + "_" + meth, tweaks_str(rec)
 
 
 def tweaks_str(rec):
@@ -259,12 +269,14 @@ def tweaks_str(rec):
 _LAST_IPASS = {2: 0, 3: 1, 4: 1}     # status -> last ladder step taken (STOP_GRID_SD, STOP_COSTAS, STOP_FINE_SD)
 
 
-def package_frame(rec, count, events, n_events, cyclestart_string="", band=None, odd_even=0, table=None, on_message=None, mask=0):
+def package_frame(rec, count, events, n_events, cyclestart_string="", band=None, odd_even=0, table=None, on_message=None, mask=0,
+                  ap=False):
     """Replay one frame's candidate records in the reference's order (receiver.py:389-398):
     per round all live candidates advance one ipass in llr_sd-descending (stable) order; CRC-passing
     unpack() calls update the hash table as they happen; first sighting of a message text is emitted.
     Returns the list of message dicts (reference receiver.py:61-64 keys).  mask != 0: the opt-in message types are rendered too
-    (unpack_ext) and every dict gains "msg_type"."""
+    (unpack_ext) and every dict gains "msg_type".  ap = True (a handle with a-priori calls, ft8rx_set_ap_calls): every dict gains
+    "ap", the name of the pattern that decoded it.  ipass-7 events sit at slot 2 * ap (BP, codeword test) / 2 * ap + 1 (OSD)."""
     table = table if table is not None else CallHashes()
     rec = rec[:count]
     n_ev = min(int(n_events), len(events))
@@ -288,7 +300,7 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
             stop_key = None
             if decoded_here:
                 m = int(r["method"])
-                slot = int(r["ap"]) + (5 if m == 4 else 0)
+                slot = 2 * int(r["ap"]) + (1 if m == 3 else 0) if rnd == 7 else int(r["ap"]) + (5 if m == 4 else 0)
                 seq = 0 if m == 0 else (int(r["n_its"]) + 1 if m in (1, 2) else int(r["n_its"]))
                 stop_key = (slot, seq)
             text = None
@@ -327,13 +339,15 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
                      "decode_notes": notes + tw}
                 if mask:
                     m["msg_type"] = msg_type(word)
+                if ap:
+                    m["ap"] = ap_name(int(r["ap"]))
                 out.append(m)
                 if on_message is not None:
                     on_message(m)
     return out
 
 
-def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None):
+def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None, ap=False):
     """Rows of the native packager (ft8rx_package_batch, _lib.MESSAGE_DTYPE) -> the reference's message dicts
     (receiver.py:57-65).  Same formatting as package_frame above."""
     out = []
@@ -345,7 +359,7 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
     cols = [rows[k].tolist() for k in ("f", "h0_idx", "f0_idx", "ttweak", "ftweak", "snr", "ipass", "method", "ap", "fine")]
     ext = "i3" in rows.dtype.names                   # rows of ft8rx_package_batch_ext (_lib.MESSAGE_EXT_DTYPE): the opt-in types
     types = list(zip(rows["i3"].tolist(), rows["n3"].tolist())) if ext else [None] * len(rows)
-    for f3, h0, f0, tt, ft, sn, ipass, method, ap, fn, ty in zip(*cols, types):
+    for f3, h0, f0, tt, ft, sn, ipass, method, ap_, fn, ty in zip(*cols, types):
         text = tuple(x.decode() for x in f3)
         tsec = h0 / 25.0
         fHz = 3.125 * f0
@@ -353,7 +367,7 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
             tsec = float(tsec + tt / 200)
             fHz = float(fHz + ft / 16)
         snr = "%+03d" % sn
-        rec = {"ipass": ipass, "method": method, "ap": ap, "ttweak": tt, "ftweak": ft}
+        rec = {"ipass": ipass, "method": method, "ap": ap_, "ttweak": tt, "ftweak": ft}
         notes, tw = decode_notes(rec)
         line = _msg_text(ty[0] | (ty[1] << 3), text) if ext else " ".join(text)
         d = {"band": band, "tsec": tsec, "fHz": fHz, "msg_tuple": text, "their_snr": snr, "their_tx_cycle": odd_even,
@@ -361,6 +375,8 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
              "cyclestart_string": cyclestart_string, "decode_completed": now, "tweaks": tw, "decode_notes": notes + tw}
         if ext:
             d["msg_type"] = msg_type(ty[0] | (ty[1] << 3))
+        if ap:
+            d["ap"] = ap_name(int(ap_))
         out.append(d)
         if on_message is not None:
             on_message(d)

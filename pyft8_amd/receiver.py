@@ -58,6 +58,7 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
         raise _lib.Ft8rxError(f"search_freq_range={list(search_freq_range)}: supported are 12.5 .. {_lib.MAX_F0_WIDE * df:.0f} Hz, low < high "
                               "(above 3000 Hz the wide build libft8rx_wide.so is used; the reference fails beyond ~5940 Hz, receiver.py:181-182)")
     mask = msg_types_mask(ext.pop("msg_types", 0))       # a handle setting, not a field of ft8rx_config (_lib.Config.msg_types)
+    my_call, dx_call, ap_max_hd = ext.pop("my_call", None), ext.pop("dx_call", None), ext.pop("ap_max_hd", None)
     known = {f[0] for f in _lib.Config._fields_}
     for k, v in ext.items():          # extension knobs: bp_iters_b, osd_single, osd_double, osd_triple, osd_max_hd, ...
         if k not in known:            # like the reference's fixed signature (e.g. the CLI's misspelt `search_timerange`, pyft8.py:137)
@@ -65,7 +66,21 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
         setattr(cfg, k, v)
     if mask:
         cfg.msg_types = mask
+    if ap_max_hd is not None:
+        if not 1 <= int(ap_max_hd) <= 174:
+            raise _lib.Ft8rxError(f"ap_max_hd={ap_max_hd}: a Hamming distance in 1 .. 174")
+        cfg.ap_max_hd = int(ap_max_hd)
+    set_ap_calls_cfg(cfg, my_call, dx_call)
     return cfg
+
+
+def set_ap_calls_cfg(cfg, my_call, dx_call):
+    """Check the a-priori calls (ft8rx_set_ap_calls: standard callsigns only) and store them in cfg; refuses msg_types != 0."""
+    my_call, dx_call = (my_call or None), (dx_call or None)
+    if (my_call or dx_call) and cfg.msg_types:
+        raise _lib.Ft8rxError("my_call / dx_call (a-priori decoding) is not supported together with msg_types != 0")
+    _lib.ap_patterns(my_call, dx_call)                   # raises, naming the argument, for a call that is not a standard one
+    cfg.ap_my_call, cfg.ap_dx_call = my_call, dx_call
 
 
 def msg_types_mask(msg_types):
@@ -135,6 +150,46 @@ def frames_from_wav(path, cycle_offset_s=0.0):
     if len(x) == 0:
         return np.zeros((0, _lib.NSAMP), np.int16)
     return frames_from_ragged([x[i:i + _lib.NSAMP] for i in range(0, len(x), _lib.NSAMP)])
+
+
+def ap_calls_attempts(h, cfg, llr, bits, mask, max_hd, lock, synth, met=None):
+    """ipass 7 of one candidate's fine LLRs `llr` with the patterns (bits, mask) of _lib.ap_patterns, on handle h, by the rule of
+    kernels/ap_calls.hpp: partial patterns (5..7) BP(bp_nc0_b, bp_iters_b) on the overridden LLRs, and OSD only if BP found no valid
+    word (not for a vector with a NaN); full ones (8..10) a codeword test; each accepted only within max_hd of the hard decisions of
+    `llr`.  -> (ap, 77-bit word, distance, method) of the smallest distance (ties: pattern order), or None.  met (a list): gets the
+    (ap, word) of every valid word the attempts meet, in the batch's event order (accepted or not; a codeword only when accepted)."""
+    llr = np.asarray(llr, np.float32)
+    hard = (llr > 0).astype(np.uint8)
+    best = None
+    for k in range(6):
+        if not mask[k].any():
+            continue
+        ap = 5 + k
+        if ap >= 8:
+            hd = int((bits[k] != hard).sum())
+            word = int("".join(str(int(b)) for b in bits[k][:77]), 2)
+            res = (word, hd, _lib.M_AP_CODEWORD)
+            if hd > max_hd:
+                continue
+        else:
+            x = np.where(mask[k] == 1, np.where(bits[k] == 1, 5.0, -5.0), llr).astype(np.float32)[None]
+            with lock:
+                ok, lo, hi, _, _, _ = h.ldpc(x, cfg.bp_nc0_b, cfg.bp_iters_b)
+                method = _lib.M_LDPC_B
+                if not ok[0] and not np.isnan(x).any():
+                    ok, lo, hi, _ = h.osd(x, cfg.osd_single, cfg.osd_double, cfg.osd_triple)
+                    method = _lib.M_OSD
+            if not ok[0]:
+                continue
+            word = (int(hi[0]) << 64) | int(lo[0])
+            cw = synth.encode174(word)
+            hd = int(sum(((cw >> (173 - i)) & 1) != hard[i] for i in range(174)))
+            res = (word, hd, method)
+        if met is not None:
+            met.append((ap, word))
+        if res[1] <= max_hd and (best is None or res[1] < best[2]):
+            best = (ap, res[0], res[1], res[2])
+    return best
 
 
 class Candidate:
@@ -210,6 +265,30 @@ class Candidate:
             self.decode_notes = f"{self.source}_{self.pat_name}_OSD"
             self.decode_result = D.osd_012(self.llr)
 
+    def _decode_ap_calls(self, rx):
+        """ipass 7 (ft8rx_set_ap_calls) of this candidate through the single-vector entry points, as k_bp_ap / k_osd_ap /
+        k_select_ap do it in the batch: every enabled pattern on the fine LLRs, the smallest distance within ap_max_hd wins.  The
+        valid words met before the accepted one go through the call-hash table first, as the batch's replay of its events does."""
+        from . import decoders as D
+        from . import synth
+        bits, mask = _lib.ap_patterns(rx.cfg.ap_my_call, rx.cfg.ap_dx_call)
+        max_hd = rx.cfg.ap_max_hd if rx.cfg.ap_max_hd is not None else _lib.AP_MAX_HD_DEFAULT
+        met = []
+        with rx._hlock:
+            best = ap_calls_attempts(rx._handle(1), rx.cfg, self.llr0, bits, mask, max_hd, rx._hlock, synth, met)
+        if best is None:
+            for _, w in met:
+                D.unpack(w)
+            return False
+        ap, word, hd, method = best
+        for a, w in met:
+            if a < ap:
+                D.unpack(w)
+        self.decode_result = D.unpack(word)
+        self.ap_result = dict(ap=ap, word=word, osd_hd=hd, method=method)
+        self.decode_notes = "fine_" + _m.AP_CALL_NAMES[ap - 5].replace(" ", "_") + "_" + ("LDPC20", "OSD", "CODEWORD")[(2, 3, 5).index(method)]
+        return self.decode_result is not None
+
     def decode(self, current_max_ipass):
         """One step of the ipass ladder per call (reference receiver.py:68-107)."""
         if self._rx is None:
@@ -240,7 +319,11 @@ class Candidate:
             for self.pat_name, self.llr in self.saved_llrs:
                 self._attempt("osd", None)
         elif step == 7:
-            self.decode_result = "stop"
+            found = False
+            if self.source == "fine" and not self.decode_result and (rx.cfg.ap_my_call or rx.cfg.ap_dx_call):
+                found = self._decode_ap_calls(rx)
+            if not found:
+                self.decode_result = "stop"
         if step == 2:
             self.llr0 = self.llr.copy()
         if step in _LADDER:
@@ -578,6 +661,21 @@ class Receiver:
     def set_band(self, band):
         self.band = band
 
+    def _ap_on(self):
+        return bool(self.cfg.ap_my_call or self.cfg.ap_dx_call)
+
+    def set_ap_calls(self, my_call=None, dx_call=None):
+        """The operator's own call and the call of the station being worked, as known bits of an extra decode step (ipass 7, after the
+        reference's ladder).  None / "" = unset.  Cheap: call it whenever the DX station changes; in live mode it
+        takes effect at the next cycle.  Standard callsigns only."""
+        set_ap_calls_cfg(self.cfg, my_call, dx_call)
+        with self._hlock:
+            if self._h is not None:
+                self._h.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
+        with self._live_lock:
+            if self._live is not None:
+                self._live.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
+
     def search(self, cyclestart_string, odd_even, search_f_idxs=None):
         """Costas sync search over one cycle of audio_in.search_grid (reference receiver.py:338-367).
 
@@ -690,14 +788,16 @@ class Receiver:
             raise _lib.Ft8rxError('research must be "full" or "local"')
         if self.cfg.msg_types and int(passes) > 1:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with msg_types != 0")
+        if self._ap_on() and int(passes) > 1:
+            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with my_call / dx_call (a-priori decoding)")
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
         msgs, mcnt = self._package(rec, cnt, ev, evc)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
-        out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message)
-               for f in range(B)]
+        out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message,
+                                ap=self._ap_on()) for f in range(B)]
         seen = [{" ".join(d["msg_tuple"]) for d in out[f]} for f in range(B)]
         for _ in range(1, int(passes)):
             sigs = self._subtraction_list(msgs, mcnt, rec, subtract_min_snr)
@@ -816,7 +916,8 @@ class Receiver:
             with self._live_lock:
                 rec, cnt, ev, evc = self._live_handle().decode_batch(frame[None])
             msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
-            dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC))
+            dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
+                                     ap=self._ap_on())
             seen = self._cycle_seen.setdefault(t0, set())
             for k in [k for k in self._cycle_seen if k < t0 - 4 * T_CYC]:
                 del self._cycle_seen[k]
