@@ -38,6 +38,8 @@
  *     ft8rx_osd_ext                                                                    (order-3 / distance-gate knobs)
  *     ft8rx_set_msg_types  ft8rx_package_batch_ext  ft8rx_valid77_ext                  (opt-in message types)
  *     ft8rx_set_ap_calls  ft8rx_set_ap_max_hd  ft8rx_ap_patterns  ft8rx_ap_calls_probe (opt-in a-priori calls, ipass 7)
+ *     ft8rx_set_recall  ft8rx_fetch_recall  ft8rx_set_recall_gates  ft8rx_recall_hypotheses  ft8rx_recall_probe  ft8rx_package_batch_recall
+ *                                                                                      (opt-in recall of stations heard 30 s earlier, ipass 8)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
@@ -116,7 +118,8 @@ typedef struct {
 enum { FT8RX_ST_ACTIVE = 0, FT8RX_ST_DECODED = 1, FT8RX_ST_STOP_GRID_SD = 2, FT8RX_ST_STOP_COSTAS = 3,
        FT8RX_ST_STOP_FINE_SD = 4, FT8RX_ST_EXHAUSTED = 5 };
 enum { FT8RX_M_GOOD91 = 0, FT8RX_M_LDPC_A = 1, FT8RX_M_LDPC_B = 2, FT8RX_M_OSD = 3, FT8RX_M_LDPC_B_OSD = 4,
-       FT8RX_M_AP_CODEWORD = 5 /* ipass 7, full pattern: codeword test (ft8rx_set_ap_calls) */ };
+       FT8RX_M_AP_CODEWORD = 5 /* ipass 7, full pattern: codeword test (ft8rx_set_ap_calls) */,
+       FT8RX_M_RECALL = 6      /* ipass 8: hypothesis test of a recall entry (ft8rx_set_recall) */ };
 
 /* One candidate's outcome (replaces the state of a reference `Candidate`, receiver.py:29-66). 48 bytes. */
 typedef struct {
@@ -312,6 +315,50 @@ int  ft8rx_ap_patterns(const char* my_call, const char* dx_call, uint8_t* bits_o
  * and ap / method / osd_hd where a pattern was accepted, status EXHAUSTED otherwise) and the frame's event log (events: FT8RX_EVENT_CAP
  * entries; *event_count may exceed that).  -1 while no call is set. */
 int  ft8rx_ap_calls_probe(ft8rx_handle* h, const float* llr, int n, ft8rx_record* records, ft8rx_event* events, int32_t* event_count);
+/* Opt-in recall decoding (extension): ipass 8.  A recall entry is a message the same stream decoded two cycles
+ * (30 s) earlier, with its grid position.  For every entry the next batch runs a forced fine sync at (f0_idx, h0_idx) -- the tweak
+ * scan runs; the sync threshold, the Costas gate and llr_sd_min are not applied -- and tests the entry's likely continuations against
+ * the LLRs of that grid: for "A B X" (A a standard call) the word itself, A B RRR / RR73 / 73, A B -30 .. +30, A B R-30 .. R+30 (the
+ * repeat's duplicate dropped; at most 126); for "CQ / QRZ / DE B X" the word itself.  The hypothesis whose codeword has the smallest
+ * soft distance D = sum |llr| over the disagreeing positions wins (ties: list order); it is accepted iff its Hamming distance hd to
+ * the hard decisions is <= max_hd and the runner-up's hd exceeds it by >= min_gap (no runner-up: hd 174).
+ * Only i3 = 1 / 2 words whose second call is a standard call and whose first is a standard call or a DE / QRZ / CQ token qualify;
+ * others are skipped.  An entry is also skipped when a ladder record of its frame is DECODED within +-2 f0 bins and +-4 h0 rows.
+ * The ladder's records, counts and events do not change: results go to a separate area, ft8rx_fetch_recall. */
+#define FT8RX_RECALL_MAX 64                  /* entries per frame */
+#define FT8RX_RECALL_MAX_HD_DEFAULT 46
+#define FT8RX_RECALL_MIN_GAP_DEFAULT 12
+typedef struct {                             /* 24 bytes */
+    uint64_t msg_lo, msg_hi;                 /* the 77-bit word, as ft8rx_record holds it */
+    int16_t  f0_idx, h0_idx;                 /* its grid position (the record's) */
+    int8_t   ttweak, ftweak;                 /* its fine tweaks (informative: the forced fine sync scans its own) */
+    uint16_t pad;                            /* 0 */
+} ft8rx_recall_entry;
+/* entries [n_frames][FT8RX_RECALL_MAX] (row f: counts[f] <= FT8RX_RECALL_MAX entries of frame f of the next batch), consumed by the
+ * next enqueue (ft8rx_enqueue_batch*, ft8rx_decode_batch), like ft8rx_set_search_mask; the batch must have exactly n_frames frames.
+ * Waits for the batches in flight.  NULL / n_frames = 0 clears a pending setting.  Positions outside the configured search range are
+ * refused.  Refused with msg_types != 0 and on the packed output; ft8rx_decode_messages refuses a pending setting. */
+int  ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const int32_t* counts, int n_frames);
+/* the recall results of the batch the last ft8rx_fetch_results / ft8rx_decode_batch handed out: records [n_frames][FT8RX_RECALL_MAX]
+ * (record e = entry e: ipass 8, method FT8RX_M_RECALL, status DECODED (accepted) or EXHAUSTED (tested, rejected), ap = the
+ * hypothesis class 0 repeat / 1 RRR / 2 RR73 / 3 73 / 4 report / 5 R-report, n_its = its index in the list, osd_hd = its hd,
+ * pad2 = the runner-up's hd, score / grid_sd = the two soft distances (grid_sd -1: no runner-up), fine_sd / snr_fine of the grid's
+ * LLRs, ttweak / ftweak / nsync of the forced fine sync; a skipped entry's record stays zero) and counts [n_frames] (0 for a batch
+ * enqueued without entries). */
+int  ft8rx_fetch_recall(ft8rx_handle* h, int n_frames, ft8rx_record* records, int32_t* counts);
+/* max_hd 1..174, min_gap 0..174; applies to batches enqueued afterwards */
+int  ft8rx_set_recall_gates(ft8rx_handle* h, int32_t max_hd, int32_t min_gap);
+/* Host only (tests): the hypothesis list of one entry -> its length (0: the entry does not qualify), words [126] */
+int  ft8rx_recall_hypotheses(const ft8rx_recall_entry* entry, uint64_t* words_lo, uint64_t* words_hi);
+/* Test entry: k_recall_score alone on caller-supplied fine grids sgrid [n][79][8] (magnitudes, ft8rx_fine's sgrid) for entries [n]
+ * (no skip rule, tweaks 0) -> records [n] as ft8rx_fetch_recall gives them. */
+int  ft8rx_recall_probe(ft8rx_handle* h, const float* sgrid, const ft8rx_recall_entry* entries, int n, ft8rx_record* records);
+/* ft8rx_package_batch plus each frame's recall results (ft8rx_fetch_recall: recall [n_frames][FT8RX_RECALL_MAX], recall_counts): after
+ * all of a frame's ladder messages, the accepted ones in entry order (cand = the entry index, ipass 8), unless the frame has emitted
+ * the same text already; each updates the call-hash table as a ladder decode of the word does.  No GPU needed. */
+int  ft8rx_package_batch_recall(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
+                                const ft8rx_record* recall, const int32_t* recall_counts, int n_frames, int max_cands, ft8rx_message* out,
+                                int max_msgs, int32_t* out_counts, int n_threads, ft8rx_hashes* table, int32_t* flags);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -44,6 +44,8 @@ class Config(C.Structure):
     ap_my_call = None
     ap_dx_call = None
     ap_max_hd = None                 # None = the library's default (FT8RX_AP_MAX_HD_DEFAULT)
+    # recall (ft8rx_set_recall, ipass 8): entries are set per batch; this flag only marks a receiver that uses them (refusals)
+    recall = False
 
 
 RECORD_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("score", "<f4"), ("grid_sd", "<f4"), ("fine_sd", "<f4"),
@@ -79,6 +81,14 @@ AP_MAX_HD_DEFAULT = 36               # FT8RX_AP_MAX_HD_DEFAULT
 AP_CALL_PATTERNS = {5: ("MY ???", "my"), 6: ("MY DX ???", "both"), 7: ("CQ DX ???", "dx"),
                     8: ("MY DX RRR", "both"), 9: ("MY DX 73", "both"), 10: ("MY DX RR73", "both")}
 M_GOOD91, M_LDPC_A, M_LDPC_B, M_OSD, M_LDPC_B_OSD = range(5)
+# recall of stations heard 30 s earlier (ft8rx_set_recall, ipass 8; include/ft8rx.h)
+M_RECALL = 6                         # FT8RX_M_RECALL
+RECALL_MAX = 64                      # FT8RX_RECALL_MAX: entries per frame
+RECALL_MAX_HD_DEFAULT, RECALL_MIN_GAP_DEFAULT = 46, 12      # FT8RX_RECALL_MAX_HD_DEFAULT / _MIN_GAP_DEFAULT
+RECALL_CLASSES = ("repeat", "RRR", "RR73", "73", "report", "R-report")      # the record's ap field on ipass 8
+RECALL_ENTRY_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("f0_idx", "<i2"), ("h0_idx", "<i2"), ("ttweak", "i1"),
+                               ("ftweak", "i1"), ("pad", "<u2")])
+assert RECALL_ENTRY_DTYPE.itemsize == 24
 
 _libs = {}
 _reject_log = [None]                  # set_reject_log's current path: applied to builds loaded later as well
@@ -489,6 +499,57 @@ class Handle:
             raise Ft8rxError(f"set_search_mask: mask must be [n_frames, {nf0}]")
         self._chk(self._L.ft8rx_set_search_mask(self._h, m.ctypes.data_as(C.c_void_p), m.shape[0]), "ft8rx_set_search_mask")
 
+    def set_recall(self, entries, counts=None):
+        """ft8rx_set_recall: recall entries for the NEXT batch (ipass 8) -- entries [n_frames, RECALL_MAX] of
+        RECALL_ENTRY_DTYPE with counts [n_frames], or a list (per frame) of RECALL_ENTRY_DTYPE arrays / lists of entries; None
+        clears a pending setting.  The batch must have n_frames frames."""
+        L = self._L
+        L.ft8rx_set_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if entries is None:
+            self._chk(L.ft8rx_set_recall(self._h, None, None, 0), "ft8rx_set_recall")
+            return
+        if counts is None:
+            rows = [np.asarray(e, RECALL_ENTRY_DTYPE).reshape(-1) for e in entries]
+            if any(len(r) > RECALL_MAX for r in rows):
+                raise Ft8rxError(f"set_recall: at most {RECALL_MAX} entries per frame")
+            ent = np.zeros((len(rows), RECALL_MAX), RECALL_ENTRY_DTYPE)
+            for f, r in enumerate(rows):
+                ent[f, :len(r)] = r
+            counts = [len(r) for r in rows]
+        else:
+            ent = np.ascontiguousarray(entries, RECALL_ENTRY_DTYPE)
+        cnt = np.ascontiguousarray(counts, np.int32)
+        if ent.ndim != 2 or ent.shape[1] != RECALL_MAX or cnt.shape != (ent.shape[0],):
+            raise Ft8rxError(f"set_recall: entries must be [n_frames, {RECALL_MAX}] with counts [n_frames]")
+        self._chk(L.ft8rx_set_recall(self._h, ent.ctypes.data, cnt.ctypes.data, int(ent.shape[0])), "ft8rx_set_recall")
+
+    def fetch_recall(self, B):
+        """ft8rx_fetch_recall: (records [B, RECALL_MAX] of RECORD_DTYPE, counts [B]) of the batch the last fetch / decode_batch handed
+        out; record e belongs to entry e (zero where the entry was skipped)."""
+        rec = np.zeros((int(B), RECALL_MAX), RECORD_DTYPE)
+        cnt = np.zeros(int(B), np.int32)
+        L = self._L
+        L.ft8rx_fetch_recall.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(L.ft8rx_fetch_recall(self._h, int(B), rec.ctypes.data, cnt.ctypes.data), "ft8rx_fetch_recall")
+        return rec, cnt
+
+    def set_recall_gates(self, max_hd=RECALL_MAX_HD_DEFAULT, min_gap=RECALL_MIN_GAP_DEFAULT):
+        L = self._L
+        L.ft8rx_set_recall_gates.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        self._chk(L.ft8rx_set_recall_gates(self._h, int(max_hd), int(min_gap)), "ft8rx_set_recall_gates")
+
+    def recall_probe(self, sgrid, entries):
+        """ft8rx_recall_probe: k_recall_score alone on fine grids sgrid [n, 79, 8] for entries [n] -> records [n] (RECORD_DTYPE)."""
+        sg = np.ascontiguousarray(sgrid, np.float32).reshape(-1, 632)
+        ent = np.ascontiguousarray(entries, RECALL_ENTRY_DTYPE).reshape(-1)
+        if len(ent) != len(sg):
+            raise Ft8rxError("recall_probe: one grid per entry")
+        rec = np.zeros(len(ent), RECORD_DTYPE)
+        L = self._L
+        L.ft8rx_recall_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(L.ft8rx_recall_probe(self._h, sg.ctypes.data, ent.ctypes.data, len(ent), rec.ctypes.data), "ft8rx_recall_probe")
+        return rec
+
     def set_profiling(self, on):
         self._L.ft8rx_set_profiling(self._h, int(bool(on)))
 
@@ -824,6 +885,50 @@ def package_batch_ext(rec, cnt, ev, evc, mask, max_msgs=None, n_threads=None, ta
         raise Ft8rxError(f"ft8rx_package_batch_ext failed ({rc})")
     _warn_truncation(flags, "package_batch_ext")
     return (out, oc, flags) if return_flags else (out, oc)
+
+
+def package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, max_msgs=None, n_threads=None, table=None):
+    """ft8rx_package_batch_recall: package_batch, then each frame's accepted recall records (fetch_recall) after its ladder messages,
+    in entry order, unless the frame has the text already -> (messages[B, max_msgs], counts[B])."""
+    rec = np.ascontiguousarray(rec)
+    ev = np.ascontiguousarray(ev)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    evc = np.ascontiguousarray(evc, np.int32)
+    rrec = np.ascontiguousarray(rrec, RECORD_DTYPE)
+    rcnt = np.ascontiguousarray(rcnt, np.int32)
+    B, mc = rec.shape
+    if ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE or rrec.shape != (B, RECALL_MAX) or rcnt.shape != (B,):
+        raise Ft8rxError("package_batch_recall: records/events/recall are not the arrays returned by decode_batch/fetch_recall")
+    if max_msgs is None:
+        max_msgs = max(mc, 1) + RECALL_MAX
+    out = np.zeros((B, max_msgs), MESSAGE_DTYPE)
+    oc = np.zeros(B, np.int32)
+    flags = np.zeros(B, np.int32)
+    if n_threads is None:
+        n_threads = min(32, os.cpu_count() or 1)
+    L = lib()
+    L.ft8rx_package_batch_recall.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                C.c_void_p]
+    rc = L.ft8rx_package_batch_recall(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, rrec.ctypes.data, rcnt.ctypes.data,
+                                      int(B), int(mc), out.ctypes.data, int(max_msgs), oc.ctypes.data, int(n_threads),
+                                      table._t if table is not None else None, flags.ctypes.data)
+    if rc != 0:
+        raise Ft8rxError(f"ft8rx_package_batch_recall failed ({rc})")
+    _warn_truncation(flags, "package_batch_recall")
+    return out, oc
+
+
+def recall_hypotheses(entry):
+    """ft8rx_recall_hypotheses (host only): the hypothesis words of one entry (RECALL_ENTRY_DTYPE) as Python ints, in list order;
+    [] for an entry that does not qualify."""
+    e = np.asarray(entry, RECALL_ENTRY_DTYPE).reshape(1)
+    lo, hi = np.zeros(126, np.uint64), np.zeros(126, np.uint64)
+    L = lib()
+    L.ft8rx_recall_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    n = L.ft8rx_recall_hypotheses(e.ctypes.data, lo.ctypes.data, hi.ctypes.data)
+    if n < 0:
+        raise Ft8rxError("ft8rx_recall_hypotheses failed")
+    return [(int(hi[i]) << 64) | int(lo[i]) for i in range(n)]
 
 
 def packed_capacity(n_frames, max_cands=MAX_CANDS, per_frame=None):

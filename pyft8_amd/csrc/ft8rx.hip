@@ -15,6 +15,8 @@
 //                                       with ballot pivoting, lane-per-trial CRC-14 + validity, k_select2
 //   k_bp_ap, k_osd_ap (cand, pattern)   opt-in ipass 7 (ft8rx_set_ap_calls): the operator's and the DX station's calls as known bits,
 //                                       only while a call is set (kernels/ap_calls.hpp)
+//   k_fine (trip), k_recall_score       opt-in ipass 8 (ft8rx_set_recall): forced fine sync at the positions of messages heard 30 s
+//                                       earlier and a hypothesis test per entry, only for a batch with entries (kernels/recall.hpp)
 // A batch is cut into chunks whose chains run on separate HIP streams -- free-running: chunk i of batch k+1 follows chunk i of batch k
 // on stream i, no per-batch fork / join; results land in one of two result slots and are copied to page-locked host buffers by a copy
 // stream while the next batch computes; the used part of the event log is packed by k_ev_scan / k_ev_compact straight into
@@ -48,6 +50,7 @@
 #include "kernels/fine_sync.hpp"
 #include "kernels/osd.hpp"
 #include "kernels/ap_calls.hpp"
+#include "kernels/recall.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -96,6 +99,14 @@ struct ft8rx_handle {
     uint32_t ap_version, ap_chunk_version[16];   // the setting's version, and the version each chunk's device copy holds
     ApCalls* d_apc;                      // [16] per-chunk device copies of `ap`, written on the chunk's stream (enqueue_chain)
     int32_t* d_apcount;                  // [16][2] ipass-7 list lengths per chunk: candidates, OSD attempts
+    // recall (ft8rx_set_recall, kernels/recall.hpp; allocated on first use): the pending entries of the next batch and its per-frame
+    // triple offsets (host copy rc_off), the forced fine sync's scratch, and per result slot the batch's entry copy and results
+    bool rc_armed; int rc_frames; bool rc_td; std::vector<int32_t> rc_off;
+    int32_t rc_max_hd, rc_min_gap;
+    ft8rx_recall_entry* d_rc_src; int32_t* d_rc_srccnt; int32_t* d_rc_off;
+    int32_t* d_rc_trip; int32_t* d_rc_tout; float* d_rc_tsd; float* d_rc_sgrid; float* d_rc_llr;
+    ft8rx_recall_entry* d_rc_ent[2]; int32_t* d_rc_cnt[2]; ft8rx_record* d_rc_rec[2];
+    ft8rx_record* h_rc_rec[2]; int32_t* h_rc_cnt[2]; bool slot_recall[2];
     int sub_frames;                      // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
     hipStream_t sub[8];
     hipEvent_t ev_fork, ev_join[8];
@@ -324,6 +335,8 @@ void ft8rx_destroy(ft8rx_handle* h) {
         if (h->h_evc[k]) hipHostFree(h->h_evc[k]);
         if (h->h_evpacked[k]) hipHostFree(h->h_evpacked[k]);
         if (h->h_pkhdr[k]) hipHostFree(h->h_pkhdr[k]);
+        if (h->h_rc_rec[k]) hipHostFree(h->h_rc_rec[k]);
+        if (h->h_rc_cnt[k]) hipHostFree(h->h_rc_cnt[k]);
     }
     delete h;
 }
@@ -343,6 +356,10 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     h->cfg = *cfg; h->device = device; h->max_frames = max_frames; h->stream = nullptr; h->profiling = false; h->n_stage = 0;
     memset(&h->ap, 0, sizeof(h->ap)); h->ap.max_hd = FT8RX_AP_MAX_HD_DEFAULT; h->ap_version = 0; for (int i = 0; i < 16; i++) h->ap_chunk_version[i] = 0;
     h->d_apc = nullptr; h->d_apcount = nullptr;
+    h->rc_armed = false; h->rc_frames = 0; h->rc_td = false; h->rc_max_hd = FT8RX_RECALL_MAX_HD_DEFAULT; h->rc_min_gap = FT8RX_RECALL_MIN_GAP_DEFAULT;
+    h->d_rc_src = nullptr; h->d_rc_srccnt = nullptr; h->d_rc_off = nullptr; h->d_rc_trip = nullptr; h->d_rc_tout = nullptr; h->d_rc_tsd = nullptr;
+    h->d_rc_sgrid = nullptr; h->d_rc_llr = nullptr;
+    for (int k = 0; k < 2; k++) { h->d_rc_ent[k] = nullptr; h->d_rc_cnt[k] = nullptr; h->d_rc_rec[k] = nullptr; h->h_rc_rec[k] = nullptr; h->h_rc_cnt[k] = nullptr; h->slot_recall[k] = false; }
     h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
     h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
     for (int k = 0; k < 2; k++) { h->ev_comp[k] = h->ev_done[k] = nullptr; h->h_rec[k] = nullptr; h->h_cnt[k] = nullptr; h->h_ev[k] = nullptr; h->h_evc[k] = nullptr; h->h_evpacked[k] = nullptr; h->d_evpacked[k] = nullptr; h->d_evoffs[k] = nullptr; h->slot_B[k] = 0; }
@@ -456,6 +473,15 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
         ok &= hipMemcpyToSymbol(HIP_SYMBOL(d_VAR_E), ve, sizeof(ve)) == hipSuccess;
     }
     ok &= hipMemcpyToSymbol(HIP_SYMBOL(d_G0), FT8_G0, sizeof(FT8_G0)) == hipSuccess;
+    {   // recall's parity columns (kernels/recall.hpp: d_RCG): parity bit 91 + j of the systematic generator
+        static uint64_t rcg[83][2];
+        memset(rcg, 0, sizeof(rcg));
+        for (int r = 0; r < 91; r++) for (int j = 0; j < 83; j++) {
+            const int v = 91 + j;
+            if ((FT8_G0[r][v >> 6] >> (v & 63)) & 1ull) rcg[j][r >> 6] |= 1ull << (r & 63);
+        }
+        ok &= hipMemcpyToSymbol(HIP_SYMBOL(d_RCG), rcg, sizeof(rcg)) == hipSuccess;
+    }
     {   // per-check membership masks (3 x 64 bits), so a lane gets its two checks' masks with 6 coalesced loads
         static uint64_t cm[128][3];
         memset(cm, 0, sizeof(cm));
@@ -661,6 +687,26 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
         }
         launch_ap_calls(h, B, llr0, rec, ncand, attO, ev, evc, wl[WL_BP0].items, wl[WL_OSDNAN].items, h->d_apcount + 2 * chunk, apc, s);
     }
+    if (h->slot_recall[slot]) {
+        // ipass 8 (ft8rx_set_recall, kernels/recall.hpp), after the whole ladder: it reads the ladder's records (skip rule), and the
+        // cycle spectrum it resamples still lies in this chunk's grid region -- only the next batch's k_spectrogram overwrites it
+        STAGE("recall");
+        ft8rx_recall_entry* ent = h->d_rc_ent[slot] + F * FT8RX_RECALL_MAX;
+        int32_t* rcnt = h->d_rc_cnt[slot] + F;
+        k_recall_stage<<<B, FT8RX_RECALL_MAX, 0, s>>>(h->d_rc_src + F * FT8RX_RECALL_MAX, h->d_rc_srccnt + F, ent, rcnt, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
+        const int base = h->rc_off[F], n = h->rc_off[F + B] - base;
+        if (n > 0) {
+            k_recall_trip<<<B, FT8RX_RECALL_MAX, 0, s>>>(ent, rcnt, h->d_rc_off + F, h->d_rc_trip);
+            const size_t b = (size_t)base;
+            ft8rx_ilp_fine(n, s, spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->T, c, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
+                           h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr});
+            if (h->rc_td)          // an entry beyond the frequency-domain h0 range (-6.1 .. +8.3 s): k_fine left it to this one
+                k_fine_td<<<n, FINE_NT, 0, s>>>(spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->T, c, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
+                                                h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr});
+            k_recall_score<<<n, 64, 0, s>>>(h->d_rc_sgrid, h->d_rc_tout, h->d_rc_trip, h->d_rc_off + F, base, ent, rec, ncand, sh,
+                                            h->rc_max_hd, h->rc_min_gap, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
+        }
+    }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
 }
@@ -692,6 +738,9 @@ static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* 
     if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
     const int slot = h->slot_enq;
     if (host_audio && need_staging(h)) return -2;
+    if (h->rc_armed && B != h->rc_frames) { set_err(h, "recall entries were set for %d frames, the batch has %d", h->rc_frames, B); return -1; }
+    h->slot_recall[slot] = h->rc_armed;          // ft8rx_set_recall: consumed by this batch
+    h->rc_armed = false;
     int16_t* stage = h->d_audio;
     hipStream_t cs = h->copy_s;
     if (pipelined) {
@@ -831,6 +880,10 @@ static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* 
     h->slot_evpending[slot] = h->d_evpacked[slot] && (size_t)B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES;
     if (!h->slot_evpending[slot])
         HIPCHK(h, hipMemcpyAsync(h->h_ev[slot], h->s_ev[slot], sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToHost, h->copy_s));
+    if (h->slot_recall[slot]) {
+        HIPCHK(h, hipMemcpyAsync(h->h_rc_cnt[slot], h->d_rc_cnt[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
+        HIPCHK(h, hipMemcpyAsync(h->h_rc_rec[slot], h->d_rc_rec[slot], sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)B, hipMemcpyDeviceToHost, h->copy_s));
+    }
     HIPCHK(h, hipEventRecord(h->ev_done[slot], h->copy_s));
     h->slot_B[slot] = B; h->last_slot = slot; h->slot_enq ^= 1; h->inflight++;
     return 0;
@@ -873,6 +926,7 @@ int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
     if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
     if (mask && h->pk_buf[0]) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
     if (mask && h->ap.np) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_ap_calls"); return -1; }
+    if (mask && h->rc_armed) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_recall"); return -1; }
     h->msg_types = mask;                        // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
     return 0;
 }
@@ -940,6 +994,114 @@ int ft8rx_ap_patterns(const char* my_call, const char* dx_call, uint8_t* bits_ou
         if (bits_out) bits_out[k * 174 + i] = (uint8_t)((a.val[k][i >> 6] >> (i & 63)) & 1ull);
         if (mask_out) mask_out[k * 174 + i] = (uint8_t)((a.msk[k][i >> 6] >> (i & 63)) & 1ull);
     }
+    return 0;
+}
+
+// recall (kernels/recall.hpp): the kind of an entry's word -- RC_CALL "A B X", RC_TOKEN "CQ / QRZ / DE B X", RC_SKIP anything else
+static int recall_kind(uint64_t lo, uint64_t hi) {
+    const unsigned i3 = (unsigned)(lo & 7u);
+    if (i3 != 1 && i3 != 2) return RC_SKIP;
+    const uint64_t ca = ((lo >> 49) | (hi << 15)) & 0xFFFFFFFull, cb = (lo >> 20) & 0xFFFFFFFull;
+    const uint64_t STD = 2063592ull + 4194304ull;                           // NTOKENS + MAX22: the first standard call
+    if (cb < STD || !(ca < 3 || ca >= STD)) return RC_SKIP;
+    hostmsg::Hashes H; std::string f[3];
+    if (!hostmsg::unpack_ext(lo, hi & 0x1FFFull, 0, H, f)) return RC_SKIP;
+    for (int k = 0; k < 3; k++) if (f[k].find('<') != std::string::npos) return RC_SKIP;
+    return ca < 3 ? RC_TOKEN : RC_CALL;
+}
+
+int ft8rx_recall_hypotheses(const ft8rx_recall_entry* entry, uint64_t* words_lo, uint64_t* words_hi) {
+    if (!entry) return -1;
+    const uint64_t lo = entry->msg_lo, hi = entry->msg_hi & 0x1FFFull;
+    const int kind = recall_kind(lo, hi);
+    if (kind == RC_SKIP) return 0;
+    int n = 0;
+    for (int k = 0; k < 126; k++) {                 // the device's list (recall_word), the repeat's duplicate dropped
+        uint64_t w; unsigned g15 = 0, r = 0;
+        if (k == 0) w = lo;
+        else if (kind != RC_CALL) break;
+        else {
+            if (k <= 3) g15 = 32401u + (unsigned)k;
+            else if (k < 65) g15 = (unsigned)(32435 + (k - 4) - 30);
+            else { g15 = (unsigned)(32435 + (k - 65) - 30); r = 1; }
+            w = (lo & ~(0xFFFFull << 3)) | ((uint64_t)g15 << 3) | ((uint64_t)r << 18);
+            if (w == lo) continue;
+        }
+        if (words_lo) words_lo[n] = w;
+        if (words_hi) words_hi[n] = hi;
+        n++;
+    }
+    return n;
+}
+
+static int recall_alloc(ft8rx_handle* h) {
+    if (h->d_rc_src) return 0;
+    const size_t B = (size_t)h->max_frames, N = B * FT8RX_RECALL_MAX;
+    int rc = 0;
+    rc |= dalloc(h, &h->d_rc_src, N); rc |= dalloc(h, &h->d_rc_srccnt, B); rc |= dalloc(h, &h->d_rc_off, B + 1);
+    rc |= dalloc(h, &h->d_rc_trip, N * 3); rc |= dalloc(h, &h->d_rc_tout, N * 5); rc |= dalloc(h, &h->d_rc_tsd, N);
+    rc |= dalloc(h, &h->d_rc_sgrid, N * 632); rc |= dalloc(h, &h->d_rc_llr, N * 174);
+    for (int k = 0; k < 2 && !rc; k++) {
+        rc |= dalloc(h, &h->d_rc_ent[k], N); rc |= dalloc(h, &h->d_rc_cnt[k], B); rc |= dalloc(h, &h->d_rc_rec[k], N);
+        if (!rc && (hipHostMalloc((void**)&h->h_rc_rec[k], sizeof(ft8rx_record) * N, hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc((void**)&h->h_rc_cnt[k], sizeof(int32_t) * B, hipHostMallocDefault) != hipSuccess)) {
+            set_err(h, "ft8rx_set_recall: page-locked result buffers could not be allocated"); rc = -2; }
+    }
+    if (rc) { h->d_rc_src = nullptr; return -2; }
+    return 0;
+}
+
+int ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const int32_t* counts, int n_frames) {
+    if (!h) return -1;
+    ENTER(h);                                   // batches in flight were enqueued under the previous setting
+    if (!entries || n_frames == 0) { h->rc_armed = false; return 0; }
+    if (!counts || n_frames < 1 || n_frames > h->max_frames) { set_err(h, "ft8rx_set_recall: n_frames %d outside [1, %d]", n_frames, h->max_frames); return -1; }
+    if (h->msg_types) { set_err(h, "ft8rx_set_recall: not supported together with msg_types != 0"); return -1; }
+    if (h->pk_buf[0]) { set_err(h, "ft8rx_set_recall: not supported on the packed output"); return -1; }
+    const ft8rx_config& c = h->cfg;
+    std::vector<ft8rx_recall_entry> st((size_t)n_frames * FT8RX_RECALL_MAX);
+    std::vector<int32_t> cnt(n_frames), off(n_frames + 1, 0);
+    bool td = false;
+    for (int f = 0; f < n_frames; f++) {
+        if (counts[f] < 0 || counts[f] > FT8RX_RECALL_MAX) { set_err(h, "ft8rx_set_recall: counts[%d] = %d outside [0, %d]", f, counts[f], FT8RX_RECALL_MAX); return -1; }
+        cnt[f] = counts[f]; off[f + 1] = off[f] + counts[f];
+        for (int e = 0; e < counts[f]; e++) {
+            ft8rx_recall_entry E = entries[(size_t)f * FT8RX_RECALL_MAX + e];
+            if (E.f0_idx < c.f0_lo || E.f0_idx >= c.f0_hi || E.h0_idx < c.h0_lo || E.h0_idx >= c.h0_hi) {
+                set_err(h, "ft8rx_set_recall: entry %d of frame %d at (f0_idx %d, h0_idx %d) lies outside the search range", e, f, E.f0_idx, E.h0_idx); return -1; }
+            E.pad = (uint16_t)recall_kind(E.msg_lo, E.msg_hi);
+            td |= E.h0_idx < FT8RX_MIN_H0_FD || E.h0_idx > FT8RX_MAX_H0_FD;
+            st[(size_t)f * FT8RX_RECALL_MAX + e] = E;
+        }
+    }
+    if (recall_alloc(h)) return -2;
+    HIPCHK(h, hipMemcpy(h->d_rc_src, st.data(), sizeof(ft8rx_recall_entry) * st.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_rc_srccnt, cnt.data(), sizeof(int32_t) * cnt.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_rc_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
+    h->rc_off = off; h->rc_frames = n_frames; h->rc_td = td; h->rc_armed = true;
+    return 0;
+}
+
+int ft8rx_fetch_recall(ft8rx_handle* h, int n_frames, ft8rx_record* records, int32_t* counts) {
+    if (!h) return -1;
+    const int slot = h->fetched_slot;
+    if (slot < 0) { set_err(h, "ft8rx_fetch_recall: no batch has been fetched"); return -1; }
+    if (n_frames < 1 || n_frames > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_recall: %d frames requested, the batch had %d", n_frames, h->slot_B[slot]); return -1; }
+    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
+    if (!h->slot_recall[slot]) {
+        if (counts) memset(counts, 0, sizeof(int32_t) * n_frames);
+        if (records) memset(records, 0, sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)n_frames);
+        return 0;
+    }
+    if (counts) memcpy(counts, h->h_rc_cnt[slot], sizeof(int32_t) * n_frames);
+    if (records) memcpy(records, h->h_rc_rec[slot], sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)n_frames);
+    return 0;
+}
+
+int ft8rx_set_recall_gates(ft8rx_handle* h, int32_t max_hd, int32_t min_gap) {
+    if (!h) return -1;
+    if (max_hd < 1 || max_hd > 174 || min_gap < 0 || min_gap > 174) { set_err(h, "ft8rx_set_recall_gates: max_hd %d / min_gap %d outside [1, 174] / [0, 174]", max_hd, min_gap); return -1; }
+    h->rc_max_hd = max_hd; h->rc_min_gap = min_gap;
     return 0;
 }
 
@@ -1016,6 +1178,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     if (!d_buf0 && !d_buf1) { h->pk_buf[0] = h->pk_buf[1] = nullptr; h->pk_cap = 0; return 0; }
     if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
     if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
+    if (h->rc_armed) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_recall entries are pending"); return -1; }
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -1092,6 +1255,7 @@ int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_me
     if (!h || !audio || !out || !out_counts) return -1;
     if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "ft8rx_decode_messages: bad n_frames / max_msgs"); return -1; }
     if (h->msg_types) { set_err(h, "ft8rx_decode_messages: msg_types != 0 -- ft8rx_message holds only the reference's message types"); return -1; }
+    if (h->rc_armed) { set_err(h, "ft8rx_decode_messages: recall entries (ft8rx_set_recall) are not supported; use ft8rx_decode_batch + ft8rx_fetch_recall"); return -1; }
     h->inflight = 0; h->slot_fetch = h->slot_enq;                     // synchronous entry: nothing older is kept
     if (need_staging(h)) return -2;
     int rc = launch_batch(h, h->d_audio, audio, B);
@@ -1275,6 +1439,33 @@ int ft8rx_ap_calls_probe(ft8rx_handle* h, const float* llr, int n, ft8rx_record*
     HIPCHK(h, hipMemcpy(&ne, d_evc, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (event_count) *event_count = ne;
     if (events) HIPCHK(h, hipMemcpy(events, d_ev, sizeof(ft8rx_event) * (size_t)(ne < FT8RX_EVENT_CAP ? ne : FT8RX_EVENT_CAP), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// k_recall_score alone on caller-supplied fine grids: entry i is frame i's only entry, no ladder records (no skip rule), tweaks 0
+int ft8rx_recall_probe(ft8rx_handle* h, const float* sgrid, const ft8rx_recall_entry* entries, int n, ft8rx_record* records) {
+    if (!h || !sgrid || !entries || !records || n < 1) { if (h) set_err(h, "ft8rx_recall_probe: bad arguments"); return -1; }
+    ENTER(h);
+    Scratch S{h};
+    std::vector<ft8rx_recall_entry> st((size_t)n * FT8RX_RECALL_MAX);
+    std::vector<int32_t> trip(3 * (size_t)n), off(n + 1), tout(5 * (size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        ft8rx_recall_entry E = entries[i];
+        E.pad = (uint16_t)recall_kind(E.msg_lo, E.msg_hi);
+        st[(size_t)i * FT8RX_RECALL_MAX] = E;
+        trip[3 * i] = i; trip[3 * i + 1] = E.f0_idx; trip[3 * i + 2] = E.h0_idx; off[i] = i;
+    }
+    off[n] = n;
+    float* d_sg = S.put(sgrid, (size_t)n * 632); NEED(d_sg);
+    ft8rx_recall_entry* d_ent = S.put(st.data(), st.size()); NEED(d_ent);
+    int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
+    int32_t* d_off = S.put(off.data(), off.size()); NEED(d_off);
+    int32_t* d_tout = S.put(tout.data(), tout.size()); NEED(d_tout);
+    ft8rx_record* d_rec = S.get<ft8rx_record>((size_t)n * FT8RX_RECALL_MAX); NEED(d_rec);
+    HIPCHK(h, hipMemset(d_rec, 0, sizeof(ft8rx_record) * (size_t)n * FT8RX_RECALL_MAX));
+    k_recall_score<<<n, 64, 0, h->stream>>>(d_sg, d_tout, d_trip, d_off, 0, d_ent, nullptr, nullptr, 0, h->rc_max_hd, h->rc_min_gap, d_rec);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy2D(records, sizeof(ft8rx_record), d_rec, sizeof(ft8rx_record) * FT8RX_RECALL_MAX, sizeof(ft8rx_record), n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1571,6 +1762,14 @@ int ft8rx_package_batch_ext(const ft8rx_record* records, const int32_t* counts, 
     if (mask < 0 || mask > FT8RX_MT_ALL) return -1;
     return hostmsg::package_batch(records, counts, events, event_counts, n_frames, max_cands, out, max_msgs, out_counts, n_threads,
                                   table ? &table->H : nullptr, flags, (unsigned)mask);
+}
+
+int ft8rx_package_batch_recall(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
+                               const ft8rx_record* recall, const int32_t* recall_counts, int n_frames, int max_cands, ft8rx_message* out,
+                               int max_msgs, int32_t* out_counts, int n_threads, ft8rx_hashes* table, int32_t* flags) {
+    if (!recall || !recall_counts) return -1;
+    return hostmsg::package_batch(records, counts, events, event_counts, n_frames, max_cands, out, max_msgs, out_counts, n_threads,
+                                  table ? &table->H : nullptr, flags, 0u, recall, recall_counts);
 }
 
 int ft8rx_package_packed(const void* packed, uint64_t bytes, int frame_lo, int n_frames, ft8rx_message* out, int max_msgs,

@@ -329,7 +329,7 @@ static_assert(FT8RX_MAX_CANDS <= PKG_MAX_CANDS, "message layer capacity");
 // mask: the opt-in message types (unpack_ext); 0 for ft8rx_message rows
 template <typename Msg>
 static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, int nev, Msg* out, int cap, Hashes& H, int* flags,
-                         bool sparse = false, unsigned mask = 0) {
+                         bool sparse = false, unsigned mask = 0, const ft8rx_record* rrec = nullptr, int rn = 0) {
     std::vector<Ev> E; E.reserve((size_t)nev);
     int16_t pos[PKG_MAX_CANDS];
     if (sparse) {
@@ -389,6 +389,25 @@ static int package_frame(const ft8rx_record* rec, int n, const ft8rx_event* ev, 
             }
             nm++;
         }
+    }
+    // recall (ipass 8, ft8rx_fetch_recall): after every ladder message, in entry order; record e belongs to entry e (cand = e)
+    for (int e = 0; e < rn; e++) {
+        const ft8rx_record& r = rrec[e];
+        if (r.ipass != 8 || r.status != FT8RX_ST_DECODED) continue;
+        std::string got[3];
+        if (!unpack_ext(r.msg_lo, r.msg_hi, mask, H, got)) continue;
+        std::string text = msg_line(r.msg_lo, got);
+        if (std::find(seen.begin(), seen.end(), text) != seen.end()) continue;
+        seen.push_back(text);
+        if (nm < cap) {
+            Msg& o = out[nm]; memset(&o, 0, sizeof(o));
+            const size_t W = sizeof(o.f[0]) - 1;
+            for (int k = 0; k < 3; k++) { const size_t L = got[k].size() < W ? got[k].size() : W; memcpy(o.f[k], got[k].data(), L); }
+            set_type(o, r.msg_lo);
+            o.cand = (int16_t)e; o.f0_idx = r.f0_idx; o.h0_idx = r.h0_idx; o.ipass = r.ipass; o.ap = r.ap; o.method = r.method;
+            o.fine = 1; o.snr = r.snr_fine; o.ttweak = r.ttweak; o.ftweak = r.ftweak;
+        }
+        nm++;
     }
     if (nm > cap) { if (flags) *flags |= FT8RX_PKG_MSG_TRUNCATED; nm = cap; }
     return nm;
@@ -464,7 +483,8 @@ static void encode_tones(uint64_t lo, uint64_t hi, uint8_t* t) {
 template <typename Msg>
 static int package_batch(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
                          int n_frames, int max_cands, Msg* out, int max_msgs, int32_t* out_counts, int n_threads,
-                         Hashes* table, int32_t* flags, unsigned mask = 0) {
+                         Hashes* table, int32_t* flags, unsigned mask = 0, const ft8rx_record* recall = nullptr,
+                         const int32_t* recall_counts = nullptr) {
     if (!records || !counts || !events || !event_counts || !out || !out_counts || n_frames < 1 || max_cands < 1 || max_msgs < 1) return -1;
     if (n_threads < 1 || table) n_threads = 1;
     if (n_threads > n_frames) n_threads = n_frames;
@@ -479,7 +499,9 @@ static int package_batch(const ft8rx_record* records, const int32_t* counts, con
             int n = counts[f] < 0 ? 0 : (counts[f] > max_cands ? max_cands : counts[f]);
             if (!table) local.clear();
             out_counts[f] = package_frame(records + (size_t)f * max_cands, n, events + (size_t)f * FT8RX_EVENT_CAP, nev,
-                                          out + (size_t)f * max_msgs, max_msgs, table ? *table : local, &fl, false, mask);
+                                          out + (size_t)f * max_msgs, max_msgs, table ? *table : local, &fl, false, mask,
+                                          recall ? recall + (size_t)f * FT8RX_RECALL_MAX : nullptr,
+                                          recall ? (recall_counts[f] < 0 ? 0 : recall_counts[f] > FT8RX_RECALL_MAX ? FT8RX_RECALL_MAX : recall_counts[f]) : 0);
             if (flags) flags[f] = fl;
         }
     };

@@ -19,6 +19,10 @@ AP_NAMES = ("NoAP", "CQ", "RR73", "73", "RRR")
 AP_CALL_NAMES = ("MY ???", "MY DX ???", "CQ DX ???", "MY DX RRR", "MY DX 73", "MY DX RR73")
 
 
+# ipass 8 (ft8rx_set_recall): the hypothesis classes, the record's ap field
+RECALL_CLASSES = ("repeat", "RRR", "RR73", "73", "report", "R-report")
+
+
 def ap_name(ap):
     """The record's ap field -> the pattern's name (the reference's five, then the ipass-7 ones)."""
     return AP_NAMES[ap] if ap < 5 else AP_CALL_NAMES[ap - 5]
@@ -255,6 +259,8 @@ def _msg_text(bits77, text):
 def decode_notes(rec):
     """'{source}_{AP}_{method}' + tweaks, formatted as the reference does (receiver.py:42,57,121,126,133,162)."""
     fine = rec["ipass"] >= 2
+    if rec["ipass"] == 8:
+        return "fine_RECALL_" + RECALL_CLASSES[rec["ap"]], tweaks_str(rec)
     meth = ("GOOD91 ", "LDPC5", "LDPC20", "OSD", "LDPC20_OSD", "CODEWORD")[rec["method"]]
     ap = AP_NAMES[rec["ap"]] if rec["ap"] < 5 else AP_CALL_NAMES[rec["ap"] - 5].replace(" ", "_")
     return ("fine" if fine else "grid") + "_" + ap + "_" + meth, tweaks_str(rec)
@@ -270,13 +276,15 @@ _LAST_IPASS = {2: 0, 3: 1, 4: 1}     # status -> last ladder step taken (STOP_GR
 
 
 def package_frame(rec, count, events, n_events, cyclestart_string="", band=None, odd_even=0, table=None, on_message=None, mask=0,
-                  ap=False):
+                  ap=False, recall=None):
     """Replay one frame's candidate records in the reference's order (receiver.py:389-398):
     per round all live candidates advance one ipass in llr_sd-descending (stable) order; CRC-passing
     unpack() calls update the hash table as they happen; first sighting of a message text is emitted.
     Returns the list of message dicts (reference receiver.py:61-64 keys).  mask != 0: the opt-in message types are rendered too
     (unpack_ext) and every dict gains "msg_type".  ap = True (a handle with a-priori calls, ft8rx_set_ap_calls): every dict gains
-    "ap", the name of the pattern that decoded it.  ipass-7 events sit at slot 2 * ap (BP, codeword test) / 2 * ap + 1 (OSD)."""
+    "ap", the name of the pattern that decoded it.  ipass-7 events sit at slot 2 * ap (BP, codeword test) / 2 * ap + 1 (OSD).
+    recall = (records, count) of the frame's recall area (ft8rx_fetch_recall): after every ladder message, the accepted ipass-8
+    words in entry order, unless the text was emitted already; every dict then gains "recall"."""
     table = table if table is not None else CallHashes()
     rec = rec[:count]
     n_ev = min(int(n_events), len(events))
@@ -341,15 +349,46 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
                     m["msg_type"] = msg_type(word)
                 if ap:
                     m["ap"] = ap_name(int(r["ap"]))
+                if recall is not None:
+                    m["recall"] = False
                 out.append(m)
                 if on_message is not None:
                     on_message(m)
+    if recall is not None:
+        rrec, rcount = recall
+        for r in rrec[:int(rcount)]:
+            if int(r["ipass"]) != 8 or int(r["status"]) != 1:
+                continue
+            word = (int(r["msg_hi"]) << 64) | int(r["msg_lo"])
+            text = unpack_ext(word, table, mask)
+            if text is None:
+                continue
+            msg_text = _msg_text(word, text)
+            if msg_text in seen:
+                continue
+            seen.add(msg_text)
+            tsec = float(int(r["h0_idx"]) / 25.0 + int(r["ttweak"]) / 200)
+            fHz = float(3.125 * int(r["f0_idx"]) + int(r["ftweak"]) / 16)
+            snr = "%+03d" % int(r["snr_fine"])
+            notes, tw = decode_notes(r)
+            m = {"band": band, "tsec": tsec, "fHz": fHz, "msg_tuple": text, "their_snr": snr, "their_tx_cycle": odd_even,
+                 "all_txt_format": f"{cyclestart_string} {snr} {(tsec - 0.6):4.1f} {fHz:4.0f} ~ {msg_text}",
+                 "cyclestart_string": cyclestart_string, "decode_completed": time.time(), "tweaks": tw, "decode_notes": notes + tw}
+            if mask:
+                m["msg_type"] = msg_type(word)
+            if ap:
+                m["ap"] = AP_NAMES[0]
+            m["recall"] = True
+            out.append(m)
+            if on_message is not None:
+                on_message(m)
     return out
 
 
-def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None, ap=False):
+def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None, ap=False, recall=False):
     """Rows of the native packager (ft8rx_package_batch, _lib.MESSAGE_DTYPE) -> the reference's message dicts
-    (receiver.py:57-65).  Same formatting as package_frame above."""
+    (receiver.py:57-65).  Same formatting as package_frame above.  recall = True (ft8rx_package_batch_recall rows): every dict
+    gains "recall", True for the ipass-8 messages."""
     out = []
     now = time.time()
     rows = msgs[:min(int(count), len(msgs))]
@@ -376,7 +415,9 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
         if ext:
             d["msg_type"] = msg_type(ty[0] | (ty[1] << 3))
         if ap:
-            d["ap"] = ap_name(int(ap_))
+            d["ap"] = ap_name(int(ap_)) if ipass != 8 else AP_NAMES[0]
+        if recall:
+            d["recall"] = ipass == 8
         out.append(d)
         if on_message is not None:
             on_message(d)

@@ -573,7 +573,13 @@ class Receiver:
         self.verbose = verbose
         self.band = None
         self.candidates = []
+        # recall (ipass 8): poll feeds each complete cycle the messages of the cycle 30 s before it
+        self.recall = bool(extension_knobs.pop("recall", False))
+        self._recall_hist = {}                                # cycle start -> complete-frame message dicts (recall = True)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
+        if self.recall and self.cfg.msg_types:
+            raise _lib.Ft8rxError("recall=True is not supported together with msg_types != 0")
+        self.cfg.recall = self.recall
         self.search_h0_range = [self.cfg.h0_lo, self.cfg.h0_hi]
         self.search_start_hop = self.search_h0_range[1] + 43 * 4
         self.device = device
@@ -730,7 +736,7 @@ class Receiver:
         return cands
 
     def decode_frames(self, audio_i16, cyclestart_strings=None, return_records=False, passes=1, subtract_min_snr=-10,
-                      sub_pass_osd=True, research="full"):
+                      sub_pass_osd=True, research="full", recall=None):
         """Decode B independent 15-s frames.  -> list (per frame) of message dicts in emit order.
 
         passes > 1 (extension): after each pass every newly decoded signal with SNR > subtract_min_snr is
@@ -742,13 +748,19 @@ class Receiver:
         trial wins, the reference's source of false decodes) found in the later passes -- fewer false decodes, slightly less yield.
         research="local" is the experiment's re-search (receiver_sub.py:434-445), batched: the residual is searched only in the columns
         f0 - 2 .. f0 + 1 of the subtracted signals, with the sync threshold ignored (ft8rx_set_search_mask), and what that finds is not
-        subtracted again -- one sweep for all of a frame's decodes where the experiment does one per decode."""
+        subtracted again -- one sweep for all of a frame's decodes where the experiment does one per decode.
+        recall (ipass 8): per frame a list of the message dicts decoded 30 s before it in the same stream (or
+        None / [] for none) -- their continuations are tested at the same positions; recall messages follow a frame's others and
+        every dict gains "recall".  Of each frame's list the RECALL_MAX qualifying messages with the highest SNR are used."""
         audio = _as_frames(audio_i16)
         B = audio.shape[0]
         if B == 0:
             return ([], np.zeros((0, self.cfg.max_cands), _lib.RECORD_DTYPE), np.zeros(0, np.int32)) if return_records else []
+        if recall is not None and len(recall) != B:
+            raise _lib.Ft8rxError(f"recall: one list of earlier messages per frame ({B}), got {len(recall)}")
         with self._hlock:
-            return self._decode_frames_locked(audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research)
+            return self._decode_frames_locked(audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research,
+                                              recall)
 
     def _local_mask(self, msgs, mcnt, min_snr):
         """Search mask of the local re-search: columns f0 - 2 .. f0 + 1 (receiver_sub.py:440) of every message the sweep subtracts."""
@@ -783,21 +795,37 @@ class Receiver:
             return _lib.package_batch_ext(rec, cnt, ev, evc, self.cfg.msg_types, **kw)
         return _lib.package_batch(rec, cnt, ev, evc, **kw)
 
-    def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full"):
+    def _recall_entries(self, recall):
+        from . import recall as R
+        return [R.entries_from_dicts(d or [], self.cfg) for d in recall]
+
+    def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",
+                              recall=None):
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
+        use_recall = self.recall or recall is not None
+        if use_recall and self.cfg.msg_types:
+            raise _lib.Ft8rxError("recall is not supported together with msg_types != 0")
+        if use_recall and int(passes) > 1:
+            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with recall")
         if self.cfg.msg_types and int(passes) > 1:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with msg_types != 0")
         if self._ap_on() and int(passes) > 1:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with my_call / dx_call (a-priori decoding)")
         local = research == "local"
         h = self._handle(B)
+        if use_recall:
+            h.set_recall(self._recall_entries(recall if recall is not None else [None] * B))
         rec, cnt, ev, evc = h.decode_batch(audio)
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
-        msgs, mcnt = self._package(rec, cnt, ev, evc)
+        if use_recall:
+            rrec, rcnt = h.fetch_recall(B)
+            msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt)
+        else:
+            msgs, mcnt = self._package(rec, cnt, ev, evc)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
         out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message,
-                                ap=self._ap_on()) for f in range(B)]
+                                ap=self._ap_on(), recall=use_recall) for f in range(B)]
         seen = [{" ".join(d["msg_tuple"]) for d in out[f]} for f in range(B)]
         for _ in range(1, int(passes)):
             sigs = self._subtraction_list(msgs, mcnt, rec, subtract_min_snr)
@@ -870,6 +898,8 @@ class Receiver:
         if self.cfg.msg_types:
             raise _lib.Ft8rxError("decode_frames_arrays returns _lib.MESSAGE_DTYPE rows, which cannot hold the message types of msg_types != 0: "
                                   "use decode_frames")
+        if self.recall:
+            raise _lib.Ft8rxError("decode_frames_arrays is not supported with recall=True: use decode_frames(..., recall=)")
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)
@@ -913,11 +943,25 @@ class Receiver:
             # start of the cycle the frame belongs to: a full frame is handed over at its end, an early one inside it
             t0 = T_CYC * int(t_now / T_CYC) if early else T_CYC * int((t_now - T_CYC / 2) / T_CYC)
             cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
+            # recall: only the complete-frame pass, fed with the complete-frame messages of the cycle 30 s earlier (same parity)
+            prev = self._recall_hist.get(t0 - 2 * T_CYC) if self.recall and not early else None
             with self._live_lock:
-                rec, cnt, ev, evc = self._live_handle().decode_batch(frame[None])
-            msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
+                h = self._live_handle()
+                if prev is not None:
+                    h.set_recall(self._recall_entries([prev]))
+                rec, cnt, ev, evc = h.decode_batch(frame[None])
+                if prev is not None:
+                    rrec, rcnt = h.fetch_recall(1)
+            if prev is not None:
+                msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, n_threads=1, table=self.call_hashes)
+            else:
+                msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
             dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
-                                     ap=self._ap_on())
+                                     ap=self._ap_on(), recall=self.recall)
+            if self.recall and not early:
+                self._recall_hist[t0] = dicts
+                for k in [k for k in self._recall_hist if k < t0 - 2 * T_CYC]:
+                    del self._recall_hist[k]
             seen = self._cycle_seen.setdefault(t0, set())
             for k in [k for k in self._cycle_seen if k < t0 - 4 * T_CYC]:
                 del self._cycle_seen[k]
@@ -940,9 +984,9 @@ class Receiver:
         return out
 
 
-def decode_frames(audio_i16, on_message=None, passes=1, research="full", **receiver_kwargs):
+def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=None, **receiver_kwargs):
     """decode_frames(audio_i16[B,180000], **receiver_kwargs) -> list[list[message dict]]  (SURVEY.md 8b); passes > 1 adds the
-    subtraction passes of Receiver.decode_frames."""
+    subtraction passes of Receiver.decode_frames; recall = per frame the message dicts decoded 30 s earlier (Receiver.decode_frames)."""
     audio = _as_frames(audio_i16)
-    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), **receiver_kwargs)
-    return rx.decode_frames(audio, passes=passes, research=research)
+    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, **receiver_kwargs)
+    return rx.decode_frames(audio, passes=passes, research=research, recall=recall)

@@ -319,6 +319,21 @@ def frame_from_words(index, words77, snr_range=(0.0, 8.0), seed_base=SEED_BASE):
     return np.clip(np.rint(x * 1000.0), -32768, 32767).astype(np.int16)
 
 
+def frame_with_signals(index, signals, seed_base=SEED_BASE):
+    """A frame carrying the given signals at given places: signals = [(word77, f0 Hz, t0 s, snr dB), ...] -- e.g. the same station
+    at the same spot in two cycles (recall tests).  Noise as make_frame's, keyed on (seed_base, index)."""
+    rng = np.random.Generator(np.random.Philox(key=seed_base + 99000000 + int(index)))
+    x = rng.standard_normal(NFRAME)
+    for w77, f0, t0, snr in signals:
+        amp = np.sqrt(2.0 * (2500.0 / 6000.0) * 10.0 ** (float(snr) / 10.0))
+        w = tones_to_wave(tones79(int(w77)), float(f0))
+        i0 = int(round(float(t0) * FS))
+        a, b = max(0, i0), min(NFRAME, i0 + len(w))
+        if b > a:
+            x[a:b] += amp * w[a - i0:b - i0]
+    return np.clip(np.rint(x * 1000.0), -32768, 32767).astype(np.int16)
+
+
 def make_batch(start, count, **kw):
     return np.stack([make_frame(start + i, **kw) for i in range(count)])
 
