@@ -1,6 +1,13 @@
 """bench.py -- FT8 15-s frames decoded per second on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--frames B | --config 1|2|3|4]
+    python bench.py --gpus N --steps K --warmup W [--frames B | --config 1|2|3|4] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs if
+asked and prints the line.  Everything else the benchmark measures or checks runs only with --full, after the timed steps
+and outside `value`: the keep-busy steps of --min-seconds (3 s by default there), the kernels-only rate, per-stage HIP-event
+times and the roofline figures built on them, the host-pointer (PCIe-inclusive) passes, BASELINE configs 2-4 and the CPU
+oracle baseline with its decode-set match.  Their keys stay in a plain line, as null.  (With more than one rank, or
+--force-gather, the check of what the gather inside the steps delivered runs in both: one un-overlapped gather.)
 
 Launched as one process per GPU (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`); when --gpus N > 1
 is given WITHOUT a torchrun environment, bench.py starts that launcher itself as a child process (before anything touches the GPU)
@@ -14,8 +21,8 @@ Frames are independent, so ranks shard them with no collective on the decode pat
 than one rank (or --force-gather) every batch's PACKED results -- the decoded / event-logging candidates' records
 and the used event log, ~4 KB per frame -- are gathered to rank 0 over RCCL INSIDE the timed steps, on a side
 stream that overlaps the next batch (pyft8_amd/distributed.py: PackedGather); `value` includes it.
-At N = 1 the default command then also runs BASELINE configs 2, 3 (one rank's shard) and 4 (per GPU) for a few steps
-each and nests them under "other_configs" (outside `value`).
+At N = 1 the default command with --full then also runs BASELINE configs 2, 3 (one rank's shard) and 4 (per GPU) for a few
+steps each and nests them under "other_configs" (outside `value`).
 Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement" for the roofline accounting).
 """
 import argparse
@@ -408,7 +415,9 @@ def dump_outputs(out_dir, msgs, counts, suffix=""):
     return len(frames), len(sel)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line -> (args, the set of --flags given explicitly), with the --config preset and the --full defaults applied."""
+    argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps (default 100 = 0.5 s of config 1: the un-overlapped fetch + host layer of the LAST step, 1.3 ms, then weighs 0.3 %% instead of 1.3 %% at 20)")
@@ -418,8 +427,11 @@ def main():
                     "pyft8_amd.distributed.shard: the first total %% N ranks get one more) instead of --frames per GPU -- an uneven split for flow tests")
     ap.add_argument("--unique", type=int, default=64, help="(host generator only) distinct frames generated per rank, tiled to --frames")
     ap.add_argument("--host-synth", action="store_true", help="generate frames with the numpy generator instead of the device kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-entry", action="store_true", help="skip the informational host-pointer (PCIe-inclusive) passes, whose "
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beyond the headline "
+                    "(keep-busy steps, kernels-only rate, per-stage times and roofline, host-pointer passes, configs 2-4, CPU baseline); "
+                    "a plain run reports those keys as null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-host-entry", action="store_true", help="--full: skip the informational host-pointer (PCIe-inclusive) passes, whose "
                     "chunked launches would mix part-batch kernels into a rocprofv3 per-kernel average")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for flow tests on one GPU)")
     ap.add_argument("--force-gather", action="store_true", help="run the gather collectives even with one rank (a one-rank process group is "
@@ -433,8 +445,8 @@ def main():
     ap.add_argument("--delay-ms", type=float, default=20.0)
     ap.add_argument("--render-gathered", action="store_true", help="rank 0 also renders the messages of ALL gathered frames inside the timed steps "
                     "(by default every rank renders its own shard and rank 0 keeps the packed form of the others)")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1 default command: skip the short runs of BASELINE configs 2-4")
-    ap.add_argument("--other-configs", action="store_true", help="run the short config 2-4 passes even for a non-default workload")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, N = 1 default command: skip the short runs of BASELINE configs 2-4")
+    ap.add_argument("--other-configs", action="store_true", help="--full: run the short config 2-4 passes even for a non-default workload")
     ap.add_argument("--host-threads", type=int, default=None, help="threads of the native host message layer per rank (default: min(32, this rank's CPUs))")
     ap.add_argument("--no-pin", action="store_true", help="leave the rank's CPU affinity alone")
     ap.add_argument("--share-gpu", action="store_true", help="flow tests on a box with fewer GPUs than ranks: rank r uses device r %% device_count "
@@ -454,15 +466,20 @@ def main():
     ap.add_argument("--queue-depth", type=int, default=2, choices=(1, 2), help="batches queued on the GPU behind the one that computes: 2 = "
                     "results are copied out of their slot and the slot is re-enqueued before the batch is packaged (absorbs host-side delays "
                     "of up to a step); 1 = the round-4 loop (views of the result slot, one batch queued)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="after the K timed steps keep stepping (untimed for `value`, reported as "
-                    "extra_steps) until the GPU has been busy this long, so that coarse GPU-activity samplers see the run")
+    ap.add_argument("--min-seconds", type=float, default=None, help="after the K timed steps keep stepping (untimed for `value`, reported as "
+                    "extra_steps) until the GPU has been busy this long, so that coarse GPU-activity samplers see the run (default: 3 with "
+                    "--full, 0 otherwise)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the message lists of the last one "
                     "as DIR/<name>.npy (float32/float64, at most 64 MB: a fixed seeded sample of frames beyond that; dump_outputs); "
                     "rank r > 0 of a multi-rank run writes its shard as <name>.rank<r>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    explicit = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
+    if args.other_configs and not args.full:
+        ap.error("--other-configs is part of --full")
+    if args.min_seconds is None:
+        args.min_seconds = 3.0 if args.full else 0.0
+    explicit = {a.split("=")[0] for a in argv if a.startswith("--")}
     if args.config is not None:
         preset = {1: dict(frames=256), 2: dict(frames=4096, bp_iters=30, osd=(30, 2)), 3: dict(frames=8192),
                   4: dict(frames=2048, signals=10, snr=(-24.0, -20.0), osd3=30, osd_max_hd=32)}[args.config]
@@ -471,7 +488,11 @@ def main():
                 setattr(args, k, v)
         if args.config >= 2 and "--steps" not in explicit:
             args.steps, args.warmup = 3, 1
+    return args, explicit
 
+
+def main():
+    args, explicit = parse_args()
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
         # not under a launcher: start one as a CHILD process (nothing has touched the GPU yet) and pass its exit code on
@@ -563,7 +584,9 @@ def main():
         uniq = B
         d_audio = torch.empty((B, _lib.NSAMP), dtype=torch.int16, device="cuda")
         h.synth_frames(d_audio.data_ptr(), frame0, B, n_signals=args.signals, snr_range=tuple(args.snr))
-        frames = d_audio[:min(B, 192)].cpu().numpy()  # CPU-baseline sample (bounded by cpu_baseline's 15-s budget)
+        frames = None                                 # CPU-baseline sample (--full; bounded by cpu_baseline's 15-s budget)
+        if args.full and not args.no_cpu_baseline:
+            frames = d_audio[:min(B, 192)].cpu().numpy()
         data_desc = f"{B} distinct device-generated frames"
     torch.cuda.synchronize()
 
@@ -704,16 +727,19 @@ def main():
         extra_steps, extra_dt = n_more, time.perf_counter() - t_e
         if smi is not None:
             smi.join(timeout=30)
-    # kernel-only rate (no D2H, no host layer), informational
-    h.sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        h.enqueue(d_audio.data_ptr(), B)
-    h.sync()
-    kernel_only = B * args.steps / (time.perf_counter() - t1)
+    # kernel-only rate (no D2H, no host layer), informational (--full)
+    kernel_only = None
+    if args.full:
+        h.sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            h.enqueue(d_audio.data_ptr(), B)
+        h.sync()
+        kernel_only = B * args.steps / (time.perf_counter() - t1)
     cdev = "cuda" if args.backend == "nccl" else "cpu"
     t = torch.tensor([dt], device=cdev, dtype=torch.float64)
-    own = torch.tensor([dt_own, kernel_only], device=cdev, dtype=torch.float64)   # this rank's own clock (before the closing barrier), for the per-rank table
+    # this rank's own clock (before the closing barrier), for the per-rank table; NaN: kernels-only rate not measured
+    own = torch.tensor([dt_own, float("nan") if kernel_only is None else kernel_only], device=cdev, dtype=torch.float64)
     per_rank_raw = [own]
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -722,20 +748,23 @@ def main():
     dt = float(t.item())
     per_rank_raw = [[float(x) for x in r.tolist()] for r in per_rank_raw]
 
-    # per-kernel timing (HIP events on the library's stream), outside the timed region
-    h.set_profiling(True)
-    samples = {}
-    for _ in range(5):
-        h.enqueue(d_audio.data_ptr(), B)
-        h.sync()
-        for k, v in h.stage_times().items():
-            samples.setdefault(k, []).append(v)
-    acc = {k: float(np.median(v)) for k, v in samples.items()}       # median of 5 launches per stage
-    h.set_profiling(False)
-    rec, cnt, ev, evc = h.fetch(B)
-    # informational: the host-pointer entry (ft8rx_decode_batch: pageable host audio -> H2D -> kernels -> D2H), PCIe inclusive
+    # per-kernel timing (HIP events on the library's stream), outside the timed region (--full)
+    acc = None
     pcie = pcie_pinned = pcie_sync = None
-    if not args.no_host_entry:
+    n_dec = n_fine = n_msgs = None
+    if args.full:
+        h.set_profiling(True)
+        samples = {}
+        for _ in range(5):
+            h.enqueue(d_audio.data_ptr(), B)
+            h.sync()
+            for k, v in h.stage_times().items():
+                samples.setdefault(k, []).append(v)
+        acc = {k: float(np.median(v)) for k, v in samples.items()}       # median of 5 launches per stage
+        h.set_profiling(False)
+        rec, cnt, ev, evc = h.fetch(B)
+    # informational: the host-pointer entry (ft8rx_decode_batch: pageable host audio -> H2D -> kernels -> D2H), PCIe inclusive
+    if args.full and not args.no_host_entry:
         host_audio = d_audio.cpu().numpy()
         h.decode_batch(host_audio)
         t2 = time.perf_counter()
@@ -768,11 +797,12 @@ def main():
             gc.enable()
             gather = keep_gather
         del host_audio, pinned
-    n_dec = int(sum((rec[f][:cnt[f]]["status"] == 1).sum() for f in range(B)))
-    # candidates that ran the fine-sync kernel: everything not decoded / stopped on the grid LLRs (ipass 0)
-    valid = np.arange(rec.shape[1])[None, :] < cnt[:, None]
-    n_fine = int((valid & ~(((rec["status"] == 1) & (rec["ipass"] < 2)) | (rec["status"] == 2))).sum())
-    n_msgs = sum(len(messages.package_frame(rec[f], int(cnt[f]), ev[f], int(evc[f]))) for f in range(min(B, 16)))
+    if args.full:
+        n_dec = int(sum((rec[f][:cnt[f]]["status"] == 1).sum() for f in range(B)))
+        # candidates that ran the fine-sync kernel: everything not decoded / stopped on the grid LLRs (ipass 0)
+        valid = np.arange(rec.shape[1])[None, :] < cnt[:, None]
+        n_fine = int((valid & ~(((rec["status"] == 1) & (rec["ipass"] < 2)) | (rec["status"] == 2))).sum())
+        n_msgs = sum(len(messages.package_frame(rec[f], int(cnt[f]), ev[f], int(evc[f]))) for f in range(min(B, 16)))
 
     # the gather ran inside the timed steps; here (outside) rank 0 checks what arrived: one packed part per rank, rank 0's own part
     # against its local results (decoded set byte for byte, messages rendered from the packed form = from the dense arrays)
@@ -843,9 +873,9 @@ def main():
         except Exception as e:                    # validation outside the timed region: report, do not lose the line
             gather_note = f"gather check failed: {type(e).__name__}: {e}"
 
-    # the other single-GPU BASELINE configurations, a few steps each, outside `value` (N = 1, default command)
+    # the other single-GPU BASELINE configurations, a few steps each, outside `value` (--full, N = 1, default command)
     other = None
-    if world == 1 and not args.no_other_configs and ((default_workload and args.config is None) or args.other_configs):
+    if args.full and world == 1 and not args.no_other_configs and ((default_workload and args.config is None) or args.other_configs):
         other = {}
         if gather is not None:
             gather.close()
@@ -864,14 +894,16 @@ def main():
         placements = [None] * world
         dist.all_gather_object(placements, placement)
     if rank == 0:
-        dom = max(acc, key=acc.get)
-        dom_ms = acc[dom]
-        achieved = ALG_BYTES[dom] * B / (dom_ms * 1e-3) / 1e9
+        if acc is not None:                           # (--full: the per-stage times the roofline figures rest on)
+            dom = max(acc, key=acc.get)
+            dom_ms = acc[dom]
+            achieved = ALG_BYTES[dom] * B / (dom_ms * 1e-3) / 1e9
         value = job_frames * args.steps / dt
         line = {
             "metric": "FT8 15-s frames decoded/sec", "value": value, "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": args.full,                        # False: the measurements and checks beyond the headline were not run, their keys are null
             # What `value` is: K steps of the whole path (kernels, D2H, every message rendered on the host) with the batch's audio RESIDENT
             # IN HBM and the SAME batch decoded in every step (the bench contract's definition).  SURVEY 8d defines the metric with the
             # H2D in it: `value_8d_host_audio` is the same loop over the same K steps with the audio handed over in page-locked HOST
@@ -886,13 +918,13 @@ def main():
             "config": {"workload": f"{'config 1: ' if (B, args.signals, reference_knobs) == (256, 50, True) else ''}batch of {B} synthetic 15-s frames "
                                    f"per GPU ({data_desc}), {args.signals} signals/frame, {args.snr[0]:+.0f}..{args.snr[1]:+.0f} dB SNR, "
                                    f"{'Receiver defaults' if reference_knobs else 'extension knobs'} ({knobs}); audio resident in HBM, same batch every step",
-                       "frames_per_gpu": B, "decoded_candidates_per_frame": n_dec / B,
+                       "frames_per_gpu": B, "decoded_candidates_per_frame": n_dec / B if n_dec is not None else None,
                        "unique_messages_first16": n_msgs, "messages_per_frame": float(mc_.mean()),
                        "kernel_only_frames_per_s_this_rank": kernel_only, "host_message_threads": pk_threads, "queue_depth": args.queue_depth,
                        "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                        "host_pointer_sync_entry_frames_per_s_pageable": pcie, "host_pointer_sync_entry_frames_per_s_pinned": pcie_sync,
                        "host_pointer_pipelined_entry_frames_per_s_pinned": pcie_pinned, "parallelism": f"frames sharded over {world} GPU(s), no collective on the decode path", "gather": gather_note},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "roofline": None if acc is None else {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(dom, pmc_key),
                          # the kernel's REAL memory rate: counter traffic / duration / peak (frac above prices the algorithmic bytes of SURVEY
                          # 8d, which the kernel mostly finds in L2: nobody should read it as achieved bandwidth)
@@ -923,22 +955,24 @@ def main():
                                           "fine sync 0.78 G of 18 full IFFTs); the kernel executes ONE pruned IFFT, eight frequency-domain scores and a frequency-domain grid "
                                           "per candidate (0.63 MFLOP), fused multiply-adds only where the arithmetic contract names them (the "
                                           "frequency-domain scores are almost all fma: its ceiling lies between the plain-op and the fma rate)"}},
-            "roofline_valu": roofline_valu(acc, B, dom) if default_workload else None,
-            "stage_ms": {k: round(v, 4) for k, v in acc.items()},
+            "roofline_valu": roofline_valu(acc, B, dom) if default_workload and acc is not None else None,
+            "stage_ms": {k: round(v, 4) for k, v in acc.items()} if acc is not None else None,
             "other_configs": other,
             # each rank's own clock over the K timed steps (value uses the max), its kernels-only rate, and where it ran
             "per_rank": {"ms_per_step": [round(1e3 * r[0] / args.steps, 4) for r in per_rank_raw],
                          "frames_per_s": [round(n * args.steps / r[0], 1) for n, r in zip(shard_counts, per_rank_raw)], "frames": shard_counts,
-                         "kernel_only_frames_per_s": [round(r[1], 1) for r in per_rank_raw],
+                         "kernel_only_frames_per_s": [round(r[1], 1) if r[1] == r[1] else None for r in per_rank_raw],      # (NaN: not measured)
                          "placement": placements, "gather": gather_info},
         }
         if not args.no_cpu_baseline:
-            # the CPU oracle timed on this box's host cores: rank 0 at N = 1 only (the contract); null in multi-GPU runs
-            os.sched_setaffinity(0, orig_affinity)      # the CPU baseline may use every host core, not this rank's slice
-            gpu_texts = None
-            if world == 1 and reference_knobs and not args.host_synth:           # the same frames, the reference's knobs on both sides
-                gpu_texts = [[" ".join(x.decode() for x in msgs_[f, i]["f"]) for i in range(int(mc_[f]))] for f in range(min(B, len(frames)))]      # (all three fields: an empty third one keeps its separator, as " ".join(msg_tuple) does)
-            line["cpu_baseline"] = cpu_baseline(frames, gpu_texts=gpu_texts) if world == 1 else None
+            # the CPU oracle timed on this box's host cores: rank 0 at N = 1 with --full only (the contract); null in multi-GPU and plain runs
+            line["cpu_baseline"] = None
+            if world == 1 and args.full:
+                os.sched_setaffinity(0, orig_affinity)      # the CPU baseline may use every host core, not this rank's slice
+                gpu_texts = None
+                if reference_knobs and not args.host_synth:                       # the same frames, the reference's knobs on both sides
+                    gpu_texts = [[" ".join(x.decode() for x in msgs_[f, i]["f"]) for i in range(int(mc_[f]))] for f in range(min(B, len(frames)))]      # (all three fields: an empty third one keeps its separator, as " ".join(msg_tuple) does)
+                line["cpu_baseline"] = cpu_baseline(frames, gpu_texts=gpu_texts)
         try:                                  # whatever native libraries hold in their stdio buffers (RCCL's version banner) goes out first:
             import ctypes                     # the JSON line is the LAST line of stdout
             ctypes.CDLL(None).fflush(None)

@@ -1667,12 +1667,12 @@ def test_randomised_parity_sweep():
 
 
 def test_bench_contract_line():
-    """bench.py must print exactly one JSON line with the driver's keys plus roofline and cpu_baseline."""
+    """bench.py --full must print exactly one JSON line with the driver's keys plus roofline and cpu_baseline."""
     import json as _json
     import subprocess
     import sys as _sys
     from conftest import ROOT
-    out = subprocess.run([_sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "32"],
+    out = subprocess.run([_sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "32", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -1697,3 +1697,29 @@ def test_bench_contract_line():
     m = c["decode_set_match"]                 # BASELINE's metric: "... decode-set match vs CPU ref" -- on the frames the baseline decodes anyway
     assert m["frames_compared"] > 0 and m["frames_identical"] == m["frames_compared"] and m["messages"] > 0
     assert d["value"] > 1000
+
+
+def test_bench_plain_line(tmp_path):
+    """A plain bench.py run (no --full) prints the same headline -- value = frames x steps / timed seconds, ms_per_step -- and writes
+    --dump-outputs; everything only --full measures or checks was not run, and its keys say so with null."""
+    import json as _json
+    import subprocess
+    import sys as _sys
+    from conftest import ROOT
+    out = subprocess.run([_sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "32",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1
+    d = _json.loads(lines[0])
+    assert d["metric"] == "FT8 15-s frames decoded/sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 1000
+    assert abs(d["value"] - 32 * 2 / (d["ms_per_step"] * 2 * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_valu", "stage_ms", "other_configs", "cpu_baseline", "value_8d_host_audio", "value_incl_h2d",
+              "extra_steps_frames_per_s"):
+        assert d[k] is None, k
+    assert d["extra_steps"] == 0 and d["config"]["kernel_only_frames_per_s_this_rank"] is None
+    assert d["per_rank"]["kernel_only_frames_per_s"] == [None]
+    counts = np.load(os.path.join(str(tmp_path), "message_counts.npy"))
+    assert len(counts) == 32 and abs(counts.mean() - d["config"]["messages_per_frame"]) < 1e-9
+    assert len(np.load(os.path.join(str(tmp_path), "msg_text.npy"))) == int(counts.sum()) > 0
