@@ -40,8 +40,10 @@
  *     ft8rx_set_ap_calls  ft8rx_set_ap_max_hd  ft8rx_ap_patterns  ft8rx_ap_calls_probe (opt-in a-priori calls, ipass 7)
  *     ft8rx_set_recall  ft8rx_fetch_recall  ft8rx_set_recall_gates  ft8rx_recall_hypotheses  ft8rx_recall_probe  ft8rx_package_batch_recall
  *                                                                                      (opt-in recall of stations heard 30 s earlier, ipass 8)
+ *     ft8rx_set_weak                                                                   (opt-in weak-signal sync)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
+ *     ft8rx_sync_scores_weak  ft8rx_fine_weak
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
  *
  * LIMITS of this build against the reference's open-ended kwargs (pyft8_amd.receiver.config_from_kwargs names the kwarg when one is
@@ -293,6 +295,18 @@ int  ft8rx_set_ladder_mode(ft8rx_handle* h, int mode);
  * ft8rx_package_batch_ext; ft8rx_decode_messages and the packed output (ft8rx_set_packed_output) refuse a non-zero mask.  Applies to
  * batches enqueued afterwards.  A handle setting rather than a field of ft8rx_config, whose layout callers' bindings hard-code. */
 int  ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask);
+/* Opt-in weak-signal sync (extension).  on != 0 changes three stages of the batches enqueued afterwards:
+ *   search   the Costas score summed over all three blocks (k_sync3), kept above sync_min instead of config.sync_score_min;
+ *   fine     a joint scan of ftweak -56 .. +56 (step 8, +-3.5 Hz) x ttweak -16 .. +16 (step 2) scored on all three blocks (k_fine_weak);
+ *   gates    no llr_sd_min stop at grid or fine -- the Costas gate (>= 7 of 21) is the only stop before the decoders -- and every OSD
+ *            trial (ipass 5, 6) counts only within osd_max_hd of the hard decisions (config.osd_max_hd, when non-zero, wins).
+ * The ladder, BP, OSD, the LLR arithmetic and the message layer are unchanged; records keep their layout (ttweak / ftweak now span
+ * -16 .. 16 / -56 .. 56).  on = 0 restores the reference's stages (sync_min and osd_max_hd are then ignored).  Only writes host state,
+ * allocates nothing; batches in flight keep the setting they were enqueued with.  Refused together with msg_types != 0,
+ * ft8rx_set_ap_calls, ft8rx_set_recall and the packed output.  sync_min > 0, osd_max_hd 1 .. 174. */
+#define FT8RX_WEAK_SYNC_MIN_DEFAULT 148.5f
+#define FT8RX_WEAK_OSD_MAX_HD_DEFAULT 30
+int  ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_hd);
 /* Opt-in a-priori decoding with the operator's own call and the DX station's call (extension).  NULL or ""
  * = unset; both unset (the default) = the reference's ladder, same kernels and launches.  With a call set, a candidate the whole
  * reference ladder left undecoded after the fine stage (status EXHAUSTED) gets ipass 7: the patterns whose calls are set --
@@ -382,6 +396,8 @@ int  ft8rx_sync_search(ft8rx_handle* h, const float* grid, int n_frames,
  * threshold, stable sort and cut (receiver.py:350-367) are the caller's; Receiver.search uses this for `search_f_idxs` lists that
  * are not the configured range. */
 int  ft8rx_sync_scores(ft8rx_handle* h, const float* grid, int n_frames, int f0_lo, int f0_hi, float* score, int32_t* h0_idx);
+/* ft8rx_sync_scores with weak mode's three-block score (k_sync3; ft8rx_set_weak), whatever the handle's setting */
+int  ft8rx_sync_scores_weak(ft8rx_handle* h, const float* grid, int n_frames, int f0_lo, int f0_hi, float* score, int32_t* h0_idx);
 /* Candidate._get_llr_grid/_dB_to_llr (receiver.py:136-138, 208-222) for n (frame,f0,h0) triples */
 int  ft8rx_llr_grid(ft8rx_handle* h, const float* grid, int n_frames, int n, const int32_t* frame,
                     const int32_t* f0_idx, const int32_t* h0_idx, float* llr /*[n][174]*/, float* sd, int32_t* snr);
@@ -392,6 +408,11 @@ int  ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int n_frames, f
 int  ft8rx_fine(ft8rx_handle* h, const float* spec, int n_frames, int n, const int32_t* frame,
                 const int32_t* f0_idx, const int32_t* h0_idx, int32_t* ret, int32_t* ttweak, int32_t* ftweak,
                 int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid);
+/* ft8rx_fine with weak mode's joint scan (k_fine_weak; ft8rx_set_weak), whatever the handle's setting: ret[i] is 1 or 0 (no sd
+ * gate), sd / snr are reported all the same.  Triples must lie in [0, n_frames) x [4, FT8RX_MAX_F0) x [FT8RX_MIN_H0, FT8RX_MAX_H0). */
+int  ft8rx_fine_weak(ft8rx_handle* h, const float* spec, int n_frames, int n, const int32_t* frame,
+                     const int32_t* f0_idx, const int32_t* h0_idx, int32_t* ret, int32_t* ttweak, int32_t* ftweak,
+                     int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid);
 /* ldpc_decode(llr, max_ncheck0, max_iters) (decoders.py:153-171) on n vectors.
  * ok[i]=1 => msg; has_out[i]=1 => llr_out[i] holds the mutated llr (the reference's third return) */
 int  ft8rx_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters,

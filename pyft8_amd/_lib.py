@@ -46,6 +46,11 @@ class Config(C.Structure):
     ap_max_hd = None                 # None = the library's default (FT8RX_AP_MAX_HD_DEFAULT)
     # recall (ft8rx_set_recall, ipass 8): entries are set per batch; this flag only marks a receiver that uses them (refusals)
     recall = False
+    # opt-in weak-signal sync (ft8rx_set_weak): a handle setting too, applied by Handle at create time.
+    # None = the library's defaults (FT8RX_WEAK_SYNC_MIN_DEFAULT / FT8RX_WEAK_OSD_MAX_HD_DEFAULT)
+    weak = False
+    weak_sync_min = None
+    weak_osd_max_hd = None
 
 
 RECORD_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("score", "<f4"), ("grid_sd", "<f4"), ("fine_sd", "<f4"),
@@ -77,6 +82,8 @@ assert RECORD_DTYPE.itemsize == 48 and EVENT_DTYPE.itemsize == 24 and MESSAGE_DT
 ST_ACTIVE, ST_DECODED, ST_STOP_GRID_SD, ST_STOP_COSTAS, ST_STOP_FINE_SD, ST_EXHAUSTED = range(6)
 M_AP_CODEWORD = 5                    # ipass 7, full pattern (include/ft8rx.h FT8RX_M_AP_CODEWORD)
 AP_MAX_HD_DEFAULT = 36               # FT8RX_AP_MAX_HD_DEFAULT
+WEAK_SYNC_MIN_DEFAULT = 148.5        # FT8RX_WEAK_SYNC_MIN_DEFAULT
+WEAK_OSD_MAX_HD_DEFAULT = 30         # FT8RX_WEAK_OSD_MAX_HD_DEFAULT
 # ipass-7 patterns (record field ap = 5 .. 10, ft8rx_set_ap_calls): name, calls it needs
 AP_CALL_PATTERNS = {5: ("MY ???", "my"), 6: ("MY DX ???", "both"), 7: ("CQ DX ???", "dx"),
                     8: ("MY DX RRR", "both"), 9: ("MY DX 73", "both"), 10: ("MY DX RR73", "both")}
@@ -267,6 +274,19 @@ class Handle:
             self.set_ap_max_hd(self.cfg.ap_max_hd)
         if getattr(self.cfg, "ap_my_call", None) or getattr(self.cfg, "ap_dx_call", None):
             self.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
+        if getattr(self.cfg, "weak", False):
+            self.set_weak(True, self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd)
+
+    def set_weak(self, on, sync_min=None, osd_max_hd=None):
+        """ft8rx_set_weak: weak-signal sync for the batches enqueued afterwards (None = the library's defaults)."""
+        L = self._L
+        L.ft8rx_set_weak.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32]
+        sm = WEAK_SYNC_MIN_DEFAULT if sync_min is None else float(sync_min)
+        hd = WEAK_OSD_MAX_HD_DEFAULT if osd_max_hd is None else int(osd_max_hd)
+        self._chk(L.ft8rx_set_weak(self._h, int(bool(on)), sm, hd), "ft8rx_set_weak")
+        self.cfg.weak = bool(on)
+        if on:
+            self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd = sync_min, osd_max_hd
 
     def set_ap_calls(self, my_call=None, dx_call=None):
         """ft8rx_set_ap_calls: the operator's own call and the DX station's call as ipass-7 a-priori bits (None / "" = unset); applies
@@ -594,14 +614,17 @@ class Handle:
                                           _ptr(sc, C.c_float), _ptr(cnt, C.c_int32)), "ft8rx_sync_search")
         return f0, h0, sc, cnt
 
-    def sync_scores(self, grid, f0_lo, f0_hi):
-        """ft8rx_sync_scores: per frame and f0 in [f0_lo, f0_hi) the best Costas score (first strict maximum over h0, from 0) and its h0."""
+    def sync_scores(self, grid, f0_lo, f0_hi, weak=False):
+        """ft8rx_sync_scores: per frame and f0 in [f0_lo, f0_hi) the best Costas score (first strict maximum over h0, from 0) and its h0.
+        weak=True: ft8rx_sync_scores_weak, the score summed over all three Costas blocks (k_sync3)."""
         grid = self._grid(grid)
         B, n = grid.shape[0], int(f0_hi) - int(f0_lo)
         sc = np.zeros((B, max(n, 1)), np.float32); h0 = np.zeros((B, max(n, 1)), np.int32)
         L = self._L
-        L.ft8rx_sync_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(L.ft8rx_sync_scores(self._h, grid.ctypes.data, B, int(f0_lo), int(f0_hi), sc.ctypes.data, h0.ctypes.data), "ft8rx_sync_scores")
+        name = "ft8rx_sync_scores_weak" if weak else "ft8rx_sync_scores"
+        fn = getattr(L, name)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(fn(self._h, grid.ctypes.data, B, int(f0_lo), int(f0_hi), sc.ctypes.data, h0.ctypes.data), name)
         return sc, h0
 
     def llr_grid(self, grid, frame, f0, h0):
@@ -622,7 +645,8 @@ class Handle:
         self._chk(self._L.ft8rx_cycle_spectrum(self._h, _ptr(audio, C.c_int16), B, s.ctypes.data_as(C.POINTER(C.c_float))), "ft8rx_cycle_spectrum")
         return s
 
-    def fine(self, spec, frame, f0, h0, want_sgrid=False):
+    def fine(self, spec, frame, f0, h0, want_sgrid=False, weak=False):
+        """ft8rx_fine (weak=True: ft8rx_fine_weak, the joint three-block scan of weak mode) for (frame, f0, h0) triples."""
         spec = np.ascontiguousarray(spec, np.complex64)
         if spec.ndim == 1:
             spec = spec[None]
@@ -633,10 +657,11 @@ class Handle:
         ret, tt, ft, ns, snr = (np.zeros(n, np.int32) for _ in range(5))
         llr = np.zeros((n, 174), np.float32); sd = np.zeros(n, np.float32)
         sg = np.zeros((n, 79, 8), np.float32) if want_sgrid else None
-        self._chk(self._L.ft8rx_fine(self._h, spec.ctypes.data_as(C.POINTER(C.c_float)), spec.shape[0], n, _ptr(frame, C.c_int32),
-                                   _ptr(f0, C.c_int32), _ptr(h0, C.c_int32), _ptr(ret, C.c_int32), _ptr(tt, C.c_int32), _ptr(ft, C.c_int32),
-                                   _ptr(ns, C.c_int32), _ptr(llr, C.c_float), _ptr(sd, C.c_float), _ptr(snr, C.c_int32),
-                                   _ptr(sg, C.c_float) if want_sgrid else None), "ft8rx_fine")
+        name = "ft8rx_fine_weak" if weak else "ft8rx_fine"
+        self._chk(getattr(self._L, name)(self._h, spec.ctypes.data_as(C.POINTER(C.c_float)), spec.shape[0], n, _ptr(frame, C.c_int32),
+                                         _ptr(f0, C.c_int32), _ptr(h0, C.c_int32), _ptr(ret, C.c_int32), _ptr(tt, C.c_int32), _ptr(ft, C.c_int32),
+                                         _ptr(ns, C.c_int32), _ptr(llr, C.c_float), _ptr(sd, C.c_float), _ptr(snr, C.c_int32),
+                                         _ptr(sg, C.c_float) if want_sgrid else None), name)
         return dict(ret=ret, ttweak=tt, ftweak=ft, nsync=ns, llr=llr, sd=sd, snr=snr, sgrid=sg)
 
     def ldpc(self, llr, max_ncheck0, max_iters):

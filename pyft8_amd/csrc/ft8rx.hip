@@ -15,6 +15,8 @@
 //                                       with ballot pivoting, lane-per-trial CRC-14 + validity, k_select2
 //   k_bp_ap, k_osd_ap (cand, pattern)   opt-in ipass 7 (ft8rx_set_ap_calls): the operator's and the DX station's calls as known bits,
 //                                       only while a call is set (kernels/ap_calls.hpp)
+//   k_sync3, k_fine_weak                opt-in weak mode (ft8rx_set_weak): the sync search and the fine sync scored on all three Costas
+//                                       blocks, a wide joint fine scan, no sd gates, an OSD distance gate
 //   k_fine (trip), k_recall_score       opt-in ipass 8 (ft8rx_set_recall): forced fine sync at the positions of messages heard 30 s
 //                                       earlier and a hypothesis test per entry, only for a batch with entries (kernels/recall.hpp)
 // A batch is cut into chunks whose chains run on separate HIP streams -- free-running: chunk i of batch k+1 follows chunk i of batch k
@@ -95,6 +97,7 @@ struct ft8rx_handle {
     int n_streams;                       // chunks of a batch run their kernel chains on separate streams
     int ladder_mode;                     // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
     int msg_types;                       // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
+    bool weak; float weak_sync_min; int32_t weak_osd_max_hd;     // opt-in weak mode (ft8rx_set_weak; off = the reference's stages)
     ApCalls ap;                          // ipass-7 patterns (ft8rx_set_ap_calls; ap.np = 0: off), as the host last set them
     uint32_t ap_version, ap_chunk_version[16];   // the setting's version, and the version each chunk's device copy holds
     ApCalls* d_apc;                      // [16] per-chunk device copies of `ap`, written on the chunk's stream (enqueue_chain)
@@ -360,7 +363,8 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     h->d_rc_src = nullptr; h->d_rc_srccnt = nullptr; h->d_rc_off = nullptr; h->d_rc_trip = nullptr; h->d_rc_tout = nullptr; h->d_rc_tsd = nullptr;
     h->d_rc_sgrid = nullptr; h->d_rc_llr = nullptr;
     for (int k = 0; k < 2; k++) { h->d_rc_ent[k] = nullptr; h->d_rc_cnt[k] = nullptr; h->d_rc_rec[k] = nullptr; h->h_rc_rec[k] = nullptr; h->h_rc_cnt[k] = nullptr; h->slot_recall[k] = false; }
-    h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
+    h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->weak = false; h->weak_sync_min = FT8RX_WEAK_SYNC_MIN_DEFAULT;
+    h->weak_osd_max_hd = FT8RX_WEAK_OSD_MAX_HD_DEFAULT; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
     h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
     for (int k = 0; k < 2; k++) { h->ev_comp[k] = h->ev_done[k] = nullptr; h->h_rec[k] = nullptr; h->h_cnt[k] = nullptr; h->h_ev[k] = nullptr; h->h_evc[k] = nullptr; h->h_evpacked[k] = nullptr; h->d_evpacked[k] = nullptr; h->d_evoffs[k] = nullptr; h->slot_B[k] = 0; }
     h->slot_enq = h->slot_fetch = h->inflight = 0; h->last_slot = -1;
@@ -581,6 +585,26 @@ static void launch_sync(const float* grid, float* bs, int32_t* bh, const ft8rx_c
     }
 }
 
+// weak mode (ft8rx_set_weak): the three-block score over the configured h0 range, in windows of SYNC3_WIN offsets
+static void launch_sync3(const float* grid, float* bs, int32_t* bh, const ft8rx_config& c, int B, hipStream_t s) {
+    const int ntile = (c.f0_hi - c.f0_lo + 15) / 16;
+    for (int lo = c.h0_lo; lo < c.h0_hi; lo += SYNC3_WIN) {
+        ft8rx_config w = c;
+        w.h0_lo = lo; w.h0_hi = lo + SYNC3_WIN < c.h0_hi ? lo + SYNC3_WIN : c.h0_hi;
+        if (lo == c.h0_lo) k_sync3<<<dim3(ntile, B), 256, 0, s>>>(grid, bs, bh, w);
+        else k_sync3_acc<<<dim3(ntile, B), 256, 0, s>>>(grid, bs, bh, w);
+    }
+}
+// The configuration the existing kernels see in weak mode: the weak sync threshold (k_topk), no sd stop at grid or fine
+// (k_grid_llr, k_fine_weak), and the OSD distance gate -- an explicit config.osd_max_hd wins over the setting's
+static ft8rx_config weak_config(const ft8rx_handle* h) {
+    ft8rx_config w = h->cfg;
+    w.sync_score_min = h->weak_sync_min;
+    w.llr_sd_min = -INFINITY;
+    if (!w.osd_max_hd) w.osd_max_hd = h->weak_osd_max_hd;
+    return w;
+}
+
 // ipass 7 of B frames (kernels/ap_calls.hpp): candidate list in cand_items (B * stride entries), OSD list in osd_items (B * stride * 3),
 // attempt results in attO (B * stride * 10), the two list counters at ac; the batch chain and ft8rx_ap_calls_probe launch the same
 static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_record* rec, const int32_t* ncand, Att* attO, ft8rx_event* ev,
@@ -598,7 +622,9 @@ static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_rec
 }
 
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
-    const ft8rx_config& c = h->cfg;
+    const bool weak = h->weak;                                     // the setting this batch was enqueued with
+    const ft8rx_config cw = weak ? weak_config(h) : h->cfg;
+    const ft8rx_config& c = weak ? cw : h->cfg;
     const size_t F = (size_t)f0;
     const int sh = cand_shift(c); const size_t S = (size_t)1 << sh, FS = F * S;        // candidate stride (ft8rx_create)
     const int16_t* audio = d_audio + F * FT8RX_NSAMP;
@@ -616,7 +642,8 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     STAGE("spectrogram");
     ft8rx_ilp_spectrogram(B, s, audio, grid, h->T);
     STAGE("sync");
-    launch_sync(grid, bs, bh, c, B, s);
+    if (!weak) launch_sync(grid, bs, bh, c, B, s);
+    else launch_sync3(grid, bs, bh, c, B, s);
     STAGE("topk");
     k_topk<<<B, 1024, 0, s>>>(bs, bh, rec, ncand, c, evc, wc, h->use_mask ? h->d_colmask + F * NF0MAX : nullptr);
     STAGE("grid_llr");
@@ -634,9 +661,13 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     k_cyc_a<<<dim3(40, B), 256, 0, s>>>(audio, A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, s>>>(A, spec, h->T);
     STAGE("fine");
-    ft8rx_ilp_fine(ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
-    if (c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1)      // a search_time_range beyond -6.1 .. +8.3 s: the candidates k_fine leaves out
-        k_fine_td<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
+    if (weak)
+        k_fine_weak<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
+    else {
+        ft8rx_ilp_fine(ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
+        if (c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1)      // a search_time_range beyond -6.1 .. +8.3 s: the candidates k_fine leaves out
+            k_fine_td<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
+    }
     k_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl[WL_BP1]);
     STAGE("bp_fine");
     // fine-stage BP: in ladder order (three launches; decided candidates drop out), or -- ft8rx_set_ladder_mode(h, 1), for small
@@ -921,12 +952,28 @@ int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > 8) return
 int ft8rx_set_subbatch(ft8rx_handle* h, int frames) { if (!h || frames < 0) return -1; h->sub_frames = frames; return 0; }
 int ft8rx_set_ladder_mode(ft8rx_handle* h, int mode) { if (!h || mode < 0 || mode > 1) return -1; h->ladder_mode = mode; return 0; }
 
+int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_hd) {
+    if (!h) return -1;
+    if (on) {
+        if (!(sync_min > 0.0f) || !(sync_min < INFINITY)) { set_err(h, "ft8rx_set_weak: sync_min %g must be a positive score", (double)sync_min); return -1; }
+        if (osd_max_hd < 1 || osd_max_hd > 174) { set_err(h, "ft8rx_set_weak: osd_max_hd %d outside [1, 174]", osd_max_hd); return -1; }
+        if (h->pk_buf[0]) { set_err(h, "ft8rx_set_weak: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
+        if (h->msg_types) { set_err(h, "ft8rx_set_weak: not supported together with msg_types != 0"); return -1; }
+        if (h->ap.np) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_ap_calls"); return -1; }
+        if (h->rc_armed) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_recall"); return -1; }
+        h->weak_sync_min = sync_min; h->weak_osd_max_hd = osd_max_hd;
+    }
+    h->weak = on != 0;                          // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
+    return 0;
+}
+
 int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
     if (!h) return -1;
     if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
     if (mask && h->pk_buf[0]) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
     if (mask && h->ap.np) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_ap_calls"); return -1; }
     if (mask && h->rc_armed) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_recall"); return -1; }
+    if (mask && h->weak) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_weak"); return -1; }
     h->msg_types = mask;                        // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
     return 0;
 }
@@ -974,6 +1021,7 @@ int ft8rx_set_ap_calls(ft8rx_handle* h, const char* my_call, const char* dx_call
     std::string err;
     if (build_ap_patterns(my_call, dx_call, &a, &err)) { set_err(h, "ft8rx_set_ap_calls: %s", err.c_str()); return -1; }
     if (a.np && h->msg_types) { set_err(h, "ft8rx_set_ap_calls: not supported together with msg_types != 0"); return -1; }
+    if (a.np && h->weak) { set_err(h, "ft8rx_set_ap_calls: not supported together with ft8rx_set_weak"); return -1; }
     if (a.np && h->pk_buf[0]) { set_err(h, "ft8rx_set_ap_calls: not supported on the packed output"); return -1; }
     h->ap = a; h->ap_version++;                 // batches in flight keep the setting they were enqueued with (enqueue_chain)
     return 0;
@@ -1057,6 +1105,7 @@ int ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const i
     if (!entries || n_frames == 0) { h->rc_armed = false; return 0; }
     if (!counts || n_frames < 1 || n_frames > h->max_frames) { set_err(h, "ft8rx_set_recall: n_frames %d outside [1, %d]", n_frames, h->max_frames); return -1; }
     if (h->msg_types) { set_err(h, "ft8rx_set_recall: not supported together with msg_types != 0"); return -1; }
+    if (h->weak) { set_err(h, "ft8rx_set_recall: not supported together with ft8rx_set_weak"); return -1; }
     if (h->pk_buf[0]) { set_err(h, "ft8rx_set_recall: not supported on the packed output"); return -1; }
     const ft8rx_config& c = h->cfg;
     std::vector<ft8rx_recall_entry> st((size_t)n_frames * FT8RX_RECALL_MAX);
@@ -1179,6 +1228,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
     if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
     if (h->rc_armed) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_recall entries are pending"); return -1; }
+    if (h->weak) { set_err(h, "ft8rx_set_packed_output: not supported together with ft8rx_set_weak"); return -1; }
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -1314,21 +1364,30 @@ int ft8rx_sync_search(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx
     return 0;
 }
 
-int ft8rx_sync_scores(ft8rx_handle* h, const float* grid, int B, int f0_lo, int f0_hi, float* score, int32_t* h0_idx) {
+static int sync_scores(ft8rx_handle* h, const float* grid, int B, int f0_lo, int f0_hi, float* score, int32_t* h0_idx, bool weak) {
+    const char* who = weak ? "ft8rx_sync_scores_weak" : "ft8rx_sync_scores";
     if (!h || !grid || !score || !h0_idx || B < 1 || B > h->max_frames) return -1;
     if (f0_lo < 4 || f0_hi <= f0_lo || f0_hi > FT8RX_GRID_COLS - 15 || f0_hi - f0_lo > NF0MAX) {
-        set_err(h, "ft8rx_sync_scores: f0 range [%d, %d) outside [4, %d]", f0_lo, f0_hi, FT8RX_GRID_COLS - 15); return -1; }
+        set_err(h, "%s: f0 range [%d, %d) outside [4, %d]", who, f0_lo, f0_hi, FT8RX_GRID_COLS - 15); return -1; }
     ENTER(h);
     ft8rx_config c = h->cfg;
     c.f0_lo = f0_lo; c.f0_hi = f0_hi;
     HIPCHK(h, hipMemcpy(h->d_grid, grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyHostToDevice));
-    const int nf0 = f0_hi - f0_lo, ntile = (nf0 + 15) / 16;
-    launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
+    const int nf0 = f0_hi - f0_lo;
+    if (weak) launch_sync3(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
+    else launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy2DAsync(score, sizeof(float) * nf0, h->d_best_score, sizeof(float) * NF0MAX, sizeof(float) * nf0, B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpy2DAsync(h0_idx, sizeof(int32_t) * nf0, h->d_best_h0, sizeof(int32_t) * NF0MAX, sizeof(int32_t) * nf0, B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+int ft8rx_sync_scores(ft8rx_handle* h, const float* grid, int B, int f0_lo, int f0_hi, float* score, int32_t* h0_idx) {
+    return sync_scores(h, grid, B, f0_lo, f0_hi, score, h0_idx, false);
+}
+int ft8rx_sync_scores_weak(ft8rx_handle* h, const float* grid, int B, int f0_lo, int f0_hi, float* score, int32_t* h0_idx) {
+    return sync_scores(h, grid, B, f0_lo, f0_hi, score, h0_idx, true);
 }
 
 int ft8rx_llr_grid(ft8rx_handle* h, const float* grid, int B, int n, const int32_t* frame, const int32_t* f0_idx,
@@ -1363,9 +1422,13 @@ int ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int B, float* sp
     return 0;
 }
 
-int ft8rx_fine(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
-               int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid) {
+static int fine_probe(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                      int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid, bool weak) {
     if (!h || !spec || B < 1 || B > h->max_frames || n < 1) return -1;
+    for (int i = 0; weak && i < n; i++)         // every triple must name a frame of the spectrum and a candidate the search could give
+        if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < 4 || f0_idx[i] >= FT8RX_MAX_F0 || h0_idx[i] < FT8RX_MIN_H0 || h0_idx[i] >= FT8RX_MAX_H0) {
+            set_err(h, "%s: triple %d (frame %d, f0 %d, h0 %d) outside [0, %d) x [4, %d) x [%d, %d)", weak ? "ft8rx_fine_weak" : "ft8rx_fine", i,
+                    frame[i], f0_idx[i], h0_idx[i], B, FT8RX_MAX_F0, FT8RX_MIN_H0, FT8RX_MAX_H0); return -1; }
     ENTER(h);
     HIPCHK(h, hipMemcpy(h->d_spec, spec, sizeof(cpx) * (size_t)B * FT8RX_SPEC_BINS, hipMemcpyHostToDevice));
     std::vector<int32_t> trip(3 * (size_t)n);
@@ -1377,8 +1440,13 @@ int ft8rx_fine(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* 
     float* d_sd = S.get<float>(n); NEED(d_sd);
     int32_t* d_out = S.get<int32_t>((size_t)n * 5); NEED(d_out);
     float* d_sg = sgrid ? S.get<float>((size_t)n * 632) : nullptr; if (sgrid) NEED(d_sg);
-    ft8rx_ilp_fine(n, h->stream, h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});
-    k_fine_td<<<n, FINE_NT, 0, h->stream>>>(h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});   // triples k_fine leaves out
+    if (weak) {
+        const ft8rx_config cw = weak_config(h);
+        k_fine_weak<<<n, FINE_NT, 0, h->stream>>>(h->d_spec, nullptr, nullptr, d_llr, h->T, cw, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});
+    } else {
+        ft8rx_ilp_fine(n, h->stream, h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});
+        k_fine_td<<<n, FINE_NT, 0, h->stream>>>(h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});   // triples k_fine leaves out
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<int32_t> o((size_t)n * 5);
     HIPCHK(h, hipMemcpy(o.data(), d_out, sizeof(int32_t) * o.size(), hipMemcpyDeviceToHost));
@@ -1387,6 +1455,15 @@ int ft8rx_fine(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* 
     HIPCHK(h, hipMemcpy(sd, d_sd, sizeof(float) * n, hipMemcpyDeviceToHost));
     if (sgrid) HIPCHK(h, hipMemcpy(sgrid, d_sg, sizeof(float) * (size_t)n * 632, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int ft8rx_fine(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+               int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid) {
+    return fine_probe(h, spec, B, n, frame, f0_idx, h0_idx, ret, ttweak, ftweak, nsync, llr, sd, snr, sgrid, false);
+}
+int ft8rx_fine_weak(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                    int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid) {
+    return fine_probe(h, spec, B, n, frame, f0_idx, h0_idx, ret, ttweak, ftweak, nsync, llr, sd, snr, sgrid, true);
 }
 
 int ft8rx_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t* ok, uint64_t* msg_lo,

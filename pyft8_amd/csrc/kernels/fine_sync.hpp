@@ -846,6 +846,142 @@ __global__ __launch_bounds__(FINE_NT) void k_fine_td(const cpx* __restrict__ spe
         __syncthreads();
     }
 }
+
+// ------------------------------------------------------------------------------------ weak-mode fine sync (ft8rx_set_weak, ipass 1)
+// A joint scan of ftweak -56 .. +56 step 8 (outer) x ttweak -16 .. +16 step 2 (inner), each (fb0 + ft, tb0 + tt) scored on all three
+// Costas blocks the way the reference forms its grid (oracle/ft8_oracle.c: ft8o_fine_grid): the series of the tweak's slice, every
+// symbol's 32-sample DFT at its clamped position, fine_score's per-symbol (on, off) sums in fp64 -- b ascending, then a -- rounded once.
+// The first strict maximum wins; its series gives the 79 x 8 grid.  A tweak whose slice would start below bin 0 (fb0 + ft < 150, only
+// f0 = 4 at ft = -56) is not scanned.  Built from k_fine_td's pieces: one 3200-point IFFT per frequency tweak plus the final one, 17 x 21
+// symbol DFTs per frequency tweak.  The sd gate is the caller's config (weak mode passes one that never stops, ft8rx.hip: weak_config).
+#define FW_NT 15
+#define FW_NTT 17
+FT8_DEV void fine_weak_candidate(int tid, int bid, const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec,
+                                 const int32_t* __restrict__ ncand, float* __restrict__ llr0, const Tables& T, const ft8rx_config& cfg,
+                                 const int32_t* __restrict__ trip, int32_t* __restrict__ t_out, float* __restrict__ t_sd, float* __restrict__ t_sgrid) {
+    __shared__ cpx z[3200];
+    __shared__ cpx w400[400];
+    __shared__ cpx w32[32];
+    __shared__ float mg[640];
+    __shared__ double dsum[FW_NTT * 21 * 2];
+    __shared__ float p[464], llr[176], sq[176], sc[FW_NTT + 3];
+    __shared__ int ish[4];
+    int frame, ci = 0, f0, h0;
+    if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; }
+    else {
+        frame = bid >> cand_shift(cfg); ci = bid & ((1 << cand_shift(cfg)) - 1);
+        if (ci >= ncand[frame]) return;
+        const ft8rx_record& r = rec[bid];
+        if (r.status != FT8RX_ST_ACTIVE) return;
+        f0 = r.f0_idx; h0 = r.h0_idx;
+    }
+    for (int i = tid; i < 400; i += FINE_NT) w400[i] = T.W3200[8 * i];
+    if (tid < 32) w32[tid] = T.W32[tid];
+    __syncthreads();
+    const int fb0 = 50 * f0;
+    const cpx* __restrict__ Sg = spec + (size_t)frame * FT8RX_SPEC_BINS + (fb0 - 182);
+    cpx wq[8];
+    sym32_twiddles(w32, tid & 3, wq);
+    const int tb0 = 8 * h0 + (h0 < 0 ? 1 : 0);
+    float best = 0.0f; int bft = 0, btt = -16; bool any = false;       // block-uniform (every thread runs the same pick)
+#pragma unroll 1
+    for (int fi = 0; fi < FW_NT; fi++) {
+        const int ft = -56 + 8 * fi;
+        if (fb0 + ft < 150) continue;                              // block-uniform
+        __syncthreads();                                           // the previous tweak's series and sums are consumed
+        fine_fft(Sg, 182 + ft, z, w400, T, tid, 0, 3200);
+#pragma unroll 1
+        for (int r = 0; r < (FW_NTT * 21 * 4 + FINE_NT - 1) / FINE_NT; r++) {
+            const int task = tid + FINE_NT * r, qd = task >> 2, n2 = task & 3;
+            const bool valid = qd < FW_NTT * 21;
+            const int ti = valid ? qd / 21 : 0, k = valid ? qd - 21 * ti : 0;
+            const int b = k / 7, a = k - 7 * b;
+            float mag[8];
+            fine_sym_quad<7>(z, tb0 - 16 + 2 * ti + 32 * (36 * b + a), n2, wq, mag);
+            if (valid && n2 == 0) {
+                const int c = d_COSTAS[a];
+                double off = 0.0, on = 0.0;
+#pragma unroll
+                for (int q = 0; q < 7; q++) { const double m = (double)mag[q]; on = (q == c) ? m : on; off += (q == c) ? 0.0 : m; }
+                dsum[(ti * 21 + k) * 2] = on; dsum[(ti * 21 + k) * 2 + 1] = off;
+            }
+        }
+        __syncthreads();
+        if (tid < FW_NTT) {                                        // b ascending, then a (k = 7 b + a ascending), fp64, one rounding
+            double s1 = 0.0, s2 = 0.0;
+            for (int k = 0; k < 21; k++) { s1 += dsum[(tid * 21 + k) * 2]; s2 += dsum[(tid * 21 + k) * 2 + 1]; }
+            sc[tid] = (float)(s1 + W6 * s2);
+        }
+        __syncthreads();
+        for (int ti = 0; ti < FW_NTT; ti++) {                      // ft outer, tt inner: the first strict maximum
+            const float v = sc[ti];
+            if (!any || v > best) { best = v; bft = ft; btt = -16 + 2 * ti; any = true; }
+        }
+    }
+    const int tt = btt, ft = bft, tb = tb0 + tt;
+    // --- the 79 x 8 grid from the series of the chosen tweaks, symbol by symbol at the clamped positions (as k_fine_td)
+    __syncthreads();
+    fine_fft(Sg, 182 + ft, z, w400, T, tid, 0, 3200);
+#pragma unroll 1
+    for (int r = 0; r < (316 + FINE_NT - 1) / FINE_NT; r++) {
+        const int task = tid + FINE_NT * r, sy = task >> 2, n2 = task & 3;
+        const bool valid = sy < 79;
+        float mag[8];
+        fine_sym_quad<8>(z, tb + 32 * (valid ? sy : 0), n2, wq, mag);
+        if (valid && n2 == 0) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) mg[sy * 8 + q] = mag[q];
+        }
+    }
+    __syncthreads();
+    // --- Costas gate, LLRs, record: as k_fine (receiver.py:164-173)
+    bool match = false;
+    if (tid < 21) {
+        int blk = tid / 7, a = tid - blk * 7;
+        const float* q = mg + 8 * (36 * blk + a);
+        int am = 0; for (int t = 1; t < 8; t++) if (q[t] > q[am]) am = t;
+        match = (am == d_COSTAS[a]);
+    }
+    if (tid < 64) { int nm = __popcll(__ballot(match)); if (tid == 0) ish[1] = nm; }
+    __syncthreads();
+    const int nsync = ish[1];
+    if (trip && t_sgrid) for (int i = tid; i < 632; i += FINE_NT) t_sgrid[(size_t)bid * 632 + i] = mg[i];
+    int ret = 1; float sd = 0.0f; int snr = 0;
+    if (nsync <= 6) ret = 0;
+    else {
+        for (int i = tid; i < 464; i += FINE_NT) p[i] = 20.0f * ft8_log10f(mg[8 * (int)d_PAYSYM[i >> 3] + (i & 7)]);
+        __syncthreads();
+        llr_from_p(p, llr, sq, tid, tid < 64, &sd, &snr);
+        if (tid == 0) { sc[FW_NTT] = sd; ish[2] = snr; }
+        __syncthreads();
+        sd = sc[FW_NTT]; snr = ish[2];
+        if (sd <= cfg.llr_sd_min) ret = -1;
+        float* out = llr0 + (size_t)bid * 174;
+        for (int i = tid; i < 174; i += FINE_NT) out[i] = llr[i];
+    }
+    if (tid == 0) {
+        if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
+        else {
+            ft8rx_record& r = rec[bid];
+            r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
+            if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
+            else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }
+        }
+    }
+}
+// test entry (trip != nullptr): one block per (frame, f0, h0) triple.  Pipeline: blocks stride over the fine-sync work list.
+__global__ __launch_bounds__(FINE_NT) void k_fine_weak(const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec,
+                                                       const int32_t* __restrict__ ncand, float* __restrict__ llr0, Tables T, ft8rx_config cfg,
+                                                       const int32_t* __restrict__ trip, int32_t* __restrict__ t_out,
+                                                       float* __restrict__ t_sd, float* __restrict__ t_sgrid, WorkList work) {
+    if (trip) { fine_weak_candidate(threadIdx.x, blockIdx.x, spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid); return; }
+    const int n = *work.count;
+#pragma unroll 1
+    for (int item = blockIdx.x; item < n; item += gridDim.x) {
+        fine_weak_candidate(threadIdx.x, work.items[item], spec, rec, ncand, llr0, T, cfg, nullptr, nullptr, nullptr, nullptr);
+        __syncthreads();
+    }
+}
 #endif  // !FT8RX_ILP_UNIT
 
 #endif

@@ -77,6 +77,93 @@ __global__ __launch_bounds__(256) void k_sync(const float* __restrict__ grid, fl
 __global__ __launch_bounds__(256) void k_sync_acc(const float* __restrict__ grid, float* __restrict__ best_score,
                                                   int32_t* __restrict__ best_h0, ft8rx_config cfg) { sync_block<true>(grid, best_score, best_h0, cfg); }
 
+// ------------------------------------------------------------------------------------ K2w weak-mode sync search (ft8rx_set_weak)
+// The score of k_sync summed over all three Costas blocks: symbol s of block b reads grid row h0 + 4 + 144 b + 4 s (grid_at's rules),
+// S1 and T accumulate in fp64 in the order b, s (T's 14-bin window sums k ascending, as k_sync), score = (float)(S1 + W6 (T - S1)).
+// One tile window of SYNC3_WIN offsets (+ 24 rows) is loaded per block b; each thread keeps the partial sums of its (at most 8)
+// offsets in registers across the three windows, so LDS stays at k_sync's size for a 128-offset window (38 KB, static).
+// accumulate != 0: a later window of a wide search_time_range, as k_sync_acc.
+#define SYNC3_WIN 128
+template <bool accumulate>
+FT8_DEV void sync3_block(const float* __restrict__ grid, float* __restrict__ best_score, int32_t* __restrict__ best_h0, const ft8rx_config& cfg) {
+    constexpr int NR = SYNC3_WIN + 24;
+    __shared__ double T[NR * 16];
+    __shared__ float tile[NR * 29];
+    __shared__ float redS[256];
+    __shared__ int redH[256];
+    const int nh0 = cfg.h0_hi - cfg.h0_lo;                        // <= SYNC3_WIN (launch_sync3)
+    const int nrows = nh0 + 24;
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const int f0base = cfg.f0_lo + 16 * blockIdx.x;
+    const float* g = grid + (size_t)f * FT8RX_GRID_ROWS * FT8RX_GRID_COLS;
+    const int f0l = tid & 15;
+    double s1[SYNC3_WIN / 16], ts[SYNC3_WIN / 16];
+#pragma unroll
+    for (int j = 0; j < SYNC3_WIN / 16; j++) { s1[j] = 0.0; ts[j] = 0.0; }
+#pragma unroll 1
+    for (int b = 0; b < 3; b++) {
+        const int rlo = cfg.h0_lo + 4 + 144 * b;
+        if (b) __syncthreads();                                   // the previous block's sums are read
+        for (int i = tid; i < nrows * 29; i += 256) {
+            const int r = i / 29, c = i - r * 29;
+            const int col = f0base + c;
+            const bool incol = col < FT8RX_GRID_COLS;
+            const uint32_t raw = __float_as_uint(grid_at(g, rlo + r, incol ? col : 0));
+            tile[i] = __uint_as_float(raw & (incol ? 0xFFFFFFFFu : 0u));
+        }
+        __syncthreads();
+        for (int i = tid; i < nrows * 16; i += 256) {
+            const float* row = tile + (i >> 4) * 29 + (i & 15);
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 14; k++) t += (double)row[k];
+            T[i] = t;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SYNC3_WIN / 16; j++) {
+            const int hi = (tid >> 4) + 16 * j;
+            if (hi < nh0) {
+#pragma unroll
+                for (int s = 0; s < 7; s++) {
+                    const int r = hi + 4 * s;
+                    const float* row = tile + r * 29 + f0l;
+                    ts[j] += T[r * 16 + f0l];
+                    const int c = d_COSTAS[s];
+                    s1[j] += (double)row[2 * c] + (double)row[2 * c + 1];
+                }
+            }
+        }
+    }
+    float best = 0.0f; int bh = 0;
+#pragma unroll
+    for (int j = 0; j < SYNC3_WIN / 16; j++) {
+        const int hi = (tid >> 4) + 16 * j;
+        if (hi < nh0) {
+            const float score = (float)(s1[j] + W6 * (ts[j] - s1[j]));
+            if (score > best) { best = score; bh = cfg.h0_lo + hi; }   // ascending h0 => first strict maximum
+        }
+    }
+    redS[tid] = best; redH[tid] = bh;
+    __syncthreads();
+    if (tid < 16) {
+        float bs = 0.0f; int h = 0;
+        for (int gI = 0; gI < 16; gI++) {
+            float s = redS[tid + 16 * gI]; int hh = redH[tid + 16 * gI];
+            if (s > bs || (s == bs && s > 0.0f && hh < h)) { bs = s; h = hh; }
+        }
+        int f0 = f0base + tid;
+        if (f0 < cfg.f0_hi) {
+            const size_t o = (size_t)f * NF0MAX + (f0 - cfg.f0_lo);
+            if (!accumulate || bs > best_score[o]) { best_score[o] = bs; best_h0[o] = h; }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_sync3(const float* __restrict__ grid, float* __restrict__ best_score,
+                                               int32_t* __restrict__ best_h0, ft8rx_config cfg) { sync3_block<false>(grid, best_score, best_h0, cfg); }
+__global__ __launch_bounds__(256) void k_sync3_acc(const float* __restrict__ grid, float* __restrict__ best_score,
+                                                   int32_t* __restrict__ best_h0, ft8rx_config cfg) { sync3_block<true>(grid, best_score, best_h0, cfg); }
+
 // ------------------------------------------------------------------------------------ K3 top-K
 // threshold, stable sort by score descending (ties: f0 ascending = original order), keep max_cands.
 // NF0MAX keys (1024; 2048 in the wide build) on 1024 threads: bitonic network in LDS, KPT compare-exchanges per thread and step.

@@ -189,6 +189,8 @@ class PackedGather:
                                   "decode with Receiver.decode_frames instead")
         if getattr(handle.cfg, "recall", False):
             raise _lib.Ft8rxError("PackedGather: recall is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
+        if getattr(handle.cfg, "weak", False):
+            raise _lib.Ft8rxError("PackedGather: weak=True is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
         self._lib, self.h, self.B, self.dst, self.group, self.repeat = _lib, handle, int(n_frames), dst, group, max(1, int(repeat))
         self.depth = max(2, int(depth))
         self.active = dist.is_initialized() and (dist.get_world_size(group) > 1 or force)

@@ -59,6 +59,7 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
                               "(above 3000 Hz the wide build libft8rx_wide.so is used; the reference fails beyond ~5940 Hz, receiver.py:181-182)")
     mask = msg_types_mask(ext.pop("msg_types", 0))       # a handle setting, not a field of ft8rx_config (_lib.Config.msg_types)
     my_call, dx_call, ap_max_hd = ext.pop("my_call", None), ext.pop("dx_call", None), ext.pop("ap_max_hd", None)
+    weak, weak_sync_min, weak_osd_max_hd = bool(ext.pop("weak", False)), ext.pop("weak_sync_min", None), ext.pop("weak_osd_max_hd", None)
     known = {f[0] for f in _lib.Config._fields_}
     for k, v in ext.items():          # extension knobs: bp_iters_b, osd_single, osd_double, osd_triple, osd_max_hd, ...
         if k not in known:            # like the reference's fixed signature (e.g. the CLI's misspelt `search_timerange`, pyft8.py:137)
@@ -71,7 +72,28 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
             raise _lib.Ft8rxError(f"ap_max_hd={ap_max_hd}: a Hamming distance in 1 .. 174")
         cfg.ap_max_hd = int(ap_max_hd)
     set_ap_calls_cfg(cfg, my_call, dx_call)
+    set_weak_cfg(cfg, weak, weak_sync_min, weak_osd_max_hd)
     return cfg
+
+
+def set_weak_cfg(cfg, weak, sync_min=None, osd_max_hd=None):
+    """Check the weak-mode kwargs (ft8rx_set_weak) and store them in cfg; refuses the opt-ins that act on
+    records after ipass 1 (msg_types, my_call / dx_call), naming both settings."""
+    if not weak:
+        if sync_min is not None or osd_max_hd is not None:
+            raise _lib.Ft8rxError("weak_sync_min / weak_osd_max_hd need weak=True")
+        return
+    if cfg.msg_types:
+        raise _lib.Ft8rxError("weak=True is not supported together with msg_types != 0")
+    if cfg.ap_my_call or cfg.ap_dx_call:
+        raise _lib.Ft8rxError("weak=True is not supported together with my_call / dx_call (a-priori decoding)")
+    if sync_min is not None and not (np.isfinite(float(sync_min)) and float(sync_min) > 0):
+        raise _lib.Ft8rxError(f"weak_sync_min={sync_min}: a positive three-block Costas score")
+    if osd_max_hd is not None and not 1 <= int(osd_max_hd) <= 174:
+        raise _lib.Ft8rxError(f"weak_osd_max_hd={osd_max_hd}: a Hamming distance in 1 .. 174")
+    cfg.weak = True
+    cfg.weak_sync_min = None if sync_min is None else float(sync_min)
+    cfg.weak_osd_max_hd = None if osd_max_hd is None else int(osd_max_hd)
 
 
 def set_ap_calls_cfg(cfg, my_call, dx_call):
@@ -79,6 +101,8 @@ def set_ap_calls_cfg(cfg, my_call, dx_call):
     my_call, dx_call = (my_call or None), (dx_call or None)
     if (my_call or dx_call) and cfg.msg_types:
         raise _lib.Ft8rxError("my_call / dx_call (a-priori decoding) is not supported together with msg_types != 0")
+    if (my_call or dx_call) and getattr(cfg, "weak", False):
+        raise _lib.Ft8rxError("my_call / dx_call (a-priori decoding) is not supported together with weak=True")
     _lib.ap_patterns(my_call, dx_call)                   # raises, naming the argument, for a call that is not a standard one
     cfg.ap_my_call, cfg.ap_dx_call = my_call, dx_call
 
@@ -132,6 +156,13 @@ def frames_from_ragged(frames):
 AP_PATTERNS = (("NoAP", 0, ""), ("CQ", 0, "00000000000000000000000000100"), ("RR73", 58, "0111111001110101001"),
                ("73", 58, "0111111010010100001"), ("RRR", 58, "0111111010010010001"))
 # the ipass ladder (receiver.py:68-107): step -> (attempt, AP variants, arguments)
+def _weak_osd_max_hd(cfg):
+    """The OSD distance gate of weak mode: an explicit config.osd_max_hd wins over the setting's (ft8rx.hip: weak_config)."""
+    if cfg.osd_max_hd:
+        return int(cfg.osd_max_hd)
+    return _lib.WEAK_OSD_MAX_HD_DEFAULT if cfg.weak_osd_max_hd is None else int(cfg.weak_osd_max_hd)
+
+
 _LADDER = {0: ("good91+ldpc", range(5), (35, 5, False)), 2: ("good91", range(2), None), 3: ("ldpc", range(2), (35, 5, False)),
            4: ("ldpc", range(5), (90, 20, True)), 5: ("osd", range(5), None)}
 
@@ -263,7 +294,13 @@ class Candidate:
                 self.saved_llrs.append((f"{self.pat_name}_LDPC{max_its}", out))
         else:
             self.decode_notes = f"{self.source}_{self.pat_name}_OSD"
-            self.decode_result = D.osd_012(self.llr)
+            rx = self._rx
+            if rx is not None and rx.cfg.weak:                       # weak mode: every trial within the distance gate (ft8rx_set_weak)
+                with rx._hlock:
+                    ok, lo, hi, _ = rx._handle(1).osd(np.asarray(self.llr, np.float32)[None], 30, 2, 0, _weak_osd_max_hd(rx.cfg))
+                self.decode_result = D.unpack(D._msg(lo[0], hi[0])) if ok[0] else None
+            else:
+                self.decode_result = D.osd_012(self.llr)
 
     def _decode_ap_calls(self, rx):
         """ipass 7 (ft8rx_set_ap_calls) of this candidate through the single-vector entry points, as k_bp_ap / k_osd_ap /
@@ -304,8 +341,8 @@ class Candidate:
             self.llr0 = self.llr.copy()
         elif step == 1:                                              # _get_llr_fine (receiver.py:140-173)
             spec = rx.audio_in.get_cycle_spectrum()
-            with rx._hlock:
-                f = rx._handle(1).fine(spec[None], [0], [o["f0_idx"]], [o["h0_idx"]])
+            with rx._hlock:                                          # weak mode: the joint three-block scan (ft8rx_fine_weak)
+                f = rx._handle(1).fine(spec[None], [0], [o["f0_idx"]], [o["h0_idx"]], weak=rx.cfg.weak)
             tt, ft = int(f["ttweak"][0]), int(f["ftweak"][0])
             self.tweaks = " t:%+03d f:%+03d" % (tt, ft)
             self.n_sync_matches = int(f["nsync"][0])
@@ -579,6 +616,8 @@ class Receiver:
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall and self.cfg.msg_types:
             raise _lib.Ft8rxError("recall=True is not supported together with msg_types != 0")
+        if self.recall and self.cfg.weak:
+            raise _lib.Ft8rxError("recall=True is not supported together with weak=True")
         self.cfg.recall = self.recall
         self.search_h0_range = [self.cfg.h0_lo, self.cfg.h0_hi]
         self.search_start_hop = self.search_h0_range[1] + 43 * 4
@@ -713,7 +752,16 @@ class Receiver:
             h = self._handle(1)
             grid = np.ones((1, _lib.GRID_ROWS, h.grid_cols), np.float32)
             grid[0, 1:376, :width] = rows
-            if idx == list(range(*self.audio_in.search_f0_idx_range)):
+            if self.cfg.weak:
+                # weak mode: the three-block score (ft8rx_sync_scores_weak, k_sync3) over [min, max] of the list, then k_topk's steps
+                # on the host with the weak threshold -- keep above it in iteration order, sort by score stably, cut at max_cands
+                lo, hi = min(idx), max(idx) + 1
+                sc, h0 = h.sync_scores(grid, lo, hi, weak=True)
+                thr = np.float32(_lib.WEAK_SYNC_MIN_DEFAULT if self.cfg.weak_sync_min is None else self.cfg.weak_sync_min)
+                found = [(f, int(h0[0, f - lo]), float(sc[0, f - lo])) for f in idx if sc[0, f - lo] > thr]
+                found.sort(key=lambda c: -c[2])
+                found = found[:self.cfg.max_cands]
+            elif idx == list(range(*self.audio_in.search_f0_idx_range)):
                 # the configured range: threshold / stable sort / cut on the device (k_topk), as in the decode pipeline
                 f0, h0, sc, cnt = h.sync_search(grid)
                 found = [(int(f0[0, i]), int(h0[0, i]), float(sc[0, i])) for i in range(int(cnt[0]))]
@@ -731,7 +779,8 @@ class Receiver:
         for f0i, h0i, sci in found:
             origin = {"h0_idx": h0i, "f0_idx": f0i, "tsec": h0i / 25.0, "fHz": 3.125 * f0i, "score": sci,
                       "cyclestart_string": cyclestart_string, "band": self.band, "odd_even": odd_even}
-            cands.append(Candidate(origin, [r0 + h0i + 4, r0 + h0i + 4 * 71], rx=self, grid=grid))
+            cands.append(Candidate(origin, [r0 + h0i + 4, r0 + h0i + 4 * 71], rx=self, grid=grid,
+                                   llr_sd_min=-np.inf if self.cfg.weak else 5))      # weak mode: no sd stop at grid or fine
         self.candidates = cands
         return cands
 
@@ -812,6 +861,10 @@ class Receiver:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with msg_types != 0")
         if self._ap_on() and int(passes) > 1:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with my_call / dx_call (a-priori decoding)")
+        if use_recall and self.cfg.weak:
+            raise _lib.Ft8rxError("recall is not supported together with weak=True")
+        if self.cfg.weak and int(passes) > 1:
+            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with weak=True")
         local = research == "local"
         h = self._handle(B)
         if use_recall:
