@@ -41,6 +41,7 @@
  *     ft8rx_set_recall  ft8rx_fetch_recall  ft8rx_set_recall_gates  ft8rx_recall_hypotheses  ft8rx_recall_probe  ft8rx_package_batch_recall
  *                                                                                      (opt-in recall of stations heard 30 s earlier, ipass 8)
  *     ft8rx_set_weak                                                                   (opt-in weak-signal sync)
+ *     ft8rx_set_reports  ft8rx_fetch_reports  ft8rx_report_probe                       (opt-in measured SNR / frequency / time of each decode)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
@@ -373,6 +374,46 @@ int  ft8rx_recall_probe(ft8rx_handle* h, const float* sgrid, const ft8rx_recall_
 int  ft8rx_package_batch_recall(const ft8rx_record* records, const int32_t* counts, const ft8rx_event* events, const int32_t* event_counts,
                                 const ft8rx_record* recall, const int32_t* recall_counts, int n_frames, int max_cands, ft8rx_message* out,
                                 int max_msgs, int32_t* out_counts, int n_threads, ft8rx_hashes* table, int32_t* flags);
+/* Opt-in measured signal reports (extension).  A record's snr_grid / snr_fine and its position are the
+ * reference's quantities: the spread of the payload grid, and the search-grid position plus the tweaks.  With the setting on, every
+ * record that ends a batch's chain DECODED (ipass 0 .. 6, and 7 with ft8rx_set_ap_calls) is measured once more with its own 79 tones
+ * (word -> CRC-14 -> LDPC -> Gray map, Costas blocks) on the series of its slice, fb = 50 f0_idx + ftweak:
+ *   P(tau, delta) = sum_s |sum_{n<32} z[tau + 32 s + n] e^{-2 pi i n (tone_s + delta) / 32}|^2,  samples outside [0, 3200) = 0,
+ *   tau = tb - 28 .. tb + 12 (tb = 8 h0_idx + (h0_idx < 0) + ttweak, 5-ms samples), delta = -0.7, -0.6 .. +0.7 tone spacings;
+ *   the first maximum in tau-major order, moved on each axis where it is interior by the three-point parabola (on a border: no shift
+ *   and an EDGE flag);  f_hz = 0.0625 fb + 6.25 delta,  t_sec = 0.005 tau;
+ *   snr_db = 10 log10(max(on / off - 1, 1e-3) * 6.25 / 2500) at the peak's integer tau and the interpolated delta: on = the mean over
+ *   the symbols of the rectangular |DFT|^2 at the symbol's tone, off = median / ln 2 * 32 / sum w^2 of the Hann-weighted cells
+ *   (w[n] = 1/2 - 1/2 cos(2 pi (n + 1/2) / 32), all 8 tones) more than two tones from the tone of the symbol, of the one before and of
+ *   the one after; when on / off > 300, of those cells of the tones 0 .. 5 only (a strong signal leaks into the two cells next to the
+ *   edge of the slice).  dB in 2500 Hz, the convention of the workload generator.
+ * A record whose h0_idx lies outside [FT8RX_MIN_H0_FD, FT8RX_MAX_H0_FD] or whose slice fb - 150 .. fb + 849 leaves the spectrum gets
+ * FT8RX_RP_INVALID and NaN fields.  Records, counts and events do not change; off (the default), nothing is launched or allocated.
+ * Recall records (ipass 8) get no report.  Refused together with the packed output (ft8rx_set_packed_output). */
+#define FT8RX_RP_MEASURED 1u          /* the slot's record was DECODED and a report was made (flags = 0: no report) */
+#define FT8RX_RP_INVALID  2u          /* ... but it could not be measured: the fields are NaN */
+#define FT8RX_RP_EDGE_T   4u          /* the peak lies on the border of the tau window: t_sec is not interpolated */
+#define FT8RX_RP_EDGE_F   8u          /* the peak lies on the border of the delta window: f_hz is not interpolated */
+typedef struct {                      /* 24 bytes */
+    float    snr_db;                  /* dB in 2500 Hz */
+    float    f_hz;                    /* frequency of tone 0 */
+    float    t_sec;                   /* start of symbol 0 in the frame */
+    float    score;                   /* P at the peak */
+    uint32_t flags;                   /* FT8RX_RP_* */
+    uint32_t pad;                     /* 0 */
+} ft8rx_report;
+/* on != 0: batches enqueued afterwards end with the measurement step (the first call allocates the report arrays of both result
+ * slots); 0: back to the default.  Waits for the batches in flight. */
+int  ft8rx_set_reports(ft8rx_handle* h, int32_t on);
+/* the reports of the batch the last ft8rx_fetch_results / ft8rx_decode_batch handed out: reports [n_frames][cfg.max_cands], indexed like
+ * its records (all zero for a batch enqueued with the setting off). */
+int  ft8rx_fetch_reports(ft8rx_handle* h, int n_frames, ft8rx_report* reports);
+/* Test entry: the measurement step alone -- the batch's own launch sequence -- on caller-supplied cycle spectra spec
+ * [n_frames][FT8RX_SPEC_BINS] complex64 for n candidates (frame, f0_idx, h0_idx, ttweak, ftweak, word), at most the handle's candidate
+ * stride per frame -> reports [n].  Needs no ft8rx_set_reports. */
+int  ft8rx_report_probe(ft8rx_handle* h, const float* spec, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
+                        const int32_t* h0_idx, const int32_t* ttweak, const int32_t* ftweak, const uint64_t* msg_lo, const uint64_t* msg_hi,
+                        ft8rx_report* reports);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

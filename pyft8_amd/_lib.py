@@ -51,6 +51,8 @@ class Config(C.Structure):
     weak = False
     weak_sync_min = None
     weak_osd_max_hd = None
+    # opt-in measured reports (ft8rx_set_reports): a handle setting too, applied by Handle at create time
+    reports = False
 
 
 RECORD_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("score", "<f4"), ("grid_sd", "<f4"), ("fine_sd", "<f4"),
@@ -96,6 +98,10 @@ RECALL_CLASSES = ("repeat", "RRR", "RR73", "73", "report", "R-report")      # th
 RECALL_ENTRY_DTYPE = np.dtype([("msg_lo", "<u8"), ("msg_hi", "<u8"), ("f0_idx", "<i2"), ("h0_idx", "<i2"), ("ttweak", "i1"),
                                ("ftweak", "i1"), ("pad", "<u2")])
 assert RECALL_ENTRY_DTYPE.itemsize == 24
+# measured reports (ft8rx_set_reports; include/ft8rx.h ft8rx_report, FT8RX_RP_*)
+REPORT_DTYPE = np.dtype([("snr_db", "<f4"), ("f_hz", "<f4"), ("t_sec", "<f4"), ("score", "<f4"), ("flags", "<u4"), ("pad", "<u4")])
+assert REPORT_DTYPE.itemsize == 24
+RP_MEASURED, RP_INVALID, RP_EDGE_T, RP_EDGE_F = 1, 2, 4, 8
 
 _libs = {}
 _reject_log = [None]                  # set_reject_log's current path: applied to builds loaded later as well
@@ -276,6 +282,47 @@ class Handle:
             self.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
         if getattr(self.cfg, "weak", False):
             self.set_weak(True, self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd)
+        if getattr(self.cfg, "reports", False):
+            self.set_reports(True)
+
+    def set_reports(self, on):
+        """ft8rx_set_reports: measured SNR / frequency / start time of every DECODED record for the batches enqueued afterwards
+        (DESIGN.md section 14); fetch_reports hands them out."""
+        L = self._L
+        L.ft8rx_set_reports.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(L.ft8rx_set_reports(self._h, int(bool(on))), "ft8rx_set_reports")
+        self.cfg.reports = bool(on)
+
+    def fetch_reports(self, B):
+        """ft8rx_fetch_reports: reports [B, max_cands] of REPORT_DTYPE of the batch the last fetch / decode_batch handed out, indexed
+        like its records (flags 0 = no report: the slot did not decode, or the batch ran with the setting off)."""
+        rp = np.zeros((int(B), self.cfg.max_cands), REPORT_DTYPE)
+        L = self._L
+        L.ft8rx_fetch_reports.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(L.ft8rx_fetch_reports(self._h, int(B), rp.ctypes.data), "ft8rx_fetch_reports")
+        return rp
+
+    def report_probe(self, spec, frame, f0_idx, h0_idx, ttweak, ftweak, words):
+        """ft8rx_report_probe: the measurement step alone on cycle spectra spec [B, spec_bins] complex64 for n candidates (frame,
+        f0_idx, h0_idx, ttweak, ftweak, 77-bit word as a Python int) -> reports [n] (REPORT_DTYPE)."""
+        spec = np.ascontiguousarray(spec, np.complex64)
+        if spec.ndim == 1:
+            spec = spec[None]
+        if spec.ndim != 2 or spec.shape[1] != self.spec_bins:
+            raise Ft8rxError(f"report_probe: spec must be complex64 [n_frames, {self.spec_bins}]")
+        cols = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in (frame, f0_idx, h0_idx, ttweak, ftweak)]
+        n = len(cols[0])
+        words = [int(w) for w in words]
+        if n < 1 or any(len(c) != n for c in cols) or len(words) != n:
+            raise Ft8rxError("report_probe: one frame, f0_idx, h0_idx, ttweak, ftweak and word per candidate")
+        lo = np.array([w & ((1 << 64) - 1) for w in words], np.uint64)
+        hi = np.array([w >> 64 for w in words], np.uint64)
+        rp = np.zeros(n, REPORT_DTYPE)
+        L = self._L
+        L.ft8rx_report_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        self._chk(L.ft8rx_report_probe(self._h, spec.ctypes.data, int(spec.shape[0]), n, *[c.ctypes.data for c in cols], lo.ctypes.data,
+                                       hi.ctypes.data, rp.ctypes.data), "ft8rx_report_probe")
+        return rp
 
     def set_weak(self, on, sync_min=None, osd_max_hd=None):
         """ft8rx_set_weak: weak-signal sync for the batches enqueued afterwards (None = the library's defaults)."""

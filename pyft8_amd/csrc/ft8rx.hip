@@ -19,6 +19,8 @@
 //                                       blocks, a wide joint fine scan, no sd gates, an OSD distance gate
 //   k_fine (trip), k_recall_score       opt-in ipass 8 (ft8rx_set_recall): forced fine sync at the positions of messages heard 30 s
 //                                       earlier and a hypothesis test per entry, only for a batch with entries (kernels/recall.hpp)
+//   k_report_worklist, k_report         opt-in measured reports (ft8rx_set_reports): SNR, frequency and start time of every DECODED
+//                                       record from a matched correlation with its own 79 tones (kernels/report.hpp)
 // A batch is cut into chunks whose chains run on separate HIP streams -- free-running: chunk i of batch k+1 follows chunk i of batch k
 // on stream i, no per-batch fork / join; results land in one of two result slots and are copied to page-locked host buffers by a copy
 // stream while the next batch computes; the used part of the event log is packed by k_ev_scan / k_ev_compact straight into
@@ -53,6 +55,7 @@
 #include "kernels/osd.hpp"
 #include "kernels/ap_calls.hpp"
 #include "kernels/recall.hpp"
+#include "kernels/report.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -110,6 +113,10 @@ struct ft8rx_handle {
     int32_t* d_rc_trip; int32_t* d_rc_tout; float* d_rc_tsd; float* d_rc_sgrid; float* d_rc_llr;
     ft8rx_recall_entry* d_rc_ent[2]; int32_t* d_rc_cnt[2]; ft8rx_record* d_rc_rec[2];
     ft8rx_record* h_rc_rec[2]; int32_t* h_rc_cnt[2]; bool slot_recall[2];
+    // measured reports (ft8rx_set_reports, kernels/report.hpp; allocated at the first ft8rx_set_reports(h, 1)): the work list of the
+    // DECODED slots ([max_frames][stride] ids, a counter per chunk) and per result slot the reports, [max_frames][stride] on the device
+    bool reports, slot_reports[2];
+    int32_t* d_rp_items; int32_t* d_rp_count; ft8rx_report* d_rp[2]; ft8rx_report* h_rp[2];
     int sub_frames;                      // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
     hipStream_t sub[8];
     hipEvent_t ev_fork, ev_join[8];
@@ -340,6 +347,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
         if (h->h_pkhdr[k]) hipHostFree(h->h_pkhdr[k]);
         if (h->h_rc_rec[k]) hipHostFree(h->h_rc_rec[k]);
         if (h->h_rc_cnt[k]) hipHostFree(h->h_rc_cnt[k]);
+        if (h->h_rp[k]) hipHostFree(h->h_rp[k]);
     }
     delete h;
 }
@@ -363,6 +371,8 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     h->d_rc_src = nullptr; h->d_rc_srccnt = nullptr; h->d_rc_off = nullptr; h->d_rc_trip = nullptr; h->d_rc_tout = nullptr; h->d_rc_tsd = nullptr;
     h->d_rc_sgrid = nullptr; h->d_rc_llr = nullptr;
     for (int k = 0; k < 2; k++) { h->d_rc_ent[k] = nullptr; h->d_rc_cnt[k] = nullptr; h->d_rc_rec[k] = nullptr; h->h_rc_rec[k] = nullptr; h->h_rc_cnt[k] = nullptr; h->slot_recall[k] = false; }
+    h->reports = false; h->d_rp_items = nullptr; h->d_rp_count = nullptr;
+    for (int k = 0; k < 2; k++) { h->slot_reports[k] = false; h->d_rp[k] = nullptr; h->h_rp[k] = nullptr; }
     h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->weak = false; h->weak_sync_min = FT8RX_WEAK_SYNC_MIN_DEFAULT;
     h->weak_osd_max_hd = FT8RX_WEAK_OSD_MAX_HD_DEFAULT; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
     h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
@@ -621,6 +631,18 @@ static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_rec
     k_select_ap<<<(B * S + 255) / 256, 256, 0, s>>>(rec, attO, apc, cl);
 }
 
+// the measurement step of B frames (kernels/report.hpp): the DECODED slots of rec -> items / *count, their reports -> rep (indexed like
+// rec); the batch chain and ft8rx_report_probe launch the same
+static void launch_reports(ft8rx_handle* h, int B, const cpx* spec, const ft8rx_record* rec, const int32_t* ncand, int32_t* items,
+                           int32_t* count, ft8rx_report* rep, hipStream_t s) {
+    const ft8rx_config& c = h->cfg;
+    const int sh = cand_shift(c); const size_t S = (size_t)1 << sh;
+    hipMemsetAsync(count, 0, sizeof(int32_t), s);
+    const WorkList wl = {items, count};
+    k_report_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl, rep);
+    k_report<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, rep, h->T, sh, wl);
+}
+
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
     const bool weak = h->weak;                                     // the setting this batch was enqueued with
     const ft8rx_config cw = weak ? weak_config(h) : h->cfg;
@@ -738,6 +760,12 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
                                             h->rc_max_hd, h->rc_min_gap, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
         }
     }
+    if (h->slot_reports[slot]) {
+        // measured reports (ft8rx_set_reports, kernels/report.hpp), after the last ladder step: the records are final, and the cycle
+        // spectrum still lies in this chunk's grid region (as recall relies on)
+        STAGE("report");
+        launch_reports(h, B, spec, rec, ncand, h->d_rp_items + FS, h->d_rp_count + chunk, h->d_rp[slot] + FS, s);
+    }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
 }
@@ -772,6 +800,7 @@ static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* 
     if (h->rc_armed && B != h->rc_frames) { set_err(h, "recall entries were set for %d frames, the batch has %d", h->rc_frames, B); return -1; }
     h->slot_recall[slot] = h->rc_armed;          // ft8rx_set_recall: consumed by this batch
     h->rc_armed = false;
+    h->slot_reports[slot] = h->reports;          // ft8rx_set_reports: the setting this batch is enqueued with
     int16_t* stage = h->d_audio;
     hipStream_t cs = h->copy_s;
     if (pipelined) {
@@ -915,6 +944,9 @@ static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* 
         HIPCHK(h, hipMemcpyAsync(h->h_rc_cnt[slot], h->d_rc_cnt[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
         HIPCHK(h, hipMemcpyAsync(h->h_rc_rec[slot], h->d_rc_rec[slot], sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)B, hipMemcpyDeviceToHost, h->copy_s));
     }
+    if (h->slot_reports[slot])
+        HIPCHK(h, hipMemcpy2DAsync(h->h_rp[slot], sizeof(ft8rx_report) * mc, h->d_rp[slot], sizeof(ft8rx_report) << cand_shift(h->cfg),
+                                   sizeof(ft8rx_report) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
     HIPCHK(h, hipEventRecord(h->ev_done[slot], h->copy_s));
     h->slot_B[slot] = B; h->last_slot = slot; h->slot_enq ^= 1; h->inflight++;
     return 0;
@@ -1147,6 +1179,38 @@ int ft8rx_fetch_recall(ft8rx_handle* h, int n_frames, ft8rx_record* records, int
     return 0;
 }
 
+int ft8rx_set_reports(ft8rx_handle* h, int32_t on) {
+    if (!h) return -1;
+    ENTER(h);                                   // batches in flight were enqueued under the previous setting
+    if (!on) { h->reports = false; return 0; }
+    if (h->pk_buf[0]) { set_err(h, "ft8rx_set_reports: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
+    if (!h->d_rp_items) {
+        const size_t B = (size_t)h->max_frames, N = B << cand_shift(h->cfg);
+        int rc = 0;
+        rc |= dalloc(h, &h->d_rp_items, N); rc |= dalloc(h, &h->d_rp_count, (size_t)16);
+        for (int k = 0; k < 2 && !rc; k++) {
+            rc |= dalloc(h, &h->d_rp[k], N);
+            if (!rc && hipHostMalloc((void**)&h->h_rp[k], sizeof(ft8rx_report) * B * h->cfg.max_cands, hipHostMallocDefault) != hipSuccess) {
+                set_err(h, "ft8rx_set_reports: page-locked result buffers could not be allocated"); rc = -2; }
+        }
+        if (rc) { h->d_rp_items = nullptr; return -2; }
+    }
+    h->reports = true;
+    return 0;
+}
+
+int ft8rx_fetch_reports(ft8rx_handle* h, int n_frames, ft8rx_report* reports) {
+    if (!h || !reports) return -1;
+    const int slot = h->fetched_slot;
+    if (slot < 0) { set_err(h, "ft8rx_fetch_reports: no batch has been fetched"); return -1; }
+    if (n_frames < 1 || n_frames > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_reports: %d frames requested, the batch had %d", n_frames, h->slot_B[slot]); return -1; }
+    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
+    const size_t bytes = sizeof(ft8rx_report) * (size_t)n_frames * h->cfg.max_cands;
+    if (!h->slot_reports[slot]) memset(reports, 0, bytes);
+    else memcpy(reports, h->h_rp[slot], bytes);
+    return 0;
+}
+
 int ft8rx_set_recall_gates(ft8rx_handle* h, int32_t max_hd, int32_t min_gap) {
     if (!h) return -1;
     if (max_hd < 1 || max_hd > 174 || min_gap < 0 || min_gap > 174) { set_err(h, "ft8rx_set_recall_gates: max_hd %d / min_gap %d outside [1, 174] / [0, 174]", max_hd, min_gap); return -1; }
@@ -1229,6 +1293,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
     if (h->rc_armed) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_recall entries are pending"); return -1; }
     if (h->weak) { set_err(h, "ft8rx_set_packed_output: not supported together with ft8rx_set_weak"); return -1; }
+    if (h->reports) { set_err(h, "ft8rx_set_packed_output: not supported together with ft8rx_set_reports"); return -1; }
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -1543,6 +1608,43 @@ int ft8rx_recall_probe(ft8rx_handle* h, const float* sgrid, const ft8rx_recall_e
     k_recall_score<<<n, 64, 0, h->stream>>>(d_sg, d_tout, d_trip, d_off, 0, d_ent, nullptr, nullptr, 0, h->rc_max_hd, h->rc_min_gap, d_rec);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy2D(records, sizeof(ft8rx_record), d_rec, sizeof(ft8rx_record) * FT8RX_RECALL_MAX, sizeof(ft8rx_record), n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the measurement step alone (launch_reports, as the batch chain runs it) on caller-supplied spectra: the candidates of frame f take the
+// slots 0 .. of that frame's records, each DECODED with the given position, tweaks and word
+int ft8rx_report_probe(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                       const int32_t* ttweak, const int32_t* ftweak, const uint64_t* msg_lo, const uint64_t* msg_hi, ft8rx_report* reports) {
+    if (!h || !spec || !frame || !f0_idx || !h0_idx || !ttweak || !ftweak || !msg_lo || !msg_hi || !reports || B < 1 || B > h->max_frames || n < 1) {
+        if (h) set_err(h, "ft8rx_report_probe: bad arguments (1 <= n_frames <= max_frames, n >= 1)"); return -1; }
+    const int sh = cand_shift(h->cfg); const size_t S = (size_t)1 << sh;
+    std::vector<ft8rx_record> r0((size_t)B * S);
+    memset(r0.data(), 0, sizeof(ft8rx_record) * r0.size());
+    std::vector<int32_t> nc(B, 0), where(n);
+    for (int i = 0; i < n; i++) {
+        if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < -32768 || f0_idx[i] > 32767 || h0_idx[i] < -32768 || h0_idx[i] > 32767 ||
+            ttweak[i] < -128 || ttweak[i] > 127 || ftweak[i] < -128 || ftweak[i] > 127) {
+            set_err(h, "ft8rx_report_probe: candidate %d (frame %d, f0 %d, h0 %d, tweaks %d / %d) is out of range", i, frame[i], f0_idx[i], h0_idx[i], ttweak[i], ftweak[i]); return -1; }
+        if (nc[frame[i]] >= (int)S) { set_err(h, "ft8rx_report_probe: more than %zu candidates in frame %d", S, frame[i]); return -1; }
+        where[i] = (int32_t)((size_t)frame[i] * S + nc[frame[i]]++);
+        ft8rx_record& r = r0[where[i]];
+        r.msg_lo = msg_lo[i]; r.msg_hi = msg_hi[i]; r.f0_idx = (int16_t)f0_idx[i]; r.h0_idx = (int16_t)h0_idx[i];
+        r.ttweak = (int8_t)ttweak[i]; r.ftweak = (int8_t)ftweak[i]; r.status = FT8RX_ST_DECODED;
+    }
+    ENTER(h);
+    HIPCHK(h, hipMemcpy(h->d_spec, spec, sizeof(cpx) * (size_t)B * FT8RX_SPEC_BINS, hipMemcpyHostToDevice));
+    Scratch Sc{h};
+    ft8rx_record* d_rec = Sc.put(r0.data(), r0.size()); NEED(d_rec);
+    int32_t* d_nc = Sc.put(nc.data(), nc.size()); NEED(d_nc);
+    int32_t* d_items = Sc.get<int32_t>((size_t)B * S); NEED(d_items);
+    int32_t* d_count = Sc.get<int32_t>(1); NEED(d_count);
+    ft8rx_report* d_rep = Sc.get<ft8rx_report>((size_t)B * S); NEED(d_rep);
+    launch_reports(h, B, h->d_spec, d_rec, d_nc, d_items, d_count, d_rep, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<ft8rx_report> out((size_t)B * S);
+    HIPCHK(h, hipMemcpy(out.data(), d_rep, sizeof(ft8rx_report) * out.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) reports[i] = out[where[i]];
     return 0;
 }
 

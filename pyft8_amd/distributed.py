@@ -191,6 +191,9 @@ class PackedGather:
             raise _lib.Ft8rxError("PackedGather: recall is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
         if getattr(handle.cfg, "weak", False):
             raise _lib.Ft8rxError("PackedGather: weak=True is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
+        if getattr(handle.cfg, "reports", False):
+            raise _lib.Ft8rxError("PackedGather: reports=True is not supported on the packed multi-GPU path (the packed output carries no "
+                                  "reports); decode with Receiver.decode_frames instead")
         self._lib, self.h, self.B, self.dst, self.group, self.repeat = _lib, handle, int(n_frames), dst, group, max(1, int(repeat))
         self.depth = max(2, int(depth))
         self.active = dist.is_initialized() and (dist.get_world_size(group) > 1 or force)

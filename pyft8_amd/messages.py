@@ -385,10 +385,20 @@ def package_frame(rec, count, events, n_events, cyclestart_string="", band=None,
     return out
 
 
-def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None, ap=False, recall=False):
+def report_dict(rp):
+    """One ft8rx_report (_lib.REPORT_DTYPE) -> {"snr": dB in 2500 Hz, "fHz", "tsec"}, or None for a slot without a valid report."""
+    fl = int(rp["flags"])
+    if not fl & 1 or fl & 2:
+        return None
+    return {"snr": float(rp["snr_db"]), "fHz": float(rp["f_hz"]), "tsec": float(rp["t_sec"])}
+
+
+def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_message=None, ap=False, recall=False, reports=None):
     """Rows of the native packager (ft8rx_package_batch, _lib.MESSAGE_DTYPE) -> the reference's message dicts
     (receiver.py:57-65).  Same formatting as package_frame above.  recall = True (ft8rx_package_batch_recall rows): every dict
-    gains "recall", True for the ipass-8 messages."""
+    gains "recall", True for the ipass-8 messages.  reports (the frame's row of Handle.fetch_reports; ft8rx_set_reports): every dict
+    gains "report", the measured {"snr", "fHz", "tsec"} of the message's candidate -- None where there is none (an invalid report, a
+    recall message); the reference's keys stay as they are."""
     out = []
     now = time.time()
     rows = msgs[:min(int(count), len(msgs))]
@@ -398,7 +408,10 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
     cols = [rows[k].tolist() for k in ("f", "h0_idx", "f0_idx", "ttweak", "ftweak", "snr", "ipass", "method", "ap", "fine")]
     ext = "i3" in rows.dtype.names                   # rows of ft8rx_package_batch_ext (_lib.MESSAGE_EXT_DTYPE): the opt-in types
     types = list(zip(rows["i3"].tolist(), rows["n3"].tolist())) if ext else [None] * len(rows)
-    for f3, h0, f0, tt, ft, sn, ipass, method, ap_, fn, ty in zip(*cols, types):
+    cands = rows["cand"].tolist()
+    if reports is not None:                          # whole columns again: one lookup per message below
+        r_fl, r_snr, r_f, r_t = (reports[k].tolist() for k in ("flags", "snr_db", "f_hz", "t_sec"))
+    for (f3, h0, f0, tt, ft, sn, ipass, method, ap_, fn, ty), ci in zip(zip(*cols, types), cands):
         text = tuple(x.decode() for x in f3)
         tsec = h0 / 25.0
         fHz = 3.125 * f0
@@ -418,6 +431,9 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, odd_even=0, on_m
             d["ap"] = ap_name(int(ap_)) if ipass != 8 else AP_NAMES[0]
         if recall:
             d["recall"] = ipass == 8
+        if reports is not None:
+            ok = ipass != 8 and 0 <= ci < len(r_fl) and r_fl[ci] & 3 == 1            # measured and valid (report_dict's rule)
+            d["report"] = {"snr": r_snr[ci], "fHz": r_f[ci], "tsec": r_t[ci]} if ok else None
         out.append(d)
         if on_message is not None:
             on_message(d)

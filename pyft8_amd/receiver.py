@@ -246,6 +246,7 @@ class Candidate:
         self.n_sync_matches = 100
         self.decode_notes = ""
         self.snr = 0
+        self._tt = self._ft = 0              # the fine tweaks as numbers (0 until the fine stage has accepted the candidate)
 
     # ---- receiver.py:51-66
     def check_and_package(self, duplicate_filter):
@@ -260,9 +261,27 @@ class Candidate:
                        "all_txt_format": f"{o['cyclestart_string']} {snr} {(o['tsec'] - 0.6):4.1f} {o['fHz']:4.0f} ~ {self.msg_text}",
                        "cyclestart_string": o["cyclestart_string"], "decode_completed": self._rx.time_source() if self._rx else _time.time(),
                        "tweaks": self.tweaks, "decode_notes": self.decode_notes + self.tweaks}
+            if self._rx is not None and self._rx.cfg.reports:
+                message["report"] = self._report()
             if self.on_message is not None:
                 self.on_message(message)
         self.decode_result = "stop"
+
+    def _report(self):
+        """The measured report of this decode (reports=True) through ft8rx_report_probe -- the batch's measurement step on this
+        cycle's spectrum: the word is packed back from the text (the a-priori step keeps its own), None where that is not possible."""
+        from . import synth
+        rx, o = self._rx, self.origin
+        word = getattr(self, "ap_result", None) and self.ap_result["word"]
+        if not word:
+            try:
+                word = synth.pack77(*self.decode_result)
+            except (ValueError, TypeError, IndexError, KeyError):
+                return None
+        spec = rx.audio_in.get_cycle_spectrum()
+        with rx._hlock:
+            rp = rx._handle(1).report_probe(spec[None], [0], [o["f0_idx"]], [o["h0_idx"]], [self._tt], [self._ft], [word])
+        return _m.report_dict(rp[0])
 
     def _take_llr(self, llr, sd, snr, source):                       # the tail of _dB_to_llr (receiver.py:208-222)
         self.llr, self.llr_sd, self.snr, self.source = np.array(llr, np.float32), float(sd), int(snr), source
@@ -348,6 +367,7 @@ class Candidate:
             self.n_sync_matches = int(f["nsync"][0])
             if self.n_sync_matches > 6:
                 o.update({"tsec": float(o["tsec"] + tt / 200), "fHz": float(o["fHz"] + ft / 16)})
+                self._tt, self._ft = tt, ft
                 self._take_llr(f["llr"][0], f["sd"][0], f["snr"][0], "fine")
             else:
                 self.source = "fine"
@@ -612,6 +632,8 @@ class Receiver:
         self.candidates = []
         # recall (ipass 8): poll feeds each complete cycle the messages of the cycle 30 s before it
         self.recall = bool(extension_knobs.pop("recall", False))
+        # measured reports: every message dict gains "report", the measured SNR / frequency / start time
+        self.reports = bool(extension_knobs.pop("reports", False))
         self._recall_hist = {}                                # cycle start -> complete-frame message dicts (recall = True)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall and self.cfg.msg_types:
@@ -619,6 +641,7 @@ class Receiver:
         if self.recall and self.cfg.weak:
             raise _lib.Ft8rxError("recall=True is not supported together with weak=True")
         self.cfg.recall = self.recall
+        self.cfg.reports = self.reports
         self.search_h0_range = [self.cfg.h0_lo, self.cfg.h0_hi]
         self.search_start_hop = self.search_h0_range[1] + 43 * 4
         self.device = device
@@ -865,11 +888,15 @@ class Receiver:
             raise _lib.Ft8rxError("recall is not supported together with weak=True")
         if self.cfg.weak and int(passes) > 1:
             raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with weak=True")
+        if self.reports and int(passes) > 1:
+            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with reports=True: the later passes decode a residual "
+                                  "whose spectrum the measurement does not have")
         local = research == "local"
         h = self._handle(B)
         if use_recall:
             h.set_recall(self._recall_entries(recall if recall is not None else [None] * B))
         rec, cnt, ev, evc = h.decode_batch(audio)
+        rp = h.fetch_reports(B) if self.reports else None
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
         if use_recall:
             rrec, rcnt = h.fetch_recall(B)
@@ -878,7 +905,7 @@ class Receiver:
             msgs, mcnt = self._package(rec, cnt, ev, evc)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
         out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message,
-                                ap=self._ap_on(), recall=use_recall) for f in range(B)]
+                                ap=self._ap_on(), recall=use_recall, reports=None if rp is None else rp[f]) for f in range(B)]
         seen = [{" ".join(d["msg_tuple"]) for d in out[f]} for f in range(B)]
         for _ in range(1, int(passes)):
             sigs = self._subtraction_list(msgs, mcnt, rec, subtract_min_snr)
@@ -953,6 +980,8 @@ class Receiver:
                                   "use decode_frames")
         if self.recall:
             raise _lib.Ft8rxError("decode_frames_arrays is not supported with recall=True: use decode_frames(..., recall=)")
+        if self.reports:
+            raise _lib.Ft8rxError("decode_frames_arrays returns _lib.MESSAGE_DTYPE rows, which have no place for reports=True: use decode_frames")
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)
@@ -1005,12 +1034,13 @@ class Receiver:
                 rec, cnt, ev, evc = h.decode_batch(frame[None])
                 if prev is not None:
                     rrec, rcnt = h.fetch_recall(1)
+                rp = h.fetch_reports(1) if self.reports else None
             if prev is not None:
                 msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, n_threads=1, table=self.call_hashes)
             else:
                 msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
             dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
-                                     ap=self._ap_on(), recall=self.recall)
+                                     ap=self._ap_on(), recall=self.recall, reports=None if rp is None else rp[0])
             if self.recall and not early:
                 self._recall_hist[t0] = dicts
                 for k in [k for k in self._recall_hist if k < t0 - 2 * T_CYC]:
@@ -1041,5 +1071,5 @@ def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=
     """decode_frames(audio_i16[B,180000], **receiver_kwargs) -> list[list[message dict]]  (SURVEY.md 8b); passes > 1 adds the
     subtraction passes of Receiver.decode_frames; recall = per frame the message dicts decoded 30 s earlier (Receiver.decode_frames)."""
     audio = _as_frames(audio_i16)
-    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, **receiver_kwargs)
+    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, **receiver_kwargs)       # reports=True: "report" in every dict
     return rx.decode_frames(audio, passes=passes, research=research, recall=recall)
