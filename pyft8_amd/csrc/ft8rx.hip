@@ -279,6 +279,14 @@ static int quiesce(ft8rx_handle* h, bool next_is_batch = false) {
 }
 #define ENTER(h) do { HIPCHK(h, hipSetDevice((h)->device)); { const int _q = quiesce(h); if (_q) return _q; } } while (0)
 
+// a ladder kernel, or -- msg_types != 0 -- its _ext twin: the same kernel instantiated with the extended validity predicate
+// (ft8_valid77_ext), which takes the type mask as one more argument; at 0 the code is unchanged
+template <class K, class KX, class... A>
+static void launch_mt(K k, KX kx, unsigned mt, int grid, hipStream_t s, A... a) {
+    if (!mt) k<<<grid, 64, 0, s>>>(a...);
+    else kx<<<grid, 64, 0, s>>>(a..., mt);
+}
+
 extern "C" {
 
 int ft8rx_default_config(ft8rx_config* c) {
@@ -584,25 +592,18 @@ int ft8rx_get_stage_times(ft8rx_handle* h, int* n, const char** names, float* ms
 // chip four times over, never more than there can be items
 static int ladder_grid(int max_items) { const int cap = LADDER_GRID_CAP; return max_items < cap ? max_items : cap; }
 
-// the sync search of frames [.., B) over the configured h0 range, in windows of SYNC_WIN offsets (one launch for any range up to 14 s)
-static void launch_sync(const float* grid, float* bs, int32_t* bh, const ft8rx_config& c, int B, hipStream_t s) {
+// the sync search of frames [.., B) over the configured h0 range, in windows of SYNC_WIN offsets (one launch for any range up to 14 s):
+// the first window's kernel sets the best score per f0, the later windows' one accumulates into it.  Weak mode (ft8rx_set_weak): the
+// three-block score, in windows of SYNC3_WIN offsets
+static void launch_sync(const float* grid, float* bs, int32_t* bh, const ft8rx_config& c, int B, hipStream_t s, bool weak) {
+    const auto first = weak ? k_sync3 : k_sync, acc = weak ? k_sync3_acc : k_sync_acc;
+    const int win = weak ? SYNC3_WIN : SYNC_WIN;
+    const size_t lds = weak ? 0 : sync_lds_bytes(c);
     const int ntile = (c.f0_hi - c.f0_lo + 15) / 16;
-    for (int lo = c.h0_lo; lo < c.h0_hi; lo += SYNC_WIN) {
+    for (int lo = c.h0_lo; lo < c.h0_hi; lo += win) {
         ft8rx_config w = c;
-        w.h0_lo = lo; w.h0_hi = lo + SYNC_WIN < c.h0_hi ? lo + SYNC_WIN : c.h0_hi;
-        if (lo == c.h0_lo) k_sync<<<dim3(ntile, B), 256, sync_lds_bytes(c), s>>>(grid, bs, bh, w);
-        else k_sync_acc<<<dim3(ntile, B), 256, sync_lds_bytes(c), s>>>(grid, bs, bh, w);
-    }
-}
-
-// weak mode (ft8rx_set_weak): the three-block score over the configured h0 range, in windows of SYNC3_WIN offsets
-static void launch_sync3(const float* grid, float* bs, int32_t* bh, const ft8rx_config& c, int B, hipStream_t s) {
-    const int ntile = (c.f0_hi - c.f0_lo + 15) / 16;
-    for (int lo = c.h0_lo; lo < c.h0_hi; lo += SYNC3_WIN) {
-        ft8rx_config w = c;
-        w.h0_lo = lo; w.h0_hi = lo + SYNC3_WIN < c.h0_hi ? lo + SYNC3_WIN : c.h0_hi;
-        if (lo == c.h0_lo) k_sync3<<<dim3(ntile, B), 256, 0, s>>>(grid, bs, bh, w);
-        else k_sync3_acc<<<dim3(ntile, B), 256, 0, s>>>(grid, bs, bh, w);
+        w.h0_lo = lo; w.h0_hi = lo + win < c.h0_hi ? lo + win : c.h0_hi;
+        (lo == c.h0_lo ? first : acc)<<<dim3(ntile, B), 256, lds, s>>>(grid, bs, bh, w);
     }
 }
 // The configuration the existing kernels see in weak mode: the weak sync threshold (k_topk), no sd stop at grid or fine
@@ -613,6 +614,15 @@ static ft8rx_config weak_config(const ft8rx_handle* h) {
     w.llr_sd_min = -INFINITY;
     if (!w.osd_max_hd) w.osd_max_hd = h->weak_osd_max_hd;
     return w;
+}
+// the fine sync of n_blocks work-list blocks or test triples: weak mode's kernel, or k_fine plus -- need_td -- k_fine_td for the
+// candidates beyond the frequency-domain h0 range (-6.1 .. +8.3 s) that k_fine leaves out
+static void launch_fine(ft8rx_handle* h, const ft8rx_config& cfg, bool weak, int n_blocks, hipStream_t s, const cpx* spec, ft8rx_record* rec,
+                        const int32_t* ncand, float* llr, const int32_t* trip, int32_t* t_out, float* t_sd, float* t_sgrid, WorkList work,
+                        bool need_td) {
+    if (weak) { k_fine_weak<<<n_blocks, FINE_NT, 0, s>>>(spec, rec, ncand, llr, h->T, cfg, trip, t_out, t_sd, t_sgrid, work); return; }
+    ft8rx_ilp_fine(n_blocks, s, spec, rec, ncand, llr, h->T, cfg, trip, t_out, t_sd, t_sgrid, work);
+    if (need_td) k_fine_td<<<n_blocks, FINE_NT, 0, s>>>(spec, rec, ncand, llr, h->T, cfg, trip, t_out, t_sd, t_sgrid, work);
 }
 
 // ipass 7 of B frames (kernels/ap_calls.hpp): candidate list in cand_items (B * stride entries), OSD list in osd_items (B * stride * 3),
@@ -664,69 +674,53 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     STAGE("spectrogram");
     ft8rx_ilp_spectrogram(B, s, audio, grid, h->T);
     STAGE("sync");
-    if (!weak) launch_sync(grid, bs, bh, c, B, s);
-    else launch_sync3(grid, bs, bh, c, B, s);
+    launch_sync(grid, bs, bh, c, B, s, weak);
     STAGE("topk");
     k_topk<<<B, 1024, 0, s>>>(bs, bh, rec, ncand, c, evc, wc, h->use_mask ? h->d_colmask + F * NF0MAX : nullptr);
     STAGE("grid_llr");
-    // msg_types != 0: the same kernels instantiated with the extended validity predicate (ft8_valid77_ext); at 0 the code is unchanged
-    const unsigned mt = (unsigned)h->msg_types;
-    if (!mt) k_grid_llr<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
-    else k_grid_llr_ext<<<XCD_GRID(B, c.max_cands), 64, 0, s>>>(grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B, mt);
+    const unsigned mt = (unsigned)h->msg_types;                    // (launch_mt)
+    launch_mt(k_grid_llr, k_grid_llr_ext, mt, XCD_GRID(B, c.max_cands), s, grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
     k_worklist_att<<<(B * S * 5 + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_BP0]);
     STAGE("bp_grid");
-    if (!mt) k_bp<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
-    else k_bp_ext<<<ladder_grid(B * c.max_cands * 5), 64, 0, s>>>(0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5, mt);
+    launch_mt(k_bp, k_bp_ext, mt, ladder_grid(B * c.max_cands * 5), s, 0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
     STAGE("select0");
     k_select0<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_FINE]);
     STAGE("cycle_fft");
     k_cyc_a<<<dim3(40, B), 256, 0, s>>>(audio, A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, s>>>(A, spec, h->T);
     STAGE("fine");
-    if (weak)
-        k_fine_weak<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
-    else {
-        ft8rx_ilp_fine(ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
-        if (c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1)      // a search_time_range beyond -6.1 .. +8.3 s: the candidates k_fine leaves out
-            k_fine_td<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, ncand, llr0, h->T, c, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE]);
-    }
+    launch_fine(h, c, weak, ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE],
+                c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1);      // a search_time_range beyond -6.1 .. +8.3 s
     k_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl[WL_BP1]);
     STAGE("bp_fine");
     // fine-stage BP: in ladder order (three launches; decided candidates drop out), or -- ft8rx_set_ladder_mode(h, 1), for small
     // batches where latency matters more than work -- all five variants in one launch: one dependent BP instead of three, same
     // records and messages (the event log then also holds entries of attempts the ladder would not have reached)
+    const auto bp_fine = [&](int n_variants, const WorkList& work, int v0) {      // variants v0 .. v0 + n_variants - 1 of the items of `work`
+        launch_mt(k_bp, k_bp_ext, mt, B * c.max_cands * n_variants, s, 1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b,
+                  work, v0, n_variants);
+    };
     if (h->ladder_mode == 0) {
-        if (!mt) k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1);
-        else k_bp_ext<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 1, mt);
+        bp_fine(1, wl[WL_BP1], 0);
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(0, rec, ncand, attG, attB, B, c, wl[WL_BP1B]);
-        if (!mt) k_bp<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1);
-        else k_bp_ext<<<B * c.max_cands, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1B], 1, 1, mt);
+        bp_fine(1, wl[WL_BP1B], 1);
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(1, rec, ncand, attG, attB, B, c, wl[WL_BP1C]);
-        if (!mt) k_bp<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3);
-        else k_bp_ext<<<B * c.max_cands * 3, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1C], 2, 3, mt);
+        bp_fine(3, wl[WL_BP1C], 2);
         STAGE("select1");
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(2, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     } else {
-        if (!mt) k_bp<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5);
-        else k_bp_ext<<<B * c.max_cands * 5, 64, 0, s>>>(1, llr0, rec, ncand, attG, attB, saved, ev, evc, c, c.bp_nc0_b, c.bp_iters_b, wl[WL_BP1], 0, 5, mt);
+        bp_fine(5, wl[WL_BP1], 0);
         STAGE("select1");
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     }
     STAGE("osd");
     const bool osd_wide = osd_nflip(c.osd_single, c.osd_triple) > OSD_FLIPS_A;
     const int nflip = osd_nflip(c.osd_single, c.osd_triple);
-    if (!mt) {
-        (osd_wide ? k_osd_wide : k_osd)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
-            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
-        // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
-        (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, s>>>(
-            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN]);
-    } else {
-        (osd_wide ? k_osd_wide_ext : k_osd_ext)<<<ladder_grid(B * c.max_cands * 10), 64, 0, s>>>(
-            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN], mt);
-        (osd_wide ? k_osd_nan_wide_ext : k_osd_nan_ext)<<<OSD_NAN_GRID, 64, 0, s>>>(
-            0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN], mt);
-    }
+    launch_mt(osd_wide ? k_osd_wide : k_osd, osd_wide ? k_osd_wide_ext : k_osd_ext, mt, ladder_grid(B * c.max_cands * 10), s,
+              0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
+    // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
+    launch_mt(osd_wide ? k_osd_nan_wide : k_osd_nan, osd_wide ? k_osd_nan_wide_ext : k_osd_nan_ext, mt, OSD_NAN_GRID, s,
+              0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN]);
     STAGE("select2");
     k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
     if (h->ap.np) {
@@ -751,11 +745,8 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
         if (n > 0) {
             k_recall_trip<<<B, FT8RX_RECALL_MAX, 0, s>>>(ent, rcnt, h->d_rc_off + F, h->d_rc_trip);
             const size_t b = (size_t)base;
-            ft8rx_ilp_fine(n, s, spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->T, c, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
-                           h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr});
-            if (h->rc_td)          // an entry beyond the frequency-domain h0 range (-6.1 .. +8.3 s): k_fine left it to this one
-                k_fine_td<<<n, FINE_NT, 0, s>>>(spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->T, c, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
-                                                h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr});
+            launch_fine(h, c, false, n, s, spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
+                        h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr}, h->rc_td);     // rc_td: an entry beyond k_fine's h0 range
             k_recall_score<<<n, 64, 0, s>>>(h->d_rc_sgrid, h->d_rc_tout, h->d_rc_trip, h->d_rc_off + F, base, ent, rec, ncand, sh,
                                             h->rc_max_hd, h->rc_min_gap, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
         }
@@ -1413,7 +1404,7 @@ int ft8rx_sync_search(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx
     const ft8rx_config& c = h->cfg;
     HIPCHK(h, hipMemcpy(h->d_grid, grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyHostToDevice));
     const int ntile = (c.f0_hi - c.f0_lo + 15) / 16;
-    launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
+    launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream, false);
     k_topk<<<B, 1024, 0, h->stream>>>(h->d_best_score, h->d_best_h0, h->d_rec, h->d_ncand, c, nullptr, nullptr, nullptr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t S = (size_t)1 << cand_shift(c);
@@ -1439,8 +1430,7 @@ static int sync_scores(ft8rx_handle* h, const float* grid, int B, int f0_lo, int
     c.f0_lo = f0_lo; c.f0_hi = f0_hi;
     HIPCHK(h, hipMemcpy(h->d_grid, grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyHostToDevice));
     const int nf0 = f0_hi - f0_lo;
-    if (weak) launch_sync3(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
-    else launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream);
+    launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream, weak);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpy2DAsync(score, sizeof(float) * nf0, h->d_best_score, sizeof(float) * NF0MAX, sizeof(float) * nf0, B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpy2DAsync(h0_idx, sizeof(int32_t) * nf0, h->d_best_h0, sizeof(int32_t) * NF0MAX, sizeof(int32_t) * nf0, B, hipMemcpyDeviceToHost, h->stream));
@@ -1455,13 +1445,19 @@ int ft8rx_sync_scores_weak(ft8rx_handle* h, const float* grid, int B, int f0_lo,
     return sync_scores(h, grid, B, f0_lo, f0_hi, score, h0_idx, true);
 }
 
+// the (frame, f0, h0) triples of a stage entry, interleaved as the kernels' test entries read them
+static std::vector<int32_t> pack_triples(int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx) {
+    std::vector<int32_t> trip(3 * (size_t)n);
+    for (int i = 0; i < n; i++) { trip[3 * i] = frame[i]; trip[3 * i + 1] = f0_idx[i]; trip[3 * i + 2] = h0_idx[i]; }
+    return trip;
+}
+
 int ft8rx_llr_grid(ft8rx_handle* h, const float* grid, int B, int n, const int32_t* frame, const int32_t* f0_idx,
                    const int32_t* h0_idx, float* llr, float* sd, int32_t* snr) {
     if (!h || !grid || B < 1 || B > h->max_frames || n < 1) return -1;
     ENTER(h);
     HIPCHK(h, hipMemcpy(h->d_grid, grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyHostToDevice));
-    std::vector<int32_t> trip(3 * (size_t)n);
-    for (int i = 0; i < n; i++) { trip[3 * i] = frame[i]; trip[3 * i + 1] = f0_idx[i]; trip[3 * i + 2] = h0_idx[i]; }
+    const std::vector<int32_t> trip = pack_triples(n, frame, f0_idx, h0_idx);
     Scratch S{h};
     int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
     float* d_llr = S.get<float>((size_t)n * 174); NEED(d_llr);
@@ -1496,8 +1492,7 @@ static int fine_probe(ft8rx_handle* h, const float* spec, int B, int n, const in
                     frame[i], f0_idx[i], h0_idx[i], B, FT8RX_MAX_F0, FT8RX_MIN_H0, FT8RX_MAX_H0); return -1; }
     ENTER(h);
     HIPCHK(h, hipMemcpy(h->d_spec, spec, sizeof(cpx) * (size_t)B * FT8RX_SPEC_BINS, hipMemcpyHostToDevice));
-    std::vector<int32_t> trip(3 * (size_t)n);
-    for (int i = 0; i < n; i++) { trip[3 * i] = frame[i]; trip[3 * i + 1] = f0_idx[i]; trip[3 * i + 2] = h0_idx[i]; }
+    const std::vector<int32_t> trip = pack_triples(n, frame, f0_idx, h0_idx);
     Scratch S{h};
     int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
     float* d_llr = S.get<float>((size_t)n * 174); NEED(d_llr);
@@ -1505,13 +1500,8 @@ static int fine_probe(ft8rx_handle* h, const float* spec, int B, int n, const in
     float* d_sd = S.get<float>(n); NEED(d_sd);
     int32_t* d_out = S.get<int32_t>((size_t)n * 5); NEED(d_out);
     float* d_sg = sgrid ? S.get<float>((size_t)n * 632) : nullptr; if (sgrid) NEED(d_sg);
-    if (weak) {
-        const ft8rx_config cw = weak_config(h);
-        k_fine_weak<<<n, FINE_NT, 0, h->stream>>>(h->d_spec, nullptr, nullptr, d_llr, h->T, cw, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});
-    } else {
-        ft8rx_ilp_fine(n, h->stream, h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});
-        k_fine_td<<<n, FINE_NT, 0, h->stream>>>(h->d_spec, nullptr, nullptr, d_llr, h->T, h->cfg, d_trip, d_out, d_sd, d_sg, WorkList{nullptr, nullptr});   // triples k_fine leaves out
-    }
+    launch_fine(h, weak ? weak_config(h) : h->cfg, weak, n, h->stream, h->d_spec, nullptr, nullptr, d_llr, d_trip, d_out, d_sd, d_sg,
+                WorkList{nullptr, nullptr}, true);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<int32_t> o((size_t)n * 5);
     HIPCHK(h, hipMemcpy(o.data(), d_out, sizeof(int32_t) * o.size(), hipMemcpyDeviceToHost));

@@ -617,7 +617,7 @@ FT8_DEV void fine_candidate(int tid, int bid, const cpx* __restrict__ spec, ft8r
     }
     __syncthreads();
     FT(23);
-    // --- Costas gate (receiver.py:164-167)
+    // --- Costas gate, LLRs, record (receiver.py:164-173): the contract of fine_tail (main unit), kept apart for the FT() marks and k_fine's registers
     bool match = false;
     if (tid < 21) {
         int blk = tid / 7, a = tid - blk * 7;
@@ -694,6 +694,106 @@ __global__ __launch_bounds__(FINE_NT, FINE_WV) void k_fine(const cpx* __restrict
 // position.  Ten transforms per candidate (round 3's kernel did that for every candidate); such candidates only exist with a
 // search_time_range beyond -6.1 .. +8.3 s, the launch is skipped otherwise.  Main translation unit (default scheduler).
 FT8_DEV int fine_clamp_pos(int i0) { return i0 < 0 ? 0 : (i0 > 3168 ? 3168 : i0); }
+// The candidate of block / work item `bid`: a test triple, or -- pipeline -- the position in its record while that is still ACTIVE.
+FT8_DEV bool fine_cand(int bid, const ft8rx_record* __restrict__ rec, const int32_t* __restrict__ ncand, const ft8rx_config& cfg,
+                       const int32_t* __restrict__ trip, int& frame, int& f0, int& h0) {
+    if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; return true; }
+    frame = bid >> cand_shift(cfg);
+    if ((bid & ((1 << cand_shift(cfg)) - 1)) >= ncand[frame]) return false;
+    const ft8rx_record& r = rec[bid];
+    if (r.status != FT8RX_ST_ACTIVE) return false;
+    f0 = r.f0_idx; h0 = r.h0_idx;
+    return true;
+}
+// the stage-2 twiddles and the symbol-DFT twiddles go to LDS; wq = the thread's own symbol-DFT factors (all its symbol DFTs use n2 = tid & 3)
+FT8_DEV void fine_tables(const Tables& T, cpx* w400, cpx* w32, cpx* wq, int tid) {
+    for (int i = tid; i < 400; i += FINE_NT) w400[i] = T.W3200[8 * i];
+    if (tid < 32) w32[tid] = T.W32[tid];
+    __syncthreads();
+    sym32_twiddles(w32, tid & 3, wq);
+}
+// Score of one Costas symbol (contract, receiver.py:196-205): on = |tone costas[a]|, off = the sum of the other six tones, b ascending, in
+// fp64.  Branch-free: adding +0.0 for the Costas tone leaves the running sum unchanged.
+FT8_DEV void fine_onoff(const float* mag, int a, double& on, double& off) {
+    const int c = d_COSTAS[a];
+    on = 0.0; off = 0.0;
+#pragma unroll
+    for (int b = 0; b < 7; b++) { const double m = (double)mag[b]; on = (b == c) ? m : on; off += (b == c) ? 0.0 : m; }
+}
+// the 79 x 8 grid from the full series z of the chosen tweaks, symbol by symbol at the clamped positions, four lanes each
+FT8_DEV void fine_grid_td(const cpx* z, int tb, const cpx* wq, float* mg, int tid) {
+#pragma unroll 1
+    for (int r = 0; r < (316 + FINE_NT - 1) / FINE_NT; r++) {
+        const int task = tid + FINE_NT * r, sy = task >> 2, n2 = task & 3;
+        const bool valid = sy < 79;
+        float mag[8];
+        fine_sym_quad<8>(z, tb + 32 * (valid ? sy : 0), n2, wq, mag);
+        if (valid && n2 == 0) {
+#pragma unroll
+            for (int b = 0; b < 8; b++) mg[sy * 8 + b] = mag[b];
+        }
+    }
+    __syncthreads();
+}
+// Everything behind the grid mg[79][8] of the chosen tweaks (tt, ft): Costas gate (receiver.py:164-167), LLRs of the payload symbols
+// (:168-172), sd stop (:173), then the test entry's outputs or the candidate's record.  The same contract as the tail of k_fine.
+FT8_DEV void fine_tail(const float* mg, int tt, int ft, int tid, int bid, ft8rx_record* __restrict__ rec, float* __restrict__ llr0,
+                       const ft8rx_config& cfg, const int32_t* __restrict__ trip, int32_t* __restrict__ t_out, float* __restrict__ t_sd,
+                       float* __restrict__ t_sgrid) {
+    __shared__ float p[464], llr[176], sq[176], sd_sh;
+    __shared__ int nsync_sh, snr_sh;
+    bool match = false;
+    if (tid < 21) {
+        int blk = tid / 7, a = tid - blk * 7;
+        const float* q = mg + 8 * (36 * blk + a);
+        int am = 0; for (int t = 1; t < 8; t++) if (q[t] > q[am]) am = t;
+        match = (am == d_COSTAS[a]);
+    }
+    if (tid < 64) { int nm = __popcll(__ballot(match)); if (tid == 0) nsync_sh = nm; }
+    __syncthreads();
+    const int nsync = nsync_sh;
+    if (trip && t_sgrid) for (int i = tid; i < 632; i += FINE_NT) t_sgrid[(size_t)bid * 632 + i] = mg[i];
+    int ret = 1; float sd = 0.0f; int snr = 0;
+    if (nsync <= 6) ret = 0;           // block-uniform
+    else {
+        for (int i = tid; i < 464; i += FINE_NT) p[i] = 20.0f * ft8_log10f(mg[8 * (int)d_PAYSYM[i >> 3] + (i & 7)]);   // receiver.py:170
+        __syncthreads();
+        llr_from_p(p, llr, sq, tid, tid < 64, &sd, &snr);
+        if (tid == 0) { sd_sh = sd; snr_sh = snr; }
+        __syncthreads();
+        sd = sd_sh; snr = snr_sh;
+        if (sd <= cfg.llr_sd_min) ret = -1;
+        float* out = llr0 + (size_t)bid * 174;
+        for (int i = tid; i < 174; i += FINE_NT) out[i] = llr[i];
+    }
+    if (tid == 0) {
+        if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
+        else {
+            ft8rx_record& r = rec[bid];
+            r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
+            if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
+            else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }
+        }
+    }
+}
+
+// a candidate routine of this unit, and its kernel's body.  Test entry (trip != nullptr): one block per (frame, f0, h0) triple.  Pipeline:
+// blocks stride over the fine-sync work list.
+typedef void FineCandidate(int tid, int bid, const cpx* spec, ft8rx_record* rec, const int32_t* ncand, float* llr0, const Tables& T,
+                           const ft8rx_config& cfg, const int32_t* trip, int32_t* t_out, float* t_sd, float* t_sgrid);
+template <FineCandidate CAND>
+FT8_DEV void fine_blocks(const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec, const int32_t* __restrict__ ncand,
+                         float* __restrict__ llr0, const Tables& T, const ft8rx_config& cfg, const int32_t* __restrict__ trip,
+                         int32_t* __restrict__ t_out, float* __restrict__ t_sd, float* __restrict__ t_sgrid, const WorkList& work) {
+    if (trip) { CAND(threadIdx.x, blockIdx.x, spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid); return; }
+    const int n = *work.count;
+#pragma unroll 1
+    for (int item = blockIdx.x; item < n; item += gridDim.x) {
+        CAND(threadIdx.x, work.items[item], spec, rec, ncand, llr0, T, cfg, nullptr, nullptr, nullptr, nullptr);
+        __syncthreads();                                            // the LDS images are reused by the next candidate
+    }
+}
+
 FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec,
                                const int32_t* __restrict__ ncand, float* __restrict__ llr0, const Tables& T, const ft8rx_config& cfg,
                                const int32_t* __restrict__ trip, int32_t* __restrict__ t_out, float* __restrict__ t_sd, float* __restrict__ t_sgrid) {
@@ -702,25 +802,12 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
     __shared__ cpx w32[32];
     __shared__ float mg[640];
     __shared__ double dsum[8 * 7 * 2];
-    __shared__ float p[464], llr[176], sq[176], sc[16];
-    __shared__ int ish[4];
-    int frame, ci = 0, f0, h0;
-    if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; }
-    else {
-        frame = bid >> cand_shift(cfg); ci = bid & ((1 << cand_shift(cfg)) - 1);
-        if (ci >= ncand[frame]) return;
-        const ft8rx_record& r = rec[bid];
-        if (r.status != FT8RX_ST_ACTIVE) return;
-        f0 = r.f0_idx; h0 = r.h0_idx;
-        if (h0 >= FT8RX_MIN_H0_FD && h0 <= FT8RX_MAX_H0_FD) return;  // k_fine's candidate
-    }
-    for (int i = tid; i < 400; i += FINE_NT) w400[i] = T.W3200[8 * i];
-    if (tid < 32) w32[tid] = T.W32[tid];
-    __syncthreads();
-    const int fb0 = 50 * f0;
-    const cpx* __restrict__ Sg = spec + (size_t)frame * FT8RX_SPEC_BINS + (fb0 - 182);
+    int frame, f0, h0;
+    if (!fine_cand(bid, rec, ncand, cfg, trip, frame, f0, h0)) return;
+    if (h0 >= FT8RX_MIN_H0_FD && h0 <= FT8RX_MAX_H0_FD) return;      // inside the frequency-domain range: k_fine's candidate
     cpx wq[8];
-    sym32_twiddles(w32, tid & 3, wq);
+    fine_tables(T, w400, w32, wq, tid);
+    const cpx* __restrict__ Sg = spec + (size_t)frame * FT8RX_SPEC_BINS + (50 * f0 - 182);
     const int tb0 = 8 * h0 + (h0 < 0 ? 1 : 0);
     // --- time tweaks at ftweak 0 (8 x 7 symbols, 4 lanes each); only the samples the clamped reads touch are produced
     fine_fft(Sg, 182, z, w400, T, tid, fine_clamp_pos(tb0 - 8 + 32 * 36), fine_clamp_pos(tb0 + 6 + 32 * 42) + 32);
@@ -731,13 +818,7 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
         const int ti = valid ? qd / 7 : 0, a = valid ? qd - 7 * ti : 0;
         float mag[8];
         fine_sym_quad<7>(z, tb0 - 8 + 2 * ti + 32 * (36 + a), n2, wq, mag);
-        if (valid && n2 == 0) {
-            const int c = d_COSTAS[a];
-            double off = 0.0, on = 0.0;
-#pragma unroll
-            for (int b = 0; b < 7; b++) { const double m = (double)mag[b]; on = (b == c) ? m : on; off += (b == c) ? 0.0 : m; }
-            dsum[(ti * 7 + a) * 2] = on; dsum[(ti * 7 + a) * 2 + 1] = off;
-        }
+        if (valid && n2 == 0) { double on, off; fine_onoff(mag, a, on, off); dsum[(ti * 7 + a) * 2] = on; dsum[(ti * 7 + a) * 2 + 1] = off; }
     }
     __syncthreads();
     int tt = -8; float score_f0 = 0.0f;
@@ -762,13 +843,7 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
                 const bool valid = a < 7;
                 float mag[8];
                 fine_sym_quad<7>(z, tb + 32 * (36 + (valid ? a : 0)), n2, wq, mag);
-                if (valid && n2 == 0) {
-                    const int c = d_COSTAS[a];
-                    double off = 0.0, on = 0.0;
-#pragma unroll
-                    for (int b = 0; b < 7; b++) { const double m = (double)mag[b]; on = (b == c) ? m : on; off += (b == c) ? 0.0 : m; }
-                    dsum[a * 2] = on; dsum[a * 2 + 1] = off;
-                }
+                if (valid && n2 == 0) { double on, off; fine_onoff(mag, a, on, off); dsum[a * 2] = on; dsum[a * 2 + 1] = off; }
             }
             __syncthreads();
             double s1 = 0.0, s2 = 0.0;
@@ -777,74 +852,18 @@ FT8_DEV void fine_td_candidate(int tid, int bid, const cpx* __restrict__ spec, f
         }
         if (i == 0 || v > best) { best = v; ft = f; }
     }
-    // --- the 79 x 8 grid from the series of the chosen tweaks, symbol by symbol at the clamped positions
+    // --- the chosen tweaks' series in full for the grid, then the shared tail
     __syncthreads();
     fine_fft(Sg, 182 + ft, z, w400, T, tid, 0, 3200);
-#pragma unroll 1
-    for (int r = 0; r < (316 + FINE_NT - 1) / FINE_NT; r++) {
-        const int task = tid + FINE_NT * r, sy = task >> 2, n2 = task & 3;
-        const bool valid = sy < 79;
-        float mag[8];
-        fine_sym_quad<8>(z, tb + 32 * (valid ? sy : 0), n2, wq, mag);
-        if (valid && n2 == 0) {
-#pragma unroll
-            for (int b = 0; b < 8; b++) mg[sy * 8 + b] = mag[b];
-        }
-    }
-    __syncthreads();
-    // --- Costas gate, LLRs, record: as k_fine (receiver.py:164-173)
-    bool match = false;
-    if (tid < 21) {
-        int blk = tid / 7, a = tid - blk * 7;
-        const float* q = mg + 8 * (36 * blk + a);
-        int am = 0; for (int t = 1; t < 8; t++) if (q[t] > q[am]) am = t;
-        match = (am == d_COSTAS[a]);
-    }
-    if (tid < 64) { int nm = __popcll(__ballot(match)); if (tid == 0) ish[1] = nm; }
-    __syncthreads();
-    const int nsync = ish[1];
-    if (trip && t_sgrid) for (int i = tid; i < 632; i += FINE_NT) t_sgrid[(size_t)bid * 632 + i] = mg[i];
-    int ret = 1; float sd = 0.0f; int snr = 0;
-    if (nsync <= 6) ret = 0;
-    else {
-        for (int i = tid; i < 464; i += FINE_NT) p[i] = 20.0f * ft8_log10f(mg[8 * (int)d_PAYSYM[i >> 3] + (i & 7)]);
-        __syncthreads();
-        llr_from_p(p, llr, sq, tid, tid < 64, &sd, &snr);
-        if (tid == 0) { sc[10] = sd; ish[2] = snr; }
-        __syncthreads();
-        sd = sc[10]; snr = ish[2];
-        if (sd <= cfg.llr_sd_min) ret = -1;
-        float* out = llr0 + (size_t)bid * 174;
-        for (int i = tid; i < 174; i += FINE_NT) out[i] = llr[i];
-    }
-    if (tid == 0) {
-        if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
-        else {
-            ft8rx_record& r = rec[bid];
-            r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
-            if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
-            else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }
-        }
-    }
+    fine_grid_td(z, tb, wq, mg, tid);
+    fine_tail(mg, tt, ft, tid, bid, rec, llr0, cfg, trip, t_out, t_sd, t_sgrid);
 }
-// test entry (trip != nullptr): one block per triple, triples inside the frequency-domain range are left to k_fine.  Pipeline: blocks
-// stride over the fine-sync work list and take the candidates k_fine skips.
+// the candidates k_fine leaves out (in the test entry too: triples inside the frequency-domain range are left to k_fine)
 __global__ __launch_bounds__(FINE_NT) void k_fine_td(const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec,
                                                      const int32_t* __restrict__ ncand, float* __restrict__ llr0, Tables T, ft8rx_config cfg,
                                                      const int32_t* __restrict__ trip, int32_t* __restrict__ t_out,
                                                      float* __restrict__ t_sd, float* __restrict__ t_sgrid, WorkList work) {
-    if (trip) {
-        const int h0 = trip[3 * blockIdx.x + 2];
-        if (h0 >= FT8RX_MIN_H0_FD && h0 <= FT8RX_MAX_H0_FD) return;
-        fine_td_candidate(threadIdx.x, blockIdx.x, spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid);
-        return;
-    }
-    const int n = *work.count;
-#pragma unroll 1
-    for (int item = blockIdx.x; item < n; item += gridDim.x) {
-        fine_td_candidate(threadIdx.x, work.items[item], spec, rec, ncand, llr0, T, cfg, nullptr, nullptr, nullptr, nullptr);
-        __syncthreads();
-    }
+    fine_blocks<fine_td_candidate>(spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid, work);
 }
 
 // ------------------------------------------------------------------------------------ weak-mode fine sync (ft8rx_set_weak, ipass 1)
@@ -864,32 +883,21 @@ FT8_DEV void fine_weak_candidate(int tid, int bid, const cpx* __restrict__ spec,
     __shared__ cpx w32[32];
     __shared__ float mg[640];
     __shared__ double dsum[FW_NTT * 21 * 2];
-    __shared__ float p[464], llr[176], sq[176], sc[FW_NTT + 3];
-    __shared__ int ish[4];
-    int frame, ci = 0, f0, h0;
-    if (trip) { frame = trip[3 * bid]; f0 = trip[3 * bid + 1]; h0 = trip[3 * bid + 2]; }
-    else {
-        frame = bid >> cand_shift(cfg); ci = bid & ((1 << cand_shift(cfg)) - 1);
-        if (ci >= ncand[frame]) return;
-        const ft8rx_record& r = rec[bid];
-        if (r.status != FT8RX_ST_ACTIVE) return;
-        f0 = r.f0_idx; h0 = r.h0_idx;
-    }
-    for (int i = tid; i < 400; i += FINE_NT) w400[i] = T.W3200[8 * i];
-    if (tid < 32) w32[tid] = T.W32[tid];
-    __syncthreads();
+    __shared__ float sc[FW_NTT];
+    int frame, f0, h0;
+    if (!fine_cand(bid, rec, ncand, cfg, trip, frame, f0, h0)) return;
+    cpx wq[8];
+    fine_tables(T, w400, w32, wq, tid);
     const int fb0 = 50 * f0;
     const cpx* __restrict__ Sg = spec + (size_t)frame * FT8RX_SPEC_BINS + (fb0 - 182);
-    cpx wq[8];
-    sym32_twiddles(w32, tid & 3, wq);
     const int tb0 = 8 * h0 + (h0 < 0 ? 1 : 0);
-    float best = 0.0f; int bft = 0, btt = -16; bool any = false;       // block-uniform (every thread runs the same pick)
+    float best = 0.0f; int ft = 0, tt = -16; bool any = false;         // block-uniform (every thread runs the same pick)
 #pragma unroll 1
     for (int fi = 0; fi < FW_NT; fi++) {
-        const int ft = -56 + 8 * fi;
-        if (fb0 + ft < 150) continue;                              // block-uniform
+        const int f = -56 + 8 * fi;
+        if (fb0 + f < 150) continue;                               // block-uniform
         __syncthreads();                                           // the previous tweak's series and sums are consumed
-        fine_fft(Sg, 182 + ft, z, w400, T, tid, 0, 3200);
+        fine_fft(Sg, 182 + f, z, w400, T, tid, 0, 3200);
 #pragma unroll 1
         for (int r = 0; r < (FW_NTT * 21 * 4 + FINE_NT - 1) / FINE_NT; r++) {
             const int task = tid + FINE_NT * r, qd = task >> 2, n2 = task & 3;
@@ -898,13 +906,7 @@ FT8_DEV void fine_weak_candidate(int tid, int bid, const cpx* __restrict__ spec,
             const int b = k / 7, a = k - 7 * b;
             float mag[8];
             fine_sym_quad<7>(z, tb0 - 16 + 2 * ti + 32 * (36 * b + a), n2, wq, mag);
-            if (valid && n2 == 0) {
-                const int c = d_COSTAS[a];
-                double off = 0.0, on = 0.0;
-#pragma unroll
-                for (int q = 0; q < 7; q++) { const double m = (double)mag[q]; on = (q == c) ? m : on; off += (q == c) ? 0.0 : m; }
-                dsum[(ti * 21 + k) * 2] = on; dsum[(ti * 21 + k) * 2 + 1] = off;
-            }
+            if (valid && n2 == 0) { double on, off; fine_onoff(mag, a, on, off); dsum[(ti * 21 + k) * 2] = on; dsum[(ti * 21 + k) * 2 + 1] = off; }
         }
         __syncthreads();
         if (tid < FW_NTT) {                                        // b ascending, then a (k = 7 b + a ascending), fp64, one rounding
@@ -915,72 +917,20 @@ FT8_DEV void fine_weak_candidate(int tid, int bid, const cpx* __restrict__ spec,
         __syncthreads();
         for (int ti = 0; ti < FW_NTT; ti++) {                      // ft outer, tt inner: the first strict maximum
             const float v = sc[ti];
-            if (!any || v > best) { best = v; bft = ft; btt = -16 + 2 * ti; any = true; }
+            if (!any || v > best) { best = v; ft = f; tt = -16 + 2 * ti; any = true; }
         }
     }
-    const int tt = btt, ft = bft, tb = tb0 + tt;
-    // --- the 79 x 8 grid from the series of the chosen tweaks, symbol by symbol at the clamped positions (as k_fine_td)
+    // --- the chosen tweaks' series in full for the grid, then the shared tail (as k_fine_td)
     __syncthreads();
     fine_fft(Sg, 182 + ft, z, w400, T, tid, 0, 3200);
-#pragma unroll 1
-    for (int r = 0; r < (316 + FINE_NT - 1) / FINE_NT; r++) {
-        const int task = tid + FINE_NT * r, sy = task >> 2, n2 = task & 3;
-        const bool valid = sy < 79;
-        float mag[8];
-        fine_sym_quad<8>(z, tb + 32 * (valid ? sy : 0), n2, wq, mag);
-        if (valid && n2 == 0) {
-#pragma unroll
-            for (int q = 0; q < 8; q++) mg[sy * 8 + q] = mag[q];
-        }
-    }
-    __syncthreads();
-    // --- Costas gate, LLRs, record: as k_fine (receiver.py:164-173)
-    bool match = false;
-    if (tid < 21) {
-        int blk = tid / 7, a = tid - blk * 7;
-        const float* q = mg + 8 * (36 * blk + a);
-        int am = 0; for (int t = 1; t < 8; t++) if (q[t] > q[am]) am = t;
-        match = (am == d_COSTAS[a]);
-    }
-    if (tid < 64) { int nm = __popcll(__ballot(match)); if (tid == 0) ish[1] = nm; }
-    __syncthreads();
-    const int nsync = ish[1];
-    if (trip && t_sgrid) for (int i = tid; i < 632; i += FINE_NT) t_sgrid[(size_t)bid * 632 + i] = mg[i];
-    int ret = 1; float sd = 0.0f; int snr = 0;
-    if (nsync <= 6) ret = 0;
-    else {
-        for (int i = tid; i < 464; i += FINE_NT) p[i] = 20.0f * ft8_log10f(mg[8 * (int)d_PAYSYM[i >> 3] + (i & 7)]);
-        __syncthreads();
-        llr_from_p(p, llr, sq, tid, tid < 64, &sd, &snr);
-        if (tid == 0) { sc[FW_NTT] = sd; ish[2] = snr; }
-        __syncthreads();
-        sd = sc[FW_NTT]; snr = ish[2];
-        if (sd <= cfg.llr_sd_min) ret = -1;
-        float* out = llr0 + (size_t)bid * 174;
-        for (int i = tid; i < 174; i += FINE_NT) out[i] = llr[i];
-    }
-    if (tid == 0) {
-        if (trip) { int32_t* o = t_out + 5 * (size_t)bid; o[0] = ret; o[1] = tt; o[2] = ft; o[3] = nsync; o[4] = snr; t_sd[bid] = sd; }
-        else {
-            ft8rx_record& r = rec[bid];
-            r.ttweak = (int8_t)tt; r.ftweak = (int8_t)ft; r.nsync = (uint8_t)nsync;
-            if (ret == 0) r.status = FT8RX_ST_STOP_COSTAS;
-            else { r.fine_sd = sd; r.snr_fine = (int8_t)snr; if (ret < 0) r.status = FT8RX_ST_STOP_FINE_SD; }
-        }
-    }
+    fine_grid_td(z, tb0 + tt, wq, mg, tid);
+    fine_tail(mg, tt, ft, tid, bid, rec, llr0, cfg, trip, t_out, t_sd, t_sgrid);
 }
-// test entry (trip != nullptr): one block per (frame, f0, h0) triple.  Pipeline: blocks stride over the fine-sync work list.
 __global__ __launch_bounds__(FINE_NT) void k_fine_weak(const cpx* __restrict__ spec, ft8rx_record* __restrict__ rec,
                                                        const int32_t* __restrict__ ncand, float* __restrict__ llr0, Tables T, ft8rx_config cfg,
                                                        const int32_t* __restrict__ trip, int32_t* __restrict__ t_out,
                                                        float* __restrict__ t_sd, float* __restrict__ t_sgrid, WorkList work) {
-    if (trip) { fine_weak_candidate(threadIdx.x, blockIdx.x, spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid); return; }
-    const int n = *work.count;
-#pragma unroll 1
-    for (int item = blockIdx.x; item < n; item += gridDim.x) {
-        fine_weak_candidate(threadIdx.x, work.items[item], spec, rec, ncand, llr0, T, cfg, nullptr, nullptr, nullptr, nullptr);
-        __syncthreads();
-    }
+    fine_blocks<fine_weak_candidate>(spec, rec, ncand, llr0, T, cfg, trip, t_out, t_sd, t_sgrid, work);
 }
 #endif  // !FT8RX_ILP_UNIT
 

@@ -519,13 +519,7 @@ __global__ __launch_bounds__(FINE_NT) void k_refine3(const cpx* __restrict__ spe
         const int blk = sy / 7, a = sy - 7 * blk;
         float mag[8];
         fine_sym_quad<7>(z, tb0 - 6 + ti + 32 * (36 * blk + a), n2, wq, mag);
-        if (valid && n2 == 0) {
-            const int c = d_COSTAS[a];
-            double off = 0.0, on = 0.0;
-#pragma unroll
-            for (int b = 0; b < 7; b++) { const double m = (double)mag[b]; on = (b == c) ? m : on; off += (b == c) ? 0.0 : m; }
-            dsum[(ti * 21 + sy) * 2] = on; dsum[(ti * 21 + sy) * 2 + 1] = off;
-        }
+        if (valid && n2 == 0) { double on, off; fine_onoff(mag, a, on, off); dsum[(ti * 21 + sy) * 2] = on; dsum[(ti * 21 + sy) * 2 + 1] = off; }
     }
     __syncthreads();
     if (tid == 0) {

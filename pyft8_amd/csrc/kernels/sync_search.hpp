@@ -91,7 +91,7 @@ FT8_DEV void sync3_block(const float* __restrict__ grid, float* __restrict__ bes
     __shared__ float tile[NR * 29];
     __shared__ float redS[256];
     __shared__ int redH[256];
-    const int nh0 = cfg.h0_hi - cfg.h0_lo;                        // <= SYNC3_WIN (launch_sync3)
+    const int nh0 = cfg.h0_hi - cfg.h0_lo;                        // <= SYNC3_WIN (launch_sync)
     const int nrows = nh0 + 24;
     const int f = blockIdx.y, tid = threadIdx.x;
     const int f0base = cfg.f0_lo + 16 * blockIdx.x;

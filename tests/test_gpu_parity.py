@@ -169,6 +169,33 @@ def test_fine_sync_clamp_rows_are_bit_identical(H, ocfg):
     assert n_clamped > 40 and n_boundary >= 3, (n_clamped, n_boundary)
 
 
+def test_fine_sync_far_out_survivors_are_bit_identical(H, ocfg):
+    """The far-out triples of the test above all stop at the Costas gate, so k_fine_td's tail behind the gate (receiver.py:168-173:
+    LLRs, sd stop, snr) is compared here: early far-out candidates of the same frame that pass the gate -- four go on (ret 1), three
+    stop at the sd gate (ret -1).  GPU == oracle bit for bit, LLRs, sd and snr included, and the set really holds both outcomes."""
+    from pyft8_amd import synth
+    audio = synth.make_frame(61000, n_signals=50, snr_range=(-10.0, 10.0))
+    spec = O.cycle_spectrum(audio, ocfg)
+    # (f0, h0) -> the oracle's (ret, ttweak, ftweak, nsync)
+    want = {(144, -141): (1, 6, -32, 15), (436, -141): (1, 6, -8, 14), (716, -142): (1, 6, 32, 15), (788, -144): (1, 4, 32, 14),
+            (184, -141): (-1, 6, 32, 7), (660, -141): (-1, -8, 16, 7), (644, -144): (-1, -6, -24, 7)}
+    trip = list(want)
+    f0s, h0s = np.array([t[0] for t in trip], np.int32), np.array([t[1] for t in trip], np.int32)
+    r = H.fine(spec, np.zeros(len(trip), np.int32), f0s, h0s, want_sgrid=True)
+    rets = []
+    for k, (f, h) in enumerate(trip):
+        w = O.fine(spec, f, h, ocfg)
+        assert (w["ret"], w["ttweak"], w["ftweak"], w["nsync"]) == want[(f, h)], (f, h)
+        assert (r["ret"][k], r["ttweak"][k], r["ftweak"][k], r["nsync"][k]) == (w["ret"], w["ttweak"], w["ftweak"], w["nsync"]), (f, h)
+        assert bits_equal(r["sgrid"][k], w["sgrid"]), (f, h)
+        if w["ret"] != 0:
+            assert not np.isnan(w["llr"]).any(), (f, h)
+            assert bits_equal(r["llr"][k], w["llr"]), (f, h)
+            assert np.float32(r["sd"][k]).tobytes() == np.float32(w["sd"]).tobytes() and r["snr"][k] == w["snr"], (f, h)
+        rets.append(int(w["ret"]))
+    assert rets.count(1) >= 4 and rets.count(-1) >= 3, rets
+
+
 def test_ldpc_exact(H):
     for name in GOLDEN_FRAMES:
         audio, gold, js = load_golden(name)
