@@ -625,6 +625,19 @@ static void launch_fine(ft8rx_handle* h, const ft8rx_config& cfg, bool weak, int
     if (need_td) k_fine_td<<<n_blocks, FINE_NT, 0, s>>>(spec, rec, ncand, llr, h->T, cfg, trip, t_out, t_sd, t_sgrid, work);
 }
 
+// OSD of `grid` blocks -- mode 0: striding over `work` x 10 attempts, mode 2: one raw vector each -- then of the attempts they left on `nanl`: vectors
+// with a NaN (a NaN-poisoned BP output), which the reference's numpy orders with std::sort -- a kernel of their own.  osd_wide: kernels/osd.hpp
+static bool osd_wide(int nflip) { return nflip > OSD_FLIPS_A; }
+static void launch_osd(unsigned mt, int grid, hipStream_t s, int mode, const float* llr, const float* saved, const Att* attB, ft8rx_record* rec,
+                       const int32_t* ncand, Att* attO, ft8rx_event* ev, int32_t* evc, const uint32_t* trials, int ntr, int nflip, int max_hd,
+                       int sh, WorkList work, WorkList nanl) {
+    const bool wide = osd_wide(nflip);
+    launch_mt(wide ? k_osd_wide : k_osd, wide ? k_osd_wide_ext : k_osd_ext, mt, grid, s,
+              mode, llr, saved, attB, rec, ncand, attO, ev, evc, trials, ntr, nflip, max_hd, sh, work, nanl);
+    launch_mt(wide ? k_osd_nan_wide : k_osd_nan, wide ? k_osd_nan_wide_ext : k_osd_nan_ext, mt, OSD_NAN_GRID, s,
+              mode, llr, saved, attB, rec, ncand, attO, ev, evc, trials, ntr, nflip, max_hd, sh, nanl);
+}
+
 // ipass 7 of B frames (kernels/ap_calls.hpp): candidate list in cand_items (B * stride entries), OSD list in osd_items (B * stride * 3),
 // attempt results in attO (B * stride * 10), the two list counters at ac; the batch chain and ft8rx_ap_calls_probe launch the same
 static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_record* rec, const int32_t* ncand, Att* attO, ft8rx_event* ev,
@@ -636,7 +649,7 @@ static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_rec
     const WorkList cl = {cand_items, ac}, ol = {osd_items, ac + 1};
     k_ap_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, cl);
     k_bp_ap<<<ladder_grid(B * c.max_cands * h->ap.np), 64, 0, s>>>(llr0, rec, ncand, attO, ev, evc, c, apc, cl, ol);
-    (nflip > OSD_FLIPS_A ? k_osd_ap_wide : k_osd_ap)<<<ladder_grid(B * c.max_cands * 3), 64, 0, s>>>(
+    (osd_wide(nflip) ? k_osd_ap_wide : k_osd_ap)<<<ladder_grid(B * c.max_cands * 3), 64, 0, s>>>(
         llr0, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, sh, apc, ol);
     k_select_ap<<<(B * S + 255) / 256, 256, 0, s>>>(rec, attO, apc, cl);
 }
@@ -714,13 +727,8 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     }
     STAGE("osd");
-    const bool osd_wide = osd_nflip(c.osd_single, c.osd_triple) > OSD_FLIPS_A;
-    const int nflip = osd_nflip(c.osd_single, c.osd_triple);
-    launch_mt(osd_wide ? k_osd_wide : k_osd, osd_wide ? k_osd_wide_ext : k_osd_ext, mt, ladder_grid(B * c.max_cands * 10), s,
-              0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
-    // attempts on vectors with a NaN (a NaN-poisoned BP output): the reference's numpy orders those with std::sort -- a kernel of their own
-    launch_mt(osd_wide ? k_osd_nan_wide : k_osd_nan, osd_wide ? k_osd_nan_wide_ext : k_osd_nan_ext, mt, OSD_NAN_GRID, s,
-              0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, c.osd_max_hd, sh, wl[WL_OSDNAN]);
+    launch_osd(mt, ladder_grid(B * c.max_cands * 10), s, 0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials,
+               osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
     STAGE("select2");
     k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
     if (h->ap.np) {
@@ -1653,12 +1661,8 @@ int ft8rx_osd_ext(ft8rx_handle* h, const float* llr, int n, int singleflips, int
     int32_t* d_nan = S.get<int32_t>((size_t)n + 1); NEED(d_nan);            // [0] = length of the list of NaN vectors, then the list
     HIPCHK(h, hipMemsetAsync(d_nan, 0, sizeof(int32_t), h->stream));
     const WorkList nanl{d_nan + 1, d_nan};
-    const bool osd_wide = osd_nflip(singleflips, tripleflips) > OSD_FLIPS_A;
-    (osd_wide ? k_osd_wide : k_osd)<<<n, 64, 0, h->stream>>>(
-        2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd,
-        cand_shift(h->cfg), WorkList{nullptr, nullptr}, nanl);
-    (osd_wide ? k_osd_nan_wide : k_osd_nan)<<<OSD_NAN_GRID, 64, 0, h->stream>>>(
-        2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd, cand_shift(h->cfg), nanl);
+    launch_osd(0, n, h->stream, 2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(),
+               osd_nflip(singleflips, tripleflips), max_hd, cand_shift(h->cfg), WorkList{nullptr, nullptr}, nanl);      // (msg_types do not apply here)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<Att> a(n);
     HIPCHK(h, hipMemcpy(a.data(), d_att, sizeof(Att) * n, hipMemcpyDeviceToHost));

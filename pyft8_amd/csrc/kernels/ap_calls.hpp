@@ -68,16 +68,8 @@ __global__ __launch_bounds__(64) OSD_ATTR void NAME(const float* __restrict__ ll
                                                     const int32_t* __restrict__ ncand, Att* __restrict__ att7, ft8rx_event* ev,     \
                                                     int32_t* evcount, const uint32_t* __restrict__ trials, int ntr, int nflip,      \
                                                     int sh, const ApCalls* __restrict__ apc, WorkList work) {                       \
-    const int n = *work.count;                                                                                                      \
-    const WorkList none = {nullptr, nullptr};                                                                                       \
-    _Pragma("unroll 1")                                                                                                             \
-    for (int item = blockIdx.x; item < n; item += gridDim.x) {                                                                      \
-        int lane = threadIdx.x;                                                                                                     \
-        asm volatile("" : "+v"(lane));                                                                                              \
-        osd_attempt<WIDE, false, false, true>(lane, 0, work.items[item], llr0, nullptr, nullptr, rec, ncand, att7, ev, evcount,      \
-                                              trials, ntr, nflip, 0, sh, none, 0u, apc);                                    \
-        __syncthreads();                                                                                                            \
-    }                                                                                                                               \
+    const OsdArgs a = {llr0, nullptr, nullptr, rec, ncand, att7, ev, evcount, trials, ntr, nflip, 0, sh, {nullptr, nullptr}, 0u, apc}; \
+    osd_blocks<WIDE, false, false, true>(*work.count, 0, a, [&](int item) { return work.items[item]; });                            \
 }
 OSD_AP_KERNEL(k_osd_ap, false)
 OSD_AP_KERNEL(k_osd_ap_wide, true)

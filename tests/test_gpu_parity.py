@@ -263,6 +263,22 @@ def test_osd_ties_and_nans(H):
             assert bool(ok[k]) == w_ok and (not w_ok or (((int(hi[k]) << 64) | int(lo[k])) == w_bits and trial[k] == w_trial))
 
 
+def test_osd_steals_exact(H):
+    """Valid codewords with 0 / 1 / 2 sign errors whose reliability order makes the elimination steal rows of unvisited systematic
+    columns often (parity-first), never (mixed) or sometimes (helpers.osd_steal_vectors; the conditions are checked on the host
+    first): outcome, word and trial index equal the oracle's."""
+    import helpers
+    vectors = helpers.osd_steal_vectors()
+    helpers.osd_steal_checks(vectors)
+    x = np.stack([v[3] for v in vectors])
+    for s, d in [(30, 2), (91, 91)]:
+        ok, lo, hi, trial = H.osd(x, s, d)
+        for k in range(len(x)):
+            w_ok, w_bits, w_trial, _ = O.osd(x[k], s, d)
+            print(vectors[k][0], vectors[k][1], (s, d), "oracle", w_ok, w_trial, "gpu", bool(ok[k]), trial[k])
+            assert bool(ok[k]) == w_ok and (not w_ok or (((int(hi[k]) << 64) | int(lo[k])) == w_bits and trial[k] == w_trial)), (k, s, d)
+
+
 def test_osd_order3_and_distance_gate_exact(H):
     """Extension knobs (BASELINE config 4 "OSD depth-3"; no reference counterpart): triple flips over the least reliable basis
     positions and the Hamming-distance acceptance gate, GPU vs the oracle run with the same knobs -- outcome, word, trial index

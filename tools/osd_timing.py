@@ -11,9 +11,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyft8_amd import _lib  # noqa: E402
 
-NAMES = ["LLR loads, AP override, sort keys", "np.argsort network (36 stages, keys in registers)", "generator columns in sorted order (d_G0T loads), hard decisions",
-         "Gauss-Jordan: visited columns until 91 are accepted", "flip rows published, hard-decision mask", "per-column flip words (nflip broadcast reads), un-permutation",
-         "CRC syndromes of the order-0 codeword and the flips", "trials (+ slow path of zero-syndrome trials), result"]
+# interval i ends at mark OT(i) of osd_attempt and its phases (kernels/osd.hpp)
+NAMES = ["osd_load, sort keys and NaN ballots of osd_order", "osd_order: np.argsort network (36 stages, keys in registers)",
+         "osd_hard, osd_eliminate: generator columns in sorted order (d_G0T loads), trivial positions",
+         "osd_eliminate: visited columns until the basis is complete", "osd_flip_table: flip rows published, hard-decision mask",
+         "osd_flip_table: per-column flip words (nflip broadcast reads), un-permutation",
+         "osd_syndromes: CRC syndromes of the order-0 codeword and the flips", "osd_trials (+ slow path of zero-syndrome trials)"]
 
 
 def main():
@@ -35,7 +38,6 @@ def main():
     print(f"k_osd, {B} frames: {n} attempts that ran; shader cycles of lane 0 summed over all attempts (share; cycles per attempt)")
     for i, nm in enumerate(NAMES):
         print(f"  {i} {nm:<90s} {int(out[i]):>16,d}  {100 * out[i] / tot:5.1f} %  {out[i] / max(n, 1):9.0f}")
-    print(f"  visited columns per attempt: {out[8] / max(n, 1):.1f}")
     h.close()
 
 
