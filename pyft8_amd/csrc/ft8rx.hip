@@ -24,7 +24,7 @@
 // A batch is cut into chunks whose chains run on separate HIP streams -- free-running: chunk i of batch k+1 follows chunk i of batch k
 // on stream i, no per-batch fork / join; results land in one of two result slots and are copied to page-locked host buffers by a copy
 // stream while the next batch computes; the used part of the event log is packed by k_ev_scan / k_ev_compact straight into
-// page-locked host memory (launch_batch / ft8rx_fetch_results).
+// page-locked host memory (batch_plan.hpp; launch_batch = batch_begin, batch_submit, batch_finish; ft8rx_fetch_results).
 // k_sub_* / k_subd_* subtract decoded signals (ft8rx_subtract; refine 0 = the reference experiment's subtract_signal,
 // 3 = its refine_time_origin first: k_cyc_a_f32 + k_refine3; 1 / 2 = the build's own origin re-estimation).
 // Reference line citations are to PyFT8/receiver.py and PyFT8/decoders.py (see include/ft8rx.h).
@@ -60,10 +60,11 @@
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
+#include "batch_plan.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
 // ====================================================================================== host side
-#define EV_EAGER_BYTES ((size_t)1 << 20)      /* event logs up to this size travel whole with the records (launch_batch) */
+#define EV_EAGER_BYTES ((size_t)1 << 20)      /* event logs up to this size travel whole with the records (batch_finish) */
 #define HIPCHK(h, x) do { hipError_t _e = (x); if (_e != hipSuccess) { set_err(h, "%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); return -2; } } while (0)
 
 // OSD trial list in the reference's order (decoders.py:248-272): order 0; single flips i < S; the restricted double flips
@@ -93,86 +94,110 @@ static size_t sync_lds_bytes(const ft8rx_config& c) {
 }
 static std::string g_create_err;
 
-struct ft8rx_handle {
-    ft8rx_config cfg;
-    int device, max_frames;
-    hipStream_t stream;
-    int n_streams;                       // chunks of a batch run their kernel chains on separate streams
-    int ladder_mode;                     // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
-    int msg_types;                       // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
-    bool weak; float weak_sync_min; int32_t weak_osd_max_hd;     // opt-in weak mode (ft8rx_set_weak; off = the reference's stages)
-    ApCalls ap;                          // ipass-7 patterns (ft8rx_set_ap_calls; ap.np = 0: off), as the host last set them
-    uint32_t ap_version, ap_chunk_version[16];   // the setting's version, and the version each chunk's device copy holds
-    ApCalls* d_apc;                      // [16] per-chunk device copies of `ap`, written on the chunk's stream (enqueue_chain)
-    int32_t* d_apcount;                  // [16][2] ipass-7 list lengths per chunk: candidates, OSD attempts
-    // recall (ft8rx_set_recall, kernels/recall.hpp; allocated on first use): the pending entries of the next batch and its per-frame
-    // triple offsets (host copy rc_off), the forced fine sync's scratch, and per result slot the batch's entry copy and results
-    bool rc_armed; int rc_frames; bool rc_td; std::vector<int32_t> rc_off;
-    int32_t rc_max_hd, rc_min_gap;
-    ft8rx_recall_entry* d_rc_src; int32_t* d_rc_srccnt; int32_t* d_rc_off;
-    int32_t* d_rc_trip; int32_t* d_rc_tout; float* d_rc_tsd; float* d_rc_sgrid; float* d_rc_llr;
-    ft8rx_recall_entry* d_rc_ent[2]; int32_t* d_rc_cnt[2]; ft8rx_record* d_rc_rec[2];
-    ft8rx_record* h_rc_rec[2]; int32_t* h_rc_cnt[2]; bool slot_recall[2];
-    // measured reports (ft8rx_set_reports, kernels/report.hpp; allocated at the first ft8rx_set_reports(h, 1)): the work list of the
-    // DECODED slots ([max_frames][stride] ids, a counter per chunk) and per result slot the reports, [max_frames][stride] on the device
-    bool reports, slot_reports[2];
-    int32_t* d_rp_items; int32_t* d_rp_count; ft8rx_report* d_rp[2]; ft8rx_report* h_rp[2];
-    int sub_frames;                      // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
-    hipStream_t sub[8];
-    hipEvent_t ev_fork, ev_join[8];
-    hipStream_t copy_s;              // host-to-device chunk copies of ft8rx_decode_batch, in order, never queued behind kernels
-    hipEvent_t ev_chunk[16];
-    Tables T;
-    std::vector<void*> allocs;
-    struct Chunk { void* p; size_t cap, used; };
-    std::vector<Chunk> arena;        // scratch of the stage entry points (struct Scratch)
-    int16_t* d_audio;            // staging for host-pointer entry points
-    int16_t* d_audio2;           // second staging buffer (allocated on first use): ft8rx_enqueue_batch_host double-buffers the H2D copies
-    hipStream_t h2d_s;           // host-to-device copies of the pipelined host entry: never queued behind kernels or result copies
-    float* d_grid;
-    float* d_best_score; int32_t* d_best_h0;
-    ft8rx_record* d_rec; int32_t* d_ncand;
-    float* d_llr0; float* d_saved;
-    Att *d_att0, *d_attG, *d_attB, *d_attO;
-    cpx *d_A, *d_spec;
-    ft8rx_event* d_ev; int32_t* d_evcount;
-    const uint32_t* d_trials; int n_trials;      // OSD trial list of this configuration
-    int32_t* d_work[WL_N];                       // ladder work lists (kernels/common.hpp: WorkList), [B][stride] candidate ids each
-    int32_t* d_wcount;                           // [16 chunks][WL_N] list lengths, zeroed at the head of every chunk's chain
-    uint8_t* d_colmask; bool use_mask;           // [B][NF0MAX] search mask of the local re-search (ft8rx_set_search_mask), allocated on first use
-    // Result slots.  A batch writes its records/events into slot k % 2 (slot 0 = d_rec/d_ncand/d_ev/d_evcount above) and, when its
-    // kernels are done, the copy stream moves them into page-locked host buffers while the next batch computes into the other
-    // slot; ft8rx_fetch_results hands out the oldest unfetched batch.  At most two batches' results are retained.
-    ft8rx_record* s_rec[2]; int32_t* s_ncand[2]; ft8rx_event* s_ev[2]; int32_t* s_evcount[2];
-    ft8rx_record* h_rec[2]; int32_t* h_cnt[2]; ft8rx_event* h_ev[2]; int32_t* h_evc[2];
-    hipEvent_t ev_comp[2], ev_done[2];
-    int slot_enq, slot_fetch, inflight, last_slot, slot_B[2];
-    // free-running chunk streams (launch_batch): the chunk chains of consecutive batches follow each other on their own streams
-    // without a per-batch fork / join; need_barrier = something else has used the shared workspaces (or the partition changed) since
-    hipEvent_t ev_cdone[2][8];
-    bool free_running, need_barrier; int part_B, part_n;
+// Result slots.  A batch writes its records / events into slot k % 2 and, when its kernels are done, the copy stream moves them into
+// page-locked host buffers while the next batch computes into the other slot; ft8rx_fetch_results hands out the oldest unfetched
+// batch.  At most two batches' results are retained.  Everything a batch leaves behind lives here, once per slot.
+struct ResultSlot {
+    ft8rx_record* rec = nullptr; int32_t* ncand = nullptr; ft8rx_event* ev = nullptr; int32_t* evcount = nullptr;      // on the device
+    ft8rx_record* h_rec = nullptr; int32_t* h_cnt = nullptr; ft8rx_event* h_ev = nullptr; int32_t* h_evc = nullptr;    // page-locked copies
+    hipEvent_t ev_comp = nullptr, ev_done = nullptr;     // the batch's kernels are done / its results have reached the host buffers
+    int B = 0;                                           // frames of the batch the slot holds
     // Large batches (event log > EV_EAGER_BYTES): k_ev_scan / k_ev_compact pack the used entries of the log and write them straight
     // into page-locked host memory (h_evpacked; d_evpacked = the same buffer's device address); the fetch spreads them over h_ev's
     // [frame][cap] rows (fetch_events)
-    bool slot_evpending[2];
-    int32_t* d_evoffs[2]; ft8rx_event* h_evpacked[2]; ft8rx_event* d_evpacked[2];
-    // packed results (ft8rx_set_packed_output): the caller's buffers (as device addresses), one per result slot, the scratch of the
-    // pack kernels and a page-locked mirror of each slot's header
-    unsigned char* pk_buf[2]; uint64_t pk_cap; uint64_t* d_pkneed; int32_t* d_pknrec;
-    ft8rx_packed_header* h_pkhdr[2]; ft8rx_packed_header* d_pkhdr[2]; bool slot_packed[2]; int fetched_slot;
-    hipEvent_t pk_fence[2];                      // ft8rx_packed_output_fence: the consumer's "done reading this buffer" event
-    hipEvent_t d2h_ev[32]; uint32_t d2h_next;    // ft8rx_d2h_async: tickets (a ring of events on the result-copy stream)
+    bool evpending = false;
+    int32_t* d_evoffs = nullptr; ft8rx_event* h_evpacked = nullptr; ft8rx_event* d_evpacked = nullptr;
+    // packed results (ft8rx_set_packed_output): the caller's buffer (as a device address), a page-locked mirror of its header, and
+    // ft8rx_packed_output_fence's event: the consumer's "done reading this buffer"
+    bool packed = false;
+    unsigned char* pk_buf = nullptr; hipEvent_t pk_fence = nullptr;
+    ft8rx_packed_header* h_pkhdr = nullptr; ft8rx_packed_header* d_pkhdr = nullptr;
+    // recall (ft8rx_set_recall): the batch's entry copy and results
+    bool recall = false;
+    ft8rx_recall_entry* d_rc_ent = nullptr; int32_t* d_rc_cnt = nullptr; ft8rx_record* d_rc_rec = nullptr;
+    ft8rx_record* h_rc_rec = nullptr; int32_t* h_rc_cnt = nullptr;
+    // measured reports (ft8rx_set_reports): [max_frames][stride] on the device
+    bool reports = false;
+    ft8rx_report* d_rp = nullptr; ft8rx_report* h_rp = nullptr;
+};
+
+static ApCalls ap_calls_off() { ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = FT8RX_AP_MAX_HD_DEFAULT; return a; }
+
+struct ft8rx_handle {
+    ft8rx_config cfg = {};
+    int device = 0, max_frames = 0;
+    hipStream_t stream = nullptr;
+    int n_streams = 2;                   // chunks of a batch run their kernel chains on separate streams
+    int ladder_mode = 0;                 // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
+    int msg_types = 0;                   // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
+    // opt-in weak mode (ft8rx_set_weak; off = the reference's stages)
+    bool weak = false; float weak_sync_min = FT8RX_WEAK_SYNC_MIN_DEFAULT; int32_t weak_osd_max_hd = FT8RX_WEAK_OSD_MAX_HD_DEFAULT;
+    ApCalls ap = ap_calls_off();         // ipass-7 patterns (ft8rx_set_ap_calls; ap.np = 0: off), as the host last set them
+    // the setting's version, and the version each chunk's device copy holds
+    uint32_t ap_version = 0, ap_chunk_version[batchplan::MAX_CHUNKS] = {};
+    ApCalls* d_apc = nullptr;            // [MAX_CHUNKS] per-chunk device copies of `ap`, written on the chunk's stream (enqueue_chain)
+    int32_t* d_apcount = nullptr;        // [MAX_CHUNKS][2] ipass-7 list lengths per chunk: candidates, OSD attempts
+    // recall (ft8rx_set_recall, kernels/recall.hpp; allocated on first use): the pending entries of the next batch and its per-frame
+    // triple offsets (host copy rc_off) and the forced fine sync's scratch; the batch's entry copy and results are its ResultSlot's
+    bool rc_armed = false; int rc_frames = 0; bool rc_td = false; std::vector<int32_t> rc_off;
+    int32_t rc_max_hd = FT8RX_RECALL_MAX_HD_DEFAULT, rc_min_gap = FT8RX_RECALL_MIN_GAP_DEFAULT;
+    ft8rx_recall_entry* d_rc_src = nullptr; int32_t* d_rc_srccnt = nullptr; int32_t* d_rc_off = nullptr;
+    int32_t* d_rc_trip = nullptr; int32_t* d_rc_tout = nullptr; float* d_rc_tsd = nullptr; float* d_rc_sgrid = nullptr; float* d_rc_llr = nullptr;
+    // measured reports (ft8rx_set_reports, kernels/report.hpp; allocated at the first ft8rx_set_reports(h, 1)): the work list of the
+    // DECODED slots ([max_frames][stride] ids, a counter per chunk); the reports themselves are the ResultSlot's
+    bool reports = false;
+    int32_t* d_rp_items = nullptr; int32_t* d_rp_count = nullptr;
+    int sub_frames = FT8RX_SUBBATCH_DEFAULT;     // frames per kernel chain inside a chunk (ft8rx_set_subbatch; 0 = the whole chunk in one chain)
+    hipStream_t sub[batchplan::MAX_STREAMS] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[batchplan::MAX_STREAMS] = {};
+    hipStream_t copy_s = nullptr;    // host-to-device chunk copies of ft8rx_decode_batch, in order, never queued behind kernels
+    hipEvent_t ev_chunk[batchplan::MAX_CHUNKS] = {};
+    Tables T = {};
+    std::vector<void*> allocs;
+    struct Chunk { void* p; size_t cap, used; };
+    std::vector<Chunk> arena;        // scratch of the stage entry points (struct Scratch)
+    int16_t* d_audio = nullptr;  // staging for host-pointer entry points
+    int16_t* d_audio2 = nullptr; // second staging buffer (allocated on first use): ft8rx_enqueue_batch_host double-buffers the H2D copies
+    hipStream_t h2d_s = nullptr; // host-to-device copies of the pipelined host entry: never queued behind kernels or result copies
+    float* d_grid = nullptr;
+    float* d_best_score = nullptr; int32_t* d_best_h0 = nullptr;
+    // slot 0's device buffers under the names the stage entry points use
+    ft8rx_record* d_rec = nullptr; int32_t* d_ncand = nullptr; ft8rx_event* d_ev = nullptr; int32_t* d_evcount = nullptr;
+    float* d_llr0 = nullptr; float* d_saved = nullptr;
+    Att *d_att0 = nullptr, *d_attG = nullptr, *d_attB = nullptr, *d_attO = nullptr;
+    cpx *d_A = nullptr, *d_spec = nullptr;
+    const uint32_t* d_trials = nullptr; int n_trials = 0;      // OSD trial list of this configuration
+    int32_t* d_work[WL_N] = {};                  // ladder work lists (kernels/common.hpp: WorkList), [B][stride] candidate ids each
+    int32_t* d_wcount = nullptr;                 // [MAX_CHUNKS][WL_N] list lengths, zeroed at the head of every chunk's chain
+    uint8_t* d_colmask = nullptr; bool use_mask = false;      // [B][NF0MAX] search mask of the local re-search (ft8rx_set_search_mask), allocated on first use
+    ResultSlot slots[2];
+    // the slot the next batch writes, the oldest unfetched one, how many are unfetched, the latest batch's, the one fetched last
+    int slot_enq = 0, slot_fetch = 0, inflight = 0, last_slot = -1, fetched_slot = -1;
+    // free-running chunk streams (batch_submit): the chunk chains of consecutive batches follow each other on their own streams
+    // without a per-batch fork / join; need_barrier = something else has used the shared workspaces (or the partition changed) since
+    hipEvent_t ev_cdone[2][batchplan::MAX_STREAMS] = {};
+    bool free_running = false, need_barrier = true; int part_B = 0, part_n = 0;
+    // packed results (ft8rx_set_packed_output): the capacity of each slot's buffer and the scratch of the pack kernels
+    uint64_t pk_cap = 0; uint64_t* d_pkneed = nullptr; int32_t* d_pknrec = nullptr;
+    hipEvent_t d2h_ev[32] = {}; uint32_t d2h_next = 0;      // ft8rx_d2h_async: tickets (a ring of events on the result-copy stream)
     // signal subtraction (extension, allocated on first use): float32 working copy, per-chunk partial sums, GFSK tables
-    float* d_wf; double2* d_part; double* d_pulse; double* d_pc; ft8rx_subsig* d_sigs; int32_t* d_sigcnt; int sig_cap;
-    float2 *d_zdec, *d_model, *d_adec; SubdCtx* d_subctx;      // decimated-baseband refinement (refine = 2), allocated on first use
-    double* d_ones;                                             // refine = 3: an all-ones taper table
+    float* d_wf = nullptr; double2* d_part = nullptr; double* d_pulse = nullptr; double* d_pc = nullptr;
+    ft8rx_subsig* d_sigs = nullptr; int32_t* d_sigcnt = nullptr; int sig_cap = 0;
+    float2 *d_zdec = nullptr, *d_model = nullptr, *d_adec = nullptr; SubdCtx* d_subctx = nullptr;      // decimated-baseband refinement (refine = 2), allocated on first use
+    double* d_ones = nullptr;                                   // refine = 3: an all-ones taper table
     std::string err;
-    bool profiling;
+    bool profiling = false;
     std::vector<hipEvent_t> pev;
     std::vector<const char*> pnames;
-    int n_stage;
-    float stage_ms[24];
+    int n_stage = 0;
+    float stage_ms[24] = {};
 };
+// a chunk index (BatchPlan::cb has MAX_CHUNKS + 1 boundaries) never leaves the per-chunk arrays: d_wcount, d_apc, d_apcount and
+// d_rp_count are allocated with MAX_CHUNKS entries, and a stream index never leaves sub[] / ev_join[] / ev_cdone[][]
+static_assert(sizeof(ft8rx_handle::ev_chunk) / sizeof(hipEvent_t) == batchplan::MAX_CHUNKS &&
+              sizeof(ft8rx_handle::ap_chunk_version) / sizeof(uint32_t) == batchplan::MAX_CHUNKS &&
+              sizeof(batchplan::BatchPlan::cb) / sizeof(int) == batchplan::MAX_CHUNKS + 1 &&
+              batchplan::MAX_CHUNKS == 16 && batchplan::MAX_STREAMS == 8, "per-chunk arrays and the plan's boundaries");
 
 static void set_err(ft8rx_handle* h, const char* fmt, ...) {
     char buf[512];
@@ -264,13 +289,13 @@ struct Scratch {
 };
 
 // Everything that is not a pipelined batch (stage entry points, the synchronous host entry, subtraction, profiling passes) uses the
-// handle's shared workspaces from the main stream; while the chunk streams run free (launch_batch) their work is not ordered
+// handle's shared workspaces from the main stream; while the chunk streams run free (batch_submit) their work is not ordered
 // against the main stream, so such calls first wait until the batches in flight are complete.
 static int quiesce(ft8rx_handle* h, bool next_is_batch = false) {
     // the result copy of the last batch waits for every chunk stream (free-running batches) and still reads the slot's device
     // buffers on the copy stream after a plain one -- either way nothing of a batch is pending once the copy stream is idle.
     // A plain BATCH after a plain batch need not wait on the host at all: its kernels follow the previous ones on the main stream (the
-    // sub-streams were joined into it), it writes the OTHER result slot, and that slot's previous copy is ordered by ev_done[slot] --
+    // sub-streams were joined into it), it writes the OTHER result slot, and that slot's previous copy is ordered by its ev_done --
     // so small pipelined batches (enqueue k + 1 while k's results travel) keep their overlap.
     if (h->free_running || (h->last_slot >= 0 && !next_is_batch)) HIPCHK(h, hipStreamSynchronize(h->copy_s));
     h->free_running = false;
@@ -342,20 +367,14 @@ void ft8rx_destroy(ft8rx_handle* h) {
     for (auto e : h->pev) hipEventDestroy(e);
     for (int k = 0; k < 2; k++) for (int i = 0; i < 8; i++) if (h->ev_cdone[k][i]) hipEventDestroy(h->ev_cdone[k][i]);
     for (int i = 0; i < 32; i++) if (h->d2h_ev[i]) hipEventDestroy(h->d2h_ev[i]);
-    for (int i = 0; i < 16; i++) if (h->ev_chunk[i]) hipEventDestroy(h->ev_chunk[i]);
+    for (hipEvent_t e : h->ev_chunk) if (e) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    for (int k = 0; k < 2; k++) {
-        if (h->ev_comp[k]) hipEventDestroy(h->ev_comp[k]);
-        if (h->ev_done[k]) hipEventDestroy(h->ev_done[k]);
-        if (h->h_rec[k]) hipHostFree(h->h_rec[k]);
-        if (h->h_cnt[k]) hipHostFree(h->h_cnt[k]);
-        if (h->h_ev[k]) hipHostFree(h->h_ev[k]);
-        if (h->h_evc[k]) hipHostFree(h->h_evc[k]);
-        if (h->h_evpacked[k]) hipHostFree(h->h_evpacked[k]);
-        if (h->h_pkhdr[k]) hipHostFree(h->h_pkhdr[k]);
-        if (h->h_rc_rec[k]) hipHostFree(h->h_rc_rec[k]);
-        if (h->h_rc_cnt[k]) hipHostFree(h->h_rc_cnt[k]);
-        if (h->h_rp[k]) hipHostFree(h->h_rp[k]);
+    for (ResultSlot& sl : h->slots) {
+        if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
+        if (sl.ev_done) hipEventDestroy(sl.ev_done);
+        const auto hfree = [](void* p) { if (p) hipHostFree(p); };
+        hfree(sl.h_rec); hfree(sl.h_cnt); hfree(sl.h_ev); hfree(sl.h_evc); hfree(sl.h_evpacked); hfree(sl.h_pkhdr);
+        hfree(sl.h_rc_rec); hfree(sl.h_rc_cnt); hfree(sl.h_rp);
     }
     delete h;
 }
@@ -372,29 +391,7 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_err(nullptr, "ft8rx_create: no HIP device available (this library has no CPU fallback)"); return -3; }
     if (device < 0 || device >= ndev) { set_err(nullptr, "ft8rx_create: device %d out of range (%d devices)", device, ndev); return -1; }
     ft8rx_handle* h = new ft8rx_handle();
-    h->cfg = *cfg; h->device = device; h->max_frames = max_frames; h->stream = nullptr; h->profiling = false; h->n_stage = 0;
-    memset(&h->ap, 0, sizeof(h->ap)); h->ap.max_hd = FT8RX_AP_MAX_HD_DEFAULT; h->ap_version = 0; for (int i = 0; i < 16; i++) h->ap_chunk_version[i] = 0;
-    h->d_apc = nullptr; h->d_apcount = nullptr;
-    h->rc_armed = false; h->rc_frames = 0; h->rc_td = false; h->rc_max_hd = FT8RX_RECALL_MAX_HD_DEFAULT; h->rc_min_gap = FT8RX_RECALL_MIN_GAP_DEFAULT;
-    h->d_rc_src = nullptr; h->d_rc_srccnt = nullptr; h->d_rc_off = nullptr; h->d_rc_trip = nullptr; h->d_rc_tout = nullptr; h->d_rc_tsd = nullptr;
-    h->d_rc_sgrid = nullptr; h->d_rc_llr = nullptr;
-    for (int k = 0; k < 2; k++) { h->d_rc_ent[k] = nullptr; h->d_rc_cnt[k] = nullptr; h->d_rc_rec[k] = nullptr; h->h_rc_rec[k] = nullptr; h->h_rc_cnt[k] = nullptr; h->slot_recall[k] = false; }
-    h->reports = false; h->d_rp_items = nullptr; h->d_rp_count = nullptr;
-    for (int k = 0; k < 2; k++) { h->slot_reports[k] = false; h->d_rp[k] = nullptr; h->h_rp[k] = nullptr; }
-    h->n_streams = 2; h->ladder_mode = 0; h->msg_types = 0; h->weak = false; h->weak_sync_min = FT8RX_WEAK_SYNC_MIN_DEFAULT;
-    h->weak_osd_max_hd = FT8RX_WEAK_OSD_MAX_HD_DEFAULT; h->sub_frames = FT8RX_SUBBATCH_DEFAULT; h->ev_fork = nullptr; for (int i = 0; i < 8; i++) { h->sub[i] = nullptr; h->ev_join[i] = nullptr; }
-    h->copy_s = nullptr; h->slot_evpending[0] = h->slot_evpending[1] = false; h->h2d_s = nullptr; h->d_audio = nullptr; h->d_audio2 = nullptr; for (int i = 0; i < 16; i++) h->ev_chunk[i] = nullptr;
-    for (int k = 0; k < 2; k++) { h->ev_comp[k] = h->ev_done[k] = nullptr; h->h_rec[k] = nullptr; h->h_cnt[k] = nullptr; h->h_ev[k] = nullptr; h->h_evc[k] = nullptr; h->h_evpacked[k] = nullptr; h->d_evpacked[k] = nullptr; h->d_evoffs[k] = nullptr; h->slot_B[k] = 0; }
-    h->slot_enq = h->slot_fetch = h->inflight = 0; h->last_slot = -1;
-    for (int k = 0; k < 2; k++) for (int i = 0; i < 8; i++) h->ev_cdone[k][i] = nullptr;
-    h->free_running = false; h->need_barrier = true; h->part_B = h->part_n = 0;
-    h->d_wf = nullptr; h->d_part = nullptr; h->d_pulse = nullptr; h->d_pc = nullptr; h->d_sigs = nullptr; h->d_sigcnt = nullptr; h->sig_cap = 0;
-    h->d_colmask = nullptr; h->use_mask = false;
-    for (int i = 0; i < 32; i++) h->d2h_ev[i] = nullptr;
-    h->d2h_next = 0;
-    h->pk_buf[0] = h->pk_buf[1] = nullptr; h->pk_cap = 0; h->d_pkneed = nullptr; h->d_pknrec = nullptr; h->fetched_slot = -1;
-    for (int k = 0; k < 2; k++) { h->h_pkhdr[k] = nullptr; h->d_pkhdr[k] = nullptr; h->slot_packed[k] = false; h->pk_fence[k] = nullptr; }
-    h->d_zdec = nullptr; h->d_model = nullptr; h->d_adec = nullptr; h->d_subctx = nullptr; h->d_ones = nullptr;
+    h->cfg = *cfg; h->device = device; h->max_frames = max_frames;
     if (hipSetDevice(device) != hipSuccess || !(h->stream = pool_stream(device, &StreamPool::main, true))) { set_err(nullptr, "ft8rx_create: cannot open device %d", device); delete h; return -2; }
     const size_t B = (size_t)max_frames, S = (size_t)1 << cand_shift(*cfg);      // S: per-frame stride of the per-candidate workspaces
     int rc = 0;
@@ -416,25 +413,26 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     static_assert((size_t)(96000 + FT8RX_SPEC_BINS) * sizeof(cpx) <= (size_t)FT8RX_GRID_ROWS * FT8RX_GRID_COLS * sizeof(float), "scratch A + cycle spectrum fit a frame's grid");
     if (!rc) { h->d_A = reinterpret_cast<cpx*>(h->d_grid); h->d_spec = h->d_A + B * 96000; }
     for (int i = 0; i < WL_N; i++) rc |= dalloc(h, &h->d_work[i], B * S * WL_MULT(i));      // WL_BP0 / WL_OSDNAN list attempts
-    rc |= dalloc(h, &h->d_wcount, (size_t)16 * WL_N);
-    rc |= dalloc(h, &h->d_apc, 16);                  // ft8rx_set_ap_calls allocates nothing: it is called every cycle
-    rc |= dalloc(h, &h->d_apcount, (size_t)16 * 2);
+    rc |= dalloc(h, &h->d_wcount, (size_t)batchplan::MAX_CHUNKS * WL_N);
+    rc |= dalloc(h, &h->d_apc, batchplan::MAX_CHUNKS);       // ft8rx_set_ap_calls allocates nothing: it is called every cycle
+    rc |= dalloc(h, &h->d_apcount, (size_t)batchplan::MAX_CHUNKS * 2);
     rc |= dalloc(h, &h->d_ev, B * FT8RX_EVENT_CAP);
     rc |= dalloc(h, &h->d_evcount, B);
-    h->s_rec[0] = h->d_rec; h->s_ncand[0] = h->d_ncand; h->s_ev[0] = h->d_ev; h->s_evcount[0] = h->d_evcount;
-    rc |= dalloc(h, &h->s_rec[1], B * S);
-    rc |= dalloc(h, &h->s_ncand[1], B);
-    rc |= dalloc(h, &h->s_ev[1], B * FT8RX_EVENT_CAP);
-    rc |= dalloc(h, &h->s_evcount[1], B);
+    ResultSlot* const sl = h->slots;
+    sl[0].rec = h->d_rec; sl[0].ncand = h->d_ncand; sl[0].ev = h->d_ev; sl[0].evcount = h->d_evcount;
+    rc |= dalloc(h, &sl[1].rec, B * S);
+    rc |= dalloc(h, &sl[1].ncand, B);
+    rc |= dalloc(h, &sl[1].ev, B * FT8RX_EVENT_CAP);
+    rc |= dalloc(h, &sl[1].evcount, B);
     const bool ev_compact = B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES;
-    for (int k = 0; k < 2 && ev_compact; k++) rc |= dalloc(h, &h->d_evoffs[k], B + 1);
+    for (int k = 0; k < 2 && ev_compact; k++) rc |= dalloc(h, &sl[k].d_evoffs, B + 1);
     for (int k = 0; k < 2 && !rc; k++) {
-        bool okh = hipHostMalloc((void**)&h->h_rec[k], sizeof(ft8rx_record) * B * cfg->max_cands, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&h->h_cnt[k], sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&h->h_ev[k], sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&h->h_evc[k], sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
-        if (ev_compact) okh = okh && hipHostMalloc((void**)&h->h_evpacked[k], sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess
-                                  && hipHostGetDevicePointer((void**)&h->d_evpacked[k], h->h_evpacked[k], 0) == hipSuccess;
+        bool okh = hipHostMalloc((void**)&sl[k].h_rec, sizeof(ft8rx_record) * B * cfg->max_cands, hipHostMallocDefault) == hipSuccess;
+        okh = okh && hipHostMalloc((void**)&sl[k].h_cnt, sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
+        okh = okh && hipHostMalloc((void**)&sl[k].h_ev, sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess;
+        okh = okh && hipHostMalloc((void**)&sl[k].h_evc, sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
+        if (ev_compact) okh = okh && hipHostMalloc((void**)&sl[k].h_evpacked, sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess
+                                  && hipHostGetDevicePointer((void**)&sl[k].d_evpacked, sl[k].h_evpacked, 0) == hipSuccess;
         if (!okh) { set_err(h, "ft8rx_create: page-locked result buffers (%zu frames) could not be allocated", B); rc = -2; }
     }
     if (rc) { g_create_err = h->err; ft8rx_destroy(h); return -2; }
@@ -555,18 +553,18 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     if (hipStreamSynchronize(h->stream) != hipSuccess) { set_err(nullptr, "ft8rx_create: init kernel failed"); ft8rx_destroy(h); return -2; }
     bool okc = true;
     for (int i = 0; i < 24; i++) { hipEvent_t e = nullptr; okc = okc && hipEventCreate(&e) == hipSuccess; if (e) h->pev.push_back(e); }
-    // (the chunk streams h->sub[] are created on first use, launch_batch: every stream that exists competes for one of the
-    // runtime's four hardware queues, see the note there)
+    // (the chunk streams h->sub[] are created on first use, batch_begin: every stream that exists competes for one of the
+    // runtime's four hardware queues, see the note in batch_plan.hpp)
     // (measurement aid: FT8RX_SUBS_FIRST=n creates n chunk streams BEFORE the copy streams, i.e. gives them hardware queues of their own
     // -- for A/B runs of three or four chunk streams, profiles/r06_notes.md)
     if (const char* e = getenv("FT8RX_SUBS_FIRST")) for (int i = 0; i < atoi(e) && i < 8; i++) pool_sub(device, i);
     okc = okc && (h->copy_s = pool_stream(device, &StreamPool::copy, false)) != nullptr;
     okc = okc && (h->h2d_s = pool_stream(device, &StreamPool::h2d, false)) != nullptr;
-    for (int i = 0; i < 16; i++) okc = okc && hipEventCreateWithFlags(&h->ev_chunk[i], hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t& e : h->ev_chunk) okc = okc && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     okc = okc && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < 2; k++) {
-        okc = okc && hipEventCreateWithFlags(&h->ev_comp[k], hipEventDisableTiming) == hipSuccess;
-        okc = okc && hipEventCreateWithFlags(&h->ev_done[k], hipEventDisableTiming) == hipSuccess;
+    for (ResultSlot& s : h->slots) {
+        okc = okc && hipEventCreateWithFlags(&s.ev_comp, hipEventDisableTiming) == hipSuccess;
+        okc = okc && hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming) == hipSuccess;
     }
     if (!okc) { set_err(nullptr, "ft8rx_create: cannot create HIP streams/events"); ft8rx_destroy(h); return -2; }
     *out = h;
@@ -667,6 +665,7 @@ static void launch_reports(ft8rx_handle* h, int B, const cpx* spec, const ft8rx_
 }
 
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
+    const ResultSlot& sl = h->slots[slot];
     const bool weak = h->weak;                                     // the setting this batch was enqueued with
     const ft8rx_config cw = weak ? weak_config(h) : h->cfg;
     const ft8rx_config& c = weak ? cw : h->cfg;
@@ -675,11 +674,11 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     const int16_t* audio = d_audio + F * FT8RX_NSAMP;
     float* grid = h->d_grid + F * FT8RX_GRID_ROWS * FT8RX_GRID_COLS;
     float* bs = h->d_best_score + F * NF0MAX; int32_t* bh = h->d_best_h0 + F * NF0MAX;
-    ft8rx_record* rec = h->s_rec[slot] + FS; int32_t* ncand = h->s_ncand[slot] + F;
+    ft8rx_record* rec = sl.rec + FS; int32_t* ncand = sl.ncand + F;
     float* llr0 = h->d_llr0 + FS * 174; float* saved = h->d_saved + FS * 5 * 174;
     Att* att0 = h->d_att0 + FS * 5; Att* attG = h->d_attG + FS * 2; Att* attB = h->d_attB + FS * 5; Att* attO = h->d_attO + FS * 10;
     cpx* A = reinterpret_cast<cpx*>(grid); cpx* spec = A + (size_t)B * 96000;      // inside this chunk's (by then dead) grid region, see ft8rx_create
-    ft8rx_event* ev = h->s_ev[slot] + F * FT8RX_EVENT_CAP; int32_t* evc = h->s_evcount[slot] + F;
+    ft8rx_event* ev = sl.ev + F * FT8RX_EVENT_CAP; int32_t* evc = sl.evcount + F;
 #define STAGE(name) do { if (prof) { hipEventRecord(h->pev[h->pnames.size()], s); h->pnames.push_back(name); } } while (0)
     int32_t* wc = h->d_wcount + WL_N * chunk;                      // (evc and wc are zeroed by k_topk)
     WorkList wl[WL_N];
@@ -742,13 +741,13 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
         }
         launch_ap_calls(h, B, llr0, rec, ncand, attO, ev, evc, wl[WL_BP0].items, wl[WL_OSDNAN].items, h->d_apcount + 2 * chunk, apc, s);
     }
-    if (h->slot_recall[slot]) {
+    if (sl.recall) {
         // ipass 8 (ft8rx_set_recall, kernels/recall.hpp), after the whole ladder: it reads the ladder's records (skip rule), and the
         // cycle spectrum it resamples still lies in this chunk's grid region -- only the next batch's k_spectrogram overwrites it
         STAGE("recall");
-        ft8rx_recall_entry* ent = h->d_rc_ent[slot] + F * FT8RX_RECALL_MAX;
-        int32_t* rcnt = h->d_rc_cnt[slot] + F;
-        k_recall_stage<<<B, FT8RX_RECALL_MAX, 0, s>>>(h->d_rc_src + F * FT8RX_RECALL_MAX, h->d_rc_srccnt + F, ent, rcnt, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
+        ft8rx_recall_entry* ent = sl.d_rc_ent + F * FT8RX_RECALL_MAX;
+        int32_t* rcnt = sl.d_rc_cnt + F;
+        k_recall_stage<<<B, FT8RX_RECALL_MAX, 0, s>>>(h->d_rc_src + F * FT8RX_RECALL_MAX, h->d_rc_srccnt + F, ent, rcnt, sl.d_rc_rec + F * FT8RX_RECALL_MAX);
         const int base = h->rc_off[F], n = h->rc_off[F + B] - base;
         if (n > 0) {
             k_recall_trip<<<B, FT8RX_RECALL_MAX, 0, s>>>(ent, rcnt, h->d_rc_off + F, h->d_rc_trip);
@@ -756,14 +755,14 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
             launch_fine(h, c, false, n, s, spec, nullptr, nullptr, h->d_rc_llr + b * 174, h->d_rc_trip + 3 * b, h->d_rc_tout + 5 * b,
                         h->d_rc_tsd + b, h->d_rc_sgrid + b * 632, WorkList{nullptr, nullptr}, h->rc_td);     // rc_td: an entry beyond k_fine's h0 range
             k_recall_score<<<n, 64, 0, s>>>(h->d_rc_sgrid, h->d_rc_tout, h->d_rc_trip, h->d_rc_off + F, base, ent, rec, ncand, sh,
-                                            h->rc_max_hd, h->rc_min_gap, h->d_rc_rec[slot] + F * FT8RX_RECALL_MAX);
+                                            h->rc_max_hd, h->rc_min_gap, sl.d_rc_rec + F * FT8RX_RECALL_MAX);
         }
     }
-    if (h->slot_reports[slot]) {
+    if (sl.reports) {
         // measured reports (ft8rx_set_reports, kernels/report.hpp), after the last ladder step: the records are final, and the cycle
         // spectrum still lies in this chunk's grid region (as recall relies on)
         STAGE("report");
-        launch_reports(h, B, spec, rec, ncand, h->d_rp_items + FS, h->d_rp_count + chunk, h->d_rp[slot] + FS, s);
+        launch_reports(h, B, spec, rec, ncand, h->d_rp_items + FS, h->d_rp_count + chunk, sl.d_rp + FS, s);
     }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
@@ -780,206 +779,193 @@ static void enqueue_chunk(ft8rx_handle* h, const int16_t* d_audio, int f0, int n
     for (int o = 0; o < n; o += sub) enqueue_chain(h, d_audio, f0 + o, (o + sub <= n) ? sub : n - o, s, false, slot, chunk);
 }
 
-// Launch one batch: audio either resident on the device (host_audio == nullptr) or copied from the host in chunks.
-//   profiling mode / small batches: one chain on the main stream (per-stage events bracket whole-batch launches);
-//   otherwise the batch is cut into chunks whose chains overlap on the sub-streams -- the ladder kernels (BP, OSD, fine sync)
-//   are latency bound, so chunks fill each other's stalls.  Host audio uses twice as many chunks; their copies run in order on
-//   the dedicated copy stream (never queued behind kernels, so a pageable-memory copy blocks the host only for its own
-//   duration) and each chunk's chain waits for its copy's event.
-// When the kernels are done the copy stream moves the slot's results into the page-locked host buffers.
-// pipelined = true (ft8rx_enqueue_batch_host): the audio is staged in the buffer of this batch's result slot and its copies run on
-// their own stream, gated only by the previous user of that staging buffer (two batches ago), so they overlap the kernels of
+// Launch one batch: audio either resident on the device (Entry DEVICE) or copied from the host, in chunks (HOST_SYNC) or staged in
+// the buffer of the batch's result slot (HOST_PIPELINED).  batch_plan.hpp decides how the batch is cut and ordered (one chain on the
+// main stream, fork / join over the chunk streams, or free-running chunk streams) and says why.  Host audio of the synchronous entry
+// is copied chunk by chunk in order on the dedicated copy stream (never queued behind kernels, so a pageable-memory copy blocks the
+// host only for its own duration) and each chunk's chain waits for its copy's event.
+// When the kernels are done the copy stream moves the slot's results into the page-locked host buffers (batch_finish).
+// HOST_PIPELINED (ft8rx_enqueue_batch_host): the audio is staged in the buffer of this batch's result slot and its copy runs on
+// its own stream, gated only by the previous user of that staging buffer (two batches ago), so it overlaps the kernels of
 // the batch before.
-static int launch_batch(ft8rx_handle* h, const int16_t* d_audio, const int16_t* host_audio, int B, bool pipelined = false) {
-    HIPCHK(h, hipSetDevice(h->device));
+using batchplan::BatchPlan;
+using batchplan::Entry;
+
+// Prologue: the result slot is taken (with both taken, the oldest unfetched batch is dropped), the per-batch settings are consumed,
+// a host entry gets its staging buffer (*stage; a pipelined one waits for that buffer's last reader), and the chunk streams of a
+// chunked batch are created on first use
+static int batch_begin(ft8rx_handle* h, Entry e, int B, int slot, bool chunked, int16_t** stage) {
+    ResultSlot& sl = h->slots[slot];
     h->pnames.clear();
     if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
-    const int slot = h->slot_enq;
-    if (host_audio && need_staging(h)) return -2;
+    if (e != batchplan::DEVICE && need_staging(h)) return -2;
     if (h->rc_armed && B != h->rc_frames) { set_err(h, "recall entries were set for %d frames, the batch has %d", h->rc_frames, B); return -1; }
-    h->slot_recall[slot] = h->rc_armed;          // ft8rx_set_recall: consumed by this batch
+    sl.recall = h->rc_armed;                     // ft8rx_set_recall: consumed by this batch
     h->rc_armed = false;
-    h->slot_reports[slot] = h->reports;          // ft8rx_set_reports: the setting this batch is enqueued with
-    int16_t* stage = h->d_audio;
-    hipStream_t cs = h->copy_s;
-    if (pipelined) {
+    sl.reports = h->reports;                     // ft8rx_set_reports: the setting this batch is enqueued with
+    *stage = h->d_audio;
+    if (e == batchplan::HOST_PIPELINED) {
         if (slot == 1 && !h->d_audio2 && dalloc(h, &h->d_audio2, (size_t)h->max_frames * FT8RX_NSAMP)) return -2;
-        stage = slot ? h->d_audio2 : h->d_audio;
-        d_audio = stage;
-        cs = h->h2d_s;
-        HIPCHK(h, hipStreamWaitEvent(cs, h->ev_comp[slot], 0));             // the kernels that last read this staging buffer are done
+        *stage = slot ? h->d_audio2 : h->d_audio;
+        HIPCHK(h, hipStreamWaitEvent(h->h2d_s, sl.ev_comp, 0));             // the kernels that last read this staging buffer are done
     }
-    // synchronous host entry: twice as many chunks, so that the first kernels start after 1/8 of the copy; the pipelined entry's copies
-    // already overlap the previous batch, so it keeps the 4 larger chunks of the device-resident path
-    int nc = h->profiling ? 1 : ((host_audio && !pipelined) ? 2 * h->n_streams : h->n_streams);
-    if (nc > B / 8) nc = B / 8;
-    // Chunk k runs on stream k % n_streams, where stream 0 IS the handle's main stream and streams 1.. are the (lazily created)
-    // sub-streams.  The HIP runtime maps all streams of a process onto four hardware queues, and commands of streams that share
-    // one execute in submission order: with a main stream that only forks and joins plus two chunk streams plus the two copy
-    // streams (five), the H2D stream shared a queue with a chunk stream and its event markers waited behind that chunk's kernels --
-    // in the rocprofv3 trace the second H2D chunk of the pipelined host entry started only when the previous batch's last kernel
-    // had finished (profiles/archive/r03_notes.md).  Four streams in use = a queue each.
-    const int ns = h->n_streams;
-    for (int i = 1; i < ns && nc > 1; i++) if (!h->sub[i - 1]) {
+    for (int i = 1; i < h->n_streams && chunked; i++) if (!h->sub[i - 1]) {
         if (!(h->sub[i - 1] = pool_sub(h->device, i - 1))) { set_err(h, "cannot create a chunk stream"); return -2; }
         HIPCHK(h, hipEventCreateWithFlags(&h->ev_join[i - 1], hipEventDisableTiming));
     }
+    return 0;
+}
+
+// Submission: the plan's chunks, chunk k on stream k % n_streams (stream 0 = the main stream).  audio: on the device for Entry
+// DEVICE, else on the host and copied to `stage` first, on `cs`.  The mode decides what precedes the chunks, what each chunk waits
+// for, whether an empty chunk is skipped, and what follows them.
+static int batch_submit(ft8rx_handle* h, const BatchPlan& plan, Entry e, int slot, const int16_t* audio, int16_t* stage) {
+    ResultSlot& sl = h->slots[slot];
+    const bool host = e != batchplan::DEVICE;
+    const int16_t* d_audio = host ? stage : audio; const int16_t* host_audio = host ? audio : nullptr;
+    const int ns = h->n_streams, nc = plan.nc, B = plan.cb[nc];
+    const bool free_run = plan.mode == batchplan::FREE_RUN, pipelined = e == batchplan::HOST_PIPELINED, sync_host = e == batchplan::HOST_SYNC;
+    hipStream_t cs = pipelined ? h->h2d_s : h->copy_s;
+    const size_t frame_bytes = sizeof(int16_t) * (size_t)FT8RX_NSAMP;
     auto chunk_stream = [&](int k) { const int i = k % ns; return i == 0 ? h->stream : h->sub[i - 1]; };
-    // Free-running chunk streams: with the audio resident (or staged by the pipelined host entry) and one chunk per stream, chunk i of
-    // batch k+1 simply follows chunk i of batch k on stream i.  Every workspace is indexed by frame, so a stream only ever touches
-    // its own frame range and in-stream order is all the ordering the chains need; only the result copy waits for all of them.
-    // Without the per-batch fork / join a stream that finishes its half early starts on the next batch while the other one is still
-    // in its tail.  Anything else that uses the workspaces (stage entry points, the synchronous entry, a different partition)
-    // goes through quiesce() / need_barrier.
-    // (A/B on one box, profiles/archive/r03_notes.md: 48 498 -> 49 001 frames/s end to end, 48 167 -> 48 894 including H2D.)
-    const bool free_run = !h->profiling && nc > 1 && nc == ns && !(host_audio && !pipelined);
     if (free_run) {
         for (int i = 0; i < ns; i++) for (int k = 0; k < 2; k++)
             if (!h->ev_cdone[k][i]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_cdone[k][i], hipEventDisableTiming));
-        const int per = (B + nc - 1) / nc;
         if (h->need_barrier || h->part_B != B || h->part_n != nc) {
             // first batch of a run (or another partition): everything issued so far, on any stream of this handle, first
-            if (h->free_running) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_comp[h->last_slot], 0));
+            if (h->free_running) HIPCHK(h, hipStreamWaitEvent(h->stream, h->slots[h->last_slot].ev_comp, 0));
             HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
             for (int i = 1; i < ns; i++) HIPCHK(h, hipStreamWaitEvent(h->sub[i - 1], h->ev_fork, 0));
             h->need_barrier = false; h->part_B = B; h->part_n = nc;
         }
-        if (pipelined) {
-            HIPCHK(h, hipMemcpyAsync(stage, host_audio, sizeof(int16_t) * (size_t)B * FT8RX_NSAMP, hipMemcpyHostToDevice, cs));
-            HIPCHK(h, hipEventRecord(h->ev_chunk[0], cs));
+    } else {
+        { const int q = quiesce(h, true); if (q) return q; }
+        HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_done, 0));            // the slot's previous results have left the device
+        if (plan.mode == batchplan::SINGLE) {
+            if (host_audio) HIPCHK(h, hipMemcpyAsync(stage, host_audio, frame_bytes * B, hipMemcpyHostToDevice, h->stream));
+            if (h->profiling) enqueue_chain(h, d_audio, 0, B, h->stream, true, slot, 0);      // per-stage events bracket whole-batch launches
+            else enqueue_chunk(h, d_audio, 0, B, h->stream, slot, 0);
+            return 0;
         }
-        for (int k = 0; k < nc; k++) {
-            const int f0 = k * per, n = (f0 + per <= B) ? per : B - f0;
-            hipStream_t s = chunk_stream(k);
-            HIPCHK(h, hipStreamWaitEvent(s, h->ev_done[slot], 0));          // the slot's previous results have left the device
+        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+        if (sync_host) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_fork, 0));
+        for (int i = 1; i < ns; i++) HIPCHK(h, hipStreamWaitEvent(h->sub[i - 1], h->ev_fork, 0));
+    }
+    if (pipelined) {
+        // ONE copy for the whole batch and one event: it has the whole previous batch to hide behind, and a copy stream with
+        // event markers BETWEEN its copies can stall on them (markers are queue packets: in a hardware queue shared with a
+        // chunk stream they wait their turn behind that chunk's kernels -- the second of two chunk copies then started only
+        // at the end of the previous batch, rocprofv3 trace in profiles/archive/r03_notes.md)
+        HIPCHK(h, hipMemcpyAsync(stage, host_audio, frame_bytes * B, hipMemcpyHostToDevice, cs));
+        HIPCHK(h, hipEventRecord(h->ev_chunk[0], cs));
+        if (!free_run) for (int i = 0; i < ns; i++) HIPCHK(h, hipStreamWaitEvent(chunk_stream(i), h->ev_chunk[0], 0));
+    }
+    for (int k = 0; k < nc; k++) {
+        const int f0 = plan.cb[k], n = plan.cb[k + 1] - f0;
+        if (n <= 0 && !free_run) continue;
+        hipStream_t s = chunk_stream(k);
+        if (free_run) {
+            HIPCHK(h, hipStreamWaitEvent(s, sl.ev_done, 0));                // the slot's previous results have left the device
             if (pipelined) HIPCHK(h, hipStreamWaitEvent(s, h->ev_chunk[0], 0));
-            if (n > 0) enqueue_chunk(h, d_audio, f0, n, s, slot, k);
+        } else if (sync_host) {
+            HIPCHK(h, hipMemcpyAsync(stage + (size_t)f0 * FT8RX_NSAMP, host_audio + (size_t)f0 * FT8RX_NSAMP, frame_bytes * n, hipMemcpyHostToDevice, cs));
+            HIPCHK(h, hipEventRecord(h->ev_chunk[k], cs));
+            HIPCHK(h, hipStreamWaitEvent(s, h->ev_chunk[k], 0));
+        }
+        if (n > 0) enqueue_chunk(h, d_audio, f0, n, s, slot, k);
+        if (free_run) {                                                     // only the result copy waits for every chunk
             HIPCHK(h, hipEventRecord(h->ev_cdone[slot][k], s));
             HIPCHK(h, hipStreamWaitEvent(h->copy_s, h->ev_cdone[slot][k], 0));
         }
-        h->free_running = true;
-    } else {
-    { const int q = quiesce(h, true); if (q) return q; }
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[slot], 0));          // the slot's previous results have left the device
-    if (nc <= 1) {
-        if (host_audio) HIPCHK(h, hipMemcpyAsync(stage, host_audio, sizeof(int16_t) * (size_t)B * FT8RX_NSAMP, hipMemcpyHostToDevice, h->stream));
-        if (h->profiling) enqueue_chain(h, d_audio, 0, B, h->stream, true, slot, 0);      // per-stage events bracket whole-batch launches
-        else enqueue_chunk(h, d_audio, 0, B, h->stream, slot, 0);
-    } else {
-        HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
-        if (host_audio && !pipelined) HIPCHK(h, hipStreamWaitEvent(cs, h->ev_fork, 0));
-        for (int i = 1; i < ns; i++) HIPCHK(h, hipStreamWaitEvent(h->sub[i - 1], h->ev_fork, 0));
-        const int per = (B + nc - 1) / nc;
-        // chunk boundaries: equal parts, except for the synchronous host entry, whose first kernels can only start when the first
-        // chunk's audio has crossed PCIe -- there the chunks grow geometrically (B/8, B/8, B/4, B/2 for four): the first copy is
-        // half as long and the large chunks, which run most efficiently, come last (38.8 k -> 40.5 k frames/s for 256-frame calls;
-        // other layouts -- 16/48/64/128, three streams, five or six chunks -- all land between 38 k and 41.5 k)
-        int cb[17];
-        for (int k = 0; k <= nc; k++) cb[k] = (k * per < B) ? k * per : B;
-        if (host_audio && !pipelined && nc >= 3 && B >= 8 * nc) {
-            int left = B;
-            for (int k = nc - 1; k >= 1; k--) { const int n = left / 2; cb[k] = left - n; left -= n; }
-            cb[0] = 0; cb[nc] = B;
-        }
-        if (pipelined) {
-            // ONE copy for the whole batch and one event: it has the whole previous batch to hide behind, and a copy stream with
-            // event markers BETWEEN its copies can stall on them (markers are queue packets: in a hardware queue shared with a
-            // chunk stream they wait their turn behind that chunk's kernels -- the second of two chunk copies then started only
-            // at the end of the previous batch, rocprofv3 trace in profiles/archive/r03_notes.md)
-            HIPCHK(h, hipMemcpyAsync(stage, host_audio, sizeof(int16_t) * (size_t)B * FT8RX_NSAMP, hipMemcpyHostToDevice, cs));
-            HIPCHK(h, hipEventRecord(h->ev_chunk[0], cs));
-            for (int i = 0; i < ns; i++) HIPCHK(h, hipStreamWaitEvent(chunk_stream(i), h->ev_chunk[0], 0));
-        }
-        for (int k = 0; k < nc; k++) {
-            const int f0 = cb[k], n = cb[k + 1] - cb[k];
-            if (n <= 0) continue;
-            hipStream_t s = chunk_stream(k);
-            if (host_audio && !pipelined) {
-                HIPCHK(h, hipMemcpyAsync(stage + (size_t)f0 * FT8RX_NSAMP, host_audio + (size_t)f0 * FT8RX_NSAMP,
-                                         sizeof(int16_t) * (size_t)n * FT8RX_NSAMP, hipMemcpyHostToDevice, cs));
-                HIPCHK(h, hipEventRecord(h->ev_chunk[k], cs));
-                HIPCHK(h, hipStreamWaitEvent(s, h->ev_chunk[k], 0));
-            }
-            enqueue_chunk(h, d_audio, f0, n, s, slot, k);
-        }
-        for (int i = 1; i < ns; i++) {
-            HIPCHK(h, hipEventRecord(h->ev_join[i - 1], h->sub[i - 1]));
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[i - 1], 0));
-        }
     }
+    if (free_run) h->free_running = true;
+    else for (int i = 1; i < ns; i++) {
+        HIPCHK(h, hipEventRecord(h->ev_join[i - 1], h->sub[i - 1]));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join[i - 1], 0));
     }
-    HIPCHK(h, hipGetLastError());
-    // results -> page-locked host buffers on the copy stream (overlaps the next batch, which computes into the other slot).
-    // fin = the stream on which "all kernels of this batch are done" is known: the main stream after its joins, or -- free-running
-    // chunks -- the copy stream, which has just been made to wait for every chunk
-    const int mc = h->cfg.max_cands;
-    hipStream_t fin = free_run ? h->copy_s : h->stream;
-    if (h->d_evpacked[slot] && (size_t)B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES) {      // pack the event log (see the copy below)
-        k_ev_scan<<<1, 1024, 0, fin>>>(h->s_evcount[slot], B, h->d_evoffs[slot]);
-        k_ev_compact<<<B, 64, 0, fin>>>(h->s_ev[slot], h->s_evcount[slot], h->d_evoffs[slot], h->d_evpacked[slot]);
-    }
-    h->slot_packed[slot] = h->pk_buf[slot] != nullptr;
-    if (h->slot_packed[slot]) {                              // packed results for a gather: header | frame table | kept records | used events
-        if (h->pk_fence[slot]) { HIPCHK(h, hipStreamWaitEvent(fin, h->pk_fence[slot], 0)); h->pk_fence[slot] = nullptr; }      // the consumer's asynchronous read of this buffer
-        k_pack_count<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ncand[slot], h->s_ev[slot], h->s_evcount[slot], h->d_pkneed, h->d_pknrec, cand_shift(h->cfg));
-        k_pack_scan<<<1, 1024, 0, fin>>>(h->d_pknrec, h->s_ncand[slot], h->s_evcount[slot], B, mc, (unsigned long long)h->pk_cap, h->pk_buf[slot], h->d_pkhdr[slot]);
-        k_pack_write<<<B, 256, 0, fin>>>(h->s_rec[slot], h->s_ev[slot], h->d_pkneed, B, h->pk_buf[slot], cand_shift(h->cfg));
-    }
-    HIPCHK(h, hipEventRecord(h->ev_comp[slot], fin));
-    if (!free_run) HIPCHK(h, hipStreamWaitEvent(h->copy_s, h->ev_comp[slot], 0));
-    HIPCHK(h, hipMemcpyAsync(h->h_cnt[slot], h->s_ncand[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
-    HIPCHK(h, hipMemcpy2DAsync(h->h_rec[slot], sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) << cand_shift(h->cfg),
-                               sizeof(ft8rx_record) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
-    HIPCHK(h, hipMemcpyAsync(h->h_evc[slot], h->s_evcount[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
+    return 0;
+}
+
+// Result tail: results -> page-locked host buffers on the copy stream (overlaps the next batch, which computes into the other slot).
+// fin = the stream on which "all kernels of this batch are done" is known: the main stream after its joins, or -- free-running
+// chunks -- the copy stream, which has just been made to wait for every chunk
+static int batch_finish(ft8rx_handle* h, int slot, int B, hipStream_t fin) {
+    ResultSlot& sl = h->slots[slot];
+    const int mc = h->cfg.max_cands, sh = cand_shift(h->cfg);
     // The event log is [B][FT8RX_EVENT_CAP] x 24 B = 12 KB per frame of which a frame typically uses a tenth (config 1: ~40 events).
-    // Small batches copy it whole (the latency case).  Large ones were packed above: k_ev_compact has already written the used
-    // entries -- and nothing else -- into page-locked host memory: ~8 MB instead of 100 MB per 8192-frame shard on the host link.
+    // Small batches copy it whole (the latency case).  Large ones are packed: k_ev_compact writes the used entries -- and nothing
+    // else -- into page-locked host memory: ~8 MB instead of 100 MB per 8192-frame shard on the host link.
     // (A copy-engine transfer of the packed run is not an option: an asynchronous device-to-host copy of a few hundred KB takes the
     // runtime's shader-copy path, which queued behind the next batch's kernels and cost 0.5 ms per 256-frame step.)
-    h->slot_evpending[slot] = h->d_evpacked[slot] && (size_t)B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES;
-    if (!h->slot_evpending[slot])
-        HIPCHK(h, hipMemcpyAsync(h->h_ev[slot], h->s_ev[slot], sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToHost, h->copy_s));
-    if (h->slot_recall[slot]) {
-        HIPCHK(h, hipMemcpyAsync(h->h_rc_cnt[slot], h->d_rc_cnt[slot], sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
-        HIPCHK(h, hipMemcpyAsync(h->h_rc_rec[slot], h->d_rc_rec[slot], sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)B, hipMemcpyDeviceToHost, h->copy_s));
+    const bool pack_events = sl.d_evpacked && (size_t)B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES;
+    if (pack_events) {
+        k_ev_scan<<<1, 1024, 0, fin>>>(sl.evcount, B, sl.d_evoffs);
+        k_ev_compact<<<B, 64, 0, fin>>>(sl.ev, sl.evcount, sl.d_evoffs, sl.d_evpacked);
     }
-    if (h->slot_reports[slot])
-        HIPCHK(h, hipMemcpy2DAsync(h->h_rp[slot], sizeof(ft8rx_report) * mc, h->d_rp[slot], sizeof(ft8rx_report) << cand_shift(h->cfg),
-                                   sizeof(ft8rx_report) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
-    HIPCHK(h, hipEventRecord(h->ev_done[slot], h->copy_s));
-    h->slot_B[slot] = B; h->last_slot = slot; h->slot_enq ^= 1; h->inflight++;
+    sl.packed = sl.pk_buf != nullptr;
+    if (sl.packed) {                                         // packed results for a gather: header | frame table | kept records | used events
+        if (sl.pk_fence) { HIPCHK(h, hipStreamWaitEvent(fin, sl.pk_fence, 0)); sl.pk_fence = nullptr; }      // the consumer's asynchronous read of this buffer
+        k_pack_count<<<B, 256, 0, fin>>>(sl.rec, sl.ncand, sl.ev, sl.evcount, h->d_pkneed, h->d_pknrec, sh);
+        k_pack_scan<<<1, 1024, 0, fin>>>(h->d_pknrec, sl.ncand, sl.evcount, B, mc, (unsigned long long)h->pk_cap, sl.pk_buf, sl.d_pkhdr);
+        k_pack_write<<<B, 256, 0, fin>>>(sl.rec, sl.ev, h->d_pkneed, B, sl.pk_buf, sh);
+    }
+    HIPCHK(h, hipEventRecord(sl.ev_comp, fin));
+    if (fin != h->copy_s) HIPCHK(h, hipStreamWaitEvent(h->copy_s, sl.ev_comp, 0));
+    HIPCHK(h, hipMemcpyAsync(sl.h_cnt, sl.ncand, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
+    HIPCHK(h, hipMemcpy2DAsync(sl.h_rec, sizeof(ft8rx_record) * mc, sl.rec, sizeof(ft8rx_record) << sh, sizeof(ft8rx_record) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
+    HIPCHK(h, hipMemcpyAsync(sl.h_evc, sl.evcount, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
+    sl.evpending = pack_events;
+    if (!pack_events) HIPCHK(h, hipMemcpyAsync(sl.h_ev, sl.ev, sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToHost, h->copy_s));
+    if (sl.recall) {
+        HIPCHK(h, hipMemcpyAsync(sl.h_rc_cnt, sl.d_rc_cnt, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->copy_s));
+        HIPCHK(h, hipMemcpyAsync(sl.h_rc_rec, sl.d_rc_rec, sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)B, hipMemcpyDeviceToHost, h->copy_s));
+    }
+    if (sl.reports)
+        HIPCHK(h, hipMemcpy2DAsync(sl.h_rp, sizeof(ft8rx_report) * mc, sl.d_rp, sizeof(ft8rx_report) << sh, sizeof(ft8rx_report) * mc, B, hipMemcpyDeviceToHost, h->copy_s));
+    HIPCHK(h, hipEventRecord(sl.ev_done, h->copy_s));
+    sl.B = B; h->last_slot = slot; h->slot_enq ^= 1; h->inflight++;
     return 0;
+}
+
+// audio: on the device for Entry DEVICE, else on the host
+static int launch_batch(ft8rx_handle* h, Entry e, const int16_t* audio, int B) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const BatchPlan plan = batchplan::plan_batch(B, h->n_streams, h->profiling, e);
+    const int slot = h->slot_enq;
+    int16_t* stage = nullptr;
+    if (const int rc = batch_begin(h, e, B, slot, plan.mode != batchplan::SINGLE, &stage)) return rc;
+    if (const int rc = batch_submit(h, plan, e, slot, audio, stage)) return rc;
+    HIPCHK(h, hipGetLastError());
+    return batch_finish(h, slot, B, plan.mode == batchplan::FREE_RUN ? h->copy_s : h->stream);
 }
 
 // Large batches: the packed event log (k_ev_compact, written by the GPU into page-locked memory) -> the [frame][FT8RX_EVENT_CAP] rows
 // of h_ev that the fetch functions hand out.  The per-frame counts have arrived, so the host knows each frame's offset in the
 // packed run (the same prefix sum k_ev_scan made).  Rows beyond a frame's count are not written.
-static int fetch_events(ft8rx_handle* h, int slot) {
-    if (!h->slot_evpending[slot]) return 0;
-    const int B = h->slot_B[slot];
+static void fetch_events(ResultSlot& sl) {
+    if (!sl.evpending) return;
     size_t off = 0;
-    for (int f = 0; f < B; f++) {
-        int c = h->h_evc[slot][f]; c = c > FT8RX_EVENT_CAP ? FT8RX_EVENT_CAP : (c < 0 ? 0 : c);
-        if (c) memcpy(h->h_ev[slot] + (size_t)f * FT8RX_EVENT_CAP, h->h_evpacked[slot] + off, sizeof(ft8rx_event) * (size_t)c);
+    for (int f = 0; f < sl.B; f++) {
+        int c = sl.h_evc[f]; c = c > FT8RX_EVENT_CAP ? FT8RX_EVENT_CAP : (c < 0 ? 0 : c);
+        if (c) memcpy(sl.h_ev + (size_t)f * FT8RX_EVENT_CAP, sl.h_evpacked + off, sizeof(ft8rx_event) * (size_t)c);
         off += (size_t)c;
     }
-    h->slot_evpending[slot] = false;
-    return 0;
+    sl.evpending = false;
 }
 
 int ft8rx_enqueue_batch(ft8rx_handle* h, const int16_t* d_audio, int B) {
     if (!h || !d_audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    return launch_batch(h, d_audio, nullptr, B);
+    return launch_batch(h, batchplan::DEVICE, d_audio, B);
 }
 
 int ft8rx_enqueue_batch_host(ft8rx_handle* h, const int16_t* audio, int B) {
     if (!h || !audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch_host: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    return launch_batch(h, nullptr, audio, B, true);
+    return launch_batch(h, batchplan::HOST_PIPELINED, audio, B);
 }
 
-int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > 8) return -1; h->n_streams = n; return 0; }
+int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > batchplan::MAX_STREAMS) return -1; h->n_streams = n; return 0; }
 int ft8rx_set_subbatch(ft8rx_handle* h, int frames) { if (!h || frames < 0) return -1; h->sub_frames = frames; return 0; }
 int ft8rx_set_ladder_mode(ft8rx_handle* h, int mode) { if (!h || mode < 0 || mode > 1) return -1; h->ladder_mode = mode; return 0; }
 
@@ -988,7 +974,7 @@ int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_
     if (on) {
         if (!(sync_min > 0.0f) || !(sync_min < INFINITY)) { set_err(h, "ft8rx_set_weak: sync_min %g must be a positive score", (double)sync_min); return -1; }
         if (osd_max_hd < 1 || osd_max_hd > 174) { set_err(h, "ft8rx_set_weak: osd_max_hd %d outside [1, 174]", osd_max_hd); return -1; }
-        if (h->pk_buf[0]) { set_err(h, "ft8rx_set_weak: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
+        if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_weak: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
         if (h->msg_types) { set_err(h, "ft8rx_set_weak: not supported together with msg_types != 0"); return -1; }
         if (h->ap.np) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_ap_calls"); return -1; }
         if (h->rc_armed) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_recall"); return -1; }
@@ -1001,7 +987,7 @@ int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_
 int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
     if (!h) return -1;
     if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
-    if (mask && h->pk_buf[0]) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
+    if (mask && h->slots[0].pk_buf) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
     if (mask && h->ap.np) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_ap_calls"); return -1; }
     if (mask && h->rc_armed) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_recall"); return -1; }
     if (mask && h->weak) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_weak"); return -1; }
@@ -1053,7 +1039,7 @@ int ft8rx_set_ap_calls(ft8rx_handle* h, const char* my_call, const char* dx_call
     if (build_ap_patterns(my_call, dx_call, &a, &err)) { set_err(h, "ft8rx_set_ap_calls: %s", err.c_str()); return -1; }
     if (a.np && h->msg_types) { set_err(h, "ft8rx_set_ap_calls: not supported together with msg_types != 0"); return -1; }
     if (a.np && h->weak) { set_err(h, "ft8rx_set_ap_calls: not supported together with ft8rx_set_weak"); return -1; }
-    if (a.np && h->pk_buf[0]) { set_err(h, "ft8rx_set_ap_calls: not supported on the packed output"); return -1; }
+    if (a.np && h->slots[0].pk_buf) { set_err(h, "ft8rx_set_ap_calls: not supported on the packed output"); return -1; }
     h->ap = a; h->ap_version++;                 // batches in flight keep the setting they were enqueued with (enqueue_chain)
     return 0;
 }
@@ -1066,7 +1052,7 @@ int ft8rx_set_ap_max_hd(ft8rx_handle* h, int32_t max_hd) {
 }
 
 int ft8rx_ap_patterns(const char* my_call, const char* dx_call, uint8_t* bits_out, uint8_t* mask_out) {
-    ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = FT8RX_AP_MAX_HD_DEFAULT;
+    ApCalls a = ap_calls_off();
     std::string err;
     if (build_ap_patterns(my_call, dx_call, &a, &err)) { g_create_err = "ft8rx_ap_patterns: " + err; return -1; }
     for (int k = 0; k < FT8RX_AP_N; k++) for (int i = 0; i < 174; i++) {
@@ -1121,9 +1107,10 @@ static int recall_alloc(ft8rx_handle* h) {
     rc |= dalloc(h, &h->d_rc_trip, N * 3); rc |= dalloc(h, &h->d_rc_tout, N * 5); rc |= dalloc(h, &h->d_rc_tsd, N);
     rc |= dalloc(h, &h->d_rc_sgrid, N * 632); rc |= dalloc(h, &h->d_rc_llr, N * 174);
     for (int k = 0; k < 2 && !rc; k++) {
-        rc |= dalloc(h, &h->d_rc_ent[k], N); rc |= dalloc(h, &h->d_rc_cnt[k], B); rc |= dalloc(h, &h->d_rc_rec[k], N);
-        if (!rc && (hipHostMalloc((void**)&h->h_rc_rec[k], sizeof(ft8rx_record) * N, hipHostMallocDefault) != hipSuccess ||
-                    hipHostMalloc((void**)&h->h_rc_cnt[k], sizeof(int32_t) * B, hipHostMallocDefault) != hipSuccess)) {
+        ResultSlot& sl = h->slots[k];
+        rc |= dalloc(h, &sl.d_rc_ent, N); rc |= dalloc(h, &sl.d_rc_cnt, B); rc |= dalloc(h, &sl.d_rc_rec, N);
+        if (!rc && (hipHostMalloc((void**)&sl.h_rc_rec, sizeof(ft8rx_record) * N, hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc((void**)&sl.h_rc_cnt, sizeof(int32_t) * B, hipHostMallocDefault) != hipSuccess)) {
             set_err(h, "ft8rx_set_recall: page-locked result buffers could not be allocated"); rc = -2; }
     }
     if (rc) { h->d_rc_src = nullptr; return -2; }
@@ -1137,7 +1124,7 @@ int ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const i
     if (!counts || n_frames < 1 || n_frames > h->max_frames) { set_err(h, "ft8rx_set_recall: n_frames %d outside [1, %d]", n_frames, h->max_frames); return -1; }
     if (h->msg_types) { set_err(h, "ft8rx_set_recall: not supported together with msg_types != 0"); return -1; }
     if (h->weak) { set_err(h, "ft8rx_set_recall: not supported together with ft8rx_set_weak"); return -1; }
-    if (h->pk_buf[0]) { set_err(h, "ft8rx_set_recall: not supported on the packed output"); return -1; }
+    if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_recall: not supported on the packed output"); return -1; }
     const ft8rx_config& c = h->cfg;
     std::vector<ft8rx_recall_entry> st((size_t)n_frames * FT8RX_RECALL_MAX);
     std::vector<int32_t> cnt(n_frames), off(n_frames + 1, 0);
@@ -1166,15 +1153,16 @@ int ft8rx_fetch_recall(ft8rx_handle* h, int n_frames, ft8rx_record* records, int
     if (!h) return -1;
     const int slot = h->fetched_slot;
     if (slot < 0) { set_err(h, "ft8rx_fetch_recall: no batch has been fetched"); return -1; }
-    if (n_frames < 1 || n_frames > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_recall: %d frames requested, the batch had %d", n_frames, h->slot_B[slot]); return -1; }
-    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
-    if (!h->slot_recall[slot]) {
+    const ResultSlot& sl = h->slots[slot];
+    if (n_frames < 1 || n_frames > sl.B) { set_err(h, "ft8rx_fetch_recall: %d frames requested, the batch had %d", n_frames, sl.B); return -1; }
+    HIPCHK(h, hipEventSynchronize(sl.ev_done));
+    if (!sl.recall) {
         if (counts) memset(counts, 0, sizeof(int32_t) * n_frames);
         if (records) memset(records, 0, sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)n_frames);
         return 0;
     }
-    if (counts) memcpy(counts, h->h_rc_cnt[slot], sizeof(int32_t) * n_frames);
-    if (records) memcpy(records, h->h_rc_rec[slot], sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)n_frames);
+    if (counts) memcpy(counts, sl.h_rc_cnt, sizeof(int32_t) * n_frames);
+    if (records) memcpy(records, sl.h_rc_rec, sizeof(ft8rx_record) * FT8RX_RECALL_MAX * (size_t)n_frames);
     return 0;
 }
 
@@ -1182,14 +1170,14 @@ int ft8rx_set_reports(ft8rx_handle* h, int32_t on) {
     if (!h) return -1;
     ENTER(h);                                   // batches in flight were enqueued under the previous setting
     if (!on) { h->reports = false; return 0; }
-    if (h->pk_buf[0]) { set_err(h, "ft8rx_set_reports: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
+    if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_reports: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
     if (!h->d_rp_items) {
         const size_t B = (size_t)h->max_frames, N = B << cand_shift(h->cfg);
         int rc = 0;
-        rc |= dalloc(h, &h->d_rp_items, N); rc |= dalloc(h, &h->d_rp_count, (size_t)16);
+        rc |= dalloc(h, &h->d_rp_items, N); rc |= dalloc(h, &h->d_rp_count, (size_t)batchplan::MAX_CHUNKS);
         for (int k = 0; k < 2 && !rc; k++) {
-            rc |= dalloc(h, &h->d_rp[k], N);
-            if (!rc && hipHostMalloc((void**)&h->h_rp[k], sizeof(ft8rx_report) * B * h->cfg.max_cands, hipHostMallocDefault) != hipSuccess) {
+            rc |= dalloc(h, &h->slots[k].d_rp, N);
+            if (!rc && hipHostMalloc((void**)&h->slots[k].h_rp, sizeof(ft8rx_report) * B * h->cfg.max_cands, hipHostMallocDefault) != hipSuccess) {
                 set_err(h, "ft8rx_set_reports: page-locked result buffers could not be allocated"); rc = -2; }
         }
         if (rc) { h->d_rp_items = nullptr; return -2; }
@@ -1202,11 +1190,12 @@ int ft8rx_fetch_reports(ft8rx_handle* h, int n_frames, ft8rx_report* reports) {
     if (!h || !reports) return -1;
     const int slot = h->fetched_slot;
     if (slot < 0) { set_err(h, "ft8rx_fetch_reports: no batch has been fetched"); return -1; }
-    if (n_frames < 1 || n_frames > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_reports: %d frames requested, the batch had %d", n_frames, h->slot_B[slot]); return -1; }
-    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
+    const ResultSlot& sl = h->slots[slot];
+    if (n_frames < 1 || n_frames > sl.B) { set_err(h, "ft8rx_fetch_reports: %d frames requested, the batch had %d", n_frames, sl.B); return -1; }
+    HIPCHK(h, hipEventSynchronize(sl.ev_done));
     const size_t bytes = sizeof(ft8rx_report) * (size_t)n_frames * h->cfg.max_cands;
-    if (!h->slot_reports[slot]) memset(reports, 0, bytes);
-    else memcpy(reports, h->h_rp[slot], bytes);
+    if (!sl.reports) memset(reports, 0, bytes);
+    else memcpy(reports, sl.h_rp, bytes);
     return 0;
 }
 
@@ -1243,42 +1232,51 @@ int ft8rx_sync(ft8rx_handle* h) {
     return 0;
 }
 
-int ft8rx_fetch_results(ft8rx_handle* h, int B, ft8rx_record* records, int32_t* counts, ft8rx_event* events, int32_t* event_counts) {
+// The batch a fetch hands out: the oldest unfetched one, else the latest one again, once its results have reached the host buffers
+// (with_events: and its event log lies in h_ev's rows).  to_device (ft8rx_results_to_device): always the latest one, as soon as its
+// kernels are done on every chunk stream (the results sit in the slot's device buffers).  -> 0 and *slot, or the error code
+static int fetch_begin(ft8rx_handle* h, const char* who, int B, bool with_events, bool to_device, int* slot) {
     if (!h || B < 1 || B > h->max_frames) return -1;
-    if (h->last_slot < 0) { set_err(h, "ft8rx_fetch_results: nothing has been enqueued"); return -1; }
+    if (h->last_slot < 0) { set_err(h, "%s: nothing has been enqueued", who); return -1; }
     HIPCHK(h, hipSetDevice(h->device));
-    const int slot = h->inflight ? h->slot_fetch : h->last_slot;      // oldest unfetched batch, else the latest one again
-    if (B > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_results: %d frames requested, the batch had %d", B, h->slot_B[slot]); return -1; }
-    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
-    if (events) { const int rc = fetch_events(h, slot); if (rc) return rc; }
-    const size_t mc = (size_t)h->cfg.max_cands;
-    if (counts) memcpy(counts, h->h_cnt[slot], sizeof(int32_t) * B);
-    if (records) memcpy(records, h->h_rec[slot], sizeof(ft8rx_record) * mc * B);
-    if (event_counts) memcpy(event_counts, h->h_evc[slot], sizeof(int32_t) * B);
-    if (events) for (int f = 0; f < B; f++) {              // the used entries of each frame; the rest of the caller's row is left alone
-        int c = h->h_evc[slot][f]; if (c > FT8RX_EVENT_CAP) c = FT8RX_EVENT_CAP;
-        if (c > 0) memcpy(events + (size_t)f * FT8RX_EVENT_CAP, h->h_ev[slot] + (size_t)f * FT8RX_EVENT_CAP, sizeof(ft8rx_event) * (size_t)c);
-    }
+    *slot = (h->inflight && !to_device) ? h->slot_fetch : h->last_slot;
+    ResultSlot& sl = h->slots[*slot];
+    if (B > sl.B) { set_err(h, "%s: %d frames requested, the batch had %d", who, B, sl.B); return -1; }
+    HIPCHK(h, hipEventSynchronize(to_device ? sl.ev_comp : sl.ev_done));
+    if (with_events && !to_device) fetch_events(sl);
+    return 0;
+}
+static void fetch_end(ft8rx_handle* h, int slot) {
     h->fetched_slot = slot;
     if (h->inflight) { h->slot_fetch ^= 1; h->inflight--; }
+}
+
+int ft8rx_fetch_results(ft8rx_handle* h, int B, ft8rx_record* records, int32_t* counts, ft8rx_event* events, int32_t* event_counts) {
+    int slot;
+    if (const int rc = fetch_begin(h, "ft8rx_fetch_results", B, events != nullptr, false, &slot)) return rc;
+    const ResultSlot& sl = h->slots[slot];
+    const size_t mc = (size_t)h->cfg.max_cands;
+    if (counts) memcpy(counts, sl.h_cnt, sizeof(int32_t) * B);
+    if (records) memcpy(records, sl.h_rec, sizeof(ft8rx_record) * mc * B);
+    if (event_counts) memcpy(event_counts, sl.h_evc, sizeof(int32_t) * B);
+    if (events) for (int f = 0; f < B; f++) {              // the used entries of each frame; the rest of the caller's row is left alone
+        int c = sl.h_evc[f]; if (c > FT8RX_EVENT_CAP) c = FT8RX_EVENT_CAP;
+        if (c > 0) memcpy(events + (size_t)f * FT8RX_EVENT_CAP, sl.h_ev + (size_t)f * FT8RX_EVENT_CAP, sizeof(ft8rx_event) * (size_t)c);
+    }
+    fetch_end(h, slot);
     return 0;
 }
 
 int ft8rx_fetch_results_view(ft8rx_handle* h, int B, const ft8rx_record** records, const int32_t** counts,
                              const ft8rx_event** events, const int32_t** event_counts) {
-    if (!h || B < 1 || B > h->max_frames) return -1;
-    if (h->last_slot < 0) { set_err(h, "ft8rx_fetch_results_view: nothing has been enqueued"); return -1; }
-    HIPCHK(h, hipSetDevice(h->device));
-    const int slot = h->inflight ? h->slot_fetch : h->last_slot;
-    if (B > h->slot_B[slot]) { set_err(h, "ft8rx_fetch_results_view: %d frames requested, the batch had %d", B, h->slot_B[slot]); return -1; }
-    HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
-    if (events) { const int rc = fetch_events(h, slot); if (rc) return rc; }
-    if (records) *records = h->h_rec[slot];
-    if (counts) *counts = h->h_cnt[slot];
-    if (events) *events = h->h_ev[slot];
-    if (event_counts) *event_counts = h->h_evc[slot];
-    h->fetched_slot = slot;
-    if (h->inflight) { h->slot_fetch ^= 1; h->inflight--; }
+    int slot;
+    if (const int rc = fetch_begin(h, "ft8rx_fetch_results_view", B, events != nullptr, false, &slot)) return rc;
+    const ResultSlot& sl = h->slots[slot];
+    if (records) *records = sl.h_rec;
+    if (counts) *counts = sl.h_cnt;
+    if (events) *events = sl.h_ev;
+    if (event_counts) *event_counts = sl.h_evc;
+    fetch_end(h, slot);
     return 0;
 }
 
@@ -1286,8 +1284,9 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     if (!h) return -1;
     ENTER(h);                                   // batches in flight keep the buffers they were enqueued with
     HIPCHK(h, hipStreamSynchronize(h->copy_s));
-    h->pk_fence[0] = h->pk_fence[1] = nullptr;
-    if (!d_buf0 && !d_buf1) { h->pk_buf[0] = h->pk_buf[1] = nullptr; h->pk_cap = 0; return 0; }
+    ResultSlot* const sl = h->slots;
+    sl[0].pk_fence = sl[1].pk_fence = nullptr;
+    if (!d_buf0 && !d_buf1) { sl[0].pk_buf = sl[1].pk_buf = nullptr; h->pk_cap = 0; return 0; }
     if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
     if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
     if (h->rc_armed) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_recall entries are pending"); return -1; }
@@ -1310,55 +1309,56 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
         rc |= dalloc(h, &h->d_pknrec, (size_t)h->max_frames);
         if (rc) return -2;
         for (int k = 0; k < 2; k++) {
-            if (hipHostMalloc((void**)&h->h_pkhdr[k], sizeof(ft8rx_packed_header), hipHostMallocDefault) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&h->d_pkhdr[k], h->h_pkhdr[k], 0) != hipSuccess) { set_err(h, "ft8rx_set_packed_output: page-locked header could not be allocated"); return -2; }
-            memset(h->h_pkhdr[k], 0, sizeof(ft8rx_packed_header));
+            if (hipHostMalloc((void**)&sl[k].h_pkhdr, sizeof(ft8rx_packed_header), hipHostMallocDefault) != hipSuccess ||
+                hipHostGetDevicePointer((void**)&sl[k].d_pkhdr, sl[k].h_pkhdr, 0) != hipSuccess) { set_err(h, "ft8rx_set_packed_output: page-locked header could not be allocated"); return -2; }
+            memset(sl[k].h_pkhdr, 0, sizeof(ft8rx_packed_header));
         }
     }
-    h->pk_buf[0] = dev[0]; h->pk_buf[1] = dev[1]; h->pk_cap = cap_bytes;
+    sl[0].pk_buf = dev[0]; sl[1].pk_buf = dev[1]; h->pk_cap = cap_bytes;
     return 0;
 }
 
 int ft8rx_packed_output_fence(ft8rx_handle* h, int which, void* hip_event) {
     if (!h || which < 0 || which > 1) return -1;
-    h->pk_fence[which] = (hipEvent_t)hip_event;
+    h->slots[which].pk_fence = (hipEvent_t)hip_event;
     return 0;
 }
 
 int ft8rx_packed_results(ft8rx_handle* h, int32_t* which, ft8rx_packed_header* header) {
     if (!h) return -1;
-    if (h->fetched_slot < 0 || !h->slot_packed[h->fetched_slot]) { set_err(h, "ft8rx_packed_results: the batch fetched last was enqueued without a packed output (ft8rx_set_packed_output)"); return -1; }
+    if (h->fetched_slot < 0 || !h->slots[h->fetched_slot].packed) { set_err(h, "ft8rx_packed_results: the batch fetched last was enqueued without a packed output (ft8rx_set_packed_output)"); return -1; }
     if (which) *which = h->fetched_slot;
-    if (header) *header = *h->h_pkhdr[h->fetched_slot];
+    if (header) *header = *h->slots[h->fetched_slot].h_pkhdr;
     return 0;
 }
 
 int ft8rx_results_to_device(ft8rx_handle* h, int B, ft8rx_record* d_records, int32_t* d_counts, ft8rx_event* d_events, int32_t* d_event_counts) {
-    if (!h || B < 1 || B > h->max_frames) return -1;
-    if (h->last_slot < 0) { set_err(h, "ft8rx_results_to_device: nothing has been enqueued"); return -1; }
-    HIPCHK(h, hipSetDevice(h->device));
-    const int slot = h->last_slot;
-    if (B > h->slot_B[slot]) { set_err(h, "ft8rx_results_to_device: %d frames requested, the batch had %d", B, h->slot_B[slot]); return -1; }
-    HIPCHK(h, hipEventSynchronize(h->ev_comp[slot]));                // the batch's kernels are done on every chunk stream (results sit in s_*[slot])
+    int slot;
+    if (const int rc = fetch_begin(h, "ft8rx_results_to_device", B, false, true, &slot)) return rc;
+    const ResultSlot& sl = h->slots[slot];
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int mc = h->cfg.max_cands;
-    if (d_counts) HIPCHK(h, hipMemcpyAsync(d_counts, h->s_ncand[slot], sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
-    if (d_records) HIPCHK(h, hipMemcpy2DAsync(d_records, sizeof(ft8rx_record) * mc, h->s_rec[slot], sizeof(ft8rx_record) << cand_shift(h->cfg),
+    if (d_counts) HIPCHK(h, hipMemcpyAsync(d_counts, sl.ncand, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
+    if (d_records) HIPCHK(h, hipMemcpy2DAsync(d_records, sizeof(ft8rx_record) * mc, sl.rec, sizeof(ft8rx_record) << cand_shift(h->cfg),
                                               sizeof(ft8rx_record) * mc, B, hipMemcpyDeviceToDevice, h->stream));
-    if (d_event_counts) HIPCHK(h, hipMemcpyAsync(d_event_counts, h->s_evcount[slot], sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
-    if (d_events) HIPCHK(h, hipMemcpyAsync(d_events, h->s_ev[slot], sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToDevice, h->stream));
+    if (d_event_counts) HIPCHK(h, hipMemcpyAsync(d_event_counts, sl.evcount, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
+    if (d_events) HIPCHK(h, hipMemcpyAsync(d_events, sl.ev, sizeof(ft8rx_event) * (size_t)B * FT8RX_EVENT_CAP, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// the synchronous host entries: nothing older is kept, and the audio is staged in the handle's own buffer
+static int launch_batch_sync(ft8rx_handle* h, const int16_t* audio, int B) {
+    h->inflight = 0; h->slot_fetch = h->slot_enq;
+    if (need_staging(h)) return -2;
+    return launch_batch(h, batchplan::HOST_SYNC, audio, B);
 }
 
 int ft8rx_decode_batch(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_record* records, int32_t* counts,
                        ft8rx_event* events, int32_t* event_counts) {
     if (!h || !audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_decode_batch: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    h->inflight = 0; h->slot_fetch = h->slot_enq;                     // synchronous entry: nothing older is kept
-    if (need_staging(h)) return -2;
-    int rc = launch_batch(h, h->d_audio, audio, B);
-    if (rc) return rc;
+    if (const int rc = launch_batch_sync(h, audio, B)) return rc;
     return ft8rx_fetch_results(h, B, records, counts, events, event_counts);
 }
 
@@ -1370,9 +1370,7 @@ int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_me
     if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "ft8rx_decode_messages: bad n_frames / max_msgs"); return -1; }
     if (h->msg_types) { set_err(h, "ft8rx_decode_messages: msg_types != 0 -- ft8rx_message holds only the reference's message types"); return -1; }
     if (h->rc_armed) { set_err(h, "ft8rx_decode_messages: recall entries (ft8rx_set_recall) are not supported; use ft8rx_decode_batch + ft8rx_fetch_recall"); return -1; }
-    h->inflight = 0; h->slot_fetch = h->slot_enq;                     // synchronous entry: nothing older is kept
-    if (need_staging(h)) return -2;
-    int rc = launch_batch(h, h->d_audio, audio, B);
+    int rc = launch_batch_sync(h, audio, B);
     if (rc) return rc;
     const ft8rx_record* rec; const int32_t* cnt; const ft8rx_event* ev; const int32_t* evc;
     rc = ft8rx_fetch_results_view(h, B, &rec, &cnt, &ev, &evc);
@@ -1411,7 +1409,6 @@ int ft8rx_sync_search(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx
     ENTER(h);
     const ft8rx_config& c = h->cfg;
     HIPCHK(h, hipMemcpy(h->d_grid, grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyHostToDevice));
-    const int ntile = (c.f0_hi - c.f0_lo + 15) / 16;
     launch_sync(h->d_grid, h->d_best_score, h->d_best_h0, c, B, h->stream, false);
     k_topk<<<B, 1024, 0, h->stream>>>(h->d_best_score, h->d_best_h0, h->d_rec, h->d_ncand, c, nullptr, nullptr, nullptr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1424,7 +1421,6 @@ int ft8rx_sync_search(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx
         size_t o = (size_t)f * c.max_cands + i;
         f0_idx[o] = r.f0_idx; h0_idx[o] = r.h0_idx; score[o] = r.score;
     }
-    // restore the 1.0 row in case the caller's grid differed
     return 0;
 }
 
@@ -1494,9 +1490,11 @@ int ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int B, float* sp
 static int fine_probe(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
                       int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid, bool weak) {
     if (!h || !spec || B < 1 || B > h->max_frames || n < 1) return -1;
-    for (int i = 0; weak && i < n; i++)         // every triple must name a frame of the spectrum and a candidate the search could give
+    // weak mode only (ft8rx_fine keeps its unchecked contract): every triple must name a frame of the spectrum and a candidate the
+    // search could give
+    if (weak) for (int i = 0; i < n; i++)
         if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < 4 || f0_idx[i] >= FT8RX_MAX_F0 || h0_idx[i] < FT8RX_MIN_H0 || h0_idx[i] >= FT8RX_MAX_H0) {
-            set_err(h, "%s: triple %d (frame %d, f0 %d, h0 %d) outside [0, %d) x [4, %d) x [%d, %d)", weak ? "ft8rx_fine_weak" : "ft8rx_fine", i,
+            set_err(h, "ft8rx_fine_weak: triple %d (frame %d, f0 %d, h0 %d) outside [0, %d) x [4, %d) x [%d, %d)", i,
                     frame[i], f0_idx[i], h0_idx[i], B, FT8RX_MAX_F0, FT8RX_MIN_H0, FT8RX_MAX_H0); return -1; }
     ENTER(h);
     HIPCHK(h, hipMemcpy(h->d_spec, spec, sizeof(cpx) * (size_t)B * FT8RX_SPEC_BINS, hipMemcpyHostToDevice));

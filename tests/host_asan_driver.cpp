@@ -2,7 +2,8 @@
 // Compiles pyft8_amd/csrc/host_messages.hpp on its own (g++ -fsanitize=address,undefined; no HIP) and drives the native message
 // layer -- unpack / call hashes / ordered replay / duplicate filter / tone encoder -- with (a) a records+events dump of a real frame
 // written by the test (argv[1]: n, nev, then the raw ft8rx_record[n] and ft8rx_event[nev] bytes) and (b) random 77-bit words,
-// multi-threaded, with fresh and with persistent hash tables, including truncating capacities.
+// multi-threaded, with fresh and with persistent hash tables, including truncating capacities; and (c) checks the batch partition
+// rule (pyft8_amd/csrc/batch_plan.hpp) against a table of plans derived by hand and against its invariants.
 //   make -C oracle asan && oracle/_build/asan_host [dump.bin]
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,6 +12,68 @@
 #include "../include/ft8rx.h"
 #include "../pyft8_amd/csrc/ft8_tables.h"
 #include "../pyft8_amd/csrc/host_messages.hpp"
+#include "../pyft8_amd/csrc/batch_plan.hpp"
+
+// (c) the partition rule.  -> the number of plans checked, or -(line) of the first failed check
+static long check_batch_plans() {
+    using namespace batchplan;
+#define PLAN_CHECK(x) do { if (!(x)) { fprintf(stderr, "batch plan: %s fails (B %d, streams %d, entry %d, profiling %d)\n", #x, B, ns, (int)e, (int)prof); return -(long)__LINE__; } } while (0)
+    long checked = 0;
+    {   // the expected plans, derived by hand from the rule as launch_batch had it
+        struct Row { int B, ns; Entry e; bool prof; Mode mode; int nc; int cb[MAX_CHUNKS + 1]; };
+        static const Row rows[] = {
+            {256, 2, DEVICE, false, FREE_RUN, 2, {0, 128, 256}},
+            {256, 2, HOST_PIPELINED, false, FREE_RUN, 2, {0, 128, 256}},
+            {256, 2, HOST_SYNC, false, FORK_JOIN, 4, {0, 32, 64, 128, 256}},
+            {24, 2, HOST_SYNC, false, FORK_JOIN, 3, {0, 6, 12, 24}},
+            {25, 2, HOST_SYNC, false, FORK_JOIN, 3, {0, 7, 13, 25}},
+            {16, 4, HOST_SYNC, false, FORK_JOIN, 2, {0, 8, 16}},
+            {24, 4, DEVICE, false, FORK_JOIN, 3, {0, 8, 16, 24}},
+            {24, 4, HOST_PIPELINED, false, FORK_JOIN, 3, {0, 8, 16, 24}},
+            {17, 2, DEVICE, false, FREE_RUN, 2, {0, 9, 17}},
+            {40, 8, DEVICE, false, FORK_JOIN, 5, {0, 8, 16, 24, 32, 40}},
+            {64, 8, DEVICE, false, FREE_RUN, 8, {0, 8, 16, 24, 32, 40, 48, 56, 64}},
+            {15, 2, DEVICE, false, SINGLE, 1, {0, 15}}, {15, 2, HOST_SYNC, false, SINGLE, 1, {0, 15}}, {15, 2, HOST_PIPELINED, false, SINGLE, 1, {0, 15}},
+            {7, 1, DEVICE, false, SINGLE, 1, {0, 7}}, {7, 8, HOST_SYNC, false, SINGLE, 1, {0, 7}}, {7, 4, HOST_PIPELINED, true, SINGLE, 1, {0, 7}},
+            {256, 2, DEVICE, true, SINGLE, 1, {0, 256}},
+            {129, 8, HOST_SYNC, false, FORK_JOIN, 16, {0, 1, 1, 1, 1, 1, 1, 1, 1, 2, 3, 5, 9, 17, 33, 65, 129}},
+        };
+        for (const Row& r : rows) {
+            const int B = r.B, ns = r.ns; const Entry e = r.e; const bool prof = r.prof;
+            const BatchPlan p = plan_batch(B, ns, prof, e);
+            PLAN_CHECK(p.mode == r.mode && p.nc == r.nc);
+            for (int k = 0; k <= r.nc; k++) PLAN_CHECK(p.cb[k] == r.cb[k]);
+            checked++;
+        }
+    }
+    // invariants over every batch size up to 600 and three large ones, every stream count, entry and profiling setting
+    for (int i = 1; i <= 603; i++) for (int ns = 1; ns <= MAX_STREAMS; ns++) for (int prof = 0; prof < 2; prof++) {
+        const int B = i <= 600 ? i : i == 601 ? 4096 : i == 602 ? 8192 : 8193;
+        BatchPlan by_entry[3];
+        for (int ei = 0; ei < 3; ei++) {
+            const Entry e = (Entry)ei;
+            const BatchPlan p = by_entry[ei] = plan_batch(B, ns, prof != 0, e);
+            int capped = prof ? 1 : (e == HOST_SYNC ? 2 * ns : ns);                  // the chunk count after the B / 8 cap
+            if (capped > B / 8) capped = B / 8;
+            PLAN_CHECK(p.nc >= 1 && p.nc <= MAX_CHUNKS && p.nc <= 16);
+            PLAN_CHECK(p.cb[0] == 0 && p.cb[p.nc] == B);
+            for (int k = 0; k < p.nc; k++) PLAN_CHECK(p.cb[k] <= p.cb[k + 1]);
+            PLAN_CHECK((p.mode == SINGLE) == (capped <= 1));
+            if (p.mode != SINGLE) PLAN_CHECK(p.nc == capped);
+            if (prof) PLAN_CHECK(p.mode == SINGLE);
+            if (p.mode == FREE_RUN) {
+                PLAN_CHECK(p.nc == ns && e != HOST_SYNC);
+                for (int k = 0; k < p.nc; k++) PLAN_CHECK(p.cb[k] < p.cb[k + 1]);
+            }
+            checked++;
+        }
+        const Entry e = HOST_PIPELINED;
+        PLAN_CHECK(by_entry[DEVICE].mode == by_entry[HOST_PIPELINED].mode && by_entry[DEVICE].nc == by_entry[HOST_PIPELINED].nc);
+        for (int k = 0; k <= MAX_CHUNKS; k++) PLAN_CHECK(by_entry[DEVICE].cb[k] == by_entry[HOST_PIPELINED].cb[k]);
+    }
+#undef PLAN_CHECK
+    return checked;
+}
 
 int main(int argc, char** argv) {
     std::mt19937_64 rng(12345);
@@ -127,5 +190,8 @@ int main(int argc, char** argv) {
         if (i % 16 == 0) { hostmsg::encode_tones(lo, hi, tones); acc += tones[40]; }
     }
     printf("random words: %ld unpacked, %zu hash keys, tone checksum %u\n", ok, H.size(), acc);
+    const long plans = check_batch_plans();
+    if (plans < 0) return 20;
+    printf("batch plans: %ld checked\n", plans);
     return 0;
 }

@@ -772,6 +772,53 @@ def test_pipelined_host_entry_matches_synchronous_decode():
     h.close()
 
 
+def test_fork_join_and_single_submission_with_resident_and_pipelined_audio():
+    """The submission paths of a batch (csrc/batch_plan.hpp) that no other test reaches: fork / join over the chunk streams with
+    device-resident audio and with the pipelined host entry (24 frames on four streams: 8|8|8 on three of them), one chain on the main
+    stream fed by the pipelined host entry (8 frames, both staging buffers), and fork / join right behind free-running streams and
+    back.  Every batch equals what ft8rx_decode_batch gives on a fresh default handle."""
+    from pyft8_amd import _lib
+    B = 24
+    store = _lib.Handle(max_frames=B)
+    ptr = store.staging_ptr()
+    store.synth_frames(ptr, 57000, B, n_signals=12, snr_range=(-10.0, 6.0))
+    host = store.download_audio(ptr, B)
+    ref = _lib.Handle(max_frames=B)
+    want, want8 = ref.decode_batch(host), ref.decode_batch(host[:8])
+    ref.close()
+
+    def same(a, b):
+        (ra, ca, ea, na), (rb, cb, eb, nb) = a, b
+        if not (np.array_equal(ca, cb) and np.array_equal(na, nb)):
+            return False
+        return all(ra[f, :ca[f]].tobytes() == rb[f, :cb[f]].tobytes() and
+                   sorted(ea[f, :min(na[f], _lib.EVENT_CAP)].tolist()) == sorted(eb[f, :min(nb[f], _lib.EVENT_CAP)].tolist()) for f in range(len(ca)))
+    h = _lib.Handle(max_frames=B)
+    h.set_streams(4)
+    h.enqueue(ptr, B)                                            # fork / join, device-resident audio
+    h.enqueue(ptr, B)
+    assert same(h.fetch(B), want) and same(h.fetch(B), want)
+    pinned = [h.pinned_audio(B) for _ in range(2)]
+    for a in pinned:
+        a[:] = host
+    h.enqueue_host(pinned[0])                                    # fork / join, pipelined host entry
+    h.enqueue_host(pinned[1])
+    assert same(h.fetch(B), want) and same(h.fetch(B), want)
+    h.enqueue_host(pinned[0][:8])                                # one chain, pipelined host entry: first one staging buffer, then the other
+    h.enqueue_host(pinned[1][:8])
+    assert same(h.fetch(8), want8) and same(h.fetch(8), want8)
+    h.set_streams(3)
+    h.enqueue(ptr, B)                                            # free-running 8|8|8 ...
+    h.set_streams(4)
+    h.enqueue(ptr, B)                                            # ... fork / join at once behind it ...
+    assert same(h.fetch(B), want) and same(h.fetch(B), want)
+    h.set_streams(3)
+    h.enqueue(ptr, B)                                            # ... and free-running again
+    assert same(h.fetch(B), want)
+    h.close()
+    store.close()
+
+
 def test_subtract_matches_reference_golden_and_oracle():
     """SURVEY 8f-4 primitive: ft8rx_subtract vs the reference's Receiver.subtract_signal run in isolation
     (tests/golden/subtract.npz, oracle/gen_golden_subtract.py) and vs the C oracle's restatement.  Floating-point stage:

@@ -45,3 +45,5 @@ def test_host_message_layer_under_asan_ubsan(asan_bins, tmp_path):
         ev[:min(nev, _lib.EVENT_CAP)].tofile(f)
     out = _run([asan_bins[1], str(dump)])
     assert f"frame dump: {n} candidates" in out and "20 messages per frame" in out and "random words:" in out
+    # the batch partition rule (csrc/batch_plan.hpp): 19 plans derived by hand + (603 batch sizes x 8 stream counts x 2 x 3 entries)
+    assert f"batch plans: {19 + 603 * 8 * 2 * 3} checked" in out
