@@ -7,6 +7,8 @@ import weakref
 
 import numpy as np
 
+from . import optins
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FT8RX_LIB", os.path.join(HERE, "libft8rx.so"))   # FT8RX_LIB: A/B builds of the same ABI
 # the same source with the wide layouts (-DFT8RX_WIDE, include/ft8rx.h): search_freq_range up to 5900 Hz (and up to 2048 candidates per
@@ -274,8 +276,7 @@ class Handle:
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
         if self.cfg.msg_types:
-            L.ft8rx_set_msg_types.argtypes = [C.c_void_p, C.c_int32]
-            self._chk(L.ft8rx_set_msg_types(self._h, int(self.cfg.msg_types)), "ft8rx_set_msg_types")
+            self.set_msg_types(self.cfg.msg_types)
         if getattr(self.cfg, "ap_max_hd", None) is not None:
             self.set_ap_max_hd(self.cfg.ap_max_hd)
         if getattr(self.cfg, "ap_my_call", None) or getattr(self.cfg, "ap_dx_call", None):
@@ -284,6 +285,13 @@ class Handle:
             self.set_weak(True, self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd)
         if getattr(self.cfg, "reports", False):
             self.set_reports(True)
+
+    def set_msg_types(self, mask):
+        """ft8rx_set_msg_types: the opt-in message types (MT_* bits; 0 = the reference's rule) of the batches enqueued afterwards."""
+        L = self._L
+        L.ft8rx_set_msg_types.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(L.ft8rx_set_msg_types(self._h, int(mask)), "ft8rx_set_msg_types")
+        self.cfg.msg_types = int(mask)
 
     def set_reports(self, on):
         """ft8rx_set_reports: measured SNR / frequency / start time of every DECODED record for the batches enqueued afterwards
@@ -479,9 +487,8 @@ class Handle:
         keep: the objects that own the two buffers (torch tensors, page-locked arrays).  The handle holds on to them -- and to the events
         given to packed_fence -- until the packed output is reset or the handle is closed, so the pack kernels can never write into
         memory whose Python owner has already been collected."""
-        if buf0 is not None and self.cfg.msg_types:
-            raise Ft8rxError("set_packed_output: msg_types != 0 is not supported on the packed path (ft8rx_package_packed renders only the "
-                             "reference's message types)")
+        if buf0 is not None:          # (the library refuses the other settings itself; msg_types may be set in cfg alone)
+            optins.refuse(optins.PACKED, optins.active(self.cfg) & {optins.MSG_TYPES})
         L = self._L
         L.ft8rx_set_packed_output.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         self._chk(L.ft8rx_set_packed_output(self._h, C.c_void_p(buf0 or None), C.c_void_p(buf1 or None), C.c_uint64(int(cap_bytes))),

@@ -61,6 +61,7 @@
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
+#include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
 // ====================================================================================== host side
@@ -153,7 +154,8 @@ struct ft8rx_handle {
     hipStream_t copy_s = nullptr;    // host-to-device chunk copies of ft8rx_decode_batch, in order, never queued behind kernels
     hipEvent_t ev_chunk[batchplan::MAX_CHUNKS] = {};
     Tables T = {};
-    std::vector<void*> allocs;
+    std::vector<void*> allocs, pinned;   // everything the handle owns: device memory (dalloc) and page-locked host memory (halloc)
+    unsigned ready = 0;                  // the lazily created workspace groups that are complete, 1 << WS_* (FirstUse)
     struct Chunk { void* p; size_t cap, used; };
     std::vector<Chunk> arena;        // scratch of the stage entry points (struct Scratch)
     int16_t* d_audio = nullptr;  // staging for host-pointer entry points
@@ -238,13 +240,50 @@ template <typename T> static int dalloc(ft8rx_handle* h, T** p, size_t n) {
     if (e != hipSuccess) { set_err(h, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e)); return -2; }
     h->allocs.push_back(q); *p = (T*)q; return 0;
 }
+// page-locked host memory; dev: also its device address (for kernels that write it directly)
+template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** dev = nullptr) {
+    void *q = nullptr, *d = nullptr;
+    hipError_t e = hipHostMalloc(&q, n * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess && dev && (e = hipHostGetDevicePointer(&d, q, 0)) != hipSuccess) hipHostFree(q);
+    if (e != hipSuccess) { set_err(h, "hipHostMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e)); return -2; }
+    h->pinned.push_back(q); *p = (T*)q; if (dev) *dev = (T*)d; return 0;
+}
+
+// The workspaces that are created when something first needs them, one group per user.  First use is all or nothing: the members are
+// allocated through dev() / host() and further steps (a table upload) run under FIRST_HIP; done() marks the group ready only if every
+// step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
+// handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
+// ready group, so none sees a null member.
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES };
+struct FirstUse {
+    ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
+    std::vector<void**> members;
+    FirstUse(ft8rx_handle* h_, WsGroup g_) : h(h_), g(g_), nd(h_->allocs.size()), nh(h_->pinned.size()) {}
+    template <typename T> void dev(T** p, size_t n) { if (!rc && !(rc = dalloc(h, p, n))) members.push_back((void**)p); }
+    template <typename T> void host(T** p, size_t n, T** d = nullptr) {
+        if (rc || (rc = halloc(h, p, n, d))) return;
+        members.push_back((void**)p); if (d) members.push_back((void**)d);
+    }
+    int done() {
+        if (!rc) { h->ready |= 1u << g; return 0; }
+        while (h->allocs.size() > nd) { hipFree(h->allocs.back()); h->allocs.pop_back(); }
+        while (h->pinned.size() > nh) { hipHostFree(h->pinned.back()); h->pinned.pop_back(); }
+        for (void** m : members) *m = nullptr;
+        return -2;
+    }
+};
+static bool ws_ready(const ft8rx_handle* h, WsGroup g) { return (h->ready >> g) & 1u; }
+#define FIRST_HIP(F, x) do { if (!(F).rc) { hipError_t _e = (x); if (_e != hipSuccess) { set_err((F).h, "%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); (F).rc = -2; } } } while (0)
 
 // The handle's own device audio buffer ([max_frames][180000] int16: staging of the host-pointer entry points, ft8rx_staging_audio) is
 // allocated when something first asks for it: a caller that keeps its audio resident in HBM (ft8rx_enqueue_batch) never pays the
-// 360 KB per frame.
-static int need_staging(ft8rx_handle* h) {
-    if (h->d_audio) return 0;
-    return dalloc(h, &h->d_audio, (size_t)h->max_frames * FT8RX_NSAMP);
+// 360 KB per frame.  (d_audio2: the second staging buffer of the pipelined host entry, batch_begin)
+static int need_staging(ft8rx_handle* h, bool second = false) {
+    const WsGroup g = second ? WS_STAGING2 : WS_STAGING;
+    if (ws_ready(h, g)) return 0;
+    FirstUse F(h, g);
+    F.dev(second ? &h->d_audio2 : &h->d_audio, (size_t)h->max_frames * FT8RX_NSAMP);
+    return F.done();
 }
 
 static void host_twiddle(int n, int count, std::vector<cpx>& w) {
@@ -312,6 +351,20 @@ static void launch_mt(K k, KX kx, unsigned mt, int grid, hipStream_t s, A... a) 
     else kx<<<grid, 64, 0, s>>>(a..., mt);
 }
 
+// The opt-in steps (optins.hpp): what counts as active, and the one refusal of a setter or consumer `who` of kind `which` that an
+// active setting excludes.  Turning a setting off is never refused.
+static unsigned active_optins(const ft8rx_handle* h) {
+    using namespace optins;
+    return (h->slots[0].pk_buf ? bit(PACKED) : 0) | (h->msg_types != 0 ? bit(MSG_TYPES) : 0) | (h->ap.np != 0 ? bit(AP_CALLS) : 0) |
+           (h->rc_armed ? bit(RECALL) : 0) | (h->weak ? bit(WEAK) : 0) | (h->reports ? bit(REPORTS) : 0);
+}
+static int refuse_conflict(ft8rx_handle* h, const char* who, optins::Id which, const char* hint = "") {
+    const int c = optins::conflict(active_optins(h), which);
+    if (c < 0) return 0;
+    set_err(h, "%s: not supported together with %s%s", who, optins::TABLE[c].name, hint);
+    return -1;
+}
+
 extern "C" {
 
 int ft8rx_default_config(ft8rx_config* c) {
@@ -372,10 +425,8 @@ void ft8rx_destroy(ft8rx_handle* h) {
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
-        const auto hfree = [](void* p) { if (p) hipHostFree(p); };
-        hfree(sl.h_rec); hfree(sl.h_cnt); hfree(sl.h_ev); hfree(sl.h_evc); hfree(sl.h_evpacked); hfree(sl.h_pkhdr);
-        hfree(sl.h_rc_rec); hfree(sl.h_rc_cnt); hfree(sl.h_rp);
     }
+    for (void* p : h->pinned) hipHostFree(p);
     delete h;
 }
 
@@ -427,13 +478,11 @@ int ft8rx_create(const ft8rx_config* cfg, int device, int max_frames, ft8rx_hand
     const bool ev_compact = B * FT8RX_EVENT_CAP * sizeof(ft8rx_event) > EV_EAGER_BYTES;
     for (int k = 0; k < 2 && ev_compact; k++) rc |= dalloc(h, &sl[k].d_evoffs, B + 1);
     for (int k = 0; k < 2 && !rc; k++) {
-        bool okh = hipHostMalloc((void**)&sl[k].h_rec, sizeof(ft8rx_record) * B * cfg->max_cands, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&sl[k].h_cnt, sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&sl[k].h_ev, sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess;
-        okh = okh && hipHostMalloc((void**)&sl[k].h_evc, sizeof(int32_t) * B, hipHostMallocDefault) == hipSuccess;
-        if (ev_compact) okh = okh && hipHostMalloc((void**)&sl[k].h_evpacked, sizeof(ft8rx_event) * B * FT8RX_EVENT_CAP, hipHostMallocDefault) == hipSuccess
-                                  && hipHostGetDevicePointer((void**)&sl[k].d_evpacked, sl[k].h_evpacked, 0) == hipSuccess;
-        if (!okh) { set_err(h, "ft8rx_create: page-locked result buffers (%zu frames) could not be allocated", B); rc = -2; }
+        rc = halloc(h, &sl[k].h_rec, B * cfg->max_cands);
+        if (!rc) rc = halloc(h, &sl[k].h_cnt, B);
+        if (!rc) rc = halloc(h, &sl[k].h_ev, B * FT8RX_EVENT_CAP);
+        if (!rc) rc = halloc(h, &sl[k].h_evc, B);
+        if (!rc && ev_compact) rc = halloc(h, &sl[k].h_evpacked, B * FT8RX_EVENT_CAP, &sl[k].d_evpacked);
     }
     if (rc) { g_create_err = h->err; ft8rx_destroy(h); return -2; }
     // ---- tables (double precision on the host, rounded once)
@@ -797,15 +846,16 @@ using batchplan::Entry;
 static int batch_begin(ft8rx_handle* h, Entry e, int B, int slot, bool chunked, int16_t** stage) {
     ResultSlot& sl = h->slots[slot];
     h->pnames.clear();
-    if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
+    // (first use of a staging buffer comes before anything of the handle changes: a failed one leaves it as it was)
     if (e != batchplan::DEVICE && need_staging(h)) return -2;
+    if (e == batchplan::HOST_PIPELINED && slot == 1 && need_staging(h, true)) return -2;
+    if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
     if (h->rc_armed && B != h->rc_frames) { set_err(h, "recall entries were set for %d frames, the batch has %d", h->rc_frames, B); return -1; }
     sl.recall = h->rc_armed;                     // ft8rx_set_recall: consumed by this batch
     h->rc_armed = false;
     sl.reports = h->reports;                     // ft8rx_set_reports: the setting this batch is enqueued with
     *stage = h->d_audio;
     if (e == batchplan::HOST_PIPELINED) {
-        if (slot == 1 && !h->d_audio2 && dalloc(h, &h->d_audio2, (size_t)h->max_frames * FT8RX_NSAMP)) return -2;
         *stage = slot ? h->d_audio2 : h->d_audio;
         HIPCHK(h, hipStreamWaitEvent(h->h2d_s, sl.ev_comp, 0));             // the kernels that last read this staging buffer are done
     }
@@ -974,10 +1024,7 @@ int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_
     if (on) {
         if (!(sync_min > 0.0f) || !(sync_min < INFINITY)) { set_err(h, "ft8rx_set_weak: sync_min %g must be a positive score", (double)sync_min); return -1; }
         if (osd_max_hd < 1 || osd_max_hd > 174) { set_err(h, "ft8rx_set_weak: osd_max_hd %d outside [1, 174]", osd_max_hd); return -1; }
-        if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_weak: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
-        if (h->msg_types) { set_err(h, "ft8rx_set_weak: not supported together with msg_types != 0"); return -1; }
-        if (h->ap.np) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_ap_calls"); return -1; }
-        if (h->rc_armed) { set_err(h, "ft8rx_set_weak: not supported together with ft8rx_set_recall"); return -1; }
+        if (refuse_conflict(h, "ft8rx_set_weak", optins::WEAK)) return -1;
         h->weak_sync_min = sync_min; h->weak_osd_max_hd = osd_max_hd;
     }
     h->weak = on != 0;                          // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
@@ -987,10 +1034,7 @@ int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_
 int ft8rx_set_msg_types(ft8rx_handle* h, int32_t mask) {
     if (!h) return -1;
     if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_set_msg_types: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
-    if (mask && h->slots[0].pk_buf) { set_err(h, "ft8rx_set_msg_types: the packed output renders only the reference's message types"); return -1; }
-    if (mask && h->ap.np) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_ap_calls"); return -1; }
-    if (mask && h->rc_armed) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_recall"); return -1; }
-    if (mask && h->weak) { set_err(h, "ft8rx_set_msg_types: not supported together with ft8rx_set_weak"); return -1; }
+    if (mask && refuse_conflict(h, "ft8rx_set_msg_types", optins::MSG_TYPES)) return -1;
     h->msg_types = mask;                        // batches in flight keep the setting they were enqueued with (enqueue_chain reads it)
     return 0;
 }
@@ -1037,9 +1081,7 @@ int ft8rx_set_ap_calls(ft8rx_handle* h, const char* my_call, const char* dx_call
     ApCalls a = h->ap;
     std::string err;
     if (build_ap_patterns(my_call, dx_call, &a, &err)) { set_err(h, "ft8rx_set_ap_calls: %s", err.c_str()); return -1; }
-    if (a.np && h->msg_types) { set_err(h, "ft8rx_set_ap_calls: not supported together with msg_types != 0"); return -1; }
-    if (a.np && h->weak) { set_err(h, "ft8rx_set_ap_calls: not supported together with ft8rx_set_weak"); return -1; }
-    if (a.np && h->slots[0].pk_buf) { set_err(h, "ft8rx_set_ap_calls: not supported on the packed output"); return -1; }
+    if (a.np && refuse_conflict(h, "ft8rx_set_ap_calls", optins::AP_CALLS)) return -1;
     h->ap = a; h->ap_version++;                 // batches in flight keep the setting they were enqueued with (enqueue_chain)
     return 0;
 }
@@ -1100,21 +1142,17 @@ int ft8rx_recall_hypotheses(const ft8rx_recall_entry* entry, uint64_t* words_lo,
 }
 
 static int recall_alloc(ft8rx_handle* h) {
-    if (h->d_rc_src) return 0;
+    if (ws_ready(h, WS_RECALL)) return 0;
     const size_t B = (size_t)h->max_frames, N = B * FT8RX_RECALL_MAX;
-    int rc = 0;
-    rc |= dalloc(h, &h->d_rc_src, N); rc |= dalloc(h, &h->d_rc_srccnt, B); rc |= dalloc(h, &h->d_rc_off, B + 1);
-    rc |= dalloc(h, &h->d_rc_trip, N * 3); rc |= dalloc(h, &h->d_rc_tout, N * 5); rc |= dalloc(h, &h->d_rc_tsd, N);
-    rc |= dalloc(h, &h->d_rc_sgrid, N * 632); rc |= dalloc(h, &h->d_rc_llr, N * 174);
-    for (int k = 0; k < 2 && !rc; k++) {
-        ResultSlot& sl = h->slots[k];
-        rc |= dalloc(h, &sl.d_rc_ent, N); rc |= dalloc(h, &sl.d_rc_cnt, B); rc |= dalloc(h, &sl.d_rc_rec, N);
-        if (!rc && (hipHostMalloc((void**)&sl.h_rc_rec, sizeof(ft8rx_record) * N, hipHostMallocDefault) != hipSuccess ||
-                    hipHostMalloc((void**)&sl.h_rc_cnt, sizeof(int32_t) * B, hipHostMallocDefault) != hipSuccess)) {
-            set_err(h, "ft8rx_set_recall: page-locked result buffers could not be allocated"); rc = -2; }
+    FirstUse F(h, WS_RECALL);
+    F.dev(&h->d_rc_src, N); F.dev(&h->d_rc_srccnt, B); F.dev(&h->d_rc_off, B + 1);
+    F.dev(&h->d_rc_trip, N * 3); F.dev(&h->d_rc_tout, N * 5); F.dev(&h->d_rc_tsd, N);
+    F.dev(&h->d_rc_sgrid, N * 632); F.dev(&h->d_rc_llr, N * 174);
+    for (ResultSlot& sl : h->slots) {
+        F.dev(&sl.d_rc_ent, N); F.dev(&sl.d_rc_cnt, B); F.dev(&sl.d_rc_rec, N);
+        F.host(&sl.h_rc_rec, N); F.host(&sl.h_rc_cnt, B);
     }
-    if (rc) { h->d_rc_src = nullptr; return -2; }
-    return 0;
+    return F.done();
 }
 
 int ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const int32_t* counts, int n_frames) {
@@ -1122,9 +1160,7 @@ int ft8rx_set_recall(ft8rx_handle* h, const ft8rx_recall_entry* entries, const i
     ENTER(h);                                   // batches in flight were enqueued under the previous setting
     if (!entries || n_frames == 0) { h->rc_armed = false; return 0; }
     if (!counts || n_frames < 1 || n_frames > h->max_frames) { set_err(h, "ft8rx_set_recall: n_frames %d outside [1, %d]", n_frames, h->max_frames); return -1; }
-    if (h->msg_types) { set_err(h, "ft8rx_set_recall: not supported together with msg_types != 0"); return -1; }
-    if (h->weak) { set_err(h, "ft8rx_set_recall: not supported together with ft8rx_set_weak"); return -1; }
-    if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_recall: not supported on the packed output"); return -1; }
+    if (refuse_conflict(h, "ft8rx_set_recall", optins::RECALL)) return -1;
     const ft8rx_config& c = h->cfg;
     std::vector<ft8rx_recall_entry> st((size_t)n_frames * FT8RX_RECALL_MAX);
     std::vector<int32_t> cnt(n_frames), off(n_frames + 1, 0);
@@ -1170,17 +1206,13 @@ int ft8rx_set_reports(ft8rx_handle* h, int32_t on) {
     if (!h) return -1;
     ENTER(h);                                   // batches in flight were enqueued under the previous setting
     if (!on) { h->reports = false; return 0; }
-    if (h->slots[0].pk_buf) { set_err(h, "ft8rx_set_reports: not supported together with the packed output (ft8rx_set_packed_output)"); return -1; }
-    if (!h->d_rp_items) {
+    if (refuse_conflict(h, "ft8rx_set_reports", optins::REPORTS)) return -1;
+    if (!ws_ready(h, WS_REPORTS)) {
         const size_t B = (size_t)h->max_frames, N = B << cand_shift(h->cfg);
-        int rc = 0;
-        rc |= dalloc(h, &h->d_rp_items, N); rc |= dalloc(h, &h->d_rp_count, (size_t)batchplan::MAX_CHUNKS);
-        for (int k = 0; k < 2 && !rc; k++) {
-            rc |= dalloc(h, &h->slots[k].d_rp, N);
-            if (!rc && hipHostMalloc((void**)&h->slots[k].h_rp, sizeof(ft8rx_report) * B * h->cfg.max_cands, hipHostMallocDefault) != hipSuccess) {
-                set_err(h, "ft8rx_set_reports: page-locked result buffers could not be allocated"); rc = -2; }
-        }
-        if (rc) { h->d_rp_items = nullptr; return -2; }
+        FirstUse F(h, WS_REPORTS);
+        F.dev(&h->d_rp_items, N); F.dev(&h->d_rp_count, (size_t)batchplan::MAX_CHUNKS);
+        for (ResultSlot& sl : h->slots) { F.dev(&sl.d_rp, N); F.host(&sl.h_rp, B * h->cfg.max_cands); }
+        if (F.done()) return -2;
     }
     h->reports = true;
     return 0;
@@ -1211,7 +1243,11 @@ int ft8rx_set_search_mask(ft8rx_handle* h, const uint8_t* mask, int n_frames) {
     ENTER(h);                                   // batches in flight were enqueued under the previous setting
     if (!mask) { h->use_mask = false; return 0; }
     if (n_frames < 1 || n_frames > h->max_frames) { set_err(h, "ft8rx_set_search_mask: n_frames %d outside [1, %d]", n_frames, h->max_frames); return -1; }
-    if (!h->d_colmask && dalloc(h, &h->d_colmask, (size_t)h->max_frames * NF0MAX)) return -2;
+    if (!ws_ready(h, WS_MASK)) {
+        FirstUse F(h, WS_MASK);
+        F.dev(&h->d_colmask, (size_t)h->max_frames * NF0MAX);
+        if (F.done()) return -2;
+    }
     const int nf0 = h->cfg.f0_hi - h->cfg.f0_lo;
     HIPCHK(h, hipMemsetAsync(h->d_colmask, 0, (size_t)h->max_frames * NF0MAX, h->stream));
     HIPCHK(h, hipMemcpy2DAsync(h->d_colmask, NF0MAX, mask, (size_t)nf0, (size_t)nf0, n_frames, hipMemcpyHostToDevice, h->stream));
@@ -1287,11 +1323,7 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
     ResultSlot* const sl = h->slots;
     sl[0].pk_fence = sl[1].pk_fence = nullptr;
     if (!d_buf0 && !d_buf1) { sl[0].pk_buf = sl[1].pk_buf = nullptr; h->pk_cap = 0; return 0; }
-    if (h->msg_types) { set_err(h, "ft8rx_set_packed_output: msg_types != 0 -- the packed output renders only the reference's message types"); return -1; }
-    if (h->ap.np) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_ap_calls has a call set"); return -1; }
-    if (h->rc_armed) { set_err(h, "ft8rx_set_packed_output: not supported while ft8rx_set_recall entries are pending"); return -1; }
-    if (h->weak) { set_err(h, "ft8rx_set_packed_output: not supported together with ft8rx_set_weak"); return -1; }
-    if (h->reports) { set_err(h, "ft8rx_set_packed_output: not supported together with ft8rx_set_reports"); return -1; }
+    if (refuse_conflict(h, "ft8rx_set_packed_output", optins::PACKED)) return -1;
     if (!d_buf0 || !d_buf1 || d_buf0 == d_buf1 || cap_bytes < sizeof(ft8rx_packed_header)) {
         set_err(h, "ft8rx_set_packed_output: two distinct buffers of at least %zu bytes each are needed", sizeof(ft8rx_packed_header)); return -1; }
     void* in[2] = {d_buf0, d_buf1};
@@ -1304,15 +1336,13 @@ int ft8rx_set_packed_output(ft8rx_handle* h, void* d_buf0, void* d_buf1, uint64_
         dev[k] = (unsigned char*)(at.type == hipMemoryTypeHost ? at.devicePointer : in[k]);
         if (!dev[k] || ((uintptr_t)dev[k] & 15)) { set_err(h, "ft8rx_set_packed_output: buffer %d is not device-accessible / 16-byte aligned", k); return -1; }
     }
-    if (!h->d_pkneed) {
-        int rc = dalloc(h, &h->d_pkneed, (size_t)h->max_frames * ((1 << cand_shift(h->cfg)) / 64));      // k_pack_count's mask words
-        rc |= dalloc(h, &h->d_pknrec, (size_t)h->max_frames);
-        if (rc) return -2;
-        for (int k = 0; k < 2; k++) {
-            if (hipHostMalloc((void**)&sl[k].h_pkhdr, sizeof(ft8rx_packed_header), hipHostMallocDefault) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&sl[k].d_pkhdr, sl[k].h_pkhdr, 0) != hipSuccess) { set_err(h, "ft8rx_set_packed_output: page-locked header could not be allocated"); return -2; }
-            memset(sl[k].h_pkhdr, 0, sizeof(ft8rx_packed_header));
-        }
+    if (!ws_ready(h, WS_PACKED)) {
+        FirstUse F(h, WS_PACKED);
+        F.dev(&h->d_pkneed, (size_t)h->max_frames * ((1 << cand_shift(h->cfg)) / 64));      // k_pack_count's mask words
+        F.dev(&h->d_pknrec, (size_t)h->max_frames);
+        for (int k = 0; k < 2; k++) F.host(&sl[k].h_pkhdr, 1, &sl[k].d_pkhdr);
+        if (F.done()) return -2;
+        for (int k = 0; k < 2; k++) memset(sl[k].h_pkhdr, 0, sizeof(ft8rx_packed_header));
     }
     sl[0].pk_buf = dev[0]; sl[1].pk_buf = dev[1]; h->pk_cap = cap_bytes;
     return 0;
@@ -1368,8 +1398,8 @@ int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_me
                           int n_threads, ft8rx_hashes* table, int32_t* flags) {
     if (!h || !audio || !out || !out_counts) return -1;
     if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "ft8rx_decode_messages: bad n_frames / max_msgs"); return -1; }
-    if (h->msg_types) { set_err(h, "ft8rx_decode_messages: msg_types != 0 -- ft8rx_message holds only the reference's message types"); return -1; }
-    if (h->rc_armed) { set_err(h, "ft8rx_decode_messages: recall entries (ft8rx_set_recall) are not supported; use ft8rx_decode_batch + ft8rx_fetch_recall"); return -1; }
+    if (refuse_conflict(h, "ft8rx_decode_messages", optins::DECODE_MESSAGES,
+                        " (ft8rx_message rows cannot carry it); use ft8rx_decode_batch with ft8rx_package_batch_ext / ft8rx_fetch_recall")) return -1;
     int rc = launch_batch_sync(h, audio, B);
     if (rc) return rc;
     const ft8rx_record* rec; const int32_t* cnt; const ft8rx_event* ev; const int32_t* evc;
@@ -1767,20 +1797,17 @@ int ft8rx_copy_to_host(ft8rx_handle* h, void* dst, const void* d_src, uint64_t b
     return 0;
 }
 
-int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
-                   int refine, float* audio_f32_out) {
-    if (!h || !d_audio || !sigs || !counts) return -1;
-    if (B < 1 || B > h->max_frames || max_sigs < 1 || max_sigs > 256 || refine < 0 || refine > 3) { set_err(h, "ft8rx_subtract: bad n_frames / max_sigs / refine"); return -1; }
-    ENTER(h);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_wf) {              // first use: working buffers for max_frames frames and the GFSK pulse tables (transmitter.py:41-50)
-        const size_t MB = (size_t)h->max_frames;
-        int rc = dalloc(h, &h->d_wf, MB * FT8RX_NSAMP);
-        rc |= dalloc(h, &h->d_part, MB * SUB_NCH * 20);           // also holds the refinement scan: [SUB_MAXSHIFT][SUB_NCH] <= [SUB_NCH][20]
-        rc |= dalloc(h, &h->d_pulse, (size_t)5760);
-        rc |= dalloc(h, &h->d_pc, (size_t)5760);
-        rc |= dalloc(h, &h->d_sigcnt, MB);
-        if (rc) return -2;
+// ft8rx_subtract's workspaces, each group on first use: the float32 working copy, partial sums and GFSK pulse tables
+// (transmitter.py:41-50) for max_frames frames; refine = 2: the decimated baseband copy; refine = 3: an all-ones taper table
+static int subtract_workspaces(ft8rx_handle* h, int refine) {
+    const size_t MB = (size_t)h->max_frames;
+    if (!ws_ready(h, WS_SUB)) {
+        FirstUse F(h, WS_SUB);
+        F.dev(&h->d_wf, MB * FT8RX_NSAMP);
+        F.dev(&h->d_part, MB * SUB_NCH * 20);           // also holds the refinement scan: [SUB_MAXSHIFT][SUB_NCH] <= [SUB_NCH][20]
+        F.dev(&h->d_pulse, (size_t)5760);
+        F.dev(&h->d_pc, (size_t)5760);
+        F.dev(&h->d_sigcnt, MB);
         std::vector<double> pulse(5760), pc(5760);
         const double c = M_PI * sqrt(2.0 / log(2.0)), bt = 2.0;
         double acc = 0.0;
@@ -1789,9 +1816,48 @@ int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs,
             pulse[i] = 0.5 * (erf(c * bt * (tt + 0.5)) - erf(c * bt * (tt - 0.5)));
             acc += pulse[i]; pc[i] = acc;
         }
-        HIPCHK(h, hipMemcpy(h->d_pulse, pulse.data(), sizeof(double) * 5760, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->d_pc, pc.data(), sizeof(double) * 5760, hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(h->d_pulse, pulse.data(), sizeof(double) * 5760, hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(h->d_pc, pc.data(), sizeof(double) * 5760, hipMemcpyHostToDevice));
+        if (F.done()) return -2;
     }
+    if (refine == 2 && !ws_ready(h, WS_SUBD)) {
+        FirstUse F(h, WS_SUBD);
+        F.dev(&h->d_zdec, MB * SUBD_NZ);
+        F.dev(&h->d_model, MB * SUBD_N);
+        F.dev(&h->d_adec, MB * (SUBD_N + 1));
+        F.dev(&h->d_subctx, MB);
+        if (F.done()) return -2;
+    }
+    if (refine == 3 && !ws_ready(h, WS_ONES)) {
+        FirstUse F(h, WS_ONES);
+        F.dev(&h->d_ones, (size_t)100);
+        double ones[100]; for (int i = 0; i < 100; i++) ones[i] = 1.0;
+        FIRST_HIP(F, hipMemcpy(h->d_ones, ones, sizeof(ones), hipMemcpyHostToDevice));
+        if (F.done()) return -2;
+    }
+    return 0;
+}
+
+// The refinement scans of ft8rx_subtract: coarse (10 ms / 0.25 Hz around the decoder's origin, which by the search-grid conventions
+// sits ~75 ms late and ~1.9 Hz low), then fine (2.5 ms / 0.0625 Hz); decimated = refine 2's, the same steps on a decimated baseband
+// copy (kernels/subtract.hpp): time shifts in units of 32 samples
+static SubShifts sub_shifts(bool decimated, bool fine) {
+    SubShifts t;
+    t.stride = 1;             // decimating the scan (tried 8 / 2) aliases neighbouring signals into the sum: 1 of 233 origins locked 70 ms off
+    for (int i = 0; i < SUB_MAXSHIFT; i++) t.shift[i] = 0;
+    if (fine) { t.n = 9; for (int i = 0; i < 9; i++) t.shift[i] = decimated ? SUBD_D * (-4 + i) : -120 + 30 * i; }       // -10 .. +10 ms (decimated: -10.7 .. +10.7 ms in 2.67 ms steps)
+    else if (decimated) { t.n = 15; for (int i = 0; i < 15; i++) t.shift[i] = SUBD_D * (-52 + 4 * i); }                   // -138.7 .. +10.7 ms in 10.7 ms steps
+    else { t.n = 16; for (int i = 0; i < 16; i++) t.shift[i] = -1680 + 120 * i; }                                        // -140 .. +10 ms
+    return t;
+}
+
+int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
+                   int refine, float* audio_f32_out) {
+    if (!h || !d_audio || !sigs || !counts) return -1;
+    if (B < 1 || B > h->max_frames || max_sigs < 1 || max_sigs > 256 || refine < 0 || refine > 3) { set_err(h, "ft8rx_subtract: bad n_frames / max_sigs / refine"); return -1; }
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (subtract_workspaces(h, 0)) return -2;           // the base group; the groups of refine 2 / 3 follow the audio's conversion, below
     if (h->sig_cap < max_sigs) {
         ft8rx_subsig* p = nullptr;
         if (dalloc(h, &p, (size_t)h->max_frames * max_sigs)) return -2;       // the smaller one stays in the handle's allocation list
@@ -1806,39 +1872,12 @@ int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs,
     HIPCHK(h, hipMemcpyAsync(h->d_sigcnt, counts, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
     const size_t n = (size_t)B * FT8RX_NSAMP;
     k_sub_to_f32<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(d_audio, h->d_wf, n);
+    if (subtract_workspaces(h, refine)) return -2;
     const SubTables T{h->d_pulse, h->d_pc};
-    // refinement scans: coarse (10 ms / 0.25 Hz around the decoder's origin, which by the search-grid conventions sits ~75 ms late and
-    // ~1.9 Hz low), then fine (2.5 ms / 0.0625 Hz)
-    SubShifts coarse, fine;
-    coarse.stride = 1; fine.stride = 1;          // decimating the scan (tried 8 / 2) aliases neighbouring signals into the sum: 1 of 233 origins locked 70 ms off
-    coarse.n = 16; for (int i = 0; i < 16; i++) coarse.shift[i] = -1680 + 120 * i;          // -140 .. +10 ms
-    fine.n = 9;    for (int i = 0; i < 9; i++) fine.shift[i] = -120 + 30 * i;               // -10 .. +10 ms
-    for (int i = 9; i < SUB_MAXSHIFT; i++) fine.shift[i] = 0;
-    if (refine == 2 && !h->d_zdec) {
-        const size_t MB = (size_t)h->max_frames;
-        int rc = dalloc(h, &h->d_zdec, MB * SUBD_NZ);
-        rc |= dalloc(h, &h->d_model, MB * SUBD_N);
-        rc |= dalloc(h, &h->d_adec, MB * (SUBD_N + 1));
-        rc |= dalloc(h, &h->d_subctx, MB);
-        if (rc) return -2;
-    }
-    // refine = 2: the same steps on a decimated baseband copy (kernels/subtract.hpp): time shifts in units of 32 samples
-    SubShifts dcoarse, dfine;
-    dcoarse.stride = 1; dfine.stride = 1;
-    dcoarse.n = 15; for (int i = 0; i < 15; i++) dcoarse.shift[i] = SUBD_D * (-52 + 4 * i);        // -138.7 .. +10.7 ms in 10.7 ms steps
-    dcoarse.shift[15] = 0;
-    dfine.n = 9;    for (int i = 0; i < 9; i++) dfine.shift[i] = SUBD_D * (-4 + i);                // -10.7 .. +10.7 ms in 2.67 ms steps
-    for (int i = 9; i < SUB_MAXSHIFT; i++) dfine.shift[i] = 0;
+    const SubShifts coarse = sub_shifts(false, false), fine = sub_shifts(false, true), dcoarse = sub_shifts(true, false), dfine = sub_shifts(true, true);
     const dim3 gmodel((SUBD_N + 255) / 256, B);
     Tables Tones = h->T;                                     // refine = 3: the experiment's slices have no edge tapers
-    if (refine == 3) {
-        if (!h->d_ones) {
-            if (dalloc(h, &h->d_ones, (size_t)100)) return -2;
-            double ones[100]; for (int i = 0; i < 100; i++) ones[i] = 1.0;
-            HIPCHK(h, hipMemcpy(h->d_ones, ones, sizeof(ones), hipMemcpyHostToDevice));
-        }
-        Tones.taper = h->d_ones;
-    }
+    if (refine == 3) Tones.taper = h->d_ones;
     for (int s = 0; s < nmax; s++) {
         if (refine == 3) {
             // Candidate.refine_time_origin (receiver_sub.py:58-72) on the spectrum of the residual so far, then subtract_signal as is

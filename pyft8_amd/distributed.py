@@ -180,20 +180,9 @@ class PackedGather:
     _instances = 0             # PackedGathers constructed in this process: the mailbox prefix
 
     def __init__(self, handle, n_frames, dst=0, group=None, force=False, per_frame=None, repeat=1, depth=4):
-        from . import _lib
-        if getattr(handle.cfg, "msg_types", 0):       # (stand-in handles of the flow tests carry no full config)
-            raise _lib.Ft8rxError("PackedGather: msg_types != 0 is not supported on the packed multi-GPU path (ft8rx_package_packed renders "
-                                  "only the reference's message types); decode with Receiver.decode_frames instead")
-        if getattr(handle.cfg, "ap_my_call", None) or getattr(handle.cfg, "ap_dx_call", None) or any(getattr(handle, "ap_calls", ()) or ()):
-            raise _lib.Ft8rxError("PackedGather: my_call / dx_call (a-priori decoding) is not supported on the packed multi-GPU path; "
-                                  "decode with Receiver.decode_frames instead")
-        if getattr(handle.cfg, "recall", False):
-            raise _lib.Ft8rxError("PackedGather: recall is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
-        if getattr(handle.cfg, "weak", False):
-            raise _lib.Ft8rxError("PackedGather: weak=True is not supported on the packed multi-GPU path; decode with Receiver.decode_frames instead")
-        if getattr(handle.cfg, "reports", False):
-            raise _lib.Ft8rxError("PackedGather: reports=True is not supported on the packed multi-GPU path (the packed output carries no "
-                                  "reports); decode with Receiver.decode_frames instead")
+        from . import _lib, optins
+        # (stand-in handles of the flow tests carry no full config)
+        optins.refuse(optins.PACKED_GATHER, optins.active(handle.cfg, ap_calls=getattr(handle, "ap_calls", ())))
         self._lib, self.h, self.B, self.dst, self.group, self.repeat = _lib, handle, int(n_frames), dst, group, max(1, int(repeat))
         self.depth = max(2, int(depth))
         self.active = dist.is_initialized() and (dist.get_world_size(group) > 1 or force)

@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib
 from . import messages as _m
+from . import optins as _optins
 
 T_CYC, SYM_RATE, SAMP_RATE = 15, 6.25, 12000
 WATERFALL_DOWNSAMPLE = 2
@@ -77,16 +78,12 @@ def config_from_kwargs(sync_score_min=85, max_cands=200, search_freq_range=(100,
 
 
 def set_weak_cfg(cfg, weak, sync_min=None, osd_max_hd=None):
-    """Check the weak-mode kwargs (ft8rx_set_weak) and store them in cfg; refuses the opt-ins that act on
-    records after ipass 1 (msg_types, my_call / dx_call), naming both settings."""
+    """Check the weak-mode kwargs (ft8rx_set_weak) and store them in cfg; refuses what optins.py excludes."""
     if not weak:
         if sync_min is not None or osd_max_hd is not None:
             raise _lib.Ft8rxError("weak_sync_min / weak_osd_max_hd need weak=True")
         return
-    if cfg.msg_types:
-        raise _lib.Ft8rxError("weak=True is not supported together with msg_types != 0")
-    if cfg.ap_my_call or cfg.ap_dx_call:
-        raise _lib.Ft8rxError("weak=True is not supported together with my_call / dx_call (a-priori decoding)")
+    _optins.refuse(_optins.WEAK, _optins.active(cfg))
     if sync_min is not None and not (np.isfinite(float(sync_min)) and float(sync_min) > 0):
         raise _lib.Ft8rxError(f"weak_sync_min={sync_min}: a positive three-block Costas score")
     if osd_max_hd is not None and not 1 <= int(osd_max_hd) <= 174:
@@ -97,12 +94,10 @@ def set_weak_cfg(cfg, weak, sync_min=None, osd_max_hd=None):
 
 
 def set_ap_calls_cfg(cfg, my_call, dx_call):
-    """Check the a-priori calls (ft8rx_set_ap_calls: standard callsigns only) and store them in cfg; refuses msg_types != 0."""
+    """Check the a-priori calls (ft8rx_set_ap_calls: standard callsigns only) and store them in cfg; refuses what optins.py excludes."""
     my_call, dx_call = (my_call or None), (dx_call or None)
-    if (my_call or dx_call) and cfg.msg_types:
-        raise _lib.Ft8rxError("my_call / dx_call (a-priori decoding) is not supported together with msg_types != 0")
-    if (my_call or dx_call) and getattr(cfg, "weak", False):
-        raise _lib.Ft8rxError("my_call / dx_call (a-priori decoding) is not supported together with weak=True")
+    if my_call or dx_call:
+        _optins.refuse(_optins.AP_CALLS, _optins.active(cfg))
     _lib.ap_patterns(my_call, dx_call)                   # raises, naming the argument, for a call that is not a standard one
     cfg.ap_my_call, cfg.ap_dx_call = my_call, dx_call
 
@@ -636,10 +631,8 @@ class Receiver:
         self.reports = bool(extension_knobs.pop("reports", False))
         self._recall_hist = {}                                # cycle start -> complete-frame message dicts (recall = True)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
-        if self.recall and self.cfg.msg_types:
-            raise _lib.Ft8rxError("recall=True is not supported together with msg_types != 0")
-        if self.recall and self.cfg.weak:
-            raise _lib.Ft8rxError("recall=True is not supported together with weak=True")
+        if self.recall:
+            _optins.refuse(_optins.RECALL, _optins.active(self.cfg))
         self.cfg.recall = self.recall
         self.cfg.reports = self.reports
         self.search_h0_range = [self.cfg.h0_lo, self.cfg.h0_hi]
@@ -876,21 +869,11 @@ class Receiver:
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
         use_recall = self.recall or recall is not None
-        if use_recall and self.cfg.msg_types:
-            raise _lib.Ft8rxError("recall is not supported together with msg_types != 0")
-        if use_recall and int(passes) > 1:
-            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with recall")
-        if self.cfg.msg_types and int(passes) > 1:
-            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with msg_types != 0")
-        if self._ap_on() and int(passes) > 1:
-            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with my_call / dx_call (a-priori decoding)")
-        if use_recall and self.cfg.weak:
-            raise _lib.Ft8rxError("recall is not supported together with weak=True")
-        if self.cfg.weak and int(passes) > 1:
-            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with weak=True")
-        if self.reports and int(passes) > 1:
-            raise _lib.Ft8rxError("passes > 1 (subtraction) is not supported with reports=True: the later passes decode a residual "
-                                  "whose spectrum the measurement does not have")
+        on = _optins.active(self.cfg, recall=use_recall)
+        if use_recall:
+            _optins.refuse(_optins.RECALL, on)
+        if int(passes) > 1:
+            _optins.refuse(_optins.PASSES, on)
         local = research == "local"
         h = self._handle(B)
         if use_recall:
@@ -975,13 +958,7 @@ class Receiver:
     def _decode_frames_arrays_locked(self, audio, B, n_threads, passes, subtract_min_snr, sub_pass_osd, research="full"):
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
-        if self.cfg.msg_types:
-            raise _lib.Ft8rxError("decode_frames_arrays returns _lib.MESSAGE_DTYPE rows, which cannot hold the message types of msg_types != 0: "
-                                  "use decode_frames")
-        if self.recall:
-            raise _lib.Ft8rxError("decode_frames_arrays is not supported with recall=True: use decode_frames(..., recall=)")
-        if self.reports:
-            raise _lib.Ft8rxError("decode_frames_arrays returns _lib.MESSAGE_DTYPE rows, which have no place for reports=True: use decode_frames")
+        _optins.refuse(_optins.ARRAYS, _optins.active(self.cfg))
         local = research == "local"
         h = self._handle(B)
         rec, cnt, ev, evc = h.decode_batch(audio)

@@ -3,7 +3,8 @@
 // layer -- unpack / call hashes / ordered replay / duplicate filter / tone encoder -- with (a) a records+events dump of a real frame
 // written by the test (argv[1]: n, nev, then the raw ft8rx_record[n] and ft8rx_event[nev] bytes) and (b) random 77-bit words,
 // multi-threaded, with fresh and with persistent hash tables, including truncating capacities; and (c) checks the batch partition
-// rule (pyft8_amd/csrc/batch_plan.hpp) against a table of plans derived by hand and against its invariants.
+// rule (pyft8_amd/csrc/batch_plan.hpp) against a table of plans derived by hand and against its invariants; and (d) checks the
+// opt-in compatibility table (pyft8_amd/csrc/optins.hpp) against a literal truth table and for symmetry.
 //   make -C oracle asan && oracle/_build/asan_host [dump.bin]
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +14,7 @@
 #include "../pyft8_amd/csrc/ft8_tables.h"
 #include "../pyft8_amd/csrc/host_messages.hpp"
 #include "../pyft8_amd/csrc/batch_plan.hpp"
+#include "../pyft8_amd/csrc/optins.hpp"
 
 // (c) the partition rule.  -> the number of plans checked, or -(line) of the first failed check
 static long check_batch_plans() {
@@ -72,6 +74,38 @@ static long check_batch_plans() {
         for (int k = 0; k <= MAX_CHUNKS; k++) PLAN_CHECK(by_entry[DEVICE].cb[k] == by_entry[HOST_PIPELINED].cb[k]);
     }
 #undef PLAN_CHECK
+    return checked;
+}
+
+// (d) the opt-in table.  -> the number of (asker, setting) pairs checked, or -(line) of the first failed check
+static long check_optins() {
+    using namespace optins;
+    // Which asker (row) was refused while which setting (column: packed output, msg_types, ap_calls, recall, weak, reports) was
+    // active, transcribed check by check from the setters and ft8rx_decode_messages as they stood before the table existed
+    static const int REFUSED[N_ROWS][N_SETTINGS] = {
+        /* ft8rx_set_packed_output */ {0, 1, 1, 1, 1, 1},
+        /* ft8rx_set_msg_types     */ {1, 0, 1, 1, 1, 0},
+        /* ft8rx_set_ap_calls      */ {1, 1, 0, 0, 1, 0},
+        /* ft8rx_set_recall        */ {1, 1, 0, 0, 1, 0},
+        /* ft8rx_set_weak          */ {1, 1, 1, 1, 0, 0},
+        /* ft8rx_set_reports       */ {1, 0, 0, 0, 0, 0},
+        /* ft8rx_decode_messages   */ {0, 1, 0, 1, 0, 0},
+    };
+    static_assert(N_SETTINGS == 6 && N_ROWS == 7, "six settings and one consumer");
+    long checked = 0;
+#define OPTIN_CHECK(x) do { if (!(x)) { fprintf(stderr, "opt-in table: %s fails (asker %d, setting %d)\n", #x, a, s); return -(long)__LINE__; } } while (0)
+    for (int a = 0; a < N_ROWS; a++) for (int s = 0; s < N_SETTINGS; s++) {
+        OPTIN_CHECK(TABLE[a].name && *TABLE[a].name);
+        OPTIN_CHECK((conflict(1u << s, (Id)a) == s) == (REFUSED[a][s] != 0));             // that setting alone
+        OPTIN_CHECK(REFUSED[a][s] || conflict(1u << s, (Id)a) == -1);
+        if (a < N_SETTINGS) OPTIN_CHECK(REFUSED[a][s] == REFUSED[s][a] && !REFUSED[a][a]);   // symmetric, and nothing refuses itself
+        // with everything active the first refused setting in table order is named; with nothing active, none
+        int first = -1;
+        for (int k = N_SETTINGS - 1; k >= 0; k--) if (REFUSED[a][k]) first = k;
+        OPTIN_CHECK(conflict((1u << N_SETTINGS) - 1, (Id)a) == first && conflict(0u, (Id)a) == -1);
+        checked++;
+    }
+#undef OPTIN_CHECK
     return checked;
 }
 
@@ -193,5 +227,8 @@ int main(int argc, char** argv) {
     const long plans = check_batch_plans();
     if (plans < 0) return 20;
     printf("batch plans: %ld checked\n", plans);
+    const long pairs = check_optins();
+    if (pairs < 0) return 21;
+    printf("opt-in table: %ld checked\n", pairs);
     return 0;
 }

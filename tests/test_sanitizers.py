@@ -47,3 +47,5 @@ def test_host_message_layer_under_asan_ubsan(asan_bins, tmp_path):
     assert f"frame dump: {n} candidates" in out and "20 messages per frame" in out and "random words:" in out
     # the batch partition rule (csrc/batch_plan.hpp): 19 plans derived by hand + (603 batch sizes x 8 stream counts x 2 x 3 entries)
     assert f"batch plans: {19 + 603 * 8 * 2 * 3} checked" in out
+    # the opt-in compatibility table (csrc/optins.hpp): 7 askers x 6 settings against a literal truth table, and its symmetry
+    assert "opt-in table: 42 checked" in out
