@@ -30,7 +30,7 @@
  *     multi-GPU        ft8rx_set_packed_output  ft8rx_packed_results  ft8rx_packed_output_fence  ft8rx_package_packed  ft8rx_alloc_host
  *                      ft8rx_free_host  ft8rx_d2h_async / _query / _event  ft8rx_device_pci_bus_id                                     (the gather of decoded messages)
  *   TUNING AND SERVICE (defaults are the measured best; results never depend on them)
- *     ft8rx_set_streams  ft8rx_set_subbatch  ft8rx_set_ladder_mode  ft8rx_set_reject_log  ft8rx_staging_audio  ft8rx_copy_to_host
+ *     ft8rx_set_streams  ft8rx_set_subbatch  ft8rx_set_ladder_mode  ft8rx_set_ladder_grid  ft8rx_set_reject_log  ft8rx_staging_audio  ft8rx_copy_to_host
  *     ft8rx_results_to_device
  *   EXTENSIONS (no counterpart in the reference's receive path)
  *     ft8rx_synth_frames  ft8rx_synth_frames_ex                                        (f-1: workload generator)
@@ -290,6 +290,12 @@ int  ft8rx_set_subbatch(ft8rx_handle* h, int frames);
  *     (one frame: 0.38 vs 0.49 ms host to host).  The event log then also holds CRC-passing words of attempts the ladder would not
  *     have reached; ft8rx_package_batch skips them. */
 int  ft8rx_set_ladder_mode(ft8rx_handle* h, int mode);
+/* Test and tuning seam: the most blocks a ladder kernel is launched with.  Every ladder kernel (ipass-0 and a-priori BP, fine sync,
+ * OSD, reports) runs min(items possible, cap) blocks that stride over a device work list; the compiled cap (32768 blocks) gives
+ * nearly every block one item at most, a small cap makes every block walk many.  cap = 0 restores the compiled default, 1 .. 32768
+ * is taken, anything else is refused; the NaN kernels of OSD run min(512, cap) blocks (also behind ft8rx_osd / ft8rx_osd_ext, whose main kernel keeps one block per vector).  Waits for the batches in flight, then holds
+ * for every later launch.  Records, events and messages do not depend on it (tests/test_gpu_ladder_stride.py). */
+int  ft8rx_set_ladder_grid(ft8rx_handle* h, int cap);
 /* Opt-in message types (FT8RX_MT_* bits; 0 = the default = the reference's rule): with a bit set, a CRC-valid word of that type that
  * passes its plausibility gate (csrc/ft8_dev.h: ft8_valid77_ext) stops a candidate's ladder like any other message; free text and
  * telemetry are never accepted from an OSD trial.  Records / events are then packaged with

@@ -29,6 +29,7 @@ MIN_H0, MAX_H0 = -898, 578                          # FT8RX_MIN_H0 / FT8RX_MAX_H
                                                     # indexing its 750-row grid (search_time_range -36.4 .. +22.6 s, receiver.py:346-347)
 MIN_H0_FD, MAX_H0_FD = -140, 220                    # FT8RX_MIN_H0_FD / _MAX_H0_FD: candidates inside take the frequency-domain fine sync
 MAX_F0, GRID_COLS_WIDE, SPEC_BINS_WIDE, MAX_F0_WIDE = 960, 1920, 96000, 1888      # Handle.grid_cols / .spec_bins hold the loaded variant's
+LADDER_GRID_CAP = 4 * 256 * 32                      # csrc/ft8rx.hip: the compiled grid cap of the ladder kernels (Handle.set_ladder_grid)
 MAX_CANDS_WIDE = 2048                               # FT8RX_MAX_CANDS of the wide build: more than any search range has f0 bins
 
 
@@ -226,6 +227,8 @@ def lib(wide=False):
         L.ft8rx_build_limits(C.byref(mc), C.byref(ec))
         if (mc.value, ec.value) != ((MAX_CANDS_WIDE if wide else MAX_CANDS), EVENT_CAP):
             raise Ft8rxError(f"{path} was built with capacities {(mc.value, ec.value)} (FT8RX_MAX_CANDS, FT8RX_EVENT_CAP)")
+        if not hasattr(L, "ft8rx_set_ladder_grid"):          # the newest entry of include/ft8rx.h: a library built from older source lacks it
+            raise Ft8rxError(f"{path} does not export ft8rx_set_ladder_grid: it was built from older source, build it again")
         _libs[wide] = L
         if _reject_log[0]:                                   # a reject log set before this build was loaded applies to it too
             L.ft8rx_set_reject_log.argtypes = [C.c_char_p]
@@ -560,6 +563,13 @@ class Handle:
     def set_ladder_mode(self, mode):
         """0 (default) = fine-stage BP in ladder order, three launches (throughput); 1 = one launch for the five AP variants (latency)."""
         self._chk(self._L.ft8rx_set_ladder_mode(self._h, int(mode)), "ft8rx_set_ladder_mode")
+
+    def set_ladder_grid(self, cap):
+        """ft8rx_set_ladder_grid: the most blocks a ladder kernel is launched with (0 = the compiled default, LADDER_GRID_CAP; 1 ..
+        LADDER_GRID_CAP is taken, anything else refused).  A test and tuning seam: results do not depend on it."""
+        L = self._L
+        L.ft8rx_set_ladder_grid.argtypes = [C.c_void_p, C.c_int]
+        self._chk(L.ft8rx_set_ladder_grid(self._h, int(cap)), "ft8rx_set_ladder_grid")
 
     def set_search_mask(self, mask):
         """mask[n_frames, f0_hi - f0_lo] (non-zero = search this column, any score > 0) for the following batches, or None = the

@@ -124,12 +124,17 @@ struct ResultSlot {
 
 static ApCalls ap_calls_off() { ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = FT8RX_AP_MAX_HD_DEFAULT; return a; }
 
+#ifndef LADDER_GRID_CAP
+#define LADDER_GRID_CAP (4 * 256 * 32)
+#endif
+
 struct ft8rx_handle {
     ft8rx_config cfg = {};
     int device = 0, max_frames = 0;
     hipStream_t stream = nullptr;
     int n_streams = 2;                   // chunks of a batch run their kernel chains on separate streams
     int ladder_mode = 0;                 // fine-stage BP launches: 0 = ladder order (three launches), 1 = one launch (ft8rx_set_ladder_mode)
+    int ladder_cap = LADDER_GRID_CAP;    // most blocks a ladder kernel is launched with (ladder_grid; ft8rx_set_ladder_grid)
     int msg_types = 0;                   // opt-in message types, FT8RX_MT_* bits (ft8rx_set_msg_types; 0 = the reference's rule)
     // opt-in weak mode (ft8rx_set_weak; off = the reference's stages)
     bool weak = false; float weak_sync_min = FT8RX_WEAK_SYNC_MIN_DEFAULT; int32_t weak_osd_max_hd = FT8RX_WEAK_OSD_MAX_HD_DEFAULT;
@@ -631,13 +636,9 @@ int ft8rx_get_stage_times(ft8rx_handle* h, int* n, const char** names, float* ms
 
 
 // the kernel chain for frames [f0, f0+B) on stream s (all buffers are frame-major, so a chunk is a pointer offset)
-#ifndef LADDER_GRID_CAP
-#define LADDER_GRID_CAP (4 * 256 * 32)
-#endif
-
 // ladder kernels launch a bounded grid that strides over their work list (a few items per block at most): enough blocks to fill the
-// chip four times over, never more than there can be items
-static int ladder_grid(int max_items) { const int cap = LADDER_GRID_CAP; return max_items < cap ? max_items : cap; }
+// chip four times over (LADDER_GRID_CAP; ft8rx_set_ladder_grid lowers the handle's cap), never more than there can be items
+static int ladder_grid(const ft8rx_handle* h, int max_items) { return max_items < h->ladder_cap ? max_items : h->ladder_cap; }
 
 // the sync search of frames [.., B) over the configured h0 range, in windows of SYNC_WIN offsets (one launch for any range up to 14 s):
 // the first window's kernel sets the best score per f0, the later windows' one accumulates into it.  Weak mode (ft8rx_set_weak): the
@@ -673,15 +674,16 @@ static void launch_fine(ft8rx_handle* h, const ft8rx_config& cfg, bool weak, int
 }
 
 // OSD of `grid` blocks -- mode 0: striding over `work` x 10 attempts, mode 2: one raw vector each -- then of the attempts they left on `nanl`: vectors
-// with a NaN (a NaN-poisoned BP output), which the reference's numpy orders with std::sort -- a kernel of their own.  osd_wide: kernels/osd.hpp
+// with a NaN (a NaN-poisoned BP output), which the reference's numpy orders with std::sort -- a kernel of their own, of OSD_NAN_GRID blocks
+// or the handle's cap (ft8rx_set_ladder_grid), in either mode: it strides over a list.  osd_wide: kernels/osd.hpp
 static bool osd_wide(int nflip) { return nflip > OSD_FLIPS_A; }
-static void launch_osd(unsigned mt, int grid, hipStream_t s, int mode, const float* llr, const float* saved, const Att* attB, ft8rx_record* rec,
+static void launch_osd(const ft8rx_handle* h, unsigned mt, int grid, hipStream_t s, int mode, const float* llr, const float* saved, const Att* attB, ft8rx_record* rec,
                        const int32_t* ncand, Att* attO, ft8rx_event* ev, int32_t* evc, const uint32_t* trials, int ntr, int nflip, int max_hd,
                        int sh, WorkList work, WorkList nanl) {
     const bool wide = osd_wide(nflip);
     launch_mt(wide ? k_osd_wide : k_osd, wide ? k_osd_wide_ext : k_osd_ext, mt, grid, s,
               mode, llr, saved, attB, rec, ncand, attO, ev, evc, trials, ntr, nflip, max_hd, sh, work, nanl);
-    launch_mt(wide ? k_osd_nan_wide : k_osd_nan, wide ? k_osd_nan_wide_ext : k_osd_nan_ext, mt, OSD_NAN_GRID, s,
+    launch_mt(wide ? k_osd_nan_wide : k_osd_nan, wide ? k_osd_nan_wide_ext : k_osd_nan_ext, mt, ladder_grid(h, OSD_NAN_GRID), s,
               mode, llr, saved, attB, rec, ncand, attO, ev, evc, trials, ntr, nflip, max_hd, sh, nanl);
 }
 
@@ -695,8 +697,8 @@ static void launch_ap_calls(ft8rx_handle* h, int B, const float* llr0, ft8rx_rec
     hipMemsetAsync(ac, 0, 2 * sizeof(int32_t), s);
     const WorkList cl = {cand_items, ac}, ol = {osd_items, ac + 1};
     k_ap_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, cl);
-    k_bp_ap<<<ladder_grid(B * c.max_cands * h->ap.np), 64, 0, s>>>(llr0, rec, ncand, attO, ev, evc, c, apc, cl, ol);
-    (osd_wide(nflip) ? k_osd_ap_wide : k_osd_ap)<<<ladder_grid(B * c.max_cands * 3), 64, 0, s>>>(
+    k_bp_ap<<<ladder_grid(h, B * c.max_cands * h->ap.np), 64, 0, s>>>(llr0, rec, ncand, attO, ev, evc, c, apc, cl, ol);
+    (osd_wide(nflip) ? k_osd_ap_wide : k_osd_ap)<<<ladder_grid(h, B * c.max_cands * 3), 64, 0, s>>>(
         llr0, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials, nflip, sh, apc, ol);
     k_select_ap<<<(B * S + 255) / 256, 256, 0, s>>>(rec, attO, apc, cl);
 }
@@ -710,7 +712,7 @@ static void launch_reports(ft8rx_handle* h, int B, const cpx* spec, const ft8rx_
     hipMemsetAsync(count, 0, sizeof(int32_t), s);
     const WorkList wl = {items, count};
     k_report_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl, rep);
-    k_report<<<ladder_grid(B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, rep, h->T, sh, wl);
+    k_report<<<ladder_grid(h, B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, rep, h->T, sh, wl);
 }
 
 static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
@@ -743,14 +745,14 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     launch_mt(k_grid_llr, k_grid_llr_ext, mt, XCD_GRID(B, c.max_cands), s, grid, rec, ncand, llr0, c, nullptr, nullptr, nullptr, att0, ev, evc, B);
     k_worklist_att<<<(B * S * 5 + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_BP0]);
     STAGE("bp_grid");
-    launch_mt(k_bp, k_bp_ext, mt, ladder_grid(B * c.max_cands * 5), s, 0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
+    launch_mt(k_bp, k_bp_ext, mt, ladder_grid(h, B * c.max_cands * 5), s, 0, llr0, rec, ncand, nullptr, att0, nullptr, ev, evc, c, c.bp_nc0_a, c.bp_iters_a, wl[WL_BP0], 0, 5);
     STAGE("select0");
     k_select0<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_FINE]);
     STAGE("cycle_fft");
     k_cyc_a<<<dim3(40, B), 256, 0, s>>>(audio, A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, s>>>(A, spec, h->T);
     STAGE("fine");
-    launch_fine(h, c, weak, ladder_grid(B * c.max_cands), s, spec, rec, ncand, llr0, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE],
+    launch_fine(h, c, weak, ladder_grid(h, B * c.max_cands), s, spec, rec, ncand, llr0, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE],
                 c.h0_lo < FT8RX_MIN_H0_FD || c.h0_hi > FT8RX_MAX_H0_FD + 1);      // a search_time_range beyond -6.1 .. +8.3 s
     k_worklist<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, B, sh, wl[WL_BP1]);
     STAGE("bp_fine");
@@ -775,7 +777,7 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
         k_select1<<<(B * S + 255) / 256, 256, 0, s>>>(3, rec, ncand, attG, attB, B, c, wl[WL_OSD]);
     }
     STAGE("osd");
-    launch_osd(mt, ladder_grid(B * c.max_cands * 10), s, 0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials,
+    launch_osd(h, mt, ladder_grid(h, B * c.max_cands * 10), s, 0, llr0, saved, attB, rec, ncand, attO, ev, evc, h->d_trials, h->n_trials,
                osd_nflip(c.osd_single, c.osd_triple), c.osd_max_hd, sh, wl[WL_OSD], wl[WL_OSDNAN]);
     STAGE("select2");
     k_select2<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, attO, B, sh);
@@ -1018,6 +1020,14 @@ int ft8rx_enqueue_batch_host(ft8rx_handle* h, const int16_t* audio, int B) {
 int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > batchplan::MAX_STREAMS) return -1; h->n_streams = n; return 0; }
 int ft8rx_set_subbatch(ft8rx_handle* h, int frames) { if (!h || frames < 0) return -1; h->sub_frames = frames; return 0; }
 int ft8rx_set_ladder_mode(ft8rx_handle* h, int mode) { if (!h || mode < 0 || mode > 1) return -1; h->ladder_mode = mode; return 0; }
+
+int ft8rx_set_ladder_grid(ft8rx_handle* h, int cap) {
+    if (!h) return -1;
+    if (cap < 0 || cap > LADDER_GRID_CAP) { set_err(h, "ft8rx_set_ladder_grid: cap %d outside [0, %d] (0 = the default, %d)", cap, LADDER_GRID_CAP, LADDER_GRID_CAP); return -1; }
+    ENTER(h);                                   // batches in flight were launched under the previous cap
+    h->ladder_cap = cap ? cap : LADDER_GRID_CAP;
+    return 0;
+}
 
 int ft8rx_set_weak(ft8rx_handle* h, int32_t on, float sync_min, int32_t osd_max_hd) {
     if (!h) return -1;
@@ -1689,7 +1699,7 @@ int ft8rx_osd_ext(ft8rx_handle* h, const float* llr, int n, int singleflips, int
     int32_t* d_nan = S.get<int32_t>((size_t)n + 1); NEED(d_nan);            // [0] = length of the list of NaN vectors, then the list
     HIPCHK(h, hipMemsetAsync(d_nan, 0, sizeof(int32_t), h->stream));
     const WorkList nanl{d_nan + 1, d_nan};
-    launch_osd(0, n, h->stream, 2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(),
+    launch_osd(h, 0, n, h->stream, 2, d_in, nullptr, nullptr, nullptr, nullptr, d_att, nullptr, nullptr, d_tr, (int)tr.size(),
                osd_nflip(singleflips, tripleflips), max_hd, cand_shift(h->cfg), WorkList{nullptr, nullptr}, nanl);      // (msg_types do not apply here)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<Att> a(n);

@@ -666,7 +666,9 @@ __global__ __launch_bounds__(FINE_NT, FINE_WV) void k_fine(const cpx* __restrict
     const int n = *work.count;
     // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs, the list holds a frame's candidates next to each other,
     // and their spectrum slices overlap -- so XCD x takes runs of FINE_RUN consecutive items (run = 8 k + x) and a frame's slices are
-    // fetched into one L2 instead of eight (the launch grid is a multiple of 8)
+    // fetched into one L2 instead of eight.  u -> item is a bijection on [0, nu) and every u is visited once whatever gridDim.x is, so
+    // the results do not depend on the grid; only the locality does: with a grid that is no multiple of 8 (max_cands = 150 and one
+    // frame, a small ft8rx_set_ladder_grid cap) a block's later items fall to other values of x than its XCD
 #ifndef FINE_RUN
 #define FINE_RUN 256
 #endif
