@@ -7,7 +7,7 @@ import weakref
 
 import numpy as np
 
-from . import optins
+from . import _abi, optins
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FT8RX_LIB", os.path.join(HERE, "libft8rx.so"))   # FT8RX_LIB: A/B builds of the same ABI
@@ -211,13 +211,9 @@ def lib(wide=False):
             except Exception:
                 pass
         L = C.CDLL(path)
-        L.ft8rx_last_error.restype = C.c_char_p
-        L.ft8rx_last_error.argtypes = [C.c_void_p]
-        L.ft8rx_create.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.ft8rx_destroy.argtypes = [C.c_void_p]
-        L.ft8rx_destroy.restype = None
-        L.ft8rx_staging_audio.restype = C.c_void_p
-        L.ft8rx_staging_audio.argtypes = [C.c_void_p]
+        missing = _abi.declare(L)                            # every prototype of include/ft8rx.h, once (pyft8_amd/_abi.py)
+        if missing:
+            raise Ft8rxError(f"{path} does not export {', '.join(missing)}: it was built from older source, build it again")
         gc, sb, mf = C.c_int32(), C.c_int32(), C.c_int32()
         L.ft8rx_build_info(C.byref(gc), C.byref(sb), C.byref(mf))
         want = (GRID_COLS_WIDE, SPEC_BINS_WIDE, MAX_F0_WIDE) if wide else (GRID_COLS, SPEC_BINS, MAX_F0)
@@ -227,11 +223,8 @@ def lib(wide=False):
         L.ft8rx_build_limits(C.byref(mc), C.byref(ec))
         if (mc.value, ec.value) != ((MAX_CANDS_WIDE if wide else MAX_CANDS), EVENT_CAP):
             raise Ft8rxError(f"{path} was built with capacities {(mc.value, ec.value)} (FT8RX_MAX_CANDS, FT8RX_EVENT_CAP)")
-        if not hasattr(L, "ft8rx_set_ladder_grid"):          # the newest entry of include/ft8rx.h: a library built from older source lacks it
-            raise Ft8rxError(f"{path} does not export ft8rx_set_ladder_grid: it was built from older source, build it again")
         _libs[wide] = L
         if _reject_log[0]:                                   # a reject log set before this build was loaded applies to it too
-            L.ft8rx_set_reject_log.argtypes = [C.c_char_p]
             L.ft8rx_set_reject_log(_reject_log[0].encode())
     return _libs[wide]
 
@@ -247,9 +240,7 @@ def default_config(**kw):
 def device_pci_bus_id(device):
     """PCI address ("0000:c1:00.0") of HIP device `device` (ft8rx_device_pci_bus_id), or None."""
     buf = C.create_string_buffer(64)
-    L = lib()
-    L.ft8rx_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_int]
-    return buf.value.decode() if L.ft8rx_device_pci_bus_id(int(device), buf, 64) == 0 else None
+    return buf.value.decode() if lib().ft8rx_device_pci_bus_id(int(device), buf, 64) == 0 else None
 
 
 def fft_plans():
@@ -259,8 +250,20 @@ def fft_plans():
     return {n: [x for x in p if x] for n, p in zip(names, ps)}
 
 
-def _ptr(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+def _audio(audio, refusal):
+    """Host audio -> C-contiguous int16 [n_frames, 180000]; one frame may come as a vector.  refusal: the caller's wording
+    ({shape} = what was given instead)."""
+    audio = np.ascontiguousarray(audio, np.int16)
+    if audio.ndim == 1:
+        audio = audio[None]
+    if audio.ndim != 2 or audio.shape[1] != NSAMP:
+        raise Ft8rxError(refusal.format(shape=audio.shape))
+    return audio
+
+
+def _words(bits):
+    """77-bit words (Python ints) -> (msg_lo, msg_hi) uint64 arrays, as the records hold them."""
+    return np.array([b & (2 ** 64 - 1) for b in bits], np.uint64), np.array([b >> 64 for b in bits], np.uint64)
 
 
 class Handle:
@@ -280,37 +283,31 @@ class Handle:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
         if self.cfg.msg_types:
             self.set_msg_types(self.cfg.msg_types)
-        if getattr(self.cfg, "ap_max_hd", None) is not None:
+        if self.cfg.ap_max_hd is not None:
             self.set_ap_max_hd(self.cfg.ap_max_hd)
-        if getattr(self.cfg, "ap_my_call", None) or getattr(self.cfg, "ap_dx_call", None):
+        if self.cfg.ap_my_call or self.cfg.ap_dx_call:
             self.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
-        if getattr(self.cfg, "weak", False):
+        if self.cfg.weak:
             self.set_weak(True, self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd)
-        if getattr(self.cfg, "reports", False):
+        if self.cfg.reports:
             self.set_reports(True)
 
     def set_msg_types(self, mask):
         """ft8rx_set_msg_types: the opt-in message types (MT_* bits; 0 = the reference's rule) of the batches enqueued afterwards."""
-        L = self._L
-        L.ft8rx_set_msg_types.argtypes = [C.c_void_p, C.c_int32]
-        self._chk(L.ft8rx_set_msg_types(self._h, int(mask)), "ft8rx_set_msg_types")
+        self._chk(self._L.ft8rx_set_msg_types(self._h, int(mask)), "ft8rx_set_msg_types")
         self.cfg.msg_types = int(mask)
 
     def set_reports(self, on):
         """ft8rx_set_reports: measured SNR / frequency / start time of every DECODED record for the batches enqueued afterwards
         (DESIGN.md section 14); fetch_reports hands them out."""
-        L = self._L
-        L.ft8rx_set_reports.argtypes = [C.c_void_p, C.c_int32]
-        self._chk(L.ft8rx_set_reports(self._h, int(bool(on))), "ft8rx_set_reports")
+        self._chk(self._L.ft8rx_set_reports(self._h, int(bool(on))), "ft8rx_set_reports")
         self.cfg.reports = bool(on)
 
     def fetch_reports(self, B):
         """ft8rx_fetch_reports: reports [B, max_cands] of REPORT_DTYPE of the batch the last fetch / decode_batch handed out, indexed
         like its records (flags 0 = no report: the slot did not decode, or the batch ran with the setting off)."""
         rp = np.zeros((int(B), self.cfg.max_cands), REPORT_DTYPE)
-        L = self._L
-        L.ft8rx_fetch_reports.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._chk(L.ft8rx_fetch_reports(self._h, int(B), rp.ctypes.data), "ft8rx_fetch_reports")
+        self._chk(self._L.ft8rx_fetch_reports(self._h, int(B), rp.ctypes.data), "ft8rx_fetch_reports")
         return rp
 
     def report_probe(self, spec, frame, f0_idx, h0_idx, ttweak, ftweak, words):
@@ -326,22 +323,17 @@ class Handle:
         words = [int(w) for w in words]
         if n < 1 or any(len(c) != n for c in cols) or len(words) != n:
             raise Ft8rxError("report_probe: one frame, f0_idx, h0_idx, ttweak, ftweak and word per candidate")
-        lo = np.array([w & ((1 << 64) - 1) for w in words], np.uint64)
-        hi = np.array([w >> 64 for w in words], np.uint64)
+        lo, hi = _words(words)
         rp = np.zeros(n, REPORT_DTYPE)
-        L = self._L
-        L.ft8rx_report_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
-        self._chk(L.ft8rx_report_probe(self._h, spec.ctypes.data, int(spec.shape[0]), n, *[c.ctypes.data for c in cols], lo.ctypes.data,
-                                       hi.ctypes.data, rp.ctypes.data), "ft8rx_report_probe")
+        self._chk(self._L.ft8rx_report_probe(self._h, spec.ctypes.data, int(spec.shape[0]), n, *[c.ctypes.data for c in cols], lo.ctypes.data,
+                                             hi.ctypes.data, rp.ctypes.data), "ft8rx_report_probe")
         return rp
 
     def set_weak(self, on, sync_min=None, osd_max_hd=None):
         """ft8rx_set_weak: weak-signal sync for the batches enqueued afterwards (None = the library's defaults)."""
-        L = self._L
-        L.ft8rx_set_weak.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32]
         sm = WEAK_SYNC_MIN_DEFAULT if sync_min is None else float(sync_min)
         hd = WEAK_OSD_MAX_HD_DEFAULT if osd_max_hd is None else int(osd_max_hd)
-        self._chk(L.ft8rx_set_weak(self._h, int(bool(on)), sm, hd), "ft8rx_set_weak")
+        self._chk(self._L.ft8rx_set_weak(self._h, int(bool(on)), sm, hd), "ft8rx_set_weak")
         self.cfg.weak = bool(on)
         if on:
             self.cfg.weak_sync_min, self.cfg.weak_osd_max_hd = sync_min, osd_max_hd
@@ -349,9 +341,7 @@ class Handle:
     def set_ap_calls(self, my_call=None, dx_call=None):
         """ft8rx_set_ap_calls: the operator's own call and the DX station's call as ipass-7 a-priori bits (None / "" = unset); applies
         to batches enqueued afterwards."""
-        L = self._L
-        L.ft8rx_set_ap_calls.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-        self._chk(L.ft8rx_set_ap_calls(self._h, (my_call or "").encode(), (dx_call or "").encode()), "ft8rx_set_ap_calls")
+        self._chk(self._L.ft8rx_set_ap_calls(self._h, (my_call or "").encode(), (dx_call or "").encode()), "ft8rx_set_ap_calls")
         self.ap_calls = (my_call or None, dx_call or None)
 
     def ap_calls_probe(self, llr):
@@ -362,15 +352,11 @@ class Handle:
         rec = np.zeros(n, RECORD_DTYPE)
         ev = np.zeros(EVENT_CAP, EVENT_DTYPE)
         ne = C.c_int32(0)
-        L = self._L
-        L.ft8rx_ap_calls_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-        self._chk(L.ft8rx_ap_calls_probe(self._h, llr.ctypes.data, n, rec.ctypes.data, ev.ctypes.data, C.byref(ne)), "ft8rx_ap_calls_probe")
+        self._chk(self._L.ft8rx_ap_calls_probe(self._h, llr.ctypes.data, n, rec.ctypes.data, ev.ctypes.data, C.byref(ne)), "ft8rx_ap_calls_probe")
         return rec, ev, int(ne.value)
 
     def set_ap_max_hd(self, max_hd):
-        L = self._L
-        L.ft8rx_set_ap_max_hd.argtypes = [C.c_void_p, C.c_int32]
-        self._chk(L.ft8rx_set_ap_max_hd(self._h, int(max_hd)), "ft8rx_set_ap_max_hd")
+        self._chk(self._L.ft8rx_set_ap_max_hd(self._h, int(max_hd)), "ft8rx_set_ap_max_hd")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -390,15 +376,10 @@ class Handle:
 
     # ---- whole path
     def decode_batch(self, audio):
-        audio = np.ascontiguousarray(audio, np.int16)
-        if audio.ndim == 1:
-            audio = audio[None]
-        B = audio.shape[0]
-        if audio.ndim != 2 or audio.shape[1] != NSAMP:
-            raise Ft8rxError(f"audio must be int16 [n_frames, {NSAMP}] (15 s at 12 kHz); got shape {audio.shape} -- see receiver.frames_from_ragged")
-        if B < 1:
+        audio = _audio(audio, f"audio must be int16 [n_frames, {NSAMP}] (15 s at 12 kHz); got shape {{shape}} -- see receiver.frames_from_ragged")
+        if len(audio) < 1:
             raise Ft8rxError("empty batch")
-        return self._run(audio, B)
+        return self._run(audio, len(audio))
 
     def _alloc_out(self, B):
         # records / counts are written in full by the library; of the event rows only the used entries are (the rest must read as zero)
@@ -407,43 +388,31 @@ class Handle:
 
     def _run(self, audio, B):
         rec, cnt, ev, evc = self._alloc_out(B)
-        rc = self._L.ft8rx_decode_batch(self._h, _ptr(audio, C.c_int16), B, rec.ctypes.data_as(C.c_void_p), _ptr(cnt, C.c_int32),
-                                      ev.ctypes.data_as(C.c_void_p), _ptr(evc, C.c_int32))
-        self._chk(rc, "ft8rx_decode_batch")
+        self._chk(self._L.ft8rx_decode_batch(self._h, audio.ctypes.data, B, rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data),
+                  "ft8rx_decode_batch")
         return rec, cnt, ev, evc
 
     def decode_messages(self, audio, max_msgs=None, n_threads=None, table=None, return_flags=False):
         """ft8rx_decode_messages: host audio -> (messages[B, max_msgs] of MESSAGE_DTYPE, counts[B]) in one native call.  An
         overflowed event log or message list is warned about (Ft8rxTruncationWarning) and reported per frame with return_flags."""
-        audio = np.ascontiguousarray(audio, np.int16)
-        if audio.ndim == 1:
-            audio = audio[None]
-        B = audio.shape[0]
-        if audio.shape[1] != NSAMP or B > self.max_frames:
-            raise Ft8rxError(f"audio must be [n<={self.max_frames}, {NSAMP}] int16, got {audio.shape}")
+        refusal = f"audio must be [n<={self.max_frames}, {NSAMP}] int16, got {{shape}}"
+        audio = _audio(audio, refusal)
+        if len(audio) > self.max_frames:
+            raise Ft8rxError(refusal.format(shape=audio.shape))
         max_msgs = int(max_msgs or max(1, self.cfg.max_cands))
-        out = np.zeros((B, max_msgs), MESSAGE_DTYPE)
-        oc = np.zeros(B, np.int32)
-        flags = np.zeros(B, np.int32)
-        L = self._L
-        L.ft8rx_decode_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(L.ft8rx_decode_messages(self._h, audio.ctypes.data, int(B), out.ctypes.data, max_msgs, oc.ctypes.data,
-                                          int(n_threads or min(32, os.cpu_count() or 1)), table._t if table is not None else None,
-                                          flags.ctypes.data), "ft8rx_decode_messages")
-        _warn_truncation(flags, "decode_messages")
-        return (out, oc, flags) if return_flags else (out, oc)
+        res = _package("decode_messages", self._L.ft8rx_decode_messages, [self._h, audio.ctypes.data, len(audio)], len(audio), max_msgs,
+                       n_threads or None, table, chk=self._chk)
+        return res if return_flags else res[:2]
 
     def enqueue(self, d_audio_ptr, B):
-        self._chk(self._L.ft8rx_enqueue_batch(self._h, C.c_void_p(d_audio_ptr), int(B)), "ft8rx_enqueue_batch")
+        self._chk(self._L.ft8rx_enqueue_batch(self._h, d_audio_ptr, int(B)), "ft8rx_enqueue_batch")
 
     def enqueue_host(self, audio):
         """Asynchronous decode of host audio (int16 [B, 180000], ideally from pinned_audio()): ft8rx_enqueue_batch_host.  The array
         must stay alive and unchanged until the batch has been fetched."""
         if audio.dtype != np.int16 or audio.ndim != 2 or audio.shape[1] != NSAMP or not audio.flags["C_CONTIGUOUS"]:
             raise Ft8rxError(f"enqueue_host: audio must be a C-contiguous int16 [n_frames, {NSAMP}] array")
-        L = self._L
-        L.ft8rx_enqueue_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        self._chk(L.ft8rx_enqueue_batch_host(self._h, audio.ctypes.data_as(C.c_void_p), int(audio.shape[0])), "ft8rx_enqueue_batch_host")
+        self._chk(self._L.ft8rx_enqueue_batch_host(self._h, audio.ctypes.data, int(audio.shape[0])), "ft8rx_enqueue_batch_host")
 
     def sync(self):
         self._chk(self._L.ft8rx_sync(self._h), "ft8rx_sync")
@@ -457,9 +426,8 @@ class Handle:
                                 or cnt.shape != (B,) or evc.shape != (B,) or cnt.dtype != np.int32 or evc.dtype != np.int32
                                 or not all(a.flags.c_contiguous and a.flags.writeable for a in (rec, cnt, ev, evc))):
             raise Ft8rxError("fetch: `out` is not a result set of this handle and batch size")
-        rc = self._L.ft8rx_fetch_results(self._h, int(B), rec.ctypes.data_as(C.c_void_p), _ptr(cnt, C.c_int32),
-                                       ev.ctypes.data_as(C.c_void_p), _ptr(evc, C.c_int32))
-        self._chk(rc, "ft8rx_fetch_results")
+        self._chk(self._L.ft8rx_fetch_results(self._h, int(B), rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data),
+                  "ft8rx_fetch_results")
         return rec, cnt, ev, evc
 
     def fetch_view(self, B):
@@ -467,9 +435,7 @@ class Handle:
         Valid until two more batches have been enqueued."""
         B = int(B)
         p = [C.c_void_p() for _ in range(4)]
-        L = self._L
-        L.ft8rx_fetch_results_view.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 4
-        self._chk(L.ft8rx_fetch_results_view(self._h, B, *[C.byref(x) for x in p]), "ft8rx_fetch_results_view")
+        self._chk(self._L.ft8rx_fetch_results_view(self._h, B, *[C.byref(x) for x in p]), "ft8rx_fetch_results_view")
         mc = self.cfg.max_cands
 
         def view(ptr, nbytes, dtype, shape):
@@ -479,10 +445,7 @@ class Handle:
 
     def results_to_device(self, B, d_rec, d_cnt, d_ev, d_evc):
         """Latest batch's results -> caller-owned device buffers (raw device pointers; ft8rx_results_to_device)."""
-        L = self._L
-        L.ft8rx_results_to_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
-        self._chk(L.ft8rx_results_to_device(self._h, int(B), C.c_void_p(d_rec), C.c_void_p(d_cnt), C.c_void_p(d_ev), C.c_void_p(d_evc)),
-                  "ft8rx_results_to_device")
+        self._chk(self._L.ft8rx_results_to_device(self._h, int(B), d_rec, d_cnt, d_ev, d_evc), "ft8rx_results_to_device")
 
     def set_packed_output(self, buf0, buf1, cap_bytes, keep=None):
         """ft8rx_set_packed_output: raw pointers (device memory, or page-locked host memory from pinned_bytes()) of the two buffers the
@@ -492,66 +455,47 @@ class Handle:
         memory whose Python owner has already been collected."""
         if buf0 is not None:          # (the library refuses the other settings itself; msg_types may be set in cfg alone)
             optins.refuse(optins.PACKED, optins.active(self.cfg) & {optins.MSG_TYPES})
-        L = self._L
-        L.ft8rx_set_packed_output.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
-        self._chk(L.ft8rx_set_packed_output(self._h, C.c_void_p(buf0 or None), C.c_void_p(buf1 or None), C.c_uint64(int(cap_bytes))),
-                  "ft8rx_set_packed_output")
+        self._chk(self._L.ft8rx_set_packed_output(self._h, buf0 or None, buf1 or None, int(cap_bytes)), "ft8rx_set_packed_output")
         # (the call above has waited for every batch in flight: the previous owners may go now)
         self._packed_keep = {"buffers": keep, "fence": [None, None]} if (buf0 or buf1) else None
 
     def packed_fence(self, which, hip_event, keep=None):
         """ft8rx_packed_output_fence: the next batch that packs into buffer `which` waits (on the device) for this HIP event, e.g.
         torch.cuda.Event(...).cuda_event recorded behind an asynchronous send of the buffer.  keep: the object that owns the event."""
-        L = self._L
-        L.ft8rx_packed_output_fence.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        self._chk(L.ft8rx_packed_output_fence(self._h, int(which), C.c_void_p(hip_event or None)), "ft8rx_packed_output_fence")
+        self._chk(self._L.ft8rx_packed_output_fence(self._h, int(which), hip_event or None), "ft8rx_packed_output_fence")
         if getattr(self, "_packed_keep", None) is not None:
             self._packed_keep["fence"][int(which)] = keep
 
     def d2h_async(self, dst_ptr, src_ptr, nbytes):
         """ft8rx_d2h_async: device -> page-locked host copy on the handle's result-copy stream; -> ticket (d2h_done / d2h_event)."""
-        L = self._L
-        L.ft8rx_d2h_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]
         t = C.c_int32()
-        self._chk(L.ft8rx_d2h_async(self._h, C.c_void_p(dst_ptr), C.c_void_p(src_ptr), C.c_uint64(int(nbytes)), C.byref(t)), "ft8rx_d2h_async")
+        self._chk(self._L.ft8rx_d2h_async(self._h, dst_ptr, src_ptr, int(nbytes), C.byref(t)), "ft8rx_d2h_async")
         return int(t.value)
 
     def d2h_done(self, ticket):
-        L = self._L
-        L.ft8rx_d2h_query.argtypes = [C.c_void_p, C.c_int32]
-        r = L.ft8rx_d2h_query(self._h, int(ticket))
-        if r < 0:
-            raise Ft8rxError(f"ft8rx_d2h_query failed ({r}): {L.ft8rx_last_error(self._h).decode()}")
+        r = self._L.ft8rx_d2h_query(self._h, int(ticket))
+        self._chk(min(r, 0), "ft8rx_d2h_query")
         return r == 1
 
     def d2h_event(self, ticket):
-        L = self._L
-        L.ft8rx_d2h_event.argtypes = [C.c_void_p, C.c_int32]
-        L.ft8rx_d2h_event.restype = C.c_void_p
-        return L.ft8rx_d2h_event(self._h, int(ticket))
+        return self._L.ft8rx_d2h_event(self._h, int(ticket))
 
     def packed_results(self):
         """ft8rx_packed_results: (which of the two packed buffers, its header as a dict) for the batch the last fetch returned."""
         which = C.c_int32()
         hdr = np.zeros(1, PACKED_HEADER_DTYPE)
-        L = self._L
-        L.ft8rx_packed_results.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-        self._chk(L.ft8rx_packed_results(self._h, C.byref(which), hdr.ctypes.data), "ft8rx_packed_results")
+        self._chk(self._L.ft8rx_packed_results(self._h, C.byref(which), hdr.ctypes.data), "ft8rx_packed_results")
         return int(which.value), {k: int(hdr[0][k]) for k in PACKED_HEADER_DTYPE.names}
 
     def pinned_bytes(self, nbytes):
         """uint8 array of page-locked host memory (ft8rx_alloc_host), released with the array."""
         L = self._L
-        L.ft8rx_alloc_host.restype = C.c_void_p
-        L.ft8rx_alloc_host.argtypes = [C.c_void_p, C.c_uint64]
-        L.ft8rx_free_host.argtypes = [C.c_void_p, C.c_void_p]
         p = L.ft8rx_alloc_host(self._h, int(nbytes))
         if not p:
             raise Ft8rxError(f"ft8rx_alloc_host failed: {L.ft8rx_last_error(self._h).decode()}")
         buf = (C.c_uint8 * int(nbytes)).from_address(p)
-        arr = np.frombuffer(buf, dtype=np.uint8)
-        weakref.finalize(buf, L.ft8rx_free_host, None, C.c_void_p(p))
-        return arr
+        weakref.finalize(buf, L.ft8rx_free_host, None, p)
+        return np.frombuffer(buf, dtype=np.uint8)
 
     def set_streams(self, n):
         self._chk(self._L.ft8rx_set_streams(self._h, int(n)), "ft8rx_set_streams")
@@ -567,9 +511,7 @@ class Handle:
     def set_ladder_grid(self, cap):
         """ft8rx_set_ladder_grid: the most blocks a ladder kernel is launched with (0 = the compiled default, LADDER_GRID_CAP; 1 ..
         LADDER_GRID_CAP is taken, anything else refused).  A test and tuning seam: results do not depend on it."""
-        L = self._L
-        L.ft8rx_set_ladder_grid.argtypes = [C.c_void_p, C.c_int]
-        self._chk(L.ft8rx_set_ladder_grid(self._h, int(cap)), "ft8rx_set_ladder_grid")
+        self._chk(self._L.ft8rx_set_ladder_grid(self._h, int(cap)), "ft8rx_set_ladder_grid")
 
     def set_search_mask(self, mask):
         """mask[n_frames, f0_hi - f0_lo] (non-zero = search this column, any score > 0) for the following batches, or None = the
@@ -581,14 +523,13 @@ class Handle:
         nf0 = self.cfg.f0_hi - self.cfg.f0_lo
         if m.ndim != 2 or m.shape[1] != nf0:
             raise Ft8rxError(f"set_search_mask: mask must be [n_frames, {nf0}]")
-        self._chk(self._L.ft8rx_set_search_mask(self._h, m.ctypes.data_as(C.c_void_p), m.shape[0]), "ft8rx_set_search_mask")
+        self._chk(self._L.ft8rx_set_search_mask(self._h, m.ctypes.data, m.shape[0]), "ft8rx_set_search_mask")
 
     def set_recall(self, entries, counts=None):
         """ft8rx_set_recall: recall entries for the NEXT batch (ipass 8) -- entries [n_frames, RECALL_MAX] of
         RECALL_ENTRY_DTYPE with counts [n_frames], or a list (per frame) of RECALL_ENTRY_DTYPE arrays / lists of entries; None
         clears a pending setting.  The batch must have n_frames frames."""
         L = self._L
-        L.ft8rx_set_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         if entries is None:
             self._chk(L.ft8rx_set_recall(self._h, None, None, 0), "ft8rx_set_recall")
             return
@@ -612,15 +553,11 @@ class Handle:
         out; record e belongs to entry e (zero where the entry was skipped)."""
         rec = np.zeros((int(B), RECALL_MAX), RECORD_DTYPE)
         cnt = np.zeros(int(B), np.int32)
-        L = self._L
-        L.ft8rx_fetch_recall.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(L.ft8rx_fetch_recall(self._h, int(B), rec.ctypes.data, cnt.ctypes.data), "ft8rx_fetch_recall")
+        self._chk(self._L.ft8rx_fetch_recall(self._h, int(B), rec.ctypes.data, cnt.ctypes.data), "ft8rx_fetch_recall")
         return rec, cnt
 
     def set_recall_gates(self, max_hd=RECALL_MAX_HD_DEFAULT, min_gap=RECALL_MIN_GAP_DEFAULT):
-        L = self._L
-        L.ft8rx_set_recall_gates.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        self._chk(L.ft8rx_set_recall_gates(self._h, int(max_hd), int(min_gap)), "ft8rx_set_recall_gates")
+        self._chk(self._L.ft8rx_set_recall_gates(self._h, int(max_hd), int(min_gap)), "ft8rx_set_recall_gates")
 
     def recall_probe(self, sgrid, entries):
         """ft8rx_recall_probe: k_recall_score alone on fine grids sgrid [n, 79, 8] for entries [n] -> records [n] (RECORD_DTYPE)."""
@@ -629,9 +566,7 @@ class Handle:
         if len(ent) != len(sg):
             raise Ft8rxError("recall_probe: one grid per entry")
         rec = np.zeros(len(ent), RECORD_DTYPE)
-        L = self._L
-        L.ft8rx_recall_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        self._chk(L.ft8rx_recall_probe(self._h, sg.ctypes.data, ent.ctypes.data, len(ent), rec.ctypes.data), "ft8rx_recall_probe")
+        self._chk(self._L.ft8rx_recall_probe(self._h, sg.ctypes.data, ent.ctypes.data, len(ent), rec.ctypes.data), "ft8rx_recall_probe")
         return rec
 
     def set_profiling(self, on):
@@ -646,12 +581,9 @@ class Handle:
 
     # ---- stage entry points
     def spectrogram(self, audio):
-        audio = np.ascontiguousarray(audio, np.int16)
-        if audio.ndim == 1:
-            audio = audio[None]
-        B = audio.shape[0]
-        g = np.empty((B, GRID_ROWS, self.grid_cols), np.float32)
-        self._chk(self._L.ft8rx_spectrogram(self._h, _ptr(audio, C.c_int16), B, _ptr(g, C.c_float)), "ft8rx_spectrogram")
+        audio = _audio(audio, f"spectrogram: audio must be int16 [n_frames, {NSAMP}], got shape {{shape}}")
+        g = np.empty((len(audio), GRID_ROWS, self.grid_cols), np.float32)
+        self._chk(self._L.ft8rx_spectrogram(self._h, audio.ctypes.data, len(audio), g.ctypes.data), "ft8rx_spectrogram")
         return g
 
     def hop_spectrum(self, window3840):
@@ -659,7 +591,7 @@ class Handle:
         if w.shape != (3840,):
             raise Ft8rxError(f"hop_spectrum needs the last 3840 samples, got shape {w.shape}")
         row = np.empty(self.grid_cols, np.float32)
-        self._chk(self._L.ft8rx_hop_spectrum(self._h, _ptr(w, C.c_int16), _ptr(row, C.c_float)), "ft8rx_hop_spectrum")
+        self._chk(self._L.ft8rx_hop_spectrum(self._h, w.ctypes.data, row.ctypes.data), "ft8rx_hop_spectrum")
         return row
 
     def _grid(self, grid):
@@ -674,8 +606,8 @@ class Handle:
         grid = self._grid(grid)
         B, mc = grid.shape[0], self.cfg.max_cands
         f0 = np.zeros((B, mc), np.int32); h0 = np.zeros((B, mc), np.int32); sc = np.zeros((B, mc), np.float32); cnt = np.zeros(B, np.int32)
-        self._chk(self._L.ft8rx_sync_search(self._h, _ptr(grid, C.c_float), B, _ptr(f0, C.c_int32), _ptr(h0, C.c_int32),
-                                          _ptr(sc, C.c_float), _ptr(cnt, C.c_int32)), "ft8rx_sync_search")
+        self._chk(self._L.ft8rx_sync_search(self._h, grid.ctypes.data, B, f0.ctypes.data, h0.ctypes.data, sc.ctypes.data, cnt.ctypes.data),
+                  "ft8rx_sync_search")
         return f0, h0, sc, cnt
 
     def sync_scores(self, grid, f0_lo, f0_hi, weak=False):
@@ -684,11 +616,8 @@ class Handle:
         grid = self._grid(grid)
         B, n = grid.shape[0], int(f0_hi) - int(f0_lo)
         sc = np.zeros((B, max(n, 1)), np.float32); h0 = np.zeros((B, max(n, 1)), np.int32)
-        L = self._L
         name = "ft8rx_sync_scores_weak" if weak else "ft8rx_sync_scores"
-        fn = getattr(L, name)
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(fn(self._h, grid.ctypes.data, B, int(f0_lo), int(f0_hi), sc.ctypes.data, h0.ctypes.data), name)
+        self._chk(getattr(self._L, name)(self._h, grid.ctypes.data, B, int(f0_lo), int(f0_hi), sc.ctypes.data, h0.ctypes.data), name)
         return sc, h0
 
     def llr_grid(self, grid, frame, f0, h0):
@@ -696,17 +625,14 @@ class Handle:
         frame, f0, h0 = (np.ascontiguousarray(x, np.int32) for x in (frame, f0, h0))
         n = len(f0)
         llr = np.zeros((n, 174), np.float32); sd = np.zeros(n, np.float32); snr = np.zeros(n, np.int32)
-        self._chk(self._L.ft8rx_llr_grid(self._h, _ptr(grid, C.c_float), grid.shape[0], n, _ptr(frame, C.c_int32), _ptr(f0, C.c_int32),
-                                       _ptr(h0, C.c_int32), _ptr(llr, C.c_float), _ptr(sd, C.c_float), _ptr(snr, C.c_int32)), "ft8rx_llr_grid")
+        self._chk(self._L.ft8rx_llr_grid(self._h, grid.ctypes.data, grid.shape[0], n, frame.ctypes.data, f0.ctypes.data, h0.ctypes.data,
+                                       llr.ctypes.data, sd.ctypes.data, snr.ctypes.data), "ft8rx_llr_grid")
         return llr, sd, snr
 
     def cycle_spectrum(self, audio):
-        audio = np.ascontiguousarray(audio, np.int16)
-        if audio.ndim == 1:
-            audio = audio[None]
-        B = audio.shape[0]
-        s = np.empty((B, self.spec_bins), np.complex64)
-        self._chk(self._L.ft8rx_cycle_spectrum(self._h, _ptr(audio, C.c_int16), B, s.ctypes.data_as(C.POINTER(C.c_float))), "ft8rx_cycle_spectrum")
+        audio = _audio(audio, f"cycle_spectrum: audio must be int16 [n_frames, {NSAMP}], got shape {{shape}}")
+        s = np.empty((len(audio), self.spec_bins), np.complex64)
+        self._chk(self._L.ft8rx_cycle_spectrum(self._h, audio.ctypes.data, len(audio), s.ctypes.data), "ft8rx_cycle_spectrum")
         return s
 
     def fine(self, spec, frame, f0, h0, want_sgrid=False, weak=False):
@@ -722,10 +648,8 @@ class Handle:
         llr = np.zeros((n, 174), np.float32); sd = np.zeros(n, np.float32)
         sg = np.zeros((n, 79, 8), np.float32) if want_sgrid else None
         name = "ft8rx_fine_weak" if weak else "ft8rx_fine"
-        self._chk(getattr(self._L, name)(self._h, spec.ctypes.data_as(C.POINTER(C.c_float)), spec.shape[0], n, _ptr(frame, C.c_int32),
-                                         _ptr(f0, C.c_int32), _ptr(h0, C.c_int32), _ptr(ret, C.c_int32), _ptr(tt, C.c_int32), _ptr(ft, C.c_int32),
-                                         _ptr(ns, C.c_int32), _ptr(llr, C.c_float), _ptr(sd, C.c_float), _ptr(snr, C.c_int32),
-                                         _ptr(sg, C.c_float) if want_sgrid else None), name)
+        self._chk(getattr(self._L, name)(self._h, spec.ctypes.data, spec.shape[0], n, *[a.ctypes.data for a in (frame, f0, h0, ret, tt, ft, ns, llr, sd, snr)],
+                                         sg.ctypes.data if want_sgrid else None), name)
         return dict(ret=ret, ttweak=tt, ftweak=ft, nsync=ns, llr=llr, sd=sd, snr=snr, sgrid=sg)
 
     def ldpc(self, llr, max_ncheck0, max_iters):
@@ -734,9 +658,8 @@ class Handle:
         ok, nits, has = (np.zeros(n, np.int32) for _ in range(3))
         lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         out = np.zeros((n, 174), np.float32)
-        self._chk(self._L.ft8rx_ldpc(self._h, _ptr(llr, C.c_float), n, int(max_ncheck0), int(max_iters), _ptr(ok, C.c_int32),
-                                   _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), _ptr(nits, C.c_int32), _ptr(has, C.c_int32),
-                                   _ptr(out, C.c_float)), "ft8rx_ldpc")
+        self._chk(self._L.ft8rx_ldpc(self._h, llr.ctypes.data, n, int(max_ncheck0), int(max_iters),
+                                   *[a.ctypes.data for a in (ok, lo, hi, nits, has, out)]), "ft8rx_ldpc")
         return ok, lo, hi, nits, has, out
 
     def osd(self, llr, singleflips=30, doubleflips=2, tripleflips=0, max_hd=0, want_hd=False):
@@ -744,33 +667,28 @@ class Handle:
         n = len(llr)
         ok, trial, hd = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
         lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
-        self._chk(self._L.ft8rx_osd_ext(self._h, _ptr(llr, C.c_float), n, int(singleflips), int(doubleflips), int(tripleflips), int(max_hd),
-                                      _ptr(ok, C.c_int32), _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), _ptr(trial, C.c_int32),
-                                      _ptr(hd, C.c_int32)), "ft8rx_osd_ext")
+        self._chk(self._L.ft8rx_osd_ext(self._h, llr.ctypes.data, n, int(singleflips), int(doubleflips), int(tripleflips), int(max_hd),
+                                      *[a.ctypes.data for a in (ok, lo, hi, trial, hd)]), "ft8rx_osd_ext")
         return (ok, lo, hi, trial, hd) if want_hd else (ok, lo, hi, trial)
 
     def crc_valid(self, cw91):
         cw91 = np.ascontiguousarray(cw91, np.float32).reshape(-1, 91)
         n = len(cw91)
         res = np.zeros(n, np.int32); lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
-        self._chk(self._L.ft8rx_crc_valid(self._h, _ptr(cw91, C.c_float), n, _ptr(res, C.c_int32), _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64)), "ft8rx_crc_valid")
+        self._chk(self._L.ft8rx_crc_valid(self._h, cw91.ctypes.data, n, res.ctypes.data, lo.ctypes.data, hi.ctypes.data), "ft8rx_crc_valid")
         return res, lo, hi
 
     def valid77(self, bits):
-        lo = np.array([b & (2 ** 64 - 1) for b in bits], np.uint64)
-        hi = np.array([b >> 64 for b in bits], np.uint64)
+        lo, hi = _words(bits)
         out = np.zeros(len(lo), np.int32)
-        self._chk(self._L.ft8rx_valid77(self._h, _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), len(lo), _ptr(out, C.c_int32)), "ft8rx_valid77")
+        self._chk(self._L.ft8rx_valid77(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data), "ft8rx_valid77")
         return out
 
     def valid77_ext(self, bits, mask):
         """ft8rx_valid77_ext: the validity predicate with the opt-in message types `mask` (MSG_TYPE_BITS) on the GPU."""
-        lo = np.array([b & (2 ** 64 - 1) for b in bits], np.uint64)
-        hi = np.array([b >> 64 for b in bits], np.uint64)
+        lo, hi = _words(bits)
         out = np.zeros(len(lo), np.int32)
-        L = self._L
-        L.ft8rx_valid77_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_void_p]
-        self._chk(L.ft8rx_valid77_ext(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), int(mask), out.ctypes.data), "ft8rx_valid77_ext")
+        self._chk(self._L.ft8rx_valid77_ext(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), int(mask), out.ctypes.data), "ft8rx_valid77_ext")
         return out
 
     def subtract(self, d_audio_ptr, n_frames, signals, return_float=False, refine=False, return_origins=False):
@@ -794,10 +712,8 @@ class Handle:
                     arr[f, i]["tones"] = np.asarray(tones, np.uint8)
                     arr[f, i]["fHz"], arr[f, i]["tsec"] = fHz, tsec
         out = np.empty((B, NSAMP), np.float32) if return_float else None
-        L = self._L
-        L.ft8rx_subtract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        self._chk(L.ft8rx_subtract(self._h, C.c_void_p(d_audio_ptr), B, arr.ctypes.data_as(C.c_void_p), _ptr(cnt, C.c_int32), ms,
-                                   int(refine), out.ctypes.data_as(C.c_void_p) if return_float else None), "ft8rx_subtract")
+        self._chk(self._L.ft8rx_subtract(self._h, d_audio_ptr, B, arr.ctypes.data, cnt.ctypes.data, ms, int(refine),
+                                         out.ctypes.data if return_float else None), "ft8rx_subtract")
         if return_origins:                 # (fHz, tsec) per signal after refinement
             return out, [[(float(arr[f, i]["fHz"]), float(arr[f, i]["tsec"])) for i in range(cnt[f])] for f in range(B)]
         return out
@@ -805,25 +721,14 @@ class Handle:
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for
         overlapped DMA.  The memory is released when the array (and every view of it) is garbage collected."""
-        L = self._L
-        L.ft8rx_alloc_host.restype = C.c_void_p
-        L.ft8rx_alloc_host.argtypes = [C.c_void_p, C.c_uint64]
-        L.ft8rx_free_host.argtypes = [C.c_void_p, C.c_void_p]
-        nbytes = int(n_frames) * NSAMP * 2
-        p = L.ft8rx_alloc_host(self._h, nbytes)
-        if not p:
-            raise Ft8rxError(f"ft8rx_alloc_host failed: {L.ft8rx_last_error(self._h).decode()}")
-        buf = (C.c_int16 * (int(n_frames) * NSAMP)).from_address(p)
-        arr = np.frombuffer(buf, dtype=np.int16).reshape(int(n_frames), NSAMP)
-        weakref.finalize(buf, L.ft8rx_free_host, None, C.c_void_p(p))
-        return arr
+        return self.pinned_bytes(int(n_frames) * NSAMP * 2).view(np.int16).reshape(int(n_frames), NSAMP)
 
     def staging_ptr(self):
         return int(self._L.ft8rx_staging_audio(self._h))
 
     def download_audio(self, d_ptr, n_frames):
         out = np.empty((n_frames, NSAMP), np.int16)
-        self._chk(self._L.ft8rx_copy_to_host(self._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(d_ptr), C.c_uint64(out.nbytes)), "ft8rx_copy_to_host")
+        self._chk(self._L.ft8rx_copy_to_host(self._h, out.ctypes.data, d_ptr, out.nbytes), "ft8rx_copy_to_host")
         return out
 
     def synth_frames(self, d_audio_ptr, start, count, n_signals=50, snr_range=(-10.0, 10.0), seed=0x4654385F53594E54, noise=True,
@@ -834,20 +739,14 @@ class Handle:
         recs, truth = synth.device_signal_table(start, count, n_signals, snr_range)
         assert recs.dtype.itemsize == synth.SIGNAL_DTYPE.itemsize
         q = np.ascontiguousarray(synth.pulse_cumsum(), np.float64)
-        self._chk(self._L.ft8rx_synth_frames_ex(self._h, C.c_uint64(seed), int(start), int(count), int(n_signals),
-                                              recs.ctypes.data_as(C.c_void_p), int(recs.dtype.itemsize), _ptr(q, C.c_double),
-                                              C.c_void_p(d_audio_ptr), int(not noise)), "ft8rx_synth_frames")
+        self._chk(self._L.ft8rx_synth_frames_ex(self._h, int(seed), int(start), int(count), int(n_signals), recs.ctypes.data,
+                                              int(recs.dtype.itemsize), q.ctypes.data, d_audio_ptr, int(not noise)), "ft8rx_synth_frames")
         return (truth, recs) if return_table else truth
 
     def math_probe(self, which, x):
-        if which == 2:
-            x = np.ascontiguousarray(x, np.complex64)
-            y = np.empty_like(x)
-            self._chk(self._L.ft8rx_math_probe(self._h, 2, x.ctypes.data_as(C.POINTER(C.c_float)), len(x), y.ctypes.data_as(C.POINTER(C.c_float))), "ft8rx_math_probe")
-            return y
-        x = np.ascontiguousarray(x, np.float32)
+        x = np.ascontiguousarray(x, np.complex64 if which == 2 else np.float32)          # 2: an FFT of length len(x)
         y = np.empty_like(x)
-        self._chk(self._L.ft8rx_math_probe(self._h, int(which), _ptr(x, C.c_float), x.size, _ptr(y, C.c_float)), "ft8rx_math_probe")
+        self._chk(self._L.ft8rx_math_probe(self._h, int(which), x.ctypes.data, len(x) if which == 2 else x.size, y.ctypes.data), "ft8rx_math_probe")
         return y
 
 
@@ -862,14 +761,7 @@ class CallHashTable:
     """Persistent native call-hash table (ft8rx_hashes_*; reference databases.py:8-26) for package_batch(table=...)."""
 
     def __init__(self):
-        L = lib()
-        L.ft8rx_hashes_create.restype = C.c_void_p
-        L.ft8rx_hashes_destroy.argtypes = [C.c_void_p]
-        L.ft8rx_hashes_destroy.restype = None
-        L.ft8rx_hashes_clear.argtypes = [C.c_void_p]
-        L.ft8rx_hashes_add.argtypes = [C.c_void_p, C.c_char_p]
-        L.ft8rx_hashes_size.argtypes = [C.c_void_p]
-        self._t = C.c_void_p(L.ft8rx_hashes_create())
+        self._t = C.c_void_p(lib().ft8rx_hashes_create())
         if not self._t.value:
             raise Ft8rxError("ft8rx_hashes_create failed")
 
@@ -897,16 +789,44 @@ def set_reject_log(path):
     _reject_log[0] = path
     lib()
     for L in _libs.values():
-        L.ft8rx_set_reject_log.argtypes = [C.c_char_p]
         L.ft8rx_set_reject_log(path.encode() if path else None)
 
 
-def _warn_truncation(flags, who):
+def _chk_host(rc, what):
+    if rc != 0:
+        raise Ft8rxError(f"{what} failed ({rc})")
+
+
+def _package(who, fn, head, B, max_msgs, n_threads, table, out=None, dtype=MESSAGE_DTYPE, tail=(), chk=_chk_host):
+    """What every packaging entry shares: fn(*head, out, max_msgs, out_counts, n_threads, table, flags, *tail) into fresh (messages
+    [B, max_msgs] of dtype, counts [B], flags [B]) or the caller's `out`, the thread default, the return code and the truncation
+    warning (raised in the name of who's caller) -> (messages, counts, flags)."""
+    msgs, oc, flags = out if out is not None else (np.zeros((B, max_msgs), dtype), np.zeros(B, np.int32), np.zeros(B, np.int32))
+    if n_threads is None:
+        n_threads = min(32, os.cpu_count() or 1)
+    chk(fn(*head, msgs.ctypes.data, int(max_msgs), oc.ctypes.data, int(n_threads), table._t if table is not None else None,
+           flags.ctypes.data, *tail), fn.__name__)
     if flags.any():
         import warnings
         nev, nmsg = int((flags & PKG_EVENTS_TRUNCATED != 0).sum()), int((flags & PKG_MSG_TRUNCATED != 0).sum())
         warnings.warn(f"{who}: event log overflowed in {nev} frame(s) (> {EVENT_CAP} CRC-passing words: `<...>` strings may differ), "
                       f"message list truncated in {nmsg} frame(s)", Ft8rxTruncationWarning, stacklevel=3)
+    return msgs, oc, flags
+
+
+def _dense(who, rec, cnt, ev, evc, recall=None):
+    """The dense result arrays as the packagers take them -> ([records, counts, events, event_counts (, recall, recall_counts)],
+    n_frames, max_cands)."""
+    arrs = [np.ascontiguousarray(rec), np.ascontiguousarray(cnt, np.int32), np.ascontiguousarray(ev), np.ascontiguousarray(evc, np.int32)]
+    if recall is not None:
+        arrs += [np.ascontiguousarray(recall[0], RECORD_DTYPE), np.ascontiguousarray(recall[1], np.int32)]
+    rec, ev = arrs[0], arrs[2]
+    B, mc = rec.shape
+    if (ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE
+            or (recall is not None and (arrs[4].shape != (B, RECALL_MAX) or arrs[5].shape != (B,)))):
+        what, source = ("records/events", "fetch") if recall is None else ("records/events/recall", "fetch_recall")
+        raise Ft8rxError(f"{who}: {what} are not the arrays returned by decode_batch/{source}")
+    return arrs, B, mc
 
 
 def package_batch(rec, cnt, ev, evc, max_msgs=None, n_threads=None, table=None, return_flags=False, out=None):
@@ -916,95 +836,38 @@ def package_batch(rec, cnt, ev, evc, max_msgs=None, n_threads=None, table=None, 
     message list raises Ft8rxTruncationWarning (warnings module) and is reported per frame in the flags (return_flags=True).
     out = the (messages, counts, flags) arrays of an earlier call with return_flags=True: written in place instead of fresh arrays
     (message slots beyond the counts are stale then)."""
-    rec = np.ascontiguousarray(rec)
-    ev = np.ascontiguousarray(ev)
-    cnt = np.ascontiguousarray(cnt, np.int32)
-    evc = np.ascontiguousarray(evc, np.int32)
-    B, mc = rec.shape
-    if ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE:
-        raise Ft8rxError("package_batch: records/events are not the arrays returned by decode_batch/fetch")
+    arrs, B, mc = _dense("package_batch", rec, cnt, ev, evc)
     if max_msgs is None:
         max_msgs = max(mc, 1)
     if out is not None:
-        out, oc, flags = out
-        if (out.shape != (B, max_msgs) or out.dtype != MESSAGE_DTYPE or oc.shape != (B,) or oc.dtype != np.int32 or flags.shape != (B,)
-                or flags.dtype != np.int32 or not all(a.flags.c_contiguous and a.flags.writeable for a in (out, oc, flags))):
+        msgs, oc, flags = out
+        if (msgs.shape != (B, max_msgs) or msgs.dtype != MESSAGE_DTYPE or oc.shape != (B,) or oc.dtype != np.int32 or flags.shape != (B,)
+                or flags.dtype != np.int32 or not all(a.flags.c_contiguous and a.flags.writeable for a in (msgs, oc, flags))):
             raise Ft8rxError("package_batch: `out` does not fit this batch")
-    else:
-        out = np.zeros((B, max_msgs), MESSAGE_DTYPE)
-        oc = np.zeros(B, np.int32)
-        flags = np.zeros(B, np.int32)
-    if n_threads is None:
-        n_threads = min(32, os.cpu_count() or 1)
-    L = lib()
-    L.ft8rx_package_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_int, C.c_void_p, C.c_void_p]
-    rc = L.ft8rx_package_batch(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, int(B), int(mc), out.ctypes.data,
-                               int(max_msgs), oc.ctypes.data, int(n_threads), table._t if table is not None else None, flags.ctypes.data)
-    if rc != 0:
-        raise Ft8rxError(f"ft8rx_package_batch failed ({rc})")
-    _warn_truncation(flags, "package_batch")
-    return (out, oc, flags) if return_flags else (out, oc)
+    res = _package("package_batch", lib().ft8rx_package_batch, [a.ctypes.data for a in arrs] + [int(B), int(mc)], B, max_msgs, n_threads,
+                   table, out=out)
+    return res if return_flags else res[:2]
 
 
 def package_batch_ext(rec, cnt, ev, evc, mask, max_msgs=None, n_threads=None, table=None, return_flags=False):
     """ft8rx_package_batch_ext: package_batch for records decoded with msg_types = mask -> (messages[B, max_msgs] of
     MESSAGE_EXT_DTYPE, counts[B]).  mask = 0 renders what package_batch renders."""
-    rec = np.ascontiguousarray(rec)
-    ev = np.ascontiguousarray(ev)
-    cnt = np.ascontiguousarray(cnt, np.int32)
-    evc = np.ascontiguousarray(evc, np.int32)
-    B, mc = rec.shape
-    if ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE:
-        raise Ft8rxError("package_batch_ext: records/events are not the arrays returned by decode_batch/fetch")
+    arrs, B, mc = _dense("package_batch_ext", rec, cnt, ev, evc)
     if max_msgs is None:
         max_msgs = max(mc, 1)
-    out = np.zeros((B, max_msgs), MESSAGE_EXT_DTYPE)
-    oc = np.zeros(B, np.int32)
-    flags = np.zeros(B, np.int32)
-    if n_threads is None:
-        n_threads = min(32, os.cpu_count() or 1)
-    L = lib()
-    L.ft8rx_package_batch_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32]
-    rc = L.ft8rx_package_batch_ext(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, int(B), int(mc), out.ctypes.data,
-                                   int(max_msgs), oc.ctypes.data, int(n_threads), table._t if table is not None else None,
-                                   flags.ctypes.data, int(mask))
-    if rc != 0:
-        raise Ft8rxError(f"ft8rx_package_batch_ext failed ({rc})")
-    _warn_truncation(flags, "package_batch_ext")
-    return (out, oc, flags) if return_flags else (out, oc)
+    res = _package("package_batch_ext", lib().ft8rx_package_batch_ext, [a.ctypes.data for a in arrs] + [int(B), int(mc)], B, max_msgs,
+                   n_threads, table, dtype=MESSAGE_EXT_DTYPE, tail=(int(mask),))
+    return res if return_flags else res[:2]
 
 
 def package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, max_msgs=None, n_threads=None, table=None):
     """ft8rx_package_batch_recall: package_batch, then each frame's accepted recall records (fetch_recall) after its ladder messages,
     in entry order, unless the frame has the text already -> (messages[B, max_msgs], counts[B])."""
-    rec = np.ascontiguousarray(rec)
-    ev = np.ascontiguousarray(ev)
-    cnt = np.ascontiguousarray(cnt, np.int32)
-    evc = np.ascontiguousarray(evc, np.int32)
-    rrec = np.ascontiguousarray(rrec, RECORD_DTYPE)
-    rcnt = np.ascontiguousarray(rcnt, np.int32)
-    B, mc = rec.shape
-    if ev.shape != (B, EVENT_CAP) or rec.dtype != RECORD_DTYPE or ev.dtype != EVENT_DTYPE or rrec.shape != (B, RECALL_MAX) or rcnt.shape != (B,):
-        raise Ft8rxError("package_batch_recall: records/events/recall are not the arrays returned by decode_batch/fetch_recall")
+    arrs, B, mc = _dense("package_batch_recall", rec, cnt, ev, evc, recall=(rrec, rcnt))
     if max_msgs is None:
         max_msgs = max(mc, 1) + RECALL_MAX
-    out = np.zeros((B, max_msgs), MESSAGE_DTYPE)
-    oc = np.zeros(B, np.int32)
-    flags = np.zeros(B, np.int32)
-    if n_threads is None:
-        n_threads = min(32, os.cpu_count() or 1)
-    L = lib()
-    L.ft8rx_package_batch_recall.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                                C.c_void_p]
-    rc = L.ft8rx_package_batch_recall(rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data, rrec.ctypes.data, rcnt.ctypes.data,
-                                      int(B), int(mc), out.ctypes.data, int(max_msgs), oc.ctypes.data, int(n_threads),
-                                      table._t if table is not None else None, flags.ctypes.data)
-    if rc != 0:
-        raise Ft8rxError(f"ft8rx_package_batch_recall failed ({rc})")
-    _warn_truncation(flags, "package_batch_recall")
-    return out, oc
+    return _package("package_batch_recall", lib().ft8rx_package_batch_recall, [a.ctypes.data for a in arrs] + [int(B), int(mc)], B, max_msgs,
+                    n_threads, table)[:2]
 
 
 def recall_hypotheses(entry):
@@ -1012,9 +875,7 @@ def recall_hypotheses(entry):
     [] for an entry that does not qualify."""
     e = np.asarray(entry, RECALL_ENTRY_DTYPE).reshape(1)
     lo, hi = np.zeros(126, np.uint64), np.zeros(126, np.uint64)
-    L = lib()
-    L.ft8rx_recall_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    n = L.ft8rx_recall_hypotheses(e.ctypes.data, lo.ctypes.data, hi.ctypes.data)
+    n = lib().ft8rx_recall_hypotheses(e.ctypes.data, lo.ctypes.data, hi.ctypes.data)
     if n < 0:
         raise Ft8rxError("ft8rx_recall_hypotheses failed")
     return [(int(hi[i]) << 64) | int(lo[i]) for i in range(n)]
@@ -1114,18 +975,12 @@ def package_packed(buf, frame_lo=0, n_frames=None, max_msgs=None, n_threads=None
     n = pk.n_frames - frame_lo if n_frames is None else int(n_frames)
     if max_msgs is None:
         max_msgs = max(pk.max_cands, 1)
-    out = np.zeros((max(n, 0), max_msgs), MESSAGE_DTYPE)
-    oc = np.zeros(max(n, 0), np.int32)
-    flags = np.zeros(max(n, 0), np.int32)
     if n > 0:
-        L = lib()
-        L.ft8rx_package_packed.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        rc = L.ft8rx_package_packed(pk.buf.ctypes.data, C.c_uint64(pk.nbytes), int(frame_lo), n, out.ctypes.data, int(max_msgs), oc.ctypes.data,
-                                    int(n_threads or min(32, os.cpu_count() or 1)), table._t if table is not None else None, flags.ctypes.data)
-        if rc != 0:
-            raise Ft8rxError(f"ft8rx_package_packed failed ({rc})")
-        _warn_truncation(flags, "package_packed")
-    return (out, oc, flags) if return_flags else (out, oc)
+        res = _package("package_packed", lib().ft8rx_package_packed, [pk.buf.ctypes.data, pk.nbytes, int(frame_lo), n], n, max_msgs,
+                       n_threads or None, table)
+    else:
+        res = (np.zeros((0, max_msgs), MESSAGE_DTYPE), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    return res if return_flags else res[:2]
 
 
 def merge_messages(out, out_counts, add, add_counts, pass_tag, drop_osd=False):
@@ -1139,13 +994,9 @@ def merge_messages(out, out_counts, add, add_counts, pass_tag, drop_osd=False):
         raise Ft8rxError("merge_messages: out_counts must be a contiguous int32 array (it is updated in place)")
     fresh = np.zeros_like(add)
     fc = np.zeros(add.shape[0], np.int32)
-    L = lib()
-    L.ft8rx_merge_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p]
-    rc = L.ft8rx_merge_messages(out.ctypes.data, out_counts.ctypes.data, int(out.shape[1]), add.ctypes.data, add_counts.ctypes.data,
-                                int(add.shape[1]), int(out.shape[0]), int(pass_tag), int(bool(drop_osd)), fresh.ctypes.data, fc.ctypes.data)
-    if rc != 0:
-        raise Ft8rxError(f"ft8rx_merge_messages failed ({rc})")
+    _chk_host(lib().ft8rx_merge_messages(out.ctypes.data, out_counts.ctypes.data, int(out.shape[1]), add.ctypes.data, add_counts.ctypes.data,
+                                         int(add.shape[1]), int(out.shape[0]), int(pass_tag), int(bool(drop_osd)), fresh.ctypes.data,
+                                         fc.ctypes.data), "ft8rx_merge_messages")
     return fresh, fc
 
 
@@ -1162,9 +1013,7 @@ def subtraction_list(msgs, mcnt, rec, min_snr):
     cap = max(1, int(mcnt.max()) if B else 1)
     arr = np.zeros((B, cap), SUBSIG_DTYPE)
     cnt = np.zeros(B, np.int32)
-    L = lib()
-    L.ft8rx_subtraction_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    most = L.ft8rx_subtraction_list(msgs.ctypes.data, mcnt.ctypes.data, int(msgs.shape[1]), rec.ctypes.data, int(rec.shape[1]), int(B),
+    most = lib().ft8rx_subtraction_list(msgs.ctypes.data, mcnt.ctypes.data, int(msgs.shape[1]), rec.ctypes.data, int(rec.shape[1]), int(B),
                                     int(math.floor(min_snr)), arr.ctypes.data, int(cap), cnt.ctypes.data)
     if most < 0:
         raise Ft8rxError(f"ft8rx_subtraction_list failed ({most})")
@@ -1179,9 +1028,7 @@ def encode_tones(msg_lo, msg_hi):
     lo = np.ascontiguousarray(msg_lo, np.uint64).ravel()
     hi = np.ascontiguousarray(msg_hi, np.uint64).ravel()
     out = np.zeros((len(lo), 79), np.uint8)
-    L = lib()
-    L.ft8rx_encode_tones.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    if L.ft8rx_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
+    if lib().ft8rx_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
         raise Ft8rxError("ft8rx_encode_tones failed")
     return out
 
@@ -1190,7 +1037,6 @@ def ap_patterns(my_call=None, dx_call=None):
     """ft8rx_ap_patterns (host only): the ipass-7 patterns ap 5..10 -> (bits[6, 174], mask[6, 174]) uint8 in LLR order; raises
     Ft8rxError naming the argument for a call that is not a standard callsign."""
     L = lib()
-    L.ft8rx_ap_patterns.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
     bits, mask = np.zeros((6, 174), np.uint8), np.zeros((6, 174), np.uint8)
     if L.ft8rx_ap_patterns((my_call or "").encode(), (dx_call or "").encode(), bits.ctypes.data, mask.ctypes.data) != 0:
         raise Ft8rxError(L.ft8rx_last_error(None).decode())

@@ -22,7 +22,6 @@ C_NAME = dict(ENTRY, **{optins.PACKED: "the packed output (ft8rx_set_packed_outp
 def _set_packed(h, bufs, cap):
     """The library's own call: _lib.Handle.set_packed_output answers msg_types != 0 itself, before the library is asked."""
     L = h._L
-    L.ft8rx_set_packed_output.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     p = [ctypes.c_void_p(b.ctypes.data) if b is not None else None for b in bufs]
     h._chk(L.ft8rx_set_packed_output(h._h, p[0], p[1], ctypes.c_uint64(cap)), "ft8rx_set_packed_output")
 

@@ -1813,3 +1813,106 @@ def test_bench_plain_line(tmp_path):
     counts = np.load(os.path.join(str(tmp_path), "message_counts.npy"))
     assert len(counts) == 32 and abs(counts.mean() - d["config"]["messages_per_frame"]) < 1e-9
     assert len(np.load(os.path.join(str(tmp_path), "msg_text.npy"))) == int(counts.sum()) > 0
+
+
+def test_binding_reaches_every_entry_on_both_layouts():
+    """Every foreign call takes its prototype from one table (pyft8_amd/_abi.py).  The wrappers below were called without one before
+    that table existed and are reached by no other GPU test on the layout named -- so here each runs once, on a one-frame handle,
+    with the smallest shapes (one golden frame, n = 1 vectors), and is compared with the same call on the other layout or with the
+    CPU oracle:
+      default layout (libft8rx.so): sync, set_profiling, stage_times, hop_spectrum;
+      wide layout (libft8rx_wide.so, f0_hi = 1800): sync, set_profiling, stage_times, hop_spectrum, sync_search, llr_grid, fine
+        (both scans), ldpc, osd, crc_valid, valid77, math_probe, staging_ptr, synth_frames, download_audio, enqueue, fetch,
+        set_streams, set_subbatch, set_ladder_mode, set_search_mask;
+      and Handle.decode_messages with a CallHashTable on the wide handle: a table made by the default build, updated by the wide
+        build's packager."""
+    from pyft8_amd import _lib
+    audio = load_golden("test_09")[0]
+    hd, hw = _lib.Handle(max_frames=1), _lib.Handle(_lib.default_config(f0_hi=1800), max_frames=1)
+    try:
+        assert hw.wide and not hd.wide
+        ocfg_w = O.default_config(f0_hi=1800)
+        # stage entries: wide against the oracle's wide build, and against the default layout where the two overlap
+        row_d, row_w = hd.hop_spectrum(audio[:3840]), hw.hop_spectrum(audio[:3840])
+        assert row_w.shape == (1920,) and bits_equal(row_d, row_w[:976])
+        grid_d, grid_w, spec_d, spec_w = hd.spectrogram(audio), hw.spectrogram(audio), hd.cycle_spectrum(audio), hw.cycle_spectrum(audio)
+        f0, h0, sc, cnt = hw.sync_search(grid_w)
+        want = O.sync_search(grid_w[0], ocfg_w)
+        n = int(cnt[0])
+        assert n == len(want) > 0 and list(f0[0, :n]) == [c.f0_idx for c in want] and list(h0[0, :n]) == [c.h0_idx for c in want]
+        assert bits_equal(sc[0, :n], np.array([c.score for c in want], np.float32))
+        k = int(np.argmax(f0[0, :n] < 900))                                # the best candidate both layouts hold
+        one = (np.zeros(1, np.int32), f0[0, k:k + 1], h0[0, k:k + 1])
+        for a, b in zip(hw.llr_grid(grid_w, *one), hd.llr_grid(grid_d, *one)):
+            assert bits_equal(a, b) if a.dtype == np.float32 else np.array_equal(a, b)
+        for weak in (False, True):
+            rw, rd = hw.fine(spec_w, *one, want_sgrid=True, weak=weak), hd.fine(spec_d, *one, want_sgrid=True, weak=weak)
+            for key in ("ret", "ttweak", "ftweak", "nsync", "snr"):
+                assert np.array_equal(rw[key], rd[key]), (weak, key)
+            assert bits_equal(rw["sgrid"], rd["sgrid"]) and bits_equal(rw["llr"], rd["llr"]) and bits_equal(rw["sd"], rd["sd"]), weak
+        w = O.fine(spec_w[0], int(one[1][0]), int(one[2][0]), ocfg_w)
+        rw = hw.fine(spec_w, *one, want_sgrid=True)
+        assert (rw["ret"][0], rw["ttweak"][0], rw["ftweak"][0], rw["nsync"][0]) == (w["ret"], w["ttweak"], w["ftweak"], w["nsync"])
+        assert bits_equal(rw["sgrid"][0], w["sgrid"])
+        # per-vector entries, n = 1: the same answer from both builds, and the oracle's
+        gold = load_golden("test_09")[1]
+        llr = gold["bp_llr_in"][:1]
+        for a, b in zip(hw.ldpc(llr, 35, 5), hd.ldpc(llr, 35, 5)):
+            assert bits_equal(a, b) if a.dtype == np.float32 else np.array_equal(a, b)
+        assert bool(hw.ldpc(llr, 35, 5)[0][0]) == O.ldpc(llr[0], 35, 5)[0]
+        x = llr * np.float32(0.5)
+        ow, od = hw.osd(x, 30, 2, want_hd=True), hd.osd(x, 30, 2, want_hd=True)
+        assert all(np.array_equal(a, b) for a, b in zip(ow, od)) and bool(ow[0][0]) == O.osd(x[0], 30, 2)[0]
+        word = 6257895 << 49 | 1 << 3 | 1
+        from pyft8_amd import synth
+        m91 = (word << 14) | synth.crc14(word)
+        cw = np.array([[1.0 if (m91 >> (90 - i)) & 1 else -1.0 for i in range(91)]], np.float32)
+        cr = hw.crc_valid(cw)
+        assert all(np.array_equal(a, b) for a, b in zip(cr, hd.crc_valid(cw)))
+        assert int(cr[0][0]) == O.crc_valid91(cw[0])[0] != 0 and (int(cr[2][0]) << 64) | int(cr[1][0]) == word
+        assert [bool(v) for v in hw.valid77([word, 1])] == [bool(v) for v in hd.valid77([word, 1])] == [O.valid77(word), O.valid77(1)]
+        t = np.float32([0.0, 0.5, -3.0, 40.0])
+        assert bits_equal(hw.math_probe(1, t), O.tanhf(t)) and bits_equal(hw.math_probe(0, t[1:2]), O.log10f(t[1:2]))
+        z = (np.arange(320) * (1 + 0.5j)).astype(np.complex64)
+        assert bits_equal(hw.math_probe(2, z).view(np.float32), hd.math_probe(2, z).view(np.float32))
+        # device-resident audio, the pipelined entries and the service settings on the wide handle
+        ptr_w, ptr_d = hw.staging_ptr(), hd.staging_ptr()
+        hw.synth_frames(ptr_w, 4100, 1, n_signals=6)
+        hd.synth_frames(ptr_d, 4100, 1, n_signals=6)
+        frame = hw.download_audio(ptr_w, 1)
+        assert frame.any() and frame.tobytes() == hd.download_audio(ptr_d, 1).tobytes()
+        want = hw.decode_batch(frame)
+        assert want[1][0] > 0
+
+        def same(a, b):
+            return (np.array_equal(a[1], b[1]) and np.array_equal(a[3], b[3]) and a[0][0, :a[1][0]].tobytes() == b[0][0, :b[1][0]].tobytes()
+                    and sorted(a[2][0, :a[3][0]].tolist()) == sorted(b[2][0, :b[3][0]].tolist()))
+        hw.set_streams(1); hw.set_subbatch(1); hw.set_ladder_mode(0)
+        stages = []
+        for h, p in ((hw, ptr_w), (hd, ptr_d)):
+            h.set_profiling(True)
+            h.enqueue(p, 1)
+            h.sync()
+            times = h.stage_times()
+            h.set_profiling(False)
+            assert len(times) >= 5 and all(isinstance(k, str) and k and v >= 0 for k, v in times.items()), times
+            stages.append(list(times))
+        assert stages[0] == stages[1]                                       # the same chain, stage for stage, on both layouts
+        assert same(hw.fetch(1), want)
+        hw.set_streams(2); hw.set_subbatch(256)
+        keep = np.zeros((1, hw.cfg.f0_hi - hw.cfg.f0_lo), np.uint8)
+        cols = want[0][0, :want[1][0]]["f0_idx"][:3].astype(int) - hw.cfg.f0_lo
+        keep[0, cols] = 1
+        hw.set_search_mask(keep)
+        masked = hw.decode_batch(frame)
+        hw.set_search_mask(None)
+        assert 0 < masked[1][0] <= 3 and set(masked[0][0, :masked[1][0]]["f0_idx"].astype(int) - hw.cfg.f0_lo) <= set(cols.tolist())
+        assert same(hw.decode_batch(frame), want)
+        # the cross-library pointer: the wide build's packager updates a table the default build made
+        table, fresh = _lib.CallHashTable(), _lib.CallHashTable()
+        msgs, mcnt = hw.decode_messages(audio, table=table)
+        rec, cnt, ev, evc = hw.decode_batch(audio)
+        ref, rcnt = _lib.package_batch(rec, cnt, ev, evc, table=fresh)
+        assert mcnt[0] == rcnt[0] > 0 and msgs[0, :mcnt[0]].tobytes() == ref[0, :rcnt[0]].tobytes() and len(table) == len(fresh) > 0
+    finally:
+        hd.close(); hw.close()

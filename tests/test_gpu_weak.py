@@ -1,7 +1,6 @@
 """Weak mode (ft8rx_set_weak) on the GPU: the default path is untouched, k_sync3 and k_fine_weak are bit-exact
 against their numpy twin (tests/weak_twin.py), a batch's fine fields equal the probe's, and weak mode decodes signals at -20 / -19 dB
 that the default misses without adding false decodes on noise, on BASELINE config 1 or on the two recordings."""
-import ctypes
 import json
 
 import numpy as np
@@ -259,7 +258,6 @@ def test_refusals():
     try:
         h.set_weak(True)
         with pytest.raises(_lib.Ft8rxError, match="weak"):
-            h._L.ft8rx_set_msg_types.argtypes = [ctypes.c_void_p, ctypes.c_int32]
             h._chk(h._L.ft8rx_set_msg_types(h._h, 1), "ft8rx_set_msg_types")
         with pytest.raises(_lib.Ft8rxError, match="weak"):
             h.set_ap_calls("K1ABC", None)

@@ -575,8 +575,6 @@ def test_packed_results_render_the_same_messages_as_the_dense_arrays():
     # malformed input: bad magic, cut short, overflow flag, offsets beyond the runs
     L = _lib.lib()
     out = np.zeros((4, 200), _lib.MESSAGE_DTYPE); oc = np.zeros(4, np.int32)
-    L.ft8rx_package_packed.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 
     def call(b, lo=0, n=4):
         return L.ft8rx_package_packed(b.ctypes.data, ctypes.c_uint64(len(b)), lo, n, out.ctypes.data, 200, oc.ctypes.data, 1, None, None)

@@ -1,8 +1,6 @@
 """Recall decoding of stations heard 30 s earlier (ipass 8, ft8rx_set_recall), the host side: hypothesis lists (native and the numpy
 twin), which entries qualify, entries from message rows and dicts, the packagers' rendering of ipass-8 records, and the ABI in
 both libraries.  No GPU needed."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -73,12 +71,11 @@ SYMBOLS = ["ft8rx_set_recall", "ft8rx_fetch_recall", "ft8rx_set_recall_gates", "
 
 @pytest.mark.parametrize("wide", [False, True])
 def test_abi_symbols(wide):
-    L = C.CDLL(_lib.LIB_PATH_WIDE if wide else _lib.LIB_PATH)
+    L = _lib.lib(wide)
     for s in SYMBOLS:
         assert hasattr(L, s), s
     e = _entry(("K1ABC", "W9XYZ", "-12"))
     lo, hi = np.zeros(126, np.uint64), np.zeros(126, np.uint64)
-    L.ft8rx_recall_hypotheses.argtypes = [C.c_void_p] * 3
     assert L.ft8rx_recall_hypotheses(e.ctypes.data, lo.ctypes.data, hi.ctypes.data) == 125
 
 

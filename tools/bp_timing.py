@@ -2,7 +2,6 @@
 attempt adds the shader cycles between marks.  All four k_bp launches of a batch together.  Usage on the GPU box:
     python -c "from pyft8_amd import _lib; _lib.build_variant('build/ab/bp_timing.so', ['-DBP_TIMING'])"
     FT8RX_LIB=build/ab/bp_timing.so python tools/bp_timing.py"""
-import ctypes as C
 import os
 import sys
 
@@ -24,7 +23,6 @@ def main():
     h.set_streams(1)
     h.enqueue(ptr, B); h.sync()
     L = _lib.lib()
-    L.ft8rx_debug_bp_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     out = np.zeros(8, np.uint64)
     L.ft8rx_debug_bp_times(h._h, None, 1)
     h.enqueue(ptr, B); h.sync()

@@ -2,7 +2,6 @@
 wave 0 of every k_fine block accumulates shader cycles between marks.  Usage on the GPU box:
     python -c "from pyft8_amd import _lib; _lib.build_variant('build/ab/fine_timing.so', ['-DFINE_TIMING'])"
     FT8RX_LIB=build/ab/fine_timing.so python tools/fine_timing.py"""
-import ctypes as C
 import os
 import sys
 
@@ -29,7 +28,6 @@ def main():
     h.set_streams(1)
     h.enqueue(ptr, B); h.sync()
     L = _lib.lib()
-    L.ft8rx_debug_fine_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     out = np.zeros(32, np.uint64)
     L.ft8rx_debug_fine_times(h._h, None, 1)
     h.enqueue(ptr, B); h.sync()

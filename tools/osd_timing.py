@@ -2,7 +2,6 @@
 attempt accumulates shader cycles between marks.  Usage on the GPU box:
     python -c "from pyft8_amd import _lib; _lib.build_variant('build/ab/osd_timing.so', ['-DOSD_TIMING'])"
     FT8RX_LIB=build/ab/osd_timing.so python tools/osd_timing.py"""
-import ctypes as C
 import os
 import sys
 
@@ -27,7 +26,6 @@ def main():
     h.set_streams(1)
     h.enqueue(ptr, B); h.sync()
     L = _lib.lib()
-    L.ft8rx_debug_osd_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     out = np.zeros(16, np.uint64)
     L.ft8rx_debug_osd_times(h._h, None, 1)
     h.enqueue(ptr, B); h.sync()
