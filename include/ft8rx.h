@@ -42,6 +42,7 @@
  *                                                                                      (opt-in recall of stations heard 30 s earlier, ipass 8)
  *     ft8rx_set_weak                                                                   (opt-in weak-signal sync)
  *     ft8rx_set_reports  ft8rx_fetch_reports  ft8rx_report_probe                       (opt-in measured SNR / frequency / time of each decode)
+ *     ft8rx_ddc  ft8rx_ddc_host  ft8rx_ddc_taps                                        (down-converter: real / IQ input at 24 .. 192 kHz -> 12 kHz frames)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
@@ -420,6 +421,36 @@ int  ft8rx_fetch_reports(ft8rx_handle* h, int n_frames, ft8rx_report* reports);
 int  ft8rx_report_probe(ft8rx_handle* h, const float* spec, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
                         const int32_t* h0_idx, const int32_t* ttweak, const int32_t* ftweak, const uint64_t* msg_lo, const uint64_t* msg_hi,
                         ft8rx_report* reports);
+/* Down-converter (extension): n_streams sample arrays of one kind at rate_hz = 12000 D, D = 1, 2, 4, 8, 16 (real
+ * int16 at D = 1 is a frame already and is refused), each n_samples <= 180000 D long (zero before sample 0 and after the last) ->
+ * n_out frames of 180000 int16 at 12 kHz.  Output j is the USB audio of stream src[j] with the dial f_dial_hz[j] Hz from the stream's
+ * centre (a real stream's centre is 0 Hz; any value in [-rate/2, rate/2), the spectrum wraps; outputs may share a stream):
+ *   mixer    fc = f_dial + 3000, w = round(fc / rate 2^32) mod 2^32, phase of input sample n = (w n mod 2^32) / 2^32 cycles;
+ *   filters  Kaiser-windowed sincs, zero phase: rate -> 24 kHz (D >= 4: 17 / 31 / 61 taps), then 24 -> 12 kHz (283 taps; 143 at D = 1,
+ *            where nothing is decimated); ft8rx_ddc_taps hands out the float32 taps;
+ *   audio    y[m] = gain g Re(i^m z[m]), g = 1 for IQ and 2 for real kinds: unit gain from the USB passband (audio 200 .. 5800 Hz within
+ *            +-0.003 dB; audio <= -200 Hz and >= 6200 Hz at least 74 dB down); the frame is rint(y) saturated to int16.
+ * One kernel, nothing else runs: no opt-in step is involved, the frames are ordinary frames and
+ * ft8rx_enqueue_batch(h, ft8rx_staging_audio(h), n_out) is the intended next call.  Both entries first wait for the batches in flight.
+ * Anything outside the definition is refused with -1 and an error text that names the argument. */
+#define FT8RX_DDC_REAL_I16 0
+#define FT8RX_DDC_REAL_F32 1
+#define FT8RX_DDC_IQ_I16   2          /* I, Q interleaved */
+#define FT8RX_DDC_IQ_F32   3
+/* d_in: device, [n_streams][stream_stride] samples of `kind` (aligned to a sample).  d_audio: device, [n_out][180000]; NULL = the
+ * handle's staging buffer.  d_audio_f32: optional device output [n_out][180000], y before rounding.  f_mixed_hz: optional host output
+ * [n_out], the dial frequency actually mixed, w rate / 2^32 - 3000 (taken into [-rate/2, rate/2)).  n_out <= max_frames.  Asynchronous:
+ * the kernel is queued on the handle's main stream, which every later call of the handle is ordered behind. */
+int  ft8rx_ddc(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride,
+               uint64_t n_samples, int n_out, const int32_t* src, const double* f_dial_hz, float gain,
+               int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz);
+/* the same from host memory: staged through a handle-owned device buffer (allocated on first use, grown when a later call needs
+ * more), result left in the staging audio buffer; returns when the frames are there */
+int  ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride,
+                    uint64_t n_samples, int n_out, const int32_t* src, const double* f_dial_hz, float gain, double* f_mixed_hz);
+/* host only, no GPU: the taps the kernels use.  stage 1 / 2 -> their count, and the first min(count, cap) of them in taps (float32;
+ * taps may be NULL); 0 for a stage the rate does not have; -1 for a rate the build does not take (or another stage) */
+int  ft8rx_ddc_taps(int32_t rate_hz, int stage, float* taps, int cap);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -67,6 +67,10 @@ PROTOTYPES = {
     "ft8rx_set_reports": (INT, (PTR, I32)),
     "ft8rx_fetch_reports": (INT, (PTR, INT, PTR)),
     "ft8rx_report_probe": (INT, (PTR, PTR, INT, INT) + (PTR,) * 8),
+    # down-converter
+    "ft8rx_ddc": (INT, (PTR, PTR, INT, I32, INT, U64, U64, INT, PTR, PTR, F32, PTR, PTR, PTR)),
+    "ft8rx_ddc_host": (INT, (PTR, PTR, INT, I32, INT, U64, U64, INT, PTR, PTR, F32, PTR)),
+    "ft8rx_ddc_taps": (INT, (I32, INT, PTR, INT)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

@@ -718,6 +718,32 @@ class Handle:
             return out, [[(float(arr[f, i]["fHz"]), float(arr[f, i]["tsec"])) for i in range(cnt[f])] for f in range(B)]
         return out
 
+    def ddc(self, samples, kind, rate, src, f_dial_hz, gain=1.0, want_float=False, device=False):
+        """ft8rx_ddc_host / ft8rx_ddc (DESIGN.md section 16): down-convert [n_streams][n] samples of `kind` (ddc.REAL_I16 .. ddc.IQ_F32;
+        IQ as complex or (I, Q) pairs, ddc.pack) at `rate` Hz into len(src) frames in the staging buffer (staging_ptr, download_audio),
+        output j = stream src[j] with the dial f_dial_hz[j] Hz from the stream's centre -> f_mixed_hz [n_out], the dials really mixed.
+        want_float: -> (f_mixed_hz, y float32 [n_out, 180000]), the audio before rounding.  device / want_float: the samples go
+        through a torch tensor and the device entry (ft8rx_ddc) instead of the library's own staging (ft8rx_ddc_host)."""
+        from . import ddc as _ddc
+        a, n_streams, n = _ddc.pack(samples, kind)
+        src = np.ascontiguousarray(src, np.int32).reshape(-1)
+        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
+        if len(src) != len(f) or len(src) < 1:
+            raise Ft8rxError(f"ddc: one src and one f_dial_hz per output, got {len(src)} and {len(f)}")
+        fm = np.zeros(len(src), np.float64)
+        args = (int(kind), int(rate), n_streams, n, n, len(src), src.ctypes.data, f.ctypes.data, float(gain))
+        if not (device or want_float):
+            self._chk(self._L.ft8rx_ddc_host(self._h, a.ctypes.data, *args, fm.ctypes.data), "ft8rx_ddc_host")
+            return fm
+        import torch
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_f32 = torch.empty((len(src), NSAMP), dtype=torch.float32, device=dev) if want_float else None
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.ft8rx_ddc(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc")
+        self.sync()                                          # the tensors may go once the kernel has run
+        return (fm, d_f32.cpu().numpy()) if want_float else fm
+
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for
         overlapped DMA.  The memory is released when the array (and every view of it) is garbage collected."""

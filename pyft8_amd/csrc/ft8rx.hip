@@ -34,6 +34,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <new>
 #include <string>
 #include <vector>
@@ -56,6 +57,7 @@
 #include "kernels/ap_calls.hpp"
 #include "kernels/recall.hpp"
 #include "kernels/report.hpp"
+#include "kernels/ddc.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -192,6 +194,10 @@ struct ft8rx_handle {
     ft8rx_subsig* d_sigs = nullptr; int32_t* d_sigcnt = nullptr; int sig_cap = 0;
     float2 *d_zdec = nullptr, *d_model = nullptr, *d_adec = nullptr; SubdCtx* d_subctx = nullptr;      // decimated-baseband refinement (refine = 2), allocated on first use
     double* d_ones = nullptr;                                   // refine = 3: an all-ones taper table
+    // down-converter (ft8rx_ddc, kernels/ddc.hpp; allocated on first use): the channel table of a call, [max_frames]; the input
+    // staging of ft8rx_ddc_host, grown when a call needs more
+    // (h_ddc_outs: its page-locked source; ddc_ev: behind the copy of the last call's table, so that the next call can rewrite it)
+    DdcOut* d_ddc_outs = nullptr; DdcOut* h_ddc_outs = nullptr; hipEvent_t ddc_ev = nullptr; void* d_ddc_in = nullptr; size_t ddc_in_cap = 0;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -259,7 +265,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -427,6 +433,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     for (int i = 0; i < 32; i++) if (h->d2h_ev[i]) hipEventDestroy(h->d2h_ev[i]);
     for (hipEvent_t e : h->ev_chunk) if (e) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
+    if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -1245,6 +1252,168 @@ int ft8rx_set_recall_gates(ft8rx_handle* h, int32_t max_hd, int32_t min_gap) {
     if (!h) return -1;
     if (max_hd < 1 || max_hd > 174 || min_gap < 0 || min_gap > 174) { set_err(h, "ft8rx_set_recall_gates: max_hd %d / min_gap %d outside [1, 174] / [0, 174]", max_hd, min_gap); return -1; }
     h->rc_max_hd = max_hd; h->rc_min_gap = min_gap;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- down-converter
+// Kaiser-windowed sinc, odd length from the Kaiser estimate, cutoff half way between pass and stop edge, unit DC gain; designed in
+// double, rounded once
+static double ddc_bessel_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 200; k++) { term *= (x / (2.0 * k)) * (x / (2.0 * k)); sum += term; if (term < 1e-20 * sum) break; }
+    return sum;
+}
+static std::vector<float> ddc_design(double f_pass, double f_stop, double A, double fs) {
+    int N = (int)ceil((A - 7.95) / (2.285 * 2.0 * M_PI * (f_stop - f_pass) / fs)) + 1;
+    if (N % 2 == 0) N++;
+    const double beta = 0.1102 * (A - 8.7), fc = (f_pass + f_stop) / (2.0 * fs), c = (N - 1) / 2.0;
+    std::vector<double> h(N);
+    double sum = 0.0;
+    for (int n = 0; n < N; n++) {
+        const double x = n - c, r = x / c;
+        const double sinc = x == 0.0 ? 2.0 * fc : sin(2.0 * M_PI * fc * x) / (M_PI * x);
+        h[n] = sinc * ddc_bessel_i0(beta * sqrt(1.0 - r * r)) / ddc_bessel_i0(beta);
+        sum += h[n];
+    }
+    std::vector<float> out(N);
+    for (int n = 0; n < N; n++) out[n] = (float)(h[n] / sum);
+    return out;
+}
+struct DdcTaps { std::vector<float> h1[3], h2[2]; };      // h1: D = 4, 8, 16; h2: at 24 kHz, at 12 kHz (D = 1)
+static const DdcTaps& ddc_taps() {
+    static const DdcTaps T = [] {
+        DdcTaps t;
+        for (int i = 0; i < 3; i++) t.h1[i] = ddc_design(3200.0, 20800.0, 85.0, 48000.0 * (1 << i));
+        t.h2[0] = ddc_design(2800.0, 3200.0, 75.0, 24000.0);
+        t.h2[1] = ddc_design(2800.0, 3200.0, 75.0, 12000.0);
+        return t;
+    }();
+    return T;
+}
+static int ddc_decimation(int32_t rate_hz) {               // D, or 0 for a rate the build does not take
+    for (int D = 1; D <= 16; D *= 2) if (rate_hz == 12000 * D) return D;
+    return 0;
+}
+static const std::vector<float>* ddc_stage_taps(int D, int stage) {      // nullptr: the rate has no such stage
+    const DdcTaps& T = ddc_taps();
+    if (stage == 2) return &T.h2[D == 1];
+    return D >= 4 ? &T.h1[D == 4 ? 0 : D == 8 ? 1 : 2] : nullptr;
+}
+
+int ft8rx_ddc_taps(int32_t rate_hz, int stage, float* taps, int cap) {
+    const int D = ddc_decimation(rate_hz);
+    if (!D || (stage != 1 && stage != 2)) return -1;
+    const std::vector<float>* t = ddc_stage_taps(D, stage);
+    if (!t) return 0;
+    for (int i = 0; taps && i < cap && i < (int)t->size(); i++) taps[i] = (*t)[i];
+    return (int)t->size();
+}
+
+static int ddc_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_DDC)) return 0;
+    const DdcTaps& T = ddc_taps();
+    static_assert(sizeof(c_ddc_h1) == sizeof(float) * 3 * 64 && sizeof(c_ddc_h2) == sizeof(float) * 2 * 288, "tap tables");
+    std::vector<float> a(3 * 64, 0.0f), b(2 * 288, 0.0f);
+    for (int i = 0; i < 3; i++) { if (T.h1[i].size() > 64) return -2; memcpy(&a[i * 64], T.h1[i].data(), sizeof(float) * T.h1[i].size()); }
+    for (int i = 0; i < 2; i++) { if (T.h2[i].size() > 288) return -2; memcpy(&b[i * 288], T.h2[i].data(), sizeof(float) * T.h2[i].size()); }
+    if (T.h1[0].size() != 17 || T.h1[1].size() != 31 || T.h1[2].size() != 61 || T.h2[0].size() != 283 || T.h2[1].size() != 143) {
+        set_err(h, "ft8rx_ddc: the designed filters do not have the lengths the kernels were compiled for"); return -2;
+    }
+    FirstUse F(h, WS_DDC);
+    F.dev(&h->d_ddc_outs, (size_t)h->max_frames);
+    F.host(&h->h_ddc_outs, (size_t)h->max_frames);
+    FIRST_HIP(F, hipMemcpyToSymbol(HIP_SYMBOL(c_ddc_h1), a.data(), sizeof(float) * a.size()));
+    FIRST_HIP(F, hipMemcpyToSymbol(HIP_SYMBOL(c_ddc_h2), b.data(), sizeof(float) * b.size()));
+    return F.done();
+}
+
+static const size_t DDC_SAMPLE_BYTES[4] = {2, 4, 4, 8};     // FT8RX_DDC_REAL_I16, _REAL_F32, _IQ_I16, _IQ_F32
+
+// the argument checks both entries share (everything but the input pointer) -> D, or -1 with the error text
+static int ddc_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
+                     int n_out, const int32_t* src, const double* f_dial_hz, float gain) {
+    if (kind < 0 || kind > 3) { set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32", who, kind); return -1; }
+    const int D = ddc_decimation(rate_hz);
+    if (!D) { set_err(h, "%s: rate_hz %d is not 12000 x 1, 2, 4, 8 or 16", who, (int)rate_hz); return -1; }
+    if (kind == FT8RX_DDC_REAL_I16 && D == 1) { set_err(h, "%s: kind real int16 at rate_hz 12000 is a frame already", who); return -1; }
+    if (n_streams < 1) { set_err(h, "%s: n_streams %d < 1", who, n_streams); return -1; }
+    if (n_out < 1 || n_out > h->max_frames) { set_err(h, "%s: n_out %d outside [1, %d] (max_frames)", who, n_out, h->max_frames); return -1; }
+    if (n_samples > (uint64_t)FT8RX_NSAMP * D) { set_err(h, "%s: n_samples %llu > %d (15 s at rate_hz)", who, (unsigned long long)n_samples, FT8RX_NSAMP * D); return -1; }
+    if (stream_stride < n_samples || stream_stride > ((uint64_t)1 << 40)) { set_err(h, "%s: stream_stride %llu does not hold n_samples %llu", who, (unsigned long long)stream_stride, (unsigned long long)n_samples); return -1; }
+    if (!src || !f_dial_hz) { set_err(h, "%s: src / f_dial_hz is NULL", who); return -1; }
+    for (int j = 0; j < n_out; j++) {
+        if (src[j] < 0 || src[j] >= n_streams) { set_err(h, "%s: src[%d] = %d outside [0, %d) (n_streams)", who, j, (int)src[j], n_streams); return -1; }
+        if (!(f_dial_hz[j] >= -0.5 * rate_hz && f_dial_hz[j] < 0.5 * rate_hz)) { set_err(h, "%s: f_dial_hz[%d] = %g outside [-rate_hz / 2, rate_hz / 2)", who, j, f_dial_hz[j]); return -1; }
+    }
+    if (!(fabsf(gain) <= 3.0e38f)) { set_err(h, "%s: gain is not finite", who); return -1; }
+    return D;
+}
+
+// the launch: channel table (sorted by stream, so that outputs of one stream run next to each other and share its loads in L2) -> device,
+// one kernel on the main stream
+static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_t rate_hz, uint64_t stream_stride, uint64_t n_samples, int n_out,
+                      const int32_t* src, const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    if (!h->ddc_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ddc_ev, hipEventDisableTiming));
+    else HIPCHK(h, hipEventSynchronize(h->ddc_ev));      // the previous call's table has left the page-locked buffer (long ago, as a rule)
+    DdcOut* outs = h->h_ddc_outs;
+    for (int j = 0; j < n_out; j++) {
+        const double r = nearbyint((f_dial_hz[j] + 3000.0) / (double)rate_hz * 4294967296.0);
+        const uint32_t w = (uint32_t)((long long)r & 0xffffffffLL);
+        outs[j] = DdcOut{src[j], j, w, 0u};
+        if (f_mixed_hz) {
+            double f = (double)w * (double)rate_hz / 4294967296.0 - 3000.0;
+            if (f >= 0.5 * rate_hz) f -= (double)rate_hz;
+            f_mixed_hz[j] = f;
+        }
+    }
+    std::stable_sort(outs, outs + n_out, [](const DdcOut& a, const DdcOut& b) { return a.src < b.src; });
+    HIPCHK(h, hipMemcpyAsync(h->d_ddc_outs, outs, sizeof(DdcOut) * (size_t)n_out, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ddc_ev, h->stream));
+    const float scale = gain * (kind == FT8RX_DDC_IQ_I16 || kind == FT8RX_DDC_IQ_F32 ? 1.0f : 2.0f);
+    const unsigned grid = (unsigned)n_out * DDC_TILES;
+    const unsigned long long ss = stream_stride; const int ns = (int)n_samples;
+#define DDC_GO(DD) k_ddc<DD><<<grid, DDC_NT, 0, h->stream>>>(d_in, kind, ss, ns, h->d_ddc_outs, scale, d_audio, d_audio_f32)
+    switch (D) { case 1: DDC_GO(1); break; case 2: DDC_GO(2); break; case 4: DDC_GO(4); break; case 8: DDC_GO(8); break; default: DDC_GO(16); }
+#undef DDC_GO
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ft8rx_ddc(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
+              int n_out, const int32_t* src, const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    const int D = ddc_check(h, "ft8rx_ddc", kind, rate_hz, n_streams, stream_stride, n_samples, n_out, src, f_dial_hz, gain);
+    if (D < 0) return -1;
+    if (!d_in || ((uintptr_t)d_in % DDC_SAMPLE_BYTES[kind]) != 0) { set_err(h, "ft8rx_ddc: d_in is NULL or not aligned to a sample"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h)) return -2;
+    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    return ddc_launch(h, D, d_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+}
+
+int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
+                   int n_out, const int32_t* src, const double* f_dial_hz, float gain, double* f_mixed_hz) {
+    if (!h) return -1;
+    const int D = ddc_check(h, "ft8rx_ddc_host", kind, rate_hz, n_streams, stream_stride, n_samples, n_out, src, f_dial_hz, gain);
+    if (D < 0) return -1;
+    if (!in) { set_err(h, "ft8rx_ddc_host: in is NULL"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h) || need_staging(h)) return -2;
+    const size_t bytes = (size_t)n_streams * (size_t)stream_stride * DDC_SAMPLE_BYTES[kind];
+    if (h->ddc_in_cap < bytes) {                         // first use, or a larger call: nothing of the handle reads the old buffer any more
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 256);
+        if (e != hipSuccess) { set_err(h, "ft8rx_ddc_host: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return -2; }
+        if (h->d_ddc_in) {
+            for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == h->d_ddc_in) { h->allocs.erase(h->allocs.begin() + i); break; }
+            hipFree(h->d_ddc_in);
+        }
+        h->allocs.push_back(p); h->d_ddc_in = p; h->ddc_in_cap = bytes ? bytes : 256;
+    }
+    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = ddc_launch(h, D, h->d_ddc_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 

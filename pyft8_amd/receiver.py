@@ -864,8 +864,53 @@ class Receiver:
         from . import recall as R
         return [R.entries_from_dicts(d or [], self.cfg) for d in recall]
 
+    def decode_stream(self, samples, sample_rate, iq=False, dial_offsets_hz=(0.0,), src=None, bands=None, **kw):
+        """Decode one cycle of wider input: `samples` [n_streams][n] (one stream may come as [n]) at sample_rate = 12, 24, 48, 96 or
+        192 kHz -- real (sound card: int16 or float), or with iq=True complex baseband (SDR: complex, or int16 (I, Q) pairs
+        [n_streams, n, 2]) -- is down-converted on the GPU (ft8rx_ddc) into one 12 kHz USB frame per entry of
+        dial_offsets_hz: channel j is stream src[j] (default: stream 0, or stream j when there are as many streams as channels)
+        with its dial dial_offsets_hz[j] Hz from the stream's centre (0 Hz for real input).  The frames never leave the device.
+        -> list (per channel) of message dicts, exactly what decode_frames returns for those frames; its keyword arguments (passes,
+        recall, cyclestart_strings, ...) work unchanged.  bands[j], when given, is the "band" of channel j's dicts; fHz stays the audio
+        frequency inside the channel."""
+        from . import ddc as _ddc
+        a = np.asarray(samples)
+        cplx = np.iscomplexobj(a)
+        if cplx and not iq:
+            raise _lib.Ft8rxError("samples are complex: pass iq=True")
+        if iq:
+            kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
+        else:
+            kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
+        dials = [float(f) for f in dial_offsets_hz]
+        n_out = len(dials)
+        if n_out < 1:
+            raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
+        arr, n_streams, _ = _ddc.pack(a, kind)
+        if src is None:
+            if n_streams != 1 and n_streams != n_out:
+                raise _lib.Ft8rxError(f"src: {n_streams} streams and {n_out} channels -- say which stream each channel reads")
+            src = [0] * n_out if n_streams == 1 else list(range(n_out))
+        if len(src) != n_out:
+            raise _lib.Ft8rxError(f"src: one stream index per channel ({n_out}), got {len(src)}")
+        if bands is not None and len(bands) != n_out:
+            raise _lib.Ft8rxError(f"bands: one per channel ({n_out}), got {len(bands)}")
+        if kw.get("recall") is not None and len(kw["recall"]) != n_out:
+            raise _lib.Ft8rxError(f"recall: one list of earlier messages per channel ({n_out}), got {len(kw['recall'])}")
+        args = {"cyclestart_strings": None, "return_records": False, "passes": 1, "subtract_min_snr": -10, "sub_pass_osd": True,
+                "research": "full", "recall": None}
+        for k in kw:
+            if k not in args:
+                raise TypeError(f"decode_stream() got an unexpected keyword argument '{k}'")
+        args.update(kw)
+        with self._hlock:
+            h = self._handle(n_out)
+            h.ddc(arr, kind, int(sample_rate), src, dials)
+            return self._decode_frames_locked(None, n_out, bands=bands, **args)
+
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",
-                              recall=None):
+                              recall=None, bands=None):
+        """audio None: the B frames are in the handle's staging buffer already (decode_stream); bands: per frame, instead of self.band"""
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
         use_recall = self.recall or recall is not None
@@ -878,7 +923,11 @@ class Receiver:
         h = self._handle(B)
         if use_recall:
             h.set_recall(self._recall_entries(recall if recall is not None else [None] * B))
-        rec, cnt, ev, evc = h.decode_batch(audio)
+        if audio is None:
+            h.enqueue(h.staging_ptr(), B)
+            rec, cnt, ev, evc = h.fetch(B)
+        else:
+            rec, cnt, ev, evc = h.decode_batch(audio)
         rp = h.fetch_reports(B) if self.reports else None
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
         if use_recall:
@@ -887,7 +936,8 @@ class Receiver:
         else:
             msgs, mcnt = self._package(rec, cnt, ev, evc)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
-        out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0, on_message=self.on_message,
+        band = [self.band] * B if bands is None else list(bands)
+        out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=band[f], odd_even=0, on_message=self.on_message,
                                 ap=self._ap_on(), recall=use_recall, reports=None if rp is None else rp[f]) for f in range(B)]
         seen = [{" ".join(d["msg_tuple"]) for d in out[f]} for f in range(B)]
         for _ in range(1, int(passes)):
@@ -900,7 +950,7 @@ class Receiver:
             keep = np.zeros(mcnt.shape, np.int32)
             for f in range(B):
                 new = []
-                for i, d in enumerate(_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, odd_even=0)):
+                for i, d in enumerate(_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=band[f], odd_even=0)):
                     t = " ".join(d["msg_tuple"])
                     if t not in seen[f] and (sub_pass_osd or "OSD" not in d["decode_notes"]):
                         seen[f].add(t)
