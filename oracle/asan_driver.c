@@ -27,7 +27,8 @@ static int run(const int16_t* audio, const ft8o_config* cfg) {
     return nm;
 }
 /* the subtraction functions on the first decodes of the frame: tone encoder, the experiment's refine_time_origin, the
- * build's decimated-baseband re-estimation + subtraction, the reference-style subtraction; incl. origins at the edges of the buffer */
+ * build's decimated-baseband re-estimation + subtraction, the reference-style subtraction, the build's full-rate re-estimation, the decimated subtraction at a given origin; incl. origins at the
+ * edges of the buffer */
 static int run_sub(const int16_t* audio, const ft8o_config* cfg) {
     static float wf[FT8O_NSAMP];
     int32_t nc = 0, nl = 0, nm = 0, done = 0;
@@ -44,6 +45,15 @@ static int run_sub(const int16_t* audio, const ft8o_config* cfg) {
         done += ft8o_subtract(wf, tones, msgs[i].fHz + 3.0, msgs[i].tsec);
         f = msgs[i].fHz; t = (i == 0) ? 0.0001 : 2.45;            /* start sample 1; a signal that runs off the end of the buffer */
         done += ft8o_refine2_subtract(wf, tones, &f, &t, 1);
+        /* the same edges through the refine = 2 subtraction at a given origin (incl. one far from the decimated copy) and refine = 1 */
+        done += ft8o_refine2_subtract_at(wf, tones, msgs[i].fHz, msgs[i].tsec, msgs[i].fHz + 0.25, msgs[i].tsec + 64.0 / 12000.0);
+        done += ft8o_refine2_subtract_at(wf, tones, msgs[i].fHz, msgs[i].tsec, msgs[i].fHz, (i == 0) ? 0.0001 : 2.45);
+        f = msgs[i].fHz; t = msgs[i].tsec;
+        ft8o_refine1(wf, tones, &f, &t);
+        done += ft8o_subtract(wf, tones, f, t);
+        f = msgs[i].fHz; t = (i == 0) ? 0.0001 : 2.45;
+        ft8o_refine1(wf, tones, &f, &t);
+        done += ft8o_subtract(wf, tones, f, t);
     }
     /* the local re-search: a mask shorter than / as long as / longer than the search range, then the configured search again */
     static uint8_t mask[5000];

@@ -1486,7 +1486,8 @@ void ft8o_refine_time_origin(const float* audio_f32, const ft8o_config* c, doubl
 /* ------------------------------------------------------------------------------------------------------------------
  * The build's own origin re-estimation and subtraction on a decimated baseband copy (ft8rx_subtract refine = 2; EXTENSION, no
  * reference counterpart): a plain double-precision statement of what pyft8_amd/csrc/kernels/subtract.hpp computes in float32 with
- * hardware sin/cos -- tolerance stage (tests compare the chosen grid points and the residual, not bits).
+ * hardware sin/cos -- tolerance stage, not bits: tests/test_gpu_subtract.py compares the chosen grid points (the same point, at most one
+ * signal of the fixed set a fine step off) and, with ft8o_refine2_subtract_at at the GPU's own origins, the residual at every sample.
  *   fc = (fHz - 0.5) + 21.875;  s00 = int(12000 tsec)
  *   z[m]   = sum_{|j| < 32} (32 - |j|) x[n_c + j] e^{-2 pi i fc (n_c + j) / 12000},  n_c = s00 + 32 (m - 64),  m < 4864      (mix + triangular decimator)
  *   c[m]   = conj(sig[32 m] e^{-2 pi i fc (s0 + 32 m) / 12000}) / (1024 g(tone of sample 32 m)),  m < 4736                    (model for the current origin)
@@ -1528,6 +1529,28 @@ static void subd_model(const uint8_t* tones, const double* cum, double fHz, doub
         cm[m].re = (sr * cr + si * ci) * sc; cm[m].im = (sr * ci - si * cr) * sc;       /* conj(sig e^{-i th}) */
     }
 }
+/* arg-max of |sum_ch Y[z][ch] e^{-2 pi i df t_ch}|^2 over (shift, df), t_ch = (ch + 1/2) chunk / 12000; ties go to the lowest (z, j); moves
+ * the origin to the best point unless no energy is > 0 (k_sub_pick) */
+static void sub_pick(dcpx (*Y)[128], const int* shift, int nshift, int chunk, double df_lo, double df_step, int ndf, double* fHz, double* tsec) {
+    const int s0 = (int)(12000.0 * *tsec);
+    double be = -1.0; int bz = 0, bj = 0;
+    for (int z = 0; z < nshift; z++) for (int j = 0; j < ndf; j++) {
+        const double df = df_lo + df_step * (double)j;
+        double er = 0.0, ei = 0.0;
+        for (int ch = 0; ch < 128; ch++) {
+            const double ang = -2.0 * M_PI * df * (((double)ch + 0.5) * (double)chunk / 12000.0);
+            const double cr = cos(ang), ci = sin(ang);
+            er += Y[z][ch].re * cr - Y[z][ch].im * ci; ei += Y[z][ch].re * ci + Y[z][ch].im * cr;
+        }
+        const double e = er * er + ei * ei;
+        if (e > be) { be = e; bz = z; bj = j; }
+    }
+    if (be > 0.0) {
+        const int s0n = s0 + shift[bz];
+        *tsec = ((double)s0n + 0.5) / 12000.0;
+        *fHz += (df_lo + df_step * (double)bj) - 0.5;
+    }
+}
 static void subd_scan_pick(const dcpx* zd, const dcpx* cm, int s00, const int* shift, int nshift, double df_lo, double df_step, int ndf,
                            double* fHz, double* tsec) {
     const int s0 = (int)(12000.0 * *tsec);
@@ -1547,33 +1570,13 @@ static void subd_scan_pick(const dcpx* zd, const dcpx* cm, int s00, const int* s
             Y[z][ch].re = ar; Y[z][ch].im = ai;
         }
     }
-    double be = -1.0; int bz = 0, bj = 0;
-    for (int z = 0; z < nshift; z++) for (int j = 0; j < ndf; j++) {
-        const double df = df_lo + df_step * (double)j;
-        double er = 0.0, ei = 0.0;
-        for (int ch = 0; ch < 128; ch++) {
-            const double ang = -2.0 * M_PI * df * (((double)ch + 0.5) * (double)(SUBD_D * SUBD_CH) / 12000.0);
-            const double cr = cos(ang), ci = sin(ang);
-            er += Y[z][ch].re * cr - Y[z][ch].im * ci; ei += Y[z][ch].re * ci + Y[z][ch].im * cr;
-        }
-        const double e = er * er + ei * ei;
-        if (e > be) { be = e; bz = z; bj = j; }
-    }
-    if (be > 0.0) {
-        const int s0n = s0 + shift[bz];
-        *tsec = ((double)s0n + 0.5) / 12000.0;
-        *fHz += (df_lo + df_step * (double)bj) - 0.5;
-    }
+    sub_pick(Y, shift, nshift, SUBD_D * SUBD_CH, df_lo, df_step, ndf, fHz, tsec);
     free(Y);
 }
-/* refine = 2 for one signal: re-estimates (fHz, tsec) in place and, if `subtract`, removes the signal from audio (float32, in place).
- * returns 1 if the signal was subtracted */
-int ft8o_refine2_subtract(float* audio, const uint8_t* tones, double* fHz, double* tsec, int subtract) {
-    sub_init();
-    double cum[80]; cum[0] = 0.0;
-    for (int i = 0; i < 79; i++) cum[i + 1] = cum[i] + (double)tones[i];
-    const double fc = *fHz - 0.5 + 21.875;
-    const int s00 = (int)(12000.0 * *tsec);
+/* the decimated baseband copy of the audio around the origin the signal came with: fc, s00 and z[SUBD_NZ] (caller frees) */
+static dcpx* subd_context(const float* audio, double fHz0, double tsec0, double* fc_out, int* s00_out) {
+    const double fc = fHz0 - 0.5 + 21.875;
+    const int s00 = (int)(12000.0 * tsec0);
     /* mixed-down samples over the span the decimator touches, then the triangular filter */
     const int n_lo = s00 + SUBD_D * (0 - SUBD_PAD) - 31, n_hi = s00 + SUBD_D * (SUBD_NZ - 1 - SUBD_PAD) + 31;
     const int span = n_hi - n_lo + 1;
@@ -1592,6 +1595,59 @@ int ft8o_refine2_subtract(float* audio, const uint8_t* tones, double* fHz, doubl
         zd[m].re = ar; zd[m].im = ai;
     }
     free(xb);
+    *fc_out = fc; *s00_out = s00;
+    return zd;
+}
+/* amplitude estimate on the decimated copy + full-rate subtraction at the origin (fHz, tsec); cm is scratch [SUBD_N].  Decimated samples
+ * outside the copy (an origin more than 64 decimated samples from s00: no scan reaches one) count as 0.  returns 1 if subtracted */
+static int subd_subtract_at(float* audio, const uint8_t* tones, const double* cum, const dcpx* zd, dcpx* cm, double fc, int s00,
+                            double fHz, double tsec) {
+    const int s0 = (int)(12000.0 * tsec);
+    if (!(s0 > 0 && s0 + SUB_L <= FT8O_NSAMP)) return 0;
+    subd_model(tones, cum, fHz, tsec, fc, cm);
+    const int off = (s0 - s00) / SUBD_D;
+    double Ar[20], Ai[20];
+    for (int k = 0; k < 20; k++) { Ar[k] = 0.0; Ai[k] = 0.0; }
+    for (int m = 0; m < SUBD_N; m++) {
+        const int idx = SUBD_PAD + off + m;
+        if (idx < 0 || idx >= SUBD_NZ) continue;
+        const dcpx zv = zd[idx], wv = cm[m];
+        const double yr = zv.re * wv.re - zv.im * wv.im, yi = zv.re * wv.im + zv.im * wv.re;
+        for (int k = 0; k < 20; k++) {
+            const double ang = -2.0 * M_PI * (double)(((long long)k * SUBD_D * m) % 192000) / 192000.0;
+            const double cr = cos(ang), ci = sin(ang);
+            Ar[k] += yr * cr - yi * ci; Ai[k] += yr * ci + yi * cr;
+        }
+    }
+    for (int k = 0; k < 20; k++) { Ar[k] *= (double)SUBD_D / 192000.0; Ai[k] *= (double)SUBD_D / 192000.0; }
+    dcpx* ad = (dcpx*)malloc(sizeof(dcpx) * (SUBD_N + 1));
+    for (int m = 0; m <= SUBD_N; m++) {
+        double er = 0.0, ei = 0.0;
+        for (int k = 0; k < 20; k++) {
+            const double ang = 2.0 * M_PI * (double)(((long long)k * SUBD_D * m) % 192000) / 192000.0;
+            const double cr = cos(ang), ci = sin(ang);
+            er += Ar[k] * cr - Ai[k] * ci; ei += Ar[k] * ci + Ai[k] * cr;
+        }
+        ad[m].re = er; ad[m].im = ei;
+    }
+    for (int n = 0; n < SUB_L; n++) {
+        double sr, si; sub_sig(tones, cum, fHz - 0.5, n, &sr, &si);
+        int md = n >> 5; if (md > SUBD_N - 1) md = SUBD_N - 1;
+        double fq = (double)(n - SUBD_D * md) / 32.0; if (fq > 1.0) fq = 1.0;
+        const double er = ad[md].re + fq * (ad[md + 1].re - ad[md].re), ei = ad[md].im + fq * (ad[md + 1].im - ad[md].im);
+        audio[s0 + n] = (float)((double)audio[s0 + n] - 2.0 * (er * sr - ei * si));
+    }
+    free(ad);
+    return 1;
+}
+/* refine = 2 for one signal: re-estimates (fHz, tsec) in place and, if `subtract`, removes the signal from audio (float32, in place).
+ * returns 1 if the signal was subtracted */
+int ft8o_refine2_subtract(float* audio, const uint8_t* tones, double* fHz, double* tsec, int subtract) {
+    sub_init();
+    double cum[80]; cum[0] = 0.0;
+    for (int i = 0; i < 79; i++) cum[i + 1] = cum[i] + (double)tones[i];
+    double fc; int s00;
+    dcpx* zd = subd_context(audio, *fHz, *tsec, &fc, &s00);
     dcpx* cm = (dcpx*)malloc(sizeof(dcpx) * SUBD_N);
     int coarse[15], fine[9];
     for (int i = 0; i < 15; i++) coarse[i] = SUBD_D * (-52 + 4 * i);
@@ -1600,43 +1656,67 @@ int ft8o_refine2_subtract(float* audio, const uint8_t* tones, double* fHz, doubl
     subd_scan_pick(zd, cm, s00, coarse, 15, -1.0, 0.0625, 113, fHz, tsec);
     subd_model(tones, cum, *fHz, *tsec, fc, cm);
     subd_scan_pick(zd, cm, s00, fine, 9, 0.4375, 0.015625, 9, fHz, tsec);
-    int done = 0;
-    const int s0 = (int)(12000.0 * *tsec);
-    if (subtract && s0 > 0 && s0 + SUB_L <= FT8O_NSAMP) {
-        subd_model(tones, cum, *fHz, *tsec, fc, cm);
-        const int off = (s0 - s00) / SUBD_D;
-        double Ar[20], Ai[20];
-        for (int k = 0; k < 20; k++) { Ar[k] = 0.0; Ai[k] = 0.0; }
-        for (int m = 0; m < SUBD_N; m++) {
-            const dcpx zv = zd[SUBD_PAD + off + m], wv = cm[m];
-            const double yr = zv.re * wv.re - zv.im * wv.im, yi = zv.re * wv.im + zv.im * wv.re;
-            for (int k = 0; k < 20; k++) {
-                const double ang = -2.0 * M_PI * (double)(((long long)k * SUBD_D * m) % 192000) / 192000.0;
-                const double cr = cos(ang), ci = sin(ang);
-                Ar[k] += yr * cr - yi * ci; Ai[k] += yr * ci + yi * cr;
-            }
-        }
-        for (int k = 0; k < 20; k++) { Ar[k] *= (double)SUBD_D / 192000.0; Ai[k] *= (double)SUBD_D / 192000.0; }
-        dcpx* ad = (dcpx*)malloc(sizeof(dcpx) * (SUBD_N + 1));
-        for (int m = 0; m <= SUBD_N; m++) {
-            double er = 0.0, ei = 0.0;
-            for (int k = 0; k < 20; k++) {
-                const double ang = 2.0 * M_PI * (double)(((long long)k * SUBD_D * m) % 192000) / 192000.0;
-                const double cr = cos(ang), ci = sin(ang);
-                er += Ar[k] * cr - Ai[k] * ci; ei += Ar[k] * ci + Ai[k] * cr;
-            }
-            ad[m].re = er; ad[m].im = ei;
-        }
-        for (int n = 0; n < SUB_L; n++) {
-            double sr, si; sub_sig(tones, cum, *fHz - 0.5, n, &sr, &si);
-            int md = n >> 5; if (md > SUBD_N - 1) md = SUBD_N - 1;
-            double fq = (double)(n - SUBD_D * md) / 32.0; if (fq > 1.0) fq = 1.0;
-            const double er = ad[md].re + fq * (ad[md + 1].re - ad[md].re), ei = ad[md].im + fq * (ad[md + 1].im - ad[md].im);
-            audio[s0 + n] = (float)((double)audio[s0 + n] - 2.0 * (er * sr - ei * si));
-        }
-        free(ad);
-        done = 1;
-    }
+    const int done = subtract ? subd_subtract_at(audio, tones, cum, zd, cm, fc, s00, *fHz, *tsec) : 0;
     free(cm); free(zd);
     return done;
+}
+/* the last third of refine = 2 alone: the amplitude estimate and the full-rate subtraction at a GIVEN final origin (fHz, tsec), on the
+ * decimated copy built for the origin the signal came with (fHz0, tsec0: they fix fc and s00, as in ft8o_refine2_subtract).  Lets a
+ * test subtract at exactly the origin another implementation chose.  returns 1 if the signal was subtracted */
+int ft8o_refine2_subtract_at(float* audio, const uint8_t* tones, double fHz0, double tsec0, double fHz, double tsec) {
+    sub_init();
+    double cum[80]; cum[0] = 0.0;
+    for (int i = 0; i < 79; i++) cum[i + 1] = cum[i] + (double)tones[i];
+    double fc; int s00;
+    dcpx* zd = subd_context(audio, fHz0, tsec0, &fc, &s00);
+    dcpx* cm = (dcpx*)malloc(sizeof(dcpx) * SUBD_N);
+    const int done = subd_subtract_at(audio, tones, cum, zd, cm, fc, s00, fHz, tsec);
+    free(cm); free(zd);
+    return done;
+}
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The build's full-rate origin re-estimation (ft8rx_subtract refine = 1; EXTENSION, no reference counterpart): a plain double-precision
+ * statement of k_sub_scan + k_sub_pick of pyft8_amd/csrc/kernels/subtract.hpp as ft8rx_subtract calls them -- tolerance stage.
+ *   scan:   Y[z][ch] = sum_{m in chunk ch (1185 samples)} x[s0 + shift_z + m] conj(sig[m]),  sig = the model at (fHz - 0.5), s0 = int(12000 tsec);
+ *           samples outside the buffer count as 0; a shift is skipped unless b0 = s0 + shift_z has b0 > 0 and b0 + L <= NSAMP
+ *   pick:   as refine = 2's, with t_ch = (ch + 1/2) 1185 / 12000
+ *   coarse: shifts -1680 + 120 i, i < 16; df = -1 + j / 16, j < 113;   fine: shifts -120 + 30 i, i < 9; df = 0.4375 + j / 64, j < 9
+ * The subtraction that follows is ft8o_subtract at the refined origin. */
+static void sub1_scan_pick(const float* audio, const uint8_t* tones, const double* cum, const int* shift, int nshift,
+                           double df_lo, double df_step, int ndf, double* fHz, double* tsec) {
+    const int s0 = (int)(12000.0 * *tsec);
+    const int chunk = SUB_L / 128;
+    dcpx (*Y)[128] = (dcpx (*)[128])calloc((size_t)nshift * 128, sizeof(dcpx));
+    double* sr = (double*)malloc(sizeof(double) * SUB_L * 2);
+    double* si = sr + SUB_L;
+    int any = 0;
+    for (int z = 0; z < nshift; z++) { const int b0 = s0 + shift[z]; any |= (b0 > 0 && b0 + SUB_L <= FT8O_NSAMP); }
+    if (any) for (int m = 0; m < SUB_L; m++) sub_sig(tones, cum, *fHz - 0.5, m, &sr[m], &si[m]);
+    for (int z = 0; z < nshift; z++) {
+        const int b0 = s0 + shift[z];
+        if (!(b0 > 0 && b0 + SUB_L <= FT8O_NSAMP)) continue;
+        for (int ch = 0; ch < 128; ch++) {
+            double ar = 0.0, ai = 0.0;
+            for (int m = ch * chunk; m < (ch + 1) * chunk; m++) {
+                const int g = b0 + m;
+                if (g < 0 || g >= FT8O_NSAMP) continue;
+                const double x = (double)audio[g];
+                ar += x * sr[m]; ai -= x * si[m];
+            }
+            Y[z][ch].re = ar; Y[z][ch].im = ai;
+        }
+    }
+    sub_pick(Y, shift, nshift, chunk, df_lo, df_step, ndf, fHz, tsec);
+    free(sr); free(Y);
+}
+void ft8o_refine1(const float* audio, const uint8_t* tones, double* fHz, double* tsec) {
+    sub_init();
+    double cum[80]; cum[0] = 0.0;
+    for (int i = 0; i < 79; i++) cum[i + 1] = cum[i] + (double)tones[i];
+    int coarse[16], fine[9];
+    for (int i = 0; i < 16; i++) coarse[i] = -1680 + 120 * i;
+    for (int i = 0; i < 9; i++) fine[i] = -120 + 30 * i;
+    sub1_scan_pick(audio, tones, cum, coarse, 16, -1.0, 0.0625, 113, fHz, tsec);
+    sub1_scan_pick(audio, tones, cum, fine, 9, 0.4375, 0.015625, 9, fHz, tsec);
 }

@@ -128,6 +128,12 @@ void  ft8o_refine_time_origin(const float* audio_f32, const ft8o_config* c, doub
 /* the build's own re-estimation on a decimated baseband copy + subtraction (ft8rx_subtract refine = 2; extension): updates
  * (fHz, tsec); subtracts in place if `subtract`; returns 1 if subtracted */
 int   ft8o_refine2_subtract(float* audio /*[180000]*/, const uint8_t* tones79, double* fHz, double* tsec, int subtract);
+/* the amplitude estimate and the subtraction of refine = 2 alone, at a given final origin (fHz, tsec); the decimated copy is the one of
+ * the origin the signal came with (fHz0, tsec0).  returns 1 if subtracted */
+int   ft8o_refine2_subtract_at(float* audio /*[180000]*/, const uint8_t* tones79, double fHz0, double tsec0, double fHz, double tsec);
+/* the build's full-rate re-estimation (ft8rx_subtract refine = 1; extension): k_sub_scan + k_sub_pick, coarse then fine, in double;
+ * updates (fHz, tsec); the subtraction that follows it is ft8o_subtract */
+void  ft8o_refine1(const float* audio /*[180000]*/, const uint8_t* tones79, double* fHz, double* tsec);
 
 #ifdef __cplusplus
 }

@@ -333,6 +333,31 @@ def refine2_subtract(audio_f32, tones79, fHz, tsec, subtract=True):
     return bool(done), f.value, ts.value
 
 
+def refine2_subtract_at(audio_f32, tones79, fHz0, tsec0, fHz, tsec):
+    """The amplitude estimate and the subtraction of refine = 2 alone, at the given final origin (fHz, tsec), in place; the decimated
+    copy is built around the origin the signal came with (fHz0, tsec0), as refine2_subtract builds it.  -> True if subtracted."""
+    assert audio_f32.dtype == np.float32 and audio_f32.shape == (NSAMP,) and audio_f32.flags.c_contiguous
+    t = np.ascontiguousarray(tones79, np.uint8)
+    assert t.shape == (79,)
+    fn = lib().ft8o_refine2_subtract_at
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]
+    return bool(fn(audio_f32.ctypes.data, t.ctypes.data, float(fHz0), float(tsec0), float(fHz), float(tsec)))
+
+
+def refine1(audio_f32, tones79, fHz, tsec):
+    """The build's refine = 1 re-estimation (full-rate scans) for one signal on a float32 buffer -> (fHz, tsec); subtract() follows it."""
+    a = np.ascontiguousarray(audio_f32, np.float32)
+    assert a.shape == (NSAMP,)
+    t = np.ascontiguousarray(tones79, np.uint8)
+    assert t.shape == (79,)
+    f, ts = C.c_double(float(fHz)), C.c_double(float(tsec))
+    fn = lib().ft8o_refine1
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    fn.restype = None
+    fn(a.ctypes.data, t.ctypes.data, C.byref(f), C.byref(ts))
+    return f.value, ts.value
+
+
 def subtraction_list(res, min_snr=-10):
     """The signals a subtraction sweep removes (ft8rx_subtraction_list): every message of the frame with snr > min_snr, in emit order,
     as (tones, fHz, tsec) with the origin the message dict reports (receiver.py:166)."""
