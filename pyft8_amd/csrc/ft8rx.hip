@@ -2020,14 +2020,38 @@ static int subtract_workspaces(ft8rx_handle* h, int refine) {
 // The refinement scans of ft8rx_subtract: coarse (10 ms / 0.25 Hz around the decoder's origin, which by the search-grid conventions
 // sits ~75 ms late and ~1.9 Hz low), then fine (2.5 ms / 0.0625 Hz); decimated = refine 2's, the same steps on a decimated baseband
 // copy (kernels/subtract.hpp): time shifts in units of 32 samples
+// (decimating the scan itself, every 8th / 2nd sample, was tried: it aliases neighbouring signals into the sums, 1 of 233 origins locked 70 ms off)
 static SubShifts sub_shifts(bool decimated, bool fine) {
     SubShifts t;
-    t.stride = 1;             // decimating the scan (tried 8 / 2) aliases neighbouring signals into the sum: 1 of 233 origins locked 70 ms off
     for (int i = 0; i < SUB_MAXSHIFT; i++) t.shift[i] = 0;
     if (fine) { t.n = 9; for (int i = 0; i < 9; i++) t.shift[i] = decimated ? SUBD_D * (-4 + i) : -120 + 30 * i; }       // -10 .. +10 ms (decimated: -10.7 .. +10.7 ms in 2.67 ms steps)
     else if (decimated) { t.n = 15; for (int i = 0; i < 15; i++) t.shift[i] = SUBD_D * (-52 + 4 * i); }                   // -138.7 .. +10.7 ms in 10.7 ms steps
     else { t.n = 16; for (int i = 0; i < 16; i++) t.shift[i] = -1680 + 120 * i; }                                        // -140 .. +10 ms
     return t;
+}
+// ... and the frequency grid k_sub_pick tries with each: df = df_lo + df_step * [0, ndf)
+static const struct { float df_lo, df_step; int ndf; } SUB_GRID[2] = {
+    {-1.0f, 0.0625f, 113},         // coarse: signal - model = -1 .. +6 Hz; the sum is coherent over 12.6 s, so the grid must be as fine as 1/16 Hz
+    {0.4375f, 0.015625f, 9},       // fine: around the +0.5 Hz the coarse step left
+};
+static_assert(SUB_MAXSHIFT * SUB_NCH <= SUB_NCH * 20, "the refinement scan [SUB_MAXSHIFT][SUB_NCH] lives in d_part [SUB_NCH][20]");
+
+// refine 1 / 2: coarse scan, pick, fine scan, pick for signal sel.s of B frames; decimated = on the baseband copy k_subd_mix made
+static void sub_refine(ft8rx_handle* h, int B, const SubSel& sel, const SubTables& T, bool decimated) {
+    for (int fine = 0; fine < 2; fine++) {
+        const SubShifts sh = sub_shifts(decimated, fine);
+        if (decimated) {
+            k_subd_model<<<dim3((SUBD_N + 255) / 256, B), 256, 0, h->stream>>>(sel, T, h->d_subctx, h->d_model);
+            k_subd_scan<<<B, 256, 0, h->stream>>>(h->d_zdec, h->d_model, sel, h->d_subctx, sh, h->d_part);
+        } else k_sub_scan<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, sel, T, sh, h->d_part);
+        k_sub_pick<<<B, 256, 0, h->stream>>>(sel, sh, h->d_part, SUB_GRID[fine].df_lo, SUB_GRID[fine].df_step, SUB_GRID[fine].ndf,
+                                             decimated ? SUBD_D * SUBD_CH : SUB_CH);
+    }
+}
+// the reference's subtract_signal at full rate
+static void sub_apply_fullrate(ft8rx_handle* h, int B, const SubSel& sel, const SubTables& T) {
+    k_sub_accum<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, sel, T, h->d_part);
+    k_sub_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, sel, T, h->d_part);
 }
 
 int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
@@ -2053,41 +2077,26 @@ int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs,
     k_sub_to_f32<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(d_audio, h->d_wf, n);
     if (subtract_workspaces(h, refine)) return -2;
     const SubTables T{h->d_pulse, h->d_pc};
-    const SubShifts coarse = sub_shifts(false, false), fine = sub_shifts(false, true), dcoarse = sub_shifts(true, false), dfine = sub_shifts(true, true);
-    const dim3 gmodel((SUBD_N + 255) / 256, B);
     Tables Tones = h->T;                                     // refine = 3: the experiment's slices have no edge tapers
     if (refine == 3) Tones.taper = h->d_ones;
     for (int s = 0; s < nmax; s++) {
+        const SubSel sel{h->d_sigs, h->d_sigcnt, max_sigs, s};
+        if (refine == 2) {                                   // everything but the subtraction itself on the decimated baseband copy
+            k_subd_mix<<<dim3(SUBD_NZ / 256, B), 256, 0, h->stream>>>(h->d_wf, sel, h->d_zdec, h->d_subctx);
+            sub_refine(h, B, sel, T, true);
+            k_subd_model<<<dim3((SUBD_N + 255) / 256, B), 256, 0, h->stream>>>(sel, T, h->d_subctx, h->d_model);
+            k_subd_accum<<<B, 256, 0, h->stream>>>(h->d_zdec, h->d_model, sel, h->d_subctx, h->d_adec);
+            k_subd_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, sel, T, h->d_adec);
+            continue;
+        }
+        if (refine == 1) sub_refine(h, B, sel, T, false);
         if (refine == 3) {
             // Candidate.refine_time_origin (receiver_sub.py:58-72) on the spectrum of the residual so far, then subtract_signal as is
             k_cyc_a_f32<<<dim3(40, B), 256, 0, h->stream>>>(h->d_wf, h->d_A, h->T);
             k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, h->stream>>>(h->d_A, h->d_spec, h->T);
-            k_refine3<<<B, FINE_NT, 0, h->stream>>>(h->d_spec, h->d_sigs, h->d_sigcnt, max_sigs, s, Tones);
-            k_sub_accum<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_part);
-            k_sub_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_part);
-            continue;
+            k_refine3<<<B, FINE_NT, 0, h->stream>>>(h->d_spec, sel, Tones);
         }
-        if (refine == 2) {
-            k_subd_mix<<<dim3(SUBD_NZ / 256, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, h->d_zdec, h->d_subctx);
-            k_subd_model<<<gmodel, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_subctx, h->d_model);
-            k_subd_scan<<<B, 256, 0, h->stream>>>(h->d_zdec, h->d_model, h->d_sigs, h->d_sigcnt, max_sigs, s, h->d_subctx, dcoarse, h->d_part);
-            k_sub_pick<<<B, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, dcoarse, h->d_part, -1.0f, 0.0625f, 113, SUBD_D * SUBD_CH);
-            k_subd_model<<<gmodel, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_subctx, h->d_model);
-            k_subd_scan<<<B, 256, 0, h->stream>>>(h->d_zdec, h->d_model, h->d_sigs, h->d_sigcnt, max_sigs, s, h->d_subctx, dfine, h->d_part);
-            k_sub_pick<<<B, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, dfine, h->d_part, 0.4375f, 0.015625f, 9, SUBD_D * SUBD_CH);
-            k_subd_model<<<gmodel, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_subctx, h->d_model);
-            k_subd_accum<<<B, 256, 0, h->stream>>>(h->d_zdec, h->d_model, h->d_sigs, h->d_sigcnt, max_sigs, s, h->d_subctx, h->d_adec);
-            k_subd_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_adec);
-            continue;
-        }
-        if (refine) {
-            k_sub_scan<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, coarse, h->d_part);
-            k_sub_pick<<<B, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, coarse, h->d_part, -1.0f, 0.0625f, 113, SUB_CH);   // signal - model: -1 .. +6 Hz; the sum is coherent over 12.6 s, so the grid must be as fine as 1/16 Hz
-            k_sub_scan<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, fine, h->d_part);
-            k_sub_pick<<<B, 256, 0, h->stream>>>(h->d_sigs, h->d_sigcnt, max_sigs, s, fine, h->d_part, 0.4375f, 0.015625f, 9, SUB_CH);   // around the +0.5 Hz the coarse step left
-        }
-        k_sub_accum<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_part);
-        k_sub_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, h->d_sigs, h->d_sigcnt, max_sigs, s, T, h->d_part);
+        sub_apply_fullrate(h, B, sel, T);
     }
     k_sub_to_i16<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->d_wf, d_audio, n);
     HIPCHK(h, hipGetLastError());

@@ -8,7 +8,16 @@
 // The 10 raw samples a thread contributes are requested up front (straight-line, from clamped addresses), then converted into the
 // LDS tile: the former load->store loop waited for every load separately (191 -> 146 us; two to four frames per block with the
 // later frames' samples prefetched behind the first transform gain nothing on top: 142 us).
-FT8_DEV void cyc_a_load(const int16_t* __restrict__ a, int n2b, int tid, uint32_t (&raw)[10]) {
+// The audio is int16 (k_cyc_a: a sample pair is one 32-bit word) or the float32 working copy of the subtraction (k_cyc_a_f32):
+// cyc_a_pair fetches the pair at sample `at` under the mask inb, cyc_a_point converts it to the LDS tile's element.
+FT8_DEV uint32_t cyc_a_pair(const int16_t* __restrict__ a, int at, int inb) { return *reinterpret_cast<const uint32_t*>(a + at) & (uint32_t)inb; }
+FT8_DEV float2 cyc_a_pair(const float* __restrict__ a, int at, int inb) {
+    const float2 v = *reinterpret_cast<const float2*>(a + at);
+    return make_float2(__uint_as_float(__float_as_uint(v.x) & (uint32_t)inb), __uint_as_float(__float_as_uint(v.y) & (uint32_t)inb));
+}
+FT8_DEV cpx cyc_a_point(uint32_t raw) { return make_float2((float)(int16_t)(raw & 0xFFFFu), (float)(int16_t)(raw >> 16)); }
+FT8_DEV cpx cyc_a_point(float2 raw) { return raw; }
+template <class In, class Raw> FT8_DEV void cyc_a_load(const In* __restrict__ a, int n2b, int tid, Raw (&raw)[10]) {
 #pragma unroll
     for (int q = 0; q < 10; q++) {
         const int i = tid + 256 * q, ic = i < 2400 ? i : 0;
@@ -17,14 +26,14 @@ FT8_DEV void cyc_a_load(const int16_t* __restrict__ a, int n2b, int tid, uint32_
         // zero padding beyond the 180000 samples (receiver.py:283: a 192000-sample buffer) by integer masking of a clamped load -- a
         // select would be turned back into a branch around the load (one memory round trip per basic block)
         const int inb = (2 * m < FT8RX_NSAMP) ? -1 : 0;
-        raw[q] = *reinterpret_cast<const uint32_t*>(a + ((2 * m) & inb)) & (uint32_t)inb;
+        raw[q] = cyc_a_pair(a, (2 * m) & inb, inb);
     }
 }
-FT8_DEV void cyc_a_frame(const uint32_t (&raw)[10], cpx* bufA, cpx* bufB, cpx* __restrict__ out, const Tables& T, int n2b, int tid) {
+template <class Raw> FT8_DEV void cyc_a_frame(const Raw (&raw)[10], cpx* bufA, cpx* bufB, cpx* __restrict__ out, const Tables& T, int n2b, int tid) {
 #pragma unroll
     for (int q = 0; q < 10; q++) {
         const int i = tid + 256 * q;
-        if (i < 2400) bufA[(i & 7) * 300 + (i >> 3)] = make_float2((float)(int16_t)(raw[q] & 0xFFFFu), (float)(int16_t)(raw[q] >> 16));
+        if (i < 2400) bufA[(i & 7) * 300 + (i >> 3)] = cyc_a_point(raw[q]);
     }
     // the four-step twiddles of this thread's ten outputs: requested before the transform, used after it
     cpx w[10];

@@ -11,6 +11,9 @@
 // subtracted in list order (a later signal sees the residual of the earlier ones), signal s of all frames at once:
 //   k_sub_accum  (chunk, frame): partial sums of the 20 DFT bins over 1185 samples  -> part[frame][chunk][20]
 //   k_sub_apply  (chunk, frame): bins = fixed-order sum of the 128 partials; subtracts the chunk in place
+// What the kernels of this file share, each written once: SubSel (which signal) and sub_begin (is there one; its origin; its
+// model staged in LDS), sub_fits (the guard), sub_chunk / sub_walk_chunk / sub_walk (a wavefront's chunks, the model at every sample),
+// sub_bins_analyse / sub_bins_synth (the 20-bin low-pass as a phasor recurrence) and wave_sum2 (the fixed-order 64-lane sum).
 // Arithmetic: GFSK phase in fp64 (it reaches 1e5 rad), everything else fp32 with fp64 accumulators; results agree with the
 // oracle / reference to ~1e-6 of the signal amplitude (tolerance stage, not bit-exact).
 #define SUB_L (79 * 1920)
@@ -47,63 +50,96 @@ FT8_DEV void sub_signal(const ft8rx_subsig& S, const double* __restrict__ cum /*
 #define SUB_CPW 4
 #define SUB_GRIDX (SUB_NCH / (4 * SUB_CPW))
 
-FT8_DEV bool sub_setup(const ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts, int max_sigs, int s, int frame,
-                       ft8rx_subsig* S, double* cum, int* s0) {
-    if (s >= counts[frame]) return false;
-    if (threadIdx.x < 24) reinterpret_cast<uint32_t*>(S)[threadIdx.x] = reinterpret_cast<const uint32_t*>(sigs + (size_t)frame * max_sigs + s)[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x < 80) { int a = 0; for (int i = 0; i < (int)threadIdx.x; i++) a += S->tones[i]; cum[threadIdx.x] = (double)a; }   // tones before symbol i
-    __syncthreads();
-    *s0 = (int)(12000.0 * S->tsec);
-    return *s0 > 0 && *s0 + SUB_L <= FT8RX_NSAMP;                 // the reference's guard (receiver_sub.py:390) + "fits the buffer"
+// signal s of every frame: the argument of every per-signal kernel (k_sub_pick and k_refine3 write the origin back through sigs)
+struct SubSel { ft8rx_subsig* sigs; const int32_t* counts; int max_sigs; int s; };
+struct SubModel { ft8rx_subsig S; double cum[80]; };            // LDS: the signal and the tones before symbol i, what sub_signal reads
+
+FT8_DEV bool sub_fits(int s0) { return s0 > 0 && s0 + SUB_L <= FT8RX_NSAMP; }   // the reference's guard (receiver_sub.py:390) + "fits the buffer"
+
+// The prologue of every per-signal kernel: signal s of this frame, or nullptr if the frame has none (block-uniform); *s0 = its start
+// sample, whether it fits or not.  With M the signal and cum[] are staged in LDS first (two barriers: every thread of the block calls).
+FT8_DEV ft8rx_subsig* sub_begin(const SubSel& sel, int frame, SubModel* M, int* s0) {
+    if (sel.s >= sel.counts[frame]) return nullptr;
+    ft8rx_subsig* g = sel.sigs + (size_t)frame * sel.max_sigs + sel.s;
+    if (M) {
+        if (threadIdx.x < 24) reinterpret_cast<uint32_t*>(&M->S)[threadIdx.x] = reinterpret_cast<const uint32_t*>(g)[threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x < 80) { int a = 0; for (int i = 0; i < (int)threadIdx.x; i++) a += M->S.tones[i]; M->cum[threadIdx.x] = (double)a; }
+        __syncthreads();
+    }
+    *s0 = (int)(12000.0 * (M ? M->S.tsec : g->tsec));
+    return g;
 }
 
-__global__ __launch_bounds__(256) void k_sub_accum(const float* __restrict__ wf, const ft8rx_subsig* __restrict__ sigs,
-                                                   const int32_t* __restrict__ counts, int max_sigs, int s, SubTables T,
-                                                   double2* __restrict__ part /*[B][SUB_NCH][20]*/) {
-    __shared__ ft8rx_subsig S;
-    __shared__ double cum[80];
-    const int frame = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+// chunk i (< SUB_CPW) of this wavefront, and the samples of chunk ch with the model's value at each: f(m, sr, si)
+FT8_DEV int sub_chunk(int i) { return (blockIdx.x * 4 + (threadIdx.x >> 6)) * SUB_CPW + i; }
+template <class F> FT8_DEV void sub_walk_chunk(const SubModel& M, const SubTables& T, int ch, F f) {
+    for (int m = ch * SUB_CH + (threadIdx.x & 63); m < (ch + 1) * SUB_CH; m += 64) {
+        float sr, si;
+        sub_signal(M.S, M.cum, T, m, &sr, &si);
+        f(m, sr, si);
+    }
+}
+template <class F> FT8_DEV void sub_walk(const SubModel& M, const SubTables& T, F f) {
+    for (int i = 0; i < SUB_CPW; i++) sub_walk_chunk(M, T, sub_chunk(i), f);
+}
+
+// The 20-bin low-pass as a phasor recurrence, r = w^k with w = (wr, wi) = e^{-+2 pi i m / 192000}: analysis f[k] += y r (wi < 0),
+// synthesis e = sum_k A[k] r (wi > 0)
+FT8_DEV void sub_bins_analyse(float yr, float yi, float wr, float wi, float (&fr_)[20], float (&fi_)[20]) {
+    float rr = 1.0f, ri = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 20; k++) {
+        fr_[k] += yr * rr - yi * ri; fi_[k] += yr * ri + yi * rr;
+        const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
+    }
+}
+FT8_DEV void sub_bins_synth(const float* Ar, const float* Ai /*LDS [20]*/, float wr, float wi, float* er_, float* ei_) {
+    float rr = 1.0f, ri = 0.0f, er = 0.0f, ei = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 20; k++) {
+        er += Ar[k] * rr - Ai[k] * ri; ei += Ar[k] * ri + Ai[k] * rr;
+        const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
+    }
+    *er_ = er; *ei_ = ei;
+}
+// fixed-order butterfly over the 64 lanes: every lane ends with the same sum
+FT8_DEV void wave_sum2(double& vr, double& vi) {
+    for (int o = 32; o > 0; o >>= 1) { vr += __shfl_xor(vr, o); vi += __shfl_xor(vi, o); }
+}
+
+__global__ __launch_bounds__(256) void k_sub_accum(const float* __restrict__ wf, SubSel sel, SubTables T, double2* __restrict__ part /*[B][SUB_NCH][20]*/) {
+    __shared__ SubModel M;
+    const int frame = blockIdx.y, lane = threadIdx.x & 63;
     int s0;
-    if (!sub_setup(sigs, counts, max_sigs, s, frame, &S, cum, &s0)) return;
+    if (!sub_begin(sel, frame, &M, &s0) || !sub_fits(s0)) return;
     const float* x = wf + (size_t)frame * FT8RX_NSAMP + s0;
     for (int i = 0; i < SUB_CPW; i++) {
-        const int ch = (blockIdx.x * 4 + wave) * SUB_CPW + i;
+        const int ch = sub_chunk(i);
         float fr_[20], fi_[20];                                       // 19 terms per lane in fp32, the cross-lane sums in fp64
 #pragma unroll
         for (int k = 0; k < 20; k++) { fr_[k] = 0.0f; fi_[k] = 0.0f; }
-        for (int m = ch * SUB_CH + lane; m < (ch + 1) * SUB_CH; m += 64) {
-            float sr, si;
-            sub_signal(S, cum, T, m, &sr, &si);
+        sub_walk_chunk(M, T, ch, [&](int m, float sr, float si) {
             const float xv = x[m];
             const float yr = xv * sr, yi = -(xv * si);              // y = x conj(sig)  (complex64 in the reference)
             const float rv = (float)m * (1.0f / 192000.0f);        // e^{-2 pi i m / 192000}
-            const float wr = __builtin_amdgcn_cosf(rv), wi = -__builtin_amdgcn_sinf(rv);
-            float rr = 1.0f, ri = 0.0f;
+            sub_bins_analyse(yr, yi, __builtin_amdgcn_cosf(rv), -__builtin_amdgcn_sinf(rv), fr_, fi_);
+        });
 #pragma unroll
-            for (int k = 0; k < 20; k++) {
-                fr_[k] += yr * rr - yi * ri; fi_[k] += yr * ri + yi * rr;
-                const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 20; k++) {                                // fixed-order butterfly over the 64 lanes
+        for (int k = 0; k < 20; k++) {
             double vr = (double)fr_[k], vi = (double)fi_[k];
-            for (int o = 32; o > 0; o >>= 1) { vr += __shfl_xor(vr, o); vi += __shfl_xor(vi, o); }
+            wave_sum2(vr, vi);
             if (lane == k) part[((size_t)frame * SUB_NCH + ch) * 20 + k] = make_double2(vr, vi);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_sub_apply(float* __restrict__ wf, const ft8rx_subsig* __restrict__ sigs,
-                                                   const int32_t* __restrict__ counts, int max_sigs, int s, SubTables T,
-                                                   const double2* __restrict__ part) {
-    __shared__ ft8rx_subsig S;
-    __shared__ double cum[80];
+__global__ __launch_bounds__(256) void k_sub_apply(float* __restrict__ wf, SubSel sel, SubTables T, const double2* __restrict__ part) {
+    __shared__ SubModel M;
     __shared__ float Ar[20], Ai[20];
-    const int frame = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int frame = blockIdx.y, tid = threadIdx.x;
     int s0;
-    if (!sub_setup(sigs, counts, max_sigs, s, frame, &S, cum, &s0)) return;
+    if (!sub_begin(sel, frame, &M, &s0) || !sub_fits(s0)) return;
     if (tid < 20) {
         double vr = 0.0, vi = 0.0;
         for (int c = 0; c < SUB_NCH; c++) { const double2 v = part[((size_t)frame * SUB_NCH + c) * 20 + tid]; vr += v.x; vi += v.y; }
@@ -111,22 +147,12 @@ __global__ __launch_bounds__(256) void k_sub_apply(float* __restrict__ wf, const
     }
     __syncthreads();
     float* x = wf + (size_t)frame * FT8RX_NSAMP + s0;
-    for (int i = 0; i < SUB_CPW; i++) {
-        const int ch = (blockIdx.x * 4 + wave) * SUB_CPW + i;
-        for (int m = ch * SUB_CH + lane; m < (ch + 1) * SUB_CH; m += 64) {
-            float sr, si;
-            sub_signal(S, cum, T, m, &sr, &si);
-            const float rv = (float)m * (1.0f / 192000.0f);        // e^{+2 pi i m / 192000}
-            const float wr = __builtin_amdgcn_cosf(rv), wi = __builtin_amdgcn_sinf(rv);
-            float rr = 1.0f, ri = 0.0f, er = 0.0f, ei = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 20; k++) {
-                er += Ar[k] * rr - Ai[k] * ri; ei += Ar[k] * ri + Ai[k] * rr;
-                const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
-            }
-            x[m] = x[m] - 2.0f * (er * sr - ei * si);
-        }
-    }
+    sub_walk(M, T, [&](int m, float sr, float si) {
+        const float rv = (float)m * (1.0f / 192000.0f);            // e^{+2 pi i m / 192000}
+        float er, ei;
+        sub_bins_synth(Ar, Ai, __builtin_amdgcn_cosf(rv), __builtin_amdgcn_sinf(rv), &er, &ei);
+        x[m] = x[m] - 2.0f * (er * sr - ei * si);
+    });
 }
 
 // ---- origin refinement (extension; the reference's refine_time_origin, receiver_sub.py:58-72, scans time only, in 5 ms steps, on
@@ -136,23 +162,19 @@ __global__ __launch_bounds__(256) void k_sub_apply(float* __restrict__ wf, const
 // moves the signal's (tsec, fHz) to the best (shift, df).
 #define SUB_MAXSHIFT 16
 #define SUB_MAXSPAN 1800
-struct SubShifts { int n; int stride; int shift[SUB_MAXSHIFT]; };   // start-sample shifts relative to int(12000 tsec); stride > 1 would
-                                                                  // decimate the scan (tried: it aliases neighbouring signals into the sums)
+struct SubShifts { int n; int shift[SUB_MAXSHIFT]; };               // start-sample shifts relative to int(12000 tsec), ascending
 
-__global__ __launch_bounds__(256) void k_sub_scan(const float* __restrict__ wf, const ft8rx_subsig* __restrict__ sigs,
-                                                  const int32_t* __restrict__ counts, int max_sigs, int s, SubTables T, SubShifts sh,
+__global__ __launch_bounds__(256) void k_sub_scan(const float* __restrict__ wf, SubSel sel, SubTables T, SubShifts sh,
                                                   double2* __restrict__ scan /*[B][SUB_MAXSHIFT][SUB_NCH]*/) {
-    __shared__ ft8rx_subsig S;
-    __shared__ double cum[80];
-    const int frame = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __shared__ SubModel M;
+    const int frame = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int s0;
-    if (s >= counts[frame]) return;
-    sub_setup(sigs, counts, max_sigs, s, frame, &S, cum, &s0);
+    if (!sub_begin(sel, frame, &M, &s0)) return;                     // an origin that does not fit: the guard is per shift, below
     const float* xf = wf + (size_t)frame * FT8RX_NSAMP;
     __shared__ float xs[4][SUB_CH + SUB_MAXSPAN + 3];                // per wavefront: the audio its chunk sees under every shift
     const int span = sh.shift[sh.n - 1] - sh.shift[0];               // shifts ascend; span <= SUB_MAXSPAN (host)
     for (int i = 0; i < SUB_CPW; i++) {
-        const int ch = (blockIdx.x * 4 + wave) * SUB_CPW + i;
+        const int ch = sub_chunk(i);
         __syncthreads();                                              // the previous chunk's reads are done
         const int g0 = s0 + sh.shift[0] + ch * SUB_CH;
         for (int j = lane; j < SUB_CH + span; j += 64) { const int g = g0 + j; xs[wave][j] = (g >= 0 && g < FT8RX_NSAMP) ? xf[g] : 0.0f; }
@@ -161,36 +183,34 @@ __global__ __launch_bounds__(256) void k_sub_scan(const float* __restrict__ wf, 
         float ar[SUB_MAXSHIFT], ai[SUB_MAXSHIFT];
 #pragma unroll
         for (int z = 0; z < SUB_MAXSHIFT; z++) { ar[z] = 0.0f; ai[z] = 0.0f; }
-        for (int m = ch * SUB_CH + lane * sh.stride; m < (ch + 1) * SUB_CH; m += 64 * sh.stride) {
-            float sr, si;
-            sub_signal(S, cum, T, m, &sr, &si);
+        sub_walk_chunk(M, T, ch, [&](int m, float sr, float si) {
             const float* xw = xs[wave] + (m - ch * SUB_CH) - sh.shift[0];
 #pragma unroll
             for (int z = 0; z < SUB_MAXSHIFT; z++) {
-                const int b0 = s0 + sh.shift[z];                     // wave-uniform
-                if (z < sh.n && b0 > 0 && b0 + SUB_L <= FT8RX_NSAMP) {
+                if (z < sh.n && sub_fits(s0 + sh.shift[z])) {           // wave-uniform
                     const float xv = xw[sh.shift[z]];
                     ar[z] += xv * sr; ai[z] -= xv * si;
                 }
             }
-        }
+        });
 #pragma unroll
         for (int z = 0; z < SUB_MAXSHIFT; z++) {
             double vr = (double)ar[z], vi = (double)ai[z];
-            for (int o = 32; o > 0; o >>= 1) { vr += __shfl_xor(vr, o); vi += __shfl_xor(vi, o); }
+            wave_sum2(vr, vi);
             if (lane == z && z < sh.n) scan[((size_t)frame * SUB_MAXSHIFT + z) * SUB_NCH + ch] = make_double2(vr, vi);
         }
     }
 }
 
 // one block per frame: best (shift, df) of signal s; df on [df_lo, df_lo + ndf * df_step)
-__global__ __launch_bounds__(256) void k_sub_pick(ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts, int max_sigs, int s,
-                                                  SubShifts sh, const double2* __restrict__ scan, float df_lo, float df_step, int ndf,
+__global__ __launch_bounds__(256) void k_sub_pick(SubSel sel, SubShifts sh, const double2* __restrict__ scan, float df_lo, float df_step, int ndf,
                                                   int chunk_samples) {
     __shared__ float best_e[256];
     __shared__ int best_i[256];
     const int frame = blockIdx.x, tid = threadIdx.x;
-    if (s >= counts[frame]) return;
+    int s00;
+    ft8rx_subsig* S = sub_begin(sel, frame, nullptr, &s00);
+    if (!S) return;
     float be = -1.0f; int bi = 0;
     for (int idx = tid; idx < sh.n * ndf; idx += 256) {
         const int z = idx / ndf, j = idx - z * ndf;
@@ -220,12 +240,11 @@ __global__ __launch_bounds__(256) void k_sub_pick(ft8rx_subsig* __restrict__ sig
     }
     if (tid == 0 && best_e[0] > 0.0f) {
         const int z = best_i[0] / ndf, j = best_i[0] - z * ndf;
-        ft8rx_subsig& S = sigs[(size_t)frame * max_sigs + s];
-        const int s0 = (int)(12000.0 * S.tsec) + sh.shift[z];
-        S.tsec = ((double)s0 + 0.5) / 12000.0;                        // int(12000 tsec) = s0 exactly
+        const int s0 = s00 + sh.shift[z];
+        S->tsec = ((double)s0 + 0.5) / 12000.0;                       // int(12000 tsec) = s0 exactly
         // the model's tone 0 is at fHz - 0.5 (receiver_sub.py:387), so that the signal sits mid-band of the 0 .. 1.19 Hz low-pass:
         // df is the signal's offset from the model, and the new fHz puts it at +0.5 Hz again
-        S.fHz += (double)(df_lo + df_step * (float)j) - 0.5;
+        S->fHz += (double)(df_lo + df_step * (float)j) - 0.5;
     }
 }
 
@@ -244,7 +263,7 @@ __global__ __launch_bounds__(256) void k_sub_pick(ft8rx_subsig* __restrict__ sig
 #define SUBD_N (SUB_NCH * SUBD_CH)              /* 4736 */
 #define SUBD_PAD 64                             /* decimated samples kept before s00 (coarse shifts reach -56) */
 #define SUBD_NZ (SUBD_PAD + SUBD_N + 64)        /* 4864 = 19 x 256 */
-struct SubdCtx { double fc; int s00; int pad; };
+struct SubdCtx { double fc; int s00; };
 
 // response of the triangular decimator (boxcar 32 applied twice) at offset f Hz from the mixing frequency, relative to DC
 FT8_DEV float subd_droop(float f) {
@@ -275,17 +294,16 @@ FT8_DEV void subd_block(const float* xs, int nb, int lb, double fc, float* sr_, 
 }
 // grid (SUBD_NZ / 256, B): z[m] = sum_{j=-31..31} (32 - |j|) x[n_c + j] e^{-2 pi i fc (n_c + j) / 12000},  n_c = s00 + 32 (m - SUBD_PAD)
 //   = R[m-1] + 32 S[m] - R[m]  with the block sums S[m] = sum_{k<32} xb[32 m + k], R[m] = sum_k k xb[32 m + k]
-__global__ __launch_bounds__(256) void k_subd_mix(const float* __restrict__ wf, const ft8rx_subsig* __restrict__ sigs,
-                                                  const int32_t* __restrict__ counts, int max_sigs, int s,
-                                                  float2* __restrict__ zdec /*[B][SUBD_NZ]*/, SubdCtx* __restrict__ ctx /*[B]*/) {
+__global__ __launch_bounds__(256) void k_subd_mix(const float* __restrict__ wf, SubSel sel, float2* __restrict__ zdec /*[B][SUBD_NZ]*/,
+                                                  SubdCtx* __restrict__ ctx /*[B]*/) {
     __shared__ float xs[257 * 33];                                       // 257 blocks of 32 samples, one pad word per block (bank-conflict free)
     __shared__ float2 Rs[257];
     const int frame = blockIdx.y, tid = threadIdx.x;
-    if (s >= counts[frame]) return;
-    const ft8rx_subsig& S = sigs[(size_t)frame * max_sigs + s];
-    const double fc = S.fHz - 0.5 + 21.875;
-    const int s00 = (int)(12000.0 * S.tsec);
-    if (blockIdx.x == 0 && tid == 0) { SubdCtx c; c.fc = fc; c.s00 = s00; c.pad = 0; ctx[frame] = c; }
+    int s00;
+    const ft8rx_subsig* S = sub_begin(sel, frame, nullptr, &s00);
+    if (!S) return;
+    const double fc = S->fHz - 0.5 + 21.875;
+    if (blockIdx.x == 0 && tid == 0) { SubdCtx c; c.fc = fc; c.s00 = s00; ctx[frame] = c; }
     const int m0 = 256 * (int)blockIdx.x;                                // first decimated sample of this block
     const int nb = s00 + SUBD_D * (m0 - 1 - SUBD_PAD);                   // full-rate index of LDS block 0 (= decimated block m0 - 1)
     const float* x = wf + (size_t)frame * FT8RX_NSAMP;
@@ -302,19 +320,17 @@ __global__ __launch_bounds__(256) void k_subd_mix(const float* __restrict__ wf, 
 
 // grid (ceil(SUBD_N / 256), B): c[m] = conj(model_bb[m]) / (1024 g) -- the correlation weight against z -- for the signal's CURRENT
 // origin (fHz, tsec as refined so far): model_bb[m] = sig[32 m] e^{-2 pi i fc (s0 + 32 m) / fs}, g = the decimator's droop at the current tone
-__global__ __launch_bounds__(256) void k_subd_model(const ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts, int max_sigs,
-                                                    int s, SubTables T, const SubdCtx* __restrict__ ctx, float2* __restrict__ model /*[B][SUBD_N]*/) {
-    __shared__ ft8rx_subsig S;
-    __shared__ double cum[80];
+__global__ __launch_bounds__(256) void k_subd_model(SubSel sel, SubTables T, const SubdCtx* __restrict__ ctx, float2* __restrict__ model /*[B][SUBD_N]*/) {
+    __shared__ SubModel M;
     const int frame = blockIdx.y, tid = threadIdx.x;
     int s0;
-    if (s >= counts[frame]) return;
-    sub_setup(sigs, counts, max_sigs, s, frame, &S, cum, &s0);
+    if (!sub_begin(sel, frame, &M, &s0)) return;
+    const ft8rx_subsig& S = M.S;
     const int m = 256 * (int)blockIdx.x + tid;
     if (m >= SUBD_N) return;
     const int n = SUBD_D * m;
     float sr, si;
-    sub_signal(S, cum, T, n, &sr, &si);
+    sub_signal(S, M.cum, T, n, &sr, &si);
     const double fc = ctx[frame].fc;
     const double rev = fc * ((double)(s0 + n) / 12000.0);              // k_subd_mix mixes with the ABSOLUTE sample index: so must the model,
     const float fr = (float)(rev - floor(rev));                        // or the amplitude estimate comes out rotated by a constant phase
@@ -329,13 +345,11 @@ __global__ __launch_bounds__(256) void k_subd_model(const ft8rx_subsig* __restri
 
 // one block per frame: Y[z][c] = sum_{m in chunk c} zdec[SUBD_PAD + off + m + shift_z / 32] c[m], off = (int(12000 tsec) - s00) / 32.
 // Same output layout as k_sub_scan (-> k_sub_pick).  Thread = (chunk, half of the shifts).
-__global__ __launch_bounds__(256) void k_subd_scan(const float2* __restrict__ zdec, const float2* __restrict__ model,
-                                                   const ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts, int max_sigs,
-                                                   int s, const SubdCtx* __restrict__ ctx, SubShifts sh, double2* __restrict__ scan) {
+__global__ __launch_bounds__(256) void k_subd_scan(const float2* __restrict__ zdec, const float2* __restrict__ model, SubSel sel,
+                                                   const SubdCtx* __restrict__ ctx, SubShifts sh, double2* __restrict__ scan) {
     const int frame = blockIdx.x, tid = threadIdx.x;
-    if (s >= counts[frame]) return;
-    const ft8rx_subsig& S = sigs[(size_t)frame * max_sigs + s];
-    const int s0 = (int)(12000.0 * S.tsec);
+    int s0;
+    if (!sub_begin(sel, frame, nullptr, &s0)) return;
     const int off = (s0 - ctx[frame].s00) / SUBD_D;
     const int c = tid & 127, zh = tid >> 7;
     const float2* z = zdec + (size_t)frame * SUBD_NZ + SUBD_PAD + off + c * SUBD_CH;
@@ -348,8 +362,7 @@ __global__ __launch_bounds__(256) void k_subd_scan(const float2* __restrict__ zd
 #pragma unroll
         for (int q = 0; q < SUB_MAXSHIFT / 2; q++) {
             const int zi = 2 * q + zh;
-            const int b0 = s0 + sh.shift[zi < sh.n ? zi : 0];
-            if (zi < sh.n && b0 > 0 && b0 + SUB_L <= FT8RX_NSAMP) {
+            if (zi < sh.n && sub_fits(s0 + sh.shift[zi < sh.n ? zi : 0])) {
                 const int idx = m + sh.shift[zi] / SUBD_D;
                 const int lo = -(SUBD_PAD + off + c * SUBD_CH), hi = SUBD_NZ + lo;       // stay inside this frame's zdec row
                 const float2 zv = (idx >= lo && idx < hi) ? z[idx] : make_float2(0.0f, 0.0f);
@@ -367,16 +380,14 @@ __global__ __launch_bounds__(256) void k_subd_scan(const float2* __restrict__ zd
 // one block per frame: the 20 low bins of y[m] = zdec[..] c[m] (the complex amplitude), then a(t) on the 375 Hz grid:
 // adec[m] = (32 / 192000) sum_k A_k e^{+2 pi i k 32 m / 192000},  m = 0 .. SUBD_N  (what Receiver.subtract_signal's ifft of the 20
 // kept bins gives at sample 32 m)
-__global__ __launch_bounds__(256) void k_subd_accum(const float2* __restrict__ zdec, const float2* __restrict__ model,
-                                                    const ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts, int max_sigs,
-                                                    int s, const SubdCtx* __restrict__ ctx, float2* __restrict__ adec /*[B][SUBD_N + 1]*/) {
+__global__ __launch_bounds__(256) void k_subd_accum(const float2* __restrict__ zdec, const float2* __restrict__ model, SubSel sel,
+                                                    const SubdCtx* __restrict__ ctx, float2* __restrict__ adec /*[B][SUBD_N + 1]*/) {
     __shared__ double pr[4][20], pi_[4][20];
     __shared__ float Ar[20], Ai[20];
     const int frame = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (s >= counts[frame]) return;
-    const ft8rx_subsig& S = sigs[(size_t)frame * max_sigs + s];
-    const int s0 = (int)(12000.0 * S.tsec);
-    const bool ok = s0 > 0 && s0 + SUB_L <= FT8RX_NSAMP;
+    int s0;
+    if (!sub_begin(sel, frame, nullptr, &s0)) return;
+    const bool ok = sub_fits(s0);
     const int off = (s0 - ctx[frame].s00) / SUBD_D;
     const float2* z = zdec + (size_t)frame * SUBD_NZ + SUBD_PAD + off;
     const float2* w = model + (size_t)frame * SUBD_N;
@@ -387,18 +398,12 @@ __global__ __launch_bounds__(256) void k_subd_accum(const float2* __restrict__ z
         const float2 zv = z[m], wv = w[m];
         const float yr = zv.x * wv.x - zv.y * wv.y, yi = zv.x * wv.y + zv.y * wv.x;
         const float rv = (float)(SUBD_D * m) * (1.0f / 192000.0f);
-        const float wr = __builtin_amdgcn_cosf(rv), wi = -__builtin_amdgcn_sinf(rv);
-        float rr = 1.0f, ri = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 20; k++) {
-            fr_[k] += yr * rr - yi * ri; fi_[k] += yr * ri + yi * rr;
-            const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
-        }
+        sub_bins_analyse(yr, yi, __builtin_amdgcn_cosf(rv), -__builtin_amdgcn_sinf(rv), fr_, fi_);
     }
 #pragma unroll
     for (int k = 0; k < 20; k++) {
         double vr = (double)fr_[k], vi = (double)fi_[k];
-        for (int o = 32; o > 0; o >>= 1) { vr += __shfl_xor(vr, o); vi += __shfl_xor(vi, o); }
+        wave_sum2(vr, vi);
         if (lane == 0) { pr[wave][k] = vr; pi_[wave][k] = vi; }
     }
     __syncthreads();
@@ -410,41 +415,28 @@ __global__ __launch_bounds__(256) void k_subd_accum(const float2* __restrict__ z
     __syncthreads();
     for (int m = tid; m <= SUBD_N; m += 256) {
         const float rv = (float)(SUBD_D * m) * (1.0f / 192000.0f);
-        const float wr = __builtin_amdgcn_cosf(rv), wi = __builtin_amdgcn_sinf(rv);
-        float rr = 1.0f, ri = 0.0f, er = 0.0f, ei = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 20; k++) {
-            er += Ar[k] * rr - Ai[k] * ri; ei += Ar[k] * ri + Ai[k] * rr;
-            const float t = rr * wr - ri * wi; ri = rr * wi + ri * wr; rr = t;
-        }
+        float er, ei;
+        sub_bins_synth(Ar, Ai, __builtin_amdgcn_cosf(rv), __builtin_amdgcn_sinf(rv), &er, &ei);
         adec[(size_t)frame * (SUBD_N + 1) + m] = make_float2(er, ei);
     }
 }
 
 // full rate: x[n] -= 2 Re(a(n) sig[n]) with a(n) interpolated between adec[n / 32] and adec[n / 32 + 1] (beyond the last decimated
 // sample -- the final 128 of the 151 680 -- the last value is held)
-__global__ __launch_bounds__(256) void k_subd_apply(float* __restrict__ wf, const ft8rx_subsig* __restrict__ sigs,
-                                                    const int32_t* __restrict__ counts, int max_sigs, int s, SubTables T,
-                                                    const float2* __restrict__ adec) {
-    __shared__ ft8rx_subsig S;
-    __shared__ double cum[80];
-    const int frame = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+__global__ __launch_bounds__(256) void k_subd_apply(float* __restrict__ wf, SubSel sel, SubTables T, const float2* __restrict__ adec) {
+    __shared__ SubModel M;
+    const int frame = blockIdx.y;
     int s0;
-    if (!sub_setup(sigs, counts, max_sigs, s, frame, &S, cum, &s0)) return;
+    if (!sub_begin(sel, frame, &M, &s0) || !sub_fits(s0)) return;
     float* x = wf + (size_t)frame * FT8RX_NSAMP + s0;
     const float2* a = adec + (size_t)frame * (SUBD_N + 1);
-    for (int i = 0; i < SUB_CPW; i++) {
-        const int ch = (blockIdx.x * 4 + wave) * SUB_CPW + i;
-        for (int m = ch * SUB_CH + lane; m < (ch + 1) * SUB_CH; m += 64) {
-            float sr, si;
-            sub_signal(S, cum, T, m, &sr, &si);
-            int md = m >> 5; if (md > SUBD_N - 1) md = SUBD_N - 1;
-            const float2 a0 = a[md], a1 = a[md + 1];
-            float fq = (float)(m - SUBD_D * md) * (1.0f / 32.0f); if (fq > 1.0f) fq = 1.0f;
-            const float er = a0.x + fq * (a1.x - a0.x), ei = a0.y + fq * (a1.y - a0.y);
-            x[m] = x[m] - 2.0f * (er * sr - ei * si);
-        }
-    }
+    sub_walk(M, T, [&](int m, float sr, float si) {
+        int md = m >> 5; if (md > SUBD_N - 1) md = SUBD_N - 1;
+        const float2 a0 = a[md], a1 = a[md + 1];
+        float fq = (float)(m - SUBD_D * md) * (1.0f / 32.0f); if (fq > 1.0f) fq = 1.0f;
+        const float er = a0.x + fq * (a1.x - a0.x), ei = a0.y + fq * (a1.y - a0.y);
+        x[m] = x[m] - 2.0f * (er * sr - ei * si);
+    });
 }
 
 // ---- refine = 3: Candidate.refine_time_origin of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:58-72) ----
@@ -454,50 +446,26 @@ __global__ __launch_bounds__(256) void k_subd_apply(float* __restrict__ wf, cons
 // i.e. of the residual the earlier subtractions left (:273-276; the fb loop of :64 passes fb_0 every time).  First strict maximum;
 // tsec = tb / 200, fHz = fb_0 / 16.  Per signal index s and batch: k_cyc_a_f32 + k_cyc_bc (spectrum of the working copy), then
 // k_refine3 (one block per frame).  Same FFT plans, symbol DFT and fp64 score sums as k_fine: bit-exact against ft8o_refine_time_origin.
-FT8_DEV void cyc_a_load_f32(const float* __restrict__ a, int n2b, int tid, float2 (&raw)[10]) {
-#pragma unroll
-    for (int q = 0; q < 10; q++) {
-        const int i = tid + 256 * q, ic = i < 2400 ? i : 0;
-        const int c = ic & 7, n1 = ic >> 3;
-        const int m = 320 * n1 + n2b + c;
-        const int inb = (2 * m < FT8RX_NSAMP) ? -1 : 0;                     // zero padding by masking a clamped load (cyc_a_load)
-        const float2 v = *reinterpret_cast<const float2*>(a + ((2 * m) & inb));
-        raw[q] = make_float2(__uint_as_float(__float_as_uint(v.x) & (uint32_t)inb), __uint_as_float(__float_as_uint(v.y) & (uint32_t)inb));
-    }
-}
-__global__ __launch_bounds__(256) void k_cyc_a_f32(const float* __restrict__ audio, cpx* __restrict__ A, Tables T) {
+__global__ __launch_bounds__(256) void k_cyc_a_f32(const float* __restrict__ audio, cpx* __restrict__ A, Tables T) {   // k_cyc_a on the float32 working copy
     __shared__ cpx bufA[8 * 300];
     __shared__ cpx bufB[8 * 300];
     const int tile = (blockIdx.x & 7) * 5 + (blockIdx.x >> 3);
     const int f = blockIdx.y, tid = threadIdx.x, n2b = 8 * tile;
     float2 raw[10];
-    cyc_a_load_f32(audio + (size_t)f * FT8RX_NSAMP, n2b, tid, raw);
-#pragma unroll
-    for (int q = 0; q < 10; q++) { const int i = tid + 256 * q; if (i < 2400) bufA[(i & 7) * 300 + (i >> 3)] = raw[q]; }
-    cpx w[10];
-#pragma unroll
-    for (int q = 0; q < 10; q++) { const int i = tid + 256 * q, ic = i < 2400 ? i : 0; w[q] = T.W96000[(n2b + (ic & 7)) * (ic >> 3)]; }
-    __syncthreads();
-    cpx* r = lds_fft<300, 5, 5, 4, 3>(bufA, bufB, T.W300, 8, tid, 256);
-    cpx* out = A + (size_t)f * 96000;
-#pragma unroll
-    for (int q = 0; q < 10; q++) {
-        const int i = tid + 256 * q;
-        if (i < 2400) { const int c = i & 7, k1 = i >> 3; out[k1 * 320 + n2b + c] = cmul(r[c * 300 + k1], w[q]); }
-    }
+    cyc_a_load(audio + (size_t)f * FT8RX_NSAMP, n2b, tid, raw);
+    cyc_a_frame(raw, bufA, bufB, A + (size_t)f * 96000, T, n2b, tid);
 }
 
 // one block of FINE_NT threads per frame; T.taper must point at 100 ones (the experiment's slice has no tapers)
-__global__ __launch_bounds__(FINE_NT) void k_refine3(const cpx* __restrict__ spec, ft8rx_subsig* __restrict__ sigs, const int32_t* __restrict__ counts,
-                                                     int max_sigs, int s, Tables T) {
+__global__ __launch_bounds__(FINE_NT) void k_refine3(const cpx* __restrict__ spec, SubSel sel, Tables T) {
     __shared__ cpx z[3200];
     __shared__ cpx slice[FINE_SLICE];
     __shared__ cpx w400[400];
     __shared__ cpx w32[32];
     __shared__ __attribute__((aligned(8))) double dsum[12 * 21 * 2];
     const int frame = blockIdx.x, tid = threadIdx.x;
-    if (s >= counts[frame]) return;
-    ft8rx_subsig& S = sigs[(size_t)frame * max_sigs + s];
+    if (sel.s >= sel.counts[frame]) return;
+    ft8rx_subsig& S = sel.sigs[(size_t)frame * sel.max_sigs + sel.s];
     const int fb0 = (int)(0.5 + S.fHz * 16.0);                       // receiver_sub.py:59
     const int tb0 = (int)(0.5 + S.tsec * 200.0);                     // :60
     if (fb0 - 182 < 0 || fb0 - 182 + FINE_SLICE > FT8RX_SPEC_BINS) return;        // outside the kept spectrum: the origin stays as it is
