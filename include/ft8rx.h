@@ -43,6 +43,8 @@
  *     ft8rx_set_weak                                                                   (opt-in weak-signal sync)
  *     ft8rx_set_reports  ft8rx_fetch_reports  ft8rx_report_probe                       (opt-in measured SNR / frequency / time of each decode)
  *     ft8rx_ddc  ft8rx_ddc_host  ft8rx_ddc_taps                                        (down-converter: real / IQ input at 24 .. 192 kHz -> 12 kHz frames)
+ *     ft8rx_ddc_stream_open  ft8rx_ddc_stream_push  ft8rx_ddc_stream_frame  ft8rx_ddc_stream_info  ft8rx_ddc_stream_read
+ *     ft8rx_ddc_stream_close                                                           (the same on a continuous stream, state on the device)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
@@ -451,6 +453,37 @@ int  ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, 
 /* host only, no GPU: the taps the kernels use.  stage 1 / 2 -> their count, and the first min(count, cap) of them in taps (float32;
  * taps may be NULL); 0 for a stage the rate does not have; -1 for a rate the build does not take (or another stage) */
 int  ft8rx_ddc_taps(int32_t rate_hz, int stage, float* taps, int cap);
+/* Streaming down-converter (extension): the definition above on a continuous stream, pushed in chunks of any
+ * length, one stream set per handle.  Input index n and output index m = n / D are ABSOLUTE: they count from index 0 of the sample
+ * clock and never restart; only n mod 2^32 enters the mixer phase, so it is exact at any n.  The stream begins at n_origin (a multiple
+ * of 1008 D; live code passes 0) and is zero before it.  State, all on the handle, allocated by open, released by close or
+ * ft8rx_destroy, nothing allocated in between: per stream a ring of the newest input samples in their own kind (a power of two that
+ * holds one second and one tile's span), per channel a ring of the last 360000 outputs (two cycles; int16, optionally float32 before
+ * rounding), a channel table of its own, 64-bit counters.  ft8rx_ddc / ft8rx_ddc_host between two pushes leave all of it untouched.
+ * Outputs are produced in whole tiles of 1008 anchored at m = 1008 k, with the arithmetic of ft8rx_ddc's tile: every output is the same
+ * bits however the stream was cut into chunks, and the first cycle of a stream with n_origin = 0 is ft8rx_ddc's output bit for bit.  An
+ * output exists once its tile's last input has been pushed: at most 84 ms (one tile) + C2 R1 + C1 input samples (about 6 ms) after its
+ * own sample.
+ * open   kind, rate_hz, n_streams, n_out (<= max_frames), src, f_dial_hz, gain, f_mixed_hz: as ft8rx_ddc, refused by the same checks;
+ *        keep_f32 != 0: also keep the float32 ring (tests).  Refused while a stream is open.
+ * push   n_new samples of every stream, 1 .. rate_hz (one second): in = [n_streams][n_new] samples, host memory (copied through a
+ *        page-locked buffer) or, on_device != 0, device memory; at most two copies per stream into the rings, then ONE kernel for every
+ *        tile whose inputs are now complete.  Asynchronous on the handle's main stream.  m_produced: optional, the absolute index one
+ *        past the last output produced so far.
+ * frame  frame j position p = output m_first + p of channel j, for p < n_have; zero from n_have on, before the origin and from
+ *        m_produced on.  m_first is a signed index passed as its 64-bit two's complement (it may be odd, negative, before the origin).
+ *        d_audio: device [n_out][180000], NULL = the staging audio (ft8rx_enqueue_batch(h, ft8rx_staging_audio(h), n_out) is the
+ *        intended next call).  Refused with -1 when part of the range has left the ring.  Waits for the batches in flight.
+ * read   test aid: outputs [m_first, m_first + n) of every channel, all of them in the ring, -> host y_i16 / y_f32 [n_out][n] (either
+ *        may be NULL); synchronous.
+ * info   ring capacities in samples, samples pushed per stream, m_produced. */
+int  ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src,
+                           const double* f_dial_hz, float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz);
+int  ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
+int  ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16_t* d_audio);
+int  ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first, int n, int16_t* y_i16, float* y_f32);
+int  ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced);
+int  ft8rx_ddc_stream_close(ft8rx_handle* h);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

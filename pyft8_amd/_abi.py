@@ -71,6 +71,12 @@ PROTOTYPES = {
     "ft8rx_ddc": (INT, (PTR, PTR, INT, I32, INT, U64, U64, INT, PTR, PTR, F32, PTR, PTR, PTR)),
     "ft8rx_ddc_host": (INT, (PTR, PTR, INT, I32, INT, U64, U64, INT, PTR, PTR, F32, PTR)),
     "ft8rx_ddc_taps": (INT, (I32, INT, PTR, INT)),
+    "ft8rx_ddc_stream_open": (INT, (PTR, INT, I32, INT, INT, PTR, PTR, F32, U64, INT, PTR)),
+    "ft8rx_ddc_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
+    "ft8rx_ddc_stream_frame": (INT, (PTR, U64, INT, PTR)),
+    "ft8rx_ddc_stream_read": (INT, (PTR, U64, INT, PTR, PTR)),
+    "ft8rx_ddc_stream_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_ddc_stream_close": (INT, (PTR,)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

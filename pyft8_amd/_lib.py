@@ -278,6 +278,7 @@ class Handle:
         self.device = int(device)
         self._h = C.c_void_p()
         self.ap_calls = (None, None)
+        self._ds = None                    # the open down-converter stream: (kind, n_streams, n_out)
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
@@ -743,6 +744,58 @@ class Handle:
         self._chk(self._L.ft8rx_ddc(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc")
         self.sync()                                          # the tensors may go once the kernel has run
         return (fm, d_f32.cpu().numpy()) if want_float else fm
+
+    # ---- streaming down-converter (ft8rx_ddc_stream_*): one stream set per handle, state on the device
+    def ddc_stream_open(self, kind, rate, n_streams, src, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
+        """Open the stream: n_streams inputs of `kind` at `rate` Hz feed len(src) channels (channel j = stream src[j], dial
+        f_dial_hz[j]); n_origin = absolute index of the first sample that will be pushed, a multiple of 1008 D.  -> f_mixed_hz."""
+        src = np.ascontiguousarray(src, np.int32).reshape(-1)
+        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
+        if len(src) != len(f) or len(src) < 1:
+            raise Ft8rxError(f"ddc_stream_open: one src and one f_dial_hz per channel, got {len(src)} and {len(f)}")
+        fm = np.zeros(len(src), np.float64)
+        self._chk(self._L.ft8rx_ddc_stream_open(self._h, int(kind), int(rate), int(n_streams), len(src), src.ctypes.data, f.ctypes.data,
+                                                float(gain), int(n_origin), int(bool(keep_f32)), fm.ctypes.data), "ft8rx_ddc_stream_open")
+        self._ds = (int(kind), int(n_streams), len(src))
+        return fm
+
+    def ddc_stream_push(self, samples):
+        """Push the next samples of every stream ([n_streams][n], forms of ddc.pack; 1 .. one second) -> absolute index one past the
+        last output produced so far.  Asynchronous."""
+        from . import ddc as _ddc
+        if self._ds is None:
+            raise Ft8rxError("ddc_stream_push: no stream is open (ddc_stream_open)")
+        a, n_streams, n = _ddc.pack(samples, self._ds[0])
+        if n_streams != self._ds[1]:
+            raise Ft8rxError(f"ddc_stream_push: {n_streams} streams, the open stream has {self._ds[1]}")
+        m = C.c_uint64()
+        self._chk(self._L.ft8rx_ddc_stream_push(self._h, a.ctypes.data, n, 0, C.byref(m)), "ft8rx_ddc_stream_push")
+        return int(m.value)
+
+    def ddc_stream_frame(self, m_first, n_have=NSAMP, d_audio_ptr=None):
+        """Gather outputs [m_first, m_first + n_have) of every channel into the frames of the staging buffer (or d_audio_ptr)."""
+        self._chk(self._L.ft8rx_ddc_stream_frame(self._h, int(m_first) & 0xFFFFFFFFFFFFFFFF, int(n_have), d_audio_ptr), "ft8rx_ddc_stream_frame")
+
+    def ddc_stream_read(self, m_first, n, want_float=False):
+        """Test aid: outputs [m_first, m_first + n) of every channel out of the ring -> int16 [n_out, n] (, float32 [n_out, n])."""
+        if self._ds is None:
+            raise Ft8rxError("ddc_stream_read: no stream is open (ddc_stream_open)")
+        y = np.zeros((self._ds[2], int(n)), np.int16)
+        f = np.zeros((self._ds[2], int(n)), np.float32) if want_float else None
+        self._chk(self._L.ft8rx_ddc_stream_read(self._h, int(m_first) & 0xFFFFFFFFFFFFFFFF, int(n), y.ctypes.data,
+                                                f.ctypes.data if want_float else None), "ft8rx_ddc_stream_read")
+        return (y, f) if want_float else y
+
+    def ddc_stream_info(self):
+        """-> {"in_capacity", "out_capacity", "n_pushed", "m_produced"}: ring capacities in samples, samples pushed, outputs produced
+        (absolute index one past the last)."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._chk(self._L.ft8rx_ddc_stream_info(self._h, *[C.byref(x) for x in v]), "ft8rx_ddc_stream_info")
+        return dict(zip(("in_capacity", "out_capacity", "n_pushed", "m_produced"), (int(x.value) for x in v)))
+
+    def ddc_stream_close(self):
+        self._chk(self._L.ft8rx_ddc_stream_close(self._h), "ft8rx_ddc_stream_close")
+        self._ds = None
 
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for

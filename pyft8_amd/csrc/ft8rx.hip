@@ -63,6 +63,7 @@
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
+#include "ddc_ring.hpp"
 #include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
@@ -198,6 +199,16 @@ struct ft8rx_handle {
     // staging of ft8rx_ddc_host, grown when a call needs more
     // (h_ddc_outs: its page-locked source; ddc_ev: behind the copy of the last call's table, so that the next call can rewrite it)
     DdcOut* d_ddc_outs = nullptr; DdcOut* h_ddc_outs = nullptr; hipEvent_t ddc_ev = nullptr; void* d_ddc_in = nullptr; size_t ddc_in_cap = 0;
+    // streaming down-converter (ft8rx_ddc_stream_*): everything is allocated by open and released by close (or
+    // destroy); it shares nothing but the tap tables with the one-shot above.  d_in: [n_streams][cap] samples of `kind`, the newest cap
+    // of each stream; d_out / d_f32: [n_out][OUT_RING]; h_stage: page-locked, one second of every stream; ev: behind the last copy out
+    // of h_stage.  n_origin, pushed, tiles: absolute index of the first sample, samples pushed, first tile not produced yet.
+    struct DdcStream {
+        bool open = false; int kind = 0, D = 0, n_streams = 0, n_out = 0; int32_t rate = 0; float scale = 0.0f;
+        int64_t n_origin = 0, pushed = 0, tiles = 0, cap = 0;
+        void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
+        hipEvent_t ev = nullptr;
+    } ds;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -211,6 +222,16 @@ static_assert(sizeof(ft8rx_handle::ev_chunk) / sizeof(hipEvent_t) == batchplan::
               sizeof(ft8rx_handle::ap_chunk_version) / sizeof(uint32_t) == batchplan::MAX_CHUNKS &&
               sizeof(batchplan::BatchPlan::cb) / sizeof(int) == batchplan::MAX_CHUNKS + 1 &&
               batchplan::MAX_CHUNKS == 16 && batchplan::MAX_STREAMS == 8, "per-chunk arrays and the plan's boundaries");
+
+// the streaming down-converter's index arithmetic (ddc_ring.hpp, host only) against the kernels' geometry
+static_assert(ddcring::TILE == DDC_TO && ddcring::OUT_RING == 2 * FT8RX_NSAMP, "ddc_ring.hpp: tile and output ring");
+template <int D> constexpr bool ddc_ring_geom_ok() {
+    using G = DdcGeom<D>;
+    return ddcring::geom(D).R1 == G::R1 && ddcring::geom(D).C1 == G::C1 && ddcring::geom(D).R2 == G::R2 && ddcring::geom(D).C2 == G::C2 &&
+           ddcring::last(D) == (int64_t)(G::NV - 1 - G::C2) * G::R1 + G::C1 && ddcring::in_capacity(D) >= 12000 * D + ddcring::span(D);
+}
+static_assert(ddc_ring_geom_ok<1>() && ddc_ring_geom_ok<2>() && ddc_ring_geom_ok<4>() && ddc_ring_geom_ok<8>() && ddc_ring_geom_ok<16>(),
+              "ddc_ring.hpp: the filter geometry is the kernels'");
 
 static void set_err(ft8rx_handle* h, const char* fmt, ...) {
     char buf[512];
@@ -434,6 +455,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     for (hipEvent_t e : h->ev_chunk) if (e) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
+    if (h->ds.ev) hipEventDestroy(h->ds.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -1349,13 +1371,9 @@ static int ddc_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz
     return D;
 }
 
-// the launch: channel table (sorted by stream, so that outputs of one stream run next to each other and share its loads in L2) -> device,
-// one kernel on the main stream
-static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_t rate_hz, uint64_t stream_stride, uint64_t n_samples, int n_out,
-                      const int32_t* src, const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
-    if (!h->ddc_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ddc_ev, hipEventDisableTiming));
-    else HIPCHK(h, hipEventSynchronize(h->ddc_ev));      // the previous call's table has left the page-locked buffer (long ago, as a rule)
-    DdcOut* outs = h->h_ddc_outs;
+// the channel table of n_out outputs: frequency words, sorted by stream (so that outputs of one stream run next to each other and share
+// its loads in L2); f_mixed_hz: optional, the dials really mixed
+static void ddc_table(DdcOut* outs, int32_t rate_hz, int n_out, const int32_t* src, const double* f_dial_hz, double* f_mixed_hz) {
     for (int j = 0; j < n_out; j++) {
         const double r = nearbyint((f_dial_hz[j] + 3000.0) / (double)rate_hz * 4294967296.0);
         const uint32_t w = (uint32_t)((long long)r & 0xffffffffLL);
@@ -1367,6 +1385,16 @@ static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_
         }
     }
     std::stable_sort(outs, outs + n_out, [](const DdcOut& a, const DdcOut& b) { return a.src < b.src; });
+}
+
+// the launch: channel table (sorted by stream, so that outputs of one stream run next to each other and share its loads in L2) -> device,
+// one kernel on the main stream
+static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_t rate_hz, uint64_t stream_stride, uint64_t n_samples, int n_out,
+                      const int32_t* src, const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    if (!h->ddc_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ddc_ev, hipEventDisableTiming));
+    else HIPCHK(h, hipEventSynchronize(h->ddc_ev));      // the previous call's table has left the page-locked buffer (long ago, as a rule)
+    DdcOut* outs = h->h_ddc_outs;
+    ddc_table(outs, rate_hz, n_out, src, f_dial_hz, f_mixed_hz);
     HIPCHK(h, hipMemcpyAsync(h->d_ddc_outs, outs, sizeof(DdcOut) * (size_t)n_out, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(h->ddc_ev, h->stream));
     const float scale = gain * (kind == FT8RX_DDC_IQ_I16 || kind == FT8RX_DDC_IQ_F32 ? 1.0f : 2.0f);
@@ -1414,6 +1442,171 @@ int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, i
     if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
     if (const int rc = ddc_launch(h, D, h->d_ddc_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- streaming down-converter.  The index arithmetic is ddc_ring.hpp's.
+// hand one allocation of the handle back (ft8rx_ddc_stream_close; everything else lives until ft8rx_destroy)
+static void release_dev(ft8rx_handle* h, void* p) {
+    if (!p) return;
+    for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == p) { h->allocs.erase(h->allocs.begin() + i); break; }
+    hipFree(p);
+}
+static void release_host(ft8rx_handle* h, void* p) {
+    if (!p) return;
+    for (size_t i = 0; i < h->pinned.size(); i++) if (h->pinned[i] == p) { h->pinned.erase(h->pinned.begin() + i); break; }
+    hipHostFree(p);
+}
+static void ddc_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::DdcStream& s = h->ds;
+    release_dev(h, s.d_in); release_dev(h, s.d_out); release_dev(h, s.d_f32); release_dev(h, s.d_outs); release_host(h, s.h_stage);
+    const hipEvent_t ev = s.ev;
+    s = ft8rx_handle::DdcStream();
+    s.ev = ev;
+}
+
+int ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
+                          float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    if (h->ds.open) { set_err(h, "ft8rx_ddc_stream_open: a stream is open on this handle already (ft8rx_ddc_stream_close)"); return -1; }
+    const int D = ddc_check(h, "ft8rx_ddc_stream_open", kind, rate_hz, n_streams, 0, 0, n_out, src, f_dial_hz, gain);
+    if (D < 0) return -1;
+    if (n_origin % (uint64_t)(DDC_TO * D) != 0 || n_origin > ((uint64_t)1 << 62)) {
+        set_err(h, "ft8rx_ddc_stream_open: n_origin %llu is not a multiple of %d (1008 D)", (unsigned long long)n_origin, DDC_TO * D); return -1;
+    }
+    ENTER(h);
+    if (ddc_workspaces(h)) return -2;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.ev) HIPCHK(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    const size_t sb = DDC_SAMPLE_BYTES[kind], cap = (size_t)ddcring::in_capacity(D);
+    char* d_in = nullptr;
+    int rc = dalloc(h, &d_in, (size_t)n_streams * cap * sb);
+    s.d_in = d_in;
+    if (!rc) rc = dalloc(h, &s.d_out, (size_t)n_out * ddcring::OUT_RING);
+    if (!rc && keep_f32) rc = dalloc(h, &s.d_f32, (size_t)n_out * ddcring::OUT_RING);
+    if (!rc) rc = dalloc(h, &s.d_outs, (size_t)n_out);
+    if (!rc) rc = halloc(h, &s.h_stage, (size_t)n_streams * (size_t)rate_hz * sb);
+    if (rc) { ddc_stream_release(h); return -2; }
+    std::vector<DdcOut> outs((size_t)n_out);
+    ddc_table(outs.data(), rate_hz, n_out, src, f_dial_hz, f_mixed_hz);
+    hipError_t e = hipMemcpyAsync(s.d_outs, outs.data(), sizeof(DdcOut) * (size_t)n_out, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.d_out, 0, sizeof(int16_t) * (size_t)n_out * ddcring::OUT_RING, h->stream);
+    if (e == hipSuccess && s.d_f32) e = hipMemsetAsync(s.d_f32, 0, sizeof(float) * (size_t)n_out * ddcring::OUT_RING, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the table is a pageable vector of this call
+    if (e != hipSuccess) { set_err(h, "ft8rx_ddc_stream_open: %s", hipGetErrorString(e)); ddc_stream_release(h); return -2; }
+    s.kind = kind; s.D = D; s.rate = rate_hz; s.n_streams = n_streams; s.n_out = n_out; s.cap = (int64_t)cap;
+    s.scale = gain * (kind == FT8RX_DDC_IQ_I16 || kind == FT8RX_DDC_IQ_F32 ? 1.0f : 2.0f);
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.tiles = s.n_origin / (DDC_TO * D);
+    s.open = true;
+    return 0;
+}
+
+int ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+    if (!h) return -1;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_stream_push: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
+    if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
+    const size_t sb = DDC_SAMPLE_BYTES[s.kind];
+    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_stream_push: in is NULL or not aligned to a sample"); return -1; }
+    // (no ENTER: a push touches the stream's own rings only, on the main stream; batches in flight read neither)
+    HIPCHK(h, hipSetDevice(h->device));
+    const char* from = (const char*)in;
+    if (!on_device) {                                    // through the page-locked buffer, once the previous push's copies have left it
+        HIPCHK(h, hipEventSynchronize(s.ev));
+        memcpy(s.h_stage, in, (size_t)s.n_streams * (size_t)n_new * sb);
+        from = s.h_stage;
+    }
+    const hipMemcpyKind dir = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const ddcring::Split sp = ddcring::split(s.pushed, (int64_t)n_new, s.cap);
+    for (int i = 0; i < s.n_streams; i++) {              // at most two copies per stream: up to the ring's end, then from its start
+        char* ring = (char*)s.d_in + (size_t)i * (size_t)s.cap * sb;
+        const char* chunk = from + (size_t)i * (size_t)n_new * sb;
+        HIPCHK(h, hipMemcpyAsync(ring + (size_t)sp.pos * sb, chunk, (size_t)sp.first * sb, dir, h->stream));
+        if (sp.second) HIPCHK(h, hipMemcpyAsync(ring, chunk + (size_t)sp.first * sb, (size_t)sp.second * sb, dir, h->stream));
+    }
+    if (!on_device) HIPCHK(h, hipEventRecord(s.ev, h->stream));
+    s.pushed += (int64_t)n_new;
+    const int64_t n_end = s.n_origin + s.pushed, done = ddcring::tiles_done(s.n_origin, n_end, s.D);
+    const int n_tiles = (int)(done - s.tiles);           // at most 12000 / 1008 + 1
+    if (n_tiles > 0) {
+        const unsigned grid = (unsigned)s.n_out * (unsigned)n_tiles;
+#define DDC_GO(DD) k_ddc_stream<DD><<<grid, DDC_NT, 0, h->stream>>>(s.d_in, s.kind, (unsigned long long)s.cap, (long long)s.n_origin, (long long)n_end, \
+                                                                   s.d_outs, (long long)s.tiles, n_tiles, s.scale, (int)ddcring::OUT_RING, s.d_out, s.d_f32)
+        switch (s.D) { case 1: DDC_GO(1); break; case 2: DDC_GO(2); break; case 4: DDC_GO(4); break; case 8: DDC_GO(8); break; default: DDC_GO(16); }
+#undef DDC_GO
+        HIPCHK(h, hipGetLastError());
+        s.tiles = done;
+    }
+    if (m_produced) *m_produced = (uint64_t)(s.tiles * DDC_TO);
+    return 0;
+}
+
+int ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first_u, int n_have, int16_t* d_audio) {
+    if (!h) return -1;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_stream_frame: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
+    if (n_have < 0 || n_have > FT8RX_NSAMP) { set_err(h, "ft8rx_ddc_stream_frame: n_have %d outside [0, %d]", n_have, FT8RX_NSAMP); return -1; }
+    const int64_t m_first = (int64_t)m_first_u;          // two's complement: a negative index lies before index 0
+    if (m_first < -((int64_t)1 << 62) || m_first > ((int64_t)1 << 62)) { set_err(h, "ft8rx_ddc_stream_frame: m_first out of range"); return -1; }
+    const int64_t m_origin = s.n_origin / s.D, m_done = s.tiles * DDC_TO;
+    if (!ddcring::held(m_first, n_have, m_origin, m_done).ok) {
+        set_err(h, "ft8rx_ddc_stream_frame: outputs from %lld on have left the ring (it holds %lld .. %lld)", (long long)(m_first > m_origin ? m_first : m_origin),
+                (long long)(m_done - ddcring::OUT_RING), (long long)m_done);
+        return -1;
+    }
+    ENTER(h);                                            // a batch in flight may still read the staging audio
+    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    k_ddc_gather<<<dim3((FT8RX_NSAMP + 255) / 256, (unsigned)s.n_out), 256, 0, h->stream>>>(s.d_out, (int)ddcring::OUT_RING, (long long)m_first, n_have,
+                                                                                          (long long)m_origin, (long long)m_done, d_audio);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first_u, int n, int16_t* y_i16, float* y_f32) {
+    if (!h) return -1;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_stream_read: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
+    const int64_t m_first = (int64_t)m_first_u, m_origin = s.n_origin / s.D, m_done = s.tiles * DDC_TO;
+    if (n < 1 || m_first < m_origin || m_first + n > m_done || m_first < m_done - ddcring::OUT_RING) {
+        set_err(h, "ft8rx_ddc_stream_read: outputs [%lld, %lld) are not all in the ring (it holds %lld .. %lld)", (long long)m_first, (long long)(m_first + n),
+                (long long)(m_done - ddcring::OUT_RING > m_origin ? m_done - ddcring::OUT_RING : m_origin), (long long)m_done);
+        return -1;
+    }
+    if (y_f32 && !s.d_f32) { set_err(h, "ft8rx_ddc_stream_read: the stream was opened without the float32 copy (keep_f32)"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int64_t pos = ddcring::out_pos(m_first), first = n < ddcring::OUT_RING - pos ? n : ddcring::OUT_RING - pos;
+    for (int j = 0; j < s.n_out; j++) {
+        const size_t row = (size_t)j * ddcring::OUT_RING;
+        if (y_i16) {
+            HIPCHK(h, hipMemcpy(y_i16 + (size_t)j * n, s.d_out + row + pos, sizeof(int16_t) * (size_t)first, hipMemcpyDeviceToHost));
+            if (first < n) HIPCHK(h, hipMemcpy(y_i16 + (size_t)j * n + first, s.d_out + row, sizeof(int16_t) * (size_t)(n - first), hipMemcpyDeviceToHost));
+        }
+        if (y_f32) {
+            HIPCHK(h, hipMemcpy(y_f32 + (size_t)j * n, s.d_f32 + row + pos, sizeof(float) * (size_t)first, hipMemcpyDeviceToHost));
+            if (first < n) HIPCHK(h, hipMemcpy(y_f32 + (size_t)j * n + first, s.d_f32 + row, sizeof(float) * (size_t)(n - first), hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+int ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced) {
+    if (!h) return -1;
+    const ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_stream_info: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
+    if (in_capacity) *in_capacity = (uint64_t)s.cap;
+    if (out_capacity) *out_capacity = (uint64_t)ddcring::OUT_RING;
+    if (n_pushed) *n_pushed = (uint64_t)s.pushed;
+    if (m_produced) *m_produced = (uint64_t)(s.tiles * DDC_TO);
+    return 0;
+}
+
+int ft8rx_ddc_stream_close(ft8rx_handle* h) {
+    if (!h) return -1;
+    if (!h->ds.open) { set_err(h, "ft8rx_ddc_stream_close: no stream is open"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the rings
+    ddc_stream_release(h);
     return 0;
 }
 

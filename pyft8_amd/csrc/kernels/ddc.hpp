@@ -5,7 +5,11 @@
 //   v[k] = sum_j h1[j] u[k R1 + j - C1]                   D >= 4 only (R1 = D / 2); otherwise v = u
 //   z[m] = sum_j h2[j] v[m R2 + j - C2]                   R2 = 2 (1 at D = 1)
 //   y[m] = scale Re(i^m z[m])                             scale = gain g_kind
-// The host side (design of the taps, argument checks, launch) is in ft8rx.hip.
+// The tile is written once (ddc_tile) and used by two kernels: k_ddc (one call = one cycle, the input an array of the call) and
+// k_ddc_stream (a continuous stream, the input a ring of the newest samples, the output a ring of two cycles,
+// indices absolute); k_ddc_gather cuts frames out of that ring.
+// The host side (design of the taps, argument checks, launch, the stream's state) is in ft8rx.hip, the stream's index arithmetic in
+// ddc_ring.hpp.
 #pragma once
 
 #define DDC_NT 256                     // threads per block
@@ -56,35 +60,28 @@ __device__ __forceinline__ float2 ddc_phasor(uint32_t p) {
 __device__ __forceinline__ float2 ddc_cmul(float2 a, float2 b) {
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
-// sample n of a stream (base = its first sample) as a complex float; zero outside [0, n_samples)
-__device__ __forceinline__ float2 ddc_load(const void* __restrict__ in, int kind, size_t base, int n, int n_samples) {
-    if (n < 0 || n >= n_samples) return make_float2(0.0f, 0.0f);
-    const size_t i = base + (size_t)n;
+// sample i of an array of `kind` as a complex float
+__device__ __forceinline__ float2 ddc_fetch(const void* __restrict__ in, int kind, size_t i) {
     if (kind == FT8RX_DDC_IQ_I16) { const short2 v = ((const short2*)in)[i]; return make_float2((float)v.x, (float)v.y); }
     if (kind == FT8RX_DDC_IQ_F32) return ((const float2*)in)[i];
     if (kind == FT8RX_DDC_REAL_I16) return make_float2((float)((const int16_t*)in)[i], 0.0f);
     return make_float2(((const float*)in)[i], 0.0f);
 }
 
-template <int D>
-__global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int kind, unsigned long long stream_stride, int n_samples,
-                                                const DdcOut* __restrict__ outs, float scale, int16_t* __restrict__ audio,
-                                                float* __restrict__ audio_f32) {
+// One output tile, the body of k_ddc and of k_ddc_stream: load + mix -> LDS, stage 1 -> the v image, stage 2, i^m, scale.  The tile's
+// first output index is a multiple of 4 and its first input is n0; only n0 mod 2^32 (p0) enters the phase.  load(i) is input sample
+// n0 + i (zero where the stream has none), store(o, y) takes output o of the tile, o < DDC_TO, before rounding.
+template <int D, class Load, class Store>
+__device__ __forceinline__ void ddc_tile(uint32_t w, uint32_t p0, float scale, Load load, Store store) {
     using G = DdcGeom<D>;
     constexpr int R1 = G::R1, N1 = G::N1, R2 = G::R2, N2 = G::N2, S = G::S, BL = G::BL;
     __shared__ float sv[G::VF];
     __shared__ float2 su[R1 > 1 ? R1 * BL : 1];
     __shared__ float2 sq[DDC_QN];
     const int t = threadIdx.x;
-    // stream-major: the blocks of one output follow each other, outputs sorted by stream (outs is in that order)
-    const DdcOut o = outs[blockIdx.x / DDC_TILES];
-    const int m0 = (int)(blockIdx.x % DDC_TILES) * DDC_TO;
-    const int k0 = m0 * R2 - G::C2;                   // first v index of the tile
-    const int n0 = k0 * R1 - G::C1;                   // first input index of the tile (negative in the first tile)
-    const size_t base = (size_t)o.src * (size_t)stream_stride;
     // phase of input n0 + t + 256 e = phase(n0 + t) + phase(256 e), integers mod 2^32: one phasor per thread, one table per tile
-    const float2 P = ddc_phasor(o.w * (uint32_t)(n0 + t));
-    if (t < DDC_QN) sq[t] = ddc_phasor(o.w * (uint32_t)(DDC_NT * t));
+    const float2 P = ddc_phasor(w * (p0 + (uint32_t)t));
+    if (t < DDC_QN) sq[t] = ddc_phasor(w * (uint32_t)(DDC_NT * t));
     __syncthreads();
 
     auto store_v = [&](int i, float2 v) {
@@ -93,16 +90,16 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int
     };
     if constexpr (R1 == 1) {                          // no stage 1: the mixed input is v
         for (int i = t; i < G::NV; i += DDC_NT)
-            store_v(i, ddc_cmul(ddc_load(in, kind, base, n0 + i, n_samples), ddc_cmul(P, sq[i / DDC_NT])));
+            store_v(i, ddc_cmul(load(i), ddc_cmul(P, sq[i / DDC_NT])));
     } else {
         const float* h1 = c_ddc_h1[G::H1];
         for (int c = 0; c < G::NCH; c++) {
-            const int nb = n0 + DDC_NT * R1 * c;      // first input index under the chunk
+            const int nb = DDC_NT * R1 * c;           // first input under the chunk, from n0
             if (c) __syncthreads();                   // the previous chunk has been read
             for (int e = 0; e * DDC_NT < G::LU; e++) {
                 const int l = t + DDC_NT * e;
                 if (l < G::LU)
-                    su[(l % R1) * BL + l / R1] = ddc_cmul(ddc_load(in, kind, base, nb + l, n_samples), ddc_cmul(P, sq[e + R1 * c]));
+                    su[(l % R1) * BL + l / R1] = ddc_cmul(load(nb + l), ddc_cmul(P, sq[e + R1 * c]));
             }
             __syncthreads();
             const int i = c * DDC_NT + t;
@@ -119,8 +116,8 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int
     }
     __syncthreads();
 
-    // stage 2: outputs o = t + 256 q.  Re(i^m z) is +re, -im, -re, +im of z for m = 0, 1, 2, 3 (mod 4), and m0 is a multiple of 4:
-    // a lane needs one component only, the same for its four outputs
+    // stage 2: outputs o = t + 256 q.  Re(i^m z) is +re, -im, -re, +im of z for m = 0, 1, 2, 3 (mod 4), and the tile starts at a
+    // multiple of 4: a lane needs one component only, the same for its four outputs
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if constexpr (R2 == 2) {
         const float* h2 = c_ddc_h2[0];
@@ -149,12 +146,74 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int
     const float sg = ((t & 3) == 0 || (t & 3) == 3) ? scale : -scale;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const int oo = t + DDC_NT * q, m = m0 + oo;
-        if (oo < DDC_TO && m < FT8RX_NSAMP) {
-            const float y = sg * acc[q];
-            const size_t at = (size_t)o.out * FT8RX_NSAMP + (size_t)m;
-            if (audio_f32) audio_f32[at] = y;
-            audio[at] = (int16_t)fminf(fmaxf(rintf(y), -32768.0f), 32767.0f);
-        }
+        const int oo = t + DDC_NT * q;
+        if (oo < DDC_TO) store(oo, sg * acc[q]);
     }
+}
+__device__ __forceinline__ int16_t ddc_round(float y) { return (int16_t)fminf(fmaxf(rintf(y), -32768.0f), 32767.0f); }
+
+template <int D>
+__global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int kind, unsigned long long stream_stride, int n_samples,
+                                                const DdcOut* __restrict__ outs, float scale, int16_t* __restrict__ audio,
+                                                float* __restrict__ audio_f32) {
+    using G = DdcGeom<D>;
+    // stream-major: the blocks of one output follow each other, outputs sorted by stream (outs is in that order)
+    const DdcOut o = outs[blockIdx.x / DDC_TILES];
+    const int m0 = (int)(blockIdx.x % DDC_TILES) * DDC_TO;
+    const int k0 = m0 * G::R2 - G::C2;                // first v index of the tile
+    const int n0 = k0 * G::R1 - G::C1;                // first input index of the tile (negative in the first tile)
+    const size_t base = (size_t)o.src * (size_t)stream_stride;
+    ddc_tile<D>(o.w, (uint32_t)n0, scale,
+                [&](int i) {                          // the input is zero outside [0, n_samples)
+                    const int n = n0 + i;
+                    return n < 0 || n >= n_samples ? make_float2(0.0f, 0.0f) : ddc_fetch(in, kind, base + (size_t)n);
+                },
+                [&](int oo, float y) {
+                    const int m = m0 + oo;
+                    if (m >= FT8RX_NSAMP) return;
+                    const size_t at = (size_t)o.out * FT8RX_NSAMP + (size_t)m;
+                    if (audio_f32) audio_f32[at] = y;
+                    audio[at] = ddc_round(y);
+                });
+}
+
+// The streaming down-converter (ft8rx_ddc_stream_push): the same tile on a continuous stream.  Indices are
+// absolute and 64 bit: tile `tile` holds the outputs m = DDC_TO tile + o.  Its input comes out of the stream's ring of the newest
+// `cap` samples (a power of two; sample n at (n - n_origin) & (cap - 1)), zero before the origin n_origin (and from n_end on, which
+// no complete tile reaches); its output goes to the channel's ring at m mod ring_len.  One block per (channel, new tile).
+template <int D>
+__global__ __launch_bounds__(DDC_NT) void k_ddc_stream(const void* __restrict__ ring_in, int kind, unsigned long long cap, long long n_origin,
+                                                       long long n_end, const DdcOut* __restrict__ outs, long long tile_first, int n_tiles,
+                                                       float scale, int ring_len, int16_t* __restrict__ ring_out, float* __restrict__ ring_f32) {
+    using G = DdcGeom<D>;
+    const DdcOut o = outs[blockIdx.x / n_tiles];
+    const long long m0 = (tile_first + (long long)(blockIdx.x % n_tiles)) * DDC_TO;
+    const long long n0 = (m0 * G::R2 - G::C2) * G::R1 - G::C1;
+    const size_t base = (size_t)o.src * (size_t)cap;
+    const int r0 = (int)(m0 % ring_len);              // m0 >= 0: the origin is not negative
+    const size_t row = (size_t)o.out * (size_t)ring_len;
+    ddc_tile<D>(o.w, (uint32_t)(unsigned long long)n0, scale,
+                [&](int i) {
+                    const long long n = n0 + i;
+                    return n < n_origin || n >= n_end ? make_float2(0.0f, 0.0f)
+                                                      : ddc_fetch(ring_in, kind, base + (size_t)((unsigned long long)(n - n_origin) & (cap - 1)));
+                },
+                [&](int oo, float y) {
+                    int r = r0 + oo;
+                    if (r >= ring_len) r -= ring_len;
+                    if (ring_f32) ring_f32[row + r] = y;
+                    ring_out[row + r] = ddc_round(y);
+                });
+}
+
+// ft8rx_ddc_stream_frame: frame j position p = output m_first + p of channel j out of its ring; zero from n_have on and where the
+// stream has no output (before m_origin, from m_done on)
+__global__ __launch_bounds__(256) void k_ddc_gather(const int16_t* __restrict__ ring, int ring_len, long long m_first, int n_have,
+                                                    long long m_origin, long long m_done, int16_t* __restrict__ audio) {
+    const int p = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (p >= FT8RX_NSAMP) return;
+    const long long m = m_first + p;
+    int16_t v = 0;
+    if (p < n_have && m >= m_origin && m < m_done) v = ring[(size_t)j * ring_len + (size_t)(m % ring_len)];
+    audio[(size_t)j * FT8RX_NSAMP + p] = v;
 }

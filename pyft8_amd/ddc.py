@@ -97,6 +97,48 @@ def reference(x, kind, rate, f_dial_hz, gain=1.0):
     return y, f_mixed
 
 
+def _stream_z(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin):
+    """z[m] (complex128) of the continuous definition for the absolute outputs m_lo <= m < m_hi; x[0] is absolute input n_origin."""
+    if kind not in (REAL_I16, REAL_F32, IQ_I16, IQ_F32):
+        raise _lib.Ft8rxError(f"kind {kind} is not one of REAL_I16, REAL_F32, IQ_I16, IQ_F32")
+    D = decimation(rate)
+    if kind == REAL_I16 and D == 1:
+        raise _lib.Ft8rxError("kind real int16 at rate 12000 is a frame already")
+    if not -0.5 * rate <= f_dial_hz < 0.5 * rate:
+        raise _lib.Ft8rxError(f"f_dial_hz {f_dial_hz} outside [-rate / 2, rate / 2)")
+    m_lo, m_hi, n_origin = int(m_lo), int(m_hi), int(n_origin)
+    if m_hi <= m_lo or n_origin < 0:
+        raise _lib.Ft8rxError(f"outputs [{m_lo}, {m_hi}) / n_origin {n_origin}: need m_lo < m_hi and n_origin >= 0")
+    x = as_complex(x, kind)
+    w, _ = frequency_word(rate, f_dial_hz)
+    h1, h2 = taps(rate, 1), taps(rate, 2)
+    r2 = 1 if D == 1 else 2
+    r1 = D // r2
+    c1, c2 = (len(h1) - 1) // 2 if len(h1) else 0, (len(h2) - 1) // 2
+    pad2 = c2 // r2 + 2                                 # v is taken for k_a <= k < k_b, k_a = (m_lo - pad2) r2: stage 2 reaches c2 each way
+    k_a, k_b = (m_lo - pad2) * r2, (m_hi + pad2) * r2
+    pad1 = c1 // r1 + 2                                 # u for n_a <= n < n_b, n_a = (k_a - pad1) r1
+    n_a, n_b = (k_a - pad1) * r1, (k_b + pad1) * r1
+    u = np.zeros(n_b - n_a, np.complex128)              # the input is zero before the origin and after the last sample
+    lo, hi = max(n_a, n_origin), min(n_b, n_origin + len(x))
+    if hi > lo:
+        n = np.arange(lo, hi, dtype=np.uint64)
+        phase = ((n & np.uint64(0xFFFFFFFF)) * np.uint64(w)) & np.uint64(0xFFFFFFFF)          # exact: both factors below 2^32
+        u[lo - n_a:hi - n_a] = x[lo - n_origin:hi - n_origin] * np.exp(-2j * np.pi * (phase.astype(np.float64) / 4294967296.0))
+    v = _centred(u, h1, r1, pad1, pad1 + k_b - k_a) if len(h1) else u[pad1 * r1:pad1 * r1 + k_b - k_a]
+    return _centred(v, h2, r2, pad2, pad2 + m_hi - m_lo)
+
+
+def reference_stream(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin=0, gain=1.0):
+    """The float64 twin of the continuous definition: input of any length whose first sample x[0] has the
+    absolute index n_origin (zero before it and after its end) -> y float64 for the absolute outputs m_lo <= m < m_hi.  n_origin sets
+    the mixer phase (w n mod 2^32, exact at any n) and, through m, i^m.  Taps, frequency word and gain are reference's."""
+    z = _stream_z(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin)
+    m = np.arange(int(m_lo), int(m_hi))
+    g = 1.0 if is_iq(kind) else 2.0
+    return float(gain) * g * np.real(z * (1j ** (m % 4)))
+
+
 def iq_from_wav(path):
     """A 16-bit .wav at a supported rate -> (samples, kind, rate): mono = real int16 [n] (REAL_I16), stereo = IQ with I left and Q
     right, int16 [n, 2] (IQ_I16).  (receiver.frames_from_wav reads finished 12 kHz frames.)"""

@@ -27,6 +27,7 @@ import numpy as np
 from . import _lib
 from . import messages as _m
 from . import optins as _optins
+from . import wide_in as _wide_in
 
 T_CYC, SYM_RATE, SAMP_RATE = 15, 6.25, 12000
 WATERFALL_DOWNSAMPLE = 2
@@ -583,7 +584,7 @@ class Receiver:
     def __init__(self, input_device_keywords, on_message, sync_score_min=85, max_cands=200,
                  search_freq_range=[100, 3000], search_time_range=[-2.5 + 0.5, 2.5 + 0.5], verbose=False,
                  device=0, max_frames=1, time_source=None, sleep=None, audio_source=None, autostart=None, early_decode_hop=(320, 340),
-                 **extension_knobs):
+                 sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, **extension_knobs):
         if search_freq_range[1] > 5900 or search_freq_range[0] < 12.5 or search_freq_range[0] >= search_freq_range[1]:
             # the reference sizes its grid from search_freq_range (receiver.py:234-240) and itself fails beyond ~5940 Hz, where the
             # fine-sync slice runs off the cycle spectrum (receiver.py:181-182).  Here the layouts are compile-time: up to 3000 Hz runs
@@ -644,6 +645,12 @@ class Receiver:
         self.call_hashes = _lib.CallHashTable()       # persistent across the cycles of the stream (poll); batches use fresh ones
         self._handle(max_frames)                      # fail loudly now if there is no GPU / library
         self.audio_in = AudioIn(search_freq_range, self, input_device_keywords)
+        # wide live input (sample_rate given): the source delivers real or IQ chunks at 12 .. 192 kHz, which
+        # the streaming down-converter turns into the channels dial_offsets_hz on the live handle (wide_in.WideIn; wide_in.push(chunk)
+        # may also be called directly).  audio_in stays the 12 kHz object: its search grid and waterfall are not maintained for wide input.
+        self.wide_in = None
+        if sample_rate is not None:
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first)
         # The reference starts its audio thread and manage_cycle in the constructor (receiver.py:252, 336).  Same here when there
         # is something to listen to: an explicit audio_source, or PortAudio (PyAudio importable and a device matches the keywords).
         if autostart is None:
@@ -652,18 +659,27 @@ class Receiver:
             self.start(audio_source)
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
-    def start(self, audio_source=None):
+    def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None):
         """Open the audio source (AudioIn.open) and start the daemon that decodes completed cycles: every 0.1 s (the reference's
         poll period, receiver.py:383) it calls poll(); on_message runs on that thread, as in the reference.  Unlike the
-        reference, whose daemon dies on the first exception, an exception is kept in .thread_error and the loop ends."""
+        reference, whose daemon dies on the first exception, an exception is kept in .thread_error and the loop ends.
+        sample_rate (here or in the constructor): audio_source is an iterator of chunks of any length at that rate -- real, or IQ
+        with iq=True, the forms of decode_stream -- feeding the channels dial_offsets_hz (wide_in.WideIn.open); t_first = the time of
+        its first sample (default: time_source() at the first chunk)."""
         if self._thread is not None and self._thread.is_alive():
             return self
         self._stop.clear()
         self.thread_error = None
-        if self.audio_in._feeder is not None and not self.audio_in._feeder.is_alive():
-            self.audio_in._feeder = None
-        if audio_source is not None or self.audio_in.stream is None and self.audio_in._feeder is None:
-            self.audio_in.open(audio_source)
+        if sample_rate is not None:
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first)
+        if self.wide_in is not None:
+            if audio_source is not None:
+                self.wide_in.open(audio_source)
+        else:
+            if self.audio_in._feeder is not None and not self.audio_in._feeder.is_alive():
+                self.audio_in._feeder = None
+            if audio_source is not None or self.audio_in.stream is None and self.audio_in._feeder is None:
+                self.audio_in.open(audio_source)
 
         def manage_cycle():
             try:
@@ -682,6 +698,8 @@ class Receiver:
         if self._thread is not None and self._thread is not _threading.current_thread():
             self._thread.join(timeout)
         self.audio_in.close(timeout)
+        if self.wide_in is not None:
+            self.wide_in.close(timeout)
         self.close()
         self._raise_thread_error()
 
@@ -712,10 +730,13 @@ class Receiver:
             self._h.set_ladder_mode(1 if n_frames < 128 else 0)       # crossover measured at 64..128 frames per call (profiles/archive/r02_latency.txt)
             return self._h
 
-    def _live_handle(self):
-        """The live path's own one-frame handle (hop spectra and the per-cycle decodes of poll); call with _live_lock held."""
-        if self._live is None:
-            self._live = _lib.Handle(self.cfg, device=self.device, max_frames=1)
+    def _live_handle(self, n_frames=1):
+        """The live path's own handle (hop spectra and the per-cycle decodes of poll: one frame; wide input: one frame per channel,
+        and the down-converter's stream); call with _live_lock held."""
+        if self._live is None or self._live.max_frames < n_frames:
+            if self._live is not None:
+                self._live.close()
+            self._live = _lib.Handle(self.cfg, device=self.device, max_frames=n_frames)
             self._live.set_ladder_mode(1)
         return self._live
 
@@ -1034,6 +1055,75 @@ class Receiver:
         return self.decode_frames(np.asarray(audio_i16)[None], [cyclestart_string])[0]
 
     # ---- streaming mode (stands in for the manage_cycle thread, receiver.py:372-412)
+    def _deliver(self, row, dicts, t0, early, seen_by_cycle, hist_by_cycle, out):
+        """The tail of a live pass, for the 12 kHz path and for each channel of the wide path alike: `dicts` are the messages of the
+        pass (`row`: their MESSAGE_DTYPE rows) for the cycle that starts at t0; early = hops of the cycle received so far, 0 = the
+        complete frame.  Keeps the recall history (hist_by_cycle) and the per-cycle duplicate filter (seen_by_cycle), applies the
+        early-pass filter and hands what is left to `out` and on_message."""
+        if self.recall and not early:
+            hist_by_cycle[t0] = dicts
+            for k in [k for k in hist_by_cycle if k < t0 - 2 * T_CYC]:
+                del hist_by_cycle[k]
+        seen = seen_by_cycle.setdefault(t0, set())
+        for k in [k for k in seen_by_cycle if k < t0 - 4 * T_CYC]:
+            del seen_by_cycle[k]
+        for i, d in enumerate(dicts):
+            # early pass: only candidates whose PAYLOAD symbols (7..71) lie inside the hops received so far -- the reference's own
+            # criterion for starting on a candidate (its search_grid_bounds, receiver.py:355,389; the last Costas block only
+            # counts towards the sync gate) -- and no OSD decodes: first-CRC-valid-wins on a frame whose tail is padding
+            # produces false decodes that the complete frame does not; what OSD finds is delivered by the end-of-cycle pass
+            if early and (int(row[i]["h0_idx"]) + 4 + 4 * 72 + 4 > early or
+                          int(row[i]["method"]) in (_lib.M_OSD, _lib.M_LDPC_B_OSD)):
+                continue
+            text = " ".join(d["msg_tuple"])
+            if text in seen:                                       # the reference's per-cycle duplicate filter (receiver.py:52-54)
+                continue
+            seen.add(text)
+            d["early"] = bool(early)
+            out.append(d)
+            if self.on_message is not None:
+                self.on_message(d)
+
+    def _poll_wide(self, out):
+        """The passes of the wide input that have fallen due (wide_in.PassScheduler): gather the K channels' frames out of the
+        down-converter's rings, decode them as one batch on the live handle, deliver per channel.  Every dict carries "channel": j;
+        band = bands[j]; fHz stays the audio frequency inside the channel.  The channels share the persistent call-hash table and are
+        replayed into it in ascending order (package_batch(table=))."""
+        w = self.wide_in
+        K = w.n_channels
+        while True:
+            with w._lock:
+                if not w._ready:
+                    break
+                c, hop, m_first, n_have = w._ready.pop(0)
+            t0 = T_CYC * c
+            cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
+            # recall: only the complete-frame pass, per channel the complete-frame messages of the same channel 30 s earlier
+            prev = [w.recall_hist[j].get(t0 - 2 * T_CYC) for j in range(K)] if self.recall and not hop else None
+            if prev is not None and all(p is None for p in prev):
+                prev = None
+            with self._live_lock:
+                h = self._live_handle(K)
+                if prev is not None:
+                    h.set_recall(self._recall_entries(prev))
+                h.ddc_stream_frame(m_first, n_have)
+                h.enqueue(h.staging_ptr(), K)
+                rec, cnt, ev, evc = h.fetch(K)
+                if prev is not None:
+                    rrec, rcnt = h.fetch_recall(K)
+                rp = h.fetch_reports(K) if self.reports else None
+            if prev is not None:
+                msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, n_threads=1, table=self.call_hashes)
+            else:
+                msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
+            for j in range(K):
+                dicts = _m.message_dicts(msgs[j], mcnt[j], cyclestart_string=cs, band=w.bands[j] if w.bands is not None else self.band,
+                                         odd_even=int((t0 % (2 * T_CYC)) / T_CYC), ap=self._ap_on(), recall=self.recall,
+                                         reports=None if rp is None else rp[j])
+                for d in dicts:
+                    d["channel"] = j
+                self._deliver(msgs[j], dicts, t0, hop, w.seen[j], w.recall_hist[j], out)
+
     def poll(self):
         """Decode every cycle that audio_in._callback has completed since the last call; messages go to on_message
         on the caller's thread.  -> list of message dicts.  Receiver.start() runs this on a daemon thread (the stand-in for
@@ -1068,29 +1158,9 @@ class Receiver:
                 msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
             dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
                                      ap=self._ap_on(), recall=self.recall, reports=None if rp is None else rp[0])
-            if self.recall and not early:
-                self._recall_hist[t0] = dicts
-                for k in [k for k in self._recall_hist if k < t0 - 2 * T_CYC]:
-                    del self._recall_hist[k]
-            seen = self._cycle_seen.setdefault(t0, set())
-            for k in [k for k in self._cycle_seen if k < t0 - 4 * T_CYC]:
-                del self._cycle_seen[k]
-            for i, d in enumerate(dicts):
-                # early pass: only candidates whose PAYLOAD symbols (7..71) lie inside the hops received so far -- the reference's own
-                # criterion for starting on a candidate (its search_grid_bounds, receiver.py:355,389; the last Costas block only
-                # counts towards the sync gate) -- and no OSD decodes: first-CRC-valid-wins on a frame whose tail is padding
-                # produces false decodes that the complete frame does not; what OSD finds is delivered by the end-of-cycle pass
-                if early and (int(msgs[0, i]["h0_idx"]) + 4 + 4 * 72 + 4 > early or
-                              int(msgs[0, i]["method"]) in (_lib.M_OSD, _lib.M_LDPC_B_OSD)):
-                    continue
-                text = " ".join(d["msg_tuple"])
-                if text in seen:                                       # the reference's per-cycle duplicate filter (receiver.py:52-54)
-                    continue
-                seen.add(text)
-                d["early"] = bool(early)
-                out.append(d)
-                if self.on_message is not None:
-                    self.on_message(d)
+            self._deliver(msgs[0], dicts, t0, early, self._cycle_seen, self._recall_hist, out)
+        if self.wide_in is not None:
+            self._poll_wide(out)
         return out
 
 

@@ -1,0 +1,195 @@
+"""Live input wider than a 12 kHz frame: real or IQ samples at 12 .. 192 kHz, in chunks of any length, feed K
+channels of one receiver through the streaming down-converter (ft8rx_ddc_stream_*).  WideIn is the sibling of receiver.AudioIn: its
+push(chunk) is what AudioIn._callback is for 12 kHz hops; Receiver.poll() runs the passes it has found due.
+
+Time is the sample clock: the first sample is t_first, absolute 12 kHz output m is t_first + m / 12000, cycle c starts at output
+m_c = round((15 c - t_first) 12000).  Drift of the source's clock against wall time is not corrected.  PassScheduler and produced()
+are pure Python (tests/test_ddc_stream.py runs them without a GPU)."""
+import threading as _threading
+
+import numpy as np
+
+from . import _lib
+from . import ddc as _ddc
+
+NSAMP = _lib.NSAMP
+HOP = 480                     # 12 kHz samples per hop of early_decode_hops
+TILE = 1008                   # outputs per tile of the down-converter (csrc/kernels/ddc.hpp: DDC_TO)
+T_CYC = 15
+HEAD_MAX = 6000               # a cycle is decoded if at most this many of its first outputs lie before the stream (0.5 s, taken as zero)
+
+
+def _last_input(D):
+    """Offset of the last input a tile needs from the input of its first output (csrc/ddc_ring.hpp: last)"""
+    r2 = 1 if D == 1 else 2
+    r1 = D // r2
+    c1 = {4: 8, 8: 15, 16: 30}.get(D, 0)
+    c2 = 71 if D == 1 else 141
+    return ((TILE - 1) * r2 + c2) * r1 + c1
+
+
+def produced(n_pushed, D):
+    """Outputs that exist after n_pushed samples of a stream that began at index 0: whole tiles whose last input has arrived
+    (csrc/ddc_ring.hpp: tiles_done).  An output exists at most one tile (84 ms) + the filters' reach (about 6 ms) after its sample."""
+    have = int(n_pushed) - 1 - _last_input(D)
+    return 0 if have < 0 else (have // (TILE * D) + 1) * TILE
+
+
+class PassScheduler:
+    """Which decode passes are due, from the sample clock alone.  A pass is (cycle c, hop, m_first, n_have): hop = the hops of the
+    cycle received (an early pass; n_have = 480 hop) or 0 (the complete cycle, n_have = 180000); m_first = m_c, the cycle's first
+    output, which may be negative by up to 6000 for the first cycle (those outputs are zero).  Passes come in the order they fall
+    due: the early hops of a cycle ascending, then the cycle itself, then the next cycle."""
+
+    def __init__(self, t_first, early_hops=()):
+        self.t_first = float(t_first)
+        self.hops = tuple(sorted(int(x) for x in early_hops))
+        c = int(np.floor(self.t_first / T_CYC))
+        while self.cycle_start(c) < -HEAD_MAX:
+            c += 1
+        self.cycle, self.step = c, 0                    # the next pass: hop self.hops[step], or the complete cycle at step == len(hops)
+
+    def cycle_start(self, c):
+        """m_c: the absolute output index at which cycle c (t = 15 c) starts"""
+        return int(round((T_CYC * c - self.t_first) * 12000.0))
+
+    def due(self, m_produced):
+        """The passes whose outputs all exist now (m_first + n_have <= m_produced), each handed out once"""
+        out = []
+        while True:
+            m_c = self.cycle_start(self.cycle)
+            hop = self.hops[self.step] if self.step < len(self.hops) else 0
+            n_have = HOP * hop if hop else NSAMP
+            if m_c + n_have > m_produced:
+                return out
+            out.append((self.cycle, hop, m_c, n_have))
+            self.step += 1
+            if not hop:
+                self.cycle, self.step = self.cycle + 1, 0
+
+
+class WideIn:
+    """The wide live input of one Receiver: K = len(dial_offsets_hz) channels out of the source's streams.
+
+    push(chunk) takes the next samples in the forms of Receiver.decode_stream -- real int16 or float [n], complex [n] or int16 (I, Q)
+    pairs [n, 2] with iq=True, several streams as [n_streams, n(, 2)] -- of any length, hands them to the down-converter on the
+    receiver's live handle (created with max_frames = K) and notes the passes that have fallen due; Receiver.poll() gathers and decodes
+    them.  The samples never come back to the host.  open(source) feeds push from an iterator of chunks on a daemon thread; at the
+    end of a finite source it pushes zeros until the outputs of the last real sample exist, notes the passes then due and sets
+    source_exhausted."""
+
+    def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None):
+        self._rx = receiver
+        self.sample_rate = int(sample_rate)
+        self.D = _ddc.decimation(self.sample_rate)
+        self.iq = bool(iq)
+        self.dials = [float(f) for f in dial_offsets_hz]
+        self.n_channels = len(self.dials)
+        if self.n_channels < 1:
+            raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
+        if bands is not None and len(bands) != self.n_channels:
+            raise _lib.Ft8rxError(f"bands: one per channel ({self.n_channels}), got {len(bands)}")
+        if src is not None and len(src) != self.n_channels:
+            raise _lib.Ft8rxError(f"src: one stream index per channel ({self.n_channels}), got {len(src)}")
+        self.bands = list(bands) if bands is not None else None
+        self.src = None if src is None else [int(s) for s in src]
+        self.t_first = t_first
+        self.kind = None
+        self.n_streams = None
+        self.f_mixed_hz = None
+        self.sched = None
+        self.n_pushed = 0                        # real samples per stream
+        self.m_produced = 0
+        self.source_exhausted = False
+        self._ready = []                         # passes that are due and not yet decoded: (cycle, hop, m_first, n_have)
+        self._lock = _threading.Lock()           # push may run on the feeder thread, poll() on the manage_cycle stand-in
+        self._feeder = None
+        # per channel: the texts delivered per cycle (duplicate filter) and the complete-frame messages per cycle (recall)
+        self.seen = [{} for _ in range(self.n_channels)]
+        self.recall_hist = [{} for _ in range(self.n_channels)]
+
+    def _start(self, chunk):
+        """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
+        a = np.asarray(chunk)
+        cplx = np.iscomplexobj(a)
+        if cplx and not self.iq:
+            raise _lib.Ft8rxError("samples are complex: pass iq=True")
+        if self.iq:
+            self.kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
+        else:
+            self.kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
+        _, self.n_streams, _ = _ddc.pack(a, self.kind)
+        if self.src is None:
+            if self.n_streams != 1 and self.n_streams != self.n_channels:
+                raise _lib.Ft8rxError(f"src: {self.n_streams} streams and {self.n_channels} channels -- say which stream each channel reads")
+            self.src = [0] * self.n_channels if self.n_streams == 1 else list(range(self.n_channels))
+        if self.t_first is None:
+            self.t_first = self._rx.time_source()
+        self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
+        with self._rx._live_lock:
+            h = self._rx._live_handle(self.n_channels)
+            self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+
+    def _push(self, a, real):
+        """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples"""
+        with self._rx._live_lock:
+            self.m_produced = self._rx._live_handle(self.n_channels).ddc_stream_push(a)
+        if real:
+            self.n_pushed += a.shape[1]
+
+    def _note(self, m_avail):
+        due = self.sched.due(m_avail)
+        if due:
+            with self._lock:
+                self._ready += due
+
+    def push(self, chunk):
+        """The next samples of the source, any length (a longer chunk is handed on a second at a time)"""
+        if self.sched is None:
+            self._start(chunk)
+        a, n_streams, n = _ddc.pack(chunk, self.kind)
+        if n_streams != self.n_streams:
+            raise _lib.Ft8rxError(f"push: {n_streams} streams, the source began with {self.n_streams}")
+        for at in range(0, n, self.sample_rate):
+            self._push(a[:, at:at + self.sample_rate], True)
+            self._note(self.m_produced)
+
+    def flush(self):
+        """End of a finite source: zeros until the outputs of the last real sample exist; the passes those outputs complete"""
+        if self.sched is None:
+            return
+        m_real = -(-self.n_pushed // self.D)
+        shape = (self.n_streams, TILE * self.D) + ((2,) if _ddc.is_iq(self.kind) else ())
+        zeros = np.zeros(shape, np.int16 if self.kind in (_ddc.REAL_I16, _ddc.IQ_I16) else np.float32)
+        while self.m_produced < m_real:
+            self._push(zeros, False)
+        self._note(m_real)
+
+    def open(self, source):
+        """Feed push() from an iterator of chunks on a daemon thread.  Pacing is the iterator's business (a live source blocks until
+        its next chunk exists; a test advances its virtual clock inside the generator)."""
+        def feed():
+            try:
+                for chunk in source:
+                    if self._rx._stop.is_set():
+                        break
+                    self.push(chunk)
+                else:
+                    self.flush()
+                    self.source_exhausted = True
+            except Exception as e:          # noqa: BLE001 -- surfaced by Receiver.poll()/stop() instead of dying silently on a daemon thread
+                self._rx.thread_error = e
+            finally:
+                self._feeder = None
+        self.source_exhausted = False
+        t = self._feeder = _threading.Thread(target=feed, name="ft8rx-wide-in", daemon=True)
+        t.start()
+        return self
+
+    def close(self, timeout=5.0):
+        """Wait for the feeder thread (it ends at its next chunk once the receiver's stop flag is set)."""
+        t = self._feeder
+        if t is not None and t is not _threading.current_thread():
+            t.join(timeout)
+            if not t.is_alive():
+                self._feeder = None
