@@ -45,6 +45,9 @@
  *     ft8rx_ddc  ft8rx_ddc_host  ft8rx_ddc_taps                                        (down-converter: real / IQ input at 24 .. 192 kHz -> 12 kHz frames)
  *     ft8rx_ddc_stream_open  ft8rx_ddc_stream_push  ft8rx_ddc_stream_frame  ft8rx_ddc_stream_info  ft8rx_ddc_stream_read
  *     ft8rx_ddc_stream_close                                                           (the same on a continuous stream, state on the device)
+ *     ft8rx_ddc_wide  ft8rx_ddc_wide_host  ft8rx_ddc_wide_taps  ft8rx_ddc_wide_plan     (pre-decimator: ONE stream at 240 kHz .. 129.6 MHz, 8- or
+ *     ft8rx_ddc_wide_stream_open  ft8rx_ddc_wide_stream_push  ft8rx_ddc_wide_stream_read_mid   16-bit, in front of the down-converter)
+ *     ft8rx_ddc_wide_stream_close
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
@@ -484,6 +487,59 @@ int  ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16
 int  ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first, int n, int16_t* y_i16, float* y_f32);
 int  ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced);
 int  ft8rx_ddc_stream_close(ft8rx_handle* h);
+/* Wide pre-decimator (extension): ONE stream at rate_hz, a multiple of 48000 in [240000, 129600000] -- RTL-SDR
+ * and HackRF (8-bit IQ), Airspy HF+ (IQ int16 at 384 / 768 kHz), direct-sampling receivers (real int16 at 64.8 / 129.6 MS/s) -- in front
+ * of the down-converter above, which is used unchanged behind it.  rate_mid = the largest of 192000, 96000, 48000 that divides rate_hz
+ * with R0 = rate_hz / rate_mid >= 2; R0 <= 1350 (ft8rx_ddc_wide_plan; anything else is refused, naming rate_hz).  Per channel j:
+ *   mixer    w0 = round((f_dial + 3000) / rate 2^32) mod 2^32, f0 = w0 rate / 2^32 in [-rate/2, rate/2),
+ *            u[n] = x[n] e^{-2 pi i (w0 n mod 2^32) / 2^32}: the wanted audio lands at the centre of the intermediate stream;
+ *   filter   v[k] = g0 sum_j h0[j] u[k R0 + j - C0], h0 = the Kaiser recipe of section 16 at fs = rate_hz, pass 3200 Hz, stop
+ *            rate_mid - 3200 Hz, 85 dB (ft8rx_ddc_wide_taps; 33 taps at 240 kHz, 145 at 2.4 MHz, 3883 at 64.8 MHz), g0 = 2 for the
+ *            real kind and 1 for IQ;
+ *   then     v, an IQ float32 stream at rate_mid, goes through the definition above (ft8rx_ddc / ft8rx_ddc_stream_*) with the dial
+ *            f_dial - f0 (about -3000 Hz) and `gain`; f_mixed_hz = f0 + what that stage really mixed.
+ * The passband and stopband promise of ft8rx_ddc holds for the whole chain (images of rate_mid at least 83 dB down).  Sample values:
+ * the 16-bit kinds as they are; IQ uint8 x = 256 (u - 127.5), IQ int8 x = 256 s per component, so full scale and gain mean the same
+ * for every kind.  Refusals return -1 with a text that names the argument. */
+#define FT8RX_WIDE_REAL_I16 16
+#define FT8RX_WIDE_IQ_I16   17         /* I, Q interleaved, as the two 8-bit kinds */
+#define FT8RX_WIDE_IQ_U8    18
+#define FT8RX_WIDE_IQ_I8    19
+/* host only, no GPU: the plan of a rate -> 0 and rate_mid_hz / r0 (either may be NULL), or -1 for a rate that is refused */
+int  ft8rx_ddc_wide_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* r0);
+/* host only, no GPU: h0 of a rate -> its length and the first min(length, cap) taps (float32; taps may be NULL); -1 for a refused rate */
+int  ft8rx_ddc_wide_taps(int32_t rate_hz, float* taps, int cap);
+/* One call = one cycle: d_in = n_samples <= 15 rate_hz samples of `kind` on the device (aligned to a sample; zero before sample 0 and
+ * after the last) -> n_out (<= max_frames) frames, channel j with the dial f_dial_hz[j] Hz from the stream's centre (the real kind: the
+ * absolute frequency), in [-rate/2, rate/2).  The pre-stage writes [n_out][n_mid] intermediate samples into a handle-owned buffer
+ * (allocated on first use, grown when a call needs more, as the tap tables of the channels), then ft8rx_ddc's kernel runs on it with
+ * one stream per output.  d_audio, d_audio_f32, f_mixed_hz: as ft8rx_ddc.  Waits for the batches in flight and for the handle's main
+ * stream (the tables are uploaded synchronously); the kernels are queued on that stream.  Refused while a wide stream is open. */
+int  ft8rx_ddc_wide(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                    const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz);
+/* the same from host memory, staged through the handle's input buffer of ft8rx_ddc_host; result in the staging audio buffer; returns
+ * when the frames are there */
+int  ft8rx_ddc_wide_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                         const double* f_dial_hz, float gain, double* f_mixed_hz);
+/* The same on a continuous stream, one per handle.  Indices are absolute as in ft8rx_ddc_stream_*: input n, intermediate k = n / R0,
+ * output m = n / (rate_hz / 12000); only n mod 2^32 enters the mixer phase (at 64.8 MS/s n passes 2^32 every 66 s).  State, allocated
+ * by open and released by close or ft8rx_destroy, nothing in between: the last len(h0) - 1 + R0 input samples in their own kind, one
+ * second of input (device and page-locked), one second of intermediate samples, the channels' tables, and the streaming
+ * down-converter behind it (n_out IQ float32 streams at rate_mid), which open opens, push feeds on the device and close closes.
+ * open      n_origin: absolute index of the first sample, a multiple of 1008 rate_hz / 12000; keep_f32 as ft8rx_ddc_stream_open.  Refused
+ *           while a wide or a plain stream is open; while it is open ft8rx_ddc_stream_open / _push / _close and ft8rx_ddc_wide are refused.
+ * push      n_new = 1 .. rate_hz samples, host memory or (on_device != 0) device memory: ONE kernel makes every intermediate sample
+ *           whose last input has arrived (none, if the push completes none), at most two copies update the history, then the push
+ *           of the stage behind.  Every sample is the same bits however the stream was cut into chunks, and with n_origin = 0 the
+ *           first cycle is ft8rx_ddc_wide's bit for bit.  m_produced as ft8rx_ddc_stream_push.  Asynchronous on the main stream.
+ * then      ft8rx_ddc_stream_frame / _read / _info work as on a plain stream (info counts intermediate samples).
+ * read_mid  test aid: intermediate samples [k_first, k_first + n) of every channel -> host mid [n_out][n][2] float32 (re, im);
+ *           held are the newest in_capacity (ft8rx_ddc_stream_info) samples; synchronous. */
+int  ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain,
+                                uint64_t n_origin, int keep_f32, double* f_mixed_hz);
+int  ft8rx_ddc_wide_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
+int  ft8rx_ddc_wide_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid);
+int  ft8rx_ddc_wide_stream_close(ft8rx_handle* h);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -77,6 +77,14 @@ PROTOTYPES = {
     "ft8rx_ddc_stream_read": (INT, (PTR, U64, INT, PTR, PTR)),
     "ft8rx_ddc_stream_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
     "ft8rx_ddc_stream_close": (INT, (PTR,)),
+    "ft8rx_ddc_wide_plan": (INT, (I32, PTR, PTR)),
+    "ft8rx_ddc_wide_taps": (INT, (I32, PTR, INT)),
+    "ft8rx_ddc_wide": (INT, (PTR, PTR, INT, I32, U64, INT, PTR, F32, PTR, PTR, PTR)),
+    "ft8rx_ddc_wide_host": (INT, (PTR, PTR, INT, I32, U64, INT, PTR, F32, PTR)),
+    "ft8rx_ddc_wide_stream_open": (INT, (PTR, INT, I32, INT, PTR, F32, U64, INT, PTR)),
+    "ft8rx_ddc_wide_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
+    "ft8rx_ddc_wide_stream_read_mid": (INT, (PTR, U64, INT, PTR)),
+    "ft8rx_ddc_wide_stream_close": (INT, (PTR,)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

@@ -35,6 +35,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <map>
 #include <new>
 #include <string>
 #include <vector>
@@ -58,12 +59,14 @@
 #include "kernels/recall.hpp"
 #include "kernels/report.hpp"
 #include "kernels/ddc.hpp"
+#include "kernels/ddc_wide.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
 #include "ddc_ring.hpp"
+#include "ddc_wide_ring.hpp"
 #include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
@@ -209,6 +212,21 @@ struct ft8rx_handle {
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
         hipEvent_t ev = nullptr;
     } ds;
+    // wide pre-decimator (ft8rx_ddc_wide*, kernels/ddc_wide.hpp).  One-shot: the channels' tap tables
+    // [n_out][n_taps] and frequency words, and the intermediate samples [n_out][n_mid], each grown when a call needs more.
+    void* d_wide_tab = nullptr; size_t wide_tab_cap = 0; void* d_wide_w0 = nullptr; size_t wide_w0_cap = 0;
+    void* d_wide_mid = nullptr; size_t wide_mid_cap = 0;
+    // ... and its stream: everything is allocated by open and released by close (or destroy).  d_hist: the newest H input samples in
+    // their own kind (sample n at (n - n_origin) mod H); d_chunk / h_stage: one second of input, device / page-locked; d_mid:
+    // [n_out][rate_mid], what one push makes; the down-converter behind it is the stream `ds` above, fed on the device.
+    // n_origin, pushed, k_done: absolute index of the first sample, samples pushed, first intermediate sample not made yet.
+    struct WideStream {
+        bool open = false; int kind = 0, n_out = 0, n_taps = 0, R0 = 0, H = 0; int32_t rate = 0, rate_mid = 0; float g0 = 0.0f;
+        int64_t n_origin = 0, pushed = 0, k_done = 0;
+        char* d_hist = nullptr; char* d_chunk = nullptr; char* h_stage = nullptr; float2* d_mid = nullptr; float2* d_tab = nullptr;
+        uint32_t* d_w0 = nullptr;
+        hipEvent_t ev = nullptr;
+    } wds;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -456,6 +474,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
     if (h->ds.ev) hipEventDestroy(h->ds.ev);
+    if (h->wds.ev) hipEventDestroy(h->wds.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -1465,9 +1484,19 @@ static void ddc_stream_release(ft8rx_handle* h) {
     s.ev = ev;
 }
 
+// (the bodies of open and push: the wide stream, DESIGN.md section 16.2, opens and feeds the stream behind it through them)
+static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
+                           float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz);
+static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
+
 int ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
                           float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
     if (!h) return -1;
+    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_open: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)"); return -1; }
+    return ddc_stream_open(h, kind, rate_hz, n_streams, n_out, src, f_dial_hz, gain, n_origin, keep_f32, f_mixed_hz);
+}
+static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
+                           float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
     if (h->ds.open) { set_err(h, "ft8rx_ddc_stream_open: a stream is open on this handle already (ft8rx_ddc_stream_close)"); return -1; }
     const int D = ddc_check(h, "ft8rx_ddc_stream_open", kind, rate_hz, n_streams, 0, 0, n_out, src, f_dial_hz, gain);
     if (D < 0) return -1;
@@ -1503,6 +1532,10 @@ int ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_stre
 
 int ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
     if (!h) return -1;
+    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_push: the open stream is a wide stream (ft8rx_ddc_wide_stream_push)"); return -1; }
+    return ddc_stream_push(h, in, n_new, on_device, m_produced);
+}
+static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
     ft8rx_handle::DdcStream& s = h->ds;
     if (!s.open) { set_err(h, "ft8rx_ddc_stream_push: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
     if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
@@ -1603,9 +1636,315 @@ int ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_
 
 int ft8rx_ddc_stream_close(ft8rx_handle* h) {
     if (!h) return -1;
+    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_close: the open stream is a wide stream (ft8rx_ddc_wide_stream_close)"); return -1; }
     if (!h->ds.open) { set_err(h, "ft8rx_ddc_stream_close: no stream is open"); return -1; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the rings
+    ddc_stream_release(h);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- wide pre-decimator
+// The kernel's tile and the limits, against the pure index arithmetic of ddc_wide_ring.hpp
+static_assert(ddcwide::PIECE == DDW_JP && ddcwide::LDS_SAMPLES == DDW_LS && ddcwide::TILE_MAX == DDW_TK && DDW_JP % 64 == 0 && DDW_TK == 4 * (DDW_NT / 64),
+              "ddc_wide_ring.hpp: the tile of kernels/ddc_wide.hpp");
+constexpr bool ddw_tiles_fit() {
+    for (int64_t r = 2; r <= ddcwide::MAX_R0; r++)
+        if (ddcwide::tile_outputs(r) < 1 || (ddcwide::tile_outputs(r) - 1) * r + DDW_JP > DDW_LS) return false;
+    return true;
+}
+static_assert(ddw_tiles_fit(), "ddc_wide_ring.hpp: a tile's input under one piece of taps fits the LDS image");
+static_assert(ddcwide::plan(240000).rate_mid == 48000 && ddcwide::plan(240000).R0 == 5 && ddcwide::plan(64800000).rate_mid == 96000 &&
+              ddcwide::plan(129600000).R0 == 675 && ddcwide::plan(192000).rate_mid == 0 && ddcwide::plan(129648000).rate_mid == 0, "ddc_wide_ring.hpp: plan");
+static_assert(sizeof(float2) * DDW_LS <= 64 * 1024, "the LDS image is static shared memory");
+
+static const size_t DDW_SAMPLE_BYTES[4] = {2, 4, 2, 2};     // FT8RX_WIDE_REAL_I16, _IQ_I16, _IQ_U8, _IQ_I8
+static bool ddw_is_iq(int kind) { return kind != FT8RX_WIDE_REAL_I16; }
+
+// h0 of a rate: the recipe of ddc_design at fs = rate, pass 3200 Hz, stop rate_mid - 3200 Hz, 85 dB; designed once per rate
+static const std::vector<float>* ddw_taps(int32_t rate_hz) {
+    const ddcwide::Plan p = ddcwide::plan(rate_hz);
+    if (!p.rate_mid) return nullptr;
+    static std::mutex mu;
+    static std::map<int32_t, std::vector<float>> designed;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = designed.find(rate_hz);
+    if (it == designed.end()) it = designed.emplace(rate_hz, ddc_design(3200.0, (double)p.rate_mid - 3200.0, 85.0, (double)rate_hz)).first;
+    return (int64_t)it->second.size() <= ddcwide::MAX_TAPS ? &it->second : nullptr;
+}
+
+int ft8rx_ddc_wide_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* r0) {
+    const ddcwide::Plan p = ddcwide::plan(rate_hz);
+    if (!p.rate_mid) return -1;
+    if (rate_mid_hz) *rate_mid_hz = (int32_t)p.rate_mid;
+    if (r0) *r0 = (int32_t)p.R0;
+    return 0;
+}
+
+int ft8rx_ddc_wide_taps(int32_t rate_hz, float* taps, int cap) {
+    const std::vector<float>* t = ddw_taps(rate_hz);
+    if (!t) return -1;
+    for (int i = 0; taps && i < cap && i < (int)t->size(); i++) taps[i] = (*t)[i];
+    return (int)t->size();
+}
+
+// the argument checks every entry shares -> the plan's rate_mid, or -1 with the error text
+static int ddw_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
+    if (kind < FT8RX_WIDE_REAL_I16 || kind > FT8RX_WIDE_IQ_I8) { set_err(h, "%s: kind %d is not one of FT8RX_WIDE_REAL_I16 .. FT8RX_WIDE_IQ_I8", who, kind); return -1; }
+    if (!ddcwide::plan(rate_hz).rate_mid || !ddw_taps(rate_hz)) {
+        set_err(h, "%s: rate_hz %d is not a multiple of 48000 in [240000, 129600000] with rate_hz / rate_mid <= 1350", who, (int)rate_hz); return -1;
+    }
+    if (n_out < 1 || n_out > h->max_frames || n_out > 65535) { set_err(h, "%s: n_out %d outside [1, %d] (max_frames; at most 65535)", who, n_out, h->max_frames); return -1; }
+    if (!f_dial_hz) { set_err(h, "%s: f_dial_hz is NULL", who); return -1; }
+    for (int j = 0; j < n_out; j++)
+        if (!(f_dial_hz[j] >= -0.5 * rate_hz && f_dial_hz[j] < 0.5 * rate_hz)) { set_err(h, "%s: f_dial_hz[%d] = %g outside [-rate_hz / 2, rate_hz / 2)", who, j, f_dial_hz[j]); return -1; }
+    if (!(fabsf(gain) <= 3.0e38f)) { set_err(h, "%s: gain is not finite", who); return -1; }
+    return (int)ddcwide::plan(rate_hz).rate_mid;
+}
+
+// per channel: the frequency word w0, the table W[j] = h0[j] e^{-2 pi i (w0 j mod 2^32) / 2^32} (double, rounded once), the dial left for
+// the stage behind (f_dial - f0, about -3000 Hz) and f0 itself, both taken into [-rate / 2, rate / 2)
+static void ddw_tables(int32_t rate_hz, const std::vector<float>& h0, int n_out, const double* f_dial_hz, std::vector<float2>& tab, std::vector<uint32_t>& w0s,
+                       std::vector<double>& dial_mid, std::vector<double>& f0s) {
+    const size_t N = h0.size();
+    tab.resize((size_t)n_out * N); w0s.resize((size_t)n_out); dial_mid.resize((size_t)n_out); f0s.resize((size_t)n_out);
+    for (int c = 0; c < n_out; c++) {
+        const double r = nearbyint((f_dial_hz[c] + 3000.0) / (double)rate_hz * 4294967296.0);
+        const uint32_t w0 = (uint32_t)((long long)r & 0xffffffffLL);
+        double f0 = (double)w0 * (double)rate_hz / 4294967296.0;
+        if (f0 >= 0.5 * rate_hz) f0 -= (double)rate_hz;
+        double d = f_dial_hz[c] - f0;
+        d -= (double)rate_hz * nearbyint(d / (double)rate_hz);
+        w0s[c] = w0; f0s[c] = f0; dial_mid[c] = d;
+        for (size_t j = 0; j < N; j++) {
+            const double a = -(double)(uint32_t)(w0 * (uint32_t)j) * (M_PI / 2147483648.0);
+            tab[(size_t)c * N + j] = make_float2((float)((double)h0[j] * cos(a)), (float)((double)h0[j] * sin(a)));
+        }
+    }
+}
+// what the caller sees as mixed: f0 + the dial the stage behind really mixed, in [-rate / 2, rate / 2)
+static void ddw_mixed(int32_t rate_hz, int n_out, const std::vector<double>& f0s, double* f_mixed_hz) {
+    for (int c = 0; f_mixed_hz && c < n_out; c++) {
+        double f = f0s[c] + f_mixed_hz[c];
+        if (f >= 0.5 * rate_hz) f -= (double)rate_hz;
+        if (f < -0.5 * rate_hz) f += (double)rate_hz;
+        f_mixed_hz[c] = f;
+    }
+}
+
+// a handle-owned device buffer that only grows: first use, or a larger call (nothing of the handle reads the old one any more)
+static int ddw_reserve(ft8rx_handle* h, const char* who, void** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes && *p) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes ? bytes : 256);
+    if (e != hipSuccess) { set_err(h, "%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e)); return -2; }
+    if (*p) {
+        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == *p) { h->allocs.erase(h->allocs.begin() + i); break; }
+        hipFree(*p);
+    }
+    h->allocs.push_back(q); *p = q; *cap = bytes ? bytes : 256;
+    return 0;
+}
+
+// the one-shot behind its checks: pre-stage into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
+static int ddw_run(ft8rx_handle* h, const char* who, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz,
+                   float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    const ddcwide::Plan p = ddcwide::plan(rate_hz);
+    const std::vector<float>& h0 = *ddw_taps(rate_hz);
+    const int D = (int)(p.rate_mid / 12000), n_taps = (int)h0.size(), tk = (int)ddcwide::tile_outputs(p.R0);
+    const int64_t n_mid = ddcwide::mid_count((int64_t)n_samples, n_taps, p.R0, (int64_t)FT8RX_NSAMP * D);
+    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s, fm((size_t)n_out);
+    ddw_tables(rate_hz, h0, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
+    if (ddw_reserve(h, who, &h->d_wide_tab, &h->wide_tab_cap, sizeof(float2) * tab.size()) ||
+        ddw_reserve(h, who, &h->d_wide_w0, &h->wide_w0_cap, sizeof(uint32_t) * w0s.size()) ||
+        ddw_reserve(h, who, &h->d_wide_mid, &h->wide_mid_cap, sizeof(float2) * (size_t)n_out * (size_t)n_mid)) return -2;
+    // the tables are pageable vectors of this call, and an earlier call's kernel may still read the device copies
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_wide_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_wide_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((n_mid + tk - 1) / tk), (unsigned)n_out);
+    const float g0 = ddw_is_iq(kind) ? 1.0f : 2.0f;
+    if (ddw_is_iq(kind))
+        k_ddc_pre<true><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, (const uint32_t*)h->d_wide_w0, n_taps,
+                                                        (int)p.R0, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid);
+    else
+        k_ddc_pre<false><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, (const uint32_t*)h->d_wide_w0, n_taps,
+                                                         (int)p.R0, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid);
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> src((size_t)n_out);
+    for (int j = 0; j < n_out; j++) src[j] = j;
+    if (const int rc = ddc_launch(h, D, h->d_wide_mid, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), dial_mid.data(),
+                                  gain, d_audio, d_audio_f32, fm.data())) return rc;
+    if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz); }
+    return 0;
+}
+
+static int ddw_check_oneshot(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain) {
+    if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+    if (n_samples > (uint64_t)15 * (uint64_t)rate_hz) { set_err(h, "%s: n_samples %llu > %llu (15 s at rate_hz)", who, (unsigned long long)n_samples, 15ull * (unsigned long long)rate_hz); return -1; }
+    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    return 0;
+}
+
+int ft8rx_ddc_wide(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                   int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    if (ddw_check_oneshot(h, "ft8rx_ddc_wide", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!d_in || ((uintptr_t)d_in % DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16]) != 0) { set_err(h, "ft8rx_ddc_wide: d_in is NULL or not aligned to a sample"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h)) return -2;
+    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    return ddw_run(h, "ft8rx_ddc_wide", d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+}
+
+int ft8rx_ddc_wide_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                        double* f_mixed_hz) {
+    if (!h) return -1;
+    if (ddw_check_oneshot(h, "ft8rx_ddc_wide_host", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!in) { set_err(h, "ft8rx_ddc_wide_host: in is NULL"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h) || need_staging(h)) return -2;
+    const size_t bytes = (size_t)n_samples * DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16];
+    if (ddw_reserve(h, "ft8rx_ddc_wide_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
+    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = ddw_run(h, "ft8rx_ddc_wide_host", h->d_ddc_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- the wide stream: the pre-stage on a continuous stream, in front of the streaming down-converter (section 16.1), which it opens,
+// feeds on the device and closes.  The index arithmetic is ddc_wide_ring.hpp's.
+static void ddw_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::WideStream& s = h->wds;
+    release_dev(h, s.d_hist); release_dev(h, s.d_chunk); release_dev(h, s.d_mid); release_dev(h, s.d_tab); release_dev(h, s.d_w0); release_host(h, s.h_stage);
+    const hipEvent_t ev = s.ev;
+    s = ft8rx_handle::WideStream();
+    s.ev = ev;
+}
+
+int ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
+                               int keep_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    const char* who = "ft8rx_ddc_wide_stream_open";
+    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle already (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    if (h->ds.open) { set_err(h, "%s: a stream is open on this handle already (ft8rx_ddc_stream_close)", who); return -1; }
+    if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+    const uint64_t grid = (uint64_t)DDC_TO * ((uint64_t)rate_hz / 12000);
+    if (n_origin % grid != 0 || n_origin > ((uint64_t)1 << 62)) {
+        set_err(h, "%s: n_origin %llu is not a multiple of %llu (1008 rate_hz / 12000)", who, (unsigned long long)n_origin, (unsigned long long)grid); return -1;
+    }
+    ENTER(h);
+    const ddcwide::Plan p = ddcwide::plan(rate_hz);
+    const std::vector<float>& h0 = *ddw_taps(rate_hz);
+    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s;
+    ddw_tables(rate_hz, h0, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
+    std::vector<int32_t> src((size_t)n_out);
+    for (int j = 0; j < n_out; j++) src[j] = j;
+    // the stage behind: n_out IQ float32 streams at rate_mid, one channel each, from the same origin
+    if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, n_out, n_out, src.data(), dial_mid.data(), gain, n_origin / (uint64_t)p.R0,
+                                       keep_f32, f_mixed_hz)) return rc;
+    ft8rx_handle::WideStream& s = h->wds;
+    const size_t sb = DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16];
+    const int H = (int)ddcwide::history((int64_t)h0.size(), p.R0);
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
+    if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (!rc) rc = dalloc(h, &s.d_hist, (size_t)H * sb);
+    if (!rc) rc = dalloc(h, &s.d_chunk, (size_t)rate_hz * sb);
+    if (!rc) rc = dalloc(h, &s.d_mid, (size_t)n_out * (size_t)p.rate_mid);
+    if (!rc) rc = dalloc(h, &s.d_tab, tab.size());
+    if (!rc) rc = dalloc(h, &s.d_w0, w0s.size());
+    if (!rc) rc = halloc(h, &s.h_stage, (size_t)rate_hz * sb);
+    if (!rc) {
+        e = hipMemcpyAsync(s.d_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(s.d_hist, 0, (size_t)H * sb, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the tables are pageable vectors of this call
+        if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    }
+    if (rc) { ddw_stream_release(h); ddc_stream_release(h); return -2; }
+    ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz);
+    s.kind = kind; s.n_out = n_out; s.n_taps = (int)h0.size(); s.R0 = (int)p.R0; s.H = H; s.rate = rate_hz; s.rate_mid = (int32_t)p.rate_mid;
+    s.g0 = ddw_is_iq(kind) ? 1.0f : 2.0f;
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = s.n_origin / s.R0;
+    s.open = true;
+    return 0;
+}
+
+int ft8rx_ddc_wide_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+    if (!h) return -1;
+    ft8rx_handle::WideStream& s = h->wds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_wide_stream_push: no wide stream is open (ft8rx_ddc_wide_stream_open)"); return -1; }
+    if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_wide_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
+    const size_t sb = DDW_SAMPLE_BYTES[s.kind - FT8RX_WIDE_REAL_I16];
+    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_wide_stream_push: in is NULL or not aligned to a sample"); return -1; }
+    // (no ENTER: a push touches the streams' own buffers only, on the main stream; batches in flight read none of them)
+    HIPCHK(h, hipSetDevice(h->device));
+    const char* chunk = (const char*)in;
+    if (!on_device) {                                    // through the page-locked buffer, once the previous push's copy has left it
+        HIPCHK(h, hipEventSynchronize(s.ev));
+        memcpy(s.h_stage, in, (size_t)n_new * sb);
+        HIPCHK(h, hipMemcpyAsync(s.d_chunk, s.h_stage, (size_t)n_new * sb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(s.ev, h->stream));
+        chunk = s.d_chunk;
+    }
+    const int64_t n_start = s.n_origin + s.pushed, n_end = n_start + (int64_t)n_new;
+    const int64_t k_new = ddcwide::mid_done(s.n_origin, n_end, s.n_taps, s.R0);
+    const int n_k = (int)(k_new - s.k_done);             // at most rate_mid: a push is at most a second
+    if (n_k > 0) {
+        const int tk = (int)ddcwide::tile_outputs(s.R0);
+        const dim3 grid((unsigned)((n_k + tk - 1) / tk), (unsigned)s.n_out);
+        const int p_last = s.pushed ? (int)ddcwide::hist_pos(n_start - 1, s.n_origin, s.H) : 0;
+#define DDW_GO(IQ) k_ddc_pre_stream<IQ><<<grid, DDW_NT, 0, h->stream>>>(s.d_hist, s.H, p_last, chunk, s.kind, (long long)s.n_origin, (long long)n_start, \
+                       (long long)n_end, s.d_tab, s.d_w0, s.n_taps, s.R0, tk, s.g0, (long long)s.k_done, n_k, s.d_mid)
+        if (ddw_is_iq(s.kind)) DDW_GO(true); else DDW_GO(false);
+#undef DDW_GO
+        HIPCHK(h, hipGetLastError());
+    }
+    // the chunk's last H samples into the history, behind the kernel that read the old ones
+    const ddcwide::Keep kp = ddcwide::keep(s.pushed, (int64_t)n_new, s.H);
+    HIPCHK(h, hipMemcpyAsync(s.d_hist + (size_t)kp.pos * sb, chunk + (size_t)kp.skip * sb, (size_t)kp.first * sb, hipMemcpyDeviceToDevice, h->stream));
+    if (kp.second) HIPCHK(h, hipMemcpyAsync(s.d_hist, chunk + (size_t)(kp.skip + kp.first) * sb, (size_t)kp.second * sb, hipMemcpyDeviceToDevice, h->stream));
+    s.pushed += (int64_t)n_new;
+    if (n_k > 0) {
+        s.k_done = k_new;
+        return ddc_stream_push(h, s.d_mid, (uint64_t)n_k, 1, m_produced);
+    }
+    if (m_produced) *m_produced = (uint64_t)(h->ds.tiles * DDC_TO);
+    return 0;
+}
+
+int ft8rx_ddc_wide_stream_read_mid(ft8rx_handle* h, uint64_t k_first_u, int n, float* mid) {
+    if (!h) return -1;
+    const ft8rx_handle::WideStream& s = h->wds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_wide_stream_read_mid: no wide stream is open (ft8rx_ddc_wide_stream_open)"); return -1; }
+    const int64_t k_first = (int64_t)k_first_u, k_origin = s.n_origin / s.R0, cap = h->ds.cap;
+    if (n < 1 || !mid || k_first < k_origin || k_first + n > s.k_done || k_first < s.k_done - cap) {
+        set_err(h, "ft8rx_ddc_wide_stream_read_mid: intermediate samples [%lld, %lld) are not all held (held: %lld .. %lld)", (long long)k_first,
+                (long long)(k_first + n), (long long)(s.k_done - cap > k_origin ? s.k_done - cap : k_origin), (long long)s.k_done);
+        return -1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the stage behind keeps the newest `cap` samples of every channel: sample k at (k - k_origin) & (cap - 1)
+    const int64_t pos = (k_first - k_origin) & (cap - 1), first = n < cap - pos ? n : cap - pos;
+    const float2* ring = (const float2*)h->ds.d_in;
+    float2* out = (float2*)mid;
+    for (int j = 0; j < s.n_out; j++) {
+        HIPCHK(h, hipMemcpy(out + (size_t)j * n, ring + (size_t)j * cap + pos, sizeof(float2) * (size_t)first, hipMemcpyDeviceToHost));
+        if (first < n) HIPCHK(h, hipMemcpy(out + (size_t)j * n + first, ring + (size_t)j * cap, sizeof(float2) * (size_t)(n - first), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int ft8rx_ddc_wide_stream_close(ft8rx_handle* h) {
+    if (!h) return -1;
+    if (!h->wds.open) { set_err(h, "ft8rx_ddc_wide_stream_close: no wide stream is open"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the buffers
+    ddw_stream_release(h);
     ddc_stream_release(h);
     return 0;
 }

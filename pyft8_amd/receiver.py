@@ -887,27 +887,42 @@ class Receiver:
 
     def decode_stream(self, samples, sample_rate, iq=False, dial_offsets_hz=(0.0,), src=None, bands=None, **kw):
         """Decode one cycle of wider input: `samples` [n_streams][n] (one stream may come as [n]) at sample_rate = 12, 24, 48, 96 or
-        192 kHz -- real (sound card: int16 or float), or with iq=True complex baseband (SDR: complex, or int16 (I, Q) pairs
+        192 kHz (or ONE stream at a wide rate, see below) -- real (sound card: int16 or float), or with iq=True complex baseband (SDR: complex, or int16 (I, Q) pairs
         [n_streams, n, 2]) -- is down-converted on the GPU (ft8rx_ddc) into one 12 kHz USB frame per entry of
         dial_offsets_hz: channel j is stream src[j] (default: stream 0, or stream j when there are as many streams as channels)
         with its dial dial_offsets_hz[j] Hz from the stream's centre (0 Hz for real input).  The frames never leave the device.
         -> list (per channel) of message dicts, exactly what decode_frames returns for those frames; its keyword arguments (passes,
         recall, cyclestart_strings, ...) work unchanged.  bands[j], when given, is the "band" of channel j's dicts; fHz stays the audio
-        frequency inside the channel."""
+        frequency inside the channel.
+        A wide rate (a multiple of 48 kHz from 240 kHz to 129.6 MHz: ddc_wide.plan) takes ONE stream through the pre-decimator
+        (ft8rx_ddc_wide); its kind is the dtype's: with iq=True uint8 (RTL-SDR), int8 (HackRF) or int16 (I, Q)
+        pairs [n, 2], without it real int16 [n] (direct sampling; the dials are then absolute frequencies).  Float or complex samples
+        are refused there."""
         from . import ddc as _ddc
+        from . import ddc_wide as _dw
         a = np.asarray(samples)
-        cplx = np.iscomplexobj(a)
-        if cplx and not iq:
-            raise _lib.Ft8rxError("samples are complex: pass iq=True")
-        if iq:
-            kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
-        else:
-            kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
             raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
-        arr, n_streams, _ = _ddc.pack(a, kind)
+        wide = sample_rate not in _ddc.RATES and _dw.accepts(sample_rate)
+        if wide:                                # ONE stream through the pre-decimator (ft8rx_ddc_wide, DESIGN.md section 16.2)
+            kind = _dw.kind_of(a, iq)
+            if a.ndim == (3 if iq else 2):
+                if a.shape[0] != 1:
+                    raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {sample_rate} Hz -- a wide rate takes one stream")
+                a = a[0]
+            arr, _ = _dw.pack(a, kind)
+            n_streams = 1
+        else:
+            cplx = np.iscomplexobj(a)
+            if cplx and not iq:
+                raise _lib.Ft8rxError("samples are complex: pass iq=True")
+            if iq:
+                kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
+            else:
+                kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
+            arr, n_streams, _ = _ddc.pack(a, kind)
         if src is None:
             if n_streams != 1 and n_streams != n_out:
                 raise _lib.Ft8rxError(f"src: {n_streams} streams and {n_out} channels -- say which stream each channel reads")
@@ -926,7 +941,12 @@ class Receiver:
         args.update(kw)
         with self._hlock:
             h = self._handle(n_out)
-            h.ddc(arr, kind, int(sample_rate), src, dials)
+            if wide:
+                if any(int(j) != 0 for j in src):
+                    raise _lib.Ft8rxError(f"src: {list(src)} -- a wide rate takes one stream, every channel reads stream 0")
+                h.ddc_wide(arr, kind, int(sample_rate), dials)
+            else:
+                h.ddc(arr, kind, int(sample_rate), src, dials)
             return self._decode_frames_locked(None, n_out, bands=bands, **args)
 
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",

@@ -1,5 +1,6 @@
 """Live input wider than a 12 kHz frame: real or IQ samples at 12 .. 192 kHz, in chunks of any length, feed K
-channels of one receiver through the streaming down-converter (ft8rx_ddc_stream_*).  WideIn is the sibling of receiver.AudioIn: its
+channels of one receiver through the streaming down-converter (ft8rx_ddc_stream_*); ONE stream at a wide rate (240 kHz .. 129.6 MHz,
+8- or 16-bit integers: ddc_wide.py, section 16.2) goes through the pre-decimator in front of it (ft8rx_ddc_wide_stream_*).  WideIn is the sibling of receiver.AudioIn: its
 push(chunk) is what AudioIn._callback is for 12 kHz hops; Receiver.poll() runs the passes it has found due.
 
 Time is the sample clock: the first sample is t_first, absolute 12 kHz output m is t_first + m / 12000, cycle c starts at output
@@ -11,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from . import ddc as _ddc
+from . import ddc_wide as _dw
 
 NSAMP = _lib.NSAMP
 HOP = 480                     # 12 kHz samples per hop of early_decode_hops
@@ -81,7 +83,10 @@ class WideIn:
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
-        self.D = _ddc.decimation(self.sample_rate)
+        # a wide rate (ddc_wide.plan: 240 kHz .. 129.6 MHz) is ONE stream through the pre-decimator (ft8rx_ddc_wide_stream_*, DESIGN.md
+        # section 16.2); D is then the input samples per 12 kHz output all the same
+        self.wide = self.sample_rate not in _ddc.RATES and _dw.accepts(self.sample_rate)
+        self.D = self.sample_rate // 12000 if self.wide else _ddc.decimation(self.sample_rate)
         self.iq = bool(iq)
         self.dials = [float(f) for f in dial_offsets_hz]
         self.n_channels = len(self.dials)
@@ -112,13 +117,17 @@ class WideIn:
         """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
         a = np.asarray(chunk)
         cplx = np.iscomplexobj(a)
-        if cplx and not self.iq:
+        if self.wide:
+            self.kind = _dw.kind_of(a, self.iq)
+        elif cplx and not self.iq:
             raise _lib.Ft8rxError("samples are complex: pass iq=True")
-        if self.iq:
+        elif self.iq:
             self.kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
         else:
             self.kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
-        _, self.n_streams, _ = _ddc.pack(a, self.kind)
+        _, self.n_streams, _ = self._pack(a)
+        if self.wide and (self.src is not None and any(self.src)):
+            raise _lib.Ft8rxError(f"src: {self.src} -- a wide rate takes one stream, every channel reads stream 0")
         if self.src is None:
             if self.n_streams != 1 and self.n_streams != self.n_channels:
                 raise _lib.Ft8rxError(f"src: {self.n_streams} streams and {self.n_channels} channels -- say which stream each channel reads")
@@ -128,12 +137,28 @@ class WideIn:
         self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+            if self.wide:
+                self.f_mixed_hz = h.ddc_wide_stream_open(self.kind, self.sample_rate, self.dials)
+            else:
+                self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+
+    def _pack(self, chunk):
+        """-> ([n_streams][n] samples packed for self.kind, n_streams, n); a wide rate: one stream, [1][n]"""
+        if not self.wide:
+            return _ddc.pack(chunk, self.kind)
+        a = np.asarray(chunk)
+        if a.ndim == (3 if self.iq else 2):
+            if a.shape[0] != 1:
+                raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {self.sample_rate} Hz -- a wide rate takes one stream")
+            a = a[0]
+        a, n = _dw.pack(a, self.kind)
+        return a[None], 1, n
 
     def _push(self, a, real):
         """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples"""
         with self._rx._live_lock:
-            self.m_produced = self._rx._live_handle(self.n_channels).ddc_stream_push(a)
+            h = self._rx._live_handle(self.n_channels)
+            self.m_produced = h.ddc_wide_stream_push(a[0]) if self.wide else h.ddc_stream_push(a)
         if real:
             self.n_pushed += a.shape[1]
 
@@ -147,7 +172,7 @@ class WideIn:
         """The next samples of the source, any length (a longer chunk is handed on a second at a time)"""
         if self.sched is None:
             self._start(chunk)
-        a, n_streams, n = _ddc.pack(chunk, self.kind)
+        a, n_streams, n = self._pack(chunk)
         if n_streams != self.n_streams:
             raise _lib.Ft8rxError(f"push: {n_streams} streams, the source began with {self.n_streams}")
         for at in range(0, n, self.sample_rate):
@@ -159,8 +184,11 @@ class WideIn:
         if self.sched is None:
             return
         m_real = -(-self.n_pushed // self.D)
-        shape = (self.n_streams, TILE * self.D) + ((2,) if _ddc.is_iq(self.kind) else ())
-        zeros = np.zeros(shape, np.int16 if self.kind in (_ddc.REAL_I16, _ddc.IQ_I16) else np.float32)
+        if self.wide:                          # (uint8 has no zero: 128 is half a step, 128 counts of the int16 scale, above it)
+            zeros = np.full((1, TILE * self.D) + ((2,) if self.iq else ()), 128 if self.kind == _dw.IQ_U8 else 0, _dw._DTYPE[self.kind])
+        else:
+            shape = (self.n_streams, TILE * self.D) + ((2,) if _ddc.is_iq(self.kind) else ())
+            zeros = np.zeros(shape, np.int16 if self.kind in (_ddc.REAL_I16, _ddc.IQ_I16) else np.float32)
         while self.m_produced < m_real:
             self._push(zeros, False)
         self._note(m_real)
