@@ -48,6 +48,9 @@
  *     ft8rx_ddc_wide  ft8rx_ddc_wide_host  ft8rx_ddc_wide_taps  ft8rx_ddc_wide_plan     (pre-decimator: ONE stream at 240 kHz .. 129.6 MHz, 8- or
  *     ft8rx_ddc_wide_stream_open  ft8rx_ddc_wide_stream_push  ft8rx_ddc_wide_stream_read_mid   16-bit, in front of the down-converter)
  *     ft8rx_ddc_wide_stream_close
+ *     ft8rx_ddc_rat  ft8rx_ddc_rat_host  ft8rx_ddc_rat_taps  ft8rx_ddc_rat_plan         (rational resampler: ONE stream at any other rate,
+ *     ft8rx_ddc_rat_stream_open  ft8rx_ddc_rat_stream_push  ft8rx_ddc_rat_stream_read_mid      44.1 kHz, 2.048 MS/s, 10 MS/s ..., in front of
+ *     ft8rx_ddc_rat_stream_close                                                       the down-converter)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
@@ -540,6 +543,51 @@ int  ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int 
 int  ft8rx_ddc_wide_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
 int  ft8rx_ddc_wide_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid);
 int  ft8rx_ddc_wide_stream_close(ft8rx_handle* h);
+/* Rational resampler (extension): ONE stream at an integer rate_hz in [16000, 129600000] that neither ft8rx_ddc
+ * nor ft8rx_ddc_wide takes -- sound cards at 44100 / 22050 / 16000 Hz, RTL-SDR at 2.048 / 1.024 MS/s and 250 kS/s, HackRF at 8 / 10 /
+ * 20 MS/s -- in front of the down-converter above, which is used unchanged behind it.  Kinds: FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32 and
+ * FT8RX_WIDE_IQ_U8 / FT8RX_WIDE_IQ_I8 (with the sample values of ft8rx_ddc_wide); any other is refused, naming kind.
+ *   plan     for mid in 192000, 96000, 48000: g = gcd(rate, mid), L = mid / g, M = rate / g; rate_mid = the mid with the smallest L, ties
+ *            to the largest; rate_mid = rate L / M.  The prototype h is the Kaiser recipe of section 16 at fs = rate L, pass 3200 Hz,
+ *            stop min(rate, rate_mid) - 3200 Hz, 85 dB, odd length N, C = (N - 1) / 2, scaled to sum h = L (44100: 160 / 147, N = 1007;
+ *            2048000: 3 / 32, N = 179; 10000000: 3 / 625, N = 3873).  Refused, naming rate_hz: L > 320 or N > 8448.
+ *   mixer    w0 = round((f_dial + 3000) / rate 2^32) mod 2^32, u[n] = x[n] e^{-2 pi i (w0 n mod 2^32) / 2^32}, x = 0 outside the stream;
+ *   filter   t_k = k M + C,  v[k] = g0 sum_{0 <= j < N, j = t_k (mod L)} h[j] u[(t_k - j) / L],  g0 = 2 for real kinds and 1 for IQ, all
+ *            indices in 64-bit integers: intermediate sample k sits at input time k M / L, its last input is t_k / L;
+ *   then     v, an IQ float32 stream at rate_mid, goes through ft8rx_ddc / ft8rx_ddc_stream_* with the dial f_dial - f0 and `gain`, as
+ *            behind ft8rx_ddc_wide; f_mixed_hz = f0 + what that stage really mixed.
+ * The passband and stopband promise of ft8rx_ddc holds for the whole chain.  Refusals return -1 with a text that names the argument. */
+/* host only, no GPU: the plan of a rate -> 0 and rate_mid_hz / l / m / n_taps (each may be NULL), or -1 for a rate that is refused */
+int  ft8rx_ddc_rat_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* l, int32_t* m, int32_t* n_taps);
+/* host only, no GPU: h of a rate -> its length and the first min(length, cap) taps (float32; taps may be NULL); -1 for a refused rate */
+int  ft8rx_ddc_rat_taps(int32_t rate_hz, float* taps, int cap);
+/* One call = one cycle: n_samples <= 15 rate_hz samples of `kind` -> n_out frames.  Arguments, buffer ownership (the handle's buffers of
+ * ft8rx_ddc_wide, grown when a call needs more) and ordering as ft8rx_ddc_wide / ft8rx_ddc_wide_host.  Refused while a rational or a wide
+ * stream is open. */
+int  ft8rx_ddc_rat(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                   const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz);
+int  ft8rx_ddc_rat_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                        const double* f_dial_hz, float gain, double* f_mixed_hz);
+/* The same on a continuous stream, one per handle, as ft8rx_ddc_wide_stream_*: indices are absolute (input n < 2^52, intermediate k);
+ * state is allocated by open and released by close or ft8rx_destroy, nothing in between: the last ceil(N / L) input samples in their
+ * own kind, one second of input (device and page-locked), one second of intermediate samples, the channels' tables, and the streaming
+ * down-converter behind it.
+ * open      n_origin: absolute index of the first sample; k_origin = n_origin L / M must be an integer and a multiple of
+ *           1008 rate_mid / 12000 (0 always is; the grid is 18522 samples at 44100 Hz, 840000 at 10 MS/s); anything else is refused,
+ *           naming n_origin.
+ *           Refused while any stream is open; while it is open ft8rx_ddc_stream_open / _push / _close, ft8rx_ddc_wide_stream_open,
+ *           ft8rx_ddc_wide and ft8rx_ddc_rat are refused (ft8rx_ddc is not, and leaves the stream alone).
+ * push      n_new = 1 .. rate_hz samples, host or (on_device != 0) device memory: ONE kernel makes every intermediate sample whose last
+ *           input has arrived (none, if the push completes none), at most two copies update the history, then the on-device push of
+ *           the stage behind.  Every sample is the same bits however the stream was cut into chunks, and with n_origin = 0 the first
+ *           cycle is ft8rx_ddc_rat's bit for bit.  Asynchronous on the main stream.
+ * then      ft8rx_ddc_stream_frame / _read / _info work as on a plain stream (info counts intermediate samples).
+ * read_mid  test aid, as ft8rx_ddc_wide_stream_read_mid. */
+int  ft8rx_ddc_rat_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain,
+                               uint64_t n_origin, int keep_f32, double* f_mixed_hz);
+int  ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
+int  ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid);
+int  ft8rx_ddc_rat_stream_close(ft8rx_handle* h);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -85,6 +85,14 @@ PROTOTYPES = {
     "ft8rx_ddc_wide_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
     "ft8rx_ddc_wide_stream_read_mid": (INT, (PTR, U64, INT, PTR)),
     "ft8rx_ddc_wide_stream_close": (INT, (PTR,)),
+    "ft8rx_ddc_rat_plan": (INT, (I32, PTR, PTR, PTR, PTR)),
+    "ft8rx_ddc_rat_taps": (INT, (I32, PTR, INT)),
+    "ft8rx_ddc_rat": (INT, (PTR, PTR, INT, I32, U64, INT, PTR, F32, PTR, PTR, PTR)),
+    "ft8rx_ddc_rat_host": (INT, (PTR, PTR, INT, I32, U64, INT, PTR, F32, PTR)),
+    "ft8rx_ddc_rat_stream_open": (INT, (PTR, INT, I32, INT, PTR, F32, U64, INT, PTR)),
+    "ft8rx_ddc_rat_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
+    "ft8rx_ddc_rat_stream_read_mid": (INT, (PTR, U64, INT, PTR)),
+    "ft8rx_ddc_rat_stream_close": (INT, (PTR,)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

@@ -280,6 +280,7 @@ class Handle:
         self.ap_calls = (None, None)
         self._ds = None                    # the open down-converter stream: (kind, n_streams, n_out)
         self._wds = None                   # the open wide stream (ddc_wide_stream_open): (kind, n_out); _ds then describes the stage behind it
+        self._rts = None                   # the open rational stream (ddc_rat_stream_open): (kind, n_out); likewise
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
@@ -865,6 +866,74 @@ class Handle:
     def ddc_wide_stream_close(self):
         self._chk(self._L.ft8rx_ddc_wide_stream_close(self._h), "ft8rx_ddc_wide_stream_close")
         self._wds = self._ds = None
+
+    # ---- rational resampler (ft8rx_ddc_rat*): ONE stream at 44.1 kHz, 2.048 MS/s, ... in front of the down-converter
+    def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
+        """ft8rx_ddc_rat_host / ft8rx_ddc_rat: one stream of `kind` (ddc_rat.REAL_I16 .. ddc_rat.IQ_I8; forms of ddc_rat.pack) at `rate`
+        Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
+        [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
+        from . import ddc_rat as _dr
+        a, n = _dr.pack(samples, kind)
+        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
+        if len(f) < 1:
+            raise Ft8rxError("ddc_rat: at least one f_dial_hz")
+        fm = np.zeros(len(f), np.float64)
+        args = (int(kind), int(rate), n, len(f), f.ctypes.data, float(gain))
+        if not (device or want_float):
+            self._chk(self._L.ft8rx_ddc_rat_host(self._h, a.ctypes.data, *args, fm.ctypes.data), "ft8rx_ddc_rat_host")
+            return fm
+        import torch
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        d_f32 = torch.empty((len(f), NSAMP), dtype=torch.float32, device=dev) if want_float else None
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.ft8rx_ddc_rat(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc_rat")
+        self.sync()                                          # the tensors may go once the kernels have run
+        return (fm, d_f32.cpu().numpy()) if want_float else fm
+
+    def ddc_rat_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
+        """Open the rational stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the
+        first sample that will be pushed (ddc_rat.origin_ok).  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
+        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
+        if len(f) < 1:
+            raise Ft8rxError("ddc_rat_stream_open: at least one f_dial_hz")
+        fm = np.zeros(len(f), np.float64)
+        self._chk(self._L.ft8rx_ddc_rat_stream_open(self._h, int(kind), int(rate), len(f), f.ctypes.data, float(gain), int(n_origin),
+                                                    int(bool(keep_f32)), fm.ctypes.data), "ft8rx_ddc_rat_stream_open")
+        self._rts = (int(kind), len(f))
+        self._ds = (3, len(f), len(f))                       # the stage behind: one IQ float32 stream per channel
+        return fm
+
+    def ddc_rat_stream_push(self, samples, device=False):
+        """Push the next samples (forms of ddc_rat.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced so
+        far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
+        from . import ddc_rat as _dr
+        if self._rts is None:
+            raise Ft8rxError("ddc_rat_stream_push: no rational stream is open (ddc_rat_stream_open)")
+        a, n = _dr.pack(samples, self._rts[0])
+        m = C.c_uint64()
+        if not device:
+            self._chk(self._L.ft8rx_ddc_rat_stream_push(self._h, a.ctypes.data, n, 0, C.byref(m)), "ft8rx_ddc_rat_stream_push")
+            return int(m.value)
+        import torch
+        dev = torch.device("cuda", self.device)
+        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.ft8rx_ddc_rat_stream_push(self._h, d_in.data_ptr(), n, 1, C.byref(m)), "ft8rx_ddc_rat_stream_push")
+        self.sync()
+        return int(m.value)
+
+    def ddc_rat_stream_read_mid(self, k_first, n):
+        """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
+        if self._rts is None:
+            raise Ft8rxError("ddc_rat_stream_read_mid: no rational stream is open (ddc_rat_stream_open)")
+        v = np.zeros((self._rts[1], int(n)), np.complex64)
+        self._chk(self._L.ft8rx_ddc_rat_stream_read_mid(self._h, int(k_first), int(n), v.ctypes.data), "ft8rx_ddc_rat_stream_read_mid")
+        return v
+
+    def ddc_rat_stream_close(self):
+        self._chk(self._L.ft8rx_ddc_rat_stream_close(self._h), "ft8rx_ddc_rat_stream_close")
+        self._rts = self._ds = None
 
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for

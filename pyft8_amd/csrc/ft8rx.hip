@@ -60,6 +60,7 @@
 #include "kernels/report.hpp"
 #include "kernels/ddc.hpp"
 #include "kernels/ddc_wide.hpp"
+#include "kernels/ddc_rat.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -67,6 +68,7 @@
 #include "batch_plan.hpp"
 #include "ddc_ring.hpp"
 #include "ddc_wide_ring.hpp"
+#include "ddc_rat_ring.hpp"
 #include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
@@ -227,6 +229,17 @@ struct ft8rx_handle {
         uint32_t* d_w0 = nullptr;
         hipEvent_t ev = nullptr;
     } wds;
+    // rational resampler (ft8rx_ddc_rat*, kernels/ddc_rat.hpp).  The one-shot uses the three buffers of the wide
+    // one-shot above (tables, frequency words, intermediate samples: one call at a time uses them).  Its stream, as the wide stream's:
+    // everything is allocated by open and released by close (or destroy); d_hist: the newest H input samples in their own kind; d_mid:
+    // [n_out][rate_mid]; the down-converter behind it is the stream `ds`.
+    struct RatStream {
+        bool open = false, lane = false; int kind = 0, n_out = 0, n_taps = 0, L = 0, M = 0, P = 0, H = 0; int32_t rate = 0, rate_mid = 0; float g0 = 0.0f;
+        int64_t n_origin = 0, pushed = 0, k_done = 0;
+        char* d_hist = nullptr; char* d_chunk = nullptr; char* h_stage = nullptr; float2* d_mid = nullptr; float2* d_tab = nullptr;
+        uint32_t* d_w0 = nullptr;
+        hipEvent_t ev = nullptr;
+    } rts;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -475,6 +488,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
     if (h->ds.ev) hipEventDestroy(h->ds.ev);
     if (h->wds.ev) hipEventDestroy(h->wds.ev);
+    if (h->rts.ev) hipEventDestroy(h->rts.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -1297,14 +1311,14 @@ int ft8rx_set_recall_gates(ft8rx_handle* h, int32_t max_hd, int32_t min_gap) {
 }
 
 // ---------------------------------------------------------------------------- down-converter
-// Kaiser-windowed sinc, odd length from the Kaiser estimate, cutoff half way between pass and stop edge, unit DC gain; designed in
+// Kaiser-windowed sinc, odd length from the Kaiser estimate, cutoff half way between pass and stop edge, DC gain 1 (dc_gain: the rational resampler's L); designed in
 // double, rounded once
 static double ddc_bessel_i0(double x) {
     double sum = 1.0, term = 1.0;
     for (int k = 1; k < 200; k++) { term *= (x / (2.0 * k)) * (x / (2.0 * k)); sum += term; if (term < 1e-20 * sum) break; }
     return sum;
 }
-static std::vector<float> ddc_design(double f_pass, double f_stop, double A, double fs) {
+static std::vector<float> ddc_design(double f_pass, double f_stop, double A, double fs, double dc_gain = 1.0) {
     int N = (int)ceil((A - 7.95) / (2.285 * 2.0 * M_PI * (f_stop - f_pass) / fs)) + 1;
     if (N % 2 == 0) N++;
     const double beta = 0.1102 * (A - 8.7), fc = (f_pass + f_stop) / (2.0 * fs), c = (N - 1) / 2.0;
@@ -1317,7 +1331,7 @@ static std::vector<float> ddc_design(double f_pass, double f_stop, double A, dou
         sum += h[n];
     }
     std::vector<float> out(N);
-    for (int n = 0; n < N; n++) out[n] = (float)(h[n] / sum);
+    for (int n = 0; n < N; n++) out[n] = (float)(dc_gain * (h[n] / sum));
     return out;
 }
 struct DdcTaps { std::vector<float> h1[3], h2[2]; };      // h1: D = 4, 8, 16; h2: at 24 kHz, at 12 kHz (D = 1)
@@ -1493,6 +1507,7 @@ int ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_stre
                           float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
     if (!h) return -1;
     if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_open: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)"); return -1; }
+    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_open: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)"); return -1; }
     return ddc_stream_open(h, kind, rate_hz, n_streams, n_out, src, f_dial_hz, gain, n_origin, keep_f32, f_mixed_hz);
 }
 static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
@@ -1533,6 +1548,7 @@ static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_str
 int ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
     if (!h) return -1;
     if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_push: the open stream is a wide stream (ft8rx_ddc_wide_stream_push)"); return -1; }
+    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_push: the open stream is a rational stream (ft8rx_ddc_rat_stream_push)"); return -1; }
     return ddc_stream_push(h, in, n_new, on_device, m_produced);
 }
 static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
@@ -1637,6 +1653,7 @@ int ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_
 int ft8rx_ddc_stream_close(ft8rx_handle* h) {
     if (!h) return -1;
     if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_close: the open stream is a wide stream (ft8rx_ddc_wide_stream_close)"); return -1; }
+    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_close: the open stream is a rational stream (ft8rx_ddc_rat_stream_close)"); return -1; }
     if (!h->ds.open) { set_err(h, "ft8rx_ddc_stream_close: no stream is open"); return -1; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the rings
@@ -1784,6 +1801,7 @@ static int ddw_check_oneshot(ft8rx_handle* h, const char* who, int kind, int32_t
     if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
     if (n_samples > (uint64_t)15 * (uint64_t)rate_hz) { set_err(h, "%s: n_samples %llu > %llu (15 s at rate_hz)", who, (unsigned long long)n_samples, 15ull * (unsigned long long)rate_hz); return -1; }
     if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
     return 0;
 }
 
@@ -1828,6 +1846,7 @@ int ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n
     if (!h) return -1;
     const char* who = "ft8rx_ddc_wide_stream_open";
     if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle already (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
     if (h->ds.open) { set_err(h, "%s: a stream is open on this handle already (ft8rx_ddc_stream_close)", who); return -1; }
     if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
     const uint64_t grid = (uint64_t)DDC_TO * ((uint64_t)rate_hz / 12000);
@@ -1945,6 +1964,313 @@ int ft8rx_ddc_wide_stream_close(ft8rx_handle* h) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the buffers
     ddw_stream_release(h);
+    ddc_stream_release(h);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- rational resampler
+// The kernel's tiles and the limits, against the pure index arithmetic of ddc_rat_ring.hpp
+static_assert(ddcrat::LANE_P == 64 && ddcrat::LANE_TABLE == DDR_TAB && ddcrat::LANE_SAMPLES == DDR_LS_LANE && ddcrat::LANE_TILE == DDR_NT &&
+              ddcrat::PIECE == DDR_JP && ddcrat::WAVE_SAMPLES == DDR_LS_WAVE && ddcrat::WAVE_TILE == DDR_TK_WAVE && DDR_JP % 64 == 0 &&
+              DDR_TK_WAVE == 4 * (DDR_NT / 64), "ddc_rat_ring.hpp: the tiles of kernels/ddc_rat.hpp");
+static_assert(DdrLds<true, true>::BYTES <= 64 * 1024 && DdrLds<true, false>::BYTES <= 64 * 1024, "the LDS image is static shared memory");
+static_assert(ddcrat::plan(44100).rate_mid == 48000 && ddcrat::plan(44100).L == 160 && ddcrat::plan(44100).M == 147 &&
+              ddcrat::plan(2048000).rate_mid == 192000 && ddcrat::plan(2048000).L == 3 && ddcrat::plan(2048000).M == 32 &&
+              ddcrat::plan(20000000).rate_mid == 96000 && ddcrat::plan(48000).rate_mid == 0 && ddcrat::plan(2400000).rate_mid == 0 &&
+              ddcrat::plan(900001).rate_mid == 0 && ddcrat::plan(15999).rate_mid == 0, "ddc_rat_ring.hpp: plan");
+// a tile of either regime holds at least one output and its inputs fit the LDS image, whatever M / L and P
+constexpr bool ddr_tiles_fit() {
+    for (int64_t m = 1; m <= ddcrat::MAX_TAPS; m += 7)
+        for (int64_t p = 1; p <= ddcrat::LANE_P; p += 9) {
+            const int64_t a = ddcrat::tile_fit(DDR_LS_LANE, p, 1, m, DDR_NT), b = ddcrat::tile_fit(DDR_LS_WAVE, DDR_JP, 1, m, DDR_TK_WAVE);
+            if (a < 1 || (a - 1) * m + 1 + p > DDR_LS_LANE || b < 1 || (b - 1) * m + 1 + DDR_JP > DDR_LS_WAVE) return false;
+        }
+    return true;
+}
+static_assert(ddr_tiles_fit(), "ddc_rat_ring.hpp: a tile's input fits the LDS image");
+
+static bool ddr_kind_ok(int kind) { return (kind >= FT8RX_DDC_REAL_I16 && kind <= FT8RX_DDC_IQ_F32) || kind == FT8RX_WIDE_IQ_U8 || kind == FT8RX_WIDE_IQ_I8; }
+static size_t ddr_sample_bytes(int kind) { return kind <= FT8RX_DDC_IQ_F32 ? DDC_SAMPLE_BYTES[kind] : 2; }
+static bool ddr_is_iq(int kind) { return kind != FT8RX_DDC_REAL_I16 && kind != FT8RX_DDC_REAL_F32; }
+
+// h of a rate: the recipe of ddc_design at fs = rate L, pass 3200 Hz, stop min(rate, rate_mid) - 3200 Hz, 85 dB, sum h = L; designed
+// once per rate.  nullptr: the plan refuses the rate, or the filter is longer than MAX_TAPS (its length is worked out before it is made)
+static const std::vector<float>* ddr_taps(int32_t rate_hz) {
+    const ddcrat::Plan p = ddcrat::plan(rate_hz);
+    if (!p.rate_mid) return nullptr;
+    const double fs = (double)rate_hz * (double)p.L, f_stop = (double)(rate_hz < p.rate_mid ? rate_hz : p.rate_mid) - 3200.0;
+    if ((85.0 - 7.95) / (2.285 * 2.0 * M_PI * (f_stop - 3200.0) / fs) + 2.0 > (double)ddcrat::MAX_TAPS) return nullptr;
+    static std::mutex mu;
+    static std::map<int32_t, std::vector<float>> designed;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = designed.find(rate_hz);
+    if (it == designed.end()) it = designed.emplace(rate_hz, ddc_design(3200.0, f_stop, 85.0, fs, (double)p.L)).first;
+    return (int64_t)it->second.size() <= ddcrat::MAX_TAPS ? &it->second : nullptr;
+}
+
+int ft8rx_ddc_rat_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* l, int32_t* m, int32_t* n_taps) {
+    const ddcrat::Plan p = ddcrat::plan(rate_hz);
+    const std::vector<float>* t = ddr_taps(rate_hz);
+    if (!t) return -1;
+    if (rate_mid_hz) *rate_mid_hz = (int32_t)p.rate_mid;
+    if (l) *l = (int32_t)p.L;
+    if (m) *m = (int32_t)p.M;
+    if (n_taps) *n_taps = (int32_t)t->size();
+    return 0;
+}
+
+int ft8rx_ddc_rat_taps(int32_t rate_hz, float* taps, int cap) {
+    const std::vector<float>* t = ddr_taps(rate_hz);
+    if (!t) return -1;
+    for (int i = 0; taps && i < cap && i < (int)t->size(); i++) taps[i] = (*t)[i];
+    return (int)t->size();
+}
+
+// the argument checks every entry shares -> 0, or -1 with the error text
+static int ddr_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
+    if (!ddr_kind_ok(kind)) { set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32, FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8", who, kind); return -1; }
+    if (!ddr_taps(rate_hz)) {
+        set_err(h, "%s: rate_hz %d is not taken: outside [16000, 129600000], a rate of ft8rx_ddc or ft8rx_ddc_wide, L > 320 or more than 8448 taps", who, (int)rate_hz);
+        return -1;
+    }
+    if (n_out < 1 || n_out > h->max_frames || n_out > 65535) { set_err(h, "%s: n_out %d outside [1, %d] (max_frames; at most 65535)", who, n_out, h->max_frames); return -1; }
+    if (!f_dial_hz) { set_err(h, "%s: f_dial_hz is NULL", who); return -1; }
+    for (int j = 0; j < n_out; j++)
+        if (!(f_dial_hz[j] >= -0.5 * rate_hz && f_dial_hz[j] < 0.5 * rate_hz)) { set_err(h, "%s: f_dial_hz[%d] = %g outside [-rate_hz / 2, rate_hz / 2)", who, j, f_dial_hz[j]); return -1; }
+    if (!(fabsf(gain) <= 3.0e38f)) { set_err(h, "%s: gain is not finite", who); return -1; }
+    return 0;
+}
+
+// per channel: the frequency word w0, the table by phase T[phi][i] = h[phi + i L] e^{+2 pi i (w0 i mod 2^32) / 2^32} (double, rounded once;
+// zero from N on), the dial left for the stage behind (f_dial - f0, about -3000 Hz) and f0 itself, both taken into [-rate / 2, rate / 2)
+static void ddr_tables(int32_t rate_hz, const std::vector<float>& hp, int L, int n_out, const double* f_dial_hz, std::vector<float2>& tab,
+                       std::vector<uint32_t>& w0s, std::vector<double>& dial_mid, std::vector<double>& f0s) {
+    const size_t N = hp.size(), P = (size_t)ddcrat::phase_taps((int64_t)N, L), LP = (size_t)L * P;
+    tab.assign((size_t)n_out * LP, make_float2(0.0f, 0.0f)); w0s.resize((size_t)n_out); dial_mid.resize((size_t)n_out); f0s.resize((size_t)n_out);
+    for (int c = 0; c < n_out; c++) {
+        const double r = nearbyint((f_dial_hz[c] + 3000.0) / (double)rate_hz * 4294967296.0);
+        const uint32_t w0 = (uint32_t)((long long)r & 0xffffffffLL);
+        double f0 = (double)w0 * (double)rate_hz / 4294967296.0;
+        if (f0 >= 0.5 * rate_hz) f0 -= (double)rate_hz;
+        double d = f_dial_hz[c] - f0;
+        d -= (double)rate_hz * nearbyint(d / (double)rate_hz);
+        w0s[c] = w0; f0s[c] = f0; dial_mid[c] = d;
+        for (size_t i = 0; i < P; i++) {
+            const double a = (double)(uint32_t)(w0 * (uint32_t)i) * (M_PI / 2147483648.0), ca = cos(a), sa = sin(a);
+            for (size_t phi = 0; phi < (size_t)L && phi + i * (size_t)L < N; phi++) {
+                const double hv = (double)hp[phi + i * (size_t)L];
+                tab[(size_t)c * LP + phi * P + i] = make_float2((float)(hv * ca), (float)(hv * sa));
+            }
+        }
+    }
+}
+
+// the one-shot behind its checks: the resampler into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
+static int ddr_run(ft8rx_handle* h, const char* who, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz,
+                   float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    const ddcrat::Plan p = ddcrat::plan(rate_hz);
+    const std::vector<float>& hp = *ddr_taps(rate_hz);
+    const int D = (int)(p.rate_mid / 12000), N = (int)hp.size(), L = (int)p.L, M = (int)p.M, P = (int)ddcrat::phase_taps(N, L);
+    const int tk = (int)ddcrat::tile_outputs(N, L, M);
+    const bool lane = ddcrat::lane_regime(N, L);
+    const int64_t n_mid = ddcrat::mid_count((int64_t)n_samples, N, L, M, (int64_t)FT8RX_NSAMP * D);
+    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s, fm((size_t)n_out);
+    ddr_tables(rate_hz, hp, L, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
+    if (ddw_reserve(h, who, &h->d_wide_tab, &h->wide_tab_cap, sizeof(float2) * tab.size()) ||
+        ddw_reserve(h, who, &h->d_wide_w0, &h->wide_w0_cap, sizeof(uint32_t) * w0s.size()) ||
+        ddw_reserve(h, who, &h->d_wide_mid, &h->wide_mid_cap, sizeof(float2) * (size_t)n_out * (size_t)n_mid)) return -2;
+    // the tables are pageable vectors of this call, and an earlier call's kernel may still read the device copies
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d_wide_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_wide_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((n_mid + tk - 1) / tk), (unsigned)n_out);
+    const float g0 = ddr_is_iq(kind) ? 1.0f : 2.0f;
+#define DDR_GO(IQ, LANE) k_ddc_rat<IQ, LANE><<<grid, DDR_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, \
+                             (const uint32_t*)h->d_wide_w0, (N - 1) / 2, L, M, P, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid)
+    if (ddr_is_iq(kind)) { if (lane) DDR_GO(true, true); else DDR_GO(true, false); }
+    else { if (lane) DDR_GO(false, true); else DDR_GO(false, false); }
+#undef DDR_GO
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> src((size_t)n_out);
+    for (int j = 0; j < n_out; j++) src[j] = j;
+    if (const int rc = ddc_launch(h, D, h->d_wide_mid, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), dial_mid.data(),
+                                  gain, d_audio, d_audio_f32, fm.data())) return rc;
+    if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz); }
+    return 0;
+}
+
+static int ddr_check_oneshot(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain) {
+    if (ddr_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+    if (n_samples > (uint64_t)15 * (uint64_t)rate_hz) { set_err(h, "%s: n_samples %llu > %llu (15 s at rate_hz)", who, (unsigned long long)n_samples, 15ull * (unsigned long long)rate_hz); return -1; }
+    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
+    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    return 0;
+}
+
+int ft8rx_ddc_rat(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                  int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    if (ddr_check_oneshot(h, "ft8rx_ddc_rat", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!d_in || ((uintptr_t)d_in % ddr_sample_bytes(kind)) != 0) { set_err(h, "ft8rx_ddc_rat: d_in is NULL or not aligned to a sample"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h)) return -2;
+    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    return ddr_run(h, "ft8rx_ddc_rat", d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+}
+
+int ft8rx_ddc_rat_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                       double* f_mixed_hz) {
+    if (!h) return -1;
+    if (ddr_check_oneshot(h, "ft8rx_ddc_rat_host", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!in) { set_err(h, "ft8rx_ddc_rat_host: in is NULL"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h) || need_staging(h)) return -2;
+    const size_t bytes = (size_t)n_samples * ddr_sample_bytes(kind);
+    if (ddw_reserve(h, "ft8rx_ddc_rat_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
+    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = ddr_run(h, "ft8rx_ddc_rat_host", h->d_ddc_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- the rational stream: the resampler on a continuous stream, in front of the streaming down-converter (section 16.1), which it
+// opens, feeds on the device and closes.  The index arithmetic is ddc_rat_ring.hpp's.
+static void ddr_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::RatStream& s = h->rts;
+    release_dev(h, s.d_hist); release_dev(h, s.d_chunk); release_dev(h, s.d_mid); release_dev(h, s.d_tab); release_dev(h, s.d_w0); release_host(h, s.h_stage);
+    const hipEvent_t ev = s.ev;
+    s = ft8rx_handle::RatStream();
+    s.ev = ev;
+}
+
+int ft8rx_ddc_rat_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
+                              int keep_f32, double* f_mixed_hz) {
+    if (!h) return -1;
+    const char* who = "ft8rx_ddc_rat_stream_open";
+    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle already (ft8rx_ddc_rat_stream_close)", who); return -1; }
+    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    if (h->ds.open) { set_err(h, "%s: a stream is open on this handle already (ft8rx_ddc_stream_close)", who); return -1; }
+    if (ddr_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+    const ddcrat::Plan p = ddcrat::plan(rate_hz);
+    if (n_origin > (uint64_t)ddcrat::N_MAX || !ddcrat::origin_ok((int64_t)n_origin, p.rate_mid, p.L, p.M)) {
+        set_err(h, "%s: n_origin %llu: n_origin L / M must be an integer multiple of %d (1008 rate_mid / 12000), n_origin <= 2^52", who,
+                (unsigned long long)n_origin, (int)(DDC_TO * (p.rate_mid / 12000)));
+        return -1;
+    }
+    ENTER(h);
+    const std::vector<float>& hp = *ddr_taps(rate_hz);
+    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s;
+    ddr_tables(rate_hz, hp, (int)p.L, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
+    std::vector<int32_t> src((size_t)n_out);
+    for (int j = 0; j < n_out; j++) src[j] = j;
+    // the stage behind: n_out IQ float32 streams at rate_mid, one channel each, from the same origin
+    if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, n_out, n_out, src.data(), dial_mid.data(), gain,
+                                       (uint64_t)ddcrat::k_origin((int64_t)n_origin, p.L, p.M), keep_f32, f_mixed_hz)) return rc;
+    ft8rx_handle::RatStream& s = h->rts;
+    const size_t sb = ddr_sample_bytes(kind);
+    const int H = (int)ddcrat::history((int64_t)hp.size(), p.L);
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
+    if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (!rc) rc = dalloc(h, &s.d_hist, (size_t)H * sb);
+    if (!rc) rc = dalloc(h, &s.d_chunk, (size_t)rate_hz * sb);
+    if (!rc) rc = dalloc(h, &s.d_mid, (size_t)n_out * (size_t)p.rate_mid);
+    if (!rc) rc = dalloc(h, &s.d_tab, tab.size());
+    if (!rc) rc = dalloc(h, &s.d_w0, w0s.size());
+    if (!rc) rc = halloc(h, &s.h_stage, (size_t)rate_hz * sb);
+    if (!rc) {
+        e = hipMemcpyAsync(s.d_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(s.d_hist, 0, (size_t)H * sb, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the tables are pageable vectors of this call
+        if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    }
+    if (rc) { ddr_stream_release(h); ddc_stream_release(h); return -2; }
+    ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz);
+    s.kind = kind; s.n_out = n_out; s.n_taps = (int)hp.size(); s.L = (int)p.L; s.M = (int)p.M; s.P = (int)ddcrat::phase_taps((int64_t)hp.size(), p.L); s.H = H;
+    s.lane = ddcrat::lane_regime((int64_t)hp.size(), p.L);
+    s.rate = rate_hz; s.rate_mid = (int32_t)p.rate_mid;
+    s.g0 = ddr_is_iq(kind) ? 1.0f : 2.0f;
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = ddcrat::k_origin(s.n_origin, s.L, s.M);
+    s.open = true;
+    return 0;
+}
+
+int ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+    if (!h) return -1;
+    ft8rx_handle::RatStream& s = h->rts;
+    if (!s.open) { set_err(h, "ft8rx_ddc_rat_stream_push: no rational stream is open (ft8rx_ddc_rat_stream_open)"); return -1; }
+    if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_rat_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
+    const size_t sb = ddr_sample_bytes(s.kind);
+    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_rat_stream_push: in is NULL or not aligned to a sample"); return -1; }
+    if (s.n_origin + s.pushed + (int64_t)n_new > 2 * ddcrat::N_MAX) { set_err(h, "ft8rx_ddc_rat_stream_push: n_new %llu takes the stream past index 2^53", (unsigned long long)n_new); return -1; }
+    // (no ENTER: a push touches the streams' own buffers only, on the main stream; batches in flight read none of them)
+    HIPCHK(h, hipSetDevice(h->device));
+    const char* chunk = (const char*)in;
+    if (!on_device) {                                    // through the page-locked buffer, once the previous push's copy has left it
+        HIPCHK(h, hipEventSynchronize(s.ev));
+        memcpy(s.h_stage, in, (size_t)n_new * sb);
+        HIPCHK(h, hipMemcpyAsync(s.d_chunk, s.h_stage, (size_t)n_new * sb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(s.ev, h->stream));
+        chunk = s.d_chunk;
+    }
+    const int64_t n_start = s.n_origin + s.pushed, n_end = n_start + (int64_t)n_new;
+    const int64_t k_new = ddcrat::mid_done(s.n_origin, n_end, s.n_taps, s.L, s.M);
+    const int n_k = (int)(k_new - s.k_done);             // at most rate_mid: a push is at most a second
+    if (n_k > 0) {
+        const int tk = (int)ddcrat::tile_outputs(s.n_taps, s.L, s.M);
+        const dim3 grid((unsigned)((n_k + tk - 1) / tk), (unsigned)s.n_out);
+        const int p_last = s.pushed ? (int)ddcrat::hist_pos(n_start - 1, s.n_origin, s.H) : 0;
+#define DDR_GO(IQ, LANE) k_ddc_rat_stream<IQ, LANE><<<grid, DDR_NT, 0, h->stream>>>(s.d_hist, s.H, p_last, chunk, s.kind, (long long)s.n_origin, \
+                             (long long)n_start, (long long)n_end, s.d_tab, s.d_w0, (s.n_taps - 1) / 2, s.L, s.M, s.P, tk, s.g0, (long long)s.k_done, n_k, s.d_mid)
+        if (ddr_is_iq(s.kind)) { if (s.lane) DDR_GO(true, true); else DDR_GO(true, false); }
+        else { if (s.lane) DDR_GO(false, true); else DDR_GO(false, false); }
+#undef DDR_GO
+        HIPCHK(h, hipGetLastError());
+    }
+    // the chunk's last H samples into the history, behind the kernel that read the old ones
+    const ddcrat::Keep kp = ddcrat::keep(s.pushed, (int64_t)n_new, s.H);
+    HIPCHK(h, hipMemcpyAsync(s.d_hist + (size_t)kp.pos * sb, chunk + (size_t)kp.skip * sb, (size_t)kp.first * sb, hipMemcpyDeviceToDevice, h->stream));
+    if (kp.second) HIPCHK(h, hipMemcpyAsync(s.d_hist, chunk + (size_t)(kp.skip + kp.first) * sb, (size_t)kp.second * sb, hipMemcpyDeviceToDevice, h->stream));
+    s.pushed += (int64_t)n_new;
+    if (n_k > 0) {
+        s.k_done = k_new;
+        return ddc_stream_push(h, s.d_mid, (uint64_t)n_k, 1, m_produced);
+    }
+    if (m_produced) *m_produced = (uint64_t)(h->ds.tiles * DDC_TO);
+    return 0;
+}
+
+int ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first_u, int n, float* mid) {
+    if (!h) return -1;
+    const ft8rx_handle::RatStream& s = h->rts;
+    if (!s.open) { set_err(h, "ft8rx_ddc_rat_stream_read_mid: no rational stream is open (ft8rx_ddc_rat_stream_open)"); return -1; }
+    const int64_t k_first = (int64_t)k_first_u, k_origin = ddcrat::k_origin(s.n_origin, s.L, s.M), cap = h->ds.cap;
+    if (n < 1 || !mid || k_first < k_origin || k_first + n > s.k_done || k_first < s.k_done - cap) {
+        set_err(h, "ft8rx_ddc_rat_stream_read_mid: intermediate samples [%lld, %lld) are not all held (held: %lld .. %lld)", (long long)k_first,
+                (long long)(k_first + n), (long long)(s.k_done - cap > k_origin ? s.k_done - cap : k_origin), (long long)s.k_done);
+        return -1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the stage behind keeps the newest `cap` samples of every channel: sample k at (k - k_origin) & (cap - 1)
+    const int64_t pos = (k_first - k_origin) & (cap - 1), first = n < cap - pos ? n : cap - pos;
+    const float2* ring = (const float2*)h->ds.d_in;
+    float2* out = (float2*)mid;
+    for (int j = 0; j < s.n_out; j++) {
+        HIPCHK(h, hipMemcpy(out + (size_t)j * n, ring + (size_t)j * cap + pos, sizeof(float2) * (size_t)first, hipMemcpyDeviceToHost));
+        if (first < n) HIPCHK(h, hipMemcpy(out + (size_t)j * n + first, ring + (size_t)j * cap, sizeof(float2) * (size_t)(n - first), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int ft8rx_ddc_rat_stream_close(ft8rx_handle* h) {
+    if (!h) return -1;
+    if (!h->rts.open) { set_err(h, "ft8rx_ddc_rat_stream_close: no rational stream is open"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the buffers
+    ddr_stream_release(h);
     ddc_stream_release(h);
     return 0;
 }

@@ -584,7 +584,7 @@ class Receiver:
     def __init__(self, input_device_keywords, on_message, sync_score_min=85, max_cands=200,
                  search_freq_range=[100, 3000], search_time_range=[-2.5 + 0.5, 2.5 + 0.5], verbose=False,
                  device=0, max_frames=1, time_source=None, sleep=None, audio_source=None, autostart=None, early_decode_hop=(320, 340),
-                 sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, **extension_knobs):
+                 sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False, **extension_knobs):
         if search_freq_range[1] > 5900 or search_freq_range[0] < 12.5 or search_freq_range[0] >= search_freq_range[1]:
             # the reference sizes its grid from search_freq_range (receiver.py:234-240) and itself fails beyond ~5940 Hz, where the
             # fine-sync slice runs off the cycle spectrum (receiver.py:181-182).  Here the layouts are compile-time: up to 3000 Hz runs
@@ -650,7 +650,7 @@ class Receiver:
         # may also be called directly).  audio_in stays the 12 kHz object: its search grid and waterfall are not maintained for wide input.
         self.wide_in = None
         if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first)
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
         # The reference starts its audio thread and manage_cycle in the constructor (receiver.py:252, 336).  Same here when there
         # is something to listen to: an explicit audio_source, or PortAudio (PyAudio importable and a device matches the keywords).
         if autostart is None:
@@ -659,19 +659,20 @@ class Receiver:
             self.start(audio_source)
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
-    def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None):
+    def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False):
         """Open the audio source (AudioIn.open) and start the daemon that decodes completed cycles: every 0.1 s (the reference's
         poll period, receiver.py:383) it calls poll(); on_message runs on that thread, as in the reference.  Unlike the
         reference, whose daemon dies on the first exception, an exception is kept in .thread_error and the loop ends.
         sample_rate (here or in the constructor): audio_source is an iterator of chunks of any length at that rate -- real, or IQ
         with iq=True, the forms of decode_stream -- feeding the channels dial_offsets_hz (wide_in.WideIn.open); t_first = the time of
-        its first sample (default: time_source() at the first chunk)."""
+        its first sample (default: time_source() at the first chunk).  resample=True: a rate that is no multiple of 12 kHz goes through
+        the rational resampler (wide_in.WideIn)."""
         if self._thread is not None and self._thread.is_alive():
             return self
         self._stop.clear()
         self.thread_error = None
         if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first)
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
         if self.wide_in is not None:
             if audio_source is not None:
                 self.wide_in.open(audio_source)
@@ -885,7 +886,7 @@ class Receiver:
         from . import recall as R
         return [R.entries_from_dicts(d or [], self.cfg) for d in recall]
 
-    def decode_stream(self, samples, sample_rate, iq=False, dial_offsets_hz=(0.0,), src=None, bands=None, **kw):
+    def decode_stream(self, samples, sample_rate, iq=False, dial_offsets_hz=(0.0,), src=None, bands=None, resample=False, **kw):
         """Decode one cycle of wider input: `samples` [n_streams][n] (one stream may come as [n]) at sample_rate = 12, 24, 48, 96 or
         192 kHz (or ONE stream at a wide rate, see below) -- real (sound card: int16 or float), or with iq=True complex baseband (SDR: complex, or int16 (I, Q) pairs
         [n_streams, n, 2]) -- is down-converted on the GPU (ft8rx_ddc) into one 12 kHz USB frame per entry of
@@ -897,16 +898,34 @@ class Receiver:
         A wide rate (a multiple of 48 kHz from 240 kHz to 129.6 MHz: ddc_wide.plan) takes ONE stream through the pre-decimator
         (ft8rx_ddc_wide); its kind is the dtype's: with iq=True uint8 (RTL-SDR), int8 (HackRF) or int16 (I, Q)
         pairs [n, 2], without it real int16 [n] (direct sampling; the dials are then absolute frequencies).  Float or complex samples
-        are refused there."""
+        are refused there.
+        resample=True: the path is chosen by the rate -- a rate of ddc.RATES and a wide rate as above, any other rate that
+        ddc_rat.accepts (44.1 kHz, 2.048 MS/s, 10 MS/s: ONE stream, any of the dtypes above) through the rational resampler
+        (ft8rx_ddc_rat); a rate none of the three takes is refused, naming the rate.  Without it every rate
+        behaves and is refused as it always was."""
         from . import ddc as _ddc
         from . import ddc_wide as _dw
+        from . import ddc_rat as _dr
         a = np.asarray(samples)
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
             raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
         wide = sample_rate not in _ddc.RATES and _dw.accepts(sample_rate)
-        if wide:                                # ONE stream through the pre-decimator (ft8rx_ddc_wide, DESIGN.md section 16.2)
+        rat = bool(resample) and sample_rate not in _ddc.RATES and not wide
+        if rat:                                 # ONE stream through the rational resampler (ft8rx_ddc_rat, DESIGN.md section 16.3)
+            if not _dr.accepts(sample_rate):
+                raise _lib.Ft8rxError(f"rate {sample_rate} is taken by none of ddc, ddc_wide and ddc_rat")
+            kind = _dr.kind_of(a, iq)
+            if _dr.is_iq(kind) and not iq:
+                raise _lib.Ft8rxError("samples are complex: pass iq=True")
+            if a.ndim == (2 if a.dtype.kind == "c" else 3 if iq else 2):
+                if a.shape[0] != 1:
+                    raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {sample_rate} Hz -- a resampled rate takes one stream")
+                a = a[0]
+            arr, _ = _dr.pack(a, kind)
+            n_streams = 1
+        elif wide:                                # ONE stream through the pre-decimator (ft8rx_ddc_wide, DESIGN.md section 16.2)
             kind = _dw.kind_of(a, iq)
             if a.ndim == (3 if iq else 2):
                 if a.shape[0] != 1:
@@ -941,7 +960,11 @@ class Receiver:
         args.update(kw)
         with self._hlock:
             h = self._handle(n_out)
-            if wide:
+            if rat:
+                if any(int(j) != 0 for j in src):
+                    raise _lib.Ft8rxError(f"src: {list(src)} -- a resampled rate takes one stream, every channel reads stream 0")
+                h.ddc_rat(arr, kind, int(sample_rate), dials)
+            elif wide:
                 if any(int(j) != 0 for j in src):
                     raise _lib.Ft8rxError(f"src: {list(src)} -- a wide rate takes one stream, every channel reads stream 0")
                 h.ddc_wide(arr, kind, int(sample_rate), dials)

@@ -1,6 +1,8 @@
 """Live input wider than a 12 kHz frame: real or IQ samples at 12 .. 192 kHz, in chunks of any length, feed K
 channels of one receiver through the streaming down-converter (ft8rx_ddc_stream_*); ONE stream at a wide rate (240 kHz .. 129.6 MHz,
-8- or 16-bit integers: ddc_wide.py, section 16.2) goes through the pre-decimator in front of it (ft8rx_ddc_wide_stream_*).  WideIn is the sibling of receiver.AudioIn: its
+8- or 16-bit integers: ddc_wide.py, section 16.2) goes through the pre-decimator in front of it (ft8rx_ddc_wide_stream_*), and with
+resample=True ONE stream at any other rate ddc_rat.py takes (44.1 kHz, 2.048 MS/s: section 16.3) through the rational resampler
+(ft8rx_ddc_rat_stream_*).  WideIn is the sibling of receiver.AudioIn: its
 push(chunk) is what AudioIn._callback is for 12 kHz hops; Receiver.poll() runs the passes it has found due.
 
 Time is the sample clock: the first sample is t_first, absolute 12 kHz output m is t_first + m / 12000, cycle c starts at output
@@ -13,6 +15,7 @@ import numpy as np
 from . import _lib
 from . import ddc as _ddc
 from . import ddc_wide as _dw
+from . import ddc_rat as _dr
 
 NSAMP = _lib.NSAMP
 HOP = 480                     # 12 kHz samples per hop of early_decode_hops
@@ -80,13 +83,18 @@ class WideIn:
     end of a finite source it pushes zeros until the outputs of the last real sample exist, notes the passes then due and sets
     source_exhausted."""
 
-    def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None):
+    def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
         # a wide rate (ddc_wide.plan: 240 kHz .. 129.6 MHz) is ONE stream through the pre-decimator (ft8rx_ddc_wide_stream_*, DESIGN.md
         # section 16.2); D is then the input samples per 12 kHz output all the same
         self.wide = self.sample_rate not in _ddc.RATES and _dw.accepts(self.sample_rate)
-        self.D = self.sample_rate // 12000 if self.wide else _ddc.decimation(self.sample_rate)
+        # resample=True: a rate neither of them takes is ONE stream through the rational resampler (ft8rx_ddc_rat_stream_*, section 16.3);
+        # sample_rate / 12000 is then no integer, and input counts become output counts by exact integer arithmetic (_outputs)
+        self.rat = bool(resample) and self.sample_rate not in _ddc.RATES and not self.wide
+        if self.rat and not _dr.accepts(self.sample_rate):
+            raise _lib.Ft8rxError(f"rate {self.sample_rate} is taken by none of ddc, ddc_wide and ddc_rat")
+        self.D = None if self.rat else self.sample_rate // 12000 if self.wide else _ddc.decimation(self.sample_rate)
         self.iq = bool(iq)
         self.dials = [float(f) for f in dial_offsets_hz]
         self.n_channels = len(self.dials)
@@ -117,7 +125,11 @@ class WideIn:
         """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
         a = np.asarray(chunk)
         cplx = np.iscomplexobj(a)
-        if self.wide:
+        if self.rat:
+            self.kind = _dr.kind_of(a, self.iq)
+            if not self.iq and _dr.is_iq(self.kind):
+                raise _lib.Ft8rxError("samples are complex: pass iq=True")
+        elif self.wide:
             self.kind = _dw.kind_of(a, self.iq)
         elif cplx and not self.iq:
             raise _lib.Ft8rxError("samples are complex: pass iq=True")
@@ -128,6 +140,8 @@ class WideIn:
         _, self.n_streams, _ = self._pack(a)
         if self.wide and (self.src is not None and any(self.src)):
             raise _lib.Ft8rxError(f"src: {self.src} -- a wide rate takes one stream, every channel reads stream 0")
+        if self.rat and (self.src is not None and any(self.src)):
+            raise _lib.Ft8rxError(f"src: {self.src} -- a resampled rate takes one stream, every channel reads stream 0")
         if self.src is None:
             if self.n_streams != 1 and self.n_streams != self.n_channels:
                 raise _lib.Ft8rxError(f"src: {self.n_streams} streams and {self.n_channels} channels -- say which stream each channel reads")
@@ -137,30 +151,36 @@ class WideIn:
         self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            if self.wide:
+            if self.rat:
+                self.f_mixed_hz = h.ddc_rat_stream_open(self.kind, self.sample_rate, self.dials)
+            elif self.wide:
                 self.f_mixed_hz = h.ddc_wide_stream_open(self.kind, self.sample_rate, self.dials)
             else:
                 self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
 
     def _pack(self, chunk):
-        """-> ([n_streams][n] samples packed for self.kind, n_streams, n); a wide rate: one stream, [1][n]"""
-        if not self.wide:
+        """-> ([n_streams][n] samples packed for self.kind, n_streams, n); a wide or a resampled rate: one stream, [1][n]"""
+        if not (self.wide or self.rat):
             return _ddc.pack(chunk, self.kind)
         a = np.asarray(chunk)
-        if a.ndim == (3 if self.iq else 2):
+        if a.ndim == (2 if a.dtype.kind == "c" else 3 if self.iq else 2):
             if a.shape[0] != 1:
-                raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {self.sample_rate} Hz -- a wide rate takes one stream")
+                raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {self.sample_rate} Hz -- a {'resampled' if self.rat else 'wide'} rate takes one stream")
             a = a[0]
-        a, n = _dw.pack(a, self.kind)
+        a, n = (_dr if self.rat else _dw).pack(a, self.kind)
         return a[None], 1, n
 
     def _push(self, a, real):
         """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples"""
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            self.m_produced = h.ddc_wide_stream_push(a[0]) if self.wide else h.ddc_stream_push(a)
+            self.m_produced = h.ddc_rat_stream_push(a[0]) if self.rat else h.ddc_wide_stream_push(a[0]) if self.wide else h.ddc_stream_push(a)
         if real:
             self.n_pushed += a.shape[1]
+
+    def _outputs(self, n):
+        """12 kHz outputs that n input samples span, rounded up: ceil(n 12000 / sample_rate), in integers"""
+        return -(-int(n) * 12000 // self.sample_rate)
 
     def _note(self, m_avail):
         due = self.sched.due(m_avail)
@@ -183,8 +203,11 @@ class WideIn:
         """End of a finite source: zeros until the outputs of the last real sample exist; the passes those outputs complete"""
         if self.sched is None:
             return
-        m_real = -(-self.n_pushed // self.D)
-        if self.wide:                          # (uint8 has no zero: 128 is half a step, 128 counts of the int16 scale, above it)
+        m_real = self._outputs(self.n_pushed)
+        if self.rat:                           # a tile's worth of rest samples, rounded up
+            n = -(-TILE * self.sample_rate // 12000)
+            zeros = np.full((1, n) + ((2,) if _dr.is_iq(self.kind) else ()), 128 if self.kind == _dr.IQ_U8 else 0, _dr._DTYPE[self.kind])
+        elif self.wide:                          # (uint8 has no zero: 128 is half a step, 128 counts of the int16 scale, above it)
             zeros = np.full((1, TILE * self.D) + ((2,) if self.iq else ()), 128 if self.kind == _dw.IQ_U8 else 0, _dw._DTYPE[self.kind])
         else:
             shape = (self.n_streams, TILE * self.D) + ((2,) if _ddc.is_iq(self.kind) else ())
