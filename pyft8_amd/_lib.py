@@ -266,6 +266,16 @@ def _words(bits):
     return np.array([b & (2 ** 64 - 1) for b in bits], np.uint64), np.array([b >> 64 for b in bits], np.uint64)
 
 
+_PRE_WORD = {"ddc_wide": "wide", "ddc_rat": "rational"}      # a pre-stage stream in messages, by the module of its stage
+_PRE_FIELD = {"ddc_wide": "_wds", "ddc_rat": "_rts"}         # ... and the Handle field that describes it while it is open
+
+
+def _pre_module(name):
+    """pyft8_amd.ddc_wide or pyft8_amd.ddc_rat (they import this module, so they are imported on use)"""
+    import importlib
+    return importlib.import_module("." + name, __package__)
+
+
 class Handle:
     """One HIP device + stream + preallocated workspaces for up to max_frames frames."""
 
@@ -280,7 +290,7 @@ class Handle:
         self.ap_calls = (None, None)
         self._ds = None                    # the open down-converter stream: (kind, n_streams, n_out)
         self._wds = None                   # the open wide stream (ddc_wide_stream_open): (kind, n_out); _ds then describes the stage behind it
-        self._rts = None                   # the open rational stream (ddc_rat_stream_open): (kind, n_out); likewise
+        self._rts = None                   # the open rational stream (ddc_rat_stream_open): (kind, n_out); likewise (_PRE_FIELD: at most one of the two)
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
         if rc != 0:
             raise Ft8rxError(f"ft8rx_create failed ({rc}): {L.ft8rx_last_error(None).decode()}")
@@ -799,141 +809,117 @@ class Handle:
         self._chk(self._L.ft8rx_ddc_stream_close(self._h), "ft8rx_ddc_stream_close")
         self._ds = None
 
-    # ---- wide pre-decimator (ft8rx_ddc_wide*): ONE stream at 240 kHz .. 129.6 MHz in front of the down-converter
-    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
-        """ft8rx_ddc_wide_host / ft8rx_ddc_wide: one stream of `kind` (ddc_wide.REAL_I16 .. ddc_wide.IQ_I8; forms of ddc_wide.pack) at
-        `rate` Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
-        [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        from . import ddc_wide as _dw
-        a, n = _dw.pack(samples, kind)
+    # ---- the input pre-stages, written once: `name` is "ddc_wide" or "ddc_rat", the prefix of the C entries
+    # (ft8rx_<name>*) and of the methods below, and the module that packs the samples of its kinds
+    def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device):
+        a, n = _pre_module(name).pack(samples, kind)
         f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
         if len(f) < 1:
-            raise Ft8rxError("ddc_wide: at least one f_dial_hz")
+            raise Ft8rxError(f"{name}: at least one f_dial_hz")
         fm = np.zeros(len(f), np.float64)
         args = (int(kind), int(rate), n, len(f), f.ctypes.data, float(gain))
         if not (device or want_float):
-            self._chk(self._L.ft8rx_ddc_wide_host(self._h, a.ctypes.data, *args, fm.ctypes.data), "ft8rx_ddc_wide_host")
+            self._chk(getattr(self._L, f"ft8rx_{name}_host")(self._h, a.ctypes.data, *args, fm.ctypes.data), f"ft8rx_{name}_host")
             return fm
         import torch
         dev = torch.device("cuda", self.device)
         d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
         d_f32 = torch.empty((len(f), NSAMP), dtype=torch.float32, device=dev) if want_float else None
         torch.cuda.synchronize(dev)
-        self._chk(self._L.ft8rx_ddc_wide(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc_wide")
+        self._chk(getattr(self._L, f"ft8rx_{name}")(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), f"ft8rx_{name}")
         self.sync()                                          # the tensors may go once the kernels have run
         return (fm, d_f32.cpu().numpy()) if want_float else fm
 
-    def ddc_wide_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
-        """Open the wide stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the first
-        sample that will be pushed, a multiple of 1008 rate / 12000.  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
+    def _pre_open(self, name, kind, rate, f_dial_hz, gain, n_origin, keep_f32):
         f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
         if len(f) < 1:
-            raise Ft8rxError("ddc_wide_stream_open: at least one f_dial_hz")
+            raise Ft8rxError(f"{name}_stream_open: at least one f_dial_hz")
         fm = np.zeros(len(f), np.float64)
-        self._chk(self._L.ft8rx_ddc_wide_stream_open(self._h, int(kind), int(rate), len(f), f.ctypes.data, float(gain), int(n_origin),
-                                                     int(bool(keep_f32)), fm.ctypes.data), "ft8rx_ddc_wide_stream_open")
-        self._wds = (int(kind), len(f))
+        self._chk(getattr(self._L, f"ft8rx_{name}_stream_open")(self._h, int(kind), int(rate), len(f), f.ctypes.data, float(gain), int(n_origin),
+                                                                int(bool(keep_f32)), fm.ctypes.data), f"ft8rx_{name}_stream_open")
+        setattr(self, _PRE_FIELD[name], (int(kind), len(f)))
         self._ds = (3, len(f), len(f))                       # the stage behind: one IQ float32 stream per channel
         return fm
 
-    def ddc_wide_stream_push(self, samples, device=False):
-        """Push the next samples (forms of ddc_wide.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced
-        so far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
-        from . import ddc_wide as _dw
-        if self._wds is None:
-            raise Ft8rxError("ddc_wide_stream_push: no wide stream is open (ddc_wide_stream_open)")
-        a, n = _dw.pack(samples, self._wds[0])
+    def _pre_stream(self, name, what):
+        """the open stream of stage `name`, or the refusal of method `what`"""
+        s = getattr(self, _PRE_FIELD[name])
+        if s is None:
+            raise Ft8rxError(f"{name}_stream_{what}: no {_PRE_WORD[name]} stream is open ({name}_stream_open)")
+        return s
+
+    def _pre_push(self, name, samples, device):
+        a, n = _pre_module(name).pack(samples, self._pre_stream(name, "push")[0])
+        entry = f"ft8rx_{name}_stream_push"
         m = C.c_uint64()
         if not device:
-            self._chk(self._L.ft8rx_ddc_wide_stream_push(self._h, a.ctypes.data, n, 0, C.byref(m)), "ft8rx_ddc_wide_stream_push")
+            self._chk(getattr(self._L, entry)(self._h, a.ctypes.data, n, 0, C.byref(m)), entry)
             return int(m.value)
         import torch
         dev = torch.device("cuda", self.device)
         d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
         torch.cuda.synchronize(dev)
-        self._chk(self._L.ft8rx_ddc_wide_stream_push(self._h, d_in.data_ptr(), n, 1, C.byref(m)), "ft8rx_ddc_wide_stream_push")
+        self._chk(getattr(self._L, entry)(self._h, d_in.data_ptr(), n, 1, C.byref(m)), entry)
         self.sync()
         return int(m.value)
 
-    def ddc_wide_stream_read_mid(self, k_first, n):
-        """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
-        if self._wds is None:
-            raise Ft8rxError("ddc_wide_stream_read_mid: no wide stream is open (ddc_wide_stream_open)")
-        v = np.zeros((self._wds[1], int(n)), np.complex64)
-        self._chk(self._L.ft8rx_ddc_wide_stream_read_mid(self._h, int(k_first), int(n), v.ctypes.data), "ft8rx_ddc_wide_stream_read_mid")
+    def _pre_read_mid(self, name, k_first, n):
+        v = np.zeros((self._pre_stream(name, "read_mid")[1], int(n)), np.complex64)
+        self._chk(getattr(self._L, f"ft8rx_{name}_stream_read_mid")(self._h, int(k_first), int(n), v.ctypes.data), f"ft8rx_{name}_stream_read_mid")
         return v
 
+    def _pre_close(self, name):
+        self._chk(getattr(self._L, f"ft8rx_{name}_stream_close")(self._h), f"ft8rx_{name}_stream_close")
+        setattr(self, _PRE_FIELD[name], None)
+        self._ds = None
+
+    # ---- wide pre-decimator (ft8rx_ddc_wide*, DESIGN.md section 16.2): ONE stream at 240 kHz .. 129.6 MHz in front of the down-converter
+    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
+        """ft8rx_ddc_wide_host / ft8rx_ddc_wide: one stream of `kind` (ddc_wide.REAL_I16 .. ddc_wide.IQ_I8; forms of ddc_wide.pack) at
+        `rate` Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
+        [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
+        return self._pre_oneshot("ddc_wide", samples, kind, rate, f_dial_hz, gain, want_float, device)
+
+    def ddc_wide_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
+        """Open the wide stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the first
+        sample that will be pushed, a multiple of 1008 rate / 12000.  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
+        return self._pre_open("ddc_wide", kind, rate, f_dial_hz, gain, n_origin, keep_f32)
+
+    def ddc_wide_stream_push(self, samples, device=False):
+        """Push the next samples (forms of ddc_wide.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced
+        so far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
+        return self._pre_push("ddc_wide", samples, device)
+
+    def ddc_wide_stream_read_mid(self, k_first, n):
+        """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
+        return self._pre_read_mid("ddc_wide", k_first, n)
+
     def ddc_wide_stream_close(self):
-        self._chk(self._L.ft8rx_ddc_wide_stream_close(self._h), "ft8rx_ddc_wide_stream_close")
-        self._wds = self._ds = None
+        self._pre_close("ddc_wide")
 
     # ---- rational resampler (ft8rx_ddc_rat*, DESIGN.md section 16.3): ONE stream at 44.1 kHz, 2.048 MS/s, ... in front of the down-converter
     def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
         """ft8rx_ddc_rat_host / ft8rx_ddc_rat: one stream of `kind` (ddc_rat.REAL_I16 .. ddc_rat.IQ_I8; forms of ddc_rat.pack) at `rate`
         Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
         [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        from . import ddc_rat as _dr
-        a, n = _dr.pack(samples, kind)
-        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
-        if len(f) < 1:
-            raise Ft8rxError("ddc_rat: at least one f_dial_hz")
-        fm = np.zeros(len(f), np.float64)
-        args = (int(kind), int(rate), n, len(f), f.ctypes.data, float(gain))
-        if not (device or want_float):
-            self._chk(self._L.ft8rx_ddc_rat_host(self._h, a.ctypes.data, *args, fm.ctypes.data), "ft8rx_ddc_rat_host")
-            return fm
-        import torch
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        d_f32 = torch.empty((len(f), NSAMP), dtype=torch.float32, device=dev) if want_float else None
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.ft8rx_ddc_rat(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc_rat")
-        self.sync()                                          # the tensors may go once the kernels have run
-        return (fm, d_f32.cpu().numpy()) if want_float else fm
+        return self._pre_oneshot("ddc_rat", samples, kind, rate, f_dial_hz, gain, want_float, device)
 
     def ddc_rat_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
         """Open the rational stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the
         first sample that will be pushed (ddc_rat.origin_ok).  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
-        f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
-        if len(f) < 1:
-            raise Ft8rxError("ddc_rat_stream_open: at least one f_dial_hz")
-        fm = np.zeros(len(f), np.float64)
-        self._chk(self._L.ft8rx_ddc_rat_stream_open(self._h, int(kind), int(rate), len(f), f.ctypes.data, float(gain), int(n_origin),
-                                                    int(bool(keep_f32)), fm.ctypes.data), "ft8rx_ddc_rat_stream_open")
-        self._rts = (int(kind), len(f))
-        self._ds = (3, len(f), len(f))                       # the stage behind: one IQ float32 stream per channel
-        return fm
+        return self._pre_open("ddc_rat", kind, rate, f_dial_hz, gain, n_origin, keep_f32)
 
     def ddc_rat_stream_push(self, samples, device=False):
         """Push the next samples (forms of ddc_rat.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced so
         far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
-        from . import ddc_rat as _dr
-        if self._rts is None:
-            raise Ft8rxError("ddc_rat_stream_push: no rational stream is open (ddc_rat_stream_open)")
-        a, n = _dr.pack(samples, self._rts[0])
-        m = C.c_uint64()
-        if not device:
-            self._chk(self._L.ft8rx_ddc_rat_stream_push(self._h, a.ctypes.data, n, 0, C.byref(m)), "ft8rx_ddc_rat_stream_push")
-            return int(m.value)
-        import torch
-        dev = torch.device("cuda", self.device)
-        d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.ft8rx_ddc_rat_stream_push(self._h, d_in.data_ptr(), n, 1, C.byref(m)), "ft8rx_ddc_rat_stream_push")
-        self.sync()
-        return int(m.value)
+        return self._pre_push("ddc_rat", samples, device)
 
     def ddc_rat_stream_read_mid(self, k_first, n):
         """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
-        if self._rts is None:
-            raise Ft8rxError("ddc_rat_stream_read_mid: no rational stream is open (ddc_rat_stream_open)")
-        v = np.zeros((self._rts[1], int(n)), np.complex64)
-        self._chk(self._L.ft8rx_ddc_rat_stream_read_mid(self._h, int(k_first), int(n), v.ctypes.data), "ft8rx_ddc_rat_stream_read_mid")
-        return v
+        return self._pre_read_mid("ddc_rat", k_first, n)
 
     def ddc_rat_stream_close(self):
-        self._chk(self._L.ft8rx_ddc_rat_stream_close(self._h), "ft8rx_ddc_rat_stream_close")
-        self._rts = self._ds = None
+        self._pre_close("ddc_rat")
 
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for

@@ -1,7 +1,7 @@
-// ddc_rat_ring.hpp -- the index arithmetic of the rational resampler (ft8rx_ddc_rat*): the plan of a rate, the
-// inputs an intermediate sample reads, which intermediate samples a push completes, where a chunk lands in the history ring, how many
-// outputs a tile of either kernel regime holds.  Pure functions of 64-bit indices.  No HIP: compiles with plain g++
-// (tests/ddc_rat_ring_check.cpp checks it under the host sanitizers).
+// ddc_rat_ring.hpp -- what is the rational resampler's own in its index arithmetic (ft8rx_ddc_rat*): the plan of a
+// rate, the limits, the inputs an intermediate sample reads, the history the stream keeps, how many outputs a tile of either kernel
+// regime holds.  Which intermediate samples a push completes, the origin and the history ring are ddc_pre_ring.hpp's.  Pure functions
+// of 64-bit indices.  No HIP: compiles with plain g++ (tests/ddc_rat_ring_check.cpp checks it under the host sanitizers).
 //
 // Indices are ABSOLUTE: input sample n counts from index 0 of the sample clock; intermediate sample k sits at input time k M / L, with
 // rate_mid = rate L / M.  With the prototype h of N taps (odd), C = (N - 1) / 2 and t_k = k M + C,
@@ -65,33 +65,13 @@ constexpr int64_t tile_outputs(int64_t N, int64_t L, int64_t M) {
 // less than P back from there
 constexpr int64_t history(int64_t N, int64_t L) { return phase_taps(N, L); }
 
-// is n_origin a valid origin, and its intermediate sample
-inline bool origin_ok(int64_t n_origin, int64_t rate_mid, int64_t L, int64_t M) {
-    if (n_origin < 0 || n_origin > N_MAX || (n_origin * L) % M != 0) return false;
-    return (n_origin * L / M) % (1008 * (rate_mid / 12000)) == 0;
-}
-inline int64_t k_origin(int64_t n_origin, int64_t L, int64_t M) { return n_origin * L / M; }
-
-// absolute index of the first intermediate sample that is NOT complete when the inputs [.., n_end) exist: k is complete iff its last
-// input, (k M + C) / L, is below n_end, i.e. k M + C < n_end L.  Never below the origin's sample.
-inline int64_t mid_done(int64_t n_origin, int64_t n_end, int64_t N, int64_t L, int64_t M) {
-    const int64_t k0 = k_origin(n_origin, L, M), have = n_end * L - (N - 1) / 2 - 1;
-    if (have < 0) return k0;
-    const int64_t k = have / M + 1;
-    return k > k0 ? k : k0;
-}
-
-// intermediate samples of a one-shot call on n_samples inputs (zero outside): those whose first tap, h[0] at input (t_k - N + 1) / L,
-// can still meet a non-zero input, k M + C - (N - 1) <= (n_samples - 1) L; at most `cap` (15 s at the intermediate rate), at least one
-inline int64_t mid_count(int64_t n_samples, int64_t N, int64_t L, int64_t M, int64_t cap) {
-    if (n_samples < 1) return 1;
-    const int64_t k = ((n_samples - 1) * L + (N - 1) / 2) / M + 1;
-    return k < cap ? k : cap;
-}
-
-// position of absolute input n in the history ring of H samples (n >= n_origin), and what a push keeps: as the wide path
-inline int64_t hist_pos(int64_t n, int64_t n_origin, int64_t H) { return ddcwide::hist_pos(n, n_origin, H); }
-using Keep = ddcwide::Keep;
-inline Keep keep(int64_t pushed, int64_t n_new, int64_t H) { return ddcwide::keep(pushed, n_new, H); }
+// the shared arithmetic under this stage's names, the origin with this stage's bound
+inline bool origin_ok(int64_t n_origin, int64_t rate_mid, int64_t L, int64_t M) { return ddcpre::origin_ok(n_origin, N_MAX, rate_mid, L, M); }
+using ddcpre::k_origin;
+using ddcpre::mid_done;
+using ddcpre::mid_count;
+using ddcpre::hist_pos;
+using ddcpre::Keep;
+using ddcpre::keep;
 
 }  // namespace ddcrat

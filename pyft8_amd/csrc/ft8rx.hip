@@ -38,6 +38,8 @@
 #include <map>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/ft8rx.h"
 #include "ft8_dev.h"
@@ -136,6 +138,22 @@ static ApCalls ap_calls_off() { ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = 
 #define LADDER_GRID_CAP (4 * 256 * 32)
 #endif
 
+// The front stage of a rate, filled from the plan by pre_plan: ONE stream at `rate` -> per channel IQ float32 at
+// rate_mid = rate L / M through a per-channel table of the n_taps prototype taps.  The wide pre-decimator is L = 1, M = R0.
+enum { PRE_WIDE = 0, PRE_RAT = 1 };
+static const char* const PRE_NAME[2] = {"wide", "rational"};                       // in messages
+static const char* const PRE_ENTRY[2] = {"ft8rx_ddc_wide", "ft8rx_ddc_rat"};
+struct PreStage {
+    int which = PRE_WIDE;
+    int32_t rate = 0, rate_mid = 0;              // rate_mid = 0: the rate is refused
+    int L = 1, M = 1, n_taps = 0;
+    int P = 0, H = 0, tk = 0; bool lane = false; // taps per phase (rational), history of a stream, outputs per tile, the rational kernel's regime
+    const std::vector<float>* taps = nullptr;    // the prototype (pre_taps); nullptr: the rate is refused
+    uint32_t kinds = 0;                          // bit k: input kind k is taken
+    int64_t n_max = 0, end_max = 0;              // bound of an origin, and of the index a stream may reach
+    const char *name = "", *entry = "";          // PRE_NAME, PRE_ENTRY of `which`
+};
+
 struct ft8rx_handle {
     ft8rx_config cfg = {};
     int device = 0, max_frames = 0;
@@ -214,32 +232,23 @@ struct ft8rx_handle {
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
         hipEvent_t ev = nullptr;
     } ds;
-    // wide pre-decimator (ft8rx_ddc_wide*, kernels/ddc_wide.hpp).  One-shot: the channels' tap tables
-    // [n_out][n_taps] and frequency words, and the intermediate samples [n_out][n_mid], each grown when a call needs more.
-    void* d_wide_tab = nullptr; size_t wide_tab_cap = 0; void* d_wide_w0 = nullptr; size_t wide_w0_cap = 0;
-    void* d_wide_mid = nullptr; size_t wide_mid_cap = 0;
-    // ... and its stream: everything is allocated by open and released by close (or destroy).  d_hist: the newest H input samples in
-    // their own kind (sample n at (n - n_origin) mod H); d_chunk / h_stage: one second of input, device / page-locked; d_mid:
-    // [n_out][rate_mid], what one push makes; the down-converter behind it is the stream `ds` above, fed on the device.
-    // n_origin, pushed, k_done: absolute index of the first sample, samples pushed, first intermediate sample not made yet.
-    struct WideStream {
-        bool open = false; int kind = 0, n_out = 0, n_taps = 0, R0 = 0, H = 0; int32_t rate = 0, rate_mid = 0; float g0 = 0.0f;
+    // input pre-stages (ft8rx_ddc_wide*, ft8rx_ddc_rat*; kernels/ddc_wide.hpp, kernels/ddc_rat.hpp).  One-shot: the
+    // channels' tap tables and frequency words, and the intermediate samples [n_out][n_mid], each grown when a call needs more (one
+    // call at a time uses them, whichever stage it runs).
+    void* d_pre_tab = nullptr; size_t pre_tab_cap = 0; void* d_pre_w0 = nullptr; size_t pre_w0_cap = 0;
+    void* d_pre_mid = nullptr; size_t pre_mid_cap = 0;
+    // ... and their stream, at most one of either stage: everything is allocated by open and released by close (or destroy).  st: the
+    // stage of the open stream; d_hist: the newest st.H input samples in their own kind (sample n at (n - n_origin) mod H); d_chunk /
+    // h_stage: one second of input, device / page-locked; d_mid: [n_out][rate_mid], what one push makes; the down-converter behind it
+    // is the stream `ds` above, fed on the device.  n_origin, pushed, k_done: absolute index of the first sample, samples pushed, first
+    // intermediate sample not made yet.
+    struct PreStream {
+        bool open = false; PreStage st; int kind = 0, n_out = 0; float g0 = 0.0f;
         int64_t n_origin = 0, pushed = 0, k_done = 0;
         char* d_hist = nullptr; char* d_chunk = nullptr; char* h_stage = nullptr; float2* d_mid = nullptr; float2* d_tab = nullptr;
         uint32_t* d_w0 = nullptr;
         hipEvent_t ev = nullptr;
-    } wds;
-    // rational resampler (ft8rx_ddc_rat*, kernels/ddc_rat.hpp).  The one-shot uses the three buffers of the wide
-    // one-shot above (tables, frequency words, intermediate samples: one call at a time uses them).  Its stream, as the wide stream's:
-    // everything is allocated by open and released by close (or destroy); d_hist: the newest H input samples in their own kind; d_mid:
-    // [n_out][rate_mid]; the down-converter behind it is the stream `ds`.
-    struct RatStream {
-        bool open = false, lane = false; int kind = 0, n_out = 0, n_taps = 0, L = 0, M = 0, P = 0, H = 0; int32_t rate = 0, rate_mid = 0; float g0 = 0.0f;
-        int64_t n_origin = 0, pushed = 0, k_done = 0;
-        char* d_hist = nullptr; char* d_chunk = nullptr; char* h_stage = nullptr; float2* d_mid = nullptr; float2* d_tab = nullptr;
-        uint32_t* d_w0 = nullptr;
-        hipEvent_t ev = nullptr;
-    } rts;
+    } ps;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -296,6 +305,9 @@ static hipStream_t pool_sub(int device, int i) {
     if (!P.sub[i] && hipStreamCreateWithFlags(&P.sub[i], hipStreamNonBlocking) != hipSuccess) P.sub[i] = nullptr;
     return P.sub[i];
 }
+
+// f(std::true_type()) or f(std::false_type()): a run-time bool as a template argument of what f launches
+template <class F> static void with_bool(bool b, F f) { if (b) f(std::true_type()); else f(std::false_type()); }
 
 template <typename T> static int dalloc(ft8rx_handle* h, T** p, size_t n) {
     void* q = nullptr;
@@ -487,8 +499,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
     if (h->ds.ev) hipEventDestroy(h->ds.ev);
-    if (h->wds.ev) hipEventDestroy(h->wds.ev);
-    if (h->rts.ev) hipEventDestroy(h->rts.ev);
+    if (h->ps.ev) hipEventDestroy(h->ps.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -1452,33 +1463,6 @@ int ft8rx_ddc(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, int 
     return ddc_launch(h, D, d_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
 }
 
-int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
-                   int n_out, const int32_t* src, const double* f_dial_hz, float gain, double* f_mixed_hz) {
-    if (!h) return -1;
-    const int D = ddc_check(h, "ft8rx_ddc_host", kind, rate_hz, n_streams, stream_stride, n_samples, n_out, src, f_dial_hz, gain);
-    if (D < 0) return -1;
-    if (!in) { set_err(h, "ft8rx_ddc_host: in is NULL"); return -1; }
-    ENTER(h);
-    if (ddc_workspaces(h) || need_staging(h)) return -2;
-    const size_t bytes = (size_t)n_streams * (size_t)stream_stride * DDC_SAMPLE_BYTES[kind];
-    if (h->ddc_in_cap < bytes) {                         // first use, or a larger call: nothing of the handle reads the old buffer any more
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 256);
-        if (e != hipSuccess) { set_err(h, "ft8rx_ddc_host: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return -2; }
-        if (h->d_ddc_in) {
-            for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == h->d_ddc_in) { h->allocs.erase(h->allocs.begin() + i); break; }
-            hipFree(h->d_ddc_in);
-        }
-        h->allocs.push_back(p); h->d_ddc_in = p; h->ddc_in_cap = bytes ? bytes : 256;
-    }
-    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = ddc_launch(h, D, h->d_ddc_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ---- streaming down-converter (DESIGN.md section 16.1).  The index arithmetic is ddc_ring.hpp's.
 // hand one allocation of the handle back (ft8rx_ddc_stream_close; everything else lives until ft8rx_destroy)
 static void release_dev(ft8rx_handle* h, void* p) {
     if (!p) return;
@@ -1490,6 +1474,35 @@ static void release_host(ft8rx_handle* h, void* p) {
     for (size_t i = 0; i < h->pinned.size(); i++) if (h->pinned[i] == p) { h->pinned.erase(h->pinned.begin() + i); break; }
     hipHostFree(p);
 }
+// a handle-owned device buffer that only grows: first use, or a larger call (nothing of the handle reads the old one any more)
+static int grow_dev(ft8rx_handle* h, const char* who, void** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes && *p) return 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes ? bytes : 256);
+    if (e != hipSuccess) { set_err(h, "%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e)); return -2; }
+    release_dev(h, *p);
+    h->allocs.push_back(q); *p = q; *cap = bytes ? bytes : 256;
+    return 0;
+}
+
+int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
+                   int n_out, const int32_t* src, const double* f_dial_hz, float gain, double* f_mixed_hz) {
+    if (!h) return -1;
+    const int D = ddc_check(h, "ft8rx_ddc_host", kind, rate_hz, n_streams, stream_stride, n_samples, n_out, src, f_dial_hz, gain);
+    if (D < 0) return -1;
+    if (!in) { set_err(h, "ft8rx_ddc_host: in is NULL"); return -1; }
+    ENTER(h);
+    if (ddc_workspaces(h) || need_staging(h)) return -2;
+    const size_t bytes = (size_t)n_streams * (size_t)stream_stride * DDC_SAMPLE_BYTES[kind];
+    if (grow_dev(h, "ft8rx_ddc_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;
+    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = ddc_launch(h, D, h->d_ddc_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- streaming down-converter (DESIGN.md section 16.1).  The index arithmetic is ddc_ring.hpp's.
 static void ddc_stream_release(ft8rx_handle* h) {
     ft8rx_handle::DdcStream& s = h->ds;
     release_dev(h, s.d_in); release_dev(h, s.d_out); release_dev(h, s.d_f32); release_dev(h, s.d_outs); release_host(h, s.h_stage);
@@ -1498,16 +1511,27 @@ static void ddc_stream_release(ft8rx_handle* h) {
     s.ev = ev;
 }
 
-// (the bodies of open and push: the wide stream, DESIGN.md section 16.2, opens and feeds the stream behind it through them)
+// (the bodies of open and push: a pre-stage stream, DESIGN.md section 16.4, opens and feeds the stream behind it through them)
 static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
                            float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz);
 static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
 
+// while a pre-stage stream (section 16.4) is open, `ds` is the stage behind it: the plain entries and the one-shots refuse
+static int pre_refuse_open(ft8rx_handle* h, const char* who) {
+    if (!h->ps.open) return 0;
+    set_err(h, "%s: a %s stream is open on this handle (%s_stream_close)", who, h->ps.st.name, h->ps.st.entry);
+    return -1;
+}
+static int pre_refuse_other(ft8rx_handle* h, const char* who, const char* verb) {
+    if (!h->ps.open) return 0;
+    set_err(h, "%s: the open stream is a %s stream (%s_stream_%s)", who, h->ps.st.name, h->ps.st.entry, verb);
+    return -1;
+}
+
 int ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
                           float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
     if (!h) return -1;
-    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_open: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)"); return -1; }
-    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_open: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)"); return -1; }
+    if (pre_refuse_open(h, "ft8rx_ddc_stream_open")) return -1;
     return ddc_stream_open(h, kind, rate_hz, n_streams, n_out, src, f_dial_hz, gain, n_origin, keep_f32, f_mixed_hz);
 }
 static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src, const double* f_dial_hz,
@@ -1547,8 +1571,7 @@ static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_str
 
 int ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
     if (!h) return -1;
-    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_push: the open stream is a wide stream (ft8rx_ddc_wide_stream_push)"); return -1; }
-    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_push: the open stream is a rational stream (ft8rx_ddc_rat_stream_push)"); return -1; }
+    if (pre_refuse_other(h, "ft8rx_ddc_stream_push", "push")) return -1;
     return ddc_stream_push(h, in, n_new, on_device, m_produced);
 }
 static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
@@ -1652,8 +1675,7 @@ int ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_
 
 int ft8rx_ddc_stream_close(ft8rx_handle* h) {
     if (!h) return -1;
-    if (h->wds.open) { set_err(h, "ft8rx_ddc_stream_close: the open stream is a wide stream (ft8rx_ddc_wide_stream_close)"); return -1; }
-    if (h->rts.open) { set_err(h, "ft8rx_ddc_stream_close: the open stream is a rational stream (ft8rx_ddc_rat_stream_close)"); return -1; }
+    if (pre_refuse_other(h, "ft8rx_ddc_stream_close", "close")) return -1;
     if (!h->ds.open) { set_err(h, "ft8rx_ddc_stream_close: no stream is open"); return -1; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the rings
@@ -1661,8 +1683,9 @@ int ft8rx_ddc_stream_close(ft8rx_handle* h) {
     return 0;
 }
 
-// ---------------------------------------------------------------------------- wide pre-decimator
-// The kernel's tile and the limits, against the pure index arithmetic of ddc_wide_ring.hpp
+// ---------------------------------------------------------------------------- input pre-stages (DESIGN.md sections 16.2 - 16.4)
+// The wide pre-decimator (ft8rx_ddc_wide*) and the rational resampler (ft8rx_ddc_rat*) share one host path: a PreStage says what differs.
+// The kernels' tiles and the limits, against the pure index arithmetic of ddc_wide_ring.hpp and ddc_rat_ring.hpp
 static_assert(ddcwide::PIECE == DDW_JP && ddcwide::LDS_SAMPLES == DDW_LS && ddcwide::TILE_MAX == DDW_TK && DDW_JP % 64 == 0 && DDW_TK == 4 * (DDW_NT / 64),
               "ddc_wide_ring.hpp: the tile of kernels/ddc_wide.hpp");
 constexpr bool ddw_tiles_fit() {
@@ -1674,302 +1697,6 @@ static_assert(ddw_tiles_fit(), "ddc_wide_ring.hpp: a tile's input under one piec
 static_assert(ddcwide::plan(240000).rate_mid == 48000 && ddcwide::plan(240000).R0 == 5 && ddcwide::plan(64800000).rate_mid == 96000 &&
               ddcwide::plan(129600000).R0 == 675 && ddcwide::plan(192000).rate_mid == 0 && ddcwide::plan(129648000).rate_mid == 0, "ddc_wide_ring.hpp: plan");
 static_assert(sizeof(float2) * DDW_LS <= 64 * 1024, "the LDS image is static shared memory");
-
-static const size_t DDW_SAMPLE_BYTES[4] = {2, 4, 2, 2};     // FT8RX_WIDE_REAL_I16, _IQ_I16, _IQ_U8, _IQ_I8
-static bool ddw_is_iq(int kind) { return kind != FT8RX_WIDE_REAL_I16; }
-
-// h0 of a rate: the recipe of ddc_design at fs = rate, pass 3200 Hz, stop rate_mid - 3200 Hz, 85 dB; designed once per rate
-static const std::vector<float>* ddw_taps(int32_t rate_hz) {
-    const ddcwide::Plan p = ddcwide::plan(rate_hz);
-    if (!p.rate_mid) return nullptr;
-    static std::mutex mu;
-    static std::map<int32_t, std::vector<float>> designed;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = designed.find(rate_hz);
-    if (it == designed.end()) it = designed.emplace(rate_hz, ddc_design(3200.0, (double)p.rate_mid - 3200.0, 85.0, (double)rate_hz)).first;
-    return (int64_t)it->second.size() <= ddcwide::MAX_TAPS ? &it->second : nullptr;
-}
-
-int ft8rx_ddc_wide_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* r0) {
-    const ddcwide::Plan p = ddcwide::plan(rate_hz);
-    if (!p.rate_mid) return -1;
-    if (rate_mid_hz) *rate_mid_hz = (int32_t)p.rate_mid;
-    if (r0) *r0 = (int32_t)p.R0;
-    return 0;
-}
-
-int ft8rx_ddc_wide_taps(int32_t rate_hz, float* taps, int cap) {
-    const std::vector<float>* t = ddw_taps(rate_hz);
-    if (!t) return -1;
-    for (int i = 0; taps && i < cap && i < (int)t->size(); i++) taps[i] = (*t)[i];
-    return (int)t->size();
-}
-
-// the argument checks every entry shares -> the plan's rate_mid, or -1 with the error text
-static int ddw_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
-    if (kind < FT8RX_WIDE_REAL_I16 || kind > FT8RX_WIDE_IQ_I8) { set_err(h, "%s: kind %d is not one of FT8RX_WIDE_REAL_I16 .. FT8RX_WIDE_IQ_I8", who, kind); return -1; }
-    if (!ddcwide::plan(rate_hz).rate_mid || !ddw_taps(rate_hz)) {
-        set_err(h, "%s: rate_hz %d is not a multiple of 48000 in [240000, 129600000] with rate_hz / rate_mid <= 1350", who, (int)rate_hz); return -1;
-    }
-    if (n_out < 1 || n_out > h->max_frames || n_out > 65535) { set_err(h, "%s: n_out %d outside [1, %d] (max_frames; at most 65535)", who, n_out, h->max_frames); return -1; }
-    if (!f_dial_hz) { set_err(h, "%s: f_dial_hz is NULL", who); return -1; }
-    for (int j = 0; j < n_out; j++)
-        if (!(f_dial_hz[j] >= -0.5 * rate_hz && f_dial_hz[j] < 0.5 * rate_hz)) { set_err(h, "%s: f_dial_hz[%d] = %g outside [-rate_hz / 2, rate_hz / 2)", who, j, f_dial_hz[j]); return -1; }
-    if (!(fabsf(gain) <= 3.0e38f)) { set_err(h, "%s: gain is not finite", who); return -1; }
-    return (int)ddcwide::plan(rate_hz).rate_mid;
-}
-
-// per channel: the frequency word w0, the table W[j] = h0[j] e^{-2 pi i (w0 j mod 2^32) / 2^32} (double, rounded once), the dial left for
-// the stage behind (f_dial - f0, about -3000 Hz) and f0 itself, both taken into [-rate / 2, rate / 2)
-static void ddw_tables(int32_t rate_hz, const std::vector<float>& h0, int n_out, const double* f_dial_hz, std::vector<float2>& tab, std::vector<uint32_t>& w0s,
-                       std::vector<double>& dial_mid, std::vector<double>& f0s) {
-    const size_t N = h0.size();
-    tab.resize((size_t)n_out * N); w0s.resize((size_t)n_out); dial_mid.resize((size_t)n_out); f0s.resize((size_t)n_out);
-    for (int c = 0; c < n_out; c++) {
-        const double r = nearbyint((f_dial_hz[c] + 3000.0) / (double)rate_hz * 4294967296.0);
-        const uint32_t w0 = (uint32_t)((long long)r & 0xffffffffLL);
-        double f0 = (double)w0 * (double)rate_hz / 4294967296.0;
-        if (f0 >= 0.5 * rate_hz) f0 -= (double)rate_hz;
-        double d = f_dial_hz[c] - f0;
-        d -= (double)rate_hz * nearbyint(d / (double)rate_hz);
-        w0s[c] = w0; f0s[c] = f0; dial_mid[c] = d;
-        for (size_t j = 0; j < N; j++) {
-            const double a = -(double)(uint32_t)(w0 * (uint32_t)j) * (M_PI / 2147483648.0);
-            tab[(size_t)c * N + j] = make_float2((float)((double)h0[j] * cos(a)), (float)((double)h0[j] * sin(a)));
-        }
-    }
-}
-// what the caller sees as mixed: f0 + the dial the stage behind really mixed, in [-rate / 2, rate / 2)
-static void ddw_mixed(int32_t rate_hz, int n_out, const std::vector<double>& f0s, double* f_mixed_hz) {
-    for (int c = 0; f_mixed_hz && c < n_out; c++) {
-        double f = f0s[c] + f_mixed_hz[c];
-        if (f >= 0.5 * rate_hz) f -= (double)rate_hz;
-        if (f < -0.5 * rate_hz) f += (double)rate_hz;
-        f_mixed_hz[c] = f;
-    }
-}
-
-// a handle-owned device buffer that only grows: first use, or a larger call (nothing of the handle reads the old one any more)
-static int ddw_reserve(ft8rx_handle* h, const char* who, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return 0;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes ? bytes : 256);
-    if (e != hipSuccess) { set_err(h, "%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e)); return -2; }
-    if (*p) {
-        for (size_t i = 0; i < h->allocs.size(); i++) if (h->allocs[i] == *p) { h->allocs.erase(h->allocs.begin() + i); break; }
-        hipFree(*p);
-    }
-    h->allocs.push_back(q); *p = q; *cap = bytes ? bytes : 256;
-    return 0;
-}
-
-// the one-shot behind its checks: pre-stage into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
-static int ddw_run(ft8rx_handle* h, const char* who, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz,
-                   float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
-    const ddcwide::Plan p = ddcwide::plan(rate_hz);
-    const std::vector<float>& h0 = *ddw_taps(rate_hz);
-    const int D = (int)(p.rate_mid / 12000), n_taps = (int)h0.size(), tk = (int)ddcwide::tile_outputs(p.R0);
-    const int64_t n_mid = ddcwide::mid_count((int64_t)n_samples, n_taps, p.R0, (int64_t)FT8RX_NSAMP * D);
-    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s, fm((size_t)n_out);
-    ddw_tables(rate_hz, h0, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
-    if (ddw_reserve(h, who, &h->d_wide_tab, &h->wide_tab_cap, sizeof(float2) * tab.size()) ||
-        ddw_reserve(h, who, &h->d_wide_w0, &h->wide_w0_cap, sizeof(uint32_t) * w0s.size()) ||
-        ddw_reserve(h, who, &h->d_wide_mid, &h->wide_mid_cap, sizeof(float2) * (size_t)n_out * (size_t)n_mid)) return -2;
-    // the tables are pageable vectors of this call, and an earlier call's kernel may still read the device copies
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_wide_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_wide_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice));
-    const dim3 grid((unsigned)((n_mid + tk - 1) / tk), (unsigned)n_out);
-    const float g0 = ddw_is_iq(kind) ? 1.0f : 2.0f;
-    if (ddw_is_iq(kind))
-        k_ddc_pre<true><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, (const uint32_t*)h->d_wide_w0, n_taps,
-                                                        (int)p.R0, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid);
-    else
-        k_ddc_pre<false><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, (const uint32_t*)h->d_wide_w0, n_taps,
-                                                         (int)p.R0, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid);
-    HIPCHK(h, hipGetLastError());
-    std::vector<int32_t> src((size_t)n_out);
-    for (int j = 0; j < n_out; j++) src[j] = j;
-    if (const int rc = ddc_launch(h, D, h->d_wide_mid, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), dial_mid.data(),
-                                  gain, d_audio, d_audio_f32, fm.data())) return rc;
-    if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz); }
-    return 0;
-}
-
-static int ddw_check_oneshot(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain) {
-    if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
-    if (n_samples > (uint64_t)15 * (uint64_t)rate_hz) { set_err(h, "%s: n_samples %llu > %llu (15 s at rate_hz)", who, (unsigned long long)n_samples, 15ull * (unsigned long long)rate_hz); return -1; }
-    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
-    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
-    return 0;
-}
-
-int ft8rx_ddc_wide(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
-                   int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
-    if (!h) return -1;
-    if (ddw_check_oneshot(h, "ft8rx_ddc_wide", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
-    if (!d_in || ((uintptr_t)d_in % DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16]) != 0) { set_err(h, "ft8rx_ddc_wide: d_in is NULL or not aligned to a sample"); return -1; }
-    ENTER(h);
-    if (ddc_workspaces(h)) return -2;
-    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
-    return ddw_run(h, "ft8rx_ddc_wide", d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
-}
-
-int ft8rx_ddc_wide_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
-                        double* f_mixed_hz) {
-    if (!h) return -1;
-    if (ddw_check_oneshot(h, "ft8rx_ddc_wide_host", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
-    if (!in) { set_err(h, "ft8rx_ddc_wide_host: in is NULL"); return -1; }
-    ENTER(h);
-    if (ddc_workspaces(h) || need_staging(h)) return -2;
-    const size_t bytes = (size_t)n_samples * DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16];
-    if (ddw_reserve(h, "ft8rx_ddc_wide_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
-    if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = ddw_run(h, "ft8rx_ddc_wide_host", h->d_ddc_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ---- the wide stream: the pre-stage on a continuous stream, in front of the streaming down-converter (section 16.1), which it opens,
-// feeds on the device and closes.  The index arithmetic is ddc_wide_ring.hpp's.
-static void ddw_stream_release(ft8rx_handle* h) {
-    ft8rx_handle::WideStream& s = h->wds;
-    release_dev(h, s.d_hist); release_dev(h, s.d_chunk); release_dev(h, s.d_mid); release_dev(h, s.d_tab); release_dev(h, s.d_w0); release_host(h, s.h_stage);
-    const hipEvent_t ev = s.ev;
-    s = ft8rx_handle::WideStream();
-    s.ev = ev;
-}
-
-int ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
-                               int keep_f32, double* f_mixed_hz) {
-    if (!h) return -1;
-    const char* who = "ft8rx_ddc_wide_stream_open";
-    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle already (ft8rx_ddc_wide_stream_close)", who); return -1; }
-    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
-    if (h->ds.open) { set_err(h, "%s: a stream is open on this handle already (ft8rx_ddc_stream_close)", who); return -1; }
-    if (ddw_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
-    const uint64_t grid = (uint64_t)DDC_TO * ((uint64_t)rate_hz / 12000);
-    if (n_origin % grid != 0 || n_origin > ((uint64_t)1 << 62)) {
-        set_err(h, "%s: n_origin %llu is not a multiple of %llu (1008 rate_hz / 12000)", who, (unsigned long long)n_origin, (unsigned long long)grid); return -1;
-    }
-    ENTER(h);
-    const ddcwide::Plan p = ddcwide::plan(rate_hz);
-    const std::vector<float>& h0 = *ddw_taps(rate_hz);
-    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s;
-    ddw_tables(rate_hz, h0, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
-    std::vector<int32_t> src((size_t)n_out);
-    for (int j = 0; j < n_out; j++) src[j] = j;
-    // the stage behind: n_out IQ float32 streams at rate_mid, one channel each, from the same origin
-    if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, n_out, n_out, src.data(), dial_mid.data(), gain, n_origin / (uint64_t)p.R0,
-                                       keep_f32, f_mixed_hz)) return rc;
-    ft8rx_handle::WideStream& s = h->wds;
-    const size_t sb = DDW_SAMPLE_BYTES[kind - FT8RX_WIDE_REAL_I16];
-    const int H = (int)ddcwide::history((int64_t)h0.size(), p.R0);
-    int rc = 0;
-    hipError_t e = hipSuccess;
-    if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
-    if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
-    if (!rc) rc = dalloc(h, &s.d_hist, (size_t)H * sb);
-    if (!rc) rc = dalloc(h, &s.d_chunk, (size_t)rate_hz * sb);
-    if (!rc) rc = dalloc(h, &s.d_mid, (size_t)n_out * (size_t)p.rate_mid);
-    if (!rc) rc = dalloc(h, &s.d_tab, tab.size());
-    if (!rc) rc = dalloc(h, &s.d_w0, w0s.size());
-    if (!rc) rc = halloc(h, &s.h_stage, (size_t)rate_hz * sb);
-    if (!rc) {
-        e = hipMemcpyAsync(s.d_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.d_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s.d_hist, 0, (size_t)H * sb, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the tables are pageable vectors of this call
-        if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
-    }
-    if (rc) { ddw_stream_release(h); ddc_stream_release(h); return -2; }
-    ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz);
-    s.kind = kind; s.n_out = n_out; s.n_taps = (int)h0.size(); s.R0 = (int)p.R0; s.H = H; s.rate = rate_hz; s.rate_mid = (int32_t)p.rate_mid;
-    s.g0 = ddw_is_iq(kind) ? 1.0f : 2.0f;
-    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = s.n_origin / s.R0;
-    s.open = true;
-    return 0;
-}
-
-int ft8rx_ddc_wide_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
-    if (!h) return -1;
-    ft8rx_handle::WideStream& s = h->wds;
-    if (!s.open) { set_err(h, "ft8rx_ddc_wide_stream_push: no wide stream is open (ft8rx_ddc_wide_stream_open)"); return -1; }
-    if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_wide_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
-    const size_t sb = DDW_SAMPLE_BYTES[s.kind - FT8RX_WIDE_REAL_I16];
-    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_wide_stream_push: in is NULL or not aligned to a sample"); return -1; }
-    // (no ENTER: a push touches the streams' own buffers only, on the main stream; batches in flight read none of them)
-    HIPCHK(h, hipSetDevice(h->device));
-    const char* chunk = (const char*)in;
-    if (!on_device) {                                    // through the page-locked buffer, once the previous push's copy has left it
-        HIPCHK(h, hipEventSynchronize(s.ev));
-        memcpy(s.h_stage, in, (size_t)n_new * sb);
-        HIPCHK(h, hipMemcpyAsync(s.d_chunk, s.h_stage, (size_t)n_new * sb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipEventRecord(s.ev, h->stream));
-        chunk = s.d_chunk;
-    }
-    const int64_t n_start = s.n_origin + s.pushed, n_end = n_start + (int64_t)n_new;
-    const int64_t k_new = ddcwide::mid_done(s.n_origin, n_end, s.n_taps, s.R0);
-    const int n_k = (int)(k_new - s.k_done);             // at most rate_mid: a push is at most a second
-    if (n_k > 0) {
-        const int tk = (int)ddcwide::tile_outputs(s.R0);
-        const dim3 grid((unsigned)((n_k + tk - 1) / tk), (unsigned)s.n_out);
-        const int p_last = s.pushed ? (int)ddcwide::hist_pos(n_start - 1, s.n_origin, s.H) : 0;
-#define DDW_GO(IQ) k_ddc_pre_stream<IQ><<<grid, DDW_NT, 0, h->stream>>>(s.d_hist, s.H, p_last, chunk, s.kind, (long long)s.n_origin, (long long)n_start, \
-                       (long long)n_end, s.d_tab, s.d_w0, s.n_taps, s.R0, tk, s.g0, (long long)s.k_done, n_k, s.d_mid)
-        if (ddw_is_iq(s.kind)) DDW_GO(true); else DDW_GO(false);
-#undef DDW_GO
-        HIPCHK(h, hipGetLastError());
-    }
-    // the chunk's last H samples into the history, behind the kernel that read the old ones
-    const ddcwide::Keep kp = ddcwide::keep(s.pushed, (int64_t)n_new, s.H);
-    HIPCHK(h, hipMemcpyAsync(s.d_hist + (size_t)kp.pos * sb, chunk + (size_t)kp.skip * sb, (size_t)kp.first * sb, hipMemcpyDeviceToDevice, h->stream));
-    if (kp.second) HIPCHK(h, hipMemcpyAsync(s.d_hist, chunk + (size_t)(kp.skip + kp.first) * sb, (size_t)kp.second * sb, hipMemcpyDeviceToDevice, h->stream));
-    s.pushed += (int64_t)n_new;
-    if (n_k > 0) {
-        s.k_done = k_new;
-        return ddc_stream_push(h, s.d_mid, (uint64_t)n_k, 1, m_produced);
-    }
-    if (m_produced) *m_produced = (uint64_t)(h->ds.tiles * DDC_TO);
-    return 0;
-}
-
-int ft8rx_ddc_wide_stream_read_mid(ft8rx_handle* h, uint64_t k_first_u, int n, float* mid) {
-    if (!h) return -1;
-    const ft8rx_handle::WideStream& s = h->wds;
-    if (!s.open) { set_err(h, "ft8rx_ddc_wide_stream_read_mid: no wide stream is open (ft8rx_ddc_wide_stream_open)"); return -1; }
-    const int64_t k_first = (int64_t)k_first_u, k_origin = s.n_origin / s.R0, cap = h->ds.cap;
-    if (n < 1 || !mid || k_first < k_origin || k_first + n > s.k_done || k_first < s.k_done - cap) {
-        set_err(h, "ft8rx_ddc_wide_stream_read_mid: intermediate samples [%lld, %lld) are not all held (held: %lld .. %lld)", (long long)k_first,
-                (long long)(k_first + n), (long long)(s.k_done - cap > k_origin ? s.k_done - cap : k_origin), (long long)s.k_done);
-        return -1;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    // the stage behind keeps the newest `cap` samples of every channel: sample k at (k - k_origin) & (cap - 1)
-    const int64_t pos = (k_first - k_origin) & (cap - 1), first = n < cap - pos ? n : cap - pos;
-    const float2* ring = (const float2*)h->ds.d_in;
-    float2* out = (float2*)mid;
-    for (int j = 0; j < s.n_out; j++) {
-        HIPCHK(h, hipMemcpy(out + (size_t)j * n, ring + (size_t)j * cap + pos, sizeof(float2) * (size_t)first, hipMemcpyDeviceToHost));
-        if (first < n) HIPCHK(h, hipMemcpy(out + (size_t)j * n + first, ring + (size_t)j * cap, sizeof(float2) * (size_t)(n - first), hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-int ft8rx_ddc_wide_stream_close(ft8rx_handle* h) {
-    if (!h) return -1;
-    if (!h->wds.open) { set_err(h, "ft8rx_ddc_wide_stream_close: no wide stream is open"); return -1; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the buffers
-    ddw_stream_release(h);
-    ddc_stream_release(h);
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- rational resampler
-// The kernel's tiles and the limits, against the pure index arithmetic of ddc_rat_ring.hpp
 static_assert(ddcrat::LANE_P == 64 && ddcrat::LANE_TABLE == DDR_TAB && ddcrat::LANE_SAMPLES == DDR_LS_LANE && ddcrat::LANE_TILE == DDR_NT &&
               ddcrat::PIECE == DDR_JP && ddcrat::WAVE_SAMPLES == DDR_LS_WAVE && ddcrat::WAVE_TILE == DDR_TK_WAVE && DDR_JP % 64 == 0 &&
               DDR_TK_WAVE == 4 * (DDR_NT / 64), "ddc_rat_ring.hpp: the tiles of kernels/ddc_rat.hpp");
@@ -1989,48 +1716,100 @@ constexpr bool ddr_tiles_fit() {
 }
 static_assert(ddr_tiles_fit(), "ddc_rat_ring.hpp: a tile's input fits the LDS image");
 
-static bool ddr_kind_ok(int kind) { return (kind >= FT8RX_DDC_REAL_I16 && kind <= FT8RX_DDC_IQ_F32) || kind == FT8RX_WIDE_IQ_U8 || kind == FT8RX_WIDE_IQ_I8; }
-static size_t ddr_sample_bytes(int kind) { return kind <= FT8RX_DDC_IQ_F32 ? DDC_SAMPLE_BYTES[kind] : 2; }
-static bool ddr_is_iq(int kind) { return kind != FT8RX_DDC_REAL_I16 && kind != FT8RX_DDC_REAL_F32; }
+// bytes of one sample of any kind a pre-stage takes (FT8RX_DDC_*: 0 .. 3, FT8RX_WIDE_*: 16 .. 19), and whether it is an (I, Q) pair
+static size_t pre_sample_bytes(int kind) { return kind <= FT8RX_DDC_IQ_F32 ? DDC_SAMPLE_BYTES[kind] : kind == FT8RX_WIDE_IQ_I16 ? 4 : 2; }
+static bool pre_is_iq(int kind) { return kind != FT8RX_DDC_REAL_I16 && kind != FT8RX_DDC_REAL_F32 && kind != FT8RX_WIDE_REAL_I16; }
+constexpr uint32_t pre_kinds(int lo, int hi) { return ((2u << hi) - 1u) & ~((1u << lo) - 1u); }
 
-// h of a rate: the recipe of ddc_design at fs = rate L, pass 3200 Hz, stop min(rate, rate_mid) - 3200 Hz, 85 dB, sum h = L; designed
-// once per rate.  nullptr: the plan refuses the rate, or the filter is longer than MAX_TAPS (its length is worked out before it is made)
-static const std::vector<float>* ddr_taps(int32_t rate_hz) {
-    const ddcrat::Plan p = ddcrat::plan(rate_hz);
-    if (!p.rate_mid) return nullptr;
-    const double fs = (double)rate_hz * (double)p.L, f_stop = (double)(rate_hz < p.rate_mid ? rate_hz : p.rate_mid) - 3200.0;
-    if ((85.0 - 7.95) / (2.285 * 2.0 * M_PI * (f_stop - 3200.0) / fs) + 2.0 > (double)ddcrat::MAX_TAPS) return nullptr;
+// The prototype of a rate, designed once per (stage, rate) by the recipe of ddc_design at 85 dB, pass 3200 Hz.
+//   wide      h0 at fs = rate, stop rate_mid - 3200 Hz
+//   rational  h at fs = rate L, stop min(rate, rate_mid) - 3200 Hz, sum h = L; its length is worked out before it is made
+// nullptr: the plan refuses the rate, or the filter is longer than the stage's MAX_TAPS
+static const std::vector<float>* pre_taps(int which, int32_t rate_hz) {
+    double fs, f_stop, dc = 1.0;
+    int64_t most;
+    if (which == PRE_WIDE) {
+        const ddcwide::Plan p = ddcwide::plan(rate_hz);
+        if (!p.rate_mid) return nullptr;
+        fs = (double)rate_hz; f_stop = (double)p.rate_mid - 3200.0; most = ddcwide::MAX_TAPS;
+    } else {
+        const ddcrat::Plan p = ddcrat::plan(rate_hz);
+        if (!p.rate_mid) return nullptr;
+        fs = (double)rate_hz * (double)p.L; f_stop = (double)(rate_hz < p.rate_mid ? rate_hz : p.rate_mid) - 3200.0; dc = (double)p.L; most = ddcrat::MAX_TAPS;
+        if ((85.0 - 7.95) / (2.285 * 2.0 * M_PI * (f_stop - 3200.0) / fs) + 2.0 > (double)most) return nullptr;
+    }
     static std::mutex mu;
-    static std::map<int32_t, std::vector<float>> designed;
+    static std::map<std::pair<int, int32_t>, std::vector<float>> designed;
     std::lock_guard<std::mutex> lock(mu);
-    auto it = designed.find(rate_hz);
-    if (it == designed.end()) it = designed.emplace(rate_hz, ddc_design(3200.0, f_stop, 85.0, fs, (double)p.L)).first;
-    return (int64_t)it->second.size() <= ddcrat::MAX_TAPS ? &it->second : nullptr;
+    const std::pair<int, int32_t> key(which, rate_hz);
+    auto it = designed.find(key);
+    if (it == designed.end()) it = designed.emplace(key, ddc_design(3200.0, f_stop, 85.0, fs, dc)).first;
+    return (int64_t)it->second.size() <= most ? &it->second : nullptr;
 }
 
-int ft8rx_ddc_rat_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* l, int32_t* m, int32_t* n_taps) {
-    const ddcrat::Plan p = ddcrat::plan(rate_hz);
-    const std::vector<float>* t = ddr_taps(rate_hz);
-    if (!t) return -1;
+// the front stage of a rate; taps == nullptr: refused
+static PreStage pre_plan(int which, int32_t rate_hz) {
+    PreStage d;
+    d.which = which; d.rate = rate_hz;
+    d.name = PRE_NAME[which]; d.entry = PRE_ENTRY[which];
+    d.kinds = which == PRE_WIDE ? pre_kinds(FT8RX_WIDE_REAL_I16, FT8RX_WIDE_IQ_I8)
+                                : pre_kinds(FT8RX_DDC_REAL_I16, FT8RX_DDC_IQ_F32) | pre_kinds(FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8);
+    d.taps = pre_taps(which, rate_hz);
+    if (!d.taps) return d;
+    d.n_taps = (int)d.taps->size();
+    if (which == PRE_WIDE) {
+        const ddcwide::Plan p = ddcwide::plan(rate_hz);
+        d.rate_mid = (int32_t)p.rate_mid; d.M = (int)p.R0;
+        d.H = (int)ddcwide::history(d.n_taps, p.R0); d.tk = (int)ddcwide::tile_outputs(p.R0);
+        d.n_max = ddcwide::N_MAX; d.end_max = INT64_MAX;
+    } else {
+        const ddcrat::Plan p = ddcrat::plan(rate_hz);
+        d.rate_mid = (int32_t)p.rate_mid; d.L = (int)p.L; d.M = (int)p.M;
+        d.P = (int)ddcrat::phase_taps(d.n_taps, p.L); d.H = (int)ddcrat::history(d.n_taps, p.L); d.tk = (int)ddcrat::tile_outputs(d.n_taps, p.L, p.M);
+        d.lane = ddcrat::lane_regime(d.n_taps, p.L);
+        d.n_max = ddcrat::N_MAX; d.end_max = 2 * ddcrat::N_MAX;      // a stream ends below 2^53, so that n L stays below 2^62
+    }
+    return d;
+}
+
+int ft8rx_ddc_wide_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* r0) {
+    const ddcwide::Plan p = ddcwide::plan(rate_hz);
+    if (!p.rate_mid) return -1;
     if (rate_mid_hz) *rate_mid_hz = (int32_t)p.rate_mid;
-    if (l) *l = (int32_t)p.L;
-    if (m) *m = (int32_t)p.M;
-    if (n_taps) *n_taps = (int32_t)t->size();
+    if (r0) *r0 = (int32_t)p.R0;
     return 0;
 }
 
-int ft8rx_ddc_rat_taps(int32_t rate_hz, float* taps, int cap) {
-    const std::vector<float>* t = ddr_taps(rate_hz);
+int ft8rx_ddc_rat_plan(int32_t rate_hz, int32_t* rate_mid_hz, int32_t* l, int32_t* m, int32_t* n_taps) {
+    const PreStage d = pre_plan(PRE_RAT, rate_hz);
+    if (!d.taps) return -1;
+    if (rate_mid_hz) *rate_mid_hz = d.rate_mid;
+    if (l) *l = d.L;
+    if (m) *m = d.M;
+    if (n_taps) *n_taps = d.n_taps;
+    return 0;
+}
+
+static int pre_taps_out(int which, int32_t rate_hz, float* taps, int cap) {
+    const std::vector<float>* t = pre_taps(which, rate_hz);
     if (!t) return -1;
     for (int i = 0; taps && i < cap && i < (int)t->size(); i++) taps[i] = (*t)[i];
     return (int)t->size();
 }
+int ft8rx_ddc_wide_taps(int32_t rate_hz, float* taps, int cap) { return pre_taps_out(PRE_WIDE, rate_hz, taps, cap); }
+int ft8rx_ddc_rat_taps(int32_t rate_hz, float* taps, int cap) { return pre_taps_out(PRE_RAT, rate_hz, taps, cap); }
 
-// the argument checks every entry shares -> 0, or -1 with the error text
-static int ddr_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
-    if (!ddr_kind_ok(kind)) { set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32, FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8", who, kind); return -1; }
-    if (!ddr_taps(rate_hz)) {
-        set_err(h, "%s: rate_hz %d is not taken: outside [16000, 129600000], a rate of ft8rx_ddc or ft8rx_ddc_wide, L > 320 or more than 8448 taps", who, (int)rate_hz);
+// the argument checks every entry shares -> 0 and the stage in d, or -1 with the error text
+static int pre_check(ft8rx_handle* h, const char* who, int which, PreStage& d, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
+    d = pre_plan(which, rate_hz);
+    if (kind < 0 || kind > 31 || !(d.kinds >> kind & 1u)) {
+        if (which == PRE_WIDE) set_err(h, "%s: kind %d is not one of FT8RX_WIDE_REAL_I16 .. FT8RX_WIDE_IQ_I8", who, kind);
+        else set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32, FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8", who, kind);
+        return -1;
+    }
+    if (!d.taps) {
+        if (which == PRE_WIDE) set_err(h, "%s: rate_hz %d is not a multiple of 48000 in [240000, 129600000] with rate_hz / rate_mid <= 1350", who, (int)rate_hz);
+        else set_err(h, "%s: rate_hz %d is not taken: outside [16000, 129600000], a rate of ft8rx_ddc or ft8rx_ddc_wide, L > 320 or more than 8448 taps", who, (int)rate_hz);
         return -1;
     }
     if (n_out < 1 || n_out > h->max_frames || n_out > 65535) { set_err(h, "%s: n_out %d outside [1, %d] (max_frames; at most 65535)", who, n_out, h->max_frames); return -1; }
@@ -2041,170 +1820,247 @@ static int ddr_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz
     return 0;
 }
 
-// per channel: the frequency word w0, the table by phase T[phi][i] = h[phi + i L] e^{+2 pi i (w0 i mod 2^32) / 2^32} (double, rounded once;
-// zero from N on), the dial left for the stage behind (f_dial - f0, about -3000 Hz) and f0 itself, both taken into [-rate / 2, rate / 2)
-static void ddr_tables(int32_t rate_hz, const std::vector<float>& hp, int L, int n_out, const double* f_dial_hz, std::vector<float2>& tab,
-                       std::vector<uint32_t>& w0s, std::vector<double>& dial_mid, std::vector<double>& f0s) {
-    const size_t N = hp.size(), P = (size_t)ddcrat::phase_taps((int64_t)N, L), LP = (size_t)L * P;
-    tab.assign((size_t)n_out * LP, make_float2(0.0f, 0.0f)); w0s.resize((size_t)n_out); dial_mid.resize((size_t)n_out); f0s.resize((size_t)n_out);
-    for (int c = 0; c < n_out; c++) {
-        const double r = nearbyint((f_dial_hz[c] + 3000.0) / (double)rate_hz * 4294967296.0);
-        const uint32_t w0 = (uint32_t)((long long)r & 0xffffffffLL);
-        double f0 = (double)w0 * (double)rate_hz / 4294967296.0;
-        if (f0 >= 0.5 * rate_hz) f0 -= (double)rate_hz;
-        double d = f_dial_hz[c] - f0;
-        d -= (double)rate_hz * nearbyint(d / (double)rate_hz);
-        w0s[c] = w0; f0s[c] = f0; dial_mid[c] = d;
-        for (size_t i = 0; i < P; i++) {
-            const double a = (double)(uint32_t)(w0 * (uint32_t)i) * (M_PI / 2147483648.0), ca = cos(a), sa = sin(a);
-            for (size_t phi = 0; phi < (size_t)L && phi + i * (size_t)L < N; phi++) {
-                const double hv = (double)hp[phi + i * (size_t)L];
-                tab[(size_t)c * LP + phi * P + i] = make_float2((float)(hv * ca), (float)(hv * sa));
-            }
+// One channel's table.  Wide: W[j] = h0[j] e^{-2 pi i (w0 j mod 2^32) / 2^32}, [n_taps].  Rational: by phase, T[phi][i] = h[phi + i L]
+// e^{+2 pi i (w0 i mod 2^32) / 2^32}, [L][P], zero from N on.  Both in double, rounded once.
+static void pre_fill_wide(const std::vector<float>& h0, uint32_t w0, float2* tab) {
+    for (size_t j = 0; j < h0.size(); j++) {
+        const double a = -(double)(uint32_t)(w0 * (uint32_t)j) * (M_PI / 2147483648.0);
+        tab[j] = make_float2((float)((double)h0[j] * cos(a)), (float)((double)h0[j] * sin(a)));
+    }
+}
+static void pre_fill_rat(const std::vector<float>& hp, size_t L, size_t P, uint32_t w0, float2* tab) {
+    const size_t N = hp.size();
+    for (size_t i = 0; i < P; i++) {
+        const double a = (double)(uint32_t)(w0 * (uint32_t)i) * (M_PI / 2147483648.0), ca = cos(a), sa = sin(a);
+        for (size_t phi = 0; phi < L && phi + i * L < N; phi++) {
+            const double hv = (double)hp[phi + i * L];
+            tab[phi * P + i] = make_float2((float)(hv * ca), (float)(hv * sa));
         }
     }
 }
+// per channel: the frequency word w0, its table, the dial left for the stage behind (f_dial - f0, about -3000 Hz) and f0 itself, both
+// taken into [-rate / 2, rate / 2)
+struct PreTables { std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s; };
+static void pre_tables(const PreStage& d, int n_out, const double* f_dial_hz, PreTables& t) {
+    const size_t per = d.which == PRE_WIDE ? (size_t)d.n_taps : (size_t)d.L * (size_t)d.P;
+    const double rate = (double)d.rate;
+    t.tab.assign((size_t)n_out * per, make_float2(0.0f, 0.0f)); t.w0s.resize((size_t)n_out); t.dial_mid.resize((size_t)n_out); t.f0s.resize((size_t)n_out);
+    for (int c = 0; c < n_out; c++) {
+        const double r = nearbyint((f_dial_hz[c] + 3000.0) / rate * 4294967296.0);
+        const uint32_t w0 = (uint32_t)((long long)r & 0xffffffffLL);
+        double f0 = (double)w0 * rate / 4294967296.0;
+        if (f0 >= 0.5 * d.rate) f0 -= rate;
+        double dm = f_dial_hz[c] - f0;
+        dm -= rate * nearbyint(dm / rate);
+        t.w0s[c] = w0; t.f0s[c] = f0; t.dial_mid[c] = dm;
+        if (d.which == PRE_WIDE) pre_fill_wide(*d.taps, w0, t.tab.data() + (size_t)c * per);
+        else pre_fill_rat(*d.taps, (size_t)d.L, (size_t)d.P, w0, t.tab.data() + (size_t)c * per);
+    }
+}
+// what the caller sees as mixed: f0 + the dial the stage behind really mixed, in [-rate / 2, rate / 2)
+static void pre_mixed(int32_t rate_hz, int n_out, const std::vector<double>& f0s, double* f_mixed_hz) {
+    for (int c = 0; f_mixed_hz && c < n_out; c++) {
+        double f = f0s[c] + f_mixed_hz[c];
+        if (f >= 0.5 * rate_hz) f -= (double)rate_hz;
+        if (f < -0.5 * rate_hz) f += (double)rate_hz;
+        f_mixed_hz[c] = f;
+    }
+}
 
-// the one-shot behind its checks: the resampler into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
-static int ddr_run(ft8rx_handle* h, const char* who, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz,
+// The two launches (with_bool: a run-time bool as a template argument).
+// One call: in = n_samples samples of `kind` -> mid [n_out][n_mid]
+static void pre_launch(ft8rx_handle* h, const PreStage& d, const void* d_in, int kind, long long n_samples, const float2* tab, const uint32_t* w0s,
+                       int n_out, long long n_mid, float2* mid) {
+    const dim3 grid((unsigned)((n_mid + d.tk - 1) / d.tk), (unsigned)n_out);
+    const float g0 = pre_is_iq(kind) ? 1.0f : 2.0f;
+    with_bool(pre_is_iq(kind), [&](auto iq) {
+        constexpr bool IQ = decltype(iq)::value;
+        if (d.which == PRE_WIDE) k_ddc_pre<IQ><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, n_samples, tab, w0s, d.n_taps, d.M, d.tk, g0, n_mid, mid);
+        else with_bool(d.lane, [&](auto lane) {
+            k_ddc_rat<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(d_in, kind, n_samples, tab, w0s, (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, g0, n_mid, mid);
+        });
+    });
+}
+// The stream: intermediate samples k_done .. k_done + n_k - 1 of every channel from the history and the chunk [n_start, n_end) -> s.d_mid
+static void pre_launch_stream(ft8rx_handle* h, const ft8rx_handle::PreStream& s, const void* chunk, long long n_start, long long n_end, int n_k) {
+    const PreStage& d = s.st;
+    const dim3 grid((unsigned)((n_k + d.tk - 1) / d.tk), (unsigned)s.n_out);
+    const int p_last = s.pushed ? (int)ddcpre::hist_pos(n_start - 1, s.n_origin, d.H) : 0;
+    const long long n_origin = s.n_origin, k_first = s.k_done;
+    with_bool(pre_is_iq(s.kind), [&](auto iq) {
+        constexpr bool IQ = decltype(iq)::value;
+        if (d.which == PRE_WIDE)
+            k_ddc_pre_stream<IQ><<<grid, DDW_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.kind, n_origin, n_start, n_end, s.d_tab, s.d_w0, d.n_taps, d.M, d.tk,
+                                                                 s.g0, k_first, n_k, s.d_mid);
+        else with_bool(d.lane, [&](auto lane) {
+            k_ddc_rat_stream<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.kind, n_origin, n_start, n_end, s.d_tab, s.d_w0,
+                                                                                       (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, s.g0, k_first, n_k, s.d_mid);
+        });
+    });
+}
+
+// the one-shot behind its checks: the pre-stage into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
+static int pre_run(ft8rx_handle* h, const char* who, const PreStage& d, const void* d_in, int kind, uint64_t n_samples, int n_out, const double* f_dial_hz,
                    float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
-    const ddcrat::Plan p = ddcrat::plan(rate_hz);
-    const std::vector<float>& hp = *ddr_taps(rate_hz);
-    const int D = (int)(p.rate_mid / 12000), N = (int)hp.size(), L = (int)p.L, M = (int)p.M, P = (int)ddcrat::phase_taps(N, L);
-    const int tk = (int)ddcrat::tile_outputs(N, L, M);
-    const bool lane = ddcrat::lane_regime(N, L);
-    const int64_t n_mid = ddcrat::mid_count((int64_t)n_samples, N, L, M, (int64_t)FT8RX_NSAMP * D);
-    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s, fm((size_t)n_out);
-    ddr_tables(rate_hz, hp, L, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
-    if (ddw_reserve(h, who, &h->d_wide_tab, &h->wide_tab_cap, sizeof(float2) * tab.size()) ||
-        ddw_reserve(h, who, &h->d_wide_w0, &h->wide_w0_cap, sizeof(uint32_t) * w0s.size()) ||
-        ddw_reserve(h, who, &h->d_wide_mid, &h->wide_mid_cap, sizeof(float2) * (size_t)n_out * (size_t)n_mid)) return -2;
+    const int D = d.rate_mid / 12000;
+    const int64_t n_mid = ddcpre::mid_count((int64_t)n_samples, d.n_taps, d.L, d.M, (int64_t)FT8RX_NSAMP * D);
+    PreTables t;
+    std::vector<double> fm((size_t)n_out);
+    pre_tables(d, n_out, f_dial_hz, t);
+    if (grow_dev(h, who, &h->d_pre_tab, &h->pre_tab_cap, sizeof(float2) * t.tab.size()) ||
+        grow_dev(h, who, &h->d_pre_w0, &h->pre_w0_cap, sizeof(uint32_t) * t.w0s.size()) ||
+        grow_dev(h, who, &h->d_pre_mid, &h->pre_mid_cap, sizeof(float2) * (size_t)n_out * (size_t)n_mid)) return -2;
     // the tables are pageable vectors of this call, and an earlier call's kernel may still read the device copies
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->d_wide_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_wide_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice));
-    const dim3 grid((unsigned)((n_mid + tk - 1) / tk), (unsigned)n_out);
-    const float g0 = ddr_is_iq(kind) ? 1.0f : 2.0f;
-#define DDR_GO(IQ, LANE) k_ddc_rat<IQ, LANE><<<grid, DDR_NT, 0, h->stream>>>(d_in, kind, (long long)n_samples, (const float2*)h->d_wide_tab, \
-                             (const uint32_t*)h->d_wide_w0, (N - 1) / 2, L, M, P, tk, g0, (long long)n_mid, (float2*)h->d_wide_mid)
-    if (ddr_is_iq(kind)) { if (lane) DDR_GO(true, true); else DDR_GO(true, false); }
-    else { if (lane) DDR_GO(false, true); else DDR_GO(false, false); }
-#undef DDR_GO
+    HIPCHK(h, hipMemcpy(h->d_pre_tab, t.tab.data(), sizeof(float2) * t.tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_pre_w0, t.w0s.data(), sizeof(uint32_t) * t.w0s.size(), hipMemcpyHostToDevice));
+    pre_launch(h, d, d_in, kind, (long long)n_samples, (const float2*)h->d_pre_tab, (const uint32_t*)h->d_pre_w0, n_out, (long long)n_mid, (float2*)h->d_pre_mid);
     HIPCHK(h, hipGetLastError());
     std::vector<int32_t> src((size_t)n_out);
     for (int j = 0; j < n_out; j++) src[j] = j;
-    if (const int rc = ddc_launch(h, D, h->d_wide_mid, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), dial_mid.data(),
+    if (const int rc = ddc_launch(h, D, h->d_pre_mid, FT8RX_DDC_IQ_F32, d.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), t.dial_mid.data(),
                                   gain, d_audio, d_audio_f32, fm.data())) return rc;
-    if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz); }
+    if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; pre_mixed(d.rate, n_out, t.f0s, f_mixed_hz); }
     return 0;
 }
 
-static int ddr_check_oneshot(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain) {
-    if (ddr_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+static int pre_check_oneshot(ft8rx_handle* h, const char* who, int which, PreStage& d, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                             const double* f_dial_hz, float gain) {
+    if (pre_check(h, who, which, d, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
     if (n_samples > (uint64_t)15 * (uint64_t)rate_hz) { set_err(h, "%s: n_samples %llu > %llu (15 s at rate_hz)", who, (unsigned long long)n_samples, 15ull * (unsigned long long)rate_hz); return -1; }
-    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle (ft8rx_ddc_rat_stream_close)", who); return -1; }
-    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
-    return 0;
+    return pre_refuse_open(h, who);
 }
 
-int ft8rx_ddc_rat(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
-                  int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+// the device entry (d_in on the device; d_audio: NULL = the staging buffer) and the host entry
+static int pre_oneshot(ft8rx_handle* h, const char* who, int which, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                       const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
     if (!h) return -1;
-    if (ddr_check_oneshot(h, "ft8rx_ddc_rat", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
-    if (!d_in || ((uintptr_t)d_in % ddr_sample_bytes(kind)) != 0) { set_err(h, "ft8rx_ddc_rat: d_in is NULL or not aligned to a sample"); return -1; }
+    PreStage d;
+    if (pre_check_oneshot(h, who, which, d, kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!d_in || ((uintptr_t)d_in % pre_sample_bytes(kind)) != 0) { set_err(h, "%s: d_in is NULL or not aligned to a sample", who); return -1; }
     ENTER(h);
     if (ddc_workspaces(h)) return -2;
     if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
-    return ddr_run(h, "ft8rx_ddc_rat", d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+    return pre_run(h, who, d, d_in, kind, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
 }
-
-int ft8rx_ddc_rat_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
-                       double* f_mixed_hz) {
+static int pre_oneshot_host(ft8rx_handle* h, const char* who, int which, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
+                            const double* f_dial_hz, float gain, double* f_mixed_hz) {
     if (!h) return -1;
-    if (ddr_check_oneshot(h, "ft8rx_ddc_rat_host", kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
-    if (!in) { set_err(h, "ft8rx_ddc_rat_host: in is NULL"); return -1; }
+    PreStage d;
+    if (pre_check_oneshot(h, who, which, d, kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
+    if (!in) { set_err(h, "%s: in is NULL", who); return -1; }
     ENTER(h);
     if (ddc_workspaces(h) || need_staging(h)) return -2;
-    const size_t bytes = (size_t)n_samples * ddr_sample_bytes(kind);
-    if (ddw_reserve(h, "ft8rx_ddc_rat_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
+    const size_t bytes = (size_t)n_samples * pre_sample_bytes(kind);
+    if (grow_dev(h, who, &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
     if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = ddr_run(h, "ft8rx_ddc_rat_host", h->d_ddc_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    if (const int rc = pre_run(h, who, d, h->d_ddc_in, kind, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 
-// ---- the rational stream: the resampler on a continuous stream, in front of the streaming down-converter (section 16.1), which it
-// opens, feeds on the device and closes.  The index arithmetic is ddc_rat_ring.hpp's.
-static void ddr_stream_release(ft8rx_handle* h) {
-    ft8rx_handle::RatStream& s = h->rts;
+int ft8rx_ddc_wide(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                   int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    return pre_oneshot(h, "ft8rx_ddc_wide", PRE_WIDE, d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+}
+int ft8rx_ddc_rat(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                  int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
+    return pre_oneshot(h, "ft8rx_ddc_rat", PRE_RAT, d_in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+}
+int ft8rx_ddc_wide_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                        double* f_mixed_hz) {
+    return pre_oneshot_host(h, "ft8rx_ddc_wide_host", PRE_WIDE, in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, f_mixed_hz);
+}
+int ft8rx_ddc_rat_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out, const double* f_dial_hz, float gain,
+                       double* f_mixed_hz) {
+    return pre_oneshot_host(h, "ft8rx_ddc_rat_host", PRE_RAT, in, kind, rate_hz, n_samples, n_out, f_dial_hz, gain, f_mixed_hz);
+}
+
+// ---- the pre-stage stream: the stage on a continuous stream, in front of the streaming down-converter (section 16.1), which it opens,
+// feeds on the device and closes.  The index arithmetic is ddc_pre_ring.hpp's.
+static void pre_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::PreStream& s = h->ps;
     release_dev(h, s.d_hist); release_dev(h, s.d_chunk); release_dev(h, s.d_mid); release_dev(h, s.d_tab); release_dev(h, s.d_w0); release_host(h, s.h_stage);
     const hipEvent_t ev = s.ev;
-    s = ft8rx_handle::RatStream();
+    s = ft8rx_handle::PreStream();
     s.ev = ev;
 }
 
-int ft8rx_ddc_rat_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
-                              int keep_f32, double* f_mixed_hz) {
+static int pre_stream_open(ft8rx_handle* h, const char* who, int which, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain,
+                           uint64_t n_origin, int keep_f32, double* f_mixed_hz) {
     if (!h) return -1;
-    const char* who = "ft8rx_ddc_rat_stream_open";
-    if (h->rts.open) { set_err(h, "%s: a rational stream is open on this handle already (ft8rx_ddc_rat_stream_close)", who); return -1; }
-    if (h->wds.open) { set_err(h, "%s: a wide stream is open on this handle (ft8rx_ddc_wide_stream_close)", who); return -1; }
+    if (h->ps.open) {
+        set_err(h, "%s: a %s stream is open on this handle%s (%s_stream_close)", who, h->ps.st.name, h->ps.st.which == which ? " already" : "", h->ps.st.entry);
+        return -1;
+    }
     if (h->ds.open) { set_err(h, "%s: a stream is open on this handle already (ft8rx_ddc_stream_close)", who); return -1; }
-    if (ddr_check(h, who, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
-    const ddcrat::Plan p = ddcrat::plan(rate_hz);
-    if (n_origin > (uint64_t)ddcrat::N_MAX || !ddcrat::origin_ok((int64_t)n_origin, p.rate_mid, p.L, p.M)) {
-        set_err(h, "%s: n_origin %llu: n_origin L / M must be an integer multiple of %d (1008 rate_mid / 12000), n_origin <= 2^52", who,
-                (unsigned long long)n_origin, (int)(DDC_TO * (p.rate_mid / 12000)));
+    PreStage d;
+    if (pre_check(h, who, which, d, kind, rate_hz, n_out, f_dial_hz, gain) < 0) return -1;
+    // the origin: k_origin = n_origin L / M lies on the tile grid of the stage behind (wide: n_origin is a multiple of 1008 rate / 12000)
+    if (n_origin > (uint64_t)d.n_max || !ddcpre::origin_ok((int64_t)n_origin, d.n_max, d.rate_mid, d.L, d.M)) {
+        if (which == PRE_WIDE)
+            set_err(h, "%s: n_origin %llu is not a multiple of %llu (1008 rate_hz / 12000)", who, (unsigned long long)n_origin,
+                    (unsigned long long)DDC_TO * ((unsigned long long)rate_hz / 12000));
+        else
+            set_err(h, "%s: n_origin %llu: n_origin L / M must be an integer multiple of %d (1008 rate_mid / 12000), n_origin <= 2^52", who,
+                    (unsigned long long)n_origin, (int)(DDC_TO * (d.rate_mid / 12000)));
         return -1;
     }
     ENTER(h);
-    const std::vector<float>& hp = *ddr_taps(rate_hz);
-    std::vector<float2> tab; std::vector<uint32_t> w0s; std::vector<double> dial_mid, f0s;
-    ddr_tables(rate_hz, hp, (int)p.L, n_out, f_dial_hz, tab, w0s, dial_mid, f0s);
+    PreTables t;
+    pre_tables(d, n_out, f_dial_hz, t);
     std::vector<int32_t> src((size_t)n_out);
     for (int j = 0; j < n_out; j++) src[j] = j;
     // the stage behind: n_out IQ float32 streams at rate_mid, one channel each, from the same origin
-    if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, (int32_t)p.rate_mid, n_out, n_out, src.data(), dial_mid.data(), gain,
-                                       (uint64_t)ddcrat::k_origin((int64_t)n_origin, p.L, p.M), keep_f32, f_mixed_hz)) return rc;
-    ft8rx_handle::RatStream& s = h->rts;
-    const size_t sb = ddr_sample_bytes(kind);
-    const int H = (int)ddcrat::history((int64_t)hp.size(), p.L);
+    const int64_t k_origin = ddcpre::k_origin((int64_t)n_origin, d.L, d.M);
+    if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, d.rate_mid, n_out, n_out, src.data(), t.dial_mid.data(), gain, (uint64_t)k_origin, keep_f32,
+                                       f_mixed_hz)) return rc;
+    ft8rx_handle::PreStream& s = h->ps;
+    const size_t sb = pre_sample_bytes(kind);
     int rc = 0;
     hipError_t e = hipSuccess;
     if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
     if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
-    if (!rc) rc = dalloc(h, &s.d_hist, (size_t)H * sb);
+    if (!rc) rc = dalloc(h, &s.d_hist, (size_t)d.H * sb);
     if (!rc) rc = dalloc(h, &s.d_chunk, (size_t)rate_hz * sb);
-    if (!rc) rc = dalloc(h, &s.d_mid, (size_t)n_out * (size_t)p.rate_mid);
-    if (!rc) rc = dalloc(h, &s.d_tab, tab.size());
-    if (!rc) rc = dalloc(h, &s.d_w0, w0s.size());
+    if (!rc) rc = dalloc(h, &s.d_mid, (size_t)n_out * (size_t)d.rate_mid);
+    if (!rc) rc = dalloc(h, &s.d_tab, t.tab.size());
+    if (!rc) rc = dalloc(h, &s.d_w0, t.w0s.size());
     if (!rc) rc = halloc(h, &s.h_stage, (size_t)rate_hz * sb);
     if (!rc) {
-        e = hipMemcpyAsync(s.d_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.d_w0, w0s.data(), sizeof(uint32_t) * w0s.size(), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s.d_hist, 0, (size_t)H * sb, h->stream);
+        e = hipMemcpyAsync(s.d_tab, t.tab.data(), sizeof(float2) * t.tab.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d_w0, t.w0s.data(), sizeof(uint32_t) * t.w0s.size(), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(s.d_hist, 0, (size_t)d.H * sb, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the tables are pageable vectors of this call
         if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
     }
-    if (rc) { ddr_stream_release(h); ddc_stream_release(h); return -2; }
-    ddw_mixed(rate_hz, n_out, f0s, f_mixed_hz);
-    s.kind = kind; s.n_out = n_out; s.n_taps = (int)hp.size(); s.L = (int)p.L; s.M = (int)p.M; s.P = (int)ddcrat::phase_taps((int64_t)hp.size(), p.L); s.H = H;
-    s.lane = ddcrat::lane_regime((int64_t)hp.size(), p.L);
-    s.rate = rate_hz; s.rate_mid = (int32_t)p.rate_mid;
-    s.g0 = ddr_is_iq(kind) ? 1.0f : 2.0f;
-    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = ddcrat::k_origin(s.n_origin, s.L, s.M);
+    if (rc) { pre_stream_release(h); ddc_stream_release(h); return -2; }
+    pre_mixed(rate_hz, n_out, t.f0s, f_mixed_hz);
+    s.st = d; s.kind = kind; s.n_out = n_out;
+    s.g0 = pre_is_iq(kind) ? 1.0f : 2.0f;
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = k_origin;
     s.open = true;
     return 0;
 }
 
-int ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+// the open stream of stage `which`, or nullptr with the error text
+static ft8rx_handle::PreStream* pre_stream_of(ft8rx_handle* h, const char* who, int which, bool hint) {
+    if (h->ps.open && h->ps.st.which == which) return &h->ps;
+    if (hint) set_err(h, "%s: no %s stream is open (%s_stream_open)", who, PRE_NAME[which], PRE_ENTRY[which]);
+    else set_err(h, "%s: no %s stream is open", who, PRE_NAME[which]);
+    return nullptr;
+}
+
+static int pre_stream_push(ft8rx_handle* h, const char* who, int which, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
     if (!h) return -1;
-    ft8rx_handle::RatStream& s = h->rts;
-    if (!s.open) { set_err(h, "ft8rx_ddc_rat_stream_push: no rational stream is open (ft8rx_ddc_rat_stream_open)"); return -1; }
-    if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_rat_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
-    const size_t sb = ddr_sample_bytes(s.kind);
-    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_rat_stream_push: in is NULL or not aligned to a sample"); return -1; }
-    if (s.n_origin + s.pushed + (int64_t)n_new > 2 * ddcrat::N_MAX) { set_err(h, "ft8rx_ddc_rat_stream_push: n_new %llu takes the stream past index 2^53", (unsigned long long)n_new); return -1; }
+    ft8rx_handle::PreStream* ps = pre_stream_of(h, who, which, true);
+    if (!ps) return -1;
+    ft8rx_handle::PreStream& s = *ps;
+    const PreStage& d = s.st;
+    if (n_new < 1 || n_new > (uint64_t)d.rate) { set_err(h, "%s: n_new %llu outside [1, %d] (one second)", who, (unsigned long long)n_new, (int)d.rate); return -1; }
+    const size_t sb = pre_sample_bytes(s.kind);
+    if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "%s: in is NULL or not aligned to a sample", who); return -1; }
+    if (s.n_origin + s.pushed + (int64_t)n_new > d.end_max) { set_err(h, "%s: n_new %llu takes the stream past index 2^53", who, (unsigned long long)n_new); return -1; }
     // (no ENTER: a push touches the streams' own buffers only, on the main stream; batches in flight read none of them)
     HIPCHK(h, hipSetDevice(h->device));
     const char* chunk = (const char*)in;
@@ -2216,21 +2072,14 @@ int ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, i
         chunk = s.d_chunk;
     }
     const int64_t n_start = s.n_origin + s.pushed, n_end = n_start + (int64_t)n_new;
-    const int64_t k_new = ddcrat::mid_done(s.n_origin, n_end, s.n_taps, s.L, s.M);
+    const int64_t k_new = ddcpre::mid_done(s.n_origin, n_end, d.n_taps, d.L, d.M);
     const int n_k = (int)(k_new - s.k_done);             // at most rate_mid: a push is at most a second
     if (n_k > 0) {
-        const int tk = (int)ddcrat::tile_outputs(s.n_taps, s.L, s.M);
-        const dim3 grid((unsigned)((n_k + tk - 1) / tk), (unsigned)s.n_out);
-        const int p_last = s.pushed ? (int)ddcrat::hist_pos(n_start - 1, s.n_origin, s.H) : 0;
-#define DDR_GO(IQ, LANE) k_ddc_rat_stream<IQ, LANE><<<grid, DDR_NT, 0, h->stream>>>(s.d_hist, s.H, p_last, chunk, s.kind, (long long)s.n_origin, \
-                             (long long)n_start, (long long)n_end, s.d_tab, s.d_w0, (s.n_taps - 1) / 2, s.L, s.M, s.P, tk, s.g0, (long long)s.k_done, n_k, s.d_mid)
-        if (ddr_is_iq(s.kind)) { if (s.lane) DDR_GO(true, true); else DDR_GO(true, false); }
-        else { if (s.lane) DDR_GO(false, true); else DDR_GO(false, false); }
-#undef DDR_GO
+        pre_launch_stream(h, s, chunk, (long long)n_start, (long long)n_end, n_k);
         HIPCHK(h, hipGetLastError());
     }
     // the chunk's last H samples into the history, behind the kernel that read the old ones
-    const ddcrat::Keep kp = ddcrat::keep(s.pushed, (int64_t)n_new, s.H);
+    const ddcpre::Keep kp = ddcpre::keep(s.pushed, (int64_t)n_new, d.H);
     HIPCHK(h, hipMemcpyAsync(s.d_hist + (size_t)kp.pos * sb, chunk + (size_t)kp.skip * sb, (size_t)kp.first * sb, hipMemcpyDeviceToDevice, h->stream));
     if (kp.second) HIPCHK(h, hipMemcpyAsync(s.d_hist, chunk + (size_t)(kp.skip + kp.first) * sb, (size_t)kp.second * sb, hipMemcpyDeviceToDevice, h->stream));
     s.pushed += (int64_t)n_new;
@@ -2242,13 +2091,14 @@ int ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, i
     return 0;
 }
 
-int ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first_u, int n, float* mid) {
+static int pre_stream_read_mid(ft8rx_handle* h, const char* who, int which, uint64_t k_first_u, int n, float* mid) {
     if (!h) return -1;
-    const ft8rx_handle::RatStream& s = h->rts;
-    if (!s.open) { set_err(h, "ft8rx_ddc_rat_stream_read_mid: no rational stream is open (ft8rx_ddc_rat_stream_open)"); return -1; }
-    const int64_t k_first = (int64_t)k_first_u, k_origin = ddcrat::k_origin(s.n_origin, s.L, s.M), cap = h->ds.cap;
+    const ft8rx_handle::PreStream* ps = pre_stream_of(h, who, which, true);
+    if (!ps) return -1;
+    const ft8rx_handle::PreStream& s = *ps;
+    const int64_t k_first = (int64_t)k_first_u, k_origin = ddcpre::k_origin(s.n_origin, s.st.L, s.st.M), cap = h->ds.cap;
     if (n < 1 || !mid || k_first < k_origin || k_first + n > s.k_done || k_first < s.k_done - cap) {
-        set_err(h, "ft8rx_ddc_rat_stream_read_mid: intermediate samples [%lld, %lld) are not all held (held: %lld .. %lld)", (long long)k_first,
+        set_err(h, "%s: intermediate samples [%lld, %lld) are not all held (held: %lld .. %lld)", who, (long long)k_first,
                 (long long)(k_first + n), (long long)(s.k_done - cap > k_origin ? s.k_done - cap : k_origin), (long long)s.k_done);
         return -1;
     }
@@ -2265,15 +2115,38 @@ int ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first_u, int n, fl
     return 0;
 }
 
-int ft8rx_ddc_rat_stream_close(ft8rx_handle* h) {
+static int pre_stream_close(ft8rx_handle* h, const char* who, int which) {
     if (!h) return -1;
-    if (!h->rts.open) { set_err(h, "ft8rx_ddc_rat_stream_close: no rational stream is open"); return -1; }
+    if (!pre_stream_of(h, who, which, false)) return -1;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes and gathers that still use the buffers
-    ddr_stream_release(h);
+    pre_stream_release(h);
     ddc_stream_release(h);
     return 0;
 }
+
+int ft8rx_ddc_wide_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
+                               int keep_f32, double* f_mixed_hz) {
+    return pre_stream_open(h, "ft8rx_ddc_wide_stream_open", PRE_WIDE, kind, rate_hz, n_out, f_dial_hz, gain, n_origin, keep_f32, f_mixed_hz);
+}
+int ft8rx_ddc_rat_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain, uint64_t n_origin,
+                              int keep_f32, double* f_mixed_hz) {
+    return pre_stream_open(h, "ft8rx_ddc_rat_stream_open", PRE_RAT, kind, rate_hz, n_out, f_dial_hz, gain, n_origin, keep_f32, f_mixed_hz);
+}
+int ft8rx_ddc_wide_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+    return pre_stream_push(h, "ft8rx_ddc_wide_stream_push", PRE_WIDE, in, n_new, on_device, m_produced);
+}
+int ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced) {
+    return pre_stream_push(h, "ft8rx_ddc_rat_stream_push", PRE_RAT, in, n_new, on_device, m_produced);
+}
+int ft8rx_ddc_wide_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid) {
+    return pre_stream_read_mid(h, "ft8rx_ddc_wide_stream_read_mid", PRE_WIDE, k_first, n, mid);
+}
+int ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid) {
+    return pre_stream_read_mid(h, "ft8rx_ddc_rat_stream_read_mid", PRE_RAT, k_first, n, mid);
+}
+int ft8rx_ddc_wide_stream_close(ft8rx_handle* h) { return pre_stream_close(h, "ft8rx_ddc_wide_stream_close", PRE_WIDE); }
+int ft8rx_ddc_rat_stream_close(ft8rx_handle* h) { return pre_stream_close(h, "ft8rx_ddc_rat_stream_close", PRE_RAT); }
 
 int ft8rx_set_search_mask(ft8rx_handle* h, const uint8_t* mask, int n_frames) {
     if (!h) return -1;

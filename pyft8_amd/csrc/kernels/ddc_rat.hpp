@@ -6,7 +6,7 @@
 //   v[k] = g0 sum_{0 <= j < N, j = t_k (mod L)} h[j] u[(t_k - j) / L]
 //        = g0 e^{-2 pi i (w0 b_k mod 2^32) / 2^32} sum_{i < P} T[phi_k][i] x[b_k - i]     b_k = t_k / L, phi_k = t_k mod L, P = ceil(N / L)
 //   T[phi][i] = h[phi + i L] e^{+2 pi i (w0 i mod 2^32) / 2^32}                      per channel, zero from N on, evaluated in double and
-//                                                                                  rounded once (ft8rx.hip: ddr_tables)
+//                                                                                  rounded once (ft8rx.hip: pre_fill_rat)
 // All index arithmetic is in 64-bit integers (n < 2^52, L <= 320).  The tile is written once (ddr_tile) and used by two kernels:
 // k_ddc_rat (one call, the input an array) and k_ddc_rat_stream (a continuous stream: the input is the history ring and the chunk just
 // pushed).  A block owns `tk` consecutive outputs of one channel (blockIdx.y).  Two regimes, a property of the rate alone
@@ -17,8 +17,8 @@
 //         kept in LDS (newest first, so that a lane's reads run with its taps); wave w makes outputs w, w + 4, w + 8, w + 12 of the tile,
 //         its lane l the taps i = l (mod 64) in ascending order; then a butterfly over the lanes.
 // The order of an output's sum depends on the plan, phi_k, i and the lane alone: an output is the same bits wherever its tile or its
-// chunk begins.  The host side (design of h, the tables, argument checks, launches, the stream's state) is in ft8rx.hip, the index
-// arithmetic in ddc_rat_ring.hpp.
+// chunk begins.  The host side (design of h, the tables, argument checks, launches, the stream's state) is the one pre-stage path of
+// ft8rx.hip, the index arithmetic in ddc_rat_ring.hpp and ddc_pre_ring.hpp.
 #pragma once
 
 #define DDR_NT 256                     // threads per block: 4 waves

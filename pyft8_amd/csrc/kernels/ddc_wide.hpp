@@ -3,7 +3,7 @@
 // down-converter of kernels/ddc.hpp takes from there (k_ddc / k_ddc_stream, unchanged).
 //   u[n] = x[n] e^{-2 pi i (w0 n mod 2^32) / 2^32}        x = 0 outside the stream
 //   v[k] = g0 sum_j h0[j] u[k R0 + j - C0]                = g0 e^{-2 pi i (w0 (k R0 - C0) mod 2^32) / 2^32} sum_j W[j] x[k R0 + j - C0]
-//   W[j] = h0[j] e^{-2 pi i (w0 j mod 2^32) / 2^32}       per channel, evaluated in double and rounded once (ft8rx.hip: ddw_tables)
+//   W[j] = h0[j] e^{-2 pi i (w0 j mod 2^32) / 2^32}       per channel, evaluated in double and rounded once (ft8rx.hip: pre_fill_wide)
 // The tile is written once (ddw_tile) and used by two kernels: k_ddc_pre (one call, the input an array) and k_ddc_pre_stream (a
 // continuous stream: the input is the history ring and the chunk just pushed).  A block owns `tk` consecutive outputs of one channel
 // (blockIdx.y; the channels of a tile run next to each other and share the input in L2).  The taps go by in pieces of DDW_JP: per piece
@@ -11,8 +11,8 @@
 // w, w + 4, w + 8, w + 12 of the tile, its lane l the taps j = l (mod 64) of all of them in ascending order, so that a table entry
 // (read coalesced, out of L2) serves up to four outputs and every LDS read is 64 consecutive samples.  Then a butterfly over the
 // lanes.  The order of each sum depends on j and the lane alone: an output is the same bits wherever its tile begins.
-// The host side (design of h0, the tables, argument checks, launches, the stream's state) is in ft8rx.hip, the index arithmetic in
-// ddc_wide_ring.hpp.
+// The host side (design of h0, the tables, argument checks, launches, the stream's state) is the one pre-stage path of ft8rx.hip
+// (DESIGN.md section 16.4), the index arithmetic in ddc_wide_ring.hpp and ddc_pre_ring.hpp.
 #pragma once
 
 #define DDW_NT 256                     // threads per block: 4 waves

@@ -5,6 +5,8 @@ The GPU stage is ft8rx_ddc_rat* (Handle.ddc_rat, Handle.ddc_rat_stream_*, Receiv
 the plan of a rate and the taps of the prototype (both from the library, the single source), the frequency words, and the float64 twins
 of the definition.  The twins make only the intermediate samples that are asked for, by direct dot products over the taps of each
 sample's phase."""
+import sys
+
 import numpy as np
 
 from . import _lib
@@ -80,16 +82,7 @@ def frequency_words(rate, f_dial_hz):
     """(w0, f0, dial_mid, f_mixed_hz) of a dial `f_dial_hz` from the stream's centre: the resampler's 32-bit frequency word, the
     frequency it really mixes (in [-rate/2, rate/2)), the dial left for the down-converter behind it (f_dial - f0, about -3000 Hz) and
     the dial the whole chain really mixes."""
-    rate_mid = plan(rate)[0]
-    w0 = int(np.rint((float(f_dial_hz) + 3000.0) / float(rate) * 4294967296.0)) % (1 << 32)
-    f0 = w0 * float(rate) / 4294967296.0
-    if f0 >= 0.5 * rate:
-        f0 -= rate
-    d = float(f_dial_hz) - f0
-    d -= rate * np.rint(d / rate)
-    f = f0 + _ddc.frequency_word(rate_mid, d)[1]
-    f = f - rate if f >= 0.5 * rate else f + rate if f < -0.5 * rate else f
-    return w0, f0, float(d), float(f)
+    return _dw._words(rate, plan(rate)[0], f_dial_hz)
 
 
 def pack(samples, kind):
@@ -117,13 +110,7 @@ def sample_values(x, kind):
     a = np.asarray(x)
     if a.ndim == 1 and (a.dtype.kind == "c" if is_iq(kind) else a.dtype == np.float64):
         return a.astype(np.complex128 if is_iq(kind) else np.float64)
-    a, _ = pack(x, kind)
-    a = a.astype(np.float64)
-    if kind == IQ_U8:
-        a = 256.0 * (a - 127.5)
-    elif kind == IQ_I8:
-        a = 256.0 * a
-    return a[:, 0] + 1j * a[:, 1] if is_iq(kind) else a
+    return _dw._values(pack(x, kind)[0], kind, is_iq(kind))
 
 
 def phase_table(rate, w0=0):
@@ -185,20 +172,10 @@ def origin_ok(n_origin, rate):
     return 0 <= n_origin <= N_MAX and (n_origin * L) % M == 0 and (n_origin * L // M) % (TILE * (rate_mid // 12000)) == 0
 
 
-def _reference(xv, iq, rate, f_dial_hz, gain):
-    rate_mid = plan(rate)[0]
-    if len(xv) > 15 * rate:
-        raise _lib.Ft8rxError(f"x: {len(xv)} samples > {15 * rate} (15 s at {rate} Hz)")
-    _, _, dial_mid, f_mixed = frequency_words(rate, f_dial_hz)
-    v = _mid(xv, iq, rate, f_dial_hz, 0, mid_count(len(xv), rate), 0)
-    y, _ = _ddc.reference(v, _ddc.IQ_F32, rate_mid, dial_mid, gain)
-    return y, f_mixed
-
-
 def reference(x, kind, rate, f_dial_hz, gain=1.0):
     """The float64 twin of the whole chain for one cycle and one channel -> (y float64 [180000], f_mixed_hz): the resampler, then
     ddc.reference on its output as an IQ stream at rate_mid with the dial f_dial - f0.  The frame is rint(y) saturated to int16."""
-    return _reference(sample_values(x, kind), is_iq(kind), rate, f_dial_hz, gain)
+    return _dw._reference(sys.modules[__name__], sample_values(x, kind), is_iq(kind), rate, f_dial_hz, gain)
 
 
 def reference_stream(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin=0, gain=1.0):
@@ -212,16 +189,7 @@ def reference_stream(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin=0, gain=1.0)
         raise _lib.Ft8rxError(f"outputs [{m_lo}, {m_hi}): need m_lo < m_hi")
     if not origin_ok(n_origin, rate):
         raise _lib.Ft8rxError(f"n_origin {n_origin}: n_origin L / M must be an integer multiple of {TILE * D} (1008 rate_mid / 12000)")
-    dial_mid = frequency_words(rate, f_dial_hz)[2]
-    h1, h2 = _ddc.taps(rate_mid, 1), _ddc.taps(rate_mid, 2)
-    reach = (len(h2) - 1) // 2 * (D // 2) + (len(h1) - 1) // 2             # intermediate samples an output reaches each way
-    k_origin = n_origin * L // M
-    k_lo, k_hi = max(m_lo * D - reach, k_origin), (m_hi - 1) * D + reach + 1
-    if k_hi <= k_lo:
-        return np.zeros(m_hi - m_lo)
-    v = _mid(sample_values(x, kind), is_iq(kind), rate, f_dial_hz, k_lo, k_hi, n_origin)
-    # the intermediate stream is zero before k_origin and the outputs asked for reach nothing before k_lo: it may begin at k_lo
-    return _ddc.reference_stream(v, _ddc.IQ_F32, rate_mid, dial_mid, m_lo, m_hi, n_origin=k_lo, gain=gain)
+    return _dw._reference_stream(sys.modules[__name__], x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin, n_origin * L // M, gain)
 
 
 def iq_from_wav(path):

@@ -5,6 +5,8 @@ The GPU stage is ft8rx_ddc_wide* (Handle.ddc_wide, Handle.ddc_wide_stream_*, Rec
 rate and the taps of the pre-filter (both from the library, the single source), the frequency words, and the float64 twins of the
 definition.  The twins make only the intermediate samples that are asked for, by direct dot products, so that the 64.8 MHz cases need
 neither the whole stream at once nor a long FFT."""
+import sys
+
 import numpy as np
 
 from . import _lib
@@ -69,11 +71,8 @@ def taps(rate):
     return buf[:n].copy()
 
 
-def frequency_words(rate, f_dial_hz):
-    """(w0, f0, dial_mid, f_mixed_hz) of a dial `f_dial_hz` from the stream's centre: the pre-stage's 32-bit frequency word, the
-    frequency it really mixes (in [-rate/2, rate/2)), the dial left for the down-converter behind it (f_dial - f0, about -3000 Hz) and
-    the dial the whole chain really mixes."""
-    rate_mid, _ = plan(rate)
+def _words(rate, rate_mid, f_dial_hz):
+    """frequency_words behind the plan (this module's and ddc_rat's)"""
     w0 = int(np.rint((float(f_dial_hz) + 3000.0) / float(rate) * 4294967296.0)) % (1 << 32)
     f0 = w0 * float(rate) / 4294967296.0
     if f0 >= 0.5 * rate:
@@ -83,6 +82,13 @@ def frequency_words(rate, f_dial_hz):
     f = f0 + _ddc.frequency_word(rate_mid, d)[1]
     f = f - rate if f >= 0.5 * rate else f + rate if f < -0.5 * rate else f
     return w0, f0, float(d), float(f)
+
+
+def frequency_words(rate, f_dial_hz):
+    """(w0, f0, dial_mid, f_mixed_hz) of a dial `f_dial_hz` from the stream's centre: the pre-stage's 32-bit frequency word, the
+    frequency it really mixes (in [-rate/2, rate/2)), the dial left for the down-converter behind it (f_dial - f0, about -3000 Hz) and
+    the dial the whole chain really mixes."""
+    return _words(rate, plan(rate)[0], f_dial_hz)
 
 
 def pack(samples, kind):
@@ -106,13 +112,17 @@ def sample_values(x, kind):
     a = np.asarray(x)
     if a.ndim == 1 and a.dtype.kind == ("c" if is_iq(kind) else "f"):
         return a.astype(np.complex128 if is_iq(kind) else np.float64)
-    a, _ = pack(x, kind)
+    return _values(pack(x, kind)[0], kind, is_iq(kind))
+
+
+def _values(a, kind, iq):
+    """packed samples (this module's kinds and ddc_rat's) -> float64 [n] or complex128 [n]: the 8-bit kinds on the int16 scale"""
     a = a.astype(np.float64)
     if kind == IQ_U8:
         a = 256.0 * (a - 127.5)
     elif kind == IQ_I8:
         a = 256.0 * a
-    return a[:, 0] + 1j * a[:, 1] if is_iq(kind) else a
+    return a[:, 0] + 1j * a[:, 1] if iq else a
 
 
 def _phasor(p):
@@ -162,12 +172,13 @@ def mid_count(n_samples, rate):
     return min((n_samples - 1 + (len(taps(rate)) - 1) // 2) // R0 + 1, NSAMP * (rate_mid // 12000))
 
 
-def _reference(xv, iq, rate, f_dial_hz, gain):
-    rate_mid, _ = plan(rate)
+def _reference(mod, xv, iq, rate, f_dial_hz, gain):
+    """reference() of `mod` (this module or ddc_rat: its plan, frequency words, _mid and mid_count) on sample values"""
+    rate_mid = mod.plan(rate)[0]
     if len(xv) > 15 * rate:
         raise _lib.Ft8rxError(f"x: {len(xv)} samples > {15 * rate} (15 s at {rate} Hz)")
-    _, _, dial_mid, f_mixed = frequency_words(rate, f_dial_hz)
-    v = _mid(xv, iq, rate, f_dial_hz, 0, mid_count(len(xv), rate), 0)
+    _, _, dial_mid, f_mixed = mod.frequency_words(rate, f_dial_hz)
+    v = mod._mid(xv, iq, rate, f_dial_hz, 0, mod.mid_count(len(xv), rate), 0)
     y, _ = _ddc.reference(v, _ddc.IQ_F32, rate_mid, dial_mid, gain)
     return y, f_mixed
 
@@ -175,7 +186,22 @@ def _reference(xv, iq, rate, f_dial_hz, gain):
 def reference(x, kind, rate, f_dial_hz, gain=1.0):
     """The float64 twin of the whole chain for one cycle and one channel -> (y float64 [180000], f_mixed_hz): the pre-stage, then
     ddc.reference on its output as an IQ stream at rate_mid with the dial f_dial - f0.  The frame is rint(y) saturated to int16."""
-    return _reference(sample_values(x, kind), is_iq(kind), rate, f_dial_hz, gain)
+    return _reference(sys.modules[__name__], sample_values(x, kind), is_iq(kind), rate, f_dial_hz, gain)
+
+
+def _reference_stream(mod, x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin, k_origin, gain):
+    """reference_stream() of `mod` behind its checks of the origin, whose intermediate sample is k_origin"""
+    rate_mid = mod.plan(rate)[0]
+    D = rate_mid // 12000
+    dial_mid = mod.frequency_words(rate, f_dial_hz)[2]
+    h1, h2 = _ddc.taps(rate_mid, 1), _ddc.taps(rate_mid, 2)
+    reach = (len(h2) - 1) // 2 * (D // 2) + (len(h1) - 1) // 2             # intermediate samples an output reaches each way
+    k_lo, k_hi = max(m_lo * D - reach, k_origin), (m_hi - 1) * D + reach + 1
+    if k_hi <= k_lo:
+        return np.zeros(m_hi - m_lo)
+    v = mod._mid(mod.sample_values(x, kind), mod.is_iq(kind), rate, f_dial_hz, k_lo, k_hi, n_origin)
+    # the intermediate stream is zero before k_origin and the outputs asked for reach nothing before k_lo: it may begin at k_lo
+    return _ddc.reference_stream(v, _ddc.IQ_F32, rate_mid, dial_mid, m_lo, m_hi, n_origin=k_lo, gain=gain)
 
 
 def reference_stream(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin=0, gain=1.0):
@@ -189,13 +215,4 @@ def reference_stream(x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin=0, gain=1.0)
         raise _lib.Ft8rxError(f"outputs [{m_lo}, {m_hi}) / n_origin {n_origin}: need m_lo < m_hi and n_origin >= 0")
     if n_origin % (TILE * D * R0):
         raise _lib.Ft8rxError(f"n_origin {n_origin} is not a multiple of {TILE * D * R0} (1008 rate / 12000)")
-    dial_mid = frequency_words(rate, f_dial_hz)[2]
-    h1, h2 = _ddc.taps(rate_mid, 1), _ddc.taps(rate_mid, 2)
-    reach = (len(h2) - 1) // 2 * (D // 2) + (len(h1) - 1) // 2             # intermediate samples an output reaches each way
-    k_origin = n_origin // R0
-    k_lo, k_hi = max(m_lo * D - reach, k_origin), (m_hi - 1) * D + reach + 1
-    if k_hi <= k_lo:
-        return np.zeros(m_hi - m_lo)
-    v = _mid(sample_values(x, kind), is_iq(kind), rate, f_dial_hz, k_lo, k_hi, n_origin)
-    # the intermediate stream is zero before k_origin and the outputs asked for reach nothing before k_lo: it may begin at k_lo
-    return _ddc.reference_stream(v, _ddc.IQ_F32, rate_mid, dial_mid, m_lo, m_hi, n_origin=k_lo, gain=gain)
+    return _reference_stream(sys.modules[__name__], x, kind, rate, f_dial_hz, m_lo, m_hi, n_origin, n_origin // R0, gain)

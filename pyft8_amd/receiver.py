@@ -904,34 +904,18 @@ class Receiver:
         (ft8rx_ddc_rat); a rate none of the three takes is refused, naming the rate.  Without it every rate
         behaves and is refused as it always was."""
         from . import ddc as _ddc
-        from . import ddc_wide as _dw
         from . import ddc_rat as _dr
         a = np.asarray(samples)
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
             raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
-        wide = sample_rate not in _ddc.RATES and _dw.accepts(sample_rate)
-        rat = bool(resample) and sample_rate not in _ddc.RATES and not wide
-        if rat:                                 # ONE stream through the rational resampler (ft8rx_ddc_rat, DESIGN.md section 16.3)
-            if not _dr.accepts(sample_rate):
-                raise _lib.Ft8rxError(f"rate {sample_rate} is taken by none of ddc, ddc_wide and ddc_rat")
-            kind = _dr.kind_of(a, iq)
-            if _dr.is_iq(kind) and not iq:
+        mod = _wide_in.front_end(sample_rate, resample)
+        if mod is not _ddc:                       # ONE stream through a pre-stage: ft8rx_ddc_wide (DESIGN.md section 16.2) or ft8rx_ddc_rat (16.3)
+            kind = mod.kind_of(a, iq)
+            if mod.is_iq(kind) and not iq:
                 raise _lib.Ft8rxError("samples are complex: pass iq=True")
-            if a.ndim == (2 if a.dtype.kind == "c" else 3 if iq else 2):
-                if a.shape[0] != 1:
-                    raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {sample_rate} Hz -- a resampled rate takes one stream")
-                a = a[0]
-            arr, _ = _dr.pack(a, kind)
-            n_streams = 1
-        elif wide:                                # ONE stream through the pre-decimator (ft8rx_ddc_wide, DESIGN.md section 16.2)
-            kind = _dw.kind_of(a, iq)
-            if a.ndim == (3 if iq else 2):
-                if a.shape[0] != 1:
-                    raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {sample_rate} Hz -- a wide rate takes one stream")
-                a = a[0]
-            arr, _ = _dw.pack(a, kind)
+            arr, _ = mod.pack(_wide_in.one_stream(mod, a, iq, sample_rate), kind)
             n_streams = 1
         else:
             cplx = np.iscomplexobj(a)
@@ -960,14 +944,9 @@ class Receiver:
         args.update(kw)
         with self._hlock:
             h = self._handle(n_out)
-            if rat:
-                if any(int(j) != 0 for j in src):
-                    raise _lib.Ft8rxError(f"src: {list(src)} -- a resampled rate takes one stream, every channel reads stream 0")
-                h.ddc_rat(arr, kind, int(sample_rate), dials)
-            elif wide:
-                if any(int(j) != 0 for j in src):
-                    raise _lib.Ft8rxError(f"src: {list(src)} -- a wide rate takes one stream, every channel reads stream 0")
-                h.ddc_wide(arr, kind, int(sample_rate), dials)
+            if mod is not _ddc:
+                _wide_in.stream_zero(mod, src)
+                (h.ddc_rat if mod is _dr else h.ddc_wide)(arr, kind, int(sample_rate), dials)
             else:
                 h.ddc(arr, kind, int(sample_rate), src, dials)
             return self._decode_frames_locked(None, n_out, bands=bands, **args)

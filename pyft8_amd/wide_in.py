@@ -24,6 +24,39 @@ T_CYC = 15
 HEAD_MAX = 6000               # a cycle is decoded if at most this many of its first outputs lie before the stream (0.5 s, taken as zero)
 
 
+_ONE_STREAM = {_dw: "wide", _dr: "resampled"}         # the rates that take ONE stream through a pre-stage, in messages
+
+
+def front_end(rate, resample):
+    """The module of the path a rate takes: ddc for the rates of ddc.RATES (12 .. 192 kHz); ddc_wide for a wide rate (ddc_wide.plan:
+    ONE stream through the pre-decimator); with `resample` ddc_rat for any other rate it accepts (ONE stream
+    through the rational resampler, section 16.3), and a rate none of the three takes is refused here.  Without `resample` every
+    other rate is ddc's, which refuses it as it always did."""
+    if rate not in _ddc.RATES:
+        if _dw.accepts(rate):
+            return _dw
+        if resample:
+            if not _dr.accepts(rate):
+                raise _lib.Ft8rxError(f"rate {rate} is taken by none of ddc, ddc_wide and ddc_rat")
+            return _dr
+    return _ddc
+
+
+def one_stream(mod, a, iq, rate):
+    """The samples of a pre-stage rate (mod: ddc_wide or ddc_rat) as ONE stream: [1][n(, 2)] -> [n(, 2)]; more streams are refused"""
+    if a.ndim == (2 if a.dtype.kind == "c" else 3 if iq else 2):
+        if a.shape[0] != 1:
+            raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {rate} Hz -- a {_ONE_STREAM[mod]} rate takes one stream")
+        a = a[0]
+    return a
+
+
+def stream_zero(mod, src):
+    """... and every channel reads that stream"""
+    if any(int(j) != 0 for j in src):
+        raise _lib.Ft8rxError(f"src: {list(src)} -- a {_ONE_STREAM[mod]} rate takes one stream, every channel reads stream 0")
+
+
 def _last_input(D):
     """Offset of the last input a tile needs from the input of its first output (csrc/ddc_ring.hpp: last)"""
     r2 = 1 if D == 1 else 2
@@ -86,14 +119,11 @@ class WideIn:
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
-        # a wide rate (ddc_wide.plan: 240 kHz .. 129.6 MHz) is ONE stream through the pre-decimator (ft8rx_ddc_wide_stream_*, DESIGN.md
-        # section 16.2); D is then the input samples per 12 kHz output all the same
-        self.wide = self.sample_rate not in _ddc.RATES and _dw.accepts(self.sample_rate)
-        # resample=True: a rate neither of them takes is ONE stream through the rational resampler (ft8rx_ddc_rat_stream_*, section 16.3);
-        # sample_rate / 12000 is then no integer, and input counts become output counts by exact integer arithmetic (_outputs)
-        self.rat = bool(resample) and self.sample_rate not in _ddc.RATES and not self.wide
-        if self.rat and not _dr.accepts(self.sample_rate):
-            raise _lib.Ft8rxError(f"rate {self.sample_rate} is taken by none of ddc, ddc_wide and ddc_rat")
+        # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a wide rate
+        # D is the input samples per 12 kHz output all the same; at a resampled rate sample_rate / 12000 is no integer, and input counts
+        # become output counts by exact integer arithmetic (_outputs)
+        self.mod = front_end(self.sample_rate, resample)
+        self.wide, self.rat = self.mod is _dw, self.mod is _dr
         self.D = None if self.rat else self.sample_rate // 12000 if self.wide else _ddc.decimation(self.sample_rate)
         self.iq = bool(iq)
         self.dials = [float(f) for f in dial_offsets_hz]
@@ -125,12 +155,10 @@ class WideIn:
         """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
         a = np.asarray(chunk)
         cplx = np.iscomplexobj(a)
-        if self.rat:
-            self.kind = _dr.kind_of(a, self.iq)
-            if not self.iq and _dr.is_iq(self.kind):
+        if self.mod is not _ddc:
+            self.kind = self.mod.kind_of(a, self.iq)
+            if not self.iq and self.mod.is_iq(self.kind):
                 raise _lib.Ft8rxError("samples are complex: pass iq=True")
-        elif self.wide:
-            self.kind = _dw.kind_of(a, self.iq)
         elif cplx and not self.iq:
             raise _lib.Ft8rxError("samples are complex: pass iq=True")
         elif self.iq:
@@ -138,10 +166,8 @@ class WideIn:
         else:
             self.kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
         _, self.n_streams, _ = self._pack(a)
-        if self.wide and (self.src is not None and any(self.src)):
-            raise _lib.Ft8rxError(f"src: {self.src} -- a wide rate takes one stream, every channel reads stream 0")
-        if self.rat and (self.src is not None and any(self.src)):
-            raise _lib.Ft8rxError(f"src: {self.src} -- a resampled rate takes one stream, every channel reads stream 0")
+        if self.mod is not _ddc and self.src is not None:
+            stream_zero(self.mod, self.src)
         if self.src is None:
             if self.n_streams != 1 and self.n_streams != self.n_channels:
                 raise _lib.Ft8rxError(f"src: {self.n_streams} streams and {self.n_channels} channels -- say which stream each channel reads")
@@ -151,23 +177,16 @@ class WideIn:
         self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            if self.rat:
-                self.f_mixed_hz = h.ddc_rat_stream_open(self.kind, self.sample_rate, self.dials)
-            elif self.wide:
-                self.f_mixed_hz = h.ddc_wide_stream_open(self.kind, self.sample_rate, self.dials)
+            if self.mod is not _ddc:
+                self.f_mixed_hz = (h.ddc_rat_stream_open if self.rat else h.ddc_wide_stream_open)(self.kind, self.sample_rate, self.dials)
             else:
                 self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
 
     def _pack(self, chunk):
         """-> ([n_streams][n] samples packed for self.kind, n_streams, n); a wide or a resampled rate: one stream, [1][n]"""
-        if not (self.wide or self.rat):
+        if self.mod is _ddc:
             return _ddc.pack(chunk, self.kind)
-        a = np.asarray(chunk)
-        if a.ndim == (2 if a.dtype.kind == "c" else 3 if self.iq else 2):
-            if a.shape[0] != 1:
-                raise _lib.Ft8rxError(f"samples: {a.shape[0]} streams at {self.sample_rate} Hz -- a {'resampled' if self.rat else 'wide'} rate takes one stream")
-            a = a[0]
-        a, n = (_dr if self.rat else _dw).pack(a, self.kind)
+        a, n = self.mod.pack(one_stream(self.mod, np.asarray(chunk), self.iq, self.sample_rate), self.kind)
         return a[None], 1, n
 
     def _push(self, a, real):

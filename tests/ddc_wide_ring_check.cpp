@@ -3,7 +3,8 @@
 // one second of samples against a model of the history ring and checks, for six rates: the count of complete intermediate samples
 // against its definition, that every input a new intermediate sample reads lies before the origin, in the chunk or still in the ring
 // at the position the kernel computes (kernels/ddc_wide.hpp: k_ddc_pre_stream), and the split of the history update -- at the origin,
-// across n = 2^32 and at 2^50.  Then the plans, the tile sizes and the one-shot count.
+// across n = 2^32 and at 2^50.  Then the plans, the tile sizes and the one-shot count, and the shared forms of ddc_pre_ring.hpp at
+// L = 1, M = R0 against the wide stage's own closed forms and its modulus rule for an origin.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +64,48 @@ static void check_stream(int64_t rate, int64_t N0, int64_t n_origin, uint32_t se
     }
 }
 
+// The closed forms the wide header had before the shared arithmetic of ddc_pre_ring.hpp took their place, written out here so that the
+// expected values do not come from the code under test
+static int64_t wide_mid_done(int64_t n_origin, int64_t n_end, int64_t N0, int64_t R0) {
+    const int64_t k0 = n_origin / R0, have = n_end - 1 - (N0 - 1) / 2;
+    if (have < 0) return k0;
+    const int64_t k = have / R0 + 1;
+    return k > k0 ? k : k0;
+}
+static int64_t wide_mid_count(int64_t n_samples, int64_t N0, int64_t R0, int64_t cap) {
+    if (n_samples < 1) return 1;
+    const int64_t k = (n_samples - 1 + (N0 - 1) / 2) / R0 + 1;
+    return k < cap ? k : cap;
+}
+static bool wide_origin_ok(uint64_t n_origin, int64_t rate) {
+    return n_origin % (uint64_t)(1008 * (rate / 12000)) == 0 && n_origin <= ((uint64_t)1 << 62);
+}
+
+// the shared forms at L = 1, M = R0 against those, around tile and tap boundaries
+static void check_shared_forms(int64_t rate, int64_t N0) {
+    const Plan p = plan(rate);
+    const int64_t R0 = p.R0, C0 = (N0 - 1) / 2, tk = tile_outputs(R0), grid = 1008 * (rate / 12000), cap = 180000 * (p.rate_mid / 12000);
+    const int64_t origins[4] = {0, grid, 5 * grid, ((int64_t)1 << 40) / grid * grid};
+    const int64_t around[8] = {0, C0, N0, R0, tk * R0, tk * R0 + C0, 3 * tk * R0 - C0 + N0, grid};
+    for (int64_t o : origins) {
+        CHECK(ddcpre::k_origin(o, 1, R0) == o / R0 && ddcpre::k_origin(o, 1, R0) * R0 == o);
+        for (int64_t a : around)
+            for (int64_t d = -2; d <= 2; d++) {
+                const int64_t n_end = o + a + d;
+                if (n_end >= 0) CHECK(ddcpre::mid_done(o, n_end, N0, 1, R0) == wide_mid_done(o, n_end, N0, R0));
+                const int64_t n = a + d;
+                CHECK(ddcpre::mid_count(n, N0, 1, R0, cap) == wide_mid_count(n, N0, R0, cap));
+                CHECK(ddcpre::mid_count(n, N0, 1, R0, 7) == wide_mid_count(n, N0, R0, 7));
+                // the origin rule: n_origin L / M an integer on the tile grid of the stage behind == a multiple of 1008 rate / 12000
+                const int64_t cand = o + (a % 3 == 0 ? a : R0 * a) + d;
+                if (cand >= 0) CHECK(ddcpre::origin_ok(cand, N_MAX, p.rate_mid, 1, R0) == wide_origin_ok((uint64_t)cand, rate));
+            }
+        CHECK(ddcpre::origin_ok(o, N_MAX, p.rate_mid, 1, R0) && !ddcpre::origin_ok(o + R0, N_MAX, p.rate_mid, 1, R0) && !ddcpre::origin_ok(o + grid / 2, N_MAX, p.rate_mid, 1, R0));
+    }
+    CHECK(!ddcpre::origin_ok(-grid, N_MAX, p.rate_mid, 1, R0) && !ddcpre::origin_ok(N_MAX / grid * grid + grid, N_MAX, p.rate_mid, 1, R0));
+    CHECK(ddcpre::origin_ok(N_MAX / grid * grid, N_MAX, p.rate_mid, 1, R0) == wide_origin_ok((uint64_t)(N_MAX / grid * grid), rate));
+}
+
 int main() {
     const int64_t rates[6] = {240000, 384000, 768000, 2400000, 64800000, 129600000};
     const int64_t mids[6] = {48000, 192000, 192000, 96000, 96000, 192000}, r0s[6] = {5, 2, 4, 25, 675, 675};
@@ -99,6 +142,12 @@ int main() {
     for (int64_t n = 1; n < 400; n++) {
         const int64_t k = mid_count(n, 33, 5, 1 << 30);
         CHECK((k - 1) * 5 - 16 <= n - 1 && k * 5 - 16 > n - 1);                                // k - 1 still reaches the last input, k does not
+    }
+    // the shared arithmetic at L = 1, M = R0 is the wide stage's own: a small sweep of accepted R0 (N0 = 6 R0 + 1 or + 3, odd, like the designs)
+    for (int i = 0; i < 6; i++) check_shared_forms(rates[i], taps[i]);
+    for (int64_t r = RATE_MIN; r <= RATE_MAX; r += 48000 * 37) {
+        const Plan p = plan(r);
+        if (p.rate_mid) check_shared_forms(r, (6 * p.R0 + 1) | 1);
     }
     printf("ddc wide ring arithmetic: %ld checked\n", checks);
     return 0;
