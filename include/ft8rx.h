@@ -588,6 +588,37 @@ int  ft8rx_ddc_rat_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n
 int  ft8rx_ddc_rat_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
 int  ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, float* mid);
 int  ft8rx_ddc_rat_stream_close(ft8rx_handle* h);
+/* Noise blanker (extension): impulse blanking of 12 kHz frames in place, an input stage like ft8rx_ddc and not a
+ * handle setting -- the blanked frames are ordinary frames.  Everything is integer arithmetic that fits int32; pyft8_amd/blanker.py holds
+ * the numpy twin, which gives the same bits.  A frame is 375 blocks of 480 samples, frames are independent.
+ *   level   m_b = the element at sorted position 240 (from 0) of the 480 values |x| of block b (|-32768| = 32768);
+ *           L_b = the element at sorted position 2 of the five values m[clamp(b + d, 0, 374)], d = -2 .. 2;
+ *   hit     sample n of block b iff L_b > 0 and 256 |x[n]| > threshold_q8 L_b (L_b = 0, digital silence: the block passes untouched);
+ *   gate    d[n] = distance to the nearest hit of the same frame; w = 0 for d <= guard, T[d - guard] for guard < d <= guard + taper,
+ *           32768 beyond; T[j] = rint(32768 * 0.5 (1 - cos(pi j / (taper + 1)))), j = 1 .. taper (ft8rx_blank_taper);
+ *   output  y[n] = (x[n] w[n] + 16384) >> 15 with an arithmetic shift: y = x where w = 32768, and a frame without hits keeps its bytes
+ *           (it is not written at all);
+ *   stats   per frame int32[4]: hits, samples with w < 32768, samples with w = 0, blocks with L_b = 0.
+ * threshold_q8 = rint(256 k) in [512, 16384] (default k = 8: 5.4 sigma of Gaussian noise, whose median |x| is 0.6745 sigma), guard in
+ * [0, 64] (default 6), taper in [0, 64] (default 6).  Anything else returns -1 with a text that names the argument. */
+#define FT8RX_BLANK_THRESHOLD_Q8_DEFAULT 2048
+#define FT8RX_BLANK_GUARD_DEFAULT        6
+#define FT8RX_BLANK_TAPER_DEFAULT        6
+#define FT8RX_BLANK_MIN_THRESHOLD_Q8     512
+#define FT8RX_BLANK_MAX_THRESHOLD_Q8     16384
+#define FT8RX_BLANK_MAX_GUARD            64
+#define FT8RX_BLANK_MAX_TAPER            64
+/* d_audio: device [n_frames][180000] int16 (aligned to a sample; 16-byte alignment takes the vector path), NULL = the staging audio;
+ * n_frames in [1, max_frames].  stats: host [n_frames][4], optional; levels: host [n_frames][375][2] = (m_b, L_b), optional, a test
+ * aid.  Waits for the batches in flight, then queues its kernels on the handle's main stream (the hit mask of every frame is complete
+ * before the first sample is rewritten); returns after completion when stats or levels is given, otherwise at once. */
+int  ft8rx_blank(ft8rx_handle* h, int16_t* d_audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats,
+                 int32_t* levels);
+/* the same from host memory: the frames are copied into the staging audio and blanked there; returns when they are
+ * (ft8rx_enqueue_batch(h, ft8rx_staging_audio(h), n_frames) is the intended next call) */
+int  ft8rx_blank_host(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats);
+/* host only, no GPU: T[1 .. taper] -> taper, and the first min(taper, cap) entries in w (w may be NULL); -1 for taper outside [0, 64] */
+int  ft8rx_blank_taper(int taper, int32_t* w, int cap);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -93,6 +93,10 @@ PROTOTYPES = {
     "ft8rx_ddc_rat_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
     "ft8rx_ddc_rat_stream_read_mid": (INT, (PTR, U64, INT, PTR)),
     "ft8rx_ddc_rat_stream_close": (INT, (PTR,)),
+    # noise blanker
+    "ft8rx_blank": (INT, (PTR, PTR, INT, I32, INT, INT, PTR, PTR)),
+    "ft8rx_blank_host": (INT, (PTR, PTR, INT, I32, INT, INT, PTR)),
+    "ft8rx_blank_taper": (INT, (INT, PTR, INT)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

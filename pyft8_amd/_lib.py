@@ -921,6 +921,27 @@ class Handle:
     def ddc_rat_stream_close(self):
         self._pre_close("ddc_rat")
 
+    # ---- noise blanker (ft8rx_blank*; pyft8_amd/blanker.py holds the twin and the parameter checks)
+    def blank(self, d_audio_ptr, n_frames, threshold_q8=2048, guard=6, taper=6, want_stats=True, want_levels=False):
+        """ft8rx_blank: blank n_frames frames in place on the device (d_audio_ptr: a raw device pointer, None = the staging audio)
+        -> stats int32 [n_frames, 4] (None without want_stats: the call is then only queued); want_levels: -> (stats, levels int32
+        [n_frames, 375, 2] = (m_b, L_b))."""
+        B = int(n_frames)
+        stats = np.zeros((max(B, 0), 4), np.int32) if want_stats else None
+        lv = np.zeros((max(B, 0), 375, 2), np.int32) if want_levels else None
+        self._chk(self._L.ft8rx_blank(self._h, d_audio_ptr or None, B, int(threshold_q8), int(guard), int(taper),
+                                      stats.ctypes.data if want_stats else None, lv.ctypes.data if want_levels else None), "ft8rx_blank")
+        return (stats, lv) if want_levels else stats
+
+    def blank_host(self, audio, threshold_q8=2048, guard=6, taper=6):
+        """ft8rx_blank_host: host frames int16 [n_frames, 180000] -> the staging audio, blanked there (enqueue(staging_ptr(), n) is the
+        next call) -> stats int32 [n_frames, 4]."""
+        audio = _audio(audio, f"blank_host: audio must be int16 [n_frames, {NSAMP}], got shape {{shape}}")
+        stats = np.zeros((len(audio), 4), np.int32)
+        self._chk(self._L.ft8rx_blank_host(self._h, audio.ctypes.data, len(audio), int(threshold_q8), int(guard), int(taper), stats.ctypes.data),
+                  "ft8rx_blank_host")
+        return stats
+
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for
         overlapped DMA.  The memory is released when the array (and every view of it) is garbage collected."""
@@ -1244,6 +1265,15 @@ def ap_patterns(my_call=None, dx_call=None):
     if L.ft8rx_ap_patterns((my_call or "").encode(), (dx_call or "").encode(), bits.ctypes.data, mask.ctypes.data) != 0:
         raise Ft8rxError(L.ft8rx_last_error(None).decode())
     return bits, mask
+
+
+def blank_taper(taper):
+    """ft8rx_blank_taper (host only): T[1 .. taper] of the noise blanker's gate, int32 [taper]"""
+    w = np.zeros(max(int(taper), 1), np.int32)
+    n = lib().ft8rx_blank_taper(int(taper), w.ctypes.data, len(w))
+    if n < 0:
+        raise Ft8rxError(f"ft8rx_blank_taper: taper {taper} outside [0, 64]")
+    return w[:n]
 
 
 def default_handle(max_frames=1):

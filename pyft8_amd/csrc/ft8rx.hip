@@ -63,6 +63,7 @@
 #include "kernels/ddc.hpp"
 #include "kernels/ddc_wide.hpp"
 #include "kernels/ddc_rat.hpp"
+#include "kernels/blanker.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -249,6 +250,10 @@ struct ft8rx_handle {
         uint32_t* d_w0 = nullptr;
         hipEvent_t ev = nullptr;
     } ps;
+    // noise blanker (ft8rx_blank, kernels/blanker.hpp; allocated on first use): (m_b, L_b) [max_frames][375][2], the
+    // hit mask [max_frames][2813] 64-bit words, the counters' tile partials [max_frames][88][4], the counters [max_frames][4] and the
+    // taper tables [65][65]
+    int32_t* d_bl_lv = nullptr; uint64_t* d_bl_mask = nullptr; int32_t* d_bl_part = nullptr; int32_t* d_bl_stats = nullptr; int32_t* d_bl_taper = nullptr;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -329,7 +334,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -2147,6 +2152,90 @@ int ft8rx_ddc_rat_stream_read_mid(ft8rx_handle* h, uint64_t k_first, int n, floa
 }
 int ft8rx_ddc_wide_stream_close(ft8rx_handle* h) { return pre_stream_close(h, "ft8rx_ddc_wide_stream_close", PRE_WIDE); }
 int ft8rx_ddc_rat_stream_close(ft8rx_handle* h) { return pre_stream_close(h, "ft8rx_ddc_rat_stream_close", PRE_RAT); }
+
+// ---- noise blanker (kernels/blanker.hpp)
+// T[1 .. R] of taper = R at t[1 .. R] (t[0] is not used): computed in double, rounded once
+static void blank_taper(int R, int32_t* t) {
+    t[0] = 0;
+    for (int j = 1; j <= R; j++) t[j] = (int32_t)nearbyint(32768.0 * 0.5 * (1.0 - cos(M_PI * (double)j / (double)(R + 1))));
+}
+
+int ft8rx_blank_taper(int taper, int32_t* w, int cap) {
+    if (taper < 0 || taper > FT8RX_BLANK_MAX_TAPER) return -1;
+    int32_t t[FT8RX_BLANK_MAX_TAPER + 1];
+    blank_taper(taper, t);
+    for (int j = 1; w && j <= taper && j <= cap; j++) w[j - 1] = t[j];
+    return taper;
+}
+
+static int blank_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_BLANK)) return 0;
+    static_assert(BLK_TAPER_ROW == FT8RX_BLANK_MAX_TAPER + 1 && BLK_HALO == FT8RX_BLANK_MAX_GUARD + FT8RX_BLANK_MAX_TAPER &&
+                  BLK_N * BLK_PER_FRAME == FT8RX_NSAMP && 8 * BLK_GROUPS == FT8RX_NSAMP && 64 * BLK_WORDS >= FT8RX_NSAMP &&
+                  BLK_TILES * BLK_NT >= BLK_GROUPS && BLK_TILES * 32 >= BLK_WORDS, "blanker geometry");
+    std::vector<int32_t> tab((size_t)BLK_TAPER_ROW * BLK_TAPER_ROW, 0);
+    for (int R = 0; R <= FT8RX_BLANK_MAX_TAPER; R++) blank_taper(R, &tab[(size_t)R * BLK_TAPER_ROW]);
+    FirstUse F(h, WS_BLANK);
+    F.dev(&h->d_bl_lv, (size_t)h->max_frames * BLK_PER_FRAME * 2);
+    F.dev(&h->d_bl_mask, (size_t)h->max_frames * BLK_WORDS);
+    F.dev(&h->d_bl_part, (size_t)h->max_frames * BLK_TILES * 4);
+    F.dev(&h->d_bl_stats, (size_t)h->max_frames * 4);
+    F.dev(&h->d_bl_taper, tab.size());
+    // (the upper half of a frame's last mask word is never written: it stays zero from here on)
+    FIRST_HIP(F, hipMemset(h->d_bl_mask, 0, sizeof(uint64_t) * (size_t)h->max_frames * BLK_WORDS));
+    FIRST_HIP(F, hipMemcpy(h->d_bl_taper, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+    return F.done();
+}
+
+static int blank_check(ft8rx_handle* h, const char* who, int n_frames, int32_t threshold_q8, int guard, int taper) {
+    if (n_frames < 1 || n_frames > h->max_frames) { set_err(h, "%s: n_frames %d outside [1, %d] (max_frames)", who, n_frames, h->max_frames); return -1; }
+    if (threshold_q8 < FT8RX_BLANK_MIN_THRESHOLD_Q8 || threshold_q8 > FT8RX_BLANK_MAX_THRESHOLD_Q8) {
+        set_err(h, "%s: threshold_q8 %d outside [%d, %d] (256 k, k = 2 .. 64)", who, (int)threshold_q8, FT8RX_BLANK_MIN_THRESHOLD_Q8, FT8RX_BLANK_MAX_THRESHOLD_Q8); return -1;
+    }
+    if (guard < 0 || guard > FT8RX_BLANK_MAX_GUARD) { set_err(h, "%s: guard %d outside [0, %d]", who, guard, FT8RX_BLANK_MAX_GUARD); return -1; }
+    if (taper < 0 || taper > FT8RX_BLANK_MAX_TAPER) { set_err(h, "%s: taper %d outside [0, %d]", who, taper, FT8RX_BLANK_MAX_TAPER); return -1; }
+    return 0;
+}
+
+// the launches on the main stream, then -- stats or levels given -- their copies and the wait for them
+static int blank_run(ft8rx_handle* h, int16_t* d_audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats, int32_t* levels) {
+    const int n_blocks = n_frames * BLK_PER_FRAME;
+    const dim3 tiles(BLK_TILES, (unsigned)n_frames);
+    with_bool(((uintptr_t)d_audio % 16) == 0, [&](auto vec) {
+        constexpr bool V = decltype(vec)::value;
+        k_blank_level<V><<<(n_blocks + BLK_NT / 64 - 1) / (BLK_NT / 64), BLK_NT, 0, h->stream>>>(d_audio, n_blocks, h->d_bl_lv);
+        k_blank_hits<V><<<tiles, BLK_NT, 0, h->stream>>>(d_audio, threshold_q8, h->d_bl_lv, reinterpret_cast<uint8_t*>(h->d_bl_mask), h->d_bl_part);
+        k_blank_gate<V><<<tiles, BLK_NT, 0, h->stream>>>(d_audio, h->d_bl_mask, guard, taper, h->d_bl_taper, h->d_bl_part);
+    });
+    if (stats) k_blank_stats<<<(4 * n_frames + BLK_NT - 1) / BLK_NT, BLK_NT, 0, h->stream>>>(h->d_bl_part, n_frames, h->d_bl_stats);
+    HIPCHK(h, hipGetLastError());
+    if (stats) HIPCHK(h, hipMemcpyAsync(stats, h->d_bl_stats, sizeof(int32_t) * 4 * (size_t)n_frames, hipMemcpyDeviceToHost, h->stream));
+    if (levels) HIPCHK(h, hipMemcpyAsync(levels, h->d_bl_lv, sizeof(int32_t) * 2 * (size_t)n_blocks, hipMemcpyDeviceToHost, h->stream));
+    if (stats || levels) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ft8rx_blank(ft8rx_handle* h, int16_t* d_audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats, int32_t* levels) {
+    if (!h) return -1;
+    if (blank_check(h, "ft8rx_blank", n_frames, threshold_q8, guard, taper)) return -1;
+    if (((uintptr_t)d_audio % sizeof(int16_t)) != 0) { set_err(h, "ft8rx_blank: d_audio is not aligned to a sample"); return -1; }
+    ENTER(h);
+    if (blank_workspaces(h)) return -2;
+    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    return blank_run(h, d_audio, n_frames, threshold_q8, guard, taper, stats, levels);
+}
+
+int ft8rx_blank_host(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats) {
+    if (!h) return -1;
+    if (blank_check(h, "ft8rx_blank_host", n_frames, threshold_q8, guard, taper)) return -1;
+    if (!audio) { set_err(h, "ft8rx_blank_host: audio is NULL"); return -1; }
+    ENTER(h);
+    if (blank_workspaces(h) || need_staging(h)) return -2;
+    HIPCHK(h, hipMemcpyAsync(h->d_audio, audio, sizeof(int16_t) * (size_t)n_frames * FT8RX_NSAMP, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = blank_run(h, h->d_audio, n_frames, threshold_q8, guard, taper, stats, nullptr)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
 
 int ft8rx_set_search_mask(ft8rx_handle* h, const uint8_t* mask, int n_frames) {
     if (!h) return -1;

@@ -18,6 +18,11 @@ PyAudio if that module is importable (reference receiver.py:252, 266-270), or an
 `audio_source` -- plus a daemon thread that stands in for Receiver.manage_cycle (receiver.py:336, 372-412): it wakes every 0.1 s on
 the `time_source` / `sleep` seam (time_utils.py:7-14) and decodes every completed cycle (poll()).  `Receiver.start()` / `.stop()`
 do the same explicitly.
+
+Noise blanker (extension): Receiver(..., noise_blanker=True | k | {"threshold": k, "guard": G, "taper": R}) blanks
+impulses in every frame that is about to be decoded -- decode_frames / decode_frames_arrays, decode_stream, the live passes of poll --
+on the GPU (ft8rx_blank) and leaves the per-frame counters of the last batch in `blanker_stats`.  The live `audio_in.search_grid` /
+`waterfall_data`, and search() on them, stay the unblanked audio.  Off (the default) nothing of it runs.
 """
 import threading as _threading
 import time as _time
@@ -25,6 +30,7 @@ import time as _time
 import numpy as np
 
 from . import _lib
+from . import blanker as _blanker
 from . import messages as _m
 from . import optins as _optins
 from . import wide_in as _wide_in
@@ -631,6 +637,14 @@ class Receiver:
         # measured reports: every message dict gains "report", the measured SNR / frequency / start time
         self.reports = bool(extension_knobs.pop("reports", False))
         self._recall_hist = {}                                # cycle start -> complete-frame message dicts (recall = True)
+        # noise blanker: None / False = off, True = the defaults, a number = the threshold k, a dict of threshold /
+        # guard / taper.  An input stage, not a handle setting: the frames are blanked on the GPU (ft8rx_blank) wherever they are about
+        # to be decoded -- decode_frames / decode_frames_arrays (once, before the first pass), decode_stream (behind the
+        # down-converter), the live passes of poll (early passes included) -- and everything behind sees ordinary frames.  The live
+        # search_grid / waterfall of audio_in, and search() on it, stay the unblanked audio.  blanker_stats: the last batch's int32
+        # [B, 4] = hits, samples with w < 32768, samples with w = 0, blocks with L_b = 0 per frame.
+        self.noise_blanker = _blanker.params(extension_knobs.pop("noise_blanker", None))
+        self.blanker_stats = None
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall:
             _optins.refuse(_optins.RECALL, _optins.active(self.cfg))
@@ -875,6 +889,15 @@ class Receiver:
         finally:
             h.set_search_mask(None)
 
+    def _decode_host(self, h, audio):
+        """Host frames -> (records, counts, events, event counts) on handle h: ft8rx_decode_batch, or -- noise blanker on -- the frames
+        go to the staging audio, are blanked there (ft8rx_blank_host) and the batch is enqueued from it."""
+        if self.noise_blanker is None:
+            return h.decode_batch(audio)
+        self.blanker_stats = h.blank_host(audio, *self.noise_blanker)
+        h.enqueue(h.staging_ptr(), len(audio))
+        return h.fetch(len(audio))
+
     def _package(self, rec, cnt, ev, evc, **kw):
         """The native host message layer for this receiver's config: ft8rx_package_batch, or ft8rx_package_batch_ext when the config
         opts into more message types (msg_types != 0; rows of _lib.MESSAGE_EXT_DTYPE)."""
@@ -967,10 +990,12 @@ class Receiver:
         if use_recall:
             h.set_recall(self._recall_entries(recall if recall is not None else [None] * B))
         if audio is None:
+            if self.noise_blanker is not None:
+                self.blanker_stats = h.blank(None, B, *self.noise_blanker)
             h.enqueue(h.staging_ptr(), B)
             rec, cnt, ev, evc = h.fetch(B)
         else:
-            rec, cnt, ev, evc = h.decode_batch(audio)
+            rec, cnt, ev, evc = self._decode_host(h, audio)
         rp = h.fetch_reports(B) if self.reports else None
         # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
         if use_recall:
@@ -1054,7 +1079,7 @@ class Receiver:
         _optins.refuse(_optins.ARRAYS, _optins.active(self.cfg))
         local = research == "local"
         h = self._handle(B)
-        rec, cnt, ev, evc = h.decode_batch(audio)
+        rec, cnt, ev, evc = self._decode_host(h, audio)
         msgs, mcnt = _lib.package_batch(rec, cnt, ev, evc, n_threads=n_threads)
         if passes <= 1:
             return msgs, mcnt, rec, cnt
@@ -1129,6 +1154,8 @@ class Receiver:
                 if prev is not None:
                     h.set_recall(self._recall_entries(prev))
                 h.ddc_stream_frame(m_first, n_have)
+                if self.noise_blanker is not None:
+                    self.blanker_stats = h.blank(None, K, *self.noise_blanker)
                 h.enqueue(h.staging_ptr(), K)
                 rec, cnt, ev, evc = h.fetch(K)
                 if prev is not None:
@@ -1170,7 +1197,7 @@ class Receiver:
                 h = self._live_handle()
                 if prev is not None:
                     h.set_recall(self._recall_entries([prev]))
-                rec, cnt, ev, evc = h.decode_batch(frame[None])
+                rec, cnt, ev, evc = self._decode_host(h, frame[None])
                 if prev is not None:
                     rrec, rcnt = h.fetch_recall(1)
                 rp = h.fetch_reports(1) if self.reports else None
@@ -1188,7 +1215,9 @@ class Receiver:
 
 def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=None, **receiver_kwargs):
     """decode_frames(audio_i16[B,180000], **receiver_kwargs) -> list[list[message dict]]  (SURVEY.md 8b); passes > 1 adds the
-    subtraction passes of Receiver.decode_frames; recall = per frame the message dicts decoded 30 s earlier (Receiver.decode_frames)."""
+    subtraction passes of Receiver.decode_frames; recall = per frame the message dicts decoded 30 s earlier (Receiver.decode_frames);
+    noise_blanker= (None / True / a threshold k / a dict of threshold, guard, taper) goes to Receiver with the other keyword arguments:
+    the frames are blanked on the GPU (ft8rx_blank_host) before the first pass."""
     audio = _as_frames(audio_i16)
     rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, **receiver_kwargs)       # reports=True: "report" in every dict
     return rx.decode_frames(audio, passes=passes, research=research, recall=recall)
