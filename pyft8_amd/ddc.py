@@ -8,12 +8,25 @@ from . import _lib
 
 REAL_I16, REAL_F32, IQ_I16, IQ_F32 = range(4)          # include/ft8rx.h FT8RX_DDC_*
 KIND_NAMES = ("real int16", "real float32", "IQ int16", "IQ float32")
+_DTYPE = {REAL_I16: np.int16, REAL_F32: np.float32, IQ_I16: np.int16, IQ_F32: np.float32}
 RATES = tuple(12000 * d for d in (1, 2, 4, 8, 16))
 NSAMP = _lib.NSAMP
 
 
 def is_iq(kind):
     return kind in (IQ_I16, IQ_F32)
+
+
+def kind_of(samples, iq):
+    """The kind of an array by its dtype: with iq IQ float32 for complex or float samples and IQ int16 for the rest, without it real
+    int16 for integers and real float32 for the rest.  Complex samples without iq are refused."""
+    a = np.asarray(samples)
+    cplx = np.iscomplexobj(a)
+    if cplx and not iq:
+        raise _lib.Ft8rxError("samples are complex: pass iq=True")
+    if iq:
+        return IQ_F32 if cplx or a.dtype.kind == "f" else IQ_I16
+    return REAL_I16 if a.dtype.kind in "iu" else REAL_F32
 
 
 def decimation(rate):
@@ -164,7 +177,7 @@ def pack(samples, kind):
     if kind not in (REAL_I16, REAL_F32, IQ_I16, IQ_F32):
         raise _lib.Ft8rxError(f"kind {kind} is not one of REAL_I16, REAL_F32, IQ_I16, IQ_F32")
     a = np.asarray(samples)
-    base = np.int16 if kind in (REAL_I16, IQ_I16) else np.float32
+    base = _DTYPE[kind]
     if is_iq(kind):
         if np.iscomplexobj(a):
             if kind == IQ_I16:

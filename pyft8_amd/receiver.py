@@ -663,14 +663,18 @@ class Receiver:
         # the streaming down-converter turns into the channels dial_offsets_hz on the live handle (wide_in.WideIn; wide_in.push(chunk)
         # may also be called directly).  audio_in stays the 12 kHz object: its search grid and waterfall are not maintained for wide input.
         self.wide_in = None
-        if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample)
         # The reference starts its audio thread and manage_cycle in the constructor (receiver.py:252, 336).  Same here when there
         # is something to listen to: an explicit audio_source, or PortAudio (PyAudio importable and a device matches the keywords).
         if autostart is None:
             autostart = audio_source is not None or (bool(input_device_keywords) and _pyaudio_device(self.audio_in, input_device_keywords))
         if autostart:
             self.start(audio_source)
+
+    def _set_wide_in(self, sample_rate, iq, dial_offsets_hz, bands, t_first, resample):
+        """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
+        if sample_rate is not None:
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
     def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False):
@@ -685,8 +689,7 @@ class Receiver:
             return self
         self._stop.clear()
         self.thread_error = None
-        if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample)
         if self.wide_in is not None:
             if audio_source is not None:
                 self.wide_in.open(audio_source)
@@ -877,33 +880,57 @@ class Receiver:
             mask[fi[ok], c[ok] - lo] = 1
         return mask
 
-    def _residual_decode(self, h, B, local, msgs, mcnt, min_snr):
-        """Decode the frames in the handle's staging buffer (after a subtraction sweep); local = the experiment's local re-search."""
-        if not local:
+    def _pass(self, h, B, frames, recall, gather=None):
+        """One decode of a batch of B frames on handle h, for every entry of this class; the caller holds h's lock.  frames: host frames
+        int16 [B, 180000], or None = they are in h's staging buffer already (decode_stream), or `gather(h)` brings them there (the live
+        wide input).  recall: the entries per frame (_recall_entries), or None = no recall step.  The noise blanker, when on, blanks the
+        frames in the staging buffer first and leaves its counters in blanker_stats.
+        -> (records, counts, events, event counts), (recall records, counts) or None, reports [B, max_cands] or None.
+        A step around the decode of a batch belongs here ("Adding a step around the batch")."""
+        if recall is not None:
+            h.set_recall(recall)
+        if gather is not None:
+            gather(h)
+        if frames is not None and self.noise_blanker is None:
+            res = h.decode_batch(frames)
+        else:
+            if self.noise_blanker is not None:
+                self.blanker_stats = h.blank(None, B, *self.noise_blanker) if frames is None else h.blank_host(frames, *self.noise_blanker)
             h.enqueue(h.staging_ptr(), B)
-            return h.fetch(B)
-        h.set_search_mask(self._local_mask(msgs, mcnt, min_snr))
-        try:
-            h.enqueue(h.staging_ptr(), B)
-            return h.fetch(B)
-        finally:
-            h.set_search_mask(None)
+            res = h.fetch(B)
+        return res, (h.fetch_recall(B) if recall is not None else None), (h.fetch_reports(B) if self.reports else None)
 
-    def _decode_host(self, h, audio):
-        """Host frames -> (records, counts, events, event counts) on handle h: ft8rx_decode_batch, or -- noise blanker on -- the frames
-        go to the staging audio, are blanked there (ft8rx_blank_host) and the batch is enqueued from it."""
-        if self.noise_blanker is None:
-            return h.decode_batch(audio)
-        self.blanker_stats = h.blank_host(audio, *self.noise_blanker)
-        h.enqueue(h.staging_ptr(), len(audio))
-        return h.fetch(len(audio))
-
-    def _package(self, rec, cnt, ev, evc, **kw):
-        """The native host message layer for this receiver's config: ft8rx_package_batch, or ft8rx_package_batch_ext when the config
-        opts into more message types (msg_types != 0; rows of _lib.MESSAGE_EXT_DTYPE)."""
+    def _package(self, res, rres=None, **kw):
+        """The native host message layer (multithreaded; messages.package_frame is its Python twin) for the results of _pass:
+        ft8rx_package_batch_recall when the pass had a recall step, ft8rx_package_batch_ext when the config opts into more message
+        types (msg_types != 0; rows of _lib.MESSAGE_EXT_DTYPE), else ft8rx_package_batch.  kw: table= / n_threads= of those."""
+        if rres is not None:
+            return _lib.package_batch_recall(*res, *rres, **kw)
         if self.cfg.msg_types:
-            return _lib.package_batch_ext(rec, cnt, ev, evc, self.cfg.msg_types, **kw)
-        return _lib.package_batch(rec, cnt, ev, evc, **kw)
+            return _lib.package_batch_ext(*res, self.cfg.msg_types, **kw)
+        return _lib.package_batch(*res, **kw)
+
+    def _later_passes(self, h, B, passes, msgs, mcnt, res, min_snr, local, merge, **pkg_kw):
+        """Passes 2 .. `passes` of a batch whose frames pass 1 left in h's staging buffer (msgs, mcnt: its messages, res: its results):
+        subtract the fresh messages of the pass before, decode the residual -- local: the experiment's local re-search, one sweep --
+        and hand the packaged messages to merge(p, msgs, counts) -> the fresh ones (rows, counts).  -> the results of the last pass run"""
+        for p in range(1, int(passes)):
+            sigs = self._subtraction_list(msgs, mcnt, res[0], min_snr)
+            if not sigs[1].any():
+                break
+            h.subtract(h.staging_ptr(), B, sigs, refine=self.subtract_refine)    # the pass before left the frames in the handle's device buffer
+            if local:
+                h.set_search_mask(self._local_mask(msgs, mcnt, min_snr))
+            try:
+                h.enqueue(h.staging_ptr(), B)
+                res = h.fetch(B)
+            finally:
+                if local:
+                    h.set_search_mask(None)
+            msgs, mcnt = merge(p, *_lib.package_batch(*res, **pkg_kw))
+            if local:
+                break                                                # candidates of the local re-search are not subtracted again (:444)
+        return res
 
     def _recall_entries(self, recall):
         from . import recall as R
@@ -926,35 +953,13 @@ class Receiver:
         ddc_rat.accepts (44.1 kHz, 2.048 MS/s, 10 MS/s: ONE stream, any of the dtypes above) through the rational resampler
         (ft8rx_ddc_rat); a rate none of the three takes is refused, naming the rate.  Without it every rate
         behaves and is refused as it always was."""
-        from . import ddc as _ddc
-        from . import ddc_rat as _dr
-        a = np.asarray(samples)
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
             raise _lib.Ft8rxError("dial_offsets_hz: at least one channel")
         mod = _wide_in.front_end(sample_rate, resample)
-        if mod is not _ddc:                       # ONE stream through a pre-stage: ft8rx_ddc_wide (DESIGN.md section 16.2) or ft8rx_ddc_rat (16.3)
-            kind = mod.kind_of(a, iq)
-            if mod.is_iq(kind) and not iq:
-                raise _lib.Ft8rxError("samples are complex: pass iq=True")
-            arr, _ = mod.pack(_wide_in.one_stream(mod, a, iq, sample_rate), kind)
-            n_streams = 1
-        else:
-            cplx = np.iscomplexobj(a)
-            if cplx and not iq:
-                raise _lib.Ft8rxError("samples are complex: pass iq=True")
-            if iq:
-                kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
-            else:
-                kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
-            arr, n_streams, _ = _ddc.pack(a, kind)
-        if src is None:
-            if n_streams != 1 and n_streams != n_out:
-                raise _lib.Ft8rxError(f"src: {n_streams} streams and {n_out} channels -- say which stream each channel reads")
-            src = [0] * n_out if n_streams == 1 else list(range(n_out))
-        if len(src) != n_out:
-            raise _lib.Ft8rxError(f"src: one stream index per channel ({n_out}), got {len(src)}")
+        arr, kind, n_streams, _ = _wide_in.pack(samples, iq, sample_rate, mod)
+        src = _wide_in.sources(mod, src, n_streams, n_out)
         if bands is not None and len(bands) != n_out:
             raise _lib.Ft8rxError(f"bands: one per channel ({n_out}), got {len(bands)}")
         if kw.get("recall") is not None and len(kw["recall"]) != n_out:
@@ -966,12 +971,7 @@ class Receiver:
                 raise TypeError(f"decode_stream() got an unexpected keyword argument '{k}'")
         args.update(kw)
         with self._hlock:
-            h = self._handle(n_out)
-            if mod is not _ddc:
-                _wide_in.stream_zero(mod, src)
-                (h.ddc_rat if mod is _dr else h.ddc_wide)(arr, kind, int(sample_rate), dials)
-            else:
-                h.ddc(arr, kind, int(sample_rate), src, dials)
+            _wide_in.HANDLE_CALLS[mod][0](self._handle(n_out), arr, kind, int(sample_rate), src, dials)
             return self._decode_frames_locked(None, n_out, bands=bands, **args)
 
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",
@@ -985,53 +985,32 @@ class Receiver:
             _optins.refuse(_optins.RECALL, on)
         if int(passes) > 1:
             _optins.refuse(_optins.PASSES, on)
-        local = research == "local"
         h = self._handle(B)
-        if use_recall:
-            h.set_recall(self._recall_entries(recall if recall is not None else [None] * B))
-        if audio is None:
-            if self.noise_blanker is not None:
-                self.blanker_stats = h.blank(None, B, *self.noise_blanker)
-            h.enqueue(h.staging_ptr(), B)
-            rec, cnt, ev, evc = h.fetch(B)
-        else:
-            rec, cnt, ev, evc = self._decode_host(h, audio)
-        rp = h.fetch_reports(B) if self.reports else None
-        # host message layer: native, multithreaded (ft8rx_package_batch); messages.package_frame is its Python twin
-        if use_recall:
-            rrec, rcnt = h.fetch_recall(B)
-            msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt)
-        else:
-            msgs, mcnt = self._package(rec, cnt, ev, evc)
+        entries = self._recall_entries(recall if recall is not None else [None] * B) if use_recall else None
+        res, rres, rp = self._pass(h, B, audio, entries)
+        msgs, mcnt = self._package(res, rres)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
         band = [self.band] * B if bands is None else list(bands)
         out = [_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=band[f], odd_even=0, on_message=self.on_message,
                                 ap=self._ap_on(), recall=use_recall, reports=None if rp is None else rp[f]) for f in range(B)]
         seen = [{" ".join(d["msg_tuple"]) for d in out[f]} for f in range(B)]
-        for _ in range(1, int(passes)):
-            sigs = self._subtraction_list(msgs, mcnt, rec, subtract_min_snr)
-            if not sigs[1].any():
-                break
-            h.subtract(h.staging_ptr(), B, sigs, refine=self.subtract_refine)    # decode_batch left the frames in the handle's device buffer
-            rec, cnt, ev, evc = self._residual_decode(h, B, local, msgs, mcnt, subtract_min_snr)
-            msgs, mcnt = _lib.package_batch(rec, cnt, ev, evc)
+
+        def merge(p, msgs, mcnt):
+            """the dict flavour: new texts only, tagged "_SUB", delivered in emit order; their rows compacted to the front of msgs"""
             keep = np.zeros(mcnt.shape, np.int32)
             for f in range(B):
-                new = []
                 for i, d in enumerate(_m.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=band[f], odd_even=0)):
                     t = " ".join(d["msg_tuple"])
                     if t not in seen[f] and (sub_pass_osd or "OSD" not in d["decode_notes"]):
                         seen[f].add(t)
                         d["decode_notes"] += "_SUB"
-                        new.append(d)
+                        out[f].append(d)
                         msgs[f, keep[f]] = msgs[f, i]                # compact: only the new messages are subtracted next
                         keep[f] += 1
                         if self.on_message is not None:
                             self.on_message(d)
-                out[f] += new
-            mcnt = keep
-            if local:
-                break                                                # candidates of the local re-search are not subtracted again (:444)
+            return msgs, keep
+        rec, cnt = self._later_passes(h, B, passes, msgs, mcnt, res, subtract_min_snr, research == "local", merge)[:2]
         return (out, rec, cnt) if return_records else out
 
     @staticmethod
@@ -1070,33 +1049,20 @@ class Receiver:
         B = audio.shape[0]
         if B == 0:
             raise _lib.Ft8rxError("empty batch")
-        with self._hlock:
-            return self._decode_frames_arrays_locked(audio, B, n_threads, passes, subtract_min_snr, sub_pass_osd, research)
-
-    def _decode_frames_arrays_locked(self, audio, B, n_threads, passes, subtract_min_snr, sub_pass_osd, research="full"):
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
         _optins.refuse(_optins.ARRAYS, _optins.active(self.cfg))
-        local = research == "local"
-        h = self._handle(B)
-        rec, cnt, ev, evc = self._decode_host(h, audio)
-        msgs, mcnt = _lib.package_batch(rec, cnt, ev, evc, n_threads=n_threads)
-        if passes <= 1:
-            return msgs, mcnt, rec, cnt
-        out, ocnt = msgs.copy(), np.ascontiguousarray(mcnt, np.int32).copy()
-        cur_m, cur_c, cur_rec = msgs, mcnt, rec
-        for p in range(1, int(passes)):
-            sigs = self._subtraction_list(cur_m, cur_c, cur_rec, subtract_min_snr)
-            if not sigs[1].any():
-                break
-            h.subtract(h.staging_ptr(), B, sigs, refine=self.subtract_refine)
-            rec2, cnt2, ev2, evc2 = self._residual_decode(h, B, local, cur_m, cur_c, subtract_min_snr)
-            m2, c2 = _lib.package_batch(rec2, cnt2, ev2, evc2, n_threads=n_threads)
-            new_m, new_c = _lib.merge_messages(out, ocnt, m2, c2, p, drop_osd=not sub_pass_osd)      # native: appends in place
-            cur_m, cur_c, cur_rec = new_m, new_c, rec2
-            if local:
-                break
-        return out, ocnt, rec, cnt
+        with self._hlock:
+            h = self._handle(B)
+            res = self._pass(h, B, audio, None)[0]
+            msgs, mcnt = _lib.package_batch(*res, n_threads=n_threads)
+            if passes > 1:
+                # the array flavour of the merge is native (appends in place, up to the width of `out`)
+                out, ocnt = msgs.copy(), np.ascontiguousarray(mcnt, np.int32).copy()
+                self._later_passes(h, B, passes, msgs, mcnt, res, subtract_min_snr, research == "local",
+                                   lambda p, m2, c2: _lib.merge_messages(out, ocnt, m2, c2, p, drop_osd=not sub_pass_osd), n_threads=n_threads)
+                msgs, mcnt = out, ocnt
+            return msgs, mcnt, res[0], res[1]
 
     def decode_frame(self, audio_i16, cyclestart_string="700101_000015"):
         return self.decode_frames(np.asarray(audio_i16)[None], [cyclestart_string])[0]
@@ -1131,52 +1097,36 @@ class Receiver:
             if self.on_message is not None:
                 self.on_message(d)
 
-    def _poll_wide(self, out):
-        """The passes of the wide input that have fallen due (wide_in.PassScheduler): gather the K channels' frames out of the
-        down-converter's rings, decode them as one batch on the live handle, deliver per channel.  Every dict carries "channel": j;
-        band = bands[j]; fHz stays the audio frequency inside the channel.  The channels share the persistent call-hash table and are
-        replayed into it in ascending order (package_batch(table=))."""
-        w = self.wide_in
-        K = w.n_channels
-        while True:
-            with w._lock:
-                if not w._ready:
-                    break
-                c, hop, m_first, n_have = w._ready.pop(0)
-            t0 = T_CYC * c
-            cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
-            # recall: only the complete-frame pass, per channel the complete-frame messages of the same channel 30 s earlier
-            prev = [w.recall_hist[j].get(t0 - 2 * T_CYC) for j in range(K)] if self.recall and not hop else None
-            if prev is not None and all(p is None for p in prev):
-                prev = None
-            with self._live_lock:
-                h = self._live_handle(K)
-                if prev is not None:
-                    h.set_recall(self._recall_entries(prev))
-                h.ddc_stream_frame(m_first, n_have)
-                if self.noise_blanker is not None:
-                    self.blanker_stats = h.blank(None, K, *self.noise_blanker)
-                h.enqueue(h.staging_ptr(), K)
-                rec, cnt, ev, evc = h.fetch(K)
-                if prev is not None:
-                    rrec, rcnt = h.fetch_recall(K)
-                rp = h.fetch_reports(K) if self.reports else None
-            if prev is not None:
-                msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, n_threads=1, table=self.call_hashes)
-            else:
-                msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
-            for j in range(K):
-                dicts = _m.message_dicts(msgs[j], mcnt[j], cyclestart_string=cs, band=w.bands[j] if w.bands is not None else self.band,
-                                         odd_even=int((t0 % (2 * T_CYC)) / T_CYC), ap=self._ap_on(), recall=self.recall,
-                                         reports=None if rp is None else rp[j])
+    def _live_pass(self, t0, early, K, frames, gather, bands, channels, seen, hist, out):
+        """One live pass over the K frames of the cycle that starts at t0 -- the 12 kHz path: K = 1, a host frame; the wide path: one
+        frame per channel, which gather(h) brings into the live handle's staging buffer: decode them as one batch on the live handle,
+        package with the persistent call-hash table (the frames are replayed into it in ascending order, package_batch(table=)) and
+        deliver per frame (_deliver) with its band bands[j], its duplicate filter seen[j], its recall history hist[j] and -- channels
+        not None -- "channel": channels[j]."""
+        cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
+        # recall: only the complete-frame pass, per frame the complete-frame messages of the same channel 30 s earlier (same parity),
+        # and only when at least one frame has such a history
+        prev = [hist[j].get(t0 - 2 * T_CYC) for j in range(K)] if self.recall and not early else None
+        if prev is not None and all(p is None for p in prev):
+            prev = None
+        with self._live_lock:
+            res, rres, rp = self._pass(self._live_handle(K), K, frames, None if prev is None else self._recall_entries(prev), gather)
+        # the host message layer runs outside _live_lock: an audio callback that waits for a hop spectrum is not held up by it
+        msgs, mcnt = self._package(res, rres, n_threads=1, table=self.call_hashes)
+        for j in range(K):
+            dicts = _m.message_dicts(msgs[j], mcnt[j], cyclestart_string=cs, band=bands[j], odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
+                                     ap=self._ap_on(), recall=self.recall, reports=None if rp is None else rp[j])
+            if channels is not None:
                 for d in dicts:
-                    d["channel"] = j
-                self._deliver(msgs[j], dicts, t0, hop, w.seen[j], w.recall_hist[j], out)
+                    d["channel"] = channels[j]
+            self._deliver(msgs[j], dicts, t0, early, seen[j], hist[j], out)
 
     def poll(self):
-        """Decode every cycle that audio_in._callback has completed since the last call; messages go to on_message
-        on the caller's thread.  -> list of message dicts.  Receiver.start() runs this on a daemon thread (the stand-in for
-        manage_cycle); without it, call poll() from your own loop (e.g. every 0.1 s).
+        """Decode every cycle that audio_in._callback has completed since the last call, then the passes of the wide input that have
+        fallen due (wide_in.PassScheduler); messages go to on_message on the caller's thread.  -> list of message dicts.
+        Receiver.start() runs this on a daemon thread (the stand-in for manage_cycle); without it, call poll() from your own loop
+        (e.g. every 0.1 s).  Wide input: every dict carries "channel": j; band = bands[j]; fHz stays the audio frequency inside the
+        channel.
 
         Unlike batched decode_frames (independent frames, a fresh call-hash table per frame), the stream is ONE receiver: the
         frames share the persistent table self.call_hashes, as the reference's process-global databases.call_hashes does
@@ -1190,26 +1140,16 @@ class Receiver:
                 frame, t_now, early = self.audio_in._ready.pop(0)           # early: hops of the cycle received so far, 0 = the complete frame
             # start of the cycle the frame belongs to: a full frame is handed over at its end, an early one inside it
             t0 = T_CYC * int(t_now / T_CYC) if early else T_CYC * int((t_now - T_CYC / 2) / T_CYC)
-            cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
-            # recall: only the complete-frame pass, fed with the complete-frame messages of the cycle 30 s earlier (same parity)
-            prev = self._recall_hist.get(t0 - 2 * T_CYC) if self.recall and not early else None
-            with self._live_lock:
-                h = self._live_handle()
-                if prev is not None:
-                    h.set_recall(self._recall_entries([prev]))
-                rec, cnt, ev, evc = self._decode_host(h, frame[None])
-                if prev is not None:
-                    rrec, rcnt = h.fetch_recall(1)
-                rp = h.fetch_reports(1) if self.reports else None
-            if prev is not None:
-                msgs, mcnt = _lib.package_batch_recall(rec, cnt, ev, evc, rrec, rcnt, n_threads=1, table=self.call_hashes)
-            else:
-                msgs, mcnt = self._package(rec, cnt, ev, evc, n_threads=1, table=self.call_hashes)
-            dicts = _m.message_dicts(msgs[0], mcnt[0], cyclestart_string=cs, band=self.band, odd_even=int((t0 % (2 * T_CYC)) / T_CYC),
-                                     ap=self._ap_on(), recall=self.recall, reports=None if rp is None else rp[0])
-            self._deliver(msgs[0], dicts, t0, early, self._cycle_seen, self._recall_hist, out)
-        if self.wide_in is not None:
-            self._poll_wide(out)
+            self._live_pass(t0, early, 1, frame[None], None, [self.band], None, [self._cycle_seen], [self._recall_hist], out)
+        w = self.wide_in
+        while w is not None:
+            with w._lock:
+                if not w._ready:
+                    break
+                c, hop, m_first, n_have = w._ready.pop(0)
+            K = w.n_channels
+            self._live_pass(T_CYC * c, hop, K, None, lambda h: h.ddc_stream_frame(m_first, n_have),
+                            w.bands if w.bands is not None else [self.band] * K, range(K), w.seen, w.recall_hist, out)
         return out
 
 

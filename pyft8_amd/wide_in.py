@@ -57,6 +57,53 @@ def stream_zero(mod, src):
         raise _lib.Ft8rxError(f"src: {list(src)} -- a {_ONE_STREAM[mod]} rate takes one stream, every channel reads stream 0")
 
 
+def pack(samples, iq, rate, mod, kind=None):
+    """The samples of any front end (mod = front_end(rate, ...)) as its Handle methods take them -> (packed [n_streams][n(, 2)], kind,
+    n_streams, n).  kind: the kind a stream began with (WideIn), or None = the samples' own by mod.kind_of, complex ones without iq
+    refused.  A pre-stage rate takes ONE stream (one_stream), which comes back as [1][n(, 2)]."""
+    a = np.asarray(samples)
+    if kind is None:
+        kind = mod.kind_of(a, iq)
+        if mod.is_iq(kind) and not iq:
+            raise _lib.Ft8rxError("samples are complex: pass iq=True")
+    if mod not in _ONE_STREAM:
+        arr, n_streams, n = mod.pack(a, kind)
+        return arr, kind, n_streams, n
+    arr, n = mod.pack(one_stream(mod, a, iq, rate), kind)
+    return arr[None], kind, 1, n
+
+
+def sources(mod, src, n_streams, n_channels):
+    """src, the stream each channel reads: given, one index per channel (all 0 at a pre-stage rate); None = stream 0 for every channel,
+    or stream j for channel j when there are as many streams as channels"""
+    if src is None:
+        if n_streams != 1 and n_streams != n_channels:
+            raise _lib.Ft8rxError(f"src: {n_streams} streams and {n_channels} channels -- say which stream each channel reads")
+        return [0] * n_channels if n_streams == 1 else list(range(n_channels))
+    if len(src) != n_channels:
+        raise _lib.Ft8rxError(f"src: one stream index per channel ({n_channels}), got {len(src)}")
+    if mod in _ONE_STREAM:
+        stream_zero(mod, src)
+    return src
+
+
+def _pre_stage(name):
+    """The row of a pre-stage in HANDLE_CALLS: its Handle methods take ONE stream as [n(, 2)], and neither n_streams nor src"""
+    return (lambda h, a, kind, rate, src, dials: getattr(h, name)(a[0], kind, rate, dials),
+            lambda h, kind, rate, n_streams, src, dials: getattr(h, name + "_stream_open")(kind, rate, dials),
+            lambda h, a: getattr(h, name + "_stream_push")(a[0]))
+
+
+# module -> how the one-shot call (h, packed, kind, rate, src, dials), the stream open (h, kind, rate, n_streams, src, dials)
+# and the stream push (h, packed) reach the Handle; packed is what pack() returns, [n_streams][n(, 2)]
+HANDLE_CALLS = {
+    _ddc: (lambda h, a, kind, rate, src, dials: h.ddc(a, kind, rate, src, dials),
+           lambda h, kind, rate, n_streams, src, dials: h.ddc_stream_open(kind, rate, n_streams, src, dials),
+           lambda h, a: h.ddc_stream_push(a)),
+    _dw: _pre_stage("ddc_wide"),
+    _dr: _pre_stage("ddc_rat")}
+
+
 def _last_input(D):
     """Offset of the last input a tile needs from the input of its first output (csrc/ddc_ring.hpp: last)"""
     r2 = 1 if D == 1 else 2
@@ -119,12 +166,12 @@ class WideIn:
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
-        # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a wide rate
-        # D is the input samples per 12 kHz output all the same; at a resampled rate sample_rate / 12000 is no integer, and input counts
-        # become output counts by exact integer arithmetic (_outputs)
+        # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a resampled
+        # rate sample_rate / 12000 is no integer, so input counts become output counts by exact integer arithmetic at every rate (_outputs)
         self.mod = front_end(self.sample_rate, resample)
-        self.wide, self.rat = self.mod is _dw, self.mod is _dr
-        self.D = None if self.rat else self.sample_rate // 12000 if self.wide else _ddc.decimation(self.sample_rate)
+        self.wide, self.rat = self.mod is _dw, self.mod is _dr          # descriptions: pack() and HANDLE_CALLS[self.mod] are what act
+        if self.mod is _ddc:
+            _ddc.decimation(self.sample_rate)                           # a rate that front_end left to ddc and that ddc does not take
         self.iq = bool(iq)
         self.dials = [float(f) for f in dial_offsets_hz]
         self.n_channels = len(self.dials)
@@ -153,47 +200,19 @@ class WideIn:
 
     def _start(self, chunk):
         """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
-        a = np.asarray(chunk)
-        cplx = np.iscomplexobj(a)
-        if self.mod is not _ddc:
-            self.kind = self.mod.kind_of(a, self.iq)
-            if not self.iq and self.mod.is_iq(self.kind):
-                raise _lib.Ft8rxError("samples are complex: pass iq=True")
-        elif cplx and not self.iq:
-            raise _lib.Ft8rxError("samples are complex: pass iq=True")
-        elif self.iq:
-            self.kind = _ddc.IQ_F32 if cplx or a.dtype.kind == "f" else _ddc.IQ_I16
-        else:
-            self.kind = _ddc.REAL_I16 if a.dtype.kind in "iu" else _ddc.REAL_F32
-        _, self.n_streams, _ = self._pack(a)
-        if self.mod is not _ddc and self.src is not None:
-            stream_zero(self.mod, self.src)
-        if self.src is None:
-            if self.n_streams != 1 and self.n_streams != self.n_channels:
-                raise _lib.Ft8rxError(f"src: {self.n_streams} streams and {self.n_channels} channels -- say which stream each channel reads")
-            self.src = [0] * self.n_channels if self.n_streams == 1 else list(range(self.n_channels))
+        _, self.kind, self.n_streams, _ = pack(chunk, self.iq, self.sample_rate, self.mod)
+        self.src = sources(self.mod, self.src, self.n_streams, self.n_channels)
         if self.t_first is None:
             self.t_first = self._rx.time_source()
         self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            if self.mod is not _ddc:
-                self.f_mixed_hz = (h.ddc_rat_stream_open if self.rat else h.ddc_wide_stream_open)(self.kind, self.sample_rate, self.dials)
-            else:
-                self.f_mixed_hz = h.ddc_stream_open(self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
-
-    def _pack(self, chunk):
-        """-> ([n_streams][n] samples packed for self.kind, n_streams, n); a wide or a resampled rate: one stream, [1][n]"""
-        if self.mod is _ddc:
-            return _ddc.pack(chunk, self.kind)
-        a, n = self.mod.pack(one_stream(self.mod, np.asarray(chunk), self.iq, self.sample_rate), self.kind)
-        return a[None], 1, n
+            self.f_mixed_hz = HANDLE_CALLS[self.mod][1](h, self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
 
     def _push(self, a, real):
         """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples"""
         with self._rx._live_lock:
-            h = self._rx._live_handle(self.n_channels)
-            self.m_produced = h.ddc_rat_stream_push(a[0]) if self.rat else h.ddc_wide_stream_push(a[0]) if self.wide else h.ddc_stream_push(a)
+            self.m_produced = HANDLE_CALLS[self.mod][2](self._rx._live_handle(self.n_channels), a)
         if real:
             self.n_pushed += a.shape[1]
 
@@ -211,7 +230,7 @@ class WideIn:
         """The next samples of the source, any length (a longer chunk is handed on a second at a time)"""
         if self.sched is None:
             self._start(chunk)
-        a, n_streams, n = self._pack(chunk)
+        a, _, n_streams, n = pack(chunk, self.iq, self.sample_rate, self.mod, self.kind)
         if n_streams != self.n_streams:
             raise _lib.Ft8rxError(f"push: {n_streams} streams, the source began with {self.n_streams}")
         for at in range(0, n, self.sample_rate):
@@ -223,14 +242,11 @@ class WideIn:
         if self.sched is None:
             return
         m_real = self._outputs(self.n_pushed)
-        if self.rat:                           # a tile's worth of rest samples, rounded up
-            n = -(-TILE * self.sample_rate // 12000)
-            zeros = np.full((1, n) + ((2,) if _dr.is_iq(self.kind) else ()), 128 if self.kind == _dr.IQ_U8 else 0, _dr._DTYPE[self.kind])
-        elif self.wide:                          # (uint8 has no zero: 128 is half a step, 128 counts of the int16 scale, above it)
-            zeros = np.full((1, TILE * self.D) + ((2,) if self.iq else ()), 128 if self.kind == _dw.IQ_U8 else 0, _dw._DTYPE[self.kind])
-        else:
-            shape = (self.n_streams, TILE * self.D) + ((2,) if _ddc.is_iq(self.kind) else ())
-            zeros = np.zeros(shape, np.int16 if self.kind in (_ddc.REAL_I16, _ddc.IQ_I16) else np.float32)
+        # a tile's worth of rest samples per stream, rounded up (1008 D at a multiple of 12 kHz); uint8 has no zero: 128 is half a step,
+        # 128 counts of the int16 scale, above it
+        dtype = self.mod._DTYPE[self.kind]
+        zeros = np.full((self.n_streams, -(-TILE * self.sample_rate // 12000)) + ((2,) if self.mod.is_iq(self.kind) else ()),
+                        128 if dtype == np.uint8 else 0, dtype)
         while self.m_produced < m_real:
             self._push(zeros, False)
         self._note(m_real)
