@@ -45,6 +45,7 @@
  *     ft8rx_ddc  ft8rx_ddc_host  ft8rx_ddc_taps                                        (down-converter: real / IQ input at 24 .. 192 kHz -> 12 kHz frames)
  *     ft8rx_ddc_stream_open  ft8rx_ddc_stream_push  ft8rx_ddc_stream_frame  ft8rx_ddc_stream_info  ft8rx_ddc_stream_read
  *     ft8rx_ddc_stream_close                                                           (the same on a continuous stream, state on the device)
+ *     ft8rx_ddc_stream_grid_open  ft8rx_ddc_stream_grid_info  ft8rx_ddc_stream_grid_read  (opt-in spectrogram rows of every channel behind it)
  *     ft8rx_ddc_wide  ft8rx_ddc_wide_host  ft8rx_ddc_wide_taps  ft8rx_ddc_wide_plan     (pre-decimator: ONE stream at 240 kHz .. 129.6 MHz, 8- or
  *     ft8rx_ddc_wide_stream_open  ft8rx_ddc_wide_stream_push  ft8rx_ddc_wide_stream_read_mid   16-bit, in front of the down-converter)
  *     ft8rx_ddc_wide_stream_close
@@ -490,6 +491,26 @@ int  ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16
 int  ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first, int n, int16_t* y_i16, float* y_f32);
 int  ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced);
 int  ft8rx_ddc_stream_close(ft8rx_handle* h);
+/* Spectrogram stage behind the stream (extension, opt-in): the rows of ft8rx_spectrogram for every channel and
+ * every hop, computed on the device straight from the output ring -- the waterfall and search grid of live wide input.  It serves a
+ * plain stream and the stream behind a wide or rational one (ft8rx_ddc_wide_stream_*, ft8rx_ddc_rat_stream_*) alike.  With the grid
+ * open at hop phase p0, row q of channel j is the Hann window, 3840-point real FFT and 10 log10(max(|X|^2, 1e-24)) (FT8RX_GRID_COLS
+ * values) of the outputs y_j[p0 + 480 q - 3840, p0 + 480 q), zeros before the stream's first output; hop q is a row iff p0 + 480 q
+ * lies beyond the first output's index, and it exists once m_produced >= p0 + 480 q.  A row depends on the ring's contents alone, so
+ * it is the same bytes however the stream was cut into chunks, and it is byte for byte row h of ft8rx_spectrogram on the frame of
+ * the outputs from m_first = p0 + 480 (q - h) on (8 <= h <= 375; 1 <= h <= 7 while only zeros lie before m_first).
+ * grid_open  hop_phase in [0, 480), n_rows in [16, 750] (rows held per channel, the newest; 750 = two cycles): after any of the three
+ *            stream opens and before the first push; refused otherwise and on a second open.  Allocates the grid ring
+ *            [n_out][n_rows][FT8RX_GRID_COLS] float32; released by the stream's close or ft8rx_destroy.  Without it a push does
+ *            nothing new.
+ * push       (ft8rx_ddc_stream_push and the pre-stage pushes, unchanged) with the grid open also launches ONE kernel behind the
+ *            tiles for the hops they complete (none, if they complete none; of more than n_rows new hops the newest n_rows).
+ * grid_info  rows held [q_first_held, q_next), FT8RX_GRID_COLS, n_rows (any pointer may be NULL).
+ * grid_read  rows [q_first, q_first + n) of every channel -> host rows [n_out][n][cols] float32, after the stream's work is done;
+ *            refused with -1, naming the rows the ring holds, when one of them is not produced yet or no longer held. */
+int  ft8rx_ddc_stream_grid_open(ft8rx_handle* h, int hop_phase, int n_rows);
+int  ft8rx_ddc_stream_grid_info(ft8rx_handle* h, uint64_t* q_first_held, uint64_t* q_next, int32_t* cols, int32_t* n_rows);
+int  ft8rx_ddc_stream_grid_read(ft8rx_handle* h, uint64_t q_first, int n, float* rows);
 /* Wide pre-decimator (extension): ONE stream at rate_hz, a multiple of 48000 in [240000, 129600000] -- RTL-SDR
  * and HackRF (8-bit IQ), Airspy HF+ (IQ int16 at 384 / 768 kHz), direct-sampling receivers (real int16 at 64.8 / 129.6 MS/s) -- in front
  * of the down-converter above, which is used unchanged behind it.  rate_mid = the largest of 192000, 96000, 48000 that divides rate_hz

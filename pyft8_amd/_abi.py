@@ -77,6 +77,9 @@ PROTOTYPES = {
     "ft8rx_ddc_stream_read": (INT, (PTR, U64, INT, PTR, PTR)),
     "ft8rx_ddc_stream_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
     "ft8rx_ddc_stream_close": (INT, (PTR,)),
+    "ft8rx_ddc_stream_grid_open": (INT, (PTR, INT, INT)),
+    "ft8rx_ddc_stream_grid_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_ddc_stream_grid_read": (INT, (PTR, U64, INT, PTR)),
     "ft8rx_ddc_wide_plan": (INT, (I32, PTR, PTR)),
     "ft8rx_ddc_wide_taps": (INT, (I32, PTR, INT)),
     "ft8rx_ddc_wide": (INT, (PTR, PTR, INT, I32, U64, INT, PTR, F32, PTR, PTR, PTR)),

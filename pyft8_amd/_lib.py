@@ -809,6 +809,27 @@ class Handle:
         self._chk(self._L.ft8rx_ddc_stream_close(self._h), "ft8rx_ddc_stream_close")
         self._ds = None
 
+    # ---- the spectrogram stage behind the open stream, plain or pre-stage (ft8rx_ddc_stream_grid_*)
+    def ddc_stream_grid_open(self, hop_phase, n_rows=750):
+        """Open the grid before the first push: row q of every channel is the spectrogram row of the 12 kHz outputs
+        [hop_phase + 480 q - 3840, hop_phase + 480 q); the newest n_rows (16 .. 750) rows per channel are held on the device."""
+        self._chk(self._L.ft8rx_ddc_stream_grid_open(self._h, int(hop_phase), int(n_rows)), "ft8rx_ddc_stream_grid_open")
+
+    def ddc_stream_grid_info(self):
+        """-> {"q_first_held", "q_next", "cols", "n_rows"}: the grid ring holds rows [q_first_held, q_next) of `cols` values."""
+        q = [C.c_uint64(), C.c_uint64()]
+        v = [C.c_int32(), C.c_int32()]
+        self._chk(self._L.ft8rx_ddc_stream_grid_info(self._h, *[C.byref(x) for x in q + v]), "ft8rx_ddc_stream_grid_info")
+        return dict(zip(("q_first_held", "q_next", "cols", "n_rows"), (int(x.value) for x in q + v)))
+
+    def ddc_stream_grid_read(self, q_first, n):
+        """Rows [q_first, q_first + n) of every channel -> float32 [n_out, n, grid_cols], once the stream's work is done."""
+        if self._ds is None:
+            raise Ft8rxError("ddc_stream_grid_read: no stream is open (ddc_stream_open)")
+        rows = np.empty((self._ds[2], max(int(n), 0), self.grid_cols), np.float32)
+        self._chk(self._L.ft8rx_ddc_stream_grid_read(self._h, int(q_first) & 0xFFFFFFFFFFFFFFFF, int(n), rows.ctypes.data), "ft8rx_ddc_stream_grid_read")
+        return rows
+
     # ---- the input pre-stages (DESIGN.md section 16.4), written once: `name` is "ddc_wide" or "ddc_rat", the prefix of the C entries
     # (ft8rx_<name>*) and of the methods below, and the module that packs the samples of its kinds
     def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device):

@@ -70,6 +70,7 @@
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
 #include "ddc_ring.hpp"
+#include "ddc_grid_ring.hpp"
 #include "ddc_wide_ring.hpp"
 #include "ddc_rat_ring.hpp"
 #include "optins.hpp"
@@ -227,10 +228,13 @@ struct ft8rx_handle {
     // destroy); it shares nothing but the tap tables with the one-shot above.  d_in: [n_streams][cap] samples of `kind`, the newest cap
     // of each stream; d_out / d_f32: [n_out][OUT_RING]; h_stage: page-locked, one second of every stream; ev: behind the last copy out
     // of h_stage.  n_origin, pushed, tiles: absolute index of the first sample, samples pushed, first tile not produced yet.
+    // The spectrogram stage behind it (ft8rx_ddc_stream_grid_*, section 16.5; nothing of it exists until grid_open): d_grid
+    // [n_out][g_rows][FT8RX_GRID_COLS], row q at q mod g_rows; g_p0: the hop phase.
     struct DdcStream {
         bool open = false; int kind = 0, D = 0, n_streams = 0, n_out = 0; int32_t rate = 0; float scale = 0.0f;
         int64_t n_origin = 0, pushed = 0, tiles = 0, cap = 0;
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
+        float* d_grid = nullptr; int g_p0 = 0, g_rows = 0;
         hipEvent_t ev = nullptr;
     } ds;
     // input pre-stages (ft8rx_ddc_wide*, ft8rx_ddc_rat*; kernels/ddc_wide.hpp, kernels/ddc_rat.hpp).  One-shot: the
@@ -277,6 +281,12 @@ template <int D> constexpr bool ddc_ring_geom_ok() {
 }
 static_assert(ddc_ring_geom_ok<1>() && ddc_ring_geom_ok<2>() && ddc_ring_geom_ok<4>() && ddc_ring_geom_ok<8>() && ddc_ring_geom_ok<16>(),
               "ddc_ring.hpp: the filter geometry is the kernels'");
+
+// ... and of the spectrogram stage behind it (ddc_grid_ring.hpp) against k_grid_stream's: hop and window of spectrogram_hop, the output
+// ring, two cycles of rows at the most; the hops of one launch (at most the grid ring's rows) advance less than one turn of the ring
+static_assert(ddcgrid::HOP == 480 && ddcgrid::WIN == 3840 && ddcgrid::WIN == 2 * 1920 && ddcgrid::OUT_RING == ddcring::OUT_RING &&
+              375 * ddcgrid::HOP == FT8RX_NSAMP && ddcgrid::MAX_ROWS == 2 * 375 && ddcgrid::MIN_ROWS >= 1 &&
+              ddcgrid::HOP * ddcgrid::MAX_ROWS <= ddcgrid::OUT_RING && ddcgrid::WIN <= ddcgrid::OUT_RING, "ddc_grid_ring.hpp: k_grid_stream's geometry");
 
 static void set_err(ft8rx_handle* h, const char* fmt, ...) {
     char buf[512];
@@ -1511,6 +1521,7 @@ int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, i
 static void ddc_stream_release(ft8rx_handle* h) {
     ft8rx_handle::DdcStream& s = h->ds;
     release_dev(h, s.d_in); release_dev(h, s.d_out); release_dev(h, s.d_f32); release_dev(h, s.d_outs); release_host(h, s.h_stage);
+    release_dev(h, s.d_grid);
     const hipEvent_t ev = s.ev;
     s = ft8rx_handle::DdcStream();
     s.ev = ev;
@@ -1612,6 +1623,16 @@ static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
         switch (s.D) { case 1: DDC_GO(1); break; case 2: DDC_GO(2); break; case 4: DDC_GO(4); break; case 8: DDC_GO(8); break; default: DDC_GO(16); }
 #undef DDC_GO
         HIPCHK(h, hipGetLastError());
+        if (s.d_grid) {                                  // the rows these tiles complete, behind them on the same stream (section 16.5)
+            const int64_t m_origin = s.n_origin / s.D;
+            const ddcgrid::Hops hp = ddcgrid::completed(s.tiles * DDC_TO, done * DDC_TO, s.g_p0, m_origin, s.g_rows);
+            if (hp.end > hp.first) {
+                k_grid_stream<<<dim3((unsigned)(hp.end - hp.first), (unsigned)s.n_out), SPEC_NT, 0, h->stream>>>(
+                    s.d_out, (int)ddcring::OUT_RING, (int)ddcgrid::window_slot(hp.first, s.g_p0), (int)ddcgrid::zero_prefix(hp.first, s.g_p0, m_origin),
+                    s.d_grid, s.g_rows, (int)ddcgrid::row_slot(hp.first, s.g_rows), h->T);
+                HIPCHK(h, hipGetLastError());
+            }
+        }
         s.tiles = done;
     }
     if (m_produced) *m_produced = (uint64_t)(s.tiles * DDC_TO);
@@ -1675,6 +1696,61 @@ int ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_
     if (out_capacity) *out_capacity = (uint64_t)ddcring::OUT_RING;
     if (n_pushed) *n_pushed = (uint64_t)s.pushed;
     if (m_produced) *m_produced = (uint64_t)(s.tiles * DDC_TO);
+    return 0;
+}
+
+// ---- the spectrogram stage behind the stream.  The index arithmetic is ddc_grid_ring.hpp's.  The three entries
+// serve a plain stream and the stage behind a pre-stage stream alike (as ft8rx_ddc_stream_frame / _read / _info do).
+int ft8rx_ddc_stream_grid_open(ft8rx_handle* h, int hop_phase, int n_rows) {
+    if (!h) return -1;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "ft8rx_ddc_stream_grid_open: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
+    if (s.d_grid) { set_err(h, "ft8rx_ddc_stream_grid_open: the grid is open already (p0 %d, %d rows)", s.g_p0, s.g_rows); return -1; }
+    const int64_t pushed = h->ps.open ? h->ps.pushed : s.pushed;
+    if (pushed) { set_err(h, "ft8rx_ddc_stream_grid_open: %lld samples have been pushed already (open the grid before the first push)", (long long)pushed); return -1; }
+    if (hop_phase < 0 || hop_phase >= ddcgrid::HOP) { set_err(h, "ft8rx_ddc_stream_grid_open: hop_phase %d outside [0, %d)", hop_phase, (int)ddcgrid::HOP); return -1; }
+    if (n_rows < ddcgrid::MIN_ROWS || n_rows > ddcgrid::MAX_ROWS) {
+        set_err(h, "ft8rx_ddc_stream_grid_open: n_rows %d outside [%d, %d]", n_rows, (int)ddcgrid::MIN_ROWS, (int)ddcgrid::MAX_ROWS); return -1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (dalloc(h, &s.d_grid, (size_t)s.n_out * (size_t)n_rows * FT8RX_GRID_COLS)) return -2;
+    s.g_p0 = hop_phase; s.g_rows = n_rows;
+    return 0;
+}
+
+int ft8rx_ddc_stream_grid_info(ft8rx_handle* h, uint64_t* q_first_held, uint64_t* q_next, int32_t* cols, int32_t* n_rows) {
+    if (!h) return -1;
+    const ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open || !s.d_grid) { set_err(h, "ft8rx_ddc_stream_grid_info: no grid is open (ft8rx_ddc_stream_grid_open)"); return -1; }
+    const ddcgrid::Held hd = ddcgrid::held(s.tiles * DDC_TO, s.g_p0, s.n_origin / s.D, s.g_rows);
+    if (q_first_held) *q_first_held = (uint64_t)hd.first;
+    if (q_next) *q_next = (uint64_t)hd.next;
+    if (cols) *cols = FT8RX_GRID_COLS;
+    if (n_rows) *n_rows = s.g_rows;
+    return 0;
+}
+
+int ft8rx_ddc_stream_grid_read(ft8rx_handle* h, uint64_t q_first_u, int n, float* rows) {
+    if (!h) return -1;
+    const ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open || !s.d_grid) { set_err(h, "ft8rx_ddc_stream_grid_read: no grid is open (ft8rx_ddc_stream_grid_open)"); return -1; }
+    if (!rows) { set_err(h, "ft8rx_ddc_stream_grid_read: rows is NULL"); return -1; }
+    const ddcgrid::Held hd = ddcgrid::held(s.tiles * DDC_TO, s.g_p0, s.n_origin / s.D, s.g_rows);
+    const int64_t q_first = (int64_t)q_first_u;
+    if (n < 1 || q_first < hd.first || q_first > hd.next || n > hd.next - q_first) {
+        set_err(h, "ft8rx_ddc_stream_grid_read: rows [%lld, %lld) are not all in the grid ring (it holds %lld .. %lld)", (long long)q_first,
+                (long long)(q_first + (n > 0 ? n : 0)), (long long)hd.first, (long long)hd.next);
+        return -1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int64_t pos = ddcgrid::row_slot(q_first, s.g_rows), first = n < s.g_rows - pos ? n : s.g_rows - pos;
+    for (int j = 0; j < s.n_out; j++) {                  // at most two copies per channel: up to the grid ring's end, then from its start
+        const float* ring = s.d_grid + (size_t)j * (size_t)s.g_rows * FT8RX_GRID_COLS;
+        float* to = rows + (size_t)j * (size_t)n * FT8RX_GRID_COLS;
+        HIPCHK(h, hipMemcpy(to, ring + (size_t)pos * FT8RX_GRID_COLS, sizeof(float) * (size_t)first * FT8RX_GRID_COLS, hipMemcpyDeviceToHost));
+        if (first < n) HIPCHK(h, hipMemcpy(to + (size_t)first * FT8RX_GRID_COLS, ring, sizeof(float) * (size_t)(n - first) * FT8RX_GRID_COLS, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

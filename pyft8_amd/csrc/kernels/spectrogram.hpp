@@ -1,6 +1,7 @@
 // spectrogram.hpp -- K1: 375-hop dB spectrogram (receiver.py:288-306)
-// Part of libft8rx.so.  k_spectrogram / k_hop_spectrum are built in the second translation unit only (ft8rx_ilp.hip, ILP scheduling:
-// FT8RX_ILP_UNIT) and launched through ilp_launch.hpp; k_fill_row0 belongs to the main unit.
+// Part of libft8rx.so.  The arithmetic of a row, spectrogram_hop, is shared device code of both translation units; k_spectrogram /
+// k_hop_spectrum are built in the second one only (ft8rx_ilp.hip, ILP scheduling: FT8RX_ILP_UNIT) and launched through ilp_launch.hpp;
+// k_fill_row0 and k_grid_stream (rows off the streaming down-converter's output ring) belong to the main unit.
 #ifndef FT8RX_SPECTROGRAM_HPP
 #define FT8RX_SPECTROGRAM_HPP
 
@@ -11,16 +12,30 @@
 //   [4,4]  120 groups of 16 (one per thread), twiddles from the LDS table w240[t] = W1920[8 t],
 //   [5,3]  128 groups of 15 (one per thread), compile-time twiddles,
 // then the real-FFT split and 20 log10|.|.
+// Where the samples come from is the caller's: load(m) -> samples 2 m (low half) and 2 m + 1 (high half) of the window as int16 bit
+// patterns, m = 0 .. 1919 (SpecLoadFrame: a frame in memory; SpecLoadRing: the down-converter's output ring).
 #define SPEC_NT 128
-#ifdef FT8RX_ILP_UNIT
-FT8_DEV void spectrogram_hop(const int16_t* __restrict__ a, int base, float* __restrict__ out, const Tables& T,
-                             cpx* z, cpx* w240, int tid) {
+// a[base .. base + 3840) of an int16 array, base even: one aligned pair per load; zeros where the index is negative
+struct SpecLoadFrame {
+    const int16_t* __restrict__ a; int base;
+    FT8_DEV uint32_t operator()(int m) const {
+        const int i0 = base + 2 * m;
+        // samples before the frame start are zeros (the ring starts zeroed, receiver.py:248): masked with integer ALU ops --
+        // a select here is turned back into a branch around the load, i.e. one memory round trip per basic block
+        uint32_t raw = *reinterpret_cast<const uint32_t*>(a + (i0 & ~(i0 >> 31)));
+        raw &= ~(uint32_t)(i0 >> 31);
+        return raw;
+    }
+};
+
+template <class Load>
+FT8_DEV void spectrogram_hop(const Load& load, float* __restrict__ out, const Tables& T, cpx* z, cpx* w240, int tid) {
     const cpx* __restrict__ W = T.W1920;
     // stage-2 twiddle table: requested now, stored to LDS just before the first barrier (a load -> wait -> store loop here delayed
     // the whole block by a memory round trip before its first sample load)
     const cpx wa = W[8 * tid], wb = W[8 * (tid + SPEC_NT < 240 ? tid + SPEC_NT : 0)];
     {   // pass [8]: n = 1920, s = 1, m = 240: butterfly p reads samples m = p + 240 j.  Straight-line: loads from clamped addresses,
-        // zeros by select (hops before the frame start), twiddle multiplies unconditional (W^0 = (1, -0) is an exact identity).
+        // zeros by masking (hops before the frame start: the loads above), twiddle multiplies unconditional (W^0 = (1, -0) is an exact identity).
         cpx v[2][8];
         cpx w[2][8];
 #pragma unroll
@@ -29,11 +44,8 @@ FT8_DEV void spectrogram_hop(const int16_t* __restrict__ a, int base, float* __r
             const int pc = (p < 240) ? p : 239;
 #pragma unroll
             for (int j = 0; j < 8; j++) {
-                const int m = pc + 240 * j, i0 = base + 2 * m;
-                // samples before the frame start are zeros (the ring starts zeroed, receiver.py:248): masked with integer ALU ops --
-                // a select here is turned back into a branch around the load, i.e. one memory round trip per basic block
-                uint32_t raw = *reinterpret_cast<const uint32_t*>(a + (i0 & ~(i0 >> 31)));
-                raw &= ~(uint32_t)(i0 >> 31);
+                const int m = pc + 240 * j;
+                const uint32_t raw = load(m);
                 const float2 wn = *reinterpret_cast<const float2*>(T.win + 2 * m);
                 v[i][j] = make_float2((float)(int16_t)(raw & 0xFFFFu) * wn.x, (float)(int16_t)(raw >> 16) * wn.y);
             }
@@ -118,6 +130,7 @@ FT8_DEV void spectrogram_hop(const int16_t* __restrict__ a, int base, float* __r
     }
 }
 
+#ifdef FT8RX_ILP_UNIT
 __global__ __launch_bounds__(SPEC_NT) void k_spectrogram(const int16_t* __restrict__ audio, float* __restrict__ grid, Tables T) {
     __shared__ cpx z[1920];
     __shared__ cpx w240[240];
@@ -131,7 +144,7 @@ __global__ __launch_bounds__(SPEC_NT) void k_spectrogram(const int16_t* __restri
         for (int i = tid; i < FT8RX_GRID_COLS; i += SPEC_NT) row0[i] = 1.0f;
         return;
     }
-    spectrogram_hop(audio + (size_t)f * FT8RX_NSAMP, 480 * hop - 3840,
+    spectrogram_hop(SpecLoadFrame{audio + (size_t)f * FT8RX_NSAMP, 480 * hop - 3840},
                     grid + ((size_t)f * FT8RX_GRID_ROWS + hop) * FT8RX_GRID_COLS, T, z, w240, tid);
 }
 
@@ -139,13 +152,47 @@ __global__ __launch_bounds__(SPEC_NT) void k_spectrogram(const int16_t* __restri
 __global__ __launch_bounds__(SPEC_NT) void k_hop_spectrum(const int16_t* __restrict__ win3840, float* __restrict__ row, Tables T) {
     __shared__ cpx z[1920];
     __shared__ cpx w240[240];
-    spectrogram_hop(win3840, 0, row, T, z, w240, threadIdx.x);
+    spectrogram_hop(SpecLoadFrame{win3840, 0}, row, T, z, w240, threadIdx.x);
 }
 
 #else
 __global__ void k_fill_row0(float* grid, int B) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B * FT8RX_GRID_COLS) grid[(size_t)(i / FT8RX_GRID_COLS) * FT8RX_GRID_ROWS * FT8RX_GRID_COLS + (i % FT8RX_GRID_COLS)] = 1.0f;
+}
+
+// ------------------------------------------------------------------------------------ rows off the down-converter's output ring
+// (index arithmetic: ddc_grid_ring.hpp).  A window of one channel's int16 output ring [ring_n]: sample i sits
+// at slot + i, less ring_n once past the ring's end (one wrap at the most: slot < ring_n, i < 3840 <= ring_n); the first nz samples
+// lie before the stream's origin and are zeros.  The first index may be odd, so the two samples of a pair are loaded one by one.
+struct SpecLoadRing {
+    const int16_t* __restrict__ ring; int slot, nz, ring_n;
+    FT8_DEV uint32_t operator()(int m) const {
+        int i0 = slot + 2 * m, i1 = i0 + 1;
+        i0 -= (i0 >= ring_n) ? ring_n : 0;
+        i1 -= (i1 >= ring_n) ? ring_n : 0;
+        // zeros before the origin by masking, as SpecLoadFrame does (the addresses are inside the ring whatever nz is)
+        const uint32_t lo = (uint32_t)(uint16_t)ring[i0] & ~(uint32_t)((2 * m - nz) >> 31);
+        const uint32_t hi = (uint32_t)(uint16_t)ring[i1] & ~(uint32_t)((2 * m + 1 - nz) >> 31);
+        return lo | (hi << 16);
+    }
+};
+
+// one block per (new hop, channel): block (b, j) computes hop q_first + b of channel j from d_out [n_out][ring_n] into row
+// (row0 + b) mod n_rows of d_grid [n_out][n_rows][FT8RX_GRID_COLS].  The host hands over the FIRST hop's ring slot (slot0 < ring_n),
+// zero prefix (nz0 in [0, 3840)) and grid row (row0 < n_rows); hop b is 480 b samples on, and gridDim.x <= n_rows and
+// 480 gridDim.x <= ring_n keep every wrap a single compare and subtract (ft8rx.hip: ddc_stream_push).
+__global__ __launch_bounds__(SPEC_NT) void k_grid_stream(const int16_t* __restrict__ d_out, int ring_n, int slot0, int nz0, float* __restrict__ d_grid,
+                                                         int n_rows, int row0, Tables T) {
+    __shared__ cpx z[1920];
+    __shared__ cpx w240[240];
+    const int b = blockIdx.x, j = blockIdx.y;
+    int slot = slot0 + 480 * b, row = row0 + b, nz = nz0 - 480 * b;
+    slot -= (slot >= ring_n) ? ring_n : 0;
+    row -= (row >= n_rows) ? n_rows : 0;
+    nz = nz > 0 ? nz : 0;
+    spectrogram_hop(SpecLoadRing{d_out + (size_t)j * ring_n, slot, nz, ring_n},
+                    d_grid + ((size_t)j * n_rows + row) * FT8RX_GRID_COLS, T, z, w240, threadIdx.x);
 }
 #endif  // FT8RX_ILP_UNIT
 

@@ -280,10 +280,18 @@ class Candidate:
                 word = synth.pack77(*self.decode_result)
             except (ValueError, TypeError, IndexError, KeyError):
                 return None
-        spec = rx.audio_in.get_cycle_spectrum()
+        spec = self._cycle_spectrum()
         with rx._hlock:
             rp = rx._handle(1).report_probe(spec[None], [0], [o["f0_idx"]], [o["h0_idx"]], [self._tt], [self._ft], [word])
         return _m.report_dict(rp[0])
+
+    def _cycle_spectrum(self):
+        """The cycle spectrum behind this candidate's grid: audio_in's, or -- a candidate of search(channel=j) -- that of channel j's
+        frame of the newest complete cycle of its parity (wide_in.WideIn.cycle_spectrum)"""
+        rx, o = self._rx, self.origin
+        if "channel" in o:
+            return rx.wide_in.cycle_spectrum(o["channel"], o["odd_even"])
+        return rx.audio_in.get_cycle_spectrum()
 
     def _take_llr(self, llr, sd, snr, source):                       # the tail of _dB_to_llr (receiver.py:208-222)
         self.llr, self.llr_sd, self.snr, self.source = np.array(llr, np.float32), float(sd), int(snr), source
@@ -361,7 +369,7 @@ class Candidate:
             self._take_llr(llr[0], sd[0], snr[0], "grid")
             self.llr0 = self.llr.copy()
         elif step == 1:                                              # _get_llr_fine (receiver.py:140-173)
-            spec = rx.audio_in.get_cycle_spectrum()
+            spec = self._cycle_spectrum()
             with rx._hlock:                                          # weak mode: the joint three-block scan (ft8rx_fine_weak)
                 f = rx._handle(1).fine(spec[None], [0], [o["f0_idx"]], [o["h0_idx"]], weak=rx.cfg.weak)
             tt, ft = int(f["ttweak"][0]), int(f["ftweak"][0])
@@ -590,7 +598,8 @@ class Receiver:
     def __init__(self, input_device_keywords, on_message, sync_score_min=85, max_cands=200,
                  search_freq_range=[100, 3000], search_time_range=[-2.5 + 0.5, 2.5 + 0.5], verbose=False,
                  device=0, max_frames=1, time_source=None, sleep=None, audio_source=None, autostart=None, early_decode_hop=(320, 340),
-                 sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False, **extension_knobs):
+                 sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False, waterfall=False,
+                 **extension_knobs):
         if search_freq_range[1] > 5900 or search_freq_range[0] < 12.5 or search_freq_range[0] >= search_freq_range[1]:
             # the reference sizes its grid from search_freq_range (receiver.py:234-240) and itself fails beyond ~5940 Hz, where the
             # fine-sync slice runs off the cycle spectrum (receiver.py:181-182).  Here the layouts are compile-time: up to 3000 Hz runs
@@ -661,9 +670,10 @@ class Receiver:
         self.audio_in = AudioIn(search_freq_range, self, input_device_keywords)
         # wide live input (sample_rate given): the source delivers real or IQ chunks at 12 .. 192 kHz, which
         # the streaming down-converter turns into the channels dial_offsets_hz on the live handle (wide_in.WideIn; wide_in.push(chunk)
-        # may also be called directly).  audio_in stays the 12 kHz object: its search grid and waterfall are not maintained for wide input.
+        # may also be called directly).  audio_in stays the 12 kHz object; with waterfall=True the channels have a search grid and a
+        # waterfall of their own (wide_in.search_grid[j] / .waterfall_data[j], search(channel=j)).
         self.wide_in = None
-        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall)
         # The reference starts its audio thread and manage_cycle in the constructor (receiver.py:252, 336).  Same here when there
         # is something to listen to: an explicit audio_source, or PortAudio (PyAudio importable and a device matches the keywords).
         if autostart is None:
@@ -671,25 +681,28 @@ class Receiver:
         if autostart:
             self.start(audio_source)
 
-    def _set_wide_in(self, sample_rate, iq, dial_offsets_hz, bands, t_first, resample):
+    def _set_wide_in(self, sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall=False):
         """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
         if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample)
+            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
+                                           waterfall=waterfall)
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
-    def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False):
+    def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False,
+              waterfall=False):
         """Open the audio source (AudioIn.open) and start the daemon that decodes completed cycles: every 0.1 s (the reference's
         poll period, receiver.py:383) it calls poll(); on_message runs on that thread, as in the reference.  Unlike the
         reference, whose daemon dies on the first exception, an exception is kept in .thread_error and the loop ends.
         sample_rate (here or in the constructor): audio_source is an iterator of chunks of any length at that rate -- real, or IQ
         with iq=True, the forms of decode_stream -- feeding the channels dial_offsets_hz (wide_in.WideIn.open); t_first = the time of
         its first sample (default: time_source() at the first chunk).  resample=True: a rate that is no multiple of 12 kHz goes through
-        the rational resampler (wide_in.WideIn)."""
+        the rational resampler (wide_in.WideIn).  waterfall=True: the channels' search grids and waterfalls are
+        kept (wide_in.WideIn, section 16.5)."""
         if self._thread is not None and self._thread.is_alive():
             return self
         self._stop.clear()
         self.thread_error = None
-        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall)
         if self.wide_in is not None:
             if audio_source is not None:
                 self.wide_in.open(audio_source)
@@ -776,8 +789,21 @@ class Receiver:
             if self._live is not None:
                 self._live.set_ap_calls(self.cfg.ap_my_call, self.cfg.ap_dx_call)
 
-    def search(self, cyclestart_string, odd_even, search_f_idxs=None):
-        """Costas sync search over one cycle of audio_in.search_grid (reference receiver.py:338-367).
+    def _search_source(self, channel):
+        """(the 750-row grid search() reads, the band of its candidates): audio_in's, or channel j's of the wide input"""
+        if channel is None:
+            return self.audio_in.search_grid, self.band
+        w = self.wide_in
+        if w is None or not w.waterfall:
+            raise _lib.Ft8rxError(f"search(channel={channel}): the receiver keeps no grid of its channels (Receiver(..., sample_rate=, waterfall=True))")
+        if not isinstance(channel, (int, np.integer)) or not 0 <= channel < w.n_channels:
+            raise _lib.Ft8rxError(f"search(channel={channel}): the wide input has channels 0 .. {w.n_channels - 1}")
+        return w.search_grid[channel], (w.bands[channel] if w.bands is not None else self.band)
+
+    def search(self, cyclestart_string, odd_even, search_f_idxs=None, channel=None):
+        """Costas sync search over one cycle of audio_in.search_grid (reference receiver.py:338-367) -- or, with channel=j, of
+        wide_in.search_grid[j] (waterfall=True): the candidates then carry band = bands[j] and "channel": j in
+        their origin, and decode() on them takes the cycle spectrum of that channel's frame out of the down-converter's ring.
 
         odd_even selects the half of the 750-row grid (rows odd_even*375 + 1 ... + 375); hops before the cycle's
         first row read 1.0 (frame-complete semantics, DESIGN.md section 1 -- the live reference would see the
@@ -788,6 +814,7 @@ class Receiver:
         by those three steps on the host."""
         if odd_even not in (0, 1):
             raise _lib.Ft8rxError("odd_even must be 0 or 1")
+        search_grid, band = self._search_source(channel)
         if search_f_idxs is None:
             idx = list(range(*self.audio_in.search_f0_idx_range))
         else:
@@ -795,14 +822,13 @@ class Receiver:
         if not idx:
             self.candidates = []
             return []
-        width = self.audio_in.search_grid.shape[1]
+        width = search_grid.shape[1]
         if min(idx) < 4 or max(idx) + 16 > width:
             raise _lib.Ft8rxError(f"search_f_idxs must stay within [4, {width - 16}] (the grid has {width} columns, receiver.py:240)")
         if len(set(idx)) != len(idx):
             raise _lib.Ft8rxError("search_f_idxs holds an index twice")
         r0 = odd_even * self.audio_in.search_hops_per_cycle
-        rows = self.audio_in.search_grid[r0 + 1:r0 + 376] if odd_even == 0 else \
-            np.concatenate([self.audio_in.search_grid[r0 + 1:], self.audio_in.search_grid[:1]])
+        rows = search_grid[r0 + 1:r0 + 376] if odd_even == 0 else np.concatenate([search_grid[r0 + 1:], search_grid[:1]])
         with self._hlock:
             h = self._handle(1)
             grid = np.ones((1, _lib.GRID_ROWS, h.grid_cols), np.float32)
@@ -833,7 +859,9 @@ class Receiver:
         cands = []
         for f0i, h0i, sci in found:
             origin = {"h0_idx": h0i, "f0_idx": f0i, "tsec": h0i / 25.0, "fHz": 3.125 * f0i, "score": sci,
-                      "cyclestart_string": cyclestart_string, "band": self.band, "odd_even": odd_even}
+                      "cyclestart_string": cyclestart_string, "band": band, "odd_even": odd_even}
+            if channel is not None:
+                origin["channel"] = int(channel)
             cands.append(Candidate(origin, [r0 + h0i + 4, r0 + h0i + 4 * 71], rx=self, grid=grid,
                                    llr_sd_min=-np.inf if self.cfg.weak else 5))      # weak mode: no sd stop at grid or fine
         self.candidates = cands

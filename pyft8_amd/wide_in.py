@@ -153,8 +153,58 @@ class PassScheduler:
                 self.cycle, self.step = self.cycle + 1, 0
 
 
+# ---- the waterfall / search grid of the channels (waterfall=True).  The device computes row q of every channel
+# from the outputs [p0 + 480 q - 3840, p0 + 480 q) (ft8rx_ddc_stream_grid_*); these pure functions say which q that is for a hop of a
+# cycle, and where it goes in the 750-row grid Receiver.search reads.  The stream of a WideIn begins at output index 0.
+HOPS_PER_CYCLE = NSAMP // HOP      # 375
+GRID_ROWS = 2 * HOPS_PER_CYCLE     # 750: two cycles, the reference's grid
+
+
+def grid_phase(m_c0):
+    """p0, the hop phase of the grid: the first cycle's start m_c0 (it may be negative) modulo a hop, so that every hop of that cycle
+    -- and of every later one, 375 hops apart -- ends on a row"""
+    return int(m_c0) % HOP
+
+
+def grid_hops_done(m_produced, p0):
+    """The first row that does not exist yet when the outputs [.., m_produced) do: the number of q >= 0 with p0 + 480 q <= m_produced
+    (csrc/ddc_grid_ring.hpp: hops_done)"""
+    return 0 if m_produced < p0 else (int(m_produced) - p0) // HOP + 1
+
+
+def grid_rows_completed(m_before, m_after, p0, n_rows=GRID_ROWS):
+    """The rows [q_first, q_end) a push completes that moved m_produced from m_before to m_after, for a stream that began at output
+    0: hop 0 is no row when p0 = 0 (its window holds nothing of the stream), and of more than n_rows new rows only the newest n_rows
+    are held (csrc/ddc_grid_ring.hpp: completed)"""
+    q_end = grid_hops_done(m_after, p0)
+    q_first = max(grid_hops_done(m_before, p0), grid_hops_done(0, p0), q_end - n_rows)
+    return min(q_first, q_end), q_end
+
+
+def grid_place(q, m_c0, c0):
+    """Row q of the device -> (cycle c, hop h in 1 .. 375, row of the 750-row grid): with q_0 = (m_c0 - p0) / 480, the row that ends
+    where the first cycle c0 starts, row q is hop h = (q - q_0 - 1) mod 375 + 1 of cycle c = c0 + (q - q_0 - 1) div 375 and goes to
+    grid row (375 (c mod 2) + h) mod 750 -- the odd cycle's hop 375 to row 0, the layout Receiver.search reads."""
+    k = int(q) - (int(m_c0) - grid_phase(m_c0)) // HOP - 1
+    c, h = int(c0) + k // HOPS_PER_CYCLE, k % HOPS_PER_CYCLE + 1
+    return c, h, (HOPS_PER_CYCLE * (c % 2) + h) % GRID_ROWS
+
+
+def grid_row_of(c, h, m_c0, c0):
+    """The inverse: the device's row q of hop h of cycle c"""
+    return (int(m_c0) - grid_phase(m_c0)) // HOP + HOPS_PER_CYCLE * (int(c) - int(c0)) + int(h)
+
+
 class WideIn:
     """The wide live input of one Receiver: K = len(dial_offsets_hz) channels out of the source's streams.
+
+    waterfall=True: the device also computes the spectrogram row of every channel at every hop, straight
+    from the down-converter's output ring (ft8rx_ddc_stream_grid_*), and after every push the rows it completed are read once into
+    search_grid[j] ([750][width] float32, 1.0 until written; width = the 12 kHz path's for the receiver's search_freq_range), of which
+    waterfall_data[j]["data"] is a live view (the keys of AudioIn.waterfall_data).  The grid opens at the hop phase p0 = m_c mod 480
+    of the scheduler's first cycle; cycle starts are 180000 = 375 x 480 outputs apart, so hop h of cycle c lands in grid row
+    (375 (c mod 2) + h) mod 750 and is hop h of the very frame the complete pass decodes.  If a later cycle_start lands one sample
+    off through float rounding, the grid keeps its phase.  The grid shows the unblanked audio.  Off (the default) nothing of it exists.
 
     push(chunk) takes the next samples in the forms of Receiver.decode_stream -- real int16 or float [n], complex [n] or int16 (I, Q)
     pairs [n, 2] with iq=True, several streams as [n_streams, n(, 2)] -- of any length, hands them to the down-converter on the
@@ -163,7 +213,8 @@ class WideIn:
     end of a finite source it pushes zeros until the outputs of the last real sample exist, notes the passes then due and sets
     source_exhausted."""
 
-    def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False):
+    def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False,
+                 waterfall=False):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
         # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a resampled
@@ -197,6 +248,17 @@ class WideIn:
         # per channel: the texts delivered per cycle (duplicate filter) and the complete-frame messages per cycle (recall)
         self.seen = [{} for _ in range(self.n_channels)]
         self.recall_hist = [{} for _ in range(self.n_channels)]
+        # waterfall=True: per channel the 750-row grid and the reference's waterfall dict on it (a live view); None otherwise
+        self.waterfall = bool(waterfall)
+        self.search_grid = self.waterfall_data = None
+        self.grid_phase = None                   # p0, and the first cycle (c0, m_c0) the rows are placed by; the next row to read
+        self._grid_c0 = self._grid_q = None
+        self._spec_cache = (None, None, None)    # cycle_spectrum: (cycle, its frames [K][180000], {channel: spectrum})
+        if self.waterfall:
+            ai = receiver.audio_in
+            self.search_grid = [np.ones((GRID_ROWS, ai.search_grid.shape[1]), np.float32) for _ in range(self.n_channels)]
+            d = int(round(ai.waterfall_data["df"] / ai.df))             # the 12 kHz path's downsampling (receiver.WATERFALL_DOWNSAMPLE)
+            self.waterfall_data = [dict(ai.waterfall_data, data=g[::d, ::d].T) for g in self.search_grid]
 
     def _start(self, chunk):
         """The first chunk decides the sample kind and the number of streams, sets the clock and opens the device stream."""
@@ -208,13 +270,60 @@ class WideIn:
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
             self.f_mixed_hz = HANDLE_CALLS[self.mod][1](h, self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+            if self.waterfall:                   # the rows of every hop of the scheduler's cycles, behind whichever stream was opened
+                c0 = self.sched.cycle
+                self._grid_c0 = (c0, self.sched.cycle_start(c0))
+                self.grid_phase = grid_phase(self._grid_c0[1])
+                self._grid_q = grid_hops_done(0, self.grid_phase)
+                h.ddc_stream_grid_open(self.grid_phase, GRID_ROWS)
 
     def _push(self, a, real):
-        """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples"""
+        """One chunk of at most a second ([n_streams][n], packed) to the device; real: it counts as source samples.  waterfall: the
+        rows the chunk completed are read once and written in place into search_grid"""
         with self._rx._live_lock:
-            self.m_produced = HANDLE_CALLS[self.mod][2](self._rx._live_handle(self.n_channels), a)
+            h = self._rx._live_handle(self.n_channels)
+            self.m_produced = HANDLE_CALLS[self.mod][2](h, a)
+            if self.waterfall:
+                q_first, q_end = grid_rows_completed(0, self.m_produced, self.grid_phase)
+                q_first = max(q_first, self._grid_q)
+                if q_end > q_first:
+                    rows = h.ddc_stream_grid_read(q_first, q_end - q_first)
+                    c0, m_c0 = self._grid_c0
+                    for i in range(q_end - q_first):
+                        r = grid_place(q_first + i, m_c0, c0)[2]
+                        for j, g in enumerate(self.search_grid):
+                            g[r, :] = rows[j, i, :g.shape[1]]
+                    self._grid_q = q_end
         if real:
             self.n_pushed += a.shape[1]
+
+    def grid_cycle(self, odd_even):
+        """The newest cycle of parity odd_even whose 375 rows are all in search_grid, or None"""
+        if not self.waterfall or self._grid_q is None:
+            return None
+        c0, m_c0 = self._grid_c0
+        c = c0 + (self._grid_q - 1 - grid_row_of(c0, 0, m_c0, c0)) // HOPS_PER_CYCLE - 1
+        c -= (c - int(odd_even)) % 2
+        return c if c >= c0 else None            # (the cycle before the first one the scheduler decodes is never whole)
+
+    def cycle_spectrum(self, channel, odd_even):
+        """The cycle spectrum (complex64 [spec_bins]) of channel `channel`'s frame of grid_cycle(odd_even): the frame whose hops the
+        rows of that half of search_grid[channel] are, gathered out of the down-converter's ring (Candidate.decode's fine step)"""
+        c = self.grid_cycle(odd_even)
+        if c is None:
+            raise _lib.Ft8rxError(f"cycle_spectrum: no complete cycle of parity {odd_even} is in the grid of the channels yet")
+        if self._spec_cache[0] != c:
+            c0, m_c0 = self._grid_c0
+            with self._rx._live_lock:
+                h = self._rx._live_handle(self.n_channels)
+                h.ddc_stream_frame(m_c0 + NSAMP * (c - c0), NSAMP)
+                frames = h.download_audio(h.staging_ptr(), self.n_channels)
+            self._spec_cache = (c, frames, {})
+        _, frames, specs = self._spec_cache
+        if channel not in specs:
+            with self._rx._hlock:
+                specs[channel] = self._rx._handle(1).cycle_spectrum(frames[channel])[0]
+        return specs[channel]
 
     def _outputs(self, n):
         """12 kHz outputs that n input samples span, rounded up: ceil(n 12000 / sample_rate), in integers"""
