@@ -640,6 +640,63 @@ int  ft8rx_blank(ft8rx_handle* h, int16_t* d_audio, int n_frames, int32_t thresh
 int  ft8rx_blank_host(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_t threshold_q8, int guard, int taper, int32_t* stats);
 /* host only, no GPU: T[1 .. taper] -> taper, and the first min(taper, cap) entries in w (w may be NULL); -1 for taper outside [0, 64] */
 int  ft8rx_blank_taper(int taper, int32_t* w, int cap);
+/* Input-rate noise blanker (extension): the blanker above on the raw integer samples of ONE input stream at
+ * their own rate, in front of ft8rx_ddc / ft8rx_ddc_wide / ft8rx_ddc_rat, whose device entries take the blanked samples.  A stand-alone
+ * input stage: no down-converter kernel, ring or setting changes.  pyft8_amd/blank_in.py holds the numpy twin, which gives the same bits.
+ *   kinds   FT8RX_DDC_REAL_I16, FT8RX_DDC_IQ_I16, FT8RX_WIDE_REAL_I16, FT8RX_WIDE_IQ_I16, FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8;
+ *   value   per component c = x (int16), s (int8), 2 u - 255 (uint8); a[n] = |c| (real) or |cI| + |cQ| (IQ), at most 65536; a[n] = 0
+ *           for every index outside the stream (before n_origin, behind the last sample of a one-shot call or a finished stream);
+ *   level   block b is [b B, (b + 1) B) of the ABSOLUTE sample index; m_b = the element at sorted position B / 2 of its B values a;
+ *           L_b = the element at sorted position 2 of m[b - 2 .. b + 2], no clamping (m = 0 outside the stream);
+ *   hit     sample n of block b iff L_b > 0 and 256 a[n] > threshold_q8 L_b (2^24 and 2^30: int32);
+ *   gate    as ft8rx_blank, d[n] = distance to the nearest hit of the stream, the same table ft8rx_blank_taper; per component
+ *           c' = (c w + 16384) >> 15, stored as int16 / int8 c' or uint8 (c' + 255) >> 1; w = 32768 returns the input byte;
+ *   stats   int64[4]: hits, samples with w < 32768, samples with w = 0, blocks [n_origin / B, n_end / B) with L_b = 0.
+ * Streaming: after the inputs [.., n_end) exist the samples [n_origin, max(n_origin, (n_end / B - 2) B - (guard + taper))) are final
+ * and released (ft8rx_blank_in_released) -- a function of n_end alone, so every released byte is the same however the stream was cut
+ * into pushes; finish declares everything beyond n_end to be outside the stream and releases the rest.  A one-shot call on n samples
+ * is the stream with n_origin = 0, pushed n samples and finished.  Latency: at most 3 B + guard + taper samples.
+ * block: a power of two in [256, 4096]; threshold_q8 in [512, 16384]; guard, taper in [0, 64].  Anything else returns -1 with a text
+ * that names the argument. */
+#define FT8RX_BLANK_IN_BLOCK_DEFAULT             1024
+#define FT8RX_BLANK_IN_MIN_BLOCK                 256
+#define FT8RX_BLANK_IN_MAX_BLOCK                 4096
+#define FT8RX_BLANK_IN_THRESHOLD_Q8_DEFAULT_REAL 2048    /* k = 8, as ft8rx_blank */
+#define FT8RX_BLANK_IN_THRESHOLD_Q8_DEFAULT_IQ   1408    /* k = 5.5: the median of |I| + |Q| is 1.4866 sigma */
+#define FT8RX_BLANK_IN_GUARD_DEFAULT             6
+#define FT8RX_BLANK_IN_TAPER_DEFAULT             6
+#define FT8RX_BLANK_IN_MAX_SAMPLES               2147483648ull   /* of a one-shot call */
+#define FT8RX_BLANK_IN_MAX_PUSH                  268435456ull    /* of a stream's max_push */
+/* d_samples: device, n_samples samples of `kind` (aligned to a sample; 16-byte alignment takes the vector path).  d_out: NULL = in
+ * place, otherwise the samples are copied there first and blanked there (the same alignment rule).  stats: host [4], optional; levels:
+ * host [ceil(n_samples / block)][2] = (m_b, L_b), optional, a test aid.  Waits for the batches in flight, then queues its work on the
+ * handle's main stream; returns after completion when stats or levels is given, otherwise at once.  The workspaces (levels, hit mask,
+ * partial counters) belong to the handle: made at the first call, grown when a call needs more. */
+int  ft8rx_blank_in(ft8rx_handle* h, void* d_samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper,
+                    void* d_out, int64_t* stats, int32_t* levels);
+/* the same from host memory: copied into a device buffer of the handle (made at the first call, grown on demand) and blanked there;
+ * *d_out = that buffer, valid until the next ft8rx_blank_in / ft8rx_blank_in_host call.  Returns when the samples have been copied
+ * (and blanked, when stats is given); what is queued on the main stream next -- the d_in entry of a down-converter -- follows it. */
+int  ft8rx_blank_in_host(ft8rx_handle* h, const void* samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper,
+                         int64_t* stats, void** d_out);
+/* The stream: one per handle, independent of any down-converter stream (ft8rx_ddc* calls in between leave it alone).  open allocates
+ * everything (two work buffers of 4 block + guard + taper + max_push samples, the rings, a page-locked chunk), close or ft8rx_destroy
+ * releases it, nothing is allocated in between.  n_origin: the absolute index of the first sample, at most 2^53. */
+int  ft8rx_blank_in_stream_open(ft8rx_handle* h, int kind, int block, int32_t threshold_q8, int guard, int taper, uint64_t n_origin,
+                                uint64_t max_push);
+/* n_new in [0, max_push] samples from host memory or (on_device) device memory; finish != 0: the stream ends behind them, and only
+ * info and close are accepted afterwards.  -> *d_out = the device address of the newly released samples, *n_first their absolute
+ * index, *n_out their count (0 is possible, and up to block more than n_new; finish: everything left); each may be NULL.  The samples
+ * stay valid until the next push.  Queued on the handle's main stream; does not wait for it. */
+int  ft8rx_blank_in_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, int finish, void** d_out, uint64_t* n_first,
+                                uint64_t* n_out);
+/* samples pushed, samples released (absolute index of the first one that is not), the cumulative stats [4]; each may be NULL.  Waits
+ * for the main stream when stats is given. */
+int  ft8rx_blank_in_stream_info(ft8rx_handle* h, uint64_t* n_pushed, uint64_t* n_released, int64_t* stats);
+int  ft8rx_blank_in_stream_close(ft8rx_handle* h);
+/* host only, no GPU: *released = the absolute index of the first sample that is not final once [.., n_end) exist -> 0, or -1 for
+ * arguments outside the definition (n_end < n_origin included) */
+int  ft8rx_blank_in_released(uint64_t n_origin, uint64_t n_end, int block, int guard, int taper, uint64_t* released);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

@@ -100,6 +100,14 @@ PROTOTYPES = {
     "ft8rx_blank": (INT, (PTR, PTR, INT, I32, INT, INT, PTR, PTR)),
     "ft8rx_blank_host": (INT, (PTR, PTR, INT, I32, INT, INT, PTR)),
     "ft8rx_blank_taper": (INT, (INT, PTR, INT)),
+    # input-rate noise blanker
+    "ft8rx_blank_in": (INT, (PTR, PTR, INT, U64, INT, I32, INT, INT, PTR, PTR, PTR)),
+    "ft8rx_blank_in_host": (INT, (PTR, PTR, INT, U64, INT, I32, INT, INT, PTR, PTR)),
+    "ft8rx_blank_in_stream_open": (INT, (PTR, INT, INT, I32, INT, INT, U64, U64)),
+    "ft8rx_blank_in_stream_push": (INT, (PTR, PTR, U64, INT, INT, PTR, PTR, PTR)),
+    "ft8rx_blank_in_stream_info": (INT, (PTR, PTR, PTR, PTR)),
+    "ft8rx_blank_in_stream_close": (INT, (PTR,)),
+    "ft8rx_blank_in_released": (INT, (U64, U64, INT, INT, INT, PTR)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

@@ -289,6 +289,7 @@ class Handle:
         self._h = C.c_void_p()
         self.ap_calls = (None, None)
         self._ds = None                    # the open down-converter stream: (kind, n_streams, n_out)
+        self._bis = None                   # the open input blanker stream: its kind
         self._wds = None                   # the open wide stream (ddc_wide_stream_open): (kind, n_out); _ds then describes the stage behind it
         self._rts = None                   # the open rational stream (ddc_rat_stream_open): (kind, n_out); likewise (_PRE_FIELD: at most one of the two)
         rc = L.ft8rx_create(C.byref(self.cfg), self.device, self.max_frames, C.byref(self._h))
@@ -731,13 +732,24 @@ class Handle:
             return out, [[(float(arr[f, i]["fHz"]), float(arr[f, i]["tsec"])) for i in range(cnt[f])] for f in range(B)]
         return out
 
-    def ddc(self, samples, kind, rate, src, f_dial_hz, gain=1.0, want_float=False, device=False):
+    def ddc(self, samples, kind, rate, src, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
         """ft8rx_ddc_host / ft8rx_ddc (DESIGN.md section 16): down-convert [n_streams][n] samples of `kind` (ddc.REAL_I16 .. ddc.IQ_F32;
         IQ as complex or (I, Q) pairs, ddc.pack) at `rate` Hz into len(src) frames in the staging buffer (staging_ptr, download_audio),
         output j = stream src[j] with the dial f_dial_hz[j] Hz from the stream's centre -> f_mixed_hz [n_out], the dials really mixed.
         want_float: -> (f_mixed_hz, y float32 [n_out, 180000]), the audio before rounding.  device / want_float: the samples go
-        through a torch tensor and the device entry (ft8rx_ddc) instead of the library's own staging (ft8rx_ddc_host)."""
+        through a torch tensor and the device entry (ft8rx_ddc) instead of the library's own staging (ft8rx_ddc_host).  d_ptr, n: ONE
+        stream of n samples that is on the device already (a raw address, what blank_in returns; `samples` is not looked at): the
+        device entry on it, queued and not waited for."""
         from . import ddc as _ddc
+        if d_ptr is not None:
+            src = np.ascontiguousarray(src, np.int32).reshape(-1)
+            f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
+            if len(src) != len(f) or len(src) < 1:
+                raise Ft8rxError(f"ddc: one src and one f_dial_hz per output, got {len(src)} and {len(f)}")
+            fm = np.zeros(len(src), np.float64)
+            self._chk(self._L.ft8rx_ddc(self._h, int(d_ptr), int(kind), int(rate), 1, int(n), int(n), len(src), src.ctypes.data, f.ctypes.data,
+                                        float(gain), None, None, fm.ctypes.data), "ft8rx_ddc")
+            return fm
         a, n_streams, n = _ddc.pack(samples, kind)
         src = np.ascontiguousarray(src, np.int32).reshape(-1)
         f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
@@ -771,12 +783,18 @@ class Handle:
         self._ds = (int(kind), int(n_streams), len(src))
         return fm
 
-    def ddc_stream_push(self, samples):
+    def ddc_stream_push(self, samples, d_ptr=None, n=None):
         """Push the next samples of every stream ([n_streams][n], forms of ddc.pack; 1 .. one second) -> absolute index one past the
-        last output produced so far.  Asynchronous."""
+        last output produced so far.  Asynchronous.  d_ptr, n: the n next samples of the ONE stream, on the device already."""
         from . import ddc as _ddc
         if self._ds is None:
             raise Ft8rxError("ddc_stream_push: no stream is open (ddc_stream_open)")
+        if d_ptr is not None:
+            if self._ds[1] != 1:
+                raise Ft8rxError(f"ddc_stream_push: d_ptr carries one stream, the open stream has {self._ds[1]}")
+            m = C.c_uint64()
+            self._chk(self._L.ft8rx_ddc_stream_push(self._h, int(d_ptr), int(n), 1, C.byref(m)), "ft8rx_ddc_stream_push")
+            return int(m.value)
         a, n_streams, n = _ddc.pack(samples, self._ds[0])
         if n_streams != self._ds[1]:
             raise Ft8rxError(f"ddc_stream_push: {n_streams} streams, the open stream has {self._ds[1]}")
@@ -832,12 +850,17 @@ class Handle:
 
     # ---- the input pre-stages, written once: `name` is "ddc_wide" or "ddc_rat", the prefix of the C entries
     # (ft8rx_<name>*) and of the methods below, and the module that packs the samples of its kinds
-    def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device):
-        a, n = _pre_module(name).pack(samples, kind)
+    def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr=None, n=None):
+        if d_ptr is None:
+            a, n = _pre_module(name).pack(samples, kind)
         f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
         if len(f) < 1:
             raise Ft8rxError(f"{name}: at least one f_dial_hz")
         fm = np.zeros(len(f), np.float64)
+        if d_ptr is not None:                                # on the device already: the device entry, queued and not waited for
+            self._chk(getattr(self._L, f"ft8rx_{name}")(self._h, int(d_ptr), int(kind), int(rate), int(n), len(f), f.ctypes.data, float(gain),
+                                                        None, None, fm.ctypes.data), f"ft8rx_{name}")
+            return fm
         args = (int(kind), int(rate), n, len(f), f.ctypes.data, float(gain))
         if not (device or want_float):
             self._chk(getattr(self._L, f"ft8rx_{name}_host")(self._h, a.ctypes.data, *args, fm.ctypes.data), f"ft8rx_{name}_host")
@@ -869,10 +892,14 @@ class Handle:
             raise Ft8rxError(f"{name}_stream_{what}: no {_PRE_WORD[name]} stream is open ({name}_stream_open)")
         return s
 
-    def _pre_push(self, name, samples, device):
-        a, n = _pre_module(name).pack(samples, self._pre_stream(name, "push")[0])
+    def _pre_push(self, name, samples, device, d_ptr=None, n=None):
+        kind = self._pre_stream(name, "push")[0]
         entry = f"ft8rx_{name}_stream_push"
         m = C.c_uint64()
+        if d_ptr is not None:                                # on the device already: queued and not waited for
+            self._chk(getattr(self._L, entry)(self._h, int(d_ptr), int(n), 1, C.byref(m)), entry)
+            return int(m.value)
+        a, n = _pre_module(name).pack(samples, kind)
         if not device:
             self._chk(getattr(self._L, entry)(self._h, a.ctypes.data, n, 0, C.byref(m)), entry)
             return int(m.value)
@@ -895,21 +922,22 @@ class Handle:
         self._ds = None
 
     # ---- wide pre-decimator (ft8rx_ddc_wide*): ONE stream at 240 kHz .. 129.6 MHz in front of the down-converter
-    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
+    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
         """ft8rx_ddc_wide_host / ft8rx_ddc_wide: one stream of `kind` (ddc_wide.REAL_I16 .. ddc_wide.IQ_I8; forms of ddc_wide.pack) at
         `rate` Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
         [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        return self._pre_oneshot("ddc_wide", samples, kind, rate, f_dial_hz, gain, want_float, device)
+        return self._pre_oneshot("ddc_wide", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n)
 
     def ddc_wide_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
         """Open the wide stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the first
         sample that will be pushed, a multiple of 1008 rate / 12000.  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
         return self._pre_open("ddc_wide", kind, rate, f_dial_hz, gain, n_origin, keep_f32)
 
-    def ddc_wide_stream_push(self, samples, device=False):
+    def ddc_wide_stream_push(self, samples, device=False, d_ptr=None, n=None):
         """Push the next samples (forms of ddc_wide.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced
-        so far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
-        return self._pre_push("ddc_wide", samples, device)
+        so far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream).
+        d_ptr, n: the n next samples, on the device already (a raw address, what blank_in_stream_push releases)."""
+        return self._pre_push("ddc_wide", samples, device, d_ptr, n)
 
     def ddc_wide_stream_read_mid(self, k_first, n):
         """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
@@ -919,21 +947,22 @@ class Handle:
         self._pre_close("ddc_wide")
 
     # ---- rational resampler (ft8rx_ddc_rat*): ONE stream at 44.1 kHz, 2.048 MS/s, ... in front of the down-converter
-    def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False):
+    def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
         """ft8rx_ddc_rat_host / ft8rx_ddc_rat: one stream of `kind` (ddc_rat.REAL_I16 .. ddc_rat.IQ_I8; forms of ddc_rat.pack) at `rate`
         Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
         [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        return self._pre_oneshot("ddc_rat", samples, kind, rate, f_dial_hz, gain, want_float, device)
+        return self._pre_oneshot("ddc_rat", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n)
 
     def ddc_rat_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
         """Open the rational stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the
         first sample that will be pushed (ddc_rat.origin_ok).  -> f_mixed_hz.  ddc_stream_frame / _read / _info then work on it."""
         return self._pre_open("ddc_rat", kind, rate, f_dial_hz, gain, n_origin, keep_f32)
 
-    def ddc_rat_stream_push(self, samples, device=False):
+    def ddc_rat_stream_push(self, samples, device=False, d_ptr=None, n=None):
         """Push the next samples (forms of ddc_rat.pack; 1 .. one second) -> absolute index one past the last 12 kHz output produced so
-        far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream)."""
-        return self._pre_push("ddc_rat", samples, device)
+        far.  Asynchronous.  device: through a torch tensor and the device form of the entry (the call then waits for the stream).
+        d_ptr, n: the n next samples, on the device already (a raw address, what blank_in_stream_push releases)."""
+        return self._pre_push("ddc_rat", samples, device, d_ptr, n)
 
     def ddc_rat_stream_read_mid(self, k_first, n):
         """Test aid: intermediate samples [k_first, k_first + n) of every channel -> complex64 [n_out, n]."""
@@ -962,6 +991,85 @@ class Handle:
         self._chk(self._L.ft8rx_blank_host(self._h, audio.ctypes.data, len(audio), int(threshold_q8), int(guard), int(taper), stats.ctypes.data),
                   "ft8rx_blank_host")
         return stats
+
+    # ---- input-rate noise blanker (ft8rx_blank_in*; pyft8_amd/blank_in.py holds the twin and the parameter checks)
+    def blank_in(self, samples, kind, block=1024, threshold_q8=None, guard=6, taper=6, d_ptr=None, n=None, d_out=None, want_stats=True,
+                 want_levels=False, download=False):
+        """ft8rx_blank_in_host / ft8rx_blank_in: blank ONE stream's samples of `kind` (forms of blank_in.pack) at their own rate.
+        Host samples go into the handle's device buffer and are blanked there -> (d_ptr, n, stats int64 [4]): the raw device address
+        a down-converter's d_ptr argument takes, valid until the next blank_in call.  d_ptr, n: samples on the device already, in
+        place or into d_out -> (d_out or d_ptr, n, stats or None[, levels int32 [n_blocks, 2] = (m_b, L_b)]).  download: the blanked
+        samples come back too, as the last element."""
+        from . import blank_in as _bi
+        q8 = int(threshold_q8) if threshold_q8 is not None else (1408 if _bi.is_iq(kind) else 2048)
+        stats = np.zeros(4, np.int64) if want_stats else None
+        if d_ptr is None:
+            a, n = _bi.pack(samples, kind)
+            out = C.c_void_p()
+            self._chk(self._L.ft8rx_blank_in_host(self._h, a.ctypes.data, int(kind), n, int(block), q8, int(guard), int(taper),
+                                                  stats.ctypes.data if want_stats else None, C.byref(out)), "ft8rx_blank_in_host")
+            res = [int(out.value or 0), n, stats]
+            shape, dt = a.shape, a.dtype
+        else:
+            n = int(n)
+            lv = np.zeros((max(-(-n // max(int(block), 1)), 0), 2), np.int32) if want_levels else None
+            self._chk(self._L.ft8rx_blank_in(self._h, int(d_ptr), int(kind), n, int(block), q8, int(guard), int(taper), d_out or None,
+                                             stats.ctypes.data if want_stats else None, lv.ctypes.data if want_levels else None), "ft8rx_blank_in")
+            res = [int(d_out or d_ptr), n, stats] + ([lv] if want_levels else [])
+            shape, dt = ((n, 2) if _bi.is_iq(kind) else (n,)), _bi._DTYPE[kind]
+        if download:
+            y = np.empty(shape, dt)
+            self.sync()
+            self._chk(self._L.ft8rx_copy_to_host(self._h, y.ctypes.data, res[0], y.nbytes), "ft8rx_copy_to_host")
+            res.append(y)
+        return tuple(res)
+
+    def blank_in_stream_open(self, kind, block=1024, threshold_q8=None, guard=6, taper=6, n_origin=0, max_push=1 << 20):
+        """Open the handle's input blanker stream (one per handle, independent of the down-converter streams): everything is allocated
+        here and released by blank_in_stream_close."""
+        from . import blank_in as _bi
+        q8 = int(threshold_q8) if threshold_q8 is not None else (1408 if _bi.is_iq(kind) else 2048)
+        self._chk(self._L.ft8rx_blank_in_stream_open(self._h, int(kind), int(block), q8, int(guard), int(taper), int(n_origin), int(max_push)),
+                  "ft8rx_blank_in_stream_open")
+        self._bis = int(kind)
+
+    def blank_in_stream_push(self, samples=None, finish=False, d_ptr=None, n=None, download=False):
+        """Push the next samples (forms of blank_in.pack, 0 .. max_push; None = none; d_ptr, n: on the device already) -> (d_out,
+        n_first, n_out): the raw device address, absolute index and count of the samples this push released, valid until the next
+        push.  finish: the stream ends here and everything left is released.  download: -> (d_out, n_first, n_out, samples)."""
+        from . import blank_in as _bi
+        if getattr(self, "_bis", None) is None:
+            raise Ft8rxError("blank_in_stream_push: no input blanker stream is open (blank_in_stream_open)")
+        kind = self._bis
+        out, first, cnt = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        if d_ptr is not None:
+            args = (int(d_ptr), int(n), 1)
+        elif samples is None:
+            args = (None, 0, 0)
+        else:
+            a, n = _bi.pack(samples, kind)
+            args = (a.ctypes.data, n, 0)
+        self._chk(self._L.ft8rx_blank_in_stream_push(self._h, *args, int(bool(finish)), C.byref(out), C.byref(first), C.byref(cnt)),
+                  "ft8rx_blank_in_stream_push")
+        res = (int(out.value or 0), int(first.value), int(cnt.value))
+        if not download:
+            return res
+        y = np.empty((res[2], 2) if _bi.is_iq(kind) else (res[2],), _bi._DTYPE[kind])
+        if res[2]:
+            self.sync()
+            self._chk(self._L.ft8rx_copy_to_host(self._h, y.ctypes.data, res[0], y.nbytes), "ft8rx_copy_to_host")
+        return res + (y,)
+
+    def blank_in_stream_info(self):
+        """-> {"n_pushed", "n_released", "stats"}: samples pushed, absolute index of the first sample not released, int64 [4]"""
+        p, r = C.c_uint64(), C.c_uint64()
+        stats = np.zeros(4, np.int64)
+        self._chk(self._L.ft8rx_blank_in_stream_info(self._h, C.byref(p), C.byref(r), stats.ctypes.data), "ft8rx_blank_in_stream_info")
+        return {"n_pushed": int(p.value), "n_released": int(r.value), "stats": stats}
+
+    def blank_in_stream_close(self):
+        self._chk(self._L.ft8rx_blank_in_stream_close(self._h), "ft8rx_blank_in_stream_close")
+        self._bis = None
 
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for

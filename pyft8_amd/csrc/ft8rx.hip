@@ -64,6 +64,7 @@
 #include "kernels/ddc_wide.hpp"
 #include "kernels/ddc_rat.hpp"
 #include "kernels/blanker.hpp"
+#include "kernels/blank_in.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -73,6 +74,7 @@
 #include "ddc_grid_ring.hpp"
 #include "ddc_wide_ring.hpp"
 #include "ddc_rat_ring.hpp"
+#include "blank_in_ring.hpp"
 #include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
@@ -258,6 +260,24 @@ struct ft8rx_handle {
     // hit mask [max_frames][2813] 64-bit words, the counters' tile partials [max_frames][88][4], the counters [max_frames][4] and the
     // taper tables [65][65]
     int32_t* d_bl_lv = nullptr; uint64_t* d_bl_mask = nullptr; int32_t* d_bl_part = nullptr; int32_t* d_bl_stats = nullptr; int32_t* d_bl_taper = nullptr;
+    // input-rate noise blanker (ft8rx_blank_in*, kernels/blank_in.hpp).  BlankInWs: what one run works in -- the
+    // level ring [lv_cap][2], the hit mask ring (mask_words 64-bit words), the partial counters of one hit and one gate launch
+    // [part_cap][2] each, the cumulative counters int64[4].  bi: the one-shot entries' (first use, grown on demand), with the host
+    // entry's sample buffer d_bi_buf; d_bi_taper: the taper tables [65][65].  bis: the stream -- everything allocated by open and
+    // released by close (or destroy): two work buffers used in turn ([leftover | chunk], `base` = absolute index of the current one's
+    // first sample), the page-locked chunk.
+    struct BlankInWs {
+        int32_t* d_lv = nullptr; size_t lv_cap = 0; uint64_t* d_mask = nullptr; size_t mask_words = 0;
+        int32_t* d_part_h = nullptr; int32_t* d_part_g = nullptr; size_t part_cap = 0; long long* d_stats = nullptr;
+    } bi;
+    char* d_bi_buf = nullptr; size_t bi_buf_cap = 0; int32_t* d_bi_taper = nullptr;
+    struct BlankInStream {
+        bool open = false, finished = false; int kind = 0, fmt = 0, log2_b = 0, guard = 0, taper = 0, cur = 0; int32_t threshold_q8 = 0;
+        int64_t n_origin = 0, pushed = 0, max_push = 0, base = 0;
+        char* d_work[2] = {nullptr, nullptr}; char* h_stage = nullptr;
+        BlankInWs ws;
+        hipEvent_t ev = nullptr;
+    } bis;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -344,7 +364,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -515,6 +535,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     if (h->ddc_ev) hipEventDestroy(h->ddc_ev);
     if (h->ds.ev) hipEventDestroy(h->ds.ev);
     if (h->ps.ev) hipEventDestroy(h->ps.ev);
+    if (h->bis.ev) hipEventDestroy(h->bis.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -2310,6 +2331,276 @@ int ft8rx_blank_host(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_
     HIPCHK(h, hipMemcpyAsync(h->d_audio, audio, sizeof(int16_t) * (size_t)n_frames * FT8RX_NSAMP, hipMemcpyHostToDevice, h->stream));
     if (const int rc = blank_run(h, h->d_audio, n_frames, threshold_q8, guard, taper, stats, nullptr)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- input-rate noise blanker (kernels/blank_in.hpp; the index arithmetic is blank_in_ring.hpp's)
+static int blank_in_fmt(int kind) {
+    switch (kind) {
+        case FT8RX_DDC_REAL_I16: case FT8RX_WIDE_REAL_I16: return BIN_REAL_I16;
+        case FT8RX_DDC_IQ_I16: case FT8RX_WIDE_IQ_I16: return BIN_IQ_I16;
+        case FT8RX_WIDE_IQ_U8: return BIN_IQ_U8;
+        case FT8RX_WIDE_IQ_I8: return BIN_IQ_I8;
+        default: return -1;
+    }
+}
+static size_t blank_in_sample_bytes(int fmt) { return fmt == BIN_REAL_I16 ? 2 : fmt == BIN_IQ_I16 ? 4 : 2; }
+static int blank_in_log2(int block) {
+    for (int k = 8; k <= 12; k++) if (block == (1 << k)) return k;
+    return -1;
+}
+// the text of a refusal -> err (host only: ft8rx_blank_in_released has no handle), or nullptr
+static const char* blank_in_refusal(int kind, bool with_kind, int block, int32_t threshold_q8, int guard, int taper, char* err, size_t cap) {
+    static_assert(FT8RX_BLANK_IN_MIN_BLOCK == 256 && FT8RX_BLANK_IN_MAX_BLOCK == 4096 && BIN_HALO == FT8RX_BLANK_MAX_GUARD + FT8RX_BLANK_MAX_TAPER &&
+                  BIN_TAPER_ROW == FT8RX_BLANK_MAX_TAPER + 1 && FT8RX_BLANK_IN_MAX_BLOCK <= 16 * BIN_NT, "input blanker geometry");
+    if (with_kind && blank_in_fmt(kind) < 0) snprintf(err, cap, "kind %d is not an integer kind (real int16, IQ int16, IQ uint8, IQ int8)", kind);
+    else if (blank_in_log2(block) < 0) snprintf(err, cap, "block %d is not a power of two in [%d, %d]", block, FT8RX_BLANK_IN_MIN_BLOCK, FT8RX_BLANK_IN_MAX_BLOCK);
+    else if (threshold_q8 < FT8RX_BLANK_MIN_THRESHOLD_Q8 || threshold_q8 > FT8RX_BLANK_MAX_THRESHOLD_Q8)
+        snprintf(err, cap, "threshold_q8 %d outside [%d, %d] (256 k, k = 2 .. 64)", (int)threshold_q8, FT8RX_BLANK_MIN_THRESHOLD_Q8, FT8RX_BLANK_MAX_THRESHOLD_Q8);
+    else if (guard < 0 || guard > FT8RX_BLANK_MAX_GUARD) snprintf(err, cap, "guard %d outside [0, %d]", guard, FT8RX_BLANK_MAX_GUARD);
+    else if (taper < 0 || taper > FT8RX_BLANK_MAX_TAPER) snprintf(err, cap, "taper %d outside [0, %d]", taper, FT8RX_BLANK_MAX_TAPER);
+    else return nullptr;
+    return err;
+}
+static int blank_in_check(ft8rx_handle* h, const char* who, int kind, int block, int32_t threshold_q8, int guard, int taper) {
+    char text[200];
+    if (!blank_in_refusal(kind, true, block, threshold_q8, guard, taper, text, sizeof(text))) return 0;
+    set_err(h, "%s: %s", who, text);
+    return -1;
+}
+
+int ft8rx_blank_in_released(uint64_t n_origin, uint64_t n_end, int block, int guard, int taper, uint64_t* released) {
+    char text[200];
+    if (blank_in_refusal(0, false, block, FT8RX_BLANK_IN_THRESHOLD_Q8_DEFAULT_REAL, guard, taper, text, sizeof(text))) return -1;
+    if (n_end < n_origin || n_end > ((uint64_t)1 << 62)) return -1;
+    if (released) *released = (uint64_t)blankin::released((int64_t)n_origin, (int64_t)n_end, block, guard, taper);
+    return 0;
+}
+
+// the taper tables (shared by the one-shot entries and the stream; 17 KB, made once)
+static int blank_in_tables(ft8rx_handle* h) {
+    if (ws_ready(h, WS_BLANK_IN)) return 0;
+    std::vector<int32_t> tab((size_t)BIN_TAPER_ROW * BIN_TAPER_ROW, 0);
+    for (int R = 0; R <= FT8RX_BLANK_MAX_TAPER; R++) blank_taper(R, &tab[(size_t)R * BIN_TAPER_ROW]);
+    FirstUse F(h, WS_BLANK_IN);
+    F.dev(&h->d_bi_taper, tab.size());
+    FIRST_HIP(F, hipMemcpy(h->d_bi_taper, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+    return F.done();
+}
+
+// what a run of at most n_max new samples needs: every ring holds what a push reads of the pushes before it (blank_in_ring.hpp)
+struct BlankInSizes { size_t lv_cap, mask_words, part_cap; };
+static BlankInSizes blank_in_sizes(int64_t n_max, int64_t B) {
+    BlankInSizes z{16, 64, 0};
+    while ((int64_t)z.lv_cap < n_max / B + 16) z.lv_cap *= 2;
+    while ((int64_t)z.mask_words * 64 < n_max + 8 * B + 8192) z.mask_words *= 2;
+    z.part_cap = (size_t)((n_max + 8 * B + 256) / 2048 + 4);
+    return z;
+}
+static void blank_in_ws_release(ft8rx_handle* h, ft8rx_handle::BlankInWs& w) {
+    release_dev(h, w.d_lv); release_dev(h, w.d_mask); release_dev(h, w.d_part_h); release_dev(h, w.d_part_g); release_dev(h, w.d_stats);
+    w = ft8rx_handle::BlankInWs();
+}
+// all or nothing; a workspace that is large enough stays
+static int blank_in_ws_alloc(ft8rx_handle* h, ft8rx_handle::BlankInWs& w, const BlankInSizes& z) {
+    if (w.d_lv && w.lv_cap >= z.lv_cap && w.mask_words >= z.mask_words && w.part_cap >= z.part_cap) return 0;
+    blank_in_ws_release(h, w);
+    int rc = dalloc(h, &w.d_lv, 2 * z.lv_cap);
+    if (!rc) rc = dalloc(h, &w.d_mask, z.mask_words);
+    if (!rc) rc = dalloc(h, &w.d_part_h, 2 * z.part_cap);
+    if (!rc) rc = dalloc(h, &w.d_part_g, 2 * z.part_cap);
+    if (!rc) rc = dalloc(h, &w.d_stats, (size_t)4);
+    if (rc) { blank_in_ws_release(h, w); return -2; }
+    w.lv_cap = z.lv_cap; w.mask_words = z.mask_words; w.part_cap = z.part_cap;
+    return 0;
+}
+
+// The launches of one plan on the main stream.  x: the sample of absolute index p.base; the stream's samples [n_origin, p.n_end) exist.
+static int blank_in_launch(ft8rx_handle* h, ft8rx_handle::BlankInWs& w, int fmt, char* x, const blankin::Plan& p, int64_t n_origin, int log2_b,
+                           int32_t threshold_q8, int guard, int taper) {
+    const int64_t B = (int64_t)1 << log2_b;
+    const BinWin W{x, (long long)p.base, (long long)n_origin, (long long)p.n_end};
+    const int64_t n_lv = p.lv1 - p.lv0, n_h = ((p.hb1 - p.hb0) * (B / 8) + BIN_NT - 1) / BIN_NT;
+    const int64_t n_g = p.g1 > p.g0 ? ((p.g1 - 1) >> 11) - (p.g0 >> 11) + 1 : 0;
+    if (n_h > (int64_t)w.part_cap || n_g > (int64_t)w.part_cap || n_lv + 8 > (int64_t)w.lv_cap) { set_err(h, "input blanker: a plan beyond its workspaces"); return -2; }
+    const bool vec = ((uintptr_t)x % 16) == 0;
+    auto run = [&](auto f, auto v) {
+        constexpr int F = decltype(f)::value;
+        constexpr bool V = decltype(v)::value;
+        if (n_lv > 0) k_blankin_level<F, V><<<(unsigned)n_lv, BIN_NT, 0, h->stream>>>(W, log2_b, (long long)p.lv0, w.d_lv, (int)w.lv_cap);
+        if (n_h > 0)
+            k_blankin_hits<F, V><<<(unsigned)n_h, BIN_NT, 0, h->stream>>>(W, log2_b, (long long)p.hb0, (long long)p.hb1, (long long)p.b_first, (long long)p.b_have,
+                                                                       (long long)(p.n_end / B), threshold_q8, w.d_lv, (int)w.lv_cap,
+                                                                       reinterpret_cast<uint8_t*>(w.d_mask), (long long)(8 * w.mask_words), w.d_part_h);
+        if (n_g > 0)
+            k_blankin_gate<F, V><<<(unsigned)n_g, BIN_NT, 0, h->stream>>>(W, (long long)p.g0, (long long)p.g1, (long long)(p.b_first * B), (long long)p.m_hi, w.d_mask,
+                                                                       (long long)w.mask_words, guard, taper, h->d_bi_taper, w.d_part_g);
+    };
+    with_bool(vec, [&](auto v) {
+        switch (fmt) {
+            case BIN_REAL_I16: run(std::integral_constant<int, BIN_REAL_I16>(), v); break;
+            case BIN_IQ_I16: run(std::integral_constant<int, BIN_IQ_I16>(), v); break;
+            case BIN_IQ_U8: run(std::integral_constant<int, BIN_IQ_U8>(), v); break;
+            default: run(std::integral_constant<int, BIN_IQ_I8>(), v); break;
+        }
+    });
+    if (n_h > 0 || n_g > 0) k_blankin_stats<<<1, BIN_NT, 0, h->stream>>>(w.d_part_h, (int)n_h, w.d_part_g, (int)n_g, w.d_stats);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the one-shot on n samples at d: the stream with n_origin = 0, pushed n samples and finished
+static int blank_in_oneshot(ft8rx_handle* h, char* d, int fmt, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper, int64_t* stats,
+                            int32_t* levels) {
+    const int log2_b = blank_in_log2(block);
+    if (blank_in_tables(h) || blank_in_ws_alloc(h, h->bi, blank_in_sizes((int64_t)n_samples, block))) return -2;
+    const blankin::Plan p = blankin::plan(0, 0, (int64_t)n_samples, true, block, guard, taper);
+    HIPCHK(h, hipMemsetAsync(h->bi.d_stats, 0, sizeof(long long) * 4, h->stream));
+    if (const int rc = blank_in_launch(h, h->bi, fmt, d, p, 0, log2_b, threshold_q8, guard, taper)) return rc;
+    if (stats) HIPCHK(h, hipMemcpyAsync(stats, h->bi.d_stats, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (levels) HIPCHK(h, hipMemcpyAsync(levels, h->bi.d_lv, sizeof(int32_t) * 2 * (size_t)p.b_have, hipMemcpyDeviceToHost, h->stream));
+    if (stats || levels) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+static int blank_in_n_check(ft8rx_handle* h, const char* who, uint64_t n_samples) {
+    if (n_samples >= 1 && n_samples <= FT8RX_BLANK_IN_MAX_SAMPLES) return 0;
+    set_err(h, "%s: n_samples %llu outside [1, %llu]", who, (unsigned long long)n_samples, (unsigned long long)FT8RX_BLANK_IN_MAX_SAMPLES);
+    return -1;
+}
+
+int ft8rx_blank_in(ft8rx_handle* h, void* d_samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper, void* d_out,
+                   int64_t* stats, int32_t* levels) {
+    if (!h) return -1;
+    if (blank_in_check(h, "ft8rx_blank_in", kind, block, threshold_q8, guard, taper) || blank_in_n_check(h, "ft8rx_blank_in", n_samples)) return -1;
+    const int fmt = blank_in_fmt(kind);
+    const size_t sb = blank_in_sample_bytes(fmt), align = fmt == BIN_IQ_U8 || fmt == BIN_IQ_I8 ? 1 : 2;
+    if (!d_samples || ((uintptr_t)d_samples % align) != 0) { set_err(h, "ft8rx_blank_in: d_samples is NULL or not aligned to a sample"); return -1; }
+    if (((uintptr_t)d_out % align) != 0) { set_err(h, "ft8rx_blank_in: d_out is not aligned to a sample"); return -1; }
+    ENTER(h);
+    if (d_out && d_out != d_samples) HIPCHK(h, hipMemcpyAsync(d_out, d_samples, (size_t)n_samples * sb, hipMemcpyDeviceToDevice, h->stream));
+    return blank_in_oneshot(h, (char*)(d_out ? d_out : d_samples), fmt, n_samples, block, threshold_q8, guard, taper, stats, levels);
+}
+
+int ft8rx_blank_in_host(ft8rx_handle* h, const void* samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper,
+                        int64_t* stats, void** d_out) {
+    if (!h) return -1;
+    if (blank_in_check(h, "ft8rx_blank_in_host", kind, block, threshold_q8, guard, taper) || blank_in_n_check(h, "ft8rx_blank_in_host", n_samples)) return -1;
+    if (!samples) { set_err(h, "ft8rx_blank_in_host: samples is NULL"); return -1; }
+    const int fmt = blank_in_fmt(kind);
+    const size_t bytes = (size_t)n_samples * blank_in_sample_bytes(fmt);
+    ENTER(h);
+    if (h->bi_buf_cap < bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));     // what was queued behind the last call still reads the old buffer
+        release_dev(h, h->d_bi_buf); h->d_bi_buf = nullptr; h->bi_buf_cap = 0;
+        if (dalloc(h, &h->d_bi_buf, bytes)) return -2;
+        h->bi_buf_cap = bytes;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_bi_buf, samples, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));         // the caller's memory is free again
+    if (const int rc = blank_in_oneshot(h, h->d_bi_buf, fmt, n_samples, block, threshold_q8, guard, taper, stats, nullptr)) return rc;
+    if (d_out) *d_out = h->d_bi_buf;
+    return 0;
+}
+
+static void blank_in_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::BlankInStream& s = h->bis;
+    release_dev(h, s.d_work[0]); release_dev(h, s.d_work[1]); release_host(h, s.h_stage);
+    blank_in_ws_release(h, s.ws);
+    const hipEvent_t ev = s.ev;
+    s = ft8rx_handle::BlankInStream();
+    s.ev = ev;
+}
+
+int ft8rx_blank_in_stream_open(ft8rx_handle* h, int kind, int block, int32_t threshold_q8, int guard, int taper, uint64_t n_origin, uint64_t max_push) {
+    if (!h) return -1;
+    const char* who = "ft8rx_blank_in_stream_open";
+    if (h->bis.open) { set_err(h, "%s: an input blanker stream is open on this handle already (ft8rx_blank_in_stream_close)", who); return -1; }
+    if (blank_in_check(h, who, kind, block, threshold_q8, guard, taper)) return -1;
+    if (n_origin > ((uint64_t)1 << 53)) { set_err(h, "%s: n_origin %llu beyond 2^53", who, (unsigned long long)n_origin); return -1; }
+    if (max_push < 1 || max_push > FT8RX_BLANK_IN_MAX_PUSH) {
+        set_err(h, "%s: max_push %llu outside [1, %llu]", who, (unsigned long long)max_push, (unsigned long long)FT8RX_BLANK_IN_MAX_PUSH); return -1;
+    }
+    ENTER(h);
+    if (blank_in_tables(h)) return -2;
+    ft8rx_handle::BlankInStream& s = h->bis;
+    const int fmt = blank_in_fmt(kind);
+    const size_t sb = blank_in_sample_bytes(fmt), work = (size_t)blankin::capacity(block, guard, taper, (int64_t)max_push) * sb;
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
+    if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (!rc) rc = dalloc(h, &s.d_work[0], work);
+    if (!rc) rc = dalloc(h, &s.d_work[1], work);
+    if (!rc) rc = halloc(h, &s.h_stage, (size_t)max_push * sb);
+    if (!rc) rc = blank_in_ws_alloc(h, s.ws, blank_in_sizes((int64_t)max_push, block));
+    if (!rc && (e = hipMemsetAsync(s.ws.d_stats, 0, sizeof(long long) * 4, h->stream)) != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (rc) { blank_in_stream_release(h); return -2; }
+    s.kind = kind; s.fmt = fmt; s.log2_b = blank_in_log2(block); s.threshold_q8 = threshold_q8; s.guard = guard; s.taper = taper;
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.max_push = (int64_t)max_push; s.base = (int64_t)n_origin / block * block; s.cur = 0;
+    s.finished = false; s.open = true;
+    return 0;
+}
+
+int ft8rx_blank_in_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, int finish, void** d_out, uint64_t* n_first,
+                               uint64_t* n_out) {
+    if (!h) return -1;
+    const char* who = "ft8rx_blank_in_stream_push";
+    ft8rx_handle::BlankInStream& s = h->bis;
+    if (!s.open) { set_err(h, "%s: no input blanker stream is open (ft8rx_blank_in_stream_open)", who); return -1; }
+    if (s.finished) { set_err(h, "%s: the stream is finished: only ft8rx_blank_in_stream_info and ft8rx_blank_in_stream_close are accepted", who); return -1; }
+    if (n_new > (uint64_t)s.max_push) { set_err(h, "%s: n_new %llu outside [0, %llu] (max_push)", who, (unsigned long long)n_new, (unsigned long long)s.max_push); return -1; }
+    const size_t sb = blank_in_sample_bytes(s.fmt), align = s.fmt == BIN_IQ_U8 || s.fmt == BIN_IQ_I8 ? 1 : 2;
+    if (n_new && (!in || (on_device && ((uintptr_t)in % align) != 0))) { set_err(h, "%s: in is NULL or not aligned to a sample", who); return -1; }
+    if (s.n_origin + s.pushed + (int64_t)n_new > ((int64_t)1 << 54)) { set_err(h, "%s: n_new %llu takes the stream past index 2^54", who, (unsigned long long)n_new); return -1; }
+    // (no ENTER: a push touches the stream's own buffers only, on the main stream; batches in flight read none of them)
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t B = (int64_t)1 << s.log2_b, n_start = s.n_origin + s.pushed;
+    const blankin::Plan p = blankin::plan(s.n_origin, n_start, (int64_t)n_new, finish != 0, B, s.guard, s.taper);
+    // the other work buffer: the leftover to its front -- behind whatever consumed the samples the last push released -- then the chunk
+    char* old = s.d_work[s.cur];
+    char* x = s.d_work[s.cur ^ 1];
+    if (p.left_n > 0)
+        HIPCHK(h, hipMemcpyAsync(x + (size_t)(p.g0 - p.base) * sb, old + (size_t)(p.g0 - s.base) * sb, (size_t)p.left_n * sb, hipMemcpyDeviceToDevice, h->stream));
+    if (n_new) {
+        char* dst = x + (size_t)(n_start - p.base) * sb;
+        if (on_device) {
+            HIPCHK(h, hipMemcpyAsync(dst, in, (size_t)n_new * sb, hipMemcpyDeviceToDevice, h->stream));
+        } else {                                         // through the page-locked buffer, once the previous push's copy has left it
+            HIPCHK(h, hipEventSynchronize(s.ev));
+            memcpy(s.h_stage, in, (size_t)n_new * sb);
+            HIPCHK(h, hipMemcpyAsync(dst, s.h_stage, (size_t)n_new * sb, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipEventRecord(s.ev, h->stream));
+        }
+    }
+    if (const int rc = blank_in_launch(h, s.ws, s.fmt, x, p, s.n_origin, s.log2_b, s.threshold_q8, s.guard, s.taper)) return rc;
+    s.cur ^= 1; s.base = p.base; s.pushed += (int64_t)n_new; s.finished = finish != 0;
+    if (d_out) *d_out = x + (size_t)(p.g0 - p.base) * sb;
+    if (n_first) *n_first = (uint64_t)p.g0;
+    if (n_out) *n_out = (uint64_t)(p.g1 - p.g0);
+    return 0;
+}
+
+int ft8rx_blank_in_stream_info(ft8rx_handle* h, uint64_t* n_pushed, uint64_t* n_released, int64_t* stats) {
+    if (!h) return -1;
+    const ft8rx_handle::BlankInStream& s = h->bis;
+    if (!s.open) { set_err(h, "ft8rx_blank_in_stream_info: no input blanker stream is open (ft8rx_blank_in_stream_open)"); return -1; }
+    const int64_t n_end = s.n_origin + s.pushed;
+    if (n_pushed) *n_pushed = (uint64_t)s.pushed;
+    if (n_released) *n_released = (uint64_t)(s.finished ? n_end : blankin::released(s.n_origin, n_end, (int64_t)1 << s.log2_b, s.guard, s.taper));
+    if (stats) {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipMemcpyAsync(stats, s.ws.d_stats, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+int ft8rx_blank_in_stream_close(ft8rx_handle* h) {
+    if (!h) return -1;
+    if (!h->bis.open) { set_err(h, "ft8rx_blank_in_stream_close: no input blanker stream is open"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes, and what consumed the released samples
+    blank_in_stream_release(h);
     return 0;
 }
 

@@ -23,6 +23,11 @@ Noise blanker (extension): Receiver(..., noise_blanker=Tru
 impulses in every frame that is about to be decoded -- decode_frames / decode_frames_arrays, decode_stream, the live passes of poll --
 on the GPU (ft8rx_blank) and leaves the per-frame counters of the last batch in `blanker_stats`.  The live `audio_in.search_grid` /
 `waterfall_data`, and search() on them, stay the unblanked audio.  Off (the default) nothing of it runs.
+
+Input blanker (extension): Receiver(..., input_blanker=True | k | {"threshold": k, "guard": G, "taper": R,
+"block": B}), and the same keyword on decode_stream, blanks ONE stream of integer samples at its own rate on the GPU (ft8rx_blank_in*)
+in front of the down-converter, which reads the blanked samples on the device; `input_blanker_stats` holds the cumulative counters.
+The live search grid / waterfall of the channels show the blanked input.  Off (the default) nothing of it runs.
 """
 import threading as _threading
 import time as _time
@@ -654,6 +659,13 @@ class Receiver:
         # [B, 4] = hits, samples with w < 32768, samples with w = 0, blocks with L_b = 0 per frame.
         self.noise_blanker = _blanker.params(extension_knobs.pop("noise_blanker", None))
         self.blanker_stats = None
+        # input blanker: the same values, and a dict may also hold block.  An input stage in FRONT of the
+        # down-converter: ONE stream of integer samples is blanked at its own rate on the GPU (ft8rx_blank_in*) and handed to the
+        # front end on the device -- decode_stream (its own keyword overrides this one) and the wide live input.  Unlike noise_blanker
+        # the live search grid / waterfall of the channels show the blanked input.  input_blanker_stats: the cumulative int64 [4].
+        self.input_blanker = extension_knobs.pop("input_blanker", None)
+        _wide_in.input_blanker_params(self.input_blanker, 17, 1, 240000)      # a value outside the definition is refused here
+        self._input_blanker_stats = None
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall:
             _optins.refuse(_optins.RECALL, _optins.active(self.cfg))
@@ -685,7 +697,13 @@ class Receiver:
         """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
         if sample_rate is not None:
             self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
-                                           waterfall=waterfall)
+                                           waterfall=waterfall, input_blanker=self.input_blanker)
+
+    @property
+    def input_blanker_stats(self):
+        """int64 [4] of the input blanker: the live stream's cumulative counts, else the last decode_stream's; None while it is off"""
+        live = self.wide_in.input_blanker_stats() if self.wide_in is not None else None
+        return live if live is not None else self._input_blanker_stats
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
     def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False,
@@ -980,7 +998,11 @@ class Receiver:
         resample=True: the path is chosen by the rate -- a rate of ddc.RATES and a wide rate as above, any other rate that
         ddc_rat.accepts (44.1 kHz, 2.048 MS/s, 10 MS/s: ONE stream, any of the dtypes above) through the rational resampler
         (ft8rx_ddc_rat); a rate none of the three takes is refused, naming the rate.  Without it every rate
-        behaves and is refused as it always was."""
+        behaves and is refused as it always was.
+        input_blanker= (default: the receiver's; None / True / a threshold k / a dict of threshold, guard, taper, block): ONE stream
+        of integer samples is blanked at its own rate on the device (ft8rx_blank_in_host) and the front end
+        reads it there; more streams, or float / complex samples, are refused."""
+        input_blanker = kw.pop("input_blanker", self.input_blanker)
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
@@ -998,8 +1020,14 @@ class Receiver:
             if k not in args:
                 raise TypeError(f"decode_stream() got an unexpected keyword argument '{k}'")
         args.update(kw)
+        ib = _wide_in.input_blanker_params(input_blanker, kind, n_streams, int(sample_rate))
         with self._hlock:
-            _wide_in.HANDLE_CALLS[mod][0](self._handle(n_out), arr, kind, int(sample_rate), src, dials)
+            h = self._handle(n_out)
+            if ib is None:
+                _wide_in.HANDLE_CALLS[mod][0](h, arr, kind, int(sample_rate), src, dials)
+            else:
+                d_ptr, n, self._input_blanker_stats = h.blank_in(arr[0], kind, *ib)
+                _wide_in.HANDLE_CALLS[mod][3](h, d_ptr, n, kind, int(sample_rate), src, dials)
             return self._decode_frames_locked(None, n_out, bands=bands, **args)
 
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",

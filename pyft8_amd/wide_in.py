@@ -16,6 +16,7 @@ from . import _lib
 from . import ddc as _ddc
 from . import ddc_wide as _dw
 from . import ddc_rat as _dr
+from . import blank_in as _bi
 
 NSAMP = _lib.NSAMP
 HOP = 480                     # 12 kHz samples per hop of early_decode_hops
@@ -91,17 +92,35 @@ def _pre_stage(name):
     """The row of a pre-stage in HANDLE_CALLS: its Handle methods take ONE stream as [n(, 2)], and neither n_streams nor src"""
     return (lambda h, a, kind, rate, src, dials: getattr(h, name)(a[0], kind, rate, dials),
             lambda h, kind, rate, n_streams, src, dials: getattr(h, name + "_stream_open")(kind, rate, dials),
-            lambda h, a: getattr(h, name + "_stream_push")(a[0]))
+            lambda h, a: getattr(h, name + "_stream_push")(a[0]),
+            lambda h, d_ptr, n, kind, rate, src, dials: getattr(h, name)(None, kind, rate, dials, d_ptr=d_ptr, n=n),
+            lambda h, d_ptr, n: getattr(h, name + "_stream_push")(None, d_ptr=d_ptr, n=n))
 
 
 # module -> how the one-shot call (h, packed, kind, rate, src, dials), the stream open (h, kind, rate, n_streams, src, dials)
-# and the stream push (h, packed) reach the Handle; packed is what pack() returns, [n_streams][n(, 2)]
+# and the stream push (h, packed) reach the Handle; packed is what pack() returns, [n_streams][n(, 2)].  Behind the input blanker
+# (input_blanker=; DESIGN.md section 17.1) the one stream is on the device already: the one-shot call (h, d_ptr, n, kind, rate, src,
+# dials) and the push (h, d_ptr, n)
 HANDLE_CALLS = {
     _ddc: (lambda h, a, kind, rate, src, dials: h.ddc(a, kind, rate, src, dials),
            lambda h, kind, rate, n_streams, src, dials: h.ddc_stream_open(kind, rate, n_streams, src, dials),
-           lambda h, a: h.ddc_stream_push(a)),
+           lambda h, a: h.ddc_stream_push(a),
+           lambda h, d_ptr, n, kind, rate, src, dials: h.ddc(None, kind, rate, src, dials, d_ptr=d_ptr, n=n),
+           lambda h, d_ptr, n: h.ddc_stream_push(None, d_ptr=d_ptr, n=n)),
     _dw: _pre_stage("ddc_wide"),
     _dr: _pre_stage("ddc_rat")}
+
+
+def input_blanker_params(input_blanker, kind, n_streams, rate):
+    """input_blanker= of decode_stream / WideIn for a source of `kind` and n_streams -> None (off) or (block, threshold_q8, guard,
+    taper); more than one stream and float / complex samples are refused, naming the keyword and the reason"""
+    if input_blanker is None or input_blanker is False:
+        return None
+    if n_streams != 1:
+        raise _lib.Ft8rxError(f"input_blanker: {n_streams} streams -- the input blanker takes one stream")
+    if kind not in _bi.KINDS:
+        raise _lib.Ft8rxError("input_blanker: float / complex samples -- the input blanker takes the integer kinds only (int16, uint8, int8)")
+    return _bi.params(input_blanker, kind, rate)
 
 
 def _last_input(D):
@@ -204,7 +223,8 @@ class WideIn:
     waterfall_data[j]["data"] is a live view (the keys of AudioIn.waterfall_data).  The grid opens at the hop phase p0 = m_c mod 480
     of the scheduler's first cycle; cycle starts are 180000 = 375 x 480 outputs apart, so hop h of cycle c lands in grid row
     (375 (c mod 2) + h) mod 750 and is hop h of the very frame the complete pass decodes.  If a later cycle_start lands one sample
-    off through float rounding, the grid keeps its phase.  The grid shows the unblanked audio.  Off (the default) nothing of it exists.
+    off through float rounding, the grid keeps its phase.  The grid shows the audio before noise_blanker (section 17) but behind input_blanker (section 17.1),
+    which works in front of the down-converter: with it the rows are those of the blanked input.  Off (the default) nothing of it exists.
 
     push(chunk) takes the next samples in the forms of Receiver.decode_stream -- real int16 or float [n], complex [n] or int16 (I, Q)
     pairs [n, 2] with iq=True, several streams as [n_streams, n(, 2)] -- of any length, hands them to the down-converter on the
@@ -214,9 +234,15 @@ class WideIn:
     source_exhausted."""
 
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False,
-                 waterfall=False):
+                 waterfall=False, input_blanker=None):
         self._rx = receiver
         self.sample_rate = int(sample_rate)
+        # input_blanker (DESIGN.md section 17.1): the ONE stream's integer samples are blanked at their own rate on the device
+        # (ft8rx_blank_in_stream_*) and what that releases goes to the front end's device push; the kind decides at the first chunk
+        self.input_blanker = input_blanker
+        _bi.params(input_blanker, _bi.WIDE_IQ_I16, self.sample_rate)    # a value outside the definition is refused here
+        self._ib = None                                                 # (block, threshold_q8, guard, taper) once the stream is open
+        self._ib_done = False                                           # flush has finished it
         # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a resampled
         # rate sample_rate / 12000 is no integer, so input counts become output counts by exact integer arithmetic at every rate (_outputs)
         self.mod = front_end(self.sample_rate, resample)
@@ -269,7 +295,11 @@ class WideIn:
         self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
+            ib = input_blanker_params(self.input_blanker, self.kind, self.n_streams, self.sample_rate)
             self.f_mixed_hz = HANDLE_CALLS[self.mod][1](h, self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+            if ib is not None:
+                h.blank_in_stream_open(self.kind, *ib, n_origin=0, max_push=self.sample_rate)
+                self._ib = ib
             if self.waterfall:                   # the rows of every hop of the scheduler's cycles, behind whichever stream was opened
                 c0 = self.sched.cycle
                 self._grid_c0 = (c0, self.sched.cycle_start(c0))
@@ -282,7 +312,10 @@ class WideIn:
         rows the chunk completed are read once and written in place into search_grid"""
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
-            self.m_produced = HANDLE_CALLS[self.mod][2](h, a)
+            if self._ib is not None and real:
+                self._forward(h, h.blank_in_stream_push(a[0]), a[0][:1].nbytes)
+            else:
+                self.m_produced = HANDLE_CALLS[self.mod][2](h, a)
             if self.waterfall:
                 q_first, q_end = grid_rows_completed(0, self.m_produced, self.grid_phase)
                 q_first = max(q_first, self._grid_q)
@@ -296,6 +329,20 @@ class WideIn:
                     self._grid_q = q_end
         if real:
             self.n_pushed += a.shape[1]
+
+    def _forward(self, h, released, sample_bytes):
+        """What the input blanker released (d_out, n_first, n_out) to the front end's device push, a second at a time; nothing
+        released, nothing pushed"""
+        d_out, _, n_out = released
+        for at in range(0, n_out, self.sample_rate):
+            self.m_produced = HANDLE_CALLS[self.mod][4](h, d_out + at * sample_bytes, min(self.sample_rate, n_out - at))
+
+    def input_blanker_stats(self):
+        """The input blanker's cumulative int64 [4] (hits, samples with w < 32768, with w = 0, blocks with L_b = 0), or None"""
+        if self._ib is None:
+            return None
+        with self._rx._live_lock:
+            return self._rx._live_handle(self.n_channels).blank_in_stream_info()["stats"]
 
     def grid_cycle(self, odd_even):
         """The newest cycle of parity odd_even whose 375 rows are all in search_grid, or None"""
@@ -351,6 +398,12 @@ class WideIn:
         if self.sched is None:
             return
         m_real = self._outputs(self.n_pushed)
+        if self._ib is not None:                 # the blanker's stream ends here: what it still holds goes on, the zeros go past it
+            with self._rx._live_lock:
+                h = self._rx._live_handle(self.n_channels)
+                if not self._ib_done:
+                    self._ib_done = True
+                    self._forward(h, h.blank_in_stream_push(None, finish=True), np.zeros(1, self.mod._DTYPE[self.kind]).nbytes * (2 if self.mod.is_iq(self.kind) else 1))
         # a tile's worth of rest samples per stream, rounded up (1008 D at a multiple of 12 kHz); uint8 has no zero: 128 is half a step,
         # 128 counts of the int16 scale, above it
         dtype = self.mod._DTYPE[self.kind]
