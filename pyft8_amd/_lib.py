@@ -1000,8 +1000,8 @@ class Handle:
         a down-converter's d_ptr argument takes, valid until the next blank_in call.  d_ptr, n: samples on the device already, in
         place or into d_out -> (d_out or d_ptr, n, stats or None[, levels int32 [n_blocks, 2] = (m_b, L_b)]).  download: the blanked
         samples come back too, as the last element."""
-        from . import blank_in as _bi
-        q8 = int(threshold_q8) if threshold_q8 is not None else (1408 if _bi.is_iq(kind) else 2048)
+        from . import blank_in as _bi, kinds as _k
+        q8 = int(threshold_q8) if threshold_q8 is not None else int(256 * _bi.threshold_default(kind))
         stats = np.zeros(4, np.int64) if want_stats else None
         if d_ptr is None:
             a, n = _bi.pack(samples, kind)
@@ -1016,7 +1016,7 @@ class Handle:
             self._chk(self._L.ft8rx_blank_in(self._h, int(d_ptr), int(kind), n, int(block), q8, int(guard), int(taper), d_out or None,
                                              stats.ctypes.data if want_stats else None, lv.ctypes.data if want_levels else None), "ft8rx_blank_in")
             res = [int(d_out or d_ptr), n, stats] + ([lv] if want_levels else [])
-            shape, dt = ((n, 2) if _bi.is_iq(kind) else (n,)), _bi._DTYPE[kind]
+            shape, dt = _k.shape(kind, n), _k.DTYPE[kind]
         if download:
             y = np.empty(shape, dt)
             self.sync()
@@ -1028,7 +1028,7 @@ class Handle:
         """Open the handle's input blanker stream (one per handle, independent of the down-converter streams): everything is allocated
         here and released by blank_in_stream_close."""
         from . import blank_in as _bi
-        q8 = int(threshold_q8) if threshold_q8 is not None else (1408 if _bi.is_iq(kind) else 2048)
+        q8 = int(threshold_q8) if threshold_q8 is not None else int(256 * _bi.threshold_default(kind))
         self._chk(self._L.ft8rx_blank_in_stream_open(self._h, int(kind), int(block), q8, int(guard), int(taper), int(n_origin), int(max_push)),
                   "ft8rx_blank_in_stream_open")
         self._bis = int(kind)
@@ -1037,7 +1037,7 @@ class Handle:
         """Push the next samples (forms of blank_in.pack, 0 .. max_push; None = none; d_ptr, n: on the device already) -> (d_out,
         n_first, n_out): the raw device address, absolute index and count of the samples this push released, valid until the next
         push.  finish: the stream ends here and everything left is released.  download: -> (d_out, n_first, n_out, samples)."""
-        from . import blank_in as _bi
+        from . import blank_in as _bi, kinds as _k
         if getattr(self, "_bis", None) is None:
             raise Ft8rxError("blank_in_stream_push: no input blanker stream is open (blank_in_stream_open)")
         kind = self._bis
@@ -1054,7 +1054,7 @@ class Handle:
         res = (int(out.value or 0), int(first.value), int(cnt.value))
         if not download:
             return res
-        y = np.empty((res[2], 2) if _bi.is_iq(kind) else (res[2],), _bi._DTYPE[kind])
+        y = np.empty(_k.shape(kind, res[2]), _k.DTYPE[kind])
         if res[2]:
             self.sync()
             self._chk(self._L.ft8rx_copy_to_host(self._h, y.ctypes.data, res[0], y.nbytes), "ft8rx_copy_to_host")

@@ -14,25 +14,28 @@ integer arithmetic (int64 here, int32 on the device), so twin and kernels agree 
 import numpy as np
 
 from . import _lib, blanker
+from . import kinds as _k
+from .kinds import REAL_I16, IQ_I16, WIDE_REAL_I16, WIDE_IQ_I16, WIDE_IQ_U8, WIDE_IQ_I8, components, store  # noqa: F401 -- the integer kinds
 
-REAL_I16, IQ_I16 = 0, 2                                           # include/ft8rx.h FT8RX_DDC_*
-WIDE_REAL_I16, WIDE_IQ_I16, WIDE_IQ_U8, WIDE_IQ_I8 = 16, 17, 18, 19   # FT8RX_WIDE_*
-KINDS = (REAL_I16, IQ_I16, WIDE_REAL_I16, WIDE_IQ_I16, WIDE_IQ_U8, WIDE_IQ_I8)
-_DTYPE = {REAL_I16: np.int16, IQ_I16: np.int16, WIDE_REAL_I16: np.int16, WIDE_IQ_I16: np.int16, WIDE_IQ_U8: np.uint8, WIDE_IQ_I8: np.int8}
+KINDS, KIND_NAMES, _DTYPE = _k.view((REAL_I16, IQ_I16, WIDE_REAL_I16, WIDE_IQ_I16, WIDE_IQ_U8, WIDE_IQ_I8))
 BLOCK_DEFAULT, MIN_BLOCK, MAX_BLOCK = 1024, 256, 4096             # FT8RX_BLANK_IN_*
-THRESHOLD_DEFAULT_REAL, THRESHOLD_DEFAULT_IQ = 8.0, 5.5
+THRESHOLD_DEFAULT_REAL, THRESHOLD_DEFAULT_IQ = _k.BLANK_IN_THRESHOLD_REAL, _k.BLANK_IN_THRESHOLD_IQ
 GUARD_DEFAULT, TAPER_DEFAULT = 6, 6
 MEDIAN_REAL, MEDIAN_IQ = 0.6745, 1.4866                           # the median of |x| and of |I| + |Q| in sigma (Gaussian noise)
 
 
-def is_iq(kind):
+def _kind(kind):
     if kind not in KINDS:
         raise _lib.Ft8rxError(f"input blanker: kind={kind!r} is not an integer kind (real int16, IQ int16, IQ uint8, IQ int8)")
-    return kind not in (REAL_I16, WIDE_REAL_I16)
+    return kind
+
+
+def is_iq(kind):
+    return _k.is_iq(_kind(kind))
 
 
 def threshold_default(kind):
-    return THRESHOLD_DEFAULT_IQ if is_iq(kind) else THRESHOLD_DEFAULT_REAL
+    return _k.blank_in_threshold(_kind(kind))
 
 
 def false_hit_probability(k, iq):
@@ -56,10 +59,10 @@ def block_for_rate(sample_rate):
 def check(kind, block=BLOCK_DEFAULT, threshold=None, guard=GUARD_DEFAULT, taper=TAPER_DEFAULT):
     """-> (block, threshold_q8, guard, taper) as ft8rx_blank_in takes them; anything outside the definition is refused, naming the
     argument.  threshold None = the kind's default (k = 8 real, 5.5 IQ)."""
-    iq = is_iq(kind)
+    _kind(kind)
     if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or not MIN_BLOCK <= int(block) <= MAX_BLOCK or int(block) & (int(block) - 1):
         raise _lib.Ft8rxError(f"input blanker: block={block!r}: a power of two in [{MIN_BLOCK}, {MAX_BLOCK}]")
-    k = (THRESHOLD_DEFAULT_IQ if iq else THRESHOLD_DEFAULT_REAL) if threshold is None else threshold
+    k = threshold_default(kind) if threshold is None else threshold
     try:
         q8, g, r = blanker.check(k, guard, taper)
     except _lib.Ft8rxError as e:
@@ -93,30 +96,12 @@ def released(n_origin, n_end, block, guard, taper):
 
 def pack(samples, kind):
     """One stream's samples as the C-contiguous array ft8rx_blank_in takes -> (array, n): real int16 [n]; IQ (I, Q) pairs [n, 2]."""
-    iq = is_iq(kind)
+    _kind(kind)
     a = np.asarray(samples)
-    dt = _DTYPE[kind]
     if a.dtype.kind in "fc":
         raise _lib.Ft8rxError(f"input blanker: samples of dtype {a.dtype}: the blanker takes the integer kinds only (kind)")
-    if a.ndim != (2 if iq else 1) or (iq and a.shape[1] != 2):
-        raise _lib.Ft8rxError(f"input blanker: ONE stream, {'(I, Q) pairs [n, 2]' if iq else '[n]'}, got shape {a.shape}")
-    if a.dtype != dt:
-        info = np.iinfo(dt)
-        if not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < info.min or a.max() > info.max)):
-            raise _lib.Ft8rxError(f"input blanker: kind {kind} needs integers in the {np.dtype(dt).name} range, got dtype {a.dtype}")
-    a = np.ascontiguousarray(a, dt)
-    return a, a.shape[0]
-
-
-def components(a, kind):
-    """packed samples -> int64 component values c, [n] or [n, 2]"""
-    c = a.astype(np.int64)
-    return 2 * c - 255 if kind == WIDE_IQ_U8 else c
-
-
-def store(c, kind):
-    """component values -> the kind's bytes"""
-    return ((c + 255) >> 1).astype(np.uint8) if kind == WIDE_IQ_U8 else c.astype(_DTYPE[kind])
+    return _k.pack_stream(a, kind, "input blanker: ONE stream, {form}, got shape {shape}",
+                          "input blanker: kind {kind} needs integers in the {dtype} range, got dtype {got}")
 
 
 def magnitude(c):

@@ -43,6 +43,7 @@
 #include <vector>
 #include "../../include/ft8rx.h"
 #include "ft8_dev.h"
+#include "sample_fmt.hpp"
 
 #define WL_MULT(i) ((i) == WL_BP0 ? 5 : (i) == WL_OSDNAN ? 10 : 1)      /* entries per candidate slot of work list i */
 #define NF0MAX (FT8RX_MAX_F0 > 1024 ? 2048 : 1024)     /* per-frame stride of the per-f0 sync results; k_topk sorts this many keys */
@@ -60,6 +61,7 @@
 #include "kernels/ap_calls.hpp"
 #include "kernels/recall.hpp"
 #include "kernels/report.hpp"
+#include "kernels/sample.hpp"
 #include "kernels/ddc.hpp"
 #include "kernels/ddc_wide.hpp"
 #include "kernels/ddc_rat.hpp"
@@ -147,13 +149,13 @@ static ApCalls ap_calls_off() { ApCalls a; memset(&a, 0, sizeof(a)); a.max_hd = 
 enum { PRE_WIDE = 0, PRE_RAT = 1 };
 static const char* const PRE_NAME[2] = {"wide", "rational"};                       // in messages
 static const char* const PRE_ENTRY[2] = {"ft8rx_ddc_wide", "ft8rx_ddc_rat"};
+static const uint32_t PRE_KINDS[2] = {SF_KINDS_WIDE, SF_KINDS_RAT};                 // the kinds each takes (sample_fmt.hpp)
 struct PreStage {
     int which = PRE_WIDE;
     int32_t rate = 0, rate_mid = 0;              // rate_mid = 0: the rate is refused
     int L = 1, M = 1, n_taps = 0;
     int P = 0, H = 0, tk = 0; bool lane = false; // taps per phase (rational), history of a stream, outputs per tile, the rational kernel's regime
     const std::vector<float>* taps = nullptr;    // the prototype (pre_taps); nullptr: the rate is refused
-    uint32_t kinds = 0;                          // bit k: input kind k is taken
     int64_t n_max = 0, end_max = 0;              // bound of an origin, and of the index a stream may reach
     const char *name = "", *entry = "";          // PRE_NAME, PRE_ENTRY of `which`
 };
@@ -227,13 +229,13 @@ struct ft8rx_handle {
     // (h_ddc_outs: its page-locked source; ddc_ev: behind the copy of the last call's table, so that the next call can rewrite it)
     DdcOut* d_ddc_outs = nullptr; DdcOut* h_ddc_outs = nullptr; hipEvent_t ddc_ev = nullptr; void* d_ddc_in = nullptr; size_t ddc_in_cap = 0;
     // streaming down-converter (ft8rx_ddc_stream_*): everything is allocated by open and released by close (or
-    // destroy); it shares nothing but the tap tables with the one-shot above.  d_in: [n_streams][cap] samples of `kind`, the newest cap
+    // destroy); it shares nothing but the tap tables with the one-shot above.  d_in: [n_streams][cap] samples of `fmt`, the newest cap
     // of each stream; d_out / d_f32: [n_out][OUT_RING]; h_stage: page-locked, one second of every stream; ev: behind the last copy out
     // of h_stage.  n_origin, pushed, tiles: absolute index of the first sample, samples pushed, first tile not produced yet.
     // The spectrogram stage behind it (ft8rx_ddc_stream_grid_*, section 16.5; nothing of it exists until grid_open): d_grid
     // [n_out][g_rows][FT8RX_GRID_COLS], row q at q mod g_rows; g_p0: the hop phase.
     struct DdcStream {
-        bool open = false; int kind = 0, D = 0, n_streams = 0, n_out = 0; int32_t rate = 0; float scale = 0.0f;
+        bool open = false; int fmt = 0, D = 0, n_streams = 0, n_out = 0; int32_t rate = 0; float scale = 0.0f;
         int64_t n_origin = 0, pushed = 0, tiles = 0, cap = 0;
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
         float* d_grid = nullptr; int g_p0 = 0, g_rows = 0;
@@ -245,12 +247,12 @@ struct ft8rx_handle {
     void* d_pre_tab = nullptr; size_t pre_tab_cap = 0; void* d_pre_w0 = nullptr; size_t pre_w0_cap = 0;
     void* d_pre_mid = nullptr; size_t pre_mid_cap = 0;
     // ... and their stream, at most one of either stage: everything is allocated by open and released by close (or destroy).  st: the
-    // stage of the open stream; d_hist: the newest st.H input samples in their own kind (sample n at (n - n_origin) mod H); d_chunk /
+    // stage of the open stream; d_hist: the newest st.H input samples in their own format `fmt` (sample n at (n - n_origin) mod H); d_chunk /
     // h_stage: one second of input, device / page-locked; d_mid: [n_out][rate_mid], what one push makes; the down-converter behind it
     // is the stream `ds` above, fed on the device.  n_origin, pushed, k_done: absolute index of the first sample, samples pushed, first
     // intermediate sample not made yet.
     struct PreStream {
-        bool open = false; PreStage st; int kind = 0, n_out = 0; float g0 = 0.0f;
+        bool open = false; PreStage st; int fmt = 0, n_out = 0;
         int64_t n_origin = 0, pushed = 0, k_done = 0;
         char* d_hist = nullptr; char* d_chunk = nullptr; char* h_stage = nullptr; float2* d_mid = nullptr; float2* d_tab = nullptr;
         uint32_t* d_w0 = nullptr;
@@ -272,7 +274,7 @@ struct ft8rx_handle {
     } bi;
     char* d_bi_buf = nullptr; size_t bi_buf_cap = 0; int32_t* d_bi_taper = nullptr;
     struct BlankInStream {
-        bool open = false, finished = false; int kind = 0, fmt = 0, log2_b = 0, guard = 0, taper = 0, cur = 0; int32_t threshold_q8 = 0;
+        bool open = false, finished = false; int fmt = 0, log2_b = 0, guard = 0, taper = 0, cur = 0; int32_t threshold_q8 = 0;
         int64_t n_origin = 0, pushed = 0, max_push = 0, base = 0;
         char* d_work[2] = {nullptr, nullptr}; char* h_stage = nullptr;
         BlankInWs ws;
@@ -1429,12 +1431,10 @@ static int ddc_workspaces(ft8rx_handle* h) {
     return F.done();
 }
 
-static const size_t DDC_SAMPLE_BYTES[4] = {2, 4, 4, 8};     // FT8RX_DDC_REAL_I16, _REAL_F32, _IQ_I16, _IQ_F32
-
 // the argument checks both entries share (everything but the input pointer) -> D, or -1 with the error text
 static int ddc_check(ft8rx_handle* h, const char* who, int kind, int32_t rate_hz, int n_streams, uint64_t stream_stride, uint64_t n_samples,
                      int n_out, const int32_t* src, const double* f_dial_hz, float gain) {
-    if (kind < 0 || kind > 3) { set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32", who, kind); return -1; }
+    if (!sf_kind_in(SF_KINDS_DDC, kind)) { set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32", who, kind); return -1; }
     const int D = ddc_decimation(rate_hz);
     if (!D) { set_err(h, "%s: rate_hz %d is not 12000 x 1, 2, 4, 8 or 16", who, (int)rate_hz); return -1; }
     if (kind == FT8RX_DDC_REAL_I16 && D == 1) { set_err(h, "%s: kind real int16 at rate_hz 12000 is a frame already", who); return -1; }
@@ -1469,7 +1469,7 @@ static void ddc_table(DdcOut* outs, int32_t rate_hz, int n_out, const int32_t* s
 
 // the launch: channel table (sorted by stream, so that outputs of one stream run next to each other and share its loads in L2) -> device,
 // one kernel on the main stream
-static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_t rate_hz, uint64_t stream_stride, uint64_t n_samples, int n_out,
+static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int fmt, int32_t rate_hz, uint64_t stream_stride, uint64_t n_samples, int n_out,
                       const int32_t* src, const double* f_dial_hz, float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
     if (!h->ddc_ev) HIPCHK(h, hipEventCreateWithFlags(&h->ddc_ev, hipEventDisableTiming));
     else HIPCHK(h, hipEventSynchronize(h->ddc_ev));      // the previous call's table has left the page-locked buffer (long ago, as a rule)
@@ -1477,10 +1477,10 @@ static int ddc_launch(ft8rx_handle* h, int D, const void* d_in, int kind, int32_
     ddc_table(outs, rate_hz, n_out, src, f_dial_hz, f_mixed_hz);
     HIPCHK(h, hipMemcpyAsync(h->d_ddc_outs, outs, sizeof(DdcOut) * (size_t)n_out, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(h->ddc_ev, h->stream));
-    const float scale = gain * (kind == FT8RX_DDC_IQ_I16 || kind == FT8RX_DDC_IQ_F32 ? 1.0f : 2.0f);
+    const float scale = gain * sf_real_gain(fmt);
     const unsigned grid = (unsigned)n_out * DDC_TILES;
     const unsigned long long ss = stream_stride; const int ns = (int)n_samples;
-#define DDC_GO(DD) k_ddc<DD><<<grid, DDC_NT, 0, h->stream>>>(d_in, kind, ss, ns, h->d_ddc_outs, scale, d_audio, d_audio_f32)
+#define DDC_GO(DD) k_ddc<DD><<<grid, DDC_NT, 0, h->stream>>>(d_in, fmt, ss, ns, h->d_ddc_outs, scale, d_audio, d_audio_f32)
     switch (D) { case 1: DDC_GO(1); break; case 2: DDC_GO(2); break; case 4: DDC_GO(4); break; case 8: DDC_GO(8); break; default: DDC_GO(16); }
 #undef DDC_GO
     HIPCHK(h, hipGetLastError());
@@ -1492,11 +1492,12 @@ int ft8rx_ddc(ft8rx_handle* h, const void* d_in, int kind, int32_t rate_hz, int 
     if (!h) return -1;
     const int D = ddc_check(h, "ft8rx_ddc", kind, rate_hz, n_streams, stream_stride, n_samples, n_out, src, f_dial_hz, gain);
     if (D < 0) return -1;
-    if (!d_in || ((uintptr_t)d_in % DDC_SAMPLE_BYTES[kind]) != 0) { set_err(h, "ft8rx_ddc: d_in is NULL or not aligned to a sample"); return -1; }
+    const int fmt = sample_fmt(kind);
+    if (!d_in || ((uintptr_t)d_in % sf_sample_bytes(fmt)) != 0) { set_err(h, "ft8rx_ddc: d_in is NULL or not aligned to a sample"); return -1; }
     ENTER(h);
     if (ddc_workspaces(h)) return -2;
     if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
-    return ddc_launch(h, D, d_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+    return ddc_launch(h, D, d_in, fmt, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
 }
 
 // hand one allocation of the handle back (ft8rx_ddc_stream_close; everything else lives until ft8rx_destroy)
@@ -1530,10 +1531,11 @@ int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, i
     if (!in) { set_err(h, "ft8rx_ddc_host: in is NULL"); return -1; }
     ENTER(h);
     if (ddc_workspaces(h) || need_staging(h)) return -2;
-    const size_t bytes = (size_t)n_streams * (size_t)stream_stride * DDC_SAMPLE_BYTES[kind];
+    const int fmt = sample_fmt(kind);
+    const size_t bytes = (size_t)n_streams * (size_t)stream_stride * sf_sample_bytes(fmt);
     if (grow_dev(h, "ft8rx_ddc_host", &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;
     if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = ddc_launch(h, D, h->d_ddc_in, kind, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    if (const int rc = ddc_launch(h, D, h->d_ddc_in, fmt, rate_hz, stream_stride, n_samples, n_out, src, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -1583,7 +1585,8 @@ static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_str
     if (ddc_workspaces(h)) return -2;
     ft8rx_handle::DdcStream& s = h->ds;
     if (!s.ev) HIPCHK(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    const size_t sb = DDC_SAMPLE_BYTES[kind], cap = (size_t)ddcring::in_capacity(D);
+    const int fmt = sample_fmt(kind);
+    const size_t sb = sf_sample_bytes(fmt), cap = (size_t)ddcring::in_capacity(D);
     char* d_in = nullptr;
     int rc = dalloc(h, &d_in, (size_t)n_streams * cap * sb);
     s.d_in = d_in;
@@ -1599,8 +1602,8 @@ static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_str
     if (e == hipSuccess && s.d_f32) e = hipMemsetAsync(s.d_f32, 0, sizeof(float) * (size_t)n_out * ddcring::OUT_RING, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // the table is a pageable vector of this call
     if (e != hipSuccess) { set_err(h, "ft8rx_ddc_stream_open: %s", hipGetErrorString(e)); ddc_stream_release(h); return -2; }
-    s.kind = kind; s.D = D; s.rate = rate_hz; s.n_streams = n_streams; s.n_out = n_out; s.cap = (int64_t)cap;
-    s.scale = gain * (kind == FT8RX_DDC_IQ_I16 || kind == FT8RX_DDC_IQ_F32 ? 1.0f : 2.0f);
+    s.fmt = fmt; s.D = D; s.rate = rate_hz; s.n_streams = n_streams; s.n_out = n_out; s.cap = (int64_t)cap;
+    s.scale = gain * sf_real_gain(fmt);
     s.n_origin = (int64_t)n_origin; s.pushed = 0; s.tiles = s.n_origin / (DDC_TO * D);
     s.open = true;
     return 0;
@@ -1615,7 +1618,7 @@ static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
     ft8rx_handle::DdcStream& s = h->ds;
     if (!s.open) { set_err(h, "ft8rx_ddc_stream_push: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
     if (n_new < 1 || n_new > (uint64_t)s.rate) { set_err(h, "ft8rx_ddc_stream_push: n_new %llu outside [1, %d] (one second)", (unsigned long long)n_new, (int)s.rate); return -1; }
-    const size_t sb = DDC_SAMPLE_BYTES[s.kind];
+    const size_t sb = sf_sample_bytes(s.fmt);
     if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "ft8rx_ddc_stream_push: in is NULL or not aligned to a sample"); return -1; }
     // (no ENTER: a push touches the stream's own rings only, on the main stream; batches in flight read neither)
     HIPCHK(h, hipSetDevice(h->device));
@@ -1639,7 +1642,7 @@ static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
     const int n_tiles = (int)(done - s.tiles);           // at most 12000 / 1008 + 1
     if (n_tiles > 0) {
         const unsigned grid = (unsigned)s.n_out * (unsigned)n_tiles;
-#define DDC_GO(DD) k_ddc_stream<DD><<<grid, DDC_NT, 0, h->stream>>>(s.d_in, s.kind, (unsigned long long)s.cap, (long long)s.n_origin, (long long)n_end, \
+#define DDC_GO(DD) k_ddc_stream<DD><<<grid, DDC_NT, 0, h->stream>>>(s.d_in, s.fmt, (unsigned long long)s.cap, (long long)s.n_origin, (long long)n_end, \
                                                                    s.d_outs, (long long)s.tiles, n_tiles, s.scale, (int)ddcring::OUT_RING, s.d_out, s.d_f32)
         switch (s.D) { case 1: DDC_GO(1); break; case 2: DDC_GO(2); break; case 4: DDC_GO(4); break; case 8: DDC_GO(8); break; default: DDC_GO(16); }
 #undef DDC_GO
@@ -1818,11 +1821,6 @@ constexpr bool ddr_tiles_fit() {
 }
 static_assert(ddr_tiles_fit(), "ddc_rat_ring.hpp: a tile's input fits the LDS image");
 
-// bytes of one sample of any kind a pre-stage takes (FT8RX_DDC_*: 0 .. 3, FT8RX_WIDE_*: 16 .. 19), and whether it is an (I, Q) pair
-static size_t pre_sample_bytes(int kind) { return kind <= FT8RX_DDC_IQ_F32 ? DDC_SAMPLE_BYTES[kind] : kind == FT8RX_WIDE_IQ_I16 ? 4 : 2; }
-static bool pre_is_iq(int kind) { return kind != FT8RX_DDC_REAL_I16 && kind != FT8RX_DDC_REAL_F32 && kind != FT8RX_WIDE_REAL_I16; }
-constexpr uint32_t pre_kinds(int lo, int hi) { return ((2u << hi) - 1u) & ~((1u << lo) - 1u); }
-
 // The prototype of a rate, designed once per (stage, rate) by the recipe of ddc_design at 85 dB, pass 3200 Hz.
 //   wide      h0 at fs = rate, stop rate_mid - 3200 Hz
 //   rational  h at fs = rate L, stop min(rate, rate_mid) - 3200 Hz, sum h = L; its length is worked out before it is made
@@ -1854,8 +1852,6 @@ static PreStage pre_plan(int which, int32_t rate_hz) {
     PreStage d;
     d.which = which; d.rate = rate_hz;
     d.name = PRE_NAME[which]; d.entry = PRE_ENTRY[which];
-    d.kinds = which == PRE_WIDE ? pre_kinds(FT8RX_WIDE_REAL_I16, FT8RX_WIDE_IQ_I8)
-                                : pre_kinds(FT8RX_DDC_REAL_I16, FT8RX_DDC_IQ_F32) | pre_kinds(FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8);
     d.taps = pre_taps(which, rate_hz);
     if (!d.taps) return d;
     d.n_taps = (int)d.taps->size();
@@ -1904,7 +1900,7 @@ int ft8rx_ddc_rat_taps(int32_t rate_hz, float* taps, int cap) { return pre_taps_
 // the argument checks every entry shares -> 0 and the stage in d, or -1 with the error text
 static int pre_check(ft8rx_handle* h, const char* who, int which, PreStage& d, int kind, int32_t rate_hz, int n_out, const double* f_dial_hz, float gain) {
     d = pre_plan(which, rate_hz);
-    if (kind < 0 || kind > 31 || !(d.kinds >> kind & 1u)) {
+    if (!sf_kind_in(PRE_KINDS[which], kind)) {
         if (which == PRE_WIDE) set_err(h, "%s: kind %d is not one of FT8RX_WIDE_REAL_I16 .. FT8RX_WIDE_IQ_I8", who, kind);
         else set_err(h, "%s: kind %d is not one of FT8RX_DDC_REAL_I16 .. FT8RX_DDC_IQ_F32, FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8", who, kind);
         return -1;
@@ -1970,16 +1966,16 @@ static void pre_mixed(int32_t rate_hz, int n_out, const std::vector<double>& f0s
 }
 
 // The two launches (with_bool: a run-time bool as a template argument).
-// One call: in = n_samples samples of `kind` -> mid [n_out][n_mid]
-static void pre_launch(ft8rx_handle* h, const PreStage& d, const void* d_in, int kind, long long n_samples, const float2* tab, const uint32_t* w0s,
+// One call: in = n_samples samples of format `fmt` -> mid [n_out][n_mid]
+static void pre_launch(ft8rx_handle* h, const PreStage& d, const void* d_in, int fmt, long long n_samples, const float2* tab, const uint32_t* w0s,
                        int n_out, long long n_mid, float2* mid) {
     const dim3 grid((unsigned)((n_mid + d.tk - 1) / d.tk), (unsigned)n_out);
-    const float g0 = pre_is_iq(kind) ? 1.0f : 2.0f;
-    with_bool(pre_is_iq(kind), [&](auto iq) {
+    const float g0 = sf_real_gain(fmt);
+    with_bool(sf_is_iq(fmt), [&](auto iq) {
         constexpr bool IQ = decltype(iq)::value;
-        if (d.which == PRE_WIDE) k_ddc_pre<IQ><<<grid, DDW_NT, 0, h->stream>>>(d_in, kind, n_samples, tab, w0s, d.n_taps, d.M, d.tk, g0, n_mid, mid);
+        if (d.which == PRE_WIDE) k_ddc_pre<IQ><<<grid, DDW_NT, 0, h->stream>>>(d_in, fmt, n_samples, tab, w0s, d.n_taps, d.M, d.tk, g0, n_mid, mid);
         else with_bool(d.lane, [&](auto lane) {
-            k_ddc_rat<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(d_in, kind, n_samples, tab, w0s, (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, g0, n_mid, mid);
+            k_ddc_rat<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(d_in, fmt, n_samples, tab, w0s, (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, g0, n_mid, mid);
         });
     });
 }
@@ -1989,20 +1985,21 @@ static void pre_launch_stream(ft8rx_handle* h, const ft8rx_handle::PreStream& s,
     const dim3 grid((unsigned)((n_k + d.tk - 1) / d.tk), (unsigned)s.n_out);
     const int p_last = s.pushed ? (int)ddcpre::hist_pos(n_start - 1, s.n_origin, d.H) : 0;
     const long long n_origin = s.n_origin, k_first = s.k_done;
-    with_bool(pre_is_iq(s.kind), [&](auto iq) {
+    const float g0 = sf_real_gain(s.fmt);
+    with_bool(sf_is_iq(s.fmt), [&](auto iq) {
         constexpr bool IQ = decltype(iq)::value;
         if (d.which == PRE_WIDE)
-            k_ddc_pre_stream<IQ><<<grid, DDW_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.kind, n_origin, n_start, n_end, s.d_tab, s.d_w0, d.n_taps, d.M, d.tk,
-                                                                 s.g0, k_first, n_k, s.d_mid);
+            k_ddc_pre_stream<IQ><<<grid, DDW_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.fmt, n_origin, n_start, n_end, s.d_tab, s.d_w0, d.n_taps, d.M, d.tk,
+                                                                 g0, k_first, n_k, s.d_mid);
         else with_bool(d.lane, [&](auto lane) {
-            k_ddc_rat_stream<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.kind, n_origin, n_start, n_end, s.d_tab, s.d_w0,
-                                                                                       (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, s.g0, k_first, n_k, s.d_mid);
+            k_ddc_rat_stream<IQ, decltype(lane)::value><<<grid, DDR_NT, 0, h->stream>>>(s.d_hist, d.H, p_last, chunk, s.fmt, n_origin, n_start, n_end, s.d_tab, s.d_w0,
+                                                                                       (d.n_taps - 1) / 2, d.L, d.M, d.P, d.tk, g0, k_first, n_k, s.d_mid);
         });
     });
 }
 
 // the one-shot behind its checks: the pre-stage into the handle's intermediate buffer, then k_ddc<D> on it with one stream per output
-static int pre_run(ft8rx_handle* h, const char* who, const PreStage& d, const void* d_in, int kind, uint64_t n_samples, int n_out, const double* f_dial_hz,
+static int pre_run(ft8rx_handle* h, const char* who, const PreStage& d, const void* d_in, int fmt, uint64_t n_samples, int n_out, const double* f_dial_hz,
                    float gain, int16_t* d_audio, float* d_audio_f32, double* f_mixed_hz) {
     const int D = d.rate_mid / 12000;
     const int64_t n_mid = ddcpre::mid_count((int64_t)n_samples, d.n_taps, d.L, d.M, (int64_t)FT8RX_NSAMP * D);
@@ -2016,11 +2013,11 @@ static int pre_run(ft8rx_handle* h, const char* who, const PreStage& d, const vo
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(h->d_pre_tab, t.tab.data(), sizeof(float2) * t.tab.size(), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_pre_w0, t.w0s.data(), sizeof(uint32_t) * t.w0s.size(), hipMemcpyHostToDevice));
-    pre_launch(h, d, d_in, kind, (long long)n_samples, (const float2*)h->d_pre_tab, (const uint32_t*)h->d_pre_w0, n_out, (long long)n_mid, (float2*)h->d_pre_mid);
+    pre_launch(h, d, d_in, fmt, (long long)n_samples, (const float2*)h->d_pre_tab, (const uint32_t*)h->d_pre_w0, n_out, (long long)n_mid, (float2*)h->d_pre_mid);
     HIPCHK(h, hipGetLastError());
     std::vector<int32_t> src((size_t)n_out);
     for (int j = 0; j < n_out; j++) src[j] = j;
-    if (const int rc = ddc_launch(h, D, h->d_pre_mid, FT8RX_DDC_IQ_F32, d.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), t.dial_mid.data(),
+    if (const int rc = ddc_launch(h, D, h->d_pre_mid, SF_IQ_F32, d.rate_mid, (uint64_t)n_mid, (uint64_t)n_mid, n_out, src.data(), t.dial_mid.data(),
                                   gain, d_audio, d_audio_f32, fm.data())) return rc;
     if (f_mixed_hz) { for (int j = 0; j < n_out; j++) f_mixed_hz[j] = fm[j]; pre_mixed(d.rate, n_out, t.f0s, f_mixed_hz); }
     return 0;
@@ -2039,11 +2036,12 @@ static int pre_oneshot(ft8rx_handle* h, const char* who, int which, const void* 
     if (!h) return -1;
     PreStage d;
     if (pre_check_oneshot(h, who, which, d, kind, rate_hz, n_samples, n_out, f_dial_hz, gain)) return -1;
-    if (!d_in || ((uintptr_t)d_in % pre_sample_bytes(kind)) != 0) { set_err(h, "%s: d_in is NULL or not aligned to a sample", who); return -1; }
+    const int fmt = sample_fmt(kind);
+    if (!d_in || ((uintptr_t)d_in % sf_sample_bytes(fmt)) != 0) { set_err(h, "%s: d_in is NULL or not aligned to a sample", who); return -1; }
     ENTER(h);
     if (ddc_workspaces(h)) return -2;
     if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
-    return pre_run(h, who, d, d_in, kind, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
+    return pre_run(h, who, d, d_in, fmt, n_samples, n_out, f_dial_hz, gain, d_audio, d_audio_f32, f_mixed_hz);
 }
 static int pre_oneshot_host(ft8rx_handle* h, const char* who, int which, const void* in, int kind, int32_t rate_hz, uint64_t n_samples, int n_out,
                             const double* f_dial_hz, float gain, double* f_mixed_hz) {
@@ -2053,10 +2051,11 @@ static int pre_oneshot_host(ft8rx_handle* h, const char* who, int which, const v
     if (!in) { set_err(h, "%s: in is NULL", who); return -1; }
     ENTER(h);
     if (ddc_workspaces(h) || need_staging(h)) return -2;
-    const size_t bytes = (size_t)n_samples * pre_sample_bytes(kind);
+    const int fmt = sample_fmt(kind);
+    const size_t bytes = (size_t)n_samples * sf_sample_bytes(fmt);
     if (grow_dev(h, who, &h->d_ddc_in, &h->ddc_in_cap, bytes)) return -2;      // the input staging of ft8rx_ddc_host
     if (bytes) HIPCHK(h, hipMemcpyAsync(h->d_ddc_in, in, bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = pre_run(h, who, d, h->d_ddc_in, kind, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
+    if (const int rc = pre_run(h, who, d, h->d_ddc_in, fmt, n_samples, n_out, f_dial_hz, gain, h->d_audio, nullptr, f_mixed_hz)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2118,7 +2117,8 @@ static int pre_stream_open(ft8rx_handle* h, const char* who, int which, int kind
     if (const int rc = ddc_stream_open(h, FT8RX_DDC_IQ_F32, d.rate_mid, n_out, n_out, src.data(), t.dial_mid.data(), gain, (uint64_t)k_origin, keep_f32,
                                        f_mixed_hz)) return rc;
     ft8rx_handle::PreStream& s = h->ps;
-    const size_t sb = pre_sample_bytes(kind);
+    const int fmt = sample_fmt(kind);
+    const size_t sb = sf_sample_bytes(fmt);
     int rc = 0;
     hipError_t e = hipSuccess;
     if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
@@ -2138,8 +2138,7 @@ static int pre_stream_open(ft8rx_handle* h, const char* who, int which, int kind
     }
     if (rc) { pre_stream_release(h); ddc_stream_release(h); return -2; }
     pre_mixed(rate_hz, n_out, t.f0s, f_mixed_hz);
-    s.st = d; s.kind = kind; s.n_out = n_out;
-    s.g0 = pre_is_iq(kind) ? 1.0f : 2.0f;
+    s.st = d; s.fmt = fmt; s.n_out = n_out;
     s.n_origin = (int64_t)n_origin; s.pushed = 0; s.k_done = k_origin;
     s.open = true;
     return 0;
@@ -2160,7 +2159,7 @@ static int pre_stream_push(ft8rx_handle* h, const char* who, int which, const vo
     ft8rx_handle::PreStream& s = *ps;
     const PreStage& d = s.st;
     if (n_new < 1 || n_new > (uint64_t)d.rate) { set_err(h, "%s: n_new %llu outside [1, %d] (one second)", who, (unsigned long long)n_new, (int)d.rate); return -1; }
-    const size_t sb = pre_sample_bytes(s.kind);
+    const size_t sb = sf_sample_bytes(s.fmt);
     if (!in || (on_device && ((uintptr_t)in % sb) != 0)) { set_err(h, "%s: in is NULL or not aligned to a sample", who); return -1; }
     if (s.n_origin + s.pushed + (int64_t)n_new > d.end_max) { set_err(h, "%s: n_new %llu takes the stream past index 2^53", who, (unsigned long long)n_new); return -1; }
     // (no ENTER: a push touches the streams' own buffers only, on the main stream; batches in flight read none of them)
@@ -2335,16 +2334,6 @@ int ft8rx_blank_host(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_
 }
 
 // ---- input-rate noise blanker (kernels/blank_in.hpp; the index arithmetic is blank_in_ring.hpp's)
-static int blank_in_fmt(int kind) {
-    switch (kind) {
-        case FT8RX_DDC_REAL_I16: case FT8RX_WIDE_REAL_I16: return BIN_REAL_I16;
-        case FT8RX_DDC_IQ_I16: case FT8RX_WIDE_IQ_I16: return BIN_IQ_I16;
-        case FT8RX_WIDE_IQ_U8: return BIN_IQ_U8;
-        case FT8RX_WIDE_IQ_I8: return BIN_IQ_I8;
-        default: return -1;
-    }
-}
-static size_t blank_in_sample_bytes(int fmt) { return fmt == BIN_REAL_I16 ? 2 : fmt == BIN_IQ_I16 ? 4 : 2; }
 static int blank_in_log2(int block) {
     for (int k = 8; k <= 12; k++) if (block == (1 << k)) return k;
     return -1;
@@ -2353,7 +2342,7 @@ static int blank_in_log2(int block) {
 static const char* blank_in_refusal(int kind, bool with_kind, int block, int32_t threshold_q8, int guard, int taper, char* err, size_t cap) {
     static_assert(FT8RX_BLANK_IN_MIN_BLOCK == 256 && FT8RX_BLANK_IN_MAX_BLOCK == 4096 && BIN_HALO == FT8RX_BLANK_MAX_GUARD + FT8RX_BLANK_MAX_TAPER &&
                   BIN_TAPER_ROW == FT8RX_BLANK_MAX_TAPER + 1 && FT8RX_BLANK_IN_MAX_BLOCK <= 16 * BIN_NT, "input blanker geometry");
-    if (with_kind && blank_in_fmt(kind) < 0) snprintf(err, cap, "kind %d is not an integer kind (real int16, IQ int16, IQ uint8, IQ int8)", kind);
+    if (with_kind && !sf_kind_in(SF_KINDS_BLANK_IN, kind)) snprintf(err, cap, "kind %d is not an integer kind (real int16, IQ int16, IQ uint8, IQ int8)", kind);
     else if (blank_in_log2(block) < 0) snprintf(err, cap, "block %d is not a power of two in [%d, %d]", block, FT8RX_BLANK_IN_MIN_BLOCK, FT8RX_BLANK_IN_MAX_BLOCK);
     else if (threshold_q8 < FT8RX_BLANK_MIN_THRESHOLD_Q8 || threshold_q8 > FT8RX_BLANK_MAX_THRESHOLD_Q8)
         snprintf(err, cap, "threshold_q8 %d outside [%d, %d] (256 k, k = 2 .. 64)", (int)threshold_q8, FT8RX_BLANK_MIN_THRESHOLD_Q8, FT8RX_BLANK_MAX_THRESHOLD_Q8);
@@ -2362,9 +2351,10 @@ static const char* blank_in_refusal(int kind, bool with_kind, int block, int32_t
     else return nullptr;
     return err;
 }
+// the argument checks of an entry -> the format of its kind, or -1 with the error text
 static int blank_in_check(ft8rx_handle* h, const char* who, int kind, int block, int32_t threshold_q8, int guard, int taper) {
     char text[200];
-    if (!blank_in_refusal(kind, true, block, threshold_q8, guard, taper, text, sizeof(text))) return 0;
+    if (!blank_in_refusal(kind, true, block, threshold_q8, guard, taper, text, sizeof(text))) return sample_fmt(kind);
     set_err(h, "%s: %s", who, text);
     return -1;
 }
@@ -2438,10 +2428,10 @@ static int blank_in_launch(ft8rx_handle* h, ft8rx_handle::BlankInWs& w, int fmt,
     };
     with_bool(vec, [&](auto v) {
         switch (fmt) {
-            case BIN_REAL_I16: run(std::integral_constant<int, BIN_REAL_I16>(), v); break;
-            case BIN_IQ_I16: run(std::integral_constant<int, BIN_IQ_I16>(), v); break;
-            case BIN_IQ_U8: run(std::integral_constant<int, BIN_IQ_U8>(), v); break;
-            default: run(std::integral_constant<int, BIN_IQ_I8>(), v); break;
+            case SF_REAL_I16: run(std::integral_constant<int, SF_REAL_I16>(), v); break;
+            case SF_IQ_I16: run(std::integral_constant<int, SF_IQ_I16>(), v); break;
+            case SF_IQ_U8: run(std::integral_constant<int, SF_IQ_U8>(), v); break;
+            default: run(std::integral_constant<int, SF_IQ_I8>(), v); break;
         }
     });
     if (n_h > 0 || n_g > 0) k_blankin_stats<<<1, BIN_NT, 0, h->stream>>>(w.d_part_h, (int)n_h, w.d_part_g, (int)n_g, w.d_stats);
@@ -2471,9 +2461,9 @@ static int blank_in_n_check(ft8rx_handle* h, const char* who, uint64_t n_samples
 int ft8rx_blank_in(ft8rx_handle* h, void* d_samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper, void* d_out,
                    int64_t* stats, int32_t* levels) {
     if (!h) return -1;
-    if (blank_in_check(h, "ft8rx_blank_in", kind, block, threshold_q8, guard, taper) || blank_in_n_check(h, "ft8rx_blank_in", n_samples)) return -1;
-    const int fmt = blank_in_fmt(kind);
-    const size_t sb = blank_in_sample_bytes(fmt), align = fmt == BIN_IQ_U8 || fmt == BIN_IQ_I8 ? 1 : 2;
+    const int fmt = blank_in_check(h, "ft8rx_blank_in", kind, block, threshold_q8, guard, taper);
+    if (fmt < 0 || blank_in_n_check(h, "ft8rx_blank_in", n_samples)) return -1;
+    const size_t sb = sf_sample_bytes(fmt), align = sf_component_bytes(fmt);      // (the messages' "sample": a component is enough)
     if (!d_samples || ((uintptr_t)d_samples % align) != 0) { set_err(h, "ft8rx_blank_in: d_samples is NULL or not aligned to a sample"); return -1; }
     if (((uintptr_t)d_out % align) != 0) { set_err(h, "ft8rx_blank_in: d_out is not aligned to a sample"); return -1; }
     ENTER(h);
@@ -2484,10 +2474,10 @@ int ft8rx_blank_in(ft8rx_handle* h, void* d_samples, int kind, uint64_t n_sample
 int ft8rx_blank_in_host(ft8rx_handle* h, const void* samples, int kind, uint64_t n_samples, int block, int32_t threshold_q8, int guard, int taper,
                         int64_t* stats, void** d_out) {
     if (!h) return -1;
-    if (blank_in_check(h, "ft8rx_blank_in_host", kind, block, threshold_q8, guard, taper) || blank_in_n_check(h, "ft8rx_blank_in_host", n_samples)) return -1;
+    const int fmt = blank_in_check(h, "ft8rx_blank_in_host", kind, block, threshold_q8, guard, taper);
+    if (fmt < 0 || blank_in_n_check(h, "ft8rx_blank_in_host", n_samples)) return -1;
     if (!samples) { set_err(h, "ft8rx_blank_in_host: samples is NULL"); return -1; }
-    const int fmt = blank_in_fmt(kind);
-    const size_t bytes = (size_t)n_samples * blank_in_sample_bytes(fmt);
+    const size_t bytes = (size_t)n_samples * sf_sample_bytes(fmt);
     ENTER(h);
     if (h->bi_buf_cap < bytes) {
         HIPCHK(h, hipStreamSynchronize(h->stream));     // what was queued behind the last call still reads the old buffer
@@ -2515,7 +2505,8 @@ int ft8rx_blank_in_stream_open(ft8rx_handle* h, int kind, int block, int32_t thr
     if (!h) return -1;
     const char* who = "ft8rx_blank_in_stream_open";
     if (h->bis.open) { set_err(h, "%s: an input blanker stream is open on this handle already (ft8rx_blank_in_stream_close)", who); return -1; }
-    if (blank_in_check(h, who, kind, block, threshold_q8, guard, taper)) return -1;
+    const int fmt = blank_in_check(h, who, kind, block, threshold_q8, guard, taper);
+    if (fmt < 0) return -1;
     if (n_origin > ((uint64_t)1 << 53)) { set_err(h, "%s: n_origin %llu beyond 2^53", who, (unsigned long long)n_origin); return -1; }
     if (max_push < 1 || max_push > FT8RX_BLANK_IN_MAX_PUSH) {
         set_err(h, "%s: max_push %llu outside [1, %llu]", who, (unsigned long long)max_push, (unsigned long long)FT8RX_BLANK_IN_MAX_PUSH); return -1;
@@ -2523,8 +2514,7 @@ int ft8rx_blank_in_stream_open(ft8rx_handle* h, int kind, int block, int32_t thr
     ENTER(h);
     if (blank_in_tables(h)) return -2;
     ft8rx_handle::BlankInStream& s = h->bis;
-    const int fmt = blank_in_fmt(kind);
-    const size_t sb = blank_in_sample_bytes(fmt), work = (size_t)blankin::capacity(block, guard, taper, (int64_t)max_push) * sb;
+    const size_t sb = sf_sample_bytes(fmt), work = (size_t)blankin::capacity(block, guard, taper, (int64_t)max_push) * sb;
     int rc = 0;
     hipError_t e = hipSuccess;
     if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
@@ -2535,7 +2525,7 @@ int ft8rx_blank_in_stream_open(ft8rx_handle* h, int kind, int block, int32_t thr
     if (!rc) rc = blank_in_ws_alloc(h, s.ws, blank_in_sizes((int64_t)max_push, block));
     if (!rc && (e = hipMemsetAsync(s.ws.d_stats, 0, sizeof(long long) * 4, h->stream)) != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
     if (rc) { blank_in_stream_release(h); return -2; }
-    s.kind = kind; s.fmt = fmt; s.log2_b = blank_in_log2(block); s.threshold_q8 = threshold_q8; s.guard = guard; s.taper = taper;
+    s.fmt = fmt; s.log2_b = blank_in_log2(block); s.threshold_q8 = threshold_q8; s.guard = guard; s.taper = taper;
     s.n_origin = (int64_t)n_origin; s.pushed = 0; s.max_push = (int64_t)max_push; s.base = (int64_t)n_origin / block * block; s.cur = 0;
     s.finished = false; s.open = true;
     return 0;
@@ -2549,7 +2539,7 @@ int ft8rx_blank_in_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, 
     if (!s.open) { set_err(h, "%s: no input blanker stream is open (ft8rx_blank_in_stream_open)", who); return -1; }
     if (s.finished) { set_err(h, "%s: the stream is finished: only ft8rx_blank_in_stream_info and ft8rx_blank_in_stream_close are accepted", who); return -1; }
     if (n_new > (uint64_t)s.max_push) { set_err(h, "%s: n_new %llu outside [0, %llu] (max_push)", who, (unsigned long long)n_new, (unsigned long long)s.max_push); return -1; }
-    const size_t sb = blank_in_sample_bytes(s.fmt), align = s.fmt == BIN_IQ_U8 || s.fmt == BIN_IQ_I8 ? 1 : 2;
+    const size_t sb = sf_sample_bytes(s.fmt), align = sf_component_bytes(s.fmt);
     if (n_new && (!in || (on_device && ((uintptr_t)in % align) != 0))) { set_err(h, "%s: in is NULL or not aligned to a sample", who); return -1; }
     if (s.n_origin + s.pushed + (int64_t)n_new > ((int64_t)1 << 54)) { set_err(h, "%s: n_new %llu takes the stream past index 2^54", who, (unsigned long long)n_new); return -1; }
     // (no ENTER: a push touches the stream's own buffers only, on the main stream; batches in flight read none of them)

@@ -18,29 +18,21 @@
 // Statistics: per-block partials that every block writes in full, summed into the stream's int64 counters by k_blankin_stats: exact,
 // no atomics.
 // VEC = x is 16-byte aligned: a group that lies wholly inside the stream goes by 16-byte accesses; the groups at the stream's ends,
-// and every group of a buffer that is only sample-aligned, go sample by sample.
+// and every group of a buffer that is only component-aligned, go sample by sample.
+// FMT: the format (sample_fmt.hpp; SF_REAL_I16, SF_IQ_I16, SF_IQ_U8 or SF_IQ_I8), a compile-time parameter; NC, CB, SB below are its
+// components per sample, bytes per component and bytes per sample.
 #pragma once
 
 #define BIN_NT 256
 #define BIN_HALO 128                   // guard + taper at most
 #define BIN_TAPER_ROW 65               // the taper table of section 17: row R holds T[1 .. R] at [R][1 .. R]
-#define BIN_REAL_I16 0
-#define BIN_IQ_I16 1
-#define BIN_IQ_U8 2
-#define BIN_IQ_I8 3
-
-template <int FMT> struct BinFmt {
-    static constexpr int NC = FMT == BIN_REAL_I16 ? 1 : 2;                       // components per sample
-    static constexpr int CB = FMT == BIN_REAL_I16 || FMT == BIN_IQ_I16 ? 2 : 1;  // bytes per component
-    static constexpr int SB = NC * CB;                                           // bytes per sample
-};
 
 // the window of a launch: x = the sample of absolute index base; [v0, v1) = the samples that exist
 struct BinWin { char* x; long long base, v0, v1; };
 
 // component values of the 8 samples from absolute index n0 (a multiple of 8) on; samples outside [v0, v1) give 0 and are not read
-template <int FMT, bool VEC> FT8_DEV void bin_load8(const BinWin& W, long long n0, int c[8 * BinFmt<FMT>::NC]) {
-    constexpr int NC = BinFmt<FMT>::NC, CB = BinFmt<FMT>::CB, SB = BinFmt<FMT>::SB;
+template <int FMT, bool VEC> FT8_DEV void bin_load8(const BinWin& W, long long n0, int c[8 * sf_components(FMT)]) {
+    constexpr int NC = sf_components(FMT), CB = sf_component_bytes(FMT), SB = sf_sample_bytes(FMT);
     const char* p = W.x + (n0 - W.base) * SB;
     if (VEC && n0 >= W.v0 && n0 + 8 <= W.v1) {
 #pragma unroll
@@ -55,7 +47,7 @@ template <int FMT, bool VEC> FT8_DEV void bin_load8(const BinWin& W, long long n
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         const int u = (w[i] >> (8 * k)) & 0xff;
-                        c[4 * i + k] = FMT == BIN_IQ_U8 ? 2 * u - 255 : (int)(int8_t)u;
+                        c[4 * i + k] = FMT == SF_IQ_U8 ? 2 * u - 255 : (int)(int8_t)u;
                     }
                 }
             }
@@ -69,7 +61,7 @@ template <int FMT, bool VEC> FT8_DEV void bin_load8(const BinWin& W, long long n
                 int v = 0;
                 if (in) {
                     if (CB == 2) v = reinterpret_cast<const int16_t*>(p)[NC * j + k];
-                    else if (FMT == BIN_IQ_U8) v = 2 * (int)reinterpret_cast<const uint8_t*>(p)[NC * j + k] - 255;
+                    else if (FMT == SF_IQ_U8) v = 2 * (int)reinterpret_cast<const uint8_t*>(p)[NC * j + k] - 255;
                     else v = reinterpret_cast<const int8_t*>(p)[NC * j + k];
                 }
                 c[NC * j + k] = v;
@@ -78,8 +70,8 @@ template <int FMT, bool VEC> FT8_DEV void bin_load8(const BinWin& W, long long n
     }
 }
 // ... and back: the samples of the group inside [g0, g1), nothing else
-template <int FMT, bool VEC> FT8_DEV void bin_store8(const BinWin& W, long long n0, long long g0, long long g1, const int c[8 * BinFmt<FMT>::NC]) {
-    constexpr int NC = BinFmt<FMT>::NC, CB = BinFmt<FMT>::CB, SB = BinFmt<FMT>::SB;
+template <int FMT, bool VEC> FT8_DEV void bin_store8(const BinWin& W, long long n0, long long g0, long long g1, const int c[8 * sf_components(FMT)]) {
+    constexpr int NC = sf_components(FMT), CB = sf_component_bytes(FMT), SB = sf_sample_bytes(FMT);
     char* p = W.x + (n0 - W.base) * SB;
     if (VEC && n0 >= g0 && n0 + 8 <= g1) {
 #pragma unroll
@@ -94,7 +86,7 @@ template <int FMT, bool VEC> FT8_DEV void bin_store8(const BinWin& W, long long 
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         const int v = c[4 * i + k];
-                        u |= ((uint32_t)(FMT == BIN_IQ_U8 ? (v + 255) >> 1 : v) & 0xffu) << (8 * k);
+                        u |= ((uint32_t)(FMT == SF_IQ_U8 ? (v + 255) >> 1 : v) & 0xffu) << (8 * k);
                     }
                     w[i] = (int)u;
                 }
@@ -109,16 +101,16 @@ template <int FMT, bool VEC> FT8_DEV void bin_store8(const BinWin& W, long long 
             for (int k = 0; k < NC; k++) {
                 const int v = c[NC * j + k];
                 if (CB == 2) reinterpret_cast<int16_t*>(p)[NC * j + k] = (int16_t)v;
-                else if (FMT == BIN_IQ_U8) reinterpret_cast<uint8_t*>(p)[NC * j + k] = (uint8_t)((v + 255) >> 1);
+                else if (FMT == SF_IQ_U8) reinterpret_cast<uint8_t*>(p)[NC * j + k] = (uint8_t)((v + 255) >> 1);
                 else reinterpret_cast<int8_t*>(p)[NC * j + k] = (int8_t)v;
             }
         }
     }
 }
-template <int FMT> FT8_DEV void bin_mag8(const int c[8 * BinFmt<FMT>::NC], int a[8]) {
+template <int FMT> FT8_DEV void bin_mag8(const int c[8 * sf_components(FMT)], int a[8]) {
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        if (BinFmt<FMT>::NC == 1) a[j] = c[j] < 0 ? -c[j] : c[j];
+        if (sf_components(FMT) == 1) a[j] = c[j] < 0 ? -c[j] : c[j];
         else a[j] = (c[2 * j] < 0 ? -c[2 * j] : c[2 * j]) + (c[2 * j + 1] < 0 ? -c[2 * j + 1] : c[2 * j + 1]);
     }
 }
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(BIN_NT) void k_blankin_level(BinWin W, int log2_b, 
     for (int q = 0; q < 2; q++) {
         const int g = tid + q * BIN_NT;
         if (g < n_groups) {
-            int c[8 * BinFmt<FMT>::NC];
+            int c[8 * sf_components(FMT)];
             bin_load8<FMT, VEC>(W, (b << log2_b) + 8 * g, c);
             bin_mag8<FMT>(c, a[q]);
         } else {
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(BIN_NT) void k_blankin_hits(BinWin W, int log2_b, l
     }
     int bits = 0;
     if (live && L > 0) {
-        int c[8 * BinFmt<FMT>::NC], a[8];
+        int c[8 * sf_components(FMT)], a[8];
         bin_load8<FMT, VEC>(W, n0, c);
         bin_mag8<FMT>(c, a);
         const int lim = threshold_q8 * L;                              // <= 16384 * 65536 = 2^30
@@ -245,7 +237,7 @@ __global__ __launch_bounds__(BIN_NT) void k_blankin_gate(BinWin W, long long g0,
     const bool work = near != 0ull && n0 + 8 > g0 && n0 < g1;
     int n_cut = 0, n_zero = 0;
     if (work) {
-        constexpr int NC = BinFmt<FMT>::NC;
+        constexpr int NC = sf_components(FMT);
         int c[8 * NC];
         BinWin Wg = W;                                                 // read what is gated, nothing else
         Wg.v0 = g0 > W.v0 ? g0 : W.v0; Wg.v1 = g1 < W.v1 ? g1 : W.v1;

@@ -4,7 +4,7 @@
 //   u[n] = x[n] e^{-2 pi i (w n mod 2^32) / 2^32}         x = 0 outside [0, n_samples)
 //   v[k] = sum_j h1[j] u[k R1 + j - C1]                   D >= 4 only (R1 = D / 2); otherwise v = u
 //   z[m] = sum_j h2[j] v[m R2 + j - C2]                   R2 = 2 (1 at D = 1)
-//   y[m] = scale Re(i^m z[m])                             scale = gain g_kind
+//   y[m] = scale Re(i^m z[m])                             scale = gain sf_real_gain(fmt)
 // The tile is written once (ddc_tile) and used by two kernels: k_ddc (one call = one cycle, the input an array of the call) and
 // k_ddc_stream (a continuous stream, the input a ring of the newest samples, the output a ring of two cycles,
 // indices absolute); k_ddc_gather cuts frames out of that ring.
@@ -60,12 +60,10 @@ __device__ __forceinline__ float2 ddc_phasor(uint32_t p) {
 __device__ __forceinline__ float2 ddc_cmul(float2 a, float2 b) {
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
-// sample i of an array of `kind` as a complex float
-__device__ __forceinline__ float2 ddc_fetch(const void* __restrict__ in, int kind, size_t i) {
-    if (kind == FT8RX_DDC_IQ_I16) { const short2 v = ((const short2*)in)[i]; return make_float2((float)v.x, (float)v.y); }
-    if (kind == FT8RX_DDC_IQ_F32) return ((const float2*)in)[i];
-    if (kind == FT8RX_DDC_REAL_I16) return make_float2((float)((const int16_t*)in)[i], 0.0f);
-    return make_float2(((const float*)in)[i], 0.0f);
+// sample i of an array of format `fmt` as a complex float
+__device__ __forceinline__ float2 ddc_fetch(const void* __restrict__ in, int fmt, size_t i) {
+    __builtin_assume(fmt >= SF_REAL_I16 && fmt <= SF_IQ_F32);      // what ddc_check lets through: no 8-bit branch is kept
+    return sf_is_iq(fmt) ? Sample<true>::fetch(in, fmt, i) : make_float2(Sample<false>::fetch(in, fmt, i), 0.0f);
 }
 
 // One output tile, the body of k_ddc and of k_ddc_stream: load + mix -> LDS, stage 1 -> the v image, stage 2, i^m, scale.  The tile's
@@ -153,7 +151,7 @@ __device__ __forceinline__ void ddc_tile(uint32_t w, uint32_t p0, float scale, L
 __device__ __forceinline__ int16_t ddc_round(float y) { return (int16_t)fminf(fmaxf(rintf(y), -32768.0f), 32767.0f); }
 
 template <int D>
-__global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int kind, unsigned long long stream_stride, int n_samples,
+__global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int fmt, unsigned long long stream_stride, int n_samples,
                                                 const DdcOut* __restrict__ outs, float scale, int16_t* __restrict__ audio,
                                                 float* __restrict__ audio_f32) {
     using G = DdcGeom<D>;
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int
     ddc_tile<D>(o.w, (uint32_t)n0, scale,
                 [&](int i) {                          // the input is zero outside [0, n_samples)
                     const int n = n0 + i;
-                    return n < 0 || n >= n_samples ? make_float2(0.0f, 0.0f) : ddc_fetch(in, kind, base + (size_t)n);
+                    return n < 0 || n >= n_samples ? make_float2(0.0f, 0.0f) : ddc_fetch(in, fmt, base + (size_t)n);
                 },
                 [&](int oo, float y) {
                     const int m = m0 + oo;
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc(const void* __restrict__ in, int
 // `cap` samples (a power of two; sample n at (n - n_origin) & (cap - 1)), zero before the origin n_origin (and from n_end on, which
 // no complete tile reaches); its output goes to the channel's ring at m mod ring_len.  One block per (channel, new tile).
 template <int D>
-__global__ __launch_bounds__(DDC_NT) void k_ddc_stream(const void* __restrict__ ring_in, int kind, unsigned long long cap, long long n_origin,
+__global__ __launch_bounds__(DDC_NT) void k_ddc_stream(const void* __restrict__ ring_in, int fmt, unsigned long long cap, long long n_origin,
                                                        long long n_end, const DdcOut* __restrict__ outs, long long tile_first, int n_tiles,
                                                        float scale, int ring_len, int16_t* __restrict__ ring_out, float* __restrict__ ring_f32) {
     using G = DdcGeom<D>;
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc_stream(const void* __restrict__ 
                 [&](int i) {
                     const long long n = n0 + i;
                     return n < n_origin || n >= n_end ? make_float2(0.0f, 0.0f)
-                                                      : ddc_fetch(ring_in, kind, base + (size_t)((unsigned long long)(n - n_origin) & (cap - 1)));
+                                                      : ddc_fetch(ring_in, fmt, base + (size_t)((unsigned long long)(n - n_origin) & (cap - 1)));
                 },
                 [&](int oo, float y) {
                     int r = r0 + oo;

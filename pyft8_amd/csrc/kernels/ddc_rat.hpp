@@ -28,34 +28,8 @@
 #define DDR_LS_WAVE 6144               // WAVE: input samples the LDS image holds
 #define DDR_TK_WAVE 16                 // WAVE: outputs per tile at most, 4 per wave
 
-// sample i of an array of `kind` as a float (real) or a complex float (IQ); the 8-bit kinds on the int16 scale, exact in float32
-template <bool IQ> struct DdrSample;
-template <> struct DdrSample<false> {
-    typedef float T;
-    static __device__ __forceinline__ float zero() { return 0.0f; }
-    static __device__ __forceinline__ float fetch(const void* __restrict__ in, int kind, size_t i) {
-        return kind == FT8RX_DDC_REAL_I16 ? (float)((const int16_t*)in)[i] : ((const float*)in)[i];
-    }
-    static __device__ __forceinline__ void mac(float2 W, float x, float& ar, float& ai) { ar = fmaf(W.x, x, ar); ai = fmaf(W.y, x, ai); }
-};
-template <> struct DdrSample<true> {
-    typedef float2 T;
-    static __device__ __forceinline__ float2 zero() { return make_float2(0.0f, 0.0f); }
-    static __device__ __forceinline__ float2 fetch(const void* __restrict__ in, int kind, size_t i) {
-        if (kind == FT8RX_DDC_IQ_I16) { const short2 v = ((const short2*)in)[i]; return make_float2((float)v.x, (float)v.y); }
-        if (kind == FT8RX_DDC_IQ_F32) return ((const float2*)in)[i];
-        if (kind == FT8RX_WIDE_IQ_U8) { const uchar2 v = ((const uchar2*)in)[i]; return make_float2((float)(256 * (int)v.x - 32640), (float)(256 * (int)v.y - 32640)); }
-        const char2 v = ((const char2*)in)[i];
-        return make_float2((float)(256 * (int)v.x), (float)(256 * (int)v.y));
-    }
-    static __device__ __forceinline__ void mac(float2 W, float2 x, float& ar, float& ai) {
-        ar = fmaf(W.x, x.x, ar); ar = fmaf(-W.y, x.y, ar);
-        ai = fmaf(W.x, x.y, ai); ai = fmaf(W.y, x.x, ai);
-    }
-};
-
 template <bool IQ, bool LANE> struct DdrLds {
-    typedef typename DdrSample<IQ>::T T;
+    typedef typename Sample<IQ>::T T;
     static constexpr int BYTES = LANE ? (int)sizeof(float2) * DDR_TAB + (int)sizeof(T) * DDR_LS_LANE : (int)sizeof(T) * DDR_LS_WAVE;
 };
 
@@ -65,7 +39,7 @@ template <bool IQ, bool LANE> struct DdrLds {
 template <bool IQ, bool LANE, class Load, class Store>
 __device__ __forceinline__ void ddr_tile(const float2* __restrict__ tab, int C, int L, int M, int P, int tk, uint32_t w0, float g0, long long k0,
                                          Load load, Store store) {
-    using S = DdrSample<IQ>;
+    using S = Sample<IQ>;
     typedef typename S::T T;
     __shared__ __align__(16) unsigned char smem[DdrLds<IQ, LANE>::BYTES];
     const int t = threadIdx.x;
@@ -127,37 +101,28 @@ __device__ __forceinline__ void ddr_tile(const float2* __restrict__ tab, int C, 
     }
 }
 
-// One call: in = n_samples samples of `kind`, zero outside -> mid [n_ch][n_mid] (intermediate samples 0 .. n_mid - 1 of every channel)
+// One call: in = n_samples samples of format `fmt`, zero outside -> mid [n_ch][n_mid] (intermediate samples 0 .. n_mid - 1 of every channel)
 template <bool IQ, bool LANE>
-__global__ __launch_bounds__(DDR_NT) void k_ddc_rat(const void* __restrict__ in, int kind, long long n_samples, const float2* __restrict__ tab,
+__global__ __launch_bounds__(DDR_NT) void k_ddc_rat(const void* __restrict__ in, int fmt, long long n_samples, const float2* __restrict__ tab,
                                                     const uint32_t* __restrict__ w0s, int C, int L, int M, int P, int tk, float g0, long long n_mid,
                                                     float2* __restrict__ mid) {
     const int ch = blockIdx.y;
     const long long k0 = (long long)blockIdx.x * tk;
-    ddr_tile<IQ, LANE>(tab + (size_t)ch * (size_t)(L * P), C, L, M, P, tk, w0s[ch], g0, k0,
-                       [&](long long n) { return n < 0 || n >= n_samples ? DdrSample<IQ>::zero() : DdrSample<IQ>::fetch(in, kind, (size_t)n); },
+    ddr_tile<IQ, LANE>(tab + (size_t)ch * (size_t)(L * P), C, L, M, P, tk, w0s[ch], g0, k0, ArrayLoad<IQ>{in, fmt, n_samples},
                        [&](int q, float2 v) { if (k0 + q < n_mid) mid[(size_t)ch * (size_t)n_mid + (size_t)(k0 + q)] = v; });
 }
 
 // The stream (ft8rx_ddc_rat_stream_push): intermediate samples k_first .. k_first + n_k - 1 of every channel -> mid [n_ch][n_k].  The
-// input is zero before n_origin; [n_start, n_end) is the chunk of this push; what came before it is in the history ring of H samples
-// (sample n_start - 1 at p_last, older ones before it, wrapping), of which a tile reaches back less than H.
+// input is the history ring and the chunk of this push (kernels/sample.hpp: StreamLoad).
 template <bool IQ, bool LANE>
-__global__ __launch_bounds__(DDR_NT) void k_ddc_rat_stream(const void* __restrict__ hist, int H, int p_last, const void* __restrict__ chunk, int kind,
+__global__ __launch_bounds__(DDR_NT) void k_ddc_rat_stream(const void* __restrict__ hist, int H, int p_last, const void* __restrict__ chunk, int fmt,
                                                            long long n_origin, long long n_start, long long n_end, const float2* __restrict__ tab,
                                                            const uint32_t* __restrict__ w0s, int C, int L, int M, int P, int tk, float g0,
                                                            long long k_first, int n_k, float2* __restrict__ mid) {
     const int ch = blockIdx.y;
     const long long k0 = k_first + (long long)blockIdx.x * tk;
     ddr_tile<IQ, LANE>(tab + (size_t)ch * (size_t)(L * P), C, L, M, P, tk, w0s[ch], g0, k0,
-                       [&](long long n) {
-                           if (n < n_origin || n >= n_end) return DdrSample<IQ>::zero();
-                           if (n >= n_start) return DdrSample<IQ>::fetch(chunk, kind, (size_t)(n - n_start));
-                           const long long d = n_start - 1 - n;
-                           if (d >= H) return DdrSample<IQ>::zero();          // (no complete output reaches that far back)
-                           const int p = p_last - (int)d;
-                           return DdrSample<IQ>::fetch(hist, kind, (size_t)(p < 0 ? p + H : p));
-                       },
+                       StreamLoad<IQ>{hist, H, p_last, chunk, fmt, n_origin, n_start, n_end},
                        [&](int q, float2 v) {
                            const long long kk = (long long)blockIdx.x * tk + q;
                            if (kk < n_k) mid[(size_t)ch * (size_t)n_k + (size_t)kk] = v;

@@ -19,44 +19,24 @@
 #define DDW_JP 1024                    // taps per piece (a multiple of 64: a tap stays with its lane)
 #define DDW_LS 6144                    // input samples the LDS image holds: 24 KB real, 48 KB IQ
 #define DDW_TK 16                      // outputs per tile at most: 4 per wave
-
-// sample i of an array of `kind` as a float (real) or a complex float (IQ); the 8-bit kinds on the int16 scale, exact in float32
-template <bool IQ> struct DdwSample;
-template <> struct DdwSample<false> {
-    typedef float T;
-    static __device__ __forceinline__ float zero() { return 0.0f; }
-    static __device__ __forceinline__ float fetch(const void* __restrict__ in, int, size_t i) { return (float)((const int16_t*)in)[i]; }
-    static __device__ __forceinline__ void mac(float2 W, float x, float& ar, float& ai) { ar = fmaf(W.x, x, ar); ai = fmaf(W.y, x, ai); }
-};
-template <> struct DdwSample<true> {
-    typedef float2 T;
-    static __device__ __forceinline__ float2 zero() { return make_float2(0.0f, 0.0f); }
-    static __device__ __forceinline__ float2 fetch(const void* __restrict__ in, int kind, size_t i) {
-        if (kind == FT8RX_WIDE_IQ_I16) { const short2 v = ((const short2*)in)[i]; return make_float2((float)v.x, (float)v.y); }
-        if (kind == FT8RX_WIDE_IQ_U8) { const uchar2 v = ((const uchar2*)in)[i]; return make_float2((float)(256 * (int)v.x - 32640), (float)(256 * (int)v.y - 32640)); }
-        const char2 v = ((const char2*)in)[i];
-        return make_float2((float)(256 * (int)v.x), (float)(256 * (int)v.y));
-    }
-    static __device__ __forceinline__ void mac(float2 W, float2 x, float& ar, float& ai) {
-        ar = fmaf(W.x, x.x, ar); ar = fmaf(-W.y, x.y, ar);
-        ai = fmaf(W.x, x.y, ai); ai = fmaf(W.y, x.x, ai);
-    }
-};
+// the wide entries take no float kind (sample_fmt.hpp: SF_KINDS_WIDE): said to the compiler, the loader's float branches are not kept
+#define DDW_FORMATS(IQ, fmt) __builtin_assume((IQ) ? (fmt) != SF_IQ_F32 : (fmt) == SF_REAL_I16)
 
 // One tile, the body of k_ddc_pre and of k_ddc_pre_stream: outputs k0 .. k0 + tk - 1 of one channel (tab: its n_taps table entries, w0:
-// its frequency word).  load(i) is input sample k0 R0 - C0 + i (zero where the stream has none), store(q, v) takes output k0 + q.
+// its frequency word).  load(n) is input sample n, absolute (zero where the stream has none), store(q, v) takes output k0 + q.
 // tk <= DDW_TK and (tk - 1) R0 + DDW_JP <= DDW_LS (ddc_wide_ring.hpp: tile_outputs).
 template <bool IQ, class Load, class Store>
 __device__ __forceinline__ void ddw_tile(const float2* __restrict__ tab, int n_taps, int R0, int tk, uint32_t w0, float g0, long long k0,
                                          Load load, Store store) {
-    using S = DdwSample<IQ>;
+    using S = Sample<IQ>;
     __shared__ typename S::T sx[DDW_LS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, C0 = (n_taps - 1) / 2;
+    const long long n0 = k0 * R0 - C0;                // the first input of the tile's first output
     float ar[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ai[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int jp = 0; jp < n_taps; jp += DDW_JP) {
         const int nj = n_taps - jp < DDW_JP ? n_taps - jp : DDW_JP, span = (tk - 1) * R0 + nj;
         if (jp) __syncthreads();                      // the previous piece has been read
-        for (int s = t; s < span; s += DDW_NT) sx[s] = load(jp + s);
+        for (int s = t; s < span; s += DDW_NT) sx[s] = load(n0 + jp + s);
         __syncthreads();
         for (int jj = lane; jj < nj; jj += 64) {
             const float2 W = tab[jp + jj];
@@ -71,7 +51,6 @@ __device__ __forceinline__ void ddw_tile(const float2* __restrict__ tab, int n_t
     for (int i = 0; i < 4; i++)
         for (int off = 32; off; off >>= 1) { ar[i] += __shfl_xor(ar[i], off); ai[i] += __shfl_xor(ai[i], off); }
     if (lane == 0) {
-        const int C0 = (n_taps - 1) / 2;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int q = wave + 4 * i;
@@ -85,41 +64,29 @@ __device__ __forceinline__ void ddw_tile(const float2* __restrict__ tab, int n_t
     }
 }
 
-// One call: in = n_samples samples of `kind`, zero outside -> mid [n_ch][n_mid] (intermediate samples 0 .. n_mid - 1 of every channel)
+// One call: in = n_samples samples of format `fmt`, zero outside -> mid [n_ch][n_mid] (intermediate samples 0 .. n_mid - 1 of every channel)
 template <bool IQ>
-__global__ __launch_bounds__(DDW_NT) void k_ddc_pre(const void* __restrict__ in, int kind, long long n_samples, const float2* __restrict__ tab,
+__global__ __launch_bounds__(DDW_NT) void k_ddc_pre(const void* __restrict__ in, int fmt, long long n_samples, const float2* __restrict__ tab,
                                                     const uint32_t* __restrict__ w0s, int n_taps, int R0, int tk, float g0, long long n_mid,
                                                     float2* __restrict__ mid) {
+    DDW_FORMATS(IQ, fmt);
     const int ch = blockIdx.y;
-    const long long k0 = (long long)blockIdx.x * tk, n0 = k0 * R0 - (n_taps - 1) / 2;
-    ddw_tile<IQ>(tab + (size_t)ch * n_taps, n_taps, R0, tk, w0s[ch], g0, k0,
-                 [&](int i) {
-                     const long long n = n0 + i;
-                     return n < 0 || n >= n_samples ? DdwSample<IQ>::zero() : DdwSample<IQ>::fetch(in, kind, (size_t)n);
-                 },
+    const long long k0 = (long long)blockIdx.x * tk;
+    ddw_tile<IQ>(tab + (size_t)ch * n_taps, n_taps, R0, tk, w0s[ch], g0, k0, ArrayLoad<IQ>{in, fmt, n_samples},
                  [&](int q, float2 v) { if (k0 + q < n_mid) mid[(size_t)ch * (size_t)n_mid + (size_t)(k0 + q)] = v; });
 }
 
 // The stream (ft8rx_ddc_wide_stream_push): intermediate samples k_first .. k_first + n_k - 1 of every channel -> mid [n_ch][n_k].  The
-// input is zero before n_origin; [n_start, n_end) is the chunk of this push; what came before it is in the history ring of H samples
-// (sample n_start - 1 at p_last, older ones before it, wrapping), of which a tile reaches back less than H.
+// input is the history ring and the chunk of this push (kernels/sample.hpp: StreamLoad).
 template <bool IQ>
-__global__ __launch_bounds__(DDW_NT) void k_ddc_pre_stream(const void* __restrict__ hist, int H, int p_last, const void* __restrict__ chunk, int kind,
+__global__ __launch_bounds__(DDW_NT) void k_ddc_pre_stream(const void* __restrict__ hist, int H, int p_last, const void* __restrict__ chunk, int fmt,
                                                            long long n_origin, long long n_start, long long n_end, const float2* __restrict__ tab,
                                                            const uint32_t* __restrict__ w0s, int n_taps, int R0, int tk, float g0,
                                                            long long k_first, int n_k, float2* __restrict__ mid) {
+    DDW_FORMATS(IQ, fmt);
     const int ch = blockIdx.y;
-    const long long k0 = k_first + (long long)blockIdx.x * tk, n0 = k0 * R0 - (n_taps - 1) / 2;
-    ddw_tile<IQ>(tab + (size_t)ch * n_taps, n_taps, R0, tk, w0s[ch], g0, k0,
-                 [&](int i) {
-                     const long long n = n0 + i;
-                     if (n < n_origin || n >= n_end) return DdwSample<IQ>::zero();
-                     if (n >= n_start) return DdwSample<IQ>::fetch(chunk, kind, (size_t)(n - n_start));
-                     const long long d = n_start - 1 - n;
-                     if (d >= H) return DdwSample<IQ>::zero();          // (no complete output reaches that far back)
-                     const int p = p_last - (int)d;
-                     return DdwSample<IQ>::fetch(hist, kind, (size_t)(p < 0 ? p + H : p));
-                 },
+    const long long k0 = k_first + (long long)blockIdx.x * tk;
+    ddw_tile<IQ>(tab + (size_t)ch * n_taps, n_taps, R0, tk, w0s[ch], g0, k0, StreamLoad<IQ>{hist, H, p_last, chunk, fmt, n_origin, n_start, n_end},
                  [&](int q, float2 v) {
                      const long long kk = (long long)blockIdx.x * tk + q;
                      if (kk < n_k) mid[(size_t)ch * (size_t)n_k + (size_t)kk] = v;

@@ -5,16 +5,16 @@ of the tables), the float64 twin of the definition, and a wav reader for real (m
 import numpy as np
 
 from . import _lib
+from . import kinds as _k
+from .kinds import REAL_I16, REAL_F32, IQ_I16, IQ_F32  # noqa: F401 -- this module's kinds: include/ft8rx.h FT8RX_DDC_*
 
-REAL_I16, REAL_F32, IQ_I16, IQ_F32 = range(4)          # include/ft8rx.h FT8RX_DDC_*
-KIND_NAMES = ("real int16", "real float32", "IQ int16", "IQ float32")
-_DTYPE = {REAL_I16: np.int16, REAL_F32: np.float32, IQ_I16: np.int16, IQ_F32: np.float32}
+KINDS, KIND_NAMES, _DTYPE = _k.view((REAL_I16, REAL_F32, IQ_I16, IQ_F32))
 RATES = tuple(12000 * d for d in (1, 2, 4, 8, 16))
 NSAMP = _lib.NSAMP
 
 
 def is_iq(kind):
-    return kind in (IQ_I16, IQ_F32)
+    return kind in KINDS and _k.is_iq(kind)
 
 
 def kind_of(samples, iq):
@@ -177,7 +177,6 @@ def pack(samples, kind):
     if kind not in (REAL_I16, REAL_F32, IQ_I16, IQ_F32):
         raise _lib.Ft8rxError(f"kind {kind} is not one of REAL_I16, REAL_F32, IQ_I16, IQ_F32")
     a = np.asarray(samples)
-    base = _DTYPE[kind]
     if is_iq(kind):
         if np.iscomplexobj(a):
             if kind == IQ_I16:
@@ -195,8 +194,5 @@ def pack(samples, kind):
             a = a[None]
         if a.ndim != 2:
             raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} needs [n_streams, n], got shape {a.shape}")
-    if a.dtype != base:
-        if base == np.int16 and (not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < -32768 or a.max() > 32767))):
-            raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} needs integers in the int16 range")
-    a = np.ascontiguousarray(a, base)
+    a = _k.as_dtype(a, kind, "samples: {name} needs integers in the {dtype} range")
     return a, a.shape[0], a.shape[1]

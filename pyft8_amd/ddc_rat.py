@@ -12,12 +12,11 @@ import numpy as np
 from . import _lib
 from . import ddc as _ddc
 from . import ddc_wide as _dw
+from . import kinds as _k
+from .kinds import REAL_I16, REAL_F32, IQ_I16, IQ_F32  # noqa: F401 -- include/ft8rx.h FT8RX_DDC_*
 
-REAL_I16, REAL_F32, IQ_I16, IQ_F32 = range(4)          # include/ft8rx.h FT8RX_DDC_*
-IQ_U8, IQ_I8 = 18, 19                                  # include/ft8rx.h FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8
-KINDS = (REAL_I16, REAL_F32, IQ_I16, IQ_F32, IQ_U8, IQ_I8)
-KIND_NAMES = {REAL_I16: "real int16", REAL_F32: "real float32", IQ_I16: "IQ int16", IQ_F32: "IQ float32", IQ_U8: "IQ uint8", IQ_I8: "IQ int8"}
-_DTYPE = {REAL_I16: np.int16, REAL_F32: np.float32, IQ_I16: np.int16, IQ_F32: np.float32, IQ_U8: np.uint8, IQ_I8: np.int8}
+IQ_U8, IQ_I8 = _k.WIDE_IQ_U8, _k.WIDE_IQ_I8            # include/ft8rx.h FT8RX_WIDE_IQ_U8, FT8RX_WIDE_IQ_I8
+KINDS, KIND_NAMES, _DTYPE = _k.view((REAL_I16, REAL_F32, IQ_I16, IQ_F32, IQ_U8, IQ_I8))
 NSAMP = _lib.NSAMP
 TILE = 1008
 N_MAX = 1 << 52
@@ -31,7 +30,7 @@ def _kind(kind):
 
 
 def is_iq(kind):
-    return _kind(kind) not in (REAL_I16, REAL_F32)
+    return _k.is_iq(_kind(kind))
 
 
 def kind_of(samples, iq):
@@ -88,19 +87,8 @@ def frequency_words(rate, f_dial_hz):
 def pack(samples, kind):
     """One stream's samples as the C-contiguous array ft8rx_ddc_rat takes for `kind` -> (array, n): real kinds [n]; IQ kinds (I, Q)
     pairs [n, 2] (IQ float32 also as complex [n])."""
-    a = np.asarray(samples)
-    dt = _DTYPE[_kind(kind)]
-    if kind == IQ_F32 and a.dtype.kind == "c" and a.ndim == 1:
-        a = np.ascontiguousarray(a, np.complex64)
-        return a.view(np.float32).reshape(-1, 2), a.shape[0]
-    if a.dtype.kind == "c" or a.ndim != (2 if is_iq(kind) else 1) or (is_iq(kind) and a.shape[1] != 2):
-        raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} is ONE stream, {'(I, Q) pairs [n, 2]' if is_iq(kind) else '[n]'}, got shape {a.shape} {a.dtype}")
-    if a.dtype != dt and np.dtype(dt).kind != "f":
-        info = np.iinfo(dt)
-        if not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < info.min or a.max() > info.max)):
-            raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} needs integers in the {np.dtype(dt).name} range, got dtype {a.dtype}")
-    a = np.ascontiguousarray(a, dt)
-    return a, a.shape[0]
+    return _k.pack_stream(samples, _kind(kind), "samples: {name} is ONE stream, {form}, got shape {shape} {got}",
+                          "samples: {name} needs integers in the {dtype} range, got dtype {got}")
 
 
 def sample_values(x, kind):
@@ -110,7 +98,7 @@ def sample_values(x, kind):
     a = np.asarray(x)
     if a.ndim == 1 and (a.dtype.kind == "c" if is_iq(kind) else a.dtype == np.float64):
         return a.astype(np.complex128 if is_iq(kind) else np.float64)
-    return _dw._values(pack(x, kind)[0], kind, is_iq(kind))
+    return _k.values(pack(x, kind)[0], kind)
 
 
 def phase_table(rate, w0=0):

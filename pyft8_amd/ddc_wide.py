@@ -11,11 +11,10 @@ import numpy as np
 
 from . import _lib
 from . import ddc as _ddc
+from . import kinds as _k
 
-REAL_I16, IQ_I16, IQ_U8, IQ_I8 = range(16, 20)         # include/ft8rx.h FT8RX_WIDE_*
-KINDS = (REAL_I16, IQ_I16, IQ_U8, IQ_I8)
-KIND_NAMES = {REAL_I16: "real int16", IQ_I16: "IQ int16", IQ_U8: "IQ uint8", IQ_I8: "IQ int8"}
-_DTYPE = {REAL_I16: np.int16, IQ_I16: np.int16, IQ_U8: np.uint8, IQ_I8: np.int8}
+REAL_I16, IQ_I16, IQ_U8, IQ_I8 = _k.WIDE_REAL_I16, _k.WIDE_IQ_I16, _k.WIDE_IQ_U8, _k.WIDE_IQ_I8      # include/ft8rx.h FT8RX_WIDE_*
+KINDS, KIND_NAMES, _DTYPE = _k.view((REAL_I16, IQ_I16, IQ_U8, IQ_I8))
 NSAMP = _lib.NSAMP
 TILE = 1008
 
@@ -27,7 +26,7 @@ def _kind(kind):
 
 
 def is_iq(kind):
-    return _kind(kind) != REAL_I16
+    return _k.is_iq(_kind(kind))
 
 
 def kind_of(samples, iq):
@@ -94,16 +93,8 @@ def frequency_words(rate, f_dial_hz):
 def pack(samples, kind):
     """One stream's samples as the C-contiguous array ft8rx_ddc_wide takes for `kind` -> (array, n): real int16 [n]; IQ kinds (I, Q)
     pairs [n, 2] of int16, uint8 or int8."""
-    a = np.asarray(samples)
-    dt = _DTYPE[_kind(kind)]
-    if a.ndim != (2 if is_iq(kind) else 1) or (is_iq(kind) and a.shape[1] != 2):
-        raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} is ONE stream, {'(I, Q) pairs [n, 2]' if is_iq(kind) else '[n]'}, got shape {a.shape}")
-    if a.dtype != dt:
-        info = np.iinfo(dt)
-        if not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < info.min or a.max() > info.max)):
-            raise _lib.Ft8rxError(f"samples: {KIND_NAMES[kind]} needs integers in the {np.dtype(dt).name} range, got dtype {a.dtype}")
-    a = np.ascontiguousarray(a, dt)
-    return a, a.shape[0]
+    return _k.pack_stream(samples, _kind(kind), "samples: {name} is ONE stream, {form}, got shape {shape}",
+                          "samples: {name} needs integers in the {dtype} range, got dtype {got}")
 
 
 def sample_values(x, kind):
@@ -112,17 +103,7 @@ def sample_values(x, kind):
     a = np.asarray(x)
     if a.ndim == 1 and a.dtype.kind == ("c" if is_iq(kind) else "f"):
         return a.astype(np.complex128 if is_iq(kind) else np.float64)
-    return _values(pack(x, kind)[0], kind, is_iq(kind))
-
-
-def _values(a, kind, iq):
-    """packed samples (this module's kinds and ddc_rat's) -> float64 [n] or complex128 [n]: the 8-bit kinds on the int16 scale"""
-    a = a.astype(np.float64)
-    if kind == IQ_U8:
-        a = 256.0 * (a - 127.5)
-    elif kind == IQ_I8:
-        a = 256.0 * a
-    return a[:, 0] + 1j * a[:, 1] if iq else a
+    return _k.values(pack(x, kind)[0], kind)
 
 
 def _phasor(p):

@@ -17,6 +17,7 @@ from . import ddc as _ddc
 from . import ddc_wide as _dw
 from . import ddc_rat as _dr
 from . import blank_in as _bi
+from . import kinds as _kinds
 
 NSAMP = _lib.NSAMP
 HOP = 480                     # 12 kHz samples per hop of early_decode_hops
@@ -313,7 +314,7 @@ class WideIn:
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
             if self._ib is not None and real:
-                self._forward(h, h.blank_in_stream_push(a[0]), a[0][:1].nbytes)
+                self._forward(h, h.blank_in_stream_push(a[0]), _kinds.sample_bytes(self.kind))
             else:
                 self.m_produced = HANDLE_CALLS[self.mod][2](h, a)
             if self.waterfall:
@@ -403,12 +404,11 @@ class WideIn:
                 h = self._rx._live_handle(self.n_channels)
                 if not self._ib_done:
                     self._ib_done = True
-                    self._forward(h, h.blank_in_stream_push(None, finish=True), np.zeros(1, self.mod._DTYPE[self.kind]).nbytes * (2 if self.mod.is_iq(self.kind) else 1))
+                    self._forward(h, h.blank_in_stream_push(None, finish=True), _kinds.sample_bytes(self.kind))
         # a tile's worth of rest samples per stream, rounded up (1008 D at a multiple of 12 kHz); uint8 has no zero: 128 is half a step,
         # 128 counts of the int16 scale, above it
-        dtype = self.mod._DTYPE[self.kind]
-        zeros = np.full((self.n_streams, -(-TILE * self.sample_rate // 12000)) + ((2,) if self.mod.is_iq(self.kind) else ()),
-                        128 if dtype == np.uint8 else 0, dtype)
+        dtype = _kinds.DTYPE[self.kind]
+        zeros = np.full((self.n_streams,) + _kinds.shape(self.kind, -(-TILE * self.sample_rate // 12000)), 128 if dtype == np.uint8 else 0, dtype)
         while self.m_produced < m_real:
             self._push(zeros, False)
         self._note(m_real)

@@ -39,6 +39,6 @@ def test_bytes_are_the_parents(got, case):
 def test_the_cases_take_every_path():
     """what the recording itself says about the cases: every stream made its tiles, and where the stage decimates one push made nothing"""
     streams = {c: v["stream"] for c, v in WANT.items() if "stream" in v}
-    assert len(streams) == 6 and all(s["m"] in (2016, 3024) for s in streams.values())
+    assert len(streams) == 12 and all(s["m"] in (2016, 3024) for s in streams.values())
     assert all(s["quiet_push"] for c, s in streams.items() if c != "rat-44100-real")          # 44100 -> 48000: every input completes a sample
     assert WANT["after-stream-wide-240000-iq16"]["one-shot"]["frames"] != WANT["wide-240000-iq16"]["one-shot"]["frames"]      # its own input
