@@ -226,6 +226,20 @@ int  ft8rx_enqueue_batch(ft8rx_handle* h, const int16_t* d_audio, int n_frames);
  * transfer behind the kernels.  `audio` must stay valid until the batch has been fetched; page-locked memory (ft8rx_alloc_host) makes
  * the copies truly asynchronous. */
 int  ft8rx_enqueue_batch_host(ft8rx_handle* h, const int16_t* audio, int n_frames);
+/* ---- float32 frames (opt-in) ------------------------------------------------------------------------------
+ * The _f32 entries take the frames as [n_frames][180000] float32 instead of int16 and are otherwise their twins: the same plan,
+ * chunks, result slots, streams, results and refusals.  Only the two kernels that read audio differ (k_spectrogram_f32, k_cyc_a_f32):
+ * they use the samples as they are where the int16 kernels convert, so integer-valued floats in the int16 range give the int16
+ * entries' results byte for byte, and everything behind the dB grid and the cycle spectrum works on level differences and normalised
+ * quantities: scaling a frame by a power of two shifts its grid by 20 log10 of the factor and changes no message.  The level is the
+ * caller's: no gain has to be chosen and nothing is rounded.  Non-finite samples are the caller's business: they are not looked for
+ * on the device, and a NaN or infinity poisons its own frame only, since every workspace is indexed by frame.
+ * Device frames (ft8rx_enqueue_batch_f32) are aligned to 8 bytes, a pair of samples.  The float staging audio
+ * (ft8rx_staging_audio_f32, 720 000 bytes per frame, and the second buffer of ft8rx_enqueue_batch_host_f32) is allocated on first use. */
+int  ft8rx_decode_batch_f32(ft8rx_handle* h, const float* audio, int n_frames,
+                            ft8rx_record* records, int32_t* counts, ft8rx_event* events, int32_t* event_counts);   /* ft8rx_decode_batch */
+int  ft8rx_enqueue_batch_f32(ft8rx_handle* h, const float* d_audio, int n_frames);                                  /* ft8rx_enqueue_batch */
+int  ft8rx_enqueue_batch_host_f32(ft8rx_handle* h, const float* audio, int n_frames);                               /* ft8rx_enqueue_batch_host */
 int  ft8rx_sync(ft8rx_handle* h);
 int  ft8rx_fetch_results(ft8rx_handle* h, int n_frames, ft8rx_record* records, int32_t* counts,
                          ft8rx_event* events, int32_t* event_counts);
@@ -472,7 +486,9 @@ int  ft8rx_ddc_taps(int32_t rate_hz, int stage, float* taps, int cap);
  * output exists once its tile's last input has been pushed: at most 84 ms (one tile) + C2 R1 + C1 input samples (about 6 ms) after its
  * own sample.
  * open   kind, rate_hz, n_streams, n_out (<= max_frames), src, f_dial_hz, gain, f_mixed_hz: as ft8rx_ddc, refused by the same checks;
- *        keep_f32 != 0: also keep the float32 ring (tests).  Refused while a stream is open.
+ *        keep_f32 != 0: also keep the float32 ring, y before rounding, 1.44 MB per channel (ft8rx_ddc_stream_frame_f32, read's y_f32);
+ *        keep_f32 = FT8RX_DDC_KEEP_F32_FRAMES: the stream runs float frames -- the ring is kept and the
+ *        spectrogram stage (ft8rx_ddc_stream_grid_*) reads it instead of the int16 ring.  Refused while a stream is open.
  * push   n_new samples of every stream, 1 .. rate_hz (one second): in = [n_streams][n_new] samples, host memory (copied through a
  *        page-locked buffer) or, on_device != 0, device memory; at most two copies per stream into the rings, then ONE kernel for every
  *        tile whose inputs are now complete.  Asynchronous on the handle's main stream.  m_produced: optional, the absolute index one
@@ -481,13 +497,18 @@ int  ft8rx_ddc_taps(int32_t rate_hz, int stage, float* taps, int cap);
  *        m_produced on.  m_first is a signed index passed as its 64-bit two's complement (it may be odd, negative, before the origin).
  *        d_audio: device [n_out][180000], NULL = the staging audio (ft8rx_enqueue_batch(h, ft8rx_staging_audio(h), n_out) is the
  *        intended next call).  Refused with -1 when part of the range has left the ring.  Waits for the batches in flight.
- * read   test aid: outputs [m_first, m_first + n) of every channel, all of them in the ring, -> host y_i16 / y_f32 [n_out][n] (either
+ * frame_f32  the same cut of the float32 ring into float32 frames, the same zero rules: d_audio device [n_out][180000] float, NULL =
+ *        the float staging audio (ft8rx_enqueue_batch_f32(h, ft8rx_staging_audio_f32(h), n_out) is the intended next call).  Also
+ *        refused, naming keep_f32, when the stream was opened without the float32 ring.
+ * read  test aid: outputs [m_first, m_first + n) of every channel, all of them in the ring, -> host y_i16 / y_f32 [n_out][n] (either
  *        may be NULL); synchronous.
  * info   ring capacities in samples, samples pushed per stream, m_produced. */
 int  ft8rx_ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_streams, int n_out, const int32_t* src,
                            const double* f_dial_hz, float gain, uint64_t n_origin, int keep_f32, double* f_mixed_hz);
 int  ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, uint64_t* m_produced);
+#define FT8RX_DDC_KEEP_F32_FRAMES 2
 int  ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16_t* d_audio);
+int  ft8rx_ddc_stream_frame_f32(ft8rx_handle* h, uint64_t m_first, int n_have, float* d_audio);
 int  ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first, int n, int16_t* y_i16, float* y_f32);
 int  ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced);
 int  ft8rx_ddc_stream_close(ft8rx_handle* h);
@@ -709,6 +730,8 @@ int  ft8rx_get_stage_times(ft8rx_handle* h, int* n, const char** names, float* m
 /* ---- stage entry points (parity tests; each mirrors one reference function) ---------------- */
 /* AudioIn.get_hop_spectrum x375 (receiver.py:288-293): grid [n][376][FT8RX_GRID_COLS] */
 int  ft8rx_spectrogram(ft8rx_handle* h, const int16_t* audio, int n_frames, float* grid);
+/* the same of float32 frames: the samples as they are, zeros before the frame start */
+int  ft8rx_spectrogram_f32(ft8rx_handle* h, const float* audio, int n_frames, float* grid);
 /* streaming mode: ONE call of AudioIn.get_hop_spectrum (receiver.py:288-293): the last 3840 int16 samples -> FT8RX_GRID_COLS dB values */
 int  ft8rx_hop_spectrum(ft8rx_handle* h, const int16_t* window3840, float* row);
 /* Receiver.search (receiver.py:338-367): per frame <= max_cands (f0,h0,score), sorted */
@@ -727,6 +750,8 @@ int  ft8rx_llr_grid(ft8rx_handle* h, const float* grid, int n_frames, int n, con
                     const int32_t* f0_idx, const int32_t* h0_idx, float* llr /*[n][174]*/, float* sd, int32_t* snr);
 /* AudioIn.get_cycle_spectrum (receiver.py:280-286): spec [n][FT8RX_SPEC_BINS] complex64 */
 int  ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int n_frames, float* spec);
+/* the same of float32 frames */
+int  ft8rx_cycle_spectrum_f32(ft8rx_handle* h, const float* audio, int n_frames, float* spec);
 /* Candidate._get_llr_fine (receiver.py:140-206) for n (frame,f0,h0) triples; sgrid [n][79][8] may be NULL.
  * ret[i]: 1 continue, 0 Costas gate failed, -1 sd gate failed */
 int  ft8rx_fine(ft8rx_handle* h, const float* spec, int n_frames, int n, const int32_t* frame,
@@ -798,6 +823,9 @@ int  ft8rx_merge_messages(ft8rx_message* out, int32_t* out_counts, int max_out, 
  * cfg.max_cands rules truncation out); n_threads / table / flags as for ft8rx_package_batch. */
 int  ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int n_frames, ft8rx_message* out, int max_msgs, int32_t* out_counts,
                            int n_threads, ft8rx_hashes* table, int32_t* flags);
+/* the same from float32 frames: ft8rx_decode_batch_f32 followed by ft8rx_package_batch */
+int  ft8rx_decode_messages_f32(ft8rx_handle* h, const float* audio, int n_frames, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                               int n_threads, ft8rx_hashes* table, int32_t* flags);
 /* the persistent call-hash table (databases.py:8-26 `call_hashes` + add_call_hashes) */
 ft8rx_hashes* ft8rx_hashes_create(void);
 void ft8rx_hashes_destroy(ft8rx_hashes* t);
@@ -809,6 +837,8 @@ int  ft8rx_hashes_size(const ft8rx_hashes* t);                       /* number o
 int  ft8rx_set_reject_log(const char* path);
 /* the handle's own device audio buffer ([max_frames][180000] int16) and a D2H copy helper (tests, tools) */
 int16_t* ft8rx_staging_audio(ft8rx_handle* h);
+/* ... and the one of float32 frames ([max_frames][180000] float), allocated on first use */
+float* ft8rx_staging_audio_f32(ft8rx_handle* h);
 int  ft8rx_copy_to_host(ft8rx_handle* h, void* dst, const void* d_src, uint64_t bytes);
 /* Asynchronous device -> page-locked-host copies on the handle's result-copy stream (the one stream no decode kernel waits behind; a
  * copy on any other stream of the process shares a hardware queue with a decode stream and holds its kernels back while it runs).
@@ -831,6 +861,10 @@ typedef struct {
  * (d_audio is a device pointer).  audio_f32_out (host, optional, [n_frames][180000]) receives the float32 residual. */
 int  ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int n_frames, ft8rx_subsig* sigs, const int32_t* counts,
                     int max_sigs, int refine, float* audio_f32_out);
+/* the same on device-resident float32 frames: the working copy is filled from d_audio without conversion and
+ * written back without rounding; everything between is ft8rx_subtract's, refine included */
+int  ft8rx_subtract_f32(ft8rx_handle* h, float* d_audio, int n_frames, ft8rx_subsig* sigs, const int32_t* counts,
+                        int max_sigs, int refine, float* audio_f32_out);
 /* refine = 0: the given (fHz, tsec) are used as they are (the reference's arithmetic).  refine = 1 (extension): before a signal is
  * subtracted its origin is re-estimated with the same signal model over all 79 symbols -- start sample within [-150, +20] ms and
  * frequency within [-1.75, +5.75] Hz of the given values -- and `sigs` is updated with the refined origins.  (The decoder's

@@ -31,6 +31,16 @@ PROTOTYPES = {
     "ft8rx_fetch_results_view": (INT, (PTR, INT) + _RECS),
     "ft8rx_results_to_device": (INT, (PTR, INT) + _RECS),
     "ft8rx_decode_messages": (INT, (PTR, PTR, INT) + _PKG),
+    # float32 frames: the twins of the entries above and below
+    "ft8rx_decode_batch_f32": (INT, (PTR, PTR, INT) + _RECS),
+    "ft8rx_enqueue_batch_f32": (INT, (PTR, PTR, INT)),
+    "ft8rx_enqueue_batch_host_f32": (INT, (PTR, PTR, INT)),
+    "ft8rx_decode_messages_f32": (INT, (PTR, PTR, INT) + _PKG),
+    "ft8rx_staging_audio_f32": (PTR, (PTR,)),
+    "ft8rx_spectrogram_f32": (INT, (PTR, PTR, INT, PTR)),
+    "ft8rx_cycle_spectrum_f32": (INT, (PTR, PTR, INT, PTR)),
+    "ft8rx_ddc_stream_frame_f32": (INT, (PTR, U64, INT, PTR)),
+    "ft8rx_subtract_f32": (INT, (PTR, PTR, INT, PTR, PTR, INT, INT, PTR)),
     # packed results
     "ft8rx_set_packed_output": (INT, (PTR, PTR, PTR, U64)),
     "ft8rx_packed_results": (INT, (PTR, PTR, PTR)),

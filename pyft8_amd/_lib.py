@@ -261,6 +261,25 @@ def _audio(audio, refusal):
     return audio
 
 
+def _audio_f32(audio, refusal):
+    """Host float frames -> C-contiguous float32 [n_frames, 180000]; float64 is rounded to float32 once, any
+    other dtype is refused (integers are the int16 path's)."""
+    audio = np.asarray(audio)
+    if audio.dtype not in (np.float32, np.float64):
+        raise Ft8rxError(refusal.format(shape=f"dtype {audio.dtype}"))
+    audio = np.ascontiguousarray(audio, np.float32)
+    if audio.ndim == 1:
+        audio = audio[None]
+    if audio.ndim != 2 or audio.shape[1] != NSAMP:
+        raise Ft8rxError(refusal.format(shape=audio.shape))
+    return audio
+
+
+def _keep_f32(keep_f32):
+    """keep_f32 of the stream opens: False / True, or 2 = the stream runs float frames (FT8RX_DDC_KEEP_F32_FRAMES)"""
+    return 2 if keep_f32 is not True and keep_f32 == 2 else (1 if keep_f32 else 0)
+
+
 def _words(bits):
     """77-bit words (Python ints) -> (msg_lo, msg_hi) uint64 arrays, as the records hold them."""
     return np.array([b & (2 ** 64 - 1) for b in bits], np.uint64), np.array([b >> 64 for b in bits], np.uint64)
@@ -417,6 +436,61 @@ class Handle:
         res = _package("decode_messages", self._L.ft8rx_decode_messages, [self._h, audio.ctypes.data, len(audio)], len(audio), max_msgs,
                        n_threads or None, table, chk=self._chk)
         return res if return_flags else res[:2]
+
+    # ---- float32 frames: the twins of the int16 entries around them
+    def decode_batch_f32(self, audio):
+        audio = _audio_f32(audio, f"audio must be float32 [n_frames, {NSAMP}] (15 s at 12 kHz); got {{shape}} -- see receiver.frames_from_ragged_f32")
+        if len(audio) < 1:
+            raise Ft8rxError("empty batch")
+        B = len(audio)
+        rec, cnt, ev, evc = self._alloc_out(B)
+        self._chk(self._L.ft8rx_decode_batch_f32(self._h, audio.ctypes.data, B, rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data),
+                  "ft8rx_decode_batch_f32")
+        return rec, cnt, ev, evc
+
+    def decode_messages_f32(self, audio, max_msgs=None, n_threads=None, table=None, return_flags=False):
+        """ft8rx_decode_messages_f32: decode_messages of float32 frames"""
+        refusal = f"audio must be [n<={self.max_frames}, {NSAMP}] float32, got {{shape}}"
+        audio = _audio_f32(audio, refusal)
+        if len(audio) > self.max_frames:
+            raise Ft8rxError(refusal.format(shape=audio.shape))
+        max_msgs = int(max_msgs or max(1, self.cfg.max_cands))
+        res = _package("decode_messages_f32", self._L.ft8rx_decode_messages_f32, [self._h, audio.ctypes.data, len(audio)], len(audio), max_msgs,
+                       n_threads or None, table, chk=self._chk)
+        return res if return_flags else res[:2]
+
+    def enqueue_f32(self, d_audio_ptr, B):
+        self._chk(self._L.ft8rx_enqueue_batch_f32(self._h, d_audio_ptr, int(B)), "ft8rx_enqueue_batch_f32")
+
+    def enqueue_host_f32(self, audio):
+        """enqueue_host of float32 frames (ft8rx_enqueue_batch_host_f32); the array stays alive and unchanged until the fetch"""
+        if audio.dtype != np.float32 or audio.ndim != 2 or audio.shape[1] != NSAMP or not audio.flags["C_CONTIGUOUS"]:
+            raise Ft8rxError(f"enqueue_host_f32: audio must be a C-contiguous float32 [n_frames, {NSAMP}] array")
+        self._chk(self._L.ft8rx_enqueue_batch_host_f32(self._h, audio.ctypes.data, int(audio.shape[0])), "ft8rx_enqueue_batch_host_f32")
+
+    def staging_ptr_f32(self):
+        return int(self._L.ft8rx_staging_audio_f32(self._h) or 0)
+
+    def download_audio_f32(self, d_ptr, n_frames):
+        out = np.empty((n_frames, NSAMP), np.float32)
+        self._chk(self._L.ft8rx_copy_to_host(self._h, out.ctypes.data, d_ptr, out.nbytes), "ft8rx_copy_to_host")
+        return out
+
+    def spectrogram_f32(self, audio):
+        audio = _audio_f32(audio, f"spectrogram_f32: audio must be float32 [n_frames, {NSAMP}], got {{shape}}")
+        g = np.empty((len(audio), GRID_ROWS, self.grid_cols), np.float32)
+        self._chk(self._L.ft8rx_spectrogram_f32(self._h, audio.ctypes.data, len(audio), g.ctypes.data), "ft8rx_spectrogram_f32")
+        return g
+
+    def cycle_spectrum_f32(self, audio):
+        audio = _audio_f32(audio, f"cycle_spectrum_f32: audio must be float32 [n_frames, {NSAMP}], got {{shape}}")
+        s = np.empty((len(audio), self.spec_bins), np.complex64)
+        self._chk(self._L.ft8rx_cycle_spectrum_f32(self._h, audio.ctypes.data, len(audio), s.ctypes.data), "ft8rx_cycle_spectrum_f32")
+        return s
+
+    def ddc_stream_frame_f32(self, m_first, n_have=NSAMP, d_audio_ptr=None):
+        """Gather outputs [m_first, m_first + n_have) of every channel out of the float32 ring into the float staging audio (or d_audio_ptr)."""
+        self._chk(self._L.ft8rx_ddc_stream_frame_f32(self._h, int(m_first) & 0xFFFFFFFFFFFFFFFF, int(n_have), d_audio_ptr), "ft8rx_ddc_stream_frame_f32")
 
     def enqueue(self, d_audio_ptr, B):
         self._chk(self._L.ft8rx_enqueue_batch(self._h, d_audio_ptr, int(B)), "ft8rx_enqueue_batch")
@@ -705,11 +779,12 @@ class Handle:
         self._chk(self._L.ft8rx_valid77_ext(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), int(mask), out.ctypes.data), "ft8rx_valid77_ext")
         return out
 
-    def subtract(self, d_audio_ptr, n_frames, signals, return_float=False, refine=False, return_origins=False):
+    def subtract(self, d_audio_ptr, n_frames, signals, return_float=False, refine=False, return_origins=False, float_frames=False):
         """Subtract decoded signals from device-resident int16 audio in place (ft8rx_subtract).
         signals: per frame a list of (tones79, fHz, tsec), subtracted in list order.  -> float32 residual if return_float.
         refine: 0 = as given (the reference's subtract_signal), 1 = re-estimate each origin first with full-rate scans, 2 = the same on
-        a decimated baseband copy (fast; what Receiver's multi-pass decode uses)."""
+        a decimated baseband copy (fast; what Receiver's multi-pass decode uses).  float_frames: d_audio_ptr holds float32 frames, which
+        are worked on and written back as they are (ft8rx_subtract_f32)."""
         B = int(n_frames)
         if isinstance(signals, tuple):          # (array [B, max_sigs] of SUBSIG_DTYPE, counts [B]) -- the fast path
             arr, cnt = signals
@@ -726,20 +801,22 @@ class Handle:
                     arr[f, i]["tones"] = np.asarray(tones, np.uint8)
                     arr[f, i]["fHz"], arr[f, i]["tsec"] = fHz, tsec
         out = np.empty((B, NSAMP), np.float32) if return_float else None
-        self._chk(self._L.ft8rx_subtract(self._h, d_audio_ptr, B, arr.ctypes.data, cnt.ctypes.data, ms, int(refine),
-                                         out.ctypes.data if return_float else None), "ft8rx_subtract")
+        entry = "ft8rx_subtract_f32" if float_frames else "ft8rx_subtract"
+        self._chk(getattr(self._L, entry)(self._h, d_audio_ptr, B, arr.ctypes.data, cnt.ctypes.data, ms, int(refine),
+                                          out.ctypes.data if return_float else None), entry)
         if return_origins:                 # (fHz, tsec) per signal after refinement
             return out, [[(float(arr[f, i]["fHz"]), float(arr[f, i]["tsec"])) for i in range(cnt[f])] for f in range(B)]
         return out
 
-    def ddc(self, samples, kind, rate, src, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
+    def ddc(self, samples, kind, rate, src, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None, d_f32_ptr=None):
         """ft8rx_ddc_host / ft8rx_ddc (DESIGN.md section 16): down-convert [n_streams][n] samples of `kind` (ddc.REAL_I16 .. ddc.IQ_F32;
         IQ as complex or (I, Q) pairs, ddc.pack) at `rate` Hz into len(src) frames in the staging buffer (staging_ptr, download_audio),
         output j = stream src[j] with the dial f_dial_hz[j] Hz from the stream's centre -> f_mixed_hz [n_out], the dials really mixed.
         want_float: -> (f_mixed_hz, y float32 [n_out, 180000]), the audio before rounding.  device / want_float: the samples go
         through a torch tensor and the device entry (ft8rx_ddc) instead of the library's own staging (ft8rx_ddc_host).  d_ptr, n: ONE
         stream of n samples that is on the device already (a raw address, what blank_in returns; `samples` is not looked at): the
-        device entry on it, queued and not waited for."""
+        device entry on it, queued and not waited for.  d_f32_ptr: a device address [n_out][180000] float32 that receives the audio before
+        rounding (float frames, DESIGN.md section 18: staging_ptr_f32()); the device entry, -> f_mixed_hz."""
         from . import ddc as _ddc
         if d_ptr is not None:
             src = np.ascontiguousarray(src, np.int32).reshape(-1)
@@ -748,7 +825,7 @@ class Handle:
                 raise Ft8rxError(f"ddc: one src and one f_dial_hz per output, got {len(src)} and {len(f)}")
             fm = np.zeros(len(src), np.float64)
             self._chk(self._L.ft8rx_ddc(self._h, int(d_ptr), int(kind), int(rate), 1, int(n), int(n), len(src), src.ctypes.data, f.ctypes.data,
-                                        float(gain), None, None, fm.ctypes.data), "ft8rx_ddc")
+                                        float(gain), None, d_f32_ptr, fm.ctypes.data), "ft8rx_ddc")
             return fm
         a, n_streams, n = _ddc.pack(samples, kind)
         src = np.ascontiguousarray(src, np.int32).reshape(-1)
@@ -757,7 +834,7 @@ class Handle:
             raise Ft8rxError(f"ddc: one src and one f_dial_hz per output, got {len(src)} and {len(f)}")
         fm = np.zeros(len(src), np.float64)
         args = (int(kind), int(rate), n_streams, n, n, len(src), src.ctypes.data, f.ctypes.data, float(gain))
-        if not (device or want_float):
+        if not (device or want_float or d_f32_ptr is not None):
             self._chk(self._L.ft8rx_ddc_host(self._h, a.ctypes.data, *args, fm.ctypes.data), "ft8rx_ddc_host")
             return fm
         import torch
@@ -765,7 +842,7 @@ class Handle:
         d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
         d_f32 = torch.empty((len(src), NSAMP), dtype=torch.float32, device=dev) if want_float else None
         torch.cuda.synchronize(dev)
-        self._chk(self._L.ft8rx_ddc(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), "ft8rx_ddc")
+        self._chk(self._L.ft8rx_ddc(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else d_f32_ptr, fm.ctypes.data), "ft8rx_ddc")
         self.sync()                                          # the tensors may go once the kernel has run
         return (fm, d_f32.cpu().numpy()) if want_float else fm
 
@@ -779,7 +856,7 @@ class Handle:
             raise Ft8rxError(f"ddc_stream_open: one src and one f_dial_hz per channel, got {len(src)} and {len(f)}")
         fm = np.zeros(len(src), np.float64)
         self._chk(self._L.ft8rx_ddc_stream_open(self._h, int(kind), int(rate), int(n_streams), len(src), src.ctypes.data, f.ctypes.data,
-                                                float(gain), int(n_origin), int(bool(keep_f32)), fm.ctypes.data), "ft8rx_ddc_stream_open")
+                                                float(gain), int(n_origin), _keep_f32(keep_f32), fm.ctypes.data), "ft8rx_ddc_stream_open")
         self._ds = (int(kind), int(n_streams), len(src))
         return fm
 
@@ -850,7 +927,7 @@ class Handle:
 
     # ---- the input pre-stages, written once: `name` is "ddc_wide" or "ddc_rat", the prefix of the C entries
     # (ft8rx_<name>*) and of the methods below, and the module that packs the samples of its kinds
-    def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr=None, n=None):
+    def _pre_oneshot(self, name, samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr=None, n=None, d_f32_ptr=None):
         if d_ptr is None:
             a, n = _pre_module(name).pack(samples, kind)
         f = np.ascontiguousarray(f_dial_hz, np.float64).reshape(-1)
@@ -859,10 +936,10 @@ class Handle:
         fm = np.zeros(len(f), np.float64)
         if d_ptr is not None:                                # on the device already: the device entry, queued and not waited for
             self._chk(getattr(self._L, f"ft8rx_{name}")(self._h, int(d_ptr), int(kind), int(rate), int(n), len(f), f.ctypes.data, float(gain),
-                                                        None, None, fm.ctypes.data), f"ft8rx_{name}")
+                                                        None, d_f32_ptr, fm.ctypes.data), f"ft8rx_{name}")
             return fm
         args = (int(kind), int(rate), n, len(f), f.ctypes.data, float(gain))
-        if not (device or want_float):
+        if not (device or want_float or d_f32_ptr is not None):
             self._chk(getattr(self._L, f"ft8rx_{name}_host")(self._h, a.ctypes.data, *args, fm.ctypes.data), f"ft8rx_{name}_host")
             return fm
         import torch
@@ -870,7 +947,7 @@ class Handle:
         d_in = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
         d_f32 = torch.empty((len(f), NSAMP), dtype=torch.float32, device=dev) if want_float else None
         torch.cuda.synchronize(dev)
-        self._chk(getattr(self._L, f"ft8rx_{name}")(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else None, fm.ctypes.data), f"ft8rx_{name}")
+        self._chk(getattr(self._L, f"ft8rx_{name}")(self._h, d_in.data_ptr(), *args, None, d_f32.data_ptr() if want_float else d_f32_ptr, fm.ctypes.data), f"ft8rx_{name}")
         self.sync()                                          # the tensors may go once the kernels have run
         return (fm, d_f32.cpu().numpy()) if want_float else fm
 
@@ -880,7 +957,7 @@ class Handle:
             raise Ft8rxError(f"{name}_stream_open: at least one f_dial_hz")
         fm = np.zeros(len(f), np.float64)
         self._chk(getattr(self._L, f"ft8rx_{name}_stream_open")(self._h, int(kind), int(rate), len(f), f.ctypes.data, float(gain), int(n_origin),
-                                                                int(bool(keep_f32)), fm.ctypes.data), f"ft8rx_{name}_stream_open")
+                                                                _keep_f32(keep_f32), fm.ctypes.data), f"ft8rx_{name}_stream_open")
         setattr(self, _PRE_FIELD[name], (int(kind), len(f)))
         self._ds = (3, len(f), len(f))                       # the stage behind: one IQ float32 stream per channel
         return fm
@@ -922,11 +999,11 @@ class Handle:
         self._ds = None
 
     # ---- wide pre-decimator (ft8rx_ddc_wide*): ONE stream at 240 kHz .. 129.6 MHz in front of the down-converter
-    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
+    def ddc_wide(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None, d_f32_ptr=None):
         """ft8rx_ddc_wide_host / ft8rx_ddc_wide: one stream of `kind` (ddc_wide.REAL_I16 .. ddc_wide.IQ_I8; forms of ddc_wide.pack) at
         `rate` Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
         [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        return self._pre_oneshot("ddc_wide", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n)
+        return self._pre_oneshot("ddc_wide", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n, d_f32_ptr)
 
     def ddc_wide_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
         """Open the wide stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the first
@@ -947,11 +1024,11 @@ class Handle:
         self._pre_close("ddc_wide")
 
     # ---- rational resampler (ft8rx_ddc_rat*): ONE stream at 44.1 kHz, 2.048 MS/s, ... in front of the down-converter
-    def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None):
+    def ddc_rat(self, samples, kind, rate, f_dial_hz, gain=1.0, want_float=False, device=False, d_ptr=None, n=None, d_f32_ptr=None):
         """ft8rx_ddc_rat_host / ft8rx_ddc_rat: one stream of `kind` (ddc_rat.REAL_I16 .. ddc_rat.IQ_I8; forms of ddc_rat.pack) at `rate`
         Hz into len(f_dial_hz) frames in the staging buffer -> f_mixed_hz [n_out].  want_float: -> (f_mixed_hz, y float32
         [n_out, 180000]).  device / want_float: through a torch tensor and the device entry, as Handle.ddc."""
-        return self._pre_oneshot("ddc_rat", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n)
+        return self._pre_oneshot("ddc_rat", samples, kind, rate, f_dial_hz, gain, want_float, device, d_ptr, n, d_f32_ptr)
 
     def ddc_rat_stream_open(self, kind, rate, f_dial_hz, gain=1.0, n_origin=0, keep_f32=False):
         """Open the rational stream: one input of `kind` at `rate` Hz feeds len(f_dial_hz) channels; n_origin = absolute index of the

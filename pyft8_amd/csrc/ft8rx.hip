@@ -197,6 +197,8 @@ struct ft8rx_handle {
     std::vector<Chunk> arena;        // scratch of the stage entry points (struct Scratch)
     int16_t* d_audio = nullptr;  // staging for host-pointer entry points
     int16_t* d_audio2 = nullptr; // second staging buffer (allocated on first use): ft8rx_enqueue_batch_host double-buffers the H2D copies
+    float* d_audio_f = nullptr;  // float32 frames (allocated on first use): the staging of the _f32 host entries ...
+    float* d_audio2_f = nullptr; // ... and the second buffer of ft8rx_enqueue_batch_host_f32
     hipStream_t h2d_s = nullptr; // host-to-device copies of the pipelined host entry: never queued behind kernels or result copies
     float* d_grid = nullptr;
     float* d_best_score = nullptr; int32_t* d_best_h0 = nullptr;
@@ -239,6 +241,7 @@ struct ft8rx_handle {
         int64_t n_origin = 0, pushed = 0, tiles = 0, cap = 0;
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
         float* d_grid = nullptr; int g_p0 = 0, g_rows = 0;
+        bool f32_frames = false;         // opened with keep_f32 = FT8RX_DDC_KEEP_F32_FRAMES: the grid stage reads d_f32
         hipEvent_t ev = nullptr;
     } ds;
     // input pre-stages (ft8rx_ddc_wide*, ft8rx_ddc_rat*; kernels/ddc_wide.hpp, kernels/ddc_rat.hpp).  One-shot: the
@@ -366,7 +369,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -396,6 +399,25 @@ static int need_staging(ft8rx_handle* h, bool second = false) {
     FirstUse F(h, g);
     F.dev(second ? &h->d_audio2 : &h->d_audio, (size_t)h->max_frames * FT8RX_NSAMP);
     return F.done();
+}
+// ... and the float32 frames' ([max_frames][180000] float: staging of the _f32 entry points, ft8rx_staging_audio_f32), 720 KB per frame
+static int need_staging_f32(ft8rx_handle* h, bool second = false) {
+    const WsGroup g = second ? WS_STAGING2_F32 : WS_STAGING_F32;
+    if (ws_ready(h, g)) return 0;
+    FirstUse F(h, g);
+    F.dev(second ? &h->d_audio2_f : &h->d_audio_f, (size_t)h->max_frames * FT8RX_NSAMP);
+    return F.done();
+}
+// The frames of a batch: int16 (sb = 2) or float32 (sb = 4) samples, on the device or on the host.  Only the two
+// kernels that read audio (launch_spectrogram, launch_cyc_a) and the copies look at sb.
+struct Frames {
+    const void* p; int sb;
+    Frames at(size_t frame) const { return Frames{(const char*)p + frame * FT8RX_NSAMP * (size_t)sb, sb}; }
+    size_t bytes(size_t n_frames) const { return n_frames * FT8RX_NSAMP * (size_t)sb; }
+};
+static int need_staging(ft8rx_handle* h, int sb, bool second) { return sb == 4 ? need_staging_f32(h, second) : need_staging(h, second); }
+static void* staging_of(ft8rx_handle* h, int sb, bool second) {
+    return sb == 4 ? (void*)(second ? h->d_audio2_f : h->d_audio_f) : (void*)(second ? h->d_audio2 : h->d_audio);
 }
 
 static void host_twiddle(int n, int count, std::vector<cpx>& w) {
@@ -826,14 +848,24 @@ static void launch_reports(ft8rx_handle* h, int B, const cpx* spec, const ft8rx_
     k_report<<<ladder_grid(h, B * c.max_cands), FINE_NT, 0, s>>>(spec, rec, rep, h->T, sh, wl);
 }
 
-static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
+// the two kernels of the chain that read audio, in the form of the frames' samples (B frames from a.p on)
+static void launch_spectrogram(int B, hipStream_t s, const Frames& a, float* grid, const Tables& T) {
+    if (a.sb == 4) k_spectrogram_f32<<<dim3(376, B), SPEC_NT, 0, s>>>((const float*)a.p, grid, T);
+    else ft8rx_ilp_spectrogram(B, s, (const int16_t*)a.p, grid, T);
+}
+static void launch_cyc_a(int B, hipStream_t s, const Frames& a, cpx* A, const Tables& T) {
+    if (a.sb == 4) k_cyc_a_f32<<<dim3(40, B), 256, 0, s>>>((const float*)a.p, A, T);
+    else k_cyc_a<<<dim3(40, B), 256, 0, s>>>((const int16_t*)a.p, A, T);
+}
+
+static void enqueue_chain(ft8rx_handle* h, const Frames& d_audio, int f0, int B, hipStream_t s, bool prof, int slot, int chunk) {
     const ResultSlot& sl = h->slots[slot];
     const bool weak = h->weak;                                     // the setting this batch was enqueued with
     const ft8rx_config cw = weak ? weak_config(h) : h->cfg;
     const ft8rx_config& c = weak ? cw : h->cfg;
     const size_t F = (size_t)f0;
     const int sh = cand_shift(c); const size_t S = (size_t)1 << sh, FS = F * S;        // candidate stride (ft8rx_create)
-    const int16_t* audio = d_audio + F * FT8RX_NSAMP;
+    const Frames audio = d_audio.at(F);
     float* grid = h->d_grid + F * FT8RX_GRID_ROWS * FT8RX_GRID_COLS;
     float* bs = h->d_best_score + F * NF0MAX; int32_t* bh = h->d_best_h0 + F * NF0MAX;
     ft8rx_record* rec = sl.rec + FS; int32_t* ncand = sl.ncand + F;
@@ -846,7 +878,7 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     WorkList wl[WL_N];
     for (int i = 0; i < WL_N; i++) { wl[i].items = h->d_work[i] + FS * WL_MULT(i); wl[i].count = wc + i; }
     STAGE("spectrogram");
-    ft8rx_ilp_spectrogram(B, s, audio, grid, h->T);
+    launch_spectrogram(B, s, audio, grid, h->T);
     STAGE("sync");
     launch_sync(grid, bs, bh, c, B, s, weak);
     STAGE("topk");
@@ -860,7 +892,7 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
     STAGE("select0");
     k_select0<<<(B * S + 255) / 256, 256, 0, s>>>(rec, ncand, att0, B, sh, wl[WL_FINE]);
     STAGE("cycle_fft");
-    k_cyc_a<<<dim3(40, B), 256, 0, s>>>(audio, A, h->T);
+    launch_cyc_a(B, s, audio, A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, s>>>(A, spec, h->T);
     STAGE("fine");
     launch_fine(h, c, weak, ladder_grid(h, B * c.max_cands), s, spec, rec, ncand, llr0, nullptr, nullptr, nullptr, nullptr, wl[WL_FINE],
@@ -936,7 +968,7 @@ static void enqueue_chain(ft8rx_handle* h, const int16_t* d_audio, int f0, int B
 // stage of it came from HBM (k_spectrogram 0.36 -> 0.42 ms per 256 frames, profiles/archive/r04_batch_sweep.txt).  Every workspace is indexed
 // by frame and the chunk's work-list counters are re-zeroed by each chain's k_topk, so consecutive sub-batches on one stream need
 // nothing but stream order.  Results do not depend on the partition (tests/test_gpu_parity.py: test_subbatch_partition_invariance).
-static void enqueue_chunk(ft8rx_handle* h, const int16_t* d_audio, int f0, int n, hipStream_t s, int slot, int chunk) {
+static void enqueue_chunk(ft8rx_handle* h, const Frames& d_audio, int f0, int n, hipStream_t s, int slot, int chunk) {
     const int sub = (h->sub_frames > 0 && h->sub_frames < n) ? h->sub_frames : n;
     for (int o = 0; o < n; o += sub) enqueue_chain(h, d_audio, f0 + o, (o + sub <= n) ? sub : n - o, s, false, slot, chunk);
 }
@@ -956,20 +988,20 @@ using batchplan::Entry;
 // Prologue: the result slot is taken (with both taken, the oldest unfetched batch is dropped), the per-batch settings are consumed,
 // a host entry gets its staging buffer (*stage; a pipelined one waits for that buffer's last reader), and the chunk streams of a
 // chunked batch are created on first use
-static int batch_begin(ft8rx_handle* h, Entry e, int B, int slot, bool chunked, int16_t** stage) {
+static int batch_begin(ft8rx_handle* h, Entry e, int B, int slot, bool chunked, int sb, void** stage) {
     ResultSlot& sl = h->slots[slot];
     h->pnames.clear();
     // (first use of a staging buffer comes before anything of the handle changes: a failed one leaves it as it was)
-    if (e != batchplan::DEVICE && need_staging(h)) return -2;
-    if (e == batchplan::HOST_PIPELINED && slot == 1 && need_staging(h, true)) return -2;
+    if (e != batchplan::DEVICE && need_staging(h, sb, false)) return -2;
+    if (e == batchplan::HOST_PIPELINED && slot == 1 && need_staging(h, sb, true)) return -2;
     if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
     if (h->rc_armed && B != h->rc_frames) { set_err(h, "recall entries were set for %d frames, the batch has %d", h->rc_frames, B); return -1; }
     sl.recall = h->rc_armed;                     // ft8rx_set_recall: consumed by this batch
     h->rc_armed = false;
     sl.reports = h->reports;                     // ft8rx_set_reports: the setting this batch is enqueued with
-    *stage = h->d_audio;
+    *stage = staging_of(h, sb, false);
     if (e == batchplan::HOST_PIPELINED) {
-        *stage = slot ? h->d_audio2 : h->d_audio;
+        *stage = staging_of(h, sb, slot != 0);
         HIPCHK(h, hipStreamWaitEvent(h->h2d_s, sl.ev_comp, 0));             // the kernels that last read this staging buffer are done
     }
     for (int i = 1; i < h->n_streams && chunked; i++) if (!h->sub[i - 1]) {
@@ -982,14 +1014,14 @@ static int batch_begin(ft8rx_handle* h, Entry e, int B, int slot, bool chunked, 
 // Submission: the plan's chunks, chunk k on stream k % n_streams (stream 0 = the main stream).  audio: on the device for Entry
 // DEVICE, else on the host and copied to `stage` first, on `cs`.  The mode decides what precedes the chunks, what each chunk waits
 // for, whether an empty chunk is skipped, and what follows them.
-static int batch_submit(ft8rx_handle* h, const BatchPlan& plan, Entry e, int slot, const int16_t* audio, int16_t* stage) {
+static int batch_submit(ft8rx_handle* h, const BatchPlan& plan, Entry e, int slot, const Frames& audio, void* stage) {
     ResultSlot& sl = h->slots[slot];
     const bool host = e != batchplan::DEVICE;
-    const int16_t* d_audio = host ? stage : audio; const int16_t* host_audio = host ? audio : nullptr;
+    const Frames d_audio = host ? Frames{stage, audio.sb} : audio; const char* host_audio = host ? (const char*)audio.p : nullptr;
     const int ns = h->n_streams, nc = plan.nc, B = plan.cb[nc];
     const bool free_run = plan.mode == batchplan::FREE_RUN, pipelined = e == batchplan::HOST_PIPELINED, sync_host = e == batchplan::HOST_SYNC;
     hipStream_t cs = pipelined ? h->h2d_s : h->copy_s;
-    const size_t frame_bytes = sizeof(int16_t) * (size_t)FT8RX_NSAMP;
+    const size_t frame_bytes = audio.bytes(1);                 // host copies are sized by the sample bytes
     auto chunk_stream = [&](int k) { const int i = k % ns; return i == 0 ? h->stream : h->sub[i - 1]; };
     if (free_run) {
         for (int i = 0; i < ns; i++) for (int k = 0; k < 2; k++)
@@ -1031,7 +1063,7 @@ static int batch_submit(ft8rx_handle* h, const BatchPlan& plan, Entry e, int slo
             HIPCHK(h, hipStreamWaitEvent(s, sl.ev_done, 0));                // the slot's previous results have left the device
             if (pipelined) HIPCHK(h, hipStreamWaitEvent(s, h->ev_chunk[0], 0));
         } else if (sync_host) {
-            HIPCHK(h, hipMemcpyAsync(stage + (size_t)f0 * FT8RX_NSAMP, host_audio + (size_t)f0 * FT8RX_NSAMP, frame_bytes * n, hipMemcpyHostToDevice, cs));
+            HIPCHK(h, hipMemcpyAsync((char*)stage + frame_bytes * f0, host_audio + frame_bytes * f0, frame_bytes * n, hipMemcpyHostToDevice, cs));
             HIPCHK(h, hipEventRecord(h->ev_chunk[k], cs));
             HIPCHK(h, hipStreamWaitEvent(s, h->ev_chunk[k], 0));
         }
@@ -1091,12 +1123,12 @@ static int batch_finish(ft8rx_handle* h, int slot, int B, hipStream_t fin) {
 }
 
 // audio: on the device for Entry DEVICE, else on the host
-static int launch_batch(ft8rx_handle* h, Entry e, const int16_t* audio, int B) {
+static int launch_batch(ft8rx_handle* h, Entry e, const Frames& audio, int B) {
     HIPCHK(h, hipSetDevice(h->device));
     const BatchPlan plan = batchplan::plan_batch(B, h->n_streams, h->profiling, e);
     const int slot = h->slot_enq;
-    int16_t* stage = nullptr;
-    if (const int rc = batch_begin(h, e, B, slot, plan.mode != batchplan::SINGLE, &stage)) return rc;
+    void* stage = nullptr;
+    if (const int rc = batch_begin(h, e, B, slot, plan.mode != batchplan::SINGLE, audio.sb, &stage)) return rc;
     if (const int rc = batch_submit(h, plan, e, slot, audio, stage)) return rc;
     HIPCHK(h, hipGetLastError());
     return batch_finish(h, slot, B, plan.mode == batchplan::FREE_RUN ? h->copy_s : h->stream);
@@ -1119,13 +1151,32 @@ static void fetch_events(ResultSlot& sl) {
 int ft8rx_enqueue_batch(ft8rx_handle* h, const int16_t* d_audio, int B) {
     if (!h || !d_audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    return launch_batch(h, batchplan::DEVICE, d_audio, B);
+    return launch_batch(h, batchplan::DEVICE, Frames{d_audio, 2}, B);
 }
 
 int ft8rx_enqueue_batch_host(ft8rx_handle* h, const int16_t* audio, int B) {
     if (!h || !audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch_host: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    return launch_batch(h, batchplan::HOST_PIPELINED, audio, B);
+    return launch_batch(h, batchplan::HOST_PIPELINED, Frames{audio, 2}, B);
+}
+
+// float32 frames: the same plan, chunks, slots and streams; the kernels load sample pairs as 8-byte words
+static bool f32_aligned(ft8rx_handle* h, const char* who, const float* d_audio) {
+    if (((uintptr_t)d_audio % 8) == 0) return true;
+    set_err(h, "%s: d_audio is not aligned to 8 bytes (a pair of float32 samples)", who);
+    return false;
+}
+int ft8rx_enqueue_batch_f32(ft8rx_handle* h, const float* d_audio, int B) {
+    if (!h || !d_audio) return -1;
+    if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch_f32: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
+    if (!f32_aligned(h, "ft8rx_enqueue_batch_f32", d_audio)) return -1;
+    return launch_batch(h, batchplan::DEVICE, Frames{d_audio, 4}, B);
+}
+
+int ft8rx_enqueue_batch_host_f32(ft8rx_handle* h, const float* audio, int B) {
+    if (!h || !audio) return -1;
+    if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_enqueue_batch_host_f32: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
+    return launch_batch(h, batchplan::HOST_PIPELINED, Frames{audio, 4}, B);
 }
 
 int ft8rx_set_streams(ft8rx_handle* h, int n) { if (!h || n < 1 || n > batchplan::MAX_STREAMS) return -1; h->n_streams = n; return 0; }
@@ -1604,6 +1655,7 @@ static int ddc_stream_open(ft8rx_handle* h, int kind, int32_t rate_hz, int n_str
     if (e != hipSuccess) { set_err(h, "ft8rx_ddc_stream_open: %s", hipGetErrorString(e)); ddc_stream_release(h); return -2; }
     s.fmt = fmt; s.D = D; s.rate = rate_hz; s.n_streams = n_streams; s.n_out = n_out; s.cap = (int64_t)cap;
     s.scale = gain * sf_real_gain(fmt);
+    s.f32_frames = keep_f32 == FT8RX_DDC_KEEP_F32_FRAMES;
     s.n_origin = (int64_t)n_origin; s.pushed = 0; s.tiles = s.n_origin / (DDC_TO * D);
     s.open = true;
     return 0;
@@ -1651,9 +1703,13 @@ static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
             const int64_t m_origin = s.n_origin / s.D;
             const ddcgrid::Hops hp = ddcgrid::completed(s.tiles * DDC_TO, done * DDC_TO, s.g_p0, m_origin, s.g_rows);
             if (hp.end > hp.first) {
-                k_grid_stream<<<dim3((unsigned)(hp.end - hp.first), (unsigned)s.n_out), SPEC_NT, 0, h->stream>>>(
-                    s.d_out, (int)ddcring::OUT_RING, (int)ddcgrid::window_slot(hp.first, s.g_p0), (int)ddcgrid::zero_prefix(hp.first, s.g_p0, m_origin),
-                    s.d_grid, s.g_rows, (int)ddcgrid::row_slot(hp.first, s.g_rows), h->T);
+                const dim3 g((unsigned)(hp.end - hp.first), (unsigned)s.n_out);
+                const int slot0 = (int)ddcgrid::window_slot(hp.first, s.g_p0), nz0 = (int)ddcgrid::zero_prefix(hp.first, s.g_p0, m_origin);
+                const int row0 = (int)ddcgrid::row_slot(hp.first, s.g_rows);
+                if (s.f32_frames)       // a stream of float frames: the rows of the unrounded ring
+                    k_grid_stream<SpecLoadRingF32><<<g, SPEC_NT, 0, h->stream>>>(s.d_f32, (int)ddcring::OUT_RING, slot0, nz0, s.d_grid, s.g_rows, row0, h->T);
+                else
+                    k_grid_stream<SpecLoadRing><<<g, SPEC_NT, 0, h->stream>>>(s.d_out, (int)ddcring::OUT_RING, slot0, nz0, s.d_grid, s.g_rows, row0, h->T);
                 HIPCHK(h, hipGetLastError());
             }
         }
@@ -1663,25 +1719,35 @@ static int ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
     return 0;
 }
 
-int ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first_u, int n_have, int16_t* d_audio) {
+// the two frame entries: the int16 ring into int16 frames, or (f32) the float32 ring into float32 frames; d_audio NULL = the staging buffer
+static int ddc_stream_frame(ft8rx_handle* h, const char* who, uint64_t m_first_u, int n_have, void* d_audio, bool f32) {
     if (!h) return -1;
     ft8rx_handle::DdcStream& s = h->ds;
-    if (!s.open) { set_err(h, "ft8rx_ddc_stream_frame: no stream is open (ft8rx_ddc_stream_open)"); return -1; }
-    if (n_have < 0 || n_have > FT8RX_NSAMP) { set_err(h, "ft8rx_ddc_stream_frame: n_have %d outside [0, %d]", n_have, FT8RX_NSAMP); return -1; }
+    if (!s.open) { set_err(h, "%s: no stream is open (ft8rx_ddc_stream_open)", who); return -1; }
+    if (f32 && !s.d_f32) { set_err(h, "%s: the stream was opened without the float32 ring (keep_f32)", who); return -1; }
+    if (n_have < 0 || n_have > FT8RX_NSAMP) { set_err(h, "%s: n_have %d outside [0, %d]", who, n_have, FT8RX_NSAMP); return -1; }
     const int64_t m_first = (int64_t)m_first_u;          // two's complement: a negative index lies before index 0
-    if (m_first < -((int64_t)1 << 62) || m_first > ((int64_t)1 << 62)) { set_err(h, "ft8rx_ddc_stream_frame: m_first out of range"); return -1; }
+    if (m_first < -((int64_t)1 << 62) || m_first > ((int64_t)1 << 62)) { set_err(h, "%s: m_first out of range", who); return -1; }
     const int64_t m_origin = s.n_origin / s.D, m_done = s.tiles * DDC_TO;
     if (!ddcring::held(m_first, n_have, m_origin, m_done).ok) {
-        set_err(h, "ft8rx_ddc_stream_frame: outputs from %lld on have left the ring (it holds %lld .. %lld)", (long long)(m_first > m_origin ? m_first : m_origin),
+        set_err(h, "%s: outputs from %lld on have left the ring (it holds %lld .. %lld)", who, (long long)(m_first > m_origin ? m_first : m_origin),
                 (long long)(m_done - ddcring::OUT_RING), (long long)m_done);
         return -1;
     }
+    if (f32 && ((uintptr_t)d_audio % sizeof(float)) != 0) { set_err(h, "%s: d_audio is not aligned to a sample", who); return -1; }
     ENTER(h);                                            // a batch in flight may still read the staging audio
-    if (!d_audio) { if (need_staging(h)) return -2; d_audio = h->d_audio; }
-    k_ddc_gather<<<dim3((FT8RX_NSAMP + 255) / 256, (unsigned)s.n_out), 256, 0, h->stream>>>(s.d_out, (int)ddcring::OUT_RING, (long long)m_first, n_have,
-                                                                                          (long long)m_origin, (long long)m_done, d_audio);
+    if (!d_audio) { if (need_staging(h, f32 ? 4 : 2, false)) return -2; d_audio = staging_of(h, f32 ? 4 : 2, false); }
+    const dim3 g((FT8RX_NSAMP + 255) / 256, (unsigned)s.n_out);
+    if (f32) k_ddc_gather_f32<<<g, 256, 0, h->stream>>>(s.d_f32, (int)ddcring::OUT_RING, (long long)m_first, n_have, (long long)m_origin, (long long)m_done, (float*)d_audio);
+    else k_ddc_gather<<<g, 256, 0, h->stream>>>(s.d_out, (int)ddcring::OUT_RING, (long long)m_first, n_have, (long long)m_origin, (long long)m_done, (int16_t*)d_audio);
     HIPCHK(h, hipGetLastError());
     return 0;
+}
+int ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16_t* d_audio) {
+    return ddc_stream_frame(h, "ft8rx_ddc_stream_frame", m_first, n_have, d_audio, false);
+}
+int ft8rx_ddc_stream_frame_f32(ft8rx_handle* h, uint64_t m_first, int n_have, float* d_audio) {
+    return ddc_stream_frame(h, "ft8rx_ddc_stream_frame_f32", m_first, n_have, d_audio, true);
 }
 
 int ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first_u, int n, int16_t* y_i16, float* y_f32) {
@@ -2734,9 +2800,9 @@ int ft8rx_results_to_device(ft8rx_handle* h, int B, ft8rx_record* d_records, int
 }
 
 // the synchronous host entries: nothing older is kept, and the audio is staged in the handle's own buffer
-static int launch_batch_sync(ft8rx_handle* h, const int16_t* audio, int B) {
+static int launch_batch_sync(ft8rx_handle* h, const Frames& audio, int B) {
     h->inflight = 0; h->slot_fetch = h->slot_enq;
-    if (need_staging(h)) return -2;
+    if (need_staging(h, audio.sb, false)) return -2;
     return launch_batch(h, batchplan::HOST_SYNC, audio, B);
 }
 
@@ -2744,17 +2810,24 @@ int ft8rx_decode_batch(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_recor
                        ft8rx_event* events, int32_t* event_counts) {
     if (!h || !audio) return -1;
     if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_decode_batch: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
-    if (const int rc = launch_batch_sync(h, audio, B)) return rc;
+    if (const int rc = launch_batch_sync(h, Frames{audio, 2}, B)) return rc;
+    return ft8rx_fetch_results(h, B, records, counts, events, event_counts);
+}
+int ft8rx_decode_batch_f32(ft8rx_handle* h, const float* audio, int B, ft8rx_record* records, int32_t* counts,
+                           ft8rx_event* events, int32_t* event_counts) {
+    if (!h || !audio) return -1;
+    if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_decode_batch_f32: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
+    if (const int rc = launch_batch_sync(h, Frames{audio, 4}, B)) return rc;
     return ft8rx_fetch_results(h, B, records, counts, events, event_counts);
 }
 
 // One call from host audio to rendered messages: ft8rx_decode_batch + ft8rx_package_batch without the intermediate copies (the
 // packager reads the handle's page-locked result buffers in place).
-int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_message* out, int max_msgs, int32_t* out_counts,
-                          int n_threads, ft8rx_hashes* table, int32_t* flags) {
-    if (!h || !audio || !out || !out_counts) return -1;
-    if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "ft8rx_decode_messages: bad n_frames / max_msgs"); return -1; }
-    if (refuse_conflict(h, "ft8rx_decode_messages", optins::DECODE_MESSAGES,
+static int decode_messages(ft8rx_handle* h, const char* who, const Frames& audio, int B, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                           int n_threads, ft8rx_hashes* table, int32_t* flags) {
+    if (!h || !audio.p || !out || !out_counts) return -1;
+    if (B < 1 || B > h->max_frames || max_msgs < 1) { set_err(h, "%s: bad n_frames / max_msgs", who); return -1; }
+    if (refuse_conflict(h, who, optins::DECODE_MESSAGES,
                         " (ft8rx_message rows cannot carry it); use ft8rx_decode_batch with ft8rx_package_batch_ext / ft8rx_fetch_recall")) return -1;
     int rc = launch_batch_sync(h, audio, B);
     if (rc) return rc;
@@ -2763,20 +2836,37 @@ int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_me
     if (rc) return rc;
     return hostmsg::package_batch(rec, cnt, ev, evc, B, h->cfg.max_cands, out, max_msgs, out_counts, n_threads, table ? &table->H : nullptr, flags);
 }
+int ft8rx_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                          int n_threads, ft8rx_hashes* table, int32_t* flags) {
+    return decode_messages(h, "ft8rx_decode_messages", Frames{audio, 2}, B, out, max_msgs, out_counts, n_threads, table, flags);
+}
+int ft8rx_decode_messages_f32(ft8rx_handle* h, const float* audio, int B, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                              int n_threads, ft8rx_hashes* table, int32_t* flags) {
+    return decode_messages(h, "ft8rx_decode_messages_f32", Frames{audio, 4}, B, out, max_msgs, out_counts, n_threads, table, flags);
+}
 
 // ---------------------------------------------------------------------------- stage entry points
 #define NEED(p) do { if (!(p)) { set_err(h, "scratch allocation/copy failed (%s:%d)", __FILE__, __LINE__); return -2; } } while (0)
 
-int ft8rx_spectrogram(ft8rx_handle* h, const int16_t* audio, int B, float* grid) {
-    if (!h || !audio || !grid || B < 1 || B > h->max_frames) return -1;
+// host frames -> the staging buffer of their sample form (*d: the frames there)
+static int stage_frames(ft8rx_handle* h, const Frames& audio, int B, Frames* d) {
+    if (need_staging(h, audio.sb, false)) return -2;
+    *d = Frames{staging_of(h, audio.sb, false), audio.sb};
+    HIPCHK(h, hipMemcpy(const_cast<void*>(d->p), audio.p, audio.bytes((size_t)B), hipMemcpyHostToDevice));
+    return 0;
+}
+static int spectrogram_entry(ft8rx_handle* h, const Frames& audio, int B, float* grid) {
+    if (!h || !audio.p || !grid || B < 1 || B > h->max_frames) return -1;
     ENTER(h);
-    if (need_staging(h)) return -2;
-    HIPCHK(h, hipMemcpy(h->d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_NSAMP, hipMemcpyHostToDevice));
-    ft8rx_ilp_spectrogram(B, h->stream, h->d_audio, h->d_grid, h->T);
+    Frames d;
+    if (const int rc = stage_frames(h, audio, B, &d)) return rc;
+    launch_spectrogram(B, h->stream, d, h->d_grid, h->T);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(grid, h->d_grid, sizeof(float) * (size_t)B * FT8RX_GRID_ROWS * FT8RX_GRID_COLS, hipMemcpyDeviceToHost));
     return 0;
 }
+int ft8rx_spectrogram(ft8rx_handle* h, const int16_t* audio, int B, float* grid) { return spectrogram_entry(h, Frames{audio, 2}, B, grid); }
+int ft8rx_spectrogram_f32(ft8rx_handle* h, const float* audio, int B, float* grid) { return spectrogram_entry(h, Frames{audio, 4}, B, grid); }
 
 int ft8rx_hop_spectrum(ft8rx_handle* h, const int16_t* window3840, float* row) {
     if (!h || !window3840 || !row) return -1;
@@ -2861,17 +2951,19 @@ int ft8rx_llr_grid(ft8rx_handle* h, const float* grid, int B, int n, const int32
     return 0;
 }
 
-int ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int B, float* spec) {
-    if (!h || !audio || !spec || B < 1 || B > h->max_frames) return -1;
+static int cycle_spectrum_entry(ft8rx_handle* h, const Frames& audio, int B, float* spec) {
+    if (!h || !audio.p || !spec || B < 1 || B > h->max_frames) return -1;
     ENTER(h);
-    if (need_staging(h)) return -2;
-    HIPCHK(h, hipMemcpy(h->d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_NSAMP, hipMemcpyHostToDevice));
-    k_cyc_a<<<dim3(40, B), 256, 0, h->stream>>>(h->d_audio, h->d_A, h->T);
+    Frames d;
+    if (const int rc = stage_frames(h, audio, B, &d)) return rc;
+    launch_cyc_a(B, h->stream, d, h->d_A, h->T);
     k_cyc_bc<<<dim3(CYC_BC_GRID, B), 256, 0, h->stream>>>(h->d_A, h->d_spec, h->T);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(spec, h->d_spec, sizeof(cpx) * (size_t)B * FT8RX_SPEC_BINS, hipMemcpyDeviceToHost));
     return 0;
 }
+int ft8rx_cycle_spectrum(ft8rx_handle* h, const int16_t* audio, int B, float* spec) { return cycle_spectrum_entry(h, Frames{audio, 2}, B, spec); }
+int ft8rx_cycle_spectrum_f32(ft8rx_handle* h, const float* audio, int B, float* spec) { return cycle_spectrum_entry(h, Frames{audio, 4}, B, spec); }
 
 static int fine_probe(ft8rx_handle* h, const float* spec, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
                       int32_t* ret, int32_t* ttweak, int32_t* ftweak, int32_t* nsync, float* llr, float* sd, int32_t* snr, float* sgrid, bool weak) {
@@ -3108,6 +3200,10 @@ int16_t* ft8rx_staging_audio(ft8rx_handle* h) {
     if (!h || hipSetDevice(h->device) != hipSuccess || need_staging(h)) return nullptr;
     return h->d_audio;
 }
+float* ft8rx_staging_audio_f32(ft8rx_handle* h) {
+    if (!h || hipSetDevice(h->device) != hipSuccess || need_staging_f32(h)) return nullptr;
+    return h->d_audio_f;
+}
 
 // Asynchronous D2H copies for a consumer of device-side results (the gather on rank `dst`, pyft8_amd/distributed.py), on the handle's
 // RESULT-COPY stream: the one stream of the handle no decode kernel ever waits behind.  The runtime maps streams onto four hardware
@@ -3231,10 +3327,12 @@ static void sub_apply_fullrate(ft8rx_handle* h, int B, const SubSel& sel, const 
     k_sub_apply<<<dim3(SUB_GRIDX, B), 256, 0, h->stream>>>(h->d_wf, sel, T, h->d_part);
 }
 
-int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
-                   int refine, float* audio_f32_out) {
-    if (!h || !d_audio || !sigs || !counts) return -1;
-    if (B < 1 || B > h->max_frames || max_sigs < 1 || max_sigs > 256 || refine < 0 || refine > 3) { set_err(h, "ft8rx_subtract: bad n_frames / max_sigs / refine"); return -1; }
+// the two entries: int16 frames (converted into the float32 working copy and rounded back), or float32 frames (d_f32: copied into the
+// working copy and back as they are); everything between those two steps is the same
+static int subtract_run(ft8rx_handle* h, const char* who, int16_t* d_audio, float* d_f32, int B, ft8rx_subsig* sigs, const int32_t* counts,
+                        int max_sigs, int refine, float* audio_f32_out) {
+    if (!h || (!d_audio && !d_f32) || !sigs || !counts) return -1;
+    if (B < 1 || B > h->max_frames || max_sigs < 1 || max_sigs > 256 || refine < 0 || refine > 3) { set_err(h, "%s: bad n_frames / max_sigs / refine", who); return -1; }
     ENTER(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (subtract_workspaces(h, 0)) return -2;           // the base group; the groups of refine 2 / 3 follow the audio's conversion, below
@@ -3245,13 +3343,14 @@ int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs,
     }
     int nmax = 0;
     for (int f = 0; f < B; f++) {
-        if (counts[f] < 0 || counts[f] > max_sigs) { set_err(h, "ft8rx_subtract: counts[%d] = %d outside [0, %d]", f, counts[f], max_sigs); return -1; }
+        if (counts[f] < 0 || counts[f] > max_sigs) { set_err(h, "%s: counts[%d] = %d outside [0, %d]", who, f, counts[f], max_sigs); return -1; }
         if (counts[f] > nmax) nmax = counts[f];
     }
     HIPCHK(h, hipMemcpyAsync(h->d_sigs, sigs, sizeof(ft8rx_subsig) * (size_t)B * max_sigs, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_sigcnt, counts, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
     const size_t n = (size_t)B * FT8RX_NSAMP;
-    k_sub_to_f32<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(d_audio, h->d_wf, n);
+    if (d_f32) HIPCHK(h, hipMemcpyAsync(h->d_wf, d_f32, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
+    else k_sub_to_f32<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(d_audio, h->d_wf, n);
     if (subtract_workspaces(h, refine)) return -2;
     const SubTables T{h->d_pulse, h->d_pc};
     Tables Tones = h->T;                                     // refine = 3: the experiment's slices have no edge tapers
@@ -3275,12 +3374,24 @@ int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs,
         }
         sub_apply_fullrate(h, B, sel, T);
     }
-    k_sub_to_i16<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->d_wf, d_audio, n);
+    if (d_f32) HIPCHK(h, hipMemcpyAsync(d_f32, h->d_wf, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
+    else k_sub_to_i16<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->d_wf, d_audio, n);
     HIPCHK(h, hipGetLastError());
     if (audio_f32_out) HIPCHK(h, hipMemcpyAsync(audio_f32_out, h->d_wf, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
     if (refine) HIPCHK(h, hipMemcpyAsync(sigs, h->d_sigs, sizeof(ft8rx_subsig) * (size_t)B * max_sigs, hipMemcpyDeviceToHost, h->stream));   // the refined origins
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+int ft8rx_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
+                   int refine, float* audio_f32_out) {
+    if (!d_audio) return -1;
+    return subtract_run(h, "ft8rx_subtract", d_audio, nullptr, B, sigs, counts, max_sigs, refine, audio_f32_out);
+}
+int ft8rx_subtract_f32(ft8rx_handle* h, float* d_audio, int B, ft8rx_subsig* sigs, const int32_t* counts, int max_sigs,
+                       int refine, float* audio_f32_out) {
+    if (!d_audio) return -1;
+    if (h && ((uintptr_t)d_audio % sizeof(float)) != 0) { set_err(h, "ft8rx_subtract_f32: d_audio is not aligned to a sample"); return -1; }
+    return subtract_run(h, "ft8rx_subtract_f32", nullptr, d_audio, B, sigs, counts, max_sigs, refine, audio_f32_out);
 }
 
 int ft8rx_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n, uint8_t* tones) {

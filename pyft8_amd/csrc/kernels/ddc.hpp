@@ -206,12 +206,22 @@ __global__ __launch_bounds__(DDC_NT) void k_ddc_stream(const void* __restrict__ 
 
 // ft8rx_ddc_stream_frame: frame j position p = output m_first + p of channel j out of its ring; zero from n_have on and where the
 // stream has no output (before m_origin, from m_done on)
-__global__ __launch_bounds__(256) void k_ddc_gather(const int16_t* __restrict__ ring, int ring_len, long long m_first, int n_have,
-                                                    long long m_origin, long long m_done, int16_t* __restrict__ audio) {
+template <class S>
+FT8_DEV void ddc_gather(const S* __restrict__ ring, int ring_len, long long m_first, int n_have, long long m_origin, long long m_done,
+                        S* __restrict__ audio) {
     const int p = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (p >= FT8RX_NSAMP) return;
     const long long m = m_first + p;
-    int16_t v = 0;
+    S v = 0;
     if (p < n_have && m >= m_origin && m < m_done) v = ring[(size_t)j * ring_len + (size_t)(m % ring_len)];
     audio[(size_t)j * FT8RX_NSAMP + p] = v;
+}
+__global__ __launch_bounds__(256) void k_ddc_gather(const int16_t* __restrict__ ring, int ring_len, long long m_first, int n_have,
+                                                    long long m_origin, long long m_done, int16_t* __restrict__ audio) {
+    ddc_gather(ring, ring_len, m_first, n_have, m_origin, m_done, audio);
+}
+// ft8rx_ddc_stream_frame_f32: the same cut of the float32 output ring, the same zero rules
+__global__ __launch_bounds__(256) void k_ddc_gather_f32(const float* __restrict__ ring, int ring_len, long long m_first, int n_have,
+                                                        long long m_origin, long long m_done, float* __restrict__ audio) {
+    ddc_gather(ring, ring_len, m_first, n_have, m_origin, m_done, audio);
 }

@@ -1,7 +1,8 @@
 // spectrogram.hpp -- K1: 375-hop dB spectrogram (receiver.py:288-306)
 // Part of libft8rx.so.  The arithmetic of a row, spectrogram_hop, is shared device code of both translation units; k_spectrogram /
 // k_hop_spectrum are built in the second one only (ft8rx_ilp.hip, ILP scheduling: FT8RX_ILP_UNIT) and launched through ilp_launch.hpp;
-// k_fill_row0 and k_grid_stream (rows off the streaming down-converter's output ring) belong to the main unit.
+// k_fill_row0, k_grid_stream (rows off the streaming down-converter's output ring) and k_spectrogram_f32 (float32
+// frames) belong to the main unit.
 #ifndef FT8RX_SPECTROGRAM_HPP
 #define FT8RX_SPECTROGRAM_HPP
 
@@ -12,19 +13,31 @@
 //   [4,4]  120 groups of 16 (one per thread), twiddles from the LDS table w240[t] = W1920[8 t],
 //   [5,3]  128 groups of 15 (one per thread), compile-time twiddles,
 // then the real-FFT split and 20 log10|.|.
-// Where the samples come from is the caller's: load(m) -> samples 2 m (low half) and 2 m + 1 (high half) of the window as int16 bit
-// patterns, m = 0 .. 1919 (SpecLoadFrame: a frame in memory; SpecLoadRing: the down-converter's output ring).
+// Where the samples come from is the caller's: load(m) -> samples 2 m (.x) and 2 m + 1 (.y) of the window as floats, m = 0 .. 1919
+// (SpecLoadFrame / SpecLoadFrameF32: an int16 / float32 frame in memory; SpecLoadRing / SpecLoadRingF32: the down-converter's output
+// rings).  The int16 loaders convert exactly, (float)(int16_t); the float32 ones hand the samples on as they are.
 #define SPEC_NT 128
 // a[base .. base + 3840) of an int16 array, base even: one aligned pair per load; zeros where the index is negative
 struct SpecLoadFrame {
     const int16_t* __restrict__ a; int base;
-    FT8_DEV uint32_t operator()(int m) const {
+    FT8_DEV float2 operator()(int m) const {
         const int i0 = base + 2 * m;
         // samples before the frame start are zeros (the ring starts zeroed, receiver.py:248): masked with integer ALU ops --
         // a select here is turned back into a branch around the load, i.e. one memory round trip per basic block
         uint32_t raw = *reinterpret_cast<const uint32_t*>(a + (i0 & ~(i0 >> 31)));
         raw &= ~(uint32_t)(i0 >> 31);
-        return raw;
+        return make_float2((float)(int16_t)(raw & 0xFFFFu), (float)(int16_t)(raw >> 16));
+    }
+};
+// the same window of a float32 array (8-byte aligned, base even): one aligned 8-byte load per pair from the clamped address, zeros
+// before the frame start by masking the bit patterns
+struct SpecLoadFrameF32 {
+    const float* __restrict__ a; int base;
+    FT8_DEV float2 operator()(int m) const {
+        const int i0 = base + 2 * m;
+        const uint32_t keep = ~(uint32_t)(i0 >> 31);
+        const uint2 raw = *reinterpret_cast<const uint2*>(a + (i0 & (int)keep));
+        return make_float2(__uint_as_float(raw.x & keep), __uint_as_float(raw.y & keep));
     }
 };
 
@@ -45,9 +58,9 @@ FT8_DEV void spectrogram_hop(const Load& load, float* __restrict__ out, const Ta
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int m = pc + 240 * j;
-                const uint32_t raw = load(m);
+                const float2 x = load(m);
                 const float2 wn = *reinterpret_cast<const float2*>(T.win + 2 * m);
-                v[i][j] = make_float2((float)(int16_t)(raw & 0xFFFFu) * wn.x, (float)(int16_t)(raw >> 16) * wn.y);
+                v[i][j] = make_float2(x.x * wn.x, x.y * wn.y);
             }
 #pragma unroll
             for (int j = 1; j < 8; j++) w[i][j] = W[j * pc];
@@ -161,20 +174,49 @@ __global__ void k_fill_row0(float* grid, int B) {
     if (i < B * FT8RX_GRID_COLS) grid[(size_t)(i / FT8RX_GRID_COLS) * FT8RX_GRID_ROWS * FT8RX_GRID_COLS + (i % FT8RX_GRID_COLS)] = 1.0f;
 }
 
+// k_spectrogram on float32 frames: the same XCD hop map, LDS layout and row-0 workgroup; audio 8-byte aligned
+__global__ __launch_bounds__(SPEC_NT) void k_spectrogram_f32(const float* __restrict__ audio, float* __restrict__ grid, Tables T) {
+    __shared__ cpx z[1920];
+    __shared__ cpx w240[240];
+    static_assert(FT8RX_GRID_ROWS == 8 * 47, "the hop map below assumes gridDim.x = 376 = 8 XCDs x 47");
+    const int hop = (blockIdx.x & 7) * 47 + (blockIdx.x >> 3) + 1, f = blockIdx.y, tid = threadIdx.x;
+    if (hop > 375) {
+        float* row0 = grid + (size_t)f * FT8RX_GRID_ROWS * FT8RX_GRID_COLS;
+        for (int i = tid; i < FT8RX_GRID_COLS; i += SPEC_NT) row0[i] = 1.0f;
+        return;
+    }
+    spectrogram_hop(SpecLoadFrameF32{audio + (size_t)f * FT8RX_NSAMP, 480 * hop - 3840},
+                    grid + ((size_t)f * FT8RX_GRID_ROWS + hop) * FT8RX_GRID_COLS, T, z, w240, tid);
+}
+
 // ------------------------------------------------------------------------------------ rows off the down-converter's output ring
 // (index arithmetic: ddc_grid_ring.hpp).  A window of one channel's int16 output ring [ring_n]: sample i sits
 // at slot + i, less ring_n once past the ring's end (one wrap at the most: slot < ring_n, i < 3840 <= ring_n); the first nz samples
 // lie before the stream's origin and are zeros.  The first index may be odd, so the two samples of a pair are loaded one by one.
 struct SpecLoadRing {
+    typedef int16_t sample;
     const int16_t* __restrict__ ring; int slot, nz, ring_n;
-    FT8_DEV uint32_t operator()(int m) const {
+    FT8_DEV float2 operator()(int m) const {
         int i0 = slot + 2 * m, i1 = i0 + 1;
         i0 -= (i0 >= ring_n) ? ring_n : 0;
         i1 -= (i1 >= ring_n) ? ring_n : 0;
         // zeros before the origin by masking, as SpecLoadFrame does (the addresses are inside the ring whatever nz is)
         const uint32_t lo = (uint32_t)(uint16_t)ring[i0] & ~(uint32_t)((2 * m - nz) >> 31);
         const uint32_t hi = (uint32_t)(uint16_t)ring[i1] & ~(uint32_t)((2 * m + 1 - nz) >> 31);
-        return lo | (hi << 16);
+        return make_float2((float)(int16_t)lo, (float)(int16_t)hi);
+    }
+};
+// the same window of one channel's float32 output ring (the stream runs float frames): the same wrap, the zeros by masking the bit patterns
+struct SpecLoadRingF32 {
+    typedef float sample;
+    const float* __restrict__ ring; int slot, nz, ring_n;
+    FT8_DEV float2 operator()(int m) const {
+        int i0 = slot + 2 * m, i1 = i0 + 1;
+        i0 -= (i0 >= ring_n) ? ring_n : 0;
+        i1 -= (i1 >= ring_n) ? ring_n : 0;
+        const uint32_t lo = __float_as_uint(ring[i0]) & ~(uint32_t)((2 * m - nz) >> 31);
+        const uint32_t hi = __float_as_uint(ring[i1]) & ~(uint32_t)((2 * m + 1 - nz) >> 31);
+        return make_float2(__uint_as_float(lo), __uint_as_float(hi));
     }
 };
 
@@ -182,8 +224,10 @@ struct SpecLoadRing {
 // (row0 + b) mod n_rows of d_grid [n_out][n_rows][FT8RX_GRID_COLS].  The host hands over the FIRST hop's ring slot (slot0 < ring_n),
 // zero prefix (nz0 in [0, 3840)) and grid row (row0 < n_rows); hop b is 480 b samples on, and gridDim.x <= n_rows and
 // 480 gridDim.x <= ring_n keep every wrap a single compare and subtract (ft8rx.hip: ddc_stream_push).
-__global__ __launch_bounds__(SPEC_NT) void k_grid_stream(const int16_t* __restrict__ d_out, int ring_n, int slot0, int nz0, float* __restrict__ d_grid,
-                                                         int n_rows, int row0, Tables T) {
+// Load: SpecLoadRing on the int16 ring, SpecLoadRingF32 on the float32 ring.
+template <class Load>
+__global__ __launch_bounds__(SPEC_NT) void k_grid_stream(const typename Load::sample* __restrict__ d_out, int ring_n, int slot0, int nz0,
+                                                         float* __restrict__ d_grid, int n_rows, int row0, Tables T) {
     __shared__ cpx z[1920];
     __shared__ cpx w240[240];
     const int b = blockIdx.x, j = blockIdx.y;
@@ -191,7 +235,7 @@ __global__ __launch_bounds__(SPEC_NT) void k_grid_stream(const int16_t* __restri
     slot -= (slot >= ring_n) ? ring_n : 0;
     row -= (row >= n_rows) ? n_rows : 0;
     nz = nz > 0 ? nz : 0;
-    spectrogram_hop(SpecLoadRing{d_out + (size_t)j * ring_n, slot, nz, ring_n},
+    spectrogram_hop(Load{d_out + (size_t)j * ring_n, slot, nz, ring_n},
                     d_grid + ((size_t)j * n_rows + row) * FT8RX_GRID_COLS, T, z, w240, threadIdx.x);
 }
 #endif  // FT8RX_ILP_UNIT

@@ -28,6 +28,11 @@ Input blanker (extension): Receiver(..., input_blanker=T
 "block": B}), and the same keyword on decode_stream, blanks ONE stream of integer samples at its own rate on the GPU (ft8rx_blank_in*)
 in front of the down-converter, which reads the blanked samples on the device; `input_blanker_stats` holds the cumulative counters.
 The live search grid / waterfall of the channels show the blanked input.  Off (the default) nothing of it runs.
+
+Float frames (extension): float_frames=True -- on decode_frames / decode_frames_arrays / decode_frame with float32
+or float64 arrays, on decode_stream, or on Receiver(..., sample_rate=...) for the wide live input -- decodes unrounded float32 audio
+end to end: the level of the input no longer matters and no gain has to be chosen.  Off (the default) nothing changes: float arrays
+are refused as before.  noise_blanker, integer arithmetic on int16 by definition, is refused together with it.
 """
 import threading as _threading
 import time as _time
@@ -156,6 +161,35 @@ def frames_from_ragged(frames):
             raise _lib.Ft8rxError(f"frame {i}: {len(f)} samples > {_lib.NSAMP} (15 s at 12 kHz)")
         out[i, :len(f)] = f
     return out
+
+
+def frames_from_ragged_f32(frames):
+    """frames_from_ragged for float frames (float_frames=True): float32 / float64 input -> float32 [B, 180000],
+    float64 rounded to float32 once, shorter frames padded with zeros at the end.  Any other dtype, a longer frame and a non-finite
+    value (NaN, infinity: named with the frame) are refused."""
+    if isinstance(frames, np.ndarray) and frames.ndim == 1:
+        frames = [frames]
+    out = np.zeros((len(frames), _lib.NSAMP), np.float32)
+    for i, f in enumerate(frames):
+        f = np.asarray(f)
+        if f.ndim != 1:
+            raise _lib.Ft8rxError(f"frame {i}: expected a 1-D array of float samples, got shape {f.shape}")
+        if f.dtype not in (np.float32, np.float64):
+            raise _lib.Ft8rxError(f"frame {i}: float_frames=True takes float32 or float64 samples (got {f.dtype})")
+        if len(f) > _lib.NSAMP:
+            raise _lib.Ft8rxError(f"frame {i}: {len(f)} samples > {_lib.NSAMP} (15 s at 12 kHz)")
+        with np.errstate(over="ignore"):
+            out[i, :len(f)] = f                                   # float64 -> float32: one rounding
+        if not np.isfinite(out[i, :len(f)]).all():
+            raise _lib.Ft8rxError(f"frame {i}: non-finite samples (NaN or infinity, or a float64 beyond the float32 range)")
+    return out
+
+
+def refuse_float_with_blanker(float_frames, noise_blanker):
+    """noise_blanker is the one opt-in float frames refuse (DESIGN.md sections 15, 18)"""
+    if float_frames and noise_blanker is not None:
+        raise _lib.Ft8rxError("float_frames=True is not supported together with noise_blanker: its definition is integer arithmetic on "
+                              "int16 frames (input_blanker, in front of the down-converter, stays allowed)")
 
 
 # AP masks of the reference (receiver.py:21-27), as data: (name, first bit, forced bit values); 'CQ' also forces bits 74, 75 -> 0,
@@ -431,6 +465,13 @@ def _as_frames(audio_i16):
     return frames_from_ragged(audio_i16)
 
 
+def _as_frames_f32(audio):
+    """The float flavour (float_frames=True): anything frames_from_ragged_f32 takes, [B, n] arrays included"""
+    if isinstance(audio, np.ndarray) and audio.ndim == 2:
+        return frames_from_ragged_f32(list(audio))
+    return frames_from_ragged_f32(audio)
+
+
 class AudioIn:
     """Host-side state the reference keeps per receiver (receiver.py:225-306): the 15-s audio ring, the
     750 x 976 search grid that the GUI's waterfall views in place, and the hop pointer.
@@ -659,6 +700,10 @@ class Receiver:
         # [B, 4] = hits, samples with w < 32768, samples with w = 0, blocks with L_b = 0 per frame.
         self.noise_blanker = _blanker.params(extension_knobs.pop("noise_blanker", None))
         self.blanker_stats = None
+        # float frames: the default of float_frames= of decode_frames / decode_frames_arrays / decode_frame /
+        # decode_stream, and what the wide live input runs
+        self.float_frames = bool(extension_knobs.pop("float_frames", False))
+        refuse_float_with_blanker(self.float_frames, self.noise_blanker)
         # input blanker: the same values, and a dict may also hold block.  An input stage in FRONT of the
         # down-converter: ONE stream of integer samples is blanked at its own rate on the GPU (ft8rx_blank_in*) and handed to the
         # front end on the device -- decode_stream (its own keyword overrides this one) and the wide live input.  Unlike noise_blanker
@@ -697,7 +742,7 @@ class Receiver:
         """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
         if sample_rate is not None:
             self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
-                                           waterfall=waterfall, input_blanker=self.input_blanker)
+                                           waterfall=waterfall, input_blanker=self.input_blanker, float_frames=self.float_frames)
 
     @property
     def input_blanker_stats(self):
@@ -886,7 +931,7 @@ class Receiver:
         return cands
 
     def decode_frames(self, audio_i16, cyclestart_strings=None, return_records=False, passes=1, subtract_min_snr=-10,
-                      sub_pass_osd=True, research="full", recall=None):
+                      sub_pass_osd=True, research="full", recall=None, float_frames=None):
         """Decode B independent 15-s frames.  -> list (per frame) of message dicts in emit order.
 
         passes > 1 (extension): after each pass every newly decoded signal with SNR > subtract_min_snr is
@@ -901,8 +946,11 @@ class Receiver:
         subtracted again -- one sweep for all of a frame's decodes where the experiment does one per decode.
         recall (ipass 8): per frame a list of the message dicts decoded 30 s before it in the same stream (or
         None / [] for none) -- their continuations are tested at the same positions; recall messages follow a frame's others and
-        every dict gains "recall".  Of each frame's list the RECALL_MAX qualifying messages with the highest SNR are used."""
-        audio = _as_frames(audio_i16)
+        every dict gains "recall".  Of each frame's list the RECALL_MAX qualifying messages with the highest SNR are used.
+        float_frames=True (default: the receiver's): the frames are float32 / float64 arrays (frames_from_ragged_f32)
+        at any level and are decoded unrounded; the later passes subtract in float32 and do not round the residual."""
+        f32 = self._float_frames(float_frames)
+        audio = _as_frames_f32(audio_i16) if f32 else _as_frames(audio_i16)
         B = audio.shape[0]
         if B == 0:
             return ([], np.zeros((0, self.cfg.max_cands), _lib.RECORD_DTYPE), np.zeros(0, np.int32)) if return_records else []
@@ -910,7 +958,13 @@ class Receiver:
             raise _lib.Ft8rxError(f"recall: one list of earlier messages per frame ({B}), got {len(recall)}")
         with self._hlock:
             return self._decode_frames_locked(audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research,
-                                              recall)
+                                              recall, f32=f32)
+
+    def _float_frames(self, float_frames):
+        """float_frames= of an entry (None = the receiver's) -> bool; refused together with noise_blanker"""
+        f32 = self.float_frames if float_frames is None else bool(float_frames)
+        refuse_float_with_blanker(f32, self.noise_blanker)
+        return f32
 
     def _local_mask(self, msgs, mcnt, min_snr):
         """Search mask of the local re-search: columns f0 - 2 .. f0 + 1 (receiver_sub.py:440) of every message the sweep subtracts."""
@@ -926,18 +980,25 @@ class Receiver:
             mask[fi[ok], c[ok] - lo] = 1
         return mask
 
-    def _pass(self, h, B, frames, recall, gather=None):
+    def _pass(self, h, B, frames, recall, gather=None, f32=False):
         """One decode of a batch of B frames on handle h, for every entry of this class; the caller holds h's lock.  frames: host frames
         int16 [B, 180000], or None = they are in h's staging buffer already (decode_stream), or `gather(h)` brings them there (the live
         wide input).  recall: the entries per frame (_recall_entries), or None = no recall step.  The noise blanker, when on, blanks the
-        frames in the staging buffer first and leaves its counters in blanker_stats.
+        frames in the staging buffer first and leaves its counters in blanker_stats.  f32: the frames are float32 --
+        host frames float32 [B, 180000], or in h's float staging buffer; the noise blanker is off then (refuse_float_with_blanker).
         -> (records, counts, events, event counts), (recall records, counts) or None, reports [B, max_cands] or None.
         A step around the decode of a batch belongs here ("Adding a step around the batch")."""
         if recall is not None:
             h.set_recall(recall)
         if gather is not None:
             gather(h)
-        if frames is not None and self.noise_blanker is None:
+        if f32:
+            if frames is not None:
+                res = h.decode_batch_f32(frames)
+            else:
+                h.enqueue_f32(h.staging_ptr_f32(), B)
+                res = h.fetch(B)
+        elif frames is not None and self.noise_blanker is None:
             res = h.decode_batch(frames)
         else:
             if self.noise_blanker is not None:
@@ -956,19 +1017,22 @@ class Receiver:
             return _lib.package_batch_ext(*res, self.cfg.msg_types, **kw)
         return _lib.package_batch(*res, **kw)
 
-    def _later_passes(self, h, B, passes, msgs, mcnt, res, min_snr, local, merge, **pkg_kw):
+    def _later_passes(self, h, B, passes, msgs, mcnt, res, min_snr, local, merge, f32=False, **pkg_kw):
         """Passes 2 .. `passes` of a batch whose frames pass 1 left in h's staging buffer (msgs, mcnt: its messages, res: its results):
         subtract the fresh messages of the pass before, decode the residual -- local: the experiment's local re-search, one sweep --
-        and hand the packaged messages to merge(p, msgs, counts) -> the fresh ones (rows, counts).  -> the results of the last pass run"""
+        and hand the packaged messages to merge(p, msgs, counts) -> the fresh ones (rows, counts).  -> the results of the last pass run.
+        f32: the frames are in the float staging buffer and stay float32 between the passes (ft8rx_subtract_f32: no rounding)"""
+        staging, enqueue = (h.staging_ptr_f32, h.enqueue_f32) if f32 else (h.staging_ptr, h.enqueue)
         for p in range(1, int(passes)):
             sigs = self._subtraction_list(msgs, mcnt, res[0], min_snr)
             if not sigs[1].any():
                 break
-            h.subtract(h.staging_ptr(), B, sigs, refine=self.subtract_refine)    # the pass before left the frames in the handle's device buffer
+            # the pass before left the frames in the handle's device buffer (f32: the float one, and the float entry)
+            h.subtract(staging(), B, sigs, refine=self.subtract_refine, **({"float_frames": True} if f32 else {}))
             if local:
                 h.set_search_mask(self._local_mask(msgs, mcnt, min_snr))
             try:
-                h.enqueue(h.staging_ptr(), B)
+                enqueue(staging(), B)
                 res = h.fetch(B)
             finally:
                 if local:
@@ -1001,8 +1065,11 @@ class Receiver:
         behaves and is refused as it always was.
         input_blanker= (default: the receiver's; None / True / a threshold k / a dict of threshold, guard, taper, block): ONE stream
         of integer samples is blanked at its own rate on the device (ft8rx_blank_in_host) and the front end
-        reads it there; more streams, or float / complex samples, are refused."""
+        reads it there; more streams, or float / complex samples, are refused.
+        float_frames= (default: the receiver's): the down-converter's output before rounding is decoded as float32
+        frames -- a quiet wide source whose 12 kHz channels stay under one count of int16 decodes as at full level."""
         input_blanker = kw.pop("input_blanker", self.input_blanker)
+        f32 = self._float_frames(kw.pop("float_frames", None))
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
         if n_out < 1:
@@ -1023,16 +1090,18 @@ class Receiver:
         ib = _wide_in.input_blanker_params(input_blanker, kind, n_streams, int(sample_rate))
         with self._hlock:
             h = self._handle(n_out)
+            d_f32 = h.staging_ptr_f32() if f32 else None       # float frames: the audio before rounding, into the float staging buffer
             if ib is None:
-                _wide_in.HANDLE_CALLS[mod][0](h, arr, kind, int(sample_rate), src, dials)
+                _wide_in.HANDLE_CALLS[mod][0](h, arr, kind, int(sample_rate), src, dials, d_f32)
             else:
                 d_ptr, n, self._input_blanker_stats = h.blank_in(arr[0], kind, *ib)
-                _wide_in.HANDLE_CALLS[mod][3](h, d_ptr, n, kind, int(sample_rate), src, dials)
-            return self._decode_frames_locked(None, n_out, bands=bands, **args)
+                _wide_in.HANDLE_CALLS[mod][3](h, d_ptr, n, kind, int(sample_rate), src, dials, d_f32)
+            return self._decode_frames_locked(None, n_out, bands=bands, f32=f32, **args)
 
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",
-                              recall=None, bands=None):
-        """audio None: the B frames are in the handle's staging buffer already (decode_stream); bands: per frame, instead of self.band"""
+                              recall=None, bands=None, f32=False):
+        """audio None: the B frames are in the handle's staging buffer already (decode_stream); bands: per frame, instead of self.band;
+        f32: float frames (float32 host frames, or the float staging buffer)"""
         if research not in ("full", "local"):
             raise _lib.Ft8rxError('research must be "full" or "local"')
         use_recall = self.recall or recall is not None
@@ -1043,7 +1112,7 @@ class Receiver:
             _optins.refuse(_optins.PASSES, on)
         h = self._handle(B)
         entries = self._recall_entries(recall if recall is not None else [None] * B) if use_recall else None
-        res, rres, rp = self._pass(h, B, audio, entries)
+        res, rres, rp = self._pass(h, B, audio, entries, f32=f32)
         msgs, mcnt = self._package(res, rres)
         cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000015" for f in range(B)]
         band = [self.band] * B if bands is None else list(bands)
@@ -1066,7 +1135,7 @@ class Receiver:
                         if self.on_message is not None:
                             self.on_message(d)
             return msgs, keep
-        rec, cnt = self._later_passes(h, B, passes, msgs, mcnt, res, subtract_min_snr, research == "local", merge)[:2]
+        rec, cnt = self._later_passes(h, B, passes, msgs, mcnt, res, subtract_min_snr, research == "local", merge, f32=f32)[:2]
         return (out, rec, cnt) if return_records else out
 
     @staticmethod
@@ -1096,12 +1165,14 @@ class Receiver:
         arr["tsec"][fi, slot] = m["h0_idx"] / 25.0 + np.where(fine, m["ttweak"] / 200.0, 0.0)
         return arr, cnt
 
-    def decode_frames_arrays(self, audio_i16, n_threads=None, passes=1, subtract_min_snr=-10, sub_pass_osd=True, research="full"):
+    def decode_frames_arrays(self, audio_i16, n_threads=None, passes=1, subtract_min_snr=-10, sub_pass_osd=True, research="full",
+                             float_frames=None):
         """High-throughput variant of decode_frames: no Python dicts.  -> (messages[B, 128] of _lib.MESSAGE_DTYPE,
         counts[B], records[B, max_cands], record_counts[B]); rows are in the reference's emit order.  With passes > 1 (see
         decode_frames) the messages of the later passes are appended per frame and carry the pass index (1, 2, ...) in
-        messages["pad"][:, :, 0]; the returned records are those of the first pass."""
-        audio = _as_frames(audio_i16)
+        messages["pad"][:, :, 0]; the returned records are those of the first pass.  float_frames: as decode_frames."""
+        f32 = self._float_frames(float_frames)
+        audio = _as_frames_f32(audio_i16) if f32 else _as_frames(audio_i16)
         B = audio.shape[0]
         if B == 0:
             raise _lib.Ft8rxError("empty batch")
@@ -1110,18 +1181,19 @@ class Receiver:
         _optins.refuse(_optins.ARRAYS, _optins.active(self.cfg))
         with self._hlock:
             h = self._handle(B)
-            res = self._pass(h, B, audio, None)[0]
+            res = self._pass(h, B, audio, None, f32=f32)[0]
             msgs, mcnt = _lib.package_batch(*res, n_threads=n_threads)
             if passes > 1:
                 # the array flavour of the merge is native (appends in place, up to the width of `out`)
                 out, ocnt = msgs.copy(), np.ascontiguousarray(mcnt, np.int32).copy()
                 self._later_passes(h, B, passes, msgs, mcnt, res, subtract_min_snr, research == "local",
-                                   lambda p, m2, c2: _lib.merge_messages(out, ocnt, m2, c2, p, drop_osd=not sub_pass_osd), n_threads=n_threads)
+                                   lambda p, m2, c2: _lib.merge_messages(out, ocnt, m2, c2, p, drop_osd=not sub_pass_osd), f32=f32,
+                                   n_threads=n_threads)
                 msgs, mcnt = out, ocnt
             return msgs, mcnt, res[0], res[1]
 
-    def decode_frame(self, audio_i16, cyclestart_string="700101_000015"):
-        return self.decode_frames(np.asarray(audio_i16)[None], [cyclestart_string])[0]
+    def decode_frame(self, audio_i16, cyclestart_string="700101_000015", float_frames=None):
+        return self.decode_frames(np.asarray(audio_i16)[None], [cyclestart_string], float_frames=float_frames)[0]
 
     # ---- streaming mode (stands in for the manage_cycle thread, receiver.py:372-412)
     def _deliver(self, row, dicts, t0, early, seen_by_cycle, hist_by_cycle, out):
@@ -1153,12 +1225,12 @@ class Receiver:
             if self.on_message is not None:
                 self.on_message(d)
 
-    def _live_pass(self, t0, early, K, frames, gather, bands, channels, seen, hist, out):
+    def _live_pass(self, t0, early, K, frames, gather, bands, channels, seen, hist, out, f32=False):
         """One live pass over the K frames of the cycle that starts at t0 -- the 12 kHz path: K = 1, a host frame; the wide path: one
         frame per channel, which gather(h) brings into the live handle's staging buffer: decode them as one batch on the live handle,
         package with the persistent call-hash table (the frames are replayed into it in ascending order, package_batch(table=)) and
         deliver per frame (_deliver) with its band bands[j], its duplicate filter seen[j], its recall history hist[j] and -- channels
-        not None -- "channel": channels[j]."""
+        not None -- "channel": channels[j].  f32: gather brings float frames into the float staging buffer."""
         cs = _time.strftime("%y%m%d_%H%M%S", _time.gmtime(t0))
         # recall: only the complete-frame pass, per frame the complete-frame messages of the same channel 30 s earlier (same parity),
         # and only when at least one frame has such a history
@@ -1166,7 +1238,7 @@ class Receiver:
         if prev is not None and all(p is None for p in prev):
             prev = None
         with self._live_lock:
-            res, rres, rp = self._pass(self._live_handle(K), K, frames, None if prev is None else self._recall_entries(prev), gather)
+            res, rres, rp = self._pass(self._live_handle(K), K, frames, None if prev is None else self._recall_entries(prev), gather, f32=f32)
         # the host message layer runs outside _live_lock: an audio callback that waits for a hop spectrum is not held up by it
         msgs, mcnt = self._package(res, rres, n_threads=1, table=self.call_hashes)
         for j in range(K):
@@ -1204,16 +1276,19 @@ class Receiver:
                     break
                 c, hop, m_first, n_have = w._ready.pop(0)
             K = w.n_channels
-            self._live_pass(T_CYC * c, hop, K, None, lambda h: h.ddc_stream_frame(m_first, n_have),
-                            w.bands if w.bands is not None else [self.band] * K, range(K), w.seen, w.recall_hist, out)
+            gather = (lambda h: h.ddc_stream_frame_f32(m_first, n_have)) if w.float_frames else (lambda h: h.ddc_stream_frame(m_first, n_have))
+            self._live_pass(T_CYC * c, hop, K, None, gather,
+                            w.bands if w.bands is not None else [self.band] * K, range(K), w.seen, w.recall_hist, out, f32=w.float_frames)
         return out
 
 
-def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=None, **receiver_kwargs):
+def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=None, float_frames=False, **receiver_kwargs):
     """decode_frames(audio_i16[B,180000], **receiver_kwargs) -> list[list[message dict]]  (SURVEY.md 8b); passes > 1 adds the
     subtraction passes of Receiver.decode_frames; recall = per frame the message dicts decoded 30 s earlier (Receiver.decode_frames);
     noise_blanker= (None / True / a threshold k / a dict of threshold, guard, taper) goes to Receiver with the other keyword arguments:
-    the frames are blanked on the GPU (ft8rx_blank_host) before the first pass."""
-    audio = _as_frames(audio_i16)
-    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, **receiver_kwargs)       # reports=True: "report" in every dict
+    the frames are blanked on the GPU (ft8rx_blank_host) before the first pass.  float_frames=True: float32 / float64 frames at any level,
+    decoded unrounded (Receiver.decode_frames)."""
+    audio = _as_frames_f32(audio_i16) if float_frames else _as_frames(audio_i16)
+    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, float_frames=bool(float_frames),
+                  **receiver_kwargs)       # reports=True: "report" in every dict
     return rx.decode_frames(audio, passes=passes, research=research, recall=recall)

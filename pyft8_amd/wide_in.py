@@ -89,24 +89,30 @@ def sources(mod, src, n_streams, n_channels):
     return src
 
 
+def _given(**kw):
+    """The keyword arguments that are set: a call without float frames is the call it always was"""
+    return {k: v for k, v in kw.items() if v}
+
+
 def _pre_stage(name):
     """The row of a pre-stage in HANDLE_CALLS: its Handle methods take ONE stream as [n(, 2)], and neither n_streams nor src"""
-    return (lambda h, a, kind, rate, src, dials: getattr(h, name)(a[0], kind, rate, dials),
-            lambda h, kind, rate, n_streams, src, dials: getattr(h, name + "_stream_open")(kind, rate, dials),
+    return (lambda h, a, kind, rate, src, dials, d_f32=None: getattr(h, name)(a[0], kind, rate, dials, **_given(d_f32_ptr=d_f32)),
+            lambda h, kind, rate, n_streams, src, dials, keep_f32=False: getattr(h, name + "_stream_open")(kind, rate, dials, **_given(keep_f32=keep_f32)),
             lambda h, a: getattr(h, name + "_stream_push")(a[0]),
-            lambda h, d_ptr, n, kind, rate, src, dials: getattr(h, name)(None, kind, rate, dials, d_ptr=d_ptr, n=n),
+            lambda h, d_ptr, n, kind, rate, src, dials, d_f32=None: getattr(h, name)(None, kind, rate, dials, d_ptr=d_ptr, n=n, **_given(d_f32_ptr=d_f32)),
             lambda h, d_ptr, n: getattr(h, name + "_stream_push")(None, d_ptr=d_ptr, n=n))
 
 
 # module -> how the one-shot call (h, packed, kind, rate, src, dials), the stream open (h, kind, rate, n_streams, src, dials)
 # and the stream push (h, packed) reach the Handle; packed is what pack() returns, [n_streams][n(, 2)].  Behind the input blanker
 # (input_blanker=; DESIGN.md section 17.1) the one stream is on the device already: the one-shot call (h, d_ptr, n, kind, rate, src,
-# dials) and the push (h, d_ptr, n)
+# dials) and the push (h, d_ptr, n).  Float frames (DESIGN.md section 18): the one-shot calls take d_f32, the device address that receives
+# the audio before rounding, and the open takes keep_f32 (2 = the stream runs float frames)
 HANDLE_CALLS = {
-    _ddc: (lambda h, a, kind, rate, src, dials: h.ddc(a, kind, rate, src, dials),
-           lambda h, kind, rate, n_streams, src, dials: h.ddc_stream_open(kind, rate, n_streams, src, dials),
+    _ddc: (lambda h, a, kind, rate, src, dials, d_f32=None: h.ddc(a, kind, rate, src, dials, **_given(d_f32_ptr=d_f32)),
+           lambda h, kind, rate, n_streams, src, dials, keep_f32=False: h.ddc_stream_open(kind, rate, n_streams, src, dials, **_given(keep_f32=keep_f32)),
            lambda h, a: h.ddc_stream_push(a),
-           lambda h, d_ptr, n, kind, rate, src, dials: h.ddc(None, kind, rate, src, dials, d_ptr=d_ptr, n=n),
+           lambda h, d_ptr, n, kind, rate, src, dials, d_f32=None: h.ddc(None, kind, rate, src, dials, d_ptr=d_ptr, n=n, **_given(d_f32_ptr=d_f32)),
            lambda h, d_ptr, n: h.ddc_stream_push(None, d_ptr=d_ptr, n=n)),
     _dw: _pre_stage("ddc_wide"),
     _dr: _pre_stage("ddc_rat")}
@@ -235,8 +241,11 @@ class WideIn:
     source_exhausted."""
 
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False,
-                 waterfall=False, input_blanker=None):
+                 waterfall=False, input_blanker=None, float_frames=False):
         self._rx = receiver
+        # float_frames (DESIGN.md section 18): the stream keeps the float32 output ring (1.44 MB per channel), every pass gathers and
+        # decodes float frames, and with waterfall=True the rows come from that ring
+        self.float_frames = bool(float_frames)
         self.sample_rate = int(sample_rate)
         # input_blanker (DESIGN.md section 17.1): the ONE stream's integer samples are blanked at their own rate on the device
         # (ft8rx_blank_in_stream_*) and what that releases goes to the front end's device push; the kind decides at the first chunk
@@ -297,7 +306,8 @@ class WideIn:
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
             ib = input_blanker_params(self.input_blanker, self.kind, self.n_streams, self.sample_rate)
-            self.f_mixed_hz = HANDLE_CALLS[self.mod][1](h, self.kind, self.sample_rate, self.n_streams, self.src, self.dials)
+            self.f_mixed_hz = HANDLE_CALLS[self.mod][1](h, self.kind, self.sample_rate, self.n_streams, self.src, self.dials,
+                                                        2 if self.float_frames else False)
             if ib is not None:
                 h.blank_in_stream_open(self.kind, *ib, n_origin=0, max_push=self.sample_rate)
                 self._ib = ib
@@ -364,13 +374,18 @@ class WideIn:
             c0, m_c0 = self._grid_c0
             with self._rx._live_lock:
                 h = self._rx._live_handle(self.n_channels)
-                h.ddc_stream_frame(m_c0 + NSAMP * (c - c0), NSAMP)
-                frames = h.download_audio(h.staging_ptr(), self.n_channels)
+                if self.float_frames:
+                    h.ddc_stream_frame_f32(m_c0 + NSAMP * (c - c0), NSAMP)
+                    frames = h.download_audio_f32(h.staging_ptr_f32(), self.n_channels)
+                else:
+                    h.ddc_stream_frame(m_c0 + NSAMP * (c - c0), NSAMP)
+                    frames = h.download_audio(h.staging_ptr(), self.n_channels)
             self._spec_cache = (c, frames, {})
         _, frames, specs = self._spec_cache
         if channel not in specs:
             with self._rx._hlock:
-                specs[channel] = self._rx._handle(1).cycle_spectrum(frames[channel])[0]
+                h1 = self._rx._handle(1)
+                specs[channel] = (h1.cycle_spectrum_f32 if self.float_frames else h1.cycle_spectrum)(frames[channel])[0]
         return specs[channel]
 
     def _outputs(self, n):
