@@ -200,7 +200,14 @@ static void make_window(void) {
     g_win_ok = 1;
 }
 
+/* one body on float32 samples; the int16 entry converts (exactly) and calls it, as ft8o_cycle_spectrum does */
 void ft8o_spectrogram(const int16_t* audio, const ft8o_config* c, float* grid) {
+    float* x = (float*)malloc(sizeof(float) * FT8O_NSAMP);
+    for (int i = 0; i < FT8O_NSAMP; i++) x[i] = (float)audio[i];          /* exact */
+    ft8o_spectrogram_f32(x, c, grid);
+    free(x);
+}
+void ft8o_spectrogram_f32(const float* audio, const ft8o_config* c, float* grid) {
     if (!g_win_ok) make_window();
     const cpx* W = get_twiddle(1920);
     const cpx* WR = get_twiddle(3840);
@@ -211,8 +218,8 @@ void ft8o_spectrogram(const int16_t* audio, const ft8o_config* c, float* grid) {
         int base = 480 * r - 3840;                                   /* window = last 3840 samples after hop r */
         for (int m = 0; m < 1920; m++) {
             int i0 = base + 2 * m, i1 = i0 + 1;
-            float x0 = (i0 >= 0) ? (float)audio[i0] * g_win[2 * m] : 0.0f * g_win[2 * m];
-            float x1 = (i1 >= 0) ? (float)audio[i1] * g_win[2 * m + 1] : 0.0f * g_win[2 * m + 1];
+            float x0 = (i0 >= 0) ? audio[i0] * g_win[2 * m] : 0.0f * g_win[2 * m];
+            float x1 = (i1 >= 0) ? audio[i1] * g_win[2 * m + 1] : 0.0f * g_win[2 * m + 1];
             z[m].re = x0; z[m].im = x1;
         }
         fft_core(z, y, 1920, c->plan1920, W);
@@ -1228,10 +1235,19 @@ static int run_ldpc_frame(fctx* fc, float* llr, int nc0, int iters, ft8o_cand* c
 
 int ft8o_decode_frame(const int16_t* audio, const ft8o_config* cfg, ft8o_cand* cands, int32_t* n_cands,
                       ft8o_event* log, int32_t log_cap, int32_t* n_log, ft8o_msg* msgs, int32_t msg_cap, int32_t* n_msgs) {
+    float* x = (float*)malloc(sizeof(float) * FT8O_NSAMP);
+    for (int i = 0; i < FT8O_NSAMP; i++) x[i] = (float)audio[i];          /* exact */
+    int r = ft8o_decode_frame_f32(x, cfg, cands, n_cands, log, log_cap, n_log, msgs, msg_cap, n_msgs);
+    free(x);
+    return r;
+}
+/* the one body of the whole-frame decode, on float32 samples */
+int ft8o_decode_frame_f32(const float* audio, const ft8o_config* cfg, ft8o_cand* cands, int32_t* n_cands,
+                          ft8o_event* log, int32_t log_cap, int32_t* n_log, ft8o_msg* msgs, int32_t msg_cap, int32_t* n_msgs) {
     float* grid = (float*)malloc(sizeof(float) * FT8O_GRID_ROWS * FT8O_GRID_COLS);
     float* spec = NULL;
     ft8o_cand* all = (ft8o_cand*)malloc(sizeof(ft8o_cand) * 2048);     /* one candidate per f0 bin at most: < 960 (1888 in the wide build) */
-    ft8o_spectrogram(audio, cfg, grid);
+    ft8o_spectrogram_f32(audio, cfg, grid);
     int n = ft8o_sync_search(grid, cfg, all);
     memcpy(cands, all, sizeof(ft8o_cand) * (size_t)n);
     free(all);
@@ -1270,7 +1286,7 @@ int ft8o_decode_frame(const int16_t* audio, const ft8o_config* cfg, ft8o_cand* c
                     if (run_ldpc_frame(&fc, s->llr, cfg->bp_nc0_a, cfg->bp_iters_a, c, &has_out)) { done = 1; c->method = FT8O_M_LDPC_A; c->ap = ap; }
                 }
             } else if (ip == 1) {
-                if (!spec) { spec = (float*)malloc(sizeof(float) * 2 * FT8O_SPEC_BINS); ft8o_cycle_spectrum(audio, cfg, spec); }
+                if (!spec) { spec = (float*)malloc(sizeof(float) * 2 * FT8O_SPEC_BINS); ft8o_cycle_spectrum_f32(audio, cfg, spec); }
                 float sd; int32_t snr;
                 int r = ft8o_fine(spec, cfg, c->f0_idx, c->h0_idx, &c->ttweak, &c->ftweak, &c->nsync, s->llr, &sd, &snr, NULL);
                 if (r == 0) c->status = FT8O_ST_STOP_COSTAS;

@@ -115,6 +115,12 @@ int   ft8o_unpack77(void* hash, uint64_t lo, uint64_t hi, char out[3][16]);
 int   ft8o_decode_frame(const int16_t* audio, const ft8o_config* c, ft8o_cand* cands, int32_t* n_cands,
                         ft8o_event* log, int32_t log_cap, int32_t* n_log, ft8o_msg* msgs, int32_t msg_cap, int32_t* n_msgs);
 
+/* float32 frames: the bodies of ft8o_spectrogram and ft8o_decode_frame, which convert their int16 samples
+ * exactly and call these; ft8o_decode_frame_f32 takes its cycle spectrum from ft8o_cycle_spectrum_f32 */
+void  ft8o_spectrogram_f32(const float* audio /*[180000]*/, const ft8o_config* c, float* grid);
+int   ft8o_decode_frame_f32(const float* audio /*[180000]*/, const ft8o_config* c, ft8o_cand* cands, int32_t* n_cands,
+                            ft8o_event* log, int32_t log_cap, int32_t* n_log, ft8o_msg* msgs, int32_t msg_cap, int32_t* n_msgs);
+
 /* signal subtraction: Receiver.subtract_signal, reference tests/pipeline/receiver_sub.py:380-402, with
  * symbols_to_complex_audio (PyFT8/transmitter.py:41-70).  audio = the receiver's float32 ring (180000 samples), modified in
  * place; returns 1 if the signal was subtracted, 0 if the reference's guard (sig_s0 > 0, whole signal inside the buffer) fails. */

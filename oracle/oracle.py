@@ -138,6 +138,16 @@ def spectrogram(audio, cfg=None):
     return g
 
 
+def spectrogram_f32(audio_f32, cfg=None):
+    """spectrogram() of a float32 frame (ft8o_spectrogram_f32, the body of the int16 entry)"""
+    cfg = cfg or default_config()
+    a = np.ascontiguousarray(audio_f32, np.float32)
+    assert a.shape == (NSAMP,)
+    g = np.empty((GRID_ROWS, GRID_COLS_WIDE if _wide(cfg) else GRID_COLS), np.float32)
+    lib(_wide(cfg)).ft8o_spectrogram_f32(_p(a), C.byref(cfg), _p(g))
+    return g
+
+
 def sync_search(grid, cfg=None):
     cfg = cfg or default_config()
     grid = np.ascontiguousarray(grid, np.float32)
@@ -261,15 +271,23 @@ def valid77(bits77):
 
 def decode_frame(audio, cfg=None):
     """Whole-frame oracle decode -> dict(cands, events, msgs)."""
+    return _decode_frame("ft8o_decode_frame", np.ascontiguousarray(audio, np.int16), C.c_int16, cfg)
+
+
+def decode_frame_f32(audio_f32, cfg=None):
+    """decode_frame() of a float32 frame (ft8o_decode_frame_f32, the body of the int16 entry)."""
+    return _decode_frame("ft8o_decode_frame_f32", np.ascontiguousarray(audio_f32, np.float32), C.c_float, cfg)
+
+
+def _decode_frame(entry, audio, ctype, cfg):
     cfg = cfg or default_config()
-    audio = np.ascontiguousarray(audio, np.int16)
     assert audio.shape == (NSAMP,)
     cands = (Cand * max(1, cfg.max_cands))()
     log = (Event * 4096)()
     mcap = max(256, cfg.max_cands)
     msgs = (Msg * mcap)()
     nc, nl, nm = C.c_int32(), C.c_int32(), C.c_int32()
-    lib(_wide(cfg)).ft8o_decode_frame(_p(audio, C.c_int16), C.byref(cfg), cands, C.byref(nc), log, 4096, C.byref(nl), msgs, mcap, C.byref(nm))
+    getattr(lib(_wide(cfg)), entry)(_p(audio, ctype), C.byref(cfg), cands, C.byref(nc), log, 4096, C.byref(nl), msgs, mcap, C.byref(nm))
     out_msgs = []
     for i in range(min(nm.value, mcap)):
         m = msgs[i]

@@ -52,8 +52,9 @@ FT8_DEV float ft8_log10f(float x) {
     return __builtin_fmaf(fe, 0.301025390625f, __builtin_fmaf(fe, 4.6050390e-6f, lnm * 0.4342945f));
 }
 
-// The same function for arguments known to be positive, normal and finite (2^-126 <= x <= 3e38): the three range checks above are
-// dead code for them and cost two divergent branches per call.  The spectrogram's argument is |X| + 1e-12 with |X| <= 32768 x 3840.
+// The same function for arguments known to be positive, normal and finite (2^-126 <= x < 2^128), its whole domain: the three range
+// checks above are dead code for them and cost two divergent branches per call.  The spectrogram's argument is max(|X|^2, 1e-24); float
+// frames bring any level, and +inf, a power that overflowed, would read as 2^128: 385.3 dB, not the contract's inf.
 FT8_DEV float ft8_log10f_normal(float x) {
     const uint32_t ix = __float_as_uint(x);
     int e = (int)(ix >> 23) - 127;

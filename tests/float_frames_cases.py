@@ -1,6 +1,7 @@
-"""Shared inputs of tests/test_float_frames.py and tests/test_gpu_float_frames.py (float32 frames): the four
-integer-valued frames, and the two-channel IQ streams built from golden frames -- at full level and so quiet that every int16 frame
-the down-converter makes of them is zero.  Everything is built once and handed out unchanged."""
+"""Shared inputs of tests/test_float_frames.py, tests/test_gpu_float_frames.py and tests/test_gpu_float_levels.py (float32 frames,
+DESIGN.md section 18): the four integer-valued frames, the level and edge frames with full 24-bit mantissas, and the two-channel IQ
+streams built from golden frames -- at full level and so quiet that every int16 frame the down-converter makes of them is zero.
+Everything is built once and handed out unchanged."""
 import numpy as np
 
 import ddc_cases as cases
@@ -41,6 +42,46 @@ def runs_frame():
 def int_frames():
     """int16 [4, 180000]: synth_000000, test_08, an all-zero frame, the runs frame"""
     return _once("int", lambda: np.stack([load_golden("synth_000000")[0], load_golden("test_08")[0], np.zeros(NSAMP, np.int16), runs_frame()]))
+
+
+# ---- level frames: float32(float64(a) * c) of a golden frame.  No c is a power of two, so the mantissas are full: 24 significant bits
+LEVELS = {"NORM": 0.7071 / 32768,             # the [-1, 1] convention of float audio
+          "QUIET": 8.3e-10,                   # normalised audio 90 dB down
+          "LOUD": 51234.5}                    # int32-scaled floats, peak about 1.7e9
+EDGE = 30000.0                                # the edge samples, in int16 counts before the scaling
+EDGE_BASE = {"QUIET": "synth_000000", "LOUD": "test_08", "NORM": "synth_000000"}
+STAGE_ORDER = ("QUIET", "LOUD", "NORM")       # the stage batch: these edge frames, then the integer-valued test_08
+
+
+def scaled(a, c):
+    """float32(float64(a) * c): one rounding"""
+    return (np.asarray(a, np.float64) * float(c)).astype(np.float32)
+
+
+def level_frame(name, level):
+    """float32 [180000]: the golden frame `name` at LEVELS[level]"""
+    return _once(("level", name, level), lambda: scaled(load_golden(name)[0], LEVELS[level]))
+
+
+def level_frames():
+    """[(name, level, float32 [180000])]: the six level frames, CHANNELS x LEVELS"""
+    return [(n, lv, level_frame(n, lv)) for lv in LEVELS for n in CHANNELS]
+
+
+def edge_frame(level):
+    """The level frame of EDGE_BASE[level] with its first two samples at +30000 c and its last two at -30000 c: what a zero mask
+    that leaked would read, before the frame's start (its own head) or beyond sample 180 000 (the next frame's head)"""
+    def make():
+        a = load_golden(EDGE_BASE[level])[0].astype(np.float64)
+        a[:2], a[-2:] = EDGE, -EDGE
+        return scaled(a, LEVELS[level])
+    return _once(("edge", level), make)
+
+
+def stage_batch():
+    """float32 [4, 180000]: QUIET edge, LOUD edge, NORM edge, integer-valued test_08.  A leak past sample 180 000 of the quiet frame
+    reads the loud frame's start; a leak before a frame's start reads its own large first samples"""
+    return _once("stage", lambda: np.stack([edge_frame(lv) for lv in STAGE_ORDER] + [load_golden("test_08")[0].astype(np.float32)]))
 
 
 def offsets():

@@ -10,6 +10,7 @@ import pytest
 
 import oracle as O
 from conftest import GOLDEN_FRAMES, load_golden
+from helpers import check_frame as _check_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -327,36 +328,6 @@ def test_crc_and_validity_exact(H):
     for k in range(len(cw)):
         r, bits = O.crc_valid91(cw[k])
         assert res[k] == r and (r == 0 or ((int(hi[k]) << 64) | int(lo[k])) == bits)
-
-
-def _check_frame(rec, cnt, ev, evc, audio, js, ocfg):
-    from pyft8_amd import messages as M
-    r = O.decode_frame(audio, ocfg)
-    n = int(cnt)
-    assert n == len(r["cands"])
-    for i, c in enumerate(r["cands"]):
-        g = rec[i]
-        assert (g["f0_idx"], g["h0_idx"]) == (c.f0_idx, c.h0_idx)
-        assert np.float32(g["score"]) == np.float32(c.score)
-        assert int(g["status"]) == c.status, (i, int(g["status"]), c.status)
-        assert np.float32(g["grid_sd"]) == np.float32(c.grid_sd) and g["snr_grid"] == c.snr_grid
-        if c.status in (1, 4, 5) and (c.status != 1 or c.ipass >= 2):
-            assert (g["ttweak"], g["ftweak"], g["nsync"]) == (c.ttweak, c.ftweak, c.nsync)
-            assert np.float32(g["fine_sd"]) == np.float32(c.fine_sd) and g["snr_fine"] == c.snr_fine
-        if c.status == 1:
-            assert (int(g["ipass"]), int(g["ap"]), int(g["method"]), int(g["n_its"])) == (c.ipass, c.ap, c.method, c.n_its), i
-            assert (int(g["msg_lo"]), int(g["msg_hi"])) == (c.msg_lo, c.msg_hi)
-    msgs = M.package_frame(rec, n, ev, int(evc), cyclestart_string="700101_000015")
-    o_txt = [" ".join(m["msg_tuple"]) for m in r["msgs"]]
-    g_txt = [" ".join(m["msg_tuple"]) for m in msgs]
-    assert g_txt == o_txt
-    if js is not None:
-        assert g_txt == [" ".join(m["msg_tuple"]) for m in js["messages"]]
-        for m, ref in zip(msgs, js["messages"]):
-            for key in ("tsec", "fHz", "their_snr", "all_txt_format", "tweaks", "decode_notes", "cyclestart_string", "their_tx_cycle"):
-                assert m[key] == ref[key], (key, m[key], ref[key])
-            assert list(m["msg_tuple"]) == ref["msg_tuple"]
-    return len(g_txt)
 
 
 def test_decode_batch_golden_frames(H, ocfg):
