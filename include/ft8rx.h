@@ -718,6 +718,57 @@ int  ft8rx_blank_in_stream_close(ft8rx_handle* h);
 /* host only, no GPU: *released = the absolute index of the first sample that is not final once [.., n_end) exist -> 0, or -1 for
  * arguments outside the definition (n_end < n_origin included) */
 int  ft8rx_blank_in_released(uint64_t n_origin, uint64_t n_end, int block, int guard, int taper, uint64_t* released);
+/* Panorama (extension): the averaged power spectrum of ONE raw input stream of any kind (FT8RX_DDC_*,
+ * FT8RX_WIDE_*) at its own rate, and how often it touched the converter's rails.  A stand-alone input stage: nothing else changes, and
+ * it runs beside any down-converter or input blanker stream.  pyft8_amd/pan.py holds the float64 twin.
+ *   value   the sample on the int16 scale (uint8 256 (u - 127.5), int8 256 s, the others as they are); a real kind has Im = 0;
+ *   window  w = the ABSOLUTE samples [w N, (w + 1) N), N = n_fft, weighted by the periodic Hann window ft8rx_pan_window; only
+ *           complete windows count; X_w = the N-point DFT in float32, p_w[k] = Re^2 + Im^2;
+ *   row     r = the windows [r A, (r + 1) A), A = n_avg: P_r[j] = the float32 SUM of p_w[k(j)] in window order, not normalised; only
+ *           rows whose samples all lie in the stream exist, the first being ceil(ceil(n_origin / N) / A);
+ *   bins    IQ kinds N per row, ascending frequency: j is bin k = (j + N / 2) mod N at (j - N / 2) rate / N; real kinds N / 2, j = k;
+ *   stats   int32 [2] per row, exact: samples with a component at the format's lowest or highest code (int16 -32768 / 32767, int8
+ *           -128 / 127, uint8 0 / 255), and the largest |c| of a component, c = x (int16), s (int8), 2 u - 255 (uint8); float kinds 0, 0.
+ * n_fft: a power of two in [256, 8192]; n_avg in [1, 65536].  Anything else returns -1 with a text that names the argument. */
+#define FT8RX_PAN_FFT_DEFAULT  2048
+#define FT8RX_PAN_MIN_FFT      256
+#define FT8RX_PAN_MAX_FFT      8192
+#define FT8RX_PAN_MAX_AVG      65536
+#define FT8RX_PAN_ROWS_DEFAULT 256
+#define FT8RX_PAN_MAX_ROWS     65536
+#define FT8RX_PAN_MAX_SAMPLES  2147483648ull   /* of a one-shot call */
+#define FT8RX_PAN_MAX_PUSH     268435456ull    /* of a stream's max_push */
+/* host only, no GPU: the weights, computed in double and rounded once -> n_fft, and the first min(n_fft, cap) of them in w (w may be
+ * NULL); -1 for an n_fft outside the definition */
+int  ft8rx_pan_window(int n_fft, float* w, int cap);
+/* host only, no GPU: rows[0] = the first row of a stream that began at n_origin, rows[1] = the first row that is NOT complete once
+ * the samples [n_origin, n_end) exist (rows[1] - rows[0] rows exist) -> 0, or -1 for arguments outside the definition */
+int  ft8rx_pan_rows_done(uint64_t n_origin, uint64_t n_end, int n_fft, int n_avg, uint64_t* rows);
+/* The one-shot on n_samples device samples of `kind` from index 0 (aligned to a component; samples behind the last complete row are
+ * not read): *n_rows_out = (n_samples / n_fft) / n_avg rows -> rows, host [n_rows][bins], and stats, host [n_rows][2]; each may be
+ * NULL.  Waits for the batches in flight, queues its work on the handle's main stream and returns after completion.  The workspaces
+ * belong to the handle: made at the first call, grown when a call needs more. */
+int  ft8rx_pan(ft8rx_handle* h, const void* d_samples, int kind, uint64_t n_samples, int n_fft, int n_avg, float* rows, int32_t* stats,
+               uint64_t* n_rows_out);
+/* the same from host memory: the samples are copied into a device buffer of the handle first */
+int  ft8rx_pan_host(ft8rx_handle* h, const void* samples, int kind, uint64_t n_samples, int n_fft, int n_avg, float* rows, int32_t* stats,
+                    uint64_t* n_rows_out);
+/* The stream: one per handle, independent of every other stream of the handle.  open allocates everything (a work buffer of
+ * n_fft - 1 + max_push samples, a leftover of n_fft, a page-locked chunk, one tile of window powers, the ring of n_rows + 1 rows),
+ * close or ft8rx_destroy releases it, nothing is allocated in between.  n_rows in [1, 65536]: the finished rows the ring keeps;
+ * n_origin: the absolute index of the first sample, at most 2^53. */
+int  ft8rx_pan_stream_open(ft8rx_handle* h, int kind, int n_fft, int n_avg, int n_rows, uint64_t n_origin, uint64_t max_push);
+/* n_new in [0, max_push] samples from host memory or (on_device) device memory, copied once into the work buffer: *d_samples = the
+ * device address of the chunk's first sample there, valid until the next push -- what a down-converter's device push takes, so that a
+ * chunk crosses the bus once; *rows_done = the first row that is not complete yet.  Each may be NULL.  Queued on the handle's main
+ * stream; does not wait for it. */
+int  ft8rx_pan_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, void** d_samples, uint64_t* rows_done);
+/* the finished rows [r_first, r_first + n) -> rows, host [n][bins], and stats, host [n][2] (each may be NULL); rows that are not
+ * complete yet or that the ring no longer holds are refused, naming the rows it holds.  Returns after completion. */
+int  ft8rx_pan_stream_read(ft8rx_handle* h, uint64_t r_first, int n, float* rows, int32_t* stats);
+/* samples pushed, the first row that is not complete, the oldest row the ring holds, bins per row; each may be NULL */
+int  ft8rx_pan_stream_info(ft8rx_handle* h, uint64_t* n_pushed, uint64_t* rows_done, uint64_t* r_lo, int* bins);
+int  ft8rx_pan_stream_close(ft8rx_handle* h);
 /* Local re-search of the reference's subtraction experiment (tests/pipeline/receiver_sub.py:434-445: after a signal has been
  * subtracted, search(f0_idx - 2 .. f0_idx + 1, ignore_sync_score_min = True)): mask[n_frames][cfg.f0_hi - cfg.f0_lo], one byte per
  * search column.  While a mask is set, the candidate selection of every batch (Receiver.search, receiver.py:338-367) takes ONLY the

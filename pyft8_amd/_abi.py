@@ -118,6 +118,16 @@ PROTOTYPES = {
     "ft8rx_blank_in_stream_info": (INT, (PTR, PTR, PTR, PTR)),
     "ft8rx_blank_in_stream_close": (INT, (PTR,)),
     "ft8rx_blank_in_released": (INT, (U64, U64, INT, INT, INT, PTR)),
+    # panorama
+    "ft8rx_pan_window": (INT, (INT, PTR, INT)),
+    "ft8rx_pan_rows_done": (INT, (U64, U64, INT, INT, PTR)),
+    "ft8rx_pan": (INT, (PTR, PTR, INT, U64, INT, INT, PTR, PTR, PTR)),
+    "ft8rx_pan_host": (INT, (PTR, PTR, INT, U64, INT, INT, PTR, PTR, PTR)),
+    "ft8rx_pan_stream_open": (INT, (PTR, INT, INT, INT, INT, U64, U64)),
+    "ft8rx_pan_stream_push": (INT, (PTR, PTR, U64, INT, PTR, PTR)),
+    "ft8rx_pan_stream_read": (INT, (PTR, U64, INT, PTR, PTR)),
+    "ft8rx_pan_stream_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_pan_stream_close": (INT, (PTR,)),
     # stage entry points
     "ft8rx_spectrogram": (INT, (PTR, PTR, INT, PTR)),
     "ft8rx_hop_spectrum": (INT, (PTR, PTR, PTR)),

@@ -1148,6 +1148,76 @@ class Handle:
         self._chk(self._L.ft8rx_blank_in_stream_close(self._h), "ft8rx_blank_in_stream_close")
         self._bis = None
 
+    # ---- panorama (ft8rx_pan*; pyft8_amd/pan.py holds the twin, the parameter checks and the axes)
+    @staticmethod
+    def _pan_stats(kind, stats):
+        from . import kinds as _k
+        return stats.astype(np.int64) if _k.is_integer(kind) else None
+
+    def pan(self, samples, kind, n_fft=2048, n_avg=1, d_ptr=None, n=None):
+        """ft8rx_pan_host / ft8rx_pan: the panorama of ONE stream's samples of `kind` (forms of pan.pack; d_ptr, n: on the device
+        already) -> (rows float32 [n_rows, bins] = sums of n_avg window powers, stats int64 [n_rows, 2] = (samples at a rail, largest
+        |c|), None for a float kind)."""
+        from . import pan as _pan
+        if d_ptr is None:
+            a, n = _pan.pack(samples, kind)
+            entry, name, src = self._L.ft8rx_pan_host, "ft8rx_pan_host", a.ctypes.data
+        else:
+            entry, name, src, n = self._L.ft8rx_pan, "ft8rx_pan", int(d_ptr), int(n)
+        n_rows = max(n // max(int(n_fft), 1) // max(int(n_avg), 1), 0)
+        rows = np.zeros((n_rows, _pan.bins(kind, max(int(n_fft), 2))), np.float32)
+        stats = np.zeros((n_rows, 2), np.int32)
+        cnt = C.c_uint64()
+        self._chk(entry(self._h, src, int(kind), n, int(n_fft), int(n_avg), rows.ctypes.data, stats.ctypes.data, C.byref(cnt)), name)
+        if int(cnt.value) != n_rows:
+            raise Ft8rxError(f"{name}: {cnt.value} rows, expected {n_rows}")
+        return rows, self._pan_stats(kind, stats)
+
+    def pan_host(self, samples, kind, n_fft=2048, n_avg=1):
+        return self.pan(samples, kind, n_fft, n_avg)
+
+    def pan_stream_open(self, kind, n_fft=2048, n_avg=1, n_rows=256, n_origin=0, max_push=1 << 20):
+        """Open the handle's panorama stream (one per handle, independent of every other stream): everything is allocated here and
+        released by pan_stream_close."""
+        self._chk(self._L.ft8rx_pan_stream_open(self._h, int(kind), int(n_fft), int(n_avg), int(n_rows), int(n_origin), int(max_push)),
+                  "ft8rx_pan_stream_open")
+        self._pans = int(kind)
+
+    def pan_stream_push(self, samples=None, d_ptr=None, n=None):
+        """Push the next samples (forms of pan.pack, 0 .. max_push; d_ptr, n: on the device already) -> (d_samples, rows_done): the raw
+        device address of the chunk's first sample in the stream's work buffer, valid until the next push (what a down-converter's
+        d_ptr push takes), and the first row that is not complete yet."""
+        from . import pan as _pan
+        if getattr(self, "_pans", None) is None:
+            raise Ft8rxError("pan_stream_push: no panorama stream is open (pan_stream_open)")
+        out, done = C.c_void_p(), C.c_uint64()
+        if d_ptr is not None:
+            args = (int(d_ptr), int(n), 1)
+        elif samples is None:
+            args = (None, 0, 0)
+        else:
+            a, n = _pan.pack(samples, self._pans)
+            args = (a.ctypes.data, n, 0)
+        self._chk(self._L.ft8rx_pan_stream_push(self._h, *args, C.byref(out), C.byref(done)), "ft8rx_pan_stream_push")
+        return int(out.value or 0), int(done.value)
+
+    def pan_stream_info(self):
+        """-> {"n_pushed", "rows_done", "r_lo", "bins"}: samples pushed, the first row not complete, the oldest row held, bins per row"""
+        p, d, lo, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+        self._chk(self._L.ft8rx_pan_stream_info(self._h, C.byref(p), C.byref(d), C.byref(lo), C.byref(b)), "ft8rx_pan_stream_info")
+        return {"n_pushed": int(p.value), "rows_done": int(d.value), "r_lo": int(lo.value), "bins": int(b.value)}
+
+    def pan_stream_read(self, r_first, n):
+        """The finished rows [r_first, r_first + n) -> (rows float32 [n, bins], stats int64 [n, 2] or None for a float kind)"""
+        bins = self.pan_stream_info()["bins"]
+        rows, stats = np.zeros((max(int(n), 0), bins), np.float32), np.zeros((max(int(n), 0), 2), np.int32)
+        self._chk(self._L.ft8rx_pan_stream_read(self._h, int(r_first), int(n), rows.ctypes.data, stats.ctypes.data), "ft8rx_pan_stream_read")
+        return rows, self._pan_stats(self._pans, stats)
+
+    def pan_stream_close(self):
+        self._chk(self._L.ft8rx_pan_stream_close(self._h), "ft8rx_pan_stream_close")
+        self._pans = None
+
     def pinned_audio(self, n_frames):
         """int16 [n_frames, 180000] array in page-locked host memory (ft8rx_alloc_host): fill it and pass it to decode_batch for
         overlapped DMA.  The memory is released when the array (and every view of it) is garbage collected."""

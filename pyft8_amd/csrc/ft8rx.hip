@@ -67,6 +67,7 @@
 #include "kernels/ddc_rat.hpp"
 #include "kernels/blanker.hpp"
 #include "kernels/blank_in.hpp"
+#include "kernels/pan.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -77,6 +78,7 @@
 #include "ddc_wide_ring.hpp"
 #include "ddc_rat_ring.hpp"
 #include "blank_in_ring.hpp"
+#include "pan_ring.hpp"
 #include "optins.hpp"
 #include "ilp_launch.hpp"       // k_fine, k_spectrogram and k_hop_spectrum are launched from the second translation unit (ft8rx_ilp.hip)
 
@@ -283,6 +285,23 @@ struct ft8rx_handle {
         BlankInWs ws;
         hipEvent_t ev = nullptr;
     } bis;
+    // panorama (ft8rx_pan*, kernels/pan.hpp).  PanWs: what a run works in -- the window's weights [n_fft], the
+    // powers [tile_w][bins] and statistics [tile_w][2] of one tile of windows, the rows [slots][bins] and their statistics [slots][2].
+    // d_pan_tw: the twiddles [8192], made with the one-shot entries' weight table at the first use of either.  pan: the one-shot
+    // entries' (grown on demand; slots = the rows of the call), with the host entry's sample buffer d_pan_in.  pans: the stream --
+    // everything allocated by open and released by close (or destroy): the work buffer [leftover | chunk], the leftover's own copy,
+    // the page-locked chunk.
+    struct PanWs { float* d_win = nullptr; int win_n = 0; float* d_pw = nullptr; int32_t* d_wstat = nullptr; size_t tile_w = 0;
+                   float* d_ring = nullptr; int32_t* d_rstat = nullptr; size_t slots = 0; } pan;
+    cpx* d_pan_tw = nullptr; size_t pan_pw_cap = 0, pan_wstat_cap = 0, pan_ring_cap = 0, pan_rstat_cap = 0;
+    void* d_pan_in = nullptr; size_t pan_in_cap = 0;
+    struct PanStream {
+        bool open = false; int fmt = 0, N = 0, A = 0, n_rows = 0;
+        int64_t n_origin = 0, pushed = 0, max_push = 0;
+        char* d_work = nullptr; char* d_left = nullptr; char* h_stage = nullptr;
+        PanWs ws;
+        hipEvent_t ev = nullptr;
+    } pans;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -369,7 +388,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -560,6 +579,7 @@ void ft8rx_destroy(ft8rx_handle* h) {
     if (h->ds.ev) hipEventDestroy(h->ds.ev);
     if (h->ps.ev) hipEventDestroy(h->ps.ev);
     if (h->bis.ev) hipEventDestroy(h->bis.ev);
+    if (h->pans.ev) hipEventDestroy(h->pans.ev);
     for (ResultSlot& sl : h->slots) {
         if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
         if (sl.ev_done) hipEventDestroy(sl.ev_done);
@@ -2657,6 +2677,287 @@ int ft8rx_blank_in_stream_close(ft8rx_handle* h) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes, and what consumed the released samples
     blank_in_stream_release(h);
+    return 0;
+}
+
+// ---- panorama (kernels/pan.hpp; the index arithmetic is pan_ring.hpp's)
+#define PAN_TILE_BYTES ((size_t)32 << 20)      /* the powers of one tile of windows: what k_pan_power writes and k_pan_rows reads back */
+static_assert(FT8RX_PAN_MIN_FFT == 256 && FT8RX_PAN_MAX_FFT == PAN_TW_N && FT8RX_PAN_MIN_FFT / 2 % PAN_ROWS_NT == 0 && PAN_ROWS_NT == 128 &&
+              (uint64_t)FT8RX_PAN_MAX_FFT * FT8RX_PAN_MAX_AVG <= (1ull << 29), "panorama geometry: bins in 128s, a row's count in int32");
+// the text of a refusal -> err (host only: ft8rx_pan_rows_done has no handle), or nullptr
+static const char* pan_refusal(int kind, bool with_kind, int n_fft, int n_avg, char* err, size_t cap) {
+    if (with_kind && sample_fmt(kind) < 0) snprintf(err, cap, "kind %d is none of the sample kinds (FT8RX_DDC_*, FT8RX_WIDE_*)", kind);
+    else if (n_fft < FT8RX_PAN_MIN_FFT || n_fft > FT8RX_PAN_MAX_FFT || (n_fft & (n_fft - 1)))
+        snprintf(err, cap, "n_fft %d is not a power of two in [%d, %d]", n_fft, FT8RX_PAN_MIN_FFT, FT8RX_PAN_MAX_FFT);
+    else if (n_avg < 1 || n_avg > FT8RX_PAN_MAX_AVG) snprintf(err, cap, "n_avg %d outside [1, %d]", n_avg, FT8RX_PAN_MAX_AVG);
+    else return nullptr;
+    return err;
+}
+static int pan_check(ft8rx_handle* h, const char* who, int kind, int n_fft, int n_avg) {
+    char text[200];
+    if (!pan_refusal(kind, true, n_fft, n_avg, text, sizeof(text))) return sample_fmt(kind);
+    set_err(h, "%s: %s", who, text);
+    return -1;
+}
+
+// the periodic Hann window, in double, rounded once
+static void pan_window(int N, float* w) {
+    for (int i = 0; i < N; i++) w[i] = (float)(0.5 * (1.0 - cos(2.0 * M_PI * (double)i / (double)N)));
+}
+int ft8rx_pan_window(int n_fft, float* w, int cap) {
+    char text[200];
+    if (pan_refusal(0, false, n_fft, 1, text, sizeof(text))) return -1;
+    if (w && cap > 0) {
+        std::vector<float> t((size_t)n_fft);
+        pan_window(n_fft, t.data());
+        memcpy(w, t.data(), sizeof(float) * (size_t)(cap < n_fft ? cap : n_fft));
+    }
+    return n_fft;
+}
+int ft8rx_pan_rows_done(uint64_t n_origin, uint64_t n_end, int n_fft, int n_avg, uint64_t* rows) {
+    char text[200];
+    if (pan_refusal(0, false, n_fft, n_avg, text, sizeof(text))) return -1;
+    if (n_end < n_origin || n_end > ((uint64_t)1 << 62)) return -1;
+    if (rows) {
+        rows[0] = (uint64_t)panring::r_first((int64_t)n_origin, n_fft, n_avg);
+        rows[1] = (uint64_t)panring::rows_done((int64_t)n_origin, (int64_t)n_end, n_fft, n_avg);
+    }
+    return 0;
+}
+
+// the twiddles W_8192^k: the quarter turn in double, the quadrants by exact rotation, rounded once; and the one-shot entries' weight table
+static int pan_tables(ft8rx_handle* h) {
+    if (ws_ready(h, WS_PAN)) return 0;
+    std::vector<cpx> tw((size_t)PAN_TW_N);
+    for (int k = 0; k < PAN_TW_N; k++) {
+        const int q = k / (PAN_TW_N / 4), r = k % (PAN_TW_N / 4);
+        const double c = r ? cos(2.0 * M_PI * r / PAN_TW_N) : 1.0, s = r ? sin(2.0 * M_PI * r / PAN_TW_N) : 0.0;      // e^(-i a) = (c, -s)
+        const double re[4] = {c, -s, -c, s}, im[4] = {-s, -c, s, c};                                           // times (-i)^q
+        tw[(size_t)k] = make_float2((float)re[q], (float)im[q]);
+    }
+    FirstUse F(h, WS_PAN);
+    F.dev(&h->d_pan_tw, tw.size());
+    F.dev(&h->pan.d_win, (size_t)PAN_TW_N);
+    FIRST_HIP(F, hipMemcpy(h->d_pan_tw, tw.data(), sizeof(cpx) * tw.size(), hipMemcpyHostToDevice));
+    return F.done();
+}
+// windows per tile of a workspace for `bins` bins that never sees more than max_win windows in one run
+static size_t pan_tile_cap(int bins, int64_t max_win) {
+    const size_t t = PAN_TILE_BYTES / (sizeof(float) * (size_t)bins);
+    return (int64_t)t < max_win ? t : (size_t)(max_win > 1 ? max_win : 1);
+}
+
+// The launches of the windows [w0, w0 + n_win) on the main stream: x = the first sample of window w0.
+static int pan_run(ft8rx_handle* h, const ft8rx_handle::PanWs& w, int fmt, int N, int A, const char* x, int64_t w0, int64_t n_win) {
+    const bool iq = sf_is_iq(fmt), aligned = ((uintptr_t)x % sf_sample_bytes(fmt)) == 0;
+    const int bins = iq ? N : N / 2;
+    const size_t sb = sf_sample_bytes(fmt);
+    for (int64_t t = 0; t < n_win; t += (int64_t)w.tile_w) {
+        const int64_t nw = n_win - t < (int64_t)w.tile_w ? n_win - t : (int64_t)w.tile_w, wa = w0 + t;
+        const char* xt = x + (size_t)t * (size_t)N * sb;
+        auto power = [&](auto n, auto q, auto al) {
+            constexpr int NN = decltype(n)::value;
+            k_pan_power<NN, decltype(q)::value, decltype(al)::value><<<(unsigned)nw, pan_nt(NN), 0, h->stream>>>(xt, fmt, w.d_win, h->d_pan_tw, w.d_pw, w.d_wstat);
+        };
+        with_bool(iq, [&](auto q) { with_bool(aligned, [&](auto al) {
+            switch (N) {
+                case 256: power(std::integral_constant<int, 256>(), q, al); break;
+                case 512: power(std::integral_constant<int, 512>(), q, al); break;
+                case 1024: power(std::integral_constant<int, 1024>(), q, al); break;
+                case 2048: power(std::integral_constant<int, 2048>(), q, al); break;
+                case 4096: power(std::integral_constant<int, 4096>(), q, al); break;
+                default: power(std::integral_constant<int, 8192>(), q, al); break;
+            }
+        }); });
+        const int64_t ra = wa / A, rb = (wa + nw - 1) / A;
+        k_pan_rows<<<dim3((unsigned)(rb - ra + 1), (unsigned)(bins / PAN_ROWS_NT + 1)), PAN_ROWS_NT, 0, h->stream>>>(
+            w.d_pw, w.d_wstat, (long long)wa, (int)nw, (long long)A, bins, (long long)ra, w.d_ring, w.d_rstat, (long long)w.slots);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the one-shot on n samples at d: the stream with n_origin = 0 and a ring that holds every row
+static int pan_oneshot(ft8rx_handle* h, const char* who, const char* d, int fmt, uint64_t n_samples, int N, int A, float* rows, int32_t* stats, uint64_t* n_rows_out) {
+    const int64_t R = (int64_t)(n_samples / (uint64_t)N) / A;
+    if (n_rows_out) *n_rows_out = (uint64_t)R;
+    if (R == 0 || (!rows && !stats)) return 0;
+    const int bins = sf_is_iq(fmt) ? N : N / 2;
+    if (pan_tables(h)) return -2;
+    ft8rx_handle::PanWs& w = h->pan;
+    const size_t tile = pan_tile_cap(bins, R * A);
+    if (grow_dev(h, who, (void**)&w.d_pw, &h->pan_pw_cap, sizeof(float) * tile * (size_t)bins) ||
+        grow_dev(h, who, (void**)&w.d_wstat, &h->pan_wstat_cap, sizeof(int32_t) * 2 * tile) ||
+        grow_dev(h, who, (void**)&w.d_ring, &h->pan_ring_cap, sizeof(float) * (size_t)R * (size_t)bins) ||
+        grow_dev(h, who, (void**)&w.d_rstat, &h->pan_rstat_cap, sizeof(int32_t) * 2 * (size_t)R)) return -2;
+    w.tile_w = tile; w.slots = (size_t)R;
+    if (w.win_n != N) {                                   // another n_fft than the last call's: nothing queued reads the old table any more
+        std::vector<float> t((size_t)N);
+        pan_window(N, t.data());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(w.d_win, t.data(), sizeof(float) * (size_t)N, hipMemcpyHostToDevice));
+        w.win_n = N;
+    }
+    if (const int rc = pan_run(h, w, fmt, N, A, d, 0, R * A)) return rc;
+    if (rows) HIPCHK(h, hipMemcpyAsync(rows, w.d_ring, sizeof(float) * (size_t)R * (size_t)bins, hipMemcpyDeviceToHost, h->stream));
+    if (stats) HIPCHK(h, hipMemcpyAsync(stats, w.d_rstat, sizeof(int32_t) * 2 * (size_t)R, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+static int pan_n_check(ft8rx_handle* h, const char* who, uint64_t n_samples) {
+    if (n_samples <= FT8RX_PAN_MAX_SAMPLES) return 0;
+    set_err(h, "%s: n_samples %llu outside [0, %llu]", who, (unsigned long long)n_samples, (unsigned long long)FT8RX_PAN_MAX_SAMPLES);
+    return -1;
+}
+
+int ft8rx_pan(ft8rx_handle* h, const void* d_samples, int kind, uint64_t n_samples, int n_fft, int n_avg, float* rows, int32_t* stats, uint64_t* n_rows_out) {
+    if (!h) return -1;
+    const int fmt = pan_check(h, "ft8rx_pan", kind, n_fft, n_avg);
+    if (fmt < 0 || pan_n_check(h, "ft8rx_pan", n_samples)) return -1;
+    if (!d_samples || ((uintptr_t)d_samples % sf_component_bytes(fmt)) != 0) { set_err(h, "ft8rx_pan: d_samples is NULL or not aligned to a component"); return -1; }
+    ENTER(h);
+    return pan_oneshot(h, "ft8rx_pan", (const char*)d_samples, fmt, n_samples, n_fft, n_avg, rows, stats, n_rows_out);
+}
+
+int ft8rx_pan_host(ft8rx_handle* h, const void* samples, int kind, uint64_t n_samples, int n_fft, int n_avg, float* rows, int32_t* stats, uint64_t* n_rows_out) {
+    if (!h) return -1;
+    const int fmt = pan_check(h, "ft8rx_pan_host", kind, n_fft, n_avg);
+    if (fmt < 0 || pan_n_check(h, "ft8rx_pan_host", n_samples)) return -1;
+    if (!samples) { set_err(h, "ft8rx_pan_host: samples is NULL"); return -1; }
+    ENTER(h);
+    const size_t bytes = (size_t)(n_samples / (uint64_t)n_fft / (uint64_t)n_avg) * (size_t)n_avg * (size_t)n_fft * sf_sample_bytes(fmt);      // whole rows only
+    if (bytes) {
+        if (grow_dev(h, "ft8rx_pan_host", &h->d_pan_in, &h->pan_in_cap, bytes)) return -2;
+        HIPCHK(h, hipMemcpyAsync(h->d_pan_in, samples, bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));         // the caller's memory is free again
+    }
+    return pan_oneshot(h, "ft8rx_pan_host", (const char*)h->d_pan_in, fmt, n_samples, n_fft, n_avg, rows, stats, n_rows_out);
+}
+
+static void pan_stream_release(ft8rx_handle* h) {
+    ft8rx_handle::PanStream& s = h->pans;
+    release_dev(h, s.d_work); release_dev(h, s.d_left); release_host(h, s.h_stage);
+    release_dev(h, s.ws.d_win); release_dev(h, s.ws.d_pw); release_dev(h, s.ws.d_wstat); release_dev(h, s.ws.d_ring); release_dev(h, s.ws.d_rstat);
+    const hipEvent_t ev = s.ev;
+    s = ft8rx_handle::PanStream();
+    s.ev = ev;
+}
+
+int ft8rx_pan_stream_open(ft8rx_handle* h, int kind, int n_fft, int n_avg, int n_rows, uint64_t n_origin, uint64_t max_push) {
+    if (!h) return -1;
+    const char* who = "ft8rx_pan_stream_open";
+    if (h->pans.open) { set_err(h, "%s: a panorama stream is open on this handle already (ft8rx_pan_stream_close)", who); return -1; }
+    const int fmt = pan_check(h, who, kind, n_fft, n_avg);
+    if (fmt < 0) return -1;
+    if (n_rows < 1 || n_rows > FT8RX_PAN_MAX_ROWS) { set_err(h, "%s: n_rows %d outside [1, %d]", who, n_rows, FT8RX_PAN_MAX_ROWS); return -1; }
+    if (n_origin > ((uint64_t)1 << 53)) { set_err(h, "%s: n_origin %llu beyond 2^53", who, (unsigned long long)n_origin); return -1; }
+    if (max_push < 1 || max_push > FT8RX_PAN_MAX_PUSH) {
+        set_err(h, "%s: max_push %llu outside [1, %llu]", who, (unsigned long long)max_push, (unsigned long long)FT8RX_PAN_MAX_PUSH); return -1;
+    }
+    ENTER(h);
+    if (pan_tables(h)) return -2;
+    ft8rx_handle::PanStream& s = h->pans;
+    const size_t sb = sf_sample_bytes(fmt);
+    const int bins = sf_is_iq(fmt) ? n_fft : n_fft / 2;
+    const size_t slots = (size_t)panring::slots(n_rows);
+    const size_t tile = (size_t)panring::tile_windows((int64_t)pan_tile_cap(bins, (int64_t)(max_push / (uint64_t)n_fft) + 1), n_rows, n_avg);
+    std::vector<float> win((size_t)n_fft);
+    pan_window(n_fft, win.data());
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if (!s.ev) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
+    if (e != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (!rc) rc = dalloc(h, &s.d_work, (size_t)panring::capacity(n_fft, (int64_t)max_push) * sb);
+    if (!rc) rc = dalloc(h, &s.d_left, (size_t)n_fft * sb);
+    if (!rc) rc = halloc(h, &s.h_stage, (size_t)max_push * sb);
+    if (!rc) rc = dalloc(h, &s.ws.d_win, (size_t)n_fft);
+    if (!rc) rc = dalloc(h, &s.ws.d_pw, tile * (size_t)bins);
+    if (!rc) rc = dalloc(h, &s.ws.d_wstat, 2 * tile);
+    if (!rc) rc = dalloc(h, &s.ws.d_ring, slots * (size_t)bins);
+    if (!rc) rc = dalloc(h, &s.ws.d_rstat, 2 * slots);
+    if (!rc && (e = hipMemcpy(s.ws.d_win, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice)) != hipSuccess) { set_err(h, "%s: %s", who, hipGetErrorString(e)); rc = -2; }
+    if (rc) { pan_stream_release(h); return -2; }
+    s.ws.win_n = n_fft; s.ws.tile_w = tile; s.ws.slots = slots;
+    s.fmt = fmt; s.N = n_fft; s.A = n_avg; s.n_rows = n_rows;
+    s.n_origin = (int64_t)n_origin; s.pushed = 0; s.max_push = (int64_t)max_push; s.open = true;
+    return 0;
+}
+
+int ft8rx_pan_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int on_device, void** d_samples, uint64_t* rows_done) {
+    if (!h) return -1;
+    const char* who = "ft8rx_pan_stream_push";
+    ft8rx_handle::PanStream& s = h->pans;
+    if (!s.open) { set_err(h, "%s: no panorama stream is open (ft8rx_pan_stream_open)", who); return -1; }
+    if (n_new > (uint64_t)s.max_push) { set_err(h, "%s: n_new %llu outside [0, %llu] (max_push)", who, (unsigned long long)n_new, (unsigned long long)s.max_push); return -1; }
+    const size_t sb = sf_sample_bytes(s.fmt), align = sf_component_bytes(s.fmt);
+    if (n_new && (!in || (on_device && ((uintptr_t)in % align) != 0))) { set_err(h, "%s: in is NULL or not aligned to a component", who); return -1; }
+    if (s.n_origin + s.pushed + (int64_t)n_new > ((int64_t)1 << 54)) { set_err(h, "%s: n_new %llu takes the stream past index 2^54", who, (unsigned long long)n_new); return -1; }
+    // (no ENTER: a push touches the stream's own buffers only, on the main stream; batches in flight read none of them)
+    HIPCHK(h, hipSetDevice(h->device));
+    const panring::Plan p = panring::plan(s.n_origin, s.n_origin + s.pushed, (int64_t)n_new, s.N, s.A);
+    // [leftover | chunk]: behind whatever read the last chunk from this buffer (the front end's device push is on the same stream)
+    if (p.left_n > 0) HIPCHK(h, hipMemcpyAsync(s.d_work, s.d_left, (size_t)p.left_n * sb, hipMemcpyDeviceToDevice, h->stream));
+    char* dst = s.d_work + (size_t)p.chunk_at * sb;
+    if (n_new) {
+        if (on_device) {
+            HIPCHK(h, hipMemcpyAsync(dst, in, (size_t)n_new * sb, hipMemcpyDeviceToDevice, h->stream));
+        } else {                                         // through the page-locked buffer, once the previous push's copy has left it
+            HIPCHK(h, hipEventSynchronize(s.ev));
+            memcpy(s.h_stage, in, (size_t)n_new * sb);
+            HIPCHK(h, hipMemcpyAsync(dst, s.h_stage, (size_t)n_new * sb, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipEventRecord(s.ev, h->stream));
+        }
+    }
+    if (p.w1 > p.w0)
+        if (const int rc = pan_run(h, s.ws, s.fmt, s.N, s.A, s.d_work + (size_t)p.first_at * sb, p.w0, p.w1 - p.w0)) return rc;
+    if (p.keep_n > 0) HIPCHK(h, hipMemcpyAsync(s.d_left, s.d_work + (size_t)p.keep_at * sb, (size_t)p.keep_n * sb, hipMemcpyDeviceToDevice, h->stream));
+    s.pushed += (int64_t)n_new;
+    if (d_samples) *d_samples = dst;
+    if (rows_done) *rows_done = (uint64_t)p.r1;
+    return 0;
+}
+
+int ft8rx_pan_stream_read(ft8rx_handle* h, uint64_t r_first, int n, float* rows, int32_t* stats) {
+    if (!h) return -1;
+    const char* who = "ft8rx_pan_stream_read";
+    const ft8rx_handle::PanStream& s = h->pans;
+    if (!s.open) { set_err(h, "%s: no panorama stream is open (ft8rx_pan_stream_open)", who); return -1; }
+    const panring::Held held = panring::held(s.n_origin, s.n_origin + s.pushed, s.N, s.A, s.n_rows);
+    if (n < 0 || (int64_t)r_first < held.r_lo || r_first > (uint64_t)held.r_hi || (int64_t)r_first + n > held.r_hi) {
+        set_err(h, "%s: r_first %llu, n %d: the ring holds the rows [%lld, %lld)", who, (unsigned long long)r_first, n, (long long)held.r_lo, (long long)held.r_hi);
+        return -1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bins = sf_is_iq(s.fmt) ? (size_t)s.N : (size_t)s.N / 2;
+    for (int i = 0; i < n;) {                            // in runs that do not wrap
+        const size_t slot = (size_t)((r_first + (uint64_t)i) % s.ws.slots);
+        const int run = (size_t)(n - i) < s.ws.slots - slot ? n - i : (int)(s.ws.slots - slot);
+        if (rows) HIPCHK(h, hipMemcpyAsync(rows + (size_t)i * bins, s.ws.d_ring + slot * bins, sizeof(float) * (size_t)run * bins, hipMemcpyDeviceToHost, h->stream));
+        if (stats) HIPCHK(h, hipMemcpyAsync(stats + 2 * (size_t)i, s.ws.d_rstat + 2 * slot, sizeof(int32_t) * 2 * (size_t)run, hipMemcpyDeviceToHost, h->stream));
+        i += run;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ft8rx_pan_stream_info(ft8rx_handle* h, uint64_t* n_pushed, uint64_t* rows_done, uint64_t* r_lo, int* bins) {
+    if (!h) return -1;
+    const ft8rx_handle::PanStream& s = h->pans;
+    if (!s.open) { set_err(h, "ft8rx_pan_stream_info: no panorama stream is open (ft8rx_pan_stream_open)"); return -1; }
+    const panring::Held held = panring::held(s.n_origin, s.n_origin + s.pushed, s.N, s.A, s.n_rows);
+    if (n_pushed) *n_pushed = (uint64_t)s.pushed;
+    if (rows_done) *rows_done = (uint64_t)held.r_hi;
+    if (r_lo) *r_lo = (uint64_t)held.r_lo;
+    if (bins) *bins = sf_is_iq(s.fmt) ? s.N : s.N / 2;
+    return 0;
+}
+
+int ft8rx_pan_stream_close(ft8rx_handle* h) {
+    if (!h) return -1;
+    if (!h->pans.open) { set_err(h, "ft8rx_pan_stream_close: no panorama stream is open"); return -1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // pushes, and what read the chunk from the work buffer
+    pan_stream_release(h);
     return 0;
 }
 

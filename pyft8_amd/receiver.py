@@ -29,6 +29,11 @@ Input blanker (extension): Receiver(..., input_blanker=T
 in front of the down-converter, which reads the blanked samples on the device; `input_blanker_stats` holds the cumulative counters.
 The live search grid / waterfall of the channels show the blanked input.  Off (the default) nothing of it runs.
 
+Panorama (extension): Receiver(..., sample_rate=..., panorama=True | {"n_fft", "n_avg" or "period_s", "rows"}),
+and the same keyword on decode_stream, keeps the averaged power spectrum of ONE raw input stream at its own rate and the count of
+samples at the converter's rails (ft8rx_pan*), computed on the GPU from the samples the front end reads; `panorama` holds the rows,
+their statistics and the frequency axis.  Off (the default) nothing of it runs.
+
 Float frames (extension): float_frames=True -- on decode_frames / decode_frames_arrays / decode_frame with float32
 or float64 arrays, on decode_stream, or on Receiver(..., sample_rate=...) for the wide live input -- decodes unrounded float32 audio
 end to end: the level of the input no longer matters and no gain has to be chosen.  Off (the default) nothing changes: float arrays
@@ -43,6 +48,7 @@ from . import _lib
 from . import blanker as _blanker
 from . import messages as _m
 from . import optins as _optins
+from . import pan as _pan
 from . import wide_in as _wide_in
 
 T_CYC, SYM_RATE, SAMP_RATE = 15, 6.25, 12000
@@ -711,6 +717,12 @@ class Receiver:
         self.input_blanker = extension_knobs.pop("input_blanker", None)
         _wide_in.input_blanker_params(self.input_blanker, 17, 1, 240000)      # a value outside the definition is refused here
         self._input_blanker_stats = None
+        # panorama: None / True / a dict of n_fft, n_avg or period_s, rows.  An input stage beside the down-
+        # converter: the averaged power spectrum and rail count of ONE raw stream at its own rate (ft8rx_pan*) -- decode_stream (its own
+        # keyword overrides this one) and the wide live input.  `panorama` holds the result.
+        self.panorama_opt = extension_knobs.pop("panorama", None)
+        _pan.params(self.panorama_opt, 240000)                                # a value outside the definition is refused here
+        self._panorama = None
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall:
             _optins.refuse(_optins.RECALL, _optins.active(self.cfg))
@@ -742,7 +754,14 @@ class Receiver:
         """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
         if sample_rate is not None:
             self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
-                                           waterfall=waterfall, input_blanker=self.input_blanker, float_frames=self.float_frames)
+                                           waterfall=waterfall, input_blanker=self.input_blanker, float_frames=self.float_frames,
+                                           **({"panorama": self.panorama_opt} if self.panorama_opt else {}))
+
+    @property
+    def panorama(self):
+        """The panorama: the live stream's dict (wide_in.panorama), else the last decode_stream's; None while off"""
+        live = self.wide_in.panorama if self.wide_in is not None else None
+        return live if live is not None else self._panorama
 
     @property
     def input_blanker_stats(self):
@@ -1069,6 +1088,7 @@ class Receiver:
         float_frames= (default: the receiver's): the down-converter's output before rounding is decoded as float32
         frames -- a quiet wide source whose 12 kHz channels stay under one count of int16 decodes as at full level."""
         input_blanker = kw.pop("input_blanker", self.input_blanker)
+        pn = _pan.params(kw.pop("panorama", self.panorama_opt), int(sample_rate))
         f32 = self._float_frames(kw.pop("float_frames", None))
         dials = [float(f) for f in dial_offsets_hz]
         n_out = len(dials)
@@ -1088,15 +1108,27 @@ class Receiver:
                 raise TypeError(f"decode_stream() got an unexpected keyword argument '{k}'")
         args.update(kw)
         ib = _wide_in.input_blanker_params(input_blanker, kind, n_streams, int(sample_rate))
+        if pn is not None:
+            _pan.one_stream(True, n_streams)
         with self._hlock:
             h = self._handle(n_out)
             d_f32 = h.staging_ptr_f32() if f32 else None       # float frames: the audio before rounding, into the float staging buffer
             if ib is None:
+                if pn is not None:
+                    self._panorama = self._pan_result(h.pan(arr[0], kind, pn[0], pn[1]), kind, int(sample_rate), pn)
                 _wide_in.HANDLE_CALLS[mod][0](h, arr, kind, int(sample_rate), src, dials, d_f32)
             else:
                 d_ptr, n, self._input_blanker_stats = h.blank_in(arr[0], kind, *ib)
+                if pn is not None:                                 # what the front end sees: the blanked samples, on the device
+                    self._panorama = self._pan_result(h.pan(None, kind, pn[0], pn[1], d_ptr=d_ptr, n=n), kind, int(sample_rate), pn)
                 _wide_in.HANDLE_CALLS[mod][3](h, d_ptr, n, kind, int(sample_rate), src, dials, d_f32)
             return self._decode_frames_locked(None, n_out, bands=bands, f32=f32, **args)
+
+    @staticmethod
+    def _pan_result(res, kind, rate, pn):
+        """the one-shot's (rows, stats) as the dict of wide_in.WideIn.panorama: every row of the call, in order"""
+        return {"data": res[0], "stats": res[1], "r_next": len(res[0]), "f_hz": _pan.freqs(kind, rate, pn[0]), "row_seconds": pn[0] * pn[1] / float(rate),
+                "n_fft": pn[0], "n_avg": pn[1]}
 
     def _decode_frames_locked(self, audio, B, cyclestart_strings, return_records, passes, subtract_min_snr, sub_pass_osd, research="full",
                               recall=None, bands=None, f32=False):

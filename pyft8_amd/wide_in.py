@@ -17,6 +17,7 @@ from . import ddc as _ddc
 from . import ddc_wide as _dw
 from . import ddc_rat as _dr
 from . import blank_in as _bi
+from . import pan as _pan
 from . import kinds as _kinds
 
 NSAMP = _lib.NSAMP
@@ -233,6 +234,13 @@ class WideIn:
     off through float rounding, the grid keeps its phase.  The grid shows the audio before noise_blanker (section 17) but behind input_blanker (section 17.1),
     which works in front of the down-converter: with it the rows are those of the blanked input.  Off (the default) nothing of it exists.
 
+    panorama=True | {"n_fft", "n_avg" or "period_s", "rows"}: the device also keeps the averaged power
+    spectrum of the ONE raw stream at its own rate (ft8rx_pan_stream_*), behind input_blanker when that is on -- what the front end
+    sees.  After every push the rows it finished are read once into panorama["data"] (float32 [rows, bins], row r at r mod rows, zero
+    until written); panorama["stats"] holds their (samples at a rail, largest |c|), None for float samples; "r_next" is the first row
+    not there yet, "f_hz" the bins' frequencies, "row_seconds" a row's length; panorama_time(r) is the time of row r's first sample.
+    Without input_blanker the chunk goes to the device once, into the panorama's buffer, and the front end reads it there.
+
     push(chunk) takes the next samples in the forms of Receiver.decode_stream -- real int16 or float [n], complex [n] or int16 (I, Q)
     pairs [n, 2] with iq=True, several streams as [n_streams, n(, 2)] -- of any length, hands them to the down-converter on the
     receiver's live handle (created with max_frames = K) and notes the passes that have fallen due; Receiver.poll() gathers and decodes
@@ -241,7 +249,7 @@ class WideIn:
     source_exhausted."""
 
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False,
-                 waterfall=False, input_blanker=None, float_frames=False):
+                 waterfall=False, input_blanker=None, float_frames=False, panorama=None):
         self._rx = receiver
         # float_frames (DESIGN.md section 18): the stream keeps the float32 output ring (1.44 MB per channel), every pass gathers and
         # decodes float frames, and with waterfall=True the rows come from that ring
@@ -253,6 +261,11 @@ class WideIn:
         _bi.params(input_blanker, _bi.WIDE_IQ_I16, self.sample_rate)    # a value outside the definition is refused here
         self._ib = None                                                 # (block, threshold_q8, guard, taper) once the stream is open
         self._ib_done = False                                           # flush has finished it
+        # panorama: the keyword as given, refused here when outside the definition; the stream opens with the
+        # first chunk, which decides the kind
+        self._pan_opt = panorama
+        self._pan = _pan.params(panorama, self.sample_rate)             # (n_fft, n_avg, rows) or None
+        self.panorama = None
         # the path (front_end): ddc, or ONE stream through a pre-stage (ft8rx_ddc_wide_stream_* / ft8rx_ddc_rat_stream_*).  At a resampled
         # rate sample_rate / 12000 is no integer, so input counts become output counts by exact integer arithmetic at every rate (_outputs)
         self.mod = front_end(self.sample_rate, resample)
@@ -311,6 +324,15 @@ class WideIn:
             if ib is not None:
                 h.blank_in_stream_open(self.kind, *ib, n_origin=0, max_push=self.sample_rate)
                 self._ib = ib
+            if self._pan is not None:
+                _pan.one_stream(self._pan_opt, self.n_streams)
+                n_fft, n_avg, rows = self._pan
+                h.pan_stream_open(self.kind, n_fft, n_avg, rows, n_origin=0, max_push=self.sample_rate)
+                integer = _kinds.is_integer(self.kind)
+                self.panorama = {"data": np.zeros((rows, _pan.bins(self.kind, n_fft)), np.float32),
+                                 "stats": np.zeros((rows, 2), np.int64) if integer else None, "r_next": 0,
+                                 "f_hz": _pan.freqs(self.kind, self.sample_rate, n_fft), "row_seconds": n_fft * n_avg / float(self.sample_rate),
+                                 "n_fft": n_fft, "n_avg": n_avg}
             if self.waterfall:                   # the rows of every hop of the scheduler's cycles, behind whichever stream was opened
                 c0 = self.sched.cycle
                 self._grid_c0 = (c0, self.sched.cycle_start(c0))
@@ -325,6 +347,10 @@ class WideIn:
             h = self._rx._live_handle(self.n_channels)
             if self._ib is not None and real:
                 self._forward(h, h.blank_in_stream_push(a[0]), _kinds.sample_bytes(self.kind))
+            elif self.panorama is not None and real:         # the chunk crosses once, into the panorama's buffer; the front end reads it there
+                d_samples, r_done = h.pan_stream_push(a[0])
+                self.m_produced = HANDLE_CALLS[self.mod][4](h, d_samples, a.shape[1])
+                self._pan_read(h, r_done)
             else:
                 self.m_produced = HANDLE_CALLS[self.mod][2](h, a)
             if self.waterfall:
@@ -346,7 +372,28 @@ class WideIn:
         released, nothing pushed"""
         d_out, _, n_out = released
         for at in range(0, n_out, self.sample_rate):
+            if self.panorama is not None:
+                self._pan_read(h, h.pan_stream_push(None, d_ptr=d_out + at * sample_bytes, n=min(self.sample_rate, n_out - at))[1])
             self.m_produced = HANDLE_CALLS[self.mod][4](h, d_out + at * sample_bytes, min(self.sample_rate, n_out - at))
+
+    def _pan_read(self, h, r_done):
+        """The rows the last push finished, read once and written in place: row r at r mod rows"""
+        p = self.panorama
+        n_rows = len(p["data"])
+        r0 = max(p["r_next"], r_done - n_rows)
+        if r_done > r0:
+            rows, stats = h.pan_stream_read(r0, r_done - r0)
+            at = np.arange(r0, r_done) % n_rows
+            p["data"][at] = rows
+            if stats is not None:
+                p["stats"][at] = stats
+            p["r_next"] = r_done
+
+    def panorama_time(self, r):
+        """The time of the first sample of panorama row r on the scheduler's clock: t_first + r n_avg n_fft / sample_rate"""
+        if self._pan is None or self.t_first is None:
+            return None
+        return self.t_first + int(r) * self._pan[0] * self._pan[1] / float(self.sample_rate)
 
     def input_blanker_stats(self):
         """The input blanker's cumulative int64 [4] (hits, samples with w < 32768, with w = 0, blocks with L_b = 0), or None"""
