@@ -942,6 +942,60 @@ int  ft8rx_free_host(ft8rx_handle* h, void* p);               /* h may be NULL *
 /* arithmetic-contract probes: which 0 = log10f, 1 = tanhf; 2 = forward FFT of length n (x = interleaved complex) */
 int  ft8rx_math_probe(ft8rx_handle* h, int which, const float* x, int n, float* y);
 
+/* ---- FT4 (extension) ------------------------------------------------------
+ * Opt-in decoding of 7.5-s FT4 frames: int16 mono at 12 kHz, 90000 samples, nominal signal start 0.5 s into the slot.  FT4 shares
+ * FT8's 77-bit messages, CRC-14 and LDPC(174,91); the front end is its own (kernels/ft4.hpp; pyft8_amd/ft4.py is the float64 twin
+ * that defines it): a 618 x 577 dB grid (1152-point FFT every 144 samples: two bins per tone, four rows per symbol), a search over
+ * the four Costas blocks, per candidate a 9 x 5 fine sync on the audio (steps of 36 samples and 2.6042 Hz) and a symbol-synchronous
+ * demodulator; behind it BP(bp_nc0_b, bp_iters_b), then OSD(osd_single, osd_double) under a Hamming-distance gate, with the 77 bits
+ * descrambled between the CRC test and the validity predicate.  The layout does not depend on FT8RX_WIDE; the search range is
+ * 12.5 .. 5900 Hz and -0.5 .. +2.0 s unless ft8rx_ft4_set_range narrows it; max_cands is the handle's.
+ * Records: f0_idx = bin (10.41667 Hz), h0_idx = row (12 ms), ttweak = dt / 36 samples, ftweak = df / 2.60417 Hz, so that
+ *   t = (144 h0_idx + 36 ttweak) / 12000 s,  f = 10.41667 f0_idx + 2.60417 ftweak Hz (tone 0);
+ * snr_fine = the demodulator's report, score = the search score (grid_sd = fine_sd = score), ipass 4 / method FT8RX_M_LDPC_B for a BP
+ * decode, ipass 5 / FT8RX_M_OSD with osd_hd for an OSD decode; msg_lo / msg_hi hold the descrambled word.  Every decode logs one
+ * event.  Results are fetched and packaged through the FT8 calls (ft8rx_fetch_results, ft8rx_package_batch / _ext).
+ * The workspaces (1.6 MB per frame of max_frames, 2.1 KB per candidate slot) are allocated at the first FT4 call on a
+ * handle, all or nothing; a handle that never decodes FT4 allocates and launches nothing of this.
+ * FT4 runs with msg_types; it is refused, by name, while ft8rx_set_ap_calls, ft8rx_set_recall, ft8rx_set_weak, ft8rx_set_reports or
+ * the packed output is active.  No foreign FT4 signal has been decoded yet: the mode is pinned to the protocol constants and the twin. */
+#define FT8RX_FT4_NSAMP 90000
+#define FT8RX_FT4_ROWS  618
+#define FT8RX_FT4_COLS  577
+#define FT8RX_FT4_SYNC_MIN_DEFAULT   100.0f
+#define FT8RX_FT4_OSD_MAX_HD_DEFAULT 40      /* the largest gate without a false decode on 2048 noise frames (profiles/ft4_notes.md) */
+/* host int16 [n_frames][90000] -> records [n_frames][max_cands], counts, events [n_frames][FT8RX_EVENT_CAP], event_counts */
+int  ft8rx_ft4_decode_batch(ft8rx_handle* h, const int16_t* audio, int n_frames, ft8rx_record* records, int32_t* counts,
+                            ft8rx_event* events, int32_t* event_counts);
+/* the same on device-resident frames (4-byte aligned); the results are fetched with ft8rx_fetch_results */
+int  ft8rx_ft4_enqueue_batch(ft8rx_handle* h, const int16_t* d_audio, int n_frames);
+/* the knobs: the search threshold and OSD's distance gate; 0 = the default */
+int  ft8rx_ft4_set(ft8rx_handle* h, float sync_min, int32_t osd_max_hd);
+/* the search range in bins [f0_lo, f0_hi) within [0, 571) and rows [h0_lo, h0_hi) within [-1024, 1024); all four 0 = the default */
+int  ft8rx_ft4_set_range(ft8rx_handle* h, int32_t f0_lo, int32_t f0_hi, int32_t h0_lo, int32_t h0_hi);
+/* bytes of FT4 workspace the handle holds (0 until its first FT4 call) and the current knobs and range [4]; any pointer may be NULL */
+int  ft8rx_ft4_info(ft8rx_handle* h, uint64_t* workspace_bytes, float* sync_min, int32_t* osd_max_hd, int32_t* range);
+/* ft8rx_ft4_decode_batch followed by ft8rx_package_batch (msg_types = 0) -- with msg_types set, use ft8rx_ft4_decode_batch and
+ * ft8rx_package_batch_ext */
+int  ft8rx_ft4_decode_messages(ft8rx_handle* h, const int16_t* audio, int n_frames, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                               int n_threads, ft8rx_hashes* table, int32_t* flags);
+/* stage entry points (tests).  grid: dB [n_frames][618][577]; power (optional): the same layout before the logarithm */
+int  ft8rx_ft4_grid(ft8rx_handle* h, const int16_t* audio, int n_frames, float* grid, float* power);
+/* the search on caller-supplied grids -> per frame f0_idx / h0_idx / score [max_cands] in output order and counts; best_score /
+ * best_h0 (optional, [n_frames][f0_hi - f0_lo]): the per-bin maxima before threshold and neighbour suppression */
+int  ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int n_frames, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts,
+                    float* best_score, int32_t* best_h0);
+/* fine sync and demodulation of n (frame, f0, h0) triples -> tweak [n][2] = (dt / 36, df index), metric [n], llr [n][174], snr [n] */
+int  ft8rx_ft4_demod(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
+                     const int32_t* h0_idx, int32_t* tweak, float* metric, float* llr, int32_t* snr);
+/* ft8rx_ldpc / ft8rx_osd_ext on raw LLR vectors of FT4 codewords: the returned words are descrambled; mask = FT8RX_MT_* bits */
+int  ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,
+                    uint64_t* msg_hi, int32_t* n_its, int32_t* has_out, float* llr_out);
+int  ft8rx_ft4_osd(ft8rx_handle* h, const float* llr, int n, int singleflips, int doubleflips, int tripleflips, int max_hd, int32_t mask,
+                   int32_t* ok, uint64_t* msg_lo, uint64_t* msg_hi, int32_t* trial, int32_t* hd);
+/* 77-bit words -> the 105 transmitted tones, [n][105].  Host function, no GPU. */
+int  ft8rx_ft4_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n, uint8_t* tones);
+
 #ifdef __cplusplus
 }
 #endif

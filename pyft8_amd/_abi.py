@@ -151,6 +151,19 @@ PROTOTYPES = {
     "ft8rx_subtract": (INT, (PTR, PTR, INT, PTR, PTR, INT, INT, PTR)),
     "ft8rx_subtraction_list": (INT, (PTR, PTR, INT, PTR, INT, INT, INT, PTR, INT, PTR)),
     "ft8rx_encode_tones": (INT, (PTR, PTR, INT, PTR)),
+    # FT4 (7.5-s frames)
+    "ft8rx_ft4_decode_batch": (INT, (PTR, PTR, INT) + _RECS),
+    "ft8rx_ft4_enqueue_batch": (INT, (PTR, PTR, INT)),
+    "ft8rx_ft4_set": (INT, (PTR, F32, I32)),
+    "ft8rx_ft4_set_range": (INT, (PTR, I32, I32, I32, I32)),
+    "ft8rx_ft4_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_ft4_decode_messages": (INT, (PTR, PTR, INT) + _PKG),
+    "ft8rx_ft4_grid": (INT, (PTR, PTR, INT, PTR, PTR)),
+    "ft8rx_ft4_sync": (INT, (PTR, PTR, INT) + (PTR,) * 6),
+    "ft8rx_ft4_demod": (INT, (PTR, PTR, INT, INT) + (PTR,) * 7),
+    "ft8rx_ft4_ldpc": (INT, (PTR, PTR, INT, INT, INT, I32) + (PTR,) * 6),
+    "ft8rx_ft4_osd": (INT, (PTR, PTR, INT, INT, INT, INT, INT, I32) + (PTR,) * 5),
+    "ft8rx_ft4_encode_tones": (INT, (PTR, PTR, INT, PTR)),
     # host message layer
     "ft8rx_package_batch": (INT, _RECS + (INT, INT) + _PKG),
     "ft8rx_package_batch_ext": (INT, _RECS + (INT, INT) + _PKG + (I32,)),

@@ -31,6 +31,7 @@ MIN_H0_FD, MAX_H0_FD = -140, 220                    # FT8RX_MIN_H0_FD / _MAX_H0_
 MAX_F0, GRID_COLS_WIDE, SPEC_BINS_WIDE, MAX_F0_WIDE = 960, 1920, 96000, 1888      # Handle.grid_cols / .spec_bins hold the loaded variant's
 LADDER_GRID_CAP = 4 * 256 * 32                      # csrc/ft8rx.hip: the compiled grid cap of the ladder kernels (Handle.set_ladder_grid)
 MAX_CANDS_WIDE = 2048                               # FT8RX_MAX_CANDS of the wide build: more than any search range has f0 bins
+FT4_NSAMP, FT4_ROWS, FT4_COLS = 90000, 618, 577     # FT8RX_FT4_*: 7.5-s frames and their dB grid, the same in both builds
 
 
 class Config(C.Structure):
@@ -758,6 +759,100 @@ class Handle:
         self._chk(self._L.ft8rx_osd_ext(self._h, llr.ctypes.data, n, int(singleflips), int(doubleflips), int(tripleflips), int(max_hd),
                                       *[a.ctypes.data for a in (ok, lo, hi, trial, hd)]), "ft8rx_osd_ext")
         return (ok, lo, hi, trial, hd) if want_hd else (ok, lo, hi, trial)
+
+    # ---- FT4 (7.5-s frames; DESIGN.md section 19, pyft8_amd/ft4.py)
+    def _ft4_audio(self, audio, who):
+        audio = np.ascontiguousarray(audio, np.int16)
+        if audio.ndim == 1:
+            audio = audio[None]
+        if audio.ndim != 2 or audio.shape[1] != FT4_NSAMP or not 1 <= len(audio) <= self.max_frames:
+            raise Ft8rxError(f"{who}: audio must be int16 [1 <= n <= {self.max_frames}, {FT4_NSAMP}] (7.5 s at 12 kHz); got shape {audio.shape}")
+        return audio
+
+    def ft4_set(self, sync_min=None, osd_max_hd=None):
+        """ft8rx_ft4_set: the search threshold and OSD's distance gate of the FT4 batches enqueued afterwards (None = the default)."""
+        self._chk(self._L.ft8rx_ft4_set(self._h, float(sync_min or 0.0), int(osd_max_hd or 0)), "ft8rx_ft4_set")
+
+    def ft4_set_range(self, f0_lo=0, f0_hi=0, h0_lo=0, h0_hi=0):
+        """ft8rx_ft4_set_range: bins [f0_lo, f0_hi) of 10.4167 Hz and rows [h0_lo, h0_hi) of 12 ms (ft4.freq_range_to_f0 /
+        ft4.time_range_to_h0); all zero = the default, 12.5 .. 5900 Hz and -0.5 .. +2.0 s."""
+        self._chk(self._L.ft8rx_ft4_set_range(self._h, int(f0_lo), int(f0_hi), int(h0_lo), int(h0_hi)), "ft8rx_ft4_set_range")
+
+    def ft4_info(self):
+        """ft8rx_ft4_info -> dict(workspace_bytes (0 until the handle's first FT4 call), sync_min, osd_max_hd, range)."""
+        wb, sm, hd, rg = C.c_uint64(), C.c_float(), C.c_int32(), (C.c_int32 * 4)()
+        self._chk(self._L.ft8rx_ft4_info(self._h, C.byref(wb), C.byref(sm), C.byref(hd), rg), "ft8rx_ft4_info")
+        return dict(workspace_bytes=int(wb.value), sync_min=float(sm.value), osd_max_hd=int(hd.value), range=tuple(rg))
+
+    def ft4_decode(self, audio):
+        """ft8rx_ft4_decode_batch: host int16 [B, 90000] -> (records [B, max_cands], counts, events, event counts); FT4's record fields:
+        include/ft8rx.h."""
+        audio = self._ft4_audio(audio, "ft4_decode")
+        B = len(audio)
+        rec, cnt, ev, evc = self._alloc_out(B)
+        self._chk(self._L.ft8rx_ft4_decode_batch(self._h, audio.ctypes.data, B, rec.ctypes.data, cnt.ctypes.data, ev.ctypes.data, evc.ctypes.data),
+                  "ft8rx_ft4_decode_batch")
+        return rec, cnt, ev, evc
+
+    def ft4_enqueue(self, d_audio_ptr, B):
+        self._chk(self._L.ft8rx_ft4_enqueue_batch(self._h, C.c_void_p(d_audio_ptr), int(B)), "ft8rx_ft4_enqueue_batch")
+
+    def ft4_grid(self, audio, want_power=False):
+        """ft8rx_ft4_grid -> dB [B, 618, 577] float32 (and the powers before the logarithm)."""
+        audio = self._ft4_audio(audio, "ft4_grid")
+        g = np.empty((len(audio), FT4_ROWS, FT4_COLS), np.float32)
+        p = np.empty_like(g) if want_power else None
+        self._chk(self._L.ft8rx_ft4_grid(self._h, audio.ctypes.data, len(audio), g.ctypes.data, p.ctypes.data if want_power else None), "ft8rx_ft4_grid")
+        return (g, p) if want_power else g
+
+    def ft4_sync(self, grid, want_best=False):
+        """ft8rx_ft4_sync on dB grids [B, 618, 577] -> (f0, h0, score [B, max_cands], counts [B]) and, want_best, the per-bin maxima
+        (best score, best h0) [B, f0_hi - f0_lo] before threshold and neighbour suppression."""
+        grid = np.ascontiguousarray(grid, np.float32)
+        if grid.ndim == 2:
+            grid = grid[None]
+        if grid.shape[1:] != (FT4_ROWS, FT4_COLS) or not 1 <= len(grid) <= self.max_frames:
+            raise Ft8rxError(f"ft4_sync: grid must be [1 <= n <= {self.max_frames}][{FT4_ROWS}][{FT4_COLS}], got {grid.shape}")
+        B, mc = len(grid), self.cfg.max_cands
+        f0 = np.zeros((B, mc), np.int32); h0 = np.zeros((B, mc), np.int32); sc = np.zeros((B, mc), np.float32); cnt = np.zeros(B, np.int32)
+        rg = self.ft4_info()["range"]
+        bs = np.zeros((B, rg[1] - rg[0]), np.float32); bh = np.zeros((B, rg[1] - rg[0]), np.int32)
+        self._chk(self._L.ft8rx_ft4_sync(self._h, grid.ctypes.data, B, f0.ctypes.data, h0.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
+                                         bs.ctypes.data if want_best else None, bh.ctypes.data if want_best else None), "ft8rx_ft4_sync")
+        return (f0, h0, sc, cnt, bs, bh) if want_best else (f0, h0, sc, cnt)
+
+    def ft4_demod(self, audio, frame, f0, h0):
+        """ft8rx_ft4_demod: fine sync and demodulation of (frame, f0, h0) triples -> dict(ttweak, ftweak, metric, llr [n, 174], snr)."""
+        audio = self._ft4_audio(audio, "ft4_demod")
+        frame, f0, h0 = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (frame, f0, h0))
+        n = len(f0)
+        if n < 1 or len(frame) != n or len(h0) != n:
+            raise Ft8rxError("ft4_demod: one frame, f0 and h0 per candidate")
+        tw = np.zeros((n, 2), np.int32); met = np.zeros(n, np.float32); llr = np.zeros((n, 174), np.float32); snr = np.zeros(n, np.int32)
+        self._chk(self._L.ft8rx_ft4_demod(self._h, audio.ctypes.data, len(audio), n, frame.ctypes.data, f0.ctypes.data, h0.ctypes.data,
+                                          tw.ctypes.data, met.ctypes.data, llr.ctypes.data, snr.ctypes.data), "ft8rx_ft4_demod")
+        return dict(ttweak=tw[:, 0].copy(), ftweak=tw[:, 1].copy(), metric=met, llr=llr, snr=snr)
+
+    def ft4_ldpc(self, llr, max_ncheck0, max_iters, mask=0):
+        """ft8rx_ft4_ldpc: ldpc() on LLRs of FT4 codewords; the words come back descrambled."""
+        llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)
+        n = len(llr)
+        ok, nits, has = (np.zeros(n, np.int32) for _ in range(3))
+        lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        out = np.zeros((n, 174), np.float32)
+        self._chk(self._L.ft8rx_ft4_ldpc(self._h, llr.ctypes.data, n, int(max_ncheck0), int(max_iters), int(mask),
+                                         *[a.ctypes.data for a in (ok, lo, hi, nits, has, out)]), "ft8rx_ft4_ldpc")
+        return ok, lo, hi, nits, has, out
+
+    def ft4_osd(self, llr, singleflips=30, doubleflips=2, tripleflips=0, max_hd=0, mask=0):
+        """ft8rx_ft4_osd: osd() on LLRs of FT4 codewords -> (ok, lo, hi, trial, hd); the words come back descrambled."""
+        llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)
+        n = len(llr)
+        ok, trial, hd = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        self._chk(self._L.ft8rx_ft4_osd(self._h, llr.ctypes.data, n, int(singleflips), int(doubleflips), int(tripleflips), int(max_hd), int(mask),
+                                        *[a.ctypes.data for a in (ok, lo, hi, trial, hd)]), "ft8rx_ft4_osd")
+        return ok, lo, hi, trial, hd
 
     def crc_valid(self, cw91):
         cw91 = np.ascontiguousarray(cw91, np.float32).reshape(-1, 91)
@@ -1530,6 +1625,16 @@ def encode_tones(msg_lo, msg_hi):
     out = np.zeros((len(lo), 79), np.uint8)
     if lib().ft8rx_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
         raise Ft8rxError("ft8rx_encode_tones failed")
+    return out
+
+
+def ft4_encode_tones(msg_lo, msg_hi):
+    """77-bit words -> uint8 [n, 105] FT4 tone sequences (ft8rx_ft4_encode_tones, host only; ft4.tones105 is its twin)."""
+    lo = np.ascontiguousarray(msg_lo, np.uint64).ravel()
+    hi = np.ascontiguousarray(msg_hi, np.uint64).ravel()
+    out = np.zeros((len(lo), 105), np.uint8)
+    if lib().ft8rx_ft4_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
+        raise Ft8rxError("ft8rx_ft4_encode_tones failed")
     return out
 
 

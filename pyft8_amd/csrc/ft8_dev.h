@@ -454,16 +454,28 @@ FT8_DEV unsigned ft8_crc_syndrome_wave(uint64_t b0, uint64_t b1, int lane) {
     return (unsigned)__builtin_amdgcn_readfirstlane((int)ft8_xor_row16(ft8_crc_entry(b0, b1 & ((1ull << 27) - 1), lane)));
 }
 
+// FT4 (kernels/ft4.hpp) sends the 77 bits XORed with a fixed vector; the CRC-14 and the LDPC code cover the
+// scrambled bits.  FT8_MT_FT4 in the mask of an EXT check (above the FT8RX_MT_* bits, never set by ft8rx_set_msg_types) descrambles the
+// word between the CRC test and the validity predicate: *lo / *hi then hold the message.  rvec as a 77-bit integer, first transmitted
+// bit = bit 76: bytes 4A 5E 89 B4 B0 8A 79 55 BE 28 left-aligned.
+#define FT8_MT_FT4 0x40000000u
+#define FT4_RVEC_LO 0xd13696114f2ab7c5ull
+#define FT4_RVEC_HI 0x94bull
+FT8_DEV void ft4_descramble(unsigned mask, uint64_t* lo, uint64_t* hi) {
+    if (mask & FT8_MT_FT4) { *lo ^= FT4_RVEC_LO; *hi ^= FT4_RVEC_HI; }
+}
+
 // 0 = no CRC match (or all-zero message), 1 = CRC ok but unpack() -> None, 2 = accepted.
 // EXT = false is the reference's predicate (the kernels of a handle with msg_types = 0 are instantiated with it: the same code as
-// before the extension); EXT = true applies ft8_valid77_ext(mask, osd).
+// before the extension); EXT = true applies ft8_valid77_ext(mask, osd), behind the FT4 flag's descrambling.
 template <bool EXT = false>
 FT8_DEV int ft8_crc_check(uint64_t b0, uint64_t b1, uint64_t* lo, uint64_t* hi, unsigned mask = 0, bool osd = false) {
     if (ft8_crc_syndrome(b0, b1 & ((1ull << 27) - 1)) != 0) return 0;        // 12 table lookups instead of a 77-step bit loop
     unsigned crc;
     ft8_cw_to_msg(b0, b1, lo, hi, &crc);
     if (*lo == 0 && *hi == 0) return 0;
-    return (EXT ? ft8_valid77_ext(*lo, *hi, mask, osd) : ft8_valid77(*lo, *hi)) ? 2 : 1;
+    if (EXT) ft4_descramble(mask, lo, hi);
+    return (EXT ? ft8_valid77_ext(*lo, *hi, mask & FT8RX_MT_ALL, osd) : ft8_valid77(*lo, *hi)) ? 2 : 1;
 }
 // the same for a wave-uniform word, all 64 lanes active
 template <bool EXT = false>
@@ -472,6 +484,7 @@ FT8_DEV int ft8_crc_check_wave(uint64_t b0, uint64_t b1, int lane, uint64_t* lo,
     unsigned crc;
     ft8_cw_to_msg(b0, b1, lo, hi, &crc);
     if (*lo == 0 && *hi == 0) return 0;
-    return (EXT ? ft8_valid77_ext(*lo, *hi, mask) : ft8_valid77(*lo, *hi)) ? 2 : 1;
+    if (EXT) ft4_descramble(mask, lo, hi);
+    return (EXT ? ft8_valid77_ext(*lo, *hi, mask & FT8RX_MT_ALL) : ft8_valid77(*lo, *hi)) ? 2 : 1;
 }
 #endif  // FT8RX_ILP_UNIT

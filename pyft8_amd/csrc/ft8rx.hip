@@ -68,6 +68,7 @@
 #include "kernels/blanker.hpp"
 #include "kernels/blank_in.hpp"
 #include "kernels/pan.hpp"
+#include "kernels/ft4.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/probes.hpp"
@@ -302,6 +303,20 @@ struct ft8rx_handle {
         PanWs ws;
         hipEvent_t ev = nullptr;
     } pans;
+    // FT4 (ft8rx_ft4_*, kernels/ft4.hpp; everything allocated at the first FT4 call, WS_FT4): the knobs and the search
+    // range; frames [max_frames][90000], the dB grid [max_frames][618][577], the FFT's tables, the per-f0 maxima before / after
+    // k_ft4_peaks [max_frames][NF0MAX]; per candidate slot ([max_frames << cand_shift]) the triples, LLRs, BP outputs, tweaks, metric,
+    // SNR, BP and OSD attempts, the OSD list, its dense LLR rows and its NaN list; the two list counters and their page-locked copy
+    struct Ft4 {
+        float sync_min = FT8RX_FT4_SYNC_MIN_DEFAULT; int32_t osd_max_hd = FT8RX_FT4_OSD_MAX_HD_DEFAULT;
+        Ft4Range range = {2, 567, -42, 168};     // 12.5 .. 5900 Hz, -0.5 .. +2.0 s
+        size_t bytes = 0;
+        int16_t* d_audio = nullptr; float* d_grid = nullptr; float* d_win = nullptr; cpx* d_w576 = nullptr; cpx* d_wr = nullptr;
+        float* d_raw = nullptr; float* d_kept = nullptr; int32_t* d_bh = nullptr;
+        int32_t* d_trip = nullptr; float* d_llr = nullptr; float* d_saved = nullptr; int32_t* d_tweak = nullptr; float* d_metric = nullptr;
+        int32_t* d_snr = nullptr; Att* d_att = nullptr; Att* d_attO = nullptr; int32_t* d_items = nullptr; float* d_dense = nullptr;
+        int32_t* d_nan = nullptr; int32_t* d_count = nullptr; int32_t* h_count = nullptr;
+    } ft4;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -388,7 +403,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4 };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3494,6 +3509,292 @@ int ft8rx_valid77_ext(ft8rx_handle* h, const uint64_t* msg_lo, const uint64_t* m
     k_valid_ext_probe<<<(n + 255) / 256, 256, 0, h->stream>>>(d_lo, d_hi, n, (unsigned)mask, d_v);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(valid, d_v, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- FT4 (kernels/ft4.hpp)
+// Everything FT4 owns, at the first FT4 call on the handle, all or nothing (FirstUse)
+static int ft4_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4)) return 0;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const size_t mf = (size_t)h->max_frames, S = mf << cand_shift(h->cfg);
+    FirstUse F(h, WS_FT4);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_audio, mf * FT8RX_FT4_NSAMP); dev(&w.d_grid, mf * FT8RX_FT4_ROWS * FT8RX_FT4_COLS);
+    dev(&w.d_win, (size_t)FT4_NFFT); dev(&w.d_w576, (size_t)576); dev(&w.d_wr, (size_t)FT8RX_FT4_COLS);
+    dev(&w.d_raw, mf * NF0MAX); dev(&w.d_kept, mf * NF0MAX); dev(&w.d_bh, mf * NF0MAX);
+    dev(&w.d_trip, S * 3); dev(&w.d_llr, S * 174); dev(&w.d_saved, S * 174); dev(&w.d_tweak, S * 2); dev(&w.d_metric, S); dev(&w.d_snr, S);
+    dev(&w.d_att, S); dev(&w.d_attO, S); dev(&w.d_items, S); dev(&w.d_dense, S * 174); dev(&w.d_nan, S + 1); dev(&w.d_count, (size_t)2);
+    F.host(&w.h_count, (size_t)2);
+    if (!F.rc) {
+        std::vector<float> win(FT4_NFFT);
+        for (int i = 0; i < FT4_NFFT; i++) win[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)FT4_NFFT));
+        std::vector<cpx> w576, wr;
+        host_twiddle(576, 576, w576); host_twiddle(FT4_NFFT, FT8RX_FT4_COLS, wr);
+        FIRST_HIP(F, hipMemcpy(w.d_win, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(w.d_w576, w576.data(), sizeof(cpx) * w576.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(w.d_wr, wr.data(), sizeof(cpx) * wr.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemset(w.d_tweak, 0, sizeof(int32_t) * S * 2));
+        FIRST_HIP(F, hipMemset(w.d_metric, 0, sizeof(float) * S));
+        FIRST_HIP(F, hipMemset(w.d_snr, 0, sizeof(int32_t) * S));
+    }
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
+static int ft4_refuse(ft8rx_handle* h, const char* who) {
+    const int c = optins::conflict(active_optins(h), optins::FT4_ROW);
+    if (c < 0) return 0;
+    set_err(h, "%s: %s is not supported together with %s", who, optins::FT4_ROW.name, optins::TABLE[c].name);
+    return -1;
+}
+static void ft4_launch_grid(ft8rx_handle* h, const int16_t* d_audio, int B, float* grid, float* power, hipStream_t s) {
+    k_ft4_grid<<<dim3(FT8RX_FT4_ROWS / FT4_GR, B), FT4_GRID_NT, 0, s>>>(d_audio, grid, power, h->ft4.d_win, h->ft4.d_w576, h->ft4.d_wr);
+}
+// grid -> the per-f0 maxima (d_raw, d_bh), the survivors (d_kept), then k_topk's records and counts
+static void ft4_launch_sync(ft8rx_handle* h, const float* grid, int B, ft8rx_record* rec, int32_t* ncand, int32_t* evcount, hipStream_t s) {
+    const ft8rx_handle::Ft4& w = h->ft4;
+    const int nf0 = w.range.f0_hi - w.range.f0_lo;
+    k_ft4_sync<<<dim3((nf0 + 15) / 16, B), 256, 0, s>>>(grid, w.d_raw, w.d_bh, w.range);
+    k_ft4_peaks<<<dim3((nf0 + 255) / 256, B), 256, 0, s>>>(w.d_raw, w.d_kept, nf0, w.sync_min, B);
+    ft8rx_config c = h->cfg;
+    c.f0_lo = w.range.f0_lo; c.f0_hi = w.range.f0_hi; c.sync_score_min = 0.0f;      // k_topk: every surviving (positive) score, best first
+    k_topk<<<B, 1024, 0, s>>>(w.d_kept, w.d_bh, rec, ncand, c, evcount, nullptr, nullptr);
+}
+// BP then OSD on n raw LLR vectors with the FT4 flag; att / attO [n]; OSD runs on every vector (the stage entries) -- the chain calls
+// the two halves itself.  mt: FT8RX_MT_* bits
+static void ft4_launch_bp(ft8rx_handle* h, const float* llr, int n, int nc0, int iters, unsigned mt, Att* att, float* saved, hipStream_t s) {
+    k_bp_ext<<<n, 64, 0, s>>>(2, llr, nullptr, nullptr, nullptr, att, saved, nullptr, nullptr, h->cfg, nc0, iters, WorkList{nullptr, nullptr}, 0, 1, mt | FT8_MT_FT4);
+}
+static void ft4_launch_osd(ft8rx_handle* h, const float* llr, int n, const uint32_t* trials, int ntr, int nflip, int max_hd, unsigned mt, Att* attO,
+                           int32_t* nan /*[n + 1], [0] zeroed*/, hipStream_t s) {
+    launch_osd(h, mt | FT8_MT_FT4, n, s, 2, llr, nullptr, nullptr, nullptr, nullptr, attO, nullptr, nullptr, trials, ntr, nflip, max_hd,
+               cand_shift(h->cfg), WorkList{nullptr, nullptr}, WorkList{nan + 1, nan});
+}
+
+// One FT4 batch on the main stream into the next result slot: grid, search, demodulation, BP, the OSD list (one host round trip for
+// its length: OSD's raw-vector mode takes one block per vector), OSD, records and events; then the FT8 result tail (batch_finish).
+static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* audio, bool on_host, int B) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (ft4_refuse(h, who)) return -1;
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const int slot = h->slot_enq;
+    ResultSlot& sl = h->slots[slot];
+    h->pnames.clear();
+    if (h->inflight == 2) { h->slot_fetch ^= 1; h->inflight = 1; }          // the oldest unfetched batch is dropped
+    sl.recall = false; sl.reports = false;
+    { const int q = quiesce(h, true); if (q) return q; }
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipStreamWaitEvent(s, sl.ev_done, 0));                        // the slot's previous results have left the device
+    const int16_t* d_audio = audio;
+    if (on_host) {
+        HIPCHK(h, hipMemcpyAsync(w.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice, s));
+        d_audio = w.d_audio;
+    }
+    const ft8rx_config& c = h->cfg;
+    const int sh = cand_shift(c), n = B << sh;
+    const unsigned mt = (unsigned)h->msg_types;
+    const bool prof = h->profiling;
+#define STAGE(name) do { if (prof) { hipEventRecord(h->pev[h->pnames.size()], s); h->pnames.push_back(name); } } while (0)
+    STAGE("ft4_grid");
+    ft4_launch_grid(h, d_audio, B, w.d_grid, nullptr, s);
+    STAGE("ft4_sync");
+    ft4_launch_sync(h, w.d_grid, B, sl.rec, sl.ncand, sl.evcount, s);
+    STAGE("ft4_demod");
+    k_ft4_trip<<<(n + 255) / 256, 256, 0, s>>>(sl.rec, sl.ncand, B, sh, w.d_trip);
+    k_ft4_demod<<<n, FT4_DEMOD_NT, 0, s>>>(d_audio, w.d_trip, w.d_llr, w.d_tweak, w.d_metric, w.d_snr);
+    STAGE("ft4_bp");
+    ft4_launch_bp(h, w.d_llr, n, c.bp_nc0_b, c.bp_iters_b, mt, w.d_att, w.d_saved, s);
+    HIPCHK(h, hipMemsetAsync(w.d_count, 0, 2 * sizeof(int32_t), s));
+    k_ft4_after_bp<<<(n + 255) / 256, 256, 0, s>>>(sl.rec, sl.ncand, B, sh, w.d_att, w.d_tweak, w.d_snr, sl.ev, sl.evcount, WorkList{w.d_items, w.d_count});
+    HIPCHK(h, hipMemcpyAsync(w.h_count, w.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int n_osd = w.h_count[0];
+    if (n_osd < 0 || n_osd > n) { set_err(h, "%s: the OSD list holds %d of %d slots", who, n_osd, n); return -2; }
+    STAGE("ft4_osd");
+    if (n_osd > 0) {
+        k_ft4_gather<<<n_osd, 64, 0, s>>>(w.d_llr, w.d_items, w.d_dense);
+        HIPCHK(h, hipMemsetAsync(w.d_nan, 0, sizeof(int32_t), s));
+        ft4_launch_osd(h, w.d_dense, n_osd, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), w.osd_max_hd, mt, w.d_attO, w.d_nan, s);
+        k_ft4_after_osd<<<(n_osd + 255) / 256, 256, 0, s>>>(sl.rec, sh, w.d_attO, w.d_items, n_osd, sl.ev, sl.evcount);
+    }
+    if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
+#undef STAGE
+    HIPCHK(h, hipGetLastError());
+    return batch_finish(h, slot, B, s);
+}
+static bool ft4_frames_ok(ft8rx_handle* h, const char* who, const void* audio, int B) {
+    if (!h || !audio) return false;
+    if (B < 1 || B > h->max_frames) { set_err(h, "%s: n_frames %d outside [1, %d]", who, B, h->max_frames); return false; }
+    return true;
+}
+
+int ft8rx_ft4_enqueue_batch(ft8rx_handle* h, const int16_t* d_audio, int B) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_enqueue_batch", d_audio, B)) return -1;
+    if ((uintptr_t)d_audio % 4) { set_err(h, "ft8rx_ft4_enqueue_batch: d_audio is not aligned to 4 bytes (a pair of int16 samples)"); return -1; }
+    return ft4_launch_batch(h, "ft8rx_ft4_enqueue_batch", d_audio, false, B);
+}
+int ft8rx_ft4_decode_batch(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_record* records, int32_t* counts, ft8rx_event* events, int32_t* event_counts) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_decode_batch", audio, B)) return -1;
+    h->inflight = 0; h->slot_fetch = h->slot_enq;
+    if (const int rc = ft4_launch_batch(h, "ft8rx_ft4_decode_batch", audio, true, B)) return rc;
+    return ft8rx_fetch_results(h, B, records, counts, events, event_counts);
+}
+int ft8rx_ft4_decode_messages(ft8rx_handle* h, const int16_t* audio, int B, ft8rx_message* out, int max_msgs, int32_t* out_counts,
+                              int n_threads, ft8rx_hashes* table, int32_t* flags) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_decode_messages", audio, B) || !out || !out_counts) return -1;
+    if (max_msgs < 1) { set_err(h, "ft8rx_ft4_decode_messages: bad max_msgs"); return -1; }
+    if (h->msg_types) { set_err(h, "ft8rx_ft4_decode_messages: not supported together with msg_types != 0 (ft8rx_message rows cannot carry it); "
+                                   "use ft8rx_ft4_decode_batch with ft8rx_package_batch_ext"); return -1; }
+    h->inflight = 0; h->slot_fetch = h->slot_enq;
+    int rc = ft4_launch_batch(h, "ft8rx_ft4_decode_messages", audio, true, B);
+    if (rc) return rc;
+    const ft8rx_record* rec; const int32_t* cnt; const ft8rx_event* ev; const int32_t* evc;
+    rc = ft8rx_fetch_results_view(h, B, &rec, &cnt, &ev, &evc);
+    if (rc) return rc;
+    return hostmsg::package_batch(rec, cnt, ev, evc, B, h->cfg.max_cands, out, max_msgs, out_counts, n_threads, table ? &table->H : nullptr, flags);
+}
+
+int ft8rx_ft4_set(ft8rx_handle* h, float sync_min, int32_t osd_max_hd) {
+    if (!h) return -1;
+    if (sync_min == 0.0f) sync_min = FT8RX_FT4_SYNC_MIN_DEFAULT;
+    if (osd_max_hd == 0) osd_max_hd = FT8RX_FT4_OSD_MAX_HD_DEFAULT;
+    if (!(sync_min > 0.0f) || !(sync_min < INFINITY)) { set_err(h, "ft8rx_ft4_set: sync_min %g must be a positive score (0 = the default)", (double)sync_min); return -1; }
+    if (osd_max_hd < 1 || osd_max_hd > 174) { set_err(h, "ft8rx_ft4_set: osd_max_hd %d outside [1, 174] (0 = the default)", osd_max_hd); return -1; }
+    h->ft4.sync_min = sync_min; h->ft4.osd_max_hd = osd_max_hd;
+    return 0;
+}
+int ft8rx_ft4_set_range(ft8rx_handle* h, int32_t f0_lo, int32_t f0_hi, int32_t h0_lo, int32_t h0_hi) {
+    if (!h) return -1;
+    if (!f0_lo && !f0_hi && !h0_lo && !h0_hi) { h->ft4.range = ft8rx_handle::Ft4().range; return 0; }
+    if (f0_lo < 0 || f0_hi <= f0_lo || f0_hi > FT8RX_FT4_COLS - 6 || h0_lo < -1024 || h0_hi <= h0_lo || h0_hi > 1024) {
+        set_err(h, "ft8rx_ft4_set_range: bins [%d, %d) must lie in [0, %d), rows [%d, %d) in [-1024, 1024)", f0_lo, f0_hi, FT8RX_FT4_COLS - 6, h0_lo, h0_hi); return -1; }
+    h->ft4.range = Ft4Range{f0_lo, f0_hi, h0_lo, h0_hi};
+    return 0;
+}
+int ft8rx_ft4_info(ft8rx_handle* h, uint64_t* workspace_bytes, float* sync_min, int32_t* osd_max_hd, int32_t* range) {
+    if (!h) return -1;
+    if (workspace_bytes) *workspace_bytes = ws_ready(h, WS_FT4) ? (uint64_t)h->ft4.bytes : 0;
+    if (sync_min) *sync_min = h->ft4.sync_min;
+    if (osd_max_hd) *osd_max_hd = h->ft4.osd_max_hd;
+    if (range) { range[0] = h->ft4.range.f0_lo; range[1] = h->ft4.range.f0_hi; range[2] = h->ft4.range.h0_lo; range[3] = h->ft4.range.h0_hi; }
+    return 0;
+}
+
+int ft8rx_ft4_grid(ft8rx_handle* h, const int16_t* audio, int B, float* grid, float* power) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_grid", audio, B) || !grid) return -1;
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const size_t n = (size_t)B * FT8RX_FT4_ROWS * FT8RX_FT4_COLS;
+    Scratch S{h};
+    float* d_pw = nullptr;
+    if (power) { d_pw = S.get<float>(n); NEED(d_pw); }
+    HIPCHK(h, hipMemcpy(w.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice));
+    ft4_launch_grid(h, w.d_audio, B, w.d_grid, d_pw, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(grid, w.d_grid, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (power) HIPCHK(h, hipMemcpy(power, d_pw, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts,
+                   float* best_score, int32_t* best_h0) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_sync", grid, B) || !f0_idx || !h0_idx || !score || !counts) return -1;
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const int sh = cand_shift(h->cfg), mc = h->cfg.max_cands, nf0 = w.range.f0_hi - w.range.f0_lo;
+    HIPCHK(h, hipMemcpy(w.d_grid, grid, sizeof(float) * (size_t)B * FT8RX_FT4_ROWS * FT8RX_FT4_COLS, hipMemcpyHostToDevice));
+    ft4_launch_sync(h, w.d_grid, B, h->d_rec, h->d_ncand, h->d_evcount, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<ft8rx_record> rec((size_t)B << sh);
+    HIPCHK(h, hipMemcpy(rec.data(), h->d_rec, sizeof(ft8rx_record) * rec.size(), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(counts, h->d_ncand, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    for (int f = 0; f < B; f++) for (int i = 0; i < mc; i++) {
+        const ft8rx_record& r = rec[((size_t)f << sh) + i];
+        const bool live = i < counts[f];
+        f0_idx[(size_t)f * mc + i] = live ? r.f0_idx : 0; h0_idx[(size_t)f * mc + i] = live ? r.h0_idx : 0; score[(size_t)f * mc + i] = live ? r.score : 0.0f;
+    }
+    if (best_score) HIPCHK(h, hipMemcpy2D(best_score, sizeof(float) * nf0, w.d_raw, sizeof(float) * NF0MAX, sizeof(float) * nf0, B, hipMemcpyDeviceToHost));
+    if (best_h0) HIPCHK(h, hipMemcpy2D(best_h0, sizeof(int32_t) * nf0, w.d_bh, sizeof(int32_t) * NF0MAX, sizeof(int32_t) * nf0, B, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_demod(ft8rx_handle* h, const int16_t* audio, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                    int32_t* tweak, float* metric, float* llr, int32_t* snr) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_demod", audio, B) || n < 1 || !frame || !f0_idx || !h0_idx || !tweak || !metric || !llr || !snr) return -1;
+    for (int i = 0; i < n; i++)
+        if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < 0 || f0_idx[i] >= FT8RX_FT4_COLS - 6 || h0_idx[i] < -1024 || h0_idx[i] >= 1024) {
+            set_err(h, "ft8rx_ft4_demod: candidate %d (frame %d, f0 %d, h0 %d) is out of range", i, frame[i], f0_idx[i], h0_idx[i]); return -1; }
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const std::vector<int32_t> trip = pack_triples(n, frame, f0_idx, h0_idx);
+    Scratch S{h};
+    int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
+    float* d_llr = S.get<float>((size_t)n * 174); NEED(d_llr);
+    int32_t* d_tw = S.get<int32_t>((size_t)n * 2); NEED(d_tw);
+    float* d_met = S.get<float>(n); NEED(d_met);
+    int32_t* d_snr = S.get<int32_t>(n); NEED(d_snr);
+    HIPCHK(h, hipMemcpy(w.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice));
+    k_ft4_demod<<<n, FT4_DEMOD_NT, 0, h->stream>>>(w.d_audio, d_trip, d_llr, d_tw, d_met, d_snr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(llr, d_llr, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(tweak, d_tw, sizeof(int32_t) * (size_t)n * 2, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(metric, d_met, sizeof(float) * n, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(snr, d_snr, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,
+                   uint64_t* msg_hi, int32_t* n_its, int32_t* has_out, float* llr_out) {
+    if (!h || !llr || n < 1 || !ok || !msg_lo || !msg_hi || !n_its || !has_out) return -1;
+    if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_ft4_ldpc: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
+    ENTER(h);
+    Scratch S{h};
+    float* d_in = S.put(llr, (size_t)n * 174); NEED(d_in);
+    float* d_out = S.get<float>((size_t)n * 174); NEED(d_out);
+    HIPCHK(h, hipMemset(d_out, 0, sizeof(float) * (size_t)n * 174));
+    Att* d_att = S.get<Att>(n); NEED(d_att);
+    ft4_launch_bp(h, d_in, n, max_ncheck0, max_iters, (unsigned)mask, d_att, d_out, h->stream);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<Att> a(n);
+    HIPCHK(h, hipMemcpy(a.data(), d_att, sizeof(Att) * n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) { ok[i] = a[i].ok; msg_lo[i] = a[i].lo; msg_hi[i] = a[i].hi; n_its[i] = a[i].ok ? a[i].n_its : -1; has_out[i] = a[i].has_out; }
+    if (llr_out) HIPCHK(h, hipMemcpy(llr_out, d_out, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_osd(ft8rx_handle* h, const float* llr, int n, int singleflips, int doubleflips, int tripleflips, int max_hd, int32_t mask,
+                  int32_t* ok, uint64_t* msg_lo, uint64_t* msg_hi, int32_t* trial, int32_t* hd) {
+    if (!h || !llr || n < 1 || !ok || !msg_lo || !msg_hi || !trial) return -1;
+    if (mask < 0 || mask > FT8RX_MT_ALL) { set_err(h, "ft8rx_ft4_osd: mask %d outside [0, %d]", mask, FT8RX_MT_ALL); return -1; }
+    if (singleflips < 0 || singleflips > OSD_MAXFLIP || doubleflips < 0 || doubleflips > OSD_MAXFLIP || tripleflips < 0 || tripleflips > 40 ||
+        max_hd < 0 || max_hd > 174) { set_err(h, "ft8rx_ft4_osd: flip counts out of range"); return -1; }
+    const std::vector<uint32_t> tr = osd_trial_table(singleflips, doubleflips, tripleflips);
+    if (tr.size() > OSD_MAXTRIALS) { set_err(h, "ft8rx_ft4_osd: %zu trials exceed %d", tr.size(), OSD_MAXTRIALS); return -1; }
+    ENTER(h);
+    Scratch S{h};
+    float* d_in = S.put(llr, (size_t)n * 174); NEED(d_in);
+    uint32_t* d_tr = S.put(tr.data(), tr.size()); NEED(d_tr);
+    Att* d_att = S.get<Att>(n); NEED(d_att);
+    int32_t* d_nan = S.get<int32_t>((size_t)n + 1); NEED(d_nan);
+    HIPCHK(h, hipMemsetAsync(d_nan, 0, sizeof(int32_t), h->stream));
+    ft4_launch_osd(h, d_in, n, d_tr, (int)tr.size(), osd_nflip(singleflips, tripleflips), max_hd, (unsigned)mask, d_att, d_nan, h->stream);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<Att> a(n);
+    HIPCHK(h, hipMemcpy(a.data(), d_att, sizeof(Att) * n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        ok[i] = a[i].ok; msg_lo[i] = a[i].lo; msg_hi[i] = a[i].hi; trial[i] = a[i].ok ? a[i].n_its : -1;
+        if (hd) hd[i] = a[i].ok ? a[i].pad[0] : -1;
+    }
+    return 0;
+}
+int ft8rx_ft4_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n, uint8_t* tones) {
+    if (!msg_lo || !msg_hi || !tones || n < 0) return -1;
+    for (int i = 0; i < n; i++) hostmsg::encode_tones_ft4(msg_lo[i], msg_hi[i], tones + (size_t)i * 105);
     return 0;
 }
 

@@ -476,6 +476,20 @@ static void encode_tones(uint64_t lo, uint64_t hi, uint8_t* t) {
         t[(sidx < 29 ? 7 : 14) + sidx] = gray[v];
     }
 }
+// 77-bit word -> the 105 FT4 tones (pyft8_amd/ft4.py tones105): the word XOR rvec through the same CRC-14 and LDPC encode, two bits
+// per symbol through the Gray map 0 1 3 2, framed  R S4a D29 S4b D29 S4c D29 S4d R  (R = tone 0; b, c, d = a XOR 1, 2, 3)
+static void encode_tones_ft4(uint64_t lo, uint64_t hi, uint8_t* t) {
+    static const uint8_t gray[4] = {0, 1, 3, 2};
+    uint64_t cw[3];
+    encode_cw174(lo ^ 0xd13696114f2ab7c5ull, (hi ^ 0x94bull) & 0x1FFFull, cw);        // rvec, first transmitted bit = bit 76
+    t[0] = 0; t[104] = 0;
+    for (int b = 0; b < 4; b++) for (int s = 0; s < 4; s++) t[1 + 33 * b + s] = (uint8_t)(gray[s] ^ b);
+    for (int i = 0; i < 87; i++) {
+        const int b0 = 2 * i, b1 = 2 * i + 1;
+        const unsigned v = (unsigned)(((cw[b0 >> 6] >> (b0 & 63)) & 1ull) << 1) | (unsigned)((cw[b1 >> 6] >> (b1 & 63)) & 1ull);
+        t[(i < 29 ? 5 : i < 58 ? 9 : 13) + i] = gray[v];
+    }
+}
 
 // records/events of n_frames frames -> messages; table == nullptr: a fresh hash table per frame (frames spread over n_threads
 // threads); table != nullptr: frames in order on the caller's thread, all sharing (and updating) that table.

@@ -22,11 +22,16 @@ constexpr Row TABLE[N_ROWS] = {
     {"ft8rx_decode_messages",                       bit(MSG_TYPES) | bit(RECALL)},      // ft8rx_message rows hold neither
 };
 
-// the first setting, in table order, that is active and that `asked` cannot run with; -1 = none
-inline int conflict(unsigned active, Id asked) {
-    const unsigned hit = active & TABLE[asked].excludes;
+// FT4 decoding (ft8rx_ft4_*), a consumer row of its own: its ladder is BP and OSD on the demodulator's LLRs with
+// the msg_types mask, nothing else.  (TABLE's rows are the ones tests/host_asan_driver.cpp holds to its literal truth table.)
+constexpr Row FT4_ROW = {"FT4 decoding (ft8rx_ft4_decode_batch)", bit(PACKED) | bit(AP_CALLS) | bit(RECALL) | bit(WEAK) | bit(REPORTS)};
+
+// the first setting, in table order, that is active and that the row cannot run with; -1 = none
+constexpr int conflict(unsigned active, const Row& row) {
+    const unsigned hit = active & row.excludes;
     for (int i = 0; i < N_SETTINGS; i++) if (hit & (1u << i)) return i;
     return -1;
 }
+inline int conflict(unsigned active, Id asked) { return conflict(active, TABLE[asked]); }
 
 }  // namespace optins

@@ -1,0 +1,366 @@
+"""FT4 (host/numpy, float64): the protocol constants, a synthesiser and the twin of the GPU front end (csrc/kernels/ft4.hpp).
+
+FT4 shares FT8's 77-bit messages, CRC-14 and LDPC(174,91); it differs in front of the decoder: 7.5-s slots, 4-GFSK at 20.8333 baud
+(576 samples per symbol at 12 kHz, BT = 1.0), 105 symbols  R S4a D29 S4b D29 S4c D29 S4d R  and a 77-bit scrambling vector that is
+XORed onto the message before the CRC and the LDPC code.  The constants are committed as data (QEX 2020 / the WSJT-X generator
+tables and the byte table of ft8_lib agree on them; tests/test_ft4.py holds their checks).  No foreign FT4 signal has been decoded
+yet: the mode is pinned to these constants and to this twin.
+
+The twin is the definition the kernels are held to (tests/test_gpu_ft4.py):
+  grid     P[r][k] = |rfft(hann_periodic(1152) x[144 r : 144 r + 1152])[k]|^2, r = 0 .. 617, k = 0 .. 576 (10.4167 Hz; two bins per
+           tone, four rows per symbol), kept as dB = 10 log10(max(P, 1e-24))
+  search   score(f0, h0) = sum over the 16 Costas symbols s of dB[tone] - mean dB[other three tones], row h0 + 4 s - 2, columns
+           f0 + 2 tone, rows outside the grid contribute 0; per f0 the first strict maximum over h0; kept: best >= sync_min and
+           >= both neighbours' best (a tie goes to the lower bin); then the max_cands highest, ties in f0 order
+  fine     9 x 5 trials dt = -144 .. 144 step 36 samples, df = -2 .. 2 x 2.6042 Hz: sum over the 16 sync symbols of the magnitude of
+           the 576-sample rectangular DFT at the Costas tone, straight from the audio (zeros outside the frame); first maximum in
+           (dt, df) order
+  demod    the 105 x 4 amplitude matrix at the winner; 174 max-log LLRs on amplitudes (positive = bit 1), scaled 2.83 / std (all
+           zero where std = 0; otherwise an LLR of exactly 0 -- a symbol outside the frame -- becomes +0.001); SNR from the
+           matrix's powers
+"""
+import numpy as np
+
+from .ft8_tables import CHK_N, CHK_V
+from .synth import encode174, pack77, pack77_ext, random_message        # noqa: F401  (re-exported: the FT4 generator's message side)
+
+FS = 12000
+NSPS = 576
+NFRAME = 90000
+NSYM = 105
+NFFT, HOP, ROWS, COLS = 1152, 144, 618, 577
+BIN_HZ = FS / NFFT                     # 10.41667
+TONE_HZ = FS / NSPS                    # 20.83333
+DF_HZ = FS / 4608                      # 2.60417: the fine frequency step
+DT_STEP, N_DT, N_DF = 36, 9, 5
+COSTAS4 = ((0, 1, 3, 2), (1, 0, 2, 3), (2, 3, 1, 0), (3, 2, 0, 1))
+SYNC_POS = (1, 34, 67, 100)
+GRAY4 = (0, 1, 3, 2)                   # 2-bit value -> tone
+GRAY4_INV = (0, 1, 3, 2)               # tone -> 2-bit value
+RVEC_BITS = "0100101001011110100010011011010010110000100010100111100101010101101111100" "0101"
+RVEC = int(RVEC_BITS, 2)               # as a 77-bit integer, first transmitted bit = bit 76
+SEED_BASE = 0x46543400
+SYNC_MIN_DEFAULT = 100.0
+OSD_MAX_HD_DEFAULT = 40                # FT8RX_FT4_OSD_MAX_HD_DEFAULT: the largest gate without a false decode on 2048 noise frames
+OSD_MAX_HD_MSG_TYPES = 24              # ... and with msg_types = all (one false RTTY-RU word from 28 on): what Receiver takes then
+LLR_SCALE = 2.83
+LLR_ZERO = 1e-3                        # what an LLR of exactly 0 becomes: the shared BP's message update divides by tanh(llr / 2)
+# symbol index of each of the 87 data symbols, and (symbol, tone) of the 16 sync symbols
+DATA_POS = tuple(list(range(5, 34)) + list(range(38, 67)) + list(range(71, 100)))
+SYNC_SYMS = tuple((p + s, COSTAS4[b][s]) for b, p in enumerate(SYNC_POS) for s in range(4))
+
+
+# ----------------------------------------------------------------------------- transmit side
+def tones105(bits77):
+    """77-bit message -> the 105 tones (0 .. 3) of its FT4 transmission."""
+    cw = encode174(int(bits77) ^ RVEC)
+    d = [GRAY4[(cw >> (172 - 2 * i)) & 3] for i in range(87)]
+    return ([0] + list(COSTAS4[0]) + d[:29] + list(COSTAS4[1]) + d[29:58] + list(COSTAS4[2]) + d[58:] + list(COSTAS4[3]) + [0])
+
+
+def tones_to_bits77(tones):
+    """The inverse of tones105 on an error-free tone list: the descrambled 77-bit message (no CRC check)."""
+    cw = 0
+    for p in DATA_POS:
+        cw = (cw << 2) | GRAY4_INV[int(tones[p])]
+    return (cw >> 97) ^ RVEC
+
+
+def _gfsk_pulse(bt=1.0):
+    from math import erf, log, pi, sqrt
+    k = pi * sqrt(2.0 / log(2.0)) * bt
+    t = (np.arange(3 * NSPS) - 1.5 * NSPS) / NSPS
+    return np.array([0.5 * (erf(k * (x + 0.5)) - erf(k * (x - 0.5))) for x in t])
+
+
+_PULSE = None
+
+
+def tones_to_wave(tones, f0):
+    """105 tones -> the real 4-GFSK waveform, 105 * 576 samples, unit amplitude; f0 = the frequency of tone 0.  The first and the
+    last symbol (the ramp symbols) are shaped by a raised cosine over the whole symbol."""
+    global _PULSE
+    if _PULSE is None:
+        _PULSE = _gfsk_pulse()
+    n = len(tones)
+    ext = [tones[0]] + list(tones) + [tones[-1]]          # dummy edge symbols
+    dphi = np.zeros((n + 2) * NSPS + 2 * NSPS)
+    for i, t in enumerate(ext):
+        dphi[i * NSPS:i * NSPS + 3 * NSPS] += t * _PULSE
+    dphi = dphi[2 * NSPS: 2 * NSPS + n * NSPS]
+    dphi = 2 * np.pi * (f0 + TONE_HZ * dphi) / FS
+    w = np.sin(np.cumsum(dphi) - dphi)
+    ramp = 0.5 * (1 - np.cos(np.pi * np.arange(NSPS) / NSPS))
+    w[:NSPS] *= ramp
+    w[-NSPS:] *= ramp[::-1]
+    return w
+
+
+def amplitude(snr_db):
+    """Amplitude (in units of the noise's standard deviation) of a carrier at snr_db in 2500 Hz, synth.make_frame's convention."""
+    return np.sqrt(2.0 * (2500.0 / 6000.0) * 10.0 ** (float(snr_db) / 10.0))
+
+
+def frame_with_signals(index, signals, seed_base=SEED_BASE, noise=True):
+    """A 7.5-s frame carrying signals = [(word77, f0 Hz, t0 s, snr dB), ...] at the given places (t0 may be negative or run past
+    the end: the part inside the frame is added) -> int16[90000].  Noise: unit variance x 1000 counts, Philox keyed on the index."""
+    rng = np.random.Generator(np.random.Philox(key=seed_base + 99000000 + int(index)))
+    x = rng.standard_normal(NFRAME) if noise else np.zeros(NFRAME)
+    for w77, f0, t0, snr in signals:
+        w = tones_to_wave(tones105(int(w77)), float(f0))
+        i0 = int(round(float(t0) * FS))
+        a, b = max(0, i0), min(NFRAME, i0 + len(w))
+        if b > a:
+            x[a:b] += amplitude(snr) * w[a - i0:b - i0]
+    return np.clip(np.rint(x * 1000.0), -32768, 32767).astype(np.int16)
+
+
+def make_frame(index, n_signals=6, snr_range=(-8.0, 5.0), seed_base=SEED_BASE, return_truth=False, freq_range=(200.0, 2800.0),
+               t0_range=(0.1, 1.5), min_sep_hz=150.0, words=None):
+    """One synthetic FT4 frame -> int16[90000] (and the truth list if asked): n_signals standard messages (or the given 77-bit
+    `words`), carriers in freq_range at least min_sep_hz apart, starts in t0_range seconds, SNR uniform in snr_range (dB in 2500 Hz)."""
+    rng = np.random.Generator(np.random.Philox(key=seed_base + int(index)))
+    x = rng.standard_normal(NFRAME)
+    truth, used = [], []
+    n = len(words) if words is not None else n_signals
+    for k in range(n):
+        msg = random_message(rng)
+        for _ in range(1000):
+            f0 = rng.uniform(*freq_range)
+            if all(abs(f0 - u) >= min_sep_hz for u in used):
+                break
+        else:
+            raise ValueError("make_frame: the carriers do not fit the range at this separation")
+        used.append(f0)
+        t0 = rng.uniform(*t0_range)
+        snr = rng.uniform(*snr_range)
+        w77 = int(words[k]) if words is not None else pack77(*msg)
+        w = tones_to_wave(tones105(w77), f0)
+        i0 = int(round(t0 * FS))
+        m = min(len(w), NFRAME - i0)
+        x[i0:i0 + m] += amplitude(snr) * w[:m]
+        truth.append(dict(msg=" ".join(msg) if words is None else None, word=w77, f0=float(f0), t0=i0 / FS, snr=float(snr)))
+    y = np.clip(np.rint(x * 1000.0), -32768, 32767).astype(np.int16)
+    return (y, truth) if return_truth else y
+
+
+# ----------------------------------------------------------------------------- the twin: grid and search
+def hann_periodic(n=NFFT):
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+
+
+def grid_power(x):
+    """int16 / float [90000] -> P float64 [618][577]."""
+    x = np.asarray(x, np.float64)
+    idx = HOP * np.arange(ROWS)[:, None] + np.arange(NFFT)[None, :]
+    X = np.fft.rfft(x[idx] * hann_periodic()[None, :], axis=1)
+    return X.real ** 2 + X.imag ** 2
+
+
+def grid_db(P):
+    return 10.0 * np.log10(np.maximum(P, 1e-24))
+
+
+def time_range_to_h0(search_time_range=(-0.5, 2.0)):
+    """Absolute start seconds -> (h0_lo, h0_hi), h0_hi exclusive, in rows of 12 ms."""
+    lo, hi = search_time_range
+    return int(np.rint(lo * FS / HOP)), int(np.rint(hi * FS / HOP)) + 1
+
+
+def freq_range_to_f0(search_freq_range=(12.5, 5900.0)):
+    """Hz -> (f0_lo, f0_hi), f0_hi exclusive, bins of 10.4167 Hz; tone 3 sits 6 bins above f0, so f0_hi <= 571."""
+    lo, hi = search_freq_range
+    a, b = int(np.ceil(lo / BIN_HZ - 1e-9)), int(np.floor(hi / BIN_HZ + 1e-9)) + 1
+    return max(a, 0), min(b, COLS - 6)
+
+
+def score_map(db, f0_lo, f0_hi, h0_lo, h0_hi, weights=None):
+    """score[f0 - f0_lo][h0 - h0_lo] of the search.  weights = (own, other): the factors of the tone's own term and of each of the
+    other three (default 1, -1/3; tests bound the score's error with (1, +1/3) on a map of per-bin dB errors)."""
+    own, oth = (1.0, -1.0 / 3.0) if weights is None else weights
+    f0s, h0s = np.arange(f0_lo, f0_hi), np.arange(h0_lo, h0_hi)
+    out = np.zeros((len(f0s), len(h0s)))
+    for sym, tone in SYNC_SYMS:
+        rows = h0s + 4 * sym - 2
+        ok = (rows >= 0) & (rows < ROWS)
+        r = np.clip(rows, 0, ROWS - 1)
+        t4 = np.stack([db[r][:, f0s + 2 * t] for t in range(4)])           # [4][h0][f0]
+        term = own * t4[tone] + oth * (t4.sum(axis=0) - t4[tone])
+        out += np.where(ok[:, None], term, 0.0).T
+    return out
+
+
+def search(db, f0_lo, f0_hi, h0_lo, h0_hi, sync_min=SYNC_MIN_DEFAULT, max_cands=200, full=False):
+    """-> [(f0, h0, score), ...] in output order (score descending, ties in f0 order); full: also (best[f0], h0[f0], score map)."""
+    S = score_map(db, f0_lo, f0_hi, h0_lo, h0_hi)
+    bh = np.argmax(S, axis=1)                                              # the first maximum
+    best = S[np.arange(len(S)), bh]
+    n = len(best)
+    keep = []
+    for i in range(n):
+        if not best[i] >= sync_min:
+            continue
+        if i > 0 and best[i - 1] >= best[i]:
+            continue
+        if i + 1 < n and best[i + 1] > best[i]:
+            continue
+        keep.append(i)
+    keep.sort(key=lambda i: -best[i])                                      # stable: ties stay in f0 order
+    out = [(f0_lo + i, h0_lo + int(bh[i]), float(best[i])) for i in keep[:max_cands]]
+    return (out, best, h0_lo + bh, S) if full else out
+
+
+# ----------------------------------------------------------------------------- the twin: fine sync and demodulation
+_N = np.arange(NSPS)
+
+
+def _symbols(x, starts):
+    """The 576 samples from each of `starts` on, zeros outside x -> [len(starts)][576]."""
+    i = np.asarray(starts)[:, None] + _N[None, :]
+    ok = (i >= 0) & (i < len(x))
+    return np.where(ok, x[np.clip(i, 0, len(x) - 1)], 0.0)
+
+
+def _phasors(fq):
+    """e^(-2 pi i (fq n mod 4608) / 4608), n < 576, for each frequency fq (x 12000 / 4608 Hz) -> [len(fq)][576]: the 576-sample
+    rectangular DFT's kernel, the phase restarting at the symbol's first sample."""
+    return np.exp(-2j * np.pi * ((np.asarray(fq)[:, None] * _N[None, :]) % 4608) / 4608.0)
+
+
+def fine_metrics(x, f0, h0):
+    """The 9 x 5 sync metrics of candidate (f0 bin, h0 row), [dt index][df index]."""
+    x = np.asarray(x, np.float64)
+    syms = np.array([s for s, _ in SYNC_SYMS])
+    tones = np.array([t for _, t in SYNC_SYMS])
+    m = np.zeros((N_DT, N_DF))
+    for a in range(N_DT):
+        V = _symbols(x, HOP * h0 + DT_STEP * (a - N_DT // 2) + NSPS * syms)
+        for b in range(N_DF):
+            m[a, b] = np.abs((V * _phasors(4 * f0 + (b - N_DF // 2) + 8 * tones)).sum(axis=1)).sum()
+    return m
+
+
+def amplitudes(x, f0, h0, tt, ft):
+    """The 105 x 4 amplitude matrix at time tweak tt (x 36 samples) and frequency tweak ft (x 2.6042 Hz)."""
+    x = np.asarray(x, np.float64)
+    V = _symbols(x, HOP * h0 + DT_STEP * tt + NSPS * np.arange(NSYM))
+    return np.abs(V @ _phasors(4 * f0 + ft + 8 * np.arange(4)).T)
+
+
+def llr_from_amplitudes(A):
+    """174 max-log LLRs (positive = bit 1) of the 87 data symbols, scaled to 2.83 / std; all zero where std is 0, otherwise no LLR is
+    exactly 0: the BP behind it (the reference's update, e / ((e - 1.18)(e + 1.18)) with e = P / t) turns a zero into NaNs."""
+    D = A[list(DATA_POS)]
+    msb = np.maximum(D[:, 2], D[:, 3]) - np.maximum(D[:, 0], D[:, 1])       # tones 2, 3 carry values 3, 2
+    lsb = np.maximum(D[:, 1], D[:, 2]) - np.maximum(D[:, 0], D[:, 3])       # tones 1, 2 carry values 1, 3
+    llr = np.stack([msb, lsb], axis=1).reshape(174)
+    sd = np.std(llr)
+    if not sd > 0:
+        return np.zeros(174)
+    llr = LLR_SCALE * llr / sd
+    llr[llr == 0.0] = LLR_ZERO                                              # a symbol outside the frame, or in digital silence
+    return llr
+
+
+def snr_from_amplitudes(A):
+    """The report: 10 log10((S - N) / N) - 10 log10(2500 / 20.8333), rounded, clipped to +-24 (-24 where S <= N or N = 0)."""
+    P = A * A
+    top = P.max(axis=1)
+    S, N = top.mean(), ((P.sum(axis=1) - top) / 3.0).mean()
+    if not (N > 0 and S > N):
+        return -24
+    return int(np.clip(np.rint(10.0 * np.log10((S - N) / N) - 10.0 * np.log10(2500.0 / TONE_HZ)), -24, 24))
+
+
+def demod(x, f0, h0):
+    """Fine sync and demodulation of one candidate -> dict(tt, ft, metric, metrics, llr, snr, amps)."""
+    m = fine_metrics(x, f0, h0)
+    k = int(np.argmax(m))                                                  # first maximum in (dt, df) order
+    tt, ft = k // N_DF - N_DT // 2, k % N_DF - N_DF // 2
+    A = amplitudes(x, f0, h0, tt, ft)
+    return dict(tt=tt, ft=ft, metric=float(m.flat[k]), metrics=m, llr=llr_from_amplitudes(A), snr=snr_from_amplitudes(A), amps=A)
+
+
+# ----------------------------------------------------------------------------- message dicts of the GPU path (Receiver.decode_frames_ft4)
+def slot_parity(cyclestart_string):
+    """'YYMMDD_HHMMSS' (the seconds may carry a fraction: '..._000007.5') -> 0 / 1, the parity of the 7.5-s slot that starts then."""
+    try:
+        t = cyclestart_string.split("_")[1]
+        sec = int(t[0:2]) * 3600 + int(t[2:4]) * 60 + float(t[4:])
+    except (IndexError, ValueError):
+        return 0
+    return int(sec // 7.5) % 2
+
+
+def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None):
+    """Rows of the native packager (ft8rx_package_batch / _ext on FT4 records) -> message dicts with the keys of the FT8 ones and FT4's
+    values: tsec = (144 h0 + 36 tt) / 12000, fHz = 10.41667 f0 + 2.60417 ft, "mode": "FT4", '+' in all_txt_format, their_tx_cycle =
+    the slot's parity."""
+    import time
+    from . import messages as _m
+    out = []
+    now = time.time()
+    rows = msgs[:min(int(count), len(msgs))]
+    ext = len(rows) > 0 and "i3" in rows.dtype.names
+    parity = slot_parity(cyclestart_string)
+    for r in rows:
+        text = tuple(x.decode() for x in r["f"].tolist())
+        tt, ft = int(r["ttweak"]), int(r["ftweak"])
+        tsec = (HOP * int(r["h0_idx"]) + DT_STEP * tt) / FS
+        fHz = BIN_HZ * int(r["f0_idx"]) + DF_HZ * ft
+        snr = "%+03d" % int(r["snr"])
+        rec = {"ipass": int(r["ipass"]), "method": int(r["method"]), "ap": int(r["ap"]), "ttweak": tt, "ftweak": ft}
+        notes, tw = _m.decode_notes(rec)
+        word_type = (int(r["i3"]) | (int(r["n3"]) << 3)) if ext else 1
+        line = _m._msg_text(word_type, text) if ext else " ".join(text)
+        d = {"band": band, "tsec": tsec, "fHz": fHz, "msg_tuple": text, "their_snr": snr, "their_tx_cycle": parity,
+             "all_txt_format": f"{cyclestart_string} {snr} {(tsec - 0.5):4.1f} {fHz:4.0f} + {line}",
+             "cyclestart_string": cyclestart_string, "decode_completed": now, "tweaks": tw, "decode_notes": notes + tw, "mode": "FT4"}
+        if ext:
+            d["msg_type"] = _m.msg_type(word_type)
+        out.append(d)
+        if on_message is not None:
+            on_message(d)
+    return out
+
+
+# ----------------------------------------------------------------------------- a plain sum-product decoder (CPU check of a fixture)
+def crc14_ok(bits91):
+    from .synth import crc14
+    v = int("".join(str(int(b)) for b in bits91), 2)
+    return crc14(v >> 14) == (v & 0x3FFF)
+
+
+def bp_decode(llr, max_iters=50):
+    """Sum-product BP on LDPC(174,91) (llr > 0 = bit 1) -> the descrambled 77-bit message, or None.  Shows on the CPU that a fixture
+    is decodable; it is not held to the GPU's decoder."""
+    chk = [np.array(CHK_V[c][:CHK_N[c]]) for c in range(83)]
+    L = np.asarray(llr, np.float64)
+    msg = [np.zeros(len(c)) for c in chk]                                  # check -> variable
+    for _ in range(max_iters):
+        tot = L.copy()
+        for c, m in zip(chk, msg):
+            np.add.at(tot, c, m)
+        hard = tot > 0
+        if all(hard[c].sum() % 2 == 0 for c in chk):
+            if crc14_ok(hard[:91]):
+                return (int("".join("1" if b else "0" for b in hard[:77]), 2)) ^ RVEC
+            return None
+        for i, c in enumerate(chk):
+            t = np.tanh(np.clip(-(tot[c] - msg[i]) / 2.0, -19.0, 19.0))
+            prod = np.array([np.prod(np.delete(t, j)) for j in range(len(c))])
+            msg[i] = -2.0 * np.arctanh(np.clip(prod, -0.999999999999, 0.999999999999))
+    return None
+
+
+def decode_twin(x, f0_lo=None, f0_hi=None, h0_lo=None, h0_hi=None, sync_min=SYNC_MIN_DEFAULT, max_cands=200):
+    """The whole twin on one frame: search, fine sync, demodulation, BP -> [dict(f0, h0, tt, ft, snr, word or None), ...]."""
+    a, b = freq_range_to_f0()
+    c, d = time_range_to_h0()
+    f0_lo, f0_hi = (a if f0_lo is None else f0_lo), (b if f0_hi is None else f0_hi)
+    h0_lo, h0_hi = (c if h0_lo is None else h0_lo), (d if h0_hi is None else h0_hi)
+    out = []
+    for f0, h0, score in search(grid_db(grid_power(x)), f0_lo, f0_hi, h0_lo, h0_hi, sync_min, max_cands):
+        r = demod(x, f0, h0)
+        out.append(dict(f0=f0, h0=h0, score=score, tt=r["tt"], ft=r["ft"], snr=r["snr"], llr=r["llr"], word=bp_decode(r["llr"])))
+    return out

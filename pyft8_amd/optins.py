@@ -4,7 +4,7 @@ and _lib.Handle.set_packed_output is a call of refuse(); argument-range checks s
 Adding an opt-in: DESIGN.md section 15."""
 
 PACKED, MSG_TYPES, AP_CALLS, RECALL, WEAK, REPORTS = SETTINGS = ("packed", "msg_types", "ap_calls", "recall", "weak", "reports")
-PASSES, ARRAYS, PACKED_GATHER = CONSUMERS = ("passes", "decode_frames_arrays", "packed_gather")
+PASSES, ARRAYS, PACKED_GATHER, FT4 = CONSUMERS = ("passes", "decode_frames_arrays", "packed_gather", "ft4")
 
 _FIVE = {MSG_TYPES, AP_CALLS, RECALL, WEAK, REPORTS}
 # row -> (the name refusals use, what it cannot run with, a hint: one for the row, or one per other party)
@@ -19,6 +19,8 @@ TABLE = {
              {REPORTS: "the later passes decode a residual whose spectrum the measurement does not have"}),
     ARRAYS: ("decode_frames_arrays", {MSG_TYPES, RECALL, REPORTS}, "its _lib.MESSAGE_DTYPE rows have no place for them; use decode_frames"),
     PACKED_GATHER: ("the packed multi-GPU path (PackedGather)", _FIVE, "decode with Receiver.decode_frames instead"),
+    # FT4 decoding (csrc/optins.hpp FT4_ROW): BP and OSD on the demodulator's LLRs with the msg_types mask, nothing else
+    FT4: ("FT4 decoding (decode_frames_ft4)", {PACKED, AP_CALLS, RECALL, WEAK, REPORTS}, None),
 }
 
 

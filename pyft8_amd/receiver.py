@@ -46,6 +46,7 @@ import numpy as np
 
 from . import _lib
 from . import blanker as _blanker
+from . import ft4 as _ft4
 from . import messages as _m
 from . import optins as _optins
 from . import pan as _pan
@@ -646,9 +647,13 @@ class AudioIn:
         return self.cycle_spectrum
 
 
+_FREQ_RANGE_DEFAULT = [100, 3000]                     # Receiver's defaults as objects: decode_frames_ft4 tells "not given" from them
+_TIME_RANGE_DEFAULT = [-2.5 + 0.5, 2.5 + 0.5]
+
+
 class Receiver:
     def __init__(self, input_device_keywords, on_message, sync_score_min=85, max_cands=200,
-                 search_freq_range=[100, 3000], search_time_range=[-2.5 + 0.5, 2.5 + 0.5], verbose=False,
+                 search_freq_range=_FREQ_RANGE_DEFAULT, search_time_range=_TIME_RANGE_DEFAULT, verbose=False,
                  device=0, max_frames=1, time_source=None, sleep=None, audio_source=None, autostart=None, early_decode_hop=(320, 340),
                  sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False, waterfall=False,
                  **extension_knobs):
@@ -723,6 +728,12 @@ class Receiver:
         self.panorama_opt = extension_knobs.pop("panorama", None)
         _pan.params(self.panorama_opt, 240000)                                # a value outside the definition is refused here
         self._panorama = None
+        # FT4 (decode_frames_ft4): its knobs (None = the library's defaults) and its search range -- the
+        # ranges given here, or FT4's own defaults (12.5 .. 5900 Hz, starts -0.5 .. +2.0 s) where the FT8 defaults were left alone
+        self.ft4_sync_min = extension_knobs.pop("ft4_sync_min", None)
+        self.ft4_osd_max_hd = extension_knobs.pop("ft4_osd_max_hd", None)
+        self._ft4_freq_range = None if search_freq_range is _FREQ_RANGE_DEFAULT else tuple(search_freq_range)
+        self._ft4_time_range = None if search_time_range is _TIME_RANGE_DEFAULT else tuple(search_time_range)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
         if self.recall:
             _optins.refuse(_optins.RECALL, _optins.active(self.cfg))
@@ -1227,6 +1238,43 @@ class Receiver:
     def decode_frame(self, audio_i16, cyclestart_string="700101_000015", float_frames=None):
         return self.decode_frames(np.asarray(audio_i16)[None], [cyclestart_string], float_frames=float_frames)[0]
 
+    def decode_frames_ft4(self, audio_i16, cyclestart_strings=None, return_records=False, passes=1, float_frames=None):
+        """FT4 (extension): audio_i16 [B, 90000] int16, 7.5-s frames at 12 kHz -> per frame the list of message
+        dicts (the keys of decode_frames, "mode": "FT4"; ft4.message_dicts), and the records / counts if asked.  Honours max_cands,
+        search_freq_range, search_time_range (absolute start seconds; FT4's default is -0.5 .. +2.0), msg_types, ft4_sync_min and
+        ft4_osd_max_hd; a fresh call-hash table per frame.  Refused, by name: a-priori calls, recall, weak, reports, the packed output,
+        passes > 1 and float frames."""
+        if (self.float_frames if float_frames is None else bool(float_frames)):
+            raise _lib.Ft8rxError("FT4 decoding (decode_frames_ft4) is not supported together with float_frames=True: FT4 frames are int16")
+        if int(passes) > 1:
+            raise _lib.Ft8rxError(f"FT4 decoding (decode_frames_ft4) is not supported together with {_optins.TABLE[_optins.PASSES][0]}")
+        _optins.refuse(_optins.FT4, _optins.active(self.cfg, recall=self.recall))
+        audio = np.ascontiguousarray(audio_i16, np.int16) if not isinstance(audio_i16, (list, tuple)) else np.stack([np.asarray(a, np.int16) for a in audio_i16])
+        if audio.ndim == 1:
+            audio = audio[None]
+        if audio.ndim != 2 or audio.shape[1] != _lib.FT4_NSAMP or len(audio) < 1:
+            raise _lib.Ft8rxError(f"decode_frames_ft4: audio must be int16 [n_frames, {_lib.FT4_NSAMP}] (7.5 s at 12 kHz); got shape {audio.shape}")
+        B = len(audio)
+        with self._hlock:
+            h = self._handle(B)
+            # the OSD gate: the one given, else the library's default -- with msg_types set, the lower gate of the same noise sweep
+            h.ft4_set(self.ft4_sync_min, self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES)
+            f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
+            h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
+            if f0 == (0, 0) and h0 != (0, 0):
+                f0 = _ft4.freq_range_to_f0()
+            if h0 == (0, 0) and f0 != (0, 0):
+                h0 = _ft4.time_range_to_h0()
+            h.ft4_set_range(f0[0], f0[1], h0[0], h0[1])
+            res = h.ft4_decode(audio)
+            msgs, mcnt = self._package(res)
+        cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
+        out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
+        return (out, res[0], res[1]) if return_records else out
+
+    def decode_frame_ft4(self, audio_i16, cyclestart_string="700101_000000"):
+        return self.decode_frames_ft4(np.asarray(audio_i16)[None], [cyclestart_string])[0]
+
     # ---- streaming mode (stands in for the manage_cycle thread, receiver.py:372-412)
     def _deliver(self, row, dicts, t0, early, seen_by_cycle, hist_by_cycle, out):
         """The tail of a live pass, for the 12 kHz path and for each channel of the wide path alike: `dicts` are the messages of the
@@ -1324,3 +1372,14 @@ def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=
     rx = Receiver("", on_message, max_frames=max(1, audio.shape[0]), recall=recall is not None, float_frames=bool(float_frames),
                   **receiver_kwargs)       # reports=True: "report" in every dict
     return rx.decode_frames(audio, passes=passes, research=research, recall=recall)
+
+
+def decode_frames_ft4(audio_i16, on_message=None, **receiver_kwargs):
+    """decode_frames_ft4(audio_i16[B, 90000], **receiver_kwargs) -> list[list[message dict]]: Receiver.decode_frames_ft4 on a receiver
+    of its own (FT4)."""
+    audio = np.ascontiguousarray(audio_i16, np.int16)
+    rx = Receiver("", on_message, max_frames=max(1, audio.shape[0] if audio.ndim == 2 else 1), **receiver_kwargs)
+    try:
+        return rx.decode_frames_ft4(audio)
+    finally:
+        rx.close()

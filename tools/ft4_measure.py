@@ -1,0 +1,167 @@
+"""FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
+
+    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N]
+
+--prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
+              apart, starts 0.1 .. 1.5 s), through Handle.ft4_decode and the native message layer; the 50 % point by interpolation
+--noise       false decodes on 2048 noise-only frames for a sweep of the OSD distance gate (ft4_osd_max_hd), at msg_types 0 and all
+--throughput  frames/s at B = 256 with 20 signals per frame (-14 .. +5 dB): 3 warm-up and 20 timed calls of ft4_decode (host frames, the
+              copy included) and of ft4_enqueue + fetch (device-resident frames), the stage times (ft8rx_set_profiling)
+--twin N      no GPU: the yardstick, the float64 twin with the numpy BP on N signals per step of -18 .. -11 dB (the same recipe)
+Results are merged into the file's existing sections."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from pyft8_amd import ft4  # noqa: E402
+
+PROB_SNRS = list(range(-20, -7))
+GATES = [16, 20, 24, 28, 30, 32, 36, 40, 48, 174]
+
+
+def prob_frame(step, k, snr):
+    return ft4.make_frame(100000 + 1000 * (step + 40) + k, n_signals=10, snr_range=(snr, snr), return_truth=True)
+
+
+def half_point(snrs, p):
+    for a, b, pa, pb in zip(snrs, snrs[1:], p, p[1:]):
+        if pa < 0.5 <= pb:
+            return a + (0.5 - pa) / (pb - pa) * (b - a)
+    return None
+
+
+def texts_of(h, res, mask=0):
+    from pyft8_amd import _lib
+    msgs, cnt = (_lib.package_batch_ext(*res, mask) if mask else _lib.package_batch(*res))[:2]
+    return [{" ".join(x.decode() for x in m["f"].tolist()).strip() for m in msgs[f][:cnt[f]]} for f in range(len(cnt))]
+
+
+def measure_prob(h, per_step=200):
+    out = {"snr_db": PROB_SNRS, "signals_per_step": per_step, "decoded": [], "bp": [], "osd": []}
+    for snr in PROB_SNRS:
+        frames = [prob_frame(snr, k, float(snr)) for k in range(per_step // 10)]
+        res = h.ft4_decode(np.stack([f[0] for f in frames]))
+        got = texts_of(h, res)
+        n = sum(t["msg"] in got[f] for f, (_, truth) in enumerate(frames) for t in truth)
+        rec, cnt = res[0], res[1]
+        dec = np.concatenate([rec[f, :cnt[f]] for f in range(len(cnt))])
+        dec = dec[dec["status"] == 1]
+        out["decoded"].append(n); out["bp"].append(int((dec["ipass"] == 4).sum())); out["osd"].append(int((dec["ipass"] == 5).sum()))
+        print(f"prob {snr:+d} dB: {n}/{per_step}", flush=True)
+    p = [d / per_step for d in out["decoded"]]
+    out["probability"] = p
+    out["half_point_db"] = half_point(PROB_SNRS, p)
+    return out
+
+
+def measure_twin(per_step):
+    snrs = list(range(-18, -10))
+    out = {"snr_db": snrs, "signals_per_step": per_step, "decoded": []}
+    for snr in snrs:
+        n = 0
+        for k in range((per_step + 9) // 10):
+            x, truth = prob_frame(snr, k, float(snr))
+            words = {c["word"] for c in ft4.decode_twin(x) if c["word"] is not None}
+            n += sum(t["word"] in words for t in truth[:min(10, per_step - 10 * k)])
+        out["decoded"].append(n)
+        print(f"twin {snr:+d} dB: {n}/{per_step}", flush=True)
+    p = [d / per_step for d in out["decoded"]]
+    out["probability"] = p
+    out["half_point_db"] = half_point(snrs, p)
+    return out
+
+
+def noise_frames(n, first):
+    rng = np.random.Generator(np.random.Philox(key=ft4.SEED_BASE + 7000000 + first))
+    return np.clip(np.rint(rng.standard_normal((n, ft4.NFRAME)) * 1000.0), -32768, 32767).astype(np.int16)
+
+
+def measure_noise(h, n_frames=2048, chunk=256):
+    from pyft8_amd import _lib
+    out = {"frames": n_frames, "gates": GATES, "false_decodes": {"0": [0] * len(GATES), "all": [0] * len(GATES)}, "candidates": 0, "texts": []}
+    for first in range(0, n_frames, chunk):
+        a = noise_frames(chunk, first)
+        for name, mask in (("0", 0), ("all", _lib.MT_ALL)):
+            h.set_msg_types(mask)
+            for g, gate in enumerate(GATES):
+                h.ft4_set(osd_max_hd=gate)
+                res = h.ft4_decode(a)
+                rec, cnt = res[0], res[1]
+                if g == 0 and mask == 0:
+                    out["candidates"] += int(cnt.sum())
+                k = sum(int((rec[f, :cnt[f]]["status"] == 1).sum()) for f in range(chunk))
+                out["false_decodes"][name][g] += k
+                if k:
+                    out["texts"] += [f"gate {gate} mask {name}: {t}" for s in texts_of(h, res, mask) for t in s][:4]
+        print(f"noise frames {first + chunk}: {out['false_decodes']}", flush=True)
+    h.set_msg_types(0)
+    h.ft4_set()
+    out["texts"] = out["texts"][:40]
+    return out
+
+
+def throughput_frame(k, n_signals=20):
+    """20 standard messages, carriers 140 Hz apart from 200 Hz on (+- 20 Hz), starts 0.1 .. 1.5 s, -14 .. +5 dB"""
+    rng = np.random.Generator(np.random.Philox(key=ft4.SEED_BASE + 200000 + k))
+    sigs = [(ft4.pack77(*ft4.random_message(rng)), 200.0 + 140.0 * i + rng.uniform(-20.0, 20.0), rng.uniform(0.1, 1.5), rng.uniform(-14.0, 5.0))
+            for i in range(n_signals)]
+    return ft4.frame_with_signals(200000 + k, sigs)
+
+
+def measure_throughput(h, B=256, warmup=3, steps=20):
+    import torch
+    a = np.stack([throughput_frame(k) for k in range(B)])
+    out = {"B": B, "signals_per_frame": 20, "warmup": warmup, "steps": steps}
+    for _ in range(warmup):
+        res = h.ft4_decode(a)
+    t = []
+    for _ in range(steps):
+        t0 = time.perf_counter(); res = h.ft4_decode(a); t.append(time.perf_counter() - t0)
+    out["host_frames_per_s"] = B / float(np.median(t)); out["host_step_ms"] = [round(1e3 * x, 3) for x in t]
+    out["decoded_per_frame"] = float(sum(int((res[0][f, :res[1][f]]["status"] == 1).sum()) for f in range(B))) / B
+    d = torch.from_numpy(a).to("cuda:0"); torch.cuda.synchronize()
+    for _ in range(warmup):
+        h.ft4_enqueue(d.data_ptr(), B); h.fetch(B)
+    t = []
+    for _ in range(steps):
+        t0 = time.perf_counter(); h.ft4_enqueue(d.data_ptr(), B); h.fetch(B); t.append(time.perf_counter() - t0)
+    out["device_frames_per_s"] = B / float(np.median(t)); out["device_step_ms"] = [round(1e3 * x, 3) for x in t]
+    h.set_profiling(True)
+    h.ft4_enqueue(d.data_ptr(), B); h.fetch(B); h.sync()
+    out["stage_ms"] = {k: round(float(v), 4) for k, v in h.stage_times().items()}
+    h.set_profiling(False)
+    print("throughput", out["host_frames_per_s"], out["device_frames_per_s"], out["stage_ms"], flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ft4_measure.json"))
+    ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
+    ap.add_argument("--twin", type=int, default=0)
+    ap.add_argument("--noise-frames", type=int, default=2048)
+    args = ap.parse_args()
+    res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+    if args.twin:
+        res["twin_probability"] = measure_twin(args.twin)
+    if args.prob or args.noise or args.throughput:
+        import torch  # noqa: F401 -- before libft8rx.so loads (_lib.lib)
+        from pyft8_amd import _lib
+        h = _lib.Handle(max_frames=256)
+        if args.throughput:
+            res["throughput"] = measure_throughput(h)
+        if args.prob:
+            res["probability"] = measure_prob(h)
+        if args.noise:
+            res["noise"] = measure_noise(h, args.noise_frames)
+        h.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(res, open(args.out, "w"), indent=1)
+    print("wrote", args.out)
