@@ -996,6 +996,42 @@ int  ft8rx_ft4_osd(ft8rx_handle* h, const float* llr, int n, int singleflips, in
 /* 77-bit words -> the 105 transmitted tones, [n][105].  Host function, no GPU. */
 int  ft8rx_ft4_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n, uint8_t* tones);
 
+/* ---- FT4 subtraction passes (extension; kernels/ft4_sub.hpp; pyft8_amd/ft4.py holds the float64 twin) ----
+ * A decoded signal is its start sample (144 h0_idx + 36 ttweak, may be negative), the frequency of tone 0 as an integer in units of
+ * 12000 / 4608 Hz (4 f0_idx + ftweak) and its 105 tones.  Its model s[n], n < 60480, is the complex form of the transmit waveform;
+ * y[n] = x[start + n] conj(s[n]) (x = 0 outside the frame) is low-passed to the 41 bins k = -20 .. 20 of its 60480-point transform
+ * (+-3.97 Hz) and x -= 2 Re(a s) with a the inverse transform of those bins.  No sample outside the frame is read or written. */
+typedef struct {
+    int32_t start;                   /* samples, may be negative */
+    int32_t fq;                      /* tone 0 in units of 12000/4608 Hz, [0, 4608) */
+    uint8_t tones[105];
+    uint8_t pad[7];
+} ft8rx_ft4_subsig;
+/* For every frame, signals sigs[frame][0 .. counts[frame]) ([n_frames][max_sigs], max_sigs <= 256) are subtracted in list order from
+ * a float32 working copy of the device-resident int16 frames (d_audio: a device pointer, [n_frames][90000]); the residual is rounded
+ * back in place (rint, clipped).  refine = 0: the given starts; refine = 1: before a signal is subtracted the energy of its 41 bins is
+ * evaluated at start + d, d = -24, -20 .. +24 samples, the first maximum wins and the start is written back into sigs; any other
+ * value is refused.  audio_f32_out (host, optional, [n_frames][90000]): the float32 residual before rounding.  Synchronous.  The
+ * workspaces (0.4 MB per frame of max_frames) are allocated at the first call of this or of ft8rx_ft4_sub_probe, all or nothing;
+ * ft8rx_ft4_info's figure does not include them. */
+int  ft8rx_ft4_subtract(ft8rx_handle* h, int16_t* d_audio, int n_frames, ft8rx_ft4_subsig* sigs, const int32_t* counts, int max_sigs,
+                        int refine, float* audio_f32_out);
+/* The signals a sweep removes: a frame's decoded FT4 records in emit order (BP decodes, then OSD's, each in score order), every 77-bit
+ * word once, at its first occurrence, without the words the frame already has (have_lo / have_hi [n_frames][max_have] with
+ * have_counts; NULL = none).  sigs: [n_frames][max_sigs]; returns the largest per-frame count (or < 0).  Host function, no GPU. */
+int  ft8rx_ft4_subtraction_list(const ft8rx_record* records, const int32_t* counts, int max_cands, int n_frames, const uint64_t* have_lo,
+                                const uint64_t* have_hi, const int32_t* have_counts, int max_have, ft8rx_ft4_subsig* sigs, int max_sigs,
+                                int32_t* sig_counts);
+/* bytes of FT4 subtraction workspace the handle holds (0 until its first ft8rx_ft4_subtract / ft8rx_ft4_sub_probe) */
+int  ft8rx_ft4_sub_info(ft8rx_handle* h, uint64_t* workspace_bytes);
+/* the handle's device buffer of FT4 frames ([max_frames][90000]; where the host entries leave the frames of a batch); NULL before the
+ * handle's first FT4 call */
+int16_t* ft8rx_ft4_staging_audio(ft8rx_handle* h);
+/* stage entry point (tests): n signals, signal i on frame frame[i] of the host frames -> model (optional) [n][60480][2], the bins at
+ * the given start [n][41][2] (index k + 20) and the energies of the 13 refine trials [n][13] */
+int  ft8rx_ft4_sub_probe(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const ft8rx_ft4_subsig* sigs,
+                         float* model, double* bins, double* energy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ PROTOTYPES = {
     "ft8rx_ft4_ldpc": (INT, (PTR, PTR, INT, INT, INT, I32) + (PTR,) * 6),
     "ft8rx_ft4_osd": (INT, (PTR, PTR, INT, INT, INT, INT, INT, I32) + (PTR,) * 5),
     "ft8rx_ft4_encode_tones": (INT, (PTR, PTR, INT, PTR)),
+    "ft8rx_ft4_subtract": (INT, (PTR, PTR, INT, PTR, PTR, INT, INT, PTR)),
+    "ft8rx_ft4_subtraction_list": (INT, (PTR, PTR, INT, INT, PTR, PTR, PTR, INT, PTR, INT, PTR)),
+    "ft8rx_ft4_staging_audio": (PTR, (PTR,)),
+    "ft8rx_ft4_sub_info": (INT, (PTR, PTR)),
+    "ft8rx_ft4_sub_probe": (INT, (PTR, PTR, INT, INT, PTR, PTR, PTR, PTR, PTR)),
     # host message layer
     "ft8rx_package_batch": (INT, _RECS + (INT, INT) + _PKG),
     "ft8rx_package_batch_ext": (INT, _RECS + (INT, INT) + _PKG + (I32,)),

@@ -77,6 +77,8 @@ MSG_TYPE_BITS = {"free_text": 1, "dxpedition": 2, "field_day": 4, "telemetry": 8
 MT_ALL = 63
 SUBSIG_DTYPE = np.dtype([("fHz", "<f8"), ("tsec", "<f8"), ("tones", "u1", (79,)), ("pad", "u1")])
 assert SUBSIG_DTYPE.itemsize == 96
+FT4_SUBSIG_DTYPE = np.dtype([("start", "<i4"), ("fq", "<i4"), ("tones", "u1", (105,)), ("pad", "u1", (7,))])     # ft8rx_ft4_subsig
+assert FT4_SUBSIG_DTYPE.itemsize == 120
 # packed results (include/ft8rx.h: ft8rx_packed_header / ft8rx_packed_frame): header | frame table | kept records | used events
 PACKED_MAGIC = 0x50385446
 PACKED_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("n_frames", "<i4"), ("n_records", "<i4"), ("n_events", "<i4"), ("bytes", "<u8"),
@@ -853,6 +855,59 @@ class Handle:
         self._chk(self._L.ft8rx_ft4_osd(self._h, llr.ctypes.data, n, int(singleflips), int(doubleflips), int(tripleflips), int(max_hd), int(mask),
                                         *[a.ctypes.data for a in (ok, lo, hi, trial, hd)]), "ft8rx_ft4_osd")
         return ok, lo, hi, trial, hd
+
+    def ft4_staging_ptr(self):
+        """ft8rx_ft4_staging_audio: the device buffer where ft4_decode left the frames of its batch (0 before the first FT4 call)."""
+        return int(self._L.ft8rx_ft4_staging_audio(self._h) or 0)
+
+    def ft4_sub_info(self):
+        """ft8rx_ft4_sub_info -> dict(workspace_bytes): 0 until the handle's first ft4_subtract / ft4_sub_probe."""
+        wb = C.c_uint64()
+        self._chk(self._L.ft8rx_ft4_sub_info(self._h, C.byref(wb)), "ft8rx_ft4_sub_info")
+        return dict(workspace_bytes=int(wb.value))
+
+    def ft4_subtract(self, d_audio_ptr, n_frames, signals, refine=1, return_float=False):
+        """ft8rx_ft4_subtract on device-resident int16 frames [B, 90000], in place.  signals: (array [B, max_sigs] of FT4_SUBSIG_DTYPE,
+        counts [B]), or per frame a list of (start, fq, tones105); subtracted in list order.  refine 1: the 13-trial start scan.
+        -> (signals with the starts used, counts, the float32 residual before rounding or None)."""
+        B = int(n_frames)
+        if isinstance(signals, tuple):
+            arr, cnt = signals
+            arr = np.ascontiguousarray(arr, FT4_SUBSIG_DTYPE).copy()
+            cnt = np.ascontiguousarray(cnt, np.int32)
+        else:
+            arr = np.zeros((B, max(1, max((len(s) for s in signals), default=1))), FT4_SUBSIG_DTYPE)
+            cnt = np.zeros(B, np.int32)
+            for f, lst in enumerate(signals):
+                cnt[f] = len(lst)
+                for i, (start, fq, tones) in enumerate(lst):
+                    arr[f, i]["start"], arr[f, i]["fq"], arr[f, i]["tones"] = start, fq, np.asarray(tones, np.uint8)
+        if arr.ndim != 2 or arr.shape[0] != B or len(cnt) != B:
+            raise Ft8rxError(f"ft4_subtract: signals [n_frames = {B}][max_sigs] and one count per frame expected")
+        out = np.empty((B, FT4_NSAMP), np.float32) if return_float else None
+        self._chk(self._L.ft8rx_ft4_subtract(self._h, C.c_void_p(d_audio_ptr), B, arr.ctypes.data, cnt.ctypes.data, int(arr.shape[1]), int(refine),
+                                             out.ctypes.data if return_float else None), "ft8rx_ft4_subtract")
+        return arr, cnt, out
+
+    def ft4_sub_probe(self, audio, frame, sigs, want_model=False):
+        """ft8rx_ft4_sub_probe: signal i (FT4_SUBSIG_DTYPE) on frame frame[i] of the host frames -> dict(bins complex [n, 41] at the given
+        start (index k + 20), energy [n, 13] of the refine trials, model complex64 [n, 60480] if asked)."""
+        audio = self._ft4_audio(audio, "ft4_sub_probe")
+        frame = np.ascontiguousarray(frame, np.int32).reshape(-1)
+        sigs = np.ascontiguousarray(sigs, FT4_SUBSIG_DTYPE).reshape(-1)
+        n = len(frame)
+        if n < 1 or len(sigs) != n:
+            raise Ft8rxError("ft4_sub_probe: one frame per signal")
+        bins, en = np.zeros((n, 41), np.complex128), np.zeros((n, 13), np.float64)
+        model = np.zeros((n, 60480), np.complex64) if want_model else None
+        self._chk(self._L.ft8rx_ft4_sub_probe(self._h, audio.ctypes.data, len(audio), n, frame.ctypes.data, sigs.ctypes.data,
+                                              model.ctypes.data if want_model else None, bins.ctypes.data, en.ctypes.data), "ft8rx_ft4_sub_probe")
+        return dict(bins=bins, energy=en, model=model)
+
+    def download_audio_ft4(self, d_ptr, n_frames):
+        out = np.empty((int(n_frames), FT4_NSAMP), np.int16)
+        self._chk(self._L.ft8rx_copy_to_host(self._h, out.ctypes.data, C.c_void_p(d_ptr), out.nbytes), "ft8rx_copy_to_host")
+        return out
 
     def crc_valid(self, cw91):
         cw91 = np.ascontiguousarray(cw91, np.float32).reshape(-1, 91)
@@ -1636,6 +1691,35 @@ def ft4_encode_tones(msg_lo, msg_hi):
     if lib().ft8rx_ft4_encode_tones(lo.ctypes.data, hi.ctypes.data, len(lo), out.ctypes.data) != 0:
         raise Ft8rxError("ft8rx_ft4_encode_tones failed")
     return out
+
+
+def ft4_subtraction_list(rec, cnt, have=None):
+    """ft8rx_ft4_subtraction_list (host only): per frame the decoded FT4 records in emit order, every word once, without the words
+    of have[f] (an iterable of 77-bit integers per frame) -> (signals [B, max] of FT4_SUBSIG_DTYPE, counts [B])."""
+    rec = np.ascontiguousarray(rec)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    if rec.dtype != RECORD_DTYPE or rec.ndim != 2 or len(cnt) != len(rec):
+        raise Ft8rxError("ft4_subtraction_list: record arrays as returned by ft4_decode expected")
+    B, mc = rec.shape
+    hl = hh = hc = None
+    mh = 0
+    if have is not None:
+        have = [[int(w) for w in hv] for hv in have]
+        mh = max(1, max((len(hv) for hv in have), default=1))
+        hl, hh, hc = np.zeros((B, mh), np.uint64), np.zeros((B, mh), np.uint64), np.zeros(B, np.int32)
+        for f, hv in enumerate(have):
+            hc[f] = len(hv)
+            for j, w in enumerate(hv):
+                hl[f, j], hh[f, j] = w & 0xFFFFFFFFFFFFFFFF, w >> 64
+    cap = max(1, int(min(cnt.max(), mc)) if B else 1)
+    arr = np.zeros((B, cap), FT4_SUBSIG_DTYPE)
+    out = np.zeros(B, np.int32)
+    most = lib().ft8rx_ft4_subtraction_list(rec.ctypes.data, cnt.ctypes.data, int(mc), int(B), hl.ctypes.data if mh else None,
+                                            hh.ctypes.data if mh else None, hc.ctypes.data if mh else None, int(mh), arr.ctypes.data, int(cap),
+                                            out.ctypes.data)
+    if most < 0:
+        raise Ft8rxError(f"ft8rx_ft4_subtraction_list failed ({most})")
+    return np.ascontiguousarray(arr[:, :max(1, most)]), out
 
 
 def ap_patterns(my_call=None, dx_call=None):

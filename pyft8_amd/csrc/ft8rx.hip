@@ -71,6 +71,7 @@
 #include "kernels/ft4.hpp"
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
+#include "kernels/ft4_sub.hpp"      // after subtract.hpp: it shares wave_sum2 and the int16 <-> float32 copies
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
@@ -317,6 +318,14 @@ struct ft8rx_handle {
         int32_t* d_snr = nullptr; Att* d_att = nullptr; Att* d_attO = nullptr; int32_t* d_items = nullptr; float* d_dense = nullptr;
         int32_t* d_nan = nullptr; int32_t* d_count = nullptr; int32_t* h_count = nullptr;
     } ft4;
+    // FT4 subtraction (ft8rx_ft4_subtract / _sub_probe, kernels/ft4_sub.hpp; allocated at the first of those calls, WS_FT4_SUB): the
+    // float32 working copy [max_frames][90000], the partial bins [max_frames][13][6][41], the pulse's running sum [1729], and per row
+    // the winning trial, the signal count, the frame of a probe row, the 13 energies and FT4SUB_MAXSIGS signals
+    struct Ft4Sub {
+        size_t bytes = 0;
+        float* d_wf = nullptr; double2* d_part = nullptr; double* d_pc = nullptr; int32_t* d_best = nullptr; int32_t* d_cnt = nullptr;
+        int32_t* d_frame = nullptr; double* d_energy = nullptr; ft8rx_ft4_subsig* d_sigs = nullptr;
+    } ft4sub;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -403,7 +412,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4 };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3795,6 +3804,144 @@ int ft8rx_ft4_osd(ft8rx_handle* h, const float* llr, int n, int singleflips, int
 int ft8rx_ft4_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n, uint8_t* tones) {
     if (!msg_lo || !msg_hi || !tones || n < 0) return -1;
     for (int i = 0; i < n; i++) hostmsg::encode_tones_ft4(msg_lo[i], msg_hi[i], tones + (size_t)i * 105);
+    return 0;
+}
+
+// ---- FT4 subtraction (kernels/ft4_sub.hpp)
+#define FT4SUB_MAXSIGS 256
+// Everything FT4 subtraction owns, at the first ft8rx_ft4_subtract / ft8rx_ft4_sub_probe on the handle, all or nothing
+static int ft4sub_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4_SUB)) return 0;
+    ft8rx_handle::Ft4Sub& w = h->ft4sub;
+    const size_t mf = (size_t)h->max_frames;
+    FirstUse F(h, WS_FT4_SUB);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_wf, mf * FT8RX_FT4_NSAMP); dev(&w.d_part, mf * FT4S_NT * FT4S_GRIDX * FT4S_NB); dev(&w.d_pc, (size_t)FT4S_PC);
+    dev(&w.d_best, mf); dev(&w.d_cnt, mf); dev(&w.d_frame, mf); dev(&w.d_energy, mf * FT4S_NT); dev(&w.d_sigs, mf * FT4SUB_MAXSIGS);
+    if (!F.rc) {
+        // the BT = 1.0 pulse over three symbols (ft4.py _gfsk_pulse) and its exclusive running sum
+        std::vector<double> pc(FT4S_PC);
+        const double k = M_PI * sqrt(2.0 / log(2.0));
+        double acc = 0.0;
+        for (int i = 0; i < FT4S_PC; i++) {
+            pc[i] = acc;
+            const double t = ((double)i - 1.5 * FT4_NSPS) / (double)FT4_NSPS;
+            acc += 0.5 * (erf(k * (t + 0.5)) - erf(k * (t - 0.5)));
+        }
+        FIRST_HIP(F, hipMemcpy(w.d_pc, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemset(w.d_best, 0, sizeof(int32_t) * mf));
+    }
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
+static Ft4SubShifts ft4sub_shifts(int refine) {
+    Ft4SubShifts t;
+    t.n = refine ? FT4S_NT : 1;
+    for (int i = 0; i < FT4S_NT; i++) t.shift[i] = refine ? 4 * (i - FT4S_NT / 2) : 0;
+    return t;
+}
+// a signal the kernels can walk: tones 0 .. 3, fq x 60480 below 2^31 with room, a start whose sums stay far from overflow
+static bool ft4sub_sig_ok(const ft8rx_ft4_subsig& g) {
+    if (g.fq < 0 || g.fq >= 4608 || g.start < -(1 << 20) || g.start > (1 << 20)) return false;
+    for (int i = 0; i < FT4_NSYM; i++) if (g.tones[i] > 3) return false;
+    return true;
+}
+// signal sel.s of `rows` rows: the trials' bins, the pick (energy: optional [rows][13]), and -- apply -- the subtraction
+static void ft4sub_one(ft8rx_handle* h, int rows, const Ft4SubSel& sel, const Ft4SubShifts& sh, double* energy, bool apply) {
+    const ft8rx_handle::Ft4Sub& w = h->ft4sub;
+    k_ft4_sub_bins<<<dim3(FT4S_GRIDX, rows, sh.n), 256, 0, h->stream>>>(w.d_wf, sel, w.d_pc, sh, w.d_part);
+    k_ft4_sub_pick<<<rows, 64, 0, h->stream>>>(sel, sh, w.d_part, w.d_best, energy);
+    if (apply) k_ft4_sub_apply<<<dim3(FT4S_GRIDX, rows), 256, 0, h->stream>>>(w.d_wf, sel, w.d_pc, w.d_part, w.d_best);
+}
+
+int ft8rx_ft4_subtract(ft8rx_handle* h, int16_t* d_audio, int B, ft8rx_ft4_subsig* sigs, const int32_t* counts, int max_sigs, int refine,
+                       float* audio_f32_out) {
+    if (!h || !d_audio || !sigs || !counts) return -1;
+    if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_ft4_subtract: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
+    if (max_sigs < 1 || max_sigs > FT4SUB_MAXSIGS) { set_err(h, "ft8rx_ft4_subtract: max_sigs %d outside [1, %d]", max_sigs, FT4SUB_MAXSIGS); return -1; }
+    if (refine != 0 && refine != 1) { set_err(h, "ft8rx_ft4_subtract: refine %d is not 0 (the given starts) or 1 (the 13-trial start scan)", refine); return -1; }
+    int nmax = 0;
+    for (int f = 0; f < B; f++) {
+        if (counts[f] < 0 || counts[f] > max_sigs) { set_err(h, "ft8rx_ft4_subtract: counts[%d] = %d outside [0, %d]", f, counts[f], max_sigs); return -1; }
+        for (int i = 0; i < counts[f]; i++)
+            if (!ft4sub_sig_ok(sigs[(size_t)f * max_sigs + i])) { set_err(h, "ft8rx_ft4_subtract: signal %d of frame %d is out of range (tones 0 .. 3, fq in [0, 4608), |start| <= 2^20)", i, f); return -1; }
+        if (counts[f] > nmax) nmax = counts[f];
+    }
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (const int rc = ft4sub_workspaces(h)) return rc;
+    const ft8rx_handle::Ft4Sub& w = h->ft4sub;
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(w.d_sigs, sigs, sizeof(ft8rx_ft4_subsig) * (size_t)B * max_sigs, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(w.d_cnt, counts, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    const size_t n = (size_t)B * FT8RX_FT4_NSAMP;
+    k_sub_to_f32<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_audio, w.d_wf, n);
+    const Ft4SubShifts sh = ft4sub_shifts(refine);
+    for (int i = 0; i < nmax; i++) ft4sub_one(h, B, Ft4SubSel{w.d_sigs, w.d_cnt, nullptr, max_sigs, i}, sh, nullptr, true);
+    k_sub_to_i16<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w.d_wf, d_audio, n);
+    HIPCHK(h, hipGetLastError());
+    if (audio_f32_out) HIPCHK(h, hipMemcpyAsync(audio_f32_out, w.d_wf, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    if (refine) HIPCHK(h, hipMemcpyAsync(sigs, w.d_sigs, sizeof(ft8rx_ft4_subsig) * (size_t)B * max_sigs, hipMemcpyDeviceToHost, s));   // the refined starts
+    HIPCHK(h, hipStreamSynchronize(s));
+    return 0;
+}
+int ft8rx_ft4_subtraction_list(const ft8rx_record* records, const int32_t* counts, int max_cands, int n_frames, const uint64_t* have_lo,
+                               const uint64_t* have_hi, const int32_t* have_counts, int max_have, ft8rx_ft4_subsig* sigs, int max_sigs,
+                               int32_t* sig_counts) {
+    return hostmsg::ft4_subtraction_list(records, counts, max_cands, n_frames, have_lo, have_hi, have_counts, max_have, sigs, max_sigs, sig_counts);
+}
+int ft8rx_ft4_sub_info(ft8rx_handle* h, uint64_t* workspace_bytes) {
+    if (!h || !workspace_bytes) return -1;
+    *workspace_bytes = ws_ready(h, WS_FT4_SUB) ? (uint64_t)h->ft4sub.bytes : 0;
+    return 0;
+}
+int16_t* ft8rx_ft4_staging_audio(ft8rx_handle* h) {
+    if (!h || !ws_ready(h, WS_FT4)) return nullptr;
+    return h->ft4.d_audio;
+}
+int ft8rx_ft4_sub_probe(ft8rx_handle* h, const int16_t* audio, int B, int n, const int32_t* frame, const ft8rx_ft4_subsig* sigs, float* model,
+                        double* bins, double* energy) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_sub_probe", audio, B) || n < 1 || !frame || !sigs || !bins || !energy) return -1;
+    for (int i = 0; i < n; i++)
+        if (frame[i] < 0 || frame[i] >= B || !ft4sub_sig_ok(sigs[i])) {
+            set_err(h, "ft8rx_ft4_sub_probe: signal %d (frame %d) is out of range (tones 0 .. 3, fq in [0, 4608), |start| <= 2^20)", i, frame[i]); return -1; }
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    if (const int rc = ft4sub_workspaces(h)) return rc;
+    const ft8rx_handle::Ft4Sub& w = h->ft4sub;
+    hipStream_t s = h->stream;
+    const size_t na = (size_t)B * FT8RX_FT4_NSAMP;
+    HIPCHK(h, hipMemcpy(h->ft4.d_audio, audio, sizeof(int16_t) * na, hipMemcpyHostToDevice));
+    k_sub_to_f32<<<(unsigned)((na + 255) / 256), 256, 0, s>>>(h->ft4.d_audio, w.d_wf, na);
+    Scratch S{h};
+    float2* d_model = nullptr;
+    if (model) { d_model = S.get<float2>((size_t)h->max_frames * FT4S_N); NEED(d_model); }
+    const std::vector<int32_t> ones((size_t)h->max_frames, 1);
+    HIPCHK(h, hipMemcpyAsync(w.d_cnt, ones.data(), sizeof(int32_t) * ones.size(), hipMemcpyHostToDevice, s));
+    const Ft4SubShifts sh = ft4sub_shifts(1);
+    std::vector<double2> part((size_t)FT4S_NT * FT4S_GRIDX * FT4S_NB);
+    for (int i0 = 0; i0 < n; i0 += h->max_frames) {                       // the signals in slabs of max_frames rows, one signal per row
+        const int rows = n - i0 < h->max_frames ? n - i0 : h->max_frames;
+        HIPCHK(h, hipMemcpyAsync(w.d_sigs, sigs + i0, sizeof(ft8rx_ft4_subsig) * rows, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(w.d_frame, frame + i0, sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
+        const Ft4SubSel sel{w.d_sigs, w.d_cnt, w.d_frame, 1, 0};
+        if (model) k_ft4_sub_model<<<dim3(FT4S_GRIDX, rows), 256, 0, s>>>(sel, w.d_pc, d_model);
+        ft4sub_one(h, rows, sel, sh, w.d_energy, false);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (model) HIPCHK(h, hipMemcpy(model + (size_t)i0 * FT4S_N * 2, d_model, sizeof(float2) * (size_t)rows * FT4S_N, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(energy + (size_t)i0 * FT4S_NT, w.d_energy, sizeof(double) * (size_t)rows * FT4S_NT, hipMemcpyDeviceToHost));
+        for (int r = 0; r < rows; r++) {                                  // the bins at the given start: trial 6 (shift 0), the partials in block order
+            HIPCHK(h, hipMemcpy(part.data(), w.d_part + (size_t)r * part.size(), sizeof(double2) * part.size(), hipMemcpyDeviceToHost));
+            for (int b = 0; b < FT4S_NB; b++) {
+                double vr = 0.0, vi = 0.0;
+                for (int c = 0; c < FT4S_GRIDX; c++) { const double2 v = part[((size_t)(FT4S_NT / 2) * FT4S_GRIDX + c) * FT4S_NB + b]; vr += v.x; vi += v.y; }
+                bins[((size_t)(i0 + r) * FT4S_NB + b) * 2] = vr; bins[((size_t)(i0 + r) * FT4S_NB + b) * 2 + 1] = vi;
+            }
+        }
+    }
     return 0;
 }
 

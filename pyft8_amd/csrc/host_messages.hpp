@@ -611,6 +611,49 @@ static int subtraction_list(const ft8rx_message* msgs, const int32_t* counts, in
     }
     return most;
 }
+// Input of an FT4 subtraction sweep: a frame's decoded records in emit order -- the BP decodes (ipass 4),
+// then OSD's (ipass 5), each in score order as package_frame replays them -- every 77-bit word once, at its first occurrence, none
+// of the words the frame already has (have_lo / have_hi [n_frames][max_have], NULL = none); start = 144 h0 + 36 ttweak,
+// fq = 4 f0 + ftweak.  A record whose fq falls outside [0, 4608) is left out.  -> the largest per-frame count, or -1.
+static int ft4_subtraction_list(const ft8rx_record* records, const int32_t* counts, int max_cands, int n_frames, const uint64_t* have_lo,
+                                const uint64_t* have_hi, const int32_t* have_counts, int max_have, ft8rx_ft4_subsig* sigs, int max_sigs,
+                                int32_t* sig_counts) {
+    if (!records || !counts || !sigs || !sig_counts || max_cands < 1 || n_frames < 1 || max_sigs < 1) return -1;
+    const bool have = have_lo && have_hi && have_counts && max_have > 0;
+    int most = 0;
+    std::vector<int> order;
+    for (int f = 0; f < n_frames; f++) {
+        const ft8rx_record* rec = records + (size_t)f * max_cands;
+        ft8rx_ft4_subsig* o = sigs + (size_t)f * max_sigs;
+        const int nc = counts[f] < 0 ? 0 : counts[f] > max_cands ? max_cands : counts[f];
+        order.clear();
+        for (int i = 0; i < nc; i++) if (rec[i].status == FT8RX_ST_DECODED && (rec[i].ipass == 4 || rec[i].ipass == 5)) order.push_back(i);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+            return rec[a].ipass != rec[b].ipass ? rec[a].ipass < rec[b].ipass : rec[a].fine_sd > rec[b].fine_sd; });
+        const int nh = !have ? 0 : have_counts[f] < 0 ? 0 : have_counts[f] > max_have ? max_have : have_counts[f];
+        int n = 0;
+        for (int i : order) {
+            if (n >= max_sigs) break;
+            const ft8rx_record& r = rec[i];
+            const uint64_t lo = r.msg_lo, hi = r.msg_hi & 0x1FFFull;
+            bool seen = false;
+            for (int j = 0; j < nh && !seen; j++) seen = have_lo[(size_t)f * max_have + j] == lo && (have_hi[(size_t)f * max_have + j] & 0x1FFFull) == hi;
+            if (seen) continue;
+            const int fq = 4 * (int)r.f0_idx + (int)r.ftweak;
+            if (fq < 0 || fq >= 4608) continue;
+            ft8rx_ft4_subsig g; memset(&g, 0, sizeof(g));
+            encode_tones_ft4(lo, hi, g.tones);
+            bool twice = false;                                           // the same word again: the remnant of a strong signal
+            for (int j = 0; j < n && !twice; j++) twice = memcmp(o[j].tones, g.tones, sizeof(g.tones)) == 0;
+            if (twice) continue;
+            g.start = 144 * (int)r.h0_idx + 36 * (int)r.ttweak; g.fq = fq;
+            o[n++] = g;
+        }
+        sig_counts[f] = n;
+        if (n > most) most = n;
+    }
+    return most;
+}
 }  // namespace hostmsg
 
 #endif

@@ -18,6 +18,9 @@ The twin is the definition the kernels are held to (tests/test_gpu_ft4.py):
   demod    the 105 x 4 amplitude matrix at the winner; 174 max-log LLRs on amplitudes (positive = bit 1), scaled 2.83 / std (all
            zero where std = 0; otherwise an LLR of exactly 0 -- a symbol outside the frame -- becomes +0.001); SNR from the
            matrix's powers
+and of the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/test_gpu_ft4_sub.py; stated in full where sub_model stands, below):
+  model    the complex form of tones_to_wave; bins: 41 bins (+-3.97 Hz) of the 60480-point transform of x conj(model); refine: the
+           bins' energy at 13 starts 4 samples apart, the first maximum; subtract: x -= 2 Re(a model), a = the bins' inverse transform
 """
 import numpy as np
 
@@ -363,4 +366,163 @@ def decode_twin(x, f0_lo=None, f0_hi=None, h0_lo=None, h0_hi=None, sync_min=SYNC
     for f0, h0, score in search(grid_db(grid_power(x)), f0_lo, f0_hi, h0_lo, h0_hi, sync_min, max_cands):
         r = demod(x, f0, h0)
         out.append(dict(f0=f0, h0=h0, score=score, tt=r["tt"], ft=r["ft"], snr=r["snr"], llr=r["llr"], word=bp_decode(r["llr"])))
+    return out
+
+
+# ----------------------------------------------------------------------------- the twin: subtraction passes (csrc/kernels/ft4_sub.hpp)
+# A decoded signal is (start sample s0 = 144 h0 + 36 tt, possibly negative; fq = 4 f0 + ft, tone 0 in units of 12000 / 4608 Hz; the
+# 105 tones).  model s[n], n < 60480: the complex form of tones_to_wave.  Analysis y[n] = x[s0 + n] conj(s[n]) (x = 0 outside the
+# frame), A[k] = sum_n y[n] e^{-2 pi i k n / 60480}, k = -20 .. 20: a +-3.97-Hz low-pass, wide enough for the +-1.3 Hz the fine grid
+# leaves.  Subtraction x[s0 + n] -= 2 Re(a[n] s[n]), a = the inverse transform of the 41 kept bins.  Refine: E(d) = sum_k |A_d[k]|^2
+# with the start at s0 + d for d = -24, -20 .. 24; the first maximum wins.  DESIGN.md section 19.6.
+SUB_N = NSYM * NSPS                    # 60480 model samples
+SUB_K = 20                             # bins -20 .. +20 of 12000 / 60480 = 0.198 Hz
+SUB_SHIFTS = tuple(range(-24, 25, 4))  # the 13 refine trials, samples
+
+
+def sig_from_record(f0, h0, tt, ft, word):
+    """(f0 bin, h0 row, time tweak, frequency tweak, 77-bit word) -> dict(start, fq, tones): what a subtraction sweep takes."""
+    return dict(start=HOP * int(h0) + DT_STEP * int(tt), fq=4 * int(f0) + int(ft), tones=tones105(int(word)), word=int(word))
+
+
+def sub_model(tones, fq):
+    """The complex model s[60480] of a signal with tone 0 at fq x 12000 / 4608 Hz: Im s = tones_to_wave(tones, fq * DF_HZ)."""
+    global _PULSE
+    if _PULSE is None:
+        _PULSE = _gfsk_pulse()
+    n = len(tones)
+    ext = [tones[0]] + list(tones) + [tones[-1]]
+    dphi = np.zeros((n + 2) * NSPS + 2 * NSPS)
+    for i, t in enumerate(ext):
+        dphi[i * NSPS:i * NSPS + 3 * NSPS] += t * _PULSE
+    dphi = dphi[2 * NSPS: 2 * NSPS + n * NSPS]
+    dphi = 2 * np.pi * (fq * 12000.0 / 4608.0 + TONE_HZ * dphi) / FS
+    s = np.exp(1j * (np.cumsum(dphi) - dphi))
+    ramp = 0.5 * (1 - np.cos(np.pi * np.arange(NSPS) / NSPS))
+    s[:NSPS] *= ramp
+    s[-NSPS:] *= ramp[::-1]
+    return s
+
+
+def _sub_window(x, s0, n=SUB_N):
+    """x[s0 : s0 + n] with zeros outside the frame, and the mask of the samples inside."""
+    i = int(s0) + np.arange(n)
+    ok = (i >= 0) & (i < len(x))
+    return np.where(ok, x[np.clip(i, 0, len(x) - 1)], 0.0), ok
+
+
+def sub_bins(x, s0, model):
+    """The 41 bins A[k], k = -20 .. 20 (index k + 20), of y[n] = x[s0 + n] conj(model[n])."""
+    w, _ = _sub_window(np.asarray(x, np.float64), s0, len(model))
+    Y = np.fft.fft(w * np.conj(model))
+    return np.concatenate([Y[-SUB_K:], Y[:SUB_K + 1]])
+
+
+def sub_energies(x, s0, model):
+    """E(d) of the 13 refine trials around s0."""
+    return np.array([(np.abs(sub_bins(x, s0 + d, model)) ** 2).sum() for d in SUB_SHIFTS])
+
+
+def sub_refine(x, sig, model=None):
+    """-> (the refined start: s0 + the first maximum's shift, the 13 energies)."""
+    model = sub_model(sig["tones"], sig["fq"]) if model is None else model
+    E = sub_energies(x, sig["start"], model)
+    return int(sig["start"]) + SUB_SHIFTS[int(np.argmax(E))], E
+
+
+def sub_apply(x, s0, model):
+    """Subtracts the signal at start s0 from the float64 frame x in place; samples outside the frame are never touched."""
+    A = sub_bins(x, s0, model)
+    S = np.zeros(len(model), np.complex128)
+    S[-SUB_K:] = A[:SUB_K]
+    S[:SUB_K + 1] = A[SUB_K:]
+    a = np.fft.ifft(S)
+    i = int(s0) + np.arange(len(model))
+    ok = (i >= 0) & (i < len(x))
+    x[i[ok]] -= 2.0 * (a * model).real[ok]
+
+
+def subtract(x, sigs, refine=1):
+    """Subtracts sigs (dicts of start, fq, tones) from the float64 frame x in list order, in place -> the starts used."""
+    starts = []
+    for sg in sigs:
+        model = sub_model(sg["tones"], sg["fq"])
+        s0 = sub_refine(x, sg, model)[0] if refine else int(sg["start"])
+        sub_apply(x, s0, model)
+        starts.append(s0)
+    return starts
+
+
+def subtraction_list(decodes, have=()):
+    """decodes: (f0, h0, tt, ft, word) in emit order -> the sweep's list: each word once, at its first occurrence, none of `have`."""
+    seen, out = set(int(w) for w in have), []
+    for f0, h0, tt, ft, word in decodes:
+        if int(word) in seen:
+            continue
+        seen.add(int(word))
+        out.append(sig_from_record(f0, h0, tt, ft, word))
+    return out
+
+
+_CHK_IDX = None
+
+
+def bp_decode_many(llrs, max_iters=50):
+    """bp_decode on rows of LLRs at once (the same sum-product update and stopping rule, vectorised) -> [word or None, ...]."""
+    global _CHK_IDX
+    L = np.atleast_2d(np.asarray(llrs, np.float64))
+    if _CHK_IDX is None:
+        idx = np.full((83, 7), 174, np.int64)                              # column 174: a dummy variable that is never wrong
+        for c in range(83):
+            idx[c, :CHK_N[c]] = CHK_V[c][:CHK_N[c]]
+        _CHK_IDX = idx
+    idx, pad = _CHK_IDX, _CHK_IDX == 174
+    n = len(L)
+    out = [None] * n
+    live = np.arange(n)
+    msg = np.zeros((n, 83, 7))
+    for _ in range(max_iters):
+        if len(live) == 0:
+            break
+        tot = np.concatenate([L[live], np.zeros((len(live), 1))], axis=1)
+        np.add.at(tot, (np.arange(len(live))[:, None, None], idx[None]), np.where(pad, 0.0, msg[live]))
+        hard = tot[:, :174] > 0
+        h7 = np.where(pad, False, np.concatenate([hard, np.zeros((len(live), 1), bool)], axis=1)[:, idx])
+        done = (h7.sum(axis=2) % 2 == 0).all(axis=1)
+        for j in np.nonzero(done)[0]:
+            if crc14_ok(hard[j, :91]):
+                out[live[j]] = int("".join("1" if b else "0" for b in hard[j, :77]), 2) ^ RVEC
+        keep = ~done
+        t = np.tanh(np.clip(-(tot[keep][:, idx] - msg[live[keep]]) / 2.0, -19.0, 19.0))
+        t = np.where(pad, 1.0, t)
+        prod = np.stack([np.prod(np.delete(t, j, axis=2), axis=2) for j in range(7)], axis=2)
+        live = live[keep]
+        msg[live] = np.where(pad, 0.0, -2.0 * np.arctanh(np.clip(prod, -0.999999999999, 0.999999999999)))
+    return out
+
+
+def decode_twin_passes(x, passes=2, max_cands=200, sync_min=SYNC_MIN_DEFAULT, refine=1):
+    """decode_twin with subtraction passes on one int16 frame -> [dict(start, fq, word, pass), ...], the words in emit order
+    (score order within a pass), each once.  Pass p + 1: subtract the words new since pass p from a float copy, round it back to int16
+    (rint, clipped), decode again, append the words the frame does not have yet; stops when a pass brings nothing new."""
+    a, b = freq_range_to_f0()
+    c, d = time_range_to_h0()
+    work = np.asarray(x, np.float64).copy()
+    cur = np.asarray(x, np.int16)
+    out, have, fresh = [], set(), []
+    for p in range(int(passes)):
+        if p:
+            if not fresh:
+                break
+            subtract(work, fresh, refine)
+            cur = np.clip(np.rint(work), -32768, 32767).astype(np.int16)
+            work = cur.astype(np.float64)
+        cands = search(grid_db(grid_power(cur)), a, b, c, d, sync_min, max_cands)
+        dem = [demod(cur, f0, h0) for f0, h0, _ in cands]
+        words = bp_decode_many([r["llr"] for r in dem]) if dem else []
+        dec = [(f0, h0, r["tt"], r["ft"], w) for (f0, h0, _), r, w in zip(cands, dem, words) if w is not None]
+        fresh = subtraction_list(dec, have)
+        for sg in fresh:
+            have.add(sg["word"])
+            out.append({"start": sg["start"], "fq": sg["fq"], "word": sg["word"], "pass": p + 1})
     return out

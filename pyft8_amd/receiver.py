@@ -732,6 +732,13 @@ class Receiver:
         # ranges given here, or FT4's own defaults (12.5 .. 5900 Hz, starts -0.5 .. +2.0 s) where the FT8 defaults were left alone
         self.ft4_sync_min = extension_knobs.pop("ft4_sync_min", None)
         self.ft4_osd_max_hd = extension_knobs.pop("ft4_osd_max_hd", None)
+        # ft4_passes (section 19.6): 1 = one pass; 2, 3 = remove the decoded signals and decode the residual again, that often.
+        # ft4_sub_osd_max_hd: OSD's distance gate in the passes after the first (None = the first pass's gate)
+        self.ft4_passes = extension_knobs.pop("ft4_passes", 1)
+        if isinstance(self.ft4_passes, bool) or not isinstance(self.ft4_passes, (int, np.integer)) or not 1 <= self.ft4_passes <= 3:
+            raise _lib.Ft8rxError(f"ft4_passes must be 1, 2 or 3, got {self.ft4_passes!r}")
+        self.ft4_passes = int(self.ft4_passes)
+        self.ft4_sub_osd_max_hd = extension_knobs.pop("ft4_sub_osd_max_hd", None)
         self._ft4_freq_range = None if search_freq_range is _FREQ_RANGE_DEFAULT else tuple(search_freq_range)
         self._ft4_time_range = None if search_time_range is _TIME_RANGE_DEFAULT else tuple(search_time_range)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
@@ -1242,8 +1249,10 @@ class Receiver:
         """FT4 (extension): audio_i16 [B, 90000] int16, 7.5-s frames at 12 kHz -> per frame the list of message
         dicts (the keys of decode_frames, "mode": "FT4"; ft4.message_dicts), and the records / counts if asked.  Honours max_cands,
         search_freq_range, search_time_range (absolute start seconds; FT4's default is -0.5 .. +2.0), msg_types, ft4_sync_min and
-        ft4_osd_max_hd; a fresh call-hash table per frame.  Refused, by name: a-priori calls, recall, weak, reports, the packed output,
-        passes > 1 and float frames."""
+        ft4_osd_max_hd; a fresh call-hash table per frame (and per pass).  The receiver's ft4_passes = 2 or 3 (section 19.6): the decoded
+        signals are subtracted on the device and the residual is decoded again; the later passes' messages follow pass 1's, "_SUB" in
+        their decode_notes, and the records returned are the last pass's.  Refused, by name: a-priori calls, recall, weak, reports,
+        the packed output, the per-call passes > 1 and float frames."""
         if (self.float_frames if float_frames is None else bool(float_frames)):
             raise _lib.Ft8rxError("FT4 decoding (decode_frames_ft4) is not supported together with float_frames=True: FT4 frames are int16")
         if int(passes) > 1:
@@ -1258,7 +1267,8 @@ class Receiver:
         with self._hlock:
             h = self._handle(B)
             # the OSD gate: the one given, else the library's default -- with msg_types set, the lower gate of the same noise sweep
-            h.ft4_set(self.ft4_sync_min, self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES)
+            gate = self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES
+            h.ft4_set(self.ft4_sync_min, gate)
             f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
             h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
             if f0 == (0, 0) and h0 != (0, 0):
@@ -1268,9 +1278,58 @@ class Receiver:
             h.ft4_set_range(f0[0], f0[1], h0[0], h0[1])
             res = h.ft4_decode(audio)
             msgs, mcnt = self._package(res)
-        cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
+            cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
+            if self.ft4_passes > 1:                                  # the later passes need the handle: the dicts are made under its lock
+                out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
+                res = self._later_passes_ft4(h, B, res, msgs, mcnt, out, cs, gate)
+                return (out, res[0], res[1]) if return_records else out
         out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
         return (out, res[0], res[1]) if return_records else out
+
+    @staticmethod
+    def _ft4_words(rec, msgs, mcnt, f):
+        """the 77-bit words of frame f's packaged messages, row by row (the word of the candidate a row names)"""
+        r = rec[f][msgs[f]["cand"][:int(mcnt[f])]]
+        return [(int(hi) << 64) | int(lo) for lo, hi in zip(r["msg_lo"], r["msg_hi"])]
+
+    def _later_passes_ft4(self, h, B, res, msgs, mcnt, out, cs, gate):
+        """Passes 2 .. ft4_passes of a batch whose frames pass 1 left in the handle's FT4 buffer: subtract the
+        words that are new since the pass before (each once, in emit order, the start refined), decode the rounded residual with the
+        unchanged chain, append the messages whose word the frame does not have yet ("_SUB" in decode_notes); stops when a pass brought
+        nothing to subtract in any frame.  out: the per-frame dict lists, appended in place -> the results of the last pass run."""
+        have = [set(self._ft4_words(res[0], msgs, mcnt, f)) for f in range(B)]         # the words the frame's messages carry
+        gone = [set() for _ in range(B)]                                               # the words already subtracted
+        staging = h.ft4_staging_ptr()
+        if self.ft4_sub_osd_max_hd is not None:
+            h.ft4_set(self.ft4_sync_min, self.ft4_sub_osd_max_hd)
+        try:
+            for _ in range(1, self.ft4_passes):
+                rec, cnt = res[0], res[1]
+                sigs = _lib.ft4_subtraction_list(rec, cnt, gone)
+                if not sigs[1].any():
+                    break
+                for f in range(B):
+                    r = rec[f][:int(cnt[f])]
+                    r = r[r["status"] == _lib.ST_DECODED]
+                    gone[f].update((int(hi) << 64) | int(lo) for lo, hi in zip(r["msg_lo"], r["msg_hi"]))
+                h.ft4_subtract(staging, B, sigs, refine=1)
+                h.ft4_enqueue(staging, B)
+                res = h.fetch(B)
+                msgs, mcnt = self._package(res)
+                for f in range(B):
+                    words = self._ft4_words(res[0], msgs, mcnt, f)
+                    for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band), words):
+                        if w in have[f]:
+                            continue
+                        have[f].add(w)
+                        d["decode_notes"] += "_SUB"
+                        out[f].append(d)
+                        if self.on_message is not None:
+                            self.on_message(d)
+        finally:
+            if self.ft4_sub_osd_max_hd is not None:
+                h.ft4_set(self.ft4_sync_min, gate)
+        return res
 
     def decode_frame_ft4(self, audio_i16, cyclestart_string="700101_000000"):
         return self.decode_frames_ft4(np.asarray(audio_i16)[None], [cyclestart_string])[0]

@@ -1,12 +1,15 @@
 """FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
 
-    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N]
+    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes]
 
 --prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
               apart, starts 0.1 .. 1.5 s), through Handle.ft4_decode and the native message layer; the 50 % point by interpolation
 --noise       false decodes on 2048 noise-only frames for a sweep of the OSD distance gate (ft4_osd_max_hd), at msg_types 0 and all
 --throughput  frames/s at B = 256 with 20 signals per frame (-14 .. +5 dB): 3 warm-up and 20 timed calls of ft4_decode (host frames, the
               copy included) and of ft4_enqueue + fetch (device-resident frames), the stage times (ft8rx_set_profiling)
+--passes      subtraction passes (section 19.6) on 256 crowded frames (16 signals in 300 .. 1200 Hz, -12 .. +10 dB, make_frame indices 1000 ..
+              1255): true and false decodes per frame for ft4_passes 1 / 2 / 3 at msg_types 0 (gate 40) and all (gate 24), the later
+              passes' own gate (ft4_sub_osd_max_hd) swept, the times of one subtraction sweep and of a whole two-pass batch at B = 256
 --twin N      no GPU: the yardstick, the float64 twin with the numpy BP on N signals per step of -18 .. -11 dB (the same recipe)
 Results are merged into the file's existing sections."""
 import argparse
@@ -141,11 +144,67 @@ def measure_throughput(h, B=256, warmup=3, steps=20):
     return out
 
 
+CROWDED_KW = dict(n_signals=16, snr_range=(-12, 10), freq_range=(300, 1200), t0_range=(0.2, 1.2), min_sep_hz=25)
+SUB_GATES = [None, 32, 24, 16]
+
+
+def measure_passes(B=256, first=1000):
+    import torch
+    from pyft8_amd import _lib
+    from pyft8_amd.receiver import Receiver
+    frames = [ft4.make_frame(first + k, return_truth=True, **CROWDED_KW) for k in range(B)]
+    audio = np.stack([f[0] for f in frames])
+    planted = [{t["msg"] for t in f[1]} for f in frames]
+    out = {"frames": B, "first_index": first, "recipe": {k: list(v) if isinstance(v, tuple) else v for k, v in CROWDED_KW.items()}, "signals": 16 * B, "yield": {}}
+    for name, kw in (("msg_types_0", {}), ("msg_types_all", {"msg_types": "all"})):
+        for gate in SUB_GATES:
+            for p in (1, 2, 3):
+                if p == 1 and gate is not None:
+                    continue
+                r = Receiver("", None, max_frames=B, ft4_passes=p, ft4_sub_osd_max_hd=gate, **kw)
+                t0 = time.perf_counter()
+                res = r.decode_frames_ft4(audio)
+                dt = time.perf_counter() - t0
+                r.close()
+                texts = [[" ".join(x for x in d["msg_tuple"] if x) for d in fr] for fr in res]
+                true = sum(t in planted[f] for f in range(B) for t in texts[f])
+                false = [(f, t, d["decode_notes"]) for f in range(B) for t, d in zip(texts[f], res[f]) if t not in planted[f]]
+                sub = [d for fr in res for d in fr if "_SUB" in d["decode_notes"]]
+                key = f"passes_{p}" + ("" if gate is None else f"_sub_gate_{gate}")
+                out["yield"].setdefault(name, {})[key] = {
+                    "true_per_frame": true / B, "false_per_frame": len(false) / B, "true": true, "false": len(false),
+                    "false_in_later_passes": sum("_SUB" in n for _, _, n in false), "later_pass_decodes": len(sub),
+                    "later_pass_osd": sum("OSD" in d["decode_notes"] for d in sub), "false_texts": [f"frame {first + f}: {t} ({n})" for f, t, n in false][:12],
+                    "first_call_seconds": round(dt, 3)}
+                print(name, key, out["yield"][name][key], flush=True)
+    # times at B = 256: pass 1, the list, one sweep (synchronous call, a fresh device copy each time), the second pass; then whole batches
+    h = _lib.Handle(max_frames=B)
+    res = h.ft4_decode(audio)
+    sigs = _lib.ft4_subtraction_list(res[0], res[1])
+    t = {"sweep_ms": [], "signals_in_sweep": int(sigs[1].sum()), "longest_list": int(sigs[1].max())}
+    for _ in range(6):
+        d = torch.from_numpy(audio).to("cuda:0"); torch.cuda.synchronize()
+        t0 = time.perf_counter(); h.ft4_subtract(d.data_ptr(), B, sigs, refine=1); t["sweep_ms"].append(round(1e3 * (time.perf_counter() - t0), 3))
+    t0 = time.perf_counter(); h.ft4_subtract(d.data_ptr(), B, sigs, refine=0); t["sweep_refine0_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+    h.close()
+    for p in (1, 2, 3):
+        r = Receiver("", None, max_frames=B, ft4_passes=p)
+        r.decode_frames_ft4(audio)
+        tt = []
+        for _ in range(5):
+            t0 = time.perf_counter(); r.decode_frames_ft4(audio); tt.append(round(1e3 * (time.perf_counter() - t0), 3))
+        r.close()
+        t[f"receiver_passes_{p}_ms"] = tt
+    out["times"] = t
+    print("times", t, flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ft4_measure.json"))
     ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
-    ap.add_argument("--twin", type=int, default=0)
+    ap.add_argument("--twin", type=int, default=0); ap.add_argument("--passes", action="store_true")
     ap.add_argument("--noise-frames", type=int, default=2048)
     args = ap.parse_args()
     res = json.load(open(args.out)) if os.path.exists(args.out) else {}
@@ -162,6 +221,9 @@ if __name__ == "__main__":
         if args.noise:
             res["noise"] = measure_noise(h, args.noise_frames)
         h.close()
+    if args.passes:
+        import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
+        res["passes"] = measure_passes()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     json.dump(res, open(args.out, "w"), indent=1)
     print("wrote", args.out)
