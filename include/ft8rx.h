@@ -45,6 +45,7 @@
  *     ft8rx_ddc  ft8rx_ddc_host  ft8rx_ddc_taps                                        (down-converter: real / IQ input at 24 .. 192 kHz -> 12 kHz frames)
  *     ft8rx_ddc_stream_open  ft8rx_ddc_stream_push  ft8rx_ddc_stream_frame  ft8rx_ddc_stream_info  ft8rx_ddc_stream_read
  *     ft8rx_ddc_stream_close                                                           (the same on a continuous stream, state on the device)
+ *     ft8rx_ddc_stream_frames                                                          (opt-in: 15-s or 7.5-s frames of chosen channels, live FT4)
  *     ft8rx_ddc_stream_grid_open  ft8rx_ddc_stream_grid_info  ft8rx_ddc_stream_grid_read  (opt-in spectrogram rows of every channel behind it)
  *     ft8rx_ddc_wide  ft8rx_ddc_wide_host  ft8rx_ddc_wide_taps  ft8rx_ddc_wide_plan     (pre-decimator: ONE stream at 240 kHz .. 129.6 MHz, 8- or
  *     ft8rx_ddc_wide_stream_open  ft8rx_ddc_wide_stream_push  ft8rx_ddc_wide_stream_read_mid   16-bit, in front of the down-converter)
@@ -509,6 +510,19 @@ int  ft8rx_ddc_stream_push(ft8rx_handle* h, const void* in, uint64_t n_new, int 
 #define FT8RX_DDC_KEEP_F32_FRAMES 2
 int  ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16_t* d_audio);
 int  ft8rx_ddc_stream_frame_f32(ft8rx_handle* h, uint64_t m_first, int n_have, float* d_audio);
+/* frames  (extension, opt-in; DESIGN.md section 19.7: live FT4, and the FT8 channels of a receiver that has both) frames of either length
+ *        for chosen channels: frame i position p = output m_first + p of channel channels[i], for p < n_have; zero from n_have on,
+ *        before the origin and from m_produced on -- the rules of frame.  frame_len: FT8RX_NSAMP (180000) or FT8RX_FT4_NSAMP (90000),
+ *        anything else is refused by name; 0 <= n_have <= frame_len; 1 <= n_sel <= max_frames; every channels[i] in [0, n_out),
+ *        repeats allowed; channels NULL = channels 0 .. n_sel - 1.  d_audio: device [n_sel][frame_len] int16; NULL = with frame_len
+ *        90000 the handle's FT4 frame buffer (ft8rx_ft4_staging_audio; FT4's workspaces are allocated here if this is the handle's first
+ *        FT4 call, all or nothing), with 180000 the staging audio.  ft8rx_ft4_enqueue_batch(h, ft8rx_ft4_staging_audio(h), n_sel), or
+ *        ft8rx_enqueue_batch(h, ft8rx_staging_audio(h), n_sel), is the intended next call.  Refused with -1 when part of the range has
+ *        left the ring.  Waits for the batches in flight.  The channel list lives in a table of the stream's (max_frames int32,
+ *        allocated at the stream's first call here, released by close): it is uploaded, with one wait for the main stream, only when a
+ *        call's list differs from the call before; nothing else is allocated or copied per call.  Serves the wide and the rational
+ *        stream alike (their frames come from the same ring). */
+int  ft8rx_ddc_stream_frames(ft8rx_handle* h, uint64_t m_first, int n_have, int frame_len, const int32_t* channels, int n_sel, int16_t* d_audio);
 int  ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first, int n, int16_t* y_i16, float* y_f32);
 int  ft8rx_ddc_stream_info(ft8rx_handle* h, uint64_t* in_capacity, uint64_t* out_capacity, uint64_t* n_pushed, uint64_t* m_produced);
 int  ft8rx_ddc_stream_close(ft8rx_handle* h);

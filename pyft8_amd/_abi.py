@@ -84,6 +84,7 @@ PROTOTYPES = {
     "ft8rx_ddc_stream_open": (INT, (PTR, INT, I32, INT, INT, PTR, PTR, F32, U64, INT, PTR)),
     "ft8rx_ddc_stream_push": (INT, (PTR, PTR, U64, INT, PTR)),
     "ft8rx_ddc_stream_frame": (INT, (PTR, U64, INT, PTR)),
+    "ft8rx_ddc_stream_frames": (INT, (PTR, U64, INT, INT, PTR, INT, PTR)),
     "ft8rx_ddc_stream_read": (INT, (PTR, U64, INT, PTR, PTR)),
     "ft8rx_ddc_stream_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
     "ft8rx_ddc_stream_close": (INT, (PTR,)),

@@ -1033,6 +1033,18 @@ class Handle:
         """Gather outputs [m_first, m_first + n_have) of every channel into the frames of the staging buffer (or d_audio_ptr)."""
         self._chk(self._L.ft8rx_ddc_stream_frame(self._h, int(m_first) & 0xFFFFFFFFFFFFFFFF, int(n_have), d_audio_ptr), "ft8rx_ddc_stream_frame")
 
+    def ddc_stream_frames(self, m_first, n_have, frame_len, channels=None, n_sel=None, d_audio_ptr=None):
+        """ft8rx_ddc_stream_frames: outputs [m_first, m_first + n_have) of the channels `channels` (None = channels
+        0 .. n_sel - 1, n_sel None = every channel of the stream) as frames of frame_len = NSAMP or FT4_NSAMP samples, into d_audio_ptr --
+        None = the FT4 frame buffer (ft4_staging_ptr) for frame_len 90000, the staging buffer (staging_ptr) for 180000."""
+        if channels is None:
+            ch, n = None, (self._ds[2] if self._ds is not None else 0) if n_sel is None else int(n_sel)
+        else:
+            ch = np.ascontiguousarray(channels, np.int32).reshape(-1)
+            n = len(ch)
+        self._chk(self._L.ft8rx_ddc_stream_frames(self._h, int(m_first) & 0xFFFFFFFFFFFFFFFF, int(n_have), int(frame_len),
+                                                  None if ch is None else ch.ctypes.data, n, d_audio_ptr), "ft8rx_ddc_stream_frames")
+
     def ddc_stream_read(self, m_first, n, want_float=False):
         """Test aid: outputs [m_first, m_first + n) of every channel out of the ring -> int16 [n_out, n] (, float32 [n_out, n])."""
         if self._ds is None:

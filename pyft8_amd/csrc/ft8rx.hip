@@ -76,6 +76,7 @@
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
 #include "ddc_ring.hpp"
+#include "ddc_frames.hpp"
 #include "ddc_grid_ring.hpp"
 #include "ddc_wide_ring.hpp"
 #include "ddc_rat_ring.hpp"
@@ -246,6 +247,9 @@ struct ft8rx_handle {
         void* d_in = nullptr; int16_t* d_out = nullptr; float* d_f32 = nullptr; DdcOut* d_outs = nullptr; char* h_stage = nullptr;
         float* d_grid = nullptr; int g_p0 = 0, g_rows = 0;
         bool f32_frames = false;         // opened with keep_f32 = FT8RX_DDC_KEEP_F32_FRAMES: the grid stage reads d_f32
+        // ft8rx_ddc_stream_frames (section 19.7; nothing of it exists until the stream's first such call): d_sel [max_frames], the
+        // channel of each frame of the last call's list, and that list on the host -- uploaded only when a call's list differs
+        int32_t* d_sel = nullptr; std::vector<int32_t> sel;
         hipEvent_t ev = nullptr;
     } ds;
     // input pre-stages (ft8rx_ddc_wide*, ft8rx_ddc_rat*; kernels/ddc_wide.hpp, kernels/ddc_rat.hpp).  One-shot: the
@@ -342,6 +346,7 @@ static_assert(sizeof(ft8rx_handle::ev_chunk) / sizeof(hipEvent_t) == batchplan::
 
 // the streaming down-converter's index arithmetic (ddc_ring.hpp, host only) against the kernels' geometry
 static_assert(ddcring::TILE == DDC_TO && ddcring::OUT_RING == 2 * FT8RX_NSAMP, "ddc_ring.hpp: tile and output ring");
+static_assert(ddcframes::FT8_LEN == FT8RX_NSAMP && ddcframes::FT4_LEN == FT8RX_FT4_NSAMP, "ddc_frames.hpp: the two frame lengths");
 template <int D> constexpr bool ddc_ring_geom_ok() {
     using G = DdcGeom<D>;
     return ddcring::geom(D).R1 == G::R1 && ddcring::geom(D).C1 == G::C1 && ddcring::geom(D).R2 == G::R2 && ddcring::geom(D).C2 == G::C2 &&
@@ -1639,7 +1644,7 @@ int ft8rx_ddc_host(ft8rx_handle* h, const void* in, int kind, int32_t rate_hz, i
 static void ddc_stream_release(ft8rx_handle* h) {
     ft8rx_handle::DdcStream& s = h->ds;
     release_dev(h, s.d_in); release_dev(h, s.d_out); release_dev(h, s.d_f32); release_dev(h, s.d_outs); release_host(h, s.h_stage);
-    release_dev(h, s.d_grid);
+    release_dev(h, s.d_grid); release_dev(h, s.d_sel);
     const hipEvent_t ev = s.ev;
     s = ft8rx_handle::DdcStream();
     s.ev = ev;
@@ -1792,6 +1797,51 @@ int ft8rx_ddc_stream_frame(ft8rx_handle* h, uint64_t m_first, int n_have, int16_
 }
 int ft8rx_ddc_stream_frame_f32(ft8rx_handle* h, uint64_t m_first, int n_have, float* d_audio) {
     return ddc_stream_frame(h, "ft8rx_ddc_stream_frame_f32", m_first, n_have, d_audio, true);
+}
+
+// Frames of either length for chosen channels: the argument checks are ddc_frames.hpp's, what the ring holds
+// ddc_ring.hpp's, as in the entries above.  The channel table is the stream's: allocated at the stream's first call here (max_frames
+// entries: the longest list a call may give), uploaded when the list differs from the last call's, released with the stream.
+static int ft4_workspaces(ft8rx_handle* h);
+int ft8rx_ddc_stream_frames(ft8rx_handle* h, uint64_t m_first_u, int n_have, int frame_len, const int32_t* channels, int n_sel, int16_t* d_audio) {
+    static const char* who = "ft8rx_ddc_stream_frames";
+    if (!h) return -1;
+    ft8rx_handle::DdcStream& s = h->ds;
+    if (!s.open) { set_err(h, "%s: no stream is open (ft8rx_ddc_stream_open)", who); return -1; }
+    const ddcframes::Verdict v = ddcframes::check(frame_len, n_have, channels, n_sel, s.n_out, h->max_frames);
+    if (v.bad) {
+        char msg[256];
+        ddcframes::describe(msg, sizeof msg, who, v, frame_len, n_have, channels, n_sel, s.n_out, h->max_frames);
+        set_err(h, "%s", msg);
+        return -1;
+    }
+    const int64_t m_first = (int64_t)m_first_u;          // two's complement: a negative index lies before index 0
+    if (m_first < -((int64_t)1 << 62) || m_first > ((int64_t)1 << 62)) { set_err(h, "%s: m_first out of range", who); return -1; }
+    const int64_t m_origin = s.n_origin / s.D, m_done = s.tiles * DDC_TO;
+    if (!ddcring::held(m_first, n_have, m_origin, m_done).ok) {
+        set_err(h, "%s: outputs from %lld on have left the ring (it holds %lld .. %lld)", who, (long long)(m_first > m_origin ? m_first : m_origin),
+                (long long)(m_done - ddcring::OUT_RING), (long long)m_done);
+        return -1;
+    }
+    ENTER(h);                                            // a batch in flight may still read the frames' buffer
+    if (!d_audio) {
+        if (frame_len == FT8RX_FT4_NSAMP) { if (const int rc = ft4_workspaces(h)) return rc; d_audio = h->ft4.d_audio; }
+        else { if (need_staging(h)) return -2; d_audio = h->d_audio; }
+    }
+    if (!s.d_sel && dalloc(h, &s.d_sel, (size_t)h->max_frames)) return -2;
+    if (ddcframes::differs(s.sel.data(), (int)s.sel.size(), channels, n_sel)) {
+        s.sel.resize((size_t)n_sel);
+        for (int i = 0; i < n_sel; i++) s.sel[i] = channels ? channels[i] : i;
+        // after the gathers that still read the old table, and complete before this call returns: the list is a pageable vector
+        const hipError_t e = hipMemcpyAsync(s.d_sel, s.sel.data(), sizeof(int32_t) * (size_t)n_sel, hipMemcpyHostToDevice, h->stream);
+        const hipError_t e2 = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess || e2 != hipSuccess) { s.sel.clear(); set_err(h, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : e2)); return -2; }
+    }
+    const dim3 g((unsigned)(frame_len + 255) / 256, (unsigned)n_sel);
+    k_ddc_gather_sel<<<g, 256, 0, h->stream>>>(s.d_out, (int)ddcring::OUT_RING, s.d_sel, s.n_out, (long long)m_first, n_have, (long long)m_origin,
+                                               (long long)m_done, frame_len, d_audio);
+    HIPCHK(h, hipGetLastError());
+    return 0;
 }
 
 int ft8rx_ddc_stream_read(ft8rx_handle* h, uint64_t m_first_u, int n, int16_t* y_i16, float* y_f32) {

@@ -225,3 +225,17 @@ __global__ __launch_bounds__(256) void k_ddc_gather_f32(const float* __restrict_
                                                         long long m_origin, long long m_done, float* __restrict__ audio) {
     ddc_gather(ring, ring_len, m_first, n_have, m_origin, m_done, audio);
 }
+// ft8rx_ddc_stream_frames: frame i position p = output m_first + p of channel sel[i], for frames of frame_len
+// samples (a 15-s or a 7.5-s frame), the zero rules of k_ddc_gather.  sel: the stream's table of the call's channel list, checked on
+// the host (ddc_frames.hpp); an entry outside [0, n_out) reads nothing, so no load leaves a ring row
+__global__ __launch_bounds__(256) void k_ddc_gather_sel(const int16_t* __restrict__ ring, int ring_len, const int32_t* __restrict__ sel, int n_out,
+                                                        long long m_first, int n_have, long long m_origin, long long m_done, int frame_len,
+                                                        int16_t* __restrict__ audio) {
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (p >= frame_len) return;
+    const int j = sel[i];
+    const long long m = m_first + p;
+    int16_t v = 0;
+    if (p < n_have && m >= m_origin && m < m_done && (unsigned)j < (unsigned)n_out) v = ring[(size_t)j * ring_len + (size_t)(m % ring_len)];
+    audio[(size_t)i * frame_len + p] = v;
+}

@@ -284,6 +284,14 @@ def demod(x, f0, h0):
     return dict(tt=tt, ft=ft, metric=float(m.flat[k]), metrics=m, llr=llr_from_amplitudes(A), snr=snr_from_amplitudes(A), amps=A)
 
 
+def early_ok(h0_idx, ttweak, n_have):
+    """The early-pass rule of live FT4: a decode of a slot of which only the first n_have samples exist is
+    delivered iff its whole signal -- start 144 h0 + 36 tt (it may be negative), 105 symbols of 576 samples -- with the fine sync's
+    reach of +-4 steps of 36 samples lies inside them.  The fine sync and the demodulator read the signal's own samples only, so such
+    a candidate sees the audio it sees in the complete slot."""
+    return HOP * int(h0_idx) + DT_STEP * int(ttweak) + NSYM * NSPS + DT_STEP * (N_DT // 2) <= int(n_have)
+
+
 # ----------------------------------------------------------------------------- message dicts of the GPU path (Receiver.decode_frames_ft4)
 def slot_parity(cyclestart_string):
     """'YYMMDD_HHMMSS' (the seconds may carry a fraction: '..._000007.5') -> 0 / 1, the parity of the 7.5-s slot that starts then."""

@@ -656,7 +656,7 @@ class Receiver:
                  search_freq_range=_FREQ_RANGE_DEFAULT, search_time_range=_TIME_RANGE_DEFAULT, verbose=False,
                  device=0, max_frames=1, time_source=None, sleep=None, audio_source=None, autostart=None, early_decode_hop=(320, 340),
                  sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False, waterfall=False,
-                 **extension_knobs):
+                 modes=None, **extension_knobs):
         if search_freq_range[1] > 5900 or search_freq_range[0] < 12.5 or search_freq_range[0] >= search_freq_range[1]:
             # the reference sizes its grid from search_freq_range (receiver.py:234-240) and itself fails beyond ~5940 Hz, where the
             # fine-sync slice runs off the cycle spectrum (receiver.py:181-182).  Here the layouts are compile-time: up to 3000 Hz runs
@@ -739,6 +739,9 @@ class Receiver:
             raise _lib.Ft8rxError(f"ft4_passes must be 1, 2 or 3, got {self.ft4_passes!r}")
         self.ft4_passes = int(self.ft4_passes)
         self.ft4_sub_osd_max_hd = extension_knobs.pop("ft4_sub_osd_max_hd", None)
+        # live FT4 (section 19.7; modes= here or in start()): the early passes of a 7.5-s slot, seconds into it -- one at 6.0 s (72000
+        # samples) by default, () = only the complete slot
+        self.ft4_early_samples = _wide_in.ft4_early_samples(extension_knobs.pop("ft4_early_decode_s", _wide_in.FT4_EARLY_S_DEFAULT))
         self._ft4_freq_range = None if search_freq_range is _FREQ_RANGE_DEFAULT else tuple(search_freq_range)
         self._ft4_time_range = None if search_time_range is _TIME_RANGE_DEFAULT else tuple(search_time_range)
         self.cfg = config_from_kwargs(sync_score_min, max_cands, search_freq_range, search_time_range, **extension_knobs)
@@ -760,7 +763,7 @@ class Receiver:
         # may also be called directly).  audio_in stays the 12 kHz object; with waterfall=True the channels have a search grid and a
         # waterfall of their own (wide_in.search_grid[j] / .waterfall_data[j], search(channel=j)).
         self.wide_in = None
-        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall, modes)
         # The reference starts its audio thread and manage_cycle in the constructor (receiver.py:252, 336).  Same here when there
         # is something to listen to: an explicit audio_source, or PortAudio (PyAudio importable and a device matches the keywords).
         if autostart is None:
@@ -768,12 +771,30 @@ class Receiver:
         if autostart:
             self.start(audio_source)
 
-    def _set_wide_in(self, sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall=False):
-        """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is"""
-        if sample_rate is not None:
-            self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
-                                           waterfall=waterfall, input_blanker=self.input_blanker, float_frames=self.float_frames,
-                                           **({"panorama": self.panorama_opt} if self.panorama_opt else {}))
+    def _set_wide_in(self, sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall=False, modes=None):
+        """The wide live input of the constructor's and start()'s arguments; sample_rate None leaves what there is.  modes (DESIGN.md
+        section 19.7): per-channel "FT8" / "FT4"; with an FT4 channel the opt-ins FT4 does not run with are refused here, before a stream
+        opens"""
+        if sample_rate is None:
+            if modes is not None:
+                raise _lib.Ft8rxError("modes: per-channel modes belong to the wide live input (sample_rate=, dial_offsets_hz=)")
+            return
+        if _wide_in.channel_modes(modes, len(dial_offsets_hz)) is not None:
+            self._refuse_with_ft4_channels()
+        self.wide_in = _wide_in.WideIn(self, sample_rate, iq=iq, dial_offsets_hz=dial_offsets_hz, bands=bands, t_first=t_first, resample=resample,
+                                       waterfall=waterfall, input_blanker=self.input_blanker, float_frames=self.float_frames,
+                                       **({"panorama": self.panorama_opt} if self.panorama_opt else {}),
+                                       **({"modes": modes} if modes is not None else {}))
+
+    def _refuse_with_ft4_channels(self):
+        """An FT4 channel of the live stream (modes=) and what FT4 does not run with: the rows of the opt-in table (optins.FT4: my_call /
+        dx_call, recall, weak, reports), and the two frame stages FT4 has no form of"""
+        _optins.refuse(_optins.FT4, _optins.active(self.cfg, recall=self.recall))
+        name = _optins.TABLE[_optins.FT4][0]
+        if self.noise_blanker is not None:
+            raise _lib.Ft8rxError(f"{name} is not supported together with noise_blanker: it blanks 15-s frames")
+        if self.float_frames:
+            raise _lib.Ft8rxError(f"{name} is not supported together with float_frames=True: FT4 frames are int16")
 
     @property
     def panorama(self):
@@ -789,7 +810,7 @@ class Receiver:
 
     # ---- the manage_cycle stand-in (reference receiver.py:336, 372-412)
     def start(self, audio_source=None, sample_rate=None, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, resample=False,
-              waterfall=False):
+              waterfall=False, modes=None):
         """Open the audio source (AudioIn.open) and start the daemon that decodes completed cycles: every 0.1 s (the reference's
         poll period, receiver.py:383) it calls poll(); on_message runs on that thread, as in the reference.  Unlike the
         reference, whose daemon dies on the first exception, an exception is kept in .thread_error and the loop ends.
@@ -797,12 +818,12 @@ class Receiver:
         with iq=True, the forms of decode_stream -- feeding the channels dial_offsets_hz (wide_in.WideIn.open); t_first = the time of
         its first sample (default: time_source() at the first chunk).  resample=True: a rate that is no multiple of 12 kHz goes through
         the rational resampler (wide_in.WideIn).  waterfall=True: the channels' search grids and waterfalls are
-        kept (wide_in.WideIn, section 16.5)."""
+        kept (wide_in.WideIn, section 16.5).  modes: "FT8" / "FT4" for every channel or one per channel (section 19.7)."""
         if self._thread is not None and self._thread.is_alive():
             return self
         self._stop.clear()
         self.thread_error = None
-        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall)
+        self._set_wide_in(sample_rate, iq, dial_offsets_hz, bands, t_first, resample, waterfall, modes)
         if self.wide_in is not None:
             if audio_source is not None:
                 self.wide_in.open(audio_source)
@@ -898,6 +919,8 @@ class Receiver:
             raise _lib.Ft8rxError(f"search(channel={channel}): the receiver keeps no grid of its channels (Receiver(..., sample_rate=, waterfall=True))")
         if not isinstance(channel, (int, np.integer)) or not 0 <= channel < w.n_channels:
             raise _lib.Ft8rxError(f"search(channel={channel}): the wide input has channels 0 .. {w.n_channels - 1}")
+        if w.modes is not None and w.modes[channel] == _wide_in.FT4:
+            raise _lib.Ft8rxError(f"search(channel={channel}): channel {channel} is an FT4 channel -- search() is FT8's Costas search")
         return w.search_grid[channel], (w.bands[channel] if w.bands is not None else self.band)
 
     def search(self, cyclestart_string, odd_even, search_f_idxs=None, channel=None):
@@ -1266,16 +1289,7 @@ class Receiver:
         B = len(audio)
         with self._hlock:
             h = self._handle(B)
-            # the OSD gate: the one given, else the library's default -- with msg_types set, the lower gate of the same noise sweep
-            gate = self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES
-            h.ft4_set(self.ft4_sync_min, gate)
-            f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
-            h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
-            if f0 == (0, 0) and h0 != (0, 0):
-                f0 = _ft4.freq_range_to_f0()
-            if h0 == (0, 0) and f0 != (0, 0):
-                h0 = _ft4.time_range_to_h0()
-            h.ft4_set_range(f0[0], f0[1], h0[0], h0[1])
+            gate = self._ft4_set(h)
             res = h.ft4_decode(audio)
             msgs, mcnt = self._package(res)
             cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
@@ -1286,17 +1300,33 @@ class Receiver:
         out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
         return (out, res[0], res[1]) if return_records else out
 
+    def _ft4_set(self, h):
+        """The receiver's FT4 knobs and search range on handle h (the caller holds its lock) -> the OSD gate in force"""
+        # the OSD gate: the one given, else the library's default -- with msg_types set, the lower gate of the same noise sweep
+        gate = self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES
+        h.ft4_set(self.ft4_sync_min, gate)
+        f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
+        h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
+        if f0 == (0, 0) and h0 != (0, 0):
+            f0 = _ft4.freq_range_to_f0()
+        if h0 == (0, 0) and f0 != (0, 0):
+            h0 = _ft4.time_range_to_h0()
+        h.ft4_set_range(f0[0], f0[1], h0[0], h0[1])
+        return gate
+
     @staticmethod
     def _ft4_words(rec, msgs, mcnt, f):
         """the 77-bit words of frame f's packaged messages, row by row (the word of the candidate a row names)"""
         r = rec[f][msgs[f]["cand"][:int(mcnt[f])]]
         return [(int(hi) << 64) | int(lo) for lo, hi in zip(r["msg_lo"], r["msg_hi"])]
 
-    def _later_passes_ft4(self, h, B, res, msgs, mcnt, out, cs, gate):
+    def _later_passes_ft4(self, h, B, res, msgs, mcnt, out, cs, gate, bands=None, notify=True, **pkg_kw):
         """Passes 2 .. ft4_passes of a batch whose frames pass 1 left in the handle's FT4 buffer: subtract the
         words that are new since the pass before (each once, in emit order, the start refined), decode the rounded residual with the
         unchanged chain, append the messages whose word the frame does not have yet ("_SUB" in decode_notes); stops when a pass brought
-        nothing to subtract in any frame.  out: the per-frame dict lists, appended in place -> the results of the last pass run."""
+        nothing to subtract in any frame.  out: the per-frame dict lists, appended in place -> the results of the last pass run.
+        The live pass (section 19.7): bands = one per frame, notify = False (on_message is its duplicate filter's business), pkg_kw =
+        the persistent call-hash table."""
         have = [set(self._ft4_words(res[0], msgs, mcnt, f)) for f in range(B)]         # the words the frame's messages carry
         gone = [set() for _ in range(B)]                                               # the words already subtracted
         staging = h.ft4_staging_ptr()
@@ -1315,16 +1345,16 @@ class Receiver:
                 h.ft4_subtract(staging, B, sigs, refine=1)
                 h.ft4_enqueue(staging, B)
                 res = h.fetch(B)
-                msgs, mcnt = self._package(res)
+                msgs, mcnt = self._package(res, **pkg_kw)
                 for f in range(B):
                     words = self._ft4_words(res[0], msgs, mcnt, f)
-                    for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band), words):
+                    for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band if bands is None else bands[f]), words):
                         if w in have[f]:
                             continue
                         have[f].add(w)
                         d["decode_notes"] += "_SUB"
                         out[f].append(d)
-                        if self.on_message is not None:
+                        if notify and self.on_message is not None:
                             self.on_message(d)
         finally:
             if self.ft4_sub_osd_max_hd is not None:
@@ -1388,6 +1418,53 @@ class Receiver:
                     d["channel"] = channels[j]
             self._deliver(msgs[j], dicts, t0, early, seen[j], hist[j], out)
 
+    def _deliver_ft4(self, rows, dicts, c, n_have, j, seen_by_slot, out):
+        """The tail of a live FT4 pass for channel j and slot c: rows = the messages' MESSAGE_DTYPE rows in an early pass (n_have <
+        90000: only what ft4.early_ok admits is delivered), None in the complete one; the per-slot duplicate filter on the text, slots
+        older than four slots pruned"""
+        early = n_have < _lib.FT4_NSAMP
+        seen = seen_by_slot.setdefault(c, set())
+        for k in [k for k in seen_by_slot if k < c - 4]:
+            del seen_by_slot[k]
+        for i, d in enumerate(dicts):
+            if early and not _ft4.early_ok(int(rows[i]["h0_idx"]), int(rows[i]["ttweak"]), n_have):
+                continue
+            text = " ".join(d["msg_tuple"])
+            if text in seen:
+                continue
+            seen.add(text)
+            d["channel"], d["early"], d["their_tx_cycle"] = j, early, c % 2
+            out.append(d)
+            if self.on_message is not None:
+                self.on_message(d)
+
+    def _live_pass_ft4(self, w, c, m_first, n_have, out):
+        """One live pass over the FT4 channels of the wide input for slot c (t = 7.5 c), of which n_have outputs
+        exist: gather their 7.5-s frames into the live handle's FT4 buffer, decode them as one batch, package with the persistent
+        call-hash table (the one the FT8 channels use) and deliver per channel.  The complete slot (n_have = 90000) runs the
+        receiver's ft4_passes; an early pass is always single, and delivers only signals that lie wholly inside n_have."""
+        ch = w.channels[_wide_in.FT4]
+        B, early = len(ch), n_have < _lib.FT4_NSAMP
+        cs = [_time.strftime("%y%m%d_%H%M%S", _time.gmtime(int(np.floor(_wide_in.FT4_T_SLOT * c))))] * B
+        bands = [w.bands[j] if w.bands is not None else self.band for j in ch]
+        pkg = dict(n_threads=1, table=self.call_hashes)
+        dicts = None
+        with self._live_lock:
+            h = self._live_handle(w.n_channels)
+            gate = self._ft4_set(h)
+            h.ddc_stream_frames(m_first, n_have, _lib.FT4_NSAMP, ch)
+            h.ft4_enqueue(h.ft4_staging_ptr(), B)
+            res = h.fetch(B)
+            if not early and self.ft4_passes > 1:                    # the later passes need the handle: packaged under its lock
+                msgs, mcnt = self._package(res, **pkg)
+                dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f]) for f in range(B)]
+                self._later_passes_ft4(h, B, res, msgs, mcnt, dicts, cs, gate, bands=bands, notify=False, **pkg)
+        if dicts is None:                                            # the host message layer runs outside _live_lock
+            msgs, mcnt = self._package(res, **pkg)
+            dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f]) for f in range(B)]
+        for f, j in enumerate(ch):
+            self._deliver_ft4(msgs[f] if early else None, dicts[f], c, n_have, j, w.seen[j], out)
+
     def poll(self):
         """Decode every cycle that audio_in._callback has completed since the last call, then the passes of the wide input that have
         fallen due (wide_in.PassScheduler); messages go to on_message on the caller's thread.  -> list of message dicts.
@@ -1413,7 +1490,16 @@ class Receiver:
             with w._lock:
                 if not w._ready:
                     break
-                c, hop, m_first, n_have = w._ready.pop(0)
+                c, hop, m_first, n_have, *mode = w._ready.pop(0)
+            if mode:                                                 # per-channel modes: the pass of one mode's channels
+                if mode[0] == _wide_in.FT4:
+                    self._live_pass_ft4(w, c, m_first, n_have, out)
+                    continue
+                ch = w.channels[_wide_in.FT8]
+                self._live_pass(T_CYC * c, hop, len(ch), None, lambda h: h.ddc_stream_frames(m_first, n_have, _lib.NSAMP, ch),
+                                [w.bands[j] if w.bands is not None else self.band for j in ch], ch, [w.seen[j] for j in ch],
+                                [w.recall_hist[j] for j in ch], out)
+                continue
             K = w.n_channels
             gather = (lambda h: h.ddc_stream_frame_f32(m_first, n_have)) if w.float_frames else (lambda h: h.ddc_stream_frame(m_first, n_have))
             self._live_pass(T_CYC * c, hop, K, None, gather,

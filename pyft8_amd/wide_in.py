@@ -151,19 +151,22 @@ class PassScheduler:
     """Which decode passes are due, from the sample clock alone.  A pass is (cycle c, hop, m_first, n_have): hop = the hops of the
     cycle received (an early pass; n_have = 480 hop) or 0 (the complete cycle, n_have = 180000); m_first = m_c, the cycle's first
     output, which may be negative by up to 6000 for the first cycle (those outputs are zero).  Passes come in the order they fall
-    due: the early hops of a cycle ascending, then the cycle itself, then the next cycle."""
+    due: the early hops of a cycle ascending, then the cycle itself, then the next cycle.
+    The slot geometry is a parameter (DESIGN.md section 19.7): period_s seconds and n_samp outputs per cycle, hop_len outputs per hop;
+    the defaults are FT8's 15 s, 180000 and 480.  ft4_scheduler() is FT4's: 7.5 s, 90000, early passes given in samples."""
 
-    def __init__(self, t_first, early_hops=()):
+    def __init__(self, t_first, early_hops=(), period_s=T_CYC, n_samp=NSAMP, hop_len=HOP):
         self.t_first = float(t_first)
+        self.period_s, self.n_samp, self.hop_len = period_s, int(n_samp), int(hop_len)
         self.hops = tuple(sorted(int(x) for x in early_hops))
-        c = int(np.floor(self.t_first / T_CYC))
+        c = int(np.floor(self.t_first / period_s))
         while self.cycle_start(c) < -HEAD_MAX:
             c += 1
         self.cycle, self.step = c, 0                    # the next pass: hop self.hops[step], or the complete cycle at step == len(hops)
 
     def cycle_start(self, c):
-        """m_c: the absolute output index at which cycle c (t = 15 c) starts"""
-        return int(round((T_CYC * c - self.t_first) * 12000.0))
+        """m_c: the absolute output index at which cycle c (t = 15 c; period_s c) starts"""
+        return int(round((self.period_s * c - self.t_first) * 12000.0))
 
     def due(self, m_produced):
         """The passes whose outputs all exist now (m_first + n_have <= m_produced), each handed out once"""
@@ -171,13 +174,66 @@ class PassScheduler:
         while True:
             m_c = self.cycle_start(self.cycle)
             hop = self.hops[self.step] if self.step < len(self.hops) else 0
-            n_have = HOP * hop if hop else NSAMP
+            n_have = self.hop_len * hop if hop else self.n_samp
             if m_c + n_have > m_produced:
                 return out
             out.append((self.cycle, hop, m_c, n_have))
             self.step += 1
             if not hop:
                 self.cycle, self.step = self.cycle + 1, 0
+
+
+# ---- per-channel modes (modes=): a channel of the live stream is an FT8 or an FT4 channel
+FT8, FT4 = MODES = ("FT8", "FT4")
+FT4_T_SLOT = 7.5
+FT4_NSAMP = _lib.FT4_NSAMP
+FT4_EARLY_S_DEFAULT = (6.0,)      # one early pass per slot: the nominal end of an FT4 signal is 5.54 s, the early rule admits +0.45 s
+
+
+def ft4_scheduler(t_first, early_samples=()):
+    """FT4's PassScheduler: slot c starts at m_c = round((7.5 c - t_first) 12000), its passes are (c, n, m_c, n) for every n of
+    early_samples (ascending) and then the complete slot (c, 0, m_c, 90000); the first slot is the first whose start lies at most
+    HEAD_MAX outputs before the stream's origin"""
+    return PassScheduler(t_first, early_samples, period_s=FT4_T_SLOT, n_samp=FT4_NSAMP, hop_len=1)
+
+
+def ft4_early_samples(ft4_early_decode_s):
+    """ft4_early_decode_s= of Receiver -> the early passes of an FT4 slot in samples, ascending: seconds into the slot inside (0, 7.5)
+    that are a whole number of 12 kHz samples; () / None = no early pass; anything else is refused by name"""
+    if ft4_early_decode_s is None:
+        return ()
+    vals = ft4_early_decode_s if isinstance(ft4_early_decode_s, (tuple, list)) else (ft4_early_decode_s,)
+    out = set()
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) < FT4_T_SLOT:
+            raise _lib.Ft8rxError(f"ft4_early_decode_s: {v!r} outside (0, 7.5) s (seconds into the slot; () = only the complete slot)")
+        n = float(v) * 12000.0
+        if abs(n - round(n)) > 1e-6:
+            raise _lib.Ft8rxError(f"ft4_early_decode_s: {v!r} s is not a whole number of 12 kHz samples")
+        out.add(int(round(n)))
+    return tuple(sorted(out))
+
+
+def channel_modes(modes, n_channels):
+    """modes= of Receiver / start / WideIn -> None (every channel FT8: the path without the keyword) or a tuple of "FT8" / "FT4", one
+    per channel.  None, one name for every channel, or a sequence with one name per channel; a wrong length or an unknown name is
+    refused by name"""
+    if modes is None:
+        return None
+    names = [modes] * n_channels if isinstance(modes, str) else list(modes)
+    if len(names) != n_channels:
+        raise _lib.Ft8rxError(f"modes: one per channel ({n_channels}), got {len(names)}")
+    for m in names:
+        if m not in MODES:
+            raise _lib.Ft8rxError(f"modes: unknown mode {m!r} (\"FT8\" or \"FT4\")")
+    return None if all(m == FT8 for m in names) else tuple(names)
+
+
+def merge_due(due_by_mode):
+    """The passes several schedulers on one clock hand out at the same moment, {mode: [(c, hop, m_first, n_have), ...]} -> one list of
+    (c, hop, m_first, n_have, mode) in the order they fall due: m_first + n_have ascending, FT8 before FT4 at a tie"""
+    out = [p + (mode,) for mode, due in due_by_mode.items() for p in due]
+    return sorted(out, key=lambda p: (p[2] + p[3], MODES.index(p[4])))
 
 
 # ---- the waterfall / search grid of the channels (waterfall=True; DESIGN.md section 16.5).  The device computes row q of every channel
@@ -249,7 +305,7 @@ class WideIn:
     source_exhausted."""
 
     def __init__(self, receiver, sample_rate, iq=False, dial_offsets_hz=(0.0,), bands=None, t_first=None, src=None, resample=False,
-                 waterfall=False, input_blanker=None, float_frames=False, panorama=None):
+                 waterfall=False, input_blanker=None, float_frames=False, panorama=None, modes=None):
         self._rx = receiver
         # float_frames (DESIGN.md section 18): the stream keeps the float32 output ring (1.44 MB per channel), every pass gathers and
         # decodes float frames, and with waterfall=True the rows come from that ring
@@ -282,6 +338,11 @@ class WideIn:
         if src is not None and len(src) != self.n_channels:
             raise _lib.Ft8rxError(f"src: one stream index per channel ({self.n_channels}), got {len(src)}")
         self.bands = list(bands) if bands is not None else None
+        # modes: None = every channel is an FT8 channel and nothing below differs from a receiver without the
+        # keyword; else one name per channel, the channels of each mode present, one scheduler per mode (scheds, set with the clock)
+        self.modes = channel_modes(modes, self.n_channels)
+        self.channels = None if self.modes is None else {m: [j for j, x in enumerate(self.modes) if x == m] for m in MODES if m in self.modes}
+        self.scheds = None
         self.src = None if src is None else [int(s) for s in src]
         self.t_first = t_first
         self.kind = None
@@ -291,7 +352,7 @@ class WideIn:
         self.n_pushed = 0                        # real samples per stream
         self.m_produced = 0
         self.source_exhausted = False
-        self._ready = []                         # passes that are due and not yet decoded: (cycle, hop, m_first, n_have)
+        self._ready = []                         # passes that are due and not yet decoded: (cycle, hop, m_first, n_have); modes: (..., mode)
         self._lock = _threading.Lock()           # push may run on the feeder thread, poll() on the manage_cycle stand-in
         self._feeder = None
         # per channel: the texts delivered per cycle (duplicate filter) and the complete-frame messages per cycle (recall)
@@ -315,7 +376,13 @@ class WideIn:
         self.src = sources(self.mod, self.src, self.n_streams, self.n_channels)
         if self.t_first is None:
             self.t_first = self._rx.time_source()
-        self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
+        if self.modes is None:
+            self.sched = PassScheduler(self.t_first, self._rx.early_decode_hops)
+        else:                                    # one scheduler per mode present; `sched` is the FT8 geometry (the grid's rows are mode-blind)
+            make = {FT8: lambda: PassScheduler(self.t_first, self._rx.early_decode_hops),
+                    FT4: lambda: ft4_scheduler(self.t_first, self._rx.ft4_early_samples)}
+            self.scheds = {m: make[m]() for m in self.channels}
+            self.sched = self.scheds.get(FT8) or PassScheduler(self.t_first)
         with self._rx._live_lock:
             h = self._rx._live_handle(self.n_channels)
             ib = input_blanker_params(self.input_blanker, self.kind, self.n_streams, self.sample_rate)
@@ -440,7 +507,7 @@ class WideIn:
         return -(-int(n) * 12000 // self.sample_rate)
 
     def _note(self, m_avail):
-        due = self.sched.due(m_avail)
+        due = self.sched.due(m_avail) if self.scheds is None else merge_due({m: s.due(m_avail) for m, s in self.scheds.items()})
         if due:
             with self._lock:
                 self._ready += due
