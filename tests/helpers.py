@@ -5,6 +5,14 @@ import oracle as O
 from pyft8_amd import _lib
 
 
+def bits_equal(a, b):
+    """Bitwise equality of float32 arrays; NaNs must sit at the same positions (their sign/payload bits are
+    not compared: x86 generates 0xFFC00000 for 0/0, gfx950 0x7FC00000)."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
 def records_from_oracle(r, max_cands=200):
     rec = np.zeros(max_cands, _lib.RECORD_DTYPE)
     for i, c in enumerate(r["cands"]):

@@ -10,7 +10,7 @@ import pytest
 
 import oracle as O
 from conftest import GOLDEN_FRAMES, load_golden
-from helpers import check_frame as _check_frame
+from helpers import bits_equal, check_frame as _check_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +27,6 @@ def H():
 def ocfg():
     from pyft8_amd import _lib
     return O.default_config(**_lib.fft_plans())
-
-
-def bits_equal(a, b):
-    """Bitwise equality of float32 arrays; NaNs must sit at the same positions (their sign/payload bits are
-    not compared: x86 generates 0xFFC00000 for 0/0, gfx950 0x7FC00000)."""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
 
 
 def test_native_library_loaded():
