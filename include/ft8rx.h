@@ -53,9 +53,13 @@
  *     ft8rx_ddc_rat  ft8rx_ddc_rat_host  ft8rx_ddc_rat_taps  ft8rx_ddc_rat_plan         (rational resampler: ONE stream at any other rate,
  *     ft8rx_ddc_rat_stream_open  ft8rx_ddc_rat_stream_push  ft8rx_ddc_rat_stream_read_mid      44.1 kHz, 2.048 MS/s, 10 MS/s ..., in front of
  *     ft8rx_ddc_rat_stream_close                                                       the down-converter)
+ *     ft8rx_ft4_decode_batch  ft8rx_ft4_enqueue_batch  ft8rx_ft4_decode_messages  ft8rx_ft4_set  ft8rx_ft4_set_range  ft8rx_ft4_info
+ *     ft8rx_ft4_subtract  ft8rx_ft4_subtraction_list  ft8rx_ft4_sub_info  ft8rx_ft4_staging_audio  ft8rx_ft4_encode_tones   (opt-in FT4, 7.5-s frames)
+ *     ft8rx_ft4_set_coherent  ft8rx_ft4_coh_info                                       (opt-in FT4 coherent LLRs: runs of two and four symbols)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
+ *     ft8rx_ft4_grid  ft8rx_ft4_sync  ft8rx_ft4_demod  ft8rx_ft4_coherent  ft8rx_ft4_ldpc  ft8rx_ft4_osd  ft8rx_ft4_sub_probe
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
  *
  * LIMITS of this build against the reference's open-ended kwargs (pyft8_amd.receiver.config_from_kwargs names the kwarg when one is
@@ -1002,6 +1006,22 @@ int  ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int n_frames, int32_t* f
 /* fine sync and demodulation of n (frame, f0, h0) triples -> tweak [n][2] = (dt / 36, df index), metric [n], llr [n][174], snr [n] */
 int  ft8rx_ft4_demod(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
                      const int32_t* h0_idx, int32_t* tweak, float* metric, float* llr, int32_t* snr);
+/* Coherent LLRs (opt-in; k_ft4_coh; the twin is ft4.coherent_llrs).  on != 0: every FT4 batch enqueued
+ * afterwards runs, on the candidates its BP left undecoded, the complex 105 x 4 amplitudes at the fine sync's winner, a residual-
+ * frequency scan over q = -4 .. 4 x 0.651 Hz on the 16 sync symbols, max-log LLRs over runs of two and of four symbols, and the same BP
+ * (bp_nc0_b, bp_iters_b, the handle's msg_types) on the run-of-2 rows, then on the run-of-4 rows; OSD follows on the single-symbol
+ * LLRs of what is left.  Such a decode is a BP decode (ipass 4, FT8RX_M_LDPC_B, ap 0) whose record carries the run length in nsync
+ * (2 or 4; every other FT4 record leaves nsync 0) and whose event carries slot 1 or 2.  Host state only, never refused; off (the
+ * default): nothing new is launched or allocated, every byte is as before.  The workspaces (2.9 KB per candidate slot) are allocated
+ * at the first FT4 batch that runs with the setting on, all or nothing; ft8rx_ft4_info's figure does not include them. */
+int  ft8rx_ft4_set_coherent(ft8rx_handle* h, int32_t on);
+/* bytes of coherent workspace the handle holds (0 until the first FT4 batch with the setting on) and the setting; either may be NULL */
+int  ft8rx_ft4_coh_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on);
+/* stage entry point (tests): the chain's own launch on n caller-supplied candidates (frame, f0, h0) and fine-sync winners (ttweak in
+ * -4 .. 4, ftweak in -2 .. 2) -> q [n], metrics [n][9], llr2 and llr4 [n][174] */
+int  ft8rx_ft4_coherent(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
+                        const int32_t* h0_idx, const int32_t* ttweak, const int32_t* ftweak, int32_t* q, float* metrics, float* llr2,
+                        float* llr4);
 /* ft8rx_ldpc / ft8rx_osd_ext on raw LLR vectors of FT4 codewords: the returned words are descrambled; mask = FT8RX_MT_* bits */
 int  ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,
                     uint64_t* msg_hi, int32_t* n_its, int32_t* has_out, float* llr_out);

@@ -835,6 +835,31 @@ class Handle:
                                           tw.ctypes.data, met.ctypes.data, llr.ctypes.data, snr.ctypes.data), "ft8rx_ft4_demod")
         return dict(ttweak=tw[:, 0].copy(), ftweak=tw[:, 1].copy(), metric=met, llr=llr, snr=snr)
 
+    def ft4_set_coherent(self, on):
+        """ft8rx_ft4_set_coherent: the coherent step (runs of two and four symbols) of the FT4 batches enqueued
+        afterwards, on or off."""
+        self._chk(self._L.ft8rx_ft4_set_coherent(self._h, 1 if on else 0), "ft8rx_ft4_set_coherent")
+
+    def ft4_coh_info(self):
+        """ft8rx_ft4_coh_info -> dict(workspace_bytes (0 until the first FT4 batch with the setting on), on)."""
+        wb, on = C.c_uint64(), C.c_int32()
+        self._chk(self._L.ft8rx_ft4_coh_info(self._h, C.byref(wb), C.byref(on)), "ft8rx_ft4_coh_info")
+        return dict(workspace_bytes=int(wb.value), on=bool(on.value))
+
+    def ft4_coherent(self, audio, frame, f0, h0, ttweak, ftweak):
+        """ft8rx_ft4_coherent: k_ft4_coh on (frame, f0, h0) triples at the given fine-sync winners -> dict(q [n], metrics [n, 9],
+        llr2, llr4 [n, 174])."""
+        audio = self._ft4_audio(audio, "ft4_coherent")
+        frame, f0, h0, tt, ft = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (frame, f0, h0, ttweak, ftweak))
+        n = len(f0)
+        if n < 1 or any(len(x) != n for x in (frame, h0, tt, ft)):
+            raise Ft8rxError("ft4_coherent: one frame, f0, h0, ttweak and ftweak per candidate")
+        q = np.zeros(n, np.int32); met = np.zeros((n, 9), np.float32); l2 = np.zeros((n, 174), np.float32); l4 = np.zeros((n, 174), np.float32)
+        self._chk(self._L.ft8rx_ft4_coherent(self._h, audio.ctypes.data, len(audio), n, frame.ctypes.data, f0.ctypes.data, h0.ctypes.data,
+                                             tt.ctypes.data, ft.ctypes.data, q.ctypes.data, met.ctypes.data, l2.ctypes.data, l4.ctypes.data),
+                  "ft8rx_ft4_coherent")
+        return dict(q=q, metrics=met, llr2=l2, llr4=l4)
+
     def ft4_ldpc(self, llr, max_ncheck0, max_iters, mask=0):
         """ft8rx_ft4_ldpc: ldpc() on LLRs of FT4 codewords; the words come back descrambled."""
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)

@@ -330,6 +330,14 @@ struct ft8rx_handle {
         float* d_wf = nullptr; double2* d_part = nullptr; double* d_pc = nullptr; int32_t* d_best = nullptr; int32_t* d_cnt = nullptr;
         int32_t* d_frame = nullptr; double* d_energy = nullptr; ft8rx_ft4_subsig* d_sigs = nullptr;
     } ft4sub;
+    // FT4 coherent LLRs (ft8rx_ft4_set_coherent, k_ft4_coh; allocated at the first FT4 batch that runs with the
+    // setting on, WS_FT4_COH).  Per item of the failure list (at most max_frames << cand_shift): q, the nine metrics, the run-of-2 rows
+    // and behind them the run-of-4 rows, BP's outputs and attempts for both, the list OSD gets, its counter and the page-locked copy
+    struct Ft4Coh {
+        bool on = false; size_t bytes = 0;
+        int32_t* d_q = nullptr; float* d_met = nullptr; float* d_llr = nullptr; float* d_saved = nullptr; Att* d_att = nullptr;
+        int32_t* d_items = nullptr; int32_t* d_count = nullptr; int32_t* h_count = nullptr;
+    } ft4coh;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -417,7 +425,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3602,6 +3610,21 @@ static int ft4_workspaces(ft8rx_handle* h) {
     w.bytes = rc ? 0 : bytes;
     return rc;
 }
+// Everything the coherent step owns, at the first FT4 batch that runs with ft8rx_ft4_set_coherent on, all or nothing
+static int ft4coh_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4_COH)) return 0;
+    ft8rx_handle::Ft4Coh& w = h->ft4coh;
+    const size_t S = (size_t)h->max_frames << cand_shift(h->cfg);
+    FirstUse F(h, WS_FT4_COH);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_q, S); dev(&w.d_met, S * FT4_COH_NQ); dev(&w.d_llr, 2 * S * 174); dev(&w.d_saved, 2 * S * 174); dev(&w.d_att, 2 * S);
+    dev(&w.d_items, S); dev(&w.d_count, (size_t)1);
+    F.host(&w.h_count, (size_t)1);
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
 static int ft4_refuse(ft8rx_handle* h, const char* who) {
     const int c = optins::conflict(active_optins(h), optins::FT4_ROW);
     if (c < 0) return 0;
@@ -3634,10 +3657,13 @@ static void ft4_launch_osd(ft8rx_handle* h, const float* llr, int n, const uint3
 
 // One FT4 batch on the main stream into the next result slot: grid, search, demodulation, BP, the OSD list (one host round trip for
 // its length: OSD's raw-vector mode takes one block per vector), OSD, records and events; then the FT8 result tail (batch_finish).
+// With ft8rx_ft4_set_coherent on, the coherent step stands between the list and OSD and shortens the list.
 static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* audio, bool on_host, int B) {
     HIPCHK(h, hipSetDevice(h->device));
     if (ft4_refuse(h, who)) return -1;
     if (const int rc = ft4_workspaces(h)) return rc;
+    const bool coh = h->ft4coh.on;
+    if (coh) if (const int rc = ft4coh_workspaces(h)) return rc;
     ft8rx_handle::Ft4& w = h->ft4;
     const int slot = h->slot_enq;
     ResultSlot& sl = h->slots[slot];
@@ -3670,14 +3696,31 @@ static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* aud
     k_ft4_after_bp<<<(n + 255) / 256, 256, 0, s>>>(sl.rec, sl.ncand, B, sh, w.d_att, w.d_tweak, w.d_snr, sl.ev, sl.evcount, WorkList{w.d_items, w.d_count});
     HIPCHK(h, hipMemcpyAsync(w.h_count, w.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const int n_osd = w.h_count[0];
+    int n_osd = w.h_count[0];
     if (n_osd < 0 || n_osd > n) { set_err(h, "%s: the OSD list holds %d of %d slots", who, n_osd, n); return -2; }
+    const int32_t* osd_items = w.d_items;
+    if (coh && n_osd > 0) {
+        // the coherent step on the failure list: run-of-2 and run-of-4 LLRs, the same BP on both rows in one launch (run length 2
+        // wins), and what neither decodes goes on to OSD in list order -- a second read-back, of the shorter list's length
+        STAGE("ft4_coh");
+        const ft8rx_handle::Ft4Coh& k = h->ft4coh;
+        const int nl = n_osd;
+        k_ft4_coh<<<nl, FT4_DEMOD_NT, 0, s>>>(d_audio, w.d_trip, w.d_tweak, w.d_items, k.d_q, k.d_met, k.d_llr, k.d_llr + (size_t)nl * 174);
+        ft4_launch_bp(h, k.d_llr, 2 * nl, c.bp_nc0_b, c.bp_iters_b, mt, k.d_att, k.d_saved, s);
+        HIPCHK(h, hipMemsetAsync(k.d_count, 0, sizeof(int32_t), s));
+        k_ft4_after_coh<<<(nl + 255) / 256, 256, 0, s>>>(sl.rec, sh, k.d_att, w.d_items, nl, sl.ev, sl.evcount, WorkList{k.d_items, k.d_count});
+        HIPCHK(h, hipMemcpyAsync(k.h_count, k.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        n_osd = k.h_count[0];
+        if (n_osd < 0 || n_osd > nl) { set_err(h, "%s: the OSD list behind the coherent step holds %d of %d items", who, n_osd, nl); return -2; }
+        osd_items = k.d_items;
+    }
     STAGE("ft4_osd");
     if (n_osd > 0) {
-        k_ft4_gather<<<n_osd, 64, 0, s>>>(w.d_llr, w.d_items, w.d_dense);
+        k_ft4_gather<<<n_osd, 64, 0, s>>>(w.d_llr, osd_items, w.d_dense);
         HIPCHK(h, hipMemsetAsync(w.d_nan, 0, sizeof(int32_t), s));
         ft4_launch_osd(h, w.d_dense, n_osd, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), w.osd_max_hd, mt, w.d_attO, w.d_nan, s);
-        k_ft4_after_osd<<<(n_osd + 255) / 256, 256, 0, s>>>(sl.rec, sh, w.d_attO, w.d_items, n_osd, sl.ev, sl.evcount);
+        k_ft4_after_osd<<<(n_osd + 255) / 256, 256, 0, s>>>(sl.rec, sh, w.d_attO, osd_items, n_osd, sl.ev, sl.evcount);
     }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
@@ -3739,6 +3782,18 @@ int ft8rx_ft4_info(ft8rx_handle* h, uint64_t* workspace_bytes, float* sync_min, 
     if (sync_min) *sync_min = h->ft4.sync_min;
     if (osd_max_hd) *osd_max_hd = h->ft4.osd_max_hd;
     if (range) { range[0] = h->ft4.range.f0_lo; range[1] = h->ft4.range.f0_hi; range[2] = h->ft4.range.h0_lo; range[3] = h->ft4.range.h0_hi; }
+    return 0;
+}
+
+int ft8rx_ft4_set_coherent(ft8rx_handle* h, int32_t on) {
+    if (!h) return -1;
+    h->ft4coh.on = on != 0;
+    return 0;
+}
+int ft8rx_ft4_coh_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on) {
+    if (!h) return -1;
+    if (workspace_bytes) *workspace_bytes = ws_ready(h, WS_FT4_COH) ? (uint64_t)h->ft4coh.bytes : 0;
+    if (on) *on = h->ft4coh.on ? 1 : 0;
     return 0;
 }
 
@@ -3806,6 +3861,37 @@ int ft8rx_ft4_demod(ft8rx_handle* h, const int16_t* audio, int B, int n, const i
     HIPCHK(h, hipMemcpy(tweak, d_tw, sizeof(int32_t) * (size_t)n * 2, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(metric, d_met, sizeof(float) * n, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(snr, d_snr, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_coherent(ft8rx_handle* h, const int16_t* audio, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                       const int32_t* ttweak, const int32_t* ftweak, int32_t* q, float* metrics, float* llr2, float* llr4) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_coherent", audio, B) || n < 1 || !frame || !f0_idx || !h0_idx || !ttweak || !ftweak || !q || !metrics || !llr2 || !llr4) return -1;
+    for (int i = 0; i < n; i++)
+        if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < 0 || f0_idx[i] >= FT8RX_FT4_COLS - 6 || h0_idx[i] < -1024 || h0_idx[i] >= 1024 ||
+            ttweak[i] < -(FT4_N_DT / 2) || ttweak[i] > FT4_N_DT / 2 || ftweak[i] < -(FT4_N_DF / 2) || ftweak[i] > FT4_N_DF / 2) {
+            set_err(h, "ft8rx_ft4_coherent: candidate %d (frame %d, f0 %d, h0 %d, tt %d, ft %d) is out of range", i, frame[i], f0_idx[i], h0_idx[i], ttweak[i], ftweak[i]);
+            return -1; }
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const std::vector<int32_t> trip = pack_triples(n, frame, f0_idx, h0_idx);
+    std::vector<int32_t> tw((size_t)n * 2);
+    for (int i = 0; i < n; i++) { tw[2 * i] = ttweak[i]; tw[2 * i + 1] = ftweak[i]; }
+    Scratch S{h};
+    int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
+    int32_t* d_tw = S.put(tw.data(), tw.size()); NEED(d_tw);
+    int32_t* d_q = S.get<int32_t>(n); NEED(d_q);
+    float* d_met = S.get<float>((size_t)n * FT4_COH_NQ); NEED(d_met);
+    float* d_l2 = S.get<float>((size_t)n * 174); NEED(d_l2);
+    float* d_l4 = S.get<float>((size_t)n * 174); NEED(d_l4);
+    HIPCHK(h, hipMemcpy(w.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice));
+    k_ft4_coh<<<n, FT4_DEMOD_NT, 0, h->stream>>>(w.d_audio, d_trip, d_tw, nullptr, d_q, d_met, d_l2, d_l4);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(q, d_q, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(metrics, d_met, sizeof(float) * (size_t)n * FT4_COH_NQ, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(llr2, d_l2, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(llr4, d_l4, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
     return 0;
 }
 int ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,

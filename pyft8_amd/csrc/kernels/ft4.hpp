@@ -9,7 +9,9 @@
 //   k_ft4_demod   one workgroup per candidate: 9 x 5 fine trials on the 16 sync symbols, then the 105 x 4 amplitudes at the winner,
 //                 LLRs, SNR.  A wave takes a symbol, its lanes split the 576 samples; the phasor of sample n at frequency
 //                 fq x 12000 / 4608 Hz is (fq n mod 4608) / 4608 of a turn -- an exact integer phase, restarted per symbol
-//   k_ft4_trip, k_ft4_after_bp, k_ft4_gather, k_ft4_after_osd: the chain's bookkeeping (records, events, the OSD list)
+//   k_ft4_coh     opt-in (ft8rx_ft4_set_coherent), one workgroup per candidate BP left undecoded: the complex
+//                 105 x 4 sums at the winner, a residual-frequency scan on the sync symbols, max-log LLRs over runs of 2 and 4 symbols
+//   k_ft4_trip, k_ft4_after_bp, k_ft4_after_coh, k_ft4_gather, k_ft4_after_osd: the chain's bookkeeping (records, events, the OSD list)
 // Samples outside [0, 90000) read as zero through a clamped address and a select: never an out-of-range load.
 #ifndef FT8RX_FT4_HPP
 #define FT8RX_FT4_HPP
@@ -240,6 +242,163 @@ __global__ __launch_bounds__(FT4_DEMOD_NT) void k_ft4_demod(const int16_t* __res
     }
 }
 
+// ------------------------------------------------------------------------------------ coherent LLRs (opt-in, ft8rx_ft4_set_coherent)
+// DESIGN.md section 19.8; the twin is ft4.coherent_llrs.  One workgroup per item of a dense list (items NULL: item i is slot i); slot
+// c = items[i] names the candidate trip[3 c ..] and its fine-sync winner tweak[2 c ..].  Outputs per item: q, metrics [9], llr2 and
+// llr4 [174] each.
+//   1  C[s][t] = the demodulator's 576-sample sums at the winner, kept complex, times e^{-2 pi i (fq s mod 8) / 8}: tone 0's phase
+//      advances fq / 8 of a turn per symbol, an exact eighth; rot8 and rot32 below are the two tables
+//   2  M(q), q = -4 .. 4: per Costas block |sum of its four C[s][costas] e^{-2 pi i (q s mod 32) / 32}|, the blocks added in order; the
+//      first maximum; then row s of C turns by (q s mod 32) / 32
+//   3  runs of 2 and of 4 symbols from symbol 1 on.  A lane is one assignment: two bits per symbol of the run, a sync symbol takes
+//      its Costas tone whatever its two bits say and a symbol past 103 adds nothing, so the surplus lanes repeat assignments -- harmless
+//      under max.  Per bit max{a : bit = 1} - max{a : bit = 0}: a butterfly over the other lane bits leaves each half's maximum in
+//      the half's lanes.  Runs of 2: 16 lanes, finished in the wave.  Runs of 4: the 256 threads, the four waves' halves meet in LDS
+//      once, behind the loop over the runs.  max is order-free: nothing depends on scheduling.
+//   4  each row scaled like the demodulator's
+#define FT4_COH_NQ 9
+#define FT4_COH_RUNS4 26                         /* ceil(103 / 4); the last one (101 .. 103) is all sync */
+#define FT4_COH_RUNS2 52                         /* ceil(103 / 2); the last one (103) is sync */
+FT8_DEV bool ft4_is_sync(int s) { return (s - 1) % 33 < 4; }                       // s = 1 .. 103
+FT8_DEV int ft4_costas_at(int s) { const int k = (s - 1) % 33; return (k ^ (k >> 1)) ^ ((s - 1) / 33); }
+FT8_DEV int ft4_data_index(int s) { return s - 5 - 4 * ((s - 1) / 33); }            // inverse of ft4_data_sym
+// symbol s of a run under the 2-bit value v of its lane
+FT8_DEV cpx ft4_coh_term(const cpx* C, int s, int v) {
+    if (s > FT4_NSYM - 2) return make_float2(0.0f, 0.0f);
+    return C[4 * s + (ft4_is_sync(s) ? ft4_costas_at(s) : (v ^ (v >> 1)))];
+}
+// max over the lanes that agree with this lane in bit j of the lane id, among the NB low bits
+template <int NB> FT8_DEV float ft4_half_max(float a, int j) {
+    float v = a;
+#pragma unroll
+    for (int b = 0; b < NB; b++) { const float o = __shfl_xor(v, 1 << b); v = (b == j) ? v : fmaxf(v, o); }
+    return v;
+}
+// the 174 raw differences in s_raw -> out: 2.83 / std (population), all zeros where std = 0, an exact 0 becomes +0.001 (one wave)
+FT8_DEV void ft4_scale_llrs(const float* s_raw, float* __restrict__ out, int lane) {
+    float s = 0.0f;
+    for (int i = lane; i < 174; i += 64) s += s_raw[i];
+    const float mean = ft4_wave_sum(s) / 174.0f;
+    float q = 0.0f;
+    for (int i = lane; i < 174; i += 64) { const float d = s_raw[i] - mean; q += d * d; }
+    const float sd = sqrtf(ft4_wave_sum(q) / 174.0f);
+    for (int i = lane; i < 174; i += 64) { const float v = sd > 0.0f ? (2.83f * s_raw[i]) / sd : 0.0f; out[i] = (sd > 0.0f && v == 0.0f) ? 1e-3f : v; }
+}
+
+__global__ __launch_bounds__(FT4_DEMOD_NT) void k_ft4_coh(const int16_t* __restrict__ audio, const int32_t* __restrict__ trip, const int32_t* __restrict__ tweak,
+                                                          const int32_t* __restrict__ items, int32_t* __restrict__ q_out, float* __restrict__ metrics,
+                                                          float* __restrict__ llr2, float* __restrict__ llr4) {
+    __shared__ cpx s_C[FT4_NSYM * 4];
+    __shared__ cpx s_rot8[8], s_rot32[32];
+    __shared__ float s_blk[FT4_COH_NQ * 4], s_met[FT4_COH_NQ];
+    __shared__ float s_half[FT4_COH_RUNS4][4][14];           // per run and wave: bits 0 .. 5 x (bit = 0, bit = 1), [12] the wave's maximum
+    __shared__ float s_l2[176], s_l4[176];
+    __shared__ int s_q;
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c = items ? items[i] : i;
+    const int frame = trip[3 * c], f0 = trip[3 * c + 1], h0 = trip[3 * c + 2], tt = tweak[2 * c], ft = tweak[2 * c + 1];
+    const int16_t* a = audio + (size_t)frame * FT8RX_FT4_NSAMP;
+    const int fq0 = 4 * f0 + ft;
+    if (tid < 32) { float sn, cs; sincospif(-(float)tid * (1.0f / 16.0f), &sn, &cs); s_rot32[tid] = make_float2(cs, sn); }
+    else if (tid < 40) { float sn, cs; sincospif(-(float)(tid - 32) * 0.25f, &sn, &cs); s_rot8[tid - 32] = make_float2(cs, sn); }
+    __syncthreads();
+    // ---- 1: the 105 x 4 complex sums at the winner (k_ft4_demod's loop), each times tone 0's phase at the symbol's start
+#pragma unroll 1
+    for (int sym = wv; sym < FT4_NSYM; sym += FT4_DEMOD_NT / 64) {
+        const int base = FT4_HOP * h0 + FT4_DT_STEP * tt + FT4_NSPS * sym;
+        const cpx r = s_rot8[(fq0 * sym) & 7];
+        float v[9];
+#pragma unroll
+        for (int j = 0; j < 9; j++) v[j] = ft4_sample(a, base + lane + 64 * j);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int fq = fq0 + 8 * t;
+            float re = 0.0f, im = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 9; j++) { const cpx w = ft4_phasor(fq, lane + 64 * j); re += v[j] * w.x; im -= v[j] * w.y; }
+            re = ft4_wave_sum(re); im = ft4_wave_sum(im);
+            if (lane == 0) s_C[4 * sym + t] = make_float2(re * r.x - im * r.y, re * r.y + im * r.x);
+        }
+    }
+    __syncthreads();
+    // ---- 2: the nine metrics, the first maximum, the rotation per symbol
+    if (tid < FT4_COH_NQ * 4) {
+        const int qi = tid >> 2, b = tid & 3;
+        float re = 0.0f, im = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int s = 1 + 33 * b + k;
+            const cpx z = s_C[4 * s + ft4_sync_tone(4 * b + k)], r = s_rot32[((qi - 4) * s) & 31];
+            re += z.x * r.x - z.y * r.y; im += z.x * r.y + z.y * r.x;
+        }
+        s_blk[tid] = sqrtf(re * re + im * im);
+    }
+    __syncthreads();
+    if (tid < FT4_COH_NQ) s_met[tid] = ((s_blk[4 * tid] + s_blk[4 * tid + 1]) + s_blk[4 * tid + 2]) + s_blk[4 * tid + 3];
+    __syncthreads();
+    if (tid == 0) {
+        int b = 0;
+        for (int t = 1; t < FT4_COH_NQ; t++) if (s_met[t] > s_met[b]) b = t;
+        s_q = b - 4; q_out[i] = b - 4;
+    }
+    if (tid < FT4_COH_NQ) metrics[(size_t)i * FT4_COH_NQ + tid] = s_met[tid];
+    __syncthreads();
+    const int q = s_q;
+    for (int e = tid; e < FT4_NSYM * 4; e += FT4_DEMOD_NT) {
+        const cpx z = s_C[e], r = s_rot32[(q * (e >> 2)) & 31];
+        s_C[e] = make_float2(z.x * r.x - z.y * r.y, z.x * r.y + z.y * r.x);
+    }
+    __syncthreads();
+    // ---- 3a: runs of 2 -- 16 lanes per run, 16 runs per sweep of the block
+    for (int run = tid >> 4; run < FT4_COH_RUNS2; run += FT4_DEMOD_NT / 16) {
+        const int s0 = 1 + 2 * run;
+        const cpx z0 = ft4_coh_term(s_C, s0, tid & 3), z1 = ft4_coh_term(s_C, s0 + 1, (tid >> 2) & 3);
+        const float re = z0.x + z1.x, im = z0.y + z1.y;
+        const float amp = sqrtf(re * re + im * im);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float mine = ft4_half_max<4>(amp, j), other = __shfl_xor(mine, 1 << j);
+            const int s = s0 + (j >> 1);
+            if ((tid & 15) == 0 && s <= FT4_NSYM - 2 && !ft4_is_sync(s)) s_l2[2 * ft4_data_index(s) + 1 - (j & 1)] = other - mine;      // lane bits all 0: mine = the bit-0 half
+        }
+    }
+    // ---- 3b: runs of 4 -- the block is the 256 assignments; lane bits 0 .. 5 are symbols 0 .. 2 of the run, the wave is symbol 3
+#pragma unroll 1
+    for (int run = 0; run < FT4_COH_RUNS4; run++) {
+        const int s0 = 1 + 4 * run;
+        const cpx z0 = ft4_coh_term(s_C, s0, lane & 3), z1 = ft4_coh_term(s_C, s0 + 1, (lane >> 2) & 3), z2 = ft4_coh_term(s_C, s0 + 2, (lane >> 4) & 3),
+                  z3 = ft4_coh_term(s_C, s0 + 3, wv);
+        const float re = ((z0.x + z1.x) + z2.x) + z3.x, im = ((z0.y + z1.y) + z2.y) + z3.y;
+        const float amp = sqrtf(re * re + im * im);
+        float* hm = s_half[run][wv];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            const float mine = ft4_half_max<6>(amp, j);
+            if (lane == 0) hm[2 * j] = mine;
+            if (lane == (1 << j)) hm[2 * j + 1] = mine;
+            if (j == 0) { const float all = fmaxf(mine, __shfl_xor(mine, 1)); if (lane == 0) hm[12] = all; }
+        }
+    }
+    __syncthreads();
+    if (tid < FT4_COH_RUNS4 * 8) {                           // the one LDS combine: thread = (run, bit j of the 8-bit assignment)
+        const int run = tid >> 3, j = tid & 7, s = 1 + 4 * run + (j >> 1);
+        float m0, m1;
+        if (j < 6) {
+            m0 = fmaxf(fmaxf(s_half[run][0][2 * j], s_half[run][1][2 * j]), fmaxf(s_half[run][2][2 * j], s_half[run][3][2 * j]));
+            m1 = fmaxf(fmaxf(s_half[run][0][2 * j + 1], s_half[run][1][2 * j + 1]), fmaxf(s_half[run][2][2 * j + 1], s_half[run][3][2 * j + 1]));
+        } else {                                             // symbol 3's value is the wave: bit 6 = waves 1, 3, bit 7 = waves 2, 3
+            const float w0 = s_half[run][0][12], w1 = s_half[run][1][12], w2 = s_half[run][2][12], w3 = s_half[run][3][12];
+            m0 = j == 6 ? fmaxf(w0, w2) : fmaxf(w0, w1);
+            m1 = j == 6 ? fmaxf(w1, w3) : fmaxf(w2, w3);
+        }
+        if (s <= FT4_NSYM - 2 && !ft4_is_sync(s)) s_l4[2 * ft4_data_index(s) + 1 - (j & 1)] = m1 - m0;
+    }
+    __syncthreads();
+    // ---- 4: the two rows, scaled
+    if (wv == 0) ft4_scale_llrs(s_l2, llr2 + (size_t)i * 174, lane);
+    else if (wv == 1) ft4_scale_llrs(s_l4, llr4 + (size_t)i * 174, lane);
+}
+
 // ------------------------------------------------------------------------------------ the chain's bookkeeping
 // slot c of the batch -> its triple, frame -1 for a slot k_topk left empty
 __global__ void k_ft4_trip(const ft8rx_record* __restrict__ rec, const int32_t* __restrict__ ncand, int B, int sh, int32_t* __restrict__ trip) {
@@ -264,6 +423,25 @@ __global__ __launch_bounds__(256) void k_ft4_after_bp(ft8rx_record* __restrict__
         if (a.ok) {
             r.status = FT8RX_ST_DECODED; r.ipass = 4; r.ap = 0; r.method = FT8RX_M_LDPC_B; r.n_its = a.n_its; r.msg_lo = a.lo; r.msg_hi = a.hi;
             log_event(ev, evcount, c >> sh, c & ((1 << sh) - 1), 4, 0, a.n_its + 1, a.lo, a.hi, 1);
+        } else want = true;
+    }
+    work_push_block(osdl, want, c);
+}
+// after the coherent BPs (opt-in; att [2 n]: the run-of-2 attempts of the n list items, then the run-of-4 ones): run length 2 wins; a
+// decode is a BP decode whose nsync carries the run length and whose event carries slot 1 or 2; the rest goes onto OSD's list
+__global__ __launch_bounds__(256) void k_ft4_after_coh(ft8rx_record* __restrict__ rec, int sh, const Att* __restrict__ att, const int32_t* __restrict__ items,
+                                                       int n, ft8rx_event* ev, int32_t* evcount, WorkList osdl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool want = false; int c = 0;
+    if (i < n) {
+        c = items[i];
+        const Att a2 = att[i], a4 = att[n + i];
+        if (a2.ok || a4.ok) {
+            const Att a = a2.ok ? a2 : a4;
+            ft8rx_record& r = rec[c];
+            r.status = FT8RX_ST_DECODED; r.ipass = 4; r.ap = 0; r.method = FT8RX_M_LDPC_B; r.n_its = a.n_its; r.nsync = a2.ok ? 2 : 4;
+            r.msg_lo = a.lo; r.msg_hi = a.hi;
+            log_event(ev, evcount, c >> sh, c & ((1 << sh) - 1), 4, a2.ok ? 1 : 2, a.n_its + 1, a.lo, a.hi, 1);
         } else want = true;
     }
     work_push_block(osdl, want, c);

@@ -18,7 +18,24 @@ The twin is the definition the kernels are held to (tests/test_gpu_ft4.py):
   demod    the 105 x 4 amplitude matrix at the winner; 174 max-log LLRs on amplitudes (positive = bit 1), scaled 2.83 / std (all
            zero where std = 0; otherwise an LLR of exactly 0 -- a symbol outside the frame -- becomes +0.001); SNR from the
            matrix's powers
-and of the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/test_gpu_ft4_sub.py; stated in full where sub_model stands, below):
+and, opt-in, of the coherent LLRs (k_ft4_coh, tests/test_gpu_ft4_coherent.py; coherent_llrs below).  FT4 is
+continuous-phase 4-GFSK with tone spacing = baud rate, so consecutive symbols are phase-coherent and runs of symbols can be decided
+jointly.  Input: a candidate (f0, h0) with the fine sync's winner (tt, ft); fq = 4 f0 + ft, start = 144 h0 + 36 tt:
+  complex  C[s][t] = (sum_{n < 576} x[start + 576 s + n] e^{-2 pi i ((fq + 8 t) n mod 4608) / 4608}) e^{-2 pi i ((fq s) mod 8) / 8},
+           s = 0 .. 104, t = 0 .. 3, x = 0 outside the frame.  The first factor is demod's DFT, its phase restarting per symbol; the
+           second carries tone 0's phase from symbol to symbol: fq 576 / 4608 turns per symbol is an exact number of eighths, and the
+           tones' own 8 t add whole turns.  |C| = amplitudes
+  residual for q = -4 .. 4 (quarter steps of 2.6042 Hz): M(q) = sum over the four Costas blocks b of
+           |sum_{k < 4} C[p_b + k][costas_b[k]] e^{-2 pi i ((q (p_b + k)) mod 32) / 32}|; the first maximum in the order -4 .. 4; then
+           row s of C is multiplied by e^{-2 pi i ((q s) mod 32) / 32}: a rotation per symbol, an exact 32nd of a turn, nothing inside
+           a symbol is touched
+  runs     symbols 1 .. 103 in runs of L = 2 and L = 4 consecutive symbols from symbol 1 on (the last run is shorter: 1 and 3
+           symbols); a sync symbol inside a run enters with its Costas tone, a run without data symbols is skipped; over all 4^d
+           assignments of the run's d <= 4 data symbols a = |sum over the run's symbols of C[s][tone_s]|, data tones through GRAY4;
+           per bit of the run LLR = max{a : bit = 1} - max{a : bit = 0}
+  scaling  as demod: 2.83 / std over the 174 values, all zero where std = 0, otherwise an exact 0 becomes +0.001
+L = 1 is demod's LLRs again (tests/test_ft4_coherent.py holds it to 1e-12).
+The twin also defines the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/test_gpu_ft4_sub.py; stated in full where sub_model stands, below):
   model    the complex form of tones_to_wave; bins: 41 bins (+-3.97 Hz) of the 60480-point transform of x conj(model); refine: the
            bins' energy at 13 starts 4 samples apart, the first maximum; subtract: x -= 2 Re(a model), a = the bins' inverse transform
 """
@@ -256,7 +273,11 @@ def llr_from_amplitudes(A):
     D = A[list(DATA_POS)]
     msb = np.maximum(D[:, 2], D[:, 3]) - np.maximum(D[:, 0], D[:, 1])       # tones 2, 3 carry values 3, 2
     lsb = np.maximum(D[:, 1], D[:, 2]) - np.maximum(D[:, 0], D[:, 3])       # tones 1, 2 carry values 1, 3
-    llr = np.stack([msb, lsb], axis=1).reshape(174)
+    return _scale_llrs(np.stack([msb, lsb], axis=1).reshape(174))
+
+
+def _scale_llrs(llr):
+    """174 raw differences -> 2.83 / std of them; all zero where std is 0, otherwise an exact 0 becomes +0.001."""
     sd = np.std(llr)
     if not sd > 0:
         return np.zeros(174)
@@ -284,6 +305,66 @@ def demod(x, f0, h0):
     return dict(tt=tt, ft=ft, metric=float(m.flat[k]), metrics=m, llr=llr_from_amplitudes(A), snr=snr_from_amplitudes(A), amps=A)
 
 
+# ----------------------------------------------------------------------------- the twin: coherent LLRs (k_ft4_coh)
+COH_Q = tuple(range(-4, 5))            # the residual-frequency trials, x 12000 / (32 x 576) = 0.6510 Hz: a 32nd of a turn per symbol
+_SYNC_TONE = dict(SYNC_SYMS)
+_DATA_INDEX = {p: i for i, p in enumerate(DATA_POS)}
+
+
+def complex_amplitudes(x, f0, h0, tt, ft):
+    """C[105][4] of the definition's step 1: the rectangular DFT of `amplitudes`, kept complex, times the phase tone 0 has gathered
+    since symbol 0 -- (fq s mod 8) / 8 of a turn, fq = 4 f0 + ft.  |C| is `amplitudes`."""
+    x = np.asarray(x, np.float64)
+    fq = 4 * int(f0) + int(ft)
+    V = _symbols(x, HOP * int(h0) + DT_STEP * int(tt) + NSPS * np.arange(NSYM))
+    C = V @ _phasors(fq + 8 * np.arange(4)).T
+    return C * np.exp(-2j * np.pi * ((fq * np.arange(NSYM)) % 8) / 8.0)[:, None]
+
+
+def coherent_metrics(C):
+    """M(q), q = -4 .. 4: per Costas block the magnitude of the four sync symbols' sum, each turned back by (q s mod 32) / 32 of a
+    turn; the four blocks' magnitudes added."""
+    m = np.zeros(len(COH_Q))
+    for i, q in enumerate(COH_Q):
+        for b, p in enumerate(SYNC_POS):
+            m[i] += abs(sum(C[p + k][COSTAS4[b][k]] * np.exp(-2j * np.pi * ((q * (p + k)) % 32) / 32.0) for k in range(4)))
+    return m
+
+
+def run_llrs(C, L):
+    """The 174 scaled LLRs of runs of L symbols (1, 2 or 4) on the complex amplitudes C: symbols 1 .. 103 in runs from symbol 1 on (the
+    last one shorter), a sync symbol with its Costas tone, the d data symbols of a run over all 4^d assignments through GRAY4:
+    a = |sum of the run's C[s][tone]|, and per bit max{a : bit = 1} - max{a : bit = 0}.  A run without data symbols is skipped."""
+    llr = np.zeros(174)
+    gray = list(GRAY4)
+    for s0 in range(1, NSYM - 1, L):
+        syms = range(s0, min(s0 + L, NSYM - 1))
+        data = [s for s in syms if s in _DATA_INDEX]
+        if not data:
+            continue
+        acc = np.asarray(sum(C[s][_SYNC_TONE[s]] for s in syms if s in _SYNC_TONE) + 0j)
+        for s in data:
+            acc = np.add.outer(acc, C[s][gray])                             # one axis per data symbol, indexed by its 2-bit value
+        a = np.abs(acc)
+        for k, s in enumerate(data):
+            v = np.moveaxis(a, k, 0).reshape(4, -1).max(axis=1)             # the best assignment of the others, per value of this symbol
+            llr[2 * _DATA_INDEX[s]] = max(v[2], v[3]) - max(v[0], v[1])
+            llr[2 * _DATA_INDEX[s] + 1] = max(v[1], v[3]) - max(v[0], v[2])
+    return _scale_llrs(llr)
+
+
+def coherent_llrs(x, f0, h0, tt, ft):
+    """Coherent LLRs of candidate (f0, h0) at the fine sync's winner (tt, ft) -> dict(q, metrics[9], llr1, llr2, llr4): the residual
+    frequency q (the first maximum of the metrics in the order -4 .. 4), and the LLRs of runs of 1, 2 and 4 symbols on the complex
+    amplitudes turned back by (q s mod 32) / 32 of a turn per symbol.  llr1 is llr_from_amplitudes(amplitudes(...)) again: a
+    rotation leaves a single symbol's magnitudes alone."""
+    C = complex_amplitudes(x, f0, h0, tt, ft)
+    m = coherent_metrics(C)
+    q = COH_Q[int(np.argmax(m))]
+    C = C * np.exp(-2j * np.pi * ((q * np.arange(NSYM)) % 32) / 32.0)[:, None]
+    return dict(q=q, metrics=m, llr1=run_llrs(C, 1), llr2=run_llrs(C, 2), llr4=run_llrs(C, 4))
+
+
 def early_ok(h0_idx, ttweak, n_have):
     """The early-pass rule of live FT4: a decode of a slot of which only the first n_have samples exist is
     delivered iff its whole signal -- start 144 h0 + 36 tt (it may be negative), 105 symbols of 576 samples -- with the fine sync's
@@ -303,10 +384,10 @@ def slot_parity(cyclestart_string):
     return int(sec // 7.5) % 2
 
 
-def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None):
+def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None, nsym=None):
     """Rows of the native packager (ft8rx_package_batch / _ext on FT4 records) -> message dicts with the keys of the FT8 ones and FT4's
     values: tsec = (144 h0 + 36 tt) / 12000, fHz = 10.41667 f0 + 2.60417 ft, "mode": "FT4", '+' in all_txt_format, their_tx_cycle =
-    the slot's parity."""
+    the slot's parity.  nsym (a receiver with ft4_coherent): per row the run length of its decode -> "nsym": 1, 2 or 4."""
     import time
     from . import messages as _m
     out = []
@@ -314,7 +395,7 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None)
     rows = msgs[:min(int(count), len(msgs))]
     ext = len(rows) > 0 and "i3" in rows.dtype.names
     parity = slot_parity(cyclestart_string)
-    for r in rows:
+    for k, r in enumerate(rows):
         text = tuple(x.decode() for x in r["f"].tolist())
         tt, ft = int(r["ttweak"]), int(r["ftweak"])
         tsec = (HOP * int(r["h0_idx"]) + DT_STEP * tt) / FS
@@ -329,6 +410,8 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None)
              "cyclestart_string": cyclestart_string, "decode_completed": now, "tweaks": tw, "decode_notes": notes + tw, "mode": "FT4"}
         if ext:
             d["msg_type"] = _m.msg_type(word_type)
+        if nsym is not None:
+            d["nsym"] = int(nsym[k])
         out.append(d)
         if on_message is not None:
             on_message(d)

@@ -739,6 +739,12 @@ class Receiver:
             raise _lib.Ft8rxError(f"ft4_passes must be 1, 2 or 3, got {self.ft4_passes!r}")
         self.ft4_passes = int(self.ft4_passes)
         self.ft4_sub_osd_max_hd = extension_knobs.pop("ft4_sub_osd_max_hd", None)
+        # ft4_coherent (section 19.8): the candidates BP leaves undecoded are decoded again on LLRs over runs of two and four symbols,
+        # before OSD; every FT4 message dict then says "nsym": 1, 2 or 4.  Applied in _ft4_set, so every FT4 pass gets it.
+        self.ft4_coherent = extension_knobs.pop("ft4_coherent", False)
+        if not isinstance(self.ft4_coherent, (bool, np.bool_)):
+            raise _lib.Ft8rxError(f"ft4_coherent must be True or False, got {self.ft4_coherent!r}")
+        self.ft4_coherent = bool(self.ft4_coherent)
         # live FT4 (section 19.7; modes= here or in start()): the early passes of a 7.5-s slot, seconds into it -- one at 6.0 s (72000
         # samples) by default, () = only the complete slot
         self.ft4_early_samples = _wide_in.ft4_early_samples(extension_knobs.pop("ft4_early_decode_s", _wide_in.FT4_EARLY_S_DEFAULT))
@@ -1274,7 +1280,8 @@ class Receiver:
         search_freq_range, search_time_range (absolute start seconds; FT4's default is -0.5 .. +2.0), msg_types, ft4_sync_min and
         ft4_osd_max_hd; a fresh call-hash table per frame (and per pass).  The receiver's ft4_passes = 2 or 3 (section 19.6): the decoded
         signals are subtracted on the device and the residual is decoded again; the later passes' messages follow pass 1's, "_SUB" in
-        their decode_notes, and the records returned are the last pass's.  Refused, by name: a-priori calls, recall, weak, reports,
+        their decode_notes, and the records returned are the last pass's.  The receiver's ft4_coherent=True (section 19.8): what BP
+        leaves undecoded is decoded again on LLRs over runs of two and four symbols, and every dict says "nsym": 1, 2 or 4.  Refused, by name: a-priori calls, recall, weak, reports,
         the packed output, the per-call passes > 1 and float frames."""
         if (self.float_frames if float_frames is None else bool(float_frames)):
             raise _lib.Ft8rxError("FT4 decoding (decode_frames_ft4) is not supported together with float_frames=True: FT4 frames are int16")
@@ -1294,10 +1301,12 @@ class Receiver:
             msgs, mcnt = self._package(res)
             cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
             if self.ft4_passes > 1:                                  # the later passes need the handle: the dicts are made under its lock
-                out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
+                out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message,
+                                          nsym=self._ft4_nsym(res[0], msgs, mcnt, f)) for f in range(B)]
                 res = self._later_passes_ft4(h, B, res, msgs, mcnt, out, cs, gate)
                 return (out, res[0], res[1]) if return_records else out
-        out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message) for f in range(B)]
+        out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message,
+                                  nsym=self._ft4_nsym(res[0], msgs, mcnt, f)) for f in range(B)]
         return (out, res[0], res[1]) if return_records else out
 
     def _ft4_set(self, h):
@@ -1305,6 +1314,8 @@ class Receiver:
         # the OSD gate: the one given, else the library's default -- with msg_types set, the lower gate of the same noise sweep
         gate = self.ft4_osd_max_hd if self.ft4_osd_max_hd is not None or not self.cfg.msg_types else _ft4.OSD_MAX_HD_MSG_TYPES
         h.ft4_set(self.ft4_sync_min, gate)
+        if self.ft4_coherent:                                        # a receiver without it never calls the setter: the handle's default is off
+            h.ft4_set_coherent(True)
         f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
         h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
         if f0 == (0, 0) and h0 != (0, 0):
@@ -1313,6 +1324,13 @@ class Receiver:
             h0 = _ft4.time_range_to_h0()
         h.ft4_set_range(f0[0], f0[1], h0[0], h0[1])
         return gate
+
+    def _ft4_nsym(self, rec, msgs, mcnt, f):
+        """ft4_coherent: per packaged message of frame f the run length its decode used -- the nsync of the candidate the row names, 0
+        (a single-symbol decode) read as 1; None with the setting off: the dicts gain nothing"""
+        if not self.ft4_coherent:
+            return None
+        return [int(v) or 1 for v in rec[f][msgs[f]["cand"][:int(mcnt[f])]]["nsync"]]
 
     @staticmethod
     def _ft4_words(rec, msgs, mcnt, f):
@@ -1348,7 +1366,8 @@ class Receiver:
                 msgs, mcnt = self._package(res, **pkg_kw)
                 for f in range(B):
                     words = self._ft4_words(res[0], msgs, mcnt, f)
-                    for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band if bands is None else bands[f]), words):
+                    for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band if bands is None else bands[f],
+                                                       nsym=self._ft4_nsym(res[0], msgs, mcnt, f)), words):
                         if w in have[f]:
                             continue
                         have[f].add(w)
@@ -1457,11 +1476,13 @@ class Receiver:
             res = h.fetch(B)
             if not early and self.ft4_passes > 1:                    # the later passes need the handle: packaged under its lock
                 msgs, mcnt = self._package(res, **pkg)
-                dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f]) for f in range(B)]
+                dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f], nsym=self._ft4_nsym(res[0], msgs, mcnt, f))
+                         for f in range(B)]
                 self._later_passes_ft4(h, B, res, msgs, mcnt, dicts, cs, gate, bands=bands, notify=False, **pkg)
         if dicts is None:                                            # the host message layer runs outside _live_lock
             msgs, mcnt = self._package(res, **pkg)
-            dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f]) for f in range(B)]
+            dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f], nsym=self._ft4_nsym(res[0], msgs, mcnt, f))
+                     for f in range(B)]
         for f, j in enumerate(ch):
             self._deliver_ft4(msgs[f] if early else None, dicts[f], c, n_have, j, w.seen[j], out)
 
@@ -1521,7 +1542,7 @@ def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=
 
 def decode_frames_ft4(audio_i16, on_message=None, **receiver_kwargs):
     """decode_frames_ft4(audio_i16[B, 90000], **receiver_kwargs) -> list[list[message dict]]: Receiver.decode_frames_ft4 on a receiver
-    of its own (FT4)."""
+    of its own (FT4); ft4_passes=, ft4_coherent= and the other FT4 knobs go to Receiver with the keyword arguments."""
     audio = np.ascontiguousarray(audio_i16, np.int16)
     rx = Receiver("", on_message, max_frames=max(1, audio.shape[0] if audio.ndim == 2 else 1), **receiver_kwargs)
     try:

@@ -1,6 +1,6 @@
 """FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
 
-    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes]
+    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes] [--coherent]
 
 --prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
               apart, starts 0.1 .. 1.5 s), through Handle.ft4_decode and the native message layer; the 50 % point by interpolation
@@ -10,6 +10,10 @@
 --passes      subtraction passes (section 19.6) on 256 crowded frames (16 signals in 300 .. 1200 Hz, -12 .. +10 dB, make_frame indices 1000 ..
               1255): true and false decodes per frame for ft4_passes 1 / 2 / 3 at msg_types 0 (gate 40) and all (gate 24), the later
               passes' own gate (ft4_sub_osd_max_hd) swept, the times of one subtraction sweep and of a whole two-pass batch at B = 256
+--coherent    coherent LLRs (section 19.8), each figure beside the same recipe with the setting off, on one handle in one session: decode
+              probability at -19 .. -12 dB (the recipe of --prob) with the decodes by run length; false decodes on the 2048 noise frames
+              at the default gates (40 at msg_types 0, 24 at all); frames/s at B = 256 with 20 signals per frame (device-resident), the
+              stage times and the length of the list the coherent step works on
 --twin N      no GPU: the yardstick, the float64 twin with the numpy BP on N signals per step of -18 .. -11 dB (the same recipe)
 Results are merged into the file's existing sections."""
 import argparse
@@ -144,6 +148,74 @@ def measure_throughput(h, B=256, warmup=3, steps=20):
     return out
 
 
+def measure_coherent(h, noise_frames_n=2048, chunk=256, per_step=200, B=256, warmup=3, steps=20):
+    import torch
+    from pyft8_amd import _lib
+    snrs = list(range(-19, -11))
+    out = {"probability": {"snr_db": snrs, "signals_per_step": per_step}, "noise": {"frames": noise_frames_n}, "throughput": {"B": B, "signals_per_frame": 20}}
+    live = lambda res: np.concatenate([res[0][f, :res[1][f]] for f in range(len(res[1]))])
+    # ---- decode probability
+    for name, on in (("off", False), ("on", True)):
+        h.ft4_set_coherent(on)
+        r = {"decoded": [], "bp": [], "runs_of_2": [], "runs_of_4": [], "osd": []}
+        for snr in snrs:
+            frames = [prob_frame(snr, k, float(snr)) for k in range(per_step // 10)]
+            res = h.ft4_decode(np.stack([f[0] for f in frames]))
+            got = texts_of(h, res)
+            r["decoded"].append(sum(t["msg"] in got[f] for f, (_, truth) in enumerate(frames) for t in truth))
+            dec = live(res); dec = dec[dec["status"] == 1]
+            r["bp"].append(int(((dec["ipass"] == 4) & (dec["nsync"] == 0)).sum())); r["osd"].append(int((dec["ipass"] == 5).sum()))
+            r["runs_of_2"].append(int((dec["nsync"] == 2).sum())); r["runs_of_4"].append(int((dec["nsync"] == 4).sum()))
+            print(f"coherent {name} prob {snr:+d} dB: {r['decoded'][-1]}/{per_step}", flush=True)
+        r["probability"] = [d / per_step for d in r["decoded"]]
+        r["half_point_db"] = half_point(snrs, r["probability"])
+        out["probability"][name] = r
+    # ---- false decodes on noise, the default gates
+    nz = {f"{name}_{m}": {"false_decodes": 0, "by_run_length": {"1": 0, "2": 0, "4": 0, "osd": 0}, "texts": []} for name in ("off", "on") for m in ("0", "all")}
+    cands = 0
+    for first in range(0, noise_frames_n, chunk):
+        a = noise_frames(chunk, first)
+        for m, mask, gate in (("0", 0, ft4.OSD_MAX_HD_DEFAULT), ("all", _lib.MT_ALL, ft4.OSD_MAX_HD_MSG_TYPES)):
+            h.set_msg_types(mask); h.ft4_set(osd_max_hd=gate)
+            for name, on in (("off", False), ("on", True)):
+                h.ft4_set_coherent(on)
+                res = h.ft4_decode(a)
+                if m == "0" and not on:
+                    cands += int(res[1].sum())
+                dec = live(res); dec = dec[dec["status"] == 1]
+                e = nz[f"{name}_{m}"]
+                e["false_decodes"] += len(dec)
+                for x in dec:
+                    e["by_run_length"]["osd" if x["ipass"] == 5 else str(int(x["nsync"]) or 1)] += 1
+                if len(dec):
+                    e["texts"] += [f"frame {first + f}: {t}" for f, s in enumerate(texts_of(h, res, mask)) for t in s]
+        print(f"coherent noise frames {first + chunk}: " + ", ".join(f"{k} {v['false_decodes']}" for k, v in nz.items()), flush=True)
+    h.set_msg_types(0); h.ft4_set()
+    out["noise"].update(nz); out["noise"]["candidates"] = cands
+    # ---- throughput, device-resident frames
+    a = np.stack([throughput_frame(k) for k in range(B)])
+    d = torch.from_numpy(a).to("cuda:0"); torch.cuda.synchronize()
+    for name, on in (("off", False), ("on", True), ("off_again", False), ("on_again", True)):
+        h.ft4_set_coherent(on)
+        for _ in range(warmup):
+            h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B)
+        t = []
+        for _ in range(steps):
+            t0 = time.perf_counter(); h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B); t.append(time.perf_counter() - t0)
+        rec = live(res); dec = rec[rec["status"] == 1]
+        first_bp = int(((dec["ipass"] == 4) & (dec["nsync"] == 0)).sum())
+        h.set_profiling(True)
+        h.ft4_enqueue(d.data_ptr(), B); h.fetch(B); h.sync()
+        stage = {k: round(float(v), 4) for k, v in h.stage_times().items()}
+        h.set_profiling(False)
+        out["throughput"][name] = {"device_frames_per_s": B / float(np.median(t)), "device_step_ms": [round(1e3 * x, 3) for x in t], "stage_ms": stage,
+                                   "candidates": len(rec), "decoded": len(dec), "list_behind_first_bp": len(rec) - first_bp,
+                                   "runs_of_2": int((dec["nsync"] == 2).sum()), "runs_of_4": int((dec["nsync"] == 4).sum()), "osd": int((dec["ipass"] == 5).sum())}
+        print("coherent throughput", name, out["throughput"][name]["device_frames_per_s"], stage, flush=True)
+    h.ft4_set_coherent(False)
+    return out
+
+
 CROWDED_KW = dict(n_signals=16, snr_range=(-12, 10), freq_range=(300, 1200), t0_range=(0.2, 1.2), min_sep_hz=25)
 SUB_GATES = [None, 32, 24, 16]
 
@@ -205,12 +277,12 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ft4_measure.json"))
     ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
     ap.add_argument("--twin", type=int, default=0); ap.add_argument("--passes", action="store_true")
-    ap.add_argument("--noise-frames", type=int, default=2048)
+    ap.add_argument("--noise-frames", type=int, default=2048); ap.add_argument("--coherent", action="store_true")
     args = ap.parse_args()
     res = json.load(open(args.out)) if os.path.exists(args.out) else {}
     if args.twin:
         res["twin_probability"] = measure_twin(args.twin)
-    if args.prob or args.noise or args.throughput:
+    if args.prob or args.noise or args.throughput or args.coherent:
         import torch  # noqa: F401 -- before libft8rx.so loads (_lib.lib)
         from pyft8_amd import _lib
         h = _lib.Handle(max_frames=256)
@@ -220,6 +292,8 @@ if __name__ == "__main__":
             res["probability"] = measure_prob(h)
         if args.noise:
             res["noise"] = measure_noise(h, args.noise_frames)
+        if args.coherent:
+            res["coherent"] = measure_coherent(h, args.noise_frames)
         h.close()
     if args.passes:
         import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
