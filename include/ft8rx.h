@@ -55,6 +55,7 @@
  *     ft8rx_ddc_rat_stream_close                                                       the down-converter)
  *     ft8rx_ft4_decode_batch  ft8rx_ft4_enqueue_batch  ft8rx_ft4_decode_messages  ft8rx_ft4_set  ft8rx_ft4_set_range  ft8rx_ft4_info
  *     ft8rx_ft4_subtract  ft8rx_ft4_subtraction_list  ft8rx_ft4_sub_info  ft8rx_ft4_staging_audio  ft8rx_ft4_encode_tones   (opt-in FT4, 7.5-s frames)
+ *     ft8rx_ft4_report  ft8rx_ft4_report_info                                         (opt-in measured SNR / frequency / time of FT4 decodes)
  *     ft8rx_ft4_set_coherent  ft8rx_ft4_coh_info                                       (opt-in FT4 coherent LLRs: runs of two and four symbols)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
@@ -1065,6 +1066,30 @@ int16_t* ft8rx_ft4_staging_audio(ft8rx_handle* h);
  * the given start [n][41][2] (index k + 20) and the energies of the 13 refine trials [n][13] */
 int  ft8rx_ft4_sub_probe(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const ft8rx_ft4_subsig* sigs,
                          float* model, double* bins, double* energy);
+
+/* ---- FT4 measured reports (extension; kernels/ft4_report.hpp; pyft8_amd/ft4.py holds the float64 twin) ----
+ * A decoded FT4 signal (ft8rx_ft4_subsig: start s0, fq, its 105 tones) is measured against its own model s[n], the subtraction's:
+ * y_tau[n] = x[s0 + tau + n] conj(s[n]) for the trial starts tau = -36, -30 .. +36 samples, x = 0 outside [0, n_have), and on the
+ * segment sums G_tau[j] = sum_{n < 36} y_tau[36 j + n], j < 1680:
+ *   score[tau][delta] = sum over the blocks of four symbols {1..4}, {5..8} .. {97..100}, {101..103} of |sum_{q in block} C[q]|^2,
+ *   C[q] = sum_{j < 16} G_tau[16 q + j] e^{-2 pi i delta (36 (16 q + j) + 17.5) / 12000}, delta = -6 .. +6 steps of 0.6510 Hz;
+ *   the first maximum in tau-major order, a three-point parabola on each axis where the peak is interior (FT8RX_RP_EDGE_T / _F
+ *   where it is not): t_sec = (s0 + tau + 6 dtau) / 12000, f_hz = fq 12000 / 4608 + delta, score = the maximum;
+ *   snr_db = 10 log10(max(on / off - 1, 1e-3) * 20.8333 / 2500) at the peak's tau and the interpolated delta over the valid symbols
+ *   (1 .. 103, their 576 samples wholly inside [0, n_have); fewer than 32: FT8RX_RP_INVALID and NaN fields): on = the mean |C[q]|^2,
+ *   off = the lower quartile c[(m - 1) / 4] / ln(4/3) * 576 / 216 of the m Hann-weighted cells (w[n] = 1/2 - 1/2 cos(2 pi (n + 1/2) /
+ *   576)) of the same samples at fq + 8 t, t = -5, -4, -3, 6, 7, 8, a frequency outside [8, 2296] dropped whole; off = 0 reads -50.79.
+ * d_audio: a device pointer to [n_frames][90000] int16 (ft8rx_ft4_staging_audio after an FT4 batch); it is only read.  sigs
+ * [n_frames][max_sigs] with counts [n_frames]; reports [n_frames][max_sigs]: FT8RX_RP_MEASURED on every measured slot, all zero from
+ * counts[frame] on.  scores (optional) [n_frames][max_sigs][169], on_off (optional) [n_frames][max_sigs][2]: the stages (NaN on_off
+ * with FT8RX_RP_INVALID).  Synchronous; a report is the same bytes alone or in a batch.  Refused by name before any launch: a tone
+ * above 3, fq outside [0, 4608), |start| above 2^20, n_have outside [576, 90000], max_sigs below 1.  The workspaces (0.95 MB per
+ * frame of max_frames) are allocated at the first call, all or nothing; the figures of ft8rx_ft4_info and ft8rx_ft4_sub_info do not
+ * include them. */
+int  ft8rx_ft4_report(ft8rx_handle* h, const int16_t* d_audio, int n_frames, const ft8rx_ft4_subsig* sigs, const int32_t* counts,
+                      int max_sigs, int n_have, ft8rx_report* reports, float* scores, float* on_off);
+/* bytes of FT4 report workspace the handle holds (0 until its first ft8rx_ft4_report) */
+int  ft8rx_ft4_report_info(ft8rx_handle* h, uint64_t* workspace_bytes);
 
 #ifdef __cplusplus
 }

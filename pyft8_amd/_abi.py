@@ -173,6 +173,8 @@ PROTOTYPES = {
     "ft8rx_ft4_staging_audio": (PTR, (PTR,)),
     "ft8rx_ft4_sub_info": (INT, (PTR, PTR)),
     "ft8rx_ft4_sub_probe": (INT, (PTR, PTR, INT, INT, PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_ft4_report": (INT, (PTR, PTR, INT, PTR, PTR, INT, INT, PTR, PTR, PTR)),
+    "ft8rx_ft4_report_info": (INT, (PTR, PTR)),
     # host message layer
     "ft8rx_package_batch": (INT, _RECS + (INT, INT) + _PKG),
     "ft8rx_package_batch_ext": (INT, _RECS + (INT, INT) + _PKG + (I32,)),

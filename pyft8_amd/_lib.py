@@ -929,6 +929,51 @@ class Handle:
                                               model.ctypes.data if want_model else None, bins.ctypes.data, en.ctypes.data), "ft8rx_ft4_sub_probe")
         return dict(bins=bins, energy=en, model=model)
 
+    def ft4_report_info(self):
+        """ft8rx_ft4_report_info -> dict(workspace_bytes): 0 until the handle's first ft4_report."""
+        wb = C.c_uint64()
+        self._chk(self._L.ft8rx_ft4_report_info(self._h, C.byref(wb)), "ft8rx_ft4_report_info")
+        return dict(workspace_bytes=int(wb.value))
+
+    def ft4_report(self, audio, sigs, n_have=FT4_NSAMP, stages=False):
+        """ft8rx_ft4_report: the measured reports (ft4.report is the twin) of decoded signals.  audio: a device
+        pointer to int16 frames [B, 90000] (ft4_staging_ptr after an FT4 batch), or a host array, which is uploaded.  sigs: (array
+        [B, max_sigs] of FT4_SUBSIG_DTYPE, counts [B]), or per frame a list of (start, fq, tones105).  Of each frame's samples only
+        the first n_have exist.  -> REPORT_DTYPE [B, max_sigs] (all zero from a frame's count on); stages: (reports, scores
+        [B, max_sigs, 13, 13], on_off [B, max_sigs, 2])."""
+        if isinstance(sigs, tuple):
+            arr, cnt = sigs
+            arr = np.ascontiguousarray(arr, FT4_SUBSIG_DTYPE)
+            cnt = np.ascontiguousarray(cnt, np.int32)
+        else:
+            arr = np.zeros((len(sigs), max(1, max((len(s) for s in sigs), default=1))), FT4_SUBSIG_DTYPE)
+            cnt = np.zeros(len(sigs), np.int32)
+            for f, lst in enumerate(sigs):
+                cnt[f] = len(lst)
+                for i, (start, fq, tones) in enumerate(lst):
+                    arr[f, i]["start"], arr[f, i]["fq"], arr[f, i]["tones"] = start, fq, np.asarray(tones, np.uint8)
+        if arr.ndim != 2 or len(cnt) != arr.shape[0]:
+            raise Ft8rxError("ft4_report: signals [n_frames][max_sigs] and one count per frame expected")
+        B, ms = arr.shape
+        keep = None
+        if isinstance(audio, (int, np.integer)):
+            ptr = int(audio)
+        else:
+            host = self._ft4_audio(audio, "ft4_report")
+            if len(host) != B:
+                raise Ft8rxError(f"ft4_report: {len(host)} frames for {B} rows of signals")
+            import torch
+            keep = torch.from_numpy(host if host.flags.writeable else host.copy()).to(f"cuda:{self.device}")
+            torch.cuda.synchronize(keep.device)
+            ptr = keep.data_ptr()
+        rep = np.zeros((B, ms), REPORT_DTYPE)
+        sc = np.zeros((B, ms, 13, 13), np.float32) if stages else None
+        oo = np.zeros((B, ms, 2), np.float32) if stages else None
+        self._chk(self._L.ft8rx_ft4_report(self._h, C.c_void_p(ptr), int(B), arr.ctypes.data, cnt.ctypes.data, int(ms), int(n_have), rep.ctypes.data,
+                                           sc.ctypes.data if stages else None, oo.ctypes.data if stages else None), "ft8rx_ft4_report")
+        del keep
+        return (rep, sc, oo) if stages else rep
+
     def download_audio_ft4(self, d_ptr, n_frames):
         out = np.empty((int(n_frames), FT4_NSAMP), np.int16)
         self._chk(self._L.ft8rx_copy_to_host(self._h, out.ctypes.data, C.c_void_p(d_ptr), out.nbytes), "ft8rx_copy_to_host")

@@ -72,6 +72,7 @@
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/ft4_sub.hpp"      // after subtract.hpp: it shares wave_sum2 and the int16 <-> float32 copies
+#include "kernels/ft4_report.hpp"   // after ft4_sub.hpp: it walks the subtraction's model
 #include "kernels/probes.hpp"
 #include "host_messages.hpp"
 #include "batch_plan.hpp"
@@ -330,6 +331,15 @@ struct ft8rx_handle {
         float* d_wf = nullptr; double2* d_part = nullptr; double* d_pc = nullptr; int32_t* d_best = nullptr; int32_t* d_cnt = nullptr;
         int32_t* d_frame = nullptr; double* d_energy = nullptr; ft8rx_ft4_subsig* d_sigs = nullptr;
     } ft4sub;
+    // FT4 measured reports (ft8rx_ft4_report, kernels/ft4_report.hpp; allocated at the first call,
+    // WS_FT4_REPORT): the float32 frames [max_frames][90000] (zero from n_have on), a pulse table of its own, and per row of a slab
+    // (one signal per row, FT4REP_ROWS x max_frames rows): the signal, its frame, a count of 1, the partial scores [26][169], the
+    // scores [169], the peak, the report and (on, off)
+    struct Ft4Rep {
+        size_t bytes = 0;
+        float* d_wf = nullptr; double* d_pc = nullptr; ft8rx_ft4_subsig* d_sigs = nullptr; int32_t* d_frame = nullptr; int32_t* d_one = nullptr;
+        float* d_part = nullptr; float* d_scores = nullptr; Ft4RepPeak* d_peak = nullptr; ft8rx_report* d_rep = nullptr; float* d_onoff = nullptr;
+    } ft4rep;
     // FT4 coherent LLRs (ft8rx_ft4_set_coherent, k_ft4_coh; allocated at the first FT4 batch that runs with the
     // setting on, WS_FT4_COH).  Per item of the failure list (at most max_frames << cand_shift): q, the nine metrics, the run-of-2 rows
     // and behind them the run-of-4 rows, BP's outputs and attempts for both, the list OSD gets, its counter and the page-locked copy
@@ -425,7 +435,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH, WS_FT4_REPORT };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3945,6 +3955,18 @@ int ft8rx_ft4_encode_tones(const uint64_t* msg_lo, const uint64_t* msg_hi, int n
 
 // ---- FT4 subtraction (kernels/ft4_sub.hpp)
 #define FT4SUB_MAXSIGS 256
+// the BT = 1.0 pulse over three symbols (ft4.py _gfsk_pulse) as its exclusive running sum, [FT4S_PC]
+static std::vector<double> ft4_pulse_sums() {
+    std::vector<double> pc(FT4S_PC);
+    const double k = M_PI * sqrt(2.0 / log(2.0));
+    double acc = 0.0;
+    for (int i = 0; i < FT4S_PC; i++) {
+        pc[i] = acc;
+        const double t = ((double)i - 1.5 * FT4_NSPS) / (double)FT4_NSPS;
+        acc += 0.5 * (erf(k * (t + 0.5)) - erf(k * (t - 0.5)));
+    }
+    return pc;
+}
 // Everything FT4 subtraction owns, at the first ft8rx_ft4_subtract / ft8rx_ft4_sub_probe on the handle, all or nothing
 static int ft4sub_workspaces(ft8rx_handle* h) {
     if (ws_ready(h, WS_FT4_SUB)) return 0;
@@ -3956,15 +3978,7 @@ static int ft4sub_workspaces(ft8rx_handle* h) {
     dev(&w.d_wf, mf * FT8RX_FT4_NSAMP); dev(&w.d_part, mf * FT4S_NT * FT4S_GRIDX * FT4S_NB); dev(&w.d_pc, (size_t)FT4S_PC);
     dev(&w.d_best, mf); dev(&w.d_cnt, mf); dev(&w.d_frame, mf); dev(&w.d_energy, mf * FT4S_NT); dev(&w.d_sigs, mf * FT4SUB_MAXSIGS);
     if (!F.rc) {
-        // the BT = 1.0 pulse over three symbols (ft4.py _gfsk_pulse) and its exclusive running sum
-        std::vector<double> pc(FT4S_PC);
-        const double k = M_PI * sqrt(2.0 / log(2.0));
-        double acc = 0.0;
-        for (int i = 0; i < FT4S_PC; i++) {
-            pc[i] = acc;
-            const double t = ((double)i - 1.5 * FT4_NSPS) / (double)FT4_NSPS;
-            acc += 0.5 * (erf(k * (t + 0.5)) - erf(k * (t - 0.5)));
-        }
+        const std::vector<double> pc = ft4_pulse_sums();
         FIRST_HIP(F, hipMemcpy(w.d_pc, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
         FIRST_HIP(F, hipMemset(w.d_best, 0, sizeof(int32_t) * mf));
     }
@@ -4078,6 +4092,103 @@ int ft8rx_ft4_sub_probe(ft8rx_handle* h, const int16_t* audio, int B, int n, con
             }
         }
     }
+    return 0;
+}
+
+// ---- FT4 measured reports (kernels/ft4_report.hpp)
+#define FT4REP_ROWS 32               /* rows of a slab per frame of max_frames */
+// Everything the FT4 reports own, at the first ft8rx_ft4_report on the handle, all or nothing
+static int ft4rep_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4_REPORT)) return 0;
+    ft8rx_handle::Ft4Rep& w = h->ft4rep;
+    const size_t mf = (size_t)h->max_frames, nr = mf * FT4REP_ROWS;
+    FirstUse F(h, WS_FT4_REPORT);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_wf, mf * FT8RX_FT4_NSAMP); dev(&w.d_pc, (size_t)FT4S_PC); dev(&w.d_sigs, nr); dev(&w.d_frame, nr); dev(&w.d_one, nr);
+    dev(&w.d_part, nr * FT4R_NBLK * FT4R_NP); dev(&w.d_scores, nr * FT4R_NP); dev(&w.d_peak, nr); dev(&w.d_rep, nr); dev(&w.d_onoff, nr * 2);
+    if (!F.rc) {
+        const std::vector<double> pc = ft4_pulse_sums();
+        const std::vector<int32_t> ones(nr, 1);
+        FIRST_HIP(F, hipMemcpy(w.d_pc, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(w.d_one, ones.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice));
+    }
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
+int ft8rx_ft4_report(ft8rx_handle* h, const int16_t* d_audio, int B, const ft8rx_ft4_subsig* sigs, const int32_t* counts, int max_sigs, int n_have,
+                     ft8rx_report* reports, float* scores, float* on_off) {
+    if (!h || !d_audio || !sigs || !counts || !reports) return -1;
+    if (B < 1 || B > h->max_frames) { set_err(h, "ft8rx_ft4_report: n_frames %d outside [1, %d]", B, h->max_frames); return -1; }
+    if (max_sigs < 1) { set_err(h, "ft8rx_ft4_report: max_sigs %d is below 1", max_sigs); return -1; }
+    if (n_have < FT4_NSPS || n_have > FT8RX_FT4_NSAMP) { set_err(h, "ft8rx_ft4_report: n_have %d outside [%d, %d]", n_have, FT4_NSPS, FT8RX_FT4_NSAMP); return -1; }
+    std::vector<int32_t> frame, slot;                                     // the live signals, one per row, in (frame, signal) order
+    for (int f = 0; f < B; f++) {
+        if (counts[f] < 0 || counts[f] > max_sigs) { set_err(h, "ft8rx_ft4_report: counts[%d] = %d outside [0, %d]", f, counts[f], max_sigs); return -1; }
+        for (int i = 0; i < counts[f]; i++) {
+            const ft8rx_ft4_subsig& g = sigs[(size_t)f * max_sigs + i];
+            for (int k = 0; k < FT4_NSYM; k++)
+                if (g.tones[k] > 3) { set_err(h, "ft8rx_ft4_report: signal %d of frame %d: tone %d of symbol %d is above 3", i, f, (int)g.tones[k], k); return -1; }
+            if (g.fq < 0 || g.fq >= 4608) { set_err(h, "ft8rx_ft4_report: signal %d of frame %d: fq %d outside [0, 4608)", i, f, g.fq); return -1; }
+            if (g.start < -(1 << 20) || g.start > (1 << 20)) { set_err(h, "ft8rx_ft4_report: signal %d of frame %d: |start| %d above 2^20", i, f, g.start); return -1; }
+            frame.push_back(f); slot.push_back(f * max_sigs + i);
+        }
+    }
+    ENTER(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (const int rc = ft4rep_workspaces(h)) return rc;
+    const ft8rx_handle::Ft4Rep& w = h->ft4rep;
+    hipStream_t s = h->stream;
+    const size_t total = (size_t)B * max_sigs;
+    memset(reports, 0, sizeof(ft8rx_report) * total);
+    if (scores) memset(scores, 0, sizeof(float) * total * FT4R_NP);
+    if (on_off) memset(on_off, 0, sizeof(float) * total * 2);
+    // profiling (ft8rx_set_profiling): the stages of the first slab, read like a batch's after ft8rx_sync
+    h->pnames.clear();
+    const bool prof = h->profiling;
+    bool first = true;
+#define STAGE(name) do { if (prof && first) { hipEventRecord(h->pev[h->pnames.size()], s); h->pnames.push_back(name); } } while (0)
+    STAGE("ft4_rep_f32");
+    k_ft4_rep_f32<<<dim3((FT8RX_FT4_NSAMP + 255) / 256, B), 256, 0, s>>>(d_audio, w.d_wf, n_have);
+    const size_t cap = (size_t)h->max_frames * FT4REP_ROWS, n = frame.size();
+    std::vector<ft8rx_ft4_subsig> slab(cap);
+    std::vector<ft8rx_report> rp(cap);
+    std::vector<float> sc(scores ? cap * FT4R_NP : 0), oo(on_off ? cap * 2 : 0);
+    const Ft4SubSel sel{w.d_sigs, w.d_one, w.d_frame, 1, 0};
+    for (size_t i0 = 0; i0 < n; i0 += cap) {
+        const int rows = (int)(n - i0 < cap ? n - i0 : cap);
+        for (int r = 0; r < rows; r++) slab[r] = sigs[slot[i0 + r]];
+        HIPCHK(h, hipMemcpyAsync(w.d_sigs, slab.data(), sizeof(ft8rx_ft4_subsig) * rows, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(w.d_frame, frame.data() + i0, sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
+        STAGE("ft4_rep_scan");
+        k_ft4_rep_scan<<<dim3(FT4R_NBLK / 2, rows), 128, 0, s>>>(w.d_wf, sel, w.d_pc, w.d_part);
+        STAGE("ft4_rep_pick");
+        k_ft4_rep_pick<<<rows, 64, 0, s>>>(sel, w.d_part, w.d_scores, w.d_peak);
+        STAGE("ft4_rep_snr");
+        k_ft4_rep_snr<<<rows, 256, 0, s>>>(w.d_wf, sel, w.d_pc, w.d_peak, n_have, w.d_rep, w.d_onoff);
+        if (prof && first) hipEventRecord(h->pev[h->pnames.size()], s);
+        first = false;
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(rp.data(), w.d_rep, sizeof(ft8rx_report) * rows, hipMemcpyDeviceToHost, s));
+        if (scores) HIPCHK(h, hipMemcpyAsync(sc.data(), w.d_scores, sizeof(float) * (size_t)rows * FT4R_NP, hipMemcpyDeviceToHost, s));
+        if (on_off) HIPCHK(h, hipMemcpyAsync(oo.data(), w.d_onoff, sizeof(float) * (size_t)rows * 2, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (int r = 0; r < rows; r++) {
+            const size_t o = (size_t)slot[i0 + r];
+            reports[o] = rp[r];
+            if (scores) memcpy(scores + o * FT4R_NP, sc.data() + (size_t)r * FT4R_NP, sizeof(float) * FT4R_NP);
+            if (on_off) { on_off[2 * o] = oo[2 * (size_t)r]; on_off[2 * o + 1] = oo[2 * (size_t)r + 1]; }
+        }
+    }
+    if (prof && first) hipEventRecord(h->pev[h->pnames.size()], s);      // no signal at all: the conversion is the only stage
+#undef STAGE
+    HIPCHK(h, hipStreamSynchronize(s));
+    return 0;
+}
+int ft8rx_ft4_report_info(ft8rx_handle* h, uint64_t* workspace_bytes) {
+    if (!h || !workspace_bytes) return -1;
+    *workspace_bytes = ws_ready(h, WS_FT4_REPORT) ? (uint64_t)h->ft4rep.bytes : 0;
     return 0;
 }
 

@@ -38,6 +38,8 @@ L = 1 is demod's LLRs again (tests/test_ft4_coherent.py holds it to 1e-12).
 The twin also defines the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/test_gpu_ft4_sub.py; stated in full where sub_model stands, below):
   model    the complex form of tones_to_wave; bins: 41 bins (+-3.97 Hz) of the 60480-point transform of x conj(model); refine: the
            bins' energy at 13 starts 4 samples apart, the first maximum; subtract: x -= 2 Re(a model), a = the bins' inverse transform
+and, opt-in, the measured reports (csrc/kernels/ft4_report.hpp, tests/test_gpu_ft4_report.py; stated in full where report stands, below;
+DESIGN.md section 19.9): a decoded signal against the same model on a 13 x 13 map of starts and frequencies -> SNR, frequency, time
 """
 import numpy as np
 
@@ -384,10 +386,11 @@ def slot_parity(cyclestart_string):
     return int(sec // 7.5) % 2
 
 
-def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None, nsym=None):
+def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None, nsym=None, reports=None):
     """Rows of the native packager (ft8rx_package_batch / _ext on FT4 records) -> message dicts with the keys of the FT8 ones and FT4's
     values: tsec = (144 h0 + 36 tt) / 12000, fHz = 10.41667 f0 + 2.60417 ft, "mode": "FT4", '+' in all_txt_format, their_tx_cycle =
-    the slot's parity.  nsym (a receiver with ft4_coherent): per row the run length of its decode -> "nsym": 1, 2 or 4."""
+    the slot's parity.  nsym (a receiver with ft4_coherent): per row the run length of its decode -> "nsym": 1, 2 or 4.  reports (a
+    receiver with ft4_reports; REPORT_DTYPE rows, one per message): "report": {"snr", "fHz", "tsec"}, or None where it is INVALID."""
     import time
     from . import messages as _m
     out = []
@@ -412,6 +415,10 @@ def message_dicts(msgs, count, cyclestart_string="", band=None, on_message=None,
             d["msg_type"] = _m.msg_type(word_type)
         if nsym is not None:
             d["nsym"] = int(nsym[k])
+        if reports is not None:
+            p = reports[k]
+            ok = (int(p["flags"]) & (RP_MEASURED | RP_INVALID)) == RP_MEASURED
+            d["report"] = {"snr": float(p["snr_db"]), "fHz": float(p["f_hz"]), "tsec": float(p["t_sec"])} if ok else None
         out.append(d)
         if on_message is not None:
             on_message(d)
@@ -616,4 +623,103 @@ def decode_twin_passes(x, passes=2, max_cands=200, sync_min=SYNC_MIN_DEFAULT, re
         for sg in fresh:
             have.add(sg["word"])
             out.append({"start": sg["start"], "fq": sg["fq"], "word": sg["word"], "pass": p + 1})
+    return out
+
+
+# ----------------------------------------------------------------------------- the twin: measured reports (csrc/kernels/ft4_report.hpp)
+# Once a signal has decoded its 105 tones are known, and it can be measured against its own model.  With the
+# model s = sub_model(tones, fq), trial starts s0 + tau (tau = -36, -30 .. 36) and y_tau[n] = x[s0 + tau + n] conj(s[n]) (x = 0
+# outside [0, n_have)), everything is defined on the segment sums G_tau[j] = sum_{n < 36} y_tau[36 j + n], j < 1680:
+#   score    C_tau,delta[q] = sum_{j < 16} G_tau[16 q + j] e^{-2 pi i delta (36 (16 q + j) + 17.5) / 12000}, delta = -6 .. 6 steps of
+#            0.6510 Hz; P(tau, delta) = sum over the blocks {1..4}, {5..8} .. {97..100}, {101..103} of |sum_{q in block} C[q]|^2
+#   peak     the first maximum in tau-major order; a three-point parabola on each axis where the peak is interior (a zero denominator
+#            gives 0), else RP_EDGE_T / RP_EDGE_F; t_sec = (s0 + tau + 6 dt) / 12000, f_hz = fq 12000 / 4608 + delta, score = P there
+#   SNR      at the peak's tau and the interpolated delta, over the valid symbols (q = 1 .. 103 whose 576 samples lie inside
+#            [0, n_have); fewer than RP_MIN_VALID: RP_INVALID, NaN fields): on = mean |C[q]|^2; off = the lower quartile of the
+#            Hann-weighted cells of the same samples at fq + 8 t, t in RP_CELLS (a frequency outside [8, 2296] is dropped whole),
+#            c[(m - 1) // 4] / ln(4 / 3) x 576 / 216; snr_db = 10 log10(max(on / off - 1, 1e-3) x 20.8333 / 2500), off = 0: the floor
+RP_MEASURED, RP_INVALID, RP_EDGE_T, RP_EDGE_F = 1, 2, 4, 8            # FT8RX_RP_*
+RP_TAUS = tuple(range(-36, 37, 6))     # the 13 trial starts, samples
+RP_DELTAS = tuple(range(-6, 7))        # the 13 trial frequencies, x RP_DELTA_HZ
+RP_DELTA_HZ = FS / 4608 / 4            # 0.6510 Hz: k_ft4_coh's step
+RP_SEG = 36                            # samples per segment sum: 16 segments per symbol
+RP_BLOCK = 4                           # symbols summed coherently
+RP_CELLS = (-5, -4, -3, 6, 7, 8)       # the noise cells, in tones from tone 0
+RP_FQ_LO, RP_FQ_HI = 8, 2296           # a cell frequency outside (x 2.6042 Hz) is dropped
+RP_MIN_VALID = 32
+RP_SNR_FLOOR = 1e-3
+RP_HANN_SUM2 = 216.0                   # sum w^2 of w[n] = 1/2 - 1/2 cos(2 pi (n + 1/2) / 576)
+
+
+def report_segments(x, s0, model, n_have=NFRAME):
+    """G_tau[1680] of y[n] = x[s0 + n] conj(model[n]), x = 0 outside [0, n_have)."""
+    x = np.asarray(x, np.float64)[:int(n_have)]
+    w, _ = _sub_window(x, s0, len(model))
+    return (w * np.conj(model)).reshape(-1, RP_SEG).sum(axis=1)
+
+
+def report_symbols(G, delta_steps):
+    """C[105] of the segment sums at the frequency offset delta_steps x 0.6510 Hz (a float: the interpolated peak)."""
+    j = np.arange(len(G))
+    ph = np.exp(-2j * np.pi * (float(delta_steps) * RP_DELTA_HZ) * (RP_SEG * j + 17.5) / FS)
+    return (G * ph).reshape(NSYM, NSPS // RP_SEG).sum(axis=1)
+
+
+def report_score(C):
+    """P of one (tau, delta): symbols 1 .. 103 in blocks of four from symbol 1 on, coherent inside a block."""
+    return float(sum(abs(C[a:min(a + RP_BLOCK, NSYM - 1)].sum()) ** 2 for a in range(1, NSYM - 1, RP_BLOCK)))
+
+
+def _parabola(a, b, c):
+    den = a - 2.0 * b + c
+    return 0.5 * (a - c) / den if den != 0.0 else 0.0
+
+
+def report(x, sig, n_have=NFRAME, full=False):
+    """The measured report of one decoded signal (sig_from_record's dict) on the frame x -> dict(flags, snr_db, f_hz, t_sec, score; the
+    four are NaN with RP_INVALID), and the stages: scores [13][13], on, off, tau, delta (steps, interpolated), n_valid; full: also
+    cells, the sorted cell powers."""
+    x = np.asarray(x, np.float64)
+    n_have = int(n_have)
+    s0, fq = int(sig["start"]), int(sig["fq"])
+    model = sub_model(sig["tones"], fq)
+    G = [report_segments(x, s0 + tau, model, n_have) for tau in RP_TAUS]
+    P = np.array([[report_score(report_symbols(g, d)) for d in RP_DELTAS] for g in G])
+    k = int(np.argmax(P))                                                  # the first maximum in tau-major order
+    it, idl = divmod(k, len(RP_DELTAS))
+    flags, dt, dd = RP_MEASURED, 0.0, 0.0
+    if 0 < it < len(RP_TAUS) - 1:
+        dt = _parabola(P[it - 1, idl], P[it, idl], P[it + 1, idl])
+    else:
+        flags |= RP_EDGE_T
+    if 0 < idl < len(RP_DELTAS) - 1:
+        dd = _parabola(P[it, idl - 1], P[it, idl], P[it, idl + 1])
+    else:
+        flags |= RP_EDGE_F
+    tau, delta = RP_TAUS[it], RP_DELTAS[idl] + dd
+    out = dict(scores=P, tau=tau, delta=delta, score=float(P[it, idl]))
+    starts = s0 + tau + NSPS * np.arange(NSYM)
+    valid = [q for q in range(1, NSYM - 1) if starts[q] >= 0 and starts[q] + NSPS <= n_have]
+    out["n_valid"] = len(valid)
+    if len(valid) < RP_MIN_VALID:
+        nan = float("nan")
+        out.update(flags=RP_MEASURED | RP_INVALID, snr_db=nan, f_hz=nan, t_sec=nan, score=nan, on=nan, off=nan)
+        if full:
+            out["cells"] = np.zeros(0)
+        return out
+    C = report_symbols(G[it], delta)
+    on = float(np.mean(np.abs(C[valid]) ** 2))
+    fr = [fq + 8 * t for t in RP_CELLS if RP_FQ_LO <= fq + 8 * t <= RP_FQ_HI]
+    off, cells = 0.0, np.zeros(0)
+    if fr:
+        hw = 0.5 - 0.5 * np.cos(2.0 * np.pi * (_N + 0.5) / NSPS)
+        V = _symbols(x[:n_have], starts[valid]) * hw[None, :]
+        H = V @ _phasors(fr).T
+        cells = np.sort((H.real ** 2 + H.imag ** 2).reshape(-1))
+        off = float(cells[(len(cells) - 1) // 4] / np.log(4.0 / 3.0) * NSPS / RP_HANN_SUM2)
+    ratio = on / off - 1.0 if off > 0 else RP_SNR_FLOOR
+    out.update(flags=flags, on=on, off=off, snr_db=float(10.0 * np.log10(max(ratio, RP_SNR_FLOOR) * TONE_HZ / 2500.0)),
+               f_hz=fq * DF_HZ + delta * RP_DELTA_HZ, t_sec=(s0 + tau + 6.0 * dt) / FS)
+    if full:
+        out["cells"] = cells
     return out

@@ -745,6 +745,12 @@ class Receiver:
         if not isinstance(self.ft4_coherent, (bool, np.bool_)):
             raise _lib.Ft8rxError(f"ft4_coherent must be True or False, got {self.ft4_coherent!r}")
         self.ft4_coherent = bool(self.ft4_coherent)
+        # ft4_reports (section 19.9): every FT4 message is measured against its own model on the audio its pass decoded (SNR,
+        # frequency, start time) and its dict gains "report".  An FT4 knob of the receiver, not a row of the opt-in table.
+        self.ft4_reports = extension_knobs.pop("ft4_reports", False)
+        if not isinstance(self.ft4_reports, (bool, np.bool_)):
+            raise _lib.Ft8rxError(f"ft4_reports must be True or False, got {self.ft4_reports!r}")
+        self.ft4_reports = bool(self.ft4_reports)
         # live FT4 (section 19.7; modes= here or in start()): the early passes of a 7.5-s slot, seconds into it -- one at 6.0 s (72000
         # samples) by default, () = only the complete slot
         self.ft4_early_samples = _wide_in.ft4_early_samples(extension_knobs.pop("ft4_early_decode_s", _wide_in.FT4_EARLY_S_DEFAULT))
@@ -1281,7 +1287,9 @@ class Receiver:
         ft4_osd_max_hd; a fresh call-hash table per frame (and per pass).  The receiver's ft4_passes = 2 or 3 (section 19.6): the decoded
         signals are subtracted on the device and the residual is decoded again; the later passes' messages follow pass 1's, "_SUB" in
         their decode_notes, and the records returned are the last pass's.  The receiver's ft4_coherent=True (section 19.8): what BP
-        leaves undecoded is decoded again on LLRs over runs of two and four symbols, and every dict says "nsym": 1, 2 or 4.  Refused, by name: a-priori calls, recall, weak, reports,
+        leaves undecoded is decoded again on LLRs over runs of two and four symbols, and every dict says "nsym": 1, 2 or 4.  The
+        receiver's ft4_reports=True (section 19.9): every dict carries "report": {"snr", "fHz", "tsec"} measured on the audio its pass
+        decoded (None where it could not be measured).  Refused, by name: a-priori calls, recall, weak, reports,
         the packed output, the per-call passes > 1 and float frames."""
         if (self.float_frames if float_frames is None else bool(float_frames)):
             raise _lib.Ft8rxError("FT4 decoding (decode_frames_ft4) is not supported together with float_frames=True: FT4 frames are int16")
@@ -1300,14 +1308,42 @@ class Receiver:
             res = h.ft4_decode(audio)
             msgs, mcnt = self._package(res)
             cs = [cyclestart_strings[f] if cyclestart_strings is not None else "700101_000000" for f in range(B)]
+            rp = self._ft4_measure(h, B, res[0], msgs, mcnt)
             if self.ft4_passes > 1:                                  # the later passes need the handle: the dicts are made under its lock
                 out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message,
-                                          nsym=self._ft4_nsym(res[0], msgs, mcnt, f)) for f in range(B)]
+                                          nsym=self._ft4_nsym(res[0], msgs, mcnt, f), **self._ft4_rp(rp, f)) for f in range(B)]
                 res = self._later_passes_ft4(h, B, res, msgs, mcnt, out, cs, gate)
                 return (out, res[0], res[1]) if return_records else out
         out = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band, on_message=self.on_message,
-                                  nsym=self._ft4_nsym(res[0], msgs, mcnt, f)) for f in range(B)]
+                                  nsym=self._ft4_nsym(res[0], msgs, mcnt, f), **self._ft4_rp(rp, f)) for f in range(B)]
         return (out, res[0], res[1]) if return_records else out
+
+    def _ft4_measure(self, h, B, rec, msgs, mcnt, n_have=_lib.FT4_NSAMP):
+        """ft4_reports: the measured reports (Handle.ft4_report) of the packaged messages of a batch whose frames
+        lie in the handle's FT4 buffer (the caller holds its lock), of which the first n_have samples exist: one signal per message,
+        from the record its row names -> per frame the REPORT_DTYPE rows, message by message; None with the setting off: nothing is
+        called"""
+        if not self.ft4_reports:
+            return None
+        n = [min(int(mcnt[f]), len(msgs[f])) for f in range(B)]
+        sigs = np.zeros((B, max(1, max(n))), _lib.FT4_SUBSIG_DTYPE)
+        rows = [rec[f][msgs[f]["cand"][:n[f]]] for f in range(B)]
+        tones = _lib.ft4_encode_tones(np.concatenate([r["msg_lo"] for r in rows]), np.concatenate([r["msg_hi"] for r in rows]))
+        at = 0
+        for f, r in enumerate(rows):
+            sigs[f, :n[f]]["start"] = _ft4.HOP * r["h0_idx"].astype(np.int32) + _ft4.DT_STEP * r["ttweak"].astype(np.int32)
+            sigs[f, :n[f]]["fq"] = 4 * r["f0_idx"].astype(np.int32) + r["ftweak"].astype(np.int32)
+            sigs[f, :n[f]]["tones"] = tones[at:at + n[f]]
+            at += n[f]
+        if not at:
+            return [np.zeros(0, _lib.REPORT_DTYPE) for _ in range(B)]
+        out = h.ft4_report(h.ft4_staging_ptr(), (sigs, np.asarray(n, np.int32)), n_have=n_have)
+        return [out[f, :n[f]] for f in range(B)]
+
+    @staticmethod
+    def _ft4_rp(rp, f):
+        """message_dicts' reports= of frame f; no keyword at all with the setting off"""
+        return {} if rp is None else {"reports": rp[f]}
 
     def _ft4_set(self, h):
         """The receiver's FT4 knobs and search range on handle h (the caller holds its lock) -> the OSD gate in force"""
@@ -1364,10 +1400,11 @@ class Receiver:
                 h.ft4_enqueue(staging, B)
                 res = h.fetch(B)
                 msgs, mcnt = self._package(res, **pkg_kw)
+                rp = self._ft4_measure(h, B, res[0], msgs, mcnt)                       # on the residual this pass decoded
                 for f in range(B):
                     words = self._ft4_words(res[0], msgs, mcnt, f)
                     for d, w in zip(_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=self.band if bands is None else bands[f],
-                                                       nsym=self._ft4_nsym(res[0], msgs, mcnt, f)), words):
+                                                       nsym=self._ft4_nsym(res[0], msgs, mcnt, f), **self._ft4_rp(rp, f)), words):
                         if w in have[f]:
                             continue
                         have[f].add(w)
@@ -1474,10 +1511,13 @@ class Receiver:
             h.ddc_stream_frames(m_first, n_have, _lib.FT4_NSAMP, ch)
             h.ft4_enqueue(h.ft4_staging_ptr(), B)
             res = h.fetch(B)
-            if not early and self.ft4_passes > 1:                    # the later passes need the handle: packaged under its lock
+            later = not early and self.ft4_passes > 1
+            if later or self.ft4_reports:                            # the later passes and the reports need the handle: packaged under its lock
                 msgs, mcnt = self._package(res, **pkg)
-                dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f], nsym=self._ft4_nsym(res[0], msgs, mcnt, f))
-                         for f in range(B)]
+                rp = self._ft4_measure(h, B, res[0], msgs, mcnt, n_have=n_have)       # an early pass: on the samples received
+                dicts = [_ft4.message_dicts(msgs[f], mcnt[f], cyclestart_string=cs[f], band=bands[f], nsym=self._ft4_nsym(res[0], msgs, mcnt, f),
+                                            **self._ft4_rp(rp, f)) for f in range(B)]
+            if later:
                 self._later_passes_ft4(h, B, res, msgs, mcnt, dicts, cs, gate, bands=bands, notify=False, **pkg)
         if dicts is None:                                            # the host message layer runs outside _live_lock
             msgs, mcnt = self._package(res, **pkg)
@@ -1542,7 +1582,8 @@ def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=
 
 def decode_frames_ft4(audio_i16, on_message=None, **receiver_kwargs):
     """decode_frames_ft4(audio_i16[B, 90000], **receiver_kwargs) -> list[list[message dict]]: Receiver.decode_frames_ft4 on a receiver
-    of its own (FT4); ft4_passes=, ft4_coherent= and the other FT4 knobs go to Receiver with the keyword arguments."""
+    of its own (FT4); ft4_passes=, ft4_coherent=, ft4_reports= and the other FT4 knobs go to Receiver with the keyword
+    arguments."""
     audio = np.ascontiguousarray(audio_i16, np.int16)
     rx = Receiver("", on_message, max_frames=max(1, audio.shape[0] if audio.ndim == 2 else 1), **receiver_kwargs)
     try:

@@ -1,6 +1,7 @@
 """FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
 
     python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes] [--coherent]
+    python tools/ft4_measure.py --reports [--reports-twin] [--out profiles/ft4_report_measure.json]
 
 --prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
               apart, starts 0.1 .. 1.5 s), through Handle.ft4_decode and the native message layer; the 50 % point by interpolation
@@ -14,6 +15,11 @@
               probability at -19 .. -12 dB (the recipe of --prob) with the decodes by run length; false decodes on the 2048 noise frames
               at the default gates (40 at msg_types 0, 24 at all); frames/s at B = 256 with 20 signals per frame (device-resident), the
               stage times and the length of the list the coherent step works on
+--reports     measured reports (section 19.9) -> profiles/ft4_report_measure.json: the accuracy recipe make_frame(i, n_signals=8, snr_range=
+              (-14, 15), min_sep_hz=250) against truth, frames 16 .. 79 through Receiver(ft4_reports=True) with the default fields of the
+              same messages beside it; the report stage timed with HIP events (ft8rx_set_profiling) at B = 256 with 20 signals per frame;
+              decode_frames_ft4 with the setting off and on in paired alternating runs
+--reports-twin  no GPU: frames 0 .. 15 of the same recipe through decode_twin and the twin's report, into the same file
 --twin N      no GPU: the yardstick, the float64 twin with the numpy BP on N signals per step of -18 .. -11 dB (the same recipe)
 Results are merged into the file's existing sections."""
 import argparse
@@ -272,13 +278,129 @@ def measure_passes(B=256, first=1000):
     return out
 
 
+REPORT_RECIPE = dict(n_signals=8, snr_range=(-14, 15), min_sep_hz=250, return_truth=True)
+
+
+def report_recipe_frames(indices):
+    """-> [(index, frame, truth)] and the indices where eight carriers 250 Hz apart do not fit make_frame's default band"""
+    made, missing = [], []
+    for i in indices:
+        try:
+            x, truth = ft4.make_frame(i, **REPORT_RECIPE)
+            made.append((i, x, truth))
+        except ValueError:
+            missing.append(i)
+    return made, missing
+
+
+def report_stats(rows):
+    """rows of (truth snr, snr error dB, frequency error Hz, time error ms)"""
+    e = np.asarray(rows, np.float64).reshape(-1, 4)
+    out = {}
+    for name, m in (("snr_le_0", e[:, 0] <= 0.0), ("snr_gt_0", e[:, 0] > 0.0), ("all", np.ones(len(e), bool))):
+        v = e[m]
+        if not len(v):
+            continue
+        out[name] = {"decodes": int(len(v)),
+                     "snr_db": {"mean": float(v[:, 1].mean()), "rms": float(np.sqrt((v[:, 1] ** 2).mean())), "worst": float(np.abs(v[:, 1]).max())},
+                     "f_hz": {"mean": float(v[:, 2].mean()), "rms": float(np.sqrt((v[:, 2] ** 2).mean())), "worst": float(np.abs(v[:, 2]).max())},
+                     "t_ms": {"mean": float(v[:, 3].mean()), "std": float(v[:, 3].std()), "worst": float(np.abs(v[:, 3]).max())}}
+    return out
+
+
+def measure_reports_twin(indices=range(0, 16)):
+    made, missing = report_recipe_frames(indices)
+    rows, default, edge = [], [], 0
+    for i, x, truth in made:
+        by_word, seen = {t["word"]: t for t in truth}, set()
+        for r in ft4.decode_twin(x):
+            t = by_word.get(r["word"])
+            if t is None or r["word"] in seen:
+                continue
+            seen.add(r["word"])
+            p = ft4.report(x, ft4.sig_from_record(r["f0"], r["h0"], r["tt"], r["ft"], r["word"]))
+            edge += bool(p["flags"] & (ft4.RP_EDGE_T | ft4.RP_EDGE_F))
+            rows.append((t["snr"], p["snr_db"] - t["snr"], p["f_hz"] - t["f0"], 1e3 * (p["t_sec"] - t["t0"])))
+            default.append((t["snr"], r["snr"] - t["snr"], ft4.BIN_HZ * r["f0"] + ft4.DF_HZ * r["ft"] - t["f0"],
+                            1e3 * ((ft4.HOP * r["h0"] + ft4.DT_STEP * r["tt"]) / ft4.FS - t["t0"])))
+        print(f"reports twin frame {i}: {len(rows)} decodes so far", flush=True)
+    return {"frames": [m[0] for m in made], "no_frame_at": missing, "planted": 8 * len(made), "on_a_border": edge,
+            "report": report_stats(rows), "default_fields": report_stats(default)}
+
+
+def measure_reports(B=256, warmup=2, steps=5, pairs=6):
+    import torch
+    from pyft8_amd import _lib
+    from pyft8_amd.receiver import Receiver
+    out = {}
+    # ---- accuracy: frames 16 .. 79 through the receiver
+    made, missing = report_recipe_frames(range(16, 80))
+    audio = np.stack([m[1] for m in made])
+    rx = Receiver("", None, max_frames=len(made), ft4_reports=True)
+    res = rx.decode_frames_ft4(audio)
+    rx.close()
+    rows, default, edge, invalid = [], [], 0, 0
+    for (i, _, truth), dicts in zip(made, res):
+        by_text = {t["msg"]: t for t in truth}
+        for d in dicts:
+            t = by_text.get(" ".join(x for x in d["msg_tuple"] if x))
+            if t is None:
+                continue
+            if d["report"] is None:
+                invalid += 1
+                continue
+            rows.append((t["snr"], d["report"]["snr"] - t["snr"], d["report"]["fHz"] - t["f0"], 1e3 * (d["report"]["tsec"] - t["t0"])))
+            default.append((t["snr"], int(d["their_snr"]) - t["snr"], d["fHz"] - t["f0"], 1e3 * (d["tsec"] - t["t0"])))
+    out["accuracy_gpu"] = {"frames": [m[0] for m in made], "no_frame_at": missing, "planted": 8 * len(made), "invalid": invalid,
+                           "report": report_stats(rows), "default_fields": report_stats(default)}
+    print("reports accuracy", out["accuracy_gpu"]["report"], flush=True)
+    # ---- the report stage at B = 256 with 20 signals per frame: its kernels by HIP events, the whole synchronous call by the clock
+    a = np.stack([throughput_frame(k) for k in range(B)])
+    h = _lib.Handle(max_frames=B)
+    rec, cnt = h.ft4_decode(a)[:2]
+    sigs = _lib.ft4_subtraction_list(rec, cnt)
+    ptr = h.ft4_staging_ptr()
+    for _ in range(warmup):
+        h.ft4_report(ptr, sigs)
+    t = []
+    for _ in range(steps):
+        t0 = time.perf_counter(); h.ft4_report(ptr, sigs); t.append(round(1e3 * (time.perf_counter() - t0), 3))
+    h.set_profiling(True)
+    stage = []
+    for _ in range(steps):
+        h.ft4_report(ptr, sigs); h.sync()
+        stage.append({k: round(float(v), 4) for k, v in h.stage_times().items()})
+    h.set_profiling(False)
+    out["stage"] = {"B": B, "signals": int(sigs[1].sum()), "longest_list": int(sigs[1].max()), "call_ms": t, "kernel_ms": stage,
+                    "workspace_bytes": h.ft4_report_info()["workspace_bytes"]}
+    h.close()
+    print("reports stage", out["stage"], flush=True)
+    # ---- decode_frames_ft4 with the setting off and on, paired and alternating
+    rxs = {"off": Receiver("", None, max_frames=B), "on": Receiver("", None, max_frames=B, ft4_reports=True)}
+    for r in rxs.values():
+        r.decode_frames_ft4(a)
+    tt = {"off": [], "on": []}
+    for _ in range(pairs):
+        for name in ("off", "on"):
+            t0 = time.perf_counter(); rxs[name].decode_frames_ft4(a); tt[name].append(round(1e3 * (time.perf_counter() - t0), 3))
+    for r in rxs.values():
+        r.close()
+    out["receiver"] = {"B": B, "signals_per_frame": 20, "decode_frames_ft4_ms": tt,
+                       "frames_per_s": {k: B / (1e-3 * float(np.median(v))) for k, v in tt.items()}}
+    print("reports receiver", out["receiver"], flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ft4_measure.json"))
     ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
     ap.add_argument("--twin", type=int, default=0); ap.add_argument("--passes", action="store_true")
     ap.add_argument("--noise-frames", type=int, default=2048); ap.add_argument("--coherent", action="store_true")
+    ap.add_argument("--reports", action="store_true"); ap.add_argument("--reports-twin", action="store_true")
     args = ap.parse_args()
+    if (args.reports or args.reports_twin) and args.out == ap.get_default("out"):
+        args.out = os.path.join(ROOT, "profiles", "ft4_report_measure.json")
     res = json.load(open(args.out)) if os.path.exists(args.out) else {}
     if args.twin:
         res["twin_probability"] = measure_twin(args.twin)
@@ -298,6 +420,11 @@ if __name__ == "__main__":
     if args.passes:
         import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
         res["passes"] = measure_passes()
+    if args.reports_twin:
+        res["accuracy_twin"] = measure_reports_twin()
+    if args.reports:
+        import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
+        res.update(measure_reports())
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     json.dump(res, open(args.out, "w"), indent=1)
     print("wrote", args.out)
