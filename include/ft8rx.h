@@ -57,9 +57,11 @@
  *     ft8rx_ft4_subtract  ft8rx_ft4_subtraction_list  ft8rx_ft4_sub_info  ft8rx_ft4_staging_audio  ft8rx_ft4_encode_tones   (opt-in FT4, 7.5-s frames)
  *     ft8rx_ft4_report  ft8rx_ft4_report_info                                         (opt-in measured SNR / frequency / time of FT4 decodes)
  *     ft8rx_ft4_set_coherent  ft8rx_ft4_coh_info                                       (opt-in FT4 coherent LLRs: runs of two and four symbols)
+ *     ft8rx_ft4_set_weak  ft8rx_ft4_weak_info                                          (opt-in FT4 weak search: coherent Costas sync, 2.6-Hz grid)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
+ *     ft8rx_ft4_sync_weak
  *     ft8rx_ft4_grid  ft8rx_ft4_sync  ft8rx_ft4_demod  ft8rx_ft4_coherent  ft8rx_ft4_ldpc  ft8rx_ft4_osd  ft8rx_ft4_sub_probe
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
  *
@@ -982,6 +984,7 @@ int  ft8rx_math_probe(ft8rx_handle* h, int which, const float* x, int n, float* 
 #define FT8RX_FT4_ROWS  618
 #define FT8RX_FT4_COLS  577
 #define FT8RX_FT4_SYNC_MIN_DEFAULT   100.0f
+#define FT8RX_FT4_WEAK_MIN_DEFAULT   16.17f  /* the weak search's threshold: as many noise candidates as sync_min = 100 (section 19.10) */
 #define FT8RX_FT4_OSD_MAX_HD_DEFAULT 40      /* the largest gate without a false decode on 2048 noise frames (profiles/ft4_notes.md) */
 /* host int16 [n_frames][90000] -> records [n_frames][max_cands], counts, events [n_frames][FT8RX_EVENT_CAP], event_counts */
 int  ft8rx_ft4_decode_batch(ft8rx_handle* h, const int16_t* audio, int n_frames, ft8rx_record* records, int32_t* counts,
@@ -1023,6 +1026,24 @@ int  ft8rx_ft4_coh_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on)
 int  ft8rx_ft4_coherent(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
                         const int32_t* h0_idx, const int32_t* ttweak, const int32_t* ftweak, int32_t* q, float* metrics, float* llr2,
                         float* llr4);
+/* Weak search (opt-in; k_ft4_cgrid, k_ft4_csync; the twin is ft4.search_weak).  on != 0: every FT4 batch
+ * enqueued afterwards finds its candidates by a coherent Costas sync on the 2.6042-Hz grid instead of the dB grid's search: per row
+ * (12 ms) and carrier fq (x 12000 / 4608 Hz) the complex 576-sample sums of the four tones, the carrier's phase referred to sample 0 of
+ * the frame; per (fq, h) the four Costas blocks' sums B_b, added as complex numbers inside a block, and
+ *   score = (|B_0| + |B_1| + |B_2| + |B_3|) / sqrt(N),  N = the mean |sum|^2 over the 16 sync symbols and the 4 tones  (0 .. 32);
+ * per bin f0 the first maximum over fq = 4 f0 - 2 .. 4 f0 + 1 and the h0 range.  The bins at or above weak_min (<= 0: the default)
+ * that no neighbour beats are the candidates -- the same (f0_idx, h0_idx, score) records, max_cands, range and order as without it;
+ * everything behind the list (fine sync, demodulator, BP, the coherent step, OSD, subtraction, reports) is untouched.  Host state only,
+ * never refused; off (the default): nothing new is launched or allocated, every byte is as before.  The workspace (11.6 MB per frame of
+ * max_frames: the grid, 628 rows x 2306 carriers) is allocated at the first FT4 batch that runs with the setting on, all or nothing;
+ * ft8rx_ft4_info's figure does not include it. */
+int  ft8rx_ft4_set_weak(ft8rx_handle* h, int32_t on, float weak_min);
+/* bytes of weak-search workspace the handle holds (0 until the first FT4 batch with the setting on), the setting and its threshold;
+ * any pointer may be NULL */
+int  ft8rx_ft4_weak_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on, float* weak_min);
+/* stage entry point (tests): the chain's own launches on caller-supplied frames -> what ft8rx_ft4_sync returns (best / best_h0 optional) */
+int  ft8rx_ft4_sync_weak(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_t* f0_idx, int32_t* h0_idx, float* score,
+                         int32_t* counts, float* best_score, int32_t* best_h0);
 /* ft8rx_ldpc / ft8rx_osd_ext on raw LLR vectors of FT4 codewords: the returned words are descrambled; mask = FT8RX_MT_* bits */
 int  ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,
                     uint64_t* msg_hi, int32_t* n_its, int32_t* has_out, float* llr_out);

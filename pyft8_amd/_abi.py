@@ -165,6 +165,9 @@ PROTOTYPES = {
     "ft8rx_ft4_set_coherent": (INT, (PTR, I32)),
     "ft8rx_ft4_coh_info": (INT, (PTR, PTR, PTR)),
     "ft8rx_ft4_coherent": (INT, (PTR, PTR, INT, INT) + (PTR,) * 9),
+    "ft8rx_ft4_set_weak": (INT, (PTR, I32, F32)),
+    "ft8rx_ft4_weak_info": (INT, (PTR, PTR, PTR, PTR)),
+    "ft8rx_ft4_sync_weak": (INT, (PTR, PTR, INT) + (PTR,) * 6),
     "ft8rx_ft4_ldpc": (INT, (PTR, PTR, INT, INT, INT, I32) + (PTR,) * 6),
     "ft8rx_ft4_osd": (INT, (PTR, PTR, INT, INT, INT, INT, INT, I32) + (PTR,) * 5),
     "ft8rx_ft4_encode_tones": (INT, (PTR, PTR, INT, PTR)),

@@ -860,6 +860,29 @@ class Handle:
                   "ft8rx_ft4_coherent")
         return dict(q=q, metrics=met, llr2=l2, llr4=l4)
 
+    def ft4_set_weak(self, on, weak_min=None):
+        """ft8rx_ft4_set_weak: the weak search (coherent Costas sync on the 2.6-Hz grid) of the FT4 batches
+        enqueued afterwards, on or off, and its threshold (None = the default)."""
+        self._chk(self._L.ft8rx_ft4_set_weak(self._h, 1 if on else 0, float(weak_min or 0.0)), "ft8rx_ft4_set_weak")
+
+    def ft4_weak_info(self):
+        """ft8rx_ft4_weak_info -> dict(workspace_bytes (0 until the first FT4 batch with the setting on), on, weak_min)."""
+        wb, on, wm = C.c_uint64(), C.c_int32(), C.c_float()
+        self._chk(self._L.ft8rx_ft4_weak_info(self._h, C.byref(wb), C.byref(on), C.byref(wm)), "ft8rx_ft4_weak_info")
+        return dict(workspace_bytes=int(wb.value), on=bool(on.value), weak_min=float(wm.value))
+
+    def ft4_sync_weak(self, audio, want_best=False):
+        """ft8rx_ft4_sync_weak: the weak search's own launches on frames [B, 90000] -> (f0, h0, score [B, max_cands], counts [B]) and,
+        want_best, the per-bin maxima (best score, best h0) [B, f0_hi - f0_lo] before threshold and neighbour suppression."""
+        audio = self._ft4_audio(audio, "ft4_sync_weak")
+        B, mc = len(audio), self.cfg.max_cands
+        f0 = np.zeros((B, mc), np.int32); h0 = np.zeros((B, mc), np.int32); sc = np.zeros((B, mc), np.float32); cnt = np.zeros(B, np.int32)
+        rg = self.ft4_info()["range"]
+        bs = np.zeros((B, rg[1] - rg[0]), np.float32); bh = np.zeros((B, rg[1] - rg[0]), np.int32)
+        self._chk(self._L.ft8rx_ft4_sync_weak(self._h, audio.ctypes.data, B, f0.ctypes.data, h0.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
+                                              bs.ctypes.data if want_best else None, bh.ctypes.data if want_best else None), "ft8rx_ft4_sync_weak")
+        return (f0, h0, sc, cnt, bs, bh) if want_best else (f0, h0, sc, cnt)
+
     def ft4_ldpc(self, llr, max_ncheck0, max_iters, mask=0):
         """ft8rx_ft4_ldpc: ldpc() on LLRs of FT4 codewords; the words come back descrambled."""
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)

@@ -69,6 +69,7 @@
 #include "kernels/blank_in.hpp"
 #include "kernels/pan.hpp"
 #include "kernels/ft4.hpp"
+#include "kernels/ft4_weak.hpp"     // after ft4.hpp: it shares the sample read, the Costas tables and the range
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/ft4_sub.hpp"      // after subtract.hpp: it shares wave_sum2 and the int16 <-> float32 copies
@@ -348,6 +349,12 @@ struct ft8rx_handle {
         int32_t* d_q = nullptr; float* d_met = nullptr; float* d_llr = nullptr; float* d_saved = nullptr; Att* d_att = nullptr;
         int32_t* d_items = nullptr; int32_t* d_count = nullptr; int32_t* h_count = nullptr;
     } ft4coh;
+    // FT4 weak search (ft8rx_ft4_set_weak, kernels/ft4_weak.hpp; allocated at the first FT4 batch that runs
+    // with the setting on, WS_FT4_WEAK): the complex grid [max_frames][628][2306], the five mixes [5][576] and the 32 row turns
+    struct Ft4Weak {
+        bool on = false; float weak_min = FT8RX_FT4_WEAK_MIN_DEFAULT; size_t bytes = 0;
+        cpx* d_cg = nullptr; cpx* d_mix = nullptr; cpx* d_rot = nullptr;
+    } ft4weak;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -435,7 +442,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH, WS_FT4_REPORT };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH, WS_FT4_REPORT, WS_FT4_WEAK };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3635,6 +3642,29 @@ static int ft4coh_workspaces(ft8rx_handle* h) {
     w.bytes = rc ? 0 : bytes;
     return rc;
 }
+// Everything the weak search owns, at the first FT4 batch that runs with ft8rx_ft4_set_weak on, all or nothing.  The tables are filled
+// from exact arguments: j n / 4608 and k / 32 of a turn
+static int ft4weak_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4_WEAK)) return 0;
+    ft8rx_handle::Ft4Weak& w = h->ft4weak;
+    FirstUse F(h, WS_FT4_WEAK);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_cg, (size_t)h->max_frames * FT4W_ROWS * FT4W_NFQ); dev(&w.d_mix, (size_t)FT4W_NMIX * 576); dev(&w.d_rot, (size_t)32);
+    if (!F.rc) {
+        std::vector<cpx> mix((size_t)FT4W_NMIX * 576), rot;
+        for (int j = 0; j < FT4W_NMIX; j++) for (int n = 0; n < 576; n++) {
+            const double ang = 2.0 * M_PI * (double)((j * n) % 4608) / 4608.0;
+            mix[(size_t)j * 576 + n] = make_float2((float)cos(ang), (float)(-sin(ang)));
+        }
+        host_twiddle(32, 32, rot);
+        FIRST_HIP(F, hipMemcpy(w.d_mix, mix.data(), sizeof(cpx) * mix.size(), hipMemcpyHostToDevice));
+        FIRST_HIP(F, hipMemcpy(w.d_rot, rot.data(), sizeof(cpx) * rot.size(), hipMemcpyHostToDevice));
+    }
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
 static int ft4_refuse(ft8rx_handle* h, const char* who) {
     const int c = optins::conflict(active_optins(h), optins::FT4_ROW);
     if (c < 0) return 0;
@@ -3644,15 +3674,34 @@ static int ft4_refuse(ft8rx_handle* h, const char* who) {
 static void ft4_launch_grid(ft8rx_handle* h, const int16_t* d_audio, int B, float* grid, float* power, hipStream_t s) {
     k_ft4_grid<<<dim3(FT8RX_FT4_ROWS / FT4_GR, B), FT4_GRID_NT, 0, s>>>(d_audio, grid, power, h->ft4.d_win, h->ft4.d_w576, h->ft4.d_wr);
 }
-// grid -> the per-f0 maxima (d_raw, d_bh), the survivors (d_kept), then k_topk's records and counts
+// the per-f0 maxima (d_raw, d_bh) -> the survivors at or above `floor` (d_kept), then k_topk's records and counts
+static void ft4_launch_peaks(ft8rx_handle* h, int B, float floor, ft8rx_record* rec, int32_t* ncand, int32_t* evcount, hipStream_t s) {
+    const ft8rx_handle::Ft4& w = h->ft4;
+    const int nf0 = w.range.f0_hi - w.range.f0_lo;
+    k_ft4_peaks<<<dim3((nf0 + 255) / 256, B), 256, 0, s>>>(w.d_raw, w.d_kept, nf0, floor, B);
+    ft8rx_config c = h->cfg;
+    c.f0_lo = w.range.f0_lo; c.f0_hi = w.range.f0_hi; c.sync_score_min = 0.0f;      // k_topk: every surviving (positive) score, best first
+    k_topk<<<B, 1024, 0, s>>>(w.d_kept, w.d_bh, rec, ncand, c, evcount, nullptr, nullptr);
+}
+// grid -> the per-f0 maxima, then ft4_launch_peaks
 static void ft4_launch_sync(ft8rx_handle* h, const float* grid, int B, ft8rx_record* rec, int32_t* ncand, int32_t* evcount, hipStream_t s) {
     const ft8rx_handle::Ft4& w = h->ft4;
     const int nf0 = w.range.f0_hi - w.range.f0_lo;
     k_ft4_sync<<<dim3((nf0 + 15) / 16, B), 256, 0, s>>>(grid, w.d_raw, w.d_bh, w.range);
-    k_ft4_peaks<<<dim3((nf0 + 255) / 256, B), 256, 0, s>>>(w.d_raw, w.d_kept, nf0, w.sync_min, B);
-    ft8rx_config c = h->cfg;
-    c.f0_lo = w.range.f0_lo; c.f0_hi = w.range.f0_hi; c.sync_score_min = 0.0f;      // k_topk: every surviving (positive) score, best first
-    k_topk<<<B, 1024, 0, s>>>(w.d_kept, w.d_bh, rec, ncand, c, evcount, nullptr, nullptr);
+    ft4_launch_peaks(h, B, w.sync_min, rec, ncand, evcount, s);
+}
+// the weak search (section 19.10): the complex grid on the rows the h0 range reads, those with a sample inside the frame ...
+static void ft4_launch_cgrid(ft8rx_handle* h, const int16_t* d_audio, int B, hipStream_t s) {
+    const ft8rx_handle::Ft4Weak& k = h->ft4weak;
+    const int lo = std::max(h->ft4.range.h0_lo + 4, FT4W_ROW_LO), hi = std::min(h->ft4.range.h0_hi + 4 * (FT4_NSYM - 2), FT4W_ROW_LO + FT4W_ROWS);
+    if (hi > lo) k_ft4_cgrid<<<dim3((hi - lo + FT4W_CR - 1) / FT4W_CR, B), FT4W_NT, 0, s>>>(d_audio, k.d_cg, k.d_mix, k.d_rot, h->ft4.d_w576, lo, hi);
+}
+// ... and its per-f0 maxima where k_ft4_sync writes its own, cut at weak_min
+static void ft4_launch_csync(ft8rx_handle* h, int B, ft8rx_record* rec, int32_t* ncand, int32_t* evcount, hipStream_t s) {
+    const ft8rx_handle::Ft4& w = h->ft4;
+    const int nf0 = w.range.f0_hi - w.range.f0_lo;
+    k_ft4_csync<<<dim3((nf0 + 15) / 16, B), 256, 0, s>>>(h->ft4weak.d_cg, w.d_raw, w.d_bh, w.range);
+    ft4_launch_peaks(h, B, h->ft4weak.weak_min, rec, ncand, evcount, s);
 }
 // BP then OSD on n raw LLR vectors with the FT4 flag; att / attO [n]; OSD runs on every vector (the stage entries) -- the chain calls
 // the two halves itself.  mt: FT8RX_MT_* bits
@@ -3668,12 +3717,15 @@ static void ft4_launch_osd(ft8rx_handle* h, const float* llr, int n, const uint3
 // One FT4 batch on the main stream into the next result slot: grid, search, demodulation, BP, the OSD list (one host round trip for
 // its length: OSD's raw-vector mode takes one block per vector), OSD, records and events; then the FT8 result tail (batch_finish).
 // With ft8rx_ft4_set_coherent on, the coherent step stands between the list and OSD and shortens the list.
+// With ft8rx_ft4_set_weak on, the complex grid and the coherent score stand in for grid and search (section 19.10); the rest is the same.
 static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* audio, bool on_host, int B) {
     HIPCHK(h, hipSetDevice(h->device));
     if (ft4_refuse(h, who)) return -1;
     if (const int rc = ft4_workspaces(h)) return rc;
     const bool coh = h->ft4coh.on;
     if (coh) if (const int rc = ft4coh_workspaces(h)) return rc;
+    const bool weak = h->ft4weak.on;
+    if (weak) if (const int rc = ft4weak_workspaces(h)) return rc;
     ft8rx_handle::Ft4& w = h->ft4;
     const int slot = h->slot_enq;
     ResultSlot& sl = h->slots[slot];
@@ -3693,10 +3745,17 @@ static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* aud
     const unsigned mt = (unsigned)h->msg_types;
     const bool prof = h->profiling;
 #define STAGE(name) do { if (prof) { hipEventRecord(h->pev[h->pnames.size()], s); h->pnames.push_back(name); } } while (0)
-    STAGE("ft4_grid");
-    ft4_launch_grid(h, d_audio, B, w.d_grid, nullptr, s);
-    STAGE("ft4_sync");
-    ft4_launch_sync(h, w.d_grid, B, sl.rec, sl.ncand, sl.evcount, s);
+    if (weak) {                                                             // section 19.10: in place of the dB grid and its search
+        STAGE("ft4_cgrid");
+        ft4_launch_cgrid(h, d_audio, B, s);
+        STAGE("ft4_csync");
+        ft4_launch_csync(h, B, sl.rec, sl.ncand, sl.evcount, s);
+    } else {
+        STAGE("ft4_grid");
+        ft4_launch_grid(h, d_audio, B, w.d_grid, nullptr, s);
+        STAGE("ft4_sync");
+        ft4_launch_sync(h, w.d_grid, B, sl.rec, sl.ncand, sl.evcount, s);
+    }
     STAGE("ft4_demod");
     k_ft4_trip<<<(n + 255) / 256, 256, 0, s>>>(sl.rec, sl.ncand, B, sh, w.d_trip);
     k_ft4_demod<<<n, FT4_DEMOD_NT, 0, s>>>(d_audio, w.d_trip, w.d_llr, w.d_tweak, w.d_metric, w.d_snr);
@@ -3807,6 +3866,20 @@ int ft8rx_ft4_coh_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on) 
     return 0;
 }
 
+int ft8rx_ft4_set_weak(ft8rx_handle* h, int32_t on, float weak_min) {
+    if (!h) return -1;
+    h->ft4weak.on = on != 0;
+    h->ft4weak.weak_min = (weak_min > 0.0f && weak_min < INFINITY) ? weak_min : FT8RX_FT4_WEAK_MIN_DEFAULT;
+    return 0;
+}
+int ft8rx_ft4_weak_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on, float* weak_min) {
+    if (!h) return -1;
+    if (workspace_bytes) *workspace_bytes = ws_ready(h, WS_FT4_WEAK) ? (uint64_t)h->ft4weak.bytes : 0;
+    if (on) *on = h->ft4weak.on ? 1 : 0;
+    if (weak_min) *weak_min = h->ft4weak.weak_min;
+    return 0;
+}
+
 int ft8rx_ft4_grid(ft8rx_handle* h, const int16_t* audio, int B, float* grid, float* power) {
     if (!ft4_frames_ok(h, "ft8rx_ft4_grid", audio, B) || !grid) return -1;
     ENTER(h);
@@ -3824,15 +3897,10 @@ int ft8rx_ft4_grid(ft8rx_handle* h, const int16_t* audio, int B, float* grid, fl
     if (power) HIPCHK(h, hipMemcpy(power, d_pw, sizeof(float) * n, hipMemcpyDeviceToHost));
     return 0;
 }
-int ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts,
-                   float* best_score, int32_t* best_h0) {
-    if (!ft4_frames_ok(h, "ft8rx_ft4_sync", grid, B) || !f0_idx || !h0_idx || !score || !counts) return -1;
-    ENTER(h);
-    if (const int rc = ft4_workspaces(h)) return rc;
+// the read-back of the search's stage entries: the records' (f0, h0, score) in output order, the counts, the per-bin maxima
+static int ft4_sync_results(ft8rx_handle* h, int B, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts, float* best_score, int32_t* best_h0) {
     ft8rx_handle::Ft4& w = h->ft4;
     const int sh = cand_shift(h->cfg), mc = h->cfg.max_cands, nf0 = w.range.f0_hi - w.range.f0_lo;
-    HIPCHK(h, hipMemcpy(w.d_grid, grid, sizeof(float) * (size_t)B * FT8RX_FT4_ROWS * FT8RX_FT4_COLS, hipMemcpyHostToDevice));
-    ft4_launch_sync(h, w.d_grid, B, h->d_rec, h->d_ncand, h->d_evcount, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<ft8rx_record> rec((size_t)B << sh);
@@ -3846,6 +3914,27 @@ int ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx, i
     if (best_score) HIPCHK(h, hipMemcpy2D(best_score, sizeof(float) * nf0, w.d_raw, sizeof(float) * NF0MAX, sizeof(float) * nf0, B, hipMemcpyDeviceToHost));
     if (best_h0) HIPCHK(h, hipMemcpy2D(best_h0, sizeof(int32_t) * nf0, w.d_bh, sizeof(int32_t) * NF0MAX, sizeof(int32_t) * nf0, B, hipMemcpyDeviceToHost));
     return 0;
+}
+int ft8rx_ft4_sync(ft8rx_handle* h, const float* grid, int B, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts,
+                   float* best_score, int32_t* best_h0) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_sync", grid, B) || !f0_idx || !h0_idx || !score || !counts) return -1;
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    HIPCHK(h, hipMemcpy(w.d_grid, grid, sizeof(float) * (size_t)B * FT8RX_FT4_ROWS * FT8RX_FT4_COLS, hipMemcpyHostToDevice));
+    ft4_launch_sync(h, w.d_grid, B, h->d_rec, h->d_ncand, h->d_evcount, h->stream);
+    return ft4_sync_results(h, B, f0_idx, h0_idx, score, counts, best_score, best_h0);
+}
+int ft8rx_ft4_sync_weak(ft8rx_handle* h, const int16_t* audio, int B, int32_t* f0_idx, int32_t* h0_idx, float* score, int32_t* counts,
+                        float* best_score, int32_t* best_h0) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_sync_weak", audio, B) || !f0_idx || !h0_idx || !score || !counts) return -1;
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    if (const int rc = ft4weak_workspaces(h)) return rc;
+    HIPCHK(h, hipMemcpy(h->ft4.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice));
+    ft4_launch_cgrid(h, h->ft4.d_audio, B, h->stream);
+    ft4_launch_csync(h, B, h->d_rec, h->d_ncand, h->d_evcount, h->stream);
+    return ft4_sync_results(h, B, f0_idx, h0_idx, score, counts, best_score, best_h0);
 }
 int ft8rx_ft4_demod(ft8rx_handle* h, const int16_t* audio, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
                     int32_t* tweak, float* metric, float* llr, int32_t* snr) {

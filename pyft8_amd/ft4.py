@@ -40,6 +40,21 @@ The twin also defines the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/te
            bins' energy at 13 starts 4 samples apart, the first maximum; subtract: x -= 2 Re(a model), a = the bins' inverse transform
 and, opt-in, the measured reports (csrc/kernels/ft4_report.hpp, tests/test_gpu_ft4_report.py; stated in full where report stands, below;
 DESIGN.md section 19.9): a decoded signal against the same model on a 13 x 13 map of starts and frequencies -> SNR, frequency, time
+and, opt-in, the weak search (csrc/kernels/ft4_weak.hpp, tests/test_gpu_ft4_weak.py; weak_sums, weak_score_map
+and search_weak below).  It replaces grid and search above and hands the same (f0, h0, score) candidates on.  All phases are exact
+integers over 4608; fq is a carrier in units of 12000 / 4608 Hz, r a row (its symbol starts at sample 144 r; r may be negative or run
+past the frame, samples outside the frame are zeros), t a tone:
+  sums     W[r][fq][t] = sum_{n < 576} x[144 r + n] e^{-2 pi i ((fq (144 r + n) + 8 t n) mod 4608) / 4608}: the carrier's phase is
+           referred to sample 0 of the frame, the tone's offset restarts at the symbol, as the transmitted phase does.  For r = h0 + 4 s
+           this is C[s][t] above (at tt = 0) up to one constant phase per candidate
+  score    for Costas block b with first symbol p_b: B_b(fq, h) = sum_{k < 4} W[h + 4 (p_b + k)][fq][costas_b[k]];
+           N(fq, h) = (1 / 64) sum over the 16 sync symbols and the 4 tones of |W|^2;
+           score(fq, h) = (|B_0| + |B_1| + |B_2| + |B_3|) / sqrt(N), 0 where N = 0: 0 .. 32, a clean signal on the grid near 32
+  per f0   best[f0] = the maximum of score(fq, h) over fq = 4 f0 - 2 .. 4 f0 + 1 (a negative fq is not evaluated) and h in the h0
+           range, the first maximum in (fq, h) order, fq ascending then h ascending; h0[f0] is that h; the winner's fq is not handed on
+  kept     search's rule with weak_min in place of sync_min, then the max_cands highest, ties in f0 order
+The FFT form (weak_grid): G[r][fq'] = W[r][fq'][0] for fq' = 0 .. 2305 serves all four tones, W[r][fq][t] = i^(t r) G[r][fq + 8 t]; per
+row it is eight 576-point transforms of the row's samples mixed by fq' mod 8 eighths of a bin, then a turn by (fq' r mod 32) / 32.
 """
 import numpy as np
 
@@ -65,6 +80,8 @@ SEED_BASE = 0x46543400
 SYNC_MIN_DEFAULT = 100.0
 OSD_MAX_HD_DEFAULT = 40                # FT8RX_FT4_OSD_MAX_HD_DEFAULT: the largest gate without a false decode on 2048 noise frames
 OSD_MAX_HD_MSG_TYPES = 24              # ... and with msg_types = all (one false RTTY-RU word from 28 on): what Receiver takes then
+WEAK_MIN_DEFAULT = 16.17               # FT8RX_FT4_WEAK_MIN_DEFAULT
+WEAK_NFQ = 4 * NSPS + 2                # carriers of the weak search's grid: fq' = 0 .. 2305 (f0 = 570 reads 4 f0 + 1 + 24)
 LLR_SCALE = 2.83
 LLR_ZERO = 1e-3                        # what an LLR of exactly 0 becomes: the shared BP's message update divides by tanh(llr / 2)
 # symbol index of each of the 87 data symbols, and (symbol, tone) of the 16 sync symbols
@@ -212,15 +229,13 @@ def score_map(db, f0_lo, f0_hi, h0_lo, h0_hi, weights=None):
     return out
 
 
-def search(db, f0_lo, f0_hi, h0_lo, h0_hi, sync_min=SYNC_MIN_DEFAULT, max_cands=200, full=False):
-    """-> [(f0, h0, score), ...] in output order (score descending, ties in f0 order); full: also (best[f0], h0[f0], score map)."""
-    S = score_map(db, f0_lo, f0_hi, h0_lo, h0_hi)
-    bh = np.argmax(S, axis=1)                                              # the first maximum
-    best = S[np.arange(len(S)), bh]
+def _keep(best, h0, f0_lo, floor, max_cands):
+    """best [nf0], h0 [nf0] -> the kept candidates [(f0, h0, score), ...]: best >= floor and >= both neighbours' (a tie goes to the lower
+    bin), the max_cands highest, ties in f0 order"""
     n = len(best)
     keep = []
     for i in range(n):
-        if not best[i] >= sync_min:
+        if not best[i] >= floor:
             continue
         if i > 0 and best[i - 1] >= best[i]:
             continue
@@ -228,8 +243,93 @@ def search(db, f0_lo, f0_hi, h0_lo, h0_hi, sync_min=SYNC_MIN_DEFAULT, max_cands=
             continue
         keep.append(i)
     keep.sort(key=lambda i: -best[i])                                      # stable: ties stay in f0 order
-    out = [(f0_lo + i, h0_lo + int(bh[i]), float(best[i])) for i in keep[:max_cands]]
+    return [(f0_lo + i, int(h0[i]), float(best[i])) for i in keep[:max_cands]]
+
+
+def search(db, f0_lo, f0_hi, h0_lo, h0_hi, sync_min=SYNC_MIN_DEFAULT, max_cands=200, full=False):
+    """-> [(f0, h0, score), ...] in output order (score descending, ties in f0 order); full: also (best[f0], h0[f0], score map)."""
+    S = score_map(db, f0_lo, f0_hi, h0_lo, h0_hi)
+    bh = np.argmax(S, axis=1)                                              # the first maximum
+    best = S[np.arange(len(S)), bh]
+    out = _keep(best, h0_lo + bh, f0_lo, sync_min, max_cands)
     return (out, best, h0_lo + bh, S) if full else out
+
+
+# ----------------------------------------------------------------------------- the twin: weak search (csrc/kernels/ft4_weak.hpp, section 19.10)
+def weak_sums(x, rows, fqs):
+    """W[len(rows)][len(fqs)][4] of the definition, straight from the samples: every phase an exact integer over 4608."""
+    x = np.asarray(x, np.float64)
+    rows, fqs = np.asarray(rows, np.int64).reshape(-1), np.asarray(fqs, np.int64).reshape(-1)
+    V = _symbols(x, HOP * rows)                                            # [rows][576], zeros outside the frame
+    table = np.exp(-2j * np.pi * np.arange(4608) / 4608.0)
+    out = np.zeros((len(rows), len(fqs), 4), np.complex128)
+    for i, r in enumerate(rows):
+        for t in range(4):
+            ph = (fqs[:, None] * (HOP * int(r) + _N[None, :]) + 8 * t * _N[None, :]) % 4608
+            out[i, :, t] = table[ph] @ V[i]
+    return out
+
+
+def weak_grid(x, r_lo, r_hi):
+    """The FFT form: G[r - r_lo][fq'] = W[r][fq'][0], r = r_lo .. r_hi - 1, fq' = 0 .. 2305.  fq' = 8 m + j: the row's samples times
+    e^{-2 pi i j n / 4608}, a 576-point transform, bin m, then e^{-2 pi i ((fq' r) mod 32) / 32} for the row's start."""
+    x = np.asarray(x, np.float64)
+    rows = np.arange(int(r_lo), int(r_hi))
+    V = _symbols(x, HOP * rows)
+    fq = np.arange(WEAK_NFQ)
+    G = np.zeros((len(rows), WEAK_NFQ), np.complex128)
+    for j in range(8):
+        Z = np.fft.fft(V * np.exp(-2j * np.pi * (j * _N) / 4608.0)[None, :], axis=1)
+        sel = fq[fq % 8 == j]
+        G[:, sel] = Z[:, sel // 8]
+    return G * np.exp(-2j * np.pi * ((fq[None, :] * rows[:, None]) % 32) / 32.0)
+
+
+def _weak_terms(G, r_lo, fq_lo, fq_hi, h0_lo, h0_hi):
+    """-> (B [4][fq][h] the block sums, E [fq][h] = sum of |W|^2 over the 16 sync symbols and 4 tones) on the grid G of rows r_lo .."""
+    fqs, hs = np.arange(fq_lo, fq_hi), np.arange(h0_lo, h0_hi)
+    B = np.zeros((4, len(fqs), len(hs)), np.complex128)
+    E = np.zeros((len(fqs), len(hs)))
+    for sym, tone in SYNC_SYMS:
+        b = SYNC_POS.index(sym - (sym - 1) % 33)
+        r = hs + 4 * sym
+        for t in range(4):
+            g = G[(r - r_lo)[None, :], (fqs + 8 * t)[:, None]]             # [fq][h]
+            E += g.real ** 2 + g.imag ** 2
+            if t == tone:
+                B[b] += g * (1j ** ((t * r) % 4))[None, :]                  # an exact quarter-turn power
+    return B, E
+
+
+def weak_score_map(x, fq_lo, fq_hi, h0_lo, h0_hi, full=False):
+    """score[fq - fq_lo][h - h0_lo] of the weak search; fq_lo >= 0.  full: also (S = sum of the four |B_b|, nrm = sqrt(64 N)) --
+    score = 8 S / nrm -- for the tests' error bound."""
+    G = weak_grid(x, h0_lo + 4, h0_hi + 4 * (NSYM - 2))                     # rows h0_lo + 4 .. h0_hi - 1 + 412
+    B, E = _weak_terms(G, h0_lo + 4, fq_lo, fq_hi, h0_lo, h0_hi)
+    S, nrm = np.abs(B).sum(axis=0), np.sqrt(E)
+    score = np.where(E > 0, 8.0 * S / np.where(E > 0, nrm, 1.0), 0.0)
+    return (score, S, nrm) if full else score
+
+
+def weak_best(score, fq_lo, f0_lo, f0_hi, h0_lo):
+    """The per-f0 step on a score map whose first row is carrier fq_lo: -> (best [nf0], h0 [nf0]), the first maximum in (fq, h) order
+    over fq = 4 f0 - 2 .. 4 f0 + 1, a negative fq left out."""
+    best, bh = np.zeros(f0_hi - f0_lo), np.zeros(f0_hi - f0_lo, np.int64)
+    for i, f0 in enumerate(range(f0_lo, f0_hi)):
+        a = max(4 * f0 - 2, 0) - fq_lo
+        blk = score[a:4 * f0 + 2 - fq_lo]
+        k = int(np.argmax(blk))                                             # C order: fq ascending, then h ascending
+        best[i], bh[i] = blk.flat[k], h0_lo + k % blk.shape[1]
+    return best, bh
+
+
+def search_weak(x, f0_lo, f0_hi, h0_lo, h0_hi, weak_min=WEAK_MIN_DEFAULT, max_cands=200, full=False):
+    """The weak search on one frame -> [(f0, h0, score), ...] in output order; full: also (best [nf0], h0 [nf0], score map, fq_lo)."""
+    fq_lo = max(4 * f0_lo - 2, 0)
+    S = weak_score_map(x, fq_lo, 4 * (f0_hi - 1) + 2, h0_lo, h0_hi)
+    best, bh = weak_best(S, fq_lo, f0_lo, f0_hi, h0_lo)
+    out = _keep(best, bh, f0_lo, weak_min, max_cands)
+    return (out, best, bh, S, fq_lo) if full else out
 
 
 # ----------------------------------------------------------------------------- the twin: fine sync and demodulation
@@ -454,14 +554,17 @@ def bp_decode(llr, max_iters=50):
     return None
 
 
-def decode_twin(x, f0_lo=None, f0_hi=None, h0_lo=None, h0_hi=None, sync_min=SYNC_MIN_DEFAULT, max_cands=200):
-    """The whole twin on one frame: search, fine sync, demodulation, BP -> [dict(f0, h0, tt, ft, snr, word or None), ...]."""
+def decode_twin(x, f0_lo=None, f0_hi=None, h0_lo=None, h0_hi=None, sync_min=SYNC_MIN_DEFAULT, max_cands=200, weak=False, weak_min=WEAK_MIN_DEFAULT):
+    """The whole twin on one frame: search (weak: search_weak at weak_min instead), fine sync, demodulation, BP
+    -> [dict(f0, h0, tt, ft, snr, word or None), ...]."""
     a, b = freq_range_to_f0()
     c, d = time_range_to_h0()
     f0_lo, f0_hi = (a if f0_lo is None else f0_lo), (b if f0_hi is None else f0_hi)
     h0_lo, h0_hi = (c if h0_lo is None else h0_lo), (d if h0_hi is None else h0_hi)
     out = []
-    for f0, h0, score in search(grid_db(grid_power(x)), f0_lo, f0_hi, h0_lo, h0_hi, sync_min, max_cands):
+    cands = (search_weak(x, f0_lo, f0_hi, h0_lo, h0_hi, weak_min, max_cands) if weak else
+             search(grid_db(grid_power(x)), f0_lo, f0_hi, h0_lo, h0_hi, sync_min, max_cands))
+    for f0, h0, score in cands:
         r = demod(x, f0, h0)
         out.append(dict(f0=f0, h0=h0, score=score, tt=r["tt"], ft=r["ft"], snr=r["snr"], llr=r["llr"], word=bp_decode(r["llr"])))
     return out

@@ -1,6 +1,6 @@
 """FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
 
-    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes] [--coherent]
+    python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes] [--coherent] [--weak]
     python tools/ft4_measure.py --reports [--reports-twin] [--out profiles/ft4_report_measure.json]
 
 --prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
@@ -15,6 +15,12 @@
               probability at -19 .. -12 dB (the recipe of --prob) with the decodes by run length; false decodes on the 2048 noise frames
               at the default gates (40 at msg_types 0, 24 at all); frames/s at B = 256 with 20 signals per frame (device-resident), the
               stage times and the length of the list the coherent step works on
+--weak        the weak search (section 19.10), each figure beside the same recipe with the setting off, in one session: the threshold
+              that leaves the 2048 noise frames no more candidates than the default search leaves there at sync_min = 100 (both counted
+              in this run); false decodes on those frames at that threshold, with ft4_coherent off and on, at gate 40 / msg_types 0 and
+              gate 24 / all; decode probability at -18 .. -12 dB (the recipe of --prob) in four columns -- off, weak, coherent, weak +
+              coherent -- with the truths that became candidates; frames/s at B = 256 with 20 signals per frame (device-resident),
+              off / on alternating, twice each, and the stage times
 --reports     measured reports (section 19.9) -> profiles/ft4_report_measure.json: the accuracy recipe make_frame(i, n_signals=8, snr_range=
               (-14, 15), min_sep_hz=250) against truth, frames 16 .. 79 through Receiver(ft4_reports=True) with the default fields of the
               same messages beside it; the report stage timed with HIP events (ft8rx_set_profiling) at B = 256 with 20 signals per frame;
@@ -222,6 +228,106 @@ def measure_coherent(h, noise_frames_n=2048, chunk=256, per_step=200, B=256, war
     return out
 
 
+def weak_kept(best):
+    """best [B][nf0] -> the scores of the bins k_ft4_peaks keeps at any threshold: no lower neighbour at or above, no higher one above"""
+    b = np.asarray(best, np.float64)
+    left = np.concatenate([np.full((len(b), 1), -np.inf), b[:, :-1]], axis=1)
+    right = np.concatenate([b[:, 1:], np.full((len(b), 1), -np.inf)], axis=1)
+    return b[(left < b) & (right <= b)]
+
+
+def found_as_candidates(res, frames):
+    """truths with a candidate within 1 bin and 2.5 rows"""
+    n = 0
+    for f, (_, truth) in enumerate(frames):
+        r = res[0][f, :res[1][f]]
+        for t in truth:
+            n += bool(np.any((np.abs(r["f0_idx"] - t["f0"] / ft4.BIN_HZ) <= 1) & (np.abs(r["h0_idx"] - t["t0"] * ft4.FS / ft4.HOP) <= 2.5)))
+    return n
+
+
+def measure_weak(h, noise_frames_n=2048, chunk=256, per_step=200, B=256, warmup=3, steps=20):
+    import torch
+    from pyft8_amd import _lib
+    snrs = list(range(-18, -11))
+    out = {"threshold": {"frames": noise_frames_n}, "noise": {"frames": noise_frames_n}, "probability": {"snr_db": snrs, "signals_per_step": per_step},
+           "throughput": {"B": B, "signals_per_frame": 20}}
+    live = lambda res: np.concatenate([res[0][f, :res[1][f]] for f in range(len(res[1]))])
+
+    def setting(weak, coh, weak_min=None):
+        h.ft4_set_weak(weak, weak_min); h.ft4_set_coherent(coh)
+    # ---- the threshold: the default search's candidates on the noise frames, and the weak search's kept maxima there
+    yard, kept = 0, []
+    for first in range(0, noise_frames_n, chunk):
+        a = noise_frames(chunk, first)
+        setting(False, False)
+        yard += int(h.ft4_decode(a)[1].sum())
+        kept.append(weak_kept(h.ft4_sync_weak(a, want_best=True)[4]))
+    kept = np.sort(np.concatenate(kept))[::-1]
+    # the smallest threshold, to two decimals, with no more than `yard` kept maxima at or above it (float32 scores against a float32 cut)
+    t = np.ceil(float(kept[yard]) * 100.0) / 100.0 if yard < len(kept) else 0.01
+    while int((kept >= np.float32(t)).sum()) > yard:
+        t = round(t + 0.01, 2)
+    out["threshold"].update(default_search_candidates=yard, weak_min=t, weak_candidates_at_it=int((kept >= np.float32(t)).sum()),
+                            kept_maxima=len(kept), highest=[round(float(v), 3) for v in kept[:8]],
+                            candidates_per_frame_at={f"{c:.2f}": float((kept >= np.float32(c)).sum()) / noise_frames_n for c in (15.0, 15.25, 15.5, 15.75, 16.0, 16.25, 16.5)})
+    print("weak threshold", out["threshold"], flush=True)
+    wm = t
+    # ---- false decodes on noise at that threshold, the default gates
+    cols = (("off", False, False), ("weak", True, False), ("coherent", False, True), ("weak_coherent", True, True))
+    nz = {f"{name}_{m}": {"false_decodes": 0, "candidates": 0, "texts": []} for name, _, _ in cols for m in ("0", "all")}
+    for first in range(0, noise_frames_n, chunk):
+        a = noise_frames(chunk, first)
+        for m, mask, gate in (("0", 0, ft4.OSD_MAX_HD_DEFAULT), ("all", _lib.MT_ALL, ft4.OSD_MAX_HD_MSG_TYPES)):
+            h.set_msg_types(mask); h.ft4_set(osd_max_hd=gate)
+            for name, weak, coh in cols:
+                setting(weak, coh, wm)
+                res = h.ft4_decode(a)
+                dec = live(res); dec = dec[dec["status"] == 1]
+                e = nz[f"{name}_{m}"]
+                e["false_decodes"] += len(dec); e["candidates"] += int(res[1].sum())
+                if len(dec):
+                    e["texts"] += [f"frame {first + f}: {t}" for f, s in enumerate(texts_of(h, res, mask)) for t in s]
+        print(f"weak noise frames {first + chunk}: " + ", ".join(f"{k} {v['false_decodes']}/{v['candidates']}" for k, v in nz.items()), flush=True)
+    h.set_msg_types(0); h.ft4_set()
+    out["noise"].update(nz); out["noise"]["weak_min"] = wm
+    # ---- decode probability, four columns
+    for name, weak, coh in cols:
+        setting(weak, coh, wm)
+        r = {"decoded": [], "candidates": [], "truths_as_candidates": []}
+        for snr in snrs:
+            frames = [prob_frame(snr, k, float(snr)) for k in range(per_step // 10)]
+            res = h.ft4_decode(np.stack([f[0] for f in frames]))
+            got = texts_of(h, res)
+            r["decoded"].append(sum(t["msg"] in got[f] for f, (_, truth) in enumerate(frames) for t in truth))
+            r["candidates"].append(int(res[1].sum())); r["truths_as_candidates"].append(found_as_candidates(res, frames))
+            print(f"weak {name} prob {snr:+d} dB: {r['decoded'][-1]}/{per_step}, {r['truths_as_candidates'][-1]} truths among {r['candidates'][-1]} candidates", flush=True)
+        r["probability"] = [d / per_step for d in r["decoded"]]
+        r["half_point_db"] = half_point(snrs, r["probability"])
+        out["probability"][name] = r
+    # ---- throughput, device-resident frames
+    a = np.stack([throughput_frame(k) for k in range(B)])
+    d = torch.from_numpy(a).to("cuda:0"); torch.cuda.synchronize()
+    for name, weak in (("off", False), ("on", True), ("off_again", False), ("on_again", True)):
+        setting(weak, False, wm)
+        for _ in range(warmup):
+            h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B)
+        tt = []
+        for _ in range(steps):
+            t0 = time.perf_counter(); h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B); tt.append(time.perf_counter() - t0)
+        rec = live(res)
+        h.set_profiling(True)
+        h.ft4_enqueue(d.data_ptr(), B); h.fetch(B); h.sync()
+        stage = {k: round(float(v), 4) for k, v in h.stage_times().items()}
+        h.set_profiling(False)
+        out["throughput"][name] = {"device_frames_per_s": B / float(np.median(tt)), "device_step_ms": [round(1e3 * x, 3) for x in tt], "stage_ms": stage,
+                                   "candidates": len(rec), "decoded": int((rec["status"] == 1).sum())}
+        print("weak throughput", name, out["throughput"][name]["device_frames_per_s"], stage, flush=True)
+    out["throughput"]["workspace_bytes"] = h.ft4_weak_info()["workspace_bytes"]
+    setting(False, False)
+    return out
+
+
 CROWDED_KW = dict(n_signals=16, snr_range=(-12, 10), freq_range=(300, 1200), t0_range=(0.2, 1.2), min_sep_hz=25)
 SUB_GATES = [None, 32, 24, 16]
 
@@ -397,6 +503,7 @@ if __name__ == "__main__":
     ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
     ap.add_argument("--twin", type=int, default=0); ap.add_argument("--passes", action="store_true")
     ap.add_argument("--noise-frames", type=int, default=2048); ap.add_argument("--coherent", action="store_true")
+    ap.add_argument("--weak", action="store_true")
     ap.add_argument("--reports", action="store_true"); ap.add_argument("--reports-twin", action="store_true")
     args = ap.parse_args()
     if (args.reports or args.reports_twin) and args.out == ap.get_default("out"):
@@ -404,7 +511,7 @@ if __name__ == "__main__":
     res = json.load(open(args.out)) if os.path.exists(args.out) else {}
     if args.twin:
         res["twin_probability"] = measure_twin(args.twin)
-    if args.prob or args.noise or args.throughput or args.coherent:
+    if args.prob or args.noise or args.throughput or args.coherent or args.weak:
         import torch  # noqa: F401 -- before libft8rx.so loads (_lib.lib)
         from pyft8_amd import _lib
         h = _lib.Handle(max_frames=256)
@@ -416,6 +523,8 @@ if __name__ == "__main__":
             res["noise"] = measure_noise(h, args.noise_frames)
         if args.coherent:
             res["coherent"] = measure_coherent(h, args.noise_frames)
+        if args.weak:
+            res["weak"] = measure_weak(h, args.noise_frames)
         h.close()
     if args.passes:
         import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
