@@ -58,11 +58,13 @@
  *     ft8rx_ft4_report  ft8rx_ft4_report_info                                         (opt-in measured SNR / frequency / time of FT4 decodes)
  *     ft8rx_ft4_set_coherent  ft8rx_ft4_coh_info                                       (opt-in FT4 coherent LLRs: runs of two and four symbols)
  *     ft8rx_ft4_set_weak  ft8rx_ft4_weak_info                                          (opt-in FT4 weak search: coherent Costas sync, 2.6-Hz grid)
+ *     ft8rx_ft4_set_coh_osd  ft8rx_ft4_coh_osd_info                                    (opt-in FT4 OSD on the coherent LLRs behind a whole-message score)
  *   TEST AND MEASUREMENT AIDS (stage entry points of the parity tests, timers, probes -- an adopter never calls these)
  *     ft8rx_spectrogram  ft8rx_sync_scores  ft8rx_llr_grid  ft8rx_cycle_spectrum  ft8rx_fine  ft8rx_get_fft_plans
  *     ft8rx_sync_scores_weak  ft8rx_fine_weak
  *     ft8rx_ft4_sync_weak
  *     ft8rx_ft4_grid  ft8rx_ft4_sync  ft8rx_ft4_demod  ft8rx_ft4_coherent  ft8rx_ft4_ldpc  ft8rx_ft4_osd  ft8rx_ft4_sub_probe
+ *     ft8rx_ft4_verify
  *     ft8rx_set_profiling  ft8rx_get_stage_times  ft8rx_math_probe  (and the ft8rx_debug_* symbols of timing-only builds)
  *
  * LIMITS of this build against the reference's open-ended kwargs (pyft8_amd.receiver.config_from_kwargs names the kwarg when one is
@@ -1044,6 +1046,38 @@ int  ft8rx_ft4_weak_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on
 /* stage entry point (tests): the chain's own launches on caller-supplied frames -> what ft8rx_ft4_sync returns (best / best_h0 optional) */
 int  ft8rx_ft4_sync_weak(ft8rx_handle* h, const int16_t* audio, int n_frames, int32_t* f0_idx, int32_t* h0_idx, float* score,
                          int32_t* counts, float* best_score, int32_t* best_h0);
+/* OSD on the coherent LLRs behind a whole-message score (opt-in; kernels/ft4_verify.hpp; the twin is
+ * ft4.verify_score).  on != 0: every FT4 batch enqueued afterwards that runs the coherent step (ft8rx_ft4_set_coherent; without it the
+ * setting does nothing) runs, behind the unchanged single-symbol OSD, OSD once more on the run-of-2 and the run-of-4 rows of every
+ * candidate on OSD's list: the handle's order settings and msg_types, the distance gate max_hd (<= 0: the default).  A Hamming gate
+ * alone cannot carry this step, so every word it returns is scored against the audio: with C the complex amplitudes of section 19.8,
+ * turned by q, and T the word's 105 tones,
+ *   score = A / sqrt(N),  A = sum over the 26 runs of four symbols from symbol 1 on of |sum C[s][T[s]]|,
+ *                         N = the mean |C|^2 over symbols 1 .. 103 and the 4 tones     (0 where N = 0; near 206 on a clean signal).
+ * A candidate the chain has decoded keeps its record byte for byte.  A candidate left EXHAUSTED becomes decoded by a word with
+ * score >= min_score (<= 0: the default), run length 2 winning over 4: an OSD decode (ipass 5, FT8RX_M_OSD, ap 0, n_its = the trial,
+ * osd_hd = the distance to that row's hard decisions) whose record carries the run length in nsync, rint(100 score) in pad2 and whose
+ * event carries slot 1 or 2.  Host state only, never refused; off (the default): nothing new is launched or allocated, every byte is
+ * as before.  The workspaces (1.4 KB per candidate slot) are allocated at the first FT4 batch that runs the step, all or nothing;
+ * the figures of ft8rx_ft4_info, ft8rx_ft4_coh_info and ft8rx_ft4_weak_info do not include them.
+ * Measured on an MI355X with these defaults (tools/ft4_measure.py --coh-osd, profiles/ft4_notes.md, section 19.11): no false decode on
+ * 2048 noise frames behind either search, at msg_types 0 (77.1) and all (81.0); one wrong word (score 90.6) among the 1400 signals of
+ * the decode table; 50 % decode probability at -15.9 dB instead of -15.7 (coherent alone), 44 instead of 28 of 200 signals at -17 dB
+ * behind the weak search; 40.0 k instead of 40.8 k frames/s at B = 256 (the stage: 0.13 ms).  The defaults come from 14 noise words (22
+ * at msg_types all): the gate is measured, but on a thin tail. */
+#define FT8RX_FT4_COH_OSD_MIN_SCORE_DEFAULT 77.1f   /* S_max + (S_max - S_90) of the noise words within max_hd (76.84, 76.62), rounded up */
+#define FT8RX_FT4_COH_OSD_MIN_SCORE_MSG_TYPES 81.0f /* the same from the noise words at msg_types all (79.27, 77.57): what Receiver takes then */
+#define FT8RX_FT4_COH_OSD_MAX_HD_DEFAULT    40      /* the smallest multiple of 4 that keeps 99 % of the true words (all 71 lie in 17 .. 39) */
+int  ft8rx_ft4_set_coh_osd(ft8rx_handle* h, int32_t on, float min_score, int32_t max_hd);
+/* bytes of the step's workspace the handle holds (0 until the first FT4 batch that runs it), the setting and its two gates; any
+ * pointer may be NULL */
+int  ft8rx_ft4_coh_osd_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on, float* min_score, int32_t* max_hd);
+/* stage entry point (tests): the chain's own launch of k_ft4_verify on n caller-supplied candidates (frame, f0, h0), fine-sync
+ * winners (ttweak in -4 .. 4, ftweak in -2 .. 2), residuals q in -4 .. 4 and 77-bit words -> score [n]; tones (optional): [n][105],
+ * the words' tones as the kernel encoded them */
+int  ft8rx_ft4_verify(ft8rx_handle* h, const int16_t* audio, int n_frames, int n, const int32_t* frame, const int32_t* f0_idx,
+                      const int32_t* h0_idx, const int32_t* ttweak, const int32_t* ftweak, const int32_t* q, const uint64_t* msg_lo,
+                      const uint64_t* msg_hi, float* score, uint8_t* tones);
 /* ft8rx_ldpc / ft8rx_osd_ext on raw LLR vectors of FT4 codewords: the returned words are descrambled; mask = FT8RX_MT_* bits */
 int  ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,
                     uint64_t* msg_hi, int32_t* n_its, int32_t* has_out, float* llr_out);

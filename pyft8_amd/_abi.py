@@ -168,6 +168,9 @@ PROTOTYPES = {
     "ft8rx_ft4_set_weak": (INT, (PTR, I32, F32)),
     "ft8rx_ft4_weak_info": (INT, (PTR, PTR, PTR, PTR)),
     "ft8rx_ft4_sync_weak": (INT, (PTR, PTR, INT) + (PTR,) * 6),
+    "ft8rx_ft4_set_coh_osd": (INT, (PTR, I32, F32, I32)),
+    "ft8rx_ft4_coh_osd_info": (INT, (PTR, PTR, PTR, PTR, PTR)),
+    "ft8rx_ft4_verify": (INT, (PTR, PTR, INT, INT) + (PTR,) * 10),
     "ft8rx_ft4_ldpc": (INT, (PTR, PTR, INT, INT, INT, I32) + (PTR,) * 6),
     "ft8rx_ft4_osd": (INT, (PTR, PTR, INT, INT, INT, INT, INT, I32) + (PTR,) * 5),
     "ft8rx_ft4_encode_tones": (INT, (PTR, PTR, INT, PTR)),

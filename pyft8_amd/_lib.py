@@ -883,6 +883,34 @@ class Handle:
                                               bs.ctypes.data if want_best else None, bh.ctypes.data if want_best else None), "ft8rx_ft4_sync_weak")
         return (f0, h0, sc, cnt, bs, bh) if want_best else (f0, h0, sc, cnt)
 
+    def ft4_set_coh_osd(self, on, min_score=None, max_hd=None):
+        """ft8rx_ft4_set_coh_osd: OSD on the coherent rows behind the whole-message score of the FT4 batches
+        enqueued afterwards that run the coherent step, on or off, and its two gates (None = the defaults)."""
+        self._chk(self._L.ft8rx_ft4_set_coh_osd(self._h, 1 if on else 0, float(min_score or 0.0), int(max_hd or 0)), "ft8rx_ft4_set_coh_osd")
+
+    def ft4_coh_osd_info(self):
+        """ft8rx_ft4_coh_osd_info -> dict(workspace_bytes (0 until the first FT4 batch that runs the step), on, min_score, max_hd)."""
+        wb, on, ms, hd = C.c_uint64(), C.c_int32(), C.c_float(), C.c_int32()
+        self._chk(self._L.ft8rx_ft4_coh_osd_info(self._h, C.byref(wb), C.byref(on), C.byref(ms), C.byref(hd)), "ft8rx_ft4_coh_osd_info")
+        return dict(workspace_bytes=int(wb.value), on=bool(on.value), min_score=float(ms.value), max_hd=int(hd.value))
+
+    def ft4_verify(self, audio, frame, f0, h0, ttweak, ftweak, q, words, want_tones=False):
+        """ft8rx_ft4_verify: k_ft4_verify on (frame, f0, h0) triples at the given fine-sync winners, residuals q and 77-bit words
+        (Python ints) -> score [n] float32 (and, want_tones, the tones [n, 105] uint8 as the kernel encoded them)."""
+        audio = self._ft4_audio(audio, "ft4_verify")
+        frame, f0, h0, tt, ft, q = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (frame, f0, h0, ttweak, ftweak, q))
+        n = len(f0)
+        if n < 1 or any(len(x) != n for x in (frame, h0, tt, ft, q, words)):
+            raise Ft8rxError("ft4_verify: one frame, f0, h0, ttweak, ftweak, q and word per candidate")
+        lo = np.array([int(w) & (2 ** 64 - 1) for w in words], np.uint64)
+        hi = np.array([int(w) >> 64 for w in words], np.uint64)
+        sc = np.zeros(n, np.float32)
+        tones = np.zeros((n, 105), np.uint8) if want_tones else None
+        self._chk(self._L.ft8rx_ft4_verify(self._h, audio.ctypes.data, len(audio), n, frame.ctypes.data, f0.ctypes.data, h0.ctypes.data,
+                                           tt.ctypes.data, ft.ctypes.data, q.ctypes.data, lo.ctypes.data, hi.ctypes.data, sc.ctypes.data,
+                                           tones.ctypes.data if want_tones else None), "ft8rx_ft4_verify")
+        return (sc, tones) if want_tones else sc
+
     def ft4_ldpc(self, llr, max_ncheck0, max_iters, mask=0):
         """ft8rx_ft4_ldpc: ldpc() on LLRs of FT4 codewords; the words come back descrambled."""
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, 174)

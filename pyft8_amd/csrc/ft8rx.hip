@@ -70,6 +70,7 @@
 #include "kernels/pan.hpp"
 #include "kernels/ft4.hpp"
 #include "kernels/ft4_weak.hpp"     // after ft4.hpp: it shares the sample read, the Costas tables and the range
+#include "kernels/ft4_verify.hpp"   // after ft4.hpp and recall.hpp: it shares the sample read, the Costas tables and the device encoder
 #include "kernels/synth.hpp"
 #include "kernels/subtract.hpp"
 #include "kernels/ft4_sub.hpp"      // after subtract.hpp: it shares wave_sum2 and the int16 <-> float32 copies
@@ -355,6 +356,13 @@ struct ft8rx_handle {
         bool on = false; float weak_min = FT8RX_FT4_WEAK_MIN_DEFAULT; size_t bytes = 0;
         cpx* d_cg = nullptr; cpx* d_mix = nullptr; cpx* d_rot = nullptr;
     } ft4weak;
+    // FT4 OSD on the coherent rows (ft8rx_ft4_set_coh_osd, kernels/ft4_verify.hpp; allocated at the first FT4
+    // batch that runs the step, WS_FT4_COSD).  Per candidate slot its position in the first failure list; per attempt (two per item of
+    // OSD's list, at most 2 x max_frames << cand_shift) the gathered row, OSD's outcome, its NaN list and the score
+    struct Ft4Cosd {
+        bool on = false; float min_score = FT8RX_FT4_COH_OSD_MIN_SCORE_DEFAULT; int32_t max_hd = FT8RX_FT4_COH_OSD_MAX_HD_DEFAULT; size_t bytes = 0;
+        int32_t* d_pos = nullptr; float* d_dense = nullptr; Att* d_att = nullptr; int32_t* d_nan = nullptr; float* d_score = nullptr;
+    } ft4cosd;
     std::string err;
     bool profiling = false;
     std::vector<hipEvent_t> pev;
@@ -442,7 +450,7 @@ template <typename T> static int halloc(ft8rx_handle* h, T** p, size_t n, T** de
 // step succeeded.  Otherwise it releases what the attempt allocated, takes it off the owner lists and nulls the members again: the
 // handle is as it was before the call, and the next call attempts the whole group again.  Launch sites are reached only behind a
 // ready group, so none sees a null member.
-enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH, WS_FT4_REPORT, WS_FT4_WEAK };
+enum WsGroup { WS_STAGING, WS_STAGING2, WS_STAGING_F32, WS_STAGING2_F32, WS_MASK, WS_RECALL, WS_REPORTS, WS_PACKED, WS_SUB, WS_SUBD, WS_ONES, WS_DDC, WS_BLANK, WS_BLANK_IN, WS_PAN, WS_FT4, WS_FT4_SUB, WS_FT4_COH, WS_FT4_REPORT, WS_FT4_WEAK, WS_FT4_COSD };
 struct FirstUse {
     ft8rx_handle* h; WsGroup g; size_t nd, nh; int rc = 0;
     std::vector<void**> members;
@@ -3665,6 +3673,20 @@ static int ft4weak_workspaces(ft8rx_handle* h) {
     w.bytes = rc ? 0 : bytes;
     return rc;
 }
+// Everything OSD on the coherent rows owns, at the first FT4 batch that runs with ft8rx_ft4_set_coh_osd and the coherent step on, all
+// or nothing
+static int ft4cosd_workspaces(ft8rx_handle* h) {
+    if (ws_ready(h, WS_FT4_COSD)) return 0;
+    ft8rx_handle::Ft4Cosd& w = h->ft4cosd;
+    const size_t S = (size_t)h->max_frames << cand_shift(h->cfg);
+    FirstUse F(h, WS_FT4_COSD);
+    size_t bytes = 0;
+    auto dev = [&](auto** p, size_t n) { F.dev(p, n); bytes += n * sizeof(**p); };
+    dev(&w.d_pos, S); dev(&w.d_dense, 2 * S * 174); dev(&w.d_att, 2 * S); dev(&w.d_nan, 2 * S + 1); dev(&w.d_score, 2 * S);
+    const int rc = F.done();
+    w.bytes = rc ? 0 : bytes;
+    return rc;
+}
 static int ft4_refuse(ft8rx_handle* h, const char* who) {
     const int c = optins::conflict(active_optins(h), optins::FT4_ROW);
     if (c < 0) return 0;
@@ -3726,6 +3748,8 @@ static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* aud
     if (coh) if (const int rc = ft4coh_workspaces(h)) return rc;
     const bool weak = h->ft4weak.on;
     if (weak) if (const int rc = ft4weak_workspaces(h)) return rc;
+    const bool cosd = coh && h->ft4cosd.on;
+    if (cosd) if (const int rc = ft4cosd_workspaces(h)) return rc;
     ft8rx_handle::Ft4& w = h->ft4;
     const int slot = h->slot_enq;
     ResultSlot& sl = h->slots[slot];
@@ -3768,6 +3792,7 @@ static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* aud
     int n_osd = w.h_count[0];
     if (n_osd < 0 || n_osd > n) { set_err(h, "%s: the OSD list holds %d of %d slots", who, n_osd, n); return -2; }
     const int32_t* osd_items = w.d_items;
+    const int n_coh = coh ? n_osd : 0;                                      // the rows k_ft4_coh fills, indexed by the first list
     if (coh && n_osd > 0) {
         // the coherent step on the failure list: run-of-2 and run-of-4 LLRs, the same BP on both rows in one launch (run length 2
         // wins), and what neither decodes goes on to OSD in list order -- a second read-back, of the shorter list's length
@@ -3790,6 +3815,20 @@ static int ft4_launch_batch(ft8rx_handle* h, const char* who, const int16_t* aud
         HIPCHK(h, hipMemsetAsync(w.d_nan, 0, sizeof(int32_t), s));
         ft4_launch_osd(h, w.d_dense, n_osd, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), w.osd_max_hd, mt, w.d_attO, w.d_nan, s);
         k_ft4_after_osd<<<(n_osd + 255) / 256, 256, 0, s>>>(sl.rec, sh, w.d_attO, osd_items, n_osd, sl.ev, sl.evcount);
+    }
+    if (cosd && n_osd > 0) {
+        // section 19.11: OSD once more, on the run-of-2 and then the run-of-4 rows of every item of its list (on all of them, not only the
+        // exhausted ones: no third read-back), under the wide gate; the score of each returned word; then what a candidate left
+        // EXHAUSTED may take
+        STAGE("ft4_cosd");
+        const ft8rx_handle::Ft4Cosd& v = h->ft4cosd;
+        const ft8rx_handle::Ft4Coh& k = h->ft4coh;
+        k_ft4_cosd_pos<<<(n_coh + 255) / 256, 256, 0, s>>>(w.d_items, n_coh, v.d_pos);
+        k_ft4_cosd_gather<<<2 * n_osd, 64, 0, s>>>(k.d_llr, n_coh, osd_items, n_osd, v.d_pos, v.d_dense);
+        HIPCHK(h, hipMemsetAsync(v.d_nan, 0, sizeof(int32_t), s));
+        ft4_launch_osd(h, v.d_dense, 2 * n_osd, h->d_trials, h->n_trials, osd_nflip(c.osd_single, c.osd_triple), v.max_hd, mt, v.d_att, v.d_nan, s);
+        k_ft4_verify<<<2 * n_osd, FT4_DEMOD_NT, 0, s>>>(d_audio, w.d_trip, w.d_tweak, osd_items, v.d_pos, k.d_q, v.d_att, sl.rec, n_osd, v.d_score, nullptr);
+        k_ft4_after_cosd<<<(n_osd + 255) / 256, 256, 0, s>>>(sl.rec, sh, v.d_att, v.d_score, osd_items, n_osd, v.min_score, sl.ev, sl.evcount);
     }
     if (prof) hipEventRecord(h->pev[h->pnames.size()], s);
 #undef STAGE
@@ -3877,6 +3916,22 @@ int ft8rx_ft4_weak_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on,
     if (workspace_bytes) *workspace_bytes = ws_ready(h, WS_FT4_WEAK) ? (uint64_t)h->ft4weak.bytes : 0;
     if (on) *on = h->ft4weak.on ? 1 : 0;
     if (weak_min) *weak_min = h->ft4weak.weak_min;
+    return 0;
+}
+// ---- OSD on the coherent rows (kernels/ft4_verify.hpp)
+int ft8rx_ft4_set_coh_osd(ft8rx_handle* h, int32_t on, float min_score, int32_t max_hd) {
+    if (!h) return -1;
+    h->ft4cosd.on = on != 0;
+    h->ft4cosd.min_score = (min_score > 0.0f && min_score < INFINITY) ? min_score : FT8RX_FT4_COH_OSD_MIN_SCORE_DEFAULT;
+    h->ft4cosd.max_hd = max_hd <= 0 ? FT8RX_FT4_COH_OSD_MAX_HD_DEFAULT : max_hd > 174 ? 174 : max_hd;
+    return 0;
+}
+int ft8rx_ft4_coh_osd_info(ft8rx_handle* h, uint64_t* workspace_bytes, int32_t* on, float* min_score, int32_t* max_hd) {
+    if (!h) return -1;
+    if (workspace_bytes) *workspace_bytes = ws_ready(h, WS_FT4_COSD) ? (uint64_t)h->ft4cosd.bytes : 0;
+    if (on) *on = h->ft4cosd.on ? 1 : 0;
+    if (min_score) *min_score = h->ft4cosd.min_score;
+    if (max_hd) *max_hd = h->ft4cosd.max_hd;
     return 0;
 }
 
@@ -3991,6 +4046,41 @@ int ft8rx_ft4_coherent(ft8rx_handle* h, const int16_t* audio, int B, int n, cons
     HIPCHK(h, hipMemcpy(metrics, d_met, sizeof(float) * (size_t)n * FT4_COH_NQ, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(llr2, d_l2, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(llr4, d_l4, sizeof(float) * (size_t)n * 174, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ft8rx_ft4_verify(ft8rx_handle* h, const int16_t* audio, int B, int n, const int32_t* frame, const int32_t* f0_idx, const int32_t* h0_idx,
+                     const int32_t* ttweak, const int32_t* ftweak, const int32_t* q, const uint64_t* msg_lo, const uint64_t* msg_hi, float* score,
+                     uint8_t* tones) {
+    if (!ft4_frames_ok(h, "ft8rx_ft4_verify", audio, B) || n < 1 || !frame || !f0_idx || !h0_idx || !ttweak || !ftweak || !q || !msg_lo || !msg_hi || !score) return -1;
+    for (int i = 0; i < n; i++)
+        if (frame[i] < 0 || frame[i] >= B || f0_idx[i] < 0 || f0_idx[i] >= FT8RX_FT4_COLS - 6 || h0_idx[i] < -1024 || h0_idx[i] >= 1024 ||
+            ttweak[i] < -(FT4_N_DT / 2) || ttweak[i] > FT4_N_DT / 2 || ftweak[i] < -(FT4_N_DF / 2) || ftweak[i] > FT4_N_DF / 2 || q[i] < -4 || q[i] > 4) {
+            set_err(h, "ft8rx_ft4_verify: candidate %d (frame %d, f0 %d, h0 %d, tt %d, ft %d, q %d) is out of range", i, frame[i], f0_idx[i], h0_idx[i], ttweak[i], ftweak[i], q[i]);
+            return -1; }
+    ENTER(h);
+    if (const int rc = ft4_workspaces(h)) return rc;
+    ft8rx_handle::Ft4& w = h->ft4;
+    const std::vector<int32_t> trip = pack_triples(n, frame, f0_idx, h0_idx);
+    std::vector<int32_t> tw((size_t)n * 2);
+    std::vector<Att> att(n);
+    for (int i = 0; i < n; i++) {
+        tw[2 * i] = ttweak[i]; tw[2 * i + 1] = ftweak[i];
+        att[i] = Att{}; att[i].lo = msg_lo[i]; att[i].hi = msg_hi[i] & 0x1FFFull; att[i].ok = 1;
+    }
+    Scratch S{h};
+    int32_t* d_trip = S.put(trip.data(), trip.size()); NEED(d_trip);
+    int32_t* d_tw = S.put(tw.data(), tw.size()); NEED(d_tw);
+    int32_t* d_q = S.put(q, (size_t)n); NEED(d_q);
+    Att* d_att = S.put(att.data(), att.size()); NEED(d_att);
+    float* d_sc = S.get<float>(n); NEED(d_sc);
+    uint8_t* d_tn = nullptr;
+    if (tones) { d_tn = S.get<uint8_t>((size_t)n * FT4_NSYM); NEED(d_tn); }
+    HIPCHK(h, hipMemcpy(w.d_audio, audio, sizeof(int16_t) * (size_t)B * FT8RX_FT4_NSAMP, hipMemcpyHostToDevice));
+    k_ft4_verify<<<n, FT4_DEMOD_NT, 0, h->stream>>>(w.d_audio, d_trip, d_tw, nullptr, nullptr, d_q, d_att, nullptr, n, d_sc, d_tn);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(score, d_sc, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (tones) HIPCHK(h, hipMemcpy(tones, d_tn, (size_t)n * FT4_NSYM, hipMemcpyDeviceToHost));
     return 0;
 }
 int ft8rx_ft4_ldpc(ft8rx_handle* h, const float* llr, int n, int max_ncheck0, int max_iters, int32_t mask, int32_t* ok, uint64_t* msg_lo,

@@ -35,6 +35,13 @@ jointly.  Input: a candidate (f0, h0) with the fine sync's winner (tt, ft); fq =
            per bit of the run LLR = max{a : bit = 1} - max{a : bit = 0}
   scaling  as demod: 2.83 / std over the 174 values, all zero where std = 0, otherwise an exact 0 becomes +0.001
 L = 1 is demod's LLRs again (tests/test_ft4_coherent.py holds it to 1e-12).
+and, opt-in, of the whole-message score behind OSD on those rows (k_ft4_verify, tests/test_gpu_ft4_coh_osd.py; verify_score below;
+DESIGN.md section 19.11).  Input: a candidate with its winner (tt, ft), its residual q and a 77-bit word:
+  score    C = complex above, row s turned by e^{-2 pi i ((q s) mod 32) / 32}; T = tones105(word); the runs of four symbols from symbol 1
+           on, R_k = {1 + 4 k .. min(4 + 4 k, 103)}, k = 0 .. 25 (the last one has three symbols; symbols 0 and 104 never enter):
+           A = sum_k |sum_{s in R_k} C[s][T[s]]|,  N = (1 / 412) sum_{s = 1 .. 103} sum_t |C[s][t]|^2,  score = A / sqrt(N), 0 where
+           N = 0: a clean signal scores near 206 (103 sqrt(4)), noise against a random word near 26 sqrt(pi) = 46.  The kernel adds
+           its float32 amplitudes in float64, every sum in index order
 The twin also defines the subtraction passes (csrc/kernels/ft4_sub.hpp, tests/test_gpu_ft4_sub.py; stated in full where sub_model stands, below):
   model    the complex form of tones_to_wave; bins: 41 bins (+-3.97 Hz) of the 60480-point transform of x conj(model); refine: the
            bins' energy at 13 starts 4 samples apart, the first maximum; subtract: x -= 2 Re(a model), a = the bins' inverse transform
@@ -465,6 +472,30 @@ def coherent_llrs(x, f0, h0, tt, ft):
     q = COH_Q[int(np.argmax(m))]
     C = C * np.exp(-2j * np.pi * ((q * np.arange(NSYM)) % 32) / 32.0)[:, None]
     return dict(q=q, metrics=m, llr1=run_llrs(C, 1), llr2=run_llrs(C, 2), llr4=run_llrs(C, 4))
+
+
+# ----------------------------------------------------------------------------- the twin: the whole-message score (k_ft4_verify, section 19.11)
+COH_OSD_MIN_SCORE_DEFAULT = 77.1       # FT8RX_FT4_COH_OSD_MIN_SCORE_DEFAULT: measured on the noise words within max_hd
+COH_OSD_MIN_SCORE_MSG_TYPES = 81.0     # ... and on those at msg_types = all: what Receiver takes then (the rule of OSD_MAX_HD_MSG_TYPES)
+COH_OSD_MAX_HD_DEFAULT = 40            # FT8RX_FT4_COH_OSD_MAX_HD_DEFAULT: keeps 99 % of the true words measured (hd 17 .. 39)
+VERIFY_RUNS = tuple(range(1, NSYM - 1, 4))      # first symbols of the 26 runs of four
+
+
+def verify_terms(C, tones):
+    """(A, N) of the score's definition on complex amplitudes C [105][4] that are already turned by q."""
+    C, T = np.asarray(C), np.asarray(tones, np.int64)
+    own = C[np.arange(NSYM), T]
+    A = sum(abs(own[s0:min(s0 + 4, NSYM - 1)].sum()) for s0 in VERIFY_RUNS)
+    N = float((np.abs(C[1:NSYM - 1]) ** 2).sum()) / 412.0
+    return float(A), N
+
+
+def verify_score(x, f0, h0, tt, ft, q, word77):
+    """The whole-message coherent score of the 77-bit word `word77` on candidate (f0, h0) at the fine sync's winner (tt, ft) and the
+    residual frequency q of coherent_llrs: A / sqrt(N) of the module's definition, 0 where N = 0."""
+    C = complex_amplitudes(x, f0, h0, tt, ft) * np.exp(-2j * np.pi * ((int(q) * np.arange(NSYM)) % 32) / 32.0)[:, None]
+    A, N = verify_terms(C, tones105(word77))
+    return A / np.sqrt(N) if N > 0 else 0.0
 
 
 def early_ok(h0_idx, ttweak, n_have):

@@ -752,6 +752,16 @@ class Receiver:
             raise _lib.Ft8rxError(f"ft4_weak must be True or False, got {self.ft4_weak!r}")
         self.ft4_weak = bool(self.ft4_weak)
         self.ft4_weak_min = extension_knobs.pop("ft4_weak_min", None)
+        # ft4_coh_osd (section 19.11): behind the coherent step and OSD, OSD runs once more on the run-of-2 and run-of-4 rows, and a
+        # word it returns is taken where its whole-message score reaches ft4_coh_osd_min_score (None = the library's default).  It
+        # acts on the coherent rows, so it needs ft4_coherent=True.  Applied in _ft4_set.
+        self.ft4_coh_osd = extension_knobs.pop("ft4_coh_osd", False)
+        if not isinstance(self.ft4_coh_osd, (bool, np.bool_)):
+            raise _lib.Ft8rxError(f"ft4_coh_osd must be True or False, got {self.ft4_coh_osd!r}")
+        self.ft4_coh_osd = bool(self.ft4_coh_osd)
+        self.ft4_coh_osd_min_score = extension_knobs.pop("ft4_coh_osd_min_score", None)
+        if self.ft4_coh_osd and not self.ft4_coherent:
+            raise _lib.Ft8rxError("ft4_coh_osd=True needs ft4_coherent=True: it runs OSD on the coherent step's LLRs")
         # ft4_reports (section 19.9): every FT4 message is measured against its own model on the audio its pass decoded (SNR,
         # frequency, start time) and its dict gains "report".  An FT4 knob of the receiver, not a row of the opt-in table.
         self.ft4_reports = extension_knobs.pop("ft4_reports", False)
@@ -1296,6 +1306,8 @@ class Receiver:
         their decode_notes, and the records returned are the last pass's.  The receiver's ft4_coherent=True (section 19.8): what BP
         leaves undecoded is decoded again on LLRs over runs of two and four symbols, and every dict says "nsym": 1, 2 or 4.  The
         receiver's ft4_weak=True (section 19.10): the candidates come from the coherent search on the 2.6-Hz grid; the dicts are unchanged.  The
+        receiver's ft4_coh_osd=True (section 19.11, with ft4_coherent): OSD also runs on the coherent rows, gated by a whole-message score;
+        such a message's "nsym" says 2 or 4.  The
         receiver's ft4_reports=True (section 19.9): every dict carries "report": {"snr", "fHz", "tsec"} measured on the audio its pass
         decoded (None where it could not be measured).  Refused, by name: a-priori calls, recall, weak, reports,
         the packed output, the per-call passes > 1 and float frames."""
@@ -1362,6 +1374,10 @@ class Receiver:
             h.ft4_set_coherent(True)
         if self.ft4_weak:                                            # likewise: never called without the keyword
             h.ft4_set_weak(True, self.ft4_weak_min)
+        if self.ft4_coh_osd:                                         # likewise
+            # the score gate: the one given, else the library's default -- with msg_types set, the stricter one measured for them
+            ms = self.ft4_coh_osd_min_score if self.ft4_coh_osd_min_score is not None or not self.cfg.msg_types else _ft4.COH_OSD_MIN_SCORE_MSG_TYPES
+            h.ft4_set_coh_osd(True, ms)
         f0 = _ft4.freq_range_to_f0(self._ft4_freq_range) if self._ft4_freq_range is not None else (0, 0)
         h0 = _ft4.time_range_to_h0(self._ft4_time_range) if self._ft4_time_range is not None else (0, 0)
         if f0 == (0, 0) and h0 != (0, 0):
@@ -1592,7 +1608,7 @@ def decode_frames(audio_i16, on_message=None, passes=1, research="full", recall=
 
 def decode_frames_ft4(audio_i16, on_message=None, **receiver_kwargs):
     """decode_frames_ft4(audio_i16[B, 90000], **receiver_kwargs) -> list[list[message dict]]: Receiver.decode_frames_ft4 on a receiver
-    of its own (FT4); ft4_passes=, ft4_coherent=, ft4_weak=, ft4_reports= and the other FT4 knobs go to Receiver with the keyword
+    of its own (FT4); ft4_passes=, ft4_coherent=, ft4_weak=, ft4_coh_osd=, ft4_reports= and the other FT4 knobs go to Receiver with the keyword
     arguments."""
     audio = np.ascontiguousarray(audio_i16, np.int16)
     rx = Receiver("", on_message, max_frames=max(1, audio.shape[0] if audio.ndim == 2 else 1), **receiver_kwargs)

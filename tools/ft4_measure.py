@@ -1,6 +1,7 @@
 """FT4 measurements on an MI355X -> profiles/ft4_measure.json; profiles/ft4_notes.md states what was seen.
 
     python tools/ft4_measure.py [--out profiles/ft4_measure.json] [--prob] [--noise] [--throughput] [--twin N] [--passes] [--coherent] [--weak]
+                                [--coh-osd]
     python tools/ft4_measure.py --reports [--reports-twin] [--out profiles/ft4_report_measure.json]
 
 --prob        decode probability against SNR: -20 .. -8 dB in 1-dB steps, 200 signals per step, 10 signals per frame (carriers >= 150 Hz
@@ -21,6 +22,16 @@
               gate 24 / all; decode probability at -18 .. -12 dB (the recipe of --prob) in four columns -- off, weak, coherent, weak +
               coherent -- with the truths that became candidates; frames/s at B = 256 with 20 signals per frame (device-resident),
               off / on alternating, twice each, and the stage times
+--coh-osd     OSD on the coherent rows behind the whole-message score (section 19.11), in one session.  Collection, both gates open (max_hd 174,
+              every score), weak search and coherent step on: (score, hd, run length, true or false) of every word the step returns on the
+              candidates the chain leaves EXHAUSTED -- through the stage entries ft4_coherent, ft4_osd and ft4_verify, which make the
+              chain's launches, so that the run-of-4 word is seen where a run-of-2 word would take precedence -- on the 2048 noise frames
+              (msg_types 0 and all) and on the 200-signal sets at -18 .. -14 dB.  The two defaults from it: max_hd = the smallest multiple
+              of 4 that keeps at least 99 % of the true words that score above the noise maximum; min_score = S_max + (S_max - S_90) of the
+              noise words within that max_hd, rounded up to one decimal (for msg_types all from its own noise words).  Then, with those
+              two: false decodes on the noise frames with weak on and off at msg_types 0 and all; the decode table at -18 .. -12 dB in the
+              columns coherent, coherent + cosd, weak + coherent, weak + coherent + cosd with the decodes by run length and method; frames/s
+              at B = 256 with 20 signals per frame, plain FT4 / coherent / coherent + cosd alternating, twice each, and the stage times
 --reports     measured reports (section 19.9) -> profiles/ft4_report_measure.json: the accuracy recipe make_frame(i, n_signals=8, snr_range=
               (-14, 15), min_sep_hz=250) against truth, frames 16 .. 79 through Receiver(ft4_reports=True) with the default fields of the
               same messages beside it; the report stage timed with HIP events (ft8rx_set_profiling) at B = 256 with 20 signals per frame;
@@ -328,6 +339,159 @@ def measure_weak(h, noise_frames_n=2048, chunk=256, per_step=200, B=256, warmup=
     return out
 
 
+def cosd_words(h, a, res, mask, truth_words=None):
+    """Every word the step returns on the candidates the batch `res` of frames `a` left EXHAUSTED, gates open: rows of (frame, score, hd,
+    run length, true) -- true = the word is among the frame's planted ones (never on noise)"""
+    from pyft8_amd import _lib
+    rec, cnt = res[0], res[1]
+    fr, idx = [], []
+    for f in range(len(cnt)):
+        k = np.nonzero(rec[f, :cnt[f]]["status"] == _lib.ST_EXHAUSTED)[0]
+        fr += [f] * len(k); idx += list(k)
+    if not fr:
+        return []
+    r = rec[fr, idx]
+    pos = [r[k].astype(np.int32) for k in ("f0_idx", "h0_idx", "ttweak", "ftweak")]
+    c = h.ft4_coherent(a, fr, *pos)
+    rows = []
+    for L, key in ((2, "llr2"), (4, "llr4")):
+        ok, lo, hi, _, hd = h.ft4_osd(c[key], h.cfg.osd_single, h.cfg.osd_double, h.cfg.osd_triple, 174, mask)
+        words = [(int(b) << 64) | int(x) if o else 0 for o, x, b in zip(ok, lo, hi)]
+        sc = h.ft4_verify(a, fr, *pos, c["q"], words)
+        rows += [(fr[i], float(sc[i]), int(hd[i]), L, bool(truth_words is not None and words[i] in truth_words[fr[i]])) for i in range(len(fr)) if ok[i]]
+    return rows
+
+
+def cosd_defaults(true_rows, noise_rows):
+    """(max_hd, min_score, figures) by the rule of --coh-osd from rows of (frame, score, hd, run length, true)"""
+    ns = np.array([r[1] for r in noise_rows]); nh = np.array([r[2] for r in noise_rows])
+    ts = np.array([r[1] for r in true_rows]); th = np.array([r[2] for r in true_rows])
+    top = float(ns.max())
+    good = th[ts > top]
+    max_hd = next(m for m in range(4, 180, 4) if (good <= m).sum() >= 0.99 * len(good))
+    inside = np.sort(ns[nh <= max_hd])
+    s_max, s_90 = float(inside[-1]), float(np.percentile(inside, 90))
+    min_score = float(np.ceil((s_max + (s_max - s_90)) * 10.0 - 1e-9) / 10.0)
+    return max_hd, min_score, {"noise_words": len(ns), "noise_max": top, "true_words": len(ts), "true_above_noise_max": len(good),
+                               "true_above_hd": [int(good.min()), int(good.max())] if len(good) else None, "noise_words_within_max_hd": len(inside),
+                               "s_max": s_max, "s_90": s_90}
+
+
+def measure_coh_osd(h, noise_frames_n=2048, chunk=256, per_step=200, B=256, warmup=3, steps=20):
+    import torch
+    from pyft8_amd import _lib
+    out = {"collection": {"frames": noise_frames_n, "max_hd": 174}, "noise": {"frames": noise_frames_n},
+           "probability": {"snr_db": list(range(-18, -11)), "signals_per_step": per_step}, "throughput": {"B": B, "signals_per_frame": 20}}
+    live = lambda res: np.concatenate([res[0][f, :res[1][f]] for f in range(len(res[1]))])
+    masks = (("0", 0, ft4.OSD_MAX_HD_DEFAULT), ("all", _lib.MT_ALL, ft4.OSD_MAX_HD_MSG_TYPES))
+
+    def setting(weak, coh, cosd, min_score=None, max_hd=None):
+        h.ft4_set_weak(weak); h.ft4_set_coherent(coh); h.ft4_set_coh_osd(cosd, min_score, max_hd)
+    # ---- collection: noise at both masks, then the signal sets -- with the weak search (the recipe) and, pooled with it, with the
+    # default search: its candidates are other ones, and the step runs behind either
+    noise = {"0": [], "all": []}
+    weak_only = {"0": [], "all": []}
+    for first in range(0, noise_frames_n, chunk):
+        a = noise_frames(chunk, first)
+        for m, mask, gate in masks:
+            h.set_msg_types(mask); h.ft4_set(osd_max_hd=gate)
+            for weak in (True, False):
+                setting(weak, True, False)
+                rows = [(first + r[0],) + r[1:] for r in cosd_words(h, a, h.ft4_decode(a), mask)]
+                noise[m] += rows
+                if weak:
+                    weak_only[m] += rows
+        print(f"coh-osd collection, noise frames {first + chunk}: {len(noise['0'])} / {len(noise['all'])} words ({len(weak_only['0'])} / {len(weak_only['all'])} behind the weak search)", flush=True)
+    h.set_msg_types(0); h.ft4_set()
+    sig, sig_weak = {}, []
+    for snr in range(-18, -13):
+        frames = [prob_frame(snr, k, float(snr)) for k in range(per_step // 10)]
+        a = np.stack([f[0] for f in frames])
+        sig[str(snr)] = []
+        for weak in (True, False):
+            setting(weak, True, False)
+            rows = cosd_words(h, a, h.ft4_decode(a), 0, [{t["word"] for t in truth} for _, truth in frames])
+            sig[str(snr)] += rows
+            if weak:
+                sig_weak += rows
+        tr = [r for r in sig[str(snr)] if r[4]]
+        print(f"coh-osd collection {snr:+d} dB: {len(sig[str(snr)])} words, {len(tr)} true (scores {min((r[1] for r in tr), default=0):.1f} .. {max((r[1] for r in tr), default=0):.1f})", flush=True)
+    true_rows = [r for rows in sig.values() for r in rows if r[4]]
+    false_rows = [r for rows in sig.values() for r in rows if not r[4]]
+    recipe = {m: cosd_defaults([r for r in sig_weak if r[4]], weak_only[m]) for m in weak_only}      # the weak search alone
+    out["collection"]["weak_search_alone"] = {m: {"max_hd": v[0], "min_score": v[1], **v[2]} for m, v in recipe.items()}
+    max_hd, min_score, fig = cosd_defaults(true_rows, noise["0"])
+    _, min_score_all, fig_all = cosd_defaults(true_rows, noise["all"])
+    q = lambda v: [round(float(x), 2) for x in np.percentile(v, [0, 10, 50, 90, 99, 100])] if len(v) else None
+    out["collection"].update(
+        max_hd_default=max_hd, min_score_default=min_score, min_score_msg_types_all=min_score_all, msg_types_0=fig, msg_types_all=fig_all,
+        noise_score_percentiles_0_10_50_90_99_100={m: q([r[1] for r in noise[m]]) for m in noise},
+        noise_hd_percentiles={m: q([r[2] for r in noise[m]]) for m in noise},
+        noise_top={m: sorted(((round(r[1], 2), r[2], r[3]) for r in noise[m]), reverse=True)[:12] for m in noise},
+        true_by_snr={k: {"words": len([r for r in v if r[4]]), "score": q([r[1] for r in v if r[4]]), "hd": q([r[2] for r in v if r[4]]),
+                         "above_min_score_within_max_hd": len([r for r in v if r[4] and r[1] >= min_score and r[2] <= max_hd])} for k, v in sig.items()},
+        wrong_words_on_signal_frames={"words": len(false_rows), "score": q([r[1] for r in false_rows]),
+                                      "above_min_score_within_max_hd": len([r for r in false_rows if r[1] >= min_score and r[2] <= max_hd])})
+    print("coh-osd defaults", max_hd, min_score, min_score_all, fig, fig_all, flush=True)
+    # ---- false decodes on the noise frames with the two defaults
+    nz = {f"{w}_{m}": {"false_decodes": 0, "candidates": 0, "texts": []} for w in ("weak_off", "weak_on") for m in ("0", "all")}
+    for first in range(0, noise_frames_n, chunk):
+        a = noise_frames(chunk, first)
+        for m, mask, gate in masks:
+            h.set_msg_types(mask); h.ft4_set(osd_max_hd=gate)
+            for w, weak in (("weak_off", False), ("weak_on", True)):
+                setting(weak, True, True, min_score_all if mask else min_score, max_hd)
+                res = h.ft4_decode(a)
+                dec = live(res); dec = dec[dec["status"] == 1]
+                e = nz[f"{w}_{m}"]
+                e["false_decodes"] += len(dec); e["candidates"] += int(res[1].sum())
+                if len(dec):
+                    e["texts"] += [f"frame {first + f}: {t}" for f, s in enumerate(texts_of(h, res, mask)) for t in s]
+        print(f"coh-osd noise frames {first + chunk}: " + ", ".join(f"{k} {v['false_decodes']}/{v['candidates']}" for k, v in nz.items()), flush=True)
+    h.set_msg_types(0); h.ft4_set()
+    out["noise"].update(nz); out["noise"].update(min_score=min_score, min_score_all=min_score_all, max_hd=max_hd)
+    # ---- the decode table
+    for name, weak, cosd in (("coherent", False, False), ("coherent_cosd", False, True), ("weak_coherent", True, False), ("weak_coherent_cosd", True, True)):
+        setting(weak, True, cosd, min_score, max_hd)
+        r = {"decoded": [], "false": [], "bp_1": [], "bp_2": [], "bp_4": [], "osd_1": [], "osd_2": [], "osd_4": []}
+        for snr in out["probability"]["snr_db"]:
+            frames = [prob_frame(snr, k, float(snr)) for k in range(per_step // 10)]
+            res = h.ft4_decode(np.stack([f[0] for f in frames]))
+            got = texts_of(h, res)
+            r["decoded"].append(sum(t["msg"] in got[f] for f, (_, truth) in enumerate(frames) for t in truth))
+            r["false"].append(sum(len(got[f] - {t["msg"] for t in truth}) for f, (_, truth) in enumerate(frames)))
+            dec = live(res); dec = dec[dec["status"] == 1]
+            for ip, meth in ((4, "bp"), (5, "osd")):
+                for L in (1, 2, 4):
+                    r[f"{meth}_{L}"].append(int(((dec["ipass"] == ip) & (dec["nsync"] == (0 if L == 1 else L))).sum()))
+            print(f"coh-osd {name} prob {snr:+d} dB: {r['decoded'][-1]}/{per_step}, false {r['false'][-1]}", flush=True)
+        r["probability"] = [d / per_step for d in r["decoded"]]
+        r["half_point_db"] = half_point(out["probability"]["snr_db"], r["probability"])
+        out["probability"][name] = r
+    # ---- throughput, device-resident frames
+    a = np.stack([throughput_frame(k) for k in range(B)])
+    d = torch.from_numpy(a).to("cuda:0"); torch.cuda.synchronize()
+    for name, coh, cosd in (("plain", False, False), ("coherent", True, False), ("coherent_cosd", True, True),
+                            ("plain_again", False, False), ("coherent_again", True, False), ("coherent_cosd_again", True, True)):
+        setting(False, coh, cosd, min_score, max_hd)
+        for _ in range(warmup):
+            h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B)
+        tt = []
+        for _ in range(steps):
+            t0 = time.perf_counter(); h.ft4_enqueue(d.data_ptr(), B); res = h.fetch(B); tt.append(time.perf_counter() - t0)
+        rec = live(res); dec = rec[rec["status"] == 1]
+        h.set_profiling(True)
+        h.ft4_enqueue(d.data_ptr(), B); h.fetch(B); h.sync()
+        stage = {k: round(float(v), 4) for k, v in h.stage_times().items()}
+        h.set_profiling(False)
+        out["throughput"][name] = {"device_frames_per_s": B / float(np.median(tt)), "device_step_ms": [round(1e3 * x, 3) for x in tt], "stage_ms": stage,
+                                   "candidates": len(rec), "decoded": len(dec), "cosd_decodes": int(((dec["ipass"] == 5) & (dec["nsync"] != 0)).sum())}
+        print("coh-osd throughput", name, out["throughput"][name]["device_frames_per_s"], stage, flush=True)
+    out["throughput"]["workspace_bytes"] = h.ft4_coh_osd_info()["workspace_bytes"]
+    setting(False, False, False)
+    return out
+
+
 CROWDED_KW = dict(n_signals=16, snr_range=(-12, 10), freq_range=(300, 1200), t0_range=(0.2, 1.2), min_sep_hz=25)
 SUB_GATES = [None, 32, 24, 16]
 
@@ -503,7 +667,7 @@ if __name__ == "__main__":
     ap.add_argument("--prob", action="store_true"); ap.add_argument("--noise", action="store_true"); ap.add_argument("--throughput", action="store_true")
     ap.add_argument("--twin", type=int, default=0); ap.add_argument("--passes", action="store_true")
     ap.add_argument("--noise-frames", type=int, default=2048); ap.add_argument("--coherent", action="store_true")
-    ap.add_argument("--weak", action="store_true")
+    ap.add_argument("--weak", action="store_true"); ap.add_argument("--coh-osd", action="store_true")
     ap.add_argument("--reports", action="store_true"); ap.add_argument("--reports-twin", action="store_true")
     args = ap.parse_args()
     if (args.reports or args.reports_twin) and args.out == ap.get_default("out"):
@@ -511,7 +675,7 @@ if __name__ == "__main__":
     res = json.load(open(args.out)) if os.path.exists(args.out) else {}
     if args.twin:
         res["twin_probability"] = measure_twin(args.twin)
-    if args.prob or args.noise or args.throughput or args.coherent or args.weak:
+    if args.prob or args.noise or args.throughput or args.coherent or args.weak or args.coh_osd:
         import torch  # noqa: F401 -- before libft8rx.so loads (_lib.lib)
         from pyft8_amd import _lib
         h = _lib.Handle(max_frames=256)
@@ -525,6 +689,8 @@ if __name__ == "__main__":
             res["coherent"] = measure_coherent(h, args.noise_frames)
         if args.weak:
             res["weak"] = measure_weak(h, args.noise_frames)
+        if args.coh_osd:
+            res["coh_osd"] = measure_coh_osd(h, args.noise_frames)
         h.close()
     if args.passes:
         import torch  # noqa: F401,F811 -- before libft8rx.so loads (_lib.lib)
